@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- input GB/s scanned by the PFAC match path on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c5|c6] [--size-mib 1024]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c5|c6] [--size-mib 1024] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; with --dump-outputs DIR it also writes
+what the last timed step computed (dump_outputs).  Everything else below -- the checks against the reference digests,
+the CPU baseline, the PMC passes and the side measurements of the line -- runs only with --full.
 
 One "step" = one PFAC_matchFromDevice() pass over the rank's slice of the synthetic stream, input
 and result buffers resident in HBM, transition tables already uploaded.  The stream is sharded as
@@ -11,7 +15,7 @@ there is no data-path collective, RCCL only gathers the per-rank (match count, c
 Process layout.  Started plainly (`python bench.py --gpus N`), this process is an ORCHESTRATOR that
 never touches the GPU: it builds what is missing, starts N fresh rank processes (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT in their environment -- what torch.distributed.run
-would set), relays rank 0's JSON line and exits with the worst child's code.  At N = 1 it also runs the
+would set), relays rank 0's JSON line and exits with the worst child's code.  At N = 1 with --full it also runs the
 CPU baseline in its own process (own OpenMP environment, GPU idle) and the two rocprofv3 PMC passes
 that measure the HBM traffic of the dominant kernel.  Started by `python -m torch.distributed.run`
 (RANK is set), the process is a rank.
@@ -20,7 +24,8 @@ Rank 0 prints ONE JSON line (the driver contract) that also carries
   "roofline":      algorithmic HBM bytes (5 B per input byte: 1 read + 4 written) / kernel time,
                    kernel time measured with HIP events on the launch stream inside the timed region;
                    "traffic" from the PMC passes of this run (or of the committed profile, see
-                   "traffic_source")
+                   "traffic_source"), --full only
+and, with --full:
   "cpu_baseline":  the reference's own OpenMP matcher (oracle/_ref, compiled from the unmodified
                    reference sources) timed on this host's cores on a bounded sample, N = 1 only
   "other_configs": the other single-GPU BASELINE configurations (c2 texture on/off, c5 dense/hashed), c6 = the c5 stream over
@@ -29,7 +34,7 @@ Rank 0 prints ONE JSON line (the driver contract) that also carries
   "call_size_sweep": 1 / 4 / 16 / 64 / 256 MiB calls of the headline stream through PFACX_KERNEL_AUTO, and one cold call after
                    a second of idle GPU, N = 1 only
 
-Bit-exactness (outside the timed region): every rank compares its result with the committed digest of
+Bit-exactness (--full, outside the timed region): every rank compares its result with the committed digest of
 the REFERENCE's CPU/OMP result for its slice (tests/golden/full_digests.json: match count, position
 checksum, FNV-1a-64 of the int32 vector); at sizes without a digest, with the oracle on sampled
 windows.  At N = 1 the CPU baseline's result (the reference matcher itself) is also compared with the
@@ -64,7 +69,22 @@ OTHER_STEPS = 10                 # timed launches per entry of "other_configs"
 PMC_LAUNCHES = 4                 # launches of --worker pmc that the counter means are taken over (behind one synchronised launch)
 HOST_CALLS = 20                  # timed PFAC_matchFromHost / ...Reduce calls per buffer kind (median, best, p90)
 DIGESTS = os.path.join(ROOT, "tests", "golden", "full_digests.json")
-SCRATCH = os.path.join(ROOT, "gpurun_out", "bench")
+
+
+def scratch_dir():
+    """This run's scratch directory (pattern files, the rank-0 sparse result, the PMC passes): a fresh directory under the system's
+    temporary directory -- the checkout may be read-only -- made by the first process of the run, handed to its child processes in
+    PFAC_BENCH_SCRATCH and removed when that first process exits."""
+    d = os.environ.get("PFAC_BENCH_SCRATCH")
+    if not d:
+        import atexit
+        import shutil
+        import tempfile
+        d = tempfile.mkdtemp(prefix="pfac_bench_")
+        os.environ["PFAC_BENCH_SCRATCH"] = d
+        atexit.register(shutil.rmtree, d, True)
+    os.makedirs(d, exist_ok=True)
+    return d
 
 
 def log(*a):
@@ -87,12 +107,17 @@ def parse_args(argv=None):
     ap.add_argument("--platform", default="gpu", choices=["gpu", "cpu_omp"],
                     help="cpu_omp: PFAC_setPlatform(PFAC_PLATFORM_CPU_OMP) + PFAC_matchFromHost -- a dry run of the rank/"
                          "shard/gather logic on a machine without a GPU (never the reported metric)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the checks against the reference digests, the CPU baseline, the PMC passes, the reduce API, "
+                         "the host paths, the stream probe, the call-size sweep and the other configurations (each can be left out by the --no-* options)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
-    ap.add_argument("--spread", action="store_true", help="measure the placement spread (4 buffer pairs) even with --no-other-configs")
+    ap.add_argument("--spread", action="store_true", help="with --full: measure the placement spread (4 buffer pairs) even with --no-other-configs")
     ap.add_argument("--pmc", default="auto", choices=["auto", "off"],
-                    help="auto: measure HBM traffic of the scan kernel with two rocprofv3 --pmc passes (N = 1, orchestrated runs)")
+                    help="auto: measure HBM traffic of the scan kernel with two rocprofv3 --pmc passes (N = 1, orchestrated runs with --full)")
     ap.add_argument("--cpu-seconds", type=float, default=5.0, help="target duration of ONE CPU-baseline run (3 runs are timed)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, one GPU per rank) is the real path; gloo lets several ranks share one GPU for a dry run")
@@ -173,6 +198,48 @@ def check_against_oracle_windows(ob, pattern_file, host_in, d_out, n, n_read, pe
     return ok
 
 
+# ---------------------------------------------------------------------------- --dump-outputs
+
+DUMP_PAIRS = 4 << 20                 # (position, id) pairs written at most: 12 B each
+DUMP_WINDOWS, DUMP_WINDOW = 8, 1 << 18   # verbatim windows of the result vector: 4 B per entry
+NOT_CHECKED = "not checked (plain run: --full compares with the reference digests)"
+
+
+def dump_outputs(out_dir, run, prefix=""):
+    """--dump-outputs: the int32 result vector the last launch of `run` wrote (run.n_read entries, what the caller receives) as
+    .npy files of 60 MB at most, the same from run to run for the same arguments:
+      match_positions (float64), match_ids (float32): every non-zero entry, ascending -- or DUMP_PAIRS of them evenly spaced
+                                                      over the list if there are more;
+      result_windows (float32, windows x DUMP_WINDOW):  the vector verbatim at result_window_starts (float64: the first and the last
+                                                      window, and seeded positions in between)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(run.n_read)
+    res = run.d_out[:n] if run.gpu else run.h_out[:n]
+    if run.gpu:
+        run.torch.cuda.synchronize()
+        pos = run.torch.nonzero(res).flatten()
+        if pos.numel() > DUMP_PAIRS:
+            pos = pos[run.torch.from_numpy(np.linspace(0, pos.numel() - 1, DUMP_PAIRS).astype(np.int64)).to(pos.device)]
+        ids = res[pos].cpu().numpy()
+        pos = pos.cpu().numpy()
+    else:
+        pos = np.flatnonzero(res)
+        if pos.size > DUMP_PAIRS:
+            pos = pos[np.linspace(0, pos.size - 1, DUMP_PAIRS).astype(np.int64)]
+        ids = res[pos]
+    w = min(DUMP_WINDOW, n)
+    rng = np.random.Generator(np.random.PCG64(20240))
+    starts = np.unique(np.concatenate([[0, n - w], rng.integers(0, n - w + 1, size=DUMP_WINDOWS - 2)])).astype(np.int64)
+    if run.gpu:
+        windows = run.torch.stack([res[s:s + w] for s in starts.tolist()]).cpu().numpy()
+    else:
+        windows = np.stack([res[s:s + w] for s in starts])
+    for name, a in (("match_positions", pos.astype(np.float64)), ("match_ids", ids.astype(np.float32)),
+                    ("result_windows", windows.astype(np.float32)), ("result_window_starts", starts.astype(np.float64))):
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+    log(f"[bench] --dump-outputs: {pos.size} match pairs, {starts.size} windows of {w} -> {out_dir}")
+
+
 # ----------------------------------------------------------------------------- PMC traffic
 
 def committed_traffic(workload, kernel_substr):
@@ -220,7 +287,7 @@ def measure_traffic(argv_common, kernel_substr):
     out = {}
     env = dict(os.environ, TMPDIR="/tmp")
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
-        d = os.path.join(SCRATCH, "pmc_" + counter)
+        d = os.path.join(scratch_dir(), "pmc_" + counter)
         shutil.rmtree(d, ignore_errors=True)
         cmd = [rocprof, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "pmc", "--",
                sys.executable, os.path.abspath(__file__), "--worker", "pmc"] + argv_common
@@ -282,8 +349,7 @@ def cpu_worker(args):
     from pfac_amd import workloads as wl
     cfg = wl.make_config(args.workload)
     perf_mode = cfg.perf_mode if args.perf_mode is None else (0 if args.perf_mode == "dense" else 1)
-    os.makedirs(SCRATCH, exist_ok=True)
-    pf = wl.write_pattern_file(os.path.join(SCRATCH, f"{cfg.name}_cpu.pat"), cfg.patterns)
+    pf = wl.write_pattern_file(os.path.join(scratch_dir(), f"{cfg.name}_cpu.pat"), cfg.patterns)
     oracle = ob.Oracle(pf, dense=(perf_mode == 0), hashed=(perf_mode == 1))
     use_ref = ob.have_reference()
     if perf_mode == 0:
@@ -359,8 +425,7 @@ class Run:
         if share is None:
             self.cfg = wl.make_config(name)
             self.perf_mode = self.cfg.perf_mode if perf_mode is None else perf_mode
-            os.makedirs(SCRATCH, exist_ok=True)
-            self.pattern_file = wl.write_pattern_file(os.path.join(SCRATCH, f"{self.cfg.name}_rank{rank}.pat"), self.cfg.patterns)
+            self.pattern_file = wl.write_pattern_file(os.path.join(scratch_dir(), f"{self.cfg.name}_rank{rank}.pat"), self.cfg.patterns)
             if self.gpu:
                 self.handle = api.PFAC.create()
             else:
@@ -780,12 +845,13 @@ def setup_rank(args):
     return rank, world, device, use_dist, barrier, dist
 
 
-def strong_numbers(args, sset, ms, elapsed_max, total_matches, folded, all_ok, method, world):
-    """The facts of one --scaling strong measurement (also other_configs.c4_8gib_one_gpu of the default line)."""
+def strong_numbers(args, sset, ms, elapsed_max, total_matches, folded, all_ok, method, world, check=True):
+    """The facts of one --scaling strong measurement (also other_configs.c4_8gib_one_gpu of the --full line).
+    check = False (a plain run): no result was gathered, the result facts are None."""
     from pfac_amd import sharding
     n = args.size_mib << 20
     expected = None
-    dgs = [load_digest(sset.owner.cfg.name, i, args.size_mib, last=(i == sset.total - 1)) for i in range(sset.total)]
+    dgs = [load_digest(sset.owner.cfg.name, i, args.size_mib, last=(i == sset.total - 1)) for i in range(sset.total)] if check else [None]
     if all(d is not None for d in dgs):
         ec, es = sharding.combine_checksums([(d["match_count"], d["checksum"]) for d in dgs])
         expected = {"match_count": ec, "checksum": es & 0x7FFFFFFFFFFFFFFF,
@@ -797,8 +863,8 @@ def strong_numbers(args, sset, ms, elapsed_max, total_matches, folded, all_ok, m
             "aggregate_GBps": round(sset.total * n / (elapsed_max / steps) / 1e9, 2), "ms_per_step": round(elapsed_max / steps * 1e3, 4),
             "kernel_ms_per_slice_avg": round(float(np.mean(per_launch)), 4),
             "frac": round(ALGO_BYTES_PER_INPUT_BYTE * sset.runs[0].n_read / (float(np.mean(per_launch)) / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
-            "matches": int(total_matches), "bit_exact": bool(all_ok), "bit_exact_method": method,
-            "folded_result": {"match_count": int(total_matches), "checksum": folded & 0x7FFFFFFFFFFFFFFF}, "folded_reference": expected,
+            "matches": int(total_matches) if check else None, "bit_exact": bool(all_ok) if check else None, "bit_exact_method": method,
+            "folded_result": {"match_count": int(total_matches), "checksum": folded & 0x7FFFFFFFFFFFFFFF} if check else None, "folded_reference": expected,
             "note": f"BASELINE config 4 as one workload: {sset.total} slices, each scanned with the head of its successor, dealt round-robin over "
                     f"{world} rank(s) (omp_PFAC.cpp:351-355); inputs resident in HBM, one result buffer per rank"}, all_ok
 
@@ -820,12 +886,20 @@ def strong_rank_main(args):
     perf_mode = None if args.perf_mode is None else (0 if args.perf_mode == "dense" else 1)
     sset = SliceSet(args, args.workload, perf_mode, args.texture, total, rank, world, device)
     log(f"[bench r{rank}] strong: slices {sset.index} of {total}, setup {time.perf_counter() - t_setup:.1f}s")
-    ok, method, count, checksum = sset.gate(args)
+    if args.full:
+        ok, method, count, checksum = sset.gate(args)
+    else:                                                      # the first pass, over before the settling launches are queued
+        sset.step()
+        if gpu:
+            sset.owner.torch.cuda.synchronize()
+        ok, method, count, checksum = True, NOT_CHECKED, 0, 0
     ms, elapsed = sset.timed(args.steps, args.warmup, SETTLE_STEPS if gpu else 0, barrier)
-    if not args.no_verify:                                     # the result of the last launch again (the rank's last slice)
+    if args.full and not args.no_verify:                       # the result of the last launch again (the rank's last slice)
         last, i = sset.runs[-1], sset.index[-1]
         ok2, _, _, _ = last.verify(args, i, total)
         ok = ok and ok2
+    if args.dump_outputs:                                      # the last launch of the last step: the rank's last slice
+        dump_outputs(args.dump_outputs, sset.runs[-1], f"rank{rank}_" if world > 1 else "")
     allf = sharding.all_gather_facts([count, checksum & 0x7FFFFFFFFFFFFFFF, int(ok), int(elapsed * 1e9), rank, *placement_facts(args, device)],
                                      device=device if (gpu and args.dist_backend == "nccl") else None, force=args.force_dist)
     elapsed_max = float(allf[:, 3].max()) / 1e9
@@ -833,7 +907,7 @@ def strong_rank_main(args):
     all_ok = bool(allf[:, 2].all()) and sorted(int(r) for r in allf[:, 4]) == list(range(world))
     rc = 0
     if rank == 0:
-        facts, all_ok = strong_numbers(args, sset, ms, elapsed_max, total_matches, folded, all_ok, method, world)
+        facts, all_ok = strong_numbers(args, sset, ms, elapsed_max, total_matches, folded, all_ok, method, world, check=args.full)
         info, run0 = sset.owner.info, sset.owner
         kname = kernel_name(args, run0)
         per_launch = [x / len(sset.runs) for x in ms]
@@ -900,12 +974,15 @@ def rank_main(args):
     if gpu:
         torch.cuda.synchronize()
     log(f"[bench r{rank}] first launch done {time.perf_counter() - t_setup:.1f}s")
-    ok, method, pos, ids = run.verify(args, rank, world)
-    log(f"[bench r{rank}] verified ({ok}) {time.perf_counter() - t_setup:.1f}s")
-    count = int(pos.size)
-    checksum = sharding.position_checksum(pos, ids, base=rank * run.n)
-    if rank == 0 and args.sparse_file:
-        np.savez(args.sparse_file, pos=pos, ids=ids, n=run.n, n_read=run.n_read)
+    if args.full:
+        ok, method, pos, ids = run.verify(args, rank, world)
+        log(f"[bench r{rank}] verified ({ok}) {time.perf_counter() - t_setup:.1f}s")
+        count = int(pos.size)
+        checksum = sharding.position_checksum(pos, ids, base=rank * run.n)
+        if rank == 0 and args.sparse_file:
+            np.savez(args.sparse_file, pos=pos, ids=ids, n=run.n, n_read=run.n_read)
+    else:
+        ok, method, count, checksum = True, NOT_CHECKED, 0, 0
 
     # ---- timed region: W warmup steps, then exactly K steps between barriers ---------------------
     # Host-side checks leave the GPU idle for ~1 s and its clocks drop; the first ~10 launches after
@@ -914,11 +991,13 @@ def rank_main(args):
     log(f"[bench r{rank}] timed region done {time.perf_counter() - t_setup:.1f}s")
     # the result of the LAST timed launch, checked like the first (a match lost under back-to-back launches at full clocks
     # would otherwise go unnoticed: the zeros come from other waves than the matches)
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         pos2, ids2 = run.sparse()
         if not (np.array_equal(pos2, pos) and np.array_equal(ids2, ids)):
             log(f"[bench r{rank}] RESULT OF THE LAST TIMED LAUNCH DIFFERS")
             ok = False
+    if args.dump_outputs:                                      # before anything below launches on these buffers again
+        dump_outputs(args.dump_outputs, run, f"rank{rank}_" if world > 1 else "")
 
     # ---- gather per-rank facts (RCCL: 7 x int64 per rank: count, checksum, exact, ns, rank, PCI bus id, NUMA node) ----------------------------------------
     allf = sharding.all_gather_facts([count, checksum & 0x7FFFFFFFFFFFFFFF, int(ok), int(elapsed * 1e9), rank, *placement_facts(args, device)],
@@ -932,7 +1011,7 @@ def rank_main(args):
     if rank == 0:
         # the omp_PFAC.cpp:396-439 check: the folded result of all slices == the reference's folded digests
         expected = None
-        dgs = [load_digest(run.cfg.name, r, args.size_mib, last=(r == world - 1)) for r in range(world)]
+        dgs = [load_digest(run.cfg.name, r, args.size_mib, last=(r == world - 1)) for r in range(world)] if args.full else [None]
         if all(d is not None for d in dgs):
             ec, es = sharding.combine_checksums([(d["match_count"], d["checksum"] & 0x7FFFFFFFFFFFFFFF) for d in dgs])
             expected = {"match_count": ec, "checksum": es & 0x7FFFFFFFFFFFFFFF,
@@ -959,17 +1038,17 @@ def rank_main(args):
                 "prefilter": {"ladder_last_level": int(getattr(info, "filterLadderLast", 20) or 20), "tail_table_entries": int(getattr(info, "filterTailEntries", 0) or 0),
                               "note": "tail_table_entries > 0: the full-result kernel runs its VETO instance (window walker behind the tail-hash veto, DESIGN 3.1)"},
                 "build": build_info(), "platform": args.platform,
-                "bytes_per_gpu": n, "matches": total_matches, "bit_exact": all_ok, "bit_exact_method": method,
+                "bytes_per_gpu": n, "matches": total_matches if args.full else None, "bit_exact": all_ok if args.full else None, "bit_exact_method": method,
                 "ranks_seen": ranks_seen, "rank_placement": rank_placement(allf), "dist_backend": args.dist_backend if use_dist else None,
-                "folded_result": {"match_count": total_matches, "checksum": folded & 0x7FFFFFFFFFFFFFFF},
+                "folded_result": {"match_count": total_matches, "checksum": folded & 0x7FFFFFFFFFFFFFFF} if args.full else None,
                 "folded_reference": expected,
             },
             "roofline": roofline_block(kernel_ms, run.n_read, kname),
         }
-        st = run.scan_stats()
+        st = run.scan_stats() if args.full else None
         if st:
             out["config"]["walk_stats"] = st
-        if world == 1 and gpu:
+        if world == 1 and gpu and args.full:
             torch = run.torch
             # not the headline metric: the compacted-output API on the same buffers.
             # Synchronous (the match count returns to the host), so wall clock per call.
@@ -1181,10 +1260,9 @@ def orchestrate(args, argv):
     if p.returncode != 0:
         log("[bench] build failed")
         return 2
-    os.makedirs(SCRATCH, exist_ok=True)
     n = args.gpus
-    single = n == 1 and args.platform == "gpu" and args.scaling == "weak"      # the CPU baseline and the PMC passes belong to the headline (weak) line
-    sparse_file = os.path.join(SCRATCH, f"{args.workload}_rank0_sparse.npz")
+    single = n == 1 and args.platform == "gpu" and args.scaling == "weak" and args.full   # the CPU baseline and the PMC passes belong to the headline (weak) --full line
+    sparse_file = os.path.join(scratch_dir(), f"{args.workload}_rank0_sparse.npz")
     if os.path.exists(sparse_file):
         os.remove(sparse_file)
     port = free_port()
@@ -1193,6 +1271,8 @@ def orchestrate(args, argv):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n),
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         extra = ["--sparse-file", sparse_file] if (single and r == 0 and not args.no_cpu_baseline) else []
+        if args.dump_outputs:                                   # the ranks run in ROOT: a relative DIR is the caller's
+            extra += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
         procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + argv + extra, env=env, cwd=ROOT,
                                       stdout=subprocess.PIPE if r == 0 else sys.stderr))
     out0, _ = procs[0].communicate()

@@ -61,6 +61,11 @@ class Workload:
 @pytest.fixture(scope="session")
 def workloads(workdir):
     """Small instances of the BASELINE.json configurations (oracle finishes in seconds)."""
+    return make_workloads(workdir)
+
+
+def make_workloads(workdir):
+    """{name: Workload} of the `workloads` fixture, pattern files written under workdir (also tests/golden/make_ref_facts.py)."""
     from pfac_amd import workloads as wl
 
     out = {}

@@ -107,7 +107,7 @@ def run_bench(*flags, timeout=900):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags, "--no-cpu-baseline", "--no-other-configs", "--pmc", "off"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags, "--full", "--no-cpu-baseline", "--no-other-configs", "--pmc", "off"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     return json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])

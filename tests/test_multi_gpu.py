@@ -63,7 +63,7 @@ def test_rank_path_runs_one_rccl_all_gather_on_hardware():
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", LOCAL_WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(29500 + os.getpid() % 2000), HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist-backend", "nccl", "--force-dist", "--size-mib", "64",
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs", "--pmc", "off"]
+           "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-configs", "--pmc", "off"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
     line = [l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1]

@@ -119,25 +119,51 @@ def _golden_input(wl, case, pats):
     return data
 
 
-@pytest.mark.skipif(not ob.have_reference(), reason="oracle/_ref not built (needs /root/reference)")
+def reference_facts(w, o):
+    """What the reference's own code (oracle/_ref) says about workload w, as tests/golden/ref_facts.json records it: its trie
+    (sizes, SHA-256 of the edge list) and the digest of each of its matchers' results over the restatement's tables."""
+    import hashlib
+    r = ob.Reference(w.pattern_file)
+    facts = {"num_patterns": r.t.num_patterns, "num_states": r.t.num_states, "initial_state": r.t.initial_state,
+             "max_pattern_len": r.t.max_pattern_len,
+             "edges_sha256": hashlib.sha256(json.dumps([list(e) for e in r.edges()]).encode()).hexdigest(), "results": {}}
+    for omp in (False, True):
+        facts["results"][f"dense_omp{int(omp)}"] = list(ob.digest(ob.Reference.match_dense(w.data, o.dense_table(), o.num_patterns, o.initial_state, omp)))
+        facts["results"][f"hash_omp{int(omp)}"] = list(ob.digest(ob.Reference.match_hash(w.data, o.hash_row(), o.hash_val(), o.num_patterns,
+                                                                                      o.initial_state, omp)))
+    return facts
+
+
 @pytest.mark.parametrize("name", ["c1", "ex2", "c2", "c3", "c5", "dense_hits", "binary"])
-def test_restatement_equals_reference_code(workloads, oracle_results, name):
+def test_restatement_equals_reference_code(workloads, oracle_results, golden_dir, name):
     """Trie (state numbering, edge order) identical to the reference's parsePatternFile +
     create_PFACTable_spaceDriven; the reference's scalar and OpenMP matchers agree with the
-    restatement on both table layouts."""
+    restatement on both table layouts.  Without oracle/_ref, against what the reference's code said about the same
+    workloads (tests/golden/ref_facts.json, tests/golden/make_ref_facts.py)."""
+    import hashlib
     w = workloads[name]
     o = ob.Oracle(w.pattern_file)
+    want = oracle_results[name]
+    assert np.array_equal(o.match(w.data, hashed=True), want)
+    assert np.array_equal(o.match(w.data, hashed=True, omp=True), want)
+    recorded = json.load(open(os.path.join(golden_dir, "ref_facts.json")))["workloads"][name]
+    if ob.have_reference():
+        assert reference_facts(w, o) == recorded, "tests/golden/ref_facts.json is stale: rerun tests/golden/make_ref_facts.py"
+    assert (o.num_patterns, o.num_states, o.initial_state, o.max_pattern_len) == (
+        recorded["num_patterns"], recorded["num_states"], recorded["initial_state"], recorded["max_pattern_len"])
+    assert hashlib.sha256(json.dumps([list(e) for e in o.edges()]).encode()).hexdigest() == recorded["edges_sha256"]
+    for matcher, d in recorded["results"].items():
+        assert list(ob.digest(want)) == d, matcher
+    if not ob.have_reference():
+        return
     r = ob.Reference(w.pattern_file)
     assert (r.t.num_patterns, r.t.num_states, r.t.initial_state, r.t.max_pattern_len) == (
         o.num_patterns, o.num_states, o.initial_state, o.max_pattern_len)
     assert r.edges() == o.edges()
-    want = oracle_results[name]
     for omp in (False, True):
         assert np.array_equal(ob.Reference.match_dense(w.data, o.dense_table(), o.num_patterns, o.initial_state, omp), want)
         assert np.array_equal(ob.Reference.match_hash(w.data, o.hash_row(), o.hash_val(), o.num_patterns,
                                                       o.initial_state, omp), want)
-    assert np.array_equal(o.match(w.data, hashed=True), want)
-    assert np.array_equal(o.match(w.data, hashed=True, omp=True), want)
 
 
 def test_oracle_rejects_what_the_reference_leaves_undefined(tmp_path):

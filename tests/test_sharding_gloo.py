@@ -137,7 +137,7 @@ def test_bench_spawns_the_ranks_itself_and_checks_the_reference_digests():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--platform", "cpu_omp", "--dist-backend", "gloo",
-                        "--size-mib", "8", "--steps", "1", "--warmup", "0", "--workload", "c3"],
+                        "--size-mib", "8", "--steps", "1", "--warmup", "0", "--workload", "c3", "--full"],
                        cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     line = [l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1]
@@ -169,7 +169,7 @@ def test_strong_scaling_mode_deals_the_slices_round_robin():
     folded = {}
     for gpus in (2, 1):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--scaling", "strong", "--total-mib", "64", "--size-mib", "8",
-                            "--platform", "cpu_omp", "--dist-backend", "gloo", "--steps", "1", "--warmup", "0", "--workload", "c3"],
+                            "--platform", "cpu_omp", "--dist-backend", "gloo", "--steps", "1", "--warmup", "0", "--workload", "c3", "--full"],
                            cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
         assert p.returncode == 0, p.stderr.decode()[-2000:]
         out = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -196,7 +196,7 @@ def test_eight_ranks_one_slice_each_fold_to_the_reference():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--scaling", "strong", "--total-mib", "64", "--size-mib", "8",
-                        "--platform", "cpu_omp", "--dist-backend", "gloo", "--steps", "1", "--warmup", "0", "--workload", "c3"],
+                        "--platform", "cpu_omp", "--dist-backend", "gloo", "--steps", "1", "--warmup", "0", "--workload", "c3", "--full"],
                        cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=850)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     out = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])

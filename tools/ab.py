@@ -47,7 +47,7 @@ def main():
                 for w in a.workloads.split(","):
                     ww, extra = (("c5", ["--perf-mode", "hash"]) if w == "c5h" else (w, []))
                     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup", "3", "--workload", ww,
-                           "--no-cpu-baseline", "--no-other-configs", "--spread", "--pmc", "off"] + extra + a.extra.split()
+                           "--full", "--no-cpu-baseline", "--no-other-configs", "--spread", "--pmc", "off"] + extra + a.extra.split()
                     if (spec, w) in dead:
                         continue
                     try:                                    # a variant that hangs costs one short timeout, once

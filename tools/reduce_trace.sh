@@ -2,7 +2,7 @@
 # tools/reduce_trace.sh [workload] -- kernel trace of the compacted-output call (PFAC_matchFromDeviceReduce) inside
 # bench.py's rank worker: every launch of the last calls with its duration and the idle time in front of it.
 W=${1:-c3}; O=gpurun_out/prof_reduce_$W; export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o prof -- python3 bench.py --worker rank --workload $W --no-other-configs --steps 3 --warmup 1 --no-cpu-baseline --pmc off > $O.json 2> $O.err
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o prof -- python3 bench.py --worker rank --full --workload $W --no-other-configs --steps 3 --warmup 1 --no-cpu-baseline --pmc off > $O.json 2> $O.err
 python3 - "$O/prof_kernel_trace.csv" <<PY
 import csv, sys
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))

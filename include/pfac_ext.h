@@ -79,7 +79,8 @@ typedef struct {
                                  launch counters; the reference-layout table only while PFACX_KERNEL_REFTABLE is selected */
     size_t deviceScratchBytes; /* device memory the handle's calls have left allocated (grow-only; PFACX_trim frees it): the two staging
                                  pieces of PFAC_matchFromHost / ...Reduce (9 bytes per position of a piece), the ordering scratch of the
-                                 compacted output, the list of pattern-dense chunks */
+                                 compacted output, the list of pattern-dense chunks, what the batch calls keep (pattern lengths, offsets of a
+                                 host piece, the compaction scratch of the compacted form) */
     int streamNearMisses;      /* what the handle's last big full-result launch said about its stream (host memory the launch's last block
                                  writes; nothing is waited for): 1 = full of near misses of long patterns -> PFACX_WALKER_AUTO picks STAGE ... */
     int streamDense;           /* ... 1 = most of it pattern-dense (short patterns over text, runs of a pattern byte) -> PFACX_KERNEL_AUTO
@@ -236,6 +237,32 @@ PFAC_status_t PFACX_getScanStats(PFAC_handle_t handle, PFACX_scan_stats_t *stats
  * the default stream (a few microseconds per call); PFACX_getScanStats then reports the kernel's own time -- inside
  * PFAC_matchFromDeviceReduce, say, whose other launches a caller's events cannot tell apart. */
 PFAC_status_t PFACX_setKernelTiming(PFAC_handle_t handle, int on);
+
+/* Batch matching: one input buffer of `size` bytes cut into numSegments independent segments (packets, records) by
+ * numSegments + 1 offsets -- offsets[0] == 0, offsets[numSegments] == size, never decreasing (empty segments are allowed).
+ * No match runs from one segment into the next: the result at a position p of segment k is what PFAC_matchFromHost on a CPU
+ * platform returns at p - offsets[k] for segment k alone, so the result is the concatenation of the per-segment results (a
+ * batch of one segment is the plain call).  One call costs about what the plain call over the same bytes costs (DESIGN.md
+ * "batch"), where one call per segment pays a call's fixed cost per segment.
+ * A null pointer, numSegments == 0 with size > 0, or host offsets that break the rules: PFAC_STATUS_INVALID_PARAMETER;
+ * size == 0: success, nothing done; a host-only handle on the GPU path: PFAC_STATUS_LIB_NOT_EXIST.
+ * DEVICE offsets are not checked (that would cost a sync): they are the caller's contract, like the sizes of the buffers.
+ * The kernels clamp every offset to [0, size] and take a decreasing pair as an empty segment, so bad offsets give wrong
+ * results but never a read or write outside the buffers. */
+
+/* full result over device buffers (d_offsets: numSegments + 1 size_t in device memory); asynchronous on the default stream,
+ * like PFAC_matchFromDevice */
+PFAC_status_t PFACX_matchBatchFromDevice(PFAC_handle_t handle, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                                         int *d_matched_result);
+/* full result over host buffers; follows PFAC_setPlatform (the CPU platforms match segment by segment); synchronous; h_offsets is
+ * validated */
+PFAC_status_t PFACX_matchBatchFromHost(PFAC_handle_t handle, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments,
+                                       int *h_matched_result);
+/* compacted: the (id, position) pairs in position order as PFAC_matchFromDeviceReduce returns them (d_matched_result and d_pos hold
+ * `size` entries), plus d_segFirst[numSegments + 1]: the pairs of segment k are entries [d_segFirst[k], d_segFirst[k + 1]);
+ * size < 2^31; synchronous (the count comes to the host) */
+PFAC_status_t PFACX_matchBatchFromDeviceReduce(PFAC_handle_t handle, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                                               int *d_matched_result, int *d_pos, int *d_segFirst, int *h_num_matched);
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,19 @@ PFAC_status_t PFAC_reduce_inplace_kernel(PFAC_handle_t handle, int *d_input_stri
                                          int *d_match_result, int *d_pos, int *h_num_matched,
                                          int *h_match_result, int *h_pos);
 
+/* Batch matching (no reference counterpart; include/pfac_ext.h: PFACX_matchBatch*), scan_batch.hip.  Both run behind a scan of
+ * the whole concatenation on the default stream and turn its result into the concatenation of the per-segment results:
+ * d_offsets holds numSegments + 1 entries (clamped to [0, size] on the device), d_patternLen the pattern lengths by id.
+ * PFACX_batchFixup: full result, asynchronous.  PFACX_batchReduceFixup: the *count (id, position) pairs of a compacted-output
+ * scan; pairs that lose their match drop out (order kept), *count is updated, d_segFirst[numSegments + 1] filled; synchronous. */
+PFAC_status_t PFACX_batchFixup(PFAC_handle_t handle, const char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                               int *d_matched_result, const int *d_patternLen);
+PFAC_status_t PFACX_batchReduceFixup(PFAC_handle_t handle, const char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                                     int *d_ids, int *d_pos, int *count, int *d_segFirst, const int *d_patternLen);
+typedef PFAC_status_t (*PFACX_batchFixup_protoType)(PFAC_handle_t, const char *, size_t, const size_t *, size_t, int *, const int *);
+typedef PFAC_status_t (*PFACX_batchReduceFixup_protoType)(PFAC_handle_t, const char *, size_t, const size_t *, size_t, int *, int *, int *, int *,
+                                                          const int *);
+
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of
  * `launches` launches over the first n bytes (a multiple of 4096) of d_in, or a negative value on a HIP error.

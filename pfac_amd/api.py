@@ -92,10 +92,12 @@ EXPORTED_SYMBOLS = (
     "PFACX_readPatternFromMemory", "PFACX_getScanStats", "PFACX_saveCompiled", "PFACX_loadCompiled",
     "PFACX_matchFromHostMultiGPU", "PFACX_matchFromHostReduceMultiGPU", "PFACX_readPatternFromFileEx", "PFACX_readPatternFromMemoryEx", "PFACX_trim",
     "PFACX_setKernelTiming", "PFACX_setWalker", "PFACX_prepare",
+    "PFACX_matchBatchFromDevice", "PFACX_matchBatchFromHost", "PFACX_matchBatchFromDeviceReduce",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
     "PFAC_reduce_kernel", "PFAC_reduce_inplace_kernel", "PFACX_streamProbe", "PFACX_buildInfo",
+    "PFACX_batchFixup", "PFACX_batchReduceFixup",
 )
 
 
@@ -149,6 +151,11 @@ def load_library() -> C.CDLL:
     lib.PFACX_matchFromHostMultiGPU.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     if hasattr(lib, "PFACX_matchFromHostReduceMultiGPU"):
         lib.PFACX_matchFromHostReduceMultiGPU.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
+    if hasattr(lib, "PFACX_matchBatchFromDevice"):
+        lib.PFACX_matchBatchFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.PFACX_matchBatchFromHost.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.PFACX_matchBatchFromDeviceReduce.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.POINTER(C.c_int)]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -329,6 +336,34 @@ class PFAC:
         n = C.c_int(0)
         st = self._lib.PFAC_matchFromHostReduce(self._h, h_input, size, h_result, h_pos, C.byref(n))
         return self._ret(st, "PFAC_matchFromHostReduce", check), n.value
+
+    # -- batches of independent segments (include/pfac_ext.h: PFACX_matchBatch*) ------
+    def matchBatchFromDevice(self, d_input: int, size: int, d_offsets: int, num_segments: int, d_result: int, check: bool = True) -> int:
+        """``PFACX_matchBatchFromDevice``: `d_offsets` = device address of num_segments + 1 size_t offsets."""
+        return self._ret(self._lib.PFACX_matchBatchFromDevice(self._h, d_input, size, d_offsets, num_segments, d_result),
+                         "PFACX_matchBatchFromDevice", check)
+
+    def matchBatchFromHost(self, h_input: int, size: int, h_offsets: int, num_segments: int, h_result: int, check: bool = True) -> int:
+        """``PFACX_matchBatchFromHost``: `h_offsets` = host address of num_segments + 1 size_t offsets (validated)."""
+        return self._ret(self._lib.PFACX_matchBatchFromHost(self._h, h_input, size, h_offsets, num_segments, h_result),
+                         "PFACX_matchBatchFromHost", check)
+
+    def matchBatchFromDeviceReduce(self, d_input: int, size: int, d_offsets: int, num_segments: int, d_result: int, d_pos: int,
+                                   d_seg_first: int, check: bool = True):
+        """``PFACX_matchBatchFromDeviceReduce`` -> (status, number of pairs); `d_seg_first` receives num_segments + 1 ints."""
+        n = C.c_int(0)
+        st = self._lib.PFACX_matchBatchFromDeviceReduce(self._h, d_input, size, d_offsets, num_segments, d_result, d_pos, d_seg_first, C.byref(n))
+        return self._ret(st, "PFACX_matchBatchFromDeviceReduce", check), n.value
+
+    def match_batch_host_array(self, data, offsets):
+        """matchBatchFromHost over numpy arrays: `offsets` = the num_segments + 1 segment offsets."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        out = np.full(data.size, -7, dtype=np.int32)   # poison: every element must be written
+        if data.size:
+            self.matchBatchFromHost(data.ctypes.data, data.size, offs.ctypes.data, offs.size - 1, out.ctypes.data)
+        return out
 
     # -- numpy conveniences over matchFromHost (still the C ABI underneath) ----------
     def match_host_array(self, data):

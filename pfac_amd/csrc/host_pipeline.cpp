@@ -15,6 +15,7 @@
 #include <emmintrin.h>
 #endif
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -509,6 +510,57 @@ PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t 
     const bool drained = hipStreamSynchronize(up) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
     if (!drained && st == PFAC_STATUS_SUCCESS) st = PFAC_STATUS_INTERNAL_ERROR;
     if (st == PFAC_STATUS_SUCCESS) *h_num_matched = (int)total;
+    return st;
+}
+
+/*
+ * PFACX_matchBatchFromHost on the GPU: the stream in pieces of kHostPiece positions, as for PFAC_matchFromHost.  Piece [a, b) is
+ * uploaded with its read-ahead up to w = min(size, b + maxPatternLen), the segment boundaries inside (a, w) are rebased to a and the
+ * window's ends added, the device batch runs on the window and the results of [a, b) come back.  Clipping the last segment at w is
+ * exact: no walk from a position before b reaches w.  A segment may straddle pieces or span several.  Piece by piece, in sequence
+ * (one staging buffer): the batch call is for many small buffers that are on the device already, and this form keeps its contract.
+ */
+PFAC_status_t matchBatchHostOnGpu(PFAC_context *c, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments, int *h_matched_result)
+{
+    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    const size_t overlap = (size_t)c->fa.maxPatternLen;
+    const size_t piece = size < kHostPiece ? size : kHostPiece;
+    PFAC_status_t st = ensureHostStage(c, piece + overlap);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    std::vector<size_t> local;
+    try {
+        for (size_t a = 0; a < size && st == PFAC_STATUS_SUCCESS; a += piece) {
+            const size_t b = size - a < piece ? size : a + piece;
+            const size_t w = size - b < overlap ? size : b + overlap;
+            /* the segment that holds a: the last k < numSegments with offsets[k] <= a; its successors' starts inside (a, w) */
+            size_t k = (size_t)(std::upper_bound(h_offsets, h_offsets + numSegments, a) - h_offsets) - 1;
+            local.clear();
+            local.push_back(0);
+            for (k++; k < numSegments && h_offsets[k] < w; k++) local.push_back(h_offsets[k] - a);
+            local.push_back(w - a);
+            if (c->batchOffsetsEntries < local.size()) {
+                devFree(c->d_batchOffsets);
+                c->batchOffsetsEntries = 0;
+                const size_t want = local.size() > 4096 ? local.size() : 4096;
+                if (hipMalloc(reinterpret_cast<void **>(&c->d_batchOffsets), want * sizeof(size_t)) != hipSuccess) {
+                    (void)hipGetLastError();
+                    c->d_batchOffsets = nullptr;
+                    return PFAC_STATUS_CUDA_ALLOC_FAILED;
+                }
+                c->batchOffsetsEntries = want;
+            }
+            if (hipMemcpy(c->d_stageIn[0], h_input + a, w - a, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(c->d_batchOffsets, local.data(), local.size() * sizeof(size_t), hipMemcpyHostToDevice) != hipSuccess) {
+                st = PFAC_STATUS_INTERNAL_ERROR;
+                break;
+            }
+            st = matchBatchDeviceLocked(c, c->d_stageIn[0], w - a, c->d_batchOffsets, local.size() - 1, c->d_stageOut[0]);
+            if (st == PFAC_STATUS_SUCCESS &&
+                hipMemcpy(h_matched_result + a, c->d_stageOut[0], (b - a) * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+                st = PFAC_STATUS_INTERNAL_ERROR;
+        }
+    } catch (const std::bad_alloc &) { st = PFAC_STATUS_ALLOC_FAILED; }
+    if (hipStreamSynchronize(nullptr) != hipSuccess && st == PFAC_STATUS_SUCCESS) st = PFAC_STATUS_INTERNAL_ERROR;
     return st;
 }
 

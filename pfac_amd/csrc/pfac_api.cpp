@@ -75,6 +75,17 @@ void freeHostStage(PFAC_context *c)
     c->hostStagePositions = 0;
 }
 
+/* what the batch calls keep (pfac_context.h): the pattern lengths go with the set, the rest is grow-only scratch */
+void freeBatchScratch(PFAC_context *c)
+{
+    devFree(c->d_patternLen);
+    c->patternLenEntries = 0;
+    devFree(c->d_batchOffsets);
+    c->batchOffsetsEntries = 0;
+    if (c->d_batchScratch) { (void)hipFree(c->d_batchScratch); c->d_batchScratch = nullptr; }
+    c->batchScratchBytes = 0;
+}
+
 /* ref PFAC_freeResource, PFAC.cpp:221-254 */
 void freeResources(PFAC_context *c)
 {
@@ -98,6 +109,7 @@ void freeResources(PFAC_context *c)
     devFree(c->d_final3);
     devFree(c->d_denseList);
     c->denseListEntries = 0;
+    freeBatchScratch(c);
     for (auto &child : c->children) (void)PFAC_destroy(child.second);
     c->children.clear();
     c->fa = pfac::Automaton();
@@ -275,8 +287,10 @@ PFAC_status_t loadModule(PFAC_context *c)
     c->kernel_space_driven_ptr = (PFAC_kernel_protoType)dlsym(m, "PFAC_kernel_spaceDriven_warpper");
     c->reduce_kernel_ptr = (PFAC_reduce_kernel_protoType)dlsym(m, "PFAC_reduce_kernel");
     c->reduce_inplace_kernel_ptr = (PFAC_reduce_kernel_protoType)dlsym(m, "PFAC_reduce_inplace_kernel");
+    c->batch_fixup_ptr = (PFACX_batchFixup_protoType)dlsym(m, "PFACX_batchFixup");
+    c->batch_reduce_fixup_ptr = (PFACX_batchReduceFixup_protoType)dlsym(m, "PFACX_batchReduceFixup");
     if (!c->kernel_time_driven_ptr || !c->kernel_space_driven_ptr || !c->reduce_kernel_ptr ||
-        !c->reduce_inplace_kernel_ptr)
+        !c->reduce_inplace_kernel_ptr || !c->batch_fixup_ptr || !c->batch_reduce_fixup_ptr)
         return PFAC_STATUS_INTERNAL_ERROR;
     return PFAC_STATUS_SUCCESS;
 }
@@ -628,10 +642,11 @@ PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info)
         v.deviceTableBytes = dev;
         /* ... and what its calls have left allocated (grow-only, PFACX_trim gives it back): the two staging pieces of the host
          * paths (input + ids + positions: 9 bytes per position), the scratch the compacted output is ordered through, the list
-         * of pattern-dense chunks */
+         * of pattern-dense chunks, what the batch calls keep */
         size_t scratch = 0;
         if (handle->hostStagePositions) scratch += 2 * (((handle->hostStagePositions + 3) & ~size_t(3)) + 2 * handle->hostStagePositions * sizeof(int));
         scratch += handle->reduceScratchBytes + handle->denseListEntries * sizeof(unsigned int);
+        scratch += handle->patternLenEntries * sizeof(int) + handle->batchOffsetsEntries * sizeof(size_t) + handle->batchScratchBytes;
         v.deviceScratchBytes = scratch;
         if (handle->h_modeHint) {
             v.streamNearMisses = (int)static_cast<volatile const unsigned int *>(handle->h_modeHint)[0];
@@ -700,7 +715,7 @@ PFAC_status_t PFACX_getTable(PFAC_handle_t handle, PFACX_table_t which, const vo
 extern "C" {
 
 /* pfac_ext.h: give back the grow-only device buffers of the handle (staging of PFAC_matchFromHost, copies of
- * PFAC_matchFromHostReduce, sort scratch, the dense-chunk list); the next call that needs one allocates it again */
+ * PFAC_matchFromHostReduce, sort scratch, the dense-chunk list, what the batch calls keep); the next call that needs one allocates it again */
 PFAC_status_t PFACX_trim(PFAC_handle_t handle)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
@@ -711,6 +726,7 @@ PFAC_status_t PFACX_trim(PFAC_handle_t handle)
     handle->orderCleanBase = nullptr;
     devFree(handle->d_denseList);
     handle->denseListEntries = 0;
+    freeBatchScratch(handle);
     for (auto &child : handle->children) if (child.second) (void)PFACX_trim(child.second);
     return PFAC_STATUS_SUCCESS;
 }

@@ -341,6 +341,8 @@ struct PFAC_context {
     PFAC_kernel_protoType kernel_space_driven_ptr = nullptr;
     PFAC_reduce_kernel_protoType reduce_kernel_ptr = nullptr;
     PFAC_reduce_kernel_protoType reduce_inplace_kernel_ptr = nullptr;
+    PFACX_batchFixup_protoType batch_fixup_ptr = nullptr;              /* scan_batch.hip: the batch calls (PFACX_matchBatch*) */
+    PFACX_batchReduceFixup_protoType batch_reduce_fixup_ptr = nullptr;
 
     int platform = PFAC_PLATFORM_GPU;
     int perfMode = PFAC_TIME_DRIVEN;
@@ -360,6 +362,15 @@ struct PFAC_context {
     /* chunks the filter kernel found pattern-dense and left to the simple kernel (scan_*.hip): grow-only, one entry per chunk of a launch */
     unsigned int *d_denseList = nullptr;
     size_t denseListEntries = 0;
+    /* the batch calls (PFACX_matchBatch*): device copy of fa.patternLen (uploaded on the first batch call, dropped with the set), the
+     * offsets of a piece of PFACX_matchBatchFromHost, the compaction scratch of PFACX_matchBatchFromDeviceReduce (scan_batch.hip).
+     * Grow-only scratch: PFACX_trim frees them, deviceScratchBytes counts them */
+    int *d_patternLen = nullptr;
+    size_t patternLenEntries = 0;
+    size_t *d_batchOffsets = nullptr;
+    size_t batchOffsetsEntries = 0;
+    void *d_batchScratch = nullptr;
+    size_t batchScratchBytes = 0;
 
     bool hasDevice = false;
     int device = -1;

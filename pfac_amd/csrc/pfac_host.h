@@ -61,6 +61,7 @@ constexpr size_t kHostPiece = size_t(32) << 20;
 void freeTables(PFAC_context *c);
 void freeHostStage(PFAC_context *c);
 void freeResources(PFAC_context *c);
+void freeBatchScratch(PFAC_context *c);
 PFAC_status_t bindTable(PFAC_context *c);
 PFAC_status_t bindCommon(PFAC_context *c, bool build = true);
 void correctTextureMode(PFAC_context *c);
@@ -72,6 +73,10 @@ PFAC_status_t prepareHostPath(PFAC_context *c, size_t maxBytes);
 PFAC_status_t matchDeviceLocked(PFAC_context *c, char *d_inputString, size_t size, int *d_matched_result);
 PFAC_status_t matchHostOnGpu(PFAC_context *c, char *h_inputString, size_t owned, size_t readable, int *h_matched_result);
 PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t size, size_t readable, size_t posBase, int *h_matched_result, int *h_pos, int *h_num_matched);
+/* batch_api.cpp: the batch calls (PFACX_matchBatch*) behind their argument checks; the caller holds c->lock */
+PFAC_status_t matchBatchDeviceLocked(PFAC_context *c, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments, int *d_matched_result);
+/* host_pipeline.cpp: PFACX_matchBatchFromHost on the GPU platform (h_offsets validated); the caller holds c->lock */
+PFAC_status_t matchBatchHostOnGpu(PFAC_context *c, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments, int *h_matched_result);
 
 } // namespace pfac_internal
 

@@ -92,6 +92,8 @@ typedef struct {
     int filterLog2TailGlobal;  /* log2 of the buckets of that table */
     unsigned int filterLadderSalt; /* XORed into the depth-4 hash of the prefix ladder (chosen per pattern set: pfac_context.h) */
     int filterSkipTags;        /* skip tags of the prefix ladder (PFACX_TABLE_FILTER_SKIP): depth-6 nodes with a single path down to depth 20 (at most 8) */
+    int maxMatchesPerPosition; /* the most patterns that can start at one position: the longest PFACX_TABLE_PREFIX_PATTERN chain plus one (1 when
+                                  no pattern is a prefix of another).  PFACX_matchAll* with capacity = size * maxMatchesPerPosition never truncates */
 } PFACX_info_t;
 
 PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info);
@@ -115,6 +117,9 @@ typedef enum {
                                       pattern below it) & ~0x7FF | depth of the first compared byte << 3 | bytes / 4 - 1}; bucket of a hash h =
                                       (h * 0x9E3779B1) >> (32 - filterLog2TailGlobal); an entry is occupied if (word1 & 0x7F8) != 0 */
     PFACX_TABLE_FILTER_SKIP  = 13, /* uint32[filterSkipTags]: ladder hashes (depth 6) whose candidates are next asked at depth 20 */
+    PFACX_TABLE_PREFIX_PATTERN = 14, /* int[numOfPatterns + 1] by pattern id: the id of the longest pattern that is a proper prefix of pattern id
+                                      (0: none; entry 0 is 0).  IDs that are never reported (the lower IDs of duplicate lines) have 0.  What
+                                      PFACX_matchAll* follows from the longest pattern at a position */
     PFACX_TABLE_CHAIN        = 8   /* uint32[4] per 16-byte unit: the device-only chained form of the hashed table that the
                                       GPU kernels walk in both perf modes.  chainSlots / 2 slot headers -- compact buckets,
                                       breadth first; then the 256 slots of the initial state; then the 2^chainJumpLog2
@@ -263,6 +268,37 @@ PFAC_status_t PFACX_matchBatchFromHost(PFAC_handle_t handle, char *h_input, size
  * size < 2^31; synchronous (the count comes to the host) */
 PFAC_status_t PFACX_matchBatchFromDeviceReduce(PFAC_handle_t handle, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
                                                int *d_matched_result, int *d_pos, int *d_segFirst, int *h_num_matched);
+
+/* All matches.  The calls above report ONE pattern per position, the longest that starts there.  Rule-based users (intrusion
+ * detection, log scanning) need every pattern that occurs, since each belongs to a rule of its own.
+ *   The ALL-MATCH LIST of an input is the set of pairs (position p, pattern id) such that pattern id occurs at p; positions count
+ *   from the start of the input.  ORDER: ascending position; within one position the longest pattern first, the shorter ones
+ *   behind it in descending length -- so the first pair of each position is the pair PFAC_matchFromDeviceReduce reports there.
+ *   Duplicate lines load as one pattern, reported under the highest of their IDs as in every other call, and are listed once.
+ *   The list can be longer than the input (patterns a, aa, ..., a x 8 over a run of a: up to 8 pairs per position): the count
+ *   is a size_t.  Positions are int: size < 2^31, as for the compacted calls.
+ * Every pattern that starts at p is a prefix of the longest one there, so the list follows from the longest-match result and
+ * PFACX_TABLE_PREFIX_PATTERN (DESIGN.md "all matches").
+ * d_ids / d_pos (h_ids / h_pos) hold `capacity` entries each, capacity >= size (they double as the scan's pair list, as in
+ * PFAC_matchFromDeviceReduce); a smaller capacity is PFAC_STATUS_INVALID_PARAMETER.  A list longer than capacity: exactly its first
+ * `capacity` pairs are written and nothing behind them, *h_num_matched is the full count and the call returns
+ * PFACX_STATUS_OUTPUT_TRUNCATED -- grow the arrays and call again (capacity = size * maxMatchesPerPosition of PFACX_getInfo never
+ * truncates).  Null pointers, size == 0 (success, *h_num_matched = 0), size >= 2^31 and a host-only handle on the GPU path are
+ * handled as in PFAC_matchFromDeviceReduce.  All three calls are synchronous (the count comes to the host). */
+#define PFACX_STATUS_OUTPUT_TRUNCATED ((PFAC_status_t)10100)
+
+/* over device buffers; the GPU platform's match path (whatever kernel variant, walker, perf mode and texture mode the handle selects) */
+PFAC_status_t PFACX_matchAllFromDevice(PFAC_handle_t handle, char *d_input, size_t size, int *d_ids, int *d_pos, size_t capacity,
+                                       size_t *h_num_matched);
+/* over host buffers; follows PFAC_setPlatform: the CPU platforms (host-only handles included) match on the CPU, the GPU platform
+ * runs the pipelined path of PFAC_matchFromHostReduce; either way the list is expanded in place on the host */
+PFAC_status_t PFACX_matchAllFromHost(PFAC_handle_t handle, char *h_input, size_t size, int *h_ids, int *h_pos, size_t capacity,
+                                     size_t *h_num_matched);
+/* batch form (offsets as for PFACX_matchBatch*; device offsets are clamped, never checked): every segment its own all-match list,
+ * positions relative to the buffer, the lists concatenated in segment order; d_segFirst[numSegments + 1] (device) indexes the
+ * whole list: the pairs of segment k are [d_segFirst[k], d_segFirst[k + 1]) (indices past capacity name pairs not written) */
+PFAC_status_t PFACX_matchAllBatchFromDevice(PFAC_handle_t handle, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                                            int *d_ids, int *d_pos, size_t capacity, size_t *d_segFirst, size_t *h_num_matched);
 
 #ifdef __cplusplus
 }

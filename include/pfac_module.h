@@ -61,6 +61,25 @@ typedef PFAC_status_t (*PFACX_batchFixup_protoType)(PFAC_handle_t, const char *,
 typedef PFAC_status_t (*PFACX_batchReduceFixup_protoType)(PFAC_handle_t, const char *, size_t, const size_t *, size_t, int *, int *, int *, int *,
                                                           const int *);
 
+/* All matches (no reference counterpart; include/pfac_ext.h: PFACX_matchAll*).
+ * PFACX_allReduce, scan_module.hip: PFAC_reduce_kernel (hashed == 0) / PFAC_reduce_inplace_kernel (hashed != 0) whose ordering
+ * writes the ordered (id, position) pairs into the handle's all-match scratch -- ids at PFAC_context::d_allPairs, positions
+ * allPairsEntries ints behind them -- instead of into d_match_result / d_pos, which hold `input_size` entries and take only the
+ * scan's unordered list; synchronous, *h_num_matched = the number of pairs.
+ * PFACX_allExpand, scan_all.hip: expands `count` ordered longest pairs through d_table (pfac::Int2 {prefixPattern, chainLen} by
+ * id) into d_ids / d_pos, every pattern at a position, longest first; slots >= capacity are not written; *h_total = the length
+ * of the whole list.  d_segFirst (or null): numSegments + 1 size_t, entry k = d_segFirstPairs[k] (the first longest pair of
+ * segment k) through the expansion.  d_table may be null when count == 0 or every chain has length 1 (then only d_segFirst is
+ * written).  Synchronous. */
+PFAC_status_t PFACX_allReduce(PFAC_handle_t handle, int *d_input_string, int input_size, int *d_match_result, int *d_pos,
+                              int *h_num_matched, int hashed);
+PFAC_status_t PFACX_allExpand(PFAC_handle_t handle, const int *d_pairIds, const int *d_pairPos, size_t count, const void *d_table,
+                              int *d_ids, int *d_pos, size_t capacity, const int *d_segFirstPairs, size_t numSegments, size_t *d_segFirst,
+                              size_t *h_total);
+typedef PFAC_status_t (*PFACX_allReduce_protoType)(PFAC_handle_t, int *, int, int *, int *, int *, int);
+typedef PFAC_status_t (*PFACX_allExpand_protoType)(PFAC_handle_t, const int *, const int *, size_t, const void *, int *, int *, size_t,
+                                                   const int *, size_t, size_t *, size_t *);
+
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of
  * `launches` launches over the first n bytes (a multiple of 4096) of d_in, or a negative value on a HIP error.

@@ -31,6 +31,7 @@ PFACX_READ_STRICT, PFACX_READ_STRIP_CR = 1, 2
  PFACX_TABLE_FILTER_GRAM3, PFACX_TABLE_FILTER_SHORT, PFACX_TABLE_FILTER_LADDER, PFACX_TABLE_FILTER_FINAL3,
  PFACX_TABLE_CHAIN) = range(9)
 PFACX_TABLE_FILTER_GRAM1, PFACX_TABLE_FILTER_PREFIX4, PFACX_TABLE_FILTER_TAIL, PFACX_TABLE_FILTER_TAIL_GLOBAL, PFACX_TABLE_FILTER_SKIP = 9, 10, 11, 12, 13
+PFACX_TABLE_PREFIX_PATTERN = 14
 
 
 class STATUS:
@@ -46,6 +47,7 @@ class STATUS:
     ARCH_MISMATCH = 10008
     MUTEX_ERROR = 10009
     INTERNAL_ERROR = 10010
+    OUTPUT_TRUNCATED = 10100     # pfac_ext.h: PFACX_STATUS_OUTPUT_TRUNCATED (PFACX_matchAll*)
 
 
 class PFACError(RuntimeError):
@@ -69,6 +71,7 @@ class PFACX_info(C.Structure):
         ("trailingBytesIgnored", C.c_size_t), ("deviceTableBytes", C.c_size_t), ("deviceScratchBytes", C.c_size_t),
         ("streamNearMisses", C.c_int), ("streamDense", C.c_int), ("filterLadderLast", C.c_int), ("filterTailEntries", C.c_size_t),
         ("filterTailGlobalEntries", C.c_size_t), ("filterLog2TailGlobal", C.c_int), ("filterLadderSalt", C.c_uint), ("filterSkipTags", C.c_int),
+        ("maxMatchesPerPosition", C.c_int),
     ]
 
 
@@ -93,11 +96,13 @@ EXPORTED_SYMBOLS = (
     "PFACX_matchFromHostMultiGPU", "PFACX_matchFromHostReduceMultiGPU", "PFACX_readPatternFromFileEx", "PFACX_readPatternFromMemoryEx", "PFACX_trim",
     "PFACX_setKernelTiming", "PFACX_setWalker", "PFACX_prepare",
     "PFACX_matchBatchFromDevice", "PFACX_matchBatchFromHost", "PFACX_matchBatchFromDeviceReduce",
+    "PFACX_matchAllFromDevice", "PFACX_matchAllFromHost", "PFACX_matchAllBatchFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
     "PFAC_reduce_kernel", "PFAC_reduce_inplace_kernel", "PFACX_streamProbe", "PFACX_buildInfo",
     "PFACX_batchFixup", "PFACX_batchReduceFixup",
+    "PFACX_allReduce", "PFACX_allExpand",
 )
 
 
@@ -156,6 +161,12 @@ def load_library() -> C.CDLL:
         lib.PFACX_matchBatchFromHost.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.PFACX_matchBatchFromDeviceReduce.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                          C.c_void_p, C.POINTER(C.c_int)]
+    if hasattr(lib, "PFACX_matchAllFromDevice"):
+        SZ = C.POINTER(C.c_size_t)
+        lib.PFACX_matchAllFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, SZ]
+        lib.PFACX_matchAllFromHost.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, SZ]
+        lib.PFACX_matchAllBatchFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                      C.c_size_t, C.c_void_p, SZ]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -365,6 +376,41 @@ class PFAC:
             self.matchBatchFromHost(data.ctypes.data, data.size, offs.ctypes.data, offs.size - 1, out.ctypes.data)
         return out
 
+    # -- every pattern at a position (include/pfac_ext.h: PFACX_matchAll*) ---------------
+    def matchAllFromDevice(self, d_input: int, size: int, d_ids: int, d_pos: int, capacity: int, check: bool = True):
+        """``PFACX_matchAllFromDevice`` -> (status, full length of the list).  OUTPUT_TRUNCATED is returned, not raised."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_matchAllFromDevice(self._h, d_input, size, d_ids, d_pos, capacity, C.byref(n))
+        return self._ret(st, "PFACX_matchAllFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def matchAllFromHost(self, h_input: int, size: int, h_ids: int, h_pos: int, capacity: int, check: bool = True):
+        """``PFACX_matchAllFromHost`` -> (status, full length of the list).  OUTPUT_TRUNCATED is returned, not raised."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_matchAllFromHost(self._h, h_input, size, h_ids, h_pos, capacity, C.byref(n))
+        return self._ret(st, "PFACX_matchAllFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def matchAllBatchFromDevice(self, d_input: int, size: int, d_offsets: int, num_segments: int, d_ids: int, d_pos: int, capacity: int,
+                                d_seg_first: int, check: bool = True):
+        """``PFACX_matchAllBatchFromDevice`` -> (status, full length); `d_seg_first` receives num_segments + 1 size_t."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_matchAllBatchFromDevice(self._h, d_input, size, d_offsets, num_segments, d_ids, d_pos, capacity, d_seg_first,
+                                                     C.byref(n))
+        return self._ret(st, "PFACX_matchAllBatchFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def match_all_host_array(self, data, capacity=None):
+        """matchAllFromHost over a numpy array -> (pos, ids) of every match, ascending position, longest first within one.
+        capacity=None: size * maxMatchesPerPosition (never truncates); a smaller capacity that truncates raises PFACError."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if data.size == 0:
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+        cap = data.size * max(1, int(self.info().maxMatchesPerPosition)) if capacity is None else int(capacity)
+        ids = np.full(cap, -7, dtype=np.int32)
+        pos = np.full(cap, -7, dtype=np.int32)
+        st, n = self.matchAllFromHost(data.ctypes.data, data.size, ids.ctypes.data, pos.ctypes.data, cap, check=False)
+        self._ret(st, "PFACX_matchAllFromHost", True)
+        return pos[:n].copy(), ids[:n].copy()
+
     # -- numpy conveniences over matchFromHost (still the C ABI underneath) ----------
     def match_host_array(self, data):
         import numpy as np
@@ -405,7 +451,7 @@ class PFAC:
         ptr = C.c_void_p()
         nbytes = C.c_size_t()
         self._ret(self._lib.PFACX_getTable(self._h, which, C.byref(ptr), C.byref(nbytes)), "PFACX_getTable", True)
-        dtype = np.uint32 if which >= PFACX_TABLE_FILTER_GRAM3 else np.int32
+        dtype = np.uint32 if which >= PFACX_TABLE_FILTER_GRAM3 and which != PFACX_TABLE_PREFIX_PATTERN else np.int32
         if nbytes.value == 0:
             return np.zeros(0, dtype=dtype)
         buf = (C.c_char * nbytes.value).from_address(ptr.value)

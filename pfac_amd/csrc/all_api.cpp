@@ -1,0 +1,170 @@
+/*
+ * all_api.cpp -- PFACX_matchAllFromDevice / ...FromHost / PFACX_matchAllBatchFromDevice (include/pfac_ext.h): every pattern that
+ * occurs at a position, not only the longest.
+ *
+ * Every pattern that starts at p is a prefix of the longest one that starts there, so the list is the longest-match list with each
+ * pair followed by its chain of prefix patterns (Automaton::prefixPattern).  The GPU forms run the unchanged compacted-output path
+ * with its ordered pairs in handle scratch (PFACX_allReduce), the batch fix-up of PFACX_matchBatchFromDeviceReduce where there are
+ * segments, and the expansion (scan_all.hip) into the caller's arrays.  The host form expands in place on the host.  A set in
+ * which no pattern is a prefix of another (maxChain == 1) needs no expansion: each call is its compacted counterpart.
+ */
+#include <hip/hip_runtime_api.h>
+
+#include <mutex>
+#include <shared_mutex>
+#include <vector>
+
+#include "pfac_host.h"
+
+namespace pfac_internal {
+
+/* the device copy of {prefixPattern, chainLen} by id that the expansion reads (uploaded on the first call that expands) */
+static PFAC_status_t ensureAllTable(PFAC_context *c)
+{
+    if (c->d_allTable) return PFAC_STATUS_SUCCESS;
+    std::vector<pfac::Int2> t(c->fa.prefixPattern.size());
+    for (size_t id = 0; id < t.size(); id++) t[id] = pfac::Int2{c->fa.prefixPattern[id], c->fa.chainLen[id]};
+    const PFAC_status_t st = upload(c->d_allTable, t.data(), t.size());
+    if (st == PFAC_STATUS_SUCCESS) c->allTableEntries = t.size();
+    return st;
+}
+
+/* room for the first longest pair of each segment (batch form) */
+static PFAC_status_t ensureAllSegFirst(PFAC_context *c, size_t entries)
+{
+    if (c->allSegFirstEntries >= entries) return PFAC_STATUS_SUCCESS;
+    devFree(c->d_allSegFirst);
+    c->allSegFirstEntries = 0;
+    if (hipMalloc(reinterpret_cast<void **>(&c->d_allSegFirst), entries * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        c->d_allSegFirst = nullptr;
+        return PFAC_STATUS_CUDA_ALLOC_FAILED;
+    }
+    c->allSegFirstEntries = entries;
+    return PFAC_STATUS_SUCCESS;
+}
+
+/* the GPU forms behind their argument checks (0 < size < 2^31, capacity >= size; d_offsets null: one segment, no d_segFirst) */
+static PFAC_status_t matchAllDeviceLocked(PFAC_context *c, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                                          int *d_ids, int *d_pos, size_t capacity, size_t *d_segFirst, size_t *h_num_matched)
+{
+    correctTextureMode(c);
+    const bool expand = c->fa.maxChain > 1;
+    PFAC_status_t st = PFAC_STATUS_SUCCESS;
+    if (d_offsets) st = ensurePatternLen(c);
+    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = ensureAllSegFirst(c, numSegments + 1);
+    if (st == PFAC_STATUS_SUCCESS && expand) st = ensureAllTable(c);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    int count = 0;
+    int *ids = d_ids, *pos = d_pos;
+    if (expand) {
+        st = c->all_reduce_ptr(c, reinterpret_cast<int *>(d_input), (int)size, d_ids, d_pos, &count, c->perfMode == PFAC_TIME_DRIVEN ? 0 : 1);
+        ids = c->d_allPairs;
+        pos = c->d_allPairs + c->allPairsEntries;
+    } else {
+        PFAC_reduce_kernel_protoType fn = c->perfMode == PFAC_TIME_DRIVEN ? c->reduce_kernel_ptr : c->reduce_inplace_kernel_ptr;
+        st = fn(c, reinterpret_cast<int *>(d_input), (int)size, d_ids, d_pos, &count, nullptr, nullptr);
+    }
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (d_offsets)
+        st = c->batch_reduce_fixup_ptr(c, d_input, size, d_offsets, numSegments, ids, pos, &count, c->d_allSegFirst, c->d_patternLen);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    size_t total = (size_t)count;
+    if (expand || d_offsets)
+        st = c->all_expand_ptr(c, ids, pos, (size_t)count, expand ? c->d_allTable : nullptr, d_ids, d_pos, capacity,
+                               d_offsets ? c->d_allSegFirst : nullptr, numSegments, d_segFirst, &total);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    *h_num_matched = total;
+    return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+}
+
+/* The `count` ordered longest pairs in ids / pos (room for `capacity` >= count) become the all-match list, in place: walked from
+ * the last pair to the first, pair i lands at offsets >= i, so no pair is overwritten before it has been read.  Returns the full
+ * length; slots >= capacity are not written. */
+static size_t expandOnHost(const pfac::Automaton &fa, int *ids, int *pos, size_t count, size_t capacity)
+{
+    auto chainOf = [&](int id) -> size_t { return id >= 1 && id <= fa.numPatterns && fa.chainLen[(size_t)id] > 0 ? (size_t)fa.chainLen[(size_t)id] : 1; };
+    size_t total = 0;
+    for (size_t i = 0; i < count; i++) total += chainOf(ids[i]);
+    if (fa.maxChain <= 1) return total;
+    size_t o = total;
+    for (size_t i = count; i-- > 0;) {
+        const int id = ids[i], p = pos[i];
+        const size_t c = chainOf(id);
+        o -= c;
+        int q = id;
+        for (size_t k = 0; k < c; k++) {
+            if (o + k < capacity) { ids[o + k] = q; pos[o + k] = p; }
+            q = q >= 1 && q <= fa.numPatterns ? fa.prefixPattern[(size_t)q] : 0;
+        }
+    }
+    return total;
+}
+
+} // namespace pfac_internal
+using namespace pfac_internal;
+
+extern "C" {
+
+PFAC_status_t PFACX_matchAllFromDevice(PFAC_handle_t handle, char *d_input, size_t size, int *d_ids, int *d_pos, size_t capacity,
+                                       size_t *h_num_matched)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
+    if (!d_input || !d_ids || !d_pos || !h_num_matched) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
+    if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
+    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
+    std::lock_guard<std::mutex> guard(handle->lock);
+    return matchAllDeviceLocked(handle, d_input, size, nullptr, 0, d_ids, d_pos, capacity, nullptr, h_num_matched);
+}
+
+PFAC_status_t PFACX_matchAllFromHost(PFAC_handle_t handle, char *h_input, size_t size, int *h_ids, int *h_pos, size_t capacity,
+                                     size_t *h_num_matched)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
+    if (!h_input || !h_ids || !h_pos || !h_num_matched) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
+    if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
+    size_t count = 0;
+    if (handle->platform != PFAC_PLATFORM_GPU) {
+        /* the longest match of every position into h_ids (it holds size entries), compacted in place as PFAC_matchFromHostReduce does */
+        const PFAC_status_t st = matchHostOnCpuPlatform(handle, h_input, size, h_ids);
+        if (st != PFAC_STATUS_SUCCESS) return st;
+        for (size_t i = 0; i < size; i++) {
+            const int m = h_ids[i];
+            if (m > 0) { h_ids[count] = m; h_pos[count] = (int)i; count++; }
+        }
+    } else {
+        if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+        std::lock_guard<std::mutex> guard(handle->lock);
+        int n = 0;
+        const PFAC_status_t st = matchHostReduceOnGpu(handle, h_input, size, size, 0, h_ids, h_pos, &n);
+        if (st != PFAC_STATUS_SUCCESS) return st;
+        count = (size_t)n;
+    }
+    std::shared_lock<std::shared_mutex> tables(handle->tablesInUse);
+    const size_t total = expandOnHost(handle->fa, h_ids, h_pos, count, capacity);
+    *h_num_matched = total;
+    return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t PFACX_matchAllBatchFromDevice(PFAC_handle_t handle, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                                            int *d_ids, int *d_pos, size_t capacity, size_t *d_segFirst, size_t *h_num_matched)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
+    if (!d_input || !d_offsets || !d_ids || !d_pos || !d_segFirst || !h_num_matched) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
+    if (numSegments == 0 || numSegments >= SIZE_MAX / sizeof(size_t)) return PFAC_STATUS_INVALID_PARAMETER;
+    if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
+    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
+    std::lock_guard<std::mutex> guard(handle->lock);
+    return matchAllDeviceLocked(handle, d_input, size, d_offsets, numSegments, d_ids, d_pos, capacity, d_segFirst, h_num_matched);
+}
+
+} /* extern "C" */

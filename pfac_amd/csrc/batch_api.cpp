@@ -29,7 +29,7 @@ static bool offsetsValid(const size_t *offsets, size_t numSegments, size_t size)
 }
 
 /* the device copy of the pattern lengths by id that the fix-up kernels read (uploaded on the first batch call) */
-static PFAC_status_t ensurePatternLen(PFAC_context *c)
+PFAC_status_t ensurePatternLen(PFAC_context *c)
 {
     if (c->d_patternLen) return PFAC_STATUS_SUCCESS;
     const PFAC_status_t st = upload(c->d_patternLen, c->fa.patternLen.data(), c->fa.patternLen.size());

@@ -237,6 +237,7 @@ PFAC_status_t PFACX_loadCompiled(PFAC_handle_t handle, const char *filename)
                 /* states the initial state does not reach must have no edges (state 0 is the unused one) */
                 for (size_t st = 0; ok && st < S; st++) ok = depth[st] >= 0 || fa.edgeBegin[st] == fa.edgeBegin[st + 1];
             }
+            if (ok) pfac::buildPrefixPatterns(fa);             /* the all-match tables are not in the file: derived from the checked trie */
         }
     } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
     if (!ok) return PFAC_STATUS_INVALID_PARAMETER;

@@ -208,7 +208,36 @@ PFAC_status_t compilePatternBytes(std::vector<unsigned char> bytes, Automaton &f
     for (int s = 1; s <= F; s++)
         if (trie.fanout(s) == 0) fa.numLeaves++;
     trie.flatten(fa.numStates, fa);
+    buildPrefixPatterns(fa);
     return PFAC_STATUS_SUCCESS;
+}
+
+/* The all-match tables (PFACX_matchAll*): every pattern that starts where the longest one L starts is a prefix of L, i.e. a
+ * final state on the trie path to L.  One depth-first pass from the initial state carries the last final state above each
+ * node and the number of final states on the path; states 1..F are the final ones (their ID is the pattern's). */
+void buildPrefixPatterns(Automaton &fa)
+{
+    const int F = fa.numPatterns;
+    fa.prefixPattern.assign((size_t)F + 1, 0);
+    fa.chainLen.assign((size_t)F + 1, 0);
+    fa.maxChain = 1;
+    if (F == 0 || fa.edgeBegin.empty()) return;
+    struct Frame { int state, above, depth; };
+    std::vector<Frame> stack;
+    stack.push_back(Frame{fa.initialState, 0, 0});
+    while (!stack.empty()) {
+        const Frame f = stack.back();
+        stack.pop_back();
+        int above = f.above, depth = f.depth;
+        if (f.state >= 1 && f.state <= F) {
+            fa.prefixPattern[(size_t)f.state] = above;
+            fa.chainLen[(size_t)f.state] = ++depth;
+            fa.maxChain = std::max(fa.maxChain, depth);
+            above = f.state;
+        }
+        for (int e = fa.edgeBegin[(size_t)f.state]; e < fa.edgeBegin[(size_t)f.state + 1]; e++)
+            stack.push_back(Frame{fa.edgeNext[(size_t)e], above, depth});
+    }
 }
 
 /* 256-entry transition row of the initial state: what the reference keeps in

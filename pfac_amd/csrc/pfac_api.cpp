@@ -86,6 +86,19 @@ void freeBatchScratch(PFAC_context *c)
     c->batchScratchBytes = 0;
 }
 
+/* what the all-match calls keep (pfac_context.h): the prefix table goes with the set, the rest is grow-only scratch */
+void freeAllScratch(PFAC_context *c)
+{
+    devFree(c->d_allTable);
+    c->allTableEntries = 0;
+    devFree(c->d_allPairs);
+    c->allPairsEntries = 0;
+    devFree(c->d_allSegFirst);
+    c->allSegFirstEntries = 0;
+    if (c->d_allScratch) { (void)hipFree(c->d_allScratch); c->d_allScratch = nullptr; }
+    c->allScratchBytes = 0;
+}
+
 /* ref PFAC_freeResource, PFAC.cpp:221-254 */
 void freeResources(PFAC_context *c)
 {
@@ -110,6 +123,7 @@ void freeResources(PFAC_context *c)
     devFree(c->d_denseList);
     c->denseListEntries = 0;
     freeBatchScratch(c);
+    freeAllScratch(c);
     for (auto &child : c->children) (void)PFAC_destroy(child.second);
     c->children.clear();
     c->fa = pfac::Automaton();
@@ -289,8 +303,10 @@ PFAC_status_t loadModule(PFAC_context *c)
     c->reduce_inplace_kernel_ptr = (PFAC_reduce_kernel_protoType)dlsym(m, "PFAC_reduce_inplace_kernel");
     c->batch_fixup_ptr = (PFACX_batchFixup_protoType)dlsym(m, "PFACX_batchFixup");
     c->batch_reduce_fixup_ptr = (PFACX_batchReduceFixup_protoType)dlsym(m, "PFACX_batchReduceFixup");
+    c->all_reduce_ptr = (PFACX_allReduce_protoType)dlsym(m, "PFACX_allReduce");
+    c->all_expand_ptr = (PFACX_allExpand_protoType)dlsym(m, "PFACX_allExpand");
     if (!c->kernel_time_driven_ptr || !c->kernel_space_driven_ptr || !c->reduce_kernel_ptr ||
-        !c->reduce_inplace_kernel_ptr || !c->batch_fixup_ptr || !c->batch_reduce_fixup_ptr)
+        !c->reduce_inplace_kernel_ptr || !c->batch_fixup_ptr || !c->batch_reduce_fixup_ptr || !c->all_reduce_ptr || !c->all_expand_ptr)
         return PFAC_STATUS_INTERNAL_ERROR;
     return PFAC_STATUS_SUCCESS;
 }
@@ -410,6 +426,8 @@ const char *PFAC_getErrorString(PFAC_status_t status)
 {
     if (status == PFAC_STATUS_SUCCESS) return "PFAC_STATUS_SUCCESS: operation is successful";
     if ((int)status < (int)PFAC_STATUS_BASE) return hipGetErrorString((hipError_t)status);
+    if (status == PFACX_STATUS_OUTPUT_TRUNCATED)           /* pfac_ext.h: PFACX_matchAll* */
+        return "PFACX_STATUS_OUTPUT_TRUNCATED: the list of matches is longer than the output arrays; the count is the full length";
     switch (status) {
     case PFAC_STATUS_ALLOC_FAILED: return "PFAC_STATUS_ALLOC_FAILED: allocation fails on host memory";
     case PFAC_STATUS_CUDA_ALLOC_FAILED: return "PFAC_STATUS_CUDA_ALLOC_FAILED: allocation fails on device memory";
@@ -593,6 +611,7 @@ PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info)
         v.initialState = handle->fa.initialState;
         v.maxPatternLen = handle->fa.maxPatternLen;
         v.numOfLeaves = handle->fa.numLeaves;
+        v.maxMatchesPerPosition = handle->fa.maxChain;
         v.perfMode = handle->perfMode;
         v.textureMode = handle->textureMode;
         v.platform = handle->platform;
@@ -642,11 +661,13 @@ PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info)
         v.deviceTableBytes = dev;
         /* ... and what its calls have left allocated (grow-only, PFACX_trim gives it back): the two staging pieces of the host
          * paths (input + ids + positions: 9 bytes per position), the scratch the compacted output is ordered through, the list
-         * of pattern-dense chunks, what the batch calls keep */
+         * of pattern-dense chunks, what the batch and all-match calls keep */
         size_t scratch = 0;
         if (handle->hostStagePositions) scratch += 2 * (((handle->hostStagePositions + 3) & ~size_t(3)) + 2 * handle->hostStagePositions * sizeof(int));
         scratch += handle->reduceScratchBytes + handle->denseListEntries * sizeof(unsigned int);
         scratch += handle->patternLenEntries * sizeof(int) + handle->batchOffsetsEntries * sizeof(size_t) + handle->batchScratchBytes;
+        scratch += handle->allTableEntries * sizeof(Int2) + handle->allPairsEntries * 2 * sizeof(int) + handle->allSegFirstEntries * sizeof(int) +
+                   handle->allScratchBytes;
         v.deviceScratchBytes = scratch;
         if (handle->h_modeHint) {
             v.streamNearMisses = (int)static_cast<volatile const unsigned int *>(handle->h_modeHint)[0];
@@ -695,6 +716,8 @@ PFAC_status_t PFACX_getTable(PFAC_handle_t handle, PFACX_table_t which, const vo
         *ptr = handle->filter.tailG.data(); *bytes = handle->filter.tailG.size() * sizeof(uint32_t); break;
     case PFACX_TABLE_FILTER_SKIP:
         *ptr = handle->filter.skipTags; *bytes = (size_t)handle->filter.skipCount * sizeof(uint32_t); break;
+    case PFACX_TABLE_PREFIX_PATTERN:
+        *ptr = handle->fa.prefixPattern.data(); *bytes = handle->fa.prefixPattern.size() * sizeof(int); break;
     case PFACX_TABLE_CHAIN: {
         if (handle->h_chainSlots.empty()) {
             const PFAC_status_t st = uploadChainedHashTable(handle);      /* host-only handle: builds, uploads nothing */
@@ -715,7 +738,8 @@ PFAC_status_t PFACX_getTable(PFAC_handle_t handle, PFACX_table_t which, const vo
 extern "C" {
 
 /* pfac_ext.h: give back the grow-only device buffers of the handle (staging of PFAC_matchFromHost, copies of
- * PFAC_matchFromHostReduce, sort scratch, the dense-chunk list, what the batch calls keep); the next call that needs one allocates it again */
+ * PFAC_matchFromHostReduce, sort scratch, the dense-chunk list, what the batch and all-match calls keep); the next call that needs one allocates
+ * it again */
 PFAC_status_t PFACX_trim(PFAC_handle_t handle)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
@@ -727,6 +751,7 @@ PFAC_status_t PFACX_trim(PFAC_handle_t handle)
     devFree(handle->d_denseList);
     handle->denseListEntries = 0;
     freeBatchScratch(handle);
+    freeAllScratch(handle);
     for (auto &child : handle->children) if (child.second) (void)PFACX_trim(child.second);
     return PFAC_STATUS_SUCCESS;
 }

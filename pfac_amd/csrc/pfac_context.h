@@ -47,6 +47,8 @@ constexpr int kModeVotesWord = 36 * 32;
 constexpr int kTiledDenseWord = 37 * 32;         /* tiled kernel scanning a whole big call: groups it walked in dense mode, groups in all, waves that are through (three words);
                                                     the last wave out tells the host whether the stream is pattern-dense (hostHint[1]) and leaves them zero */
 constexpr int kHostPairCountWord = 4;             /* word of the handle's mapped host memory (h_modeHint) the first ordering launch (pfac_order_count) writes the number of pairs of a compacted-output call to */
+constexpr int kHostAllTotalWord = 8;              /* words 8-9 of h_modeHint: the 64-bit length of an all-match call's list (scan_all.hip: pfac_all_block_scan) ... */
+constexpr int kHostAllDoneWord = 10;              /* ... and the sequence number its last launch writes (pfac_all_done) */
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -110,6 +112,13 @@ struct Automaton {
     std::vector<int> edgeBegin;               /* [numStates+1]                                   */
     std::vector<unsigned char> edgeCh;
     std::vector<int> edgeNext;
+    /* all-match tables (PFACX_matchAll*), derived from the trie (buildPrefixPatterns), never stored in a compiled file:
+     * prefixPattern[id] = the longest pattern that is a proper prefix of pattern id (0: none), chainLen[id] = patterns that
+     * start where id starts and are prefixes of it, id included; both [F+1] by ID, 0 for IDs the trie does not hold (the
+     * lower IDs of duplicate lines).  maxChain = the largest chainLen (1 for an empty set): PFACX_info_t::maxMatchesPerPosition */
+    std::vector<int> prefixPattern;
+    std::vector<int> chainLen;
+    int maxChain = 1;
 };
 
 /* Prefilter.  Level 1, tested for every input position: a start position can only produce a
@@ -343,6 +352,8 @@ struct PFAC_context {
     PFAC_reduce_kernel_protoType reduce_inplace_kernel_ptr = nullptr;
     PFACX_batchFixup_protoType batch_fixup_ptr = nullptr;              /* scan_batch.hip: the batch calls (PFACX_matchBatch*) */
     PFACX_batchReduceFixup_protoType batch_reduce_fixup_ptr = nullptr;
+    PFACX_allReduce_protoType all_reduce_ptr = nullptr;               /* scan_module.hip / scan_all.hip: the all-match calls (PFACX_matchAll*) */
+    PFACX_allExpand_protoType all_expand_ptr = nullptr;
 
     int platform = PFAC_PLATFORM_GPU;
     int perfMode = PFAC_TIME_DRIVEN;
@@ -371,6 +382,19 @@ struct PFAC_context {
     size_t batchOffsetsEntries = 0;
     void *d_batchScratch = nullptr;
     size_t batchScratchBytes = 0;
+    /* the all-match calls (PFACX_matchAll*): device copy of {fa.prefixPattern, fa.chainLen} by id (uploaded on the first call that
+     * expands), the ordered longest pairs (ids, then positions; the ordering of PFACX_allReduce writes them, scan_module.hip), the
+     * first longest pair of each segment (batch form), the expansion's scratch (scan_all.hip).  Grow-only scratch: PFACX_trim frees
+     * them, deviceScratchBytes counts them */
+    pfac::Int2 *d_allTable = nullptr;
+    size_t allTableEntries = 0;
+    int *d_allPairs = nullptr;
+    size_t allPairsEntries = 0;
+    int *d_allSegFirst = nullptr;
+    size_t allSegFirstEntries = 0;
+    void *d_allScratch = nullptr;
+    size_t allScratchBytes = 0;
+    unsigned int allSeq = 0;                  /* number of the last expansion (pfac_all_done writes it to host memory) */
 
     bool hasDevice = false;
     int device = -1;

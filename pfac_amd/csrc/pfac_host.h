@@ -12,6 +12,7 @@ namespace pfac {
 PFAC_status_t compilePatternFile(const char *filename, Automaton &fa, unsigned int flags = 0);
 PFAC_status_t compilePatternBytes(std::vector<unsigned char> bytes, Automaton &fa, unsigned int flags = 0);   /* flags: PFACX_READ_* */
 void buildInitialRow(const Automaton &fa, std::vector<int> &row);
+void buildPrefixPatterns(Automaton &fa);                    /* fa.prefixPattern / chainLen / maxChain from the trie */
 void buildFilter(const Automaton &fa, Filter &f);
 void buildReduceFilter(const Automaton &fa, Filter &f);     /* gram1 + prefix4 alone (buildFilter calls it; a compiled set is loaded without them) */
 
@@ -62,6 +63,7 @@ void freeTables(PFAC_context *c);
 void freeHostStage(PFAC_context *c);
 void freeResources(PFAC_context *c);
 void freeBatchScratch(PFAC_context *c);
+void freeAllScratch(PFAC_context *c);
 PFAC_status_t bindTable(PFAC_context *c);
 PFAC_status_t bindCommon(PFAC_context *c, bool build = true);
 void correctTextureMode(PFAC_context *c);
@@ -74,6 +76,7 @@ PFAC_status_t matchDeviceLocked(PFAC_context *c, char *d_inputString, size_t siz
 PFAC_status_t matchHostOnGpu(PFAC_context *c, char *h_inputString, size_t owned, size_t readable, int *h_matched_result);
 PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t size, size_t readable, size_t posBase, int *h_matched_result, int *h_pos, int *h_num_matched);
 /* batch_api.cpp: the batch calls (PFACX_matchBatch*) behind their argument checks; the caller holds c->lock */
+PFAC_status_t ensurePatternLen(PFAC_context *c);            /* the device copy of fa.patternLen the batch fix-ups read */
 PFAC_status_t matchBatchDeviceLocked(PFAC_context *c, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments, int *d_matched_result);
 /* host_pipeline.cpp: PFACX_matchBatchFromHost on the GPU platform (h_offsets validated); the caller holds c->lock */
 PFAC_status_t matchBatchHostOnGpu(PFAC_context *c, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments, int *h_matched_result);

@@ -1,0 +1,277 @@
+/*
+ * scan_all.hip -- all matches (include/pfac_ext.h: PFACX_matchAll*): the expansion of the ordered list of longest matches into
+ * the list of every (position, pattern) pair (DESIGN.md "all matches").
+ *
+ * Every pattern P that starts at p is a prefix of the longest one L that starts there (both match the bytes at p, P is not
+ * longer), so P is a final state on the trie path to L.  The host derives per pattern id the longest proper prefix pattern
+ * and the length of that chain (pattern_compiler.cpp: buildPrefixPatterns); the pairs at p are L, prefix(L), prefix(prefix(L)),
+ * ... -- longest first.  The longest-match scan is the unchanged compacted-output path (scan_module.hip: PFACX_allReduce, whose
+ * ordering writes the ordered pairs into the handle's scratch); behind it, on the default stream:
+ *   pfac_all_count       blocks own consecutive ranges of the longest pairs; each lane reads chainLen[id] (a table of 8 bytes
+ *                        per id: L2 resident for any real set), the block's total goes to blockBase[block]
+ *   pfac_all_block_scan  exclusive scan of the block totals (one block; 64-bit), the grand total to mapped host memory
+ *   pfac_all_scatter     the block's range again: lane prefix of the chain lengths, then each lane writes its pair and follows
+ *                        prefixPattern into consecutive slots; slots >= capacity are skipped (the caller learns the full count)
+ *   pfac_all_seg_first   batch form: one lane per segment boundary, the expanded offset of the first longest pair of the segment
+ *   pfac_all_done        writes the call's sequence number to mapped host memory (the host polls it instead of a stream sync)
+ * Writes are plain vector stores; no kernel of the other units is touched.
+ */
+#if !defined(__gfx950__) && defined(__HIP_DEVICE_COMPILE__)
+#error "scan_all.hip is written for gfx950 (CDNA4): wave64"
+#endif
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstdint>
+
+#include "pfac_context.h"
+
+namespace {
+
+constexpr int kAllBlock = 256;
+
+struct ExpandArgs {
+    const int *pairIds;                 /* the ordered longest pairs */
+    const int *pairPos;
+    size_t count;
+    const pfac::Int2 *table;            /* [numIds + 1] {prefixPattern, chainLen} by id */
+    int numIds;
+    size_t per;                         /* longest pairs per block: a multiple of kAllBlock */
+    unsigned long long *blockBase;      /* [blocks + 1]: block totals -> their exclusive prefix; [blocks] = the grand total */
+    unsigned int blocks;
+    int *ids;                           /* the caller's arrays: capacity entries each */
+    int *pos;
+    size_t capacity;
+    unsigned long long *pairOffset;     /* batch form: the expanded offset of every longest pair (else null) */
+};
+
+/* an id the scan cannot report (outside [1, numIds]) stands for itself alone */
+__device__ __forceinline__ unsigned int chainOf(const ExpandArgs &x, int id)
+{
+    if (id < 1 || id > x.numIds) return 1u;
+    const int c = x.table[id].y;
+    return c > 0 ? (unsigned int)c : 1u;
+}
+
+/* exclusive prefix of `own` over the block's 256 threads, and the block's total (every thread gets it) */
+__device__ __forceinline__ unsigned long long blockExclusive(unsigned long long own, unsigned long long *waveSum, unsigned long long &total)
+{
+    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned long long incl = own;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long up = __shfl_up(incl, d);
+        if ((int)lane >= d) incl += up;
+    }
+    __syncthreads();                                    /* waveSum may still be read from the previous step */
+    if (lane == 63) waveSum[wave] = incl;
+    __syncthreads();
+    unsigned long long before = 0;
+    total = 0;
+    for (unsigned int w = 0; w < kAllBlock / 64; w++) {
+        if (w < wave) before += waveSum[w];
+        total += waveSum[w];
+    }
+    return before + incl - own;
+}
+
+__global__ __launch_bounds__(kAllBlock) void pfac_all_count(ExpandArgs x)
+{
+    __shared__ unsigned long long waveSum[kAllBlock / 64];
+    const size_t first = (size_t)blockIdx.x * x.per;
+    const size_t end = x.count - first < x.per ? x.count : first + x.per;
+    unsigned long long own = 0;
+    for (size_t i = first + threadIdx.x; i < end; i += kAllBlock) own += chainOf(x, x.pairIds[i]);
+    unsigned long long total = 0;
+    (void)blockExclusive(own, waveSum, total);
+    if (threadIdx.x == 0) x.blockBase[blockIdx.x] = total;
+}
+
+/* exclusive prefix sum of blockBase[0, blocks) in place, blockBase[blocks] = the total (also to *hostTotal when given):
+ * one block of 1024 threads walks it 1024 entries at a time */
+__global__ __launch_bounds__(1024) void pfac_all_block_scan(unsigned long long *v, unsigned int n, unsigned long long *hostTotal)
+{
+    __shared__ unsigned long long waveSum[16];
+    __shared__ unsigned long long carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (unsigned int base = 0; base < n; base += 1024) {
+        const unsigned int i = base + threadIdx.x;
+        const unsigned long long x = i < n ? v[i] : 0ull;
+        unsigned long long incl = x;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long up = __shfl_up(incl, d);
+            if ((int)lane >= d) incl += up;
+        }
+        if (lane == 63) waveSum[wave] = incl;
+        __syncthreads();
+        unsigned long long before = carry;
+        for (unsigned int w = 0; w < wave; w++) before += waveSum[w];
+        if (i < n) v[i] = before + incl - x;
+        __syncthreads();
+        if (threadIdx.x == 1023) carry = before + incl;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        v[n] = carry;
+        if (hostTotal != nullptr) {
+            __hip_atomic_store(hostTotal, carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __threadfence_system();
+        }
+    }
+}
+
+__global__ __launch_bounds__(kAllBlock) void pfac_all_scatter(ExpandArgs x)
+{
+    __shared__ unsigned long long waveSum[kAllBlock / 64];
+    const size_t first = (size_t)blockIdx.x * x.per;
+    const size_t end = x.count - first < x.per ? x.count : first + x.per;
+    unsigned long long base = x.blockBase[blockIdx.x];
+    for (size_t i0 = first; i0 < end; i0 += kAllBlock) {        /* the same trip count for every thread of the block */
+        const size_t i = i0 + threadIdx.x;
+        const bool has = i < end;
+        const int id = has ? x.pairIds[i] : 0;
+        const int p = has ? x.pairPos[i] : 0;
+        const unsigned int c = has ? chainOf(x, id) : 0u;
+        unsigned long long stepTotal = 0;
+        const unsigned long long o = base + blockExclusive(c, waveSum, stepTotal);
+        base += stepTotal;
+        if (!has) continue;
+        if (x.pairOffset != nullptr) x.pairOffset[i] = o;
+        int q = id;
+        for (unsigned int k = 0; k < c; k++) {
+            if (o + k < x.capacity) {
+                x.ids[o + k] = q;
+                x.pos[o + k] = p;
+            }
+            q = q >= 1 && q <= x.numIds ? x.table[q].x : 0;
+        }
+    }
+}
+
+/* segFirst[k] for k in [0, numSegments]: first[k] (the first longest pair of segment k; clamped to count) through the expansion:
+ * pairOffset[first[k]], or the total behind the last pair.  Without an expansion (no pairOffset: every chain has length 1) the
+ * index is the same in both lists. */
+__global__ __launch_bounds__(kAllBlock) void pfac_all_seg_first(const int *first, size_t numSegments, size_t count,
+                                                               const unsigned long long *pairOffset, const unsigned long long *total,
+                                                               size_t *segFirst)
+{
+    const size_t stride = (size_t)gridDim.x * kAllBlock;
+    for (size_t k = (size_t)blockIdx.x * kAllBlock + threadIdx.x; k <= numSegments; k += stride) {
+        const int f = first[k];
+        const size_t j = f < 0 ? 0 : ((size_t)f < count ? (size_t)f : count);
+        if (pairOffset == nullptr) segFirst[k] = j;
+        else segFirst[k] = j < count ? (size_t)pairOffset[j] : (size_t)*total;
+    }
+}
+
+/* queued behind the last launch of a call: tells the host, which polls the word, that the call's launches are through */
+__global__ void pfac_all_done(unsigned int *hostDone, unsigned int seq)
+{
+    __hip_atomic_store(hostDone, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+unsigned int gridCap(const PFAC_context *c) { return (unsigned int)(c->multiProcessorCount > 0 ? c->multiProcessorCount : 256) * 8u; }
+
+/* grow-only scratch of the expansion: the block totals, then (batch form) the expanded offset of every longest pair */
+void *allScratch(PFAC_context *c, size_t bytes)
+{
+    if (c->allScratchBytes >= bytes) return c->d_allScratch;
+    if (c->d_allScratch) (void)hipFree(c->d_allScratch);
+    c->d_allScratch = nullptr;
+    c->allScratchBytes = 0;
+    const size_t grow = bytes + bytes / 2;
+    if (hipMalloc(&c->d_allScratch, grow) != hipSuccess) {
+        (void)hipGetLastError();
+        c->d_allScratch = nullptr;
+        return nullptr;
+    }
+    c->allScratchBytes = grow;
+    return c->d_allScratch;
+}
+
+/* the host waits for pfac_all_done (polled for a while, then a stream sync) */
+bool waitDone(PFAC_context *c, unsigned int seq)
+{
+    volatile unsigned int *hostDone = c->h_modeHint + pfac::kHostAllDoneWord;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned int spins = 0; __atomic_load_n(const_cast<unsigned int *>(hostDone), __ATOMIC_ACQUIRE) != seq; spins++) {
+        if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20))
+            return hipStreamSynchronize(0) == hipSuccess;
+#if defined(__x86_64__) || defined(__i386__)
+        __builtin_ia32_pause();
+#endif
+    }
+    return true;
+}
+
+} // namespace
+
+extern "C" {
+
+PFAC_status_t PFACX_allExpand(PFAC_handle_t handle, const int *d_pairIds, const int *d_pairPos, size_t count, const void *d_table,
+                              int *d_ids, int *d_pos, size_t capacity, const int *d_segFirstPairs, size_t numSegments, size_t *d_segFirst,
+                              size_t *h_total)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!h_total || (count && d_table && (!d_pairIds || !d_pairPos || !d_ids || !d_pos)) || (d_segFirst && !d_segFirstPairs))
+        return PFAC_STATUS_INVALID_PARAMETER;
+    PFAC_context *c = handle;
+    if (!d_table) {                                    /* chains of length 1: the list is the longest list, only segFirst changes type */
+        if (d_segFirst) {
+            const size_t lanes = numSegments + 1, b = (lanes + kAllBlock - 1) / kAllBlock;
+            const unsigned int grid = b < gridCap(c) ? (unsigned int)b : gridCap(c);
+            hipLaunchKernelGGL(pfac_all_seg_first, dim3(grid), dim3(kAllBlock), 0, 0, d_segFirstPairs, numSegments, count,
+                               (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, d_segFirst);
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(0) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+        }
+        *h_total = count;
+        return PFAC_STATUS_SUCCESS;
+    }
+    ExpandArgs x{};
+    x.pairIds = d_pairIds;
+    x.pairPos = d_pairPos;
+    x.count = count;
+    x.table = static_cast<const pfac::Int2 *>(d_table);
+    x.numIds = c->fa.numPatterns;
+    x.ids = d_ids;
+    x.pos = d_pos;
+    x.capacity = capacity;
+    size_t blocks = (count + kAllBlock - 1) / kAllBlock;
+    if (blocks > gridCap(c)) blocks = gridCap(c);
+    x.per = blocks ? ((count + blocks - 1) / blocks + kAllBlock - 1) / kAllBlock * kAllBlock : kAllBlock;
+    blocks = (count + x.per - 1) / x.per;
+    x.blocks = (unsigned int)blocks;
+    const size_t baseBytes = ((blocks + 1) * sizeof(unsigned long long) + 255) & ~size_t(255);
+    char *s = static_cast<char *>(allScratch(c, baseBytes + (d_segFirst ? count * sizeof(unsigned long long) : 0)));
+    if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
+    x.blockBase = reinterpret_cast<unsigned long long *>(s);
+    x.pairOffset = d_segFirst ? reinterpret_cast<unsigned long long *>(s + baseBytes) : nullptr;
+    const bool mapped = c->h_modeHint != nullptr && c->d_modeHint != nullptr;
+    unsigned long long *hostTotal = mapped ? reinterpret_cast<unsigned long long *>(c->d_modeHint + pfac::kHostAllTotalWord) : nullptr;
+    if (blocks) hipLaunchKernelGGL(pfac_all_count, dim3((unsigned int)blocks), dim3(kAllBlock), 0, 0, x);
+    hipLaunchKernelGGL(pfac_all_block_scan, dim3(1), dim3(1024), 0, 0, x.blockBase, (unsigned int)blocks, hostTotal);
+    if (blocks) hipLaunchKernelGGL(pfac_all_scatter, dim3((unsigned int)blocks), dim3(kAllBlock), 0, 0, x);
+    if (d_segFirst) {
+        const size_t lanes = numSegments + 1, b = (lanes + kAllBlock - 1) / kAllBlock;
+        const unsigned int grid = b < gridCap(c) ? (unsigned int)b : gridCap(c);
+        hipLaunchKernelGGL(pfac_all_seg_first, dim3(grid), dim3(kAllBlock), 0, 0, d_segFirstPairs, numSegments, count, x.pairOffset,
+                           x.blockBase + blocks, d_segFirst);
+    }
+    unsigned long long total = 0;
+    if (mapped) {
+        c->allSeq = c->allSeq + 1u ? c->allSeq + 1u : 1u;
+        hipLaunchKernelGGL(pfac_all_done, dim3(1), dim3(1), 0, 0, c->d_modeHint + pfac::kHostAllDoneWord, c->allSeq);
+        if (hipGetLastError() != hipSuccess || !waitDone(c, c->allSeq)) return PFAC_STATUS_INTERNAL_ERROR;
+        total = __atomic_load_n(reinterpret_cast<unsigned long long *>(c->h_modeHint + pfac::kHostAllTotalWord), __ATOMIC_ACQUIRE);
+    } else if (hipGetLastError() != hipSuccess ||
+               hipMemcpy(&total, x.blockBase + blocks, sizeof(total), hipMemcpyDeviceToHost) != hipSuccess) {
+        return PFAC_STATUS_INTERNAL_ERROR;
+    }
+    *h_total = (size_t)total;
+    return PFAC_STATUS_SUCCESS;
+}
+
+} /* extern "C" */

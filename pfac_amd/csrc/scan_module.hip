@@ -337,8 +337,29 @@ PFAC_status_t scan(PFAC_handle_t handle, char *d_input_string, size_t input_size
  * The reference needs a block-local compaction, a Thrust scan and a second gather kernel
  * (PFAC_reduce_kernel.cu:417-457) because it has no prefilter: every thread owns a result.
  */
+/* the all-match calls (PFACX_allReduce): the ordering's rank pass writes the ordered pairs into the handle's grow-only scratch
+ * PFAC_context::d_allPairs (room for as many pairs as the ordering scratch: it holds them all whenever the ordering runs) */
+PFAC_status_t orderIntoAllPairs(PFAC_context *mc, PairOrder &order)
+{
+    const size_t entries = order.o.capacity;
+    if (mc->allPairsEntries < entries) {
+        if (mc->d_allPairs) (void)hipFree(mc->d_allPairs);
+        mc->d_allPairs = nullptr;
+        mc->allPairsEntries = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&mc->d_allPairs), 2 * entries * sizeof(int)) != hipSuccess) {
+            (void)hipGetLastError();
+            mc->d_allPairs = nullptr;
+            return PFAC_STATUS_CUDA_ALLOC_FAILED;
+        }
+        mc->allPairsEntries = entries;
+    }
+    order.o.idOut = mc->d_allPairs;
+    order.o.posOut = reinterpret_cast<unsigned int *>(mc->d_allPairs + mc->allPairsEntries);
+    return PFAC_STATUS_SUCCESS;
+}
+
 PFAC_status_t reduceScan(PFAC_handle_t handle, int *d_input_string, int input_size, int *d_match_result, int *d_pos,
-                         int *h_num_matched, int *h_match_result, int *h_pos, bool hashed)
+                         int *h_num_matched, int *h_match_result, int *h_pos, bool hashed, bool intoAll = false)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
     if (!d_input_string || !d_match_result || !d_pos || !h_num_matched || input_size <= 0) return PFAC_STATUS_INVALID_PARAMETER;
@@ -348,7 +369,7 @@ PFAC_status_t reduceScan(PFAC_handle_t handle, int *d_input_string, int input_si
     PFAC_status_t st = fillArgs(c, hashed, reinterpret_cast<const char *>(d_input_string), n, d_match_result, a);
     if (st != PFAC_STATUS_SUCCESS) return st;
     const bool tex = (c->textureMode == PFAC_TEXTURE_ON);
-    const bool ordered = !c->reduceUnordered;              /* PFAC_matchFromHost scatters the pairs: any order */
+    const bool ordered = intoAll || !c->reduceUnordered;   /* PFAC_matchFromHost scatters the pairs: any order */
 
     /* the handle's scratch: the counters of this call (pairs, pairs per position bin), room to order the pairs through */
 #ifndef PFAC_REDUCE_TRACE
@@ -362,6 +383,7 @@ PFAC_status_t reduceScan(PFAC_handle_t handle, int *d_input_string, int input_si
     PairOrder order;
     const size_t expected = n / 128 > 65536 ? n / 128 : 65536;       /* room for one match per 128 bytes before the first call has been seen */
     st = order.plan(handle, n, expected, d_match_result, d_pos, handle->orderParity);
+    if (st == PFAC_STATUS_SUCCESS && intoAll) st = orderIntoAllPairs(handle, order);
     if (st != PFAC_STATUS_SUCCESS) return st;
     /* an ordered call cleans up behind itself (scan_order.inc) and hands the number of pairs over in mapped host memory: no memset in
      * front of the scan when the previous call has left this very layout clean, no device-to-host copy behind the last launch */
@@ -434,6 +456,7 @@ PFAC_status_t reduceScan(PFAC_handle_t handle, int *d_input_string, int input_si
     if (count > (unsigned int)input_size) return PFAC_STATUS_INTERNAL_ERROR;
     if (ordered && count > order.o.capacity) {             /* more pairs than the scratch held: the launches left at once */
         st = order.plan(handle, n, count, d_match_result, d_pos, handle->orderParity);
+        if (st == PFAC_STATUS_SUCCESS && intoAll) st = orderIntoAllPairs(handle, order);
         if (st != PFAC_STATUS_SUCCESS) return st;
         if (order.clearCounters() != hipSuccess || hipMemcpyAsync(order.o.count, &count, sizeof(count), hipMemcpyHostToDevice, 0) != hipSuccess ||
             order.order(c) != hipSuccess || hipStreamSynchronize(0) != hipSuccess)      /* `count` is read by that copy */
@@ -529,6 +552,13 @@ PFAC_status_t PFAC_reduce_inplace_kernel(PFAC_handle_t handle, int *d_input_stri
                                          int *d_pos, int *h_num_matched, int *h_match_result, int *h_pos)
 {
     return reduceScan(handle, d_input_string, input_size, d_match_result, d_pos, h_num_matched, h_match_result, h_pos, true);
+}
+
+/* pfac_module.h: the compacted output with its ordered pairs in the handle's all-match scratch (scan_all.hip expands them) */
+PFAC_status_t PFACX_allReduce(PFAC_handle_t handle, int *d_input_string, int input_size, int *d_match_result, int *d_pos,
+                              int *h_num_matched, int hashed)
+{
+    return reduceScan(handle, d_input_string, input_size, d_match_result, d_pos, h_num_matched, nullptr, nullptr, hashed != 0, true);
 }
 
 } /* extern "C" */

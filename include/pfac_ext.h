@@ -37,9 +37,21 @@ PFAC_status_t PFACX_readPatternFromMemory(PFAC_handle_t handle, const char *patt
  *                        (trailingBytesIgnored).
  *   PFACX_READ_STRIP_CR  "\r\n" line ends: the '\r' is not part of the pattern (the reference keeps it: user guide r1.2
  *                        p.15 item 5).  A '\r' elsewhere in a line stays.
- * flags == 0 is exactly PFAC_readPatternFromFile / PFACX_readPatternFromMemory. */
+ *   PFACX_READ_NOCASE    a caseless set (Snort's nocase, grep -iF).  ASCII fold: bytes 0x41-0x5A ('A'-'Z') map to 0x61-0x7A;
+ *                        every other byte is unchanged (no locale, no Latin-1, no UTF-8).
+ *                        A set read with this flag is exactly the set read, without it, from the pattern bytes with the ASCII
+ *                        fold applied (after PFACX_READ_STRIP_CR): pattern IDs, tables, dumps and PFACX_getInfo (but for
+ *                        caseInsensitive) are those of the folded bytes.  Every match call on such a handle returns exactly
+ *                        what the same call returns on that folded set over the input with the ASCII fold applied; the
+ *                        caller's input buffer, host or device, is never modified.  Patterns that become equal when folded
+ *                        are duplicate lines: reported under the highest of their IDs, listed once by PFACX_matchAll*.
+ *                        Reading a set without the flag makes the handle case-sensitive again.  The device calls fold into a
+ *                        grow-only handle scratch of `size` bytes (deviceScratchBytes; PFACX_trim frees it).
+ * flags == 0 is exactly PFAC_readPatternFromFile / PFACX_readPatternFromMemory.  Bit 4 is not assigned and is refused as
+ * before, like every other unknown bit. */
 #define PFACX_READ_STRICT   1u
 #define PFACX_READ_STRIP_CR 2u
+#define PFACX_READ_NOCASE   8u
 PFAC_status_t PFACX_readPatternFromFileEx(PFAC_handle_t handle, const char *filename, unsigned int flags);
 PFAC_status_t PFACX_readPatternFromMemoryEx(PFAC_handle_t handle, const char *patterns, size_t size, unsigned int flags);
 
@@ -80,7 +92,8 @@ typedef struct {
     size_t deviceScratchBytes; /* device memory the handle's calls have left allocated (grow-only; PFACX_trim frees it): the two staging
                                  pieces of PFAC_matchFromHost / ...Reduce (9 bytes per position of a piece), the ordering scratch of the
                                  compacted output, the list of pattern-dense chunks, what the batch calls keep (pattern lengths, offsets of a
-                                 host piece, the compaction scratch of the compacted form) */
+                                 host piece, the compaction scratch of the compacted form), the folded input of a caseless set's device
+                                 calls (PFACX_READ_NOCASE) */
     int streamNearMisses;      /* what the handle's last big full-result launch said about its stream (host memory the launch's last block
                                  writes; nothing is waited for): 1 = full of near misses of long patterns -> PFACX_WALKER_AUTO picks STAGE ... */
     int streamDense;           /* ... 1 = most of it pattern-dense (short patterns over text, runs of a pattern byte) -> PFACX_KERNEL_AUTO
@@ -94,6 +107,7 @@ typedef struct {
     int filterSkipTags;        /* skip tags of the prefix ladder (PFACX_TABLE_FILTER_SKIP): depth-6 nodes with a single path down to depth 20 (at most 8) */
     int maxMatchesPerPosition; /* the most patterns that can start at one position: the longest PFACX_TABLE_PREFIX_PATTERN chain plus one (1 when
                                   no pattern is a prefix of another).  PFACX_matchAll* with capacity = size * maxMatchesPerPosition never truncates */
+    int caseInsensitive;       /* 1: the set was read with PFACX_READ_NOCASE (or loaded from a caseless compiled file): every match call folds its input */
 } PFACX_info_t;
 
 PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info);
@@ -173,7 +187,9 @@ PFAC_status_t PFACX_setKernelVariant(PFAC_handle_t handle, int variant);
  * file -- trie, hashed / chained tables, prefilter bitmaps -- with a version + layout fingerprint + checksum
  * header.  PFACX_loadCompiled replaces the handle's pattern set like PFAC_readPatternFromFile does (and sets the
  * perf mode the set was saved with); a file of another build or a damaged one is PFAC_STATUS_INVALID_PARAMETER,
- * a missing one PFAC_STATUS_FILE_OPEN_ERROR.  Works on host-only handles too. */
+ * a missing one PFAC_STATUS_FILE_OPEN_ERROR.  Works on host-only handles too.  A caseless set (PFACX_READ_NOCASE)
+ * is written as format version 8 and loads as caseless; a case-sensitive one keeps version 7.  A build that knows
+ * only version 7 refuses a caseless file instead of loading it as case-sensitive. */
 PFAC_status_t PFACX_saveCompiled(PFAC_handle_t handle, const char *filename);
 PFAC_status_t PFACX_loadCompiled(PFAC_handle_t handle, const char *filename);
 

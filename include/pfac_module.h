@@ -80,6 +80,12 @@ typedef PFAC_status_t (*PFACX_allReduce_protoType)(PFAC_handle_t, int *, int, in
 typedef PFAC_status_t (*PFACX_allExpand_protoType)(PFAC_handle_t, const int *, const int *, size_t, const void *, int *, int *, size_t,
                                                    const int *, size_t, size_t *, size_t *);
 
+/* Caseless pattern sets (no reference counterpart; include/pfac_ext.h: PFACX_READ_NOCASE), scan_fold.hip: the ASCII fold of n bytes
+ * of src into dst ('A'-'Z' -> 'a'-'z', every other byte unchanged), any alignment and length, in place (src == dst) or into a buffer
+ * that does not overlap src.  Asynchronous, on the default stream: the scan behind it reads dst in stream order. */
+PFAC_status_t PFACX_foldInput(PFAC_handle_t handle, const char *src, char *dst, size_t n);
+typedef PFAC_status_t (*PFACX_foldInput_protoType)(PFAC_handle_t, const char *, char *, size_t);
+
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of
  * `launches` launches over the first n bytes (a multiple of 4096) of d_in, or a negative value on a HIP error.

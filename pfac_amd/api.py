@@ -26,7 +26,7 @@ PFAC_TIME_DRIVEN, PFAC_SPACE_DRIVEN = 0, 1
 
 PFACX_KERNEL_FILTER, PFACX_KERNEL_NAIVE, PFACX_KERNEL_AUTO, PFACX_KERNEL_REFTABLE = 0, 1, 2, 3
 PFACX_WALKER_AUTO, PFACX_WALKER_WINDOW, PFACX_WALKER_STAGE, PFACX_WALKER_VETO = 0, 1, 2, 3
-PFACX_READ_STRICT, PFACX_READ_STRIP_CR = 1, 2
+PFACX_READ_STRICT, PFACX_READ_STRIP_CR, PFACX_READ_NOCASE = 1, 2, 8
 (PFACX_TABLE_DENSE, PFACX_TABLE_HASH_ROWPTR, PFACX_TABLE_HASH_VALPTR, PFACX_TABLE_INITIAL_ROW,
  PFACX_TABLE_FILTER_GRAM3, PFACX_TABLE_FILTER_SHORT, PFACX_TABLE_FILTER_LADDER, PFACX_TABLE_FILTER_FINAL3,
  PFACX_TABLE_CHAIN) = range(9)
@@ -75,6 +75,13 @@ class PFACX_info(C.Structure):
     ]
 
 
+class PFACX_info_nocase(PFACX_info):
+    """PFACX_info_t as it is now: PFACX_info plus the field appended with PFACX_READ_NOCASE (a ctypes subclass lays its fields out
+    behind its base's, as the header does).  PFAC.caseInsensitive() reads it; PFAC.info() keeps the shorter struct, and the library
+    fills as much as structSize says."""
+    _fields_ = [("caseInsensitive", C.c_int)]
+
+
 class PFACX_scan_stats(C.Structure):
     _fields_ = [("structSize", C.c_size_t), ("walkerRounds", C.c_ulonglong), ("laneSteps", C.c_ulonglong), ("walksStarted", C.c_ulonglong),
                 ("level1Hits", C.c_ulonglong), ("tilesPerChunk", C.c_int), ("walksPerLane", C.c_int),
@@ -102,7 +109,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
     "PFAC_reduce_kernel", "PFAC_reduce_inplace_kernel", "PFACX_streamProbe", "PFACX_buildInfo",
     "PFACX_batchFixup", "PFACX_batchReduceFixup",
-    "PFACX_allReduce", "PFACX_allExpand",
+    "PFACX_allReduce", "PFACX_allExpand", "PFACX_foldInput",
 )
 
 
@@ -138,7 +145,7 @@ def load_library() -> C.CDLL:
     lib.PFAC_matchFromHost.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.PFAC_matchFromDeviceReduce.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     lib.PFAC_matchFromHostReduce.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-    lib.PFACX_getInfo.argtypes = [H, C.POINTER(PFACX_info)]
+    lib.PFACX_getInfo.argtypes = [H, C.POINTER(PFACX_info)]           # (PFACX_info_nocase is one: a subclass)
     lib.PFACX_getTable.argtypes = [H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     lib.PFACX_setKernelVariant.argtypes = [H, C.c_int]
     if hasattr(lib, "PFACX_setWalker"):                  # (tools/ab.py also loads the libraries of earlier revisions)
@@ -285,7 +292,7 @@ class PFAC:
         return self._ret(self._lib.PFACX_setKernelTiming(self._h, 1 if on else 0), "PFACX_setKernelTiming", check)
 
     def readPatternFromFileEx(self, filename, flags: int, check: bool = True) -> int:
-        """``PFACX_readPatternFromFileEx``: flags = PFACX_READ_STRICT | PFACX_READ_STRIP_CR."""
+        """``PFACX_readPatternFromFileEx``: flags = PFACX_READ_STRICT | PFACX_READ_STRIP_CR | PFACX_READ_NOCASE."""
         name = None if filename is None else os.fsencode(filename)
         return self._ret(self._lib.PFACX_readPatternFromFileEx(self._h, name, flags), "PFACX_readPatternFromFileEx", check)
 
@@ -426,6 +433,13 @@ class PFAC:
         info.structSize = C.sizeof(PFACX_info)
         self._ret(self._lib.PFACX_getInfo(self._h, C.byref(info)), "PFACX_getInfo", True)
         return info
+
+    def caseInsensitive(self) -> int:
+        """``PFACX_info_t::caseInsensitive``: 1 when the set was read with PFACX_READ_NOCASE (or loaded from a caseless compiled file)."""
+        info = PFACX_info_nocase()
+        info.structSize = C.sizeof(PFACX_info_nocase)
+        self._ret(self._lib.PFACX_getInfo(self._h, C.byref(info)), "PFACX_getInfo", True)
+        return int(info.caseInsensitive)
 
     def scanStats(self, positions: int = 0):
         """``PFACX_getScanStats`` of the last filter-kernel launch, plus the derived SURVEY 8(d) C5 figures

@@ -117,6 +117,8 @@ PFAC_status_t PFACX_matchAllFromDevice(PFAC_handle_t handle, char *d_input, size
     if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
     std::lock_guard<std::mutex> guard(handle->lock);
+    const PFAC_status_t st = foldDeviceInput(handle, d_input, size, &d_input);
+    if (st != PFAC_STATUS_SUCCESS) return st;
     return matchAllDeviceLocked(handle, d_input, size, nullptr, 0, d_ids, d_pos, capacity, nullptr, h_num_matched);
 }
 
@@ -164,6 +166,8 @@ PFAC_status_t PFACX_matchAllBatchFromDevice(PFAC_handle_t handle, char *d_input,
     if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
     std::lock_guard<std::mutex> guard(handle->lock);
+    const PFAC_status_t st = foldDeviceInput(handle, d_input, size, &d_input);
+    if (st != PFAC_STATUS_SUCCESS) return st;
     return matchAllDeviceLocked(handle, d_input, size, d_offsets, numSegments, d_ids, d_pos, capacity, d_segFirst, h_num_matched);
 }
 

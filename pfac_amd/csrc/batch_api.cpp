@@ -90,7 +90,10 @@ PFAC_status_t PFACX_matchBatchFromDevice(PFAC_handle_t handle, char *d_input, si
     if (size == 0) return PFAC_STATUS_SUCCESS;
     if (numSegments == 0 || numSegments >= SIZE_MAX / sizeof(size_t)) return PFAC_STATUS_INVALID_PARAMETER;
     std::lock_guard<std::mutex> guard(handle->lock);
-    return matchBatchDeviceLocked(handle, d_input, size, d_offsets, numSegments, d_matched_result);
+    char *in = d_input;
+    const PFAC_status_t st = foldDeviceInput(handle, d_input, size, &in);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    return matchBatchDeviceLocked(handle, in, size, d_offsets, numSegments, d_matched_result);
 }
 
 PFAC_status_t PFACX_matchBatchFromHost(PFAC_handle_t handle, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments,
@@ -120,6 +123,8 @@ PFAC_status_t PFACX_matchBatchFromDeviceReduce(PFAC_handle_t handle, char *d_inp
     std::lock_guard<std::mutex> guard(handle->lock);
     correctTextureMode(handle);
     PFAC_status_t st = ensurePatternLen(handle);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    st = foldDeviceInput(handle, d_input, size, &d_input);             /* a caseless set: the scan and the fix-up read the folded bytes */
     if (st != PFAC_STATUS_SUCCESS) return st;
     PFAC_reduce_kernel_protoType fn = handle->perfMode == PFAC_TIME_DRIVEN ? handle->reduce_kernel_ptr : handle->reduce_inplace_kernel_ptr;
     int count = 0;

@@ -37,7 +37,10 @@ constexpr uint32_t kCompiledVersion = 7;          /* 2: patterns of 1-2 bytes ar
                                                      5: the prefix ladder replaces the 4-gram bitmap, the chained table has its own compact breadth-first layout;
                                                      6: 36-byte walk-queue entries (layout fingerprint); 7: no transition table is stored any more -- hashed and
                                                      chained tables are rebuilt from the checked trie at load (a file cannot steer a device read) --, the scalars
-                                                     carry the pattern file's ignored trailing bytes */
+                                                     carry the pattern file's ignored trailing bytes.
+                                                     kCompiledVersionNoCase: the same layout for a caseless set (PFACX_READ_NOCASE): a build that
+                                                     knows only version 7 refuses it instead of matching it case-sensitively */
+constexpr uint32_t kCompiledVersionNoCase = 8;
 /* what the stored tables depend on besides the patterns: hash constants and slot layout */
 constexpr uint32_t kLayoutFingerprint = pfac::kGram3Mul ^ (pfac::kLadMul0 * 3u) ^ (pfac::kLadMul * 5u) ^ (pfac::kLadMulS * 11u) ^ (pfac::kLadMulG * 13u) ^ (pfac::kLadMulG2 * 17u) ^ (pfac::kFinal3Mul * 7u) ^ (pfac::kFinal3Mul2 * 19u) ^
                                         ((uint32_t)pfac::kLadderLevels << 12) ^
@@ -113,7 +116,7 @@ PFAC_status_t PFACX_saveCompiled(PFAC_handle_t handle, const char *filename)
         CompiledHeader h;
         std::memset(&h, 0, sizeof(h));
         std::memcpy(h.magic, kCompiledMagic, 8);
-        h.version = kCompiledVersion; h.fingerprint = kLayoutFingerprint; h.perfMode = (uint32_t)c->perfMode;
+        h.version = c->caseInsensitive ? kCompiledVersionNoCase : kCompiledVersion; h.fingerprint = kLayoutFingerprint; h.perfMode = (uint32_t)c->perfMode;
         h.jumpLog2 = 0;                                        /* (was: log2 of the stored chained table's jump slots) */
         h.payloadBytes = payload.size(); h.payloadFnv1a = fnv1a64(payload.data(), payload.size());
         FILE *fp = std::fopen(filename, "wb");
@@ -131,7 +134,7 @@ PFAC_status_t PFACX_loadCompiled(PFAC_handle_t handle, const char *filename)
     if (!fp) return PFAC_STATUS_FILE_OPEN_ERROR;
     CompiledHeader h;
     std::vector<unsigned char> payload;
-    bool ok = std::fread(&h, sizeof(h), 1, fp) == 1 && std::memcmp(h.magic, kCompiledMagic, 8) == 0 && h.version == kCompiledVersion &&
+    bool ok = std::fread(&h, sizeof(h), 1, fp) == 1 && std::memcmp(h.magic, kCompiledMagic, 8) == 0 && (h.version == kCompiledVersion || h.version == kCompiledVersionNoCase) &&
               h.fingerprint == kLayoutFingerprint && (h.perfMode == PFAC_TIME_DRIVEN || h.perfMode == PFAC_SPACE_DRIVEN) &&
               h.payloadBytes < (uint64_t(1) << 40);
     if (ok) {
@@ -212,6 +215,8 @@ PFAC_status_t PFACX_loadCompiled(PFAC_handle_t handle, const char *filename)
                 longest = fa.patternLen[id] > longest ? fa.patternLen[id] : longest;
             }
             ok = ok && fa.maxPatternLen == longest;
+            /* a caseless set holds folded bytes only: a capital could never meet the folded input */
+            for (size_t i = 0; ok && h.version == kCompiledVersionNoCase && i < fa.file.size(); i++) ok = pfac::asciiFold(fa.file[i]) == fa.file[i];
             /* the edges form a TREE below the initial state: every state is entered by at most one edge, the bytes of a
              * state's edges are distinct, no state lies deeper than the longest pattern (so no walk is longer: a cycle would
              * take a walk past the margin the kernels keep at the end of the input), and final state `id` lies exactly
@@ -249,6 +254,7 @@ PFAC_status_t PFACX_loadCompiled(PFAC_handle_t handle, const char *filename)
     c->patternFile = filename;
     c->perfMode = (int)h.perfMode;
     c->fa = std::move(fa);
+    c->caseInsensitive = h.version == kCompiledVersionNoCase;
     /* The prefilter bitmaps are rebuilt from the checked trie as well, like every table (30 ms for a Snort-scale set): a stale or
      * crafted file with a valid checksum could not make a kernel read outside a bitmap (addresses are masked), but a cleared
      * bit silently drops matches, and the full-result path (gram3 / ladder from the file) could disagree with the compacted-

@@ -33,6 +33,18 @@ struct HashStep {
     }
 };
 
+/* a caseless set (PFACX_READ_NOCASE): the input byte folded on the fly, the caller's buffer is only read */
+template <class Step>
+struct FoldedStep {
+    Step step;
+    unsigned char fold[kCharSet];
+    explicit FoldedStep(const Step &s) : step(s)
+    {
+        for (int b = 0; b < kCharSet; b++) fold[b] = asciiFold((unsigned char)b);
+    }
+    inline int operator()(int state, int ch) const { return step(state, fold[ch]); }
+};
+
 template <class Step>
 void scan(const Step &step, int numFinal, int initial, const unsigned char *in, size_t n, int *out,
           bool useOpenMP)
@@ -59,11 +71,14 @@ PFAC_status_t matchOnCpu(const PFAC_context *ctx, const unsigned char *in, size_
     if (fa.numPatterns >= fa.initialState) return PFAC_STATUS_INTERNAL_ERROR;   /* ref PFAC_CPU.cpp:45-47 */
     if (ctx->perfMode == PFAC_TIME_DRIVEN) {
         if (ctx->h_dense.empty()) return PFAC_STATUS_INTERNAL_ERROR;
-        scan(DenseStep{ctx->h_dense.data()}, fa.numPatterns, fa.initialState, in, n, out, useOpenMP);
+        const DenseStep step{ctx->h_dense.data()};
+        if (ctx->caseInsensitive) scan(FoldedStep<DenseStep>(step), fa.numPatterns, fa.initialState, in, n, out, useOpenMP);
+        else scan(step, fa.numPatterns, fa.initialState, in, n, out, useOpenMP);
     } else {
         if (ctx->h_hashRow.empty()) return PFAC_STATUS_INTERNAL_ERROR;
-        scan(HashStep{ctx->h_hashRow.data(), ctx->h_hashVal.data()}, fa.numPatterns, fa.initialState,
-             in, n, out, useOpenMP);
+        const HashStep step{ctx->h_hashRow.data(), ctx->h_hashVal.data()};
+        if (ctx->caseInsensitive) scan(FoldedStep<HashStep>(step), fa.numPatterns, fa.initialState, in, n, out, useOpenMP);
+        else scan(step, fa.numPatterns, fa.initialState, in, n, out, useOpenMP);
     }
     return PFAC_STATUS_SUCCESS;
 }

@@ -156,6 +156,8 @@ static PFAC_status_t matchHostFullVector(PFAC_context *c, char *h_inputString, s
              hipEventRecord(evUp, up) == hipSuccess && hipStreamWaitEvent(nullptr, evUp, 0) == hipSuccess;
         if (ok && used[b]) ok = hipStreamWaitEvent(nullptr, evDown, 0) == hipSuccess;   /* its results have left this buffer */
         if (!ok) { st = PFAC_STATUS_INTERNAL_ERROR; break; }
+        st = foldStaged(c, c->d_stageIn[b], scanned);                  /* a caseless set: in place, behind the upload */
+        if (st != PFAC_STATUS_SUCCESS) break;
         st = matchDeviceLocked(c, c->d_stageIn[b], scanned, c->d_stageOut[b]);
         if (st != PFAC_STATUS_SUCCESS) break;
         ok = hipEventRecord(evScan, nullptr) == hipSuccess && hipStreamWaitEvent(down, evScan, 0) == hipSuccess &&
@@ -382,6 +384,8 @@ PFAC_status_t matchHostOnGpu(PFAC_context *c, char *h_inputString, size_t owned,
             progress.wait([&]() { return uploadsQueued.load(std::memory_order_acquire) > i || uploadFailed.load(std::memory_order_relaxed); });
             ok = !uploadFailed.load(std::memory_order_relaxed) && hipStreamWaitEvent(nullptr, static_cast<hipEvent_t>(c->evUp[b]), 0) == hipSuccess;
             if (!ok) break;
+            st = foldStaged(c, c->d_stageIn[b], scanned);              /* a caseless set: in place, behind the upload */
+            if (st != PFAC_STATUS_SUCCESS) break;
             int count = 0;
             c->reduceUnordered = true;
             st = reduce(c, reinterpret_cast<int *>(c->d_stageIn[b]), (int)scanned, c->d_stageOut[b], c->d_stagePos[b], &count, nullptr, nullptr);
@@ -487,6 +491,8 @@ PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t 
         progress.wait([&]() { return uploadsQueued.load(std::memory_order_acquire) > i || uploadFailed.load(std::memory_order_relaxed); });
         ok = !uploadFailed.load(std::memory_order_relaxed) && hipStreamWaitEvent(nullptr, static_cast<hipEvent_t>(c->evUp[b]), 0) == hipSuccess;
         if (!ok) break;
+        st = foldStaged(c, c->d_stageIn[b], scanned);                  /* a caseless set: in place, behind the upload */
+        if (st != PFAC_STATUS_SUCCESS) break;
         int count = 0;
         st = reduce(c, reinterpret_cast<int *>(c->d_stageIn[b]), (int)scanned, c->d_stageOut[b], c->d_stagePos[b], &count, nullptr, nullptr);
         if (st != PFAC_STATUS_SUCCESS) break;
@@ -554,6 +560,8 @@ PFAC_status_t matchBatchHostOnGpu(PFAC_context *c, char *h_input, size_t size, c
                 st = PFAC_STATUS_INTERNAL_ERROR;
                 break;
             }
+            st = foldStaged(c, c->d_stageIn[0], w - a);                    /* a caseless set: the window in place */
+            if (st != PFAC_STATUS_SUCCESS) break;
             st = matchBatchDeviceLocked(c, c->d_stageIn[0], w - a, c->d_batchOffsets, local.size() - 1, c->d_stageOut[0]);
             if (st == PFAC_STATUS_SUCCESS &&
                 hipMemcpy(h_matched_result + a, c->d_stageOut[0], (b - a) * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)

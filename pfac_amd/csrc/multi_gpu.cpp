@@ -71,7 +71,8 @@ PFAC_status_t onDevices(PFAC_handle_t handle, size_t size, int numDevices, const
             if (st == PFAC_STATUS_SUCCESS) st = PFAC_setTextureMode(h, (PFAC_textureMode_t)c->textureMode);
             if (st == PFAC_STATUS_SUCCESS) st = PFACX_setKernelVariant(h, c->kernelVariant);
             if (st == PFAC_STATUS_SUCCESS)
-                st = PFACX_readPatternFromMemory(h, reinterpret_cast<const char *>(c->fa.file.data()), c->fa.file.size());
+                st = PFACX_readPatternFromMemoryEx(h, reinterpret_cast<const char *>(c->fa.file.data()), c->fa.file.size(),   /* (folded already, */
+                                                   c->caseInsensitive ? PFACX_READ_NOCASE : 0u);                               /* the input is not) */
             if (st != PFAC_STATUS_SUCCESS) { if (h) (void)PFAC_destroy(h); status[i] = st; return; }
             child = {devs[i], h};
         }

@@ -135,6 +135,8 @@ PFAC_status_t compilePatternBytes(std::vector<unsigned char> bytes, Automaton &f
             if (!(bytes[i] == '\r' && i + 1 < bytes.size() && bytes[i + 1] == '\n')) bytes[w++] = bytes[i];
         bytes.resize(w);
     }
+    if (flags & PFACX_READ_NOCASE)                  /* the ASCII fold (pfac_ext.h): the folded bytes ARE the set, before lines are split and sorted */
+        for (unsigned char &b : bytes) b = asciiFold(b);
     fa.file = std::move(bytes);
     const size_t got = fa.file.size();
     {   /* bytes behind the last newline: the reference counts newline-terminated lines only and silently drops them

@@ -99,6 +99,44 @@ void freeAllScratch(PFAC_context *c)
     c->allScratchBytes = 0;
 }
 
+/* the caseless sets' fold scratch (pfac_context.h) */
+void freeFoldScratch(PFAC_context *c)
+{
+    devFree(c->d_foldScratch);
+    c->foldScratchBytes = 0;
+}
+
+/* The fold of a caseless set's input, once, where it enters the library: every *Locked function and every scan behind
+ * it reads folded bytes.  The caller's device buffer is folded into the grow-only scratch (256-byte aligned, so a misaligned caller
+ * pointer reaches the aligned paths of the scan), asynchronously on the default stream. */
+PFAC_status_t foldDeviceInput(PFAC_context *c, char *d_in, size_t size, char **d_use)
+{
+    *d_use = d_in;
+    if (!c->caseInsensitive || size == 0) return PFAC_STATUS_SUCCESS;
+    if (!c->hasDevice || !c->module || !c->fold_input_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (c->foldScratchBytes < size) {
+        freeFoldScratch(c);
+        const size_t want = (size + 255) & ~size_t(255);
+        if (hipMalloc(reinterpret_cast<void **>(&c->d_foldScratch), want) != hipSuccess) {
+            (void)hipGetLastError();
+            c->d_foldScratch = nullptr;
+            return PFAC_STATUS_CUDA_ALLOC_FAILED;
+        }
+        c->foldScratchBytes = want;
+    }
+    const PFAC_status_t st = c->fold_input_ptr(c, d_in, c->d_foldScratch, size);
+    if (st == PFAC_STATUS_SUCCESS) *d_use = c->d_foldScratch;
+    return st;
+}
+
+/* ... and a staging piece of the host paths in place, behind its upload in stream order */
+PFAC_status_t foldStaged(PFAC_context *c, char *d_piece, size_t size)
+{
+    if (!c->caseInsensitive || size == 0) return PFAC_STATUS_SUCCESS;
+    if (!c->fold_input_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+    return c->fold_input_ptr(c, d_piece, d_piece, size);
+}
+
 /* ref PFAC_freeResource, PFAC.cpp:221-254 */
 void freeResources(PFAC_context *c)
 {
@@ -124,9 +162,11 @@ void freeResources(PFAC_context *c)
     c->denseListEntries = 0;
     freeBatchScratch(c);
     freeAllScratch(c);
+    freeFoldScratch(c);
     for (auto &child : c->children) (void)PFAC_destroy(child.second);
     c->children.clear();
     c->fa = pfac::Automaton();
+    c->caseInsensitive = false;
     c->filter = pfac::Filter();
     c->isPatternsReady = false;
 }
@@ -305,8 +345,10 @@ PFAC_status_t loadModule(PFAC_context *c)
     c->batch_reduce_fixup_ptr = (PFACX_batchReduceFixup_protoType)dlsym(m, "PFACX_batchReduceFixup");
     c->all_reduce_ptr = (PFACX_allReduce_protoType)dlsym(m, "PFACX_allReduce");
     c->all_expand_ptr = (PFACX_allExpand_protoType)dlsym(m, "PFACX_allExpand");
+    c->fold_input_ptr = (PFACX_foldInput_protoType)dlsym(m, "PFACX_foldInput");
     if (!c->kernel_time_driven_ptr || !c->kernel_space_driven_ptr || !c->reduce_kernel_ptr ||
-        !c->reduce_inplace_kernel_ptr || !c->batch_fixup_ptr || !c->batch_reduce_fixup_ptr || !c->all_reduce_ptr || !c->all_expand_ptr)
+        !c->reduce_inplace_kernel_ptr || !c->batch_fixup_ptr || !c->batch_reduce_fixup_ptr || !c->all_reduce_ptr || !c->all_expand_ptr ||
+        !c->fold_input_ptr)
         return PFAC_STATUS_INTERNAL_ERROR;
     return PFAC_STATUS_SUCCESS;
 }
@@ -476,7 +518,7 @@ PFAC_status_t PFAC_dumpTransitionTable(PFAC_handle_t handle, FILE *fp)
 static PFAC_status_t readFromFile(PFAC_handle_t handle, const char *filename, unsigned int flags)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!filename || (flags & ~(PFACX_READ_STRICT | PFACX_READ_STRIP_CR))) return PFAC_STATUS_INVALID_PARAMETER;
+    if (!filename || (flags & ~(PFACX_READ_STRICT | PFACX_READ_STRIP_CR | PFACX_READ_NOCASE))) return PFAC_STATUS_INVALID_PARAMETER;
     std::lock_guard<std::mutex> guard(handle->lock);
     std::unique_lock<std::shared_mutex> tables(handle->tablesInUse);
     if (handle->isPatternsReady) freeResources(handle);            /* ref PFAC.cpp:663-666 */
@@ -486,6 +528,7 @@ static PFAC_status_t readFromFile(PFAC_handle_t handle, const char *filename, un
     PFAC_status_t st = pfac::compilePatternFile(filename, handle->fa, flags);
     if (st != PFAC_STATUS_SUCCESS) { freeResources(handle); return st; }
     handle->isPatternsReady = true;
+    handle->caseInsensitive = (flags & PFACX_READ_NOCASE) != 0;
     st = bindCommon(handle);
     if (st == PFAC_STATUS_SUCCESS) st = bindTable(handle);
     if (st != PFAC_STATUS_SUCCESS) { freeResources(handle); return st; }
@@ -495,7 +538,7 @@ static PFAC_status_t readFromFile(PFAC_handle_t handle, const char *filename, un
 static PFAC_status_t readFromMemory(PFAC_handle_t handle, const char *patterns, size_t size, unsigned int flags)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if ((!patterns && size) || (flags & ~(PFACX_READ_STRICT | PFACX_READ_STRIP_CR))) return PFAC_STATUS_INVALID_PARAMETER;
+    if ((!patterns && size) || (flags & ~(PFACX_READ_STRICT | PFACX_READ_STRIP_CR | PFACX_READ_NOCASE))) return PFAC_STATUS_INVALID_PARAMETER;
     std::lock_guard<std::mutex> guard(handle->lock);
     std::unique_lock<std::shared_mutex> tables(handle->tablesInUse);
     if (handle->isPatternsReady) freeResources(handle);
@@ -506,6 +549,7 @@ static PFAC_status_t readFromMemory(PFAC_handle_t handle, const char *patterns, 
     } catch (const std::bad_alloc &) { st = PFAC_STATUS_ALLOC_FAILED; }
     if (st != PFAC_STATUS_SUCCESS) { freeResources(handle); return st; }
     handle->isPatternsReady = true;
+    handle->caseInsensitive = (flags & PFACX_READ_NOCASE) != 0;
     st = bindCommon(handle);
     if (st == PFAC_STATUS_SUCCESS) st = bindTable(handle);
     if (st != PFAC_STATUS_SUCCESS) { freeResources(handle); return st; }
@@ -536,7 +580,10 @@ PFAC_status_t PFAC_matchFromDevice(PFAC_handle_t handle, char *d_inputString, si
     if (!d_matched_result) return PFAC_STATUS_INVALID_PARAMETER;
     if (size == 0) return PFAC_STATUS_SUCCESS;
     std::lock_guard<std::mutex> guard(handle->lock);
-    return matchDeviceLocked(handle, d_inputString, size, d_matched_result);
+    char *in = d_inputString;
+    const PFAC_status_t st = foldDeviceInput(handle, d_inputString, size, &in);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    return matchDeviceLocked(handle, in, size, d_matched_result);
 }
 
 PFAC_status_t PFAC_matchFromHost(PFAC_handle_t handle, char *h_inputString, size_t size, int *h_matched_result)
@@ -562,9 +609,12 @@ PFAC_status_t PFAC_matchFromDeviceReduce(PFAC_handle_t handle, char *d_inputStri
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
     std::lock_guard<std::mutex> guard(handle->lock);          /* the match counter and the sort scratch belong to the handle */
     correctTextureMode(handle);
+    char *in = d_inputString;
+    const PFAC_status_t st = foldDeviceInput(handle, d_inputString, size, &in);
+    if (st != PFAC_STATUS_SUCCESS) return st;
     PFAC_reduce_kernel_protoType fn =
         handle->perfMode == PFAC_TIME_DRIVEN ? handle->reduce_kernel_ptr : handle->reduce_inplace_kernel_ptr;
-    return fn(handle, reinterpret_cast<int *>(d_inputString), (int)size, d_matched_result, d_pos, h_num_matched,
+    return fn(handle, reinterpret_cast<int *>(in), (int)size, d_matched_result, d_pos, h_num_matched,
               nullptr, nullptr);
 }
 
@@ -612,6 +662,7 @@ PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info)
         v.maxPatternLen = handle->fa.maxPatternLen;
         v.numOfLeaves = handle->fa.numLeaves;
         v.maxMatchesPerPosition = handle->fa.maxChain;
+        v.caseInsensitive = handle->caseInsensitive ? 1 : 0;
         v.perfMode = handle->perfMode;
         v.textureMode = handle->textureMode;
         v.platform = handle->platform;
@@ -668,6 +719,7 @@ PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info)
         scratch += handle->patternLenEntries * sizeof(int) + handle->batchOffsetsEntries * sizeof(size_t) + handle->batchScratchBytes;
         scratch += handle->allTableEntries * sizeof(Int2) + handle->allPairsEntries * 2 * sizeof(int) + handle->allSegFirstEntries * sizeof(int) +
                    handle->allScratchBytes;
+        scratch += handle->foldScratchBytes;
         v.deviceScratchBytes = scratch;
         if (handle->h_modeHint) {
             v.streamNearMisses = (int)static_cast<volatile const unsigned int *>(handle->h_modeHint)[0];
@@ -738,7 +790,7 @@ PFAC_status_t PFACX_getTable(PFAC_handle_t handle, PFACX_table_t which, const vo
 extern "C" {
 
 /* pfac_ext.h: give back the grow-only device buffers of the handle (staging of PFAC_matchFromHost, copies of
- * PFAC_matchFromHostReduce, sort scratch, the dense-chunk list, what the batch and all-match calls keep); the next call that needs one allocates
+ * PFAC_matchFromHostReduce, sort scratch, the dense-chunk list, what the batch and all-match calls keep, the fold scratch of a caseless set); the next call that needs one allocates
  * it again */
 PFAC_status_t PFACX_trim(PFAC_handle_t handle)
 {
@@ -752,6 +804,7 @@ PFAC_status_t PFACX_trim(PFAC_handle_t handle)
     handle->denseListEntries = 0;
     freeBatchScratch(handle);
     freeAllScratch(handle);
+    freeFoldScratch(handle);
     for (auto &child : handle->children) if (child.second) (void)PFACX_trim(child.second);
     return PFAC_STATUS_SUCCESS;
 }

@@ -264,11 +264,16 @@ constexpr uint32_t kFinal3Mul = 0x85EBCBu, kFinal3Mul2 = 0xB5297Bu;    /* 24-bit
 inline uint32_t final3Hash(uint32_t key24, int log2Bits) { return (uint32_t)((key24 & 0xFFFFFFu) * kFinal3Mul) >> (32 - log2Bits); }
 inline uint32_t final3Hash2(uint32_t key24, int log2Bits) { return (uint32_t)((key24 & 0xFFFFFFu) * kFinal3Mul2) >> (32 - log2Bits); }
 
+/* the ASCII fold of PFACX_READ_NOCASE: 'A'-'Z' -> 'a'-'z', every other byte unchanged (scan_fold.hip folds dwords the same way) */
+inline unsigned char asciiFold(unsigned char b) { return (unsigned char)((unsigned)(b - 'A') < 26u ? b + 32 : b); }
+
 } // namespace pfac
 
 struct PFAC_context {
     /* compiled pattern set */
     pfac::Automaton fa;
+    bool caseInsensitive = false;             /* read with PFACX_READ_NOCASE: fa holds the ASCII-folded set, every match call folds its input
+                                                 once where it enters the library (scan_fold.hip) */
     pfac::Filter filter;
     bool isPatternsReady = false;
     std::string patternFile;
@@ -354,6 +359,7 @@ struct PFAC_context {
     PFACX_batchReduceFixup_protoType batch_reduce_fixup_ptr = nullptr;
     PFACX_allReduce_protoType all_reduce_ptr = nullptr;               /* scan_module.hip / scan_all.hip: the all-match calls (PFACX_matchAll*) */
     PFACX_allExpand_protoType all_expand_ptr = nullptr;
+    PFACX_foldInput_protoType fold_input_ptr = nullptr;              /* scan_fold.hip: the input fold of a caseless set */
 
     int platform = PFAC_PLATFORM_GPU;
     int perfMode = PFAC_TIME_DRIVEN;
@@ -395,6 +401,10 @@ struct PFAC_context {
     void *d_allScratch = nullptr;
     size_t allScratchBytes = 0;
     unsigned int allSeq = 0;                  /* number of the last expansion (pfac_all_done writes it to host memory) */
+    /* caseless sets: the caller's device input folded (PFACX_foldInput), what the scan of a device call reads instead.  Grow-only
+     * scratch, 256-byte aligned: PFACX_trim frees it, deviceScratchBytes counts it */
+    char *d_foldScratch = nullptr;
+    size_t foldScratchBytes = 0;
 
     bool hasDevice = false;
     int device = -1;

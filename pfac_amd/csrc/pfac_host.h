@@ -75,6 +75,12 @@ PFAC_status_t prepareHostPath(PFAC_context *c, size_t maxBytes);
 PFAC_status_t matchDeviceLocked(PFAC_context *c, char *d_inputString, size_t size, int *d_matched_result);
 PFAC_status_t matchHostOnGpu(PFAC_context *c, char *h_inputString, size_t owned, size_t readable, int *h_matched_result);
 PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t size, size_t readable, size_t posBase, int *h_matched_result, int *h_pos, int *h_num_matched);
+/* caseless sets (PFACX_READ_NOCASE), the fold where input enters the library; the caller holds c->lock.  foldDeviceInput: the caller's
+ * device bytes into the handle's fold scratch, *d_use = what the scan reads (d_in itself for a case-sensitive handle: no launch, no
+ * scratch).  foldStaged: a staging piece in place, on the default stream behind its upload (nothing for a case-sensitive handle) */
+PFAC_status_t foldDeviceInput(PFAC_context *c, char *d_in, size_t size, char **d_use);
+PFAC_status_t foldStaged(PFAC_context *c, char *d_piece, size_t size);
+void freeFoldScratch(PFAC_context *c);
 /* batch_api.cpp: the batch calls (PFACX_matchBatch*) behind their argument checks; the caller holds c->lock */
 PFAC_status_t ensurePatternLen(PFAC_context *c);            /* the device copy of fa.patternLen the batch fix-ups read */
 PFAC_status_t matchBatchDeviceLocked(PFAC_context *c, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments, int *d_matched_result);

@@ -88,7 +88,8 @@ typedef struct {
     int ladderExtend;         /* ... this many levels further down                                          */
     size_t trailingBytesIgnored; /* bytes behind the last '\n' of the pattern file that were ignored (0: none)  */
     size_t deviceTableBytes;  /* device memory the pattern set holds: chained table, initial row, prefilter bitmaps,
-                                 launch counters; the reference-layout table only while PFACX_KERNEL_REFTABLE is selected */
+                                 launch counters; the reference-layout table only while PFACX_KERNEL_REFTABLE is selected; the carried bytes of
+                                 the handle's device-fed streams (PFACX_stream*: state, not scratch) */
     size_t deviceScratchBytes; /* device memory the handle's calls have left allocated (grow-only; PFACX_trim frees it): the two staging
                                  pieces of PFAC_matchFromHost / ...Reduce (9 bytes per position of a piece), the ordering scratch of the
                                  compacted output, the list of pattern-dense chunks, what the batch calls keep (pattern lengths, offsets of a
@@ -315,6 +316,48 @@ PFAC_status_t PFACX_matchAllFromHost(PFAC_handle_t handle, char *h_input, size_t
  * whole list: the pairs of segment k are [d_segFirst[k], d_segFirst[k + 1]) (indices past capacity name pairs not written) */
 PFAC_status_t PFACX_matchAllBatchFromDevice(PFAC_handle_t handle, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
                                             int *d_ids, int *d_pos, size_t capacity, size_t *d_segFirst, size_t *h_num_matched);
+
+/* Streams: input that arrives over time -- a reassembled TCP flow, a tailed log, a file read in pieces.  The calls above take their
+ * buffer's last byte for the end of the data; a stream carries what is still undecided from one piece to the next.
+ *   Let M = maxPatternLen of the handle's set and S, of length T, the stream's pieces so far, concatenated in call order.  The pairs
+ *   returned by all piece calls since the stream was opened (or reset), followed by the pairs of PFACX_streamFlush, are exactly the
+ *   (id, position) list PFAC_matchFromHostReduce on a CPU platform returns for S as ONE buffer -- same pairs, ascending position,
+ *   nothing twice, nothing missing -- however S was cut: pieces of 0 bytes and pieces shorter than M included.
+ *   A position is FINAL once M - 1 bytes behind it have been seen.  A piece call reports exactly the pairs at stream positions
+ *   [R, max(R, T - (M - 1))), T counted with the piece and R where the previous call stopped reporting (0 after open / reset).
+ *   PFACX_streamFlush declares the end of the stream, reports the pairs at [R, T) with the stream's end as the end of the data, and
+ *   leaves the stream reset (T = R = 0, free to be fed by either kind of call).  With M == 1 nothing is ever pending.
+ * POSITIONS are int, relative to the first byte of the piece of that call: a pair that starts in bytes carried over from earlier
+ * pieces has a negative position (never below -(M - 1)).  *h_pieceOffset receives the stream offset of the piece's first byte (T
+ * before the call), so *h_pieceOffset + position is the position in S: a stream has no 2^31 limit, one piece has (size < 2^31).
+ * The positions of PFACX_streamFlush are relative to T (all negative).
+ * capacity: entries of each of the two arrays, >= size + M (a call can report up to M - 1 carried positions on top of its own, and the
+ * arrays double as the scan's pair list); PFACX_streamFlush: >= M.  Smaller: PFAC_STATUS_INVALID_PARAMETER, the stream unchanged --
+ * as after any failed call: repeat it and get what it would have returned.
+ * A stream is fed by ONE kind of call, fixed by its first piece call of size > 0 after open / reset / flush: device calls (the carried
+ * bytes live in device memory, PFACX_streamFlush takes device arrays) or host calls (host memory, host arrays); the other kind is
+ * PFAC_STATUS_INVALID_PARAMETER.  The host form follows PFAC_setPlatform like PFACX_matchAllFromHost: the CPU platforms, host-only
+ * handles included, run entirely on the CPU; the GPU platform runs the pipelined path of PFAC_matchFromHostReduce.  The device form on
+ * a host-only handle is PFAC_STATUS_LIB_NOT_EXIST.  Null pointers and size >= 2^31: PFAC_STATUS_INVALID_PARAMETER; size == 0: success,
+ * zero pairs, the stream unchanged.  A caseless handle (PFACX_READ_NOCASE) matches the folded set over the folded stream; the caller's
+ * buffers are never modified.
+ * A stream belongs to the pattern set that was loaded when it was opened or last reset: after the handle reads or loads another set,
+ * piece and flush calls return PFAC_STATUS_INVALID_PARAMETER until PFACX_streamReset.  Any number of streams per handle (one per
+ * flow); PFAC_destroy closes the handle's streams.  A call takes the handle's lock like the other match calls (two threads may drive
+ * two streams of one handle; one stream takes one call at a time).  All calls are synchronous (the count comes to the host).
+ * MEMORY: a device-fed stream holds two buffers of M - 1 bytes for its carried bytes (plus 2 (M - 1) bytes where M exceeds 24 Ki).
+ * They are state, not scratch: counted under deviceTableBytes of PFACX_getInfo, kept by PFACX_trim, freed by PFACX_streamClose.
+ * COST: the piece is scanned in place -- no copy; a call adds one small launch for the seam to the compacted call over
+ * the same bytes, and a piece shorter than M - 1 bytes is that launch alone. */
+typedef struct PFACX_stream_s *PFACX_stream_t;
+PFAC_status_t PFACX_streamOpen(PFAC_handle_t handle, PFACX_stream_t *stream);
+PFAC_status_t PFACX_streamReset(PFACX_stream_t stream);      /* forget the carried bytes, T = R = 0; adopt the handle's current pattern set */
+PFAC_status_t PFACX_streamClose(PFACX_stream_t stream);
+PFAC_status_t PFACX_streamMatchFromDevice(PFACX_stream_t stream, char *d_piece, size_t size, int *d_ids, int *d_pos, size_t capacity,
+                                          int *h_num_matched, unsigned long long *h_pieceOffset);
+PFAC_status_t PFACX_streamMatchFromHost(PFACX_stream_t stream, char *h_piece, size_t size, int *h_ids, int *h_pos, size_t capacity,
+                                        int *h_num_matched, unsigned long long *h_pieceOffset);
+PFAC_status_t PFACX_streamFlush(PFACX_stream_t stream, int *ids, int *pos, size_t capacity, int *h_num_matched);
 
 #ifdef __cplusplus
 }

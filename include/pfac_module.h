@@ -86,6 +86,23 @@ typedef PFAC_status_t (*PFACX_allExpand_protoType)(PFAC_handle_t, const int *, c
 PFAC_status_t PFACX_foldInput(PFAC_handle_t handle, const char *src, char *dst, size_t n);
 typedef PFAC_status_t (*PFACX_foldInput_protoType)(PFAC_handle_t, const char *, char *, size_t);
 
+/* Streams (no reference counterpart; include/pfac_ext.h: PFACX_stream*).
+ * PFACX_streamSeam, scan_stream.hip: one launch for the seam between the bytes a stream carries and a new piece.  d_carry holds the
+ * last `carried` bytes of the stream so far (folded, for a caseless set), d_piece the new piece of `size` bytes (may be null when
+ * size == 0: the flush).  The launch walks start positions [0, numFinal) of [carry | first min(size, maxPatternLen - 1) bytes of the
+ * piece] -- numFinal <= carried: the carried positions this call makes final -- and writes their (id, position - carried) pairs in
+ * position order to d_ids / d_pos; it also writes the next carry, the last nextCarried = min(maxPatternLen - 1, carried + size) bytes
+ * of [carry | piece], to d_carryNext (never d_carry: a failed call leaves the stream as it was).  d_stage: device scratch of
+ * carried + min(size, maxPatternLen - 1) bytes for a seam that does not fit the LDS, else null.  Synchronous: *h_count = the pairs.
+ * PFACX_streamReduce, scan_module.hip: PFAC_reduce_kernel / PFAC_reduce_inplace_kernel (hashed != 0) for positions [0, owned) of an
+ * input of `readable` >= owned bytes: the bytes behind `owned` are read-ahead only (their positions belong to the next call). */
+PFAC_status_t PFACX_streamSeam(PFAC_handle_t handle, const char *d_carry, size_t carried, const char *d_piece, size_t size, size_t numFinal,
+                               char *d_carryNext, char *d_stage, int *d_ids, int *d_pos, int *h_count);
+PFAC_status_t PFACX_streamReduce(PFAC_handle_t handle, int *d_input_string, int owned, int readable, int *d_match_result, int *d_pos,
+                                 int *h_num_matched, int hashed);
+typedef PFAC_status_t (*PFACX_streamSeam_protoType)(PFAC_handle_t, const char *, size_t, const char *, size_t, size_t, char *, char *, int *, int *, int *);
+typedef PFAC_status_t (*PFACX_streamReduce_protoType)(PFAC_handle_t, int *, int, int, int *, int *, int *, int);
+
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of
  * `launches` launches over the first n bytes (a multiple of 4096) of d_in, or a negative value on a HIP error.

@@ -104,12 +104,14 @@ EXPORTED_SYMBOLS = (
     "PFACX_setKernelTiming", "PFACX_setWalker", "PFACX_prepare",
     "PFACX_matchBatchFromDevice", "PFACX_matchBatchFromHost", "PFACX_matchBatchFromDeviceReduce",
     "PFACX_matchAllFromDevice", "PFACX_matchAllFromHost", "PFACX_matchAllBatchFromDevice",
+    "PFACX_streamOpen", "PFACX_streamReset", "PFACX_streamClose", "PFACX_streamMatchFromDevice", "PFACX_streamMatchFromHost", "PFACX_streamFlush",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
     "PFAC_reduce_kernel", "PFAC_reduce_inplace_kernel", "PFACX_streamProbe", "PFACX_buildInfo",
     "PFACX_batchFixup", "PFACX_batchReduceFixup",
     "PFACX_allReduce", "PFACX_allExpand", "PFACX_foldInput",
+    "PFACX_streamSeam", "PFACX_streamReduce",
 )
 
 
@@ -174,6 +176,14 @@ def load_library() -> C.CDLL:
         lib.PFACX_matchAllFromHost.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, SZ]
         lib.PFACX_matchAllBatchFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                       C.c_size_t, C.c_void_p, SZ]
+    if hasattr(lib, "PFACX_streamOpen"):
+        lib.PFACX_streamOpen.argtypes = [H, C.POINTER(C.c_void_p)]
+        lib.PFACX_streamReset.argtypes = [C.c_void_p]
+        lib.PFACX_streamClose.argtypes = [C.c_void_p]
+        piece = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]
+        lib.PFACX_streamMatchFromDevice.argtypes = piece
+        lib.PFACX_streamMatchFromHost.argtypes = piece
+        lib.PFACX_streamFlush.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -418,6 +428,14 @@ class PFAC:
         self._ret(st, "PFACX_matchAllFromHost", True)
         return pos[:n].copy(), ids[:n].copy()
 
+    # -- input that arrives in pieces (include/pfac_ext.h: PFACX_stream*) ----------------
+    def streamOpen(self, check: bool = True) -> "Stream":
+        """``PFACX_streamOpen`` -> a :class:`Stream` of this handle (``.status`` holds the call's status)."""
+        s = C.c_void_p()
+        st = self._lib.PFACX_streamOpen(self._h, C.byref(s))
+        self._ret(st, "PFACX_streamOpen", check)
+        return Stream(self, s, st)
+
     # -- numpy conveniences over matchFromHost (still the C ABI underneath) ----------
     def match_host_array(self, data):
         import numpy as np
@@ -470,3 +488,66 @@ class PFAC:
             return np.zeros(0, dtype=dtype)
         buf = (C.c_char * nbytes.value).from_address(ptr.value)
         return np.frombuffer(buf, dtype=dtype).copy()
+
+
+class Stream:
+    """One stream (``PFACX_stream_t``) of a handle: pieces in, the pairs that have become final out.  Every call returns
+    ``(status, number of pairs, stream offset of the piece's first byte)``; positions are relative to that byte (negative for a
+    pair that starts in bytes carried over from earlier pieces)."""
+
+    def __init__(self, handle: PFAC, stream: C.c_void_p, status: int = 0):
+        self._owner = handle
+        self._lib = handle._lib
+        self._s = stream
+        self.status = status
+
+    def _ret(self, st: int, where: str, check: bool) -> int:
+        if check and st != 0:
+            raise PFACError(st, where, error_string(st))
+        return st
+
+    def match_device(self, d_piece: int, size: int, d_ids: int, d_pos: int, capacity: int, check: bool = True):
+        """``PFACX_streamMatchFromDevice``: capacity >= size + maxPatternLen entries in each device array."""
+        n, off = C.c_int(0), C.c_ulonglong(0)
+        st = self._lib.PFACX_streamMatchFromDevice(self._s, d_piece, size, d_ids, d_pos, capacity, C.byref(n), C.byref(off))
+        return self._ret(st, "PFACX_streamMatchFromDevice", check), n.value, off.value
+
+    def match_host(self, h_piece: int, size: int, h_ids: int, h_pos: int, capacity: int, check: bool = True):
+        """``PFACX_streamMatchFromHost``: follows PFAC_setPlatform (the CPU platforms run on the CPU)."""
+        n, off = C.c_int(0), C.c_ulonglong(0)
+        st = self._lib.PFACX_streamMatchFromHost(self._s, h_piece, size, h_ids, h_pos, capacity, C.byref(n), C.byref(off))
+        return self._ret(st, "PFACX_streamMatchFromHost", check), n.value, off.value
+
+    def flush(self, ids: int, pos: int, capacity: int, check: bool = True):
+        """``PFACX_streamFlush`` -> (status, number of pairs): the end of the stream; host arrays on a host-fed stream, device
+        arrays on a device-fed one; positions are relative to the stream's end."""
+        n = C.c_int(0)
+        st = self._lib.PFACX_streamFlush(self._s, ids, pos, capacity, C.byref(n))
+        return self._ret(st, "PFACX_streamFlush", check), n.value
+
+    def reset(self, check: bool = True) -> int:
+        return self._ret(self._lib.PFACX_streamReset(self._s), "PFACX_streamReset", check)
+
+    def close(self, check: bool = True) -> int:
+        st = self._lib.PFACX_streamClose(self._s)
+        self._s = C.c_void_p()
+        return self._ret(st, "PFACX_streamClose", check)
+
+    def match_host_array(self, piece):
+        """match_host over a numpy array -> (ids, pos, piece offset) of the pairs this piece made final."""
+        import numpy as np
+        piece = np.ascontiguousarray(piece, dtype=np.uint8)
+        cap = piece.size + max(1, int(self._owner.info().maxPatternLen))
+        ids = np.full(cap, -7, dtype=np.int32)
+        pos = np.full(cap, -7, dtype=np.int32)
+        buf = piece if piece.size else np.zeros(1, dtype=np.uint8)
+        _, n, off = self.match_host(buf.ctypes.data, piece.size, ids.ctypes.data, pos.ctypes.data, cap)
+        return ids[:n].copy(), pos[:n].copy(), off
+
+    def flush_host_array(self):
+        import numpy as np
+        cap = max(1, int(self._owner.info().maxPatternLen))
+        ids = np.full(cap, -7, dtype=np.int32)
+        pos = np.full(cap, -7, dtype=np.int32)
+        _, n = self.flush(ids.ctypes.data, pos.ctypes.data, cap)
+        return ids[:n].copy(), pos[:n].copy()

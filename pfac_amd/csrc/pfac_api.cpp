@@ -169,6 +169,7 @@ void freeResources(PFAC_context *c)
     c->caseInsensitive = false;
     c->filter = pfac::Filter();
     c->isPatternsReady = false;
+    c->setGeneration++;                        /* the handle's streams belong to the set that has just gone (PFACX_streamReset) */
 }
 
 
@@ -346,9 +347,11 @@ PFAC_status_t loadModule(PFAC_context *c)
     c->all_reduce_ptr = (PFACX_allReduce_protoType)dlsym(m, "PFACX_allReduce");
     c->all_expand_ptr = (PFACX_allExpand_protoType)dlsym(m, "PFACX_allExpand");
     c->fold_input_ptr = (PFACX_foldInput_protoType)dlsym(m, "PFACX_foldInput");
+    c->stream_seam_ptr = (PFACX_streamSeam_protoType)dlsym(m, "PFACX_streamSeam");
+    c->stream_reduce_ptr = (PFACX_streamReduce_protoType)dlsym(m, "PFACX_streamReduce");
     if (!c->kernel_time_driven_ptr || !c->kernel_space_driven_ptr || !c->reduce_kernel_ptr ||
         !c->reduce_inplace_kernel_ptr || !c->batch_fixup_ptr || !c->batch_reduce_fixup_ptr || !c->all_reduce_ptr || !c->all_expand_ptr ||
-        !c->fold_input_ptr)
+        !c->fold_input_ptr || !c->stream_seam_ptr || !c->stream_reduce_ptr)
         return PFAC_STATUS_INTERNAL_ERROR;
     return PFAC_STATUS_SUCCESS;
 }
@@ -421,6 +424,7 @@ PFAC_status_t PFACX_createHostOnly(PFAC_handle_t *handle)
 PFAC_status_t PFAC_destroy(PFAC_handle_t handle)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    closeAllStreams(handle);
     freeResources(handle);
     /* drops this handle's reference; the module stays mapped while other handles hold theirs (dlopen refcounts) */
     if (handle->module) dlclose(handle->module);
@@ -709,6 +713,7 @@ PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info)
         if (handle->d_prefix4) dev += handle->filter.prefix4.size() * sizeof(uint32_t);
         if (handle->d_tail) dev += (handle->filter.tail.size() + handle->filter.tailG.size()) * sizeof(uint32_t);
         if (handle->d_workCounters) dev += pfac::kWorkCounterWords * sizeof(unsigned int);
+        dev += streamDeviceBytes(handle);      /* the carried bytes of device-fed streams: state, not scratch (PFACX_trim keeps them) */
         v.deviceTableBytes = dev;
         /* ... and what its calls have left allocated (grow-only, PFACX_trim gives it back): the two staging pieces of the host
          * paths (input + ids + positions: 9 bytes per position), the scratch the compacted output is ordered through, the list

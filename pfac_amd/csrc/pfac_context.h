@@ -49,6 +49,7 @@ constexpr int kTiledDenseWord = 37 * 32;         /* tiled kernel scanning a whol
 constexpr int kHostPairCountWord = 4;             /* word of the handle's mapped host memory (h_modeHint) the first ordering launch (pfac_order_count) writes the number of pairs of a compacted-output call to */
 constexpr int kHostAllTotalWord = 8;              /* words 8-9 of h_modeHint: the 64-bit length of an all-match call's list (scan_all.hip: pfac_all_block_scan) ... */
 constexpr int kHostAllDoneWord = 10;              /* ... and the sequence number its last launch writes (pfac_all_done) */
+constexpr int kHostSeamCountWord = 12;             /* words 12-13 of h_modeHint: the pairs a stream call's seam launch wrote (scan_stream.hip: pfac_stream_seam) and the sequence number it writes behind them */
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -264,6 +265,10 @@ constexpr uint32_t kFinal3Mul = 0x85EBCBu, kFinal3Mul2 = 0xB5297Bu;    /* 24-bit
 inline uint32_t final3Hash(uint32_t key24, int log2Bits) { return (uint32_t)((key24 & 0xFFFFFFu) * kFinal3Mul) >> (32 - log2Bits); }
 inline uint32_t final3Hash2(uint32_t key24, int log2Bits) { return (uint32_t)((key24 & 0xFFFFFFu) * kFinal3Mul2) >> (32 - log2Bits); }
 
+/* streams (PFACX_stream*): the seam launch stages at most 2 (maxPatternLen - 1) bytes in its block's LDS when they fit this (sets with patterns of up
+ * to 24 Ki bytes), else in device scratch the stream allocates with its carry buffers (scan_stream.hip, stream_api.cpp) */
+constexpr size_t kStreamSeamLdsBytes = 48 * 1024;
+
 /* the ASCII fold of PFACX_READ_NOCASE: 'A'-'Z' -> 'a'-'z', every other byte unchanged (scan_fold.hip folds dwords the same way) */
 inline unsigned char asciiFold(unsigned char b) { return (unsigned char)((unsigned)(b - 'A') < 26u ? b + 32 : b); }
 
@@ -360,6 +365,8 @@ struct PFAC_context {
     PFACX_allReduce_protoType all_reduce_ptr = nullptr;               /* scan_module.hip / scan_all.hip: the all-match calls (PFACX_matchAll*) */
     PFACX_allExpand_protoType all_expand_ptr = nullptr;
     PFACX_foldInput_protoType fold_input_ptr = nullptr;              /* scan_fold.hip: the input fold of a caseless set */
+    PFACX_streamSeam_protoType stream_seam_ptr = nullptr;            /* scan_stream.hip: the seam of a stream call (PFACX_stream*) */
+    PFACX_streamReduce_protoType stream_reduce_ptr = nullptr;        /* scan_module.hip: the compacted scan of a piece whose last bytes are read-ahead only */
 
     int platform = PFAC_PLATFORM_GPU;
     int perfMode = PFAC_TIME_DRIVEN;
@@ -405,6 +412,13 @@ struct PFAC_context {
      * scratch, 256-byte aligned: PFACX_trim frees it, deviceScratchBytes counts it */
     char *d_foldScratch = nullptr;
     size_t foldScratchBytes = 0;
+
+    /* streams (PFACX_stream*, stream_api.cpp): the open streams of this handle (PFAC_destroy closes them) and the number of the pattern set
+     * they were opened on: whatever replaces or drops the set (freeResources) counts it up, and a stream of an older set is refused until
+     * PFACX_streamReset.  The carried bytes of device-fed streams are state, not scratch: counted under deviceTableBytes, kept by PFACX_trim */
+    std::vector<PFACX_stream_s *> streams;
+    unsigned long long setGeneration = 0;
+    unsigned int seamSeq = 0;                 /* number of the last seam launch (pfac_stream_seam writes it to host memory) */
 
     bool hasDevice = false;
     int device = -1;

@@ -81,6 +81,9 @@ PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t 
 PFAC_status_t foldDeviceInput(PFAC_context *c, char *d_in, size_t size, char **d_use);
 PFAC_status_t foldStaged(PFAC_context *c, char *d_piece, size_t size);
 void freeFoldScratch(PFAC_context *c);
+/* stream_api.cpp: PFAC_destroy closes the handle's streams; the device bytes their carries hold (PFACX_getInfo: deviceTableBytes) */
+void closeAllStreams(PFAC_context *c);
+size_t streamDeviceBytes(const PFAC_context *c);
 /* batch_api.cpp: the batch calls (PFACX_matchBatch*) behind their argument checks; the caller holds c->lock */
 PFAC_status_t ensurePatternLen(PFAC_context *c);            /* the device copy of fa.patternLen the batch fix-ups read */
 PFAC_status_t matchBatchDeviceLocked(PFAC_context *c, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments, int *d_matched_result);

@@ -7,6 +7,7 @@
  *   scan_tiled.hip    pfac_scan_tiled (chained table / reference-layout tables), pfac_scan_naive + launchers
  *   scan_order.hip    the four ordering kernels of the compacted output (PairOrder)
  *   scan_module.hip   the four symbols of the plugin seam (include/pfac_module.h), launch plans, stream probe
+ *   scan_stream.hip   pfac_stream_seam: the seam between a stream's carried bytes and its next piece (PFACX_stream*)
  */
 #ifndef PFAC_SCAN_COMMON_H_
 #define PFAC_SCAN_COMMON_H_
@@ -788,6 +789,21 @@ constexpr size_t kChunkBytesDev = kChunkBytesHost;
  * that size (a 1024-thread block with 128 registers per thread fills a CU by itself whatever its LDS). */
 constexpr int kMaxDevices = 64;
 struct ShapeCache { std::mutex lock; int perCU[kMaxDevices] = {}; };
+
+/* the walkers' view of the handle's (wide) chained table: where the initial state's bucket, the two jump tables and the extension units lie
+ * (tables.cpp: buildChainedHashTable).  The one place that knows the layout: every launcher fills its ScanArgs through this */
+inline void fillChainArgs(const PFAC_context *c, ScanArgs &a)
+{
+    a.chainSlots = reinterpret_cast<const u32x4 *>(c->d_chainSlots);
+    a.jumpShift = 32u - (uint32_t)c->chainJumpLog2;
+    a.extDelta = (uint32_t)(c->numChainSlots / 2);                         /* headers, then as many extension units */
+    a.jumpBase = (uint32_t)(c->numChainSlots / 2 - (size_t(2) << c->chainJumpLog2));         /* the jump table, then the long jump table */
+    a.jumpLongBase = a.jumpBase + (uint32_t)(size_t(1) << c->chainJumpLog2);
+    a.rootRow = a.jumpBase - (uint32_t)pfac::kCharSet;
+    const size_t bytes = c->numChainSlots * sizeof(pfac::ChainSlot);
+    a.chainBytes = bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)bytes;
+    a.maxWalk = (uint32_t)c->fa.maxPatternLen;
+}
 
 inline unsigned int gridFor(const PFAC_context *c, size_t items)
 {

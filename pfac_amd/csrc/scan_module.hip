@@ -127,13 +127,7 @@ PFAC_status_t fillArgs(const PFAC_context *c, bool hashed, const char *d_input_s
     a.denseBytes = clampExtent(c->h_dense.size() * sizeof(int));
     a.hashRowBytes = clampExtent(c->h_hashRow.size() * sizeof(Int2));
     a.hashValBytes = clampExtent(c->h_hashVal.size() * sizeof(Int2));
-    a.chainSlots = reinterpret_cast<const u32x4 *>(c->d_chainSlots);
-    a.jumpShift = 32u - (uint32_t)c->chainJumpLog2;
-    a.extDelta = (uint32_t)(c->numChainSlots / 2);                         /* headers, then as many extension units (tables.cpp) */
-    a.jumpBase = (uint32_t)(c->numChainSlots / 2 - (size_t(2) << c->chainJumpLog2));         /* the jump table, then the long jump table */
-    a.jumpLongBase = a.jumpBase + (uint32_t)(size_t(1) << c->chainJumpLog2);
-    a.rootRow = a.jumpBase - (uint32_t)pfac::kCharSet;
-    a.chainBytes = clampExtent(c->numChainSlots * sizeof(pfac::ChainSlot));
+    fillChainArgs(c, a);                                                   /* scan_common.h: the chained table and maxWalk */
     a.initialRow = c->d_initialRow;
     a.gram3 = c->d_gram3;
     a.gram1 = c->d_gram1;
@@ -151,7 +145,6 @@ PFAC_status_t fillArgs(const PFAC_context *c, bool hashed, const char *d_input_s
     for (int k = 0; k < pfac::kSkipTagsMax; k++) a.skipTags[k] = c->filter.skipTags[k];
     a.log2BitsF3 = c->filter.log2BitsF3;
     a.numFinal = c->fa.numPatterns;
-    a.maxWalk = (uint32_t)c->fa.maxPatternLen;
     a.work = c->d_workCounters;
     a.hostHint = c->d_modeHint;
     a.denseWord = (uint32_t)pfac::kDenseCountWord;
@@ -359,12 +352,14 @@ PFAC_status_t orderIntoAllPairs(PFAC_context *mc, PairOrder &order)
 }
 
 PFAC_status_t reduceScan(PFAC_handle_t handle, int *d_input_string, int input_size, int *d_match_result, int *d_pos,
-                         int *h_num_matched, int *h_match_result, int *h_pos, bool hashed, bool intoAll = false)
+                         int *h_num_matched, int *h_match_result, int *h_pos, bool hashed, bool intoAll = false, int ownedPositions = -1)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
     if (!d_input_string || !d_match_result || !d_pos || !h_num_matched || input_size <= 0) return PFAC_STATUS_INVALID_PARAMETER;
+    if (ownedPositions == 0 || ownedPositions > input_size) return PFAC_STATUS_INVALID_PARAMETER;
     const PFAC_context *c = handle;
     const size_t n = (size_t)input_size;
+    const size_t owned = ownedPositions < 0 ? n : (size_t)ownedPositions;   /* a stream's piece (PFACX_streamReduce): pairs of [0, owned), the rest is read-ahead */
     ScanArgs a;
     PFAC_status_t st = fillArgs(c, hashed, reinterpret_cast<const char *>(d_input_string), n, d_match_result, a);
     if (st != PFAC_STATUS_SUCCESS) return st;
@@ -397,7 +392,7 @@ PFAC_status_t reduceScan(PFAC_handle_t handle, int *d_input_string, int input_si
     trPlan = trUs();
 #endif
     const size_t head = headPositions(a.in, n);
-    const size_t mainLen = filterLength(c, head, n, n, true, /*reduce=*/true);
+    const size_t mainLen = filterLength(c, head, owned, n, true, /*reduce=*/true);
     a.reducePos = d_pos;
     a.reduceCount = order.o.count;
     if (mainLen) {
@@ -411,12 +406,12 @@ PFAC_status_t reduceScan(PFAC_handle_t handle, int *d_input_string, int input_si
         part.endsA0 = 0;
         part.endsA1 = (uint32_t)head;
         part.endsB0 = (uint32_t)(head + mainLen);
-        part.endsB1 = (uint32_t)n;
+        part.endsB1 = (uint32_t)owned;
         if (pfacmod::launchFilterKernel(c, part, tex, true) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
     } else {
         /* a small input (or PFACX_KERNEL_NAIVE / REFTABLE): positions [0, n) through the tiled (reference-shaped) kernel, which appends its matches to the list */
         ScanArgs part = a;
-        part.owned = n;
+        part.owned = owned;
         part.reduceBase = 0;
         if (c->kernelVariant != PFACX_KERNEL_REFTABLE) tiledTable(c, part);
         if (pfacmod::launchSimpleKernel(c, hashed, tex, part) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
@@ -559,6 +554,13 @@ PFAC_status_t PFACX_allReduce(PFAC_handle_t handle, int *d_input_string, int inp
                               int *h_num_matched, int hashed)
 {
     return reduceScan(handle, d_input_string, input_size, d_match_result, d_pos, h_num_matched, nullptr, nullptr, hashed != 0, true);
+}
+
+/* pfac_module.h: the compacted output of a stream's piece -- pairs of positions [0, owned), walks may read up to `readable` */
+PFAC_status_t PFACX_streamReduce(PFAC_handle_t handle, int *d_input_string, int owned, int readable, int *d_match_result, int *d_pos,
+                                 int *h_num_matched, int hashed)
+{
+    return reduceScan(handle, d_input_string, readable, d_match_result, d_pos, h_num_matched, nullptr, nullptr, hashed != 0, false, owned);
 }
 
 } /* extern "C" */

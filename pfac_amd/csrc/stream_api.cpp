@@ -1,0 +1,345 @@
+/*
+ * stream_api.cpp -- PFACX_streamOpen / Reset / Close / MatchFromDevice / MatchFromHost / Flush (include/pfac_ext.h): input that
+ * arrives in pieces, occurrences that straddle two pieces included.
+ *
+ * With M = maxPatternLen, a start position is final once M - 1 bytes behind it have been seen.  A stream keeps the last
+ * min(M - 1, T) bytes it has seen (the carry); exactly the positions in the carry are pending, so R = T - carried and no other state
+ * is needed.  A piece call reports the carried positions that the piece makes final (the seam: [carry | first M - 1 bytes of the
+ * piece], a few KiB at most) and the piece's own positions below size - (M - 1) (the piece in place, its last M - 1 bytes read-ahead
+ * only), then carries the last M - 1 bytes on.  The flush reports every carried position with the carry's end as the end of data.
+ *   device-fed: the carry lives in two device buffers (the seam launch writes the next one, so a failed call leaves the stream as it
+ *               was); seam = scan_stream.hip, piece = the compacted-output path for positions [0, owned) (PFACX_streamReduce).
+ *   host-fed:   the carry is host memory, kept as the caller sent it (every match path folds a caseless set's input itself); seam and
+ *               piece go through the CPU matchers on a CPU platform and through the pipelined path of PFAC_matchFromHostReduce on the
+ *               GPU platform.
+ * Every piece and flush call holds the handle's lock from the check of the pattern set to its end (and the stream's own lock: one call
+ * at a time per stream), so a set read on another thread cannot slip between a call's halves.
+ */
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "pfac_host.h"
+
+struct PFACX_stream_s {
+    PFAC_context *handle = nullptr;
+    unsigned long long generation = 0;        /* PFAC_context::setGeneration when the stream was opened or last reset */
+    int kind = 0;                             /* 0: not fed yet, 1: host calls, 2: device calls */
+    unsigned long long total = 0;             /* T: bytes seen */
+    size_t carried = 0;                       /* min(M - 1, T): the pending positions are the carried ones */
+    std::vector<unsigned char> h_carry;       /* host-fed */
+    char *d_block = nullptr;                  /* device-fed: one allocation = two carry buffers (+ the seam's stage where it does not fit the LDS) */
+    char *d_carry[2] = {nullptr, nullptr};
+    char *d_stage = nullptr;
+    size_t deviceBytes = 0;
+    int deviceM = 0;                          /* the maxPatternLen the block was sized for */
+    int cur = 0;
+    std::mutex lock;                          /* one call at a time per stream */
+};
+
+namespace pfac_internal {
+
+static void freeStreamDevice(PFACX_stream_s *s)
+{
+    devFree(s->d_block);
+    s->d_carry[0] = s->d_carry[1] = s->d_stage = nullptr;
+    s->deviceBytes = 0;
+    s->deviceM = 0;
+}
+
+void closeAllStreams(PFAC_context *c)
+{
+    for (PFACX_stream_s *s : c->streams) {
+        freeStreamDevice(s);
+        delete s;
+    }
+    c->streams.clear();
+}
+
+size_t streamDeviceBytes(const PFAC_context *c)
+{
+    size_t bytes = 0;
+    for (const PFACX_stream_s *s : c->streams) bytes += s->deviceBytes;
+    return bytes;
+}
+
+static void forget(PFACX_stream_s *s)
+{
+    s->kind = 0;
+    s->total = 0;
+    s->carried = 0;
+    s->h_carry.clear();
+    s->cur = 0;
+}
+
+/* the carry buffers of a device-fed stream, sized for the handle's pattern set (only ever resized while nothing is carried) */
+static PFAC_status_t ensureStreamDevice(PFACX_stream_s *s, int M)
+{
+    if (s->d_block && s->deviceM == M) return PFAC_STATUS_SUCCESS;
+    freeStreamDevice(s);
+    const size_t one = (((size_t)M - 1) + 255) & ~size_t(255);
+    const size_t seam = 2 * ((size_t)M - 1);
+    const size_t stage = seam > pfac::kStreamSeamLdsBytes ? ((seam + 255) & ~size_t(255)) : 0;
+    const size_t bytes = 2 * one + stage + 256;
+    if (hipMalloc(reinterpret_cast<void **>(&s->d_block), bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        s->d_block = nullptr;
+        return PFAC_STATUS_CUDA_ALLOC_FAILED;
+    }
+    s->d_carry[0] = s->d_block;
+    s->d_carry[1] = s->d_block + one + 128;
+    s->d_stage = stage ? s->d_block + 2 * one + 256 : nullptr;
+    s->deviceBytes = bytes;
+    s->deviceM = M;
+    return PFAC_STATUS_SUCCESS;
+}
+
+/* how a piece of `size` bytes splits the work: of the positions [R, T + size) the first `finalAll` are final; `seam` of them are carried */
+struct Split { size_t seam, owned; };
+static Split splitOf(size_t carried, size_t size, size_t M)
+{
+    const size_t all = carried + size;
+    const size_t finalAll = all >= M - 1 ? all - (M - 1) : 0;
+    Split sp;
+    sp.seam = finalAll < carried ? finalAll : carried;
+    sp.owned = finalAll - sp.seam;
+    return sp;
+}
+
+/* the longest match at positions [0, owned) of `readable` host bytes as (id, position + posShift) pairs behind ids / pos; CPU platforms
+ * (the caller holds c->lock: the tables first, then the match that needs no lock of its own) */
+static PFAC_status_t cpuPairs(PFAC_context *c, const char *in, size_t owned, size_t readable, int posShift, int *scratch, int *ids, int *pos, int *count)
+{
+    PFAC_status_t st = prepareCpuPlatformLocked(c);
+    if (st == PFAC_STATUS_SUCCESS) st = matchHostOnCpuPlatformPrepared(c, in, readable, scratch);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    int z = 0;
+    for (size_t i = 0; i < owned; i++) {
+        const int m = scratch[i];
+        if (m > 0) { ids[z] = m; pos[z] = (int)i + posShift; z++; }
+    }
+    *count = z;
+    return PFAC_STATUS_SUCCESS;
+}
+
+/* ... on the GPU platform (the caller holds c->lock): the pipelined host path, positions [0, owned), the rest read-ahead */
+static PFAC_status_t gpuPairs(PFAC_context *c, char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count)
+{
+    int n = 0;
+    const PFAC_status_t st = matchHostReduceOnGpu(c, in, owned, readable, 0, ids, pos, &n);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (posShift) for (int k = 0; k < n; k++) pos[k] += posShift;
+    *count = n;
+    return PFAC_STATUS_SUCCESS;
+}
+
+/* (the caller holds the handle's lock: the set cannot change between this check and the end of the call) */
+static PFAC_status_t checkStream(PFACX_stream_s *s)
+{
+    PFAC_context *c = s->handle;
+    if (!c) return PFAC_STATUS_INVALID_HANDLE;
+    if (s->generation != c->setGeneration) return PFAC_STATUS_INVALID_PARAMETER;     /* another pattern set since: PFACX_streamReset */
+    if (!c->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
+    return PFAC_STATUS_SUCCESS;
+}
+
+} // namespace pfac_internal
+using namespace pfac_internal;
+
+extern "C" {
+
+PFAC_status_t PFACX_streamOpen(PFAC_handle_t handle, PFACX_stream_t *stream)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!stream) return PFAC_STATUS_INVALID_PARAMETER;
+    *stream = nullptr;
+    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
+    PFACX_stream_s *s = new (std::nothrow) PFACX_stream_s();
+    if (!s) return PFAC_STATUS_ALLOC_FAILED;
+    std::lock_guard<std::mutex> guard(handle->lock);
+    s->handle = handle;
+    s->generation = handle->setGeneration;
+    try { handle->streams.push_back(s); } catch (const std::bad_alloc &) { delete s; return PFAC_STATUS_ALLOC_FAILED; }
+    *stream = s;
+    return PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t PFACX_streamReset(PFACX_stream_t stream)
+{
+    if (!stream || !stream->handle) return PFAC_STATUS_INVALID_HANDLE;
+    std::lock_guard<std::mutex> own(stream->lock);
+    std::lock_guard<std::mutex> guard(stream->handle->lock);
+    forget(stream);
+    stream->generation = stream->handle->setGeneration;
+    return PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t PFACX_streamClose(PFACX_stream_t stream)
+{
+    if (!stream || !stream->handle) return PFAC_STATUS_INVALID_HANDLE;
+    PFAC_context *c = stream->handle;
+    {
+        std::lock_guard<std::mutex> guard(c->lock);
+        auto it = std::find(c->streams.begin(), c->streams.end(), stream);
+        if (it == c->streams.end()) return PFAC_STATUS_INVALID_HANDLE;
+        c->streams.erase(it);
+        freeStreamDevice(stream);
+    }
+    delete stream;
+    return PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t PFACX_streamMatchFromDevice(PFACX_stream_t stream, char *d_piece, size_t size, int *d_ids, int *d_pos, size_t capacity,
+                                          int *h_num_matched, unsigned long long *h_pieceOffset)
+{
+    if (!stream || !stream->handle) return PFAC_STATUS_INVALID_HANDLE;
+    std::lock_guard<std::mutex> own(stream->lock);
+    std::lock_guard<std::mutex> guard(stream->handle->lock);      /* one lock around the set's check, M, seam and piece */
+    PFAC_status_t st = checkStream(stream);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    PFAC_context *c = stream->handle;
+    if (!d_piece || !d_ids || !d_pos || !h_num_matched || !h_pieceOffset) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size == 0) { *h_num_matched = 0; *h_pieceOffset = stream->total; return PFAC_STATUS_SUCCESS; }
+    const size_t M = (size_t)c->fa.maxPatternLen;
+    if (capacity < size || capacity - size < M) return PFAC_STATUS_INVALID_PARAMETER;
+    if (stream->kind == 1) return PFAC_STATUS_INVALID_PARAMETER;           /* a host-fed stream */
+    if (!c->hasDevice || !c->module || !c->stream_seam_ptr || !c->stream_reduce_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
+    correctTextureMode(c);
+    const Split sp = splitOf(stream->carried, size, M);
+    int seamPairs = 0, piecePairs = 0;
+    size_t nextCarried = 0;
+    if (M > 1) {
+        st = ensureStreamDevice(stream, (int)M);
+        if (st != PFAC_STATUS_SUCCESS) return st;
+        /* the seam: the carried positions this piece makes final, and the next carry into the other buffer */
+        st = c->stream_seam_ptr(c, stream->d_carry[stream->cur], stream->carried, d_piece, size, sp.seam, stream->d_carry[stream->cur ^ 1],
+                                stream->d_stage, d_ids, d_pos, &seamPairs);
+        if (st != PFAC_STATUS_SUCCESS) return st;
+        nextCarried = std::min(M - 1, stream->carried + size);
+    }
+    if (sp.owned) {
+        /* the piece in place (a caseless set: its fold, as in every device call), output behind the seam's pairs; a piece shorter than
+         * M - 1 has nothing final and never gets here */
+        char *in = d_piece;
+        st = foldDeviceInput(c, d_piece, size, &in);
+        if (st != PFAC_STATUS_SUCCESS) return st;
+        st = c->stream_reduce_ptr(c, reinterpret_cast<int *>(in), (int)sp.owned, (int)size, d_ids + seamPairs, d_pos + seamPairs, &piecePairs,
+                                  c->perfMode == PFAC_TIME_DRIVEN ? 0 : 1);
+        if (st != PFAC_STATUS_SUCCESS) return st;
+    }
+    *h_num_matched = seamPairs + piecePairs;
+    *h_pieceOffset = stream->total;
+    stream->kind = 2;
+    stream->total += size;
+    stream->carried = nextCarried;
+    if (M > 1) stream->cur ^= 1;
+    return PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t PFACX_streamMatchFromHost(PFACX_stream_t stream, char *h_piece, size_t size, int *h_ids, int *h_pos, size_t capacity,
+                                        int *h_num_matched, unsigned long long *h_pieceOffset)
+{
+    if (!stream || !stream->handle) return PFAC_STATUS_INVALID_HANDLE;
+    std::lock_guard<std::mutex> own(stream->lock);
+    std::lock_guard<std::mutex> guard(stream->handle->lock);      /* one lock around the set's check, M, seam and piece */
+    PFAC_status_t st = checkStream(stream);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    PFAC_context *c = stream->handle;
+    if (!h_piece || !h_ids || !h_pos || !h_num_matched || !h_pieceOffset) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size == 0) { *h_num_matched = 0; *h_pieceOffset = stream->total; return PFAC_STATUS_SUCCESS; }
+    const size_t M = (size_t)c->fa.maxPatternLen;
+    if (capacity < size || capacity - size < M) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
+    if (stream->kind == 2) return PFAC_STATUS_INVALID_PARAMETER;           /* a device-fed stream */
+    const bool gpu = c->platform == PFAC_PLATFORM_GPU;
+    if (gpu && (!c->hasDevice || !c->module)) return PFAC_STATUS_LIB_NOT_EXIST;
+    const size_t carried = stream->carried;
+    const Split sp = splitOf(carried, size, M);
+    const size_t head = std::min(size, M - 1);
+    int seamPairs = 0, piecePairs = 0;
+    try {
+        std::vector<unsigned char> next;                       /* the stream changes when the whole call has succeeded */
+        std::vector<int> seamIds, seamPos;
+        if (sp.seam) {
+            std::vector<unsigned char> seam(carried + head);
+            std::memcpy(seam.data(), stream->h_carry.data(), carried);
+            std::memcpy(seam.data() + carried, h_piece, head);
+            seamIds.resize(sp.seam);
+            seamPos.resize(sp.seam);
+            if (gpu) {
+                st = gpuPairs(c, reinterpret_cast<char *>(seam.data()), sp.seam, seam.size(), -(int)carried, seamIds.data(), seamPos.data(), &seamPairs);
+            } else {
+                std::vector<int> scratch(seam.size());
+                st = cpuPairs(c, reinterpret_cast<const char *>(seam.data()), sp.seam, seam.size(), -(int)carried, scratch.data(), seamIds.data(),
+                              seamPos.data(), &seamPairs);
+            }
+            if (st != PFAC_STATUS_SUCCESS) return st;
+        }
+        if (sp.owned) {
+            if (gpu) {
+                st = gpuPairs(c, h_piece, sp.owned, size, 0, h_ids + seamPairs, h_pos + seamPairs, &piecePairs);
+            } else {
+                /* every position's longest match into the caller's array behind the room of the seam's pairs (capacity >= size + M),
+                 * compacted forward in place: pair z comes from an entry at or behind M - 1 + z */
+                int *scratch = h_ids + (M - 1);
+                st = cpuPairs(c, h_piece, sp.owned, size, 0, scratch, h_ids + seamPairs, h_pos + seamPairs, &piecePairs);
+            }
+            if (st != PFAC_STATUS_SUCCESS) return st;
+        }
+        for (int k = 0; k < seamPairs; k++) { h_ids[k] = seamIds[(size_t)k]; h_pos[k] = seamPos[(size_t)k]; }
+        const size_t nextCarried = std::min(M - 1, carried + size);
+        next.resize(nextCarried);
+        const size_t fromPiece = std::min(nextCarried, size);
+        if (nextCarried > fromPiece) std::memcpy(next.data(), stream->h_carry.data() + (carried - (nextCarried - fromPiece)), nextCarried - fromPiece);
+        std::memcpy(next.data() + (nextCarried - fromPiece), h_piece + (size - fromPiece), fromPiece);
+        stream->h_carry.swap(next);
+        stream->carried = nextCarried;
+    } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
+    *h_num_matched = seamPairs + piecePairs;
+    *h_pieceOffset = stream->total;
+    stream->kind = 1;
+    stream->total += size;
+    return PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t PFACX_streamFlush(PFACX_stream_t stream, int *ids, int *pos, size_t capacity, int *h_num_matched)
+{
+    if (!stream || !stream->handle) return PFAC_STATUS_INVALID_HANDLE;
+    std::lock_guard<std::mutex> own(stream->lock);
+    std::lock_guard<std::mutex> guard(stream->handle->lock);      /* one lock around the set's check, M, seam and piece */
+    PFAC_status_t st = checkStream(stream);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    PFAC_context *c = stream->handle;
+    if (!ids || !pos || !h_num_matched) return PFAC_STATUS_INVALID_PARAMETER;
+    const size_t M = (size_t)c->fa.maxPatternLen;
+    if (capacity < M) return PFAC_STATUS_INVALID_PARAMETER;
+    const size_t carried = stream->carried;
+    int pairs = 0;
+    if (carried && stream->kind == 2) {
+        if (!c->hasDevice || !c->module || !c->stream_seam_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+        st = c->stream_seam_ptr(c, stream->d_carry[stream->cur], carried, nullptr, 0, carried, stream->d_carry[stream->cur ^ 1], stream->d_stage, ids, pos,
+                                &pairs);
+        if (st != PFAC_STATUS_SUCCESS) return st;
+    } else if (carried && stream->kind == 1) {
+        try {
+            if (c->platform == PFAC_PLATFORM_GPU) {
+                if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+                st = gpuPairs(c, reinterpret_cast<char *>(stream->h_carry.data()), carried, carried, -(int)carried, ids, pos, &pairs);
+            } else {
+                std::vector<int> scratch(carried);
+                st = cpuPairs(c, reinterpret_cast<const char *>(stream->h_carry.data()), carried, carried, -(int)carried, scratch.data(), ids, pos, &pairs);
+            }
+        } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
+        if (st != PFAC_STATUS_SUCCESS) return st;
+    }
+    *h_num_matched = pairs;
+    forget(stream);
+    return PFAC_STATUS_SUCCESS;
+}
+
+} /* extern "C" */

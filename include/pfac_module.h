@@ -63,8 +63,8 @@ typedef PFAC_status_t (*PFACX_batchReduceFixup_protoType)(PFAC_handle_t, const c
 
 /* All matches (no reference counterpart; include/pfac_ext.h: PFACX_matchAll*).
  * PFACX_allReduce, scan_module.hip: PFAC_reduce_kernel (hashed == 0) / PFAC_reduce_inplace_kernel (hashed != 0) whose ordering
- * writes the ordered (id, position) pairs into the handle's all-match scratch -- ids at PFAC_context::d_allPairs, positions
- * allPairsEntries ints behind them -- instead of into d_match_result / d_pos, which hold `input_size` entries and take only the
+ * writes the ordered (id, position) pairs into the handle's all-match scratch -- one buffer, pfac::DeviceScratch::allPairs: the ids in its first
+ * half, the positions in its second -- instead of into d_match_result / d_pos, which hold `input_size` entries and take only the
  * scan's unordered list; synchronous, *h_num_matched = the number of pairs.
  * PFACX_allExpand, scan_all.hip: expands `count` ordered longest pairs through d_table (pfac::Int2 {prefixPattern, chainLen} by
  * id) into d_ids / d_pos, every pattern at a position, longest first; slots >= capacity are not written; *h_total = the length

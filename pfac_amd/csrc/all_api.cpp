@@ -21,27 +21,10 @@ namespace pfac_internal {
 /* the device copy of {prefixPattern, chainLen} by id that the expansion reads (uploaded on the first call that expands) */
 static PFAC_status_t ensureAllTable(PFAC_context *c)
 {
-    if (c->d_allTable) return PFAC_STATUS_SUCCESS;
+    if (c->scratch.allTable) return PFAC_STATUS_SUCCESS;
     std::vector<pfac::Int2> t(c->fa.prefixPattern.size());
     for (size_t id = 0; id < t.size(); id++) t[id] = pfac::Int2{c->fa.prefixPattern[id], c->fa.chainLen[id]};
-    const PFAC_status_t st = upload(c->d_allTable, t.data(), t.size());
-    if (st == PFAC_STATUS_SUCCESS) c->allTableEntries = t.size();
-    return st;
-}
-
-/* room for the first longest pair of each segment (batch form) */
-static PFAC_status_t ensureAllSegFirst(PFAC_context *c, size_t entries)
-{
-    if (c->allSegFirstEntries >= entries) return PFAC_STATUS_SUCCESS;
-    devFree(c->d_allSegFirst);
-    c->allSegFirstEntries = 0;
-    if (hipMalloc(reinterpret_cast<void **>(&c->d_allSegFirst), entries * sizeof(int)) != hipSuccess) {
-        (void)hipGetLastError();
-        c->d_allSegFirst = nullptr;
-        return PFAC_STATUS_CUDA_ALLOC_FAILED;
-    }
-    c->allSegFirstEntries = entries;
-    return PFAC_STATUS_SUCCESS;
+    return c->scratch.allTable.upload(t.data(), t.size());
 }
 
 /* the GPU forms behind their argument checks (0 < size < 2^31, capacity >= size; d_offsets null: one segment, no d_segFirst) */
@@ -52,27 +35,26 @@ static PFAC_status_t matchAllDeviceLocked(PFAC_context *c, char *d_input, size_t
     const bool expand = c->fa.maxChain > 1;
     PFAC_status_t st = PFAC_STATUS_SUCCESS;
     if (d_offsets) st = ensurePatternLen(c);
-    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = ensureAllSegFirst(c, numSegments + 1);
+    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = c->scratch.allSegFirst.reserve(numSegments + 1);      /* the first longest pair of each segment */
     if (st == PFAC_STATUS_SUCCESS && expand) st = ensureAllTable(c);
     if (st != PFAC_STATUS_SUCCESS) return st;
     int count = 0;
     int *ids = d_ids, *pos = d_pos;
     if (expand) {
         st = c->all_reduce_ptr(c, reinterpret_cast<int *>(d_input), (int)size, d_ids, d_pos, &count, c->perfMode == PFAC_TIME_DRIVEN ? 0 : 1);
-        ids = c->d_allPairs;
-        pos = c->d_allPairs + c->allPairsEntries;
+        ids = c->scratch.allPairs.get();
+        pos = ids + c->scratch.allPairs.count() / 2;              /* one allocation: the ids, then as many positions */
     } else {
-        PFAC_reduce_kernel_protoType fn = c->perfMode == PFAC_TIME_DRIVEN ? c->reduce_kernel_ptr : c->reduce_inplace_kernel_ptr;
-        st = fn(c, reinterpret_cast<int *>(d_input), (int)size, d_ids, d_pos, &count, nullptr, nullptr);
+        st = reduceOnDevice(c, d_input, size, d_ids, d_pos, &count);
     }
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (d_offsets)
-        st = c->batch_reduce_fixup_ptr(c, d_input, size, d_offsets, numSegments, ids, pos, &count, c->d_allSegFirst, c->d_patternLen);
+        st = c->batch_reduce_fixup_ptr(c, d_input, size, d_offsets, numSegments, ids, pos, &count, c->scratch.allSegFirst.get(), c->scratch.patternLen.get());
     if (st != PFAC_STATUS_SUCCESS) return st;
     size_t total = (size_t)count;
     if (expand || d_offsets)
-        st = c->all_expand_ptr(c, ids, pos, (size_t)count, expand ? c->d_allTable : nullptr, d_ids, d_pos, capacity,
-                               d_offsets ? c->d_allSegFirst : nullptr, numSegments, d_segFirst, &total);
+        st = c->all_expand_ptr(c, ids, pos, (size_t)count, expand ? c->scratch.allTable.get() : nullptr, d_ids, d_pos, capacity,
+                               d_offsets ? c->scratch.allSegFirst.get() : nullptr, numSegments, d_segFirst, &total);
     if (st != PFAC_STATUS_SUCCESS) return st;
     *h_num_matched = total;
     return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
@@ -136,10 +118,7 @@ PFAC_status_t PFACX_matchAllFromHost(PFAC_handle_t handle, char *h_input, size_t
         /* the longest match of every position into h_ids (it holds size entries), compacted in place as PFAC_matchFromHostReduce does */
         const PFAC_status_t st = matchHostOnCpuPlatform(handle, h_input, size, h_ids);
         if (st != PFAC_STATUS_SUCCESS) return st;
-        for (size_t i = 0; i < size; i++) {
-            const int m = h_ids[i];
-            if (m > 0) { h_ids[count] = m; h_pos[count] = (int)i; count++; }
-        }
+        count = (size_t)compactPairs(h_ids, size, 0, h_ids, h_pos);
     } else {
         if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
         std::lock_guard<std::mutex> guard(handle->lock);

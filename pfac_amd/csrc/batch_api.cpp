@@ -31,10 +31,8 @@ static bool offsetsValid(const size_t *offsets, size_t numSegments, size_t size)
 /* the device copy of the pattern lengths by id that the fix-up kernels read (uploaded on the first batch call) */
 PFAC_status_t ensurePatternLen(PFAC_context *c)
 {
-    if (c->d_patternLen) return PFAC_STATUS_SUCCESS;
-    const PFAC_status_t st = upload(c->d_patternLen, c->fa.patternLen.data(), c->fa.patternLen.size());
-    if (st == PFAC_STATUS_SUCCESS) c->patternLenEntries = c->fa.patternLen.size();
-    return st;
+    if (c->scratch.patternLen) return PFAC_STATUS_SUCCESS;
+    return c->scratch.patternLen.upload(c->fa.patternLen.data(), c->fa.patternLen.size());
 }
 
 /* PFACX_matchBatchFromDevice behind the argument checks (size > 0, numSegments > 0): the scan of the concatenation, then the fix-up
@@ -46,7 +44,7 @@ PFAC_status_t matchBatchDeviceLocked(PFAC_context *c, char *d_input, size_t size
     if (st != PFAC_STATUS_SUCCESS) return st;
     st = matchDeviceLocked(c, d_input, size, d_matched_result);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    return c->batch_fixup_ptr(c, d_input, size, d_offsets, numSegments, d_matched_result, c->d_patternLen);
+    return c->batch_fixup_ptr(c, d_input, size, d_offsets, numSegments, d_matched_result, c->scratch.patternLen.get());
 }
 
 /* the CPU platforms: one match per non-empty segment.  PFAC_PLATFORM_CPU_OMP (with OMP_NUM_THREADS set, as for PFAC_matchFromHost)
@@ -126,11 +124,10 @@ PFAC_status_t PFACX_matchBatchFromDeviceReduce(PFAC_handle_t handle, char *d_inp
     if (st != PFAC_STATUS_SUCCESS) return st;
     st = foldDeviceInput(handle, d_input, size, &d_input);             /* a caseless set: the scan and the fix-up read the folded bytes */
     if (st != PFAC_STATUS_SUCCESS) return st;
-    PFAC_reduce_kernel_protoType fn = handle->perfMode == PFAC_TIME_DRIVEN ? handle->reduce_kernel_ptr : handle->reduce_inplace_kernel_ptr;
     int count = 0;
-    st = fn(handle, reinterpret_cast<int *>(d_input), (int)size, d_matched_result, d_pos, &count, nullptr, nullptr);
+    st = reduceOnDevice(handle, d_input, size, d_matched_result, d_pos, &count);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    st = handle->batch_reduce_fixup_ptr(handle, d_input, size, d_offsets, numSegments, d_matched_result, d_pos, &count, d_segFirst, handle->d_patternLen);
+    st = handle->batch_reduce_fixup_ptr(handle, d_input, size, d_offsets, numSegments, d_matched_result, d_pos, &count, d_segFirst, handle->scratch.patternLen.get());
     if (st != PFAC_STATUS_SUCCESS) return st;
     *h_num_matched = count;
     return PFAC_STATUS_SUCCESS;

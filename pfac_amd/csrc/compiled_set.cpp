@@ -260,13 +260,7 @@ PFAC_status_t PFACX_loadCompiled(PFAC_handle_t handle, const char *filename)
      * bit silently drops matches, and the full-result path (gram3 / ladder from the file) could disagree with the compacted-
      * output path (gram1 / prefix4, always rebuilt).  The file's copies are read, size-checked and dropped. */
     c->filter = pfac::Filter();
-    c->isPatternsReady = true;
-    pfac::buildInitialRow(c->fa, c->h_initialRow);
-    PFAC_status_t st;
-    try { st = bindCommon(c, /*build=*/true); } catch (const std::bad_alloc &) { st = PFAC_STATUS_ALLOC_FAILED; }
-    if (st == PFAC_STATUS_SUCCESS) st = bindTable(c);
-    if (st != PFAC_STATUS_SUCCESS) { freeResources(c); return st; }
-    return PFAC_STATUS_SUCCESS;
+    return bindCompiledSet(c);
 }
 
 } /* extern "C" */

@@ -79,13 +79,13 @@ PFAC_status_t matchDeviceLocked(PFAC_context *c, char *d_inputString, size_t siz
  */
 static PFAC_status_t ensureHostStage(PFAC_context *c, size_t need)
 {
-    if (c->hostStagePositions >= need) return PFAC_STATUS_SUCCESS;
+    pfac::DeviceScratch &s = c->scratch;
+    if (s.stagePos[1].count() >= need) return PFAC_STATUS_SUCCESS;      /* the last of the six: a stage is whole or not there */
     freeHostStage(c);
     bool ok = true;
     for (int b = 0; b < 2 && ok; b++) {
-        ok = hipMalloc(reinterpret_cast<void **>(&c->d_stageIn[b]), (need + 3) & ~size_t(3)) == hipSuccess &&
-             hipMalloc(reinterpret_cast<void **>(&c->d_stageOut[b]), need * sizeof(int)) == hipSuccess &&
-             hipMalloc(reinterpret_cast<void **>(&c->d_stagePos[b]), need * sizeof(int)) == hipSuccess;
+        ok = s.stageIn[b].reserve((need + 3) & ~size_t(3)) == PFAC_STATUS_SUCCESS && s.stageOut[b].reserve(need) == PFAC_STATUS_SUCCESS &&
+             s.stagePos[b].reserve(need) == PFAC_STATUS_SUCCESS;
         hipEvent_t e[3] = {nullptr, nullptr, nullptr};
         for (int k = 0; k < 3 && ok; k++) ok = hipEventCreateWithFlags(&e[k], hipEventDisableTiming) == hipSuccess;
         c->evUp[b] = e[0]; c->evScan[b] = e[1]; c->evDown[b] = e[2];
@@ -95,7 +95,6 @@ static PFAC_status_t ensureHostStage(PFAC_context *c, size_t need)
          hipStreamCreateWithFlags(&down, hipStreamNonBlocking) == hipSuccess;
     c->stageUp = up; c->stageDown = down;
     if (!ok) { (void)hipGetLastError(); freeHostStage(c); return PFAC_STATUS_CUDA_ALLOC_FAILED; }
-    c->hostStagePositions = need;
     return PFAC_STATUS_SUCCESS;
 }
 
@@ -119,15 +118,14 @@ PFAC_status_t prepareHostPath(PFAC_context *c, size_t maxBytes)
     bool ok = true;
     try {
         const std::vector<char> pageable(n, (char)filler);
-        ok = hipMemcpyAsync(c->d_stageIn[0], pageable.data(), n, hipMemcpyHostToDevice, up) == hipSuccess && hipStreamSynchronize(up) == hipSuccess &&
-             hipMemsetAsync(c->d_stageIn[1], filler, n, nullptr) == hipSuccess;
+        ok = hipMemcpyAsync(c->scratch.stageIn[0].get(), pageable.data(), n, hipMemcpyHostToDevice, up) == hipSuccess && hipStreamSynchronize(up) == hipSuccess &&
+             hipMemsetAsync(c->scratch.stageIn[1].get(), filler, n, nullptr) == hipSuccess;
     } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
     if (!ok) { (void)hipGetLastError(); return PFAC_STATUS_INTERNAL_ERROR; }
-    PFAC_reduce_kernel_protoType reduce = c->perfMode == PFAC_TIME_DRIVEN ? c->reduce_kernel_ptr : c->reduce_inplace_kernel_ptr;
     for (int b = 0; b < 2 && st == PFAC_STATUS_SUCCESS; b++) {              /* both buffers, the way both host calls use them: pairs in any order / in position order */
         int count = 0;
         c->reduceUnordered = b == 0;
-        st = reduce(c, reinterpret_cast<int *>(c->d_stageIn[b]), (int)n, c->d_stageOut[b], c->d_stagePos[b], &count, nullptr, nullptr);
+        st = reduceOnDevice(c, c->scratch.stageIn[b].get(), n, c->scratch.stageOut[b].get(), c->scratch.stagePos[b].get(), &count);
         c->reduceUnordered = false;
     }
     if (st == PFAC_STATUS_SUCCESS && hipStreamSynchronize(nullptr) != hipSuccess) st = PFAC_STATUS_INTERNAL_ERROR;
@@ -146,22 +144,24 @@ static PFAC_status_t matchHostFullVector(PFAC_context *c, char *h_inputString, s
     size_t i = 0;
     for (size_t off = 0; off < owned && st == PFAC_STATUS_SUCCESS; off += piece, i++) {
         const int b = (int)(i & 1);
+        char *const d_in = c->scratch.stageIn[b].get();
+        int *const d_ids = c->scratch.stageOut[b].get();
         const size_t mine = owned - off < piece ? owned - off : piece;
         const size_t scanned = readable - off < mine + overlap ? readable - off : mine + overlap;
         hipEvent_t evUp = static_cast<hipEvent_t>(c->evUp[b]), evScan = static_cast<hipEvent_t>(c->evScan[b]),
                    evDown = static_cast<hipEvent_t>(c->evDown[b]);
         bool ok = true;
         if (used[b]) ok = hipStreamWaitEvent(up, evScan, 0) == hipSuccess;          /* the scan of piece i-2 has read this buffer */
-        ok = ok && hipMemcpyAsync(c->d_stageIn[b], h_inputString + off, scanned, hipMemcpyHostToDevice, up) == hipSuccess &&
+        ok = ok && hipMemcpyAsync(d_in, h_inputString + off, scanned, hipMemcpyHostToDevice, up) == hipSuccess &&
              hipEventRecord(evUp, up) == hipSuccess && hipStreamWaitEvent(nullptr, evUp, 0) == hipSuccess;
         if (ok && used[b]) ok = hipStreamWaitEvent(nullptr, evDown, 0) == hipSuccess;   /* its results have left this buffer */
         if (!ok) { st = PFAC_STATUS_INTERNAL_ERROR; break; }
-        st = foldStaged(c, c->d_stageIn[b], scanned);                  /* a caseless set: in place, behind the upload */
+        st = foldStaged(c, d_in, scanned);                  /* a caseless set: in place, behind the upload */
         if (st != PFAC_STATUS_SUCCESS) break;
-        st = matchDeviceLocked(c, c->d_stageIn[b], scanned, c->d_stageOut[b]);
+        st = matchDeviceLocked(c, d_in, scanned, d_ids);
         if (st != PFAC_STATUS_SUCCESS) break;
         ok = hipEventRecord(evScan, nullptr) == hipSuccess && hipStreamWaitEvent(down, evScan, 0) == hipSuccess &&
-             hipMemcpyAsync(h_matched_result + off, c->d_stageOut[b], mine * sizeof(int), hipMemcpyDeviceToHost, down) == hipSuccess &&
+             hipMemcpyAsync(h_matched_result + off, d_ids, mine * sizeof(int), hipMemcpyDeviceToHost, down) == hipSuccess &&
              hipEventRecord(evDown, down) == hipSuccess;
         if (!ok) st = PFAC_STATUS_INTERNAL_ERROR;
         used[b] = true;
@@ -252,14 +252,13 @@ PFAC_status_t matchHostOnGpu(PFAC_context *c, char *h_inputString, size_t owned,
     PFAC_status_t st = ensureHostStage(c, piece + overlap);
     if (st != PFAC_STATUS_SUCCESS) return st;
     correctTextureMode(c);
-    PFAC_reduce_kernel_protoType reduce = c->perfMode == PFAC_TIME_DRIVEN ? c->reduce_kernel_ptr : c->reduce_inplace_kernel_ptr;
     hipStream_t up = static_cast<hipStream_t>(c->stageUp);
     const size_t numPieces = (owned + piece - 1) / piece;
     auto uploadPiece = [&](size_t i) -> bool {               /* into buffer i & 1, on the upload stream */
         const size_t off = i * piece;
         const size_t mine = owned - off < piece ? owned - off : piece;
         const size_t scanned = readable - off < mine + overlap ? readable - off : mine + overlap;
-        return hipMemcpyAsync(c->d_stageIn[i & 1], h_inputString + off, scanned, hipMemcpyHostToDevice, up) == hipSuccess &&
+        return hipMemcpyAsync(c->scratch.stageIn[i & 1].get(), h_inputString + off, scanned, hipMemcpyHostToDevice, up) == hipSuccess &&
                hipEventRecord(static_cast<hipEvent_t>(c->evUp[i & 1]), up) == hipSuccess;
     };
     /* the link first: nothing below is worth a microsecond of an idle copy engine */
@@ -378,17 +377,19 @@ PFAC_status_t matchHostOnGpu(PFAC_context *c, char *h_inputString, size_t owned,
     try {
         for (size_t i = 0; i < numPieces && ok && st == PFAC_STATUS_SUCCESS; i++) {
             const int b = (int)(i & 1);
+            char *const d_in = c->scratch.stageIn[b].get();
+            int *const d_ids = c->scratch.stageOut[b].get(), *const d_pos = c->scratch.stagePos[b].get();
             const size_t off = i * piece;
             const size_t mine = owned - off < piece ? owned - off : piece;
             const size_t scanned = readable - off < mine + overlap ? readable - off : mine + overlap;
             progress.wait([&]() { return uploadsQueued.load(std::memory_order_acquire) > i || uploadFailed.load(std::memory_order_relaxed); });
             ok = !uploadFailed.load(std::memory_order_relaxed) && hipStreamWaitEvent(nullptr, static_cast<hipEvent_t>(c->evUp[b]), 0) == hipSuccess;
             if (!ok) break;
-            st = foldStaged(c, c->d_stageIn[b], scanned);              /* a caseless set: in place, behind the upload */
+            st = foldStaged(c, d_in, scanned);              /* a caseless set: in place, behind the upload */
             if (st != PFAC_STATUS_SUCCESS) break;
             int count = 0;
             c->reduceUnordered = true;
-            st = reduce(c, reinterpret_cast<int *>(c->d_stageIn[b]), (int)scanned, c->d_stageOut[b], c->d_stagePos[b], &count, nullptr, nullptr);
+            st = reduceOnDevice(c, d_in, scanned, d_ids, d_pos, &count);
             c->reduceUnordered = false;
             if (st != PFAC_STATUS_SUCCESS) break;
             scansDone.store(i + 1, std::memory_order_release);     /* the scan is synchronous: its input buffer may take piece i + 2 */
@@ -396,8 +397,8 @@ PFAC_status_t matchHostOnGpu(PFAC_context *c, char *h_inputString, size_t owned,
             if ((size_t)count > mine / 8) { densePieces.push_back(i); continue; }
             pos.resize((size_t)count);
             id.resize((size_t)count);
-            if (count && (hipMemcpy(pos.data(), c->d_stagePos[b], (size_t)count * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-                          hipMemcpy(id.data(), c->d_stageOut[b], (size_t)count * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)) {
+            if (count && (hipMemcpy(pos.data(), d_pos, (size_t)count * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+                          hipMemcpy(id.data(), d_ids, (size_t)count * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)) {
                 ok = false;
                 break;
             }
@@ -448,14 +449,13 @@ PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t 
     PFAC_status_t st = ensureHostStage(c, piece + overlap);
     if (st != PFAC_STATUS_SUCCESS) return st;
     correctTextureMode(c);
-    PFAC_reduce_kernel_protoType reduce = c->perfMode == PFAC_TIME_DRIVEN ? c->reduce_kernel_ptr : c->reduce_inplace_kernel_ptr;
     hipStream_t up = static_cast<hipStream_t>(c->stageUp);
     const size_t numPieces = (size + piece - 1) / piece;
     auto uploadPiece = [&](size_t i) -> bool {               /* into buffer i & 1, on the upload stream */
         const size_t off = i * piece;
         const size_t mine = size - off < piece ? size - off : piece;
         const size_t scanned = readable - off < mine + overlap ? readable - off : mine + overlap;
-        return hipMemcpyAsync(c->d_stageIn[i & 1], h_inputString + off, scanned, hipMemcpyHostToDevice, up) == hipSuccess &&
+        return hipMemcpyAsync(c->scratch.stageIn[i & 1].get(), h_inputString + off, scanned, hipMemcpyHostToDevice, up) == hipSuccess &&
                hipEventRecord(static_cast<hipEvent_t>(c->evUp[i & 1]), up) == hipSuccess;
     };
     std::atomic<size_t> scansDone{0}, uploadsQueued{0};
@@ -485,16 +485,18 @@ PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t 
     size_t total = 0;
     for (size_t i = 0; i < numPieces && ok && st == PFAC_STATUS_SUCCESS; i++) {
         const int b = (int)(i & 1);
+        char *const d_in = c->scratch.stageIn[b].get();
+        int *const d_ids = c->scratch.stageOut[b].get(), *const d_pos = c->scratch.stagePos[b].get();
         const size_t off = i * piece;
         const size_t mine = size - off < piece ? size - off : piece;
         const size_t scanned = readable - off < mine + overlap ? readable - off : mine + overlap;
         progress.wait([&]() { return uploadsQueued.load(std::memory_order_acquire) > i || uploadFailed.load(std::memory_order_relaxed); });
         ok = !uploadFailed.load(std::memory_order_relaxed) && hipStreamWaitEvent(nullptr, static_cast<hipEvent_t>(c->evUp[b]), 0) == hipSuccess;
         if (!ok) break;
-        st = foldStaged(c, c->d_stageIn[b], scanned);                  /* a caseless set: in place, behind the upload */
+        st = foldStaged(c, d_in, scanned);                  /* a caseless set: in place, behind the upload */
         if (st != PFAC_STATUS_SUCCESS) break;
         int count = 0;
-        st = reduce(c, reinterpret_cast<int *>(c->d_stageIn[b]), (int)scanned, c->d_stageOut[b], c->d_stagePos[b], &count, nullptr, nullptr);
+        st = reduceOnDevice(c, d_in, scanned, d_ids, d_pos, &count);
         if (st != PFAC_STATUS_SUCCESS) break;
         scansDone.store(i + 1, std::memory_order_release);     /* the scan is synchronous: its input buffer may take piece i + 2 */
         progress.bump();
@@ -502,10 +504,10 @@ PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t 
         /* total <= off (a position has at most one pair); the pairs that stay (positions below `mine`) are at most `mine`, so they lie among the
          * first size - total of the list: the caller's arrays (size entries) hold what is copied */
         const size_t room = size - total, copied = (size_t)count < room ? (size_t)count : room;
-        if (hipMemcpy(h_pos + total, c->d_stagePos[b], copied * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
+        if (hipMemcpy(h_pos + total, d_pos, copied * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
         size_t keep = copied;                                  /* positions ascend: those in the overlap are a suffix */
         while (keep > 0 && (size_t)h_pos[total + keep - 1] >= mine) keep--;
-        if (keep && hipMemcpy(h_matched_result + total, c->d_stageOut[b], keep * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
+        if (keep && hipMemcpy(h_matched_result + total, d_ids, keep * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
         if (off + posBase) for (size_t k = 0; k < keep; k++) h_pos[total + k] += (int)(off + posBase);
         total += keep;
     }
@@ -533,6 +535,8 @@ PFAC_status_t matchBatchHostOnGpu(PFAC_context *c, char *h_input, size_t size, c
     const size_t piece = size < kHostPiece ? size : kHostPiece;
     PFAC_status_t st = ensureHostStage(c, piece + overlap);
     if (st != PFAC_STATUS_SUCCESS) return st;
+    char *const d_in = c->scratch.stageIn[0].get();
+    int *const d_out = c->scratch.stageOut[0].get();
     std::vector<size_t> local;
     try {
         for (size_t a = 0; a < size && st == PFAC_STATUS_SUCCESS; a += piece) {
@@ -544,27 +548,18 @@ PFAC_status_t matchBatchHostOnGpu(PFAC_context *c, char *h_input, size_t size, c
             local.push_back(0);
             for (k++; k < numSegments && h_offsets[k] < w; k++) local.push_back(h_offsets[k] - a);
             local.push_back(w - a);
-            if (c->batchOffsetsEntries < local.size()) {
-                devFree(c->d_batchOffsets);
-                c->batchOffsetsEntries = 0;
-                const size_t want = local.size() > 4096 ? local.size() : 4096;
-                if (hipMalloc(reinterpret_cast<void **>(&c->d_batchOffsets), want * sizeof(size_t)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    c->d_batchOffsets = nullptr;
-                    return PFAC_STATUS_CUDA_ALLOC_FAILED;
-                }
-                c->batchOffsetsEntries = want;
-            }
-            if (hipMemcpy(c->d_stageIn[0], h_input + a, w - a, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(c->d_batchOffsets, local.data(), local.size() * sizeof(size_t), hipMemcpyHostToDevice) != hipSuccess) {
+            st = c->scratch.batchOffsets.reserve(local.size() > 4096 ? local.size() : 4096);
+            if (st != PFAC_STATUS_SUCCESS) return st;
+            if (hipMemcpy(d_in, h_input + a, w - a, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(c->scratch.batchOffsets.get(), local.data(), local.size() * sizeof(size_t), hipMemcpyHostToDevice) != hipSuccess) {
                 st = PFAC_STATUS_INTERNAL_ERROR;
                 break;
             }
-            st = foldStaged(c, c->d_stageIn[0], w - a);                    /* a caseless set: the window in place */
+            st = foldStaged(c, d_in, w - a);                    /* a caseless set: the window in place */
             if (st != PFAC_STATUS_SUCCESS) break;
-            st = matchBatchDeviceLocked(c, c->d_stageIn[0], w - a, c->d_batchOffsets, local.size() - 1, c->d_stageOut[0]);
+            st = matchBatchDeviceLocked(c, d_in, w - a, c->scratch.batchOffsets.get(), local.size() - 1, d_out);
             if (st == PFAC_STATUS_SUCCESS &&
-                hipMemcpy(h_matched_result + a, c->d_stageOut[0], (b - a) * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+                hipMemcpy(h_matched_result + a, d_out, (b - a) * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
                 st = PFAC_STATUS_INTERNAL_ERROR;
         }
     } catch (const std::bad_alloc &) { st = PFAC_STATUS_ALLOC_FAILED; }

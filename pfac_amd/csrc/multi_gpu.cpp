@@ -200,10 +200,8 @@ PFAC_status_t PFACX_matchFromHostReduceMultiGPU(PFAC_handle_t handle, char *h_in
     if (handle->platform != PFAC_PLATFORM_GPU) {
         counts.assign((size_t)(numDevices ? numDevices : 1), 0);
         st = onCpuWorkers(handle, h_inputString, size, numDevices, bound, [&](size_t i, size_t lo, size_t hi, const int *res) {
-            int z = 0;                                                           /* the slice's pairs at the slice's own offset, positions counted from the start of the stream */
-            for (size_t k = 0; k < hi - lo; k++)
-                if (res[k] > 0) { h_matched_result[lo + (size_t)z] = res[k]; h_pos[lo + (size_t)z] = (int)(lo + k); z++; }
-            counts[i] = z;
+            /* the slice's pairs at the slice's own offset, positions counted from the start of the stream */
+            counts[i] = compactPairs(res, hi - lo, (int)lo, h_matched_result + lo, h_pos + lo);
         });
     } else {
         int visible = 0;

@@ -44,26 +44,19 @@ void freeTables(PFAC_context *c)
     std::vector<int>().swap(c->h_dense);
     std::vector<Int2>().swap(c->h_hashRow);
     std::vector<Int2>().swap(c->h_hashVal);
-    devFree(c->d_dense);
-    devFree(c->d_hashRow);
-    devFree(c->d_hashVal);
-    devFree(c->d_chainSlots);
-    devFree(c->d_denseFast);
-    c->denseFastEntries = 0;
-    devFree(c->d_chainNarrow);
-    c->numChainNarrow = 0;
+    c->tables.releasePerfMode();
     std::vector<pfac::ChainSlot>().swap(c->h_chainSlots);
-    c->numChainSlots = 0;
     c->chainJumpLog2 = 0;
     c->numOfTableEntry = c->sizeOfTableEntry = c->sizeOfTableInBytes = 0;
 }
 
+/* the host calls' staging (host_pipeline.cpp: ensureHostStage): its buffers with their streams and events */
 void freeHostStage(PFAC_context *c)
 {
     for (int b = 0; b < 2; b++) {
-        devFree(c->d_stageIn[b]);
-        devFree(c->d_stageOut[b]);
-        devFree(c->d_stagePos[b]);
+        c->scratch.stageIn[b].release();
+        c->scratch.stageOut[b].release();
+        c->scratch.stagePos[b].release();
         if (c->evUp[b]) (void)hipEventDestroy(static_cast<hipEvent_t>(c->evUp[b]));
         if (c->evScan[b]) (void)hipEventDestroy(static_cast<hipEvent_t>(c->evScan[b]));
         if (c->evDown[b]) (void)hipEventDestroy(static_cast<hipEvent_t>(c->evDown[b]));
@@ -72,38 +65,14 @@ void freeHostStage(PFAC_context *c)
     if (c->stageUp) (void)hipStreamDestroy(static_cast<hipStream_t>(c->stageUp));
     if (c->stageDown) (void)hipStreamDestroy(static_cast<hipStream_t>(c->stageDown));
     c->stageUp = c->stageDown = nullptr;
-    c->hostStagePositions = 0;
 }
 
-/* what the batch calls keep (pfac_context.h): the pattern lengths go with the set, the rest is grow-only scratch */
-void freeBatchScratch(PFAC_context *c)
+/* everything the calls have left on the device (PFACX_trim; the set's end) */
+static void freeScratch(PFAC_context *c)
 {
-    devFree(c->d_patternLen);
-    c->patternLenEntries = 0;
-    devFree(c->d_batchOffsets);
-    c->batchOffsetsEntries = 0;
-    if (c->d_batchScratch) { (void)hipFree(c->d_batchScratch); c->d_batchScratch = nullptr; }
-    c->batchScratchBytes = 0;
-}
-
-/* what the all-match calls keep (pfac_context.h): the prefix table goes with the set, the rest is grow-only scratch */
-void freeAllScratch(PFAC_context *c)
-{
-    devFree(c->d_allTable);
-    c->allTableEntries = 0;
-    devFree(c->d_allPairs);
-    c->allPairsEntries = 0;
-    devFree(c->d_allSegFirst);
-    c->allSegFirstEntries = 0;
-    if (c->d_allScratch) { (void)hipFree(c->d_allScratch); c->d_allScratch = nullptr; }
-    c->allScratchBytes = 0;
-}
-
-/* the caseless sets' fold scratch (pfac_context.h) */
-void freeFoldScratch(PFAC_context *c)
-{
-    devFree(c->d_foldScratch);
-    c->foldScratchBytes = 0;
+    freeHostStage(c);
+    c->scratch.release();
+    c->orderCleanBase = nullptr;
 }
 
 /* The fold of a caseless set's input, once, where it enters the library: every *Locked function and every scan behind
@@ -114,18 +83,10 @@ PFAC_status_t foldDeviceInput(PFAC_context *c, char *d_in, size_t size, char **d
     *d_use = d_in;
     if (!c->caseInsensitive || size == 0) return PFAC_STATUS_SUCCESS;
     if (!c->hasDevice || !c->module || !c->fold_input_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
-    if (c->foldScratchBytes < size) {
-        freeFoldScratch(c);
-        const size_t want = (size + 255) & ~size_t(255);
-        if (hipMalloc(reinterpret_cast<void **>(&c->d_foldScratch), want) != hipSuccess) {
-            (void)hipGetLastError();
-            c->d_foldScratch = nullptr;
-            return PFAC_STATUS_CUDA_ALLOC_FAILED;
-        }
-        c->foldScratchBytes = want;
-    }
-    const PFAC_status_t st = c->fold_input_ptr(c, d_in, c->d_foldScratch, size);
-    if (st == PFAC_STATUS_SUCCESS) *d_use = c->d_foldScratch;
+    PFAC_status_t st = c->scratch.fold.reserve((size + 255) & ~size_t(255));
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    st = c->fold_input_ptr(c, d_in, c->scratch.fold.get(), size);
+    if (st == PFAC_STATUS_SUCCESS) *d_use = c->scratch.fold.get();
     return st;
 }
 
@@ -142,27 +103,11 @@ void freeResources(PFAC_context *c)
 {
     freeTables(c);
     std::vector<int>().swap(c->h_initialRow);
-    devFree(c->d_initialRow);
-    devFree(c->d_gram3);
-    devFree(c->d_shortBits);
-    devFree(c->d_ladder);
-    devFree(c->d_gram1);
-    devFree(c->d_prefix4);
-    devFree(c->d_tail);
-    devFree(c->d_workCounters);
+    c->tables.release();
     if (c->h_modeHint) { (void)hipHostFree(c->h_modeHint); c->h_modeHint = c->d_modeHint = nullptr; }
-    devFree(c->d_reduceScratch);
-    c->orderCleanBase = nullptr;
-    c->reduceScratchBytes = 0;
-    freeHostStage(c);
+    freeScratch(c);
     for (auto &e : c->evTime) { if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e)); e = nullptr; }
     c->kernelTiming = c->evTimeRecorded = false;
-    devFree(c->d_final3);
-    devFree(c->d_denseList);
-    c->denseListEntries = 0;
-    freeBatchScratch(c);
-    freeAllScratch(c);
-    freeFoldScratch(c);
     for (auto &child : c->children) (void)PFAC_destroy(child.second);
     c->children.clear();
     c->fa = pfac::Automaton();
@@ -184,23 +129,20 @@ PFAC_status_t uploadChainedHashTable(PFAC_context *c)
         if (st != PFAC_STATUS_SUCCESS) return st;
     }
     if (!c->hasDevice) return PFAC_STATUS_SUCCESS;
-    c->numChainSlots = c->h_chainSlots.size();
-    st = upload(c->d_chainSlots, c->h_chainSlots.data(), c->h_chainSlots.size());
+    st = c->tables.chainSlots.upload(c->h_chainSlots.data(), c->h_chainSlots.size());
     if (st != PFAC_STATUS_SUCCESS) return st;
     {   /* the narrow form for the tiled kernel on text (pfac_context.h); without it that kernel walks the wide one */
         std::vector<pfac::ChainSlot> narrow;
         int lg = 0;
         if (pfac::buildChainedHashTable(c->fa, narrow, lg, /*narrow=*/true) == PFAC_STATUS_SUCCESS && !narrow.empty() &&
-            upload(c->d_chainNarrow, narrow.data(), narrow.size()) == PFAC_STATUS_SUCCESS) {
-            c->numChainNarrow = narrow.size();
+            c->tables.chainNarrow.upload(narrow.data(), narrow.size()) == PFAC_STATUS_SUCCESS) {
             c->chainNarrowJumpLog2 = lg;
         } else {
-            devFree(c->d_chainNarrow);
-            c->numChainNarrow = 0;
+            c->tables.chainNarrow.release();
             (void)hipGetLastError();
         }
     }
-    /* the dense table next to it for a small set that does not fold (PFAC_context::d_denseFast): states inside chains -- one way on, nothing ends there --
+    /* the dense table next to it for a small set that does not fold (DeviceTables::denseFast): states inside chains -- one way on, nothing ends there --
      * are what the chained table saves steps on; a set with less than a quarter of them keeps int[S][256] too */
     const pfac::Automaton &fa = c->fa;
     if (fa.numStates > fa.initialState && fa.numStates <= pfac::kDenseFastMaxStates) {
@@ -210,8 +152,10 @@ PFAC_status_t uploadChainedHashTable(PFAC_context *c)
             std::vector<int> dense;
             if (!c->h_dense.empty()) dense = c->h_dense;
             else if (pfac::buildDenseTable(fa, dense) != PFAC_STATUS_SUCCESS) dense.clear();
-            if (!dense.empty() && upload(c->d_denseFast, dense.data(), dense.size()) == PFAC_STATUS_SUCCESS) c->denseFastEntries = dense.size();
-            else { devFree(c->d_denseFast); c->denseFastEntries = 0; (void)hipGetLastError(); }      /* no table: AUTO keeps to the chained one */
+            if (dense.empty() || c->tables.denseFast.upload(dense.data(), dense.size()) != PFAC_STATUS_SUCCESS) {
+                c->tables.denseFast.release();                 /* no table: AUTO keeps to the chained one */
+                (void)hipGetLastError();
+            }
         }
     }
     return PFAC_STATUS_SUCCESS;
@@ -237,12 +181,10 @@ static PFAC_status_t ensureDeviceRefTable(PFAC_context *c, bool tablesLocked = f
     PFAC_status_t st = ensureHostRefTable(c, tablesLocked);
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (c->perfMode == PFAC_TIME_DRIVEN) {
-        if (!c->d_dense) st = upload(c->d_dense, c->h_dense.data(), c->h_dense.size());
-    } else if (!c->d_hashRow || !c->d_hashVal) {
-        devFree(c->d_hashRow);
-        devFree(c->d_hashVal);
-        st = upload(c->d_hashRow, c->h_hashRow.data(), c->h_hashRow.size());
-        if (st == PFAC_STATUS_SUCCESS) st = upload(c->d_hashVal, c->h_hashVal.data(), c->h_hashVal.size());
+        if (!c->tables.dense) st = c->tables.dense.upload(c->h_dense.data(), c->h_dense.size());
+    } else if (!c->tables.hashRow || !c->tables.hashVal) {
+        st = c->tables.hashRow.upload(c->h_hashRow.data(), c->h_hashRow.size());
+        if (st == PFAC_STATUS_SUCCESS) st = c->tables.hashVal.upload(c->h_hashVal.data(), c->h_hashVal.size());
     }
     return st;
 }
@@ -264,7 +206,7 @@ PFAC_status_t bindTable(PFAC_context *c)
         c->sizeOfTableEntry = sizeof(Int2);
     }
     c->sizeOfTableInBytes = c->numOfTableEntry * c->sizeOfTableEntry;
-    if (c->hasDevice && !c->d_chainSlots) {
+    if (c->hasDevice && !c->tables.chainSlots) {
         st = uploadChainedHashTable(c);
         if (st == PFAC_STATUS_SUCCESS && c->kernelVariant == PFACX_KERNEL_REFTABLE) st = ensureDeviceRefTable(c, /*tablesLocked=*/true);   /* every caller of bindTable holds tablesInUse */
         if (st != PFAC_STATUS_SUCCESS) { freeTables(c); return st; }
@@ -272,26 +214,26 @@ PFAC_status_t bindTable(PFAC_context *c)
     return PFAC_STATUS_SUCCESS;
 }
 
-/* tables that do not depend on perfMode: initial-state row and prefilter (built, or brought along by a compiled file) */
-PFAC_status_t bindCommon(PFAC_context *c, bool build)
+/* tables that do not depend on perfMode: initial-state row and prefilter */
+static PFAC_status_t bindCommon(PFAC_context *c)
 {
-    if (build) {
-        pfac::buildInitialRow(c->fa, c->h_initialRow);
-        pfac::buildFilter(c->fa, c->filter);
-    }
+    pfac::buildInitialRow(c->fa, c->h_initialRow);
+    pfac::buildFilter(c->fa, c->filter);
     if (!c->hasDevice) return PFAC_STATUS_SUCCESS;
-    PFAC_status_t st = upload(c->d_initialRow, c->h_initialRow.data(), c->h_initialRow.size());
-    if (st == PFAC_STATUS_SUCCESS) st = upload(c->d_gram3, c->filter.gram3.data(), c->filter.gram3.size());
-    if (st == PFAC_STATUS_SUCCESS) st = upload(c->d_shortBits, c->filter.shortBits.data(), c->filter.shortBits.size());
-    if (st == PFAC_STATUS_SUCCESS) st = upload(c->d_ladder, c->filter.ladder.data(), c->filter.ladder.size());
-    if (st == PFAC_STATUS_SUCCESS) st = upload(c->d_final3, c->filter.final3.data(), c->filter.final3.size());
-    if (st == PFAC_STATUS_SUCCESS) st = upload(c->d_gram1, c->filter.gram1.data(), c->filter.gram1.size());
-    if (st == PFAC_STATUS_SUCCESS) st = upload(c->d_prefix4, c->filter.prefix4.data(), c->filter.prefix4.size());
-    if (st == PFAC_STATUS_SUCCESS && !c->filter.tail.empty()) st = upload(c->d_tail, c->filter.tail.data(), c->filter.tail.size());
-    else if (st == PFAC_STATUS_SUCCESS && !c->filter.tailG.empty()) st = upload(c->d_tail, c->filter.tailG.data(), c->filter.tailG.size());
+    pfac::DeviceTables &t = c->tables;
+    const pfac::Filter &f = c->filter;
+    const std::vector<uint32_t> &tail = f.tail.empty() ? f.tailG : f.tail;      /* a set has the table in one form, or in neither */
+    PFAC_status_t st = t.initialRow.upload(c->h_initialRow.data(), c->h_initialRow.size());
+    if (st == PFAC_STATUS_SUCCESS) st = t.gram3.upload(f.gram3.data(), f.gram3.size());
+    if (st == PFAC_STATUS_SUCCESS) st = t.shortBits.upload(f.shortBits.data(), f.shortBits.size());
+    if (st == PFAC_STATUS_SUCCESS) st = t.ladder.upload(f.ladder.data(), f.ladder.size());
+    if (st == PFAC_STATUS_SUCCESS) st = t.final3.upload(f.final3.data(), f.final3.size());
+    if (st == PFAC_STATUS_SUCCESS) st = t.gram1.upload(f.gram1.data(), f.gram1.size());
+    if (st == PFAC_STATUS_SUCCESS) st = t.prefix4.upload(f.prefix4.data(), f.prefix4.size());
+    if (st == PFAC_STATUS_SUCCESS && !tail.empty()) st = t.tail.upload(tail.data(), tail.size());
     if (st == PFAC_STATUS_SUCCESS) {               /* chunk counters of the scan kernel, reset before every launch */
         const std::vector<unsigned int> zeros(pfac::kWorkCounterWords, 0u);
-        st = upload(c->d_workCounters, zeros.data(), zeros.size());
+        st = t.workCounters.upload(zeros.data(), zeros.size());
     }
     if (st == PFAC_STATUS_SUCCESS && !c->h_modeHint) {
         /* the word the scan kernel tells the host through what the stream looked like (pfac_context.h); without it AUTO means
@@ -356,31 +298,37 @@ PFAC_status_t loadModule(PFAC_context *c)
     return PFAC_STATUS_SUCCESS;
 }
 
-/* ref the CPU branch of matchFromHost / matchFromHostReduce, PFAC.cpp:899-913 */
-PFAC_status_t matchHostOnCpuPlatform(PFAC_context *c, const char *in, size_t n, int *out)
+/* The CPU platforms (ref the CPU branch of matchFromHost / matchFromHostReduce, PFAC.cpp:899-913), in two steps for a caller that holds c->lock
+ * and drives several threads through one handle (multi_gpu.cpp: the workers of a CPU-platform handle): the tables first, once -- the dense
+ * table is built on first use (ensureHostRefTable) --, then any number of threads may match side by side */
+PFAC_status_t prepareCpuPlatformLocked(PFAC_context *c) { return ensureHostRefTable(c); }
+PFAC_status_t matchHostOnCpuPlatformPrepared(PFAC_context *c, const char *in, size_t n, int *out)
 {
-    {   /* the dense table is built on first use (ensureHostRefTable) */
-        std::lock_guard<std::mutex> guard(c->lock);
-        const PFAC_status_t st = ensureHostRefTable(c);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-    }
     bool omp = false;
     if (c->platform == PFAC_PLATFORM_CPU_OMP) omp = (std::getenv("OMP_NUM_THREADS") != nullptr);
     std::shared_lock<std::shared_mutex> r(c->tablesInUse);             /* a setter on another thread waits until the match is through */
     if (c->perfMode == PFAC_TIME_DRIVEN && c->h_dense.empty()) return PFAC_STATUS_PATTERNS_NOT_READY;   /* ... or has just replaced the set: its tables are built on the next call */
     return pfac::matchOnCpu(c, reinterpret_cast<const unsigned char *>(in), n, out, omp);
 }
-
-/* ... for a caller that holds c->lock and drives several threads through one handle (multi_gpu.cpp: the workers of a CPU-platform handle):
- * the tables first, once; then any number of threads may match side by side */
-PFAC_status_t prepareCpuPlatformLocked(PFAC_context *c) { return ensureHostRefTable(c); }
-PFAC_status_t matchHostOnCpuPlatformPrepared(PFAC_context *c, const char *in, size_t n, int *out)
+PFAC_status_t matchHostOnCpuPlatform(PFAC_context *c, const char *in, size_t n, int *out)
 {
-    bool omp = false;
-    if (c->platform == PFAC_PLATFORM_CPU_OMP) omp = (std::getenv("OMP_NUM_THREADS") != nullptr);
-    std::shared_lock<std::shared_mutex> r(c->tablesInUse);
-    if (c->perfMode == PFAC_TIME_DRIVEN && c->h_dense.empty()) return PFAC_STATUS_PATTERNS_NOT_READY;
-    return pfac::matchOnCpu(c, reinterpret_cast<const unsigned char *>(in), n, out, omp);
+    PFAC_status_t st;
+    {
+        std::lock_guard<std::mutex> guard(c->lock);
+        st = prepareCpuPlatformLocked(c);
+    }
+    return st == PFAC_STATUS_SUCCESS ? matchHostOnCpuPlatformPrepared(c, in, n, out) : st;
+}
+
+/* the end of every reader of a pattern set (pfac_host.h) */
+PFAC_status_t bindCompiledSet(PFAC_context *c)
+{
+    c->isPatternsReady = true;
+    PFAC_status_t st;
+    try { st = bindCommon(c); } catch (const std::bad_alloc &) { st = PFAC_STATUS_ALLOC_FAILED; }
+    if (st == PFAC_STATUS_SUCCESS) st = bindTable(c);
+    if (st != PFAC_STATUS_SUCCESS) freeResources(c);
+    return st;
 }
 
 } // namespace pfac_internal
@@ -531,12 +479,8 @@ static PFAC_status_t readFromFile(PFAC_handle_t handle, const char *filename, un
 
     PFAC_status_t st = pfac::compilePatternFile(filename, handle->fa, flags);
     if (st != PFAC_STATUS_SUCCESS) { freeResources(handle); return st; }
-    handle->isPatternsReady = true;
     handle->caseInsensitive = (flags & PFACX_READ_NOCASE) != 0;
-    st = bindCommon(handle);
-    if (st == PFAC_STATUS_SUCCESS) st = bindTable(handle);
-    if (st != PFAC_STATUS_SUCCESS) { freeResources(handle); return st; }
-    return PFAC_STATUS_SUCCESS;
+    return bindCompiledSet(handle);
 }
 
 static PFAC_status_t readFromMemory(PFAC_handle_t handle, const char *patterns, size_t size, unsigned int flags)
@@ -552,12 +496,8 @@ static PFAC_status_t readFromMemory(PFAC_handle_t handle, const char *patterns, 
         st = pfac::compilePatternBytes(std::vector<unsigned char>(patterns, patterns + size), handle->fa, flags);
     } catch (const std::bad_alloc &) { st = PFAC_STATUS_ALLOC_FAILED; }
     if (st != PFAC_STATUS_SUCCESS) { freeResources(handle); return st; }
-    handle->isPatternsReady = true;
     handle->caseInsensitive = (flags & PFACX_READ_NOCASE) != 0;
-    st = bindCommon(handle);
-    if (st == PFAC_STATUS_SUCCESS) st = bindTable(handle);
-    if (st != PFAC_STATUS_SUCCESS) { freeResources(handle); return st; }
-    return PFAC_STATUS_SUCCESS;
+    return bindCompiledSet(handle);
 }
 
 PFAC_status_t PFAC_readPatternFromFile(PFAC_handle_t handle, char *filename) { return readFromFile(handle, filename, 0); }
@@ -616,10 +556,7 @@ PFAC_status_t PFAC_matchFromDeviceReduce(PFAC_handle_t handle, char *d_inputStri
     char *in = d_inputString;
     const PFAC_status_t st = foldDeviceInput(handle, d_inputString, size, &in);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    PFAC_reduce_kernel_protoType fn =
-        handle->perfMode == PFAC_TIME_DRIVEN ? handle->reduce_kernel_ptr : handle->reduce_inplace_kernel_ptr;
-    return fn(handle, reinterpret_cast<int *>(in), (int)size, d_matched_result, d_pos, h_num_matched,
-              nullptr, nullptr);
+    return reduceOnDevice(handle, in, size, d_matched_result, d_pos, h_num_matched);
 }
 
 PFAC_status_t PFAC_matchFromHostReduce(PFAC_handle_t handle, char *h_inputString, size_t size,
@@ -634,12 +571,7 @@ PFAC_status_t PFAC_matchFromHostReduce(PFAC_handle_t handle, char *h_inputString
     if (handle->platform != PFAC_PLATFORM_GPU) {                  /* ref PFAC.cpp:1036-1068 */
         PFAC_status_t st = matchHostOnCpuPlatform(handle, h_inputString, size, h_matched_result);
         if (st != PFAC_STATUS_SUCCESS) return st;
-        int z = 0;
-        for (size_t i = 0; i < size; i++) {
-            const int m = h_matched_result[i];
-            if (m > 0) { h_matched_result[z] = m; h_pos[z] = (int)i; z++; }
-        }
-        *h_num_matched = z;
+        *h_num_matched = compactPairs(h_matched_result, size, 0, h_matched_result, h_pos);
         return PFAC_STATUS_SUCCESS;
     }
     if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
@@ -695,37 +627,12 @@ PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info)
         v.chainJumpLog2 = handle->h_chainSlots.empty() ? 0 : handle->chainJumpLog2;
         v.chainSlots = handle->h_chainSlots.size();
         v.multiProcessorCount = handle->multiProcessorCount;
-        /* what the pattern set holds on the device: the chained table, the initial row, the prefilter bitmaps, the launch
-         * counters -- and the reference-layout table only while PFACX_KERNEL_REFTABLE has asked for it */
-        size_t dev = 0;
-        if (handle->d_chainSlots) dev += handle->numChainSlots * sizeof(pfac::ChainSlot);
-        if (handle->d_chainNarrow) dev += handle->numChainNarrow * sizeof(pfac::ChainSlot);
-        if (handle->d_dense) dev += handle->h_dense.size() * sizeof(int);
-        if (handle->d_denseFast) dev += handle->denseFastEntries * sizeof(int);
-        if (handle->d_hashRow) dev += handle->h_hashRow.size() * sizeof(Int2);
-        if (handle->d_hashVal) dev += handle->h_hashVal.size() * sizeof(Int2);
-        if (handle->d_initialRow) dev += handle->h_initialRow.size() * sizeof(int);
-        if (handle->d_gram3) dev += handle->filter.gram3.size() * sizeof(uint32_t);
-        if (handle->d_ladder) dev += handle->filter.ladder.size() * sizeof(uint32_t);
-        if (handle->d_final3) dev += handle->filter.final3.size() * sizeof(uint32_t);
-        if (handle->d_shortBits) dev += handle->filter.shortBits.size() * sizeof(uint32_t);
-        if (handle->d_gram1) dev += handle->filter.gram1.size() * sizeof(uint32_t);
-        if (handle->d_prefix4) dev += handle->filter.prefix4.size() * sizeof(uint32_t);
-        if (handle->d_tail) dev += (handle->filter.tail.size() + handle->filter.tailG.size()) * sizeof(uint32_t);
-        if (handle->d_workCounters) dev += pfac::kWorkCounterWords * sizeof(unsigned int);
-        dev += streamDeviceBytes(handle);      /* the carried bytes of device-fed streams: state, not scratch (PFACX_trim keeps them) */
-        v.deviceTableBytes = dev;
-        /* ... and what its calls have left allocated (grow-only, PFACX_trim gives it back): the two staging pieces of the host
-         * paths (input + ids + positions: 9 bytes per position), the scratch the compacted output is ordered through, the list
-         * of pattern-dense chunks, what the batch and all-match calls keep */
-        size_t scratch = 0;
-        if (handle->hostStagePositions) scratch += 2 * (((handle->hostStagePositions + 3) & ~size_t(3)) + 2 * handle->hostStagePositions * sizeof(int));
-        scratch += handle->reduceScratchBytes + handle->denseListEntries * sizeof(unsigned int);
-        scratch += handle->patternLenEntries * sizeof(int) + handle->batchOffsetsEntries * sizeof(size_t) + handle->batchScratchBytes;
-        scratch += handle->allTableEntries * sizeof(Int2) + handle->allPairsEntries * 2 * sizeof(int) + handle->allSegFirstEntries * sizeof(int) +
-                   handle->allScratchBytes;
-        scratch += handle->foldScratchBytes;
-        v.deviceScratchBytes = scratch;
+        /* what the pattern set holds on the device -- the chained tables, the initial row, the prefilter bitmaps, the launch counters, the
+         * reference-layout table only while PFACX_KERNEL_REFTABLE has asked for it -- and the carried bytes of device-fed streams: state, not
+         * scratch (PFACX_trim keeps them) */
+        v.deviceTableBytes = handle->tables.bytes() + streamDeviceBytes(handle);
+        /* ... and what its calls have left allocated (grow-only, PFACX_trim gives it back) */
+        v.deviceScratchBytes = handle->scratch.bytes();
         if (handle->h_modeHint) {
             v.streamNearMisses = (int)static_cast<volatile const unsigned int *>(handle->h_modeHint)[0];
             v.streamDense = (int)static_cast<volatile const unsigned int *>(handle->h_modeHint)[1];
@@ -794,22 +701,13 @@ PFAC_status_t PFACX_getTable(PFAC_handle_t handle, PFACX_table_t which, const vo
  * stored (S KiB: 0.5 GB for the 30 k-pattern set), it is refilled from the edges in a fraction of a second. */
 extern "C" {
 
-/* pfac_ext.h: give back the grow-only device buffers of the handle (staging of PFAC_matchFromHost, copies of
- * PFAC_matchFromHostReduce, sort scratch, the dense-chunk list, what the batch and all-match calls keep, the fold scratch of a caseless set); the next call that needs one allocates
- * it again */
+/* pfac_ext.h: give back the grow-only device buffers of the handle (pfac::DeviceScratch: whatever its calls have left allocated); the next
+ * call that needs one allocates it again */
 PFAC_status_t PFACX_trim(PFAC_handle_t handle)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
     std::lock_guard<std::mutex> guard(handle->lock);
-    freeHostStage(handle);
-    devFree(handle->d_reduceScratch);
-    handle->reduceScratchBytes = 0;
-    handle->orderCleanBase = nullptr;
-    devFree(handle->d_denseList);
-    handle->denseListEntries = 0;
-    freeBatchScratch(handle);
-    freeAllScratch(handle);
-    freeFoldScratch(handle);
+    freeScratch(handle);
     for (auto &child : handle->children) if (child.second) (void)PFACX_trim(child.second);
     return PFAC_STATUS_SUCCESS;
 }
@@ -837,10 +735,10 @@ PFAC_status_t PFACX_getScanStats(PFAC_handle_t handle, PFACX_scan_stats_t *stats
     std::memset(stats, 0, sizeof(*stats));
     if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
     std::lock_guard<std::mutex> guard(handle->lock);
-    if (!handle->hasDevice || !handle->d_workCounters) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (!handle->hasDevice || !handle->tables.workCounters.get()) return PFAC_STATUS_LIB_NOT_EXIST;
     unsigned long long v[pfac::kStatsCount + 3];             /* published by the last block of the launch: scan_*.hip, the kernel's end */
     if (hipStreamSynchronize(nullptr) != hipSuccess ||
-        hipMemcpy(v, handle->d_workCounters + pfac::kStatsPublishedWord, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(v, handle->tables.workCounters.get() + pfac::kStatsPublishedWord, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
         return PFAC_STATUS_INTERNAL_ERROR;
     stats->walkerRounds = v[0]; stats->laneSteps = v[1]; stats->walksStarted = v[2]; stats->level1Hits = v[3];
     stats->ladderCandidates = v[5];

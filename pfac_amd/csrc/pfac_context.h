@@ -17,7 +17,10 @@
 #include <shared_mutex>
 #include <string>
 #include <utility>
+#include <type_traits>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "PFAC.h"
 #include "pfac_ext.h"
@@ -272,6 +275,125 @@ constexpr size_t kStreamSeamLdsBytes = 48 * 1024;
 /* the ASCII fold of PFACX_READ_NOCASE: 'A'-'Z' -> 'a'-'z', every other byte unchanged (scan_fold.hip folds dwords the same way) */
 inline unsigned char asciiFold(unsigned char b) { return (unsigned char)((unsigned)(b - 'A') < 26u ? b + 32 : b); }
 
+/* One device allocation of the handle: the pointer and the number of T it was allocated for.  Plain data without a destructor --
+ * libpfac.so and the kernel module share PFAC_context, built by two compilers -- so whoever owns one releases it (DeviceTables /
+ * DeviceScratch below enumerate the handle's).  The size a buffer grows to is the caller's business: reserve() allocates exactly
+ * what it is asked for. */
+template <class T>
+struct DeviceBuffer {
+    T *ptr = nullptr;
+    size_t entries = 0;
+
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer &) = delete;
+    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+
+    T *get() const { return ptr; }
+    explicit operator bool() const { return ptr != nullptr; }
+    size_t count() const { return entries; }
+    size_t bytes() const { return entries * sizeof(T); }
+    void release()
+    {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        entries = 0;
+    }
+    /* room for `count` elements; a buffer that has to grow loses its contents */
+    PFAC_status_t reserve(size_t count)
+    {
+        if (entries >= count) return PFAC_STATUS_SUCCESS;
+        release();
+        if (hipMalloc(reinterpret_cast<void **>(&ptr), count * sizeof(T)) != hipSuccess) {
+            (void)hipGetLastError();
+            ptr = nullptr;
+            return PFAC_STATUS_CUDA_ALLOC_FAILED;
+        }
+        entries = count;
+        return PFAC_STATUS_SUCCESS;
+    }
+    /* a fresh copy of src[0, count) (an empty table still gets an allocation: its pointer says that it is there) */
+    PFAC_status_t upload(const T *src, size_t count)
+    {
+        release();
+        const PFAC_status_t st = reserve(count ? count : 1);
+        if (st != PFAC_STATUS_SUCCESS) return st;
+        entries = count;
+        if (count && hipMemcpy(ptr, src, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+            release();
+            return PFAC_STATUS_INTERNAL_ERROR;
+        }
+        return PFAC_STATUS_SUCCESS;
+    }
+};
+static_assert(std::is_standard_layout<DeviceBuffer<int>>::value && std::is_trivially_destructible<DeviceBuffer<int>>::value &&
+              !std::is_copy_constructible<DeviceBuffer<int>>::value, "plain data in both libraries; freed explicitly, by one owner");
+
+/* What the pattern set keeps on the device (PFACX_getInfo: deviceTableBytes).  forEach is the one list of them. */
+struct DeviceTables {
+    /* the reference-layout table of the perf mode (ref d_PFAC_table / d_hashRowPtr / d_hashValPtr): uploaded only while
+     * PFACX_KERNEL_REFTABLE asks for it */
+    DeviceBuffer<int> dense;
+    DeviceBuffer<Int2> hashRow, hashVal;
+    DeviceBuffer<ChainSlot> chainSlots;       /* the chained form of hashRow / hashVal every product kernel walks (tables.cpp); PFAC_context::chainJumpLog2 has its layout */
+    /* the NARROW chained table (tables.cpp: no wide buckets, no long jump table, no units): what the tiled kernel walks while the handle's stream
+     * is not full of near misses; device only (built from the trie with the set, dropped with it) */
+    DeviceBuffer<ChainSlot> chainNarrow;
+    /* A small pattern set whose states hardly fold into chains (most states final or branching: the patterns a, aa, ..., a x 8 of the all-match test) gains
+     * nothing from the chained table -- a step consumes one byte either way, and the chained step is three times the instructions of one gathered dword of
+     * int[S][256].  Such a set also keeps the DENSE table on the device (S KiB, at most kDenseFastMaxStates states), in both perf modes, and
+     * PFACX_KERNEL_AUTO sends the big calls of a pattern-dense stream to the tiled frame over it (scan_module.hip: scan) */
+    DeviceBuffer<int> denseFast;
+    /* ... and what does not depend on the perf mode */
+    DeviceBuffer<int> initialRow;
+    DeviceBuffer<uint32_t> gram3, shortBits, ladder, final3;
+    DeviceBuffer<uint32_t> gram1, prefix4;    /* the compacted-output kernel's level 1 and depth-4 test (struct Filter) */
+    DeviceBuffer<uint32_t> tail;              /* the tail table (struct Filter: `tail`, or `tailG` -- a set has one of them), or empty */
+    DeviceBuffer<unsigned int> workCounters;  /* kWorkCounterWords: next-chunk counters of the scan kernel (one per 128 B) */
+
+    template <class F> void forEachPerfMode(F f) { f(dense); f(hashRow); f(hashVal); f(chainSlots); f(chainNarrow); f(denseFast); }
+    template <class F> void forEach(F f)
+    {
+        forEachPerfMode(f);
+        f(initialRow); f(gram3); f(shortBits); f(ladder); f(final3); f(gram1); f(prefix4); f(tail); f(workCounters);
+    }
+    void releasePerfMode() { forEachPerfMode([](auto &b) { b.release(); }); }      /* PFAC_setPerfMode rebuilds these, and only these */
+    void release() { forEach([](auto &b) { b.release(); }); }
+    size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }
+};
+
+/* What the calls leave allocated on the device, grow-only, so that a call does not pay for hipMalloc / hipFree: PFACX_trim gives it
+ * back, PFACX_getInfo counts it (deviceScratchBytes).  forEach is the one list of them. */
+struct DeviceScratch {
+    /* staging of the host calls on the GPU platform (host_pipeline.cpp): two input, result and position buffers of a piece
+     * (+ overlap); their copy streams and events are PFAC_context::stageUp ... */
+    DeviceBuffer<char> stageIn[2];
+    DeviceBuffer<int> stageOut[2], stagePos[2];
+    DeviceBuffer<char> reduce;                /* the arrays the compacted-output path orders its pairs through (scan_order.inc) */
+    DeviceBuffer<unsigned int> denseList;     /* chunks the filter kernel found pattern-dense and left to the simple kernel (scan_*.hip): one entry per chunk of a launch */
+    /* the batch calls (PFACX_matchBatch*): device copy of fa.patternLen (uploaded on the first batch call), the offsets of a piece of
+     * PFACX_matchBatchFromHost, the compaction scratch of PFACX_matchBatchFromDeviceReduce (scan_batch.hip) */
+    DeviceBuffer<int> patternLen;
+    DeviceBuffer<size_t> batchOffsets;
+    DeviceBuffer<char> batch;
+    /* the all-match calls (PFACX_matchAll*): device copy of {fa.prefixPattern, fa.chainLen} by id (uploaded on the first call that
+     * expands), the ordered longest pairs (ONE allocation of 2 x entries ints: the ids, then the positions; the ordering of
+     * PFACX_allReduce writes them, scan_module.hip), the first longest pair of each segment (batch form), the expansion's scratch
+     * (scan_all.hip) */
+    DeviceBuffer<Int2> allTable;
+    DeviceBuffer<int> allPairs;
+    DeviceBuffer<int> allSegFirst;
+    DeviceBuffer<char> all;
+    DeviceBuffer<char> fold;                  /* caseless sets: the caller's device input folded (PFACX_foldInput), what the scan of a device call reads instead; 256-byte granules */
+
+    template <class F> void forEach(F f)
+    {
+        for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
+        f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(fold);
+    }
+    void release() { forEach([](auto &b) { b.release(); }); }
+    size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }
+};
+
 } // namespace pfac
 
 struct PFAC_context {
@@ -289,51 +411,25 @@ struct PFAC_context {
     std::vector<pfac::Int2> h_hashVal;
     std::vector<int> h_initialRow;            /* 256 ints, valid in both modes */
 
-    /* device tables */
-    int *d_dense = nullptr;
-    pfac::Int2 *d_hashRow = nullptr;
-    pfac::Int2 *d_hashVal = nullptr;
-    int *d_initialRow = nullptr;
-    /* A small pattern set whose states hardly fold into chains (most states final or branching: the patterns a, aa, ..., a x 8 of the all-match test) gains
-     * nothing from the chained table -- a step consumes one byte either way, and the chained step is three times the instructions of one gathered dword of
-     * int[S][256].  Such a set also keeps the DENSE table on the device (S KiB, at most kDenseFastMaxStates states), in both perf modes, and
-     * PFACX_KERNEL_AUTO sends the big calls of a pattern-dense stream to the tiled frame over it (scan_module.hip: scan) */
-    int *d_denseFast = nullptr;
-    size_t denseFastEntries = 0;
     std::vector<pfac::ChainSlot> h_chainSlots;               /* host copy of the chained table (PFACX_saveCompiled)       */
-    pfac::ChainSlot *d_chainSlots = nullptr;  /* device-only chained form of hashRow/hashVal (tables.cpp)          */
-    size_t numChainSlots = 0;
-    /* the NARROW chained table (tables.cpp: no wide buckets, no long jump table, no units): what the tiled kernel walks while the handle's stream
-     * is not full of near misses; device only (built from the trie with the set, dropped with it) */
-    pfac::ChainSlot *d_chainNarrow = nullptr;
-    size_t numChainNarrow = 0;
-    int chainNarrowJumpLog2 = 0;
-    int chainJumpLog2 = 0;                    /* the chained table is N = numChainSlots / 2 slot headers, then as many extension units; the last
+
+    /* everything the set keeps on the device, and everything the calls leave there */
+    pfac::DeviceTables tables;
+    pfac::DeviceScratch scratch;
+
+    int chainNarrowJumpLog2 = 0;              /* log2 of the narrow table's one jump table (tables.chainNarrow) */
+    int chainJumpLog2 = 0;                    /* the chained table is N = tables.chainSlots.count() / 2 slot headers, then as many extension units; the last
                                                  2^J headers are the LONG jump table, the 2^J before them the jump table, the 256 before
                                                  those the initial state's bucket: buckets | root(256) | jump(2^J) | long jump(2^J) | N units
                                                  (tables.cpp: buildChainedHashTable) */
-    uint32_t *d_gram3 = nullptr;
-    uint32_t *d_shortBits = nullptr;
-    uint32_t *d_ladder = nullptr;
-    uint32_t *d_gram1 = nullptr, *d_prefix4 = nullptr;   /* the compacted-output kernel's level 1 and depth-4 test (struct Filter) */
-    uint32_t *d_tail = nullptr;                          /* the tail table (struct Filter: `tail`, or `tailG` -- a set has one of them), or null */
-    /* grow-only scratch of the compacted-output path (the arrays the pairs are ordered through), owned by the handle so that a
-     * call does not pay for hipMalloc/hipFree */
-    void *d_reduceScratch = nullptr;
-    size_t reduceScratchBytes = 0;
-    /* the counters at the head of the scratch as the last ordered call left them: all zero (the ordering launches clean up behind themselves, scan_order.inc), so
+    /* the counters at the head of scratch.reduce as the last ordered call left them: all zero (the ordering launches clean up behind themselves, scan_order.inc), so
      * the next call with the same layout needs no memset in front of its scan; null = not known to be zero */
     const void *orderCleanBase = nullptr;
     size_t orderCleanBytes = 0;
     unsigned int orderSeq = 0;                /* number of the last ordered call (pfac_order_done writes it to host memory) */
     unsigned int orderParity = 0;             /* which of the two pairs of call counters the next ordered call uses */
-    /* staging of PFAC_matchFromHost / PFAC_matchFromHostReduce on the GPU platform (pfac_api.cpp): two input and two result
-     * buffers of hostStageChunk (+ overlap) positions, two copy streams, events; created on first use */
-    char *d_stageIn[2] = {nullptr, nullptr};
-    int *d_stageOut[2] = {nullptr, nullptr};
     bool reduceUnordered = false;             /* the compacted-output scan may leave its pairs in any order (set around the calls of PFAC_matchFromHost) */
-    int *d_stagePos[2] = {nullptr, nullptr};  /* positions of the compacted results of a piece (PFAC_matchFromHost) */
-    size_t hostStagePositions = 0;            /* capacity of each staging buffer, in positions */
+    /* the copy streams and events of the host calls' staging (scratch.stageIn ...; host_pipeline.cpp), created with the buffers */
     void *stageUp = nullptr, *stageDown = nullptr;                 /* hipStream_t */
     mutable bool countersDirty = false;                            /* a filter launch failed: the next one clears the launch counters itself */
     unsigned int denseParity = 0;                                  /* which of the two dense-chunk counters the next filter launch uses */
@@ -342,12 +438,10 @@ struct PFAC_context {
     void *evTime[2] = {nullptr, nullptr};                          /* hipEvent_t */
     mutable bool evTimeRecorded = false;
     void *evUp[2] = {nullptr, nullptr}, *evScan[2] = {nullptr, nullptr}, *evDown[2] = {nullptr, nullptr};   /* hipEvent_t */
-    unsigned int *d_workCounters = nullptr;   /* kWorkCounterWords: next-chunk counters of the scan kernel (one per 128 B) */
     /* one word of mapped host memory the last block of a full-result filter launch writes: 1 = the stream was full of near misses
      * (scan_filter.hip: launchChained picks the next launch's walker from it); h_: the host's pointer, d_: the device's */
     unsigned int *h_modeHint = nullptr, *d_modeHint = nullptr;
     int walker = PFACX_WALKER_AUTO;
-    uint32_t *d_final3 = nullptr;
 
     /* ref numOfTableEntry / sizeOfTableEntry / sizeOfTableInBytes, PFAC_P.h:131-133 */
     size_t numOfTableEntry = 0;
@@ -383,35 +477,7 @@ struct PFAC_context {
     std::shared_mutex tablesInUse;
     /* per-device handles of PFACX_matchFromHostMultiGPU, created on first use: (device, handle) */
     std::vector<std::pair<int, PFAC_context *>> children;
-    /* chunks the filter kernel found pattern-dense and left to the simple kernel (scan_*.hip): grow-only, one entry per chunk of a launch */
-    unsigned int *d_denseList = nullptr;
-    size_t denseListEntries = 0;
-    /* the batch calls (PFACX_matchBatch*): device copy of fa.patternLen (uploaded on the first batch call, dropped with the set), the
-     * offsets of a piece of PFACX_matchBatchFromHost, the compaction scratch of PFACX_matchBatchFromDeviceReduce (scan_batch.hip).
-     * Grow-only scratch: PFACX_trim frees them, deviceScratchBytes counts them */
-    int *d_patternLen = nullptr;
-    size_t patternLenEntries = 0;
-    size_t *d_batchOffsets = nullptr;
-    size_t batchOffsetsEntries = 0;
-    void *d_batchScratch = nullptr;
-    size_t batchScratchBytes = 0;
-    /* the all-match calls (PFACX_matchAll*): device copy of {fa.prefixPattern, fa.chainLen} by id (uploaded on the first call that
-     * expands), the ordered longest pairs (ids, then positions; the ordering of PFACX_allReduce writes them, scan_module.hip), the
-     * first longest pair of each segment (batch form), the expansion's scratch (scan_all.hip).  Grow-only scratch: PFACX_trim frees
-     * them, deviceScratchBytes counts them */
-    pfac::Int2 *d_allTable = nullptr;
-    size_t allTableEntries = 0;
-    int *d_allPairs = nullptr;
-    size_t allPairsEntries = 0;
-    int *d_allSegFirst = nullptr;
-    size_t allSegFirstEntries = 0;
-    void *d_allScratch = nullptr;
-    size_t allScratchBytes = 0;
     unsigned int allSeq = 0;                  /* number of the last expansion (pfac_all_done writes it to host memory) */
-    /* caseless sets: the caller's device input folded (PFACX_foldInput), what the scan of a device call reads instead.  Grow-only
-     * scratch, 256-byte aligned: PFACX_trim frees it, deviceScratchBytes counts it */
-    char *d_foldScratch = nullptr;
-    size_t foldScratchBytes = 0;
 
     /* streams (PFACX_stream*, stream_api.cpp): the open streams of this handle (PFAC_destroy closes them) and the number of the pattern set
      * they were opened on: whatever replaces or drops the set (freeResources) counts it up, and a stream of an older set is refused until

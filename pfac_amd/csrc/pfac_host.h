@@ -33,39 +33,17 @@ PFAC_status_t matchOnCpu(const PFAC_context *ctx, const unsigned char *in, size_
 #include <hip/hip_runtime_api.h>
 namespace pfac_internal {
 
-template <class T>
-void devFree(T *&p)
-{
-    if (p) { (void)hipFree(p); p = nullptr; }
-}
-
-template <class T>
-PFAC_status_t upload(T *&dst, const T *src, size_t count)
-{
-    const size_t bytes = (count ? count : 1) * sizeof(T);
-    if (hipMalloc(reinterpret_cast<void **>(&dst), bytes) != hipSuccess) {
-        dst = nullptr;
-        (void)hipGetLastError();
-        return PFAC_STATUS_CUDA_ALLOC_FAILED;
-    }
-    if (count && hipMemcpy(dst, src, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-        devFree(dst);
-        return PFAC_STATUS_INTERNAL_ERROR;
-    }
-    return PFAC_STATUS_SUCCESS;
-}
-
 /* positions per piece of the pipelined PFAC_matchFromHost: 32 Mi positions = 32 MiB up, 128 MiB down */
 constexpr size_t kHostPiece = size_t(32) << 20;
 
 /* pfac_api.cpp */
 void freeTables(PFAC_context *c);
-void freeHostStage(PFAC_context *c);
+void freeHostStage(PFAC_context *c);                  /* the staging buffers of the host calls with their streams and events */
 void freeResources(PFAC_context *c);
-void freeBatchScratch(PFAC_context *c);
-void freeAllScratch(PFAC_context *c);
 PFAC_status_t bindTable(PFAC_context *c);
-PFAC_status_t bindCommon(PFAC_context *c, bool build = true);
+/* the end of every reader of a pattern set (the caller holds both locks; c->fa is compiled and checked): the set is ready, its tables are
+ * built and uploaded -- or the handle is left empty */
+PFAC_status_t bindCompiledSet(PFAC_context *c);
 void correctTextureMode(PFAC_context *c);
 PFAC_status_t matchHostOnCpuPlatform(PFAC_context *c, const char *in, size_t n, int *out);
 PFAC_status_t prepareCpuPlatformLocked(PFAC_context *c);                                        /* the caller holds c->lock */
@@ -80,7 +58,23 @@ PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t 
  * scratch).  foldStaged: a staging piece in place, on the default stream behind its upload (nothing for a case-sensitive handle) */
 PFAC_status_t foldDeviceInput(PFAC_context *c, char *d_in, size_t size, char **d_use);
 PFAC_status_t foldStaged(PFAC_context *c, char *d_piece, size_t size);
-void freeFoldScratch(PFAC_context *c);
+/* the compacted-output scan of the handle's perf mode over n device bytes (the caller holds c->lock) */
+inline PFAC_status_t reduceOnDevice(PFAC_context *c, char *d_in, size_t n, int *d_ids, int *d_pos, int *h_count)
+{
+    PFAC_reduce_kernel_protoType fn = c->perfMode == PFAC_TIME_DRIVEN ? c->reduce_kernel_ptr : c->reduce_inplace_kernel_ptr;
+    return fn(c, reinterpret_cast<int *>(d_in), (int)n, d_ids, d_pos, h_count, nullptr, nullptr);
+}
+/* the non-zero results of the first `owned` entries of a full result vector as (id, position + posShift) pairs; ids may be the vector
+ * itself (pair z comes from an entry at or behind z).  Returns the number of pairs */
+inline int compactPairs(const int *results, size_t owned, int posShift, int *ids, int *pos)
+{
+    int z = 0;
+    for (size_t i = 0; i < owned; i++) {
+        const int m = results[i];
+        if (m > 0) { ids[z] = m; pos[z] = (int)i + posShift; z++; }
+    }
+    return z;
+}
 /* stream_api.cpp: PFAC_destroy closes the handle's streams; the device bytes their carries hold (PFACX_getInfo: deviceTableBytes) */
 void closeAllStreams(PFAC_context *c);
 size_t streamDeviceBytes(const PFAC_context *c);

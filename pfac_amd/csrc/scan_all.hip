@@ -21,10 +21,10 @@
 #endif
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdint>
 
 #include "pfac_context.h"
+#include "scan_common.h"
 
 namespace {
 
@@ -176,35 +176,10 @@ __global__ void pfac_all_done(unsigned int *hostDone, unsigned int seq)
 unsigned int gridCap(const PFAC_context *c) { return (unsigned int)(c->multiProcessorCount > 0 ? c->multiProcessorCount : 256) * 8u; }
 
 /* grow-only scratch of the expansion: the block totals, then (batch form) the expanded offset of every longest pair */
-void *allScratch(PFAC_context *c, size_t bytes)
+char *allScratch(PFAC_context *c, size_t bytes)
 {
-    if (c->allScratchBytes >= bytes) return c->d_allScratch;
-    if (c->d_allScratch) (void)hipFree(c->d_allScratch);
-    c->d_allScratch = nullptr;
-    c->allScratchBytes = 0;
-    const size_t grow = bytes + bytes / 2;
-    if (hipMalloc(&c->d_allScratch, grow) != hipSuccess) {
-        (void)hipGetLastError();
-        c->d_allScratch = nullptr;
-        return nullptr;
-    }
-    c->allScratchBytes = grow;
-    return c->d_allScratch;
-}
-
-/* the host waits for pfac_all_done (polled for a while, then a stream sync) */
-bool waitDone(PFAC_context *c, unsigned int seq)
-{
-    volatile unsigned int *hostDone = c->h_modeHint + pfac::kHostAllDoneWord;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned int spins = 0; __atomic_load_n(const_cast<unsigned int *>(hostDone), __ATOMIC_ACQUIRE) != seq; spins++) {
-        if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20))
-            return hipStreamSynchronize(0) == hipSuccess;
-#if defined(__x86_64__) || defined(__i386__)
-        __builtin_ia32_pause();
-#endif
-    }
-    return true;
+    if (c->scratch.all.count() < bytes && c->scratch.all.reserve(bytes + bytes / 2) != PFAC_STATUS_SUCCESS) return nullptr;
+    return c->scratch.all.get();
 }
 
 } // namespace
@@ -245,7 +220,7 @@ PFAC_status_t PFACX_allExpand(PFAC_handle_t handle, const int *d_pairIds, const 
     blocks = (count + x.per - 1) / x.per;
     x.blocks = (unsigned int)blocks;
     const size_t baseBytes = ((blocks + 1) * sizeof(unsigned long long) + 255) & ~size_t(255);
-    char *s = static_cast<char *>(allScratch(c, baseBytes + (d_segFirst ? count * sizeof(unsigned long long) : 0)));
+    char *s = allScratch(c, baseBytes + (d_segFirst ? count * sizeof(unsigned long long) : 0));
     if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
     x.blockBase = reinterpret_cast<unsigned long long *>(s);
     x.pairOffset = d_segFirst ? reinterpret_cast<unsigned long long *>(s + baseBytes) : nullptr;
@@ -264,7 +239,7 @@ PFAC_status_t PFACX_allExpand(PFAC_handle_t handle, const int *d_pairIds, const 
     if (mapped) {
         c->allSeq = c->allSeq + 1u ? c->allSeq + 1u : 1u;
         hipLaunchKernelGGL(pfac_all_done, dim3(1), dim3(1), 0, 0, c->d_modeHint + pfac::kHostAllDoneWord, c->allSeq);
-        if (hipGetLastError() != hipSuccess || !waitDone(c, c->allSeq)) return PFAC_STATUS_INTERNAL_ERROR;
+        if (hipGetLastError() != hipSuccess || waitHostSeq(c->h_modeHint + pfac::kHostAllDoneWord, c->allSeq) == HostWait::SyncFailed) return PFAC_STATUS_INTERNAL_ERROR;
         total = __atomic_load_n(reinterpret_cast<unsigned long long *>(c->h_modeHint + pfac::kHostAllTotalWord), __ATOMIC_ACQUIRE);
     } else if (hipGetLastError() != hipSuccess ||
                hipMemcpy(&total, x.blockBase + blocks, sizeof(total), hipMemcpyDeviceToHost) != hipSuccess) {

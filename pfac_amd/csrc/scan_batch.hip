@@ -205,15 +205,15 @@ uint32_t clampExtent32(size_t bytes) { return bytes > 0xFFFFFFFFull ? 0xFFFFFFFF
 /* what ChainCtx reads of the kernel arguments: the WIDE chained table as scan_module.hip (fillArgs) describes it to the other kernels */
 PFAC_status_t chainArgs(const PFAC_context *c, const char *d_input, ScanArgs &a)
 {
-    if (!c->d_chainSlots || c->chainJumpLog2 <= 0) return PFAC_STATUS_INTERNAL_ERROR;
-    const size_t chained = c->numChainSlots * sizeof(pfac::ChainSlot);
+    if (!c->tables.chainSlots || c->chainJumpLog2 <= 0) return PFAC_STATUS_INTERNAL_ERROR;
+    const size_t chained = c->tables.chainSlots.bytes(), slots = c->tables.chainSlots.count();
     if (c->textureMode == PFAC_TEXTURE_ON && chained > 0xFFFFFFFFull) return PFAC_STATUS_CUDA_ALLOC_FAILED;   /* 32-bit buffer offsets */
     a = ScanArgs{};
     a.in = reinterpret_cast<const unsigned char *>(d_input);
-    a.chainSlots = reinterpret_cast<const u32x4 *>(c->d_chainSlots);
+    a.chainSlots = reinterpret_cast<const u32x4 *>(c->tables.chainSlots.get());
     a.jumpShift = 32u - (uint32_t)c->chainJumpLog2;
-    a.extDelta = (uint32_t)(c->numChainSlots / 2);
-    a.jumpBase = (uint32_t)(c->numChainSlots / 2 - (size_t(2) << c->chainJumpLog2));
+    a.extDelta = (uint32_t)(slots / 2);
+    a.jumpBase = (uint32_t)(slots / 2 - (size_t(2) << c->chainJumpLog2));
     a.jumpLongBase = a.jumpBase + (uint32_t)(size_t(1) << c->chainJumpLog2);
     a.rootRow = a.jumpBase - (uint32_t)pfac::kCharSet;
     a.chainBytes = clampExtent32(chained);
@@ -236,20 +236,7 @@ BatchArgs batchArgs(const PFAC_context *c, const char *d_input, size_t size, con
 unsigned int gridCap(const PFAC_context *c) { return (unsigned int)(c->multiProcessorCount > 0 ? c->multiProcessorCount : 256) * 16u; }
 
 /* grow-only scratch of the compacted form: [0, 256) drop counter, then kept counts per block, then the compacted ids and positions */
-void *batchScratch(PFAC_context *c, size_t bytes)
-{
-    if (c->batchScratchBytes >= bytes) return c->d_batchScratch;
-    if (c->d_batchScratch) (void)hipFree(c->d_batchScratch);
-    c->d_batchScratch = nullptr;
-    c->batchScratchBytes = 0;
-    if (hipMalloc(&c->d_batchScratch, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        c->d_batchScratch = nullptr;
-        return nullptr;
-    }
-    c->batchScratchBytes = bytes;
-    return c->d_batchScratch;
-}
+char *batchScratch(PFAC_context *c, size_t bytes) { return c->scratch.batch.reserve(bytes) == PFAC_STATUS_SUCCESS ? c->scratch.batch.get() : nullptr; }
 
 } // namespace
 
@@ -296,7 +283,7 @@ PFAC_status_t PFACX_batchReduceFixup(PFAC_handle_t handle, const char *d_input, 
     if (n > 0 && b.maxWalk > 0) {
         const size_t blocks = ((size_t)n + kBatchBlock - 1) / kBatchBlock;
         const size_t head = 256, keptBytes = (blocks * sizeof(unsigned int) + 255) & ~size_t(255);
-        char *s = static_cast<char *>(batchScratch(c, head + keptBytes + 2 * (size_t)n * sizeof(int)));
+        char *s = batchScratch(c, head + keptBytes + 2 * (size_t)n * sizeof(int));
         if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
         unsigned int *drops = reinterpret_cast<unsigned int *>(s), *blockKept = reinterpret_cast<unsigned int *>(s + head);
         int *idsOut = reinterpret_cast<int *>(s + head + keptBytes), *posOut = idsOut + n;

@@ -16,6 +16,7 @@
 #endif
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -794,15 +795,33 @@ struct ShapeCache { std::mutex lock; int perCU[kMaxDevices] = {}; };
  * (tables.cpp: buildChainedHashTable).  The one place that knows the layout: every launcher fills its ScanArgs through this */
 inline void fillChainArgs(const PFAC_context *c, ScanArgs &a)
 {
-    a.chainSlots = reinterpret_cast<const u32x4 *>(c->d_chainSlots);
+    const size_t slots = c->tables.chainSlots.count();
+    a.chainSlots = reinterpret_cast<const u32x4 *>(c->tables.chainSlots.get());
     a.jumpShift = 32u - (uint32_t)c->chainJumpLog2;
-    a.extDelta = (uint32_t)(c->numChainSlots / 2);                         /* headers, then as many extension units */
-    a.jumpBase = (uint32_t)(c->numChainSlots / 2 - (size_t(2) << c->chainJumpLog2));         /* the jump table, then the long jump table */
+    a.extDelta = (uint32_t)(slots / 2);                                    /* headers, then as many extension units */
+    a.jumpBase = (uint32_t)(slots / 2 - (size_t(2) << c->chainJumpLog2));                    /* the jump table, then the long jump table */
     a.jumpLongBase = a.jumpBase + (uint32_t)(size_t(1) << c->chainJumpLog2);
     a.rootRow = a.jumpBase - (uint32_t)pfac::kCharSet;
-    const size_t bytes = c->numChainSlots * sizeof(pfac::ChainSlot);
+    const size_t bytes = c->tables.chainSlots.bytes();
     a.chainBytes = bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)bytes;
     a.maxWalk = (uint32_t)c->fa.maxPatternLen;
+}
+
+/* The host's wait for the sequence number (never 0) that the last launch of a call writes into a word of the handle's mapped host memory: polled for
+ * 20 ms -- a hipStreamSynchronize or a blocking hipMemcpy wakes up 30 - 50 us after the last kernel has ended --, then a stream sync.  Says how it
+ * ended; what a sync without the number means is the caller's business */
+enum class HostWait { Polled, Synced, SyncFailed };
+inline HostWait waitHostSeq(const volatile unsigned int *word, unsigned int seq)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned int spins = 0; __atomic_load_n(const_cast<const unsigned int *>(word), __ATOMIC_ACQUIRE) != seq; spins++) {
+        if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20))
+            return hipStreamSynchronize(0) == hipSuccess ? HostWait::Synced : HostWait::SyncFailed;
+#if defined(__x86_64__) || defined(__i386__)
+        __builtin_ia32_pause();
+#endif
+    }
+    return HostWait::Polled;
 }
 
 inline unsigned int gridFor(const PFAC_context *c, size_t items)
@@ -821,7 +840,7 @@ hipError_t launchFilterKernel(const PFAC_context *c, const ScanArgs &a, bool tex
 /* scan_tiled.hip: the tiled kernel over the chained table; and "whatever is not the filter kernel's" (PFACX_KERNEL_REFTABLE: over the reference-layout table of the perf mode) */
 hipError_t launchTiledKernel(const PFAC_context *c, const ScanArgs &a, bool tex);
 hipError_t launchSimpleKernel(const PFAC_context *c, bool hashed, bool tex, const ScanArgs &part);
-/* ... the tiled frame over part.dense = int[S][256] whatever the perf mode and the kernel variant (PFAC_context::d_denseFast) */
+/* ... the tiled frame over part.dense = int[S][256] whatever the perf mode and the kernel variant (DeviceTables::denseFast) */
 hipError_t launchDenseTableKernel(const PFAC_context *c, bool tex, const ScanArgs &part);
 }
 

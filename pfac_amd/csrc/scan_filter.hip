@@ -1383,7 +1383,7 @@ hipError_t launchFilter(const PFAC_context *c, const ScanArgs &a0)
     /* the launch counters are left zero by the launch before (see the kernel's end) -- unless that one failed; the stage
      * timers of the profile build are only ever added to */
     if (PFAC_TIMING || c->countersDirty) {
-        e = hipMemsetAsync(c->d_workCounters, 0, pfac::kWorkCounterWords * sizeof(unsigned int), 0);
+        e = hipMemsetAsync(c->tables.workCounters.get(), 0, pfac::kWorkCounterWords * sizeof(unsigned int), 0);
         if (e != hipSuccess) return e;
         c->countersDirty = false;
     }
@@ -1397,7 +1397,7 @@ hipError_t launchFilter(const PFAC_context *c, const ScanArgs &a0)
     {
         unsigned long long t[18];
         (void)hipDeviceSynchronize();
-        (void)hipMemcpy(t, c->d_workCounters + pfac::kStatsWord + 16, sizeof(t), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(t, c->tables.workCounters.get() + pfac::kStatsWord + 16, sizeof(t), hipMemcpyDeviceToHost);
         double sum = 0;
         for (int k = 0; k < 12; k++) sum += (double)t[k];
         static const char *names[12] = {"consume", "refill", "issue", "level1+stage", "list-fences", "ladder+append", "resolve(wait for writers)+prefetch issue", "loop/pop/other",

@@ -113,30 +113,31 @@ uint32_t clampExtent(size_t bytes) { return bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu 
 PFAC_status_t fillArgs(const PFAC_context *c, bool hashed, const char *d_input_string, size_t input_size,
                        int *d_matched_result, ScanArgs &a)
 {
-    if (!c->d_initialRow || !c->d_gram3 || !c->d_ladder || !c->d_final3 || !c->d_shortBits || !c->d_workCounters || !c->d_gram1 || !c->d_prefix4) return PFAC_STATUS_INTERNAL_ERROR;
-    if (!c->d_chainSlots || c->chainJumpLog2 <= 0) return PFAC_STATUS_INTERNAL_ERROR;
+    const pfac::DeviceTables &t = c->tables;
+    if (!t.initialRow || !t.gram3 || !t.ladder || !t.final3 || !t.shortBits || !t.workCounters || !t.gram1 || !t.prefix4) return PFAC_STATUS_INTERNAL_ERROR;
+    if (!t.chainSlots || c->chainJumpLog2 <= 0) return PFAC_STATUS_INTERNAL_ERROR;
     /* the reference-layout tables are on the device only while PFACX_KERNEL_REFTABLE is selected (pfac_api.cpp uploads them) */
-    if (c->kernelVariant == PFACX_KERNEL_REFTABLE && (hashed ? (!c->d_hashRow || !c->d_hashVal) : !c->d_dense)) return PFAC_STATUS_INTERNAL_ERROR;
+    if (c->kernelVariant == PFACX_KERNEL_REFTABLE && (hashed ? (!t.hashRow || !t.hashVal) : !t.dense)) return PFAC_STATUS_INTERNAL_ERROR;
     a = ScanArgs{};
     a.in = reinterpret_cast<const unsigned char *>(d_input_string);
     a.out = d_matched_result;
     a.n = a.owned = input_size;
-    a.dense = c->d_dense;
-    a.hashRow = c->d_hashRow;
-    a.hashVal = c->d_hashVal;
+    a.dense = t.dense.get();
+    a.hashRow = t.hashRow.get();
+    a.hashVal = t.hashVal.get();
     a.denseBytes = clampExtent(c->h_dense.size() * sizeof(int));
     a.hashRowBytes = clampExtent(c->h_hashRow.size() * sizeof(Int2));
     a.hashValBytes = clampExtent(c->h_hashVal.size() * sizeof(Int2));
     fillChainArgs(c, a);                                                   /* scan_common.h: the chained table and maxWalk */
-    a.initialRow = c->d_initialRow;
-    a.gram3 = c->d_gram3;
-    a.gram1 = c->d_gram1;
-    a.prefix4 = c->d_prefix4;
-    a.tail = (c->filter.tail.empty() && c->filter.tailG.empty()) ? nullptr : c->d_tail;       /* a set has the table in one form: LDS slots or device-memory buckets */
+    a.initialRow = t.initialRow.get();
+    a.gram3 = t.gram3.get();
+    a.gram1 = t.gram1.get();
+    a.prefix4 = t.prefix4.get();
+    a.tail = (c->filter.tail.empty() && c->filter.tailG.empty()) ? nullptr : t.tail.get();       /* a set has the table in one form: LDS slots or device-memory buckets */
     a.log2Tail = c->filter.tail.empty() ? c->filter.log2TailG : c->filter.log2Tail;
-    a.shortBits = c->d_shortBits;
-    a.ladder = c->d_ladder;
-    a.final3 = c->d_final3;
+    a.shortBits = t.shortBits.get();
+    a.ladder = t.ladder.get();
+    a.final3 = t.final3.get();
     a.log2Bits = c->filter.log2Bits;
     a.log2BitsLad = c->filter.log2BitsLad;
     a.ladderLast = c->filter.ladderLast;
@@ -145,7 +146,7 @@ PFAC_status_t fillArgs(const PFAC_context *c, bool hashed, const char *d_input_s
     for (int k = 0; k < pfac::kSkipTagsMax; k++) a.skipTags[k] = c->filter.skipTags[k];
     a.log2BitsF3 = c->filter.log2BitsF3;
     a.numFinal = c->fa.numPatterns;
-    a.work = c->d_workCounters;
+    a.work = t.workCounters.get();
     a.hostHint = c->d_modeHint;
     a.denseWord = (uint32_t)pfac::kDenseCountWord;
     a.denseWordOther = (uint32_t)pfac::kDenseCountWordB;
@@ -153,7 +154,7 @@ PFAC_status_t fillArgs(const PFAC_context *c, bool hashed, const char *d_input_s
     /* the buffer-resource ("texture") path addresses the table with 32-bit byte offsets; the
      * reference fails the texture bind for an oversized table the same way (PFAC_kernel.cu:139-142) */
     if (c->textureMode == PFAC_TEXTURE_ON) {
-        const size_t chained = c->numChainSlots * sizeof(pfac::ChainSlot), dense = hashed ? 0 : c->h_dense.size() * sizeof(int);
+        const size_t chained = t.chainSlots.bytes(), dense = hashed ? 0 : c->h_dense.size() * sizeof(int);
         if ((chained > dense ? chained : dense) > 0xFFFFFFFFull) return PFAC_STATUS_CUDA_ALLOC_FAILED;
     }
     return PFAC_STATUS_SUCCESS;
@@ -163,17 +164,18 @@ PFAC_status_t fillArgs(const PFAC_context *c, bool hashed, const char *d_input_s
  * full of near misses (the word the walker choice reads), or PFACX_WALKER_STAGE / _VETO says the caller expects them */
 void tiledTable(const PFAC_context *c, ScanArgs &a)
 {
-    if (c->d_chainNarrow == nullptr || c->numChainNarrow == 0) return;
+    const size_t slots = c->tables.chainNarrow.count();
+    if (slots == 0) return;
     const bool nearMisses = (c->h_modeHint != nullptr && *static_cast<volatile const unsigned int *>(c->h_modeHint) != 0) ||
                             c->walker == PFACX_WALKER_STAGE || c->walker == PFACX_WALKER_VETO;
     if (nearMisses) return;
-    a.chainSlots = reinterpret_cast<const u32x4 *>(c->d_chainNarrow);
+    a.chainSlots = reinterpret_cast<const u32x4 *>(c->tables.chainNarrow.get());
     a.jumpShift = 32u - (uint32_t)c->chainNarrowJumpLog2;
-    a.jumpBase = (uint32_t)(c->numChainNarrow - (size_t(1) << c->chainNarrowJumpLog2));
+    a.jumpBase = (uint32_t)(slots - (size_t(1) << c->chainNarrowJumpLog2));
     a.jumpLongBase = a.jumpBase;                       /* (no long jump table: nothing in the narrow table is long) */
     a.rootRow = a.jumpBase - (uint32_t)pfac::kCharSet;
     a.extDelta = 0;
-    a.chainBytes = clampExtent(c->numChainNarrow * sizeof(pfac::ChainSlot));
+    a.chainBytes = clampExtent(c->tables.chainNarrow.bytes());
 }
 
 /* below this many positions a call takes the tiled kernel alone: ~8 us + what the positions cost instead of the filter
@@ -239,19 +241,9 @@ PFAC_status_t scan(PFAC_handle_t handle, char *d_input_string, size_t input_size
         if (mainLen) {
             /* room for the list of pattern-dense chunks this launch may leave to the tiled kernel: a grow-only buffer of
              * the handle (the caller holds its lock) */
-            const size_t chunks = mainLen / kChunkBytesHost;
-            if (handle->denseListEntries < chunks) {
-                if (handle->d_denseList) (void)hipFree(handle->d_denseList);
-                handle->d_denseList = nullptr;
-                handle->denseListEntries = 0;
-                if (hipMalloc(reinterpret_cast<void **>(&handle->d_denseList), chunks * sizeof(unsigned int)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    handle->d_denseList = nullptr;
-                    return PFAC_STATUS_CUDA_ALLOC_FAILED;
-                }
-                handle->denseListEntries = chunks;
-            }
-            part.denseList = handle->d_denseList;
+            const PFAC_status_t room = handle->scratch.denseList.reserve(mainLen / kChunkBytesHost);
+            if (room != PFAC_STATUS_SUCCESS) return room;
+            part.denseList = handle->scratch.denseList.get();
             part.denseWord = (uint32_t)(handle->denseParity ? pfac::kDenseCountWordB : pfac::kDenseCountWord);
             part.denseWordOther = (uint32_t)(handle->denseParity ? pfac::kDenseCountWord : pfac::kDenseCountWordB);
             handle->denseParity ^= 1u;
@@ -292,12 +284,12 @@ PFAC_status_t scan(PFAC_handle_t handle, char *d_input_string, size_t input_size
             rest.n = input_size - first + back;
             headDone = true;
             rest.reportDense = (c->kernelVariant == PFACX_KERNEL_AUTO && vectorOk && ownEnd - first >= kSmallInput) ? 1u : 0u;   /* a big call sent here for its density: say if it still is */
-            /* ... and if the set is one that does not fold into chains (a few all-final states: PFAC_context::d_denseFast), through the dense table:
+            /* ... and if the set is one that does not fold into chains (a few all-final states: DeviceTables::denseFast), through the dense table:
              * a step is one byte either way there, and one gathered dword costs a third of the chained step's instructions (input in which every
              * position matches, 256 MiB: 94 -> 123 GB/s) */
-            if (rest.reportDense != 0 && c->d_denseFast != nullptr) {
-                rest.dense = c->d_denseFast;
-                rest.denseBytes = clampExtent(c->denseFastEntries * sizeof(int));
+            if (rest.reportDense != 0 && c->tables.denseFast) {
+                rest.dense = c->tables.denseFast.get();
+                rest.denseBytes = clampExtent(c->tables.denseFast.bytes());
                 e = pfacmod::launchDenseTableKernel(c, tex, rest);
             } else {
                 if (c->kernelVariant != PFACX_KERNEL_REFTABLE) tiledTable(c, rest);
@@ -331,24 +323,15 @@ PFAC_status_t scan(PFAC_handle_t handle, char *d_input_string, size_t input_size
  * (PFAC_reduce_kernel.cu:417-457) because it has no prefilter: every thread owns a result.
  */
 /* the all-match calls (PFACX_allReduce): the ordering's rank pass writes the ordered pairs into the handle's grow-only scratch
- * PFAC_context::d_allPairs (room for as many pairs as the ordering scratch: it holds them all whenever the ordering runs) */
+ * DeviceScratch::allPairs, the ids and behind them as many positions (room for as many pairs as the ordering scratch: it holds them all
+ * whenever the ordering runs) */
 PFAC_status_t orderIntoAllPairs(PFAC_context *mc, PairOrder &order)
 {
-    const size_t entries = order.o.capacity;
-    if (mc->allPairsEntries < entries) {
-        if (mc->d_allPairs) (void)hipFree(mc->d_allPairs);
-        mc->d_allPairs = nullptr;
-        mc->allPairsEntries = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&mc->d_allPairs), 2 * entries * sizeof(int)) != hipSuccess) {
-            (void)hipGetLastError();
-            mc->d_allPairs = nullptr;
-            return PFAC_STATUS_CUDA_ALLOC_FAILED;
-        }
-        mc->allPairsEntries = entries;
-    }
-    order.o.idOut = mc->d_allPairs;
-    order.o.posOut = reinterpret_cast<unsigned int *>(mc->d_allPairs + mc->allPairsEntries);
-    return PFAC_STATUS_SUCCESS;
+    pfac::DeviceBuffer<int> &pairs = mc->scratch.allPairs;
+    const PFAC_status_t st = pairs.reserve(2 * (size_t)order.o.capacity);
+    order.o.idOut = pairs.get();
+    order.o.posOut = reinterpret_cast<unsigned int *>(pairs.get() + pairs.count() / 2);
+    return st;
 }
 
 PFAC_status_t reduceScan(PFAC_handle_t handle, int *d_input_string, int input_size, int *d_match_result, int *d_pos,
@@ -430,19 +413,12 @@ PFAC_status_t reduceScan(PFAC_handle_t handle, int *d_input_string, int input_si
         trOrder = trUs();
 #endif
         /* the last launch writes the call's number into host memory: polled for a while (the call is a millisecond of GPU work per GiB) */
-        const auto t0 = std::chrono::steady_clock::now();
-        bool through = false;
-        for (unsigned int spins = 0; !(through = __atomic_load_n(const_cast<unsigned int *>(hostDone), __ATOMIC_ACQUIRE) == order.o.seq); spins++) {
-            if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#endif
-        }
-        if (!through && hipStreamSynchronize(0) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+        const HostWait through = waitHostSeq(hostDone, order.o.seq);
+        if (through == HostWait::SyncFailed) return PFAC_STATUS_INTERNAL_ERROR;
         count = *hostCount;
 #if PFAC_REDUCE_TRACE
         trDone = trUs();
-        fprintf(stderr, "PFAC_REDUCE_TRACE us: planned %.1f, scan queued %.1f, ordering queued %.1f, done %.1f (clean %d, polled %d)\n", trPlan, trScan, trOrder, trDone, (int)clean, (int)through);
+        fprintf(stderr, "PFAC_REDUCE_TRACE us: planned %.1f, scan queued %.1f, ordering queued %.1f, done %.1f (clean %d, polled %d)\n", trPlan, trScan, trOrder, trDone, (int)clean, (int)(through == HostWait::Polled));
 #endif
     } else {
         if (ordered && order.order(c) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;

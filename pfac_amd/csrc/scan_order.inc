@@ -262,16 +262,12 @@ __global__ void pfac_order_done(unsigned int *hostDone, unsigned int seq)
 /* grow-only device scratch of the compacted-output path, owned by the handle (the caller holds its lock) */
 PFAC_status_t reduceScratch(PFAC_context *mc, size_t need, char **base)
 {
-    if (mc->reduceScratchBytes < need) {
-        if (mc->d_reduceScratch) (void)hipFree(mc->d_reduceScratch);
-        mc->d_reduceScratch = nullptr;
-        mc->reduceScratchBytes = 0;
-        mc->orderCleanBase = nullptr;
-        const size_t grow = need + need / 2;
-        if (hipMalloc(&mc->d_reduceScratch, grow) != hipSuccess) { (void)hipGetLastError(); mc->d_reduceScratch = nullptr; return PFAC_STATUS_CUDA_ALLOC_FAILED; }
-        mc->reduceScratchBytes = grow;
+    if (mc->scratch.reduce.count() < need) {
+        mc->orderCleanBase = nullptr;                      /* a new allocation: nobody has left its counters zero */
+        const PFAC_status_t st = mc->scratch.reduce.reserve(need + need / 2);
+        if (st != PFAC_STATUS_SUCCESS) return st;
     }
-    *base = static_cast<char *>(mc->d_reduceScratch);
+    *base = mc->scratch.reduce.get();
     return PFAC_STATUS_SUCCESS;
 }
 
@@ -299,7 +295,7 @@ struct PairOrder {
         char *base = nullptr;
         const PFAC_status_t st = reduceScratch(mc, fixed + 2 * arrayBytes, &base);
         if (st != PFAC_STATUS_SUCCESS) return st;
-        const size_t perArray = (mc->reduceScratchBytes - fixed) / 2 / 256 * 256;
+        const size_t perArray = (mc->scratch.reduce.count() - fixed) / 2 / 256 * 256;
         o.capacity = perArray / sizeof(int) > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned int)(perArray / sizeof(int));
         o.counts = reinterpret_cast<unsigned int *>(base);
         o.crowdedCount = o.counts + padded + 2 * (parity & 1u);

@@ -23,7 +23,6 @@
 #endif
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdint>
 
 #include "pfac_context.h"
@@ -111,7 +110,7 @@ PFAC_status_t PFACX_streamSeam(PFAC_handle_t handle, const char *d_carry, size_t
     if (!h_count || !d_carryNext || (carried && !d_carry) || (size && !d_piece) || (numFinal && (!d_ids || !d_pos))) return PFAC_STATUS_INVALID_PARAMETER;
     const size_t M = (size_t)c->fa.maxPatternLen;
     if (M == 0 || carried > M - 1 || numFinal > carried) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!c->d_chainSlots || c->chainJumpLog2 <= 0 || !c->d_modeHint || !c->h_modeHint) return PFAC_STATUS_INTERNAL_ERROR;
+    if (!c->tables.chainSlots || c->chainJumpLog2 <= 0 || !c->d_modeHint || !c->h_modeHint) return PFAC_STATUS_INTERNAL_ERROR;
     const size_t head = size < M - 1 ? size : M - 1;
     const size_t staged = carried + head;
     if (staged > kSeamLdsBytes && !d_stage) return PFAC_STATUS_INVALID_PARAMETER;
@@ -142,15 +141,8 @@ PFAC_status_t PFACX_streamSeam(PFAC_handle_t handle, const char *d_carry, size_t
     hipLaunchKernelGGL(pfac_stream_seam, dim3(1), dim3(kSeamBlock), 0, 0, a, s);
     if (hipGetLastError() != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
     /* the launch writes its number into host memory behind the count: polled for a while, like the compacted-output call's (scan_module.hip) */
-    const auto t0 = std::chrono::steady_clock::now();
-    bool through = false;
-    for (unsigned int spins = 0; !(through = __atomic_load_n(const_cast<unsigned int *>(hostDone), __ATOMIC_ACQUIRE) == s.seq); spins++) {
-        if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
-#if defined(__x86_64__) || defined(__i386__)
-        __builtin_ia32_pause();
-#endif
-    }
-    if (!through && (hipStreamSynchronize(0) != hipSuccess || __atomic_load_n(const_cast<unsigned int *>(hostDone), __ATOMIC_ACQUIRE) != s.seq))
+    const HostWait w = waitHostSeq(hostDone, s.seq);
+    if (w == HostWait::SyncFailed || (w == HostWait::Synced && __atomic_load_n(const_cast<unsigned int *>(hostDone), __ATOMIC_ACQUIRE) != s.seq))
         return PFAC_STATUS_INTERNAL_ERROR;
     const unsigned int count = *hostCount;
     if (count > numFinal) return PFAC_STATUS_INTERNAL_ERROR;

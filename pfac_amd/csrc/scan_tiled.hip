@@ -850,7 +850,7 @@ hipError_t launchTiled(const PFAC_context *c, ScanArgs a)
     if (blocks < 1) blocks = 1;
     const size_t lds = fixed + hot * sizeof(pfac::ChainSlot);
 #if PFAC_TILED_STATS
-    (void)hipMemsetAsync(c->d_workCounters + pfac::kStatsWord + 48, 0, 8 * sizeof(unsigned long long), 0);
+    (void)hipMemsetAsync(c->tables.workCounters.get() + pfac::kStatsWord + 48, 0, 8 * sizeof(unsigned long long), 0);
 #endif
     if (big && hot == a.rootRow) hipLaunchKernelGGL(kernelBigHot, dim3((unsigned)blocks), dim3(threads), lds, 0, a);
     else if (big) hipLaunchKernelGGL(kernelBig, dim3((unsigned)blocks), dim3(threads), lds, 0, a);
@@ -859,7 +859,7 @@ hipError_t launchTiled(const PFAC_context *c, ScanArgs a)
     {
         unsigned long long t[8];
         (void)hipDeviceSynchronize();
-        (void)hipMemcpy(t, c->d_workCounters + pfac::kStatsWord + 48, sizeof(t), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(t, c->tables.workCounters.get() + pfac::kStatsWord + 48, sizeof(t), hipMemcpyDeviceToHost);
         fprintf(stderr, "PFAC_TILED_STATS owned %zu: groups %llu (dense %llu) passes %llu walks %llu wave-steps %llu live lane-steps %llu: %.2f steps per walk, %.1f live lanes per wave-step of %d; long-slot unit fetches: %llu wave-level, %llu lanes\n",
                 a.owned, t[7], t[6], t[5], t[4], t[2], t[3], t[4] ? (double)t[3] / t[4] : 0.0, t[2] ? (double)t[3] / t[2] : 0.0, 64 * kTiledWalks, t[0], t[1]);
     }

@@ -32,10 +32,9 @@ struct PFACX_stream_s {
     unsigned long long total = 0;             /* T: bytes seen */
     size_t carried = 0;                       /* min(M - 1, T): the pending positions are the carried ones */
     std::vector<unsigned char> h_carry;       /* host-fed */
-    char *d_block = nullptr;                  /* device-fed: one allocation = two carry buffers (+ the seam's stage where it does not fit the LDS) */
+    pfac::DeviceBuffer<char> d_block;         /* device-fed: one allocation = two carry buffers (+ the seam's stage where it does not fit the LDS) */
     char *d_carry[2] = {nullptr, nullptr};
     char *d_stage = nullptr;
-    size_t deviceBytes = 0;
     int deviceM = 0;                          /* the maxPatternLen the block was sized for */
     int cur = 0;
     std::mutex lock;                          /* one call at a time per stream */
@@ -45,9 +44,8 @@ namespace pfac_internal {
 
 static void freeStreamDevice(PFACX_stream_s *s)
 {
-    devFree(s->d_block);
+    s->d_block.release();
     s->d_carry[0] = s->d_carry[1] = s->d_stage = nullptr;
-    s->deviceBytes = 0;
     s->deviceM = 0;
 }
 
@@ -63,7 +61,7 @@ void closeAllStreams(PFAC_context *c)
 size_t streamDeviceBytes(const PFAC_context *c)
 {
     size_t bytes = 0;
-    for (const PFACX_stream_s *s : c->streams) bytes += s->deviceBytes;
+    for (const PFACX_stream_s *s : c->streams) bytes += s->d_block.bytes();
     return bytes;
 }
 
@@ -84,16 +82,11 @@ static PFAC_status_t ensureStreamDevice(PFACX_stream_s *s, int M)
     const size_t one = (((size_t)M - 1) + 255) & ~size_t(255);
     const size_t seam = 2 * ((size_t)M - 1);
     const size_t stage = seam > pfac::kStreamSeamLdsBytes ? ((seam + 255) & ~size_t(255)) : 0;
-    const size_t bytes = 2 * one + stage + 256;
-    if (hipMalloc(reinterpret_cast<void **>(&s->d_block), bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        s->d_block = nullptr;
-        return PFAC_STATUS_CUDA_ALLOC_FAILED;
-    }
-    s->d_carry[0] = s->d_block;
-    s->d_carry[1] = s->d_block + one + 128;
-    s->d_stage = stage ? s->d_block + 2 * one + 256 : nullptr;
-    s->deviceBytes = bytes;
+    const PFAC_status_t st = s->d_block.reserve(2 * one + stage + 256);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    s->d_carry[0] = s->d_block.get();
+    s->d_carry[1] = s->d_block.get() + one + 128;
+    s->d_stage = stage ? s->d_block.get() + 2 * one + 256 : nullptr;
     s->deviceM = M;
     return PFAC_STATUS_SUCCESS;
 }
@@ -117,12 +110,7 @@ static PFAC_status_t cpuPairs(PFAC_context *c, const char *in, size_t owned, siz
     PFAC_status_t st = prepareCpuPlatformLocked(c);
     if (st == PFAC_STATUS_SUCCESS) st = matchHostOnCpuPlatformPrepared(c, in, readable, scratch);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    int z = 0;
-    for (size_t i = 0; i < owned; i++) {
-        const int m = scratch[i];
-        if (m > 0) { ids[z] = m; pos[z] = (int)i + posShift; z++; }
-    }
-    *count = z;
+    *count = compactPairs(scratch, owned, posShift, ids, pos);
     return PFAC_STATUS_SUCCESS;
 }
 

@@ -359,6 +359,59 @@ PFAC_status_t PFACX_streamMatchFromHost(PFACX_stream_t stream, char *h_piece, si
                                         int *h_num_matched, unsigned long long *h_pieceOffset);
 PFAC_status_t PFACX_streamFlush(PFACX_stream_t stream, int *ids, int *pos, size_t capacity, int *h_num_matched);
 
+/* Flow sets: many streams advanced by ONE call.  A buffer of packets that belong to many reassembled flows is matched in one launch
+ * sequence -- the cost of PFACX_matchBatchFromDeviceReduce -- and every flow keeps what is still undecided from batch to batch -- the
+ * exactness of PFACX_stream*.  A flow set is numFlows streams of one handle whose state the library keeps together; flows are named
+ * by their index, 0 .. numFlows - 1.
+ *   A piece call takes one buffer of `size` bytes cut into numPieces pieces by h_offsets[numPieces + 1] (the rules of
+ *   PFACX_matchBatchFromHost: first 0, last `size`, never decreasing; empty pieces are allowed); piece k belongs to flow
+ *   h_flowIds[k].  It returns exactly what this sequence returns, the pair lists concatenated in piece order: for k = 0 ..
+ *   numPieces - 1, PFACX_streamMatchFromHost on a CPU platform with piece k on a stream of its own per flow.  The pairs of piece k are
+ *   entries [pieceFirst[k], pieceFirst[k + 1]): the carried positions the piece makes final, then the piece's own final positions,
+ *   ascending; positions are int, relative to the first byte of piece k (carried ones negative, never below -(M - 1));
+ *   h_pieceOffsets[k] is that flow's T before the call.  Finality, caseless sets and "the caller's buffers are never modified" are
+ *   those of the streams, per flow.
+ *   PFACX_flowsFlush declares the end of the n named flows: PFACX_streamFlush per flow, in the order named, first[n + 1] indexing the
+ *   pairs; those flows are left reset.
+ * OFFSETS AND FLOW IDS ARE HOST ARRAYS and are validated completely: an id >= numFlows, offsets that break the rules, or A FLOW NAMED
+ * TWICE IN ONE CALL is PFAC_STATUS_INVALID_PARAMETER.  Pieces of one flow that arrive in one batch are laid adjacent by the caller and
+ * passed as ONE piece.
+ * capacity (entries of each of ids / pos) >= size + numPieces * (M - 1), a sum below 2^31; the flush: >= max(1, n * (M - 1)).  Smaller:
+ * PFAC_STATUS_INVALID_PARAMETER.  An empty piece: zero pairs, the flow unchanged, its offset reported; size == 0 with numPieces > 0 is
+ * a batch of empty pieces and succeeds.  numPieces == 0 needs size == 0: zero pairs, pieceFirst is not written (either form).
+ * The arrays double as the scan's pair list, as in PFAC_matchFromDeviceReduce: entries below `size` may be overwritten beyond the
+ * pairs returned; nothing is written at or beyond `capacity`.
+ * A FAILED CALL -- any status but success -- LEAVES EVERY FLOW UNCHANGED: repeat it and get what it would have returned.
+ * A flow set is fed by ONE kind of call, fixed by its first piece call that carries a non-empty piece until a reset of all flows:
+ * the device form (carries in device memory; the flush takes device arrays, `first` included) or the host form (host memory, host
+ * arrays); the other kind is PFAC_STATUS_INVALID_PARAMETER.  The host form follows PFAC_setPlatform: the CPU platforms, host-only
+ * handles included, run on the CPU; the GPU platform runs the pipelined host path piece by piece (it keeps the contract, not the
+ * link rate).  The device form on a host-only handle is PFAC_STATUS_LIB_NOT_EXIST.
+ * After the handle reads or loads another pattern set every piece and flush call is PFAC_STATUS_INVALID_PARAMETER until
+ * PFACX_flowsReset(flows, NULL, 0).  Calls take the handle's lock and the set's own (one call at a time per set; two threads may
+ * drive two sets of one handle); PFAC_destroy closes the handle's flow sets.  All calls are synchronous.
+ * MEMORY: a device-fed set holds ONE allocation of 2 x numFlows x (M - 1) bytes (plus alignment) for its carries, made by the first
+ * device call: state, counted under deviceTableBytes of PFACX_getInfo, kept by PFACX_trim, freed by PFACX_flowsClose.  What a call
+ * uploads and stages (offsets, ids, per-piece counts, a staging list of pairs) is grow-only scratch of the handle:
+ * deviceScratchBytes, given back by PFACX_trim.
+ * COST: one compacted scan of the buffer in place, a handful of seam and merge launches whatever the number of pieces,
+ * and 5 - 7 ns of host and device work per piece: about the batch call for pieces of tens of KiB, several times it for packet-sized
+ * pieces, thousands of times less than one stream call per piece. */
+typedef struct PFACX_flows_s *PFACX_flows_t;
+PFAC_status_t PFACX_flowsOpen(PFAC_handle_t handle, size_t numFlows, PFACX_flows_t *flows);
+PFAC_status_t PFACX_flowsClose(PFACX_flows_t flows);
+/* forget the state of the n named flows (T = R = 0); h_flowIds == NULL, n == 0: of all flows, and adopt the handle's current set */
+PFAC_status_t PFACX_flowsReset(PFACX_flows_t flows, const unsigned int *h_flowIds, size_t n);
+PFAC_status_t PFACX_flowsMatchFromDevice(PFACX_flows_t flows, char *d_input, size_t size, const size_t *h_offsets, const unsigned int *h_flowIds,
+                                         size_t numPieces, int *d_ids, int *d_pos, size_t capacity, int *d_pieceFirst /* numPieces + 1 */,
+                                         unsigned long long *h_pieceOffsets /* numPieces */, int *h_num_matched);
+PFAC_status_t PFACX_flowsMatchFromHost(PFACX_flows_t flows, char *h_input, size_t size, const size_t *h_offsets, const unsigned int *h_flowIds,
+                                       size_t numPieces, int *h_ids, int *h_pos, size_t capacity, int *h_pieceFirst /* numPieces + 1 */,
+                                       unsigned long long *h_pieceOffsets /* numPieces */, int *h_num_matched);
+/* declare the end of the n named flows: their pending pairs, flow by flow in the order named; first[n + 1] indexes them */
+PFAC_status_t PFACX_flowsFlush(PFACX_flows_t flows, const unsigned int *h_flowIds, size_t n, int *ids, int *pos, size_t capacity, int *first,
+                               int *h_num_matched);
+
 #ifdef __cplusplus
 }
 #endif

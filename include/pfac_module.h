@@ -103,6 +103,39 @@ PFAC_status_t PFACX_streamReduce(PFAC_handle_t handle, int *d_input_string, int 
 typedef PFAC_status_t (*PFACX_streamSeam_protoType)(PFAC_handle_t, const char *, size_t, const char *, size_t, size_t, char *, char *, int *, int *, int *);
 typedef PFAC_status_t (*PFACX_streamReduce_protoType)(PFAC_handle_t, int *, int, int, int *, int *, int *, int);
 
+/* Flow sets (no reference counterpart; include/pfac_ext.h: PFACX_flows*), scan_flows.hip: the seams of many streams in one launch and
+ * the merge of their pairs with the pairs of ONE compacted scan over the whole buffer.  A piece is described on the host:
+ * its bytes are d_input[start, start + len), its flow's carry is buffer `cur` of flow `flow` (buffer b of flow f lies at
+ * d_carries + (2 f + b) * carryStride) and holds `carried` bytes, of which the first numFinal start positions become final with this
+ * piece; the launch stages their (id, position - carried) pairs at d_seamIds / d_seamPos + seamOff (numFinal entries of room) and
+ * writes the flow's next carry, the last min(maxPatternLen - 1, carried + len) bytes of [carry | piece], into the flow's OTHER buffer.
+ * d_scanIds / d_scanPos: the scanCount ordered pairs of the compacted scan over d_input as one buffer (a copy: d_ids / d_pos are
+ * written); of piece k those at [start, start + len - (maxPatternLen - 1)) count.  Output: the pairs of piece k -- seam, then scan,
+ * positions relative to `start` -- at [d_pieceFirst[k], d_pieceFirst[k + 1]) of d_ids / d_pos; nothing at or beyond `capacity` or
+ * the total.  d_stage: numPieces * stageStride bytes where 2 (maxPatternLen - 1) bytes do not fit the LDS, else null.  The
+ * unsigned arrays hold numPieces entries (d_blockSums: one per 256 pieces, + 2).  Synchronous: *h_total = the number of pairs. */
+typedef struct {
+    unsigned int start, len, flow, carried, numFinal, seamOff, cur, reserved;
+} PFACX_flowPiece_t;
+typedef struct {
+    const char *d_input;
+    const PFACX_flowPiece_t *d_pieces;
+    size_t numPieces;
+    char *d_carries;
+    size_t carryStride;
+    char *d_stage;
+    size_t stageStride;
+    int *d_seamIds, *d_seamPos;
+    unsigned int *d_seamCount, *d_pairLo, *d_counts, *d_blockSums;
+    const int *d_scanIds, *d_scanPos;
+    size_t scanCount;
+    int *d_ids, *d_pos;
+    size_t capacity;
+    int *d_pieceFirst;
+} PFACX_flowsRun_t;
+PFAC_status_t PFACX_flowsRun(PFAC_handle_t handle, const PFACX_flowsRun_t *run, int *h_total);
+typedef PFAC_status_t (*PFACX_flowsRun_protoType)(PFAC_handle_t, const PFACX_flowsRun_t *, int *);
+
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of
  * `launches` launches over the first n bytes (a multiple of 4096) of d_in, or a negative value on a HIP error.

@@ -105,13 +105,14 @@ EXPORTED_SYMBOLS = (
     "PFACX_matchBatchFromDevice", "PFACX_matchBatchFromHost", "PFACX_matchBatchFromDeviceReduce",
     "PFACX_matchAllFromDevice", "PFACX_matchAllFromHost", "PFACX_matchAllBatchFromDevice",
     "PFACX_streamOpen", "PFACX_streamReset", "PFACX_streamClose", "PFACX_streamMatchFromDevice", "PFACX_streamMatchFromHost", "PFACX_streamFlush",
+    "PFACX_flowsOpen", "PFACX_flowsClose", "PFACX_flowsReset", "PFACX_flowsMatchFromDevice", "PFACX_flowsMatchFromHost", "PFACX_flowsFlush",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
     "PFAC_reduce_kernel", "PFAC_reduce_inplace_kernel", "PFACX_streamProbe", "PFACX_buildInfo",
     "PFACX_batchFixup", "PFACX_batchReduceFixup",
     "PFACX_allReduce", "PFACX_allExpand", "PFACX_foldInput",
-    "PFACX_streamSeam", "PFACX_streamReduce",
+    "PFACX_streamSeam", "PFACX_streamReduce", "PFACX_flowsRun",
 )
 
 
@@ -184,6 +185,15 @@ def load_library() -> C.CDLL:
         lib.PFACX_streamMatchFromDevice.argtypes = piece
         lib.PFACX_streamMatchFromHost.argtypes = piece
         lib.PFACX_streamFlush.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+    if hasattr(lib, "PFACX_flowsOpen"):
+        lib.PFACX_flowsOpen.argtypes = [H, C.c_size_t, C.POINTER(C.c_void_p)]
+        lib.PFACX_flowsClose.argtypes = [C.c_void_p]
+        lib.PFACX_flowsReset.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        pieces = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                  C.c_void_p, C.POINTER(C.c_int)]
+        lib.PFACX_flowsMatchFromDevice.argtypes = pieces
+        lib.PFACX_flowsMatchFromHost.argtypes = pieces
+        lib.PFACX_flowsFlush.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -436,6 +446,14 @@ class PFAC:
         self._ret(st, "PFACX_streamOpen", check)
         return Stream(self, s, st)
 
+    # -- many streams advanced by one call (include/pfac_ext.h: PFACX_flows*) ----------------
+    def flowsOpen(self, num_flows: int, check: bool = True) -> "Flows":
+        """``PFACX_flowsOpen`` -> a :class:`Flows` set of ``num_flows`` flows of this handle (``.status`` holds the call's status)."""
+        s = C.c_void_p()
+        st = self._lib.PFACX_flowsOpen(self._h, num_flows, C.byref(s))
+        self._ret(st, "PFACX_flowsOpen", check)
+        return Flows(self, s, num_flows, st)
+
     # -- numpy conveniences over matchFromHost (still the C ABI underneath) ----------
     def match_host_array(self, data):
         import numpy as np
@@ -551,3 +569,88 @@ class Stream:
         pos = np.full(cap, -7, dtype=np.int32)
         _, n = self.flush(ids.ctypes.data, pos.ctypes.data, cap)
         return ids[:n].copy(), pos[:n].copy()
+
+
+class Flows:
+    """One flow set (``PFACX_flows_t``) of a handle: a batch of pieces, each the next piece of one flow, in; per piece the pairs
+    that have become final out.  ``offsets`` (numPieces + 1 ``size_t``) and ``flow_ids`` (numPieces ``unsigned int``) are host
+    arrays; no flow may be named twice in one call."""
+
+    def __init__(self, handle: PFAC, flows: C.c_void_p, num_flows: int, status: int = 0):
+        self._owner = handle
+        self._lib = handle._lib
+        self._f = flows
+        self.num_flows = num_flows
+        self.status = status
+
+    def _ret(self, st: int, where: str, check: bool) -> int:
+        if check and st != 0:
+            raise PFACError(st, where, error_string(st))
+        return st
+
+    def match_device(self, d_input: int, size: int, h_offsets: int, h_flow_ids: int, num_pieces: int, d_ids: int, d_pos: int, capacity: int,
+                     d_piece_first: int, h_piece_offsets: int, check: bool = True):
+        """``PFACX_flowsMatchFromDevice`` -> (status, number of pairs): capacity >= size + num_pieces * (maxPatternLen - 1)."""
+        n = C.c_int(0)
+        st = self._lib.PFACX_flowsMatchFromDevice(self._f, d_input, size, h_offsets, h_flow_ids, num_pieces, d_ids, d_pos, capacity,
+                                                  d_piece_first, h_piece_offsets, C.byref(n))
+        return self._ret(st, "PFACX_flowsMatchFromDevice", check), n.value
+
+    def match_host(self, h_input: int, size: int, h_offsets: int, h_flow_ids: int, num_pieces: int, h_ids: int, h_pos: int, capacity: int,
+                   h_piece_first: int, h_piece_offsets: int, check: bool = True):
+        """``PFACX_flowsMatchFromHost``: follows PFAC_setPlatform (the CPU platforms run on the CPU)."""
+        n = C.c_int(0)
+        st = self._lib.PFACX_flowsMatchFromHost(self._f, h_input, size, h_offsets, h_flow_ids, num_pieces, h_ids, h_pos, capacity,
+                                                h_piece_first, h_piece_offsets, C.byref(n))
+        return self._ret(st, "PFACX_flowsMatchFromHost", check), n.value
+
+    def flush(self, h_flow_ids: int, n_flows: int, ids: int, pos: int, capacity: int, first: int, check: bool = True):
+        """``PFACX_flowsFlush`` -> (status, number of pairs): the end of the named flows; host arrays on a host-fed set, device
+        arrays (``first`` included) on a device-fed one."""
+        n = C.c_int(0)
+        st = self._lib.PFACX_flowsFlush(self._f, h_flow_ids, n_flows, ids, pos, capacity, first, C.byref(n))
+        return self._ret(st, "PFACX_flowsFlush", check), n.value
+
+    def reset(self, flow_ids=None, check: bool = True) -> int:
+        """``PFACX_flowsReset``: the named flows, or (None) all flows and adopt the handle's current pattern set."""
+        import numpy as np
+        if flow_ids is None:
+            return self._ret(self._lib.PFACX_flowsReset(self._f, None, 0), "PFACX_flowsReset", check)
+        f = np.ascontiguousarray(flow_ids, dtype=np.uint32)
+        buf = f if f.size else np.zeros(1, dtype=np.uint32)
+        return self._ret(self._lib.PFACX_flowsReset(self._f, buf.ctypes.data, f.size), "PFACX_flowsReset", check)
+
+    def close(self, check: bool = True) -> int:
+        st = self._lib.PFACX_flowsClose(self._f)
+        self._f = C.c_void_p()
+        return self._ret(st, "PFACX_flowsClose", check)
+
+    def match_host_array(self, data, offsets, flow_ids, check: bool = True):
+        """match_host over numpy arrays -> (status, ids, pos, pieceFirst, pieceOffsets)."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uintp)
+        fl = np.ascontiguousarray(flow_ids, dtype=np.uint32)
+        pieces = fl.size
+        cap = data.size + pieces * max(0, int(self._owner.info().maxPatternLen) - 1) + 1
+        ids = np.full(cap, -7, dtype=np.int32)
+        pos = np.full(cap, -7, dtype=np.int32)
+        first = np.full(pieces + 1, -7, dtype=np.int32)
+        offs = np.zeros(max(1, pieces), dtype=np.uint64)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        flb = fl if fl.size else np.zeros(1, dtype=np.uint32)
+        st, n = self.match_host(buf.ctypes.data, data.size, off.ctypes.data, flb.ctypes.data, pieces, ids.ctypes.data, pos.ctypes.data, cap,
+                                first.ctypes.data, offs.ctypes.data, check=check)
+        return st, ids[:n].copy(), pos[:n].copy(), first, offs[:pieces].copy()
+
+    def flush_host_array(self, flow_ids, check: bool = True):
+        """flush over numpy arrays (a host-fed set) -> (status, ids, pos, first)."""
+        import numpy as np
+        fl = np.ascontiguousarray(flow_ids, dtype=np.uint32)
+        cap = max(1, fl.size * max(0, int(self._owner.info().maxPatternLen) - 1))
+        ids = np.full(cap, -7, dtype=np.int32)
+        pos = np.full(cap, -7, dtype=np.int32)
+        first = np.full(fl.size + 1, -7, dtype=np.int32)
+        flb = fl if fl.size else np.zeros(1, dtype=np.uint32)
+        st, n = self.flush(flb.ctypes.data, fl.size, ids.ctypes.data, pos.ctypes.data, cap, first.ctypes.data, check=check)
+        return st, ids[:n].copy(), pos[:n].copy(), first

@@ -20,7 +20,7 @@
 namespace pfac_internal {
 
 /* offsets[0] == 0, offsets[n] == size, never decreasing */
-static bool offsetsValid(const size_t *offsets, size_t numSegments, size_t size)
+bool batchOffsetsValid(const size_t *offsets, size_t numSegments, size_t size)
 {
     if (offsets[0] != 0 || offsets[numSegments] != size) return false;
     for (size_t k = 0; k < numSegments; k++)
@@ -102,7 +102,7 @@ PFAC_status_t PFACX_matchBatchFromHost(PFAC_handle_t handle, char *h_input, size
     if (!h_input || !h_offsets || !h_matched_result) return PFAC_STATUS_INVALID_PARAMETER;
     if (size == 0) return PFAC_STATUS_SUCCESS;
     if (numSegments == 0 || numSegments >= SIZE_MAX / sizeof(size_t)) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!offsetsValid(h_offsets, numSegments, size)) return PFAC_STATUS_INVALID_PARAMETER;
+    if (!batchOffsetsValid(h_offsets, numSegments, size)) return PFAC_STATUS_INVALID_PARAMETER;
     if (handle->platform != PFAC_PLATFORM_GPU) return matchBatchOnCpu(handle, h_input, h_offsets, numSegments, h_matched_result);
     std::lock_guard<std::mutex> guard(handle->lock);
     return matchBatchHostOnGpu(handle, h_input, size, h_offsets, numSegments, h_matched_result);

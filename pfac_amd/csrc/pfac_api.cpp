@@ -72,6 +72,9 @@ static void freeScratch(PFAC_context *c)
 {
     freeHostStage(c);
     c->scratch.release();
+    if (c->h_flowPieces) (void)hipHostFree(c->h_flowPieces);       /* the pinned descriptors of the flows calls (flows_api.cpp) */
+    c->h_flowPieces = nullptr;
+    c->h_flowPiecesBytes = 0;
     c->orderCleanBase = nullptr;
 }
 
@@ -291,9 +294,10 @@ PFAC_status_t loadModule(PFAC_context *c)
     c->fold_input_ptr = (PFACX_foldInput_protoType)dlsym(m, "PFACX_foldInput");
     c->stream_seam_ptr = (PFACX_streamSeam_protoType)dlsym(m, "PFACX_streamSeam");
     c->stream_reduce_ptr = (PFACX_streamReduce_protoType)dlsym(m, "PFACX_streamReduce");
+    c->flows_run_ptr = (PFACX_flowsRun_protoType)dlsym(m, "PFACX_flowsRun");
     if (!c->kernel_time_driven_ptr || !c->kernel_space_driven_ptr || !c->reduce_kernel_ptr ||
         !c->reduce_inplace_kernel_ptr || !c->batch_fixup_ptr || !c->batch_reduce_fixup_ptr || !c->all_reduce_ptr || !c->all_expand_ptr ||
-        !c->fold_input_ptr || !c->stream_seam_ptr || !c->stream_reduce_ptr)
+        !c->fold_input_ptr || !c->stream_seam_ptr || !c->stream_reduce_ptr || !c->flows_run_ptr)
         return PFAC_STATUS_INTERNAL_ERROR;
     return PFAC_STATUS_SUCCESS;
 }
@@ -373,6 +377,7 @@ PFAC_status_t PFAC_destroy(PFAC_handle_t handle)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
     closeAllStreams(handle);
+    closeAllFlowSets(handle);
     freeResources(handle);
     /* drops this handle's reference; the module stays mapped while other handles hold theirs (dlopen refcounts) */
     if (handle->module) dlclose(handle->module);
@@ -630,7 +635,7 @@ PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info)
         /* what the pattern set holds on the device -- the chained tables, the initial row, the prefilter bitmaps, the launch counters, the
          * reference-layout table only while PFACX_KERNEL_REFTABLE has asked for it -- and the carried bytes of device-fed streams: state, not
          * scratch (PFACX_trim keeps them) */
-        v.deviceTableBytes = handle->tables.bytes() + streamDeviceBytes(handle);
+        v.deviceTableBytes = handle->tables.bytes() + streamDeviceBytes(handle) + flowsDeviceBytes(handle);
         /* ... and what its calls have left allocated (grow-only, PFACX_trim gives it back) */
         v.deviceScratchBytes = handle->scratch.bytes();
         if (handle->h_modeHint) {

@@ -53,6 +53,7 @@ constexpr int kHostPairCountWord = 4;             /* word of the handle's mapped
 constexpr int kHostAllTotalWord = 8;              /* words 8-9 of h_modeHint: the 64-bit length of an all-match call's list (scan_all.hip: pfac_all_block_scan) ... */
 constexpr int kHostAllDoneWord = 10;              /* ... and the sequence number its last launch writes (pfac_all_done) */
 constexpr int kHostSeamCountWord = 12;             /* words 12-13 of h_modeHint: the pairs a stream call's seam launch wrote (scan_stream.hip: pfac_stream_seam) and the sequence number it writes behind them */
+constexpr int kHostFlowsCountWord = 14;            /* words 14-15 of h_modeHint: the pairs of a flows call (scan_flows.hip: pfac_flows_done) and the sequence number written behind them */
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -383,12 +384,16 @@ struct DeviceScratch {
     DeviceBuffer<int> allPairs;
     DeviceBuffer<int> allSegFirst;
     DeviceBuffer<char> all;
+    /* the flow sets (PFACX_flows*, flows_api.cpp): ONE allocation a call cuts into the uploaded piece descriptors, the per-piece counts, the staged
+     * seam pairs, the staged pairs of the scan and (sets whose seams do not fit the LDS) the seams' stage */
+    DeviceBuffer<char> flows;
+    DeviceBuffer<char> flowPieces;            /* ... and the piece descriptors alone: uploaded from pinned host memory (PFAC_context::h_flowPieces) under the scan, before its count is known */
     DeviceBuffer<char> fold;                  /* caseless sets: the caller's device input folded (PFACX_foldInput), what the scan of a device call reads instead; 256-byte granules */
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
-        f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(fold);
+        f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }
@@ -461,6 +466,7 @@ struct PFAC_context {
     PFACX_foldInput_protoType fold_input_ptr = nullptr;              /* scan_fold.hip: the input fold of a caseless set */
     PFACX_streamSeam_protoType stream_seam_ptr = nullptr;            /* scan_stream.hip: the seam of a stream call (PFACX_stream*) */
     PFACX_streamReduce_protoType stream_reduce_ptr = nullptr;        /* scan_module.hip: the compacted scan of a piece whose last bytes are read-ahead only */
+    PFACX_flowsRun_protoType flows_run_ptr = nullptr;                /* scan_flows.hip: the seams and the merge of a flows call (PFACX_flows*) */
 
     int platform = PFAC_PLATFORM_GPU;
     int perfMode = PFAC_TIME_DRIVEN;
@@ -485,6 +491,11 @@ struct PFAC_context {
     std::vector<PFACX_stream_s *> streams;
     unsigned long long setGeneration = 0;
     unsigned int seamSeq = 0;                 /* number of the last seam launch (pfac_stream_seam writes it to host memory) */
+    /* flow sets (PFACX_flows*, flows_api.cpp): the open sets of this handle (PFAC_destroy closes them); their carries are state like the streams' */
+    std::vector<PFACX_flows_s *> flowSets;
+    void *h_flowPieces = nullptr;             /* pinned host memory a flows call builds its piece descriptors in (grow-only; freed with the scratch) */
+    size_t h_flowPiecesBytes = 0;
+    unsigned int flowsSeq = 0;                /* number of the last flows call (pfac_flows_done writes it to host memory) */
 
     bool hasDevice = false;
     int device = -1;

@@ -78,6 +78,19 @@ inline int compactPairs(const int *results, size_t owned, int posShift, int *ids
 /* stream_api.cpp: PFAC_destroy closes the handle's streams; the device bytes their carries hold (PFACX_getInfo: deviceTableBytes) */
 void closeAllStreams(PFAC_context *c);
 size_t streamDeviceBytes(const PFAC_context *c);
+/* ... and what the stream and the flows calls share: how a piece of `size` bytes splits the work of a stream that carries `carried` bytes
+ * (of the pending and the piece's positions the first seam + owned are final, `seam` of them carried), and the longest match at
+ * positions [0, owned) of `readable` host bytes as (id, position + posShift) pairs, on the CPU platforms (scratch: `readable` ints) and on
+ * the GPU platform (the pipelined host path); the caller holds c->lock */
+struct StreamSplit { size_t seam, owned; };
+StreamSplit streamSplitOf(size_t carried, size_t size, size_t M);
+PFAC_status_t streamCpuPairs(PFAC_context *c, const char *in, size_t owned, size_t readable, int posShift, int *scratch, int *ids, int *pos, int *count);
+PFAC_status_t streamGpuPairs(PFAC_context *c, char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count);
+/* flows_api.cpp: PFAC_destroy closes the handle's flow sets; the device bytes their carries hold (PFACX_getInfo: deviceTableBytes) */
+void closeAllFlowSets(PFAC_context *c);
+size_t flowsDeviceBytes(const PFAC_context *c);
+/* batch_api.cpp: offsets[0] == 0, offsets[n] == size, never decreasing */
+bool batchOffsetsValid(const size_t *offsets, size_t numSegments, size_t size);
 /* batch_api.cpp: the batch calls (PFACX_matchBatch*) behind their argument checks; the caller holds c->lock */
 PFAC_status_t ensurePatternLen(PFAC_context *c);            /* the device copy of fa.patternLen the batch fix-ups read */
 PFAC_status_t matchBatchDeviceLocked(PFAC_context *c, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments, int *d_matched_result);

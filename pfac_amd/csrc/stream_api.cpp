@@ -92,8 +92,8 @@ static PFAC_status_t ensureStreamDevice(PFACX_stream_s *s, int M)
 }
 
 /* how a piece of `size` bytes splits the work: of the positions [R, T + size) the first `finalAll` are final; `seam` of them are carried */
-struct Split { size_t seam, owned; };
-static Split splitOf(size_t carried, size_t size, size_t M)
+using Split = StreamSplit;
+StreamSplit streamSplitOf(size_t carried, size_t size, size_t M)
 {
     const size_t all = carried + size;
     const size_t finalAll = all >= M - 1 ? all - (M - 1) : 0;
@@ -105,7 +105,7 @@ static Split splitOf(size_t carried, size_t size, size_t M)
 
 /* the longest match at positions [0, owned) of `readable` host bytes as (id, position + posShift) pairs behind ids / pos; CPU platforms
  * (the caller holds c->lock: the tables first, then the match that needs no lock of its own) */
-static PFAC_status_t cpuPairs(PFAC_context *c, const char *in, size_t owned, size_t readable, int posShift, int *scratch, int *ids, int *pos, int *count)
+PFAC_status_t streamCpuPairs(PFAC_context *c, const char *in, size_t owned, size_t readable, int posShift, int *scratch, int *ids, int *pos, int *count)
 {
     PFAC_status_t st = prepareCpuPlatformLocked(c);
     if (st == PFAC_STATUS_SUCCESS) st = matchHostOnCpuPlatformPrepared(c, in, readable, scratch);
@@ -115,7 +115,7 @@ static PFAC_status_t cpuPairs(PFAC_context *c, const char *in, size_t owned, siz
 }
 
 /* ... on the GPU platform (the caller holds c->lock): the pipelined host path, positions [0, owned), the rest read-ahead */
-static PFAC_status_t gpuPairs(PFAC_context *c, char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count)
+PFAC_status_t streamGpuPairs(PFAC_context *c, char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count)
 {
     int n = 0;
     const PFAC_status_t st = matchHostReduceOnGpu(c, in, owned, readable, 0, ids, pos, &n);
@@ -198,7 +198,7 @@ PFAC_status_t PFACX_streamMatchFromDevice(PFACX_stream_t stream, char *d_piece, 
     if (!c->hasDevice || !c->module || !c->stream_seam_ptr || !c->stream_reduce_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
     correctTextureMode(c);
-    const Split sp = splitOf(stream->carried, size, M);
+    const Split sp = streamSplitOf(stream->carried, size, M);
     int seamPairs = 0, piecePairs = 0;
     size_t nextCarried = 0;
     if (M > 1) {
@@ -247,7 +247,7 @@ PFAC_status_t PFACX_streamMatchFromHost(PFACX_stream_t stream, char *h_piece, si
     const bool gpu = c->platform == PFAC_PLATFORM_GPU;
     if (gpu && (!c->hasDevice || !c->module)) return PFAC_STATUS_LIB_NOT_EXIST;
     const size_t carried = stream->carried;
-    const Split sp = splitOf(carried, size, M);
+    const Split sp = streamSplitOf(carried, size, M);
     const size_t head = std::min(size, M - 1);
     int seamPairs = 0, piecePairs = 0;
     try {
@@ -260,22 +260,22 @@ PFAC_status_t PFACX_streamMatchFromHost(PFACX_stream_t stream, char *h_piece, si
             seamIds.resize(sp.seam);
             seamPos.resize(sp.seam);
             if (gpu) {
-                st = gpuPairs(c, reinterpret_cast<char *>(seam.data()), sp.seam, seam.size(), -(int)carried, seamIds.data(), seamPos.data(), &seamPairs);
+                st = streamGpuPairs(c, reinterpret_cast<char *>(seam.data()), sp.seam, seam.size(), -(int)carried, seamIds.data(), seamPos.data(), &seamPairs);
             } else {
                 std::vector<int> scratch(seam.size());
-                st = cpuPairs(c, reinterpret_cast<const char *>(seam.data()), sp.seam, seam.size(), -(int)carried, scratch.data(), seamIds.data(),
+                st = streamCpuPairs(c, reinterpret_cast<const char *>(seam.data()), sp.seam, seam.size(), -(int)carried, scratch.data(), seamIds.data(),
                               seamPos.data(), &seamPairs);
             }
             if (st != PFAC_STATUS_SUCCESS) return st;
         }
         if (sp.owned) {
             if (gpu) {
-                st = gpuPairs(c, h_piece, sp.owned, size, 0, h_ids + seamPairs, h_pos + seamPairs, &piecePairs);
+                st = streamGpuPairs(c, h_piece, sp.owned, size, 0, h_ids + seamPairs, h_pos + seamPairs, &piecePairs);
             } else {
                 /* every position's longest match into the caller's array behind the room of the seam's pairs (capacity >= size + M),
                  * compacted forward in place: pair z comes from an entry at or behind M - 1 + z */
                 int *scratch = h_ids + (M - 1);
-                st = cpuPairs(c, h_piece, sp.owned, size, 0, scratch, h_ids + seamPairs, h_pos + seamPairs, &piecePairs);
+                st = streamCpuPairs(c, h_piece, sp.owned, size, 0, scratch, h_ids + seamPairs, h_pos + seamPairs, &piecePairs);
             }
             if (st != PFAC_STATUS_SUCCESS) return st;
         }
@@ -317,10 +317,10 @@ PFAC_status_t PFACX_streamFlush(PFACX_stream_t stream, int *ids, int *pos, size_
         try {
             if (c->platform == PFAC_PLATFORM_GPU) {
                 if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
-                st = gpuPairs(c, reinterpret_cast<char *>(stream->h_carry.data()), carried, carried, -(int)carried, ids, pos, &pairs);
+                st = streamGpuPairs(c, reinterpret_cast<char *>(stream->h_carry.data()), carried, carried, -(int)carried, ids, pos, &pairs);
             } else {
                 std::vector<int> scratch(carried);
-                st = cpuPairs(c, reinterpret_cast<const char *>(stream->h_carry.data()), carried, carried, -(int)carried, scratch.data(), ids, pos, &pairs);
+                st = streamCpuPairs(c, reinterpret_cast<const char *>(stream->h_carry.data()), carried, carried, -(int)carried, scratch.data(), ids, pos, &pairs);
             }
         } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
         if (st != PFAC_STATUS_SUCCESS) return st;

@@ -6,7 +6,11 @@
  * compiler on a machine without a GPU, (b) compare the compiled tables
  * byte-for-byte with the oracle, (c) read the facts a multi-GPU driver needs
  * (maximum pattern length = slice overlap, reference omp_PFAC.cpp:324) and
- * (d) A/B the kernel variants.
+ * (d) A/B the kernel variants.  On top of that come the features the reference
+ * does not have: batches of segments (PFACX_matchBatch*), every pattern at a
+ * position (PFACX_matchAll*), caseless sets (PFACX_READ_NOCASE), streams
+ * (PFACX_stream*), flow sets (PFACX_flows*) and the lines that contain a
+ * pattern (PFACX_matchLines*, PFACX_gatherLinesFromDevice).
  */
 #ifndef PFAC_EXT_H_
 #define PFAC_EXT_H_
@@ -411,6 +415,52 @@ PFAC_status_t PFACX_flowsMatchFromHost(PFACX_flows_t flows, char *h_input, size_
 /* declare the end of the n named flows: their pending pairs, flow by flow in the order named; first[n + 1] indexes them */
 PFAC_status_t PFACX_flowsFlush(PFACX_flows_t flows, const unsigned int *h_flowIds, size_t n, int *ids, int *pos, size_t capacity, int *first,
                                int *h_num_matched);
+
+/* Lines: the lines of a buffer that contain a pattern -- grep -F -f patterns -- or, with PFACX_LINES_INVERT, the lines that contain none (grep -v).
+ *   LINES.  Let the input have n bytes and q_0 < ... < q_(K-1) be the positions of its '\n' bytes.  Line k, k < K, is the bytes [q_(k-1) + 1, q_k)
+ *   with q_(-1) = -1: the '\n' is not part of the line, a '\r' in front of it is.  If n > 0 and the last byte is not '\n', the bytes behind the last
+ *   '\n' are one more line (also when it is the only one); an input that ends in '\n' has no empty line behind it -- what wc -l and grep count.
+ *   numLines is K or K + 1; n == 0 has no lines.
+ *   A line MATCHES if the full result of PFAC_matchFromHost on a CPU platform over the whole buffer is non-zero at some position of the line.  No
+ *   pattern contains '\n' (the pattern format ends a pattern there), so this is "a pattern occurs inside the line"; an empty line never matches.
+ *   A caseless handle (PFACX_READ_NOCASE) folds patterns and input as in every other call; '\n' is not a letter, the line ends are those of the
+ *   caller's bytes, and the caller's buffer is never modified.
+ * PFACX_matchLines*: the selected lines in ascending order, each once however many matches it holds: lineStart[i] = the offset of the line's first
+ * byte, lineLen[i] = its length without the '\n' (0 is possible under INVERT), lineIndex[i] (unless the pointer is null) = its 0-based number k.
+ * *h_numLines and *h_numSelected are always written on success.
+ * capacity: entries of each array, >= size (smaller: PFAC_STATUS_INVALID_PARAMETER).  lineStart / lineLen double as the scan's pair list, as the
+ * arrays of every compacted call do: entries below `size` may be overwritten beyond the lines returned; nothing is written at or beyond capacity.
+ * numLines <= size: the list is never truncated.
+ * size >= 2^31, an unknown flag bit, a null pointer other than lineIndex: PFAC_STATUS_INVALID_PARAMETER; no pattern set: PFAC_STATUS_PATTERNS_NOT_READY;
+ * size == 0: success, 0 lines, 0 selected, nothing touched; the device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.
+ * Both calls are synchronous (the counts come to the host) and take the handle's lock like the other match calls.  The device form runs on whatever
+ * kernel variant, walker, perf mode and texture mode the handle selects.  The host form follows PFAC_setPlatform: the CPU platforms, host-only
+ * handles included, run entirely on the CPU (the CPU matcher plus memchr); the GPU platform runs the pipelined path of PFAC_matchFromHostReduce and
+ * does the line work on the host.
+ * MEMORY of the device form: grow-only handle scratch of about 0.32 bytes per input byte -- with B = (size + 15) / 2048 + 1: 256 B + (256 B + 256) +
+ * 128 B + 2 x (4 (B + 1) + 4 (B + 1) + 4 B) bytes, each term rounded up to 256 -- a function of the size, not of the data: deviceScratchBytes of
+ * PFACX_getInfo, freed by PFACX_trim, not allocated before the first lines call.
+ * COST: the compacted scan without its ordering launches, one more streaming read of the input, and passes over size / 8 bytes of
+ * bitmaps.
+ *
+ * PFACX_gatherLinesFromDevice: the lines (d_lineStart[i], d_lineLen[i]), i < numSelected, of d_input written as text into d_out, in list order:
+ * line i's bytes, then a '\n' behind every line -- behind a last line that had none in the input too, as grep prints it.  *h_outBytes = the sum of
+ * lineLen[i] + 1 (at most size + 1 for a list of PFACX_matchLines*).  More than outCapacity: PFACX_STATUS_OUTPUT_TRUNCATED, *h_outBytes still the
+ * full size, nothing written at or beyond outCapacity, the contents of d_out unspecified.  numSelected == 0: success, *h_outBytes = 0, d_out may be
+ * null.  The line arrays are DEVICE memory and the caller's contract, as the device offsets of the batch calls are: the kernels clamp every (start,
+ * len) to [0, size] (*h_outBytes counts the clamped lengths), so bad arrays give wrong text but never an access outside the buffers.  The call reads
+ * the caller's original bytes, never a folded copy.  Synchronous; scratch: 8 bytes per selected line (deviceScratchBytes). */
+#define PFACX_LINES_INVERT 1u     /* select the lines that do NOT match (grep -v) */
+
+PFAC_status_t PFACX_matchLinesFromDevice(PFAC_handle_t handle, char *d_input, size_t size, unsigned int flags,
+                                         int *d_lineStart, int *d_lineLen, int *d_lineIndex /* may be NULL */, size_t capacity,
+                                         size_t *h_numLines, size_t *h_numSelected);
+PFAC_status_t PFACX_matchLinesFromHost  (PFAC_handle_t handle, char *h_input, size_t size, unsigned int flags,
+                                         int *h_lineStart, int *h_lineLen, int *h_lineIndex /* may be NULL */, size_t capacity,
+                                         size_t *h_numLines, size_t *h_numSelected);
+PFAC_status_t PFACX_gatherLinesFromDevice(PFAC_handle_t handle, const char *d_input, size_t size,
+                                          const int *d_lineStart, const int *d_lineLen, size_t numSelected,
+                                          char *d_out, size_t outCapacity, size_t *h_outBytes);
 
 #ifdef __cplusplus
 }

@@ -136,6 +136,25 @@ typedef struct {
 PFAC_status_t PFACX_flowsRun(PFAC_handle_t handle, const PFACX_flowsRun_t *run, int *h_total);
 typedef PFAC_status_t (*PFACX_flowsRun_protoType)(PFAC_handle_t, const PFACX_flowsRun_t *, int *);
 
+/* Lines (no reference counterpart; include/pfac_ext.h: PFACX_matchLines* / PFACX_gatherLines*), scan_lines.hip.
+ * PFACX_linesSelect: the lines of d_input[0, size) -- 0 < size < 2^31 -- that contain a match (invert != 0: that contain none).  d_scan is what the
+ * compacted scan reads: d_input, or its folded copy for a caseless set; the newline bitmap is made from d_input.  The scan (PFAC_reduce_kernel, hashed
+ * != 0: PFAC_reduce_inplace_kernel, with its pairs left unordered) uses d_lineStart / d_lineLen (`size` entries at least) as its pair list; the
+ * select pass then overwrites them -- and d_lineIndex unless null -- with the selected lines in ascending order.  Synchronous.
+ * PFACX_linesGather: the text of numSelected lines (start, len) of d_input, each clamped to [0, size], a '\n' behind every line, into d_out; nothing is
+ * written at or beyond outCapacity; *h_outBytes = the size of the whole text.  Synchronous. */
+PFAC_status_t PFACX_linesSelect(PFAC_handle_t handle, const char *d_input, char *d_scan, size_t size, int invert, int hashed, int *d_lineStart,
+                                int *d_lineLen, int *d_lineIndex, size_t *h_numLines, size_t *h_numSelected);
+PFAC_status_t PFACX_linesGather(PFAC_handle_t handle, const char *d_input, size_t size, const int *d_lineStart, const int *d_lineLen,
+                                size_t numSelected, char *d_out, size_t outCapacity, size_t *h_outBytes);
+typedef PFAC_status_t (*PFACX_linesSelect_protoType)(PFAC_handle_t, const char *, char *, size_t, int, int, int *, int *, int *, size_t *, size_t *);
+typedef PFAC_status_t (*PFACX_linesGather_protoType)(PFAC_handle_t, const char *, size_t, const int *, const int *, size_t, char *, size_t, size_t *);
+
+/* Measurement only: the newline pass of PFACX_linesSelect alone (pfac_lines_bitmap: one read of the input, size / 8 + size / 8 + size / 16 bytes written
+ * into the handle's lines scratch).  Returns the average milliseconds of `launches` launches over the first n < 2^31 bytes of d_in, or a negative
+ * value on an error.  tools/lines_sweep.py reports it next to the fold kernel's rate. */
+double PFACX_linesBitmapProbe(PFAC_handle_t handle, const void *d_in, size_t n, int launches);
+
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of
  * `launches` launches over the first n bytes (a multiple of 4096) of d_in, or a negative value on a HIP error.

@@ -27,6 +27,7 @@ PFAC_TIME_DRIVEN, PFAC_SPACE_DRIVEN = 0, 1
 PFACX_KERNEL_FILTER, PFACX_KERNEL_NAIVE, PFACX_KERNEL_AUTO, PFACX_KERNEL_REFTABLE = 0, 1, 2, 3
 PFACX_WALKER_AUTO, PFACX_WALKER_WINDOW, PFACX_WALKER_STAGE, PFACX_WALKER_VETO = 0, 1, 2, 3
 PFACX_READ_STRICT, PFACX_READ_STRIP_CR, PFACX_READ_NOCASE = 1, 2, 8
+PFACX_LINES_INVERT = 1                          # pfac_ext.h: PFACX_matchLines* select the lines that do NOT match
 (PFACX_TABLE_DENSE, PFACX_TABLE_HASH_ROWPTR, PFACX_TABLE_HASH_VALPTR, PFACX_TABLE_INITIAL_ROW,
  PFACX_TABLE_FILTER_GRAM3, PFACX_TABLE_FILTER_SHORT, PFACX_TABLE_FILTER_LADDER, PFACX_TABLE_FILTER_FINAL3,
  PFACX_TABLE_CHAIN) = range(9)
@@ -106,6 +107,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_matchAllFromDevice", "PFACX_matchAllFromHost", "PFACX_matchAllBatchFromDevice",
     "PFACX_streamOpen", "PFACX_streamReset", "PFACX_streamClose", "PFACX_streamMatchFromDevice", "PFACX_streamMatchFromHost", "PFACX_streamFlush",
     "PFACX_flowsOpen", "PFACX_flowsClose", "PFACX_flowsReset", "PFACX_flowsMatchFromDevice", "PFACX_flowsMatchFromHost", "PFACX_flowsFlush",
+    "PFACX_matchLinesFromDevice", "PFACX_matchLinesFromHost", "PFACX_gatherLinesFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -113,6 +115,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_batchFixup", "PFACX_batchReduceFixup",
     "PFACX_allReduce", "PFACX_allExpand", "PFACX_foldInput",
     "PFACX_streamSeam", "PFACX_streamReduce", "PFACX_flowsRun",
+    "PFACX_linesSelect", "PFACX_linesGather", "PFACX_linesBitmapProbe",
 )
 
 
@@ -194,6 +197,12 @@ def load_library() -> C.CDLL:
         lib.PFACX_flowsMatchFromDevice.argtypes = pieces
         lib.PFACX_flowsMatchFromHost.argtypes = pieces
         lib.PFACX_flowsFlush.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]
+    if hasattr(lib, "PFACX_matchLinesFromDevice"):
+        SZ = C.POINTER(C.c_size_t)
+        lines = [H, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, SZ, SZ]
+        lib.PFACX_matchLinesFromDevice.argtypes = lines
+        lib.PFACX_matchLinesFromHost.argtypes = lines
+        lib.PFACX_gatherLinesFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, SZ]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -437,6 +446,43 @@ class PFAC:
         st, n = self.matchAllFromHost(data.ctypes.data, data.size, ids.ctypes.data, pos.ctypes.data, cap, check=False)
         self._ret(st, "PFACX_matchAllFromHost", True)
         return pos[:n].copy(), ids[:n].copy()
+
+    # -- the lines that contain a pattern (include/pfac_ext.h: PFACX_matchLines*) ------------
+    def matchLinesFromDevice(self, d_input: int, size: int, flags: int, d_line_start: int, d_line_len: int, d_line_index, capacity: int,
+                             check: bool = True):
+        """``PFACX_matchLinesFromDevice`` -> (status, number of lines, number of selected lines); `d_line_index` may be None."""
+        nl, ns = C.c_size_t(0), C.c_size_t(0)
+        st = self._lib.PFACX_matchLinesFromDevice(self._h, d_input, size, flags, d_line_start, d_line_len, d_line_index, capacity,
+                                                  C.byref(nl), C.byref(ns))
+        return self._ret(st, "PFACX_matchLinesFromDevice", check), nl.value, ns.value
+
+    def matchLinesFromHost(self, h_input: int, size: int, flags: int, h_line_start: int, h_line_len: int, h_line_index, capacity: int,
+                           check: bool = True):
+        """``PFACX_matchLinesFromHost`` -> (status, number of lines, number of selected lines); `h_line_index` may be None."""
+        nl, ns = C.c_size_t(0), C.c_size_t(0)
+        st = self._lib.PFACX_matchLinesFromHost(self._h, h_input, size, flags, h_line_start, h_line_len, h_line_index, capacity,
+                                                C.byref(nl), C.byref(ns))
+        return self._ret(st, "PFACX_matchLinesFromHost", check), nl.value, ns.value
+
+    def gatherLinesFromDevice(self, d_input: int, size: int, d_line_start: int, d_line_len: int, num_selected: int, d_out, out_capacity: int,
+                              check: bool = True):
+        """``PFACX_gatherLinesFromDevice`` -> (status, size of the whole text).  OUTPUT_TRUNCATED is returned, not raised."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_gatherLinesFromDevice(self._h, d_input, size, d_line_start, d_line_len, num_selected, d_out, out_capacity, C.byref(n))
+        return self._ret(st, "PFACX_gatherLinesFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def match_lines_host_array(self, data, invert: bool = False):
+        """matchLinesFromHost over a numpy array -> (number of lines, line_start, line_len, line_index) of the lines that contain a
+        pattern (invert: that contain none), ascending."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        cap = max(1, data.size)
+        start = np.full(cap, -7, dtype=np.int32)
+        length = np.full(cap, -7, dtype=np.int32)
+        index = np.full(cap, -7, dtype=np.int32)
+        _, nl, ns = self.matchLinesFromHost(data.ctypes.data if data.size else start.ctypes.data, data.size, PFACX_LINES_INVERT if invert else 0,
+                                            start.ctypes.data, length.ctypes.data, index.ctypes.data, cap)
+        return nl, start[:ns].copy(), length[:ns].copy(), index[:ns].copy()
 
     # -- input that arrives in pieces (include/pfac_ext.h: PFACX_stream*) ----------------
     def streamOpen(self, check: bool = True) -> "Stream":

@@ -242,12 +242,12 @@ static PFAC_status_t bindCommon(PFAC_context *c)
         /* the word the scan kernel tells the host through what the stream looked like (pfac_context.h); without it AUTO means
          * the register-window walker */
         void *h = nullptr, *d = nullptr;
-        if (hipHostMalloc(&h, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
+        if (hipHostMalloc(&h, pfac::kHostWords * sizeof(unsigned int), hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
             c->h_modeHint = static_cast<unsigned int *>(h);
             c->d_modeHint = static_cast<unsigned int *>(d);
             /* every word: [1] routes PFACX_KERNEL_AUTO, [4] / [5] are the pair count and the sequence number a compacted-output call polls
              * (sequence numbers are never 0); hipHostMalloc does not promise zeros, and a block given back by freeResources may come back stale */
-            std::memset(h, 0, 64);
+            std::memset(h, 0, pfac::kHostWords * sizeof(unsigned int));
         } else {
             if (h) (void)hipHostFree(h);
             (void)hipGetLastError();
@@ -295,9 +295,11 @@ PFAC_status_t loadModule(PFAC_context *c)
     c->stream_seam_ptr = (PFACX_streamSeam_protoType)dlsym(m, "PFACX_streamSeam");
     c->stream_reduce_ptr = (PFACX_streamReduce_protoType)dlsym(m, "PFACX_streamReduce");
     c->flows_run_ptr = (PFACX_flowsRun_protoType)dlsym(m, "PFACX_flowsRun");
+    c->lines_select_ptr = (PFACX_linesSelect_protoType)dlsym(m, "PFACX_linesSelect");
+    c->lines_gather_ptr = (PFACX_linesGather_protoType)dlsym(m, "PFACX_linesGather");
     if (!c->kernel_time_driven_ptr || !c->kernel_space_driven_ptr || !c->reduce_kernel_ptr ||
         !c->reduce_inplace_kernel_ptr || !c->batch_fixup_ptr || !c->batch_reduce_fixup_ptr || !c->all_reduce_ptr || !c->all_expand_ptr ||
-        !c->fold_input_ptr || !c->stream_seam_ptr || !c->stream_reduce_ptr || !c->flows_run_ptr)
+        !c->fold_input_ptr || !c->stream_seam_ptr || !c->stream_reduce_ptr || !c->flows_run_ptr || !c->lines_select_ptr || !c->lines_gather_ptr)
         return PFAC_STATUS_INTERNAL_ERROR;
     return PFAC_STATUS_SUCCESS;
 }

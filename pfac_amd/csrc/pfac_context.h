@@ -54,6 +54,9 @@ constexpr int kHostAllTotalWord = 8;              /* words 8-9 of h_modeHint: th
 constexpr int kHostAllDoneWord = 10;              /* ... and the sequence number its last launch writes (pfac_all_done) */
 constexpr int kHostSeamCountWord = 12;             /* words 12-13 of h_modeHint: the pairs a stream call's seam launch wrote (scan_stream.hip: pfac_stream_seam) and the sequence number it writes behind them */
 constexpr int kHostFlowsCountWord = 14;            /* words 14-15 of h_modeHint: the pairs of a flows call (scan_flows.hip: pfac_flows_done) and the sequence number written behind them */
+constexpr int kHostLinesWord = 16;                 /* words 16-18 of h_modeHint: the lines and the selected lines of a lines call (scan_lines.hip: pfac_lines_block_scan) and the sequence number written behind them */
+constexpr int kHostGatherWord = 20;                /* words 20-22 of h_modeHint: the 64-bit size of a gather's text (scan_lines.hip: pfac_lines_scan64) and the sequence number written behind it */
+constexpr int kHostWords = 32;                     /* words of the handle's mapped host memory (h_modeHint) */
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -389,11 +392,15 @@ struct DeviceScratch {
     DeviceBuffer<char> flows;
     DeviceBuffer<char> flowPieces;            /* ... and the piece descriptors alone: uploaded from pinned host memory (PFAC_context::h_flowPieces) under the scan, before its count is known */
     DeviceBuffer<char> fold;                  /* caseless sets: the caller's device input folded (PFACX_foldInput), what the scan of a device call reads instead; 256-byte granules */
+    /* the lines calls (PFACX_matchLines* / PFACX_gatherLines*, scan_lines.hip): ONE allocation a call cuts into the newline bitmap, the line-hit bitmap,
+     * the per-word ranks and the per-block counts (a fixed function of the input size: scan_lines.hip has the formula), or into the offsets of a gather;
+     * not allocated before the first lines call */
+    DeviceBuffer<char> lines;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
-        f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold);
+        f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }
@@ -467,6 +474,8 @@ struct PFAC_context {
     PFACX_streamSeam_protoType stream_seam_ptr = nullptr;            /* scan_stream.hip: the seam of a stream call (PFACX_stream*) */
     PFACX_streamReduce_protoType stream_reduce_ptr = nullptr;        /* scan_module.hip: the compacted scan of a piece whose last bytes are read-ahead only */
     PFACX_flowsRun_protoType flows_run_ptr = nullptr;                /* scan_flows.hip: the seams and the merge of a flows call (PFACX_flows*) */
+    PFACX_linesSelect_protoType lines_select_ptr = nullptr;          /* scan_lines.hip: the lines calls (PFACX_matchLines* / PFACX_gatherLines*) */
+    PFACX_linesGather_protoType lines_gather_ptr = nullptr;
 
     int platform = PFAC_PLATFORM_GPU;
     int perfMode = PFAC_TIME_DRIVEN;
@@ -496,6 +505,7 @@ struct PFAC_context {
     void *h_flowPieces = nullptr;             /* pinned host memory a flows call builds its piece descriptors in (grow-only; freed with the scratch) */
     size_t h_flowPiecesBytes = 0;
     unsigned int flowsSeq = 0;                /* number of the last flows call (pfac_flows_done writes it to host memory) */
+    unsigned int linesSeq = 0;                /* number of the last lines / gather call (pfac_lines_done writes it to host memory) */
 
     bool hasDevice = false;
     int device = -1;

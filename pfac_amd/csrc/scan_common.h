@@ -9,6 +9,7 @@
  *   scan_module.hip   the four symbols of the plugin seam (include/pfac_module.h), launch plans, stream probe
  *   scan_stream.hip   pfac_stream_seam: the seam between a stream's carried bytes and its next piece (PFACX_stream*)
  *   scan_flows.hip    pfac_flows_*: the seams of many streams in one launch and the merge with one scan's pairs (PFACX_flows*)
+ *   scan_lines.hip    pfac_lines_*: the newline bitmap, the lines the scan's pairs fall into, their selection and gather (PFACX_matchLines*)
  */
 #ifndef PFAC_SCAN_COMMON_H_
 #define PFAC_SCAN_COMMON_H_

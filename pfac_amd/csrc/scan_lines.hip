@@ -1,0 +1,661 @@
+/*
+ * scan_lines.hip -- lines (include/pfac_ext.h: PFACX_matchLines* / PFACX_gatherLines*): the lines of a buffer that contain a
+ * pattern, or that contain none, and their text.
+ *
+ * No pattern contains '\n' (the pattern format ends a pattern there), so no match crosses a line end: the plain compacted scan of the whole
+ * buffer is exact per line, and all that is left is to say which line a pair falls into.  Everything below is indexed by q = p + mis, the
+ * position p counted from the aligned 16-byte block that holds the first input byte (mis = address & 15): a misaligned caller pointer costs
+ * nothing but that offset.  A line is named by the '\n' that ends it; an input whose last byte is none gets a VIRTUAL newline at q = mis + size,
+ * so the unterminated last line is a line like every other.  A BLOCK is 2048 positions = 64 bitmap words = one wave, one word per lane.
+ *
+ *   pfac_lines_bitmap      one streaming pass over the input, a wave per block, 16-byte loads (two per lane; the granules that are not whole
+ *                          inside the buffer -- at most two of a launch -- byte by byte with bounds).  16 bytes become 16 bits by a SWAR compare;
+ *                          two shuffles hand every lane the 32 bits of its word.  Writes the newline bitmap, a zero word of the line-hit
+ *                          bitmap, the number of newlines of the block in front of each word (ushort) and the block's count
+ *   pfac_lines_block_scan  the exclusive prefix of the block counts (the line number at each block's start) and, with it, the running maximum
+ *                          of the blocks' last newline, a block of 1024 threads per 8192 counts that sums what lies in front of them itself; the
+ *                          total goes to mapped host memory
+ *   [the compacted scan, its pairs left unordered in the caller's arrays: scan_module.hip]
+ *   pfac_lines_mark        a thread per pair: line = block base + rank of the word + set bits below the position; atomicOr into the hit bitmap
+ *   pfac_lines_select<0>   a wave per block: the lines that end in a word are consecutive, so their hit bits are one 64-bit funnel; counts
+ *                          the selected ones (hit ^ invert) per block and notes the block's last newline
+ *   pfac_lines_block_scan  ... the first selected line of each block, the last newline in front of each block
+ *   pfac_lines_select<1>   the same walk again, writing (start, len, index) in order over the scan's pair list
+ *   pfac_lines_done        the call's sequence number to mapped host memory
+ * Only the first pass and the scan touch O(size) bytes; the rest reads size / 8 bytes of bitmaps and the pairs.
+ * SCRATCH of a select call, B = (mis + size) / 2048 + 1 blocks: 256 B (newline bitmap) + 256 B + 256 once (hit bitmap and the word a funnel may
+ * read behind it) + 128 B (ranks) + 2 x (4 (B + 1) + 4 (B + 1) + 4 B) bytes (lines, selected lines and last newline per block, and their scans), each part
+ * rounded up to 256 bytes: 0.32 bytes per input byte, whatever the data.
+ *
+ * The gather: pfac_lines_gather_count / pfac_lines_scan64 / pfac_lines_gather_offsets give every line its 64-bit offset in the text (len + 1
+ * per line, (start, len) clamped to the input), pfac_lines_gather_copy cuts the TEXT, not the list, into tiles of 4 KiB: a tile finds its
+ * first line by binary search in the offsets, stages the offsets of its lines (at most 4096) in LDS, and every thread assembles 16 output
+ * bytes -- one 3 MiB line and a million 20-byte lines are the same work per byte.  Tiles are aligned on the output address, a tile stops at
+ * outCapacity.  SCRATCH of a gather: 8 (numSelected + 1) bytes of offsets + 8 bytes per 256 .. 2048 lines of block sums.
+ * Plain C++ and vector stores only.
+ */
+#if !defined(__gfx950__) && defined(__HIP_DEVICE_COMPILE__)
+#error "scan_lines.hip is written for gfx950 (CDNA4): wave64"
+#endif
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "pfac_context.h"
+#include "scan_common.h"
+
+namespace {
+
+constexpr unsigned int kLinesThreads = 256;                /* four waves, a block of positions each */
+constexpr unsigned int kBlockShift = 11;                   /* 2048 positions per block ... */
+constexpr unsigned int kBlockWords = 64;                   /* ... = 64 bitmap words, one per lane */
+constexpr unsigned int kScanPer = 8;                       /* entries per thread and step of pfac_lines_block_scan */
+constexpr unsigned int kTile = 4096;                       /* output bytes per tile of the gather */
+
+struct LinesArgs {
+    const unsigned char *in;            /* the caller's bytes */
+    size_t n;
+    unsigned int mis;                   /* address of in & 15: q = p + mis */
+    unsigned int blocks;
+    uint32_t *nlBits;                   /* [blocks * 64] bit q: a line ends at q */
+    uint32_t *hitBits;                  /* [blocks * 64 + 64] bit k: line k holds a match */
+    uint16_t *rank;                     /* [blocks * 64] newlines of the block in front of the word */
+    unsigned int *lineCount, *lineBase; /* [blocks] newlines per block; [blocks + 1] lines in front of the block, [blocks] = the number of lines */
+    unsigned int *selCount, *selBase;   /* the same for the selected lines */
+    unsigned int *lastNl, *prevNl;      /* [blocks] q + 1 of the block's last newline (0: none; q itself may pass 2^31); of the last newline in front of the block */
+    uint32_t invert;                    /* 0 or 0xFFFFFFFF */
+    int *lineStart, *lineLen, *lineIndex;
+};
+
+/* bits 7, 15, 23, 31 of m -- one per byte -- as a nibble, byte 0 in bit 0: the four products land on bits 21..24 and nothing carries */
+__device__ __forceinline__ uint32_t nibbleOf(uint32_t m) { return (((m >> 7) * 0x00204081u) >> 21) & 0xFu; }
+
+/* bit i: byte i of x is '\n' (exact: the carry of a byte's low seven bits never leaves it) */
+__device__ __forceinline__ uint32_t newlines4(uint32_t x)
+{
+    const uint32_t t = x ^ 0x0A0A0A0Au;
+    return nibbleOf(~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u);
+}
+
+/* the 16 bits of granule g (positions q in [16 g, 16 g + 16)) */
+__device__ __forceinline__ uint32_t granuleBits(const LinesArgs &a, size_t g)
+{
+    const long long p0 = (long long)(g * 16) - (long long)a.mis;
+    if (p0 >= 0 && (size_t)p0 + 16 <= a.n) {
+        const pfacmod::u32x4 v = *reinterpret_cast<const pfacmod::u32x4 *>(a.in + p0);
+        return newlines4(v.x) | newlines4(v.y) << 4 | newlines4(v.z) << 8 | newlines4(v.w) << 12;
+    }
+    uint32_t bits = 0;
+    for (int i = 0; i < 16; i++) {
+        const long long p = p0 + i;
+        if (p >= 0 && (size_t)p < a.n) bits |= (a.in[p] == '\n' ? 1u : 0u) << i;
+        else if ((size_t)p == a.n && p > 0) bits |= (a.in[p - 1] != '\n' ? 1u : 0u) << i;      /* the virtual newline of an unterminated last line */
+    }
+    return bits;
+}
+
+__device__ __forceinline__ unsigned int waveMax(unsigned int v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned int o = __shfl_xor(v, d);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(kLinesThreads) void pfac_lines_bitmap(LinesArgs a)
+{
+    const unsigned int lane = threadIdx.x & 63u;
+    const unsigned int waves = gridDim.x * (kLinesThreads / 64);
+    for (unsigned int b = blockIdx.x * (kLinesThreads / 64) + (threadIdx.x >> 6); b < a.blocks; b += waves) {
+        const size_t g = (size_t)b * 128 + lane;
+        const uint32_t lo = granuleBits(a, g), hi = granuleBits(a, g + 64);
+        /* word w of the block = granules 2 w and 2 w + 1: the low halves of lanes 2 w, 2 w + 1 (w < 32), else the high halves of lanes 2 w - 64 ... */
+        const uint32_t both = lo | hi << 16;
+        const int src = (int)((2u * lane) & 63u);
+        const uint32_t x0 = (uint32_t)__shfl((int)both, src), x1 = (uint32_t)__shfl((int)both, src + 1);
+        const uint32_t word = lane < 32u ? (x0 & 0xFFFFu) | (x1 << 16) : (x0 >> 16) | (x1 & 0xFFFF0000u);
+        const uint32_t c = (uint32_t)__popc(word);
+        const uint32_t incl = waveInclusiveScan(c);
+        const size_t w = (size_t)b * kBlockWords + lane;
+        a.nlBits[w] = word;
+        a.hitBits[w] = 0;
+        a.rank[w] = (uint16_t)(incl - c);
+        if (lane == 63u) a.lineCount[b] = incl;
+    }
+}
+
+/* out[0, n) = the exclusive prefix sum of v[0, n), out[n] = the total (also to *hostTotal when given); m (or null): mOut[i] = the maximum of m[0, i)
+ * and 0.  A block of 1024 threads per 8192 entries; block k sums (and takes the maximum of) everything in front of its entries itself -- coalesced,
+ * from L2, at most 4 n bytes -- so there is no pass between blocks and no chain of 8192-entry steps (one block walking 512 Ki counts of a
+ * 1 GiB input took longer than the newline pass).  v and out are different arrays: the blocks read each other's input */
+__global__ __launch_bounds__(1024) void pfac_lines_block_scan(const unsigned int *v, unsigned int *out, const unsigned int *m, unsigned int *mOut, unsigned int n,
+                                                               unsigned int *hostTotal)
+{
+    __shared__ unsigned int waveSum[16];
+    __shared__ unsigned int waveTop[16];
+    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned int base = blockIdx.x * 1024u * kScanPer;
+    unsigned int front = 0, frontTop = 0;
+    for (unsigned int q = threadIdx.x; q < base / 4u; q += 1024u) {                 /* base is a multiple of 8192 */
+        const pfacmod::u32x4 c = reinterpret_cast<const pfacmod::u32x4 *>(v)[q];
+        front += c.x + c.y + c.z + c.w;
+        if (m != nullptr) {
+            const pfacmod::u32x4 t = reinterpret_cast<const pfacmod::u32x4 *>(m)[q];
+            const unsigned int t0 = t.x > t.y ? t.x : t.y, t1 = t.z > t.w ? t.z : t.w, t2 = t0 > t1 ? t0 : t1;
+            frontTop = t2 > frontTop ? t2 : frontTop;
+        }
+    }
+    const unsigned int i0 = base + threadIdx.x * kScanPer;
+    unsigned int x[kScanPer], own = 0;
+    unsigned int t[kScanPer], ownTop = 0;
+#pragma unroll
+    for (unsigned int k = 0; k < kScanPer; k++) {
+        x[k] = i0 + k < n ? v[i0 + k] : 0u;
+        t[k] = (m != nullptr && i0 + k < n) ? m[i0 + k] : 0u;
+        own += x[k];
+        ownTop = t[k] > ownTop ? t[k] : ownTop;
+    }
+    /* the fronts of all threads are one more addend in front of thread 0's entries: scan (front + own), give back own */
+    unsigned int incl = own, inclTop = ownTop, frontAll = front, frontTopAll = frontTop;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned int up = __shfl_up(incl, d);
+        const unsigned int upTop = __shfl_up(inclTop, d);
+        if ((int)lane >= d) { incl += up; inclTop = upTop > inclTop ? upTop : inclTop; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        frontAll += __shfl_xor(frontAll, d);
+        const unsigned int o = __shfl_xor(frontTopAll, d);
+        frontTopAll = o > frontTopAll ? o : frontTopAll;
+    }
+    unsigned int exclTop = __shfl_up(inclTop, 1);
+    if (lane == 0) exclTop = 0;
+    __shared__ unsigned int waveFront[16];
+    __shared__ unsigned int waveFrontTop[16];
+    if (lane == 63) { waveSum[wave] = incl; waveTop[wave] = inclTop; waveFront[wave] = frontAll; waveFrontTop[wave] = frontTopAll; }
+    __syncthreads();
+    unsigned int before = 0, beforeTop = 0;
+    for (unsigned int w = 0; w < 16; w++) {
+        before += waveFront[w];
+        beforeTop = waveFrontTop[w] > beforeTop ? waveFrontTop[w] : beforeTop;
+        if (w < wave) {
+            before += waveSum[w];
+            beforeTop = waveTop[w] > beforeTop ? waveTop[w] : beforeTop;
+        }
+    }
+    unsigned int run = before + incl - own;
+    unsigned int runTop = exclTop > beforeTop ? exclTop : beforeTop;
+#pragma unroll
+    for (unsigned int k = 0; k < kScanPer; k++) {
+        if (i0 + k < n) {
+            out[i0 + k] = run;
+            if (m != nullptr) mOut[i0 + k] = runTop;
+        }
+        run += x[k];
+        runTop = t[k] > runTop ? t[k] : runTop;
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 1023) {          /* the last thread of the last block has seen everything */
+        out[n] = run;
+        if (hostTotal != nullptr) {
+            __hip_atomic_store(hostTotal, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __threadfence_system();
+        }
+    }
+}
+
+/* a thread per pair of the scan's list: the line that holds the position */
+__global__ __launch_bounds__(kLinesThreads) void pfac_lines_mark(LinesArgs a, const int *pos, unsigned int count)
+{
+    for (unsigned int i = blockIdx.x * kLinesThreads + threadIdx.x; i < count; i += gridDim.x * kLinesThreads) {
+        const int p = pos[i];
+        if (p < 0 || (size_t)p >= a.n) continue;
+        const size_t q = (size_t)p + a.mis;
+        const size_t w = q >> 5;
+        const unsigned int line = a.lineBase[q >> kBlockShift] + a.rank[w] + (unsigned int)__popc(a.nlBits[w] & ((1u << (q & 31u)) - 1u));
+        const uint32_t bit = 1u << (line & 31u);
+        uint32_t *word = &a.hitBits[line >> 5];                /* line <= p: inside the bitmap whatever the pair says */
+        if ((__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) == 0) atomicOr(word, bit);
+    }
+}
+
+/* WRITE == 0: the selected lines that end in each block, and the block's last newline; WRITE == 1: their (start, len, index) */
+template <int WRITE>
+__global__ __launch_bounds__(kLinesThreads) void pfac_lines_select(LinesArgs a)
+{
+    const unsigned int lane = threadIdx.x & 63u;
+    const unsigned int waves = gridDim.x * (kLinesThreads / 64);
+    for (unsigned int b = blockIdx.x * (kLinesThreads / 64) + (threadIdx.x >> 6); b < a.blocks; b += waves) {
+        const size_t w = (size_t)b * kBlockWords + lane;
+        uint32_t word = a.nlBits[w];
+        const uint32_t c = (uint32_t)__popc(word);
+        const unsigned int first = a.lineBase[b] + a.rank[w];           /* the lines that end in this word: [first, first + c) */
+        const uint32_t h0 = a.hitBits[first >> 5], h1 = a.hitBits[(first >> 5) + 1];
+        const uint32_t hits = (uint32_t)((((uint64_t)h1 << 32) | h0) >> (first & 31u));
+        const uint32_t sel = (hits ^ a.invert) & (c >= 32u ? 0xFFFFFFFFu : (1u << c) - 1u);
+        const uint32_t ns = (uint32_t)__popc(sel);
+        const uint32_t incl = waveInclusiveScan(ns);
+        const unsigned int qWord = (b << kBlockShift) + lane * 32u;
+        const unsigned int last = word ? qWord + 32u - (unsigned int)__clz((int)word) : 0u;            /* q + 1 */
+        if constexpr (WRITE == 0) {
+            const unsigned int top = waveMax(last);
+            if (lane == 63u) { a.selCount[b] = incl; a.lastNl[b] = top; }
+        } else {
+            unsigned int inclTop = last;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const unsigned int up = __shfl_up(inclTop, d);
+                if ((int)lane >= d) inclTop = up > inclTop ? up : inclTop;
+            }
+            unsigned int prev = __shfl_up(inclTop, 1);                 /* q + 1 of the last newline in front of this word: where its first line starts */
+            if (lane == 0) prev = 0;
+            const unsigned int carried = a.prevNl[b];
+            prev = carried > prev ? carried : prev;
+            size_t o = (size_t)a.selBase[b] + (incl - ns);
+            for (unsigned int j = 0; word; j++) {
+                const unsigned int q = qWord + (unsigned int)__ffs((int)word) - 1u;
+                word &= word - 1u;
+                if ((sel >> j) & 1u) {
+                    const unsigned int startQ = prev > a.mis ? prev : a.mis;
+                    a.lineStart[o] = (int)(startQ - a.mis);
+                    a.lineLen[o] = (int)(q - startQ);
+                    if (a.lineIndex != nullptr) a.lineIndex[o] = (int)(first + j);
+                    o++;
+                }
+                prev = q + 1u;
+            }
+        }
+    }
+}
+
+/* queued behind the last launch of a call: tells the host, which polls the word, that the call's launches are through */
+__global__ void pfac_lines_done(unsigned int *hostDone, unsigned int seq)
+{
+    __hip_atomic_store(hostDone, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+/* ------------------------------------------------------------------ the gather */
+
+struct GatherArgs {
+    const unsigned char *in;
+    size_t n;
+    const int *start, *len;             /* the caller's lines: clamped, never trusted */
+    size_t count;
+    size_t per;                         /* lines per block of the count / offsets passes: a multiple of kLinesThreads */
+    unsigned int blocks;
+    unsigned long long *blockBase;      /* [blocks + 1] block totals -> their exclusive prefix; [blocks] = the size of the text */
+    unsigned long long *off;            /* [count] offset of each line in the text */
+    unsigned char *out;
+    size_t outCapacity;
+    unsigned int misOut;                /* address of out & 15 */
+};
+
+__device__ __forceinline__ size_t clampedStart(const GatherArgs &g, size_t i)
+{
+    const int s = g.start[i];
+    return s < 0 ? 0 : ((size_t)s > g.n ? g.n : (size_t)s);
+}
+__device__ __forceinline__ size_t clampedLen(const GatherArgs &g, size_t i, size_t s)
+{
+    const int l = g.len[i];
+    return l < 0 ? 0 : ((size_t)l > g.n - s ? g.n - s : (size_t)l);
+}
+
+/* exclusive prefix of `own` over the block's 256 threads, and the block's total (every thread gets it) */
+__device__ __forceinline__ unsigned long long blockExclusive64(unsigned long long own, unsigned long long *waveSum, unsigned long long &total)
+{
+    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned long long incl = own;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long up = __shfl_up(incl, d);
+        if ((int)lane >= d) incl += up;
+    }
+    __syncthreads();                                    /* waveSum may still be read from the previous step */
+    if (lane == 63) waveSum[wave] = incl;
+    __syncthreads();
+    unsigned long long before = 0;
+    total = 0;
+    for (unsigned int w = 0; w < kLinesThreads / 64; w++) {
+        if (w < wave) before += waveSum[w];
+        total += waveSum[w];
+    }
+    return before + incl - own;
+}
+
+__global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_count(GatherArgs g)
+{
+    __shared__ unsigned long long waveSum[kLinesThreads / 64];
+    const size_t first = (size_t)blockIdx.x * g.per;
+    const size_t end = g.count - first < g.per ? g.count : first + g.per;
+    unsigned long long own = 0;
+    for (size_t i = first + threadIdx.x; i < end; i += kLinesThreads) own += clampedLen(g, i, clampedStart(g, i)) + 1;
+    unsigned long long total = 0;
+    (void)blockExclusive64(own, waveSum, total);
+    if (threadIdx.x == 0) g.blockBase[blockIdx.x] = total;
+}
+
+/* exclusive prefix sum of v[0, n) in place, v[n] = the total (also to *hostTotal when given): one block of 1024 threads */
+__global__ __launch_bounds__(1024) void pfac_lines_scan64(unsigned long long *v, unsigned int n, unsigned long long *hostTotal)
+{
+    __shared__ unsigned long long waveSum[16];
+    __shared__ unsigned long long carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (unsigned int base = 0; base < n; base += 1024) {
+        const unsigned int i = base + threadIdx.x;
+        const unsigned long long x = i < n ? v[i] : 0ull;
+        unsigned long long incl = x;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long up = __shfl_up(incl, d);
+            if ((int)lane >= d) incl += up;
+        }
+        if (lane == 63) waveSum[wave] = incl;
+        __syncthreads();
+        unsigned long long before = carry;
+        for (unsigned int w = 0; w < wave; w++) before += waveSum[w];
+        if (i < n) v[i] = before + incl - x;
+        __syncthreads();
+        if (threadIdx.x == 1023) carry = before + incl;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        v[n] = carry;
+        if (hostTotal != nullptr) {
+            __hip_atomic_store(hostTotal, carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __threadfence_system();
+        }
+    }
+}
+
+__global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_offsets(GatherArgs g)
+{
+    __shared__ unsigned long long waveSum[kLinesThreads / 64];
+    const size_t first = (size_t)blockIdx.x * g.per;
+    const size_t end = g.count - first < g.per ? g.count : first + g.per;
+    unsigned long long base = g.blockBase[blockIdx.x];
+    for (size_t i0 = first; i0 < end; i0 += kLinesThreads) {        /* the same trip count for every thread of the block */
+        const size_t i = i0 + threadIdx.x;
+        const bool has = i < end;
+        const unsigned long long c = has ? clampedLen(g, i, clampedStart(g, i)) + 1 : 0ull;
+        unsigned long long stepTotal = 0;
+        const unsigned long long o = base + blockExclusive64(c, waveSum, stepTotal);
+        base += stepTotal;
+        if (has) g.off[i] = o;
+    }
+}
+
+/* the text, a tile of kTile output bytes at a time.  Tiles are cut in v = o + misOut, the output offset counted from the aligned 16-byte block that
+ * holds out[0]: a thread's 16 bytes are one aligned store unless they hang over an end of the text */
+__global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_copy(GatherArgs g)
+{
+    __shared__ unsigned int rel[kTile + 1];              /* offsets of the tile's lines behind its first, relative to the tile's first byte */
+    __shared__ size_t sFirst;
+    __shared__ unsigned int sCount;
+    const unsigned long long total = g.blockBase[g.blocks];
+    const unsigned long long limit = total < g.outCapacity ? total : g.outCapacity;
+    const unsigned int t = threadIdx.x;
+    for (unsigned long long vLo = (unsigned long long)blockIdx.x * kTile; vLo < limit + g.misOut; vLo += (unsigned long long)gridDim.x * kTile) {
+        const unsigned long long oLo = vLo > g.misOut ? vLo - g.misOut : 0ull;
+        const unsigned long long oEnd = vLo + kTile - g.misOut;
+        const unsigned long long oHi = oEnd < limit ? oEnd : limit;
+        if (t == 0) {
+            /* the last line that starts at or in front of oLo (off[0] == 0), and the last that starts in front of oHi */
+            size_t lo = 0, hi = g.count;
+            while (hi - lo > 1) {
+                const size_t mid = lo + (hi - lo) / 2;
+                if (g.off[mid] <= oLo) lo = mid; else hi = mid;
+            }
+            size_t lo2 = lo, hi2 = g.count;
+            while (hi2 - lo2 > 1) {
+                const size_t mid = lo2 + (hi2 - lo2) / 2;
+                if (g.off[mid] < oHi) lo2 = mid; else hi2 = mid;
+            }
+            sFirst = lo;
+            const size_t c = lo2 - lo + 1;              /* offsets are strictly ascending: at most kTile lines start inside a tile */
+            sCount = c > kTile ? kTile : (unsigned int)c;
+        }
+        __syncthreads();
+        const size_t first = sFirst;
+        const unsigned int cnt = sCount;
+        for (unsigned int j = t; j < cnt; j += kLinesThreads) rel[j] = j == 0 ? 0u : (unsigned int)(g.off[first + j] - oLo);
+        __syncthreads();
+        const unsigned long long v0 = vLo + (unsigned long long)t * 16;
+        const unsigned long long cLo = v0 > g.misOut ? v0 - g.misOut : 0ull;
+        unsigned long long cHi = v0 + 16 > g.misOut ? v0 + 16 - g.misOut : 0ull;
+        cHi = cHi < oHi ? cHi : oHi;
+        if (cLo < cHi) {
+            const unsigned int r = (unsigned int)(cLo - oLo);
+            unsigned int lo = 0, hi = cnt;
+            while (hi - lo > 1) {
+                const unsigned int mid = (lo + hi) / 2;
+                if (rel[mid] <= r) lo = mid; else hi = mid;
+            }
+            size_t i = first + lo;
+            unsigned long long k = lo == 0 ? cLo - g.off[first] : (unsigned long long)(r - rel[lo]);     /* bytes of line i in front of cLo */
+            size_t s = clampedStart(g, i), l = clampedLen(g, i, s);
+            auto next = [&]() -> uint32_t {
+                uint32_t byte = '\n';
+                if (k < l) {
+                    byte = g.in[s + k];
+                    k++;
+                } else {                                 /* the line's newline: on to the next line */
+                    k = 0;
+                    i++;
+                    if (i < g.count) { s = clampedStart(g, i); l = clampedLen(g, i, s); } else { s = 0; l = 0; }
+                }
+                return byte;
+            };
+            if (cHi - cLo == 16 && v0 >= g.misOut) {
+                uint32_t x[4];
+#pragma unroll
+                for (int d = 0; d < 4; d++) {
+                    uint32_t y = next();
+                    y |= next() << 8;
+                    y |= next() << 16;
+                    y |= next() << 24;
+                    x[d] = y;
+                }
+                *reinterpret_cast<pfacmod::u32x4 *>(g.out + cLo) = pfacmod::u32x4{x[0], x[1], x[2], x[3]};
+            } else {
+                for (unsigned long long o = cLo; o < cHi; o++) g.out[o] = (unsigned char)next();
+            }
+        }
+        __syncthreads();                                 /* rel is rewritten by the next tile */
+    }
+}
+
+unsigned int gridCap(const PFAC_context *c) { return (unsigned int)(c->multiProcessorCount > 0 ? c->multiProcessorCount : 256) * 8u; }
+
+size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
+
+/* grow-only scratch of the lines calls (exactly what a call needs: a fixed function of its size) */
+char *linesScratch(PFAC_context *c, size_t bytes)
+{
+    if (c->scratch.lines.count() < bytes && c->scratch.lines.reserve(bytes) != PFAC_STATUS_SUCCESS) return nullptr;
+    return c->scratch.lines.get();
+}
+
+unsigned int nextSeq(PFAC_context *c)
+{
+    c->linesSeq = c->linesSeq + 1u ? c->linesSeq + 1u : 1u;
+    return c->linesSeq;
+}
+
+} // namespace
+
+extern "C" {
+
+PFAC_status_t PFACX_linesSelect(PFAC_handle_t handle, const char *d_input, char *d_scan, size_t size, int invert, int hashed, int *d_lineStart,
+                                int *d_lineLen, int *d_lineIndex, size_t *h_numLines, size_t *h_numSelected)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!d_input || !d_scan || !d_lineStart || !d_lineLen || !h_numLines || !h_numSelected || size == 0 || size > (size_t)0x7fffffff)
+        return PFAC_STATUS_INVALID_PARAMETER;
+    PFAC_context *c = handle;
+    LinesArgs a{};
+    a.in = reinterpret_cast<const unsigned char *>(d_input);
+    a.n = size;
+    a.mis = (unsigned int)(reinterpret_cast<uintptr_t>(d_input) & 15u);
+    const size_t blocks = ((size_t)a.mis + size) / (size_t(1) << kBlockShift) + 1;      /* positions q in [0, mis + size] */
+    a.blocks = (unsigned int)blocks;
+    const size_t words = blocks * kBlockWords;
+    const size_t oNl = 0, oHit = oNl + round256(words * 4), oRank = oHit + round256(words * 4 + 256), oLine = oRank + round256(words * 2),
+                 oSel = oLine + 2 * round256((blocks + 1) * 4), oPrev = oSel + 2 * round256((blocks + 1) * 4), bytes = oPrev + 2 * round256(blocks * 4);
+    char *s = linesScratch(c, bytes);
+    if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
+    a.nlBits = reinterpret_cast<uint32_t *>(s + oNl);
+    a.hitBits = reinterpret_cast<uint32_t *>(s + oHit);
+    a.rank = reinterpret_cast<uint16_t *>(s + oRank);
+    a.lineBase = reinterpret_cast<unsigned int *>(s + oLine);
+    a.lineCount = reinterpret_cast<unsigned int *>(s + oLine + round256((blocks + 1) * 4));
+    a.selBase = reinterpret_cast<unsigned int *>(s + oSel);
+    a.selCount = reinterpret_cast<unsigned int *>(s + oSel + round256((blocks + 1) * 4));
+    a.prevNl = reinterpret_cast<unsigned int *>(s + oPrev);
+    a.lastNl = reinterpret_cast<unsigned int *>(s + oPrev + round256(blocks * 4));
+    a.invert = invert ? 0xFFFFFFFFu : 0u;
+    a.lineStart = d_lineStart;
+    a.lineLen = d_lineLen;
+    a.lineIndex = d_lineIndex;
+    const bool mapped = c->h_modeHint != nullptr && c->d_modeHint != nullptr;
+    unsigned int *hostWords = mapped ? c->d_modeHint + pfac::kHostLinesWord : nullptr;
+    const unsigned int waveGrid = (unsigned int)((blocks + 3) / 4 < gridCap(c) ? (blocks + 3) / 4 : gridCap(c));
+
+    /* the line index in front of the scan, on the same stream */
+    hipLaunchKernelGGL(pfac_lines_bitmap, dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
+    const unsigned int scanGrid = (a.blocks + 1024u * kScanPer - 1u) / (1024u * kScanPer);
+    hipLaunchKernelGGL(pfac_lines_block_scan, dim3(scanGrid), dim3(1024), 0, 0, (const unsigned int *)a.lineCount, a.lineBase, (const unsigned int *)nullptr,
+                       (unsigned int *)nullptr, a.blocks, hostWords);
+    if (hipGetLastError() != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+
+    /* the compacted scan, pairs in any order (the four ordering launches are not paid for): ids in d_lineStart, positions in d_lineLen */
+    int count = 0;
+    const bool wasUnordered = c->reduceUnordered;
+    c->reduceUnordered = true;
+    const PFAC_status_t st = hashed ? PFAC_reduce_inplace_kernel(handle, reinterpret_cast<int *>(d_scan), (int)size, d_lineStart, d_lineLen, &count, nullptr, nullptr)
+                                    : PFAC_reduce_kernel(handle, reinterpret_cast<int *>(d_scan), (int)size, d_lineStart, d_lineLen, &count, nullptr, nullptr);
+    c->reduceUnordered = wasUnordered;
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
+
+    if (count > 0) hipLaunchKernelGGL(pfac_lines_mark, dim3(gridFor(c, (size_t)count)), dim3(kLinesThreads), 0, 0, a, (const int *)d_lineLen, (unsigned int)count);
+    hipLaunchKernelGGL(pfac_lines_select<0>, dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
+    hipLaunchKernelGGL(pfac_lines_block_scan, dim3(scanGrid), dim3(1024), 0, 0, (const unsigned int *)a.selCount, a.selBase, (const unsigned int *)a.lastNl, a.prevNl,
+                       a.blocks, mapped ? hostWords + 1 : (unsigned int *)nullptr);
+    hipLaunchKernelGGL(pfac_lines_select<1>, dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
+    unsigned int numLines = 0, numSelected = 0;
+    if (mapped) {
+        const unsigned int seq = nextSeq(c);
+        hipLaunchKernelGGL(pfac_lines_done, dim3(1), dim3(1), 0, 0, hostWords + 2, seq);
+        if (hipGetLastError() != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+        volatile unsigned int *host = c->h_modeHint + pfac::kHostLinesWord;
+        const HostWait w = waitHostSeq(host + 2, seq);
+        if (w == HostWait::SyncFailed || (w == HostWait::Synced && __atomic_load_n(const_cast<unsigned int *>(host + 2), __ATOMIC_ACQUIRE) != seq))
+            return PFAC_STATUS_INTERNAL_ERROR;
+        numLines = host[0];
+        numSelected = host[1];
+    } else if (hipGetLastError() != hipSuccess || hipMemcpy(&numLines, a.lineBase + blocks, sizeof(numLines), hipMemcpyDeviceToHost) != hipSuccess ||
+               hipMemcpy(&numSelected, a.selBase + blocks, sizeof(numSelected), hipMemcpyDeviceToHost) != hipSuccess) {
+        return PFAC_STATUS_INTERNAL_ERROR;
+    }
+    if (numLines > size || numSelected > numLines) return PFAC_STATUS_INTERNAL_ERROR;
+    *h_numLines = numLines;
+    *h_numSelected = numSelected;
+    return PFAC_STATUS_SUCCESS;
+}
+
+/* measurement only: the newline pass alone over the first n bytes of d_in, into the handle's lines scratch */
+double PFACX_linesBitmapProbe(PFAC_handle_t handle, const void *d_in, size_t n, int launches)
+{
+    if (!handle || !d_in || n == 0 || n > (size_t)0x7fffffff || launches < 1) return -1.0;
+    PFAC_context *c = handle;
+    LinesArgs a{};
+    a.in = static_cast<const unsigned char *>(d_in);
+    a.n = n;
+    a.mis = (unsigned int)(reinterpret_cast<uintptr_t>(d_in) & 15u);
+    const size_t blocks = ((size_t)a.mis + n) / (size_t(1) << kBlockShift) + 1, words = blocks * kBlockWords;
+    const size_t oHit = round256(words * 4), oRank = oHit + round256(words * 4 + 256), oLine = oRank + round256(words * 2);
+    char *s = linesScratch(c, oLine + round256(blocks * 4));
+    if (!s) return -1.0;
+    a.blocks = (unsigned int)blocks;
+    a.nlBits = reinterpret_cast<uint32_t *>(s);
+    a.hitBits = reinterpret_cast<uint32_t *>(s + oHit);
+    a.rank = reinterpret_cast<uint16_t *>(s + oRank);
+    a.lineCount = reinterpret_cast<unsigned int *>(s + oLine);
+    const unsigned int grid = (unsigned int)((blocks + 3) / 4 < gridCap(c) ? (blocks + 3) / 4 : gridCap(c));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    double ms = -1.0;
+    if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
+        for (int r = 0; r < 3; r++) hipLaunchKernelGGL(pfac_lines_bitmap, dim3(grid), dim3(kLinesThreads), 0, 0, a);
+        (void)hipEventRecord(e0, 0);
+        for (int r = 0; r < launches; r++) hipLaunchKernelGGL(pfac_lines_bitmap, dim3(grid), dim3(kLinesThreads), 0, 0, a);
+        (void)hipEventRecord(e1, 0);
+        float t = 0;
+        if (hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&t, e0, e1) == hipSuccess && hipGetLastError() == hipSuccess) ms = (double)t / launches;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return ms;
+}
+
+PFAC_status_t PFACX_linesGather(PFAC_handle_t handle, const char *d_input, size_t size, const int *d_lineStart, const int *d_lineLen,
+                                size_t numSelected, char *d_out, size_t outCapacity, size_t *h_outBytes)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!h_outBytes || !d_lineStart || !d_lineLen || numSelected == 0 || (!d_input && size) || (!d_out && outCapacity) || size > (size_t)0x7fffffff ||
+        numSelected > (size_t)0x7fffffff)
+        return PFAC_STATUS_INVALID_PARAMETER;
+    PFAC_context *c = handle;
+    GatherArgs g{};
+    g.in = reinterpret_cast<const unsigned char *>(d_input);
+    g.n = size;
+    g.start = d_lineStart;
+    g.len = d_lineLen;
+    g.count = numSelected;
+    g.out = reinterpret_cast<unsigned char *>(d_out);
+    g.outCapacity = outCapacity;
+    g.misOut = (unsigned int)(reinterpret_cast<uintptr_t>(d_out) & 15u);
+    size_t blocks = (numSelected + kLinesThreads - 1) / kLinesThreads;
+    if (blocks > gridCap(c)) blocks = gridCap(c);
+    g.per = ((numSelected + blocks - 1) / blocks + kLinesThreads - 1) / kLinesThreads * kLinesThreads;
+    blocks = (numSelected + g.per - 1) / g.per;
+    g.blocks = (unsigned int)blocks;
+    const size_t baseBytes = round256((blocks + 1) * sizeof(unsigned long long));
+    char *s = linesScratch(c, baseBytes + round256(numSelected * sizeof(unsigned long long)));
+    if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
+    g.blockBase = reinterpret_cast<unsigned long long *>(s);
+    g.off = reinterpret_cast<unsigned long long *>(s + baseBytes);
+    const bool mapped = c->h_modeHint != nullptr && c->d_modeHint != nullptr;
+    unsigned int *hostWords = mapped ? c->d_modeHint + pfac::kHostGatherWord : nullptr;
+    hipLaunchKernelGGL(pfac_lines_gather_count, dim3(g.blocks), dim3(kLinesThreads), 0, 0, g);
+    hipLaunchKernelGGL(pfac_lines_scan64, dim3(1), dim3(1024), 0, 0, g.blockBase, g.blocks, reinterpret_cast<unsigned long long *>(hostWords));
+    hipLaunchKernelGGL(pfac_lines_gather_offsets, dim3(g.blocks), dim3(kLinesThreads), 0, 0, g);
+    /* the text is at most (size + 1) bytes per line; whatever it is, a launch never needs more tiles than outCapacity has */
+    if (outCapacity) {
+        const unsigned long long bound = (unsigned long long)numSelected * (size + 1);
+        const unsigned long long most = (bound < outCapacity ? bound : (unsigned long long)outCapacity) + g.misOut;
+        const unsigned long long tiles = (most + kTile - 1) / kTile;
+        hipLaunchKernelGGL(pfac_lines_gather_copy, dim3((unsigned int)(tiles < gridCap(c) * 4ull ? tiles : gridCap(c) * 4ull)), dim3(kLinesThreads), 0, 0, g);
+    }
+    unsigned long long total = 0;
+    if (mapped) {
+        const unsigned int seq = nextSeq(c);
+        hipLaunchKernelGGL(pfac_lines_done, dim3(1), dim3(1), 0, 0, hostWords + 2, seq);
+        if (hipGetLastError() != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+        volatile unsigned int *host = c->h_modeHint + pfac::kHostGatherWord;
+        const HostWait w = waitHostSeq(host + 2, seq);
+        if (w == HostWait::SyncFailed || (w == HostWait::Synced && __atomic_load_n(const_cast<unsigned int *>(host + 2), __ATOMIC_ACQUIRE) != seq))
+            return PFAC_STATUS_INTERNAL_ERROR;
+        total = __atomic_load_n(reinterpret_cast<unsigned long long *>(c->h_modeHint + pfac::kHostGatherWord), __ATOMIC_ACQUIRE);
+    } else if (hipGetLastError() != hipSuccess || hipMemcpy(&total, g.blockBase + blocks, sizeof(total), hipMemcpyDeviceToHost) != hipSuccess) {
+        return PFAC_STATUS_INTERNAL_ERROR;
+    }
+    *h_outBytes = (size_t)total;
+    return total > outCapacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+}
+
+} /* extern "C" */

@@ -14,7 +14,7 @@
  *               twice: for the scan's count (which sizes the staging list) and for the end of the merge.  The scan uses the
  *               caller's arrays below `size` as its pair list, like every compacted call; the merge writes nothing at or beyond
  *               the total.
- *   host-fed:   a vector per flow; the pieces go one by one through what a host-fed stream's call goes through (the CPU matchers on a
+ *   host-fed:   a vector per flow; the pieces go one by one through what a host-fed stream's call goes through (hostPiece, stream_api.cpp: the CPU matchers on a
  *               CPU platform, the pipelined host path on the GPU platform), into the caller's arrays at the running count, and the
  *               next carries are kept aside until the last piece has succeeded.
  * Every piece and flush call holds the set's own lock and the handle's lock from the check of the pattern set to its end.
@@ -199,49 +199,6 @@ PFAC_status_t runOnDevice(PFACX_flows_s *s, const char *d_input, size_t P, size_
     return c->flows_run_ptr(c, &run, total);
 }
 
-/* one host-fed piece (or, size == 0 and flush: the flow's end) through what a host-fed stream's call goes through; the pairs go to
- * ids / pos (room: size + M - 1), the flow's next carry to `next` */
-PFAC_status_t hostPiece(PFAC_context *c, const Flow &f, char *piece, size_t size, bool flush, int *ids, int *pos, std::vector<int> &scratch,
-                        std::vector<unsigned char> &next, int *count)
-{
-    const size_t M = (size_t)c->fa.maxPatternLen;
-    const bool gpu = c->platform == PFAC_PLATFORM_GPU;
-    const size_t carried = f.carried;
-    StreamSplit sp = streamSplitOf(carried, size, M);
-    if (flush) { sp.seam = carried; sp.owned = 0; }
-    const size_t head = std::min(size, M - 1);
-    int seamPairs = 0, piecePairs = 0;
-    PFAC_status_t st = PFAC_STATUS_SUCCESS;
-    if (sp.seam) {
-        std::vector<unsigned char> seam(carried + head);
-        std::memcpy(seam.data(), f.h_carry.data(), carried);
-        if (head) std::memcpy(seam.data() + carried, piece, head);
-        if (gpu) {
-            st = streamGpuPairs(c, reinterpret_cast<char *>(seam.data()), sp.seam, seam.size(), -(int)carried, ids, pos, &seamPairs);
-        } else {
-            if (scratch.size() < seam.size()) scratch.resize(seam.size());
-            st = streamCpuPairs(c, reinterpret_cast<const char *>(seam.data()), sp.seam, seam.size(), -(int)carried, scratch.data(), ids, pos, &seamPairs);
-        }
-        if (st != PFAC_STATUS_SUCCESS) return st;
-    }
-    if (sp.owned) {
-        if (gpu) {
-            st = streamGpuPairs(c, piece, sp.owned, size, 0, ids + seamPairs, pos + seamPairs, &piecePairs);
-        } else {
-            if (scratch.size() < size) scratch.resize(size);
-            st = streamCpuPairs(c, piece, sp.owned, size, 0, scratch.data(), ids + seamPairs, pos + seamPairs, &piecePairs);
-        }
-        if (st != PFAC_STATUS_SUCCESS) return st;
-    }
-    const size_t nextCarried = flush ? 0 : std::min(M - 1, carried + size);
-    next.resize(nextCarried);
-    const size_t fromPiece = std::min(nextCarried, size);
-    if (nextCarried > fromPiece) std::memcpy(next.data(), f.h_carry.data() + (carried - (nextCarried - fromPiece)), nextCarried - fromPiece);
-    if (fromPiece) std::memcpy(next.data() + (nextCarried - fromPiece), piece + (size - fromPiece), fromPiece);
-    *count = seamPairs + piecePairs;
-    return PFAC_STATUS_SUCCESS;
-}
-
 /* the argument checks both piece calls share (the caller holds both locks) */
 PFAC_status_t checkPieces(PFACX_flows_s *s, const void *input, size_t size, const size_t *h_offsets, const unsigned int *h_flowIds, size_t numPieces,
                           const int *ids, const int *pos, size_t capacity, const int *pieceFirst, const unsigned long long *h_pieceOffsets,
@@ -408,7 +365,8 @@ PFAC_status_t PFACX_flowsMatchFromHost(PFACX_flows_t flows, char *h_input, size_
             h_pieceFirst[k] = at;
             if (!len) continue;
             int n = 0;
-            st = hostPiece(c, flows->flows[h_flowIds[k]], h_input + h_offsets[k], len, false, h_ids + at, h_pos + at, scratch, next[k], &n);
+            const Flow &f = flows->flows[h_flowIds[k]];
+            st = hostPiece(c, f.h_carry.data(), f.carried, h_input + h_offsets[k], len, false, h_ids + at, h_pos + at, scratch, next[k], &n);
             if (st != PFAC_STATUS_SUCCESS) return st;
             at += n;
         }
@@ -475,7 +433,7 @@ PFAC_status_t PFACX_flowsFlush(PFACX_flows_t flows, const unsigned int *h_flowId
                 const Flow &f = flows->flows[h_flowIds[k]];
                 if (!f.carried) continue;
                 int got = 0;
-                st = hostPiece(c, f, nullptr, 0, true, ids + total, pos + total, scratch, none, &got);
+                st = hostPiece(c, f.h_carry.data(), f.carried, nullptr, 0, true, ids + total, pos + total, scratch, none, &got);
                 if (st != PFAC_STATUS_SUCCESS) return st;
                 total += got;
             }

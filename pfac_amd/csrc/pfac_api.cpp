@@ -641,8 +641,8 @@ PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info)
         /* ... and what its calls have left allocated (grow-only, PFACX_trim gives it back) */
         v.deviceScratchBytes = handle->scratch.bytes();
         if (handle->h_modeHint) {
-            v.streamNearMisses = (int)static_cast<volatile const unsigned int *>(handle->h_modeHint)[0];
-            v.streamDense = (int)static_cast<volatile const unsigned int *>(handle->h_modeHint)[1];
+            v.streamNearMisses = (int)static_cast<volatile const unsigned int *>(handle->h_modeHint)[pfac::kHostHintWord];
+            v.streamDense = (int)static_cast<volatile const unsigned int *>(handle->h_modeHint)[pfac::kHostDenseHintWord];
         }
     }
     v.structSize = callerSize < sizeof(v) ? callerSize : sizeof(v);

@@ -49,14 +49,19 @@ constexpr int kModeHintWord = 35 * 32;           /* full-result filter kernel: 1
 constexpr int kModeVotesWord = 36 * 32;
 constexpr int kTiledDenseWord = 37 * 32;         /* tiled kernel scanning a whole big call: groups it walked in dense mode, groups in all, waves that are through (three words);
                                                     the last wave out tells the host whether the stream is pattern-dense (hostHint[1]) and leaves them zero */
-constexpr int kHostPairCountWord = 4;             /* word of the handle's mapped host memory (h_modeHint) the first ordering launch (pfac_order_count) writes the number of pairs of a compacted-output call to */
-constexpr int kHostAllTotalWord = 8;              /* words 8-9 of h_modeHint: the 64-bit length of an all-match call's list (scan_all.hip: pfac_all_block_scan) ... */
-constexpr int kHostAllDoneWord = 10;              /* ... and the sequence number its last launch writes (pfac_all_done) */
-constexpr int kHostSeamCountWord = 12;             /* words 12-13 of h_modeHint: the pairs a stream call's seam launch wrote (scan_stream.hip: pfac_stream_seam) and the sequence number it writes behind them */
-constexpr int kHostFlowsCountWord = 14;            /* words 14-15 of h_modeHint: the pairs of a flows call (scan_flows.hip: pfac_flows_done) and the sequence number written behind them */
-constexpr int kHostLinesWord = 16;                 /* words 16-18 of h_modeHint: the lines and the selected lines of a lines call (scan_lines.hip: pfac_lines_block_scan) and the sequence number written behind them */
-constexpr int kHostGatherWord = 20;                /* words 20-22 of h_modeHint: the 64-bit size of a gather's text (scan_lines.hip: pfac_lines_scan64) and the sequence number written behind it */
-constexpr int kHostWords = 32;                     /* words of the handle's mapped host memory (h_modeHint) */
+/* The handle's mapped host memory (PFAC_context::h_modeHint / d_modeHint): kHostWords words.  Words 0 and 1 are the hints of the product kernels
+ * (ScanArgs::hostHint; PFACX_getScanStats reads them).  Behind them every kind of call that hands its result to the host without a copy has a slot:
+ * `value`, the first word of what its launches write (64-bit values are 8-byte aligned), and `done`, the word that takes the call's sequence
+ * number behind everything else (scan_passes.h: HostHandoff) */
+struct HostSlot { int value, done; };
+constexpr int kHostHintWord = 0, kHostDenseHintWord = 1;
+constexpr HostSlot kHostPairs = {4, 5};           /* a compacted-output call: the number of pairs (scan_order.inc: pfac_order_count) */
+constexpr HostSlot kHostAll = {8, 10};            /* an all-match call: the 64-bit length of its list (scan_all.hip) */
+constexpr HostSlot kHostSeam = {12, 13};          /* a stream call: the pairs of its seam (scan_stream.hip: pfac_stream_seam stores both words) */
+constexpr HostSlot kHostFlows = {14, 15};         /* a flows call: its pairs (scan_flows.hip: pfac_flows_done stores both words) */
+constexpr HostSlot kHostLines = {16, 18};         /* a lines call: the lines, then the selected lines (scan_lines.hip: pfac_lines_block_scan) */
+constexpr HostSlot kHostGather = {20, 22};        /* a gather: the 64-bit size of its text (scan_lines.hip) */
+constexpr int kHostWords = 32;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -438,7 +443,6 @@ struct PFAC_context {
      * the next call with the same layout needs no memset in front of its scan; null = not known to be zero */
     const void *orderCleanBase = nullptr;
     size_t orderCleanBytes = 0;
-    unsigned int orderSeq = 0;                /* number of the last ordered call (pfac_order_done writes it to host memory) */
     unsigned int orderParity = 0;             /* which of the two pairs of call counters the next ordered call uses */
     bool reduceUnordered = false;             /* the compacted-output scan may leave its pairs in any order (set around the calls of PFAC_matchFromHost) */
     /* the copy streams and events of the host calls' staging (scratch.stageIn ...; host_pipeline.cpp), created with the buffers */
@@ -453,6 +457,7 @@ struct PFAC_context {
     /* one word of mapped host memory the last block of a full-result filter launch writes: 1 = the stream was full of near misses
      * (scan_filter.hip: launchChained picks the next launch's walker from it); h_: the host's pointer, d_: the device's */
     unsigned int *h_modeHint = nullptr, *d_modeHint = nullptr;
+    unsigned int hostSeq = 0;                 /* number of the last call that handed its result over through a slot of that memory (pfac::HostSlot); never issued as 0 */
     int walker = PFACX_WALKER_AUTO;
 
     /* ref numOfTableEntry / sizeOfTableEntry / sizeOfTableInBytes, PFAC_P.h:131-133 */
@@ -492,20 +497,16 @@ struct PFAC_context {
     std::shared_mutex tablesInUse;
     /* per-device handles of PFACX_matchFromHostMultiGPU, created on first use: (device, handle) */
     std::vector<std::pair<int, PFAC_context *>> children;
-    unsigned int allSeq = 0;                  /* number of the last expansion (pfac_all_done writes it to host memory) */
 
     /* streams (PFACX_stream*, stream_api.cpp): the open streams of this handle (PFAC_destroy closes them) and the number of the pattern set
      * they were opened on: whatever replaces or drops the set (freeResources) counts it up, and a stream of an older set is refused until
      * PFACX_streamReset.  The carried bytes of device-fed streams are state, not scratch: counted under deviceTableBytes, kept by PFACX_trim */
     std::vector<PFACX_stream_s *> streams;
     unsigned long long setGeneration = 0;
-    unsigned int seamSeq = 0;                 /* number of the last seam launch (pfac_stream_seam writes it to host memory) */
     /* flow sets (PFACX_flows*, flows_api.cpp): the open sets of this handle (PFAC_destroy closes them); their carries are state like the streams' */
     std::vector<PFACX_flows_s *> flowSets;
     void *h_flowPieces = nullptr;             /* pinned host memory a flows call builds its piece descriptors in (grow-only; freed with the scratch) */
     size_t h_flowPiecesBytes = 0;
-    unsigned int flowsSeq = 0;                /* number of the last flows call (pfac_flows_done writes it to host memory) */
-    unsigned int linesSeq = 0;                /* number of the last lines / gather call (pfac_lines_done writes it to host memory) */
 
     bool hasDevice = false;
     int device = -1;

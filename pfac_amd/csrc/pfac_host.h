@@ -78,14 +78,16 @@ inline int compactPairs(const int *results, size_t owned, int posShift, int *ids
 /* stream_api.cpp: PFAC_destroy closes the handle's streams; the device bytes their carries hold (PFACX_getInfo: deviceTableBytes) */
 void closeAllStreams(PFAC_context *c);
 size_t streamDeviceBytes(const PFAC_context *c);
-/* ... and what the stream and the flows calls share: how a piece of `size` bytes splits the work of a stream that carries `carried` bytes
- * (of the pending and the piece's positions the first seam + owned are final, `seam` of them carried), and the longest match at
- * positions [0, owned) of `readable` host bytes as (id, position + posShift) pairs, on the CPU platforms (scratch: `readable` ints) and on
- * the GPU platform (the pipelined host path); the caller holds c->lock */
+/* ... and what the stream and the flows calls share (the caller holds c->lock).  streamSplitOf: how a piece of `size` bytes splits the work of a
+ * stream that carries `carried` bytes -- of the pending and the piece's positions the first seam + owned are final, `seam` of them carried.
+ * hostPiece: one host-fed piece (or, size == 0 and flush: the stream's end) of a stream whose carry is carry[0, carried): the seam
+ * [carry | head of the piece] and the piece's final positions through the CPU matchers on a CPU platform (scratch: grown as needed) and through
+ * the pipelined host path on the GPU platform; the pairs go to ids / pos (room: size + M - 1), their number to *count, the stream's next carry
+ * to `next`.  Nothing of the stream changes: the caller moves it on when its whole call has succeeded */
 struct StreamSplit { size_t seam, owned; };
 StreamSplit streamSplitOf(size_t carried, size_t size, size_t M);
-PFAC_status_t streamCpuPairs(PFAC_context *c, const char *in, size_t owned, size_t readable, int posShift, int *scratch, int *ids, int *pos, int *count);
-PFAC_status_t streamGpuPairs(PFAC_context *c, char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count);
+PFAC_status_t hostPiece(PFAC_context *c, const unsigned char *carry, size_t carried, char *piece, size_t size, bool flush, int *ids, int *pos,
+                        std::vector<int> &scratch, std::vector<unsigned char> &next, int *count);
 /* flows_api.cpp: PFAC_destroy closes the handle's flow sets; the device bytes their carries hold (PFACX_getInfo: deviceTableBytes) */
 void closeAllFlowSets(PFAC_context *c);
 size_t flowsDeviceBytes(const PFAC_context *c);

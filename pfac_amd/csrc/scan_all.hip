@@ -9,11 +9,11 @@
  * ordering writes the ordered pairs into the handle's scratch); behind it, on the default stream:
  *   pfac_all_count       blocks own consecutive ranges of the longest pairs; each lane reads chainLen[id] (a table of 8 bytes
  *                        per id: L2 resident for any real set), the block's total goes to blockBase[block]
- *   pfac_all_block_scan  exclusive scan of the block totals (one block; 64-bit), the grand total to mapped host memory
+ *   pfac_array_scan      exclusive scan of the block totals (one block; 64-bit; scan_passes.h), the grand total to mapped host memory
  *   pfac_all_scatter     the block's range again: lane prefix of the chain lengths, then each lane writes its pair and follows
  *                        prefixPattern into consecutive slots; slots >= capacity are skipped (the caller learns the full count)
  *   pfac_all_seg_first   batch form: one lane per segment boundary, the expanded offset of the first longest pair of the segment
- *   pfac_all_done        writes the call's sequence number to mapped host memory (the host polls it instead of a stream sync)
+ *   pfac_host_done       writes the call's sequence number to mapped host memory (the host polls it instead of a stream sync; scan_passes.h: HostHandoff)
  * Writes are plain vector stores; no kernel of the other units is touched.
  */
 #if !defined(__gfx950__) && defined(__HIP_DEVICE_COMPILE__)
@@ -24,7 +24,7 @@
 #include <cstdint>
 
 #include "pfac_context.h"
-#include "scan_common.h"
+#include "scan_passes.h"
 
 namespace {
 
@@ -53,28 +53,6 @@ __device__ __forceinline__ unsigned int chainOf(const ExpandArgs &x, int id)
     return c > 0 ? (unsigned int)c : 1u;
 }
 
-/* exclusive prefix of `own` over the block's 256 threads, and the block's total (every thread gets it) */
-__device__ __forceinline__ unsigned long long blockExclusive(unsigned long long own, unsigned long long *waveSum, unsigned long long &total)
-{
-    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned long long incl = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long up = __shfl_up(incl, d);
-        if ((int)lane >= d) incl += up;
-    }
-    __syncthreads();                                    /* waveSum may still be read from the previous step */
-    if (lane == 63) waveSum[wave] = incl;
-    __syncthreads();
-    unsigned long long before = 0;
-    total = 0;
-    for (unsigned int w = 0; w < kAllBlock / 64; w++) {
-        if (w < wave) before += waveSum[w];
-        total += waveSum[w];
-    }
-    return before + incl - own;
-}
-
 __global__ __launch_bounds__(kAllBlock) void pfac_all_count(ExpandArgs x)
 {
     __shared__ unsigned long long waveSum[kAllBlock / 64];
@@ -83,44 +61,8 @@ __global__ __launch_bounds__(kAllBlock) void pfac_all_count(ExpandArgs x)
     unsigned long long own = 0;
     for (size_t i = first + threadIdx.x; i < end; i += kAllBlock) own += chainOf(x, x.pairIds[i]);
     unsigned long long total = 0;
-    (void)blockExclusive(own, waveSum, total);
+    (void)blockExclusive<kAllBlock>(own, waveSum, total);
     if (threadIdx.x == 0) x.blockBase[blockIdx.x] = total;
-}
-
-/* exclusive prefix sum of blockBase[0, blocks) in place, blockBase[blocks] = the total (also to *hostTotal when given):
- * one block of 1024 threads walks it 1024 entries at a time */
-__global__ __launch_bounds__(1024) void pfac_all_block_scan(unsigned long long *v, unsigned int n, unsigned long long *hostTotal)
-{
-    __shared__ unsigned long long waveSum[16];
-    __shared__ unsigned long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (unsigned int base = 0; base < n; base += 1024) {
-        const unsigned int i = base + threadIdx.x;
-        const unsigned long long x = i < n ? v[i] : 0ull;
-        unsigned long long incl = x;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long up = __shfl_up(incl, d);
-            if ((int)lane >= d) incl += up;
-        }
-        if (lane == 63) waveSum[wave] = incl;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (unsigned int w = 0; w < wave; w++) before += waveSum[w];
-        if (i < n) v[i] = before + incl - x;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = before + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        v[n] = carry;
-        if (hostTotal != nullptr) {
-            __hip_atomic_store(hostTotal, carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __threadfence_system();
-        }
-    }
 }
 
 __global__ __launch_bounds__(kAllBlock) void pfac_all_scatter(ExpandArgs x)
@@ -136,7 +78,7 @@ __global__ __launch_bounds__(kAllBlock) void pfac_all_scatter(ExpandArgs x)
         const int p = has ? x.pairPos[i] : 0;
         const unsigned int c = has ? chainOf(x, id) : 0u;
         unsigned long long stepTotal = 0;
-        const unsigned long long o = base + blockExclusive(c, waveSum, stepTotal);
+        const unsigned long long o = base + blockExclusive<kAllBlock>((unsigned long long)c, waveSum, stepTotal);
         base += stepTotal;
         if (!has) continue;
         if (x.pairOffset != nullptr) x.pairOffset[i] = o;
@@ -167,14 +109,6 @@ __global__ __launch_bounds__(kAllBlock) void pfac_all_seg_first(const int *first
     }
 }
 
-/* queued behind the last launch of a call: tells the host, which polls the word, that the call's launches are through */
-__global__ void pfac_all_done(unsigned int *hostDone, unsigned int seq)
-{
-    __hip_atomic_store(hostDone, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-unsigned int gridCap(const PFAC_context *c) { return (unsigned int)(c->multiProcessorCount > 0 ? c->multiProcessorCount : 256) * 8u; }
-
 /* grow-only scratch of the expansion: the block totals, then (batch form) the expanded offset of every longest pair */
 char *allScratch(PFAC_context *c, size_t bytes)
 {
@@ -197,7 +131,7 @@ PFAC_status_t PFACX_allExpand(PFAC_handle_t handle, const int *d_pairIds, const 
     if (!d_table) {                                    /* chains of length 1: the list is the longest list, only segFirst changes type */
         if (d_segFirst) {
             const size_t lanes = numSegments + 1, b = (lanes + kAllBlock - 1) / kAllBlock;
-            const unsigned int grid = b < gridCap(c) ? (unsigned int)b : gridCap(c);
+            const unsigned int grid = b < gridCap(c, 8) ? (unsigned int)b : gridCap(c, 8);
             hipLaunchKernelGGL(pfac_all_seg_first, dim3(grid), dim3(kAllBlock), 0, 0, d_segFirstPairs, numSegments, count,
                                (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, d_segFirst);
             if (hipGetLastError() != hipSuccess || hipStreamSynchronize(0) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
@@ -215,32 +149,32 @@ PFAC_status_t PFACX_allExpand(PFAC_handle_t handle, const int *d_pairIds, const 
     x.pos = d_pos;
     x.capacity = capacity;
     size_t blocks = (count + kAllBlock - 1) / kAllBlock;
-    if (blocks > gridCap(c)) blocks = gridCap(c);
+    if (blocks > gridCap(c, 8)) blocks = gridCap(c, 8);
     x.per = blocks ? ((count + blocks - 1) / blocks + kAllBlock - 1) / kAllBlock * kAllBlock : kAllBlock;
     blocks = (count + x.per - 1) / x.per;
     x.blocks = (unsigned int)blocks;
-    const size_t baseBytes = ((blocks + 1) * sizeof(unsigned long long) + 255) & ~size_t(255);
+    const size_t baseBytes = round256((blocks + 1) * sizeof(unsigned long long));
     char *s = allScratch(c, baseBytes + (d_segFirst ? count * sizeof(unsigned long long) : 0));
     if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
     x.blockBase = reinterpret_cast<unsigned long long *>(s);
     x.pairOffset = d_segFirst ? reinterpret_cast<unsigned long long *>(s + baseBytes) : nullptr;
-    const bool mapped = c->h_modeHint != nullptr && c->d_modeHint != nullptr;
-    unsigned long long *hostTotal = mapped ? reinterpret_cast<unsigned long long *>(c->d_modeHint + pfac::kHostAllTotalWord) : nullptr;
+    const bool mapped = hostMapped(c);
+    const HostHandoff list = mapped ? HostHandoff(c, pfac::kHostAll) : HostHandoff();
     if (blocks) hipLaunchKernelGGL(pfac_all_count, dim3((unsigned int)blocks), dim3(kAllBlock), 0, 0, x);
-    hipLaunchKernelGGL(pfac_all_block_scan, dim3(1), dim3(1024), 0, 0, x.blockBase, (unsigned int)blocks, hostTotal);
+    hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, x.blockBase, (unsigned int)blocks, x.blockBase + blocks,
+                       reinterpret_cast<unsigned long long *>(list.d_value));
     if (blocks) hipLaunchKernelGGL(pfac_all_scatter, dim3((unsigned int)blocks), dim3(kAllBlock), 0, 0, x);
     if (d_segFirst) {
         const size_t lanes = numSegments + 1, b = (lanes + kAllBlock - 1) / kAllBlock;
-        const unsigned int grid = b < gridCap(c) ? (unsigned int)b : gridCap(c);
+        const unsigned int grid = b < gridCap(c, 8) ? (unsigned int)b : gridCap(c, 8);
         hipLaunchKernelGGL(pfac_all_seg_first, dim3(grid), dim3(kAllBlock), 0, 0, d_segFirstPairs, numSegments, count, x.pairOffset,
                            x.blockBase + blocks, d_segFirst);
     }
     unsigned long long total = 0;
     if (mapped) {
-        c->allSeq = c->allSeq + 1u ? c->allSeq + 1u : 1u;
-        hipLaunchKernelGGL(pfac_all_done, dim3(1), dim3(1), 0, 0, c->d_modeHint + pfac::kHostAllDoneWord, c->allSeq);
-        if (hipGetLastError() != hipSuccess || waitHostSeq(c->h_modeHint + pfac::kHostAllDoneWord, c->allSeq) == HostWait::SyncFailed) return PFAC_STATUS_INTERNAL_ERROR;
-        total = __atomic_load_n(reinterpret_cast<unsigned long long *>(c->h_modeHint + pfac::kHostAllTotalWord), __ATOMIC_ACQUIRE);
+        list.queueDone();
+        if (!list.wait()) return PFAC_STATUS_INTERNAL_ERROR;
+        total = list.value64();
     } else if (hipGetLastError() != hipSuccess ||
                hipMemcpy(&total, x.blockBase + blocks, sizeof(total), hipMemcpyDeviceToHost) != hipSuccess) {
         return PFAC_STATUS_INTERNAL_ERROR;

@@ -14,7 +14,7 @@
  *                             the id found does not fit the segment
  *   pfac_batch_pair_fixup     compacted result: one lane per pair, its segment by binary search in the offsets; a pair
  *                             that crosses its segment's end is walked again (new id 0: the pair drops out); kept pairs per block
- *   pfac_batch_block_scan     exclusive scan of the kept counts (one block) ...
+ *   pfac_array_scan           exclusive scan of the kept counts (one block; scan_passes.h) ...
  *   pfac_batch_compact        ... stable scatter of the kept pairs to scratch (only when some pair dropped)
  *   pfac_batch_seg_first      one lane per segment boundary: lower bound of offsets[k] among the pair positions
  *
@@ -30,7 +30,7 @@
 #include <cstdint>
 
 #include "pfac_context.h"
-#include "scan_common.h"
+#include "scan_passes.h"
 
 namespace {
 
@@ -142,29 +142,6 @@ __global__ __launch_bounds__(kBatchBlock) void pfac_batch_pair_fixup(BatchArgs b
     }
 }
 
-/* exclusive prefix sum of v[0, n) in place: one block of 1024 threads walks it 1024 entries at a time */
-__global__ __launch_bounds__(1024) void pfac_batch_block_scan(unsigned int *v, unsigned int n)
-{
-    __shared__ unsigned int waveSum[16];
-    __shared__ unsigned int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (unsigned int base = 0; base < n; base += 1024) {
-        const unsigned int i = base + threadIdx.x;
-        const unsigned int x = i < n ? v[i] : 0u;
-        const unsigned int incl = waveInclusiveScan(x);
-        if (lane == 63) waveSum[wave] = incl;
-        __syncthreads();
-        unsigned int before = carry;
-        for (uint32_t w = 0; w < wave; w++) before += waveSum[w];
-        if (i < n) v[i] = before + incl - x;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = before + incl;
-        __syncthreads();
-    }
-}
-
 /* kept pair i goes to slot blockBase[block] + (kept pairs in front of it inside the block): the order stays */
 __global__ __launch_bounds__(kBatchBlock) void pfac_batch_compact(const int *ids, const int *pos, unsigned int count, const unsigned int *blockBase,
                                                                   int *idsOut, int *posOut)
@@ -233,8 +210,6 @@ BatchArgs batchArgs(const PFAC_context *c, const char *d_input, size_t size, con
     return b;
 }
 
-unsigned int gridCap(const PFAC_context *c) { return (unsigned int)(c->multiProcessorCount > 0 ? c->multiProcessorCount : 256) * 16u; }
-
 /* grow-only scratch of the compacted form: [0, 256) drop counter, then kept counts per block, then the compacted ids and positions */
 char *batchScratch(PFAC_context *c, size_t bytes) { return c->scratch.batch.reserve(bytes) == PFAC_STATUS_SUCCESS ? c->scratch.batch.get() : nullptr; }
 
@@ -259,7 +234,7 @@ PFAC_status_t PFACX_batchFixup(PFAC_handle_t handle, const char *d_input, size_t
     while (groupLog2 < 6 && (size_t(1) << groupLog2) < want) groupLog2++;
     const size_t perBlock = ((size_t)kBatchBlock >> groupLog2) * kSegsPerTrip;      /* segments a block takes per trip */
     const size_t blocks = numSegments / perBlock + 1;
-    const unsigned int grid = blocks < gridCap(c) ? (unsigned int)blocks : gridCap(c);
+    const unsigned int grid = blocks < gridCap(c, 16) ? (unsigned int)blocks : gridCap(c, 16);
     if (c->textureMode == PFAC_TEXTURE_ON)
         hipLaunchKernelGGL(pfac_batch_fixup<true>, dim3(grid), dim3(kBatchBlock), 0, 0, b, a, d_matched_result, groupLog2);
     else
@@ -282,7 +257,7 @@ PFAC_status_t PFACX_batchReduceFixup(PFAC_handle_t handle, const char *d_input, 
     const unsigned int n = (unsigned int)*count;
     if (n > 0 && b.maxWalk > 0) {
         const size_t blocks = ((size_t)n + kBatchBlock - 1) / kBatchBlock;
-        const size_t head = 256, keptBytes = (blocks * sizeof(unsigned int) + 255) & ~size_t(255);
+        const size_t head = 256, keptBytes = round256(blocks * sizeof(unsigned int));
         char *s = batchScratch(c, head + keptBytes + 2 * (size_t)n * sizeof(int));
         if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
         unsigned int *drops = reinterpret_cast<unsigned int *>(s), *blockKept = reinterpret_cast<unsigned int *>(s + head);
@@ -298,7 +273,7 @@ PFAC_status_t PFACX_batchReduceFixup(PFAC_handle_t handle, const char *d_input, 
         if (dropped > n) return PFAC_STATUS_INTERNAL_ERROR;
         if (dropped) {                                 /* rare: a pattern that straddled a segment end and nothing shorter inside */
             const unsigned int left = n - dropped;
-            hipLaunchKernelGGL(pfac_batch_block_scan, dim3(1), dim3(1024), 0, 0, blockKept, (unsigned int)blocks);
+            hipLaunchKernelGGL(pfac_array_scan<unsigned int>, dim3(1), dim3(1024), 0, 0, blockKept, (unsigned int)blocks, (unsigned int *)nullptr, (unsigned int *)nullptr);
             hipLaunchKernelGGL(pfac_batch_compact, dim3((unsigned int)blocks), dim3(kBatchBlock), 0, 0, d_ids, d_pos, n, blockKept, idsOut, posOut);
             if (hipGetLastError() != hipSuccess ||
                 (left && (hipMemcpyAsync(d_ids, idsOut, left * sizeof(int), hipMemcpyDeviceToDevice, 0) != hipSuccess ||
@@ -308,7 +283,7 @@ PFAC_status_t PFACX_batchReduceFixup(PFAC_handle_t handle, const char *d_input, 
         }
     }
     const size_t lanes = numSegments + 1, blocks = (lanes + kBatchBlock - 1) / kBatchBlock;
-    const unsigned int grid = blocks < gridCap(c) ? (unsigned int)blocks : gridCap(c);
+    const unsigned int grid = blocks < gridCap(c, 16) ? (unsigned int)blocks : gridCap(c, 16);
     hipLaunchKernelGGL(pfac_batch_seg_first, dim3(grid), dim3(kBatchBlock), 0, 0, b, d_pos, (unsigned int)*count, d_segFirst);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(0) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
     return PFAC_STATUS_SUCCESS;

@@ -10,6 +10,7 @@
  *   scan_stream.hip   pfac_stream_seam: the seam between a stream's carried bytes and its next piece (PFACX_stream*)
  *   scan_flows.hip    pfac_flows_*: the seams of many streams in one launch and the merge with one scan's pairs (PFACX_flows*)
  *   scan_lines.hip    pfac_lines_*: the newline bitmap, the lines the scan's pairs fall into, their selection and gather (PFACX_matchLines*)
+ * scan_passes.h holds what the units around the product kernels share on top of this: the hand-off to the host, block prefix sums, the seam.
  */
 #ifndef PFAC_SCAN_COMMON_H_
 #define PFAC_SCAN_COMMON_H_
@@ -807,30 +808,6 @@ inline void fillChainArgs(const PFAC_context *c, ScanArgs &a)
     const size_t bytes = c->tables.chainSlots.bytes();
     a.chainBytes = bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)bytes;
     a.maxWalk = (uint32_t)c->fa.maxPatternLen;
-}
-
-/* The host's wait for the sequence number (never 0) that the last launch of a call writes into a word of the handle's mapped host memory: polled for
- * 20 ms -- a hipStreamSynchronize or a blocking hipMemcpy wakes up 30 - 50 us after the last kernel has ended --, then a stream sync.  Says how it
- * ended; what a sync without the number means is the caller's business */
-enum class HostWait { Polled, Synced, SyncFailed };
-inline HostWait waitHostSeq(const volatile unsigned int *word, unsigned int seq)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned int spins = 0; __atomic_load_n(const_cast<const unsigned int *>(word), __ATOMIC_ACQUIRE) != seq; spins++) {
-        if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20))
-            return hipStreamSynchronize(0) == hipSuccess ? HostWait::Synced : HostWait::SyncFailed;
-#if defined(__x86_64__) || defined(__i386__)
-        __builtin_ia32_pause();
-#endif
-    }
-    return HostWait::Polled;
-}
-
-inline unsigned int gridFor(const PFAC_context *c, size_t items)
-{
-    const size_t cap = (size_t)(c->multiProcessorCount > 0 ? c->multiProcessorCount : 256) * 8;
-    const size_t blocks = (items + 255) / 256;
-    return (unsigned int)(blocks < 1 ? 1 : blocks > cap ? cap : blocks);
 }
 
 } // namespace

@@ -13,7 +13,7 @@
  *                      the piece's first byte (negative); the flow's NEXT carry goes to its other buffer, so a failed call leaves
  *                      every flow as it was.  Two shapes, picked on the host by M: M - 1 <= 64 -- one WAVE per piece, four pieces
  *                      per block, each wave its own LDS slice, a position per lane, no loop; larger M -- one BLOCK per piece,
- *                      looping like pfac_stream_seam, block and dynamic LDS stage sized by M (M = 243: 256 threads, 484 bytes), its
+ *                      the body of pfac_stream_seam (scan_passes.h: seamBlock), block and dynamic LDS stage sized by M (M = 243: 256 threads, 484 bytes), its
  *                      stage in device scratch where 2 (M - 1) bytes exceed the LDS stage.
  *                      The flush is this launch with empty pieces.
  *   pfac_flows_count   a thread per piece: its range among the scan's position-ordered pairs by lower bound on [s, e - (M - 1)),
@@ -36,7 +36,7 @@
 #include <cstdint>
 
 #include "pfac_context.h"
-#include "scan_common.h"
+#include "scan_passes.h"
 
 namespace {
 
@@ -45,10 +45,8 @@ constexpr int kWaveSeamBlock = 256;
 constexpr int kWaveSeamWaves = kWaveSeamBlock / 64;
 constexpr int kWaveSlice = 2 * kWaveSeamMax + 16;      /* bytes of LDS per wave: [carry | head], 16-byte aligned slices */
 constexpr int kSeamBlock = 1024;
-constexpr int kSeamWaves = kSeamBlock / 64;
 constexpr size_t kSeamLdsBytes = pfac::kStreamSeamLdsBytes;
 constexpr int kPieceBlock = 256;               /* pieces per block of the merge's per-piece launches */
-constexpr int kPieceWaves = kPieceBlock / 64;
 
 struct FlowsArgs {
     const unsigned char *in;
@@ -73,10 +71,25 @@ struct FlowsArgs {
     unsigned int seq;
 };
 
-__device__ __forceinline__ unsigned char flowFold(unsigned char b, uint32_t fold) { return (unsigned char)(b + ((fold != 0 && (unsigned)(b - 'A') < 26u) ? 32 : 0)); }
+/* piece k of the call as its seam sees it (an empty descriptor: nothing staged, carried on or walked) */
+__device__ __forceinline__ SeamPiece seamPieceOf(const FlowsArgs &f, const PFACX_flowPiece_t &d)
+{
+    SeamPiece s;
+    s.carry = f.carries + ((size_t)2 * d.flow + d.cur) * f.carryStride;
+    s.carryNext = f.carries + ((size_t)2 * d.flow + (d.cur ^ 1u)) * f.carryStride;
+    s.piece = f.in + d.start;
+    s.carried = d.carried;
+    s.staged = d.carried + (d.len < f.span ? d.len : f.span);
+    s.numFinal = d.numFinal;
+    const uint32_t all = d.carried + d.len;                       /* below 2^31 (flows_api.cpp: checkPieces) */
+    s.nextCarried = all < f.span ? all : f.span;
+    s.fold = f.fold;
+    s.size = d.len;
+    return s;
+}
 
-/* M - 1 <= 64: a wave per piece.  Every wave of the block runs the whole body (a wave without a piece has an empty one), so the
- * barrier and the ballot see all lanes */
+/* M - 1 <= 64: a wave per piece, a position per lane, no loop.  Every wave of the block runs the whole body (a wave without a piece has an
+ * empty one), so the barrier and the ballot see all lanes */
 __global__ __launch_bounds__(kWaveSeamBlock) void pfac_flows_seam_wave(ScanArgs a, FlowsArgs f)
 {
     __shared__ __attribute__((aligned(16))) unsigned char slices[kWaveSeamWaves][kWaveSlice];
@@ -85,85 +98,30 @@ __global__ __launch_bounds__(kWaveSeamBlock) void pfac_flows_seam_wave(ScanArgs 
     const bool live = k < f.numPieces;
     PFACX_flowPiece_t d = PFACX_flowPiece_t{};
     if (live) d = f.pieces[k];
-    const uint32_t head = d.len < f.span ? d.len : f.span;
-    const uint32_t staged = d.carried + head;                     /* <= 2 * 64 */
-    const unsigned char *carry = f.carries + ((size_t)2 * d.flow + d.cur) * f.carryStride;
-    unsigned char *carryNext = f.carries + ((size_t)2 * d.flow + (d.cur ^ 1u)) * f.carryStride;
-    const unsigned char *piece = f.in + d.start;
+    const SeamPiece s = seamPieceOf(f, d);                        /* staged <= 2 * 64, nextCarried <= 64 */
     unsigned char *stage = slices[wave];
-    for (uint32_t i = lane; i < staged; i += 64u)
-        stage[i] = i < d.carried ? carry[i] : flowFold(piece[i - d.carried], f.fold);
-    /* the next carry: the last nextCarried bytes of [carry | piece] */
-    const uint32_t all = d.carried + d.len;
-    const uint32_t nextCarried = all < f.span ? all : f.span;
-    if (lane < nextCarried) {
-        const uint32_t j = all - nextCarried + lane;
-        carryNext[lane] = j < d.carried ? carry[j] : flowFold(piece[j - d.carried], f.fold);
-    }
+    seamStage(s, stage, lane, 64u);
+    if (lane < s.nextCarried) s.carryNext[lane] = seamByte(s, s.carried + d.len - s.nextCarried + lane);
     __syncthreads();
 
     const ChainCtx<false> ctx(a);
-    const int m = lane < d.numFinal ? boundedWalk<false>(ctx, stage, lane, staged) : 0;
+    const int m = lane < s.numFinal ? boundedWalk<false>(ctx, stage, lane, s.staged) : 0;
     const uint64_t hits = __ballot(m > 0);
-    if (m > 0) {
-        const uint32_t at = d.seamOff + laneRankIn(hits);
-        f.seamIds[at] = m;
-        f.seamPos[at] = (int)lane - (int)d.carried;
-    }
+    if (m > 0) seamEmit(s, f.seamIds, f.seamPos, d.seamOff + laneRankIn(hits), m, lane);
     if (live && lane == 0) f.seamCount[k] = (uint32_t)__popcll(hits);
 }
 
-/* larger M: a block per piece, the loop of pfac_stream_seam.  There are as many blocks as pieces, so the block and its stage are sized by M on
- * the host: min(1024, M - 1 rounded up to a wave) threads, 2 (M - 1) bytes of dynamic LDS (none where the stage is device scratch) */
+/* larger M: a block per piece, the body of pfac_stream_seam (scan_passes.h: seamBlock).  There are as many blocks as pieces, so the block and its
+ * stage are sized by M on the host: min(1024, M - 1 rounded up to a wave) threads, 2 (M - 1) bytes of dynamic LDS (none where the stage is device scratch) */
 __global__ __launch_bounds__(kSeamBlock) void pfac_flows_seam_block(ScanArgs a, FlowsArgs f)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsStage[];
-    __shared__ uint32_t waveCount[kSeamWaves];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t kBlock = blockDim.x, waves = kBlock >> 6;
+    __shared__ uint32_t waveCount[kSeamBlock / 64];
     const uint32_t k = blockIdx.x;
     const PFACX_flowPiece_t d = f.pieces[k];
-    const uint32_t head = d.len < f.span ? d.len : f.span;
-    const uint32_t staged = d.carried + head;
-    const unsigned char *carry = f.carries + ((size_t)2 * d.flow + d.cur) * f.carryStride;
-    unsigned char *carryNext = f.carries + ((size_t)2 * d.flow + (d.cur ^ 1u)) * f.carryStride;
-    const unsigned char *piece = f.in + d.start;
     unsigned char *stage = f.stage != nullptr ? f.stage + (size_t)k * f.stageStride : ldsStage;
-
-    for (uint32_t i = tid; i < staged; i += kBlock)
-        stage[i] = i < d.carried ? carry[i] : flowFold(piece[i - d.carried], f.fold);
-    const size_t all = (size_t)d.carried + d.len;
-    const uint32_t nextCarried = (uint32_t)(all < f.span ? all : f.span);
-    for (uint32_t i = tid; i < nextCarried; i += kBlock) {
-        const size_t j = all - nextCarried + i;
-        carryNext[i] = j < d.carried ? carry[j] : flowFold(piece[j - d.carried], f.fold);
-    }
-    __threadfence_block();
-    __syncthreads();
-
-    const ChainCtx<false> ctx(a);
-    uint32_t written = 0;                      /* the same in every thread */
-    for (uint32_t base = 0; base < d.numFinal; base += kBlock) {
-        const uint32_t p = base + tid;
-        const int m = p < d.numFinal ? boundedWalk<false>(ctx, stage, p, staged) : 0;
-        const uint64_t hits = __ballot(m > 0);
-        if (lane == 0) waveCount[wave] = (uint32_t)__popcll(hits);
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (uint32_t w = 0; w < waves; w++) {
-            const uint32_t cnt = waveCount[w];
-            before += w < wave ? cnt : 0u;
-            total += cnt;
-        }
-        if (m > 0) {
-            const uint32_t at = d.seamOff + written + before + laneRankIn(hits);
-            f.seamIds[at] = m;
-            f.seamPos[at] = (int)p - (int)d.carried;
-        }
-        written += total;
-        __syncthreads();                       /* waveCount is rewritten by the next trip */
-    }
-    if (tid == 0) f.seamCount[k] = written;
+    const uint32_t written = seamBlock<0>(a, seamPieceOf(f, d), stage, f.seamIds + d.seamOff, f.seamPos + d.seamOff, waveCount);
+    if (threadIdx.x == 0) f.seamCount[k] = written;
 }
 
 /* first index in pos[0, n) whose entry is >= x (pos ascending) */
@@ -177,28 +135,9 @@ __device__ __forceinline__ uint32_t lowerBound(const int *pos, uint32_t n, uint3
     return lo;
 }
 
-/* the block's exclusive scan of one value per thread (kPieceBlock threads); *blockTotal: the sum.  Every thread calls it */
-__device__ __forceinline__ uint32_t blockExclusive(uint32_t v, uint32_t *waveTotals, uint32_t *blockTotal)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t inc = waveInclusiveScan(v);
-    if (lane == 63u) waveTotals[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kPieceWaves; w++) {
-        const uint32_t t = waveTotals[w];
-        before += (uint32_t)w < wave ? t : 0u;
-        total += t;
-    }
-    __syncthreads();                           /* waveTotals may be used again */
-    *blockTotal = total;
-    return before + inc - v;
-}
-
 __global__ __launch_bounds__(kPieceBlock) void pfac_flows_count(FlowsArgs f)
 {
-    __shared__ uint32_t waveTotals[kPieceWaves];
+    __shared__ uint32_t waveTotals[kPieceBlock / 64];
     const uint32_t k = blockIdx.x * kPieceBlock + threadIdx.x;
     uint32_t count = 0;
     if (k < f.numPieces) {
@@ -213,19 +152,19 @@ __global__ __launch_bounds__(kPieceBlock) void pfac_flows_count(FlowsArgs f)
         f.counts[k] = count;
     }
     uint32_t total;
-    (void)blockExclusive(count, waveTotals, &total);
+    (void)blockExclusive<kPieceBlock>(count, waveTotals, total);
     if (threadIdx.x == 0) f.blockSums[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kPieceBlock) void pfac_flows_sums(FlowsArgs f)
 {
-    __shared__ uint32_t waveTotals[kPieceWaves];
+    __shared__ uint32_t waveTotals[kPieceBlock / 64];
     uint32_t running = 0;                      /* the same in every thread */
     for (uint32_t base = 0; base < f.numBlocks; base += kPieceBlock) {
         const uint32_t b = base + threadIdx.x;
         const uint32_t v = b < f.numBlocks ? f.blockSums[b] : 0u;
         uint32_t total;
-        const uint32_t ex = blockExclusive(v, waveTotals, &total);
+        const uint32_t ex = blockExclusive<kPieceBlock>(v, waveTotals, total);
         if (b < f.numBlocks) f.blockSums[b] = running + ex;
         running += total;
     }
@@ -237,12 +176,12 @@ __global__ __launch_bounds__(kPieceBlock) void pfac_flows_sums(FlowsArgs f)
 
 __global__ __launch_bounds__(kPieceBlock) void pfac_flows_first(FlowsArgs f)
 {
-    __shared__ uint32_t waveTotals[kPieceWaves];
+    __shared__ uint32_t waveTotals[kPieceBlock / 64];
     __shared__ uint32_t first[kPieceBlock], seams[kPieceBlock], from[kPieceBlock];
     const uint32_t k = blockIdx.x * kPieceBlock + threadIdx.x;
     const bool live = k < f.numPieces;
     uint32_t total;
-    const uint32_t at = f.blockSums[blockIdx.x] + blockExclusive(live ? f.counts[k] : 0u, waveTotals, &total);
+    const uint32_t at = f.blockSums[blockIdx.x] + blockExclusive<kPieceBlock>(live ? f.counts[k] : 0u, waveTotals, total);
     if (live) f.pieceFirst[k] = (int)at;
     first[threadIdx.x] = at;
     seams[threadIdx.x] = live && f.seamCount != nullptr ? f.seamCount[k] : 0u;
@@ -310,7 +249,7 @@ PFAC_status_t PFACX_flowsRun(PFAC_handle_t handle, const PFACX_flowsRun_t *run, 
     const bool seams = M > 1;
     if (seams && (!run->d_carries || !run->d_seamCount || run->carryStride < M - 1)) return PFAC_STATUS_INVALID_PARAMETER;
     if (seams && 2 * (M - 1) > kSeamLdsBytes && (!run->d_stage || run->stageStride < 2 * (M - 1))) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!c->tables.chainSlots || c->chainJumpLog2 <= 0 || !c->d_modeHint || !c->h_modeHint) return PFAC_STATUS_INTERNAL_ERROR;
+    if (!c->tables.chainSlots || c->chainJumpLog2 <= 0 || !hostMapped(c)) return PFAC_STATUS_INTERNAL_ERROR;
 
     ScanArgs a = ScanArgs{};
     fillChainArgs(c, a);                       /* the walk's view of the chained table (scan_common.h) */
@@ -339,9 +278,10 @@ PFAC_status_t PFACX_flowsRun(PFAC_handle_t handle, const PFACX_flowsRun_t *run, 
     f.span = (uint32_t)(M - 1);
     f.fold = c->caseInsensitive ? 1u : 0u;
     f.numBlocks = (f.numPieces + kPieceBlock - 1) / kPieceBlock;
-    f.hostCount = c->d_modeHint + pfac::kHostFlowsCountWord;
-    c->flowsSeq = c->flowsSeq + 1u ? c->flowsSeq + 1u : 1u;
-    f.seq = c->flowsSeq;
+    static_assert(pfac::kHostFlows.done == pfac::kHostFlows.value + 1, "pfac_flows_done stores the two words side by side");
+    const HostHandoff pairs(c, pfac::kHostFlows);
+    f.hostCount = pairs.d_value;
+    f.seq = pairs.seq;
 
     if (seams) {
         if (M - 1 <= (size_t)kWaveSeamMax)
@@ -357,13 +297,9 @@ PFAC_status_t PFACX_flowsRun(PFAC_handle_t handle, const PFACX_flowsRun_t *run, 
     hipLaunchKernelGGL(pfac_flows_first, dim3(f.numBlocks), dim3(kPieceBlock), 0, 0, f);
     if (f.scanCount) hipLaunchKernelGGL(pfac_flows_place, dim3(gridFor(c, f.scanCount)), dim3(256), 0, 0, f);
     hipLaunchKernelGGL(pfac_flows_done, dim3(1), dim3(64), 0, 0, f);
-    if (hipGetLastError() != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
     /* the last launch writes the call's number into host memory behind the total: polled for a while, like the compacted-output call's */
-    volatile unsigned int *hostCount = c->h_modeHint + pfac::kHostFlowsCountWord, *hostDone = hostCount + 1;
-    const HostWait w = waitHostSeq(hostDone, f.seq);
-    if (w == HostWait::SyncFailed || (w == HostWait::Synced && __atomic_load_n(const_cast<unsigned int *>(hostDone), __ATOMIC_ACQUIRE) != f.seq))
-        return PFAC_STATUS_INTERNAL_ERROR;
-    const unsigned int total = *hostCount;
+    if (!pairs.wait()) return PFAC_STATUS_INTERNAL_ERROR;
+    const unsigned int total = *pairs.h_value;
     if (total > run->capacity) return PFAC_STATUS_INTERNAL_ERROR;
     *h_total = (int)total;
     return PFAC_STATUS_SUCCESS;

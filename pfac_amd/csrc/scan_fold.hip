@@ -25,13 +25,12 @@
 #include <cstdint>
 
 #include "pfac_context.h"
+#include "scan_passes.h"
 
 namespace {
 
 constexpr int kFoldBlock = 256;
 constexpr int kFoldUnroll = 4;                 /* 16-byte steps a lane has in flight */
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct FoldArgs {
     const unsigned char *src;                  /* the caller's bytes */
@@ -50,8 +49,6 @@ __device__ __forceinline__ uint32_t foldWord(uint32_t x)
     return x | (((ge ^ gt) & ~x & 0x80808080u) >> 2);
 }
 
-__device__ __forceinline__ unsigned char foldByte(unsigned char b) { return (unsigned char)(b + ((unsigned)(b - 'A') < 26u ? 32 : 0)); }
-
 __device__ __forceinline__ u32x4 foldVec(u32x4 v) { return u32x4{foldWord(v.x), foldWord(v.y), foldWord(v.z), foldWord(v.w)}; }
 
 /* 16 bytes starting m = 4 Q + r bytes into the 32 of a | b */
@@ -68,10 +65,10 @@ __global__ __launch_bounds__(kFoldBlock) void pfac_fold(FoldArgs f)
 {
     const size_t tid = (size_t)blockIdx.x * kFoldBlock + threadIdx.x;
     const size_t lanes = (size_t)gridDim.x * kFoldBlock;
-    if (tid < f.head) f.dst[tid] = foldByte(f.src[tid]);
+    if (tid < f.head) f.dst[tid] = foldByte(f.src[tid], 1u);
     if (tid < f.tail) {
         const size_t at = f.head + f.chunks * 16 + tid;
-        f.dst[at] = foldByte(f.src[at]);
+        f.dst[at] = foldByte(f.src[at], 1u);
     }
     u32x4 *out = reinterpret_cast<u32x4 *>(f.dst + f.head);
     for (size_t j0 = tid; j0 < f.chunks; j0 += lanes * kFoldUnroll) {
@@ -131,7 +128,7 @@ PFAC_status_t PFACX_foldInput(PFAC_handle_t handle, const char *src, char *dst, 
     }
     const size_t lanes = f.chunks > f.head + f.tail ? f.chunks : f.head + f.tail;
     const size_t blocks = (lanes + kFoldBlock - 1) / kFoldBlock;
-    const size_t cap = (size_t)(c->multiProcessorCount > 0 ? c->multiProcessorCount : 256) * 8;
+    const size_t cap = gridCap(c, 8);
     const dim3 grid((unsigned int)(blocks < cap ? blocks : cap)), block(kFoldBlock);
     if (f.chunks == 0 || m == 0) hipLaunchKernelGGL(pfac_fold<-1>, grid, block, 0, 0, f);
     else if (m < 4) hipLaunchKernelGGL(pfac_fold<0>, grid, block, 0, 0, f);

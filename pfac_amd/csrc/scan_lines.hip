@@ -21,13 +21,13 @@
  *                          the selected ones (hit ^ invert) per block and notes the block's last newline
  *   pfac_lines_block_scan  ... the first selected line of each block, the last newline in front of each block
  *   pfac_lines_select<1>   the same walk again, writing (start, len, index) in order over the scan's pair list
- *   pfac_lines_done        the call's sequence number to mapped host memory
+ *   pfac_host_done         the call's sequence number to mapped host memory (scan_passes.h: HostHandoff)
  * Only the first pass and the scan touch O(size) bytes; the rest reads size / 8 bytes of bitmaps and the pairs.
  * SCRATCH of a select call, B = (mis + size) / 2048 + 1 blocks: 256 B (newline bitmap) + 256 B + 256 once (hit bitmap and the word a funnel may
  * read behind it) + 128 B (ranks) + 2 x (4 (B + 1) + 4 (B + 1) + 4 B) bytes (lines, selected lines and last newline per block, and their scans), each part
  * rounded up to 256 bytes: 0.32 bytes per input byte, whatever the data.
  *
- * The gather: pfac_lines_gather_count / pfac_lines_scan64 / pfac_lines_gather_offsets give every line its 64-bit offset in the text (len + 1
+ * The gather: pfac_lines_gather_count / pfac_array_scan (scan_passes.h) / pfac_lines_gather_offsets give every line its 64-bit offset in the text (len + 1
  * per line, (start, len) clamped to the input), pfac_lines_gather_copy cuts the TEXT, not the list, into tiles of 4 KiB: a tile finds its
  * first line by binary search in the offsets, stages the offsets of its lines (at most 4096) in LDS, and every thread assembles 16 output
  * bytes -- one 3 MiB line and a million 20-byte lines are the same work per byte.  Tiles are aligned on the output address, a tile stops at
@@ -42,7 +42,7 @@
 #include <cstdint>
 
 #include "pfac_context.h"
-#include "scan_common.h"
+#include "scan_passes.h"
 
 namespace {
 
@@ -270,12 +270,6 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_select(LinesArgs a)
     }
 }
 
-/* queued behind the last launch of a call: tells the host, which polls the word, that the call's launches are through */
-__global__ void pfac_lines_done(unsigned int *hostDone, unsigned int seq)
-{
-    __hip_atomic_store(hostDone, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 /* ------------------------------------------------------------------ the gather */
 
 struct GatherArgs {
@@ -303,28 +297,6 @@ __device__ __forceinline__ size_t clampedLen(const GatherArgs &g, size_t i, size
     return l < 0 ? 0 : ((size_t)l > g.n - s ? g.n - s : (size_t)l);
 }
 
-/* exclusive prefix of `own` over the block's 256 threads, and the block's total (every thread gets it) */
-__device__ __forceinline__ unsigned long long blockExclusive64(unsigned long long own, unsigned long long *waveSum, unsigned long long &total)
-{
-    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned long long incl = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long up = __shfl_up(incl, d);
-        if ((int)lane >= d) incl += up;
-    }
-    __syncthreads();                                    /* waveSum may still be read from the previous step */
-    if (lane == 63) waveSum[wave] = incl;
-    __syncthreads();
-    unsigned long long before = 0;
-    total = 0;
-    for (unsigned int w = 0; w < kLinesThreads / 64; w++) {
-        if (w < wave) before += waveSum[w];
-        total += waveSum[w];
-    }
-    return before + incl - own;
-}
-
 __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_count(GatherArgs g)
 {
     __shared__ unsigned long long waveSum[kLinesThreads / 64];
@@ -333,43 +305,8 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_count(GatherA
     unsigned long long own = 0;
     for (size_t i = first + threadIdx.x; i < end; i += kLinesThreads) own += clampedLen(g, i, clampedStart(g, i)) + 1;
     unsigned long long total = 0;
-    (void)blockExclusive64(own, waveSum, total);
+    (void)blockExclusive<kLinesThreads>(own, waveSum, total);
     if (threadIdx.x == 0) g.blockBase[blockIdx.x] = total;
-}
-
-/* exclusive prefix sum of v[0, n) in place, v[n] = the total (also to *hostTotal when given): one block of 1024 threads */
-__global__ __launch_bounds__(1024) void pfac_lines_scan64(unsigned long long *v, unsigned int n, unsigned long long *hostTotal)
-{
-    __shared__ unsigned long long waveSum[16];
-    __shared__ unsigned long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (unsigned int base = 0; base < n; base += 1024) {
-        const unsigned int i = base + threadIdx.x;
-        const unsigned long long x = i < n ? v[i] : 0ull;
-        unsigned long long incl = x;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long up = __shfl_up(incl, d);
-            if ((int)lane >= d) incl += up;
-        }
-        if (lane == 63) waveSum[wave] = incl;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (unsigned int w = 0; w < wave; w++) before += waveSum[w];
-        if (i < n) v[i] = before + incl - x;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = before + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        v[n] = carry;
-        if (hostTotal != nullptr) {
-            __hip_atomic_store(hostTotal, carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __threadfence_system();
-        }
-    }
 }
 
 __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_offsets(GatherArgs g)
@@ -383,7 +320,7 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_offsets(Gathe
         const bool has = i < end;
         const unsigned long long c = has ? clampedLen(g, i, clampedStart(g, i)) + 1 : 0ull;
         unsigned long long stepTotal = 0;
-        const unsigned long long o = base + blockExclusive64(c, waveSum, stepTotal);
+        const unsigned long long o = base + blockExclusive<kLinesThreads>(c, waveSum, stepTotal);
         base += stepTotal;
         if (has) g.off[i] = o;
     }
@@ -469,21 +406,11 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_copy(GatherAr
     }
 }
 
-unsigned int gridCap(const PFAC_context *c) { return (unsigned int)(c->multiProcessorCount > 0 ? c->multiProcessorCount : 256) * 8u; }
-
-size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
-
 /* grow-only scratch of the lines calls (exactly what a call needs: a fixed function of its size) */
 char *linesScratch(PFAC_context *c, size_t bytes)
 {
     if (c->scratch.lines.count() < bytes && c->scratch.lines.reserve(bytes) != PFAC_STATUS_SUCCESS) return nullptr;
     return c->scratch.lines.get();
-}
-
-unsigned int nextSeq(PFAC_context *c)
-{
-    c->linesSeq = c->linesSeq + 1u ? c->linesSeq + 1u : 1u;
-    return c->linesSeq;
 }
 
 } // namespace
@@ -521,15 +448,15 @@ PFAC_status_t PFACX_linesSelect(PFAC_handle_t handle, const char *d_input, char 
     a.lineStart = d_lineStart;
     a.lineLen = d_lineLen;
     a.lineIndex = d_lineIndex;
-    const bool mapped = c->h_modeHint != nullptr && c->d_modeHint != nullptr;
-    unsigned int *hostWords = mapped ? c->d_modeHint + pfac::kHostLinesWord : nullptr;
-    const unsigned int waveGrid = (unsigned int)((blocks + 3) / 4 < gridCap(c) ? (blocks + 3) / 4 : gridCap(c));
+    const bool mapped = hostMapped(c);
+    const HostHandoff counts = mapped ? HostHandoff(c, pfac::kHostLines) : HostHandoff();      /* the lines, then the selected lines */
+    const unsigned int waveGrid = (unsigned int)((blocks + 3) / 4 < gridCap(c, 8) ? (blocks + 3) / 4 : gridCap(c, 8));
 
     /* the line index in front of the scan, on the same stream */
     hipLaunchKernelGGL(pfac_lines_bitmap, dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
     const unsigned int scanGrid = (a.blocks + 1024u * kScanPer - 1u) / (1024u * kScanPer);
     hipLaunchKernelGGL(pfac_lines_block_scan, dim3(scanGrid), dim3(1024), 0, 0, (const unsigned int *)a.lineCount, a.lineBase, (const unsigned int *)nullptr,
-                       (unsigned int *)nullptr, a.blocks, hostWords);
+                       (unsigned int *)nullptr, a.blocks, counts.d_value);
     if (hipGetLastError() != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
 
     /* the compacted scan, pairs in any order (the four ordering launches are not paid for): ids in d_lineStart, positions in d_lineLen */
@@ -545,19 +472,14 @@ PFAC_status_t PFACX_linesSelect(PFAC_handle_t handle, const char *d_input, char 
     if (count > 0) hipLaunchKernelGGL(pfac_lines_mark, dim3(gridFor(c, (size_t)count)), dim3(kLinesThreads), 0, 0, a, (const int *)d_lineLen, (unsigned int)count);
     hipLaunchKernelGGL(pfac_lines_select<0>, dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
     hipLaunchKernelGGL(pfac_lines_block_scan, dim3(scanGrid), dim3(1024), 0, 0, (const unsigned int *)a.selCount, a.selBase, (const unsigned int *)a.lastNl, a.prevNl,
-                       a.blocks, mapped ? hostWords + 1 : (unsigned int *)nullptr);
+                       a.blocks, mapped ? counts.d_value + 1 : (unsigned int *)nullptr);
     hipLaunchKernelGGL(pfac_lines_select<1>, dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
     unsigned int numLines = 0, numSelected = 0;
     if (mapped) {
-        const unsigned int seq = nextSeq(c);
-        hipLaunchKernelGGL(pfac_lines_done, dim3(1), dim3(1), 0, 0, hostWords + 2, seq);
-        if (hipGetLastError() != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
-        volatile unsigned int *host = c->h_modeHint + pfac::kHostLinesWord;
-        const HostWait w = waitHostSeq(host + 2, seq);
-        if (w == HostWait::SyncFailed || (w == HostWait::Synced && __atomic_load_n(const_cast<unsigned int *>(host + 2), __ATOMIC_ACQUIRE) != seq))
-            return PFAC_STATUS_INTERNAL_ERROR;
-        numLines = host[0];
-        numSelected = host[1];
+        counts.queueDone();
+        if (!counts.wait()) return PFAC_STATUS_INTERNAL_ERROR;
+        numLines = counts.h_value[0];
+        numSelected = counts.h_value[1];
     } else if (hipGetLastError() != hipSuccess || hipMemcpy(&numLines, a.lineBase + blocks, sizeof(numLines), hipMemcpyDeviceToHost) != hipSuccess ||
                hipMemcpy(&numSelected, a.selBase + blocks, sizeof(numSelected), hipMemcpyDeviceToHost) != hipSuccess) {
         return PFAC_STATUS_INTERNAL_ERROR;
@@ -586,7 +508,7 @@ double PFACX_linesBitmapProbe(PFAC_handle_t handle, const void *d_in, size_t n, 
     a.hitBits = reinterpret_cast<uint32_t *>(s + oHit);
     a.rank = reinterpret_cast<uint16_t *>(s + oRank);
     a.lineCount = reinterpret_cast<unsigned int *>(s + oLine);
-    const unsigned int grid = (unsigned int)((blocks + 3) / 4 < gridCap(c) ? (blocks + 3) / 4 : gridCap(c));
+    const unsigned int grid = (unsigned int)((blocks + 3) / 4 < gridCap(c, 8) ? (blocks + 3) / 4 : gridCap(c, 8));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     double ms = -1.0;
     if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
@@ -620,7 +542,7 @@ PFAC_status_t PFACX_linesGather(PFAC_handle_t handle, const char *d_input, size_
     g.outCapacity = outCapacity;
     g.misOut = (unsigned int)(reinterpret_cast<uintptr_t>(d_out) & 15u);
     size_t blocks = (numSelected + kLinesThreads - 1) / kLinesThreads;
-    if (blocks > gridCap(c)) blocks = gridCap(c);
+    if (blocks > gridCap(c, 8)) blocks = gridCap(c, 8);
     g.per = ((numSelected + blocks - 1) / blocks + kLinesThreads - 1) / kLinesThreads * kLinesThreads;
     blocks = (numSelected + g.per - 1) / g.per;
     g.blocks = (unsigned int)blocks;
@@ -629,28 +551,24 @@ PFAC_status_t PFACX_linesGather(PFAC_handle_t handle, const char *d_input, size_
     if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
     g.blockBase = reinterpret_cast<unsigned long long *>(s);
     g.off = reinterpret_cast<unsigned long long *>(s + baseBytes);
-    const bool mapped = c->h_modeHint != nullptr && c->d_modeHint != nullptr;
-    unsigned int *hostWords = mapped ? c->d_modeHint + pfac::kHostGatherWord : nullptr;
+    const bool mapped = hostMapped(c);
+    const HostHandoff text = mapped ? HostHandoff(c, pfac::kHostGather) : HostHandoff();
     hipLaunchKernelGGL(pfac_lines_gather_count, dim3(g.blocks), dim3(kLinesThreads), 0, 0, g);
-    hipLaunchKernelGGL(pfac_lines_scan64, dim3(1), dim3(1024), 0, 0, g.blockBase, g.blocks, reinterpret_cast<unsigned long long *>(hostWords));
+    hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, g.blockBase, g.blocks, g.blockBase + g.blocks,
+                       reinterpret_cast<unsigned long long *>(text.d_value));
     hipLaunchKernelGGL(pfac_lines_gather_offsets, dim3(g.blocks), dim3(kLinesThreads), 0, 0, g);
     /* the text is at most (size + 1) bytes per line; whatever it is, a launch never needs more tiles than outCapacity has */
     if (outCapacity) {
         const unsigned long long bound = (unsigned long long)numSelected * (size + 1);
         const unsigned long long most = (bound < outCapacity ? bound : (unsigned long long)outCapacity) + g.misOut;
         const unsigned long long tiles = (most + kTile - 1) / kTile;
-        hipLaunchKernelGGL(pfac_lines_gather_copy, dim3((unsigned int)(tiles < gridCap(c) * 4ull ? tiles : gridCap(c) * 4ull)), dim3(kLinesThreads), 0, 0, g);
+        hipLaunchKernelGGL(pfac_lines_gather_copy, dim3((unsigned int)(tiles < gridCap(c, 8) * 4ull ? tiles : gridCap(c, 8) * 4ull)), dim3(kLinesThreads), 0, 0, g);
     }
     unsigned long long total = 0;
     if (mapped) {
-        const unsigned int seq = nextSeq(c);
-        hipLaunchKernelGGL(pfac_lines_done, dim3(1), dim3(1), 0, 0, hostWords + 2, seq);
-        if (hipGetLastError() != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
-        volatile unsigned int *host = c->h_modeHint + pfac::kHostGatherWord;
-        const HostWait w = waitHostSeq(host + 2, seq);
-        if (w == HostWait::SyncFailed || (w == HostWait::Synced && __atomic_load_n(const_cast<unsigned int *>(host + 2), __ATOMIC_ACQUIRE) != seq))
-            return PFAC_STATUS_INTERNAL_ERROR;
-        total = __atomic_load_n(reinterpret_cast<unsigned long long *>(c->h_modeHint + pfac::kHostGatherWord), __ATOMIC_ACQUIRE);
+        text.queueDone();
+        if (!text.wait()) return PFAC_STATUS_INTERNAL_ERROR;
+        total = text.value64();
     } else if (hipGetLastError() != hipSuccess || hipMemcpy(&total, g.blockBase + blocks, sizeof(total), hipMemcpyDeviceToHost) != hipSuccess) {
         return PFAC_STATUS_INTERNAL_ERROR;
     }

@@ -104,6 +104,7 @@
 
 #include "pfac_context.h"
 #include "scan_common.h"
+#include "scan_passes.h"
 
 namespace {
 
@@ -404,18 +405,17 @@ PFAC_status_t reduceScan(PFAC_handle_t handle, int *d_input_string, int input_si
 #endif
     unsigned int count = 0;
     if (tidy) {
-        volatile unsigned int *hostCount = c->h_modeHint + pfac::kHostPairCountWord, *hostDone = hostCount + 1;
-        handle->orderSeq = handle->orderSeq + 1u ? handle->orderSeq + 1u : 1u;
-        order.o.seq = handle->orderSeq;
-        *hostCount = 0xFFFFFFFFu;
+        const HostHandoff pairs(handle, pfac::kHostPairs);
+        *pairs.h_value = 0xFFFFFFFFu;
         if (order.order(c) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+        pairs.queueDone();
 #if PFAC_REDUCE_TRACE
         trOrder = trUs();
 #endif
         /* the last launch writes the call's number into host memory: polled for a while (the call is a millisecond of GPU work per GiB) */
-        const HostWait through = waitHostSeq(hostDone, order.o.seq);
-        if (through == HostWait::SyncFailed) return PFAC_STATUS_INTERNAL_ERROR;
-        count = *hostCount;
+        HostWait through = HostWait::Polled;
+        if (!pairs.wait(&through)) return PFAC_STATUS_INTERNAL_ERROR;
+        count = *pairs.h_value;
 #if PFAC_REDUCE_TRACE
         trDone = trUs();
         fprintf(stderr, "PFAC_REDUCE_TRACE us: planned %.1f, scan queued %.1f, ordering queued %.1f, done %.1f (clean %d, polled %d)\n", trPlan, trScan, trOrder, trDone, (int)clean, (int)(through == HostWait::Polled));
@@ -461,7 +461,16 @@ __global__ __launch_bounds__(256) void pfac_stream_1r4w(const u32x4 *in, i32x4 *
     if ((v.x ^ v.y ^ v.z ^ v.w) == 0x12345678u) *sink = v.x;      /* keeps the load */
 }
 
+/* queued behind the last launch of a call: tells the host, which polls the word, that the call's launches are through (a hipStreamSynchronize or a
+ * blocking hipMemcpy wakes up 30 - 50 us after the last kernel has ended: half of what a compacted call spent behind its scan kernel) */
+__global__ void pfac_host_done(unsigned int *hostDone, unsigned int seq)
+{
+    __hip_atomic_store(hostDone, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 } // namespace
+
+void pfacmod::queueHostDone(unsigned int *d_done, unsigned int seq) { hipLaunchKernelGGL(pfac_host_done, dim3(1), dim3(1), 0, 0, d_done, seq); }
 
 extern "C" {
 

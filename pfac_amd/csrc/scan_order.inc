@@ -52,8 +52,6 @@ struct OrderArgs {
     unsigned int *nextCounters;    /* the crowded bins' and the pairs' counter of the handle's next call (two words): the rank pass leaves them zero */
     unsigned int *hostCount;       /* mapped host memory: the number of pairs, for the host (or null) */
     unsigned int paddedBins;       /* counters the scatter pass leaves zero */
-    unsigned int *hostDone;        /* mapped host memory: pfac_order_done, queued behind the rank pass, writes `seq` here (or null) */
-    unsigned int seq;
 };
 
 __device__ __forceinline__ void orderCountPhase(const OrderArgs &o, unsigned int count)
@@ -71,28 +69,6 @@ __device__ __forceinline__ void orderCountPhase(const OrderArgs &o, unsigned int
             todo &= ~same;
         }
     }
-}
-
-/* sum over the block's 256 threads (every thread gets it) and the exclusive prefix of `own` among them */
-__device__ __forceinline__ unsigned int blockScan256(unsigned int own, unsigned int *waveSum, unsigned int &total)
-{
-    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned int incl = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned int up = __shfl_up(incl, d);
-        if ((int)lane >= d) incl += up;
-    }
-    __syncthreads();                                    /* waveSum may still be read from the previous call */
-    if (lane == 63) waveSum[wave] = incl;
-    __syncthreads();
-    unsigned int before = 0;
-    total = 0;
-    for (unsigned int w = 0; w < 4; w++) {
-        if (w < wave) before += waveSum[w];
-        total += waveSum[w];
-    }
-    return before + incl - own;
 }
 
 /* the cursors of the 1024 bins of block `blk` (every thread of the block calls it) */
@@ -116,8 +92,8 @@ __device__ __forceinline__ void orderOffsetsPhase(const OrderArgs &o, unsigned i
     }
     const u32x4 c = all[firstQuad + t];
     unsigned int base = 0, ignored = 0;
-    (void)blockScan256(front, waveSum, base);
-    unsigned int run = base + blockScan256(c.x + c.y + c.z + c.w, waveSum, ignored);
+    (void)blockExclusive<256>(front, waveSum, base);
+    unsigned int run = base + blockExclusive<256>(c.x + c.y + c.z + c.w, waveSum, ignored);
     const unsigned int bin = (firstQuad + t) * 4;
     if (c.x > kOrderCrowded) o.crowded[atomicAdd(o.crowdedCount, 1u)] = bin;
     if (c.y > kOrderCrowded) o.crowded[atomicAdd(o.crowdedCount, 1u)] = bin + 1;
@@ -196,7 +172,7 @@ __device__ __forceinline__ void orderRankPhase(const OrderArgs &o, unsigned int 
             if (w < words) own += (unsigned int)__popc(bits[w]);
         }
         unsigned int ignored = 0;
-        unsigned int run = blockScan256(own, waveSum, ignored);
+        unsigned int run = blockExclusive<256>(own, waveSum, ignored);
         for (unsigned int j = 0; j < per; j++) {
             const unsigned int w = t * per + j;
             if (w < words) { below[w] = run; run += (unsigned int)__popc(bits[w]); }
@@ -252,13 +228,6 @@ __global__ __launch_bounds__(256) void pfac_order_rank(OrderArgs o)
 }
 
 
-/* queued behind the rank pass: tells the host, which polls the word, that the call's launches are through (a hipStreamSynchronize or a
- * blocking hipMemcpy wakes up 30 - 50 us after the last kernel has ended: half of what a call spent behind its scan kernel) */
-__global__ void pfac_order_done(unsigned int *hostDone, unsigned int seq)
-{
-    __hip_atomic_store(hostDone, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 /* grow-only device scratch of the compacted-output path, owned by the handle (the caller holds its lock) */
 PFAC_status_t reduceScratch(PFAC_context *mc, size_t need, char **base)
 {
@@ -302,8 +271,7 @@ struct PairOrder {
         o.count = o.crowdedCount + 1;
         o.nextCounters = o.counts + padded + 2 * ((parity & 1u) ^ 1u);
         o.paddedBins = (unsigned int)padded;
-        o.hostCount = mc->d_modeHint ? mc->d_modeHint + pfac::kHostPairCountWord : nullptr;
-        o.hostDone = mc->d_modeHint ? mc->d_modeHint + pfac::kHostPairCountWord + 1 : nullptr;
+        o.hostCount = mc->d_modeHint ? mc->d_modeHint + pfac::kHostPairs.value : nullptr;
         o.cursor = reinterpret_cast<unsigned int *>(base + counterBytes);
         o.crowded = reinterpret_cast<unsigned int *>(base + counterBytes + cursorBytes);
         o.posTmp = reinterpret_cast<unsigned int *>(base + fixed);
@@ -320,7 +288,6 @@ struct PairOrder {
         hipLaunchKernelGGL(pfac_order_offsets, dim3((o.bins + kOrderBlockBins - 1) / kOrderBlockBins), dim3(256), 0, 0, o);
         hipLaunchKernelGGL(pfac_order_scatter, dim3(grid), dim3(256), 0, 0, o);
         hipLaunchKernelGGL(pfac_order_rank, dim3(grid), dim3(256), 0, 0, o);
-        if (o.hostDone != nullptr && o.seq != 0) hipLaunchKernelGGL(pfac_order_done, dim3(1), dim3(1), 0, 0, o.hostDone, o.seq);
         return hipGetLastError();
     }
 };

@@ -15,6 +15,7 @@
  *                      same launch writes the stream's NEXT carry, the last min(M - 1, carried + size) bytes of [carry | piece], to
  *                      the stream's other carry buffer, and hands the number of pairs to the host in mapped memory.
  *
+ * The body is seamBlock (scan_passes.h), which the flows call's block kernel shares; the kernel adds the LDS stage and the hand-off.
  * The flush of a stream is the same launch with an empty piece: every carried position, the staged bytes' end the end of the data.
  * Plain C++ and vector stores only.
  */
@@ -26,73 +27,27 @@
 #include <cstdint>
 
 #include "pfac_context.h"
-#include "scan_common.h"
+#include "scan_passes.h"
 
 namespace {
 
 constexpr int kSeamBlock = 1024;
-constexpr int kSeamWaves = kSeamBlock / 64;
 constexpr size_t kSeamLdsBytes = pfac::kStreamSeamLdsBytes;
 
-struct SeamArgs {
-    const unsigned char *carry;                /* `carried` bytes */
-    const unsigned char *piece;                /* `size` bytes (not read when size == 0) */
-    unsigned char *carryNext;                  /* nextCarried bytes are written */
+struct StreamSeamArgs {
+    SeamPiece piece;
     unsigned char *stage;                      /* device scratch of `staged` bytes, or null: LDS */
-    uint32_t carried, head, staged;            /* staged = carried + head, head = min(size, M - 1) */
-    uint32_t numFinal;                         /* start positions [0, numFinal) of the staged bytes are walked, numFinal <= carried */
-    uint32_t nextCarried;
-    uint32_t fold;                             /* a caseless set: the piece's bytes are folded where they are staged or carried on */
-    size_t size;
     int *ids, *pos;
     unsigned int *hostCount;                   /* mapped host memory: [0] the number of pairs, [1] seq, written behind it */
     unsigned int seq;
 };
 
-__device__ __forceinline__ unsigned char seamFold(unsigned char b, uint32_t fold) { return (unsigned char)(b + ((fold != 0 && (unsigned)(b - 'A') < 26u) ? 32 : 0)); }
-
-__global__ __launch_bounds__(kSeamBlock) void pfac_stream_seam(ScanArgs a, SeamArgs s)
+__global__ __launch_bounds__(kSeamBlock) void pfac_stream_seam(ScanArgs a, StreamSeamArgs s)
 {
     __shared__ __attribute__((aligned(16))) unsigned char ldsStage[kSeamLdsBytes];
-    __shared__ uint32_t waveCount[kSeamWaves];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    unsigned char *stage = s.stage != nullptr ? s.stage : ldsStage;
-
-    for (uint32_t i = tid; i < s.staged; i += kSeamBlock)
-        stage[i] = i < s.carried ? s.carry[i] : seamFold(s.piece[i - s.carried], s.fold);
-    /* the next carry: the last nextCarried bytes of [carry | piece] */
-    const size_t all = (size_t)s.carried + s.size;
-    for (uint32_t i = tid; i < s.nextCarried; i += kSeamBlock) {
-        const size_t j = all - s.nextCarried + i;
-        s.carryNext[i] = j < s.carried ? s.carry[j] : seamFold(s.piece[j - s.carried], s.fold);
-    }
-    __threadfence_block();
-    __syncthreads();
-
-    const ChainCtx<false> ctx(a);
-    uint32_t written = 0;                      /* the same in every thread */
-    for (uint32_t base = 0; base < s.numFinal; base += kSeamBlock) {
-        const uint32_t p = base + tid;
-        const int m = p < s.numFinal ? boundedWalk<false>(ctx, stage, p, s.staged) : 0;
-        const uint64_t hits = __ballot(m > 0);
-        if (lane == 0) waveCount[wave] = (uint32_t)__popcll(hits);
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kSeamWaves; w++) {
-            const uint32_t cnt = waveCount[w];
-            before += (uint32_t)w < wave ? cnt : 0u;
-            total += cnt;
-        }
-        if (m > 0) {
-            const uint32_t at = written + before + laneRankIn(hits);
-            s.ids[at] = m;
-            s.pos[at] = (int)p - (int)s.carried;
-        }
-        written += total;
-        __syncthreads();                       /* waveCount is rewritten by the next trip */
-    }
-    if (tid == 0) {
+    __shared__ uint32_t waveCount[kSeamBlock / 64];
+    const uint32_t written = seamBlock<kSeamBlock>(a, s.piece, s.stage != nullptr ? s.stage : ldsStage, s.ids, s.pos, waveCount);
+    if (threadIdx.x == 0) {
         __hip_atomic_store(s.hostCount, written, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(s.hostCount + 1, s.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
@@ -110,7 +65,7 @@ PFAC_status_t PFACX_streamSeam(PFAC_handle_t handle, const char *d_carry, size_t
     if (!h_count || !d_carryNext || (carried && !d_carry) || (size && !d_piece) || (numFinal && (!d_ids || !d_pos))) return PFAC_STATUS_INVALID_PARAMETER;
     const size_t M = (size_t)c->fa.maxPatternLen;
     if (M == 0 || carried > M - 1 || numFinal > carried) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!c->tables.chainSlots || c->chainJumpLog2 <= 0 || !c->d_modeHint || !c->h_modeHint) return PFAC_STATUS_INTERNAL_ERROR;
+    if (!c->tables.chainSlots || c->chainJumpLog2 <= 0 || !hostMapped(c)) return PFAC_STATUS_INTERNAL_ERROR;
     const size_t head = size < M - 1 ? size : M - 1;
     const size_t staged = carried + head;
     if (staged > kSeamLdsBytes && !d_stage) return PFAC_STATUS_INVALID_PARAMETER;
@@ -118,33 +73,30 @@ PFAC_status_t PFACX_streamSeam(PFAC_handle_t handle, const char *d_carry, size_t
     ScanArgs a = ScanArgs{};
     fillChainArgs(c, a);                       /* the walk's view of the chained table (scan_common.h) */
 
-    SeamArgs s;
+    StreamSeamArgs args;
+    SeamPiece &s = args.piece;
     s.carry = reinterpret_cast<const unsigned char *>(d_carry);
     s.piece = reinterpret_cast<const unsigned char *>(d_piece);
     s.carryNext = reinterpret_cast<unsigned char *>(d_carryNext);
-    s.stage = staged > kSeamLdsBytes ? reinterpret_cast<unsigned char *>(d_stage) : nullptr;
     s.carried = (uint32_t)carried;
-    s.head = (uint32_t)head;
     s.staged = (uint32_t)staged;
     s.numFinal = (uint32_t)numFinal;
     const size_t all = carried + size;
     s.nextCarried = (uint32_t)(all < M - 1 ? all : M - 1);
     s.fold = c->caseInsensitive ? 1u : 0u;
     s.size = size;
-    s.ids = d_ids;
-    s.pos = d_pos;
-    s.hostCount = c->d_modeHint + pfac::kHostSeamCountWord;
-    c->seamSeq = c->seamSeq + 1u ? c->seamSeq + 1u : 1u;
-    s.seq = c->seamSeq;
+    args.stage = staged > kSeamLdsBytes ? reinterpret_cast<unsigned char *>(d_stage) : nullptr;
+    args.ids = d_ids;
+    args.pos = d_pos;
 
-    volatile unsigned int *hostCount = c->h_modeHint + pfac::kHostSeamCountWord, *hostDone = hostCount + 1;
-    hipLaunchKernelGGL(pfac_stream_seam, dim3(1), dim3(kSeamBlock), 0, 0, a, s);
-    if (hipGetLastError() != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
-    /* the launch writes its number into host memory behind the count: polled for a while, like the compacted-output call's (scan_module.hip) */
-    const HostWait w = waitHostSeq(hostDone, s.seq);
-    if (w == HostWait::SyncFailed || (w == HostWait::Synced && __atomic_load_n(const_cast<unsigned int *>(hostDone), __ATOMIC_ACQUIRE) != s.seq))
-        return PFAC_STATUS_INTERNAL_ERROR;
-    const unsigned int count = *hostCount;
+    /* the launch itself stores the count and, behind it, the call's number */
+    static_assert(pfac::kHostSeam.done == pfac::kHostSeam.value + 1, "pfac_stream_seam stores the two words side by side");
+    const HostHandoff pairs(c, pfac::kHostSeam);
+    args.hostCount = pairs.d_value;
+    args.seq = pairs.seq;
+    hipLaunchKernelGGL(pfac_stream_seam, dim3(1), dim3(kSeamBlock), 0, 0, a, args);
+    if (!pairs.wait()) return PFAC_STATUS_INTERNAL_ERROR;
+    const unsigned int count = *pairs.h_value;
     if (count > numFinal) return PFAC_STATUS_INTERNAL_ERROR;
     *h_count = (int)count;
     return PFAC_STATUS_SUCCESS;

@@ -104,8 +104,8 @@ StreamSplit streamSplitOf(size_t carried, size_t size, size_t M)
 }
 
 /* the longest match at positions [0, owned) of `readable` host bytes as (id, position + posShift) pairs behind ids / pos; CPU platforms
- * (the caller holds c->lock: the tables first, then the match that needs no lock of its own) */
-PFAC_status_t streamCpuPairs(PFAC_context *c, const char *in, size_t owned, size_t readable, int posShift, int *scratch, int *ids, int *pos, int *count)
+ * (the caller holds c->lock: the tables first, then the match that needs no lock of its own; scratch: `readable` ints) */
+static PFAC_status_t streamCpuPairs(PFAC_context *c, const char *in, size_t owned, size_t readable, int posShift, int *scratch, int *ids, int *pos, int *count)
 {
     PFAC_status_t st = prepareCpuPlatformLocked(c);
     if (st == PFAC_STATUS_SUCCESS) st = matchHostOnCpuPlatformPrepared(c, in, readable, scratch);
@@ -115,13 +115,53 @@ PFAC_status_t streamCpuPairs(PFAC_context *c, const char *in, size_t owned, size
 }
 
 /* ... on the GPU platform (the caller holds c->lock): the pipelined host path, positions [0, owned), the rest read-ahead */
-PFAC_status_t streamGpuPairs(PFAC_context *c, char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count)
+static PFAC_status_t streamGpuPairs(PFAC_context *c, char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count)
 {
     int n = 0;
     const PFAC_status_t st = matchHostReduceOnGpu(c, in, owned, readable, 0, ids, pos, &n);
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (posShift) for (int k = 0; k < n; k++) pos[k] += posShift;
     *count = n;
+    return PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t hostPiece(PFAC_context *c, const unsigned char *carry, size_t carried, char *piece, size_t size, bool flush, int *ids, int *pos,
+                        std::vector<int> &scratch, std::vector<unsigned char> &next, int *count)
+{
+    const size_t M = (size_t)c->fa.maxPatternLen;
+    const bool gpu = c->platform == PFAC_PLATFORM_GPU;
+    StreamSplit sp = streamSplitOf(carried, size, M);
+    if (flush) { sp.seam = carried; sp.owned = 0; }
+    const size_t head = std::min(size, M - 1);
+    int seamPairs = 0, piecePairs = 0;
+    PFAC_status_t st = PFAC_STATUS_SUCCESS;
+    if (sp.seam) {
+        std::vector<unsigned char> seam(carried + head);
+        std::memcpy(seam.data(), carry, carried);
+        if (head) std::memcpy(seam.data() + carried, piece, head);
+        if (gpu) {
+            st = streamGpuPairs(c, reinterpret_cast<char *>(seam.data()), sp.seam, seam.size(), -(int)carried, ids, pos, &seamPairs);
+        } else {
+            if (scratch.size() < seam.size()) scratch.resize(seam.size());
+            st = streamCpuPairs(c, reinterpret_cast<const char *>(seam.data()), sp.seam, seam.size(), -(int)carried, scratch.data(), ids, pos, &seamPairs);
+        }
+        if (st != PFAC_STATUS_SUCCESS) return st;
+    }
+    if (sp.owned) {
+        if (gpu) {
+            st = streamGpuPairs(c, piece, sp.owned, size, 0, ids + seamPairs, pos + seamPairs, &piecePairs);
+        } else {
+            if (scratch.size() < size) scratch.resize(size);
+            st = streamCpuPairs(c, piece, sp.owned, size, 0, scratch.data(), ids + seamPairs, pos + seamPairs, &piecePairs);
+        }
+        if (st != PFAC_STATUS_SUCCESS) return st;
+    }
+    const size_t nextCarried = flush ? 0 : std::min(M - 1, carried + size);
+    next.resize(nextCarried);
+    const size_t fromPiece = std::min(nextCarried, size);
+    if (nextCarried > fromPiece) std::memcpy(next.data(), carry + (carried - (nextCarried - fromPiece)), nextCarried - fromPiece);
+    if (fromPiece) std::memcpy(next.data() + (nextCarried - fromPiece), piece + (size - fromPiece), fromPiece);
+    *count = seamPairs + piecePairs;
     return PFAC_STATUS_SUCCESS;
 }
 
@@ -246,49 +286,16 @@ PFAC_status_t PFACX_streamMatchFromHost(PFACX_stream_t stream, char *h_piece, si
     if (stream->kind == 2) return PFAC_STATUS_INVALID_PARAMETER;           /* a device-fed stream */
     const bool gpu = c->platform == PFAC_PLATFORM_GPU;
     if (gpu && (!c->hasDevice || !c->module)) return PFAC_STATUS_LIB_NOT_EXIST;
-    const size_t carried = stream->carried;
-    const Split sp = streamSplitOf(carried, size, M);
-    const size_t head = std::min(size, M - 1);
-    int seamPairs = 0, piecePairs = 0;
+    int pairs = 0;
     try {
         std::vector<unsigned char> next;                       /* the stream changes when the whole call has succeeded */
-        std::vector<int> seamIds, seamPos;
-        if (sp.seam) {
-            std::vector<unsigned char> seam(carried + head);
-            std::memcpy(seam.data(), stream->h_carry.data(), carried);
-            std::memcpy(seam.data() + carried, h_piece, head);
-            seamIds.resize(sp.seam);
-            seamPos.resize(sp.seam);
-            if (gpu) {
-                st = streamGpuPairs(c, reinterpret_cast<char *>(seam.data()), sp.seam, seam.size(), -(int)carried, seamIds.data(), seamPos.data(), &seamPairs);
-            } else {
-                std::vector<int> scratch(seam.size());
-                st = streamCpuPairs(c, reinterpret_cast<const char *>(seam.data()), sp.seam, seam.size(), -(int)carried, scratch.data(), seamIds.data(),
-                              seamPos.data(), &seamPairs);
-            }
-            if (st != PFAC_STATUS_SUCCESS) return st;
-        }
-        if (sp.owned) {
-            if (gpu) {
-                st = streamGpuPairs(c, h_piece, sp.owned, size, 0, h_ids + seamPairs, h_pos + seamPairs, &piecePairs);
-            } else {
-                /* every position's longest match into the caller's array behind the room of the seam's pairs (capacity >= size + M),
-                 * compacted forward in place: pair z comes from an entry at or behind M - 1 + z */
-                int *scratch = h_ids + (M - 1);
-                st = streamCpuPairs(c, h_piece, sp.owned, size, 0, scratch, h_ids + seamPairs, h_pos + seamPairs, &piecePairs);
-            }
-            if (st != PFAC_STATUS_SUCCESS) return st;
-        }
-        for (int k = 0; k < seamPairs; k++) { h_ids[k] = seamIds[(size_t)k]; h_pos[k] = seamPos[(size_t)k]; }
-        const size_t nextCarried = std::min(M - 1, carried + size);
-        next.resize(nextCarried);
-        const size_t fromPiece = std::min(nextCarried, size);
-        if (nextCarried > fromPiece) std::memcpy(next.data(), stream->h_carry.data() + (carried - (nextCarried - fromPiece)), nextCarried - fromPiece);
-        std::memcpy(next.data() + (nextCarried - fromPiece), h_piece + (size - fromPiece), fromPiece);
+        std::vector<int> scratch;
+        st = hostPiece(c, stream->h_carry.data(), stream->carried, h_piece, size, false, h_ids, h_pos, scratch, next, &pairs);
+        if (st != PFAC_STATUS_SUCCESS) return st;
         stream->h_carry.swap(next);
-        stream->carried = nextCarried;
+        stream->carried = stream->h_carry.size();
     } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
-    *h_num_matched = seamPairs + piecePairs;
+    *h_num_matched = pairs;
     *h_pieceOffset = stream->total;
     stream->kind = 1;
     stream->total += size;
@@ -314,14 +321,11 @@ PFAC_status_t PFACX_streamFlush(PFACX_stream_t stream, int *ids, int *pos, size_
                                 &pairs);
         if (st != PFAC_STATUS_SUCCESS) return st;
     } else if (carried && stream->kind == 1) {
+        if (c->platform == PFAC_PLATFORM_GPU && (!c->hasDevice || !c->module)) return PFAC_STATUS_LIB_NOT_EXIST;
         try {
-            if (c->platform == PFAC_PLATFORM_GPU) {
-                if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
-                st = streamGpuPairs(c, reinterpret_cast<char *>(stream->h_carry.data()), carried, carried, -(int)carried, ids, pos, &pairs);
-            } else {
-                std::vector<int> scratch(carried);
-                st = streamCpuPairs(c, reinterpret_cast<const char *>(stream->h_carry.data()), carried, carried, -(int)carried, scratch.data(), ids, pos, &pairs);
-            }
+            std::vector<unsigned char> none;
+            std::vector<int> scratch;
+            st = hostPiece(c, stream->h_carry.data(), carried, nullptr, 0, true, ids, pos, scratch, none, &pairs);
         } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
         if (st != PFAC_STATUS_SUCCESS) return st;
     }

@@ -9,8 +9,10 @@
  * (d) A/B the kernel variants.  On top of that come the features the reference
  * does not have: batches of segments (PFACX_matchBatch*), every pattern at a
  * position (PFACX_matchAll*), caseless sets (PFACX_READ_NOCASE), streams
- * (PFACX_stream*), flow sets (PFACX_flows*) and the lines that contain a
- * pattern (PFACX_matchLines*, PFACX_gatherLinesFromDevice).
+ * (PFACX_stream*), flow sets (PFACX_flows*), the lines that contain a
+ * pattern (PFACX_matchLines*, PFACX_gatherLinesFromDevice) and the bytes that
+ * belong to a match, with their redaction (PFACX_matchSpans*,
+ * PFACX_redactSpansFromDevice).
  */
 #ifndef PFAC_EXT_H_
 #define PFAC_EXT_H_
@@ -461,6 +463,48 @@ PFAC_status_t PFACX_matchLinesFromHost  (PFAC_handle_t handle, char *h_input, si
 PFAC_status_t PFACX_gatherLinesFromDevice(PFAC_handle_t handle, const char *d_input, size_t size,
                                           const int *d_lineStart, const int *d_lineLen, size_t numSelected,
                                           char *d_out, size_t outCapacity, size_t *h_outBytes);
+
+/* Spans: the bytes of a buffer that belong to a match -- what grep --color highlights -- and the buffer with those bytes overwritten (redaction).
+ *   COVERED.  Let r be the full result of PFAC_matchFromHost on a CPU platform over the whole buffer of n bytes and len(id) the length of pattern id.
+ *   Byte b is covered if some position p <= b has r[p] > 0 and b < p + len(r[p]).  Every pattern that occurs at p is a prefix of the longest one
+ *   there, so the covered bytes are the union of ALL occurrences of ALL patterns, not only of the longest.  A match always ends inside the buffer: no
+ *   clipping.
+ *   The SPANS are the maximal runs of covered bytes: ascending, disjoint and never adjacent -- matches that touch ("abab" under the pattern "ab") are
+ *   one span.  numSpans <= (n + 1) / 2 <= n: a list of `size` entries is never truncated.
+ *   A caseless handle (PFACX_READ_NOCASE): the spans of the folded set over the folded input; the caller's bytes are never modified, and the redaction
+ *   reads the caller's original bytes.
+ * PFACX_matchSpans*: span i is [spanStart[i], spanStart[i] + spanLen[i]), spanLen[i] >= 1; *h_coveredBytes = the sum of the lengths.  Both counts are
+ * written on every success.  capacity: entries of each array, >= size (smaller: PFAC_STATUS_INVALID_PARAMETER).  The arrays double as the scan's pair
+ * list, as the arrays of every compacted call do: entries below `size` may be overwritten beyond the spans returned; nothing is written at or beyond
+ * capacity.
+ * size >= 2^31 or a null pointer: PFAC_STATUS_INVALID_PARAMETER; no pattern set: PFAC_STATUS_PATTERNS_NOT_READY; size == 0: success, both counts 0,
+ * nothing touched; the device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.
+ * Both calls are synchronous (the counts come to the host) and take the handle's lock.  The device form runs on whatever kernel variant, walker, perf
+ * mode and texture mode the handle selects.  The host form follows PFAC_setPlatform: the CPU platforms, host-only handles included, run on the CPU
+ * matcher plus one sequential running-maximum pass, the list written in place (span i comes from position or pair >= i); the GPU platform runs the
+ * pipelined path of PFAC_matchFromHostReduce and merges on the host.
+ * MEMORY of the device form: grow-only handle scratch proportional to the PAIRS of the scan, not to the input -- with P pairs, S = min(P, (size + 1)
+ * / 2) and B = (P + 511) / 512: 2 x 4 S + 4 B + 4 (B + 1) + 4 B + 4 (B + 1) + 256 bytes, each term rounded up to 256: 8.04 bytes per pair at most,
+ * 4 bytes per input byte when every byte starts a match, nothing when nothing matches -- plus the device copy of the pattern lengths (4 bytes per
+ * pattern, shared with the batch calls): deviceScratchBytes of PFACX_getInfo, freed by PFACX_trim.
+ * COST: the compacted scan WITH its ordering launches, then eight small launches over the pairs; no further pass over the input.
+ *
+ * PFACX_redactSpansFromDevice: d_out[b] = fill for every b < size inside one of the numSpans spans, d_out[b] = d_input[b] for every other.  d_out ==
+ * d_input is allowed (in place: only covered bytes are written); any other overlap of the two ranges: PFAC_STATUS_INVALID_PARAMETER.  numSpans == 0: a
+ * plain copy, or nothing when in place (the span arrays may then be null).  size == 0: success, nothing touched.  Any alignment of d_input and d_out.
+ * The span arrays are DEVICE memory and the caller's contract, like the arrays of the gather call: the kernel clamps every (start, len) to [0, size]
+ * and expects the ascending disjoint list PFACX_matchSpans* returns; any other list gives unspecified text in d_out[0, size), never an access outside
+ * the two buffers.  Asynchronous on the default stream, like PFAC_matchFromDevice: nothing comes back to the host.  Takes the handle's lock; needs no
+ * pattern set and no scratch.  A host-only handle: PFAC_STATUS_LIB_NOT_EXIST. */
+PFAC_status_t PFACX_matchSpansFromDevice(PFAC_handle_t handle, char *d_input, size_t size,
+                                         int *d_spanStart, int *d_spanLen, size_t capacity,
+                                         size_t *h_numSpans, size_t *h_coveredBytes);
+PFAC_status_t PFACX_matchSpansFromHost  (PFAC_handle_t handle, char *h_input, size_t size,
+                                         int *h_spanStart, int *h_spanLen, size_t capacity,
+                                         size_t *h_numSpans, size_t *h_coveredBytes);
+PFAC_status_t PFACX_redactSpansFromDevice(PFAC_handle_t handle, const char *d_input, size_t size,
+                                          const int *d_spanStart, const int *d_spanLen, size_t numSpans,
+                                          unsigned char fill, char *d_out);
 
 #ifdef __cplusplus
 }

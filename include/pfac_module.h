@@ -155,6 +155,21 @@ typedef PFAC_status_t (*PFACX_linesGather_protoType)(PFAC_handle_t, const char *
  * value on an error.  tools/lines_sweep.py reports it next to the fold kernel's rate. */
 double PFACX_linesBitmapProbe(PFAC_handle_t handle, const void *d_in, size_t n, int launches);
 
+/* Covered spans and redaction (no reference counterpart; include/pfac_ext.h: PFACX_matchSpans* / PFACX_redactSpansFromDevice), scan_spans.hip.
+ * PFACX_spansSelect: the maximal runs of bytes of d_scan[0, size) -- 0 < size < 2^31; the caller's bytes, or their folded copy for a caseless set --
+ * that belong to a match.  The scan (PFAC_reduce_kernel, hashed != 0: PFAC_reduce_inplace_kernel, WITH its ordering launches) uses d_spanStart /
+ * d_spanLen (`size` entries at least) as its pair list; the passes behind it work on the pairs alone, through d_patternLen (the pattern lengths by id,
+ * numIds entries) and the handle's spans scratch, and then overwrite the arrays with the spans in ascending order.  Synchronous: *h_numSpans, and
+ * *h_coveredBytes = the sum of the lengths.
+ * PFACX_spansRedact: d_out[b] = fill where b lies in one of the numSpans spans (start, len) -- each clamped to [0, size] --, d_input[b] elsewhere;
+ * d_out == d_input (then only covered bytes are written) or ranges that do not overlap, any alignment of either.  Asynchronous, on the default stream. */
+PFAC_status_t PFACX_spansSelect(PFAC_handle_t handle, char *d_scan, size_t size, int hashed, const int *d_patternLen, size_t numIds, int *d_spanStart,
+                                int *d_spanLen, size_t *h_numSpans, size_t *h_coveredBytes);
+PFAC_status_t PFACX_spansRedact(PFAC_handle_t handle, const char *d_input, size_t size, const int *d_spanStart, const int *d_spanLen, size_t numSpans,
+                                unsigned char fill, char *d_out);
+typedef PFAC_status_t (*PFACX_spansSelect_protoType)(PFAC_handle_t, char *, size_t, int, const int *, size_t, int *, int *, size_t *, size_t *);
+typedef PFAC_status_t (*PFACX_spansRedact_protoType)(PFAC_handle_t, const char *, size_t, const int *, const int *, size_t, unsigned char, char *);
+
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of
  * `launches` launches over the first n bytes (a multiple of 4096) of d_in, or a negative value on a HIP error.

@@ -108,6 +108,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_streamOpen", "PFACX_streamReset", "PFACX_streamClose", "PFACX_streamMatchFromDevice", "PFACX_streamMatchFromHost", "PFACX_streamFlush",
     "PFACX_flowsOpen", "PFACX_flowsClose", "PFACX_flowsReset", "PFACX_flowsMatchFromDevice", "PFACX_flowsMatchFromHost", "PFACX_flowsFlush",
     "PFACX_matchLinesFromDevice", "PFACX_matchLinesFromHost", "PFACX_gatherLinesFromDevice",
+    "PFACX_matchSpansFromDevice", "PFACX_matchSpansFromHost", "PFACX_redactSpansFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -116,6 +117,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_allReduce", "PFACX_allExpand", "PFACX_foldInput",
     "PFACX_streamSeam", "PFACX_streamReduce", "PFACX_flowsRun",
     "PFACX_linesSelect", "PFACX_linesGather", "PFACX_linesBitmapProbe",
+    "PFACX_spansSelect", "PFACX_spansRedact",
 )
 
 
@@ -203,6 +205,12 @@ def load_library() -> C.CDLL:
         lib.PFACX_matchLinesFromDevice.argtypes = lines
         lib.PFACX_matchLinesFromHost.argtypes = lines
         lib.PFACX_gatherLinesFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, SZ]
+    if hasattr(lib, "PFACX_matchSpansFromDevice"):
+        SZ = C.POINTER(C.c_size_t)
+        spans = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, SZ, SZ]
+        lib.PFACX_matchSpansFromDevice.argtypes = spans
+        lib.PFACX_matchSpansFromHost.argtypes = spans
+        lib.PFACX_redactSpansFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_ubyte, C.c_void_p]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -483,6 +491,35 @@ class PFAC:
         _, nl, ns = self.matchLinesFromHost(data.ctypes.data if data.size else start.ctypes.data, data.size, PFACX_LINES_INVERT if invert else 0,
                                             start.ctypes.data, length.ctypes.data, index.ctypes.data, cap)
         return nl, start[:ns].copy(), length[:ns].copy(), index[:ns].copy()
+
+    # -- the bytes that belong to a match, and their redaction (include/pfac_ext.h: PFACX_matchSpans*) ------------
+    def matchSpansFromDevice(self, d_input: int, size: int, d_span_start: int, d_span_len: int, capacity: int, check: bool = True):
+        """``PFACX_matchSpansFromDevice`` -> (status, number of spans, covered bytes)."""
+        ns, cb = C.c_size_t(0), C.c_size_t(0)
+        st = self._lib.PFACX_matchSpansFromDevice(self._h, d_input, size, d_span_start, d_span_len, capacity, C.byref(ns), C.byref(cb))
+        return self._ret(st, "PFACX_matchSpansFromDevice", check), ns.value, cb.value
+
+    def matchSpansFromHost(self, h_input: int, size: int, h_span_start: int, h_span_len: int, capacity: int, check: bool = True):
+        """``PFACX_matchSpansFromHost`` -> (status, number of spans, covered bytes); follows PFAC_setPlatform."""
+        ns, cb = C.c_size_t(0), C.c_size_t(0)
+        st = self._lib.PFACX_matchSpansFromHost(self._h, h_input, size, h_span_start, h_span_len, capacity, C.byref(ns), C.byref(cb))
+        return self._ret(st, "PFACX_matchSpansFromHost", check), ns.value, cb.value
+
+    def redactSpansFromDevice(self, d_input: int, size: int, d_span_start, d_span_len, num_spans: int, fill: int, d_out: int,
+                              check: bool = True) -> int:
+        """``PFACX_redactSpansFromDevice``: asynchronous on the default stream; ``d_out == d_input`` redacts in place."""
+        return self._ret(self._lib.PFACX_redactSpansFromDevice(self._h, d_input, size, d_span_start, d_span_len, num_spans, fill & 0xFF, d_out),
+                         "PFACX_redactSpansFromDevice", check)
+
+    def match_spans_host_array(self, data):
+        """matchSpansFromHost over a numpy array -> (span_start, span_len, covered bytes), ascending."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        cap = max(1, data.size)
+        start = np.full(cap, -7, dtype=np.int32)
+        length = np.full(cap, -7, dtype=np.int32)
+        _, ns, cb = self.matchSpansFromHost(data.ctypes.data if data.size else start.ctypes.data, data.size, start.ctypes.data, length.ctypes.data, cap)
+        return start[:ns].copy(), length[:ns].copy(), cb
 
     # -- input that arrives in pieces (include/pfac_ext.h: PFACX_stream*) ----------------
     def streamOpen(self, check: bool = True) -> "Stream":

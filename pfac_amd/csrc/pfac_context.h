@@ -61,6 +61,7 @@ constexpr HostSlot kHostSeam = {12, 13};          /* a stream call: the pairs of
 constexpr HostSlot kHostFlows = {14, 15};         /* a flows call: its pairs (scan_flows.hip: pfac_flows_done stores both words) */
 constexpr HostSlot kHostLines = {16, 18};         /* a lines call: the lines, then the selected lines (scan_lines.hip: pfac_lines_block_scan) */
 constexpr HostSlot kHostGather = {20, 22};        /* a gather: the 64-bit size of its text (scan_lines.hip) */
+constexpr HostSlot kHostSpans = {24, 26};         /* a spans call: one 64-bit value, the spans | the covered bytes << 32 (scan_spans.hip: pfac_spans_finish) */
 constexpr int kHostWords = 32;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
@@ -401,11 +402,16 @@ struct DeviceScratch {
      * the per-word ranks and the per-block counts (a fixed function of the input size: scan_lines.hip has the formula), or into the offsets of a gather;
      * not allocated before the first lines call */
     DeviceBuffer<char> lines;
+    /* the spans calls (PFACX_matchSpans*, scan_spans.hip): ONE allocation a call cuts into the starts and ends of the spans and the per-block values of
+     * its pair-space passes -- 8.04 bytes per pair of the scan at most (scan_spans.hip has the formula); not allocated before the first spans call that
+     * finds a pair */
+    DeviceBuffer<char> spans;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines);
+        f(spans);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }
@@ -481,6 +487,8 @@ struct PFAC_context {
     PFACX_flowsRun_protoType flows_run_ptr = nullptr;                /* scan_flows.hip: the seams and the merge of a flows call (PFACX_flows*) */
     PFACX_linesSelect_protoType lines_select_ptr = nullptr;          /* scan_lines.hip: the lines calls (PFACX_matchLines* / PFACX_gatherLines*) */
     PFACX_linesGather_protoType lines_gather_ptr = nullptr;
+    PFACX_spansSelect_protoType spans_select_ptr = nullptr;          /* scan_spans.hip: the spans calls (PFACX_matchSpans* / PFACX_redactSpansFromDevice) */
+    PFACX_spansRedact_protoType spans_redact_ptr = nullptr;
 
     int platform = PFAC_PLATFORM_GPU;
     int perfMode = PFAC_TIME_DRIVEN;

@@ -1,6 +1,6 @@
 /*
  * scan_passes.h -- what the passes around the scan share (scan_module.hip with scan_order.inc, scan_batch.hip, scan_all.hip, scan_fold.hip,
- * scan_stream.hip, scan_flows.hip, scan_lines.hip; the product kernels' units do not include it): launch sizes, the hand-off of a call's
+ * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip; the product kernels' units do not include it): launch sizes, the hand-off of a call's
  * result to the host through mapped memory, the device fold byte, block prefix sums, the seam of a stream.  Like scan_common.h, everything is
  * in an unnamed namespace: inline device code, each unit its own copy.
  */

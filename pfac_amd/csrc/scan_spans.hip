@@ -1,0 +1,502 @@
+/*
+ * scan_spans.hip -- covered spans and redaction (include/pfac_ext.h: PFACX_matchSpans* / PFACX_redactSpansFromDevice): the bytes of a
+ * buffer that belong to a match, as maximal runs, and the buffer with those bytes overwritten.
+ *
+ * SELECT works in pair space, behind the compacted scan WITH its ordering launches (the pairs come in position order, one per position: the longest
+ * match there, of which every other pattern at the position is a prefix).  Pair i ends at end_i = pos_i + len(id_i); E_i = max(end_j, j < i), E_0 = 0;
+ * pair i HEADS a span iff i == 0 or pos_i > E_i (pos_i == E_i touches the run in front of it: one span); the span of a head ends at the E of the next
+ * head, the last one at the maximum of all ends.  A BLOCK is 512 pairs, two per thread.
+ *
+ *   pfac_spans_reduce         the largest end of each block of pairs
+ *   pfac_spans_block_scan<1>  the exclusive prefix MAXIMUM of those (what every block carries in from all the blocks in front of it, however far back
+ *                             the largest end lies); a block of 1024 threads per 8192 values that folds what lies in front of its values itself, as
+ *                             pfac_lines_block_scan does: no block waits on another, no chain of steps for the 4 Mi values of 2^31 pairs
+ *   pfac_spans_heads<0>       E_i by a max-scan over the wave (shuffles) and the block, the head flags, the heads of each block
+ *   pfac_spans_block_scan<0>  their exclusive prefix sum: the first span of each block, the number of spans
+ *   pfac_spans_heads<1>       the same walk again: head k writes start_k and end_(k-1) = E_i into handle scratch -- not over the pair list: span k may
+ *                             land on a pair that another block has not read yet
+ *   pfac_spans_emit           (start, len) of the spans over the caller's arrays, the sum of the lengths
+ *   pfac_spans_finish         both counts as one 64-bit value to mapped host memory, then pfac_host_done (scan_passes.h: HostHandoff)
+ * Nothing here touches the input: the work is proportional to the pairs.
+ * SCRATCH of a select call with P pairs, S = min(P, (size + 1) / 2) (no more spans fit the buffer), B = (P + 511) / 512 blocks:
+ * 2 x 4 S (starts and ends) + 4 B + 4 (B + 1) + 4 B + 4 (B + 1) (largest end, heads, and their scans) + 256 bytes, each part rounded up to 256:
+ * 8 bytes per pair and 16 per block: 8.04 bytes per pair at most.  No pairs: none.
+ *
+ * REDACT is cut by OUTPUT tiles of 4 KiB, aligned on the output address: a tile finds the first span that ends behind its first byte and the first that
+ * starts behind its last by a 64-ary search of one wave over the list (a probe per lane and round), stages the spans in between in LDS, 1024 at a time --
+ * an ascending disjoint list has at most 2049 in a tile, so three trips is all a tile ever makes --, and every thread builds the 16-bit cover mask of
+ * its 16 bytes from a binary search in the staged ends, blends and stores them as one aligned 16-byte store.  Source bytes that lie m bytes into an
+ * aligned block come out of two aligned loads with v_alignbyte, as in scan_fold.hip; whatever hangs over an end of either buffer goes byte by byte with
+ * bounds.  Every (start, len) is clamped to [0, size] where it is read: a bad list gives wrong text, never an access outside the buffers.  In place,
+ * only threads that cover something write.  No scratch.  Plain C++ and vector stores only.
+ */
+#if !defined(__gfx950__) && defined(__HIP_DEVICE_COMPILE__)
+#error "scan_spans.hip is written for gfx950 (CDNA4): wave64"
+#endif
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "pfac_context.h"
+#include "scan_passes.h"
+
+namespace {
+
+constexpr unsigned int kSpanThreads = 256;
+constexpr unsigned int kSpanPer = 2;                                   /* consecutive pairs per thread */
+constexpr unsigned int kSpanBlock = kSpanThreads * kSpanPer;           /* 512 pairs per block */
+constexpr unsigned int kScanPer = 8;                                   /* values per thread of pfac_spans_block_scan */
+constexpr unsigned int kTile = 4096;                                   /* output bytes per tile of the redaction */
+constexpr unsigned int kStage = 1024;                                  /* spans a tile stages at a time */
+constexpr unsigned int kStageTrips = 3;                                /* kStage * kStageTrips >= kTile / 2 + 1 */
+static_assert(kStage * kStageTrips >= kTile / 2 + 1, "a tile must be able to stage every span of an ascending disjoint list that meets it");
+
+struct SpanArgs {
+    const int *ids, *pos;               /* the scan's ordered pairs (the caller's arrays) */
+    unsigned int count, n;
+    const int *patternLen;              /* by id, numIds entries */
+    unsigned int numIds;
+    unsigned int blocks;
+    unsigned int bound;                 /* entries of outStart / outEnd */
+    unsigned int *blockMax, *blockTop;  /* [blocks] largest end of the block; [blocks + 1] largest end in front of the block, [blocks] = of all */
+    unsigned int *headCount, *headBase; /* the same for the heads: [blocks] = the number of spans */
+    unsigned int *outStart, *outEnd;    /* [bound] */
+    unsigned int *covered;              /* one word: the sum of the lengths (zeroed by the first block scan) */
+    unsigned long long *value;          /* numSpans | coveredBytes << 32 */
+    int *spanStart, *spanLen;
+};
+
+__device__ __forceinline__ unsigned int umax(unsigned int a, unsigned int b) { return a > b ? a : b; }
+
+/* position and end of pair i, both inside [0, n] whatever the pair says */
+__device__ __forceinline__ void pairOf(const SpanArgs &a, unsigned int i, unsigned int &p, unsigned int &e)
+{
+    const int at = a.pos[i], id = a.ids[i];
+    p = at < 0 ? 0u : ((unsigned int)at > a.n ? a.n : (unsigned int)at);
+    const int len = (unsigned int)id < a.numIds ? a.patternLen[id] : 0;
+    e = len <= 0 ? p : ((unsigned int)len > a.n - p ? a.n : p + (unsigned int)len);
+}
+
+/* inclusive prefix maximum over the 64 lanes */
+__device__ __forceinline__ unsigned int waveInclusiveMax(unsigned int v)
+{
+    const unsigned int lane = threadIdx.x & 63u;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned int up = __shfl_up(v, d);
+        if ((int)lane >= d) v = umax(v, up);
+    }
+    return v;
+}
+
+/* exclusive prefix maximum of `own` over the block's BLOCK threads (0 in front of thread 0), and the block's maximum; waveTop: BLOCK / 64 entries
+ * of LDS, free again at the next call */
+template <unsigned int BLOCK>
+__device__ __forceinline__ unsigned int blockExclusiveMax(unsigned int own, unsigned int *waveTop, unsigned int &top)
+{
+    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned int incl = waveInclusiveMax(own);
+    unsigned int excl = __shfl_up(incl, 1);
+    if (lane == 0) excl = 0;
+    __syncthreads();                                    /* waveTop may still be read from the previous call */
+    if (lane == 63) waveTop[wave] = incl;
+    __syncthreads();
+    unsigned int before = 0;
+    top = 0;
+#pragma unroll
+    for (unsigned int w = 0; w < BLOCK / 64; w++) {
+        const unsigned int s = waveTop[w];
+        before = w < wave ? umax(before, s) : before;
+        top = umax(top, s);
+    }
+    return umax(before, excl);
+}
+
+__global__ __launch_bounds__(kSpanThreads) void pfac_spans_reduce(SpanArgs a)
+{
+    __shared__ unsigned int waveTop[kSpanThreads / 64];
+    const unsigned int i0 = blockIdx.x * kSpanBlock + threadIdx.x * kSpanPer;
+    unsigned int own = 0;
+#pragma unroll
+    for (unsigned int k = 0; k < kSpanPer; k++) {
+        if (i0 + k < a.count) {
+            unsigned int p, e;
+            pairOf(a, i0 + k, p, e);
+            own = umax(own, e);
+        }
+    }
+    unsigned int top = 0;
+    (void)blockExclusiveMax<kSpanThreads>(own, waveTop, top);
+    if (threadIdx.x == 0) a.blockMax[blockIdx.x] = top;
+}
+
+/* out[0, n) = the exclusive prefix of v[0, n) under + (MAX == 0) or max (MAX == 1, values >= 0: 0 in front of the first), out[n] = that of all.  A
+ * block of 1024 threads per 8192 values; block k folds everything in front of its values itself -- coalesced, from L2 -- so no block waits on another.
+ * v and out are different arrays: the blocks read each other's input.  zero (or null): a word block 0 clears for the launches behind it */
+template <int MAX>
+__global__ __launch_bounds__(1024) void pfac_spans_block_scan(const unsigned int *v, unsigned int *out, unsigned int n, unsigned int *zero)
+{
+    __shared__ unsigned int waveOwn[16], waveFront[16];
+    auto op = [](unsigned int x, unsigned int y) { return MAX ? umax(x, y) : x + y; };
+    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned int base = blockIdx.x * 1024u * kScanPer;
+    if (zero != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *zero = 0;
+    unsigned int front = 0;
+    for (unsigned int q = threadIdx.x; q < base / 4u; q += 1024u) {                 /* base is a multiple of 8192 */
+        const pfacmod::u32x4 c = reinterpret_cast<const pfacmod::u32x4 *>(v)[q];
+        front = op(front, op(op(c.x, c.y), op(c.z, c.w)));
+    }
+    const unsigned int i0 = base + threadIdx.x * kScanPer;
+    unsigned int x[kScanPer], own = 0;
+#pragma unroll
+    for (unsigned int k = 0; k < kScanPer; k++) {
+        x[k] = i0 + k < n ? v[i0 + k] : 0u;
+        own = op(own, x[k]);
+    }
+    unsigned int incl = own;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned int up = __shfl_up(incl, d);
+        if ((int)lane >= d) incl = op(incl, up);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) front = op(front, __shfl_xor(front, d));
+    unsigned int excl = __shfl_up(incl, 1);
+    if (lane == 0) excl = 0;
+    if (lane == 63) { waveOwn[wave] = incl; waveFront[wave] = front; }
+    __syncthreads();
+    unsigned int before = 0;
+    for (unsigned int w = 0; w < 16; w++) {
+        before = op(before, waveFront[w]);
+        if (w < wave) before = op(before, waveOwn[w]);
+    }
+    unsigned int run = op(before, excl);
+#pragma unroll
+    for (unsigned int k = 0; k < kScanPer; k++) {
+        if (i0 + k < n) out[i0 + k] = run;
+        run = op(run, x[k]);
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 1023) out[n] = run;            /* the last thread of the last block has seen everything */
+}
+
+/* WRITE == 0: the heads of each block; WRITE == 1: start of span k, end of span k - 1 */
+template <int WRITE>
+__global__ __launch_bounds__(kSpanThreads) void pfac_spans_heads(SpanArgs a)
+{
+    __shared__ unsigned int waveTop[kSpanThreads / 64];
+    __shared__ unsigned int waveSum[kSpanThreads / 64];
+    const unsigned int i0 = blockIdx.x * kSpanBlock + threadIdx.x * kSpanPer;
+    unsigned int p[kSpanPer], e[kSpanPer], own = 0;
+#pragma unroll
+    for (unsigned int k = 0; k < kSpanPer; k++) {
+        p[k] = 0;
+        e[k] = 0;
+        if (i0 + k < a.count) pairOf(a, i0 + k, p[k], e[k]);
+        own = umax(own, e[k]);
+    }
+    unsigned int top = 0;
+    const unsigned int carried = umax(a.blockTop[blockIdx.x], blockExclusiveMax<kSpanThreads>(own, waveTop, top));      /* E of the thread's first pair */
+    unsigned int run = carried, heads = 0;
+#pragma unroll
+    for (unsigned int k = 0; k < kSpanPer; k++) {
+        if (i0 + k < a.count && (i0 + k == 0 || p[k] > run)) heads |= 1u << k;
+        run = umax(run, e[k]);
+    }
+    const unsigned int nh = (unsigned int)__popc(heads);
+    unsigned int total = 0;
+    const unsigned int rank = blockExclusive<kSpanThreads>(nh, waveSum, total);
+    if constexpr (WRITE == 0) {
+        if (threadIdx.x == 0) a.headCount[blockIdx.x] = total;
+    } else {
+        unsigned int o = a.headBase[blockIdx.x] + rank;
+        run = carried;
+#pragma unroll
+        for (unsigned int k = 0; k < kSpanPer; k++) {
+            if ((heads >> k) & 1u) {
+                if (o < a.bound) a.outStart[o] = p[k];
+                if (o > 0 && o - 1 < a.bound) a.outEnd[o - 1] = run;
+                o++;
+            }
+            run = umax(run, e[k]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kSpanThreads) void pfac_spans_emit(SpanArgs a)
+{
+    __shared__ unsigned int waveSum[kSpanThreads / 64];
+    const unsigned int all = a.headBase[a.blocks], spans = all < a.bound ? all : a.bound;
+    const unsigned int last = a.blockTop[a.blocks];
+    unsigned int own = 0;
+    for (unsigned int k = blockIdx.x * kSpanThreads + threadIdx.x; k < spans; k += gridDim.x * kSpanThreads) {
+        const unsigned int s = a.outStart[k], e = k + 1 == spans ? last : a.outEnd[k];
+        const unsigned int len = e > s ? e - s : 0u;
+        a.spanStart[k] = (int)s;
+        a.spanLen[k] = (int)len;
+        own += len;
+    }
+    unsigned int total = 0;
+    (void)blockExclusive<kSpanThreads>(own, waveSum, total);
+    if (threadIdx.x == 0 && total != 0) atomicAdd(a.covered, total);
+}
+
+__global__ void pfac_spans_finish(SpanArgs a, unsigned long long *hostValue)
+{
+    const unsigned int all = a.headBase[a.blocks], spans = all < a.bound ? all : a.bound;
+    const unsigned long long v = (unsigned long long)spans | (unsigned long long)*a.covered << 32;
+    *a.value = v;
+    if (hostValue != nullptr) {
+        __hip_atomic_store(hostValue, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __threadfence_system();
+    }
+}
+
+/* ------------------------------------------------------------------ the redaction */
+
+struct RedactArgs {
+    const unsigned char *in;
+    unsigned char *out;
+    unsigned int n;
+    const int *start, *len;             /* the caller's spans: clamped, never trusted */
+    unsigned int count;
+    uint32_t fill4;                     /* the fill byte four times */
+    unsigned int misOut;                /* address of out & 15 */
+    unsigned int inPlace;
+};
+
+__device__ __forceinline__ unsigned int spanStartOf(const RedactArgs &a, unsigned int i)
+{
+    const int s = a.start[i];
+    return s < 0 ? 0u : ((unsigned int)s > a.n ? a.n : (unsigned int)s);
+}
+__device__ __forceinline__ unsigned int spanEndOf(const RedactArgs &a, unsigned int i)
+{
+    const unsigned int s = spanStartOf(a, i);
+    const int l = a.len[i];
+    return l <= 0 ? s : ((unsigned int)l > a.n - s ? a.n : s + (unsigned int)l);
+}
+
+/* the first i of [lo, hi) with pred(i), hi if there is none, for a pred that is false, then true (any other pred: some index of [lo, hi]); the
+ * whole wave calls it and gets the same answer: a probe per lane and round, the range shrinks 65-fold a round */
+template <class P>
+__device__ __forceinline__ unsigned int waveLowerBound(unsigned int lo, unsigned int hi, P pred)
+{
+    const unsigned int lane = threadIdx.x & 63u;
+    while (hi - lo > 64u) {
+        const unsigned long long width = hi - lo;
+        const unsigned int at = lo + (unsigned int)(width * (lane + 1u) / 65u);                  /* ascending, distinct, inside [lo, hi) */
+        const unsigned long long yes = __ballot(pred(at));
+        if (yes == 0) {
+            lo = lo + (unsigned int)(width * 64u / 65u) + 1u;
+        } else {
+            const unsigned int f = (unsigned int)__ffsll((long long)yes) - 1u;
+            hi = lo + (unsigned int)(width * (f + 1u) / 65u);
+            if (f > 0) lo = lo + (unsigned int)(width * f / 65u) + 1u;
+        }
+    }
+    const unsigned long long yes = __ballot(lane < hi - lo && pred(lo + lane));
+    return yes == 0 ? hi : lo + (unsigned int)__ffsll((long long)yes) - 1u;
+}
+
+/* 16 bytes starting m = 4 Q + r bytes into the 32 of a | b (scan_fold.hip) */
+template <int Q>
+__device__ __forceinline__ pfacmod::u32x4 funnel(pfacmod::u32x4 a, pfacmod::u32x4 b, uint32_t r)
+{
+    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    return pfacmod::u32x4{__builtin_amdgcn_alignbyte(w[Q + 1], w[Q], r), __builtin_amdgcn_alignbyte(w[Q + 2], w[Q + 1], r),
+                          __builtin_amdgcn_alignbyte(w[Q + 3], w[Q + 2], r), __builtin_amdgcn_alignbyte(w[Q + 4], w[Q + 3], r)};
+}
+
+/* in[o, o + 16), o + 16 <= n: one aligned load, two and a funnel, or -- where an aligned block would reach outside the buffer -- sixteen bytes */
+__device__ __forceinline__ pfacmod::u32x4 load16(const RedactArgs &a, unsigned int o)
+{
+    const unsigned int m = (unsigned int)(reinterpret_cast<uintptr_t>(a.in + o) & 15u);         /* the same in every thread of a launch */
+    if (m == 0) return __builtin_nontemporal_load(reinterpret_cast<const pfacmod::u32x4 *>(a.in + o));
+    if (o >= m && o - m + 32u <= a.n) {
+        const pfacmod::u32x4 *blk = reinterpret_cast<const pfacmod::u32x4 *>(a.in + o - m);
+        const pfacmod::u32x4 x = __builtin_nontemporal_load(blk), y = __builtin_nontemporal_load(blk + 1);
+        switch (m >> 2) {
+        case 0: return funnel<0>(x, y, m & 3u);
+        case 1: return funnel<1>(x, y, m & 3u);
+        case 2: return funnel<2>(x, y, m & 3u);
+        default: return funnel<3>(x, y, m & 3u);
+        }
+    }
+    uint32_t w[4];
+#pragma unroll
+    for (int d = 0; d < 4; d++)
+        w[d] = (uint32_t)a.in[o + 4 * d] | (uint32_t)a.in[o + 4 * d + 1] << 8 | (uint32_t)a.in[o + 4 * d + 2] << 16 | (uint32_t)a.in[o + 4 * d + 3] << 24;
+    return pfacmod::u32x4{w[0], w[1], w[2], w[3]};
+}
+
+/* a nibble of the cover mask as the byte mask of a dword: bit i lands on bit 8 i and nothing carries */
+__device__ __forceinline__ uint32_t byteMask(uint32_t nibble) { return ((nibble * 0x00204081u) & 0x01010101u) * 0xFFu; }
+
+/* tiles are cut in v = o + misOut, the output offset counted from the aligned 16-byte block that holds out[0] */
+__global__ __launch_bounds__(kSpanThreads) void pfac_spans_redact(RedactArgs a)
+{
+    __shared__ unsigned int sStart[kStage], sEnd[kStage];
+    __shared__ unsigned int sFirst, sCount;
+    const unsigned int t = threadIdx.x;
+    const size_t vEnd = (size_t)a.n + a.misOut;
+    for (size_t vLo = (size_t)blockIdx.x * kTile; vLo < vEnd; vLo += (size_t)gridDim.x * kTile) {
+        const unsigned int oLo = vLo > a.misOut ? (unsigned int)(vLo - a.misOut) : 0u;
+        const unsigned int oHi = vLo + kTile - a.misOut < a.n ? (unsigned int)(vLo + kTile - a.misOut) : a.n;
+        if (t < 64u) {
+            /* the first span that ends behind oLo, and the first behind it that starts at or behind oHi */
+            const unsigned int first = waveLowerBound(0u, a.count, [&](unsigned int i) { return spanEndOf(a, i) > oLo; });
+            const unsigned int limit = a.count - first < kStage * kStageTrips ? a.count : first + kStage * kStageTrips;
+            const unsigned int behind = waveLowerBound(first, limit, [&](unsigned int i) { return spanStartOf(a, i) >= oHi; });
+            if (t == 0) { sFirst = first; sCount = behind - first; }
+        }
+        __syncthreads();
+        const unsigned int first = sFirst, total = sCount;
+        const size_t v0 = vLo + (size_t)t * 16;
+        const unsigned int cLo = v0 > a.misOut ? (unsigned int)(v0 - a.misOut) : 0u;
+        unsigned int cHi = v0 + 16 > a.misOut ? (unsigned int)(v0 + 16 - a.misOut < oHi ? v0 + 16 - a.misOut : oHi) : 0u;
+        const bool active = cLo < cHi;
+        uint32_t mask = 0;                                        /* bit j: byte cLo + j is covered */
+        for (unsigned int base = 0; base < total; base += kStage) {
+            const unsigned int cnt = total - base < kStage ? total - base : kStage;
+            if (base != 0) __syncthreads();                       /* the stage is rewritten */
+            for (unsigned int j = t; j < cnt; j += kSpanThreads) {
+                sStart[j] = spanStartOf(a, first + base + j);
+                sEnd[j] = spanEndOf(a, first + base + j);
+            }
+            __syncthreads();
+            if (active) {
+                unsigned int lo = 0, hi = cnt;                    /* the first staged span that ends behind cLo */
+                while (lo < hi) {
+                    const unsigned int mid = (lo + hi) / 2;
+                    if (sEnd[mid] > cLo) hi = mid; else lo = mid + 1;
+                }
+                for (unsigned int j = lo; j < cnt && sStart[j] < cHi; j++) {
+                    const unsigned int s = sStart[j] > cLo ? sStart[j] - cLo : 0u;
+                    const unsigned int e = (sEnd[j] < cHi ? sEnd[j] : cHi) - cLo;
+                    if (sEnd[j] > cLo && e > s) mask |= ((1u << e) - 1u) & ~((1u << s) - 1u);
+                }
+            }
+        }
+        if (active) {
+            if (cHi - cLo == 16u && v0 >= a.misOut) {
+                pfacmod::u32x4 *dst = reinterpret_cast<pfacmod::u32x4 *>(a.out + cLo);
+                const pfacmod::u32x4 fill = {a.fill4, a.fill4, a.fill4, a.fill4};
+                if (mask == 0xFFFFu) {
+                    __builtin_nontemporal_store(fill, dst);
+                } else if (!a.inPlace || mask != 0) {
+                    const pfacmod::u32x4 x = a.inPlace ? *dst : load16(a, cLo);
+                    const pfacmod::u32x4 m = {byteMask(mask & 15u), byteMask((mask >> 4) & 15u), byteMask((mask >> 8) & 15u), byteMask(mask >> 12)};
+                    __builtin_nontemporal_store((x & ~m) | (fill & m), dst);
+                }
+            } else {
+                for (unsigned int o = cLo; o < cHi; o++) {
+                    if ((mask >> (o - cLo)) & 1u) a.out[o] = (unsigned char)a.fill4;
+                    else if (!a.inPlace) a.out[o] = a.in[o];
+                }
+            }
+        }
+        __syncthreads();                                          /* sFirst and the stage are rewritten by the next tile */
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+PFAC_status_t PFACX_spansSelect(PFAC_handle_t handle, char *d_scan, size_t size, int hashed, const int *d_patternLen, size_t numIds, int *d_spanStart,
+                                int *d_spanLen, size_t *h_numSpans, size_t *h_coveredBytes)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!d_scan || !d_patternLen || !d_spanStart || !d_spanLen || !h_numSpans || !h_coveredBytes || size == 0 || size > (size_t)0x7fffffff)
+        return PFAC_STATUS_INVALID_PARAMETER;
+    PFAC_context *c = handle;
+
+    /* the compacted scan with its ordering launches: ids in d_spanStart, positions in d_spanLen, ascending */
+    int count = 0;
+    const bool wasUnordered = c->reduceUnordered;
+    c->reduceUnordered = false;
+    const PFAC_status_t st = hashed ? PFAC_reduce_inplace_kernel(handle, reinterpret_cast<int *>(d_scan), (int)size, d_spanStart, d_spanLen, &count, nullptr, nullptr)
+                                    : PFAC_reduce_kernel(handle, reinterpret_cast<int *>(d_scan), (int)size, d_spanStart, d_spanLen, &count, nullptr, nullptr);
+    c->reduceUnordered = wasUnordered;
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
+    *h_numSpans = 0;
+    *h_coveredBytes = 0;
+    if (count == 0) return PFAC_STATUS_SUCCESS;
+
+    SpanArgs a{};
+    a.ids = d_spanStart;
+    a.pos = d_spanLen;
+    a.count = (unsigned int)count;
+    a.n = (unsigned int)size;
+    a.patternLen = d_patternLen;
+    a.numIds = (unsigned int)(numIds < (size_t)0x7fffffff ? numIds : (size_t)0x7fffffff);
+    const size_t blocks = ((size_t)count + kSpanBlock - 1) / kSpanBlock;
+    const size_t bound = (size_t)count < (size + 1) / 2 ? (size_t)count : (size + 1) / 2;
+    a.blocks = (unsigned int)blocks;
+    a.bound = (unsigned int)bound;
+    const size_t oStart = 0, oEnd = oStart + round256(bound * 4), oMax = oEnd + round256(bound * 4), oTop = oMax + round256(blocks * 4),
+                 oCount = oTop + round256((blocks + 1) * 4), oBase = oCount + round256(blocks * 4), oValue = oBase + round256((blocks + 1) * 4),
+                 bytes = oValue + 256;
+    if (c->scratch.spans.count() < bytes && c->scratch.spans.reserve(bytes) != PFAC_STATUS_SUCCESS) return PFAC_STATUS_CUDA_ALLOC_FAILED;
+    char *s = c->scratch.spans.get();
+    a.outStart = reinterpret_cast<unsigned int *>(s + oStart);
+    a.outEnd = reinterpret_cast<unsigned int *>(s + oEnd);
+    a.blockMax = reinterpret_cast<unsigned int *>(s + oMax);
+    a.blockTop = reinterpret_cast<unsigned int *>(s + oTop);
+    a.headCount = reinterpret_cast<unsigned int *>(s + oCount);
+    a.headBase = reinterpret_cast<unsigned int *>(s + oBase);
+    a.value = reinterpret_cast<unsigned long long *>(s + oValue);
+    a.covered = reinterpret_cast<unsigned int *>(s + oValue + 8);
+    a.spanStart = d_spanStart;
+    a.spanLen = d_spanLen;
+    const bool mapped = hostMapped(c);
+    const HostHandoff counts = mapped ? HostHandoff(c, pfac::kHostSpans) : HostHandoff();
+    const unsigned int scanGrid = (a.blocks + 1024u * kScanPer - 1u) / (1024u * kScanPer);
+
+    hipLaunchKernelGGL(pfac_spans_reduce, dim3(a.blocks), dim3(kSpanThreads), 0, 0, a);
+    hipLaunchKernelGGL(pfac_spans_block_scan<1>, dim3(scanGrid), dim3(1024), 0, 0, (const unsigned int *)a.blockMax, a.blockTop, a.blocks, a.covered);
+    hipLaunchKernelGGL(pfac_spans_heads<0>, dim3(a.blocks), dim3(kSpanThreads), 0, 0, a);
+    hipLaunchKernelGGL(pfac_spans_block_scan<0>, dim3(scanGrid), dim3(1024), 0, 0, (const unsigned int *)a.headCount, a.headBase, a.blocks, (unsigned int *)nullptr);
+    hipLaunchKernelGGL(pfac_spans_heads<1>, dim3(a.blocks), dim3(kSpanThreads), 0, 0, a);
+    hipLaunchKernelGGL(pfac_spans_emit, dim3(gridFor(c, bound)), dim3(kSpanThreads), 0, 0, a);
+    hipLaunchKernelGGL(pfac_spans_finish, dim3(1), dim3(1), 0, 0, a, reinterpret_cast<unsigned long long *>(counts.d_value));
+    unsigned long long v = 0;
+    if (mapped) {
+        counts.queueDone();
+        if (!counts.wait()) return PFAC_STATUS_INTERNAL_ERROR;
+        v = counts.value64();
+    } else if (hipGetLastError() != hipSuccess || hipMemcpy(&v, a.value, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) {
+        return PFAC_STATUS_INTERNAL_ERROR;
+    }
+    const size_t spans = (size_t)(v & 0xFFFFFFFFull), covered = (size_t)(v >> 32);
+    if (spans == 0 || spans > bound || covered < spans || covered > size) return PFAC_STATUS_INTERNAL_ERROR;
+    *h_numSpans = spans;
+    *h_coveredBytes = covered;
+    return PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t PFACX_spansRedact(PFAC_handle_t handle, const char *d_input, size_t size, const int *d_spanStart, const int *d_spanLen, size_t numSpans,
+                                unsigned char fill, char *d_out)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!d_input || !d_out || size == 0 || size > (size_t)0x7fffffff || numSpans > (size_t)0x7fffffff || (numSpans && (!d_spanStart || !d_spanLen)))
+        return PFAC_STATUS_INVALID_PARAMETER;
+    const PFAC_context *c = handle;
+    RedactArgs a{};
+    a.in = reinterpret_cast<const unsigned char *>(d_input);
+    a.out = reinterpret_cast<unsigned char *>(d_out);
+    a.n = (unsigned int)size;
+    a.start = d_spanStart;
+    a.len = d_spanLen;
+    a.count = (unsigned int)numSpans;
+    a.fill4 = fill * 0x01010101u;
+    a.misOut = (unsigned int)(reinterpret_cast<uintptr_t>(d_out) & 15u);
+    a.inPlace = d_input == d_out ? 1u : 0u;
+    if (a.inPlace && numSpans == 0) return PFAC_STATUS_SUCCESS;
+    const size_t tiles = (size + a.misOut + kTile - 1) / kTile, cap = (size_t)gridCap(c, 8) * 4;
+    hipLaunchKernelGGL(pfac_spans_redact, dim3((unsigned int)(tiles < cap ? tiles : cap)), dim3(kSpanThreads), 0, 0, a);
+    return hipGetLastError() == hipSuccess ? PFAC_STATUS_SUCCESS : PFAC_STATUS_INTERNAL_ERROR;
+}
+
+} /* extern "C" */

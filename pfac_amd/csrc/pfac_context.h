@@ -59,7 +59,7 @@ constexpr HostSlot kHostPairs = {4, 5};           /* a compacted-output call: th
 constexpr HostSlot kHostAll = {8, 10};            /* an all-match call: the 64-bit length of its list (scan_all.hip) */
 constexpr HostSlot kHostSeam = {12, 13};          /* a stream call: the pairs of its seam (scan_stream.hip: pfac_stream_seam stores both words) */
 constexpr HostSlot kHostFlows = {14, 15};         /* a flows call: its pairs (scan_flows.hip: pfac_flows_done stores both words) */
-constexpr HostSlot kHostLines = {16, 18};         /* a lines call: the lines, then the selected lines (scan_lines.hip: pfac_lines_block_scan) */
+constexpr HostSlot kHostLines = {16, 18};         /* a lines call: the lines, then the selected lines (scan_lines.hip, by pfac_block_scan) */
 constexpr HostSlot kHostGather = {20, 22};        /* a gather: the 64-bit size of its text (scan_lines.hip) */
 constexpr HostSlot kHostSpans = {24, 26};         /* a spans call: one 64-bit value, the spans | the covered bytes << 32 (scan_spans.hip: pfac_spans_finish) */
 constexpr int kHostWords = 32;

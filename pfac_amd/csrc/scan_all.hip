@@ -158,8 +158,7 @@ PFAC_status_t PFACX_allExpand(PFAC_handle_t handle, const int *d_pairIds, const 
     if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
     x.blockBase = reinterpret_cast<unsigned long long *>(s);
     x.pairOffset = d_segFirst ? reinterpret_cast<unsigned long long *>(s + baseBytes) : nullptr;
-    const bool mapped = hostMapped(c);
-    const HostHandoff list = mapped ? HostHandoff(c, pfac::kHostAll) : HostHandoff();
+    const HostHandoff list(c, pfac::kHostAll);
     if (blocks) hipLaunchKernelGGL(pfac_all_count, dim3((unsigned int)blocks), dim3(kAllBlock), 0, 0, x);
     hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, x.blockBase, (unsigned int)blocks, x.blockBase + blocks,
                        reinterpret_cast<unsigned long long *>(list.d_value));
@@ -171,14 +170,7 @@ PFAC_status_t PFACX_allExpand(PFAC_handle_t handle, const int *d_pairIds, const 
                            x.blockBase + blocks, d_segFirst);
     }
     unsigned long long total = 0;
-    if (mapped) {
-        list.queueDone();
-        if (!list.wait()) return PFAC_STATUS_INTERNAL_ERROR;
-        total = list.value64();
-    } else if (hipGetLastError() != hipSuccess ||
-               hipMemcpy(&total, x.blockBase + blocks, sizeof(total), hipMemcpyDeviceToHost) != hipSuccess) {
-        return PFAC_STATUS_INTERNAL_ERROR;
-    }
+    if (!list.finish(&total, x.blockBase + blocks)) return PFAC_STATUS_INTERNAL_ERROR;
     *h_total = (size_t)total;
     return PFAC_STATUS_SUCCESS;
 }

@@ -9,7 +9,7 @@
  *                  the DESTINATION (handle scratch, a staging piece: both 256-byte aligned, so a misaligned caller pointer still
  *                  hands the scan an aligned one).  Its source bytes lie m = 0..15 bytes into an aligned 16-byte block: Q = -1 for
  *                  m == 0 (one load per step, the in-place case), else Q = m / 4 and the step takes its 16 bytes out of two
- *                  aligned source blocks with v_alignbyte (r = m % 4; the second block is the next lane's first: the extra load
+ *                  aligned source blocks with v_alignbyte (scan_passes.h: funnel; r = m % 4; the second block is the next lane's first: the extra load
  *                  hits the cache, HBM traffic stays one read and one write per byte).  Bytes in front of the body (head) and
  *                  behind it (tail), fewer than 32 each, are folded one by one by the first lanes of the grid.
  *
@@ -50,15 +50,6 @@ __device__ __forceinline__ uint32_t foldWord(uint32_t x)
 }
 
 __device__ __forceinline__ u32x4 foldVec(u32x4 v) { return u32x4{foldWord(v.x), foldWord(v.y), foldWord(v.z), foldWord(v.w)}; }
-
-/* 16 bytes starting m = 4 Q + r bytes into the 32 of a | b */
-template <int Q>
-__device__ __forceinline__ u32x4 funnel(u32x4 a, u32x4 b, uint32_t r)
-{
-    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return u32x4{__builtin_amdgcn_alignbyte(w[Q + 1], w[Q], r), __builtin_amdgcn_alignbyte(w[Q + 2], w[Q + 1], r),
-                 __builtin_amdgcn_alignbyte(w[Q + 3], w[Q + 2], r), __builtin_amdgcn_alignbyte(w[Q + 4], w[Q + 3], r)};
-}
 
 template <int Q>
 __global__ __launch_bounds__(kFoldBlock) void pfac_fold(FoldArgs f)

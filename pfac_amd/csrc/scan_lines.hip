@@ -12,14 +12,14 @@
  *                          inside the buffer -- at most two of a launch -- byte by byte with bounds).  16 bytes become 16 bits by a SWAR compare;
  *                          two shuffles hand every lane the 32 bits of its word.  Writes the newline bitmap, a zero word of the line-hit
  *                          bitmap, the number of newlines of the block in front of each word (ushort) and the block's count
- *   pfac_lines_block_scan  the exclusive prefix of the block counts (the line number at each block's start) and, with it, the running maximum
- *                          of the blocks' last newline, a block of 1024 threads per 8192 counts that sums what lies in front of them itself; the
- *                          total goes to mapped host memory
+ *   pfac_block_scan<sum>   the exclusive prefix of the block counts: the line number at each block's start (scan_passes.h: a block of 1024
+ *                          threads per 8192 counts that folds what lies in front of them itself); the total goes to mapped host memory
  *   [the compacted scan, its pairs left unordered in the caller's arrays: scan_module.hip]
  *   pfac_lines_mark        a thread per pair: line = block base + rank of the word + set bits below the position; atomicOr into the hit bitmap
  *   pfac_lines_select<0>   a wave per block: the lines that end in a word are consecutive, so their hit bits are one 64-bit funnel; counts
  *                          the selected ones (hit ^ invert) per block and notes the block's last newline
- *   pfac_lines_block_scan  ... the first selected line of each block, the last newline in front of each block
+ *   pfac_block_scan<sum, max>  the same for the selected lines and, in the same launch, the running maximum of the blocks' last newline: the
+ *                          first selected line of each block, the last newline in front of each block
  *   pfac_lines_select<1>   the same walk again, writing (start, len, index) in order over the scan's pair list
  *   pfac_host_done         the call's sequence number to mapped host memory (scan_passes.h: HostHandoff)
  * Only the first pass and the scan touch O(size) bytes; the rest reads size / 8 bytes of bitmaps and the pairs.
@@ -49,7 +49,6 @@ namespace {
 constexpr unsigned int kLinesThreads = 256;                /* four waves, a block of positions each */
 constexpr unsigned int kBlockShift = 11;                   /* 2048 positions per block ... */
 constexpr unsigned int kBlockWords = 64;                   /* ... = 64 bitmap words, one per lane */
-constexpr unsigned int kScanPer = 8;                       /* entries per thread and step of pfac_lines_block_scan */
 constexpr unsigned int kTile = 4096;                       /* output bytes per tile of the gather */
 
 struct LinesArgs {
@@ -94,16 +93,6 @@ __device__ __forceinline__ uint32_t granuleBits(const LinesArgs &a, size_t g)
     return bits;
 }
 
-__device__ __forceinline__ unsigned int waveMax(unsigned int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned int o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(kLinesThreads) void pfac_lines_bitmap(LinesArgs a)
 {
     const unsigned int lane = threadIdx.x & 63u;
@@ -123,86 +112,6 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_bitmap(LinesArgs a)
         a.hitBits[w] = 0;
         a.rank[w] = (uint16_t)(incl - c);
         if (lane == 63u) a.lineCount[b] = incl;
-    }
-}
-
-/* out[0, n) = the exclusive prefix sum of v[0, n), out[n] = the total (also to *hostTotal when given); m (or null): mOut[i] = the maximum of m[0, i)
- * and 0.  A block of 1024 threads per 8192 entries; block k sums (and takes the maximum of) everything in front of its entries itself -- coalesced,
- * from L2, at most 4 n bytes -- so there is no pass between blocks and no chain of 8192-entry steps (one block walking 512 Ki counts of a
- * 1 GiB input took longer than the newline pass).  v and out are different arrays: the blocks read each other's input */
-__global__ __launch_bounds__(1024) void pfac_lines_block_scan(const unsigned int *v, unsigned int *out, const unsigned int *m, unsigned int *mOut, unsigned int n,
-                                                               unsigned int *hostTotal)
-{
-    __shared__ unsigned int waveSum[16];
-    __shared__ unsigned int waveTop[16];
-    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const unsigned int base = blockIdx.x * 1024u * kScanPer;
-    unsigned int front = 0, frontTop = 0;
-    for (unsigned int q = threadIdx.x; q < base / 4u; q += 1024u) {                 /* base is a multiple of 8192 */
-        const pfacmod::u32x4 c = reinterpret_cast<const pfacmod::u32x4 *>(v)[q];
-        front += c.x + c.y + c.z + c.w;
-        if (m != nullptr) {
-            const pfacmod::u32x4 t = reinterpret_cast<const pfacmod::u32x4 *>(m)[q];
-            const unsigned int t0 = t.x > t.y ? t.x : t.y, t1 = t.z > t.w ? t.z : t.w, t2 = t0 > t1 ? t0 : t1;
-            frontTop = t2 > frontTop ? t2 : frontTop;
-        }
-    }
-    const unsigned int i0 = base + threadIdx.x * kScanPer;
-    unsigned int x[kScanPer], own = 0;
-    unsigned int t[kScanPer], ownTop = 0;
-#pragma unroll
-    for (unsigned int k = 0; k < kScanPer; k++) {
-        x[k] = i0 + k < n ? v[i0 + k] : 0u;
-        t[k] = (m != nullptr && i0 + k < n) ? m[i0 + k] : 0u;
-        own += x[k];
-        ownTop = t[k] > ownTop ? t[k] : ownTop;
-    }
-    /* the fronts of all threads are one more addend in front of thread 0's entries: scan (front + own), give back own */
-    unsigned int incl = own, inclTop = ownTop, frontAll = front, frontTopAll = frontTop;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned int up = __shfl_up(incl, d);
-        const unsigned int upTop = __shfl_up(inclTop, d);
-        if ((int)lane >= d) { incl += up; inclTop = upTop > inclTop ? upTop : inclTop; }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        frontAll += __shfl_xor(frontAll, d);
-        const unsigned int o = __shfl_xor(frontTopAll, d);
-        frontTopAll = o > frontTopAll ? o : frontTopAll;
-    }
-    unsigned int exclTop = __shfl_up(inclTop, 1);
-    if (lane == 0) exclTop = 0;
-    __shared__ unsigned int waveFront[16];
-    __shared__ unsigned int waveFrontTop[16];
-    if (lane == 63) { waveSum[wave] = incl; waveTop[wave] = inclTop; waveFront[wave] = frontAll; waveFrontTop[wave] = frontTopAll; }
-    __syncthreads();
-    unsigned int before = 0, beforeTop = 0;
-    for (unsigned int w = 0; w < 16; w++) {
-        before += waveFront[w];
-        beforeTop = waveFrontTop[w] > beforeTop ? waveFrontTop[w] : beforeTop;
-        if (w < wave) {
-            before += waveSum[w];
-            beforeTop = waveTop[w] > beforeTop ? waveTop[w] : beforeTop;
-        }
-    }
-    unsigned int run = before + incl - own;
-    unsigned int runTop = exclTop > beforeTop ? exclTop : beforeTop;
-#pragma unroll
-    for (unsigned int k = 0; k < kScanPer; k++) {
-        if (i0 + k < n) {
-            out[i0 + k] = run;
-            if (m != nullptr) mOut[i0 + k] = runTop;
-        }
-        run += x[k];
-        runTop = t[k] > runTop ? t[k] : runTop;
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 1023) {          /* the last thread of the last block has seen everything */
-        out[n] = run;
-        if (hostTotal != nullptr) {
-            __hip_atomic_store(hostTotal, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __threadfence_system();
-        }
     }
 }
 
@@ -240,19 +149,11 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_select(LinesArgs a)
         const unsigned int qWord = (b << kBlockShift) + lane * 32u;
         const unsigned int last = word ? qWord + 32u - (unsigned int)__clz((int)word) : 0u;            /* q + 1 */
         if constexpr (WRITE == 0) {
-            const unsigned int top = waveMax(last);
+            const unsigned int top = waveReduce(last, OpMax());
             if (lane == 63u) { a.selCount[b] = incl; a.lastNl[b] = top; }
         } else {
-            unsigned int inclTop = last;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const unsigned int up = __shfl_up(inclTop, d);
-                if ((int)lane >= d) inclTop = up > inclTop ? up : inclTop;
-            }
-            unsigned int prev = __shfl_up(inclTop, 1);                 /* q + 1 of the last newline in front of this word: where its first line starts */
-            if (lane == 0) prev = 0;
-            const unsigned int carried = a.prevNl[b];
-            prev = carried > prev ? carried : prev;
+            /* q + 1 of the last newline in front of this word: where its first line starts */
+            unsigned int prev = OpMax()(a.prevNl[b], waveExclusiveOf(waveInclusive(last, OpMax())));
             size_t o = (size_t)a.selBase[b] + (incl - ns);
             for (unsigned int j = 0; word; j++) {
                 const unsigned int q = qWord + (unsigned int)__ffs((int)word) - 1u;
@@ -286,15 +187,12 @@ struct GatherArgs {
     unsigned int misOut;                /* address of out & 15 */
 };
 
-__device__ __forceinline__ size_t clampedStart(const GatherArgs &g, size_t i)
+/* line i as input bytes [s, s + l) */
+__device__ __forceinline__ size_t lineOf(const GatherArgs &g, size_t i, size_t &s)
 {
-    const int s = g.start[i];
-    return s < 0 ? 0 : ((size_t)s > g.n ? g.n : (size_t)s);
-}
-__device__ __forceinline__ size_t clampedLen(const GatherArgs &g, size_t i, size_t s)
-{
-    const int l = g.len[i];
-    return l < 0 ? 0 : ((size_t)l > g.n - s ? g.n - s : (size_t)l);
+    size_t e;
+    clampSpan(g.start[i], g.len[i], g.n, s, e);
+    return e - s;
 }
 
 __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_count(GatherArgs g)
@@ -303,7 +201,8 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_count(GatherA
     const size_t first = (size_t)blockIdx.x * g.per;
     const size_t end = g.count - first < g.per ? g.count : first + g.per;
     unsigned long long own = 0;
-    for (size_t i = first + threadIdx.x; i < end; i += kLinesThreads) own += clampedLen(g, i, clampedStart(g, i)) + 1;
+    size_t s;
+    for (size_t i = first + threadIdx.x; i < end; i += kLinesThreads) own += lineOf(g, i, s) + 1;
     unsigned long long total = 0;
     (void)blockExclusive<kLinesThreads>(own, waveSum, total);
     if (threadIdx.x == 0) g.blockBase[blockIdx.x] = total;
@@ -318,7 +217,8 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_offsets(Gathe
     for (size_t i0 = first; i0 < end; i0 += kLinesThreads) {        /* the same trip count for every thread of the block */
         const size_t i = i0 + threadIdx.x;
         const bool has = i < end;
-        const unsigned long long c = has ? clampedLen(g, i, clampedStart(g, i)) + 1 : 0ull;
+        size_t s;
+        const unsigned long long c = has ? lineOf(g, i, s) + 1 : 0ull;
         unsigned long long stepTotal = 0;
         const unsigned long long o = base + blockExclusive<kLinesThreads>(c, waveSum, stepTotal);
         base += stepTotal;
@@ -374,7 +274,7 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_copy(GatherAr
             }
             size_t i = first + lo;
             unsigned long long k = lo == 0 ? cLo - g.off[first] : (unsigned long long)(r - rel[lo]);     /* bytes of line i in front of cLo */
-            size_t s = clampedStart(g, i), l = clampedLen(g, i, s);
+            size_t s, l = lineOf(g, i, s);
             auto next = [&]() -> uint32_t {
                 uint32_t byte = '\n';
                 if (k < l) {
@@ -383,7 +283,7 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_copy(GatherAr
                 } else {                                 /* the line's newline: on to the next line */
                     k = 0;
                     i++;
-                    if (i < g.count) { s = clampedStart(g, i); l = clampedLen(g, i, s); } else { s = 0; l = 0; }
+                    if (i < g.count) l = lineOf(g, i, s); else l = 0;
                 }
                 return byte;
             };
@@ -413,6 +313,39 @@ char *linesScratch(PFAC_context *c, size_t bytes)
     return c->scratch.lines.get();
 }
 
+/* the arguments of the passes over the n bytes at `in`, their arrays carved from the handle's lines scratch: the newline pass's (select == false)
+ * or those of a whole select call.  false: no memory */
+bool linesArgs(PFAC_context *c, const void *in, size_t n, bool select, LinesArgs &a)
+{
+    a.in = static_cast<const unsigned char *>(in);
+    a.n = n;
+    a.mis = (unsigned int)(reinterpret_cast<uintptr_t>(in) & 15u);
+    const size_t blocks = ((size_t)a.mis + n) / (size_t(1) << kBlockShift) + 1, words = blocks * kBlockWords;      /* positions q in [0, mis + n] */
+    a.blocks = (unsigned int)blocks;
+    ScratchCarver k;
+    for (int pass = 0; pass < 2; pass++) {
+        a.nlBits = k.take<uint32_t>(words);
+        a.hitBits = k.take<uint32_t>(words, 256);              /* and the word a funnel may read behind it */
+        a.rank = k.take<uint16_t>(words);
+        if (select) {
+            a.lineBase = k.take<unsigned int>(blocks + 1);
+            a.lineCount = k.take<unsigned int>(blocks + 1);
+            a.selBase = k.take<unsigned int>(blocks + 1);
+            a.selCount = k.take<unsigned int>(blocks + 1);
+            a.prevNl = k.take<unsigned int>(blocks);
+            a.lastNl = k.take<unsigned int>(blocks);
+        } else {
+            a.lineCount = k.take<unsigned int>(blocks);
+        }
+        if (pass == 0) k = ScratchCarver{linesScratch(c, k.bytes)};
+        if (k.base == nullptr) return false;
+    }
+    return true;
+}
+
+/* the grid of the passes that take a block of positions per wave */
+unsigned int waveGridFor(const PFAC_context *c, unsigned int blocks) { return (blocks + 3) / 4 < gridCap(c, 8) ? (blocks + 3) / 4 : gridCap(c, 8); }
+
 } // namespace
 
 extern "C" {
@@ -425,68 +358,33 @@ PFAC_status_t PFACX_linesSelect(PFAC_handle_t handle, const char *d_input, char 
         return PFAC_STATUS_INVALID_PARAMETER;
     PFAC_context *c = handle;
     LinesArgs a{};
-    a.in = reinterpret_cast<const unsigned char *>(d_input);
-    a.n = size;
-    a.mis = (unsigned int)(reinterpret_cast<uintptr_t>(d_input) & 15u);
-    const size_t blocks = ((size_t)a.mis + size) / (size_t(1) << kBlockShift) + 1;      /* positions q in [0, mis + size] */
-    a.blocks = (unsigned int)blocks;
-    const size_t words = blocks * kBlockWords;
-    const size_t oNl = 0, oHit = oNl + round256(words * 4), oRank = oHit + round256(words * 4 + 256), oLine = oRank + round256(words * 2),
-                 oSel = oLine + 2 * round256((blocks + 1) * 4), oPrev = oSel + 2 * round256((blocks + 1) * 4), bytes = oPrev + 2 * round256(blocks * 4);
-    char *s = linesScratch(c, bytes);
-    if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
-    a.nlBits = reinterpret_cast<uint32_t *>(s + oNl);
-    a.hitBits = reinterpret_cast<uint32_t *>(s + oHit);
-    a.rank = reinterpret_cast<uint16_t *>(s + oRank);
-    a.lineBase = reinterpret_cast<unsigned int *>(s + oLine);
-    a.lineCount = reinterpret_cast<unsigned int *>(s + oLine + round256((blocks + 1) * 4));
-    a.selBase = reinterpret_cast<unsigned int *>(s + oSel);
-    a.selCount = reinterpret_cast<unsigned int *>(s + oSel + round256((blocks + 1) * 4));
-    a.prevNl = reinterpret_cast<unsigned int *>(s + oPrev);
-    a.lastNl = reinterpret_cast<unsigned int *>(s + oPrev + round256(blocks * 4));
+    if (!linesArgs(c, d_input, size, true, a)) return PFAC_STATUS_CUDA_ALLOC_FAILED;
     a.invert = invert ? 0xFFFFFFFFu : 0u;
     a.lineStart = d_lineStart;
     a.lineLen = d_lineLen;
     a.lineIndex = d_lineIndex;
-    const bool mapped = hostMapped(c);
-    const HostHandoff counts = mapped ? HostHandoff(c, pfac::kHostLines) : HostHandoff();      /* the lines, then the selected lines */
-    const unsigned int waveGrid = (unsigned int)((blocks + 3) / 4 < gridCap(c, 8) ? (blocks + 3) / 4 : gridCap(c, 8));
+    const HostHandoff counts(c, pfac::kHostLines);             /* the lines, then the selected lines */
+    const unsigned int waveGrid = waveGridFor(c, a.blocks);
 
     /* the line index in front of the scan, on the same stream */
     hipLaunchKernelGGL(pfac_lines_bitmap, dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
-    const unsigned int scanGrid = (a.blocks + 1024u * kScanPer - 1u) / (1024u * kScanPer);
-    hipLaunchKernelGGL(pfac_lines_block_scan, dim3(scanGrid), dim3(1024), 0, 0, (const unsigned int *)a.lineCount, a.lineBase, (const unsigned int *)nullptr,
-                       (unsigned int *)nullptr, a.blocks, counts.d_value);
+    blockScan<OpSum>({{a.lineCount}, {a.lineBase}}, a.blocks, counts.word(0), nullptr);
     if (hipGetLastError() != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
 
     /* the compacted scan, pairs in any order (the four ordering launches are not paid for): ids in d_lineStart, positions in d_lineLen */
-    int count = 0;
-    const bool wasUnordered = c->reduceUnordered;
-    c->reduceUnordered = true;
-    const PFAC_status_t st = hashed ? PFAC_reduce_inplace_kernel(handle, reinterpret_cast<int *>(d_scan), (int)size, d_lineStart, d_lineLen, &count, nullptr, nullptr)
-                                    : PFAC_reduce_kernel(handle, reinterpret_cast<int *>(d_scan), (int)size, d_lineStart, d_lineLen, &count, nullptr, nullptr);
-    c->reduceUnordered = wasUnordered;
+    size_t count = 0;
+    const PFAC_status_t st = compactedScan(handle, d_scan, size, hashed, d_lineStart, d_lineLen, false, &count);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
 
-    if (count > 0) hipLaunchKernelGGL(pfac_lines_mark, dim3(gridFor(c, (size_t)count)), dim3(kLinesThreads), 0, 0, a, (const int *)d_lineLen, (unsigned int)count);
+    if (count > 0) hipLaunchKernelGGL(pfac_lines_mark, dim3(gridFor(c, count)), dim3(kLinesThreads), 0, 0, a, (const int *)d_lineLen, (unsigned int)count);
     hipLaunchKernelGGL(pfac_lines_select<0>, dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
-    hipLaunchKernelGGL(pfac_lines_block_scan, dim3(scanGrid), dim3(1024), 0, 0, (const unsigned int *)a.selCount, a.selBase, (const unsigned int *)a.lastNl, a.prevNl,
-                       a.blocks, mapped ? counts.d_value + 1 : (unsigned int *)nullptr);
+    blockScan<OpSum, OpMax, 2>({{a.selCount, a.lastNl}, {a.selBase, a.prevNl}}, a.blocks, counts.word(1), nullptr);
     hipLaunchKernelGGL(pfac_lines_select<1>, dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
-    unsigned int numLines = 0, numSelected = 0;
-    if (mapped) {
-        counts.queueDone();
-        if (!counts.wait()) return PFAC_STATUS_INTERNAL_ERROR;
-        numLines = counts.h_value[0];
-        numSelected = counts.h_value[1];
-    } else if (hipGetLastError() != hipSuccess || hipMemcpy(&numLines, a.lineBase + blocks, sizeof(numLines), hipMemcpyDeviceToHost) != hipSuccess ||
-               hipMemcpy(&numSelected, a.selBase + blocks, sizeof(numSelected), hipMemcpyDeviceToHost) != hipSuccess) {
-        return PFAC_STATUS_INTERNAL_ERROR;
-    }
-    if (numLines > size || numSelected > numLines) return PFAC_STATUS_INTERNAL_ERROR;
-    *h_numLines = numLines;
-    *h_numSelected = numSelected;
+    unsigned int lines[2] = {0, 0};                            /* all, selected */
+    if (!counts.finish(lines, a.lineBase + a.blocks, a.selBase + a.blocks)) return PFAC_STATUS_INTERNAL_ERROR;
+    if (lines[0] > size || lines[1] > lines[0]) return PFAC_STATUS_INTERNAL_ERROR;
+    *h_numLines = lines[0];
+    *h_numSelected = lines[1];
     return PFAC_STATUS_SUCCESS;
 }
 
@@ -496,19 +394,8 @@ double PFACX_linesBitmapProbe(PFAC_handle_t handle, const void *d_in, size_t n, 
     if (!handle || !d_in || n == 0 || n > (size_t)0x7fffffff || launches < 1) return -1.0;
     PFAC_context *c = handle;
     LinesArgs a{};
-    a.in = static_cast<const unsigned char *>(d_in);
-    a.n = n;
-    a.mis = (unsigned int)(reinterpret_cast<uintptr_t>(d_in) & 15u);
-    const size_t blocks = ((size_t)a.mis + n) / (size_t(1) << kBlockShift) + 1, words = blocks * kBlockWords;
-    const size_t oHit = round256(words * 4), oRank = oHit + round256(words * 4 + 256), oLine = oRank + round256(words * 2);
-    char *s = linesScratch(c, oLine + round256(blocks * 4));
-    if (!s) return -1.0;
-    a.blocks = (unsigned int)blocks;
-    a.nlBits = reinterpret_cast<uint32_t *>(s);
-    a.hitBits = reinterpret_cast<uint32_t *>(s + oHit);
-    a.rank = reinterpret_cast<uint16_t *>(s + oRank);
-    a.lineCount = reinterpret_cast<unsigned int *>(s + oLine);
-    const unsigned int grid = (unsigned int)((blocks + 3) / 4 < gridCap(c, 8) ? (blocks + 3) / 4 : gridCap(c, 8));
+    if (!linesArgs(c, d_in, n, false, a)) return -1.0;
+    const unsigned int grid = waveGridFor(c, a.blocks);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     double ms = -1.0;
     if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
@@ -546,13 +433,14 @@ PFAC_status_t PFACX_linesGather(PFAC_handle_t handle, const char *d_input, size_
     g.per = ((numSelected + blocks - 1) / blocks + kLinesThreads - 1) / kLinesThreads * kLinesThreads;
     blocks = (numSelected + g.per - 1) / g.per;
     g.blocks = (unsigned int)blocks;
-    const size_t baseBytes = round256((blocks + 1) * sizeof(unsigned long long));
-    char *s = linesScratch(c, baseBytes + round256(numSelected * sizeof(unsigned long long)));
-    if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
-    g.blockBase = reinterpret_cast<unsigned long long *>(s);
-    g.off = reinterpret_cast<unsigned long long *>(s + baseBytes);
-    const bool mapped = hostMapped(c);
-    const HostHandoff text = mapped ? HostHandoff(c, pfac::kHostGather) : HostHandoff();
+    ScratchCarver k;
+    for (int pass = 0; pass < 2; pass++) {
+        g.blockBase = k.take<unsigned long long>(blocks + 1);
+        g.off = k.take<unsigned long long>(numSelected);
+        if (pass == 0) k = ScratchCarver{linesScratch(c, k.bytes)};
+        if (k.base == nullptr) return PFAC_STATUS_CUDA_ALLOC_FAILED;
+    }
+    const HostHandoff text(c, pfac::kHostGather);
     hipLaunchKernelGGL(pfac_lines_gather_count, dim3(g.blocks), dim3(kLinesThreads), 0, 0, g);
     hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, g.blockBase, g.blocks, g.blockBase + g.blocks,
                        reinterpret_cast<unsigned long long *>(text.d_value));
@@ -565,13 +453,7 @@ PFAC_status_t PFACX_linesGather(PFAC_handle_t handle, const char *d_input, size_
         hipLaunchKernelGGL(pfac_lines_gather_copy, dim3((unsigned int)(tiles < gridCap(c, 8) * 4ull ? tiles : gridCap(c, 8) * 4ull)), dim3(kLinesThreads), 0, 0, g);
     }
     unsigned long long total = 0;
-    if (mapped) {
-        text.queueDone();
-        if (!text.wait()) return PFAC_STATUS_INTERNAL_ERROR;
-        total = text.value64();
-    } else if (hipGetLastError() != hipSuccess || hipMemcpy(&total, g.blockBase + blocks, sizeof(total), hipMemcpyDeviceToHost) != hipSuccess) {
-        return PFAC_STATUS_INTERNAL_ERROR;
-    }
+    if (!text.finish(&total, g.blockBase + blocks)) return PFAC_STATUS_INTERNAL_ERROR;
     *h_outBytes = (size_t)total;
     return total > outCapacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
 }

@@ -1,13 +1,17 @@
 /*
  * scan_passes.h -- what the passes around the scan share (scan_module.hip with scan_order.inc, scan_batch.hip, scan_all.hip, scan_fold.hip,
- * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip; the product kernels' units do not include it): launch sizes, the hand-off of a call's
- * result to the host through mapped memory, the device fold byte, block prefix sums, the seam of a stream.  Like scan_common.h, everything is
- * in an unnamed namespace: inline device code, each unit its own copy.
+ * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip; the product kernels' units do not include it): launch sizes, the layout of a
+ * call's scratch, the compacted scan as a pass runs it, the hand-off of a call's result to the host through mapped memory, the device fold byte,
+ * the clamp of a caller's (start, len), 16 bytes out of two aligned blocks (funnel), wave and block prefixes under a sum or a maximum, the two scan
+ * kernels (pfac_array_scan: one block, in place; pfac_block_scan: a block per 8192 values that folds what lies in front of them), the seam of
+ * a stream.  Like scan_common.h, everything is in an unnamed namespace: inline device code, each
+ * unit its own copy.
  */
 #ifndef PFAC_SCAN_PASSES_H_
 #define PFAC_SCAN_PASSES_H_
 
 #include "scan_common.h"
+#include "pfac_module.h"
 
 namespace pfacmod {
 /* scan_module.hip: queues pfac_host_done, the one-store kernel that writes `seq` to a word of mapped host memory, on the default stream */
@@ -28,6 +32,35 @@ inline unsigned int gridFor(const PFAC_context *c, size_t items)
 {
     const size_t cap = gridCap(c, 8), blocks = (items + 255) / 256;
     return (unsigned int)(blocks < 1 ? 1 : blocks > cap ? cap : blocks);
+}
+
+/* The layout of a call's scratch: regions in the order they are taken, each rounded up to 256 bytes (extraBytes: what a region holds behind its
+ * `count` entries).  Without a base it only counts: a layout function runs once for `bytes`, and again over the reserved buffer for the pointers */
+struct ScratchCarver {
+    char *base = nullptr;
+    size_t bytes = 0;
+    template <class T>
+    T *take(size_t count, size_t extraBytes = 0)
+    {
+        T *at = base ? reinterpret_cast<T *>(base + bytes) : nullptr;
+        bytes += round256(count * sizeof(T) + extraBytes);
+        return at;
+    }
+};
+
+/* The compacted scan of d_scan[0, size) as a pass runs it: the (id, position) pairs into d_ids / d_pos (`size` entries each), in position order or
+ * -- the four ordering launches not paid for -- in any; *count is inside [0, size].  The handle's own setting is put back */
+inline PFAC_status_t compactedScan(PFAC_handle_t handle, char *d_scan, size_t size, int hashed, int *d_ids, int *d_pos, bool ordered, size_t *count)
+{
+    int found = 0;
+    const bool wasUnordered = handle->reduceUnordered;
+    handle->reduceUnordered = !ordered;
+    const PFAC_status_t st = (hashed ? PFAC_reduce_inplace_kernel : PFAC_reduce_kernel)(handle, reinterpret_cast<int *>(d_scan), (int)size, d_ids, d_pos, &found, nullptr, nullptr);
+    handle->reduceUnordered = wasUnordered;
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (found < 0 || (size_t)found > size) return PFAC_STATUS_INTERNAL_ERROR;
+    *count = (size_t)found;
+    return PFAC_STATUS_SUCCESS;
 }
 
 /* ------------------------------------------------------------------ the hand-off to the host */
@@ -53,7 +86,8 @@ inline bool hostMapped(const PFAC_context *c) { return c->h_modeHint != nullptr 
 /* One call's hand-off through a slot of the handle's mapped words (pfac_context.h: HostSlot; the handle has them: hostMapped).  The call's
  * launches write what they hand over at d_value and, behind everything else, `seq` at d_done -- the call's last kernel where that kernel stores
  * the value too, else pfac_host_done (queueDone); the host then waits and reads h_value.  A slot's done word is only ever compared with the
- * number issued to the call that waits on it, so the handle counts all its calls with one counter */
+ * number issued to the call that waits on it, so the handle counts all its calls with one counter.  On a handle without mapped words the
+ * hand-off is empty (d_value is null: the kernels skip their host stores) and finish() copies from device memory instead */
 struct HostHandoff {
     unsigned int *d_value = nullptr, *d_done = nullptr;
     volatile unsigned int *h_value = nullptr, *h_done = nullptr;
@@ -61,8 +95,12 @@ struct HostHandoff {
 
     HostHandoff() = default;
     HostHandoff(PFAC_context *c, pfac::HostSlot slot)
-        : d_value(c->d_modeHint + slot.value), d_done(c->d_modeHint + slot.done), h_value(c->h_modeHint + slot.value), h_done(c->h_modeHint + slot.done)
     {
+        if (!hostMapped(c)) return;
+        d_value = c->d_modeHint + slot.value;
+        d_done = c->d_modeHint + slot.done;
+        h_value = c->h_modeHint + slot.value;
+        h_done = c->h_modeHint + slot.done;
         c->hostSeq = c->hostSeq + 1u ? c->hostSeq + 1u : 1u;
         seq = c->hostSeq;
     }
@@ -75,7 +113,23 @@ struct HostHandoff {
         if (how != nullptr) *how = w;
         return w == HostWait::Polled || (w == HostWait::Synced && __atomic_load_n(const_cast<const unsigned int *>(h_done), __ATOMIC_ACQUIRE) == seq);
     }
-    unsigned long long value64() const { return __atomic_load_n(reinterpret_cast<const unsigned long long *>(const_cast<const unsigned int *>(h_value)), __ATOMIC_ACQUIRE); }
+    bool mapped() const { return d_done != nullptr; }
+    /* the device address of word k of the value (null: none) */
+    unsigned int *word(unsigned int k) const { return mapped() ? d_value + k : nullptr; }
+    /* The end of the call, behind its last launch: out[0] (and out[1], given d_second) = what the launches handed over -- queueDone, wait and the
+     * mapped value, or, without mapped words, the values the launches left at d_first (and d_second), copied.  false: a launch or the wait failed */
+    template <class T>
+    bool finish(T *out, const T *d_first, const T *d_second = nullptr) const
+    {
+        if (!mapped())
+            return hipGetLastError() == hipSuccess && hipMemcpy(out, d_first, sizeof(T), hipMemcpyDeviceToHost) == hipSuccess &&
+                   (d_second == nullptr || hipMemcpy(out + 1, d_second, sizeof(T), hipMemcpyDeviceToHost) == hipSuccess);
+        queueDone();
+        if (!wait()) return false;
+        const T *h = reinterpret_cast<const T *>(const_cast<const unsigned int *>(h_value));
+        for (int k = 0; k < (d_second ? 2 : 1); k++) out[k] = __atomic_load_n(h + k, __ATOMIC_ACQUIRE);
+        return true;
+    }
 };
 
 /* ------------------------------------------------------------------ the fold of a byte */
@@ -83,32 +137,79 @@ struct HostHandoff {
 /* pfac::asciiFold on the device, for a caseless set (fold != 0) */
 __device__ __forceinline__ unsigned char foldByte(unsigned char b, uint32_t fold) { return (unsigned char)(b + ((fold != 0 && (unsigned)(b - 'A') < 26u) ? 32 : 0)); }
 
-/* ------------------------------------------------------------------ block prefix sums */
+/* ------------------------------------------------------------------ a caller's (start, len); 16 bytes off alignment */
 
-/* inclusive prefix sum over the 64 lanes: 32-bit values by DPP (waveInclusiveScan), 64-bit ones by shuffles */
-template <class T>
-__device__ __forceinline__ T waveInclusive(T v)
+/* a caller's (start, len) as [s, e) inside [0, n]: clamped where it is read, never trusted (I: the width the caller counts bytes in) */
+template <class I>
+__device__ __forceinline__ void clampSpan(int start, int len, I n, I &s, I &e)
 {
-    if constexpr (sizeof(T) == 4) {
+    s = start < 0 ? (I)0 : ((I)start > n ? n : (I)start);
+    e = len <= 0 ? s : ((I)len > n - s ? n : s + (I)len);
+}
+
+/* 16 bytes starting m = 4 Q + r bytes into the 32 of a | b: four v_alignbyte */
+template <int Q>
+__device__ __forceinline__ u32x4 funnel(u32x4 a, u32x4 b, uint32_t r)
+{
+    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    return u32x4{__builtin_amdgcn_alignbyte(w[Q + 1], w[Q], r), __builtin_amdgcn_alignbyte(w[Q + 2], w[Q + 1], r),
+                 __builtin_amdgcn_alignbyte(w[Q + 3], w[Q + 2], r), __builtin_amdgcn_alignbyte(w[Q + 4], w[Q + 3], r)};
+}
+
+/* ------------------------------------------------------------------ wave and block prefixes */
+
+/* the operators of a prefix: the sum, and the maximum of unsigned values; 0 is the identity of both */
+struct OpSum {
+    template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+struct OpMax {
+    template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a > b ? a : b; }
+};
+
+/* inclusive prefix over the 64 lanes: 32-bit sums by DPP (waveInclusiveScan), everything else by shuffles */
+template <class T, class Op = OpSum>
+__device__ __forceinline__ T waveInclusive(T v, Op op = Op())
+{
+    if constexpr (sizeof(T) == 4 && std::is_same<Op, OpSum>::value) {
         return (T)waveInclusiveScan((uint32_t)v);
     } else {
         const unsigned int lane = threadIdx.x & 63u;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             const T up = __shfl_up(v, d);
-            if ((int)lane >= d) v += up;
+            if ((int)lane >= d) v = op(v, up);
         }
         return v;
     }
 }
 
+/* what an inclusive prefix leaves in front of each lane: the identity in front of lane 0 */
+template <class T>
+__device__ __forceinline__ T waveExclusiveOf(T incl)
+{
+    const T up = __shfl_up(incl, 1);
+    return (threadIdx.x & 63u) == 0 ? (T)0 : up;
+}
+
+/* all 64 lanes' values under op, in every lane */
+template <class T, class Op>
+__device__ __forceinline__ T waveReduce(T v, Op op)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = op(v, __shfl_xor(v, d));
+    return v;
+}
+
 /* exclusive prefix of `own` over the block's BLOCK threads, and the block's total (every thread calls it, every thread gets both);
  * waveSum: BLOCK / 64 entries of LDS, free again at the next call */
-template <unsigned int BLOCK, class T>
-__device__ __forceinline__ T blockExclusive(T own, T *waveSum, T &total)
+template <unsigned int BLOCK, class T, class Op = OpSum>
+__device__ __forceinline__ T blockExclusive(T own, T *waveSum, T &total, Op op = Op())
 {
     const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const T incl = waveInclusive(own);
+    const T incl = waveInclusive(own, op);
+    T excl;
+    if constexpr (std::is_same<Op, OpSum>::value) excl = incl - own;
+    else excl = waveExclusiveOf(incl);
     __syncthreads();                                    /* waveSum may still be read from the previous call */
     if (lane == 63) waveSum[wave] = incl;
     __syncthreads();
@@ -117,10 +218,10 @@ __device__ __forceinline__ T blockExclusive(T own, T *waveSum, T &total)
 #pragma unroll
     for (unsigned int w = 0; w < BLOCK / 64; w++) {
         const T s = waveSum[w];
-        before += w < wave ? s : (T)0;
-        total += s;
+        before = w < wave ? op(before, s) : before;
+        total = op(total, s);
     }
-    return before + incl - own;
+    return op(before, excl);
 }
 
 /* exclusive prefix sum of v[0, n) in place, the sum to *total (callers that keep it pass v + n) and *hostTotal where given: one block of
@@ -153,6 +254,90 @@ __global__ __launch_bounds__(1024) void pfac_array_scan(T *v, unsigned int n, T 
             __threadfence_system();
         }
     }
+}
+
+/* The block-value scan: for each of COLS columns of n values, out[0, n) = the exclusive prefix of in[0, n) under the column's operator (Op0, Op1;
+ * 0 in front of the first).  A block of 1024 threads per kScanBlock values; block k folds everything in front of its values itself -- coalesced,
+ * from L2, at most 4 n bytes a column -- so no block waits on another and there is no chain of steps (one block walking the 512 Ki counts of a
+ * 1 GiB input took longer than the newline pass).  in and out are different arrays: the blocks read each other's input.  The first column also
+ * gets its total: to out[n] and, where given, to *hostTotal (mapped host memory); a second column has n entries of out and rides along in the
+ * same launch.  zero (or null): a word that block 0 clears for the launches behind this one */
+constexpr unsigned int kScanPer = 8;                            /* values per thread */
+constexpr unsigned int kScanBlock = 1024 * kScanPer;            /* values per block: whole 16-byte loads in front of every block */
+static_assert(kScanBlock % 4 == 0, "the front of a block is folded four values a load");
+
+struct ScanColumns {
+    const unsigned int *in[2];
+    unsigned int *out[2];
+};
+
+template <class Op0, class Op1 = Op0, unsigned int COLS = 1>
+__global__ __launch_bounds__(1024) void pfac_block_scan(ScanColumns s, unsigned int n, unsigned int *hostTotal, unsigned int *zero)
+{
+    struct ColumnOp {                                           /* c is a constant wherever the loops over the columns are unrolled */
+        unsigned int c;
+        __device__ __forceinline__ unsigned int operator()(unsigned int a, unsigned int b) const { return c == 0 ? Op0()(a, b) : Op1()(a, b); }
+    };
+    __shared__ unsigned int waveOwn[COLS][16], waveFront[COLS][16];
+    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned int base = blockIdx.x * kScanBlock;
+    const unsigned int i0 = base + threadIdx.x * kScanPer;
+    if (zero != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *zero = 0;
+    unsigned int front[COLS], x[COLS][kScanPer], excl[COLS];
+#pragma unroll
+    for (unsigned int c = 0; c < COLS; c++) front[c] = 0;
+    for (unsigned int q = threadIdx.x; q < base / 4u; q += 1024u) {
+#pragma unroll
+        for (unsigned int c = 0; c < COLS; c++) {
+            const ColumnOp op{c};
+            const u32x4 v = reinterpret_cast<const u32x4 *>(s.in[c])[q];
+            front[c] = op(front[c], op(op(v.x, v.y), op(v.z, v.w)));
+        }
+    }
+#pragma unroll
+    for (unsigned int c = 0; c < COLS; c++) {
+        const ColumnOp op{c};
+        unsigned int own = 0;
+#pragma unroll
+        for (unsigned int k = 0; k < kScanPer; k++) {
+            x[c][k] = i0 + k < n ? s.in[c][i0 + k] : 0u;
+            own = op(own, x[c][k]);
+        }
+        const unsigned int incl = waveInclusive(own, op);
+        const unsigned int frontAll = waveReduce(front[c], op);
+        excl[c] = waveExclusiveOf(incl);
+        if (lane == 63) { waveOwn[c][wave] = incl; waveFront[c][wave] = frontAll; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (unsigned int c = 0; c < COLS; c++) {
+        const ColumnOp op{c};
+        unsigned int before = 0;                                /* the fronts of all waves, and the values of the waves in front of this one */
+        for (unsigned int w = 0; w < 16; w++) {
+            before = op(before, waveFront[c][w]);
+            if (w < wave) before = op(before, waveOwn[c][w]);
+        }
+        unsigned int run = op(before, excl[c]);
+#pragma unroll
+        for (unsigned int k = 0; k < kScanPer; k++) {
+            if (i0 + k < n) s.out[c][i0 + k] = run;
+            run = op(run, x[c][k]);
+        }
+        if (c == 0 && blockIdx.x == gridDim.x - 1 && threadIdx.x == 1023) {       /* the last thread of the last block has seen everything */
+            s.out[0][n] = run;
+            if (hostTotal != nullptr) {
+                __hip_atomic_store(hostTotal, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __threadfence_system();
+            }
+        }
+    }
+}
+
+/* the launch: the one place that knows the grid */
+template <class Op0, class Op1 = Op0, unsigned int COLS = 1>
+inline void blockScan(const ScanColumns &s, unsigned int n, unsigned int *hostTotal, unsigned int *zero)
+{
+    hipLaunchKernelGGL((pfac_block_scan<Op0, Op1, COLS>), dim3((n + kScanBlock - 1) / kScanBlock), dim3(1024), 0, 0, s, n, hostTotal, zero);
 }
 
 /* ------------------------------------------------------------------ the seam of a stream (scan_stream.hip, scan_flows.hip) */

@@ -8,11 +8,11 @@
  * head, the last one at the maximum of all ends.  A BLOCK is 512 pairs, two per thread.
  *
  *   pfac_spans_reduce         the largest end of each block of pairs
- *   pfac_spans_block_scan<1>  the exclusive prefix MAXIMUM of those (what every block carries in from all the blocks in front of it, however far back
- *                             the largest end lies); a block of 1024 threads per 8192 values that folds what lies in front of its values itself, as
- *                             pfac_lines_block_scan does: no block waits on another, no chain of steps for the 4 Mi values of 2^31 pairs
+ *   pfac_block_scan<max>      the exclusive prefix MAXIMUM of those (what every block carries in from all the blocks in front of it, however far back
+ *                             the largest end lies); scan_passes.h: a block of 1024 threads per 8192 values that folds what lies in front of its
+ *                             values itself: no block waits on another, no chain of steps for the 4 Mi values of 2^31 pairs
  *   pfac_spans_heads<0>       E_i by a max-scan over the wave (shuffles) and the block, the head flags, the heads of each block
- *   pfac_spans_block_scan<0>  their exclusive prefix sum: the first span of each block, the number of spans
+ *   pfac_block_scan<sum>      their exclusive prefix sum: the first span of each block, the number of spans
  *   pfac_spans_heads<1>       the same walk again: head k writes start_k and end_(k-1) = E_i into handle scratch -- not over the pair list: span k may
  *                             land on a pair that another block has not read yet
  *   pfac_spans_emit           (start, len) of the spans over the caller's arrays, the sum of the lengths
@@ -26,7 +26,7 @@
  * starts behind its last by a 64-ary search of one wave over the list (a probe per lane and round), stages the spans in between in LDS, 1024 at a time --
  * an ascending disjoint list has at most 2049 in a tile, so three trips is all a tile ever makes --, and every thread builds the 16-bit cover mask of
  * its 16 bytes from a binary search in the staged ends, blends and stores them as one aligned 16-byte store.  Source bytes that lie m bytes into an
- * aligned block come out of two aligned loads with v_alignbyte, as in scan_fold.hip; whatever hangs over an end of either buffer goes byte by byte with
+ * aligned block come out of two aligned loads with v_alignbyte (scan_passes.h: funnel); whatever hangs over an end of either buffer goes byte by byte with
  * bounds.  Every (start, len) is clamped to [0, size] where it is read: a bad list gives wrong text, never an access outside the buffers.  In place,
  * only threads that cover something write.  No scratch.  Plain C++ and vector stores only.
  */
@@ -45,7 +45,6 @@ namespace {
 constexpr unsigned int kSpanThreads = 256;
 constexpr unsigned int kSpanPer = 2;                                   /* consecutive pairs per thread */
 constexpr unsigned int kSpanBlock = kSpanThreads * kSpanPer;           /* 512 pairs per block */
-constexpr unsigned int kScanPer = 8;                                   /* values per thread of pfac_spans_block_scan */
 constexpr unsigned int kTile = 4096;                                   /* output bytes per tile of the redaction */
 constexpr unsigned int kStage = 1024;                                  /* spans a tile stages at a time */
 constexpr unsigned int kStageTrips = 3;                                /* kStage * kStageTrips >= kTile / 2 + 1 */
@@ -66,50 +65,11 @@ struct SpanArgs {
     int *spanStart, *spanLen;
 };
 
-__device__ __forceinline__ unsigned int umax(unsigned int a, unsigned int b) { return a > b ? a : b; }
-
 /* position and end of pair i, both inside [0, n] whatever the pair says */
 __device__ __forceinline__ void pairOf(const SpanArgs &a, unsigned int i, unsigned int &p, unsigned int &e)
 {
-    const int at = a.pos[i], id = a.ids[i];
-    p = at < 0 ? 0u : ((unsigned int)at > a.n ? a.n : (unsigned int)at);
-    const int len = (unsigned int)id < a.numIds ? a.patternLen[id] : 0;
-    e = len <= 0 ? p : ((unsigned int)len > a.n - p ? a.n : p + (unsigned int)len);
-}
-
-/* inclusive prefix maximum over the 64 lanes */
-__device__ __forceinline__ unsigned int waveInclusiveMax(unsigned int v)
-{
-    const unsigned int lane = threadIdx.x & 63u;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned int up = __shfl_up(v, d);
-        if ((int)lane >= d) v = umax(v, up);
-    }
-    return v;
-}
-
-/* exclusive prefix maximum of `own` over the block's BLOCK threads (0 in front of thread 0), and the block's maximum; waveTop: BLOCK / 64 entries
- * of LDS, free again at the next call */
-template <unsigned int BLOCK>
-__device__ __forceinline__ unsigned int blockExclusiveMax(unsigned int own, unsigned int *waveTop, unsigned int &top)
-{
-    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const unsigned int incl = waveInclusiveMax(own);
-    unsigned int excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = 0;
-    __syncthreads();                                    /* waveTop may still be read from the previous call */
-    if (lane == 63) waveTop[wave] = incl;
-    __syncthreads();
-    unsigned int before = 0;
-    top = 0;
-#pragma unroll
-    for (unsigned int w = 0; w < BLOCK / 64; w++) {
-        const unsigned int s = waveTop[w];
-        before = w < wave ? umax(before, s) : before;
-        top = umax(top, s);
-    }
-    return umax(before, excl);
+    const int id = a.ids[i];
+    clampSpan(a.pos[i], (unsigned int)id < a.numIds ? a.patternLen[id] : 0, a.n, p, e);
 }
 
 __global__ __launch_bounds__(kSpanThreads) void pfac_spans_reduce(SpanArgs a)
@@ -122,61 +82,12 @@ __global__ __launch_bounds__(kSpanThreads) void pfac_spans_reduce(SpanArgs a)
         if (i0 + k < a.count) {
             unsigned int p, e;
             pairOf(a, i0 + k, p, e);
-            own = umax(own, e);
+            own = OpMax()(own, e);
         }
     }
     unsigned int top = 0;
-    (void)blockExclusiveMax<kSpanThreads>(own, waveTop, top);
+    (void)blockExclusive<kSpanThreads>(own, waveTop, top, OpMax());
     if (threadIdx.x == 0) a.blockMax[blockIdx.x] = top;
-}
-
-/* out[0, n) = the exclusive prefix of v[0, n) under + (MAX == 0) or max (MAX == 1, values >= 0: 0 in front of the first), out[n] = that of all.  A
- * block of 1024 threads per 8192 values; block k folds everything in front of its values itself -- coalesced, from L2 -- so no block waits on another.
- * v and out are different arrays: the blocks read each other's input.  zero (or null): a word block 0 clears for the launches behind it */
-template <int MAX>
-__global__ __launch_bounds__(1024) void pfac_spans_block_scan(const unsigned int *v, unsigned int *out, unsigned int n, unsigned int *zero)
-{
-    __shared__ unsigned int waveOwn[16], waveFront[16];
-    auto op = [](unsigned int x, unsigned int y) { return MAX ? umax(x, y) : x + y; };
-    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const unsigned int base = blockIdx.x * 1024u * kScanPer;
-    if (zero != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *zero = 0;
-    unsigned int front = 0;
-    for (unsigned int q = threadIdx.x; q < base / 4u; q += 1024u) {                 /* base is a multiple of 8192 */
-        const pfacmod::u32x4 c = reinterpret_cast<const pfacmod::u32x4 *>(v)[q];
-        front = op(front, op(op(c.x, c.y), op(c.z, c.w)));
-    }
-    const unsigned int i0 = base + threadIdx.x * kScanPer;
-    unsigned int x[kScanPer], own = 0;
-#pragma unroll
-    for (unsigned int k = 0; k < kScanPer; k++) {
-        x[k] = i0 + k < n ? v[i0 + k] : 0u;
-        own = op(own, x[k]);
-    }
-    unsigned int incl = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned int up = __shfl_up(incl, d);
-        if ((int)lane >= d) incl = op(incl, up);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) front = op(front, __shfl_xor(front, d));
-    unsigned int excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = 0;
-    if (lane == 63) { waveOwn[wave] = incl; waveFront[wave] = front; }
-    __syncthreads();
-    unsigned int before = 0;
-    for (unsigned int w = 0; w < 16; w++) {
-        before = op(before, waveFront[w]);
-        if (w < wave) before = op(before, waveOwn[w]);
-    }
-    unsigned int run = op(before, excl);
-#pragma unroll
-    for (unsigned int k = 0; k < kScanPer; k++) {
-        if (i0 + k < n) out[i0 + k] = run;
-        run = op(run, x[k]);
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 1023) out[n] = run;            /* the last thread of the last block has seen everything */
 }
 
 /* WRITE == 0: the heads of each block; WRITE == 1: start of span k, end of span k - 1 */
@@ -192,15 +103,15 @@ __global__ __launch_bounds__(kSpanThreads) void pfac_spans_heads(SpanArgs a)
         p[k] = 0;
         e[k] = 0;
         if (i0 + k < a.count) pairOf(a, i0 + k, p[k], e[k]);
-        own = umax(own, e[k]);
+        own = OpMax()(own, e[k]);
     }
     unsigned int top = 0;
-    const unsigned int carried = umax(a.blockTop[blockIdx.x], blockExclusiveMax<kSpanThreads>(own, waveTop, top));      /* E of the thread's first pair */
+    const unsigned int carried = OpMax()(a.blockTop[blockIdx.x], blockExclusive<kSpanThreads>(own, waveTop, top, OpMax()));      /* E of the thread's first pair */
     unsigned int run = carried, heads = 0;
 #pragma unroll
     for (unsigned int k = 0; k < kSpanPer; k++) {
         if (i0 + k < a.count && (i0 + k == 0 || p[k] > run)) heads |= 1u << k;
-        run = umax(run, e[k]);
+        run = OpMax()(run, e[k]);
     }
     const unsigned int nh = (unsigned int)__popc(heads);
     unsigned int total = 0;
@@ -217,7 +128,7 @@ __global__ __launch_bounds__(kSpanThreads) void pfac_spans_heads(SpanArgs a)
                 if (o > 0 && o - 1 < a.bound) a.outEnd[o - 1] = run;
                 o++;
             }
-            run = umax(run, e[k]);
+            run = OpMax()(run, e[k]);
         }
     }
 }
@@ -264,17 +175,8 @@ struct RedactArgs {
     unsigned int inPlace;
 };
 
-__device__ __forceinline__ unsigned int spanStartOf(const RedactArgs &a, unsigned int i)
-{
-    const int s = a.start[i];
-    return s < 0 ? 0u : ((unsigned int)s > a.n ? a.n : (unsigned int)s);
-}
-__device__ __forceinline__ unsigned int spanEndOf(const RedactArgs &a, unsigned int i)
-{
-    const unsigned int s = spanStartOf(a, i);
-    const int l = a.len[i];
-    return l <= 0 ? s : ((unsigned int)l > a.n - s ? a.n : s + (unsigned int)l);
-}
+/* span i as bytes [s, e) (a caller that wants only s never loads the length) */
+__device__ __forceinline__ void spanOf(const RedactArgs &a, unsigned int i, unsigned int &s, unsigned int &e) { clampSpan(a.start[i], a.len[i], a.n, s, e); }
 
 /* the first i of [lo, hi) with pred(i), hi if there is none, for a pred that is false, then true (any other pred: some index of [lo, hi]); the
  * whole wave calls it and gets the same answer: a probe per lane and round, the range shrinks 65-fold a round */
@@ -296,15 +198,6 @@ __device__ __forceinline__ unsigned int waveLowerBound(unsigned int lo, unsigned
     }
     const unsigned long long yes = __ballot(lane < hi - lo && pred(lo + lane));
     return yes == 0 ? hi : lo + (unsigned int)__ffsll((long long)yes) - 1u;
-}
-
-/* 16 bytes starting m = 4 Q + r bytes into the 32 of a | b (scan_fold.hip) */
-template <int Q>
-__device__ __forceinline__ pfacmod::u32x4 funnel(pfacmod::u32x4 a, pfacmod::u32x4 b, uint32_t r)
-{
-    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return pfacmod::u32x4{__builtin_amdgcn_alignbyte(w[Q + 1], w[Q], r), __builtin_amdgcn_alignbyte(w[Q + 2], w[Q + 1], r),
-                          __builtin_amdgcn_alignbyte(w[Q + 3], w[Q + 2], r), __builtin_amdgcn_alignbyte(w[Q + 4], w[Q + 3], r)};
 }
 
 /* in[o, o + 16), o + 16 <= n: one aligned load, two and a funnel, or -- where an aligned block would reach outside the buffer -- sixteen bytes */
@@ -344,9 +237,9 @@ __global__ __launch_bounds__(kSpanThreads) void pfac_spans_redact(RedactArgs a)
         const unsigned int oHi = vLo + kTile - a.misOut < a.n ? (unsigned int)(vLo + kTile - a.misOut) : a.n;
         if (t < 64u) {
             /* the first span that ends behind oLo, and the first behind it that starts at or behind oHi */
-            const unsigned int first = waveLowerBound(0u, a.count, [&](unsigned int i) { return spanEndOf(a, i) > oLo; });
+            const unsigned int first = waveLowerBound(0u, a.count, [&](unsigned int i) { unsigned int s, e; spanOf(a, i, s, e); return e > oLo; });
             const unsigned int limit = a.count - first < kStage * kStageTrips ? a.count : first + kStage * kStageTrips;
-            const unsigned int behind = waveLowerBound(first, limit, [&](unsigned int i) { return spanStartOf(a, i) >= oHi; });
+            const unsigned int behind = waveLowerBound(first, limit, [&](unsigned int i) { unsigned int s, e; spanOf(a, i, s, e); return s >= oHi; });
             if (t == 0) { sFirst = first; sCount = behind - first; }
         }
         __syncthreads();
@@ -360,8 +253,7 @@ __global__ __launch_bounds__(kSpanThreads) void pfac_spans_redact(RedactArgs a)
             const unsigned int cnt = total - base < kStage ? total - base : kStage;
             if (base != 0) __syncthreads();                       /* the stage is rewritten */
             for (unsigned int j = t; j < cnt; j += kSpanThreads) {
-                sStart[j] = spanStartOf(a, first + base + j);
-                sEnd[j] = spanEndOf(a, first + base + j);
+                spanOf(a, first + base + j, sStart[j], sEnd[j]);
             }
             __syncthreads();
             if (active) {
@@ -412,14 +304,9 @@ PFAC_status_t PFACX_spansSelect(PFAC_handle_t handle, char *d_scan, size_t size,
     PFAC_context *c = handle;
 
     /* the compacted scan with its ordering launches: ids in d_spanStart, positions in d_spanLen, ascending */
-    int count = 0;
-    const bool wasUnordered = c->reduceUnordered;
-    c->reduceUnordered = false;
-    const PFAC_status_t st = hashed ? PFAC_reduce_inplace_kernel(handle, reinterpret_cast<int *>(d_scan), (int)size, d_spanStart, d_spanLen, &count, nullptr, nullptr)
-                                    : PFAC_reduce_kernel(handle, reinterpret_cast<int *>(d_scan), (int)size, d_spanStart, d_spanLen, &count, nullptr, nullptr);
-    c->reduceUnordered = wasUnordered;
+    size_t count = 0;
+    const PFAC_status_t st = compactedScan(handle, d_scan, size, hashed, d_spanStart, d_spanLen, true, &count);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
     *h_numSpans = 0;
     *h_coveredBytes = 0;
     if (count == 0) return PFAC_STATUS_SUCCESS;
@@ -431,44 +318,38 @@ PFAC_status_t PFACX_spansSelect(PFAC_handle_t handle, char *d_scan, size_t size,
     a.n = (unsigned int)size;
     a.patternLen = d_patternLen;
     a.numIds = (unsigned int)(numIds < (size_t)0x7fffffff ? numIds : (size_t)0x7fffffff);
-    const size_t blocks = ((size_t)count + kSpanBlock - 1) / kSpanBlock;
-    const size_t bound = (size_t)count < (size + 1) / 2 ? (size_t)count : (size + 1) / 2;
+    const size_t blocks = (count + kSpanBlock - 1) / kSpanBlock;
+    const size_t bound = count < (size + 1) / 2 ? count : (size + 1) / 2;
     a.blocks = (unsigned int)blocks;
     a.bound = (unsigned int)bound;
-    const size_t oStart = 0, oEnd = oStart + round256(bound * 4), oMax = oEnd + round256(bound * 4), oTop = oMax + round256(blocks * 4),
-                 oCount = oTop + round256((blocks + 1) * 4), oBase = oCount + round256(blocks * 4), oValue = oBase + round256((blocks + 1) * 4),
-                 bytes = oValue + 256;
-    if (c->scratch.spans.count() < bytes && c->scratch.spans.reserve(bytes) != PFAC_STATUS_SUCCESS) return PFAC_STATUS_CUDA_ALLOC_FAILED;
-    char *s = c->scratch.spans.get();
-    a.outStart = reinterpret_cast<unsigned int *>(s + oStart);
-    a.outEnd = reinterpret_cast<unsigned int *>(s + oEnd);
-    a.blockMax = reinterpret_cast<unsigned int *>(s + oMax);
-    a.blockTop = reinterpret_cast<unsigned int *>(s + oTop);
-    a.headCount = reinterpret_cast<unsigned int *>(s + oCount);
-    a.headBase = reinterpret_cast<unsigned int *>(s + oBase);
-    a.value = reinterpret_cast<unsigned long long *>(s + oValue);
-    a.covered = reinterpret_cast<unsigned int *>(s + oValue + 8);
+    ScratchCarver k;
+    for (int pass = 0; pass < 2; pass++) {
+        a.outStart = k.take<unsigned int>(bound);
+        a.outEnd = k.take<unsigned int>(bound);
+        a.blockMax = k.take<unsigned int>(blocks);
+        a.blockTop = k.take<unsigned int>(blocks + 1);
+        a.headCount = k.take<unsigned int>(blocks);
+        a.headBase = k.take<unsigned int>(blocks + 1);
+        a.value = k.take<unsigned long long>(1, 8);            /* and, behind it, the word `covered` */
+        if (pass == 0) {
+            if (c->scratch.spans.count() < k.bytes && c->scratch.spans.reserve(k.bytes) != PFAC_STATUS_SUCCESS) return PFAC_STATUS_CUDA_ALLOC_FAILED;
+            k = ScratchCarver{c->scratch.spans.get()};
+        }
+    }
+    a.covered = reinterpret_cast<unsigned int *>(a.value + 1);
     a.spanStart = d_spanStart;
     a.spanLen = d_spanLen;
-    const bool mapped = hostMapped(c);
-    const HostHandoff counts = mapped ? HostHandoff(c, pfac::kHostSpans) : HostHandoff();
-    const unsigned int scanGrid = (a.blocks + 1024u * kScanPer - 1u) / (1024u * kScanPer);
+    const HostHandoff counts(c, pfac::kHostSpans);
 
     hipLaunchKernelGGL(pfac_spans_reduce, dim3(a.blocks), dim3(kSpanThreads), 0, 0, a);
-    hipLaunchKernelGGL(pfac_spans_block_scan<1>, dim3(scanGrid), dim3(1024), 0, 0, (const unsigned int *)a.blockMax, a.blockTop, a.blocks, a.covered);
+    blockScan<OpMax>({{a.blockMax}, {a.blockTop}}, a.blocks, nullptr, a.covered);
     hipLaunchKernelGGL(pfac_spans_heads<0>, dim3(a.blocks), dim3(kSpanThreads), 0, 0, a);
-    hipLaunchKernelGGL(pfac_spans_block_scan<0>, dim3(scanGrid), dim3(1024), 0, 0, (const unsigned int *)a.headCount, a.headBase, a.blocks, (unsigned int *)nullptr);
+    blockScan<OpSum>({{a.headCount}, {a.headBase}}, a.blocks, nullptr, nullptr);
     hipLaunchKernelGGL(pfac_spans_heads<1>, dim3(a.blocks), dim3(kSpanThreads), 0, 0, a);
     hipLaunchKernelGGL(pfac_spans_emit, dim3(gridFor(c, bound)), dim3(kSpanThreads), 0, 0, a);
     hipLaunchKernelGGL(pfac_spans_finish, dim3(1), dim3(1), 0, 0, a, reinterpret_cast<unsigned long long *>(counts.d_value));
     unsigned long long v = 0;
-    if (mapped) {
-        counts.queueDone();
-        if (!counts.wait()) return PFAC_STATUS_INTERNAL_ERROR;
-        v = counts.value64();
-    } else if (hipGetLastError() != hipSuccess || hipMemcpy(&v, a.value, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) {
-        return PFAC_STATUS_INTERNAL_ERROR;
-    }
+    if (!counts.finish(&v, a.value)) return PFAC_STATUS_INTERNAL_ERROR;
     const size_t spans = (size_t)(v & 0xFFFFFFFFull), covered = (size_t)(v >> 32);
     if (spans == 0 || spans > bound || covered < spans || covered > size) return PFAC_STATUS_INTERNAL_ERROR;
     *h_numSpans = spans;

@@ -324,6 +324,48 @@ def test_a_million_lines(workdir):
         h.destroy()
 
 
+def long_line_behind_a_block_of_the_block_scan():
+    """(patterns, input): 16 MiB + 16 KiB of short lines with one line that runs from block 8189 into block 8194 of the newline bitmap.  Blocks
+    8190 .. 8193 hold no newline, so the start of the line that ends in block 8194 -- the third value of the second block of the block-value scan
+    -- is the running maximum that this scan folds over the values in front of its block, and the largest lies at entry 8189, not in the last"""
+    pats = [b"NEEDLE"]
+    n = (16 << 20) + (16 << 10)
+    rng = np.random.Generator(np.random.PCG64(8194))
+    data = rng.integers(97, 123, size=n, dtype=np.uint8)
+    data[rng.random(n) < 1.0 / 60] = 10
+    lo, hi = 8190 * 2048, 8194 * 2048 + 100
+    data[lo - 700:hi + 1][data[lo - 700:hi + 1] == 10] = ord("a")
+    data[lo - 700] = 10                                      # the long line: [lo - 699, hi + 50)
+    data[hi + 50] = 10
+    for at in (1000, 5 << 20, lo + 4000, n - 3000):          # once inside the long line, and in a few short ones
+        data[at:at + 6] = np.frombuffer(b"NEEDLE", dtype=np.uint8)
+    ends = np.flatnonzero(data == 10)
+    k = int(np.searchsorted(ends, lo))
+    assert ends[k - 1] // 2048 == 8189 and ends[k] // 2048 == 8194 and ends[k] > hi
+    return pats, data
+
+
+def test_a_line_that_starts_in_front_of_a_block_of_the_block_scan(workdir):
+    pats, data = long_line_behind_a_block_of_the_block_scan()
+    pf = pattern_file(workdir, "scanblock", pats)
+    ho = api.PFAC.createHostOnly()
+    try:
+        ho.readPatternFromFile(pf)
+        want = {inv: host_lines(ho, data, inv)[0] for inv in (False, True)}
+    finally:
+        ho.destroy()
+    result = ref.brute_result(pats, data.tobytes())
+    for inv in (False, True):
+        ref.same(want[inv], ref.lines_from_result(result, data, inv), f"host engine/invert {inv}")
+    assert 8 * 1024 < want[False][2].max() < 9 * 1024 and want[False][1].size == 4
+    h = gpu_handle(pf)
+    try:
+        for inv in (False, True):
+            ref.same(device_lines(h, data, inv), want[inv], f"long line/invert {inv}")
+    finally:
+        h.destroy()
+
+
 # ---------------------------------------------------------------- shared state, trim, scratch accounting
 
 

@@ -203,20 +203,33 @@ def test_each_side_of_the_32_mib_switch(workloads, mib):
 LONG = b"L" + b"x" * 1998 + b"R"                                # 2000 bytes; the 1998 one-byte matches inside it are more than three blocks of pairs
 
 
-@pytest.mark.parametrize("lead", [0, PAIR_BLOCK - 1, PAIR_BLOCK, 3 * PAIR_BLOCK + 7])
+@pytest.mark.parametrize("lead", [0, PAIR_BLOCK - 1, PAIR_BLOCK, 3 * PAIR_BLOCK + 7, 8191 * PAIR_BLOCK - 100])
 def test_running_maximum_across_blocks_of_pairs(workdir, lead):
     """`lead` one-byte spans in front make the long match pair number `lead`: the last pair of a block, the first of the next.  Every x inside the
-    long match lies under an end that comes from up to four blocks back; the x behind the gap does not"""
+    long match lies under an end that comes from up to four blocks back; the x behind the gap does not.  The last lead puts the long match into
+    block 8190 and the pairs under it into blocks 8191 .. 8194: block 8192 is the first value of the second block of the block-value scan, so what
+    it carries in comes from that scan's fold over the values in front of it alone, and the largest end lies two values back, not in the last"""
     assert 1998 > 3 * PAIR_BLOCK
     data = b"x." * lead + LONG + b".x"
-    h = gpu_handle(pattern_file(workdir, "runmax", [LONG, b"x"]))
+    pf = pattern_file(workdir, "runmax", [LONG, b"x"])
+    h = gpu_handle(pf)
     try:
         got, covered = device_spans(h, data)
         at = 2 * lead
-        want = (np.array(list(range(0, at, 2)) + [at, at + 2001], dtype=np.int32), np.array([1] * lead + [2000, 1], dtype=np.int32))
+        want = (np.append(np.arange(0, at, 2), [at, at + 2001]).astype(np.int32), np.append(np.ones(lead), [2000, 1]).astype(np.int32))
         ref.same(got, want, f"lead {lead}")
         assert got[0].size == lead + 2 and covered == lead + 2001
-        ref.same(got, ref.spans_py([LONG, b"x"], data), f"lead {lead}/pure python")
+        if lead < 8192:
+            ref.same(got, ref.spans_py([LONG, b"x"], data), f"lead {lead}/pure python")
+        else:                                                      # minutes of pure Python: the host engine instead
+            ho = api.PFAC.createHostOnly()
+            try:
+                ho.readPatternFromFile(pf)
+                host, host_covered, _ = host_spans(ho, data)
+            finally:
+                ho.destroy()
+            ref.same(got, host, f"lead {lead}/host engine")
+            assert covered == host_covered
     finally:
         h.destroy()
 

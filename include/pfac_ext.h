@@ -10,9 +10,11 @@
  * does not have: batches of segments (PFACX_matchBatch*), every pattern at a
  * position (PFACX_matchAll*), caseless sets (PFACX_READ_NOCASE), streams
  * (PFACX_stream*), flow sets (PFACX_flows*), the lines that contain a
- * pattern (PFACX_matchLines*, PFACX_gatherLinesFromDevice) and the bytes that
+ * pattern (PFACX_matchLines*, PFACX_gatherLinesFromDevice), the bytes that
  * belong to a match, with their redaction (PFACX_matchSpans*,
- * PFACX_redactSpansFromDevice).
+ * PFACX_redactSpansFromDevice) and the number of occurrences of every pattern
+ * (PFACX_countFromDevice / ...FromHost, PFACX_countPairsFromDevice,
+ * PFACX_countNonzeroFromDevice).
  */
 #ifndef PFAC_EXT_H_
 #define PFAC_EXT_H_
@@ -505,6 +507,56 @@ PFAC_status_t PFACX_matchSpansFromHost  (PFAC_handle_t handle, char *h_input, si
 PFAC_status_t PFACX_redactSpansFromDevice(PFAC_handle_t handle, const char *d_input, size_t size,
                                           const int *d_spanStart, const int *d_spanLen, size_t numSpans,
                                           unsigned char fill, char *d_out);
+
+/* Counts: which patterns occurred, and how often -- hit counts per rule, term frequencies, grep -c per keyword -- without a pair list.
+ *   Let F = numOfPatterns and r be the full result of PFAC_matchFromHost on a CPU platform over the buffer.
+ *   L[id] = #{p : r[p] == id} is the LONGEST histogram; A[id] = #{p : pattern id occurs at p} counts ALL occurrences: the number of pairs with that
+ *   id in the all-match list of PFACX_matchAll*.  Every pattern that occurs at p is a prefix of the longest one there, so A[id] = L[id] + the sum of
+ *   A[q] over all q with PFACX_TABLE_PREFIX_PATTERN[q] == id: the counts follow from the longest matches and never cost the expanded list.
+ *   Duplicate lines are one pattern, counted under the highest of their IDs; the lower IDs stay 0.  A caseless handle (PFACX_READ_NOCASE) counts the
+ *   folded set over the folded input; the caller's bytes are never modified.
+ * counts[] is indexed by pattern id: numCounts >= F + 1 entries (smaller: PFAC_STATUS_INVALID_PARAMETER).  Entries [0, F] are written: counts[id] = A[id]
+ * (PFACX_COUNT_LONGEST: L[id]), entry 0 = 0.  With PFACX_COUNT_ACCUMULATE the call ADDS to entries [1, F] instead and leaves entry 0 alone: many buffers,
+ * the pieces of a stream.  Nothing at or beyond F + 1 is ever written.
+ * PFACX_countFromDevice / ...FromHost: *h_total = what this call added -- the sum of the chain lengths over the longest pairs, exactly *h_num_matched of
+ * PFACX_matchAll* for the same input; with PFACX_COUNT_LONGEST the number of pairs.  Both are synchronous (the scan's count comes to the host) and take
+ * the handle's lock.  size >= 2^31, an unknown flag bit or a null pointer: PFAC_STATUS_INVALID_PARAMETER; no pattern set: PFAC_STATUS_PATTERNS_NOT_READY;
+ * size == 0: success, *h_total = 0, the counts zeroed (untouched under ACCUMULATE); the device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.
+ * The device form runs on whatever kernel variant, walker, perf mode and texture mode the handle selects.  The host form follows PFAC_setPlatform:
+ * the CPU platforms, host-only handles included, run the CPU matcher plus a host loop over internal temporaries (4 bytes per input byte; a failed
+ * allocation: PFAC_STATUS_ALLOC_FAILED); the GPU platform runs the pipelined path of PFAC_matchFromHostReduce (temporaries of 8 bytes per input byte)
+ * and builds the histogram on the host.
+ * PFACX_countPairsFromDevice: the same counts from a list of pair ids the caller already has -- the ids any compacted call returned (reduce, batch,
+ * stream, flows); with ACCUMULATE over the pieces of a stream and its flush, the counts of the stream.  WITHOUT PFACX_COUNT_LONGEST EVERY PAIR ALSO
+ * COUNTS FOR EVERY PATTERN ON ITS PREFIX CHAIN, SO THE LIST MUST BE A LONGEST LIST (one pair per position), NOT THE ALL-MATCH LIST OF PFACX_matchAll*
+ * -- that list counts with PFACX_COUNT_LONGEST.  d_ids is DEVICE memory and the caller's contract: any 4-byte alignment; an id outside [1, F] is
+ * ignored, never used as an index.  numPairs == 0: the counts zeroed, or nothing under ACCUMULATE (d_ids may then be null); numPairs >= 2^31:
+ * PFAC_STATUS_INVALID_PARAMETER.  Asynchronous on the default stream, like PFACX_redactSpansFromDevice: nothing comes back to the host.
+ * PFACX_countNonzeroFromDevice: the patterns that occurred -- (d_ids[i], d_outCounts[i]) = (id, d_counts[id]) for every non-zero entry of
+ * d_counts[0, numCounts), ascending id.  *h_numDistinct = their number, *h_total = the sum of all entries; both are written on every success.  More than
+ * `capacity`: PFACX_STATUS_OUTPUT_TRUNCATED, exactly the first `capacity` entries written and nothing behind them, both values still the full ones (with
+ * capacity == 0 the arrays may be null).  numCounts == 0: success with zeros; numCounts >= 2^31: PFAC_STATUS_INVALID_PARAMETER.  Needs no pattern set:
+ * d_counts[0, numCounts) is taken as given, entry 0 takes part like any other.  Synchronous.
+ * MEMORY of the device forms: grow-only handle scratch, deviceScratchBytes of PFACX_getInfo, freed by PFACX_trim.  PFACX_countFromDevice: the pair list
+ * of the scan in the pair scratch the all-match calls own, 8 bytes per input byte; 4 (F + 1) + 8 bytes for L and the total, each rounded up to 256;
+ * and, for the all-occurrence form of a set in which a pattern is a prefix of another, the {prefix, chain length} table, 8 (F + 1) bytes, shared with
+ * PFACX_matchAll*.  PFACX_countPairsFromDevice: the last two alone.  PFACX_countNonzeroFromDevice, with B = (numCounts + 255) / 256: 4 B + 4 (B + 1) +
+ * 8 B + 16 bytes, each term rounded up to 256 (the same allocation as L: the larger of the two).
+ * COST: the compacted scan WITHOUT its ordering launches, one pass over the pairs, two passes over the F patterns. */
+#define PFACX_COUNT_LONGEST    1u   /* counts = L (one pattern per position) instead of A */
+#define PFACX_COUNT_ACCUMULATE 2u   /* add to counts[] instead of overwriting it: many buffers, the pieces of a stream */
+
+PFAC_status_t PFACX_countFromDevice(PFAC_handle_t handle, char *d_input, size_t size, unsigned int flags,
+                                    unsigned long long *d_counts, size_t numCounts, size_t *h_total);
+PFAC_status_t PFACX_countFromHost  (PFAC_handle_t handle, char *h_input, size_t size, unsigned int flags,
+                                    unsigned long long *h_counts, size_t numCounts, size_t *h_total);
+/* the same histogram from an id list the caller already has (the d_ids of ANY compacted call: reduce, batch, stream, flows) */
+PFAC_status_t PFACX_countPairsFromDevice(PFAC_handle_t handle, const int *d_ids, size_t numPairs, unsigned int flags,
+                                         unsigned long long *d_counts, size_t numCounts);
+/* the patterns that occurred: (id, count) for every counts[id] != 0, ascending id */
+PFAC_status_t PFACX_countNonzeroFromDevice(PFAC_handle_t handle, const unsigned long long *d_counts, size_t numCounts,
+                                           int *d_ids, unsigned long long *d_outCounts, size_t capacity,
+                                           size_t *h_numDistinct, unsigned long long *h_total);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,25 @@ PFAC_status_t PFACX_spansRedact(PFAC_handle_t handle, const char *d_input, size_
 typedef PFAC_status_t (*PFACX_spansSelect_protoType)(PFAC_handle_t, char *, size_t, int, const int *, size_t, int *, int *, size_t *, size_t *);
 typedef PFAC_status_t (*PFACX_spansRedact_protoType)(PFAC_handle_t, const char *, size_t, const int *, const int *, size_t, unsigned char, char *);
 
+/* Occurrence counts (no reference counterpart; include/pfac_ext.h: PFACX_count*), scan_count.hip.
+ * PFACX_countPairs: d_counts[id] (numIds + 1 entries, 64-bit) = how often pattern id occurs, from a list of LONGEST pairs.  d_scan != null: the list is
+ * made here -- the compacted scan of d_scan[0, size), 0 < size < 2^31 (PFAC_reduce_kernel, hashed != 0: PFAC_reduce_inplace_kernel, pairs left
+ * unordered) into the handle's pair scratch (pfac::DeviceScratch::allPairs) -- and d_ids / numPairs are not read; d_scan == null: the list is
+ * d_ids[0, numPairs), numPairs < 2^31, any 4-byte alignment, an id outside [1, numIds] ignored.  d_table (pfac::Int2 {prefixPattern, chainLen} by id,
+ * or null): every pair also counts for the patterns on its prefix chain; null: the longest histogram alone.  flags: PFACX_COUNT_ACCUMULATE adds to
+ * d_counts[1, numIds] and leaves entry 0 alone, else entries [0, numIds] are overwritten.  h_total (or null): what the call added -- chainLen per
+ * pair with a table, else 1; given, the call is synchronous, else asynchronous on the default stream.
+ * PFACX_countNonzero: (i, d_counts[i]) for every non-zero entry of d_counts[0, numCounts), 0 < numCounts < 2^31, ascending, into d_ids / d_outCounts;
+ * nothing at or beyond `capacity`; *h_numDistinct and *h_total (the sum of all entries) are the full values.  Synchronous. */
+PFAC_status_t PFACX_countPairs(PFAC_handle_t handle, char *d_scan, size_t size, int hashed, const int *d_ids, size_t numPairs, const void *d_table,
+                               unsigned int flags, unsigned long long *d_counts, size_t *h_total);
+PFAC_status_t PFACX_countNonzero(PFAC_handle_t handle, const unsigned long long *d_counts, size_t numCounts, int *d_ids,
+                                 unsigned long long *d_outCounts, size_t capacity, size_t *h_numDistinct, unsigned long long *h_total);
+typedef PFAC_status_t (*PFACX_countPairs_protoType)(PFAC_handle_t, char *, size_t, int, const int *, size_t, const void *, unsigned int,
+                                                    unsigned long long *, size_t *);
+typedef PFAC_status_t (*PFACX_countNonzero_protoType)(PFAC_handle_t, const unsigned long long *, size_t, int *, unsigned long long *, size_t, size_t *,
+                                                      unsigned long long *);
+
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of
  * `launches` launches over the first n bytes (a multiple of 4096) of d_in, or a negative value on a HIP error.

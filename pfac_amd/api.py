@@ -28,6 +28,9 @@ PFACX_KERNEL_FILTER, PFACX_KERNEL_NAIVE, PFACX_KERNEL_AUTO, PFACX_KERNEL_REFTABL
 PFACX_WALKER_AUTO, PFACX_WALKER_WINDOW, PFACX_WALKER_STAGE, PFACX_WALKER_VETO = 0, 1, 2, 3
 PFACX_READ_STRICT, PFACX_READ_STRIP_CR, PFACX_READ_NOCASE = 1, 2, 8
 PFACX_LINES_INVERT = 1                          # pfac_ext.h: PFACX_matchLines* select the lines that do NOT match
+PFACX_COUNT_LONGEST = 1                         # pfac_ext.h: PFACX_count* count one pattern per position, the longest
+PFACX_COUNT_ACCUMULATE = 2                      # ... add to counts[] instead of overwriting it
+PFACX_COUNT_LDS_DIRECT = 16384                  # scan_count.hip: kCountDirect -- sets with F + 1 <= this count into a counter per id in LDS, larger ones into a tagged cache
 (PFACX_TABLE_DENSE, PFACX_TABLE_HASH_ROWPTR, PFACX_TABLE_HASH_VALPTR, PFACX_TABLE_INITIAL_ROW,
  PFACX_TABLE_FILTER_GRAM3, PFACX_TABLE_FILTER_SHORT, PFACX_TABLE_FILTER_LADDER, PFACX_TABLE_FILTER_FINAL3,
  PFACX_TABLE_CHAIN) = range(9)
@@ -109,6 +112,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_flowsOpen", "PFACX_flowsClose", "PFACX_flowsReset", "PFACX_flowsMatchFromDevice", "PFACX_flowsMatchFromHost", "PFACX_flowsFlush",
     "PFACX_matchLinesFromDevice", "PFACX_matchLinesFromHost", "PFACX_gatherLinesFromDevice",
     "PFACX_matchSpansFromDevice", "PFACX_matchSpansFromHost", "PFACX_redactSpansFromDevice",
+    "PFACX_countFromDevice", "PFACX_countFromHost", "PFACX_countPairsFromDevice", "PFACX_countNonzeroFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -118,6 +122,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_streamSeam", "PFACX_streamReduce", "PFACX_flowsRun",
     "PFACX_linesSelect", "PFACX_linesGather", "PFACX_linesBitmapProbe",
     "PFACX_spansSelect", "PFACX_spansRedact",
+    "PFACX_countPairs", "PFACX_countNonzero",
 )
 
 
@@ -211,6 +216,13 @@ def load_library() -> C.CDLL:
         lib.PFACX_matchSpansFromDevice.argtypes = spans
         lib.PFACX_matchSpansFromHost.argtypes = spans
         lib.PFACX_redactSpansFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_ubyte, C.c_void_p]
+    if hasattr(lib, "PFACX_countFromDevice"):
+        SZ = C.POINTER(C.c_size_t)
+        count = [H, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t, SZ]
+        lib.PFACX_countFromDevice.argtypes = count
+        lib.PFACX_countFromHost.argtypes = count
+        lib.PFACX_countPairsFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t]
+        lib.PFACX_countNonzeroFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, SZ, C.POINTER(C.c_ulonglong)]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -520,6 +532,40 @@ class PFAC:
         length = np.full(cap, -7, dtype=np.int32)
         _, ns, cb = self.matchSpansFromHost(data.ctypes.data if data.size else start.ctypes.data, data.size, start.ctypes.data, length.ctypes.data, cap)
         return start[:ns].copy(), length[:ns].copy(), cb
+
+    # -- which patterns occurred, and how often (include/pfac_ext.h: PFACX_count*) ------------
+    def countFromDevice(self, d_input: int, size: int, flags: int, d_counts: int, num_counts: int, check: bool = True):
+        """``PFACX_countFromDevice`` -> (status, what the call added); `d_counts`: num_counts >= F + 1 ``unsigned long long`` by pattern id."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_countFromDevice(self._h, d_input, size, flags, d_counts, num_counts, C.byref(n))
+        return self._ret(st, "PFACX_countFromDevice", check), n.value
+
+    def countFromHost(self, h_input: int, size: int, flags: int, h_counts: int, num_counts: int, check: bool = True):
+        """``PFACX_countFromHost`` -> (status, what the call added); follows PFAC_setPlatform."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_countFromHost(self._h, h_input, size, flags, h_counts, num_counts, C.byref(n))
+        return self._ret(st, "PFACX_countFromHost", check), n.value
+
+    def countPairsFromDevice(self, d_ids, num_pairs: int, flags: int, d_counts: int, num_counts: int, check: bool = True) -> int:
+        """``PFACX_countPairsFromDevice``: the counts of a LONGEST id list (with PFACX_COUNT_LONGEST: of any id list); asynchronous on the
+        default stream."""
+        return self._ret(self._lib.PFACX_countPairsFromDevice(self._h, d_ids, num_pairs, flags, d_counts, num_counts), "PFACX_countPairsFromDevice", check)
+
+    def countNonzeroFromDevice(self, d_counts, num_counts: int, d_ids, d_out_counts, capacity: int, check: bool = True):
+        """``PFACX_countNonzeroFromDevice`` -> (status, distinct ids, sum of the counts).  OUTPUT_TRUNCATED is returned, not raised."""
+        nd, total = C.c_size_t(0), C.c_ulonglong(0)
+        st = self._lib.PFACX_countNonzeroFromDevice(self._h, d_counts, num_counts, d_ids, d_out_counts, capacity, C.byref(nd), C.byref(total))
+        return self._ret(st, "PFACX_countNonzeroFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), nd.value, total.value
+
+    def count_host_array(self, data, longest: bool = False):
+        """countFromHost over a numpy array -> (counts by pattern id as uint64[F + 1], what the call added): every occurrence of every
+        pattern (longest: one pattern per position)."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        counts = np.full(int(self.info().numOfPatterns) + 1, 0xDEAD, dtype=np.uint64)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        _, total = self.countFromHost(buf.ctypes.data, data.size, PFACX_COUNT_LONGEST if longest else 0, counts.ctypes.data, counts.size)
+        return counts, total
 
     # -- input that arrives in pieces (include/pfac_ext.h: PFACX_stream*) ----------------
     def streamOpen(self, check: bool = True) -> "Stream":

@@ -18,8 +18,8 @@
 
 namespace pfac_internal {
 
-/* the device copy of {prefixPattern, chainLen} by id that the expansion reads (uploaded on the first call that expands) */
-static PFAC_status_t ensureAllTable(PFAC_context *c)
+/* the device copy of {prefixPattern, chainLen} by id that the expansion and the count calls read (uploaded on the first call that needs it) */
+PFAC_status_t ensureAllTable(PFAC_context *c)
 {
     if (c->scratch.allTable) return PFAC_STATUS_SUCCESS;
     std::vector<pfac::Int2> t(c->fa.prefixPattern.size());

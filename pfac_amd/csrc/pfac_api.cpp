@@ -299,7 +299,9 @@ PFAC_status_t loadModule(PFAC_context *c)
     c->lines_gather_ptr = (PFACX_linesGather_protoType)dlsym(m, "PFACX_linesGather");
     c->spans_select_ptr = (PFACX_spansSelect_protoType)dlsym(m, "PFACX_spansSelect");
     c->spans_redact_ptr = (PFACX_spansRedact_protoType)dlsym(m, "PFACX_spansRedact");
-    if (!c->spans_select_ptr || !c->spans_redact_ptr) return PFAC_STATUS_INTERNAL_ERROR;
+    c->count_pairs_ptr = (PFACX_countPairs_protoType)dlsym(m, "PFACX_countPairs");
+    c->count_nonzero_ptr = (PFACX_countNonzero_protoType)dlsym(m, "PFACX_countNonzero");
+    if (!c->spans_select_ptr || !c->spans_redact_ptr || !c->count_pairs_ptr || !c->count_nonzero_ptr) return PFAC_STATUS_INTERNAL_ERROR;
     if (!c->kernel_time_driven_ptr || !c->kernel_space_driven_ptr || !c->reduce_kernel_ptr ||
         !c->reduce_inplace_kernel_ptr || !c->batch_fixup_ptr || !c->batch_reduce_fixup_ptr || !c->all_reduce_ptr || !c->all_expand_ptr ||
         !c->fold_input_ptr || !c->stream_seam_ptr || !c->stream_reduce_ptr || !c->flows_run_ptr || !c->lines_select_ptr || !c->lines_gather_ptr)

@@ -62,7 +62,9 @@ constexpr HostSlot kHostFlows = {14, 15};         /* a flows call: its pairs (sc
 constexpr HostSlot kHostLines = {16, 18};         /* a lines call: the lines, then the selected lines (scan_lines.hip, by pfac_block_scan) */
 constexpr HostSlot kHostGather = {20, 22};        /* a gather: the 64-bit size of its text (scan_lines.hip) */
 constexpr HostSlot kHostSpans = {24, 26};         /* a spans call: one 64-bit value, the spans | the covered bytes << 32 (scan_spans.hip: pfac_spans_finish) */
-constexpr int kHostWords = 32;
+constexpr HostSlot kHostCount = {28, 30};         /* a count call: the 64-bit number of occurrences it added (scan_count.hip: pfac_count_store) */
+constexpr HostSlot kHostNonzero = {32, 36};       /* the non-zero counts: two 64-bit values, the distinct patterns, then the sum of the counts (scan_count.hip: pfac_count_finish) */
+constexpr int kHostWords = 40;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -406,12 +408,16 @@ struct DeviceScratch {
      * its pair-space passes -- 8.04 bytes per pair of the scan at most (scan_spans.hip has the formula); not allocated before the first spans call that
      * finds a pair */
     DeviceBuffer<char> spans;
+    /* the count calls (PFACX_count*, scan_count.hip): ONE allocation a call cuts into the 32-bit longest histogram (4 bytes per pattern) and the word
+     * of its total, or into the per-block values of the non-zero compaction (scan_count.hip has the formula); the pair list of PFACX_countFromDevice is
+     * allPairs, the prefix table allTable: shared with the all-match calls */
+    DeviceBuffer<char> count;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines);
-        f(spans);
+        f(spans); f(count);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }
@@ -489,6 +495,8 @@ struct PFAC_context {
     PFACX_linesGather_protoType lines_gather_ptr = nullptr;
     PFACX_spansSelect_protoType spans_select_ptr = nullptr;          /* scan_spans.hip: the spans calls (PFACX_matchSpans* / PFACX_redactSpansFromDevice) */
     PFACX_spansRedact_protoType spans_redact_ptr = nullptr;
+    PFACX_countPairs_protoType count_pairs_ptr = nullptr;            /* scan_count.hip: the count calls (PFACX_count*) */
+    PFACX_countNonzero_protoType count_nonzero_ptr = nullptr;
 
     int platform = PFAC_PLATFORM_GPU;
     int perfMode = PFAC_TIME_DRIVEN;

@@ -96,6 +96,9 @@ bool batchOffsetsValid(const size_t *offsets, size_t numSegments, size_t size);
 /* batch_api.cpp: the batch calls (PFACX_matchBatch*) behind their argument checks; the caller holds c->lock */
 PFAC_status_t ensurePatternLen(PFAC_context *c);            /* the device copy of fa.patternLen the batch fix-ups read */
 PFAC_status_t matchBatchDeviceLocked(PFAC_context *c, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments, int *d_matched_result);
+/* all_api.cpp: the device copy of {fa.prefixPattern, fa.chainLen} by id (scratch.allTable) that the all-match expansion and the count calls read;
+ * the caller holds c->lock */
+PFAC_status_t ensureAllTable(PFAC_context *c);
 /* host_pipeline.cpp: PFACX_matchBatchFromHost on the GPU platform (h_offsets validated); the caller holds c->lock */
 PFAC_status_t matchBatchHostOnGpu(PFAC_context *c, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments, int *h_matched_result);
 

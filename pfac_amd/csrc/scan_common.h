@@ -11,6 +11,7 @@
  *   scan_flows.hip    pfac_flows_*: the seams of many streams in one launch and the merge with one scan's pairs (PFACX_flows*)
  *   scan_lines.hip    pfac_lines_*: the newline bitmap, the lines the scan's pairs fall into, their selection and gather (PFACX_matchLines*)
  *   scan_spans.hip    pfac_spans_*: the covered spans from the scan's ordered pairs (running maximum of the ends), the redaction (PFACX_matchSpans*)
+ *   scan_count.hip    pfac_count_*: the histogram of the scan's pairs, the counts along the prefix chains, the non-zero counts (PFACX_count*)
  * scan_passes.h holds what the units around the product kernels share on top of this: the hand-off to the host, block prefix sums, the seam.
  */
 #ifndef PFAC_SCAN_COMMON_H_

@@ -1,6 +1,6 @@
 /*
  * scan_passes.h -- what the passes around the scan share (scan_module.hip with scan_order.inc, scan_batch.hip, scan_all.hip, scan_fold.hip,
- * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip; the product kernels' units do not include it): launch sizes, the layout of a
+ * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip; the product kernels' units do not include it): launch sizes, the layout of a
  * call's scratch, the compacted scan as a pass runs it, the hand-off of a call's result to the host through mapped memory, the device fold byte,
  * the clamp of a caller's (start, len), 16 bytes out of two aligned blocks (funnel), wave and block prefixes under a sum or a maximum, the two scan
  * kernels (pfac_array_scan: one block, in place; pfac_block_scan: a block per 8192 values that folds what lies in front of them), the seam of

@@ -57,9 +57,6 @@ PFAC_status_t PFACX_batchFixup(PFAC_handle_t handle, const char *d_input, size_t
                                int *d_matched_result, const int *d_patternLen);
 PFAC_status_t PFACX_batchReduceFixup(PFAC_handle_t handle, const char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
                                      int *d_ids, int *d_pos, int *count, int *d_segFirst, const int *d_patternLen);
-typedef PFAC_status_t (*PFACX_batchFixup_protoType)(PFAC_handle_t, const char *, size_t, const size_t *, size_t, int *, const int *);
-typedef PFAC_status_t (*PFACX_batchReduceFixup_protoType)(PFAC_handle_t, const char *, size_t, const size_t *, size_t, int *, int *, int *, int *,
-                                                          const int *);
 
 /* All matches (no reference counterpart; include/pfac_ext.h: PFACX_matchAll*).
  * PFACX_allReduce, scan_module.hip: PFAC_reduce_kernel (hashed == 0) / PFAC_reduce_inplace_kernel (hashed != 0) whose ordering
@@ -76,15 +73,11 @@ PFAC_status_t PFACX_allReduce(PFAC_handle_t handle, int *d_input_string, int inp
 PFAC_status_t PFACX_allExpand(PFAC_handle_t handle, const int *d_pairIds, const int *d_pairPos, size_t count, const void *d_table,
                               int *d_ids, int *d_pos, size_t capacity, const int *d_segFirstPairs, size_t numSegments, size_t *d_segFirst,
                               size_t *h_total);
-typedef PFAC_status_t (*PFACX_allReduce_protoType)(PFAC_handle_t, int *, int, int *, int *, int *, int);
-typedef PFAC_status_t (*PFACX_allExpand_protoType)(PFAC_handle_t, const int *, const int *, size_t, const void *, int *, int *, size_t,
-                                                   const int *, size_t, size_t *, size_t *);
 
 /* Caseless pattern sets (no reference counterpart; include/pfac_ext.h: PFACX_READ_NOCASE), scan_fold.hip: the ASCII fold of n bytes
  * of src into dst ('A'-'Z' -> 'a'-'z', every other byte unchanged), any alignment and length, in place (src == dst) or into a buffer
  * that does not overlap src.  Asynchronous, on the default stream: the scan behind it reads dst in stream order. */
 PFAC_status_t PFACX_foldInput(PFAC_handle_t handle, const char *src, char *dst, size_t n);
-typedef PFAC_status_t (*PFACX_foldInput_protoType)(PFAC_handle_t, const char *, char *, size_t);
 
 /* Streams (no reference counterpart; include/pfac_ext.h: PFACX_stream*).
  * PFACX_streamSeam, scan_stream.hip: one launch for the seam between the bytes a stream carries and a new piece.  d_carry holds the
@@ -100,8 +93,6 @@ PFAC_status_t PFACX_streamSeam(PFAC_handle_t handle, const char *d_carry, size_t
                                char *d_carryNext, char *d_stage, int *d_ids, int *d_pos, int *h_count);
 PFAC_status_t PFACX_streamReduce(PFAC_handle_t handle, int *d_input_string, int owned, int readable, int *d_match_result, int *d_pos,
                                  int *h_num_matched, int hashed);
-typedef PFAC_status_t (*PFACX_streamSeam_protoType)(PFAC_handle_t, const char *, size_t, const char *, size_t, size_t, char *, char *, int *, int *, int *);
-typedef PFAC_status_t (*PFACX_streamReduce_protoType)(PFAC_handle_t, int *, int, int, int *, int *, int *, int);
 
 /* Flow sets (no reference counterpart; include/pfac_ext.h: PFACX_flows*), scan_flows.hip: the seams of many streams in one launch and
  * the merge of their pairs with the pairs of ONE compacted scan over the whole buffer.  A piece is described on the host:
@@ -134,7 +125,6 @@ typedef struct {
     int *d_pieceFirst;
 } PFACX_flowsRun_t;
 PFAC_status_t PFACX_flowsRun(PFAC_handle_t handle, const PFACX_flowsRun_t *run, int *h_total);
-typedef PFAC_status_t (*PFACX_flowsRun_protoType)(PFAC_handle_t, const PFACX_flowsRun_t *, int *);
 
 /* Lines (no reference counterpart; include/pfac_ext.h: PFACX_matchLines* / PFACX_gatherLines*), scan_lines.hip.
  * PFACX_linesSelect: the lines of d_input[0, size) -- 0 < size < 2^31 -- that contain a match (invert != 0: that contain none).  d_scan is what the
@@ -147,8 +137,6 @@ PFAC_status_t PFACX_linesSelect(PFAC_handle_t handle, const char *d_input, char 
                                 int *d_lineLen, int *d_lineIndex, size_t *h_numLines, size_t *h_numSelected);
 PFAC_status_t PFACX_linesGather(PFAC_handle_t handle, const char *d_input, size_t size, const int *d_lineStart, const int *d_lineLen,
                                 size_t numSelected, char *d_out, size_t outCapacity, size_t *h_outBytes);
-typedef PFAC_status_t (*PFACX_linesSelect_protoType)(PFAC_handle_t, const char *, char *, size_t, int, int, int *, int *, int *, size_t *, size_t *);
-typedef PFAC_status_t (*PFACX_linesGather_protoType)(PFAC_handle_t, const char *, size_t, const int *, const int *, size_t, char *, size_t, size_t *);
 
 /* Measurement only: the newline pass of PFACX_linesSelect alone (pfac_lines_bitmap: one read of the input, size / 8 + size / 8 + size / 16 bytes written
  * into the handle's lines scratch).  Returns the average milliseconds of `launches` launches over the first n < 2^31 bytes of d_in, or a negative
@@ -167,8 +155,6 @@ PFAC_status_t PFACX_spansSelect(PFAC_handle_t handle, char *d_scan, size_t size,
                                 int *d_spanLen, size_t *h_numSpans, size_t *h_coveredBytes);
 PFAC_status_t PFACX_spansRedact(PFAC_handle_t handle, const char *d_input, size_t size, const int *d_spanStart, const int *d_spanLen, size_t numSpans,
                                 unsigned char fill, char *d_out);
-typedef PFAC_status_t (*PFACX_spansSelect_protoType)(PFAC_handle_t, char *, size_t, int, const int *, size_t, int *, int *, size_t *, size_t *);
-typedef PFAC_status_t (*PFACX_spansRedact_protoType)(PFAC_handle_t, const char *, size_t, const int *, const int *, size_t, unsigned char, char *);
 
 /* Occurrence counts (no reference counterpart; include/pfac_ext.h: PFACX_count*), scan_count.hip.
  * PFACX_countPairs: d_counts[id] (numIds + 1 entries, 64-bit) = how often pattern id occurs, from a list of LONGEST pairs.  d_scan != null: the list is
@@ -184,10 +170,19 @@ PFAC_status_t PFACX_countPairs(PFAC_handle_t handle, char *d_scan, size_t size, 
                                unsigned int flags, unsigned long long *d_counts, size_t *h_total);
 PFAC_status_t PFACX_countNonzero(PFAC_handle_t handle, const unsigned long long *d_counts, size_t numCounts, int *d_ids,
                                  unsigned long long *d_outCounts, size_t capacity, size_t *h_numDistinct, unsigned long long *h_total);
-typedef PFAC_status_t (*PFACX_countPairs_protoType)(PFAC_handle_t, char *, size_t, int, const int *, size_t, const void *, unsigned int,
-                                                    unsigned long long *, size_t *);
-typedef PFAC_status_t (*PFACX_countNonzero_protoType)(PFAC_handle_t, const unsigned long long *, size_t, int *, unsigned long long *, size_t, size_t *,
-                                                      unsigned long long *);
+
+/* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
+ * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
+ * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
+#define PFAC_MODULE_ENTRIES(X) \
+    X(kernel_time_driven_ptr, PFAC_kernel_timeDriven_warpper) X(kernel_space_driven_ptr, PFAC_kernel_spaceDriven_warpper) \
+    X(reduce_kernel_ptr, PFAC_reduce_kernel) X(reduce_inplace_kernel_ptr, PFAC_reduce_inplace_kernel) \
+    X(batch_fixup_ptr, PFACX_batchFixup) X(batch_reduce_fixup_ptr, PFACX_batchReduceFixup) \
+    X(all_reduce_ptr, PFACX_allReduce) X(all_expand_ptr, PFACX_allExpand) X(fold_input_ptr, PFACX_foldInput) \
+    X(stream_seam_ptr, PFACX_streamSeam) X(stream_reduce_ptr, PFACX_streamReduce) X(flows_run_ptr, PFACX_flowsRun) \
+    X(lines_select_ptr, PFACX_linesSelect) X(lines_gather_ptr, PFACX_linesGather) \
+    X(spans_select_ptr, PFACX_spansSelect) X(spans_redact_ptr, PFACX_spansRedact) \
+    X(count_pairs_ptr, PFACX_countPairs) X(count_nonzero_ptr, PFACX_countNonzero)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

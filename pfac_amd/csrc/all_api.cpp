@@ -5,7 +5,8 @@
  * Every pattern that starts at p is a prefix of the longest one that starts there, so the list is the longest-match list with each
  * pair followed by its chain of prefix patterns (Automaton::prefixPattern).  The GPU forms run the unchanged compacted-output path
  * with its ordered pairs in handle scratch (PFACX_allReduce), the batch fix-up of PFACX_matchBatchFromDeviceReduce where there are
- * segments, and the expansion (scan_all.hip) into the caller's arrays.  The host form expands in place on the host.  A set in
+ * segments, and the expansion (scan_all.hip) into the caller's arrays.  The host form takes the longest pairs from hostLongestPairs and
+ * expands them in place on the host.  A set in
  * which no pattern is a prefix of another (maxChain == 1) needs no expansion: each call is its compacted counterpart.
  */
 #include <hip/hip_runtime_api.h>
@@ -27,13 +28,15 @@ PFAC_status_t ensureAllTable(PFAC_context *c)
     return c->scratch.allTable.upload(t.data(), t.size());
 }
 
-/* the GPU forms behind their argument checks (0 < size < 2^31, capacity >= size; d_offsets null: one segment, no d_segFirst) */
+/* the GPU forms behind their argument checks (0 < size < 2^31, capacity >= size; d_offsets null: one segment, no d_segFirst); the caller holds c->lock */
 static PFAC_status_t matchAllDeviceLocked(PFAC_context *c, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
                                           int *d_ids, int *d_pos, size_t capacity, size_t *d_segFirst, size_t *h_num_matched)
 {
-    correctTextureMode(c);
+    DeviceScan scan;
+    PFAC_status_t st = beginDeviceScan(c, d_input, size, &scan);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    d_input = scan.d_scan;
     const bool expand = c->fa.maxChain > 1;
-    PFAC_status_t st = PFAC_STATUS_SUCCESS;
     if (d_offsets) st = ensurePatternLen(c);
     if (st == PFAC_STATUS_SUCCESS && d_offsets) st = c->scratch.allSegFirst.reserve(numSegments + 1);      /* the first longest pair of each segment */
     if (st == PFAC_STATUS_SUCCESS && expand) st = ensureAllTable(c);
@@ -41,7 +44,7 @@ static PFAC_status_t matchAllDeviceLocked(PFAC_context *c, char *d_input, size_t
     int count = 0;
     int *ids = d_ids, *pos = d_pos;
     if (expand) {
-        st = c->all_reduce_ptr(c, reinterpret_cast<int *>(d_input), (int)size, d_ids, d_pos, &count, c->perfMode == PFAC_TIME_DRIVEN ? 0 : 1);
+        st = c->all_reduce_ptr(c, reinterpret_cast<int *>(d_input), (int)size, d_ids, d_pos, &count, scan.hashed);
         ids = c->scratch.allPairs.get();
         pos = ids + c->scratch.allPairs.count() / 2;              /* one allocation: the ids, then as many positions */
     } else {
@@ -99,8 +102,6 @@ PFAC_status_t PFACX_matchAllFromDevice(PFAC_handle_t handle, char *d_input, size
     if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
     std::lock_guard<std::mutex> guard(handle->lock);
-    const PFAC_status_t st = foldDeviceInput(handle, d_input, size, &d_input);
-    if (st != PFAC_STATUS_SUCCESS) return st;
     return matchAllDeviceLocked(handle, d_input, size, nullptr, 0, d_ids, d_pos, capacity, nullptr, h_num_matched);
 }
 
@@ -113,22 +114,11 @@ PFAC_status_t PFACX_matchAllFromHost(PFAC_handle_t handle, char *h_input, size_t
     if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
-    size_t count = 0;
-    if (handle->platform != PFAC_PLATFORM_GPU) {
-        /* the longest match of every position into h_ids (it holds size entries), compacted in place as PFAC_matchFromHostReduce does */
-        const PFAC_status_t st = matchHostOnCpuPlatform(handle, h_input, size, h_ids);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-        count = (size_t)compactPairs(h_ids, size, 0, h_ids, h_pos);
-    } else {
-        if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
-        std::lock_guard<std::mutex> guard(handle->lock);
-        int n = 0;
-        const PFAC_status_t st = matchHostReduceOnGpu(handle, h_input, size, size, 0, h_ids, h_pos, &n);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-        count = (size_t)n;
-    }
+    int count = 0;
+    const PFAC_status_t st = hostLongestPairs(handle, h_input, size, h_ids, h_pos, &count);
+    if (st != PFAC_STATUS_SUCCESS) return st;
     std::shared_lock<std::shared_mutex> tables(handle->tablesInUse);
-    const size_t total = expandOnHost(handle->fa, h_ids, h_pos, count, capacity);
+    const size_t total = expandOnHost(handle->fa, h_ids, h_pos, (size_t)count, capacity);
     *h_num_matched = total;
     return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
 }
@@ -145,8 +135,6 @@ PFAC_status_t PFACX_matchAllBatchFromDevice(PFAC_handle_t handle, char *d_input,
     if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
     std::lock_guard<std::mutex> guard(handle->lock);
-    const PFAC_status_t st = foldDeviceInput(handle, d_input, size, &d_input);
-    if (st != PFAC_STATUS_SUCCESS) return st;
     return matchAllDeviceLocked(handle, d_input, size, d_offsets, numSegments, d_ids, d_pos, capacity, d_segFirst, h_num_matched);
 }
 

@@ -119,11 +119,12 @@ PFAC_status_t PFACX_matchBatchFromDeviceReduce(PFAC_handle_t handle, char *d_inp
     if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
     std::lock_guard<std::mutex> guard(handle->lock);
-    correctTextureMode(handle);
     PFAC_status_t st = ensurePatternLen(handle);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    st = foldDeviceInput(handle, d_input, size, &d_input);             /* a caseless set: the scan and the fix-up read the folded bytes */
+    DeviceScan scan;                                                    /* a caseless set: the scan and the fix-up read the folded bytes */
+    st = beginDeviceScan(handle, d_input, size, &scan);
     if (st != PFAC_STATUS_SUCCESS) return st;
+    d_input = scan.d_scan;
     int count = 0;
     st = reduceOnDevice(handle, d_input, size, d_matched_result, d_pos, &count);
     if (st != PFAC_STATUS_SUCCESS) return st;

@@ -5,11 +5,13 @@
  * Every pattern that occurs at a position is a prefix of the longest one there, so the number of occurrences of pattern id is the longest histogram
  * summed over the patterns that have id on their prefix chain (Automaton::prefixPattern).  The device form is the compacted scan without its
  * ordering launches, into the pair scratch of the all-match calls, and a histogram, a store and a chain pass behind it (scan_count.hip:
- * PFACX_countPairs); the host form matches as the platform says -- the CPU matcher, or the pipelined path of PFAC_matchFromHostReduce -- over
- * temporaries of its own and counts here.
+ * PFACX_countPairs); the host form takes the longest pairs from hostLongestPairs into a temporary of its own -- ids and positions, `size` ints
+ * each on every platform (the positions are not read, and on a CPU platform not written beyond the pairs: the price of the one helper is address
+ * space) -- and counts here.
  */
 #include <hip/hip_runtime_api.h>
 
+#include <memory>
 #include <mutex>
 #include <new>
 #include <shared_mutex>
@@ -79,7 +81,7 @@ PFAC_status_t PFACX_countFromDevice(PFAC_handle_t handle, char *d_input, size_t 
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (!d_input || !h_total) return PFAC_STATUS_INVALID_PARAMETER;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
-    if (!handle->hasDevice || !handle->module || !handle->count_pairs_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     if (size == 0) {                                                       /* nothing matched: the counts zeroed, or left alone */
         st = handle->count_pairs_ptr(handle, nullptr, 0, 0, nullptr, 0, nullptr, flags, d_counts, nullptr);
@@ -87,14 +89,13 @@ PFAC_status_t PFACX_countFromDevice(PFAC_handle_t handle, char *d_input, size_t 
         if (st == PFAC_STATUS_SUCCESS) *h_total = 0;
         return st;
     }
-    correctTextureMode(handle);
     const void *d_table = nullptr;
     st = chainTable(handle, flags, &d_table);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    char *d_scan = d_input;
-    st = foldDeviceInput(handle, d_input, size, &d_scan);                 /* a caseless set: the scan reads the folded copy */
+    DeviceScan scan;                                                       /* a caseless set: the scan reads the folded copy */
+    st = beginDeviceScan(handle, d_input, size, &scan);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    return handle->count_pairs_ptr(handle, d_scan, size, handle->perfMode == PFAC_TIME_DRIVEN ? 0 : 1, nullptr, 0, d_table, flags, d_counts, h_total);
+    return handle->count_pairs_ptr(handle, scan.d_scan, size, scan.hashed, nullptr, 0, d_table, flags, d_counts, h_total);
 }
 
 PFAC_status_t PFACX_countFromHost(PFAC_handle_t handle, char *h_input, size_t size, unsigned int flags, unsigned long long *h_counts, size_t numCounts,
@@ -107,28 +108,20 @@ PFAC_status_t PFACX_countFromHost(PFAC_handle_t handle, char *h_input, size_t si
     if (handle->platform == PFAC_PLATFORM_GPU && (!handle->hasDevice || !handle->module)) return PFAC_STATUS_LIB_NOT_EXIST;
     const size_t F = (size_t)handle->fa.numPatterns;
     std::vector<unsigned long long> L;
-    std::vector<int> ids, pos;
+    std::unique_ptr<int[]> pairs(new (std::nothrow) int[2 * size + 1]);   /* the ids, then the positions; not initialised: a page nothing writes costs nothing */
     try {
         L.assign(F + 1, 0);
-        ids.resize(size);
-        if (handle->platform == PFAC_PLATFORM_GPU) pos.resize(size);
     } catch (const std::bad_alloc &) {
         return PFAC_STATUS_ALLOC_FAILED;
     }
-    if (size > 0 && handle->platform != PFAC_PLATFORM_GPU) {
-        st = matchHostOnCpuPlatform(handle, h_input, size, ids.data());    /* the longest match of every position */
-        if (st != PFAC_STATUS_SUCCESS) return st;
-        for (size_t p = 0; p < size; p++)
-            if (ids[p] > 0 && (size_t)ids[p] <= F) L[(size_t)ids[p]]++;
-    } else if (size > 0) {
+    if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
+    if (size > 0) {
         int n = 0;
-        {
-            std::lock_guard<std::mutex> guard(handle->lock);
-            st = matchHostReduceOnGpu(handle, h_input, size, size, 0, ids.data(), pos.data(), &n);
-        }
+        const int *ids = pairs.get();
+        st = hostLongestPairs(handle, h_input, size, pairs.get(), pairs.get() + size, &n);
         if (st != PFAC_STATUS_SUCCESS) return st;
         for (int i = 0; i < n; i++)
-            if (ids[(size_t)i] > 0 && (size_t)ids[(size_t)i] <= F) L[(size_t)ids[(size_t)i]]++;
+            if (ids[i] > 0 && (size_t)ids[i] <= F) L[(size_t)ids[i]]++;
     }
     std::shared_lock<std::shared_mutex> tables(handle->tablesInUse);
     if ((size_t)handle->fa.numPatterns != F) return PFAC_STATUS_PATTERNS_NOT_READY;          /* another thread has replaced the set meanwhile */
@@ -146,7 +139,7 @@ PFAC_status_t PFACX_countPairsFromDevice(PFAC_handle_t handle, const int *d_ids,
     PFAC_status_t st = checkCountArgs(handle, flags, d_counts, numCounts);
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (numPairs > (size_t)0x7fffffff || (numPairs && !d_ids)) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!handle->hasDevice || !handle->module || !handle->count_pairs_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     const void *d_table = nullptr;
     st = chainTable(handle, flags, &d_table);
@@ -161,7 +154,7 @@ PFAC_status_t PFACX_countNonzeroFromDevice(PFAC_handle_t handle, const unsigned 
     if (!h_numDistinct || !h_total) return PFAC_STATUS_INVALID_PARAMETER;
     if (numCounts == 0) { *h_numDistinct = 0; *h_total = 0; return PFAC_STATUS_SUCCESS; }
     if (!d_counts || (capacity && (!d_ids || !d_outCounts)) || numCounts > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!handle->hasDevice || !handle->module || !handle->count_nonzero_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     return handle->count_nonzero_ptr(handle, d_counts, numCounts, d_ids, d_outCounts, capacity, h_numDistinct, h_total);
 }

@@ -14,9 +14,9 @@
  *               twice: for the scan's count (which sizes the staging list) and for the end of the merge.  The scan uses the
  *               caller's arrays below `size` as its pair list, like every compacted call; the merge writes nothing at or beyond
  *               the total.
- *   host-fed:   a vector per flow; the pieces go one by one through what a host-fed stream's call goes through (hostPiece, stream_api.cpp: the CPU matchers on a
- *               CPU platform, the pipelined host path on the GPU platform), into the caller's arrays at the running count, and the
- *               next carries are kept aside until the last piece has succeeded.
+ *   host-fed:   a vector per flow; the pieces go one by one through what a host-fed stream's call goes through (hostPiece, stream_api.cpp:
+ *               hostLongestPairsLocked, whatever the platform), into the caller's arrays at the running count, and the next carries are
+ *               kept aside until the last piece has succeeded.
  * Every piece and flush call holds the set's own lock and the handle's lock from the check of the pattern set to its end.
  */
 #include <hip/hip_runtime_api.h>
@@ -82,15 +82,6 @@ void forget(Flow &f)
     std::vector<unsigned char>().swap(f.h_carry);
 }
 
-/* (the caller holds the handle's lock) */
-PFAC_status_t checkSet(PFACX_flows_s *s)
-{
-    PFAC_context *c = s->handle;
-    if (s->generation != c->setGeneration) return PFAC_STATUS_INVALID_PARAMETER;     /* another pattern set since: PFACX_flowsReset(flows, NULL, 0) */
-    if (!c->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
-    return PFAC_STATUS_SUCCESS;
-}
-
 /* every id below numFlows, no flow twice */
 bool idsValid(PFACX_flows_s *s, const unsigned int *ids, size_t n)
 {
@@ -117,8 +108,6 @@ PFAC_status_t ensureCarries(PFACX_flows_s *s, size_t M)
     s->deviceM = (int)M;
     return PFAC_STATUS_SUCCESS;
 }
-
-size_t up256(size_t n) { return (n + 255) & ~size_t(255); }
 
 /* room for P piece descriptors in the handle's pinned host memory (the caller fills them) and on the device */
 PFAC_status_t stagePieces(PFAC_context *c, size_t P, PFACX_flowPiece_t **h_pieces)
@@ -204,7 +193,7 @@ PFAC_status_t checkPieces(PFACX_flows_s *s, const void *input, size_t size, cons
                           const int *ids, const int *pos, size_t capacity, const int *pieceFirst, const unsigned long long *h_pieceOffsets,
                           const int *h_num_matched)
 {
-    const PFAC_status_t st = checkSet(s);
+    const PFAC_status_t st = checkSetGeneration(s->handle, s->generation);
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (!input || !h_offsets || !ids || !pos || !pieceFirst || !h_num_matched || (numPieces && (!h_flowIds || !h_pieceOffsets))) return PFAC_STATUS_INVALID_PARAMETER;
     if (numPieces == 0) return size == 0 ? PFAC_STATUS_SUCCESS : PFAC_STATUS_INVALID_PARAMETER;
@@ -285,8 +274,8 @@ PFAC_status_t PFACX_flowsMatchFromDevice(PFACX_flows_t flows, char *d_input, siz
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (numPieces == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
     if (size && flows->kind == 1) return PFAC_STATUS_INVALID_PARAMETER;          /* a host-fed set */
-    if (!c->hasDevice || !c->module || !c->flows_run_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
-    correctTextureMode(c);
+    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    correctTextureMode(c);                                                       /* (a call whose pieces have only seams resolves it too) */
     const size_t M = (size_t)c->fa.maxPatternLen;
     st = ensureCarries(flows, M);
     if (st != PFAC_STATUS_SUCCESS) return st;
@@ -320,9 +309,9 @@ PFAC_status_t PFACX_flowsMatchFromDevice(PFACX_flows_t flows, char *d_input, siz
         if (st != PFAC_STATUS_SUCCESS) return st;
         int scanCount = 0;
         if (anyOwned) {
-            char *in = d_input;
-            st = foldDeviceInput(c, d_input, size, &in);
-            if (st == PFAC_STATUS_SUCCESS) st = reduceOnDevice(c, in, size, d_ids, d_pos, &scanCount);
+            DeviceScan scan;
+            st = beginDeviceScan(c, d_input, size, &scan);
+            if (st == PFAC_STATUS_SUCCESS) st = reduceOnDevice(c, scan.d_scan, size, d_ids, d_pos, &scanCount);
             if (st != PFAC_STATUS_SUCCESS) return st;
         }
         st = runOnDevice(flows, d_input, numPieces, sumFinal, (size_t)scanCount, d_ids, d_pos, capacity, d_pieceFirst, &total);
@@ -359,14 +348,13 @@ PFAC_status_t PFACX_flowsMatchFromHost(PFACX_flows_t flows, char *h_input, size_
     int at = 0;
     try {
         std::vector<std::vector<unsigned char>> next(numPieces);                /* the flows change when the whole call has succeeded */
-        std::vector<int> scratch;
         for (size_t k = 0; k < numPieces; k++) {
             const size_t len = h_offsets[k + 1] - h_offsets[k];
             h_pieceFirst[k] = at;
             if (!len) continue;
             int n = 0;
             const Flow &f = flows->flows[h_flowIds[k]];
-            st = hostPiece(c, f.h_carry.data(), f.carried, h_input + h_offsets[k], len, false, h_ids + at, h_pos + at, scratch, next[k], &n);
+            st = hostPiece(c, f.h_carry.data(), f.carried, h_input + h_offsets[k], len, false, h_ids + at, h_pos + at, next[k], &n);
             if (st != PFAC_STATUS_SUCCESS) return st;
             at += n;
         }
@@ -393,7 +381,7 @@ PFAC_status_t PFACX_flowsFlush(PFACX_flows_t flows, const unsigned int *h_flowId
     std::lock_guard<std::mutex> own(flows->lock);
     std::lock_guard<std::mutex> guard(flows->handle->lock);
     PFAC_context *c = flows->handle;
-    PFAC_status_t st = checkSet(flows);
+    PFAC_status_t st = checkSetGeneration(c, flows->generation);
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (!ids || !pos || !first || !h_num_matched || (n && !h_flowIds)) return PFAC_STATUS_INVALID_PARAMETER;
     const size_t M = (size_t)c->fa.maxPatternLen;
@@ -404,7 +392,7 @@ PFAC_status_t PFACX_flowsFlush(PFACX_flows_t flows, const unsigned int *h_flowId
     int total = 0;
     try {
         if (flows->kind == 2 && n) {
-            if (!c->hasDevice || !c->module || !c->flows_run_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+            if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
             st = ensureCarries(flows, M);
             if (st != PFAC_STATUS_SUCCESS) return st;
             PFACX_flowPiece_t *pieces = nullptr;
@@ -426,14 +414,13 @@ PFAC_status_t PFACX_flowsFlush(PFACX_flows_t flows, const unsigned int *h_flowId
             if (st != PFAC_STATUS_SUCCESS) return st;
         } else if (flows->kind == 1) {
             if (c->platform == PFAC_PLATFORM_GPU && (!c->hasDevice || !c->module)) return PFAC_STATUS_LIB_NOT_EXIST;
-            std::vector<int> scratch;
             std::vector<unsigned char> none;
             for (size_t k = 0; k < n; k++) {
                 first[k] = total;
                 const Flow &f = flows->flows[h_flowIds[k]];
                 if (!f.carried) continue;
                 int got = 0;
-                st = hostPiece(c, f.h_carry.data(), f.carried, nullptr, 0, true, ids + total, pos + total, scratch, none, &got);
+                st = hostPiece(c, f.h_carry.data(), f.carried, nullptr, 0, true, ids + total, pos + total, none, &got);
                 if (st != PFAC_STATUS_SUCCESS) return st;
                 total += got;
             }

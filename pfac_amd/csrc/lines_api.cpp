@@ -3,10 +3,9 @@
  * contain a pattern (PFACX_LINES_INVERT: that contain none), grep -F -f.
  *
  * No pattern contains '\n', so the longest-match result of the whole buffer is exact per line.  The device form is the compacted scan with a
- * line index in front of it and a mark / select pass behind it (scan_lines.hip: PFACX_linesSelect); the host form matches as the platform says
- * -- the CPU matcher, or the pipelined path of PFAC_matchFromHostReduce -- and does the line work here: memchr for the line ends, one bit per
- * line for the hits, then the list, written in place over the arrays the match used (line k starts at or behind position k, so entry k of
- * either array is free by the time line k is listed).
+ * line index in front of it and a mark / select pass behind it (scan_lines.hip: PFACX_linesSelect); the host form takes the longest pairs from
+ * hostLongestPairs and does the line work here: memchr for the line ends, one bit per line for the hits (one walk over lines and pairs together),
+ * then the list, written in place over the arrays the pairs were in (the bits are complete by then).
  */
 #include <hip/hip_runtime_api.h>
 
@@ -71,14 +70,13 @@ PFAC_status_t PFACX_matchLinesFromDevice(PFAC_handle_t handle, char *d_input, si
     if (size == 0) { *h_numLines = 0; *h_numSelected = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
-    if (!handle->hasDevice || !handle->module || !handle->lines_select_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
-    correctTextureMode(handle);
-    char *d_scan = d_input;
-    st = foldDeviceInput(handle, d_input, size, &d_scan);                 /* a caseless set: the scan reads the folded copy, the line ends are the caller's */
+    DeviceScan scan;                                                       /* a caseless set: the scan reads the folded copy, the line ends are the caller's */
+    st = beginDeviceScan(handle, d_input, size, &scan);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    return handle->lines_select_ptr(handle, d_input, d_scan, size, (flags & PFACX_LINES_INVERT) ? 1 : 0, handle->perfMode == PFAC_TIME_DRIVEN ? 0 : 1,
-                                    d_lineStart, d_lineLen, d_lineIndex, h_numLines, h_numSelected);
+    return handle->lines_select_ptr(handle, d_input, scan.d_scan, size, (flags & PFACX_LINES_INVERT) ? 1 : 0, scan.hashed, d_lineStart, d_lineLen,
+                                    d_lineIndex, h_numLines, h_numSelected);
 }
 
 PFAC_status_t PFACX_matchLinesFromHost(PFAC_handle_t handle, char *h_input, size_t size, unsigned int flags, int *h_lineStart, int *h_lineLen,
@@ -96,29 +94,14 @@ PFAC_status_t PFACX_matchLinesFromHost(PFAC_handle_t handle, char *h_input, size
     } catch (const std::bad_alloc &) {
         return PFAC_STATUS_ALLOC_FAILED;
     }
-    if (handle->platform != PFAC_PLATFORM_GPU) {
-        /* the longest match of every position into h_lineStart (it holds size entries); a line matches if one of its positions does */
-        st = matchHostOnCpuPlatform(handle, h_input, size, h_lineStart);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-        forEachLine(h_input, size, [&](size_t k, size_t s, size_t e) {
-            for (size_t p = s; p < e; p++)
-                if (h_lineStart[p] > 0) { hit[k >> 6] |= uint64_t(1) << (k & 63); break; }
-        });
-    } else {
-        if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
-        int count = 0;
-        {
-            std::lock_guard<std::mutex> guard(handle->lock);
-            st = matchHostReduceOnGpu(handle, h_input, size, size, 0, h_lineStart, h_lineLen, &count);
-        }
-        if (st != PFAC_STATUS_SUCCESS) return st;
-        /* the pairs come in position order: one walk over lines and positions together */
-        size_t j = 0;
-        forEachLine(h_input, size, [&](size_t k, size_t, size_t e) {
-            if (j < (size_t)count && (size_t)h_lineLen[j] < e) hit[k >> 6] |= uint64_t(1) << (k & 63);
-            while (j < (size_t)count && (size_t)h_lineLen[j] < e) j++;
-        });
-    }
+    int count = 0;
+    st = hostLongestPairs(handle, h_input, size, h_lineStart, h_lineLen, &count);      /* ids, positions: in position order */
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    size_t j = 0;                                                         /* one walk over lines and positions together */
+    forEachLine(h_input, size, [&](size_t k, size_t, size_t e) {
+        if (j < (size_t)count && (size_t)h_lineLen[j] < e) hit[k >> 6] |= uint64_t(1) << (k & 63);
+        while (j < (size_t)count && (size_t)h_lineLen[j] < e) j++;
+    });
     listLines(h_input, size, hit, invert, h_lineStart, h_lineLen, h_lineIndex, h_numLines, h_numSelected);
     return PFAC_STATUS_SUCCESS;
 }
@@ -131,7 +114,7 @@ PFAC_status_t PFACX_gatherLinesFromDevice(PFAC_handle_t handle, const char *d_in
     if (numSelected == 0) { *h_outBytes = 0; return PFAC_STATUS_SUCCESS; }
     if (!d_lineStart || !d_lineLen || (!d_input && size) || (!d_out && outCapacity)) return PFAC_STATUS_INVALID_PARAMETER;
     if (size > (size_t)0x7fffffff || numSelected > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!handle->hasDevice || !handle->module || !handle->lines_gather_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     return handle->lines_gather_ptr(handle, d_input, size, d_lineStart, d_lineLen, numSelected, d_out, outCapacity, h_outBytes);
 }

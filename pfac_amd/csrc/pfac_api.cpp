@@ -85,19 +85,18 @@ PFAC_status_t foldDeviceInput(PFAC_context *c, char *d_in, size_t size, char **d
 {
     *d_use = d_in;
     if (!c->caseInsensitive || size == 0) return PFAC_STATUS_SUCCESS;
-    if (!c->hasDevice || !c->module || !c->fold_input_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
-    PFAC_status_t st = c->scratch.fold.reserve((size + 255) & ~size_t(255));
+    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    PFAC_status_t st = c->scratch.fold.reserve(up256(size));
     if (st != PFAC_STATUS_SUCCESS) return st;
     st = c->fold_input_ptr(c, d_in, c->scratch.fold.get(), size);
     if (st == PFAC_STATUS_SUCCESS) *d_use = c->scratch.fold.get();
     return st;
 }
 
-/* ... and a staging piece of the host paths in place, behind its upload in stream order */
+/* ... and a staging piece of the host paths in place, behind its upload in stream order (those paths have checked the module) */
 PFAC_status_t foldStaged(PFAC_context *c, char *d_piece, size_t size)
 {
     if (!c->caseInsensitive || size == 0) return PFAC_STATUS_SUCCESS;
-    if (!c->fold_input_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
     return c->fold_input_ptr(c, d_piece, d_piece, size);
 }
 
@@ -282,30 +281,19 @@ PFAC_status_t loadModule(PFAC_context *c)
     void *m = dlopen((selfDirectory() + name).c_str(), RTLD_NOW);
     if (!m) m = dlopen(name.c_str(), RTLD_NOW);
     if (!m) return PFAC_STATUS_LIB_NOT_EXIST;
-    c->module = m;
-    c->kernel_time_driven_ptr = (PFAC_kernel_protoType)dlsym(m, "PFAC_kernel_timeDriven_warpper");
-    c->kernel_space_driven_ptr = (PFAC_kernel_protoType)dlsym(m, "PFAC_kernel_spaceDriven_warpper");
-    c->reduce_kernel_ptr = (PFAC_reduce_kernel_protoType)dlsym(m, "PFAC_reduce_kernel");
-    c->reduce_inplace_kernel_ptr = (PFAC_reduce_kernel_protoType)dlsym(m, "PFAC_reduce_inplace_kernel");
-    c->batch_fixup_ptr = (PFACX_batchFixup_protoType)dlsym(m, "PFACX_batchFixup");
-    c->batch_reduce_fixup_ptr = (PFACX_batchReduceFixup_protoType)dlsym(m, "PFACX_batchReduceFixup");
-    c->all_reduce_ptr = (PFACX_allReduce_protoType)dlsym(m, "PFACX_allReduce");
-    c->all_expand_ptr = (PFACX_allExpand_protoType)dlsym(m, "PFACX_allExpand");
-    c->fold_input_ptr = (PFACX_foldInput_protoType)dlsym(m, "PFACX_foldInput");
-    c->stream_seam_ptr = (PFACX_streamSeam_protoType)dlsym(m, "PFACX_streamSeam");
-    c->stream_reduce_ptr = (PFACX_streamReduce_protoType)dlsym(m, "PFACX_streamReduce");
-    c->flows_run_ptr = (PFACX_flowsRun_protoType)dlsym(m, "PFACX_flowsRun");
-    c->lines_select_ptr = (PFACX_linesSelect_protoType)dlsym(m, "PFACX_linesSelect");
-    c->lines_gather_ptr = (PFACX_linesGather_protoType)dlsym(m, "PFACX_linesGather");
-    c->spans_select_ptr = (PFACX_spansSelect_protoType)dlsym(m, "PFACX_spansSelect");
-    c->spans_redact_ptr = (PFACX_spansRedact_protoType)dlsym(m, "PFACX_spansRedact");
-    c->count_pairs_ptr = (PFACX_countPairs_protoType)dlsym(m, "PFACX_countPairs");
-    c->count_nonzero_ptr = (PFACX_countNonzero_protoType)dlsym(m, "PFACX_countNonzero");
-    if (!c->spans_select_ptr || !c->spans_redact_ptr || !c->count_pairs_ptr || !c->count_nonzero_ptr) return PFAC_STATUS_INTERNAL_ERROR;
-    if (!c->kernel_time_driven_ptr || !c->kernel_space_driven_ptr || !c->reduce_kernel_ptr ||
-        !c->reduce_inplace_kernel_ptr || !c->batch_fixup_ptr || !c->batch_reduce_fixup_ptr || !c->all_reduce_ptr || !c->all_expand_ptr ||
-        !c->fold_input_ptr || !c->stream_seam_ptr || !c->stream_reduce_ptr || !c->flows_run_ptr || !c->lines_select_ptr || !c->lines_gather_ptr)
+    /* all or nothing: a module that lacks an entry point is not kept, and leaves every pointer null */
+    bool bound = true;
+#define PFAC_MODULE_BIND(member, symbol) bound = (c->member = reinterpret_cast<decltype(&symbol)>(dlsym(m, #symbol))) != nullptr && bound;
+    PFAC_MODULE_ENTRIES(PFAC_MODULE_BIND)
+#undef PFAC_MODULE_BIND
+    if (!bound) {
+#define PFAC_MODULE_UNBIND(member, symbol) c->member = nullptr;
+        PFAC_MODULE_ENTRIES(PFAC_MODULE_UNBIND)
+#undef PFAC_MODULE_UNBIND
+        dlclose(m);
         return PFAC_STATUS_INTERNAL_ERROR;
+    }
+    c->module = m;
     return PFAC_STATUS_SUCCESS;
 }
 
@@ -321,14 +309,42 @@ PFAC_status_t matchHostOnCpuPlatformPrepared(PFAC_context *c, const char *in, si
     if (c->perfMode == PFAC_TIME_DRIVEN && c->h_dense.empty()) return PFAC_STATUS_PATTERNS_NOT_READY;   /* ... or has just replaced the set: its tables are built on the next call */
     return pfac::matchOnCpu(c, reinterpret_cast<const unsigned char *>(in), n, out, omp);
 }
-PFAC_status_t matchHostOnCpuPlatform(PFAC_context *c, const char *in, size_t n, int *out)
+/* ... and the tables under c->lock, which a caller that does not hold it takes for that step alone */
+static PFAC_status_t prepareCpuPlatform(PFAC_context *c)
 {
-    PFAC_status_t st;
-    {
-        std::lock_guard<std::mutex> guard(c->lock);
-        st = prepareCpuPlatformLocked(c);
+    std::lock_guard<std::mutex> guard(c->lock);
+    return prepareCpuPlatformLocked(c);
+}
+
+/* The longest pairs of a host buffer on whatever platform the handle is on (pfac_host.h): what every host form that works on pairs calls.  On a
+ * CPU platform (ref PFAC.cpp:1036-1068) the full result vector goes into ids and is compacted in place */
+static PFAC_status_t cpuPairsPrepared(PFAC_context *c, const char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count)
+{
+    const PFAC_status_t st = matchHostOnCpuPlatformPrepared(c, in, readable, ids);
+    if (st == PFAC_STATUS_SUCCESS) *count = compactPairs(ids, owned, posShift, ids, pos);
+    return st;
+}
+PFAC_status_t hostLongestPairsLocked(PFAC_context *c, char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count)
+{
+    if (c->platform != PFAC_PLATFORM_GPU) {
+        const PFAC_status_t st = prepareCpuPlatformLocked(c);
+        return st == PFAC_STATUS_SUCCESS ? cpuPairsPrepared(c, in, owned, readable, posShift, ids, pos, count) : st;
     }
-    return st == PFAC_STATUS_SUCCESS ? matchHostOnCpuPlatformPrepared(c, in, n, out) : st;
+    int n = 0;
+    const PFAC_status_t st = matchHostReduceOnGpu(c, in, owned, readable, 0, ids, pos, &n);      /* LIB_NOT_EXIST without a device or a module */
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (posShift) for (int k = 0; k < n; k++) pos[k] += posShift;
+    *count = n;
+    return PFAC_STATUS_SUCCESS;
+}
+PFAC_status_t hostLongestPairs(PFAC_context *c, char *in, size_t size, int *ids, int *pos, int *count)
+{
+    if (c->platform != PFAC_PLATFORM_GPU) {
+        const PFAC_status_t st = prepareCpuPlatform(c);
+        return st == PFAC_STATUS_SUCCESS ? cpuPairsPrepared(c, in, size, size, 0, ids, pos, count) : st;
+    }
+    std::lock_guard<std::mutex> guard(c->lock);          /* the staging buffers, the match counter and the sort scratch belong to the handle */
+    return hostLongestPairsLocked(c, in, size, size, 0, ids, pos, count);
 }
 
 /* the end of every reader of a pattern set (pfac_host.h) */
@@ -549,8 +565,10 @@ PFAC_status_t PFAC_matchFromHost(PFAC_handle_t handle, char *h_inputString, size
     if (!h_inputString) return PFAC_STATUS_INVALID_PARAMETER;
     if (!h_matched_result) return PFAC_STATUS_INVALID_PARAMETER;
     if (size == 0) return PFAC_STATUS_SUCCESS;
-    if (handle->platform != PFAC_PLATFORM_GPU)
-        return matchHostOnCpuPlatform(handle, h_inputString, size, h_matched_result);
+    if (handle->platform != PFAC_PLATFORM_GPU) {
+        const PFAC_status_t st = prepareCpuPlatform(handle);
+        return st == PFAC_STATUS_SUCCESS ? matchHostOnCpuPlatformPrepared(handle, h_inputString, size, h_matched_result) : st;
+    }
     std::lock_guard<std::mutex> guard(handle->lock);
     return matchHostOnGpu(handle, h_inputString, size, size, h_matched_result);
 }
@@ -564,11 +582,10 @@ PFAC_status_t PFAC_matchFromDeviceReduce(PFAC_handle_t handle, char *d_inputStri
     if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
     std::lock_guard<std::mutex> guard(handle->lock);          /* the match counter and the sort scratch belong to the handle */
-    correctTextureMode(handle);
-    char *in = d_inputString;
-    const PFAC_status_t st = foldDeviceInput(handle, d_inputString, size, &in);
+    DeviceScan scan;
+    const PFAC_status_t st = beginDeviceScan(handle, d_inputString, size, &scan);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    return reduceOnDevice(handle, in, size, d_matched_result, d_pos, h_num_matched);
+    return reduceOnDevice(handle, scan.d_scan, size, d_matched_result, d_pos, h_num_matched);
 }
 
 PFAC_status_t PFAC_matchFromHostReduce(PFAC_handle_t handle, char *h_inputString, size_t size,
@@ -579,17 +596,7 @@ PFAC_status_t PFAC_matchFromHostReduce(PFAC_handle_t handle, char *h_inputString
     if (!h_inputString || !h_matched_result || !h_pos || !h_num_matched) return PFAC_STATUS_INVALID_PARAMETER;
     if (size == 0) return PFAC_STATUS_SUCCESS;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
-
-    if (handle->platform != PFAC_PLATFORM_GPU) {                  /* ref PFAC.cpp:1036-1068 */
-        PFAC_status_t st = matchHostOnCpuPlatform(handle, h_inputString, size, h_matched_result);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-        *h_num_matched = compactPairs(h_matched_result, size, 0, h_matched_result, h_pos);
-        return PFAC_STATUS_SUCCESS;
-    }
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
-    std::lock_guard<std::mutex> guard(handle->lock);
-
-    return matchHostReduceOnGpu(handle, h_inputString, size, size, 0, h_matched_result, h_pos, h_num_matched);
+    return hostLongestPairs(handle, h_inputString, size, h_matched_result, h_pos, h_num_matched);
 }
 
 /* ------------------------------------------------------------- extensions */

@@ -479,24 +479,10 @@ struct PFAC_context {
 
     /* kernel module seam (ref PFAC_P.h:136-146) */
     void *module = nullptr;
-    PFAC_kernel_protoType kernel_time_driven_ptr = nullptr;
-    PFAC_kernel_protoType kernel_space_driven_ptr = nullptr;
-    PFAC_reduce_kernel_protoType reduce_kernel_ptr = nullptr;
-    PFAC_reduce_kernel_protoType reduce_inplace_kernel_ptr = nullptr;
-    PFACX_batchFixup_protoType batch_fixup_ptr = nullptr;              /* scan_batch.hip: the batch calls (PFACX_matchBatch*) */
-    PFACX_batchReduceFixup_protoType batch_reduce_fixup_ptr = nullptr;
-    PFACX_allReduce_protoType all_reduce_ptr = nullptr;               /* scan_module.hip / scan_all.hip: the all-match calls (PFACX_matchAll*) */
-    PFACX_allExpand_protoType all_expand_ptr = nullptr;
-    PFACX_foldInput_protoType fold_input_ptr = nullptr;              /* scan_fold.hip: the input fold of a caseless set */
-    PFACX_streamSeam_protoType stream_seam_ptr = nullptr;            /* scan_stream.hip: the seam of a stream call (PFACX_stream*) */
-    PFACX_streamReduce_protoType stream_reduce_ptr = nullptr;        /* scan_module.hip: the compacted scan of a piece whose last bytes are read-ahead only */
-    PFACX_flowsRun_protoType flows_run_ptr = nullptr;                /* scan_flows.hip: the seams and the merge of a flows call (PFACX_flows*) */
-    PFACX_linesSelect_protoType lines_select_ptr = nullptr;          /* scan_lines.hip: the lines calls (PFACX_matchLines* / PFACX_gatherLines*) */
-    PFACX_linesGather_protoType lines_gather_ptr = nullptr;
-    PFACX_spansSelect_protoType spans_select_ptr = nullptr;          /* scan_spans.hip: the spans calls (PFACX_matchSpans* / PFACX_redactSpansFromDevice) */
-    PFACX_spansRedact_protoType spans_redact_ptr = nullptr;
-    PFACX_countPairs_protoType count_pairs_ptr = nullptr;            /* scan_count.hip: the count calls (PFACX_count*) */
-    PFACX_countNonzero_protoType count_nonzero_ptr = nullptr;
+    /* ... and its entry points (pfac_module.h: PFAC_MODULE_ENTRIES), bound together: module != nullptr means that none of them is null */
+#define PFAC_MODULE_MEMBER(member, symbol) decltype(&symbol) member = nullptr;
+    PFAC_MODULE_ENTRIES(PFAC_MODULE_MEMBER)
+#undef PFAC_MODULE_MEMBER
 
     int platform = PFAC_PLATFORM_GPU;
     int perfMode = PFAC_TIME_DRIVEN;

@@ -45,9 +45,23 @@ PFAC_status_t bindTable(PFAC_context *c);
  * built and uploaded -- or the handle is left empty */
 PFAC_status_t bindCompiledSet(PFAC_context *c);
 void correctTextureMode(PFAC_context *c);
-PFAC_status_t matchHostOnCpuPlatform(PFAC_context *c, const char *in, size_t n, int *out);
 PFAC_status_t prepareCpuPlatformLocked(PFAC_context *c);                                        /* the caller holds c->lock */
 PFAC_status_t matchHostOnCpuPlatformPrepared(PFAC_context *c, const char *in, size_t n, int *out);   /* ... has called the above; any number of threads */
+/* the longest match at positions [0, owned) of `readable` >= owned host bytes (the rest read-ahead only) as (id, position + posShift) pairs in position
+ * order; ids/pos hold `readable` entries at least; any platform: the CPU matcher into ids, compacted in place, or the pipelined path of the GPU
+ * platform (LIB_NOT_EXIST without a device or a module).  The caller holds c->lock */
+PFAC_status_t hostLongestPairsLocked(PFAC_context *c, char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count);
+/* ... of a whole buffer, for a caller without the lock: held for the whole call on the GPU platform, on the CPU platforms only while the tables are
+ * prepared -- several threads match there side by side */
+PFAC_status_t hostLongestPairs(PFAC_context *c, char *in, size_t size, int *ids, int *pos, int *count);
+/* what the stream and the flows calls check first (the caller holds c->lock: the set cannot change between this check and the end of the call) */
+inline PFAC_status_t checkSetGeneration(const PFAC_context *c, unsigned long long generation)
+{
+    if (generation != c->setGeneration) return PFAC_STATUS_INVALID_PARAMETER;     /* another pattern set since: PFACX_streamReset / PFACX_flowsReset */
+    if (!c->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
+    return PFAC_STATUS_SUCCESS;
+}
+inline size_t up256(size_t n) { return (n + 255) & ~size_t(255); }
 /* host_pipeline.cpp: the caller holds c->lock */
 PFAC_status_t prepareHostPath(PFAC_context *c, size_t maxBytes);
 PFAC_status_t matchDeviceLocked(PFAC_context *c, char *d_inputString, size_t size, int *d_matched_result);
@@ -58,6 +72,15 @@ PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t 
  * scratch).  foldStaged: a staging piece in place, on the default stream behind its upload (nothing for a case-sensitive handle) */
 PFAC_status_t foldDeviceInput(PFAC_context *c, char *d_in, size_t size, char **d_use);
 PFAC_status_t foldStaged(PFAC_context *c, char *d_piece, size_t size);
+/* the locked prologue of a device call that scans: the texture mode resolved, the input folded, the perf mode as the `hashed` argument of the module's
+ * entry points (the caller holds c->lock and has checked hasDevice and module) */
+struct DeviceScan { char *d_scan; int hashed; };
+inline PFAC_status_t beginDeviceScan(PFAC_context *c, char *d_input, size_t size, DeviceScan *s)
+{
+    correctTextureMode(c);
+    s->hashed = c->perfMode == PFAC_TIME_DRIVEN ? 0 : 1;
+    return foldDeviceInput(c, d_input, size, &s->d_scan);
+}
 /* the compacted-output scan of the handle's perf mode over n device bytes (the caller holds c->lock) */
 inline PFAC_status_t reduceOnDevice(PFAC_context *c, char *d_in, size_t n, int *d_ids, int *d_pos, int *h_count)
 {
@@ -81,13 +104,13 @@ size_t streamDeviceBytes(const PFAC_context *c);
 /* ... and what the stream and the flows calls share (the caller holds c->lock).  streamSplitOf: how a piece of `size` bytes splits the work of a
  * stream that carries `carried` bytes -- of the pending and the piece's positions the first seam + owned are final, `seam` of them carried.
  * hostPiece: one host-fed piece (or, size == 0 and flush: the stream's end) of a stream whose carry is carry[0, carried): the seam
- * [carry | head of the piece] and the piece's final positions through the CPU matchers on a CPU platform (scratch: grown as needed) and through
- * the pipelined host path on the GPU platform; the pairs go to ids / pos (room: size + M - 1), their number to *count, the stream's next carry
- * to `next`.  Nothing of the stream changes: the caller moves it on when its whole call has succeeded */
+ * [carry | head of the piece], in room of its own, and the piece's final positions through hostLongestPairsLocked; the pairs go to ids / pos
+ * (room: size + M - 1), their number to *count, the stream's next carry to `next`.  Nothing of the stream changes: the caller moves it on when its
+ * whole call has succeeded */
 struct StreamSplit { size_t seam, owned; };
 StreamSplit streamSplitOf(size_t carried, size_t size, size_t M);
 PFAC_status_t hostPiece(PFAC_context *c, const unsigned char *carry, size_t carried, char *piece, size_t size, bool flush, int *ids, int *pos,
-                        std::vector<int> &scratch, std::vector<unsigned char> &next, int *count);
+                        std::vector<unsigned char> &next, int *count);
 /* flows_api.cpp: PFAC_destroy closes the handle's flow sets; the device bytes their carries hold (PFACX_getInfo: deviceTableBytes) */
 void closeAllFlowSets(PFAC_context *c);
 size_t flowsDeviceBytes(const PFAC_context *c);

@@ -4,9 +4,9 @@
  *
  * Every pattern that occurs at a position is a prefix of the longest one there, so the covered bytes are the union of [p, p + len(r[p])) over the
  * non-zero positions of the longest-match result r.  The device form is the compacted scan with its ordering launches and a handful of passes over
- * the pairs behind it (scan_spans.hip: PFACX_spansSelect); the host form matches as the platform says -- the CPU matcher, or the pipelined path of
- * PFAC_matchFromHostReduce -- and merges here with one sequential running maximum, the list written in place over the arrays the match used (span i
- * comes from position or pair >= i, so entry i of either array is free by the time span i is listed).
+ * the pairs behind it (scan_spans.hip: PFACX_spansSelect); the host form takes the longest pairs from hostLongestPairs and merges here with one
+ * sequential running maximum, the list written in place over the arrays the pairs are in (span i comes from pair >= i, so entry i of either array
+ * is free by the time span i is listed).
  */
 #include <hip/hip_runtime_api.h>
 
@@ -16,7 +16,7 @@
 
 namespace pfac_internal {
 
-/* one running-maximum merge: next(p, e) yields the matches in position order, false at the end */
+/* one running-maximum merge: next(p, e) yields the matches [p, e) in position order, false at the end */
 template <class Next>
 static void mergeSpans(Next next, int *spanStart, int *spanLen, size_t *numSpans, size_t *coveredBytes)
 {
@@ -59,16 +59,15 @@ PFAC_status_t PFACX_matchSpansFromDevice(PFAC_handle_t handle, char *d_input, si
     if (size == 0) { *h_numSpans = 0; *h_coveredBytes = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
-    if (!handle->hasDevice || !handle->module || !handle->spans_select_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
-    correctTextureMode(handle);
     st = ensurePatternLen(handle);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    char *d_scan = d_input;
-    st = foldDeviceInput(handle, d_input, size, &d_scan);                 /* a caseless set: the scan reads the folded copy */
+    DeviceScan scan;                                                       /* a caseless set: the scan reads the folded copy */
+    st = beginDeviceScan(handle, d_input, size, &scan);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    return handle->spans_select_ptr(handle, d_scan, size, handle->perfMode == PFAC_TIME_DRIVEN ? 0 : 1, handle->scratch.patternLen.get(),
-                                    handle->scratch.patternLen.count(), d_spanStart, d_spanLen, h_numSpans, h_coveredBytes);
+    return handle->spans_select_ptr(handle, scan.d_scan, size, scan.hashed, handle->scratch.patternLen.get(), handle->scratch.patternLen.count(),
+                                    d_spanStart, d_spanLen, h_numSpans, h_coveredBytes);
 }
 
 PFAC_status_t PFACX_matchSpansFromHost(PFAC_handle_t handle, char *h_input, size_t size, int *h_spanStart, int *h_spanLen, size_t capacity,
@@ -81,27 +80,8 @@ PFAC_status_t PFACX_matchSpansFromHost(PFAC_handle_t handle, char *h_input, size
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
     const std::vector<int> &patternLen = handle->fa.patternLen;
     auto lenOf = [&](int id) -> size_t { return id > 0 && (size_t)id < patternLen.size() ? (size_t)patternLen[id] : 0; };
-    if (handle->platform != PFAC_PLATFORM_GPU) {
-        /* the longest match of every position into h_spanLen (it holds size entries): entry p is read before span o <= p is written */
-        st = matchHostOnCpuPlatform(handle, h_input, size, h_spanLen);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-        size_t at = 0;
-        mergeSpans([&](size_t &p, size_t &e) {
-            while (at < size && h_spanLen[at] <= 0) at++;
-            if (at == size) return false;
-            p = at;
-            e = at + lenOf(h_spanLen[at]);
-            at++;
-            return true;
-        }, h_spanStart, h_spanLen, h_numSpans, h_coveredBytes);
-        return PFAC_STATUS_SUCCESS;
-    }
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     int count = 0;
-    {
-        std::lock_guard<std::mutex> guard(handle->lock);
-        st = matchHostReduceOnGpu(handle, h_input, size, size, 0, h_spanStart, h_spanLen, &count);      /* ids, positions: in position order */
-    }
+    st = hostLongestPairs(handle, h_input, size, h_spanStart, h_spanLen, &count);      /* ids, positions: in position order */
     if (st != PFAC_STATUS_SUCCESS) return st;
     size_t j = 0;
     mergeSpans([&](size_t &p, size_t &e) {
@@ -123,7 +103,7 @@ PFAC_status_t PFACX_redactSpansFromDevice(PFAC_handle_t handle, const char *d_in
     if (size > (size_t)0x7fffffff || numSpans > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
     const uintptr_t I = reinterpret_cast<uintptr_t>(d_input), O = reinterpret_cast<uintptr_t>(d_out);
     if (I != O && I < O + size && O < I + size) return PFAC_STATUS_INVALID_PARAMETER;        /* in place, or apart */
-    if (!handle->hasDevice || !handle->module || !handle->spans_redact_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     return handle->spans_redact_ptr(handle, d_input, size, d_spanStart, d_spanLen, numSpans, fill, d_out);
 }

@@ -10,8 +10,7 @@
  *   device-fed: the carry lives in two device buffers (the seam launch writes the next one, so a failed call leaves the stream as it
  *               was); seam = scan_stream.hip, piece = the compacted-output path for positions [0, owned) (PFACX_streamReduce).
  *   host-fed:   the carry is host memory, kept as the caller sent it (every match path folds a caseless set's input itself); seam and
- *               piece go through the CPU matchers on a CPU platform and through the pipelined path of PFAC_matchFromHostReduce on the
- *               GPU platform.
+ *               piece go through hostLongestPairsLocked, whatever the platform.
  * Every piece and flush call holds the handle's lock from the check of the pattern set to its end (and the stream's own lock: one call
  * at a time per stream), so a set read on another thread cannot slip between a call's halves.
  */
@@ -79,9 +78,9 @@ static PFAC_status_t ensureStreamDevice(PFACX_stream_s *s, int M)
 {
     if (s->d_block && s->deviceM == M) return PFAC_STATUS_SUCCESS;
     freeStreamDevice(s);
-    const size_t one = (((size_t)M - 1) + 255) & ~size_t(255);
+    const size_t one = up256((size_t)M - 1);
     const size_t seam = 2 * ((size_t)M - 1);
-    const size_t stage = seam > pfac::kStreamSeamLdsBytes ? ((seam + 255) & ~size_t(255)) : 0;
+    const size_t stage = seam > pfac::kStreamSeamLdsBytes ? up256(seam) : 0;
     const PFAC_status_t st = s->d_block.reserve(2 * one + stage + 256);
     if (st != PFAC_STATUS_SUCCESS) return st;
     s->d_carry[0] = s->d_block.get();
@@ -92,68 +91,38 @@ static PFAC_status_t ensureStreamDevice(PFACX_stream_s *s, int M)
 }
 
 /* how a piece of `size` bytes splits the work: of the positions [R, T + size) the first `finalAll` are final; `seam` of them are carried */
-using Split = StreamSplit;
 StreamSplit streamSplitOf(size_t carried, size_t size, size_t M)
 {
     const size_t all = carried + size;
     const size_t finalAll = all >= M - 1 ? all - (M - 1) : 0;
-    Split sp;
+    StreamSplit sp;
     sp.seam = finalAll < carried ? finalAll : carried;
     sp.owned = finalAll - sp.seam;
     return sp;
 }
 
-/* the longest match at positions [0, owned) of `readable` host bytes as (id, position + posShift) pairs behind ids / pos; CPU platforms
- * (the caller holds c->lock: the tables first, then the match that needs no lock of its own; scratch: `readable` ints) */
-static PFAC_status_t streamCpuPairs(PFAC_context *c, const char *in, size_t owned, size_t readable, int posShift, int *scratch, int *ids, int *pos, int *count)
-{
-    PFAC_status_t st = prepareCpuPlatformLocked(c);
-    if (st == PFAC_STATUS_SUCCESS) st = matchHostOnCpuPlatformPrepared(c, in, readable, scratch);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    *count = compactPairs(scratch, owned, posShift, ids, pos);
-    return PFAC_STATUS_SUCCESS;
-}
-
-/* ... on the GPU platform (the caller holds c->lock): the pipelined host path, positions [0, owned), the rest read-ahead */
-static PFAC_status_t streamGpuPairs(PFAC_context *c, char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count)
-{
-    int n = 0;
-    const PFAC_status_t st = matchHostReduceOnGpu(c, in, owned, readable, 0, ids, pos, &n);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (posShift) for (int k = 0; k < n; k++) pos[k] += posShift;
-    *count = n;
-    return PFAC_STATUS_SUCCESS;
-}
-
 PFAC_status_t hostPiece(PFAC_context *c, const unsigned char *carry, size_t carried, char *piece, size_t size, bool flush, int *ids, int *pos,
-                        std::vector<int> &scratch, std::vector<unsigned char> &next, int *count)
+                        std::vector<unsigned char> &next, int *count)
 {
     const size_t M = (size_t)c->fa.maxPatternLen;
-    const bool gpu = c->platform == PFAC_PLATFORM_GPU;
     StreamSplit sp = streamSplitOf(carried, size, M);
     if (flush) { sp.seam = carried; sp.owned = 0; }
     const size_t head = std::min(size, M - 1);
     int seamPairs = 0, piecePairs = 0;
-    PFAC_status_t st = PFAC_STATUS_SUCCESS;
     if (sp.seam) {
+        /* [carry | head of the piece], at most 2 (M - 1) bytes, with a result entry per byte: more than the caller's arrays need hold */
         std::vector<unsigned char> seam(carried + head);
+        std::vector<int> seamIds(seam.size()), seamPos(seam.size());
         std::memcpy(seam.data(), carry, carried);
         if (head) std::memcpy(seam.data() + carried, piece, head);
-        if (gpu) {
-            st = streamGpuPairs(c, reinterpret_cast<char *>(seam.data()), sp.seam, seam.size(), -(int)carried, ids, pos, &seamPairs);
-        } else {
-            if (scratch.size() < seam.size()) scratch.resize(seam.size());
-            st = streamCpuPairs(c, reinterpret_cast<const char *>(seam.data()), sp.seam, seam.size(), -(int)carried, scratch.data(), ids, pos, &seamPairs);
-        }
+        const PFAC_status_t st = hostLongestPairsLocked(c, reinterpret_cast<char *>(seam.data()), sp.seam, seam.size(), -(int)carried, seamIds.data(),
+                                                        seamPos.data(), &seamPairs);
         if (st != PFAC_STATUS_SUCCESS) return st;
+        std::copy_n(seamIds.data(), seamPairs, ids);
+        std::copy_n(seamPos.data(), seamPairs, pos);
     }
     if (sp.owned) {
-        if (gpu) {
-            st = streamGpuPairs(c, piece, sp.owned, size, 0, ids + seamPairs, pos + seamPairs, &piecePairs);
-        } else {
-            if (scratch.size() < size) scratch.resize(size);
-            st = streamCpuPairs(c, piece, sp.owned, size, 0, scratch.data(), ids + seamPairs, pos + seamPairs, &piecePairs);
-        }
+        const PFAC_status_t st = hostLongestPairsLocked(c, piece, sp.owned, size, 0, ids + seamPairs, pos + seamPairs, &piecePairs);
         if (st != PFAC_STATUS_SUCCESS) return st;
     }
     const size_t nextCarried = flush ? 0 : std::min(M - 1, carried + size);
@@ -162,16 +131,6 @@ PFAC_status_t hostPiece(PFAC_context *c, const unsigned char *carry, size_t carr
     if (nextCarried > fromPiece) std::memcpy(next.data(), carry + (carried - (nextCarried - fromPiece)), nextCarried - fromPiece);
     if (fromPiece) std::memcpy(next.data() + (nextCarried - fromPiece), piece + (size - fromPiece), fromPiece);
     *count = seamPairs + piecePairs;
-    return PFAC_STATUS_SUCCESS;
-}
-
-/* (the caller holds the handle's lock: the set cannot change between this check and the end of the call) */
-static PFAC_status_t checkStream(PFACX_stream_s *s)
-{
-    PFAC_context *c = s->handle;
-    if (!c) return PFAC_STATUS_INVALID_HANDLE;
-    if (s->generation != c->setGeneration) return PFAC_STATUS_INVALID_PARAMETER;     /* another pattern set since: PFACX_streamReset */
-    if (!c->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
     return PFAC_STATUS_SUCCESS;
 }
 
@@ -227,7 +186,7 @@ PFAC_status_t PFACX_streamMatchFromDevice(PFACX_stream_t stream, char *d_piece, 
     if (!stream || !stream->handle) return PFAC_STATUS_INVALID_HANDLE;
     std::lock_guard<std::mutex> own(stream->lock);
     std::lock_guard<std::mutex> guard(stream->handle->lock);      /* one lock around the set's check, M, seam and piece */
-    PFAC_status_t st = checkStream(stream);
+    PFAC_status_t st = checkSetGeneration(stream->handle, stream->generation);
     if (st != PFAC_STATUS_SUCCESS) return st;
     PFAC_context *c = stream->handle;
     if (!d_piece || !d_ids || !d_pos || !h_num_matched || !h_pieceOffset) return PFAC_STATUS_INVALID_PARAMETER;
@@ -235,10 +194,10 @@ PFAC_status_t PFACX_streamMatchFromDevice(PFACX_stream_t stream, char *d_piece, 
     const size_t M = (size_t)c->fa.maxPatternLen;
     if (capacity < size || capacity - size < M) return PFAC_STATUS_INVALID_PARAMETER;
     if (stream->kind == 1) return PFAC_STATUS_INVALID_PARAMETER;           /* a host-fed stream */
-    if (!c->hasDevice || !c->module || !c->stream_seam_ptr || !c->stream_reduce_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
     if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
-    correctTextureMode(c);
-    const Split sp = streamSplitOf(stream->carried, size, M);
+    correctTextureMode(c);                                                 /* (a piece that has only a seam resolves it too) */
+    const StreamSplit sp = streamSplitOf(stream->carried, size, M);
     int seamPairs = 0, piecePairs = 0;
     size_t nextCarried = 0;
     if (M > 1) {
@@ -253,11 +212,11 @@ PFAC_status_t PFACX_streamMatchFromDevice(PFACX_stream_t stream, char *d_piece, 
     if (sp.owned) {
         /* the piece in place (a caseless set: its fold, as in every device call), output behind the seam's pairs; a piece shorter than
          * M - 1 has nothing final and never gets here */
-        char *in = d_piece;
-        st = foldDeviceInput(c, d_piece, size, &in);
+        DeviceScan scan;
+        st = beginDeviceScan(c, d_piece, size, &scan);
         if (st != PFAC_STATUS_SUCCESS) return st;
-        st = c->stream_reduce_ptr(c, reinterpret_cast<int *>(in), (int)sp.owned, (int)size, d_ids + seamPairs, d_pos + seamPairs, &piecePairs,
-                                  c->perfMode == PFAC_TIME_DRIVEN ? 0 : 1);
+        st = c->stream_reduce_ptr(c, reinterpret_cast<int *>(scan.d_scan), (int)sp.owned, (int)size, d_ids + seamPairs, d_pos + seamPairs, &piecePairs,
+                                  scan.hashed);
         if (st != PFAC_STATUS_SUCCESS) return st;
     }
     *h_num_matched = seamPairs + piecePairs;
@@ -275,7 +234,7 @@ PFAC_status_t PFACX_streamMatchFromHost(PFACX_stream_t stream, char *h_piece, si
     if (!stream || !stream->handle) return PFAC_STATUS_INVALID_HANDLE;
     std::lock_guard<std::mutex> own(stream->lock);
     std::lock_guard<std::mutex> guard(stream->handle->lock);      /* one lock around the set's check, M, seam and piece */
-    PFAC_status_t st = checkStream(stream);
+    PFAC_status_t st = checkSetGeneration(stream->handle, stream->generation);
     if (st != PFAC_STATUS_SUCCESS) return st;
     PFAC_context *c = stream->handle;
     if (!h_piece || !h_ids || !h_pos || !h_num_matched || !h_pieceOffset) return PFAC_STATUS_INVALID_PARAMETER;
@@ -289,8 +248,7 @@ PFAC_status_t PFACX_streamMatchFromHost(PFACX_stream_t stream, char *h_piece, si
     int pairs = 0;
     try {
         std::vector<unsigned char> next;                       /* the stream changes when the whole call has succeeded */
-        std::vector<int> scratch;
-        st = hostPiece(c, stream->h_carry.data(), stream->carried, h_piece, size, false, h_ids, h_pos, scratch, next, &pairs);
+        st = hostPiece(c, stream->h_carry.data(), stream->carried, h_piece, size, false, h_ids, h_pos, next, &pairs);
         if (st != PFAC_STATUS_SUCCESS) return st;
         stream->h_carry.swap(next);
         stream->carried = stream->h_carry.size();
@@ -307,7 +265,7 @@ PFAC_status_t PFACX_streamFlush(PFACX_stream_t stream, int *ids, int *pos, size_
     if (!stream || !stream->handle) return PFAC_STATUS_INVALID_HANDLE;
     std::lock_guard<std::mutex> own(stream->lock);
     std::lock_guard<std::mutex> guard(stream->handle->lock);      /* one lock around the set's check, M, seam and piece */
-    PFAC_status_t st = checkStream(stream);
+    PFAC_status_t st = checkSetGeneration(stream->handle, stream->generation);
     if (st != PFAC_STATUS_SUCCESS) return st;
     PFAC_context *c = stream->handle;
     if (!ids || !pos || !h_num_matched) return PFAC_STATUS_INVALID_PARAMETER;
@@ -316,7 +274,7 @@ PFAC_status_t PFACX_streamFlush(PFACX_stream_t stream, int *ids, int *pos, size_
     const size_t carried = stream->carried;
     int pairs = 0;
     if (carried && stream->kind == 2) {
-        if (!c->hasDevice || !c->module || !c->stream_seam_ptr) return PFAC_STATUS_LIB_NOT_EXIST;
+        if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
         st = c->stream_seam_ptr(c, stream->d_carry[stream->cur], carried, nullptr, 0, carried, stream->d_carry[stream->cur ^ 1], stream->d_stage, ids, pos,
                                 &pairs);
         if (st != PFAC_STATUS_SUCCESS) return st;
@@ -324,8 +282,7 @@ PFAC_status_t PFACX_streamFlush(PFACX_stream_t stream, int *ids, int *pos, size_
         if (c->platform == PFAC_PLATFORM_GPU && (!c->hasDevice || !c->module)) return PFAC_STATUS_LIB_NOT_EXIST;
         try {
             std::vector<unsigned char> none;
-            std::vector<int> scratch;
-            st = hostPiece(c, stream->h_carry.data(), carried, nullptr, 0, true, ids, pos, scratch, none, &pairs);
+            st = hostPiece(c, stream->h_carry.data(), carried, nullptr, 0, true, ids, pos, none, &pairs);
         } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
         if (st != PFAC_STATUS_SUCCESS) return st;
     }

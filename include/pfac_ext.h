@@ -12,9 +12,11 @@
  * (PFACX_stream*), flow sets (PFACX_flows*), the lines that contain a
  * pattern (PFACX_matchLines*, PFACX_gatherLinesFromDevice), the bytes that
  * belong to a match, with their redaction (PFACX_matchSpans*,
- * PFACX_redactSpansFromDevice) and the number of occurrences of every pattern
+ * PFACX_redactSpansFromDevice), the number of occurrences of every pattern
  * (PFACX_countFromDevice / ...FromHost, PFACX_countPairsFromDevice,
- * PFACX_countNonzeroFromDevice).
+ * PFACX_countNonzeroFromDevice) and the disjoint leftmost-longest matches
+ * with their replacement by a string per pattern (PFACX_matchDisjoint*,
+ * PFACX_replaceFromDevice / ...FromHost).
  */
 #ifndef PFAC_EXT_H_
 #define PFAC_EXT_H_
@@ -557,6 +559,68 @@ PFAC_status_t PFACX_countPairsFromDevice(PFAC_handle_t handle, const int *d_ids,
 PFAC_status_t PFACX_countNonzeroFromDevice(PFAC_handle_t handle, const unsigned long long *d_counts, size_t numCounts,
                                            int *d_ids, unsigned long long *d_outCounts, size_t capacity,
                                            size_t *h_numDistinct, unsigned long long *h_total);
+
+/* Disjoint matches and replacement: the input tokenised into matches that do not overlap -- find_iter under leftmost-longest semantics -- and the text
+ * with every token substituted by a string that belongs to its pattern (sed -e s/p1/r1/g -e ... in one pass, replace_all).
+ *   Let r be the full result of PFAC_matchFromHost on a CPU platform over the buffer of n bytes and len(id) the length of pattern id.
+ *   THE DISJOINT LIST is what this loop selects:
+ *       p = 0
+ *       while p < n:
+ *           if r[p] > 0: take (r[p], p); p += len(r[p])
+ *           else:        p += 1
+ *   Among all matches the loop takes the one that starts leftmost, among those that start at one position the longest, and goes on behind the taken
+ *   match: a match that starts inside a taken match is not taken, even if it reaches further.  The list is ascending, the ranges [p, p + len) are
+ *   disjoint (they may touch), numTokens <= n; coveredBytes is the sum of the lengths.  Duplicate lines report under the highest id, as in every other
+ *   call.  A caseless handle (PFACX_READ_NOCASE): the list of the folded set over the folded input; the caller's bytes are never modified, and the
+ *   replacement reads the caller's original bytes.
+ *   THE REPLACEMENT TEXT of a token list (id_k, start_k), k < numTokens, and a replacement table repl(id) is
+ *       gap_0 repl(id_0) gap_1 repl(id_1) ... gap_numTokens
+ *   where gap_k is the input between the end of token k - 1 (0 in front of the first token) and start_k, and the last gap runs to n.
+ *   outBytes = n - the sum of len(id_k) + the sum of |repl(id_k)|: a size_t, computed in 64 bits; it can exceed 2^32.
+ * PFACX_matchDisjoint*: token k is (ids[k], pos[k]).  Both counts are written on every success.  capacity: entries of each array, >= size (smaller:
+ * PFAC_STATUS_INVALID_PARAMETER).  The arrays double as the scan's pair list, as the arrays of every compacted call do: entries below `size` may be
+ * overwritten beyond the tokens returned; nothing is written at or beyond capacity.
+ * size >= 2^31 or a null pointer: PFAC_STATUS_INVALID_PARAMETER; no pattern set: PFAC_STATUS_PATTERNS_NOT_READY; size == 0: success, both counts 0,
+ * nothing touched; the device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.
+ * Both calls are synchronous (the counts come to the host) and take the handle's lock.  The device form runs on whatever kernel variant, walker, perf
+ * mode and texture mode the handle selects.  The host form follows PFAC_setPlatform: the CPU platforms, host-only handles included, run on the CPU
+ * matcher plus the sequential loop above over the pairs, the list written in place (token k comes from pair >= k); the GPU platform runs the pipelined
+ * path of PFAC_matchFromHostReduce and the same loop on the host.
+ * MEMORY of the device form: grow-only handle scratch proportional to the PAIRS of the scan, not to the input -- with P pairs and B = (P + 511) / 512:
+ * 2 x 4 P + P + 4 B + 4 (B + 1) + 256 bytes, each term rounded up to 256: 9.02 bytes per pair at most, nothing when nothing matches -- plus the device
+ * copy of the pattern lengths (4 bytes per pattern, shared with the batch and the spans calls): deviceScratchBytes of PFACX_getInfo, freed by PFACX_trim.
+ * COST: the compacted scan WITH its ordering launches, then 6 + ceil(log2(B)) small launches over the pairs; no further pass over the
+ * input.
+ *
+ * PFACX_replaceFromDevice: the replacement text into d_out.  The replacement of pattern id is d_replBytes[d_replOff[id], d_replOff[id + 1]): numOff
+ * >= F + 2 entries, entry 0 unused (with tokens, a smaller numOff: PFAC_STATUS_INVALID_PARAMETER); replBytes < 2^31; an empty replacement deletes the
+ * match.  The token and offset arrays are DEVICE memory and the caller's contract, like the span arrays of the redaction: every start is clamped to
+ * [0, size], the length of a token is the length of pattern id of the handle's CURRENT set, clipped to size - start, an id outside [1, F] makes the
+ * token a no-op (nothing removed, nothing inserted), every offset is clamped to [0, replBytes], a decreasing pair of offsets is an empty replacement.
+ * For the ascending disjoint list PFACX_matchDisjoint* returns the output is exactly the replacement text; any other list gives unspecified text and
+ * an unspecified *h_outBytes, never an access outside the four buffers.  More than outCapacity: PFACX_STATUS_OUTPUT_TRUNCATED, *h_outBytes still the
+ * full size, nothing written at or beyond outCapacity, the contents of d_out unspecified; with outCapacity == 0 d_out may be null: the size query.
+ * [d_out, d_out + outCapacity) must not overlap [d_input, d_input + size): PFAC_STATUS_INVALID_PARAMETER (a text whose length changes has no in-place
+ * form).  numTokens == 0: a plain copy (the token and replacement arrays may then be null); size == 0: success, *h_outBytes = 0; numTokens >= 2^31 or
+ * size >= 2^31: PFAC_STATUS_INVALID_PARAMETER; no pattern set: PFAC_STATUS_PATTERNS_NOT_READY -- unlike the redaction the call needs the pattern
+ * lengths; a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.  Any alignment of d_input, d_out and d_replBytes.  Synchronous (the size comes to the host);
+ * takes the handle's lock.  Scratch: 8 bytes per token (the same allocation as the selection's).  Matches that are deleted and touch each other own
+ * no output byte; the tile of the output they fall into still walks them.
+ * PFACX_replaceFromHost: the same contract over host arrays: one sequential loop of memcpy whatever the platform, host-only handles included. */
+PFAC_status_t PFACX_matchDisjointFromDevice(PFAC_handle_t handle, char *d_input, size_t size,
+                                            int *d_ids, int *d_pos, size_t capacity,
+                                            size_t *h_numTokens, size_t *h_coveredBytes);
+PFAC_status_t PFACX_matchDisjointFromHost  (PFAC_handle_t handle, char *h_input, size_t size,
+                                            int *h_ids, int *h_pos, size_t capacity,
+                                            size_t *h_numTokens, size_t *h_coveredBytes);
+PFAC_status_t PFACX_replaceFromDevice(PFAC_handle_t handle, const char *d_input, size_t size,
+                                      const int *d_ids, const int *d_pos, size_t numTokens,
+                                      const int *d_replOff, size_t numOff, const char *d_replBytes, size_t replBytes,
+                                      char *d_out, size_t outCapacity, size_t *h_outBytes);
+PFAC_status_t PFACX_replaceFromHost  (PFAC_handle_t handle, const char *h_input, size_t size,
+                                      const int *h_ids, const int *h_pos, size_t numTokens,
+                                      const int *h_replOff, size_t numOff, const char *h_replBytes, size_t replBytes,
+                                      char *h_out, size_t outCapacity, size_t *h_outBytes);
 
 #ifdef __cplusplus
 }

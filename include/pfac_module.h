@@ -171,6 +171,23 @@ PFAC_status_t PFACX_countPairs(PFAC_handle_t handle, char *d_scan, size_t size, 
 PFAC_status_t PFACX_countNonzero(PFAC_handle_t handle, const unsigned long long *d_counts, size_t numCounts, int *d_ids,
                                  unsigned long long *d_outCounts, size_t capacity, size_t *h_numDistinct, unsigned long long *h_total);
 
+/* Disjoint matches and their replacement (no reference counterpart; include/pfac_ext.h: PFACX_matchDisjoint* / PFACX_replace*), scan_disjoint.hip.
+ * PFACX_disjointSelect: the disjoint leftmost-longest list of d_scan[0, size) -- 0 < size < 2^31; the caller's bytes, or their folded copy for a
+ * caseless set.  The scan (PFAC_reduce_kernel, hashed != 0: PFAC_reduce_inplace_kernel, WITH its ordering launches) uses d_ids / d_pos (`size` entries
+ * at least) as its pair list; the passes behind it work on the pairs alone, through d_patternLen (the pattern lengths by id, numIds entries) and the
+ * handle's disjoint scratch, and then overwrite the arrays with the tokens in ascending order.  Synchronous: *h_numTokens, and *h_coveredBytes = the sum
+ * of the lengths.
+ * PFACX_replaceRun: the text of d_input[0, size), 0 < size < 2^31, with each of the numTokens tokens (d_ids[k], d_pos[k]), 0 < numTokens < 2^31,
+ * replaced by d_replBytes[d_replOff[id], d_replOff[id + 1]) into d_out; every start is clamped to [0, size], every length is d_patternLen[id] clipped
+ * to the buffer, every offset clamped to [0, replBytes], an id outside [1, min(numIds, numOff - 1)) a token that does nothing.  Nothing is written
+ * at or beyond outCapacity; *h_outBytes = the size of the whole text (more than outCapacity: PFACX_STATUS_OUTPUT_TRUNCATED).  d_out must not overlap
+ * d_input (the caller checks).  Synchronous. */
+PFAC_status_t PFACX_disjointSelect(PFAC_handle_t handle, char *d_scan, size_t size, int hashed, const int *d_patternLen, size_t numIds, int *d_ids,
+                                   int *d_pos, size_t *h_numTokens, size_t *h_coveredBytes);
+PFAC_status_t PFACX_replaceRun(PFAC_handle_t handle, const char *d_input, size_t size, const int *d_ids, const int *d_pos, size_t numTokens,
+                               const int *d_patternLen, size_t numIds, const int *d_replOff, size_t numOff, const char *d_replBytes, size_t replBytes,
+                               char *d_out, size_t outCapacity, size_t *h_outBytes);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -182,7 +199,8 @@ PFAC_status_t PFACX_countNonzero(PFAC_handle_t handle, const unsigned long long 
     X(stream_seam_ptr, PFACX_streamSeam) X(stream_reduce_ptr, PFACX_streamReduce) X(flows_run_ptr, PFACX_flowsRun) \
     X(lines_select_ptr, PFACX_linesSelect) X(lines_gather_ptr, PFACX_linesGather) \
     X(spans_select_ptr, PFACX_spansSelect) X(spans_redact_ptr, PFACX_spansRedact) \
-    X(count_pairs_ptr, PFACX_countPairs) X(count_nonzero_ptr, PFACX_countNonzero)
+    X(count_pairs_ptr, PFACX_countPairs) X(count_nonzero_ptr, PFACX_countNonzero) \
+    X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

@@ -30,6 +30,8 @@ PFACX_READ_STRICT, PFACX_READ_STRIP_CR, PFACX_READ_NOCASE = 1, 2, 8
 PFACX_LINES_INVERT = 1                          # pfac_ext.h: PFACX_matchLines* select the lines that do NOT match
 PFACX_COUNT_LONGEST = 1                         # pfac_ext.h: PFACX_count* count one pattern per position, the longest
 PFACX_COUNT_ACCUMULATE = 2                      # ... add to counts[] instead of overwriting it
+PFACX_DISJOINT_BLOCK = 512                      # scan_disjoint.hip: kDisjointBlock, the pairs one block of the selection takes
+PFACX_REPLACE_TILE = 4096                       # scan_disjoint.hip: kReplaceTile, the output bytes of one tile of the replacement
 PFACX_COUNT_LDS_DIRECT = 16384                  # scan_count.hip: kCountDirect -- sets with F + 1 <= this count into a counter per id in LDS, larger ones into a tagged cache
 (PFACX_TABLE_DENSE, PFACX_TABLE_HASH_ROWPTR, PFACX_TABLE_HASH_VALPTR, PFACX_TABLE_INITIAL_ROW,
  PFACX_TABLE_FILTER_GRAM3, PFACX_TABLE_FILTER_SHORT, PFACX_TABLE_FILTER_LADDER, PFACX_TABLE_FILTER_FINAL3,
@@ -113,6 +115,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_matchLinesFromDevice", "PFACX_matchLinesFromHost", "PFACX_gatherLinesFromDevice",
     "PFACX_matchSpansFromDevice", "PFACX_matchSpansFromHost", "PFACX_redactSpansFromDevice",
     "PFACX_countFromDevice", "PFACX_countFromHost", "PFACX_countPairsFromDevice", "PFACX_countNonzeroFromDevice",
+    "PFACX_matchDisjointFromDevice", "PFACX_matchDisjointFromHost", "PFACX_replaceFromDevice", "PFACX_replaceFromHost",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -123,6 +126,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_linesSelect", "PFACX_linesGather", "PFACX_linesBitmapProbe",
     "PFACX_spansSelect", "PFACX_spansRedact",
     "PFACX_countPairs", "PFACX_countNonzero",
+    "PFACX_disjointSelect", "PFACX_replaceRun",
 )
 
 
@@ -223,6 +227,14 @@ def load_library() -> C.CDLL:
         lib.PFACX_countFromHost.argtypes = count
         lib.PFACX_countPairsFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t]
         lib.PFACX_countNonzeroFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, SZ, C.POINTER(C.c_ulonglong)]
+    if hasattr(lib, "PFACX_matchDisjointFromDevice"):
+        SZ = C.POINTER(C.c_size_t)
+        disjoint = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, SZ, SZ]
+        lib.PFACX_matchDisjointFromDevice.argtypes = disjoint
+        lib.PFACX_matchDisjointFromHost.argtypes = disjoint
+        replace = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, SZ]
+        lib.PFACX_replaceFromDevice.argtypes = replace
+        lib.PFACX_replaceFromHost.argtypes = replace
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -566,6 +578,35 @@ class PFAC:
         buf = data if data.size else np.zeros(1, dtype=np.uint8)
         _, total = self.countFromHost(buf.ctypes.data, data.size, PFACX_COUNT_LONGEST if longest else 0, counts.ctypes.data, counts.size)
         return counts, total
+
+    # -- disjoint leftmost-longest matches and their replacement (include/pfac_ext.h: PFACX_matchDisjoint* / PFACX_replace*) ----
+    def matchDisjointFromDevice(self, d_input: int, size: int, d_ids: int, d_pos: int, capacity: int, check: bool = True):
+        """``PFACX_matchDisjointFromDevice`` -> (status, number of tokens, covered bytes)."""
+        nt, cb = C.c_size_t(0), C.c_size_t(0)
+        st = self._lib.PFACX_matchDisjointFromDevice(self._h, d_input, size, d_ids, d_pos, capacity, C.byref(nt), C.byref(cb))
+        return self._ret(st, "PFACX_matchDisjointFromDevice", check), nt.value, cb.value
+
+    def matchDisjointFromHost(self, h_input: int, size: int, h_ids: int, h_pos: int, capacity: int, check: bool = True):
+        """``PFACX_matchDisjointFromHost`` -> (status, number of tokens, covered bytes); follows PFAC_setPlatform."""
+        nt, cb = C.c_size_t(0), C.c_size_t(0)
+        st = self._lib.PFACX_matchDisjointFromHost(self._h, h_input, size, h_ids, h_pos, capacity, C.byref(nt), C.byref(cb))
+        return self._ret(st, "PFACX_matchDisjointFromHost", check), nt.value, cb.value
+
+    def replaceFromDevice(self, d_input: int, size: int, d_ids, d_pos, num_tokens: int, d_repl_off, num_off: int, d_repl_bytes, repl_bytes: int,
+                          d_out, out_capacity: int, check: bool = True):
+        """``PFACX_replaceFromDevice`` -> (status, size of the whole text).  OUTPUT_TRUNCATED is returned, not raised."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_replaceFromDevice(self._h, d_input, size, d_ids, d_pos, num_tokens, d_repl_off, num_off, d_repl_bytes, repl_bytes,
+                                               d_out, out_capacity, C.byref(n))
+        return self._ret(st, "PFACX_replaceFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def replaceFromHost(self, h_input: int, size: int, h_ids, h_pos, num_tokens: int, h_repl_off, num_off: int, h_repl_bytes, repl_bytes: int,
+                        h_out, out_capacity: int, check: bool = True):
+        """``PFACX_replaceFromHost`` -> (status, size of the whole text).  OUTPUT_TRUNCATED is returned, not raised."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_replaceFromHost(self._h, h_input, size, h_ids, h_pos, num_tokens, h_repl_off, num_off, h_repl_bytes, repl_bytes,
+                                             h_out, out_capacity, C.byref(n))
+        return self._ret(st, "PFACX_replaceFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
 
     # -- input that arrives in pieces (include/pfac_ext.h: PFACX_stream*) ----------------
     def streamOpen(self, check: bool = True) -> "Stream":

@@ -64,7 +64,9 @@ constexpr HostSlot kHostGather = {20, 22};        /* a gather: the 64-bit size o
 constexpr HostSlot kHostSpans = {24, 26};         /* a spans call: one 64-bit value, the spans | the covered bytes << 32 (scan_spans.hip: pfac_spans_finish) */
 constexpr HostSlot kHostCount = {28, 30};         /* a count call: the 64-bit number of occurrences it added (scan_count.hip: pfac_count_store) */
 constexpr HostSlot kHostNonzero = {32, 36};       /* the non-zero counts: two 64-bit values, the distinct patterns, then the sum of the counts (scan_count.hip: pfac_count_finish) */
-constexpr int kHostWords = 40;
+constexpr HostSlot kHostDisjoint = {40, 42};      /* a disjoint call: one 64-bit value, the tokens | the covered bytes << 32 (scan_disjoint.hip: pfac_disjoint_finish) */
+constexpr HostSlot kHostReplace = {44, 46};       /* a replacement: the 64-bit sum of (replacement - match) lengths; the size of the text is the input's plus that (scan_disjoint.hip) */
+constexpr int kHostWords = 48;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -412,12 +414,17 @@ struct DeviceScratch {
      * of its total, or into the per-block values of the non-zero compaction (scan_count.hip has the formula); the pair list of PFACX_countFromDevice is
      * allPairs, the prefix table allTable: shared with the all-match calls */
     DeviceBuffer<char> count;
+    /* the disjoint and the replace calls (PFACX_matchDisjoint* / PFACX_replace*, scan_disjoint.hip): ONE allocation a select call cuts into the two
+     * jump arrays (behind them the staged tokens), the marks and the per-block token counts -- 9.02 bytes per pair of the scan at most --, a replace
+     * call into the 64-bit output offsets of its tokens and their block sums (scan_disjoint.hip has both formulas); not allocated before the first
+     * such call that finds a pair or gets a token */
+    DeviceBuffer<char> disjoint;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines);
-        f(spans); f(count);
+        f(spans); f(count); f(disjoint);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }

@@ -12,6 +12,7 @@
  *   scan_lines.hip    pfac_lines_*: the newline bitmap, the lines the scan's pairs fall into, their selection and gather (PFACX_matchLines*)
  *   scan_spans.hip    pfac_spans_*: the covered spans from the scan's ordered pairs (running maximum of the ends), the redaction (PFACX_matchSpans*)
  *   scan_count.hip    pfac_count_*: the histogram of the scan's pairs, the counts along the prefix chains, the non-zero counts (PFACX_count*)
+ *   scan_disjoint.hip pfac_disjoint_* / pfac_replace_*: the disjoint leftmost-longest list from the scan's ordered pairs (pointer doubling), the replacement (PFACX_matchDisjoint* / PFACX_replace*)
  * scan_passes.h holds what the units around the product kernels share on top of this: the hand-off to the host, block prefix sums, the seam.
  */
 #ifndef PFAC_SCAN_COMMON_H_

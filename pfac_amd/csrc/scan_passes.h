@@ -1,8 +1,9 @@
 /*
  * scan_passes.h -- what the passes around the scan share (scan_module.hip with scan_order.inc, scan_batch.hip, scan_all.hip, scan_fold.hip,
- * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip; the product kernels' units do not include it): launch sizes, the layout of a
+ * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip, scan_disjoint.hip; the product kernels' units do not include it): launch sizes, the layout of a
  * call's scratch, the compacted scan as a pass runs it, the hand-off of a call's result to the host through mapped memory, the device fold byte,
- * the clamp of a caller's (start, len), 16 bytes out of two aligned blocks (funnel), wave and block prefixes under a sum or a maximum, the two scan
+ * the clamp of a caller's (start, len), 16 bytes out of two aligned blocks (funnel, loadBytes16), wave and block prefixes under a sum or a maximum,
+ * the 64-ary search of a wave (waveLowerBound), the two scan
  * kernels (pfac_array_scan: one block, in place; pfac_block_scan: a block per 8192 values that folds what lies in front of them), the seam of
  * a stream.  Like scan_common.h, everything is in an unnamed namespace: inline device code, each
  * unit its own copy.
@@ -156,6 +157,28 @@ __device__ __forceinline__ u32x4 funnel(u32x4 a, u32x4 b, uint32_t r)
                  __builtin_amdgcn_alignbyte(w[Q + 3], w[Q + 2], r), __builtin_amdgcn_alignbyte(w[Q + 4], w[Q + 3], r)};
 }
 
+/* in[o, o + 16) of a buffer of n bytes, o + 16 <= n: one aligned load, two and a funnel, or -- where an aligned block would reach outside the buffer -- sixteen bytes */
+__device__ __forceinline__ u32x4 loadBytes16(const unsigned char *in, unsigned int n, unsigned int o)
+{
+    const unsigned int m = (unsigned int)(reinterpret_cast<uintptr_t>(in + o) & 15u);         /* the redaction: the same in every thread of a launch */
+    if (m == 0) return __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(in + o));
+    if (o >= m && o - m + 32u <= n) {
+        const u32x4 *blk = reinterpret_cast<const u32x4 *>(in + o - m);
+        const u32x4 x = __builtin_nontemporal_load(blk), y = __builtin_nontemporal_load(blk + 1);
+        switch (m >> 2) {
+        case 0: return funnel<0>(x, y, m & 3u);
+        case 1: return funnel<1>(x, y, m & 3u);
+        case 2: return funnel<2>(x, y, m & 3u);
+        default: return funnel<3>(x, y, m & 3u);
+        }
+    }
+    uint32_t w[4];
+#pragma unroll
+    for (int d = 0; d < 4; d++)
+        w[d] = (uint32_t)in[o + 4 * d] | (uint32_t)in[o + 4 * d + 1] << 8 | (uint32_t)in[o + 4 * d + 2] << 16 | (uint32_t)in[o + 4 * d + 3] << 24;
+    return u32x4{w[0], w[1], w[2], w[3]};
+}
+
 /* ------------------------------------------------------------------ wave and block prefixes */
 
 /* the operators of a prefix: the sum, and the maximum of unsigned values; 0 is the identity of both */
@@ -198,6 +221,28 @@ __device__ __forceinline__ T waveReduce(T v, Op op)
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v = op(v, __shfl_xor(v, d));
     return v;
+}
+
+/* the first i of [lo, hi) with pred(i), hi if there is none, for a pred that is false, then true (any other pred: some index of [lo, hi]); the
+ * whole wave calls it and gets the same answer: a probe per lane and round, the range shrinks 65-fold a round */
+template <class P>
+__device__ __forceinline__ unsigned int waveLowerBound(unsigned int lo, unsigned int hi, P pred)
+{
+    const unsigned int lane = threadIdx.x & 63u;
+    while (hi - lo > 64u) {
+        const unsigned long long width = hi - lo;
+        const unsigned int at = lo + (unsigned int)(width * (lane + 1u) / 65u);                  /* ascending, distinct, inside [lo, hi) */
+        const unsigned long long yes = __ballot(pred(at));
+        if (yes == 0) {
+            lo = lo + (unsigned int)(width * 64u / 65u) + 1u;
+        } else {
+            const unsigned int f = (unsigned int)__ffsll((long long)yes) - 1u;
+            hi = lo + (unsigned int)(width * (f + 1u) / 65u);
+            if (f > 0) lo = lo + (unsigned int)(width * f / 65u) + 1u;
+        }
+    }
+    const unsigned long long yes = __ballot(lane < hi - lo && pred(lo + lane));
+    return yes == 0 ? hi : lo + (unsigned int)__ffsll((long long)yes) - 1u;
 }
 
 /* exclusive prefix of `own` over the block's BLOCK threads, and the block's total (every thread calls it, every thread gets both);

@@ -178,49 +178,8 @@ struct RedactArgs {
 /* span i as bytes [s, e) (a caller that wants only s never loads the length) */
 __device__ __forceinline__ void spanOf(const RedactArgs &a, unsigned int i, unsigned int &s, unsigned int &e) { clampSpan(a.start[i], a.len[i], a.n, s, e); }
 
-/* the first i of [lo, hi) with pred(i), hi if there is none, for a pred that is false, then true (any other pred: some index of [lo, hi]); the
- * whole wave calls it and gets the same answer: a probe per lane and round, the range shrinks 65-fold a round */
-template <class P>
-__device__ __forceinline__ unsigned int waveLowerBound(unsigned int lo, unsigned int hi, P pred)
-{
-    const unsigned int lane = threadIdx.x & 63u;
-    while (hi - lo > 64u) {
-        const unsigned long long width = hi - lo;
-        const unsigned int at = lo + (unsigned int)(width * (lane + 1u) / 65u);                  /* ascending, distinct, inside [lo, hi) */
-        const unsigned long long yes = __ballot(pred(at));
-        if (yes == 0) {
-            lo = lo + (unsigned int)(width * 64u / 65u) + 1u;
-        } else {
-            const unsigned int f = (unsigned int)__ffsll((long long)yes) - 1u;
-            hi = lo + (unsigned int)(width * (f + 1u) / 65u);
-            if (f > 0) lo = lo + (unsigned int)(width * f / 65u) + 1u;
-        }
-    }
-    const unsigned long long yes = __ballot(lane < hi - lo && pred(lo + lane));
-    return yes == 0 ? hi : lo + (unsigned int)__ffsll((long long)yes) - 1u;
-}
-
-/* in[o, o + 16), o + 16 <= n: one aligned load, two and a funnel, or -- where an aligned block would reach outside the buffer -- sixteen bytes */
-__device__ __forceinline__ pfacmod::u32x4 load16(const RedactArgs &a, unsigned int o)
-{
-    const unsigned int m = (unsigned int)(reinterpret_cast<uintptr_t>(a.in + o) & 15u);         /* the same in every thread of a launch */
-    if (m == 0) return __builtin_nontemporal_load(reinterpret_cast<const pfacmod::u32x4 *>(a.in + o));
-    if (o >= m && o - m + 32u <= a.n) {
-        const pfacmod::u32x4 *blk = reinterpret_cast<const pfacmod::u32x4 *>(a.in + o - m);
-        const pfacmod::u32x4 x = __builtin_nontemporal_load(blk), y = __builtin_nontemporal_load(blk + 1);
-        switch (m >> 2) {
-        case 0: return funnel<0>(x, y, m & 3u);
-        case 1: return funnel<1>(x, y, m & 3u);
-        case 2: return funnel<2>(x, y, m & 3u);
-        default: return funnel<3>(x, y, m & 3u);
-        }
-    }
-    uint32_t w[4];
-#pragma unroll
-    for (int d = 0; d < 4; d++)
-        w[d] = (uint32_t)a.in[o + 4 * d] | (uint32_t)a.in[o + 4 * d + 1] << 8 | (uint32_t)a.in[o + 4 * d + 2] << 16 | (uint32_t)a.in[o + 4 * d + 3] << 24;
-    return pfacmod::u32x4{w[0], w[1], w[2], w[3]};
-}
+/* in[o, o + 16), o + 16 <= n (scan_passes.h: loadBytes16) */
+__device__ __forceinline__ pfacmod::u32x4 load16(const RedactArgs &a, unsigned int o) { return loadBytes16(a.in, a.n, o); }
 
 /* a nibble of the cover mask as the byte mask of a dword: bit i lands on bit 8 i and nothing carries */
 __device__ __forceinline__ uint32_t byteMask(uint32_t nibble) { return ((nibble * 0x00204081u) & 0x01010101u) * 0xFFu; }

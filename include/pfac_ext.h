@@ -622,6 +622,57 @@ PFAC_status_t PFACX_replaceFromHost  (PFAC_handle_t handle, const char *h_input,
                                       const int *h_replOff, size_t numOff, const char *h_replBytes, size_t replBytes,
                                       char *h_out, size_t outCapacity, size_t *h_outBytes);
 
+/* Rule sets: which segments of a batch contain EVERY pattern of a rule -- a Snort rule's content strings that must all occur in one packet, "ERROR
+ * and payment-service in the same line".  The all-match list says which pattern occurred where; this is the segmented group-by over (segment, rule)
+ * behind it, done on the device behind the scan.
+ *   A RULE SET is R rules over the handle's current pattern set of F patterns: rule r is the set of pattern ids h_rulePatterns[h_ruleOff[r],
+ *   h_ruleOff[r + 1]).  Pattern id OCCURS IN SEGMENT k if the all-match list of segment k alone (PFACX_matchAll* / PFACX_matchBatch*) contains a pair
+ *   with that id: occurrences lie entirely inside the segment; a pattern that is only a proper prefix of the longest one at a position counts; a
+ *   match that crosses a segment border does not.  Rule r FIRES on segment k if every one of its patterns occurs in k.
+ *   A caseless handle (PFACX_READ_NOCASE) folds patterns and input as in every other call; the caller's bytes are never modified.  Duplicate pattern
+ *   lines are one pattern and a rule may name any of their ids: at open every named id is resolved to the id that is reported (the highest), and
+ *   after that ids repeated within one rule count once.
+ * PFACX_rulesOpen copies the arrays.  PFAC_STATUS_INVALID_PARAMETER unless: every rule has 1 to 32 distinct patterns after resolution, every id lies
+ * in [1, F], h_ruleOff[0] == 0 and the offsets never decrease, 0 < numRules < 2^24 (the total number of ids is an int: below 2^31), no pointer is
+ * null.  Without a pattern set: PFAC_STATUS_PATTERNS_NOT_READY.
+ * THE FIRED LIST: the pairs (segment, rule) = (firedSeg[i], firedRule[i]) in ascending segment order, ascending rule order within a segment, each
+ * pair once.  segFirst (numSegments + 1 entries, may be NULL): the fired rules of segment k are entries [segFirst[k], segFirst[k + 1]).  The list can
+ * be longer than the input -- one byte that is a pattern named by a thousand rules fires a thousand rules -- so `capacity` (entries of each array)
+ * is free and need not be >= size.  A list longer than capacity: exactly its first `capacity` pairs are written and nothing behind them,
+ * *h_numFired is the full count, segFirst is complete, and the call returns PFACX_STATUS_OUTPUT_TRUNCATED; with capacity == 0 the two arrays may be
+ * null: the count query.  The scan's own pair list lives in the handle's pair scratch, never in the caller's arrays.
+ * Offsets follow the rules of PFACX_matchBatch*: host offsets are validated (first 0, last `size`, never decreasing), device offsets are clamped and
+ * never checked (wrong offsets: a wrong list, never an access outside the buffers).  offsets == NULL with numSegments == 1: the whole buffer is one
+ * segment.  PFAC_STATUS_INVALID_PARAMETER: numSegments >= 2^31, size >= 2^31, a null pointer other than those named above, offsets == NULL with
+ * numSegments != 1, numSegments == 0 with size > 0.  size == 0: success, 0 fired, segFirst all zero where given and numSegments > 0.  The device form on
+ * a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.  Both calls are synchronous (the count comes to the host) and take the handle's lock.
+ * The device form runs on whatever kernel variant, walker, perf mode and texture mode the handle selects.  The host form follows PFAC_setPlatform:
+ * the CPU platforms, host-only handles included, run on the CPU -- the longest pairs segment by segment, their prefix chains, one mask per touched
+ * rule (temporaries: 4 bytes per input byte and per segment, 4 per rule); the GPU platform runs the pipelined path of PFACX_matchBatchFromHost and the
+ * same loop on the host.
+ * A rule set belongs to the pattern set that was loaded when it was opened: after the handle reads or loads another set the ids mean something
+ * else, every match call returns PFAC_STATUS_INVALID_PARAMETER and only PFACX_rulesClose works.  Any number of rule sets per handle; PFAC_destroy
+ * closes them, as it closes streams and flow sets.
+ * MEMORY: the device tables of a rule set -- with I ids in all rules after resolution: 4 (F + 2) + 4 I + 4 R bytes, three allocations made by the first
+ * device call (opening on a host-only handle works) -- are state: counted under deviceTableBytes of PFACX_getInfo, kept by PFACX_trim, freed by
+ * PFACX_rulesClose.  What a device call stages is grow-only handle scratch, deviceScratchBytes, given back by PFACX_trim: 8 (numSegments + 1) bytes
+ * rounded up to 256 for the per-segment counts and their scan, and what the scan behind it shares with other calls: the pair list (8 bytes per input
+ * byte, the pair scratch of PFACX_matchAll* / PFACX_countFromDevice), 4 (numSegments + 1) bytes for the first pair of each segment, the {prefix, chain
+ * length} table (8 (F + 1) bytes), the pattern lengths (4 (F + 1) bytes) and the fix-up's scratch of PFACX_matchBatchFromDeviceReduce.  Nothing is
+ * sized by segments x rules.
+ * COST: the ordered compacted batch scan, then two passes over the pairs whose work follows the pairs times the memberships of the
+ * patterns on their prefix chains. */
+typedef struct PFACX_rules_s *PFACX_rules_t;
+PFAC_status_t PFACX_rulesOpen (PFAC_handle_t handle, const int *h_ruleOff /* numRules + 1 */, const int *h_rulePatterns,
+                               size_t numRules, PFACX_rules_t *rules);
+PFAC_status_t PFACX_rulesClose(PFACX_rules_t rules);
+PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                                         int *d_firedSeg, int *d_firedRule, size_t capacity, size_t *d_segFirst /* numSegments + 1, may be NULL */,
+                                         size_t *h_numFired);
+PFAC_status_t PFACX_rulesMatchFromHost  (PFACX_rules_t rules, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments,
+                                         int *h_firedSeg, int *h_firedRule, size_t capacity, size_t *h_segFirst /* may be NULL */,
+                                         size_t *h_numFired);
+
 #ifdef __cplusplus
 }
 #endif

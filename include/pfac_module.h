@@ -188,6 +188,30 @@ PFAC_status_t PFACX_replaceRun(PFAC_handle_t handle, const char *d_input, size_t
                                const int *d_patternLen, size_t numIds, const int *d_replOff, size_t numOff, const char *d_replBytes, size_t replBytes,
                                char *d_out, size_t outCapacity, size_t *h_outBytes);
 
+/* Rule sets (no reference counterpart; include/pfac_ext.h: PFACX_rules*), scan_rules.hip.
+ * PFACX_rulesRun: the fired (segment, rule) list of a batch from its ordered LONGEST pairs.  d_pairIds[0, count), count < 2^31, are the ids of the
+ * ordered compacted batch scan (in the handle's pair scratch); d_segFirstPairs (numSegments + 1 ints: the first pair of each segment, as
+ * PFACX_batchReduceFixup leaves them, clamped to [0, count] where read, a decreasing pair an empty segment), or null: one segment of all pairs.
+ * d_table: pfac::Int2 {prefixPattern, chainLen} by id, numIds + 1 entries.  The rule set: d_memberOff[numIds + 2], the memberships of pattern id
+ * at d_member[d_memberOff[id], d_memberOff[id + 1]) as rule << 5 | bit, ascending rule; d_need[numRules], the full mask of each rule; 0 < numRules <
+ * 2^24.  Output: the pairs in ascending (segment, rule) order into d_firedSeg / d_firedRule, nothing at or beyond `capacity` (0: both may be null);
+ * d_segFirst (numSegments + 1 size_t, or null) indexes the whole list; *h_total = its full length.  0 < numSegments < 2^31.  Synchronous. */
+typedef struct {
+    const int *d_pairIds;
+    size_t count;
+    const int *d_segFirstPairs;
+    size_t numSegments;
+    const void *d_table;
+    size_t numIds;
+    const int *d_memberOff;
+    const unsigned int *d_member, *d_need;
+    size_t numRules;
+    int *d_firedSeg, *d_firedRule;
+    size_t capacity;
+    size_t *d_segFirst;
+} PFACX_rulesRun_t;
+PFAC_status_t PFACX_rulesRun(PFAC_handle_t handle, const PFACX_rulesRun_t *run, size_t *h_total);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -200,7 +224,8 @@ PFAC_status_t PFACX_replaceRun(PFAC_handle_t handle, const char *d_input, size_t
     X(lines_select_ptr, PFACX_linesSelect) X(lines_gather_ptr, PFACX_linesGather) \
     X(spans_select_ptr, PFACX_spansSelect) X(spans_redact_ptr, PFACX_spansRedact) \
     X(count_pairs_ptr, PFACX_countPairs) X(count_nonzero_ptr, PFACX_countNonzero) \
-    X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun)
+    X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun) \
+    X(rules_run_ptr, PFACX_rulesRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

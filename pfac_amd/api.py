@@ -32,6 +32,9 @@ PFACX_COUNT_LONGEST = 1                         # pfac_ext.h: PFACX_count* count
 PFACX_COUNT_ACCUMULATE = 2                      # ... add to counts[] instead of overwriting it
 PFACX_DISJOINT_BLOCK = 512                      # scan_disjoint.hip: kDisjointBlock, the pairs one block of the selection takes
 PFACX_REPLACE_TILE = 4096                       # scan_disjoint.hip: kReplaceTile, the output bytes of one tile of the replacement
+PFACX_RULES_WINDOW = 8192                       # scan_rules.hip: kRulesWindow, the rules whose masks a block keeps in LDS at a time
+PFACX_RULES_TOUCHED = 1024                      # scan_rules.hip: kRulesTouched, the touched-list length; a segment that touches more rules of a window sweeps the whole table
+PFACX_RULES_BLOCK_PAIRS = 256                   # scan_rules.hip: kRulesBlockPairs, the pairs a block takes from a segment in one go
 PFACX_COUNT_LDS_DIRECT = 16384                  # scan_count.hip: kCountDirect -- sets with F + 1 <= this count into a counter per id in LDS, larger ones into a tagged cache
 (PFACX_TABLE_DENSE, PFACX_TABLE_HASH_ROWPTR, PFACX_TABLE_HASH_VALPTR, PFACX_TABLE_INITIAL_ROW,
  PFACX_TABLE_FILTER_GRAM3, PFACX_TABLE_FILTER_SHORT, PFACX_TABLE_FILTER_LADDER, PFACX_TABLE_FILTER_FINAL3,
@@ -116,6 +119,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_matchSpansFromDevice", "PFACX_matchSpansFromHost", "PFACX_redactSpansFromDevice",
     "PFACX_countFromDevice", "PFACX_countFromHost", "PFACX_countPairsFromDevice", "PFACX_countNonzeroFromDevice",
     "PFACX_matchDisjointFromDevice", "PFACX_matchDisjointFromHost", "PFACX_replaceFromDevice", "PFACX_replaceFromHost",
+    "PFACX_rulesOpen", "PFACX_rulesClose", "PFACX_rulesMatchFromDevice", "PFACX_rulesMatchFromHost",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -127,6 +131,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_spansSelect", "PFACX_spansRedact",
     "PFACX_countPairs", "PFACX_countNonzero",
     "PFACX_disjointSelect", "PFACX_replaceRun",
+    "PFACX_rulesRun",
 )
 
 
@@ -235,6 +240,13 @@ def load_library() -> C.CDLL:
         replace = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, SZ]
         lib.PFACX_replaceFromDevice.argtypes = replace
         lib.PFACX_replaceFromHost.argtypes = replace
+    if hasattr(lib, "PFACX_rulesOpen"):
+        SZ = C.POINTER(C.c_size_t)
+        lib.PFACX_rulesOpen.argtypes = [H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        lib.PFACX_rulesClose.argtypes = [C.c_void_p]
+        rules = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, SZ]
+        lib.PFACX_rulesMatchFromDevice.argtypes = rules
+        lib.PFACX_rulesMatchFromHost.argtypes = rules
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -624,6 +636,19 @@ class PFAC:
         self._ret(st, "PFACX_flowsOpen", check)
         return Flows(self, s, num_flows, st)
 
+    # -- which segments contain every pattern of a rule (include/pfac_ext.h: PFACX_rules*) ----------------
+    def rulesOpen(self, rule_off, rule_patterns, check: bool = True) -> "Rules":
+        """``PFACX_rulesOpen`` -> a :class:`Rules` set of this handle (``.status`` holds the call's status): rule r is the pattern ids
+        ``rule_patterns[rule_off[r]:rule_off[r + 1]]``; the arrays are copied."""
+        import numpy as np
+        off = np.ascontiguousarray(rule_off, dtype=np.int32)
+        pats = np.ascontiguousarray(rule_patterns, dtype=np.int32)
+        buf = pats if pats.size else np.zeros(1, dtype=np.int32)
+        s = C.c_void_p()
+        st = self._lib.PFACX_rulesOpen(self._h, off.ctypes.data if off.size else None, buf.ctypes.data, max(0, off.size - 1), C.byref(s))
+        self._ret(st, "PFACX_rulesOpen", check)
+        return Rules(self, s, max(0, off.size - 1), st)
+
     # -- numpy conveniences over matchFromHost (still the C ABI underneath) ----------
     def match_host_array(self, data):
         import numpy as np
@@ -824,3 +849,58 @@ class Flows:
         flb = fl if fl.size else np.zeros(1, dtype=np.uint32)
         st, n = self.flush(flb.ctypes.data, fl.size, ids.ctypes.data, pos.ctypes.data, cap, first.ctypes.data, check=check)
         return st, ids[:n].copy(), pos[:n].copy(), first
+
+
+class Rules:
+    """One rule set (``PFACX_rules_t``) of a handle: a batch of segments in, the (segment, rule) pairs of the rules whose patterns all occur
+    in one segment out.  Every match call returns ``(status, full length of the fired list)``; OUTPUT_TRUNCATED is returned, not raised."""
+
+    def __init__(self, handle: PFAC, rules: C.c_void_p, num_rules: int, status: int = 0):
+        self._owner = handle
+        self._lib = handle._lib
+        self._r = rules
+        self.num_rules = num_rules
+        self.status = status
+
+    def _ret(self, st: int, where: str, check: bool) -> int:
+        if check and st != 0:
+            raise PFACError(st, where, error_string(st))
+        return st
+
+    def match_device(self, d_input: int, size: int, d_offsets, num_segments: int, d_fired_seg, d_fired_rule, capacity: int, d_seg_first,
+                     check: bool = True):
+        """``PFACX_rulesMatchFromDevice``: `d_offsets` (num_segments + 1 ``size_t``, device) may be None with one segment, `d_seg_first`
+        (num_segments + 1 ``size_t``, device) may be None, the two arrays may be None with capacity 0."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_rulesMatchFromDevice(self._r, d_input, size, d_offsets, num_segments, d_fired_seg, d_fired_rule, capacity, d_seg_first,
+                                                  C.byref(n))
+        return self._ret(st, "PFACX_rulesMatchFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def match_host(self, h_input: int, size: int, h_offsets, num_segments: int, h_fired_seg, h_fired_rule, capacity: int, h_seg_first,
+                   check: bool = True):
+        """``PFACX_rulesMatchFromHost``: follows PFAC_setPlatform (the CPU platforms run on the CPU)."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_rulesMatchFromHost(self._r, h_input, size, h_offsets, num_segments, h_fired_seg, h_fired_rule, capacity, h_seg_first,
+                                                C.byref(n))
+        return self._ret(st, "PFACX_rulesMatchFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def close(self, check: bool = True) -> int:
+        st = self._lib.PFACX_rulesClose(self._r)
+        self._r = C.c_void_p()
+        return self._ret(st, "PFACX_rulesClose", check)
+
+    def match_host_array(self, data, offsets=None):
+        """match_host over numpy arrays -> (seg, rule, segFirst) of the whole fired list; offsets=None: the buffer is one segment."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uintp)
+        segments = 1 if off is None else off.size - 1
+        first = np.full(segments + 1, 0xDEAD, dtype=np.uintp)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        optr = None if off is None else off.ctypes.data
+        _, n = self.match_host(buf.ctypes.data, data.size, optr, segments, None, None, 0, first.ctypes.data)       # the count query
+        seg = np.full(max(1, n), -7, dtype=np.int32)
+        rule = np.full(max(1, n), -7, dtype=np.int32)
+        st, n2 = self.match_host(buf.ctypes.data, data.size, optr, segments, seg.ctypes.data, rule.ctypes.data, n, first.ctypes.data)
+        assert st == 0 and n2 == n
+        return seg[:n].copy(), rule[:n].copy(), first

@@ -401,6 +401,7 @@ PFAC_status_t PFAC_destroy(PFAC_handle_t handle)
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
     closeAllStreams(handle);
     closeAllFlowSets(handle);
+    closeAllRuleSets(handle);
     freeResources(handle);
     /* drops this handle's reference; the module stays mapped while other handles hold theirs (dlopen refcounts) */
     if (handle->module) dlclose(handle->module);
@@ -647,9 +648,9 @@ PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info)
         v.chainSlots = handle->h_chainSlots.size();
         v.multiProcessorCount = handle->multiProcessorCount;
         /* what the pattern set holds on the device -- the chained tables, the initial row, the prefilter bitmaps, the launch counters, the
-         * reference-layout table only while PFACX_KERNEL_REFTABLE has asked for it -- and the carried bytes of device-fed streams: state, not
+         * reference-layout table only while PFACX_KERNEL_REFTABLE has asked for it -- the carried bytes of device-fed streams and the tables of rule sets: state, not
          * scratch (PFACX_trim keeps them) */
-        v.deviceTableBytes = handle->tables.bytes() + streamDeviceBytes(handle) + flowsDeviceBytes(handle);
+        v.deviceTableBytes = handle->tables.bytes() + streamDeviceBytes(handle) + flowsDeviceBytes(handle) + rulesDeviceBytes(handle);
         /* ... and what its calls have left allocated (grow-only, PFACX_trim gives it back) */
         v.deviceScratchBytes = handle->scratch.bytes();
         if (handle->h_modeHint) {

@@ -66,7 +66,8 @@ constexpr HostSlot kHostCount = {28, 30};         /* a count call: the 64-bit nu
 constexpr HostSlot kHostNonzero = {32, 36};       /* the non-zero counts: two 64-bit values, the distinct patterns, then the sum of the counts (scan_count.hip: pfac_count_finish) */
 constexpr HostSlot kHostDisjoint = {40, 42};      /* a disjoint call: one 64-bit value, the tokens | the covered bytes << 32 (scan_disjoint.hip: pfac_disjoint_finish) */
 constexpr HostSlot kHostReplace = {44, 46};       /* a replacement: the 64-bit sum of (replacement - match) lengths; the size of the text is the input's plus that (scan_disjoint.hip) */
-constexpr int kHostWords = 48;
+constexpr HostSlot kHostRules = {48, 50};         /* a rules call: the 64-bit length of its fired list (scan_rules.hip, by pfac_array_scan) */
+constexpr int kHostWords = 52;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -419,12 +420,16 @@ struct DeviceScratch {
      * call into the 64-bit output offsets of its tokens and their block sums (scan_disjoint.hip has both formulas); not allocated before the first
      * such call that finds a pair or gets a token */
     DeviceBuffer<char> disjoint;
+    /* the rules calls (PFACX_rules*, scan_rules.hip): the 64-bit fired counts of the segments and, scanned in place, the first fired pair of each:
+     * 8 (numSegments + 1) bytes rounded up to 256; the pair list is allPairs, the first pair of each segment allSegFirst, the prefix table allTable:
+     * shared with the all-match calls.  The tables of a rule set are state of that set, not scratch (rules_api.cpp) */
+    DeviceBuffer<char> rules;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines);
-        f(spans); f(count); f(disjoint);
+        f(spans); f(count); f(disjoint); f(rules);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }
@@ -514,6 +519,8 @@ struct PFAC_context {
     unsigned long long setGeneration = 0;
     /* flow sets (PFACX_flows*, flows_api.cpp): the open sets of this handle (PFAC_destroy closes them); their carries are state like the streams' */
     std::vector<PFACX_flows_s *> flowSets;
+    /* rule sets (PFACX_rules*, rules_api.cpp): the open sets of this handle (PFAC_destroy closes them); their device tables are state like the carries */
+    std::vector<PFACX_rules_s *> ruleSets;
     void *h_flowPieces = nullptr;             /* pinned host memory a flows call builds its piece descriptors in (grow-only; freed with the scratch) */
     size_t h_flowPiecesBytes = 0;
 

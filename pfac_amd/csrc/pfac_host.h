@@ -114,6 +114,9 @@ PFAC_status_t hostPiece(PFAC_context *c, const unsigned char *carry, size_t carr
 /* flows_api.cpp: PFAC_destroy closes the handle's flow sets; the device bytes their carries hold (PFACX_getInfo: deviceTableBytes) */
 void closeAllFlowSets(PFAC_context *c);
 size_t flowsDeviceBytes(const PFAC_context *c);
+/* rules_api.cpp: PFAC_destroy closes the handle's rule sets; the device bytes their tables hold (PFACX_getInfo: deviceTableBytes) */
+void closeAllRuleSets(PFAC_context *c);
+size_t rulesDeviceBytes(const PFAC_context *c);
 /* batch_api.cpp: offsets[0] == 0, offsets[n] == size, never decreasing */
 bool batchOffsetsValid(const size_t *offsets, size_t numSegments, size_t size);
 /* batch_api.cpp: the batch calls (PFACX_matchBatch*) behind their argument checks; the caller holds c->lock */

@@ -1,0 +1,329 @@
+/*
+ * rules_api.cpp -- PFACX_rulesOpen / PFACX_rulesClose / PFACX_rulesMatchFromDevice / ...FromHost (include/pfac_ext.h): which segments of a batch
+ * contain every pattern of a rule.
+ *
+ * A rule set is inverted once, at open: every named id resolved to the id that is reported (duplicate lines), the ids of a rule made distinct and
+ * numbered 0 .. 31 in ascending order, then a CSR by pattern id -- memberOff[F + 2], member[] = rule << 5 | bit, ascending rule -- and need[rule],
+ * the full mask.  Pattern id occurs in a segment iff it lies on the prefix chain (Automaton::prefixPattern) of one of the segment's longest pairs, so
+ * both forms work on longest pairs.  The device form runs the ordered compacted scan into the handle's pair scratch (DeviceScratch::allPairs: the
+ * ids in its first half, the positions in its second, `size` entries each, as PFACX_countFromDevice sizes it), the batch fix-up of
+ * PFACX_matchBatchFromDeviceReduce behind it, and PFACX_rulesRun (scan_rules.hip) over the pairs.  The host form takes the longest pairs of every
+ * segment -- the CPU platforms through hostLongestPairs, segment by segment; the GPU platform through the pipelined batch path -- and keeps one
+ * mask per touched rule in a loop of its own.
+ */
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <shared_mutex>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "pfac_host.h"
+
+struct PFACX_rules_s {
+    PFAC_context *handle = nullptr;
+    unsigned long long generation = 0;        /* PFAC_context::setGeneration when the set was opened */
+    size_t numRules = 0;
+    size_t numIds = 0;                        /* F of the pattern set it was opened on */
+    std::vector<int> memberOff;               /* [F + 2] */
+    std::vector<unsigned int> member;         /* rule << 5 | bit, ascending rule within a pattern */
+    std::vector<unsigned int> need;           /* [numRules] */
+    /* the same on the device, uploaded by the first device call: state of the set (deviceTableBytes), freed by PFACX_rulesClose */
+    pfac::DeviceBuffer<int> d_memberOff;
+    pfac::DeviceBuffer<unsigned int> d_member, d_need;
+
+    void releaseDevice() { d_memberOff.release(); d_member.release(); d_need.release(); }
+    size_t deviceBytes() const { return d_memberOff.bytes() + d_member.bytes() + d_need.bytes(); }
+};
+
+namespace pfac_internal {
+
+void closeAllRuleSets(PFAC_context *c)
+{
+    for (PFACX_rules_s *s : c->ruleSets) {
+        s->releaseDevice();
+        delete s;
+    }
+    c->ruleSets.clear();
+}
+
+size_t rulesDeviceBytes(const PFAC_context *c)
+{
+    size_t bytes = 0;
+    for (const PFACX_rules_s *s : c->ruleSets) bytes += s->deviceBytes();
+    return bytes;
+}
+
+} // namespace pfac_internal
+using namespace pfac_internal;
+
+namespace {
+
+constexpr size_t kMaxRules = size_t(1) << 24, kMaxRulePatterns = 32, kTwoGiB = size_t(1) << 31;
+
+/* The rules inverted into s (the caller holds c->lock; the arguments are checked for null).  false: a rule set the contract refuses */
+bool invertRules(const pfac::Automaton &fa, const int *ruleOff, const int *rulePatterns, size_t numRules, PFACX_rules_s *s)
+{
+    const size_t F = (size_t)fa.numPatterns;
+    if (ruleOff[0] != 0) return false;
+    for (size_t r = 0; r < numRules; r++)
+        if (ruleOff[r + 1] < ruleOff[r]) return false;
+    std::unordered_map<std::string, int> reported;          /* the bytes of a pattern -> the id it is reported under; built when a lower id of duplicate lines is named */
+    auto bytesOf = [&](size_t id) {
+        return std::string(reinterpret_cast<const char *>(fa.file.data()) + fa.patternOff[id], (size_t)fa.patternLen[id]);
+    };
+    std::vector<std::vector<int>> rules(numRules);
+    for (size_t r = 0; r < numRules; r++) {
+        std::vector<int> &ids = rules[r];
+        for (int j = ruleOff[r]; j < ruleOff[r + 1]; j++) {
+            int id = rulePatterns[j];
+            if (id < 1 || (size_t)id > F) return false;
+            if (fa.chainLen[(size_t)id] <= 0) {             /* not in the trie: the lower id of duplicate lines */
+                if (reported.empty())
+                    for (size_t q = 1; q <= F; q++)
+                        if (fa.chainLen[q] > 0) reported.emplace(bytesOf(q), (int)q);
+                const auto it = reported.find(bytesOf((size_t)id));
+                if (it == reported.end()) return false;
+                id = it->second;
+            }
+            ids.push_back(id);
+        }
+        std::sort(ids.begin(), ids.end());
+        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        if (ids.empty() || ids.size() > kMaxRulePatterns) return false;
+    }
+    s->memberOff.assign(F + 2, 0);
+    for (const std::vector<int> &ids : rules)
+        for (int id : ids) s->memberOff[(size_t)id + 1]++;
+    for (size_t id = 0; id <= F; id++) s->memberOff[id + 1] += s->memberOff[id];
+    s->member.resize((size_t)s->memberOff[F + 1]);
+    s->need.resize(numRules);
+    std::vector<int> at(s->memberOff.begin(), s->memberOff.end() - 1);
+    for (size_t r = 0; r < numRules; r++) {                 /* ascending r: the memberships of a pattern ascend */
+        const std::vector<int> &ids = rules[r];
+        for (size_t b = 0; b < ids.size(); b++) s->member[(size_t)at[(size_t)ids[b]]++] = (unsigned int)(r << 5 | b);
+        s->need[r] = ids.size() == 32 ? 0xFFFFFFFFu : (1u << ids.size()) - 1u;
+    }
+    s->numRules = numRules;
+    s->numIds = F;
+    return true;
+}
+
+/* what both match calls check first, in the order of the contract (the generation and the pattern set: under the lock) */
+PFAC_status_t checkMatchArgs(PFACX_rules_t rules, const void *input, size_t size, const size_t *offsets, size_t numSegments, const int *firedSeg,
+                             const int *firedRule, size_t capacity, const size_t *h_numFired)
+{
+    if (!rules || !rules->handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!input || !h_numFired || (capacity && (!firedSeg || !firedRule)) || (!offsets && numSegments != 1)) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size >= kTwoGiB || numSegments >= kTwoGiB || (numSegments == 0 && size > 0)) return PFAC_STATUS_INVALID_PARAMETER;
+    return PFAC_STATUS_SUCCESS;
+}
+
+/* The fired list of a batch whose longest pairs are known: the ids of segment k at ids[first[k], first[k] + numPairs[k]).  Returns the full length */
+size_t firedOnHost(const pfac::Automaton &fa, const PFACX_rules_s &s, const int *ids, const size_t *first, const int *numPairs, size_t numSegments,
+                   int *firedSeg, int *firedRule, size_t capacity, size_t *segFirst)
+{
+    std::vector<unsigned int> mask(s.numRules, 0u);
+    std::vector<unsigned int> touched, fired;
+    size_t total = 0;
+    for (size_t k = 0; k < numSegments; k++) {
+        if (segFirst) segFirst[k] = total;
+        touched.clear();
+        fired.clear();
+        for (int i = 0; i < numPairs[k]; i++) {
+            int q = ids[first[k] + (size_t)i];
+            if (q < 1 || (size_t)q > s.numIds) continue;
+            const int steps = fa.chainLen[(size_t)q];
+            for (int c = 0; c < (steps > 1 ? steps : 1) && q >= 1 && (size_t)q <= s.numIds; c++) {
+                for (int j = s.memberOff[(size_t)q]; j < s.memberOff[(size_t)q + 1]; j++) {
+                    const unsigned int m = s.member[(size_t)j], r = m >> 5;
+                    if (mask[r] == 0) touched.push_back(r);
+                    mask[r] |= 1u << (m & 31u);
+                }
+                q = fa.prefixPattern[(size_t)q];
+            }
+        }
+        for (unsigned int r : touched) {
+            if (mask[r] == s.need[r]) fired.push_back(r);
+            mask[r] = 0;
+        }
+        std::sort(fired.begin(), fired.end());
+        for (unsigned int r : fired) {
+            if (total < capacity) { firedSeg[total] = (int)k; firedRule[total] = (int)r; }
+            total++;
+        }
+    }
+    if (segFirst) segFirst[numSegments] = total;
+    return total;
+}
+
+/* the first device call of a rule set: its tables (the caller holds the handle's lock) */
+PFAC_status_t ensureDeviceTables(PFACX_rules_s *s)
+{
+    if (s->d_need) return PFAC_STATUS_SUCCESS;
+    PFAC_status_t st = s->d_memberOff.upload(s->memberOff.data(), s->memberOff.size());
+    if (st == PFAC_STATUS_SUCCESS) st = s->d_member.upload(s->member.data(), s->member.size());
+    if (st == PFAC_STATUS_SUCCESS) st = s->d_need.upload(s->need.data(), s->need.size());
+    if (st != PFAC_STATUS_SUCCESS) s->releaseDevice();
+    return st;
+}
+
+} // namespace
+
+extern "C" {
+
+PFAC_status_t PFACX_rulesOpen(PFAC_handle_t handle, const int *h_ruleOff, const int *h_rulePatterns, size_t numRules, PFACX_rules_t *rules)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!rules) return PFAC_STATUS_INVALID_PARAMETER;
+    *rules = nullptr;
+    if (!h_ruleOff || !h_rulePatterns || numRules == 0 || numRules >= kMaxRules) return PFAC_STATUS_INVALID_PARAMETER;
+    PFACX_rules_s *s = new (std::nothrow) PFACX_rules_s();
+    if (!s) return PFAC_STATUS_ALLOC_FAILED;
+    std::lock_guard<std::mutex> guard(handle->lock);
+    if (!handle->isPatternsReady) { delete s; return PFAC_STATUS_PATTERNS_NOT_READY; }
+    try {
+        if (!invertRules(handle->fa, h_ruleOff, h_rulePatterns, numRules, s)) { delete s; return PFAC_STATUS_INVALID_PARAMETER; }
+        handle->ruleSets.push_back(s);
+    } catch (const std::bad_alloc &) { delete s; return PFAC_STATUS_ALLOC_FAILED; }
+    s->handle = handle;
+    s->generation = handle->setGeneration;
+    *rules = s;
+    return PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t PFACX_rulesClose(PFACX_rules_t rules)
+{
+    if (!rules || !rules->handle) return PFAC_STATUS_INVALID_HANDLE;
+    PFAC_context *c = rules->handle;
+    {
+        std::lock_guard<std::mutex> guard(c->lock);
+        auto it = std::find(c->ruleSets.begin(), c->ruleSets.end(), rules);
+        if (it == c->ruleSets.end()) return PFAC_STATUS_INVALID_HANDLE;
+        c->ruleSets.erase(it);
+        rules->releaseDevice();
+    }
+    delete rules;
+    return PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                                         int *d_firedSeg, int *d_firedRule, size_t capacity, size_t *d_segFirst, size_t *h_numFired)
+{
+    PFAC_status_t st = checkMatchArgs(rules, d_input, size, d_offsets, numSegments, d_firedSeg, d_firedRule, capacity, h_numFired);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    PFAC_context *c = rules->handle;
+    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    std::lock_guard<std::mutex> guard(c->lock);
+    st = checkSetGeneration(c, rules->generation);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (size == 0) {
+        if (d_segFirst && numSegments && hipMemset(d_segFirst, 0, (numSegments + 1) * sizeof(size_t)) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+        *h_numFired = 0;
+        return PFAC_STATUS_SUCCESS;
+    }
+    st = ensureDeviceTables(rules);
+    if (st == PFAC_STATUS_SUCCESS) st = ensureAllTable(c);
+    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = ensurePatternLen(c);
+    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = c->scratch.allSegFirst.reserve(numSegments + 1);
+    pfac::DeviceBuffer<int> &pairs = c->scratch.allPairs;
+    if (st == PFAC_STATUS_SUCCESS) st = pairs.reserve(2 * size);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    int *ids = pairs.get(), *pos = ids + pairs.count() / 2;               /* one allocation: the ids, then as many positions */
+    DeviceScan scan;                                                      /* a caseless set: the scan and the fix-up read the folded bytes */
+    st = beginDeviceScan(c, d_input, size, &scan);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    int count = 0;
+    st = reduceOnDevice(c, scan.d_scan, size, ids, pos, &count);          /* ordered: the fix-up and the segments' first pairs search the positions */
+    if (st == PFAC_STATUS_SUCCESS && d_offsets)
+        st = c->batch_reduce_fixup_ptr(c, scan.d_scan, size, d_offsets, numSegments, ids, pos, &count, c->scratch.allSegFirst.get(), c->scratch.patternLen.get());
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (count < 0) return PFAC_STATUS_INTERNAL_ERROR;
+    PFACX_rulesRun_t run{};
+    run.d_pairIds = ids;
+    run.count = (size_t)count;
+    run.d_segFirstPairs = d_offsets ? c->scratch.allSegFirst.get() : nullptr;
+    run.numSegments = numSegments;
+    run.d_table = c->scratch.allTable.get();
+    run.numIds = rules->numIds;
+    run.d_memberOff = rules->d_memberOff.get();
+    run.d_member = rules->d_member.get();
+    run.d_need = rules->d_need.get();
+    run.numRules = rules->numRules;
+    run.d_firedSeg = d_firedSeg;
+    run.d_firedRule = d_firedRule;
+    run.capacity = capacity;
+    run.d_segFirst = d_segFirst;
+    size_t total = 0;
+    st = c->rules_run_ptr(c, &run, &total);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    *h_numFired = total;
+    return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t PFACX_rulesMatchFromHost(PFACX_rules_t rules, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments,
+                                       int *h_firedSeg, int *h_firedRule, size_t capacity, size_t *h_segFirst, size_t *h_numFired)
+{
+    PFAC_status_t st = checkMatchArgs(rules, h_input, size, h_offsets, numSegments, h_firedSeg, h_firedRule, capacity, h_numFired);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (h_offsets && numSegments && !batchOffsetsValid(h_offsets, numSegments, size)) return PFAC_STATUS_INVALID_PARAMETER;
+    PFAC_context *c = rules->handle;
+    const size_t whole[2] = {0, size};
+    const size_t *offsets = h_offsets ? h_offsets : whole;
+    const bool onGpu = c->platform == PFAC_PLATFORM_GPU;
+    std::unique_lock<std::mutex> guard(c->lock);
+    st = checkSetGeneration(c, rules->generation);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (size == 0) {
+        if (h_segFirst && numSegments) std::memset(h_segFirst, 0, (numSegments + 1) * sizeof(size_t));
+        *h_numFired = 0;
+        return PFAC_STATUS_SUCCESS;
+    }
+    if (onGpu && (!c->hasDevice || !c->module)) return PFAC_STATUS_LIB_NOT_EXIST;
+    size_t longest = 0;
+    for (size_t k = 0; k < numSegments; k++) longest = std::max(longest, offsets[k + 1] - offsets[k]);
+    /* the longest ids of segment k from ids[offsets[k]] on; not initialised: a page nothing writes costs nothing */
+    std::unique_ptr<int[]> ids(new (std::nothrow) int[size]), pos(onGpu ? nullptr : new (std::nothrow) int[longest]);
+    std::vector<int> numPairs;
+    try {
+        numPairs.assign(numSegments, 0);
+    } catch (const std::bad_alloc &) {
+        return PFAC_STATUS_ALLOC_FAILED;
+    }
+    if (!ids || (!onGpu && !pos)) return PFAC_STATUS_ALLOC_FAILED;
+    if (onGpu) {
+        /* the pipelined batch path: the full result of every segment, compacted in place (pair z of a segment comes from an entry at or behind z) */
+        st = matchBatchHostOnGpu(c, h_input, size, offsets, numSegments, ids.get());
+        if (st != PFAC_STATUS_SUCCESS) return st;
+        for (size_t k = 0; k < numSegments; k++) {
+            int z = 0;
+            for (size_t i = offsets[k]; i < offsets[k + 1]; i++)
+                if (ids[i] > 0) ids[offsets[k] + (size_t)z++] = ids[i];
+            numPairs[k] = z;
+        }
+    } else {
+        guard.unlock();                                     /* the CPU platforms: the helper takes the lock while it prepares the tables, several threads match side by side */
+        for (size_t k = 0; k < numSegments; k++) {
+            const size_t n = offsets[k + 1] - offsets[k];
+            if (n == 0) continue;
+            st = hostLongestPairs(c, h_input + offsets[k], n, ids.get() + offsets[k], pos.get(), &numPairs[k]);
+            if (st != PFAC_STATUS_SUCCESS) return st;
+        }
+    }
+    std::shared_lock<std::shared_mutex> tables(c->tablesInUse);
+    if (!onGpu && (rules->generation != c->setGeneration || (size_t)c->fa.numPatterns != rules->numIds)) return PFAC_STATUS_INVALID_PARAMETER;   /* another thread has replaced the set meanwhile */
+    try {
+        const size_t total = firedOnHost(c->fa, *rules, ids.get(), offsets, numPairs.data(), numSegments, h_firedSeg, h_firedRule, capacity, h_segFirst);
+        *h_numFired = total;
+        return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+    } catch (const std::bad_alloc &) {
+        return PFAC_STATUS_ALLOC_FAILED;
+    }
+}
+
+} /* extern "C" */

@@ -48,7 +48,7 @@ static PFAC_status_t matchAllDeviceLocked(PFAC_context *c, char *d_input, size_t
         ids = c->scratch.allPairs.get();
         pos = ids + c->scratch.allPairs.count() / 2;              /* one allocation: the ids, then as many positions */
     } else {
-        st = reduceOnDevice(c, d_input, size, d_ids, d_pos, &count);
+        st = reduceOnDevice(c, d_input, size, d_ids, d_pos, true, &count);
     }
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (d_offsets)

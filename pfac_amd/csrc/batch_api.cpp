@@ -126,7 +126,7 @@ PFAC_status_t PFACX_matchBatchFromDeviceReduce(PFAC_handle_t handle, char *d_inp
     if (st != PFAC_STATUS_SUCCESS) return st;
     d_input = scan.d_scan;
     int count = 0;
-    st = reduceOnDevice(handle, d_input, size, d_matched_result, d_pos, &count);
+    st = reduceOnDevice(handle, d_input, size, d_matched_result, d_pos, true, &count);
     if (st != PFAC_STATUS_SUCCESS) return st;
     st = handle->batch_reduce_fixup_ptr(handle, d_input, size, d_offsets, numSegments, d_matched_result, d_pos, &count, d_segFirst, handle->scratch.patternLen.get());
     if (st != PFAC_STATUS_SUCCESS) return st;

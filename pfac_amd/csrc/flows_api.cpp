@@ -311,7 +311,7 @@ PFAC_status_t PFACX_flowsMatchFromDevice(PFACX_flows_t flows, char *d_input, siz
         if (anyOwned) {
             DeviceScan scan;
             st = beginDeviceScan(c, d_input, size, &scan);
-            if (st == PFAC_STATUS_SUCCESS) st = reduceOnDevice(c, scan.d_scan, size, d_ids, d_pos, &scanCount);
+            if (st == PFAC_STATUS_SUCCESS) st = reduceOnDevice(c, scan.d_scan, size, d_ids, d_pos, true, &scanCount);
             if (st != PFAC_STATUS_SUCCESS) return st;
         }
         st = runOnDevice(flows, d_input, numPieces, sumFinal, (size_t)scanCount, d_ids, d_pos, capacity, d_pieceFirst, &total);

@@ -3,55 +3,24 @@
  * (ref PFAC/src/PFAC.cpp:879-961, 1010-1128: allocate, upload, scan, download, free, in sequence).  The stream goes through two
  * staging pieces owned by the handle: piece i + 1 uploads while piece i is scanned by the compacted-output kernel, only the
  * (position, id) pairs come back, the zeros of the result vector are written on the host.
+ * How the threads of such a call work together -- the cut into pieces, the uploader beside the scans, the zero-fill team and their waits -- is
+ * piece_pipeline.h (no HIP in it: tools/tsan_pipeline.cpp runs it under ThreadSanitizer); the HIP calls of a piece are stagedPairs() below, once for
+ * both calls, which differ in what they do with a piece's pairs.
  */
-#include <dlfcn.h>
-#include <pthread.h>
-#include <sched.h>
-#include <sys/syscall.h>
-#include <unistd.h>
 #include <hip/hip_runtime_api.h>
 
-#if defined(__SSE2__)
-#include <emmintrin.h>
-#endif
-
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <memory>
 #include <new>
-#include <system_error>
-#include <thread>
 #include <vector>
 
 #include "pfac_host.h"
+#include "piece_pipeline.h"
 
 using pfac::Int2;
 using namespace pfac_internal;
-
-namespace {
-
-/* The threads of a host call wait for each other's progress -- the uploader for a scanned buffer, the caller for an upload to be queued and for
- * a piece of its vector to be filled -- on a condition variable: round 5 spun on std::this_thread::yield(), which on a host whose cores are all
- * busy (the zero fill runs up to eight threads beside the DMA engine's reads) takes the very cores the fill threads need.  Progress counters stay
- * atomics (the fast path is one acquire load); whoever advances one calls bump(). */
-struct Progress {
-    std::mutex m;
-    std::condition_variable cv;
-    void bump() { { std::lock_guard<std::mutex> g(m); } cv.notify_all(); }
-    template <class Pred> void wait(Pred done)
-    {
-        if (done()) return;
-        std::unique_lock<std::mutex> g(m);
-        cv.wait(g, done);
-    }
-};
-
-} // namespace
 
 namespace pfac_internal {
 
@@ -105,16 +74,14 @@ static PFAC_status_t ensureHostStage(PFAC_context *c, size_t need)
 PFAC_status_t prepareHostPath(PFAC_context *c, size_t maxBytes)
 {
     if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
-    const size_t overlap = (size_t)c->fa.maxPatternLen;
-    const size_t want = maxBytes == 0 || maxBytes > kHostPiece ? kHostPiece : maxBytes;
-    PFAC_status_t st = ensureHostStage(c, want + overlap);
+    const size_t n = PieceCut(maxBytes ? maxBytes : kHostPiece, ~size_t(0), kHostPiece, (size_t)c->fa.maxPatternLen).stageNeed();   /* the longest piece of such a call */
+    PFAC_status_t st = ensureHostStage(c, n);
     if (st != PFAC_STATUS_SUCCESS) return st;
     correctTextureMode(c);
     int filler = 0;                                            /* a byte the initial state has no transition on, if there is one: the scan then finds nothing */
     for (int b = 0; b < pfac::kCharSet && (size_t)b < c->h_initialRow.size(); b++)
         if (c->h_initialRow[(size_t)b] == pfac::kTrapState) { filler = b; break; }
     hipStream_t up = static_cast<hipStream_t>(c->stageUp);
-    const size_t n = want + overlap;
     bool ok = true;
     try {
         const std::vector<char> pageable(n, (char)filler);
@@ -124,9 +91,7 @@ PFAC_status_t prepareHostPath(PFAC_context *c, size_t maxBytes)
     if (!ok) { (void)hipGetLastError(); return PFAC_STATUS_INTERNAL_ERROR; }
     for (int b = 0; b < 2 && st == PFAC_STATUS_SUCCESS; b++) {              /* both buffers, the way both host calls use them: pairs in any order / in position order */
         int count = 0;
-        c->reduceUnordered = b == 0;
-        st = reduceOnDevice(c, c->scratch.stageIn[b].get(), n, c->scratch.stageOut[b].get(), c->scratch.stagePos[b].get(), &count);
-        c->reduceUnordered = false;
+        st = reduceOnDevice(c, c->scratch.stageIn[b].get(), n, c->scratch.stageOut[b].get(), c->scratch.stagePos[b].get(), /* ordered */ b == 1, &count);
     }
     if (st == PFAC_STATUS_SUCCESS && hipStreamSynchronize(nullptr) != hipSuccess) st = PFAC_STATUS_INTERNAL_ERROR;
     return st;
@@ -135,33 +100,30 @@ PFAC_status_t prepareHostPath(PFAC_context *c, size_t maxBytes)
 /* every result crosses the link: pieces with many matches */
 static PFAC_status_t matchHostFullVector(PFAC_context *c, char *h_inputString, size_t owned, size_t readable, int *h_matched_result)
 {
-    const size_t overlap = (size_t)c->fa.maxPatternLen;
-    const size_t piece = owned < kHostPiece ? owned : kHostPiece;
-    PFAC_status_t st = ensureHostStage(c, piece + overlap);
+    const PieceCut cut(owned, readable, kHostPiece, (size_t)c->fa.maxPatternLen);
+    PFAC_status_t st = ensureHostStage(c, cut.stageNeed());
     if (st != PFAC_STATUS_SUCCESS) return st;
     hipStream_t up = static_cast<hipStream_t>(c->stageUp), down = static_cast<hipStream_t>(c->stageDown);
     bool used[2] = {false, false};
-    size_t i = 0;
-    for (size_t off = 0; off < owned && st == PFAC_STATUS_SUCCESS; off += piece, i++) {
-        const int b = (int)(i & 1);
+    for (size_t i = 0; i < cut.numPieces() && st == PFAC_STATUS_SUCCESS; i++) {
+        const Piece p = cut.at(i);
+        const int b = p.buffer;
         char *const d_in = c->scratch.stageIn[b].get();
         int *const d_ids = c->scratch.stageOut[b].get();
-        const size_t mine = owned - off < piece ? owned - off : piece;
-        const size_t scanned = readable - off < mine + overlap ? readable - off : mine + overlap;
         hipEvent_t evUp = static_cast<hipEvent_t>(c->evUp[b]), evScan = static_cast<hipEvent_t>(c->evScan[b]),
                    evDown = static_cast<hipEvent_t>(c->evDown[b]);
         bool ok = true;
         if (used[b]) ok = hipStreamWaitEvent(up, evScan, 0) == hipSuccess;          /* the scan of piece i-2 has read this buffer */
-        ok = ok && hipMemcpyAsync(d_in, h_inputString + off, scanned, hipMemcpyHostToDevice, up) == hipSuccess &&
+        ok = ok && hipMemcpyAsync(d_in, h_inputString + p.off, p.scanned, hipMemcpyHostToDevice, up) == hipSuccess &&
              hipEventRecord(evUp, up) == hipSuccess && hipStreamWaitEvent(nullptr, evUp, 0) == hipSuccess;
         if (ok && used[b]) ok = hipStreamWaitEvent(nullptr, evDown, 0) == hipSuccess;   /* its results have left this buffer */
         if (!ok) { st = PFAC_STATUS_INTERNAL_ERROR; break; }
-        st = foldStaged(c, d_in, scanned);                  /* a caseless set: in place, behind the upload */
+        st = foldStaged(c, d_in, p.scanned);                  /* a caseless set: in place, behind the upload */
         if (st != PFAC_STATUS_SUCCESS) break;
-        st = matchDeviceLocked(c, d_in, scanned, d_ids);
+        st = matchDeviceLocked(c, d_in, p.scanned, d_ids);
         if (st != PFAC_STATUS_SUCCESS) break;
         ok = hipEventRecord(evScan, nullptr) == hipSuccess && hipStreamWaitEvent(down, evScan, 0) == hipSuccess &&
-             hipMemcpyAsync(h_matched_result + off, d_ids, mine * sizeof(int), hipMemcpyDeviceToHost, down) == hipSuccess &&
+             hipMemcpyAsync(h_matched_result + p.off, d_ids, p.mine * sizeof(int), hipMemcpyDeviceToHost, down) == hipSuccess &&
              hipEventRecord(evDown, down) == hipSuccess;
         if (!ok) st = PFAC_STATUS_INTERNAL_ERROR;
         used[b] = true;
@@ -173,270 +135,116 @@ static PFAC_status_t matchHostFullVector(PFAC_context *c, char *h_inputString, s
 }
 
 /*
- * PFAC_matchFromHost on the GPU.  Four of the five bytes per position that the reference moves over the host link
- * (PFAC.cpp:916-960) are results, and nearly all of them are zero.  So the pieces are scanned with the compacted-
- * output kernel and only the (position, id) pairs come back; the zeros are written where they are needed -- by a few
- * helper threads of this call straight into the caller's result vector, while the pieces are uploaded and scanned --
- * and the pairs are scattered on top at the end.  A piece in which more than one position in eight matches takes the
- * full-vector route above instead (after the zero fill, so the two never write the same words at the same time).
+ * The staged compacted scan of a host buffer, what both calls below are built on: the pieces of `cut` go up into stageIn[i & 1] on the upload
+ * stream (evUp[i & 1] behind each; by a thread of their own: piece_pipeline.h runPieces), the default stream waits for a piece's event, folds the
+ * piece in place (a caseless set) and scans it with the compacted-output kernel, and take(piece, count, d_ids, d_pos) -> status gets its pairs --
+ * in position order if `ordered` -- while the next piece is on its way.  A pair whose position is not below piece.mine lies in the read-ahead: it
+ * is the next piece's, which finds it again.  Both streams are drained before this returns.  at(Staged) tells a caller with a clock or threads of
+ * its own where the call is; nothing is told if the staging buffers cannot be had.
  */
-/* The NUMA node a host page lives on (-1: unknown, not faulted in yet, or no such system call): move_pages with no target only reports. */
-static int numaNodeOf(const void *p)
+enum class Staged { ready, uploadsBegun, piecesDone, drained };
+template <class At, class Take>
+static PFAC_status_t stagedPairs(PFAC_context *c, char *h_inputString, const PieceCut &cut, bool ordered, At at, Take take)
 {
-#if defined(__linux__) && defined(SYS_move_pages)
-    void *page = reinterpret_cast<void *>(reinterpret_cast<uintptr_t>(p) & ~uintptr_t(4095));
-    int status = -1;
-    if (syscall(SYS_move_pages, 0, 1UL, &page, nullptr, &status, 0) == 0 && status >= 0) return status;
-#else
-    (void)p;
-#endif
-    return -1;
-}
-/* the CPUs of a NUMA node that this thread may run on (empty: unknown) */
-static bool cpusOfNumaNode(int node, cpu_set_t &out)
-{
-    CPU_ZERO(&out);
-    char path[96];
-    std::snprintf(path, sizeof(path), "/sys/devices/system/node/node%d/cpulist", node);
-    FILE *f = std::fopen(path, "r");
-    if (!f) return false;
-    char buf[4096];
-    const size_t got = std::fread(buf, 1, sizeof(buf) - 1, f);
-    std::fclose(f);
-    buf[got] = 0;
-    cpu_set_t allowed;
-    if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return false;
-    int any = 0;
-    for (char *q = buf; *q;) {
-        char *end = nullptr;
-        const long a = std::strtol(q, &end, 10);
-        if (end == q) break;
-        long b = a;
-        if (*end == '-') { q = end + 1; b = std::strtol(q, &end, 10); }
-        for (long c = a; c <= b && c < CPU_SETSIZE; c++)
-            if (c >= 0 && CPU_ISSET((int)c, &allowed)) { CPU_SET((int)c, &out); any++; }
-        q = (*end == ',') ? end + 1 : end;
-        if (*end != ',' ) break;
-    }
-    return any > 0;
-}
-
-/* zeros without reading the lines first: streaming stores, 64 bytes per trip (the result vector of a 1 GiB call is 4 GiB
- * that nothing reads before the caller does) */
-static void fillZeroStreaming(int *p, size_t n)
-{
-#if !defined(__SSE2__)
-    std::memset(p, 0, n * sizeof(int));                        /* hosts without SSE2 (aarch64, ppc64 nodes with AMD GPUs): plain stores */
-    return;
-#else
-    static const bool plain = std::getenv("PFAC_HOST_FILL_MEMSET") != nullptr;
-    if (plain) { std::memset(p, 0, n * sizeof(int)); return; }
-    while (n && (reinterpret_cast<uintptr_t>(p) & 63u)) { *p++ = 0; n--; }
-    const __m128i z = _mm_setzero_si128();
-    for (; n >= 16; n -= 16, p += 16) {
-        _mm_stream_si128(reinterpret_cast<__m128i *>(p), z);
-        _mm_stream_si128(reinterpret_cast<__m128i *>(p + 4), z);
-        _mm_stream_si128(reinterpret_cast<__m128i *>(p + 8), z);
-        _mm_stream_si128(reinterpret_cast<__m128i *>(p + 12), z);
-    }
-    while (n) { *p++ = 0; n--; }
-    _mm_sfence();
-#endif
-}
-
-PFAC_status_t matchHostOnGpu(PFAC_context *c, char *h_inputString, size_t owned, size_t readable, int *h_matched_result)
-{
-    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
-    const size_t overlap = (size_t)c->fa.maxPatternLen;
-    const size_t piece = owned < kHostPiece ? owned : kHostPiece;
-    PFAC_status_t st = ensureHostStage(c, piece + overlap);
+    PFAC_status_t st = ensureHostStage(c, cut.stageNeed());
     if (st != PFAC_STATUS_SUCCESS) return st;
     correctTextureMode(c);
     hipStream_t up = static_cast<hipStream_t>(c->stageUp);
-    const size_t numPieces = (owned + piece - 1) / piece;
-    auto uploadPiece = [&](size_t i) -> bool {               /* into buffer i & 1, on the upload stream */
-        const size_t off = i * piece;
-        const size_t mine = owned - off < piece ? owned - off : piece;
-        const size_t scanned = readable - off < mine + overlap ? readable - off : mine + overlap;
-        return hipMemcpyAsync(c->scratch.stageIn[i & 1].get(), h_inputString + off, scanned, hipMemcpyHostToDevice, up) == hipSuccess &&
-               hipEventRecord(static_cast<hipEvent_t>(c->evUp[i & 1]), up) == hipSuccess;
-    };
-    /* the link first: nothing below is worth a microsecond of an idle copy engine */
-    const bool trace = std::getenv("PFAC_HOST_TRACE") != nullptr;
-    const auto tStart = std::chrono::steady_clock::now();
-    auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tStart).count(); };
-    /* The uploads are queued by a thread of their own: hipMemcpyAsync from PAGEABLE memory does not return until the runtime
-     * has staged the piece (0.6 ms for 32 MiB), and this thread has the scans to launch and their pairs to fetch meanwhile.
-     * Piece i goes into buffer i & 1 once the scan of piece i - 2 is over. */
-    std::atomic<size_t> scansDone{0}, uploadsQueued{0};
-    std::atomic<bool> uploadFailed{false}, stopUploads{false};
-    Progress progress;                                         /* what the threads of this call wait for each other on */
+    at(Staged::ready);
     int device = 0;
     (void)hipGetDevice(&device);
-    std::thread uploader;
-    bool ok = true;
-    if (numPieces == 1) {                                      /* nothing to overlap with: no thread (tens of microseconds of a small call) */
-        ok = uploadPiece(0);
-        uploadsQueued.store(1);
-    } else {
-        try {
-            uploader = std::thread([&]() {
-                if (hipSetDevice(device) != hipSuccess) { uploadFailed.store(true); progress.bump(); return; }
-                for (size_t i = 0; i < numPieces; i++) {
-                    if (i >= 2) progress.wait([&]() { return scansDone.load(std::memory_order_acquire) + 1 >= i || stopUploads.load(std::memory_order_relaxed); });
-                    if (stopUploads.load(std::memory_order_relaxed)) return;
-                    if (!uploadPiece(i)) { uploadFailed.store(true); progress.bump(); return; }
-                    uploadsQueued.store(i + 1, std::memory_order_release);
-                    progress.bump();
-                }
-            });
-        } catch (...) { ok = false; }
-    }
-    const double tUp0 = since();
-
-    /* Zero fill of the caller's vector, in parallel with everything below: 4 bytes of host memory per position against 1 byte
-     * over the link, so it takes a few threads -- sized from the cores this thread may run on (a caller bound to a cpuset has
-     * fewer than the machine) up to 8: the fill and the link's reads share the host's memory channels, and beyond eight
-     * threads the upload loses more than the fill gains (256 MiB from pinned buffers on a 2 x 64-core box, link 54 GB/s:
-     * 47.0 / 48.8 / 43.8 / 43.3 / 46.4 GB/s with 4 / 8 / 12 / 16 / 24 threads; memset instead of streaming stores: 24.7) --
-     * streaming stores, and the pieces IN ORDER, every thread its share of each: the pairs of piece k are scattered as soon
-     * as they are back, while piece k + 1 uploads, not in one pass at the end.  (PFAC_HOST_FILL_THREADS overrides the count:
-     * a measurement aid.) */
-    unsigned helpers = 0;
-    if (owned >= (size_t(4) << 20)) {
-        unsigned hw = std::thread::hardware_concurrency();
-        cpu_set_t allowed;
-        if (sched_getaffinity(0, sizeof(allowed), &allowed) == 0) hw = (unsigned)CPU_COUNT(&allowed);
-        helpers = hw >= 64 ? 8 : hw >= 16 ? 4 : hw >= 4 ? 2 : 1;
-        if (const char *e = std::getenv("PFAC_HOST_FILL_THREADS")) { const int v = std::atoi(e); if (v >= 1 && v <= 256) helpers = (unsigned)v; }
-    }
-    auto share = [&](size_t k, unsigned t, unsigned of, size_t &lo, size_t &hi) {          /* thread t's part of piece k */
-        const size_t off = k * piece, mine = owned - off < piece ? owned - off : piece;
-        lo = off + mine * t / of / 16 * 16;
-        hi = t + 1 == of ? off + mine : off + mine * (t + 1) / of / 16 * 16;
-    };
-    std::unique_ptr<std::atomic<unsigned>[]> filled;
-    std::vector<std::thread> fillers;
-    /* read by the fill threads for as long as they run: declared where joinAll() still sees them */
-    cpu_set_t fillCpus;
-    CPU_ZERO(&fillCpus);
-    bool bindFill = false;
-    try {
-        filled.reset(new std::atomic<unsigned>[numPieces]);
-        for (size_t k = 0; k < numPieces; k++) filled[k].store(0, std::memory_order_relaxed);
-        fillers.reserve(helpers);
-        /* The fill threads run on the NUMA node the caller's result vector lives on: 4 bytes per position of streaming stores that
-         * cross the sockets' link meet the link's own reads of the input there (2 x EPYC 9575F, GPU on node 0, pinned buffers
-         * first-touched on node 1: p50 7.4 ms, p90 11.4 ms per 256 MiB call against 5.5 / 6.2 ms with the buffers on node 0 --
-         * the driver's round-4 line: 29 GB/s median; tools/host_numa_probe.py).  PFAC_HOST_FILL_ANYWHERE=1 leaves them to the OS. */
-        if (helpers && std::getenv("PFAC_HOST_FILL_ANYWHERE") == nullptr) {
-            const int node = numaNodeOf(h_matched_result + owned / 2);
-            bindFill = node >= 0 && cpusOfNumaNode(node, fillCpus);
-        }
-        for (unsigned t = 0; t < helpers; t++)
-            fillers.emplace_back([&, t]() {
-                if (bindFill) (void)pthread_setaffinity_np(pthread_self(), sizeof(fillCpus), &fillCpus);
-                for (size_t k = 0; k < numPieces; k++) {
-                    size_t lo, hi;
-                    share(k, t, helpers, lo, hi);
-                    fillZeroStreaming(h_matched_result + lo, hi - lo);
-                    filled[k].fetch_add(1, std::memory_order_release);
-                    progress.bump();
-                }
-            });
-    } catch (...) { /* no memory, or fewer threads than planned: the shares nobody started are filled by this thread, below */ }
-    if (!filled) {                                             /* not even the counters: no helper was started */
-        std::memset(h_matched_result, 0, owned * sizeof(int));
-        helpers = 0;
-    }
-    const unsigned started = (unsigned)fillers.size();
-    const double tThreads = since();
-    auto joinAll = [&]() { for (std::thread &t : fillers) if (t.joinable()) t.join(); };
-    /* piece k of the caller's vector is all zeros when this returns */
-    auto waitFilled = [&](size_t k) {
-        if (!filled) return;
-        if (helpers == 0) {                                    /* a small call: this thread fills, piece by piece */
-            size_t lo, hi;
-            share(k, 0, 1, lo, hi);
-            if (filled[k].load(std::memory_order_relaxed) == 0) { std::memset(h_matched_result + lo, 0, (hi - lo) * sizeof(int)); filled[k].store(1, std::memory_order_relaxed); }
-            return;
-        }
-        if (filled[k].load(std::memory_order_acquire) < helpers) {          /* acquire: the pairs are scattered onto words the fillers wrote */
-            for (unsigned t = started; t < helpers; t++) {          /* the shares of threads that could not be started */
-                size_t lo, hi;
-                share(k, t, helpers, lo, hi);
-                fillZeroStreaming(h_matched_result + lo, hi - lo);
-            }
-            progress.wait([&]() { return filled[k].load(std::memory_order_acquire) >= started; });
-            filled[k].store(helpers, std::memory_order_relaxed);
-        }
-    };
-
-    std::vector<int> pos, id;                                  /* the pairs of one piece */
-    std::vector<size_t> densePieces;
-    try {
-        for (size_t i = 0; i < numPieces && ok && st == PFAC_STATUS_SUCCESS; i++) {
-            const int b = (int)(i & 1);
-            char *const d_in = c->scratch.stageIn[b].get();
-            int *const d_ids = c->scratch.stageOut[b].get(), *const d_pos = c->scratch.stagePos[b].get();
-            const size_t off = i * piece;
-            const size_t mine = owned - off < piece ? owned - off : piece;
-            const size_t scanned = readable - off < mine + overlap ? readable - off : mine + overlap;
-            progress.wait([&]() { return uploadsQueued.load(std::memory_order_acquire) > i || uploadFailed.load(std::memory_order_relaxed); });
-            ok = !uploadFailed.load(std::memory_order_relaxed) && hipStreamWaitEvent(nullptr, static_cast<hipEvent_t>(c->evUp[b]), 0) == hipSuccess;
-            if (!ok) break;
-            st = foldStaged(c, d_in, scanned);              /* a caseless set: in place, behind the upload */
-            if (st != PFAC_STATUS_SUCCESS) break;
-            int count = 0;
-            c->reduceUnordered = true;
-            st = reduceOnDevice(c, d_in, scanned, d_ids, d_pos, &count);
-            c->reduceUnordered = false;
-            if (st != PFAC_STATUS_SUCCESS) break;
-            scansDone.store(i + 1, std::memory_order_release);     /* the scan is synchronous: its input buffer may take piece i + 2 */
-            progress.bump();
-            if ((size_t)count > mine / 8) { densePieces.push_back(i); continue; }
-            pos.resize((size_t)count);
-            id.resize((size_t)count);
-            if (count && (hipMemcpy(pos.data(), d_pos, (size_t)count * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-                          hipMemcpy(id.data(), d_ids, (size_t)count * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)) {
-                ok = false;
-                break;
-            }
-            waitFilled(i);                                     /* long done, as a rule: the fill runs ahead of the link */
-            for (size_t k = 0; k < pos.size(); k++)
-                if ((size_t)pos[k] < mine) h_matched_result[off + (size_t)pos[k]] = id[k];   /* beyond: the next piece's (or nobody's) */
-        }
-        if (!ok && st == PFAC_STATUS_SUCCESS) st = PFAC_STATUS_INTERNAL_ERROR;
-    } catch (const std::bad_alloc &) { st = PFAC_STATUS_ALLOC_FAILED; }
-    stopUploads.store(true);
-    progress.bump();
-    if (uploader.joinable()) uploader.join();
-    const double tLoop = since();
+    int count = 0;                                             /* of the piece scanned last */
+    st = runPieces(
+        cut.numPieces(), [&]() { return hipSetDevice(device) == hipSuccess; },
+        [&](size_t i) {
+            const Piece p = cut.at(i);
+            return hipMemcpyAsync(c->scratch.stageIn[p.buffer].get(), h_inputString + p.off, p.scanned, hipMemcpyHostToDevice, up) == hipSuccess &&
+                   hipEventRecord(static_cast<hipEvent_t>(c->evUp[p.buffer]), up) == hipSuccess;
+        },
+        [&]() { at(Staged::uploadsBegun); },
+        [&](size_t i) {
+            const Piece p = cut.at(i);
+            char *const d_in = c->scratch.stageIn[p.buffer].get();
+            if (hipStreamWaitEvent(nullptr, static_cast<hipEvent_t>(c->evUp[p.buffer]), 0) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+            const PFAC_status_t folded = foldStaged(c, d_in, p.scanned);          /* a caseless set: in place, behind the upload */
+            if (folded != PFAC_STATUS_SUCCESS) return folded;
+            return reduceOnDevice(c, d_in, p.scanned, c->scratch.stageOut[p.buffer].get(), c->scratch.stagePos[p.buffer].get(), ordered, &count);
+        },
+        [&](size_t i) {
+            const Piece p = cut.at(i);
+            return take(p, (size_t)count, c->scratch.stageOut[p.buffer].get(), c->scratch.stagePos[p.buffer].get());
+        });
+    at(Staged::piecesDone);
     const bool drained = hipStreamSynchronize(up) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
     if (!drained && st == PFAC_STATUS_SUCCESS) st = PFAC_STATUS_INTERNAL_ERROR;
-    const double tDrained = since();
-    for (size_t k = 0; k < numPieces; k++) waitFilled(k);      /* every element of the caller's vector is written, whatever happened */
-    joinAll();
-    if (trace) std::fprintf(stderr, "PFAC_HOST_TRACE %zu B %zu pieces %u helpers: first upload queued %.3f ms, threads started %.3f, piece loop done %.3f, drained %.3f, filled+joined %.3f\n",
-                            owned, numPieces, started, tUp0, tThreads, tLoop, tDrained, since());
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    for (size_t i : densePieces) {
-        const size_t off = i * piece;
-        const size_t mine = owned - off < piece ? owned - off : piece;
-        st = matchHostFullVector(c, h_inputString + off, mine, readable - off, h_matched_result + off);
-        if (st != PFAC_STATUS_SUCCESS) return st;
+    at(Staged::drained);
+    return st;
+}
+
+/*
+ * PFAC_matchFromHost on the GPU.  Four of the five bytes per position that the reference moves over the host link
+ * (PFAC.cpp:916-960) are results, and nearly all of them are zero.  So the pieces are scanned with the compacted-
+ * output kernel and only the (position, id) pairs come back; the zeros are written where they are needed -- by a few
+ * helper threads of this call straight into the caller's result vector, while the pieces are uploaded and scanned
+ * (piece_pipeline.h: ZeroFill) -- and the pairs of a piece are scattered on top as soon as they are back.  A piece in which
+ * more than one position in eight matches takes the full-vector route above instead (after the zero fill, so the two
+ * never write the same words at the same time).
+ */
+PFAC_status_t matchHostOnGpu(PFAC_context *c, char *h_inputString, size_t owned, size_t readable, int *h_matched_result)
+{
+    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    const PieceCut cut(owned, readable, kHostPiece, (size_t)c->fa.maxPatternLen);
+    unsigned helpers = 0;                                      /* of the zero fill: sized from the cores this thread may run on, up to 8 */
+    if (owned >= (size_t(4) << 20)) {
+        const unsigned hw = ZeroFill::cpusAllowed();
+        helpers = ZeroFill::fromEnv(hw >= 64 ? 8 : hw >= 16 ? 4 : hw >= 4 ? 2 : 1);
     }
-    return PFAC_STATUS_SUCCESS;
+    ZeroFill fill(h_matched_result, cut, helpers);
+    const bool trace = std::getenv("PFAC_HOST_TRACE") != nullptr;
+    std::chrono::steady_clock::time_point tStart;
+    auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tStart).count(); };
+    double tUp0 = 0, tThreads = 0, tLoop = 0;
+    auto at = [&](Staged where) {
+        if (where == Staged::ready) tStart = std::chrono::steady_clock::now();
+        else if (where == Staged::uploadsBegun) {              /* the link first: the fill is not worth a microsecond of an idle copy engine */
+            tUp0 = since();
+            fill.start();
+            tThreads = since();
+        } else if (where == Staged::piecesDone) tLoop = since();
+        else {
+            const double tDrained = since();
+            fill.finish();                                     /* every element of the caller's vector is written, whatever happened */
+            if (trace) std::fprintf(stderr, "PFAC_HOST_TRACE %zu B %zu pieces %u helpers: first upload queued %.3f ms, threads started %.3f, piece loop done %.3f, drained %.3f, filled+joined %.3f\n",
+                                    owned, cut.numPieces(), fill.started(), tUp0, tThreads, tLoop, tDrained, since());
+        }
+    };
+    std::vector<int> pos, id;                                  /* the pairs of one piece */
+    std::vector<Piece> densePieces;
+    PFAC_status_t st = stagedPairs(c, h_inputString, cut, /* ordered */ false, at, [&](const Piece &p, size_t count, const int *d_ids, const int *d_pos) {
+        if (count > p.mine / 8) { densePieces.push_back(p); return PFAC_STATUS_SUCCESS; }
+        pos.resize(count);
+        id.resize(count);
+        if (count && (hipMemcpy(pos.data(), d_pos, count * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+                      hipMemcpy(id.data(), d_ids, count * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
+            return PFAC_STATUS_INTERNAL_ERROR;
+        fill.waitFilled(p.index);                              /* long done, as a rule: the fill runs ahead of the link */
+        for (size_t k = 0; k < count; k++)
+            if ((size_t)pos[k] < p.mine) h_matched_result[p.off + (size_t)pos[k]] = id[k];   /* beyond: the next piece's (or nobody's) */
+        return PFAC_STATUS_SUCCESS;
+    });
+    for (size_t k = 0; k < densePieces.size() && st == PFAC_STATUS_SUCCESS; k++) {
+        const Piece &p = densePieces[k];
+        st = matchHostFullVector(c, h_inputString + p.off, p.mine, readable - p.off, h_matched_result + p.off);
+    }
+    return st;
 }
 
 /*
  * PFAC_matchFromHostReduce on the GPU (ref PFAC.cpp:1010-1128: one allocation of size + 8 * size device bytes, one blocking
  * copy, one scan, two copies back).  Same pipeline as PFAC_matchFromHost: the stream goes through the handle's staging
- * buffers in pieces of kHostReducePiece positions, piece i + 1 is uploaded (by a thread of its own: see matchHostOnGpu) while
- * piece i is scanned by the compacted-output kernel -- together with the maxPatternLen bytes behind it -- and its pairs, in
- * position order, are copied straight behind those of the pieces before it: pieces are in stream order, so the whole list
- * is.  A pair whose position lies in the overlap belongs to the next piece, which finds it again.  Device memory: two
- * pieces (9 bytes per position) instead of 9 bytes for every position of the stream.
+ * buffers in pieces of kHostReducePiece positions, and the pairs of a piece, in position order, are copied straight behind
+ * those of the pieces before it: pieces are in stream order, so the whole list is.  Device memory: two pieces (9 bytes per
+ * position) instead of 9 bytes for every position of the stream.
  * The stream may be a slice of a longer one (PFACX_matchFromHostReduceMultiGPU): positions [0, owned) get their pairs, `readable`
  * bytes may be read, posBase is added to every position; the caller's arrays hold `owned` entries.
  */
@@ -444,79 +252,21 @@ constexpr size_t kHostReducePiece = size_t(16) << 20;
 PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t size, size_t readable, size_t posBase, int *h_matched_result, int *h_pos, int *h_num_matched)
 {
     if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
-    const size_t overlap = (size_t)c->fa.maxPatternLen;
-    const size_t piece = size < kHostReducePiece ? size : kHostReducePiece;
-    PFAC_status_t st = ensureHostStage(c, piece + overlap);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    correctTextureMode(c);
-    hipStream_t up = static_cast<hipStream_t>(c->stageUp);
-    const size_t numPieces = (size + piece - 1) / piece;
-    auto uploadPiece = [&](size_t i) -> bool {               /* into buffer i & 1, on the upload stream */
-        const size_t off = i * piece;
-        const size_t mine = size - off < piece ? size - off : piece;
-        const size_t scanned = readable - off < mine + overlap ? readable - off : mine + overlap;
-        return hipMemcpyAsync(c->scratch.stageIn[i & 1].get(), h_inputString + off, scanned, hipMemcpyHostToDevice, up) == hipSuccess &&
-               hipEventRecord(static_cast<hipEvent_t>(c->evUp[i & 1]), up) == hipSuccess;
-    };
-    std::atomic<size_t> scansDone{0}, uploadsQueued{0};
-    std::atomic<bool> uploadFailed{false}, stopUploads{false};
-    Progress progress;
-    int device = 0;
-    (void)hipGetDevice(&device);
-    std::thread uploader;
-    bool ok = true;
-    if (numPieces == 1) {                                      /* nothing to overlap: no thread */
-        ok = uploadPiece(0);
-        uploadsQueued.store(1);
-    } else {
-        try {
-            uploader = std::thread([&]() {
-                if (hipSetDevice(device) != hipSuccess) { uploadFailed.store(true); progress.bump(); return; }
-                for (size_t i = 0; i < numPieces; i++) {
-                    if (i >= 2) progress.wait([&]() { return scansDone.load(std::memory_order_acquire) + 1 >= i || stopUploads.load(std::memory_order_relaxed); });
-                    if (stopUploads.load(std::memory_order_relaxed)) return;
-                    if (!uploadPiece(i)) { uploadFailed.store(true); progress.bump(); return; }
-                    uploadsQueued.store(i + 1, std::memory_order_release);
-                    progress.bump();
-                }
-            });
-        } catch (...) { ok = false; }
-    }
+    const PieceCut cut(size, readable, kHostReducePiece, (size_t)c->fa.maxPatternLen);
     size_t total = 0;
-    for (size_t i = 0; i < numPieces && ok && st == PFAC_STATUS_SUCCESS; i++) {
-        const int b = (int)(i & 1);
-        char *const d_in = c->scratch.stageIn[b].get();
-        int *const d_ids = c->scratch.stageOut[b].get(), *const d_pos = c->scratch.stagePos[b].get();
-        const size_t off = i * piece;
-        const size_t mine = size - off < piece ? size - off : piece;
-        const size_t scanned = readable - off < mine + overlap ? readable - off : mine + overlap;
-        progress.wait([&]() { return uploadsQueued.load(std::memory_order_acquire) > i || uploadFailed.load(std::memory_order_relaxed); });
-        ok = !uploadFailed.load(std::memory_order_relaxed) && hipStreamWaitEvent(nullptr, static_cast<hipEvent_t>(c->evUp[b]), 0) == hipSuccess;
-        if (!ok) break;
-        st = foldStaged(c, d_in, scanned);                  /* a caseless set: in place, behind the upload */
-        if (st != PFAC_STATUS_SUCCESS) break;
-        int count = 0;
-        st = reduceOnDevice(c, d_in, scanned, d_ids, d_pos, &count);
-        if (st != PFAC_STATUS_SUCCESS) break;
-        scansDone.store(i + 1, std::memory_order_release);     /* the scan is synchronous: its input buffer may take piece i + 2 */
-        progress.bump();
-        if (count == 0) continue;
-        /* total <= off (a position has at most one pair); the pairs that stay (positions below `mine`) are at most `mine`, so they lie among the
+    const PFAC_status_t st = stagedPairs(c, h_inputString, cut, /* ordered */ true, [](Staged) {}, [&](const Piece &p, size_t count, const int *d_ids, const int *d_pos) {
+        if (count == 0) return PFAC_STATUS_SUCCESS;
+        /* total <= p.off (a position has at most one pair); the pairs that stay (positions below p.mine) are at most p.mine, so they lie among the
          * first size - total of the list: the caller's arrays (size entries) hold what is copied */
-        const size_t room = size - total, copied = (size_t)count < room ? (size_t)count : room;
-        if (hipMemcpy(h_pos + total, d_pos, copied * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
+        const size_t room = size - total, copied = count < room ? count : room;
+        if (hipMemcpy(h_pos + total, d_pos, copied * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
         size_t keep = copied;                                  /* positions ascend: those in the overlap are a suffix */
-        while (keep > 0 && (size_t)h_pos[total + keep - 1] >= mine) keep--;
-        if (keep && hipMemcpy(h_matched_result + total, d_ids, keep * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
-        if (off + posBase) for (size_t k = 0; k < keep; k++) h_pos[total + k] += (int)(off + posBase);
+        while (keep > 0 && (size_t)h_pos[total + keep - 1] >= p.mine) keep--;
+        if (keep && hipMemcpy(h_matched_result + total, d_ids, keep * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+        if (p.off + posBase) for (size_t k = 0; k < keep; k++) h_pos[total + k] += (int)(p.off + posBase);
         total += keep;
-    }
-    if (!ok && st == PFAC_STATUS_SUCCESS) st = PFAC_STATUS_INTERNAL_ERROR;
-    stopUploads.store(true);
-    progress.bump();
-    if (uploader.joinable()) uploader.join();
-    const bool drained = hipStreamSynchronize(up) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
-    if (!drained && st == PFAC_STATUS_SUCCESS) st = PFAC_STATUS_INTERNAL_ERROR;
+        return PFAC_STATUS_SUCCESS;
+    });
     if (st == PFAC_STATUS_SUCCESS) *h_num_matched = (int)total;
     return st;
 }

@@ -1,37 +1,57 @@
 /*
  * multi_gpu.cpp -- PFACX_matchFromHostMultiGPU (include/pfac_ext.h): one call shards a host stream over several GPUs of the node.
  */
-#include <dlfcn.h>
-#include <pthread.h>
-#include <sched.h>
-#include <sys/syscall.h>
-#include <unistd.h>
 #include <hip/hip_runtime_api.h>
 
-#if defined(__SSE2__)
-#include <emmintrin.h>
-#endif
-
-#include <atomic>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <memory>
 #include <new>
-#include <system_error>
 #include <thread>
 #include <vector>
 
 #include "pfac_host.h"
+#include "piece_pipeline.h"
 
 using namespace pfac_internal;
 
 namespace {
 
+/* the slices of a stream of `size` bytes for `workers` workers: worker i gets [bound[i], bound[i + 1]), boundaries rounded down to the 1 KiB tile and
+ * never decreasing (pfac_amd/sharding.py plan_slices is the Python mirror) */
+std::vector<size_t> sliceBounds(size_t size, size_t workers)
+{
+    std::vector<size_t> bound(workers + 1, 0);
+    for (size_t i = 1; i < workers; i++) {
+        const size_t b = (size * i / workers) / 1024 * 1024;
+        bound[i] = b > bound[i - 1] ? b : bound[i - 1];
+    }
+    bound[workers] = size;
+    return bound;
+}
+
+/* work(i) -> status for i = 0 .. workers - 1, each on a thread of its own (worker 0 on the caller's); all are joined, the first status that is not
+ * SUCCESS comes back; ALLOC_FAILED, with nothing run on the caller's thread, if a thread could not be started */
+template <class Work>
+PFAC_status_t runWorkers(size_t workers, Work work)
+{
+    std::vector<PFAC_status_t> status(workers, PFAC_STATUS_SUCCESS);
+    auto run = [&](size_t i) { status[i] = work(i); };
+    std::vector<std::thread> threads;
+    try {
+        for (size_t i = 1; i < workers; i++) threads.emplace_back(run, i);
+    } catch (...) {
+        for (auto &t : threads) t.join();
+        return PFAC_STATUS_ALLOC_FAILED;
+    }
+    run(0);
+    for (auto &t : threads) t.join();
+    for (PFAC_status_t st : status)
+        if (st != PFAC_STATUS_SUCCESS) return st;
+    return PFAC_STATUS_SUCCESS;
+}
+
 /* The frame of both multi-GPU calls: one worker thread per listed device -- hipSetDevice, a per-device handle with this handle's pattern set and
- * modes (kept in the handle for the next call), a contiguous slice [bound[i], bound[i + 1]) of the stream (boundaries rounded to the 1 KiB tile:
- * pfac_amd/sharding.py plan_slices is the Python mirror) -- and `call(worker's handle, i, lo, hi)` on it, the worker's lock held. */
+ * modes (kept in the handle for the next call), a contiguous slice [bound[i], bound[i + 1]) of the stream (sliceBounds) -- and
+ * `call(worker's handle, i, lo, hi)` on it, the worker's lock held. */
 template <class Call>
 PFAC_status_t onDevices(PFAC_handle_t handle, size_t size, int numDevices, const int *devices, std::vector<size_t> &bound, Call call)
 {
@@ -52,16 +72,10 @@ PFAC_status_t onDevices(PFAC_handle_t handle, size_t size, int numDevices, const
     const size_t workers = devs.size();
     /* the i-th worker's handle: bound to devs[i]; a device listed twice gets two handles (two streams of work) */
     while (c->children.size() < workers) c->children.emplace_back(-1, nullptr);
-    std::vector<PFAC_status_t> status(workers, PFAC_STATUS_SUCCESS);
-    bound.assign(workers + 1, 0);
-    for (size_t i = 1; i < workers; i++) {
-        size_t b = (size * i / workers) / 1024 * 1024;
-        bound[i] = b > bound[i - 1] ? b : bound[i - 1];
-    }
-    bound[workers] = size;
-    auto work = [&](size_t i) {
-        if (bound[i + 1] == bound[i]) return;
-        if (hipSetDevice(devs[i]) != hipSuccess) { status[i] = PFAC_STATUS_INTERNAL_ERROR; return; }
+    bound = sliceBounds(size, workers);
+    auto work = [&](size_t i) -> PFAC_status_t {
+        if (bound[i + 1] == bound[i]) return PFAC_STATUS_SUCCESS;
+        if (hipSetDevice(devs[i]) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
         auto &child = c->children[i];
         if (child.second && child.first != devs[i]) { (void)PFAC_destroy(child.second); child.second = nullptr; }
         if (!child.second) {
@@ -73,39 +87,29 @@ PFAC_status_t onDevices(PFAC_handle_t handle, size_t size, int numDevices, const
             if (st == PFAC_STATUS_SUCCESS)
                 st = PFACX_readPatternFromMemoryEx(h, reinterpret_cast<const char *>(c->fa.file.data()), c->fa.file.size(),   /* (folded already, */
                                                    c->caseInsensitive ? PFACX_READ_NOCASE : 0u);                               /* the input is not) */
-            if (st != PFAC_STATUS_SUCCESS) { if (h) (void)PFAC_destroy(h); status[i] = st; return; }
+            if (st != PFAC_STATUS_SUCCESS) { if (h) (void)PFAC_destroy(h); return st; }
             child = {devs[i], h};
         }
         PFAC_context *w = child.second;
         /* a child created by an earlier call: the parent's modes may have changed since */
         if (w->perfMode != c->perfMode) {
             const PFAC_status_t st = PFAC_setPerfMode(w, (PFAC_perfMode_t)c->perfMode);
-            if (st != PFAC_STATUS_SUCCESS) { status[i] = st; return; }
+            if (st != PFAC_STATUS_SUCCESS) return st;
         }
         if (w->kernelVariant != c->kernelVariant) {
             const PFAC_status_t st = PFACX_setKernelVariant(w, c->kernelVariant);
-            if (st != PFAC_STATUS_SUCCESS) { status[i] = st; return; }
+            if (st != PFAC_STATUS_SUCCESS) return st;
         }
         std::lock_guard<std::mutex> g(w->lock);
         w->textureMode = c->textureMode;
         w->walker = c->walker;                                     /* PFACX_setWalker on the parent reaches the workers */
-        status[i] = call(w, i, bound[i], bound[i + 1]);
+        return call(w, i, bound[i], bound[i + 1]);
     };
     int callerDevice = 0;
     (void)hipGetDevice(&callerDevice);
-    std::vector<std::thread> threads;
-    try {
-        for (size_t i = 1; i < workers; i++) threads.emplace_back(work, i);
-    } catch (...) {
-        for (auto &t : threads) t.join();
-        return PFAC_STATUS_ALLOC_FAILED;
-    }
-    work(0);
-    for (auto &t : threads) t.join();
+    const PFAC_status_t st = runWorkers(workers, work);
     (void)hipSetDevice(callerDevice);
-    for (PFAC_status_t st : status)
-        if (st != PFAC_STATUS_SUCCESS) return st;
-    return PFAC_STATUS_SUCCESS;
+    return st;
 }
 
 /* A handle on a CPU platform (PFAC_setPlatform, or PFACX_createHostOnly) has no devices to shard over; the two calls then run their `numDevices`
@@ -122,35 +126,18 @@ PFAC_status_t onCpuWorkers(PFAC_handle_t handle, const char *in, size_t size, in
     if (st != PFAC_STATUS_SUCCESS) return st;
     const size_t workers = numDevices > 0 ? (size_t)numDevices : 1;
     const size_t overlap = (size_t)c->fa.maxPatternLen;
-    bound.assign(workers + 1, 0);
-    for (size_t i = 1; i < workers; i++) {
-        size_t b = (size * i / workers) / 1024 * 1024;
-        bound[i] = b > bound[i - 1] ? b : bound[i - 1];
-    }
-    bound[workers] = size;
-    std::vector<PFAC_status_t> status(workers, PFAC_STATUS_SUCCESS);
-    auto work = [&](size_t i) {
+    bound = sliceBounds(size, workers);
+    return runWorkers(workers, [&](size_t i) -> PFAC_status_t {
         const size_t lo = bound[i], hi = bound[i + 1];
-        if (hi == lo) return;
-        const size_t scanned = size - lo < hi - lo + overlap ? size - lo : hi - lo + overlap;
+        if (hi == lo) return PFAC_STATUS_SUCCESS;
+        const size_t scanned = PieceCut(hi - lo, size - lo, hi - lo, overlap).at(0).scanned;     /* the slice as one piece: with its read-ahead */
         try {
             std::vector<int> res(scanned);
-            status[i] = matchHostOnCpuPlatformPrepared(c, in + lo, scanned, res.data());
-            if (status[i] == PFAC_STATUS_SUCCESS) take(i, lo, hi, res.data());
-        } catch (const std::bad_alloc &) { status[i] = PFAC_STATUS_ALLOC_FAILED; }
-    };
-    std::vector<std::thread> threads;
-    try {
-        for (size_t i = 1; i < workers; i++) threads.emplace_back(work, i);
-    } catch (...) {
-        for (auto &t : threads) t.join();
-        return PFAC_STATUS_ALLOC_FAILED;
-    }
-    work(0);
-    for (auto &t : threads) t.join();
-    for (PFAC_status_t s : status)
-        if (s != PFAC_STATUS_SUCCESS) return s;
-    return PFAC_STATUS_SUCCESS;
+            const PFAC_status_t matched = matchHostOnCpuPlatformPrepared(c, in + lo, scanned, res.data());
+            if (matched == PFAC_STATUS_SUCCESS) take(i, lo, hi, res.data());
+            return matched;
+        } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
+    });
 }
 
 } // namespace

@@ -586,7 +586,7 @@ PFAC_status_t PFAC_matchFromDeviceReduce(PFAC_handle_t handle, char *d_inputStri
     DeviceScan scan;
     const PFAC_status_t st = beginDeviceScan(handle, d_inputString, size, &scan);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    return reduceOnDevice(handle, scan.d_scan, size, d_matched_result, d_pos, h_num_matched);
+    return reduceOnDevice(handle, scan.d_scan, size, d_matched_result, d_pos, true, h_num_matched);
 }
 
 PFAC_status_t PFAC_matchFromHostReduce(PFAC_handle_t handle, char *h_inputString, size_t size,

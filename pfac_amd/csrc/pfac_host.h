@@ -81,11 +81,17 @@ inline PFAC_status_t beginDeviceScan(PFAC_context *c, char *d_input, size_t size
     s->hashed = c->perfMode == PFAC_TIME_DRIVEN ? 0 : 1;
     return foldDeviceInput(c, d_input, size, &s->d_scan);
 }
-/* the compacted-output scan of the handle's perf mode over n device bytes (the caller holds c->lock) */
-inline PFAC_status_t reduceOnDevice(PFAC_context *c, char *d_in, size_t n, int *d_ids, int *d_pos, int *h_count)
+/* the compacted-output scan of the handle's perf mode over n device bytes, its pairs in position order or -- the ordering launches not paid for --
+ * in any (the caller holds c->lock).  The one place on the host side that sets c->reduceUnordered (the module's: scan_passes.h compactedScan); the
+ * handle's own setting is put back */
+inline PFAC_status_t reduceOnDevice(PFAC_context *c, char *d_in, size_t n, int *d_ids, int *d_pos, bool ordered, int *h_count)
 {
     PFAC_reduce_kernel_protoType fn = c->perfMode == PFAC_TIME_DRIVEN ? c->reduce_kernel_ptr : c->reduce_inplace_kernel_ptr;
-    return fn(c, reinterpret_cast<int *>(d_in), (int)n, d_ids, d_pos, h_count, nullptr, nullptr);
+    const bool wasUnordered = c->reduceUnordered;
+    c->reduceUnordered = !ordered;
+    const PFAC_status_t st = fn(c, reinterpret_cast<int *>(d_in), (int)n, d_ids, d_pos, h_count, nullptr, nullptr);
+    c->reduceUnordered = wasUnordered;
+    return st;
 }
 /* the non-zero results of the first `owned` entries of a full result vector as (id, position + posShift) pairs; ids may be the vector
  * itself (pair z comes from an entry at or behind z).  Returns the number of pairs */

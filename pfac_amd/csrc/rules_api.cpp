@@ -239,7 +239,7 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
     st = beginDeviceScan(c, d_input, size, &scan);
     if (st != PFAC_STATUS_SUCCESS) return st;
     int count = 0;
-    st = reduceOnDevice(c, scan.d_scan, size, ids, pos, &count);          /* ordered: the fix-up and the segments' first pairs search the positions */
+    st = reduceOnDevice(c, scan.d_scan, size, ids, pos, true, &count);          /* ordered: the fix-up and the segments' first pairs search the positions */
     if (st == PFAC_STATUS_SUCCESS && d_offsets)
         st = c->batch_reduce_fixup_ptr(c, scan.d_scan, size, d_offsets, numSegments, ids, pos, &count, c->scratch.allSegFirst.get(), c->scratch.patternLen.get());
     if (st != PFAC_STATUS_SUCCESS) return st;

@@ -151,6 +151,86 @@ def test_match_from_host_reduce_pieces_equal_oracle(workdir):
         o.close()
 
 
+@pytest.fixture(scope="module")
+def whole_pieces(tmp_path_factory):
+    """What the three tests below share: a set with one 1-byte pattern (`~`, taken out of the text) next to 2 000 Snort-style ones, its file, and
+    64 MiB of text -- read-only: each test plants into a copy of the part it needs."""
+    pats = [b"~"] + wl.snort_patterns(2000)
+    pf = wl.write_pattern_file(str(tmp_path_factory.mktemp("wholepieces") / "whole.pat"), pats)
+    text = wl.http_stream(64 << 20, wl.http_message_pool(pats[1:], pool_size=256, embed_fraction=0.3)).copy()
+    text[text == ord("~")] = ord("-")
+    text.setflags(write=False)
+    return pf, max(pats, key=len), text
+
+
+def _plant(data, pattern, *starts):
+    for at in starts:
+        data[at:at + len(pattern)] = np.frombuffer(pattern, dtype=np.uint8)
+
+
+def test_match_from_host_two_whole_pieces_equal_match_from_device(whole_pieces):
+    """PFAC_matchFromHost on exactly 64 MiB: two whole 32 Mi-position pieces, so the last piece has no read-ahead behind it.  The longest pattern
+    ends exactly with the first piece and again with the last byte of the stream; the result is that of one PFAC_matchFromDevice call."""
+    pf, longest, text = whole_pieces
+    n, cut = 64 << 20, 32 << 20
+    data = text[:n].copy()
+    _plant(data, longest, cut - len(longest), n - len(longest))
+    h = make_handle(pf, api.PFAC_SPACE_DRIVEN, api.PFAC_TEXTURE_OFF)
+    try:
+        want = device_match(h, data)
+        got = np.full(n, -7, dtype=np.int32)
+        h.matchFromHost(data.ctypes.data, n, got.ctypes.data)
+        assert_same(got, want, "matchFromHost, two whole pieces")
+        assert want[cut - len(longest)] != 0 and want[n - len(longest)] != 0
+    finally:
+        h.destroy()
+
+
+def test_match_from_host_reduce_three_whole_pieces_equal_match_from_device(whole_pieces):
+    """PFAC_matchFromHostReduce on exactly 48 MiB: three whole 16 Mi-position pieces, so the third upload waits for the first scan and the last piece
+    has no read-ahead.  The longest pattern straddles both cuts and ends with the last byte; pairs and count are the non-zero entries of one
+    PFAC_matchFromDevice call."""
+    pf, longest, text = whole_pieces
+    n, piece = 48 << 20, 16 << 20
+    data = text[:n].copy()
+    starts = (piece - len(longest) // 2, 2 * piece - len(longest) // 2, n - len(longest))
+    _plant(data, longest, *starts)
+    h = make_handle(pf, api.PFAC_SPACE_DRIVEN, api.PFAC_TEXTURE_ON, api.PFACX_KERNEL_AUTO)
+    try:
+        want = device_match(h, data)
+        nz = np.flatnonzero(want)
+        assert all(want[at] != 0 for at in starts)
+        ids = np.full(n, -9, dtype=np.int32)
+        pos = np.full(n, -9, dtype=np.int32)
+        _, count = h.matchFromHostReduce(data.ctypes.data, n, ids.ctypes.data, pos.ctypes.data)
+        assert count == nz.size, (count, nz.size)
+        assert np.array_equal(pos[:count], nz) and np.array_equal(ids[:count], want[nz])
+    finally:
+        h.destroy()
+
+
+def test_count_from_host_through_three_reduce_pieces_equals_cpu_platform(whole_pieces):
+    """A consumer of the staged pairs: PFACX_countFromHost on 33 MiB + 1 (three 16 Mi-position reduce pieces, the last ragged) and on 32 MiB + 1 (the
+    last piece is ONE position, which matches the 1-byte pattern), the longest pattern across both cuts.  A handle on the GPU platform and a handle
+    with the same set on PFAC_PLATFORM_CPU_OMP must count the same: every pattern's count and the total."""
+    pf, longest, text = whole_pieces
+    piece = 16 << 20
+    gpu = make_handle(pf, api.PFAC_SPACE_DRIVEN, api.PFAC_TEXTURE_ON, api.PFACX_KERNEL_AUTO)
+    cpu = make_handle(pf, api.PFAC_SPACE_DRIVEN, api.PFAC_TEXTURE_ON, api.PFACX_KERNEL_AUTO)
+    try:
+        cpu.setPlatform(api.PFAC_PLATFORM_CPU_OMP)
+        for n in ((33 << 20) + 1, (32 << 20) + 1):
+            data = text[:n].copy()
+            _plant(data, longest, piece - len(longest) // 2, min(2 * piece - len(longest) // 2, n - 1 - len(longest)))   # across the cuts, or up to the second
+            data[n - 1] = ord("~")
+            got, got_total = gpu.count_host_array(data)
+            want, want_total = cpu.count_host_array(data)
+            assert got_total == want_total and want_total > 1000, (n, got_total, want_total)
+            assert np.array_equal(got, want), (n, np.flatnonzero(got != want)[:10])
+    finally:
+        gpu.destroy()
+        cpu.destroy()
+
 
 def test_two_host_threads_share_one_handle(workloads, oracle_results):
     """The reference serialises threads that share a handle with its texture mutex (PFAC.cpp:37-56).  Here two

@@ -121,6 +121,96 @@ def prefilter_model(h, data, veto=True):
     return level1, cand, walk
 
 
+LADDER_FIRST, LADDER_STEP, SKIP_FROM_DEPTH, SKIP_TAGS_MAX = 4, 2, 6, 8        # kLadderFirst, kLadderStep, kSkipFromDepth, kSkipTagsMax
+TAIL_MIN_BYTES, TAIL_MAX_BYTES = 6, 16                                       # kTailMinBytes, kTailMaxBytes
+
+
+class LadderNode:
+    """a node of the prefix ladder: the pattern prefix it stands for, its rolling hash, S (stop) or G, and the patterns below it"""
+    __slots__ = ("prefix", "depth", "hash", "stop", "thin_stop", "below")
+
+    def __init__(self, prefix, h, stop, thin_stop, below):
+        self.prefix, self.depth, self.hash, self.stop, self.thin_stop, self.below = prefix, len(prefix), h, stop, thin_stop, below
+
+
+def ladder_hash(prefix, salt):
+    """pfac::ladderStart / ladderRoll over a prefix of 4, 6, 8, ... bytes"""
+    h = ((int.from_bytes(prefix[:4], "little") * LAD_MUL0) & 0xFFFFFFFF) ^ salt
+    for d in range(4, len(prefix), 2):
+        h = ((h ^ int.from_bytes(prefix[d:d + 2], "little")) * LAD_MUL) & 0xFFFFFFFF
+    return h
+
+
+def tail_hash(h, rest):
+    """pfac::tailRoll from the ladder hash h over `rest` (a multiple of four bytes)"""
+    for i in range(0, len(rest), 4):
+        h = ((h ^ int.from_bytes(rest[i:i + 4], "little")) * LAD_MUL) & 0xFFFFFFFF
+    return h
+
+
+def ladder_nodes(patterns, thin, extend, last, salt):
+    """Every ladder node a candidate can reach through G nodes, from the PATTERN LIST alone (struct Filter in pfac_context.h states the
+    rules; no table of the library is read).  A node is a pattern prefix of 4, 6, ... bytes.  It is a stop if a pattern ends at its
+    depth or the next, if it lies at the last level, or if at most `thin` patterns lie below it and the `extend` extra levels behind
+    the first thin node of its path are used up; only the children of G nodes are nodes."""
+    pats = sorted(set(patterns))
+    whole = set(pats)
+    nodes = []
+    frontier = None                                        # G nodes of the level above: prefix -> extra levels left
+    depth = LADDER_FIRST
+    live = [p for p in pats if len(p) >= depth]
+    while live and (frontier is None or frontier):
+        groups = {}
+        for p in live:
+            if frontier is None or p[:depth - LADDER_STEP] in frontier:
+                groups.setdefault(p[:depth], []).append(p)
+        nxt = {}
+        for q, below in groups.items():
+            ext = extend if frontier is None else frontier[q[:depth - LADDER_STEP]]
+            ends_soon = q in whole or depth >= last or any(len(p) == depth + 1 for p in below)
+            is_thin = len(below) <= thin
+            stop = ends_soon or (is_thin and ext == 0)
+            nodes.append(LadderNode(q, ladder_hash(q, salt), stop, stop and not ends_soon, below))
+            if not stop:
+                nxt[q] = ext - 1 if is_thin else ext
+        frontier = nxt
+        depth += LADDER_STEP
+        live = [p for p in live if len(p) >= depth]
+    return nodes
+
+
+def skip_tag_paths(nodes):
+    """the hashes of the depth-6 G nodes that may carry a skip tag: no other ladder node has the hash, and ONE path leads from the node
+    down to LADDER_LAST -- every pattern below it has at least LADDER_LAST bytes and they share them -- on which the ladder's own nodes
+    (depths 8 .. 18) are G nodes"""
+    count = {}
+    for nd in nodes:
+        count[nd.hash] = count.get(nd.hash, 0) + 1
+    go_on = {nd.prefix for nd in nodes if not nd.stop}
+    out = []
+    for nd in nodes:
+        if nd.depth != SKIP_FROM_DEPTH or nd.stop or count[nd.hash] != 1:
+            continue
+        first = nd.below[0]
+        single = all(len(p) >= LADDER_LAST and p[:LADDER_LAST] == first[:LADDER_LAST] for p in nd.below)
+        if single and all(first[:d] in go_on for d in range(SKIP_FROM_DEPTH, LADDER_LAST, LADDER_STEP)):
+            out.append(nd.hash)
+    return out
+
+
+def tail_entries(h):
+    """[(tag, rolled hash, bytes compared, depth of the first of them, bits of the rolled hash that are stored)] of the handle's tail
+    table, whichever form it has (PFACX_TABLE_FILTER_TAIL: three words a slot; _TAIL_GLOBAL: buckets of two 8-byte entries)"""
+    out = []
+    t = h.table(api.PFACX_TABLE_FILTER_TAIL).reshape(-1, 3)
+    for tag, want, inf in t[t[:, 2] != 0].tolist():
+        out.append((tag, want, inf & 0xFF, inf >> 8, 0xFFFFFFFF))
+    g = h.table(api.PFACX_TABLE_FILTER_TAIL_GLOBAL).reshape(-1, 2)
+    for tag, word in g[(g[:, 1] & 0x7F8) != 0].tolist():
+        out.append((tag, word & 0xFFFFF800, ((word & 7) + 1) * 4, (word >> 3) & 0xFF, 0xFFFFF800))
+    return out
+
+
 def reduce_filter_model(h, data):
     """The compacted-output kernel's filter (pfac_context.h: gram1, prefix4): (level-1 hits, positions that are walked)."""
     info = h.info()

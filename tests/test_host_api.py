@@ -17,6 +17,7 @@ import pytest
 
 from oracle import binding as ob
 from pfac_amd import api
+from tests.chain_model import ChainWalker
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -588,67 +589,12 @@ def test_chained_table_walk_equals_oracle(workloads, oracle_results, name, perf)
     h = api.PFAC.createHostOnly()
     h.setPerfMode(api.PFAC_TIME_DRIVEN if perf == "dense" else api.PFAC_SPACE_DRIVEN)
     h.readPatternFromFile(w.pattern_file)
-    slots = h.table(api.PFACX_TABLE_CHAIN).reshape(-1, 4)
-    info = h.info()
+    walker = ChainWalker(h)
     h.destroy()
-    J = info.chainJumpLog2
-    assert 10 <= J <= 20 and info.chainSlots == len(slots) and len(slots) % 2 == 0
-    ext_delta = len(slots) // 2                    # N slot headers, then N extension units: the unit of slot i at N + i
-    jump_base = ext_delta - (2 << J)               # the jump table; behind it the LONG jump table (same hash, chains of up to 23 bytes)
-    root_row = jump_base - 256
-    EMPTY, FINAL, WIDE = 1 << 14, 1 << 13, 1 << 15         # pfac_context.h: kSlotEmpty, kSlotFinal, kSlotWide; a leaf has k == 0
-    long_steps = 0
+    slots, J, jump_base = walker.slots, walker.J, walker.jump_base
 
     def walk_all(stream, expect, long_jump=False):
-        nonlocal data
-        n = len(stream)
-        data = bytes(stream) + bytes(80)
-        limit = max(n - info.maxPatternLen, 0)    # beyond it a walk would read the padding
-        used_jump = fell_back = 0
-        for i in range(limit):
-            x = int.from_bytes(data[i:i + 4], "little")
-            match = 0
-            ok, leaf, ident, row, ks, used = step(jump_base + (long_jump << J) + (((x * 0x9E3779B1) & 0xFFFFFFFF) >> (32 - J)), long_jump, data[i], i + 1)
-            if ok:
-                used_jump += 1
-            else:                                  # restart in the initial state's bucket (k = 128, S = 256: the byte itself)
-                fell_back += 1
-                ok, leaf, ident, row, ks, used = step(root_row + data[i], False, data[i], i + 1)
-            depth = 0
-            while ok:
-                if ident:
-                    match = ident
-                depth += used
-                if leaf:
-                    break
-                b0 = data[i + depth]
-                r = ((((ks >> 16) & 0xFF) * b0) >> 7) & (ks >> 24)        # pfac_context.h: chainSlotOf
-                ok, leaf, ident, row, ks, used = step(row + r, bool(ks & WIDE), b0, i + depth + 1)   # only the slots of WIDE buckets may be long
-            assert match == int(expect[i]), (name, perf, i, match, int(expect[i]))
-        return used_jump, fell_back
-
-    data = b""
-
-    def step(at, wide, b0, p):
-        """transition through the slot at index `at` (wide: the slot that led here says its bucket may hold long slots) on edge
-        byte b0 with the input behind it at p: (ok, leaf, match id or 0, end row, ks, bytes consumed)"""
-        nonlocal long_steps
-        slot = slots[at]
-        meta = int(slot[0])
-        ln = (meta >> 8) & 0x1F
-        chain = int(slot[2]).to_bytes(4, "little") + int(slot[3]).to_bytes(4, "little")
-        if ln > 7:                                 # only slots of wide buckets fold more than 7 bytes: 8 in the header, the rest in the unit
-            assert wide and ln <= 23
-            chain += b"".join(int(v).to_bytes(4, "little") for v in slots[at + ext_delta])
-        else:
-            assert not slots[at + ext_delta].any()     # the unit of a short slot is never written
-            long_steps += 1
-        ok = (meta & (EMPTY | 0xFF)) == b0 and chain[:ln] == data[p:p + ln]
-        leaf = (meta >> 16) & 0xFF == 0
-        ident = 0
-        if ok and meta & FINAL:
-            ident = int(slot[1]) if leaf else int(slot[3])
-        return ok, leaf, ident, int(slot[1]), meta, 1 + ln
+        return walker.walk_all(stream, expect, long_jump, what=(name, perf))
 
     used_jump, fell_back = walk_all(w.data[:30000], oracle_results[name])
     used_long, _ = walk_all(w.data[:30000], oracle_results[name], long_jump=True)     # the long jump table: same results (a slot that
@@ -656,7 +602,8 @@ def test_chained_table_walk_equals_oracle(workloads, oracle_results, name, perf)
     if name in ("c2", "c3"):
         assert used_jump > 0                       # the stream does contain 4-byte pattern prefixes
     if name == "c5":
-        assert long_steps > 0                      # the near-miss stream walks the long single-successor runs: wide buckets
+        assert walker.short_slot_steps > 0         # (what this test has always counted here: slots WITHOUT an extension unit)
+        assert walker.long_slots > 0               # the near-miss stream walks the long single-successor runs: wide buckets
     if name == "c2":
         # 1000 random prefixes in 8192 slots: some collide.  A pattern whose prefix lost its slot must be found
         # through the restart: a stream of exactly those patterns, against the oracle

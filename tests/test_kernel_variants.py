@@ -20,6 +20,7 @@ torch = pytest.importorskip("torch")
 
 from pfac_amd import api, sharding  # noqa: E402,F401
 from pfac_amd import workloads as wl  # noqa: E402,F401
+from tests.compiler_sets import longset_patterns  # noqa: E402
 from tests.gpu_helpers import (MODES, STAGE, VARIANTS, WALKERS, assert_same, device_match, digest_record, digests, make_handle,  # noqa: E402,F401
                                o_prefix, oracle_match, perf_asserts, run_bench, timed_match)
 
@@ -182,20 +183,7 @@ def longset(workdir):
     (chains of every length 0 .. 23 behind a branch), one 300-byte and one 700-byte pattern (several long slots in a row; deeper
     than the 128 bytes staged behind a chunk), patterns that are prefixes of patterns at depths 8, 9, 24, 25 (a final state with
     successors ends a slot early), a shared 24-byte prefix with 40 tails (BASELINE config 5's shape) and a few short ones."""
-    rng = np.random.Generator(np.random.PCG64(55))
-    low = np.arange(97, 123, dtype=np.uint8)
-    def word(n):
-        return low[rng.integers(0, low.size, n)].tobytes()
-    pats = set()
-    for n in range(9, 65):
-        pats.add(word(n))
-    p300, p700 = word(300), word(700)
-    pats.update([p300, p700, p300[:8], p300[:9], p300[:24], p300[:25], p700[:100], p700[:101] + b"X"])
-    prefix = word(24)
-    tails = [word(int(rng.integers(8, 41))) for _ in range(40)]
-    pats.update(prefix + t for t in tails)
-    pats.update([b"zq", b"q", b"zqzqzq"])
-    pats = sorted(pats)
+    pats, prefix, tails, p300, p700 = longset_patterns()            # (the recipe lives in tests/compiler_sets.py, which adds to it)
     pf = wl.write_pattern_file(os.path.join(workdir, "longset.pat"), pats)
     return pf, pats, prefix, tails, p300, p700
 

@@ -364,9 +364,7 @@ static void buildFilterImpl(const Automaton &fa, Filter &f, bool allowDeep)
     f.log2Bits = sizeLog2(depth3, 13, 18);
     f.log2BitsF3 = sizeLog2(len3, 10, 13);
     f.log2BitsLad = 19;
-    auto total = [&]() {
-        return kGram3LdsBytes + ((size_t(1) << f.log2BitsLad) + (size_t(1) << f.log2BitsF3)) / 8 + (anyShort ? 65536 / 8 : 0);   /* level 1 has its 32 KiB whatever its size */
-    };
+    auto total = [&]() { return filterBitmapLdsBytes(f.log2BitsLad, f.log2BitsF3, anyShort); };
     while (total() > kFilterLdsBudget) {
         if (f.log2BitsLad > 17) f.log2BitsLad--;
         else if (f.log2Bits > 16) f.log2Bits--;
@@ -585,7 +583,7 @@ void buildFilter(const Automaton &fa, Filter &f)
      * bitmaps leave (scan_filter.hip: vetoLdsBytes; VETO = 1).  A set whose bitmaps leave none, or with more thin stops than that table
      * holds -- Snort-scale --, keeps the table in device memory (VETO = 2: one gathered load per stopped candidate, round 6); round 5 gave
      * such a set the ladder of rounds 3 and 4 and no veto at all.  A set has one form or the other. */
-    const size_t lds = kGram3LdsBytes + ((size_t(1) << f.log2BitsLad) + (size_t(1) << f.log2BitsF3)) / 8 + (f.hasShort ? 65536 / 8 : 0) + f.tail.size() * sizeof(uint32_t);
+    const size_t lds = filterBitmapLdsBytes(f.log2BitsLad, f.log2BitsF3, f.hasShort) + f.tail.size() * sizeof(uint32_t);
     const bool inLds = !f.tail.empty() && lds <= kFilterLdsBudget && f.tailEntries * 2 >= f.tailCandidates;      /* (a table that holds less than half of the thin stops is too small: a set of tens of thousands of patterns) */
 #ifdef PFAC_NO_GLOBAL_TAIL
     if ((f.ladderLast > kLadderLast || !f.tail.empty()) && !inLds) { buildFilterImpl(fa, f, /*allowDeep=*/false); return; }

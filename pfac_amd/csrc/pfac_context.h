@@ -101,9 +101,6 @@ struct ChainSlot {
     unsigned char chain[8];                   /* chain bytes 0..7, zero padded; if the end state is final and
                                                  has successors: <= 3 chain bytes, pattern ID in [4..7]  */
 };
-constexpr size_t kGram3LdsBytes = 32 * 1024;     /* LDS set aside for the level-1 bitmap (2^18 bits at most): the ladder behind it sits at a compile-time address */
-constexpr size_t kFilterLdsBudget = 97 * 1024;   /* LDS bytes the prefilter bitmaps may take together (pattern_compiler.cpp); the rest of the
-                                                    CU's 160 KiB is the scanning waves' queues and stages (scan_*.hip checks the sum) */
 constexpr uint32_t kSlotLenShift = 8, kSlotLenMask = 0x1Fu;   /* chain length: bits 8..12 */
 constexpr uint32_t kSlotFinal = 1u << 13;     /* the end state is a final state                         */
 constexpr uint32_t kSlotEmpty = 1u << 14;     /* no transition in this slot                             */
@@ -207,6 +204,22 @@ struct Filter {
     std::vector<uint32_t> prefix4;            /* 2^kPrefix4Log2 bits */
 };
 constexpr int kGram1Log2 = 19, kPrefix4Log2 = 17;
+constexpr size_t kGram3LdsBytes = 32 * 1024;     /* LDS set aside for the level-1 bitmap (2^18 bits at most): the ladder behind it sits at a compile-time address */
+constexpr size_t kFilterLdsBudget = 97 * 1024;   /* LDS bytes the prefilter bitmaps may take together (pattern_compiler.cpp); the rest of the
+                                                    CU's 160 KiB is the scanning waves' queues and stages (scan_*.hip checks the sum) */
+constexpr size_t kShortLdsBytes = 65536 / 8;      /* the bitmap of the one- and two-byte patterns (Filter::shortBits), in LDS only when the set has such patterns */
+/* LDS bytes of the full-result kernel's prefilter bitmaps: level 1 (its 32 KiB whatever its size), the ladder, final3 and the short bitmap.  What the pattern
+ * compiler holds against kFilterLdsBudget, what the loader checks, and where the filter kernel's buffers begin (scan_filter.hip: FilterLds) */
+constexpr size_t filterBitmapLdsBytes(int log2BitsLad, int log2BitsF3, bool hasShort)
+{
+    return kGram3LdsBytes + ((size_t(1) << log2BitsLad) + (size_t(1) << log2BitsF3)) / 8 + (hasShort ? kShortLdsBytes : 0);
+}
+/* ... of the compacted-output kernel's: [0, 16 KiB) prefix4, [16, 80 KiB) gram1, then final3 and the short bitmap */
+constexpr uint32_t kPrefix4LdsBytes = (1u << kPrefix4Log2) / 8, kGram1LdsOffset = kPrefix4LdsBytes, kGram1LdsBytes = (1u << kGram1Log2) / 8;
+constexpr size_t reduceBitmapLdsBytes(int log2BitsF3, bool hasShort)
+{
+    return (size_t)kGram1LdsOffset + kGram1LdsBytes + (size_t(1) << log2BitsF3) / 8 + (hasShort ? kShortLdsBytes : 0);
+}
 constexpr int kSkipTagsMax = 8, kSkipFromDepth = 6;
 constexpr int kDenseFastMaxStates = 8192;      /* 8 MiB of int[S][256]: stays in L2 */
 

@@ -121,8 +121,9 @@ constexpr int kBlockThreads = PFAC_BLOCK_THREADS;
 constexpr int kWavesPerBlock = kBlockThreads / 64;
 constexpr int kTileBytes = 1024;              /* input bytes one wave-wide 16 B/lane load covers */
 constexpr uint32_t kLadderLdsOffset = (uint32_t)pfac::kGram3LdsBytes;  /* LDS: [0, 32 KiB) the level-1 bitmap (at most 2^18 bits), then the prefix ladder */
-/* ... of the compacted-output kernel: [0, 16 KiB) the 4-byte prefixes, [16, 80 KiB) its one-bit level-1 bitmap (pfac_context.h: gram1, prefix4) */
-constexpr uint32_t kPrefix4LdsBytes = (1u << pfac::kPrefix4Log2) / 8, kGram1LdsOffset = kPrefix4LdsBytes, kGram1LdsBytes = (1u << pfac::kGram1Log2) / 8;
+using pfac::kPrefix4LdsBytes;                 /* ... of the compacted-output kernel: prefix4, then gram1 (pfac_context.h: reduceBitmapLdsBytes) */
+using pfac::kGram1LdsOffset;
+using pfac::kGram1LdsBytes;
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 using pfacmod::u32x4;

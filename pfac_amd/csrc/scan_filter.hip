@@ -59,8 +59,6 @@ static_assert(kMergeMin <= 64 && kMergeMin < kListCap, "left-over candidates are
 #endif
 constexpr bool kStagedPatch = PFAC_PATCH_STAGED != 0;
 constexpr uint32_t kReduceCap = 16;           /* (position, id) pairs staged per wave in the REDUCE variant (a ballot with more goes out directly) */
-constexpr int kReduceScanners = kWavesPerBlock;       /* ... and no writer waves: every wave scans, with half the walk queue each (LDS) */
-constexpr uint32_t kReduceQueueCap = kQueueCap;
 /* In-order hand-out of the input: -1 = the input is cut into kWorkParts contiguous parts, one
  * counter each; G >= 0 = one moving front: granules of 2^G pieces are dealt round-robin to the parts, so
  * all parts work inside one window of parts << G pieces that sweeps the input once. */
@@ -102,6 +100,46 @@ struct Control {                                         /* LDS, one per block *
 };
 constexpr int kControlWords = (sizeof(Control) / 4 + 3) / 4 * 4;
 
+/* The block's LDS (the CU's whole 160 KiB), described once for the kernel's pointers and the launcher's byte counts:
+ *   [prefilter bitmaps][control block][the regions below, in this order, each kScanners times its words][hot slots of the chained table | tail table]
+ * The last one is not part of the description: it begins at bytes(), and the launch says how long it is (kStageWalk: what is left of the CU's LDS,
+ * launchFilter; VETO = 1: vetoLdsBytes). */
+template <bool REDUCE, bool STAGE, int VETO = 0>
+struct FilterLds {
+    /* full-result kernel: walks read their input from the wave's two staged chunks (StageLane), a queue entry is {buffer, offset};
+     * compacted-output kernel (16 scanning waves, no LDS to spare): the input travels with the entry and lives in registers */
+    static constexpr bool kStageWalk = !REDUCE && STAGE;
+    static constexpr int kWriters = REDUCE ? 0 : PFAC_WRITERS;             /* the compacted-output variant has no zeros to write: every wave scans */
+    static constexpr int kScanners = kWavesPerBlock - kWriters;
+    static constexpr int kStageBufWords = kStageWalk ? (int)(kWalkStageBytes / 4) : kStageWords;     /* words of one stage buffer */
+    static constexpr int kStageBufs = kStageWalk ? 2 : 1;                  /* kStageWalk: the chunk being filtered and the chunk before it */
+    enum Region { kQueue, kQueueB, kQueueC, kStage, kList, kPairs, kDense, kTrailing };
+    static constexpr uint32_t kWaveWords[kTrailing] = {                    /* 32-bit words per scanning wave */
+        kQueueCap * (kStageWalk ? 1 : 4),                /* queue: position + input bytes 0..11 (kStageWalk: an entry is one word) */
+        kStageWalk ? 0 : kQueueCap * 2,                  /* queueB: input bytes 12..19 */
+        (REDUCE || kStageWalk) ? 0 : kQueueCap * 4,      /* queueC: input bytes 20..35, register-window walkers of a full-result build (VETO = 2 has 20-byte
+                                                            entries and keeps the room: its list lies there) */
+        (uint32_t)(kStageBufWords * kStageBufs),         /* stage: the chunk being filtered + the bytes behind it */
+        kListCap / 2,                                    /* list: 16-bit codes of the chunk's level-1 hits */
+        (REDUCE || kStagedPatch) ? 2 * kReduceCap : 0,   /* pairs: staging of (position, id) */
+        REDUCE ? 0 : kDenseStage,                        /* dense: staging of dense chunk numbers (full-result kernel) */
+    };
+    /* where region r begins, in words behind the bitmaps */
+    static constexpr uint32_t offsetWords(int r)
+    {
+        uint32_t w = kControlWords;
+        for (int i = 0; i < r; i++) w += kScanners * kWaveWords[i];
+        return w;
+    }
+    template <int R> static constexpr uint32_t kOffsetWords = offsetWords(R);       /* (a constant of the kernel's, not a call it has to fold) */
+    static constexpr size_t kBufferBytes = 4 * (size_t)offsetWords(kTrailing);
+    /* ... and where the described part ends, in bytes from the start of LDS */
+    static constexpr size_t bytes(int log2BitsLad, int log2BitsF3, bool hasShort)
+    {
+        return (REDUCE ? pfac::reduceBitmapLdsBytes(log2BitsF3, hasShort) : pfac::filterBitmapLdsBytes(log2BitsLad, log2BitsF3, hasShort)) + kBufferBytes;
+    }
+};
+
 __device__ __forceinline__ uint32_t ldsLoad(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void ldsStore(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
@@ -137,9 +175,8 @@ void pfac_scan_filter(ScanArgs a)
     using WCtx = ChainCtx<TEX>;
     constexpr uint32_t kEntry = (REDUCE || (!STAGE && VETO == 2)) ? kEntryBytes : kEntryBytesFull;      /* (VETO = 2: see kVetoG below) */
     constexpr bool kWideEntry = kEntry > kEntryBytes;                                                    /* entries carry bytes 20..35 too (queueC) */
-    /* full-result kernel: walks read their input from the wave's two staged chunks (StageLane), a queue entry is {buffer, offset};
-     * compacted-output kernel (16 scanning waves, no LDS to spare): the input travels with the entry and lives in registers */
-    constexpr bool kStageWalk = !REDUCE && STAGE;
+    using L = FilterLds<REDUCE, STAGE, VETO>;
+    constexpr bool kStageWalk = L::kStageWalk;
     /* VETO: the register-window walker behind a deeper prefilter -- ladder levels behind the 20th byte and the tail table (pfac::Filter): what a pattern
      * set of a few thousand patterns gets (its tables leave the LDS for it); a stop of the ladder is put to the table before it becomes a walk.  Its
      * walker fetches the extension unit of a wide bucket's slot with the header once its wave has met long slots (what is left to walk are patterns
@@ -164,8 +201,7 @@ void pfac_scan_filter(ScanArgs a)
     /* (VETO = 2 keeps six more registers alive across the loop's back edge -- a batch's answers from the tail table -- and leaves the unit speculation,
      * four registers, to VETO = 1: its walker fetches a long slot's unit on the spot, like the plain window walker) */
     using WLane = std::conditional_t<kStageWalk, StageLane<TEX>, ChainLane<TEX, kEntry, kVeto && VETO == 1>>;
-    constexpr int kStageWordsK = kStageWalk ? (int)(kWalkStageBytes / 4) : kStageWords;     /* words of one stage buffer */
-    constexpr int kStageBufs = kStageWalk ? 2 : 1;
+    constexpr int kStageWordsK = L::kStageBufWords, kStageBufs = L::kStageBufs;
     constexpr int kHaloDwords = kStageWalk ? (int)(kWalkHalo / 4) : 12;                      /* dwords behind the chunk that are staged with it */
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int words3 = 1 << (a.log2Bits - 5), wordsLad = 1 << (a.log2BitsLad - 5), wordsF3 = 1 << (a.log2BitsF3 - 5);
@@ -174,18 +210,16 @@ void pfac_scan_filter(ScanArgs a)
                                                                   ds_read takes it as its immediate offset */
     uint32_t *sFinal3 = REDUCE ? sGram3 + (kGram1LdsOffset + kGram1LdsBytes) / 4 : sLadder + wordsLad;
     uint32_t *sShort = sFinal3 + wordsF3;
-    constexpr int kWriters = REDUCE ? 0 : PFAC_WRITERS;             /* the compacted-output variant has no zeros to write */
-    constexpr int kScanners = REDUCE ? kReduceScanners : kWavesPerBlock - kWriters;
-    Control *ctl = reinterpret_cast<Control *>(sShort + (HAS_SHORT ? 2048 : 0));
-    uint32_t *sQueueAll = reinterpret_cast<uint32_t *>(ctl) + kControlWords;           /* 16-byte aligned */
-    constexpr uint32_t kQCap = REDUCE ? kReduceQueueCap : kQueueCap;
-    uint32_t *sQueueBAll = sQueueAll + kScanners * kQCap * (kStageWalk ? 1 : 4);   /* ... second part of the entries: input bytes 12..19 (kStageWalk: an entry is one word) */
-    uint32_t *sQueueCAll = sQueueBAll + (kStageWalk ? 0 : kScanners * kQCap * 2);  /* ... register-window walkers of a full-result build: input bytes 20..35 */
-    uint32_t *sStageAll = sQueueCAll + ((REDUCE || kStageWalk) ? 0 : kScanners * kQCap * 4);      /* (VETO = 2 keeps the room: its list lies there) */   /* per scanning wave: the chunk being filtered + the bytes behind it (kStageWalk: and the chunk before it) */
-    uint32_t *sListAll = sStageAll + kScanners * kStageWordsK * kStageBufs;   /* per scanning wave: 16-bit codes of the chunk's level-1 hits */
-    uint32_t *sReduceAll = sListAll + kScanners * (kListCap / 2);        /* REDUCE only: per-wave staging of (position, id) */
-    uint32_t *sDenseAll = sReduceAll + ((REDUCE || kStagedPatch) ? kScanners * 2 * kReduceCap : 0);   /* full-result kernel: per-wave staging of dense chunk numbers */
-    uint32_t *sHotAll = sDenseAll + (REDUCE ? 0 : kScanners * (int)kDenseStage);                         /* kStageWalk: the first a.hotSlots slot headers of the chained table */
+    constexpr int kWriters = L::kWriters, kScanners = L::kScanners;
+    constexpr uint32_t kQCap = kQueueCap;
+    /* the end of the bitmaps: smem + L::bytes(a.log2BitsLad, a.log2BitsF3, HAS_SHORT) - L::kBufferBytes, taken from the pointers that the bitmaps need anyway */
+    Control *ctl = reinterpret_cast<Control *>(sShort + (HAS_SHORT ? pfac::kShortLdsBytes / 4 : 0));
+    uint32_t *const sBuffers = reinterpret_cast<uint32_t *>(ctl);
+    uint32_t *sQueueAll = sBuffers + L::template kOffsetWords<L::kQueue>;       /* 16-byte aligned */
+    uint32_t *sQueueBAll = sBuffers + L::template kOffsetWords<L::kQueueB>, *sQueueCAll = sBuffers + L::template kOffsetWords<L::kQueueC>;
+    uint32_t *sStageAll = sBuffers + L::template kOffsetWords<L::kStage>, *sListAll = sBuffers + L::template kOffsetWords<L::kList>;
+    uint32_t *sReduceAll = sBuffers + L::template kOffsetWords<L::kPairs>, *sDenseAll = sBuffers + L::template kOffsetWords<L::kDense>;
+    uint32_t *sHotAll = sBuffers + L::template kOffsetWords<L::kTrailing>;      /* kStageWalk: the first a.hotSlots slot headers of the chained table; VETO = 1: the tail table */
 
     const int tid = threadIdx.x;
     if (__builtin_amdgcn_groupstaticsize() != 0) __builtin_trap();   /* the level-1 bitmap is addressed by number: sGram3 must sit at LDS address 0 */
@@ -203,7 +237,7 @@ void pfac_scan_filter(ScanArgs a)
             copy16(sLadder, a.ladder, wordsLad);
         }
         copy16(sFinal3, a.final3, wordsF3);
-        if (HAS_SHORT) copy16(sShort, a.shortBits, 2048);
+        if (HAS_SHORT) copy16(sShort, a.shortBits, (int)(pfac::kShortLdsBytes / 4));
         if constexpr (kStageWalk) copy16(sHotAll, a.chainSlots, (int)a.hotSlots * 4);
         if constexpr (kVeto && !kVetoG) { if (a.tail != nullptr) copy16(sHotAll, a.tail, 3 << a.log2Tail); }      /* the tail table: behind everything else */
         if (tid < kControlWords) reinterpret_cast<uint32_t *>(ctl)[tid] = (tid == (int)(offsetof(Control, endSpan) / 4)) ? kEnd : 0u;      /* endSpan = none yet */
@@ -1303,28 +1337,30 @@ void pfac_scan_filter(ScanArgs a)
 
 /* ------------------------------------------------------------- launching */
 
-/* the CU's 160 KiB: the prefilter bitmaps (<= kFilterLdsBudget, pattern_compiler.cpp) + control block + per scanning wave a
- * walk queue (24 B per entry), the staged chunk and the hit list (+ the pair staging of the compacted-output variant) */
-constexpr size_t kScannerLdsStage = kQueueCap * 4 + 2 * kWalkStageBytes, kScannerLdsWindow = kQueueCap * (4 + kEntryBytesFull) + kStageWords * 4;
-constexpr size_t kScannerLdsFull = (size_t)(kWavesPerBlock - PFAC_WRITERS) * ((kScannerLdsStage > kScannerLdsWindow ? kScannerLdsStage : kScannerLdsWindow) +
-                                                                              kListCap * 2 + (kStagedPatch ? kReduceCap * 8 : 0) + kDenseStage * 4);
-constexpr size_t kScannerLdsReduce = (size_t)kReduceScanners * (kReduceQueueCap * 24 + kStageWords * 4 + kListCap * 2 + kReduceCap * 8);
-static_assert(pfac::kFilterLdsBudget + kControlWords * 4 + kScannerLdsFull <= kLdsPerCu, "prefilter bitmaps + scanning waves' buffers must fit the CU's LDS");
-static_assert(kGram1LdsOffset + kGram1LdsBytes + 1024 /* final3 */ + 8192 /* 2-byte bitmap */ + kControlWords * 4 + kScannerLdsReduce <= kLdsPerCu,
-              "compacted-output kernel: gram1 + prefix4 + final3 + short bitmap + scanning waves' buffers must fit the CU's LDS");
+/* the CU's 160 KiB: the prefilter bitmaps (<= kFilterLdsBudget, pattern_compiler.cpp) and the scanning waves' buffers (FilterLds) */
+using LdsWindow = FilterLds<false, false>;
+using LdsStage = FilterLds<false, true>;
+using LdsReduce = FilterLds<true, false>;
+static_assert(pfac::kFilterLdsBudget + (LdsWindow::kBufferBytes > LdsStage::kBufferBytes ? LdsWindow::kBufferBytes : LdsStage::kBufferBytes) <= kLdsPerCu,
+              "prefilter bitmaps + scanning waves' buffers must fit the CU's LDS");
+static_assert(LdsReduce::bytes(0, 13, true) <= kLdsPerCu, "compacted-output kernel: gram1 + prefix4 + final3 + short bitmap + scanning waves' buffers must fit the CU's LDS");
+/* the pattern compiler keeps a tail table in LDS when bitmaps + table <= kFilterLdsBudget (pattern_compiler.cpp: buildFilter), so
+ * the launcher finds room for every such table behind the window walker's buffers: vetoLdsBytes() != 0 */
+static_assert(pfac::kFilterLdsBudget + FilterLds<false, false, 1>::kBufferBytes <= kLdsPerCu, "a tail table that the pattern compiler keeps in LDS must find room there");
+/* The totals in bytes with the constants as shipped, at the largest bitmaps, without and with the short bitmap (the pattern compiler never asks for the
+ * latter together with the largest ladder: the arithmetic is what is pinned).  A region that changes its size has to change a number here on purpose. */
+constexpr bool kShippedShape = kWavesPerBlock == 16 && PFAC_WRITERS == 3 && kQueueCap == 64 && kListCap == 128 && kRing == 32 && !kStagedPatch;
+template <class LDS> constexpr bool ldsTotalsAre(size_t plain, size_t withShort) { return !kShippedShape || (LDS::bytes(19, 13, false) == plain && LDS::bytes(19, 13, true) == withShort); }
+static_assert(ldsTotalsAre<LdsWindow>(163744, 171936), "window walker");
+static_assert(ldsTotalsAre<LdsStage>(163120, 171312), "stage walker, before its hot slots");
+static_assert(ldsTotalsAre<FilterLds<false, false, 2>>(163744, 171936), "VETO = 2: the window walker's, with the list in queueC's place");
+static_assert(ldsTotalsAre<LdsReduce>(147344, 155536), "compacted output");
 
 size_t filterLdsBytes(const PFAC_context *c, bool reduce, bool stage)
 {
-    size_t bytes = reduce ? (size_t)kGram1LdsOffset + kGram1LdsBytes + (size_t(1) << c->filter.log2BitsF3) / 8
-                          : kLadderLdsOffset + ((size_t(1) << c->filter.log2BitsLad) + (size_t(1) << c->filter.log2BitsF3)) / 8;   /* the level-1 bitmap has its 32 KiB whatever its size */
-    if (c->filter.hasShort) bytes += 65536 / 8;
-    const size_t scanners = reduce ? (size_t)kReduceScanners : (size_t)kWavesPerBlock - PFAC_WRITERS;
-    bytes += kControlWords * sizeof(uint32_t);
-    if (!reduce && stage) bytes += scanners * (kQueueCap * 4 + 2 * kWalkStageBytes + (kListCap / 2) * sizeof(uint32_t));
-    else bytes += scanners * ((reduce ? kReduceQueueCap * (4 + kEntryBytes) : kQueueCap * (4 + kEntryBytesFull)) + (kStageWords + kListCap / 2) * sizeof(uint32_t));
-    if (reduce || kStagedPatch) bytes += scanners * kReduceCap * 2 * sizeof(uint32_t);
-    if (!reduce) bytes += scanners * kDenseStage * sizeof(uint32_t);
-    return bytes;
+    const pfac::Filter &f = c->filter;
+    auto total = [&](auto lds) { return lds.bytes(f.log2BitsLad, f.log2BitsF3, f.hasShort); };
+    return reduce ? total(LdsReduce{}) : stage ? total(LdsStage{}) : total(LdsWindow{});
 }
 
 /* LDS of the tail table behind the buffers of a window-walker launch, or 0: none, or no room */
@@ -1375,7 +1411,7 @@ hipError_t launchFilter(const PFAC_context *c, const ScanArgs &a0)
         perCU = cache.perCU[dev];
     }
     const size_t numChunks = a.n / kChunkBytesHost;
-    constexpr size_t scanners = REDUCE ? (size_t)kReduceScanners : (size_t)kWavesPerBlock - PFAC_WRITERS;
+    constexpr size_t scanners = FilterLds<REDUCE, STAGE, VETO>::kScanners;
     size_t blocks = (numChunks + scanners - 1) / scanners;
     const size_t resident = (size_t)(c->multiProcessorCount > 0 ? c->multiProcessorCount : 256) * perCU;
     if (blocks > resident) blocks = resident;
@@ -1418,6 +1454,20 @@ hipError_t launchFilter(const PFAC_context *c, const ScanArgs &a0)
     return e;
 }
 
+#ifndef PFAC_QUICK
+#define PFAC_QUICK 0                            /* development builds (register / ISA inspection): 1 = the bench instances only -- full result, buffer-resource loads */
+#endif
+
+/* the instance of a walker for this handle: `tex` and the set's short patterns become template arguments here, once */
+template <bool REDUCE, bool STAGE, int VETO>
+hipError_t launchInstance(const PFAC_context *c, const ScanArgs &a, bool tex)
+{
+    const bool hasShort = c->filter.hasShort;
+    if (tex) return hasShort ? launchFilter<true, true, REDUCE, STAGE, VETO>(c, a) : launchFilter<true, false, REDUCE, STAGE, VETO>(c, a);
+    if constexpr (PFAC_QUICK) return hipErrorNotSupported;
+    else return hasShort ? launchFilter<false, true, REDUCE, STAGE, VETO>(c, a) : launchFilter<false, false, REDUCE, STAGE, VETO>(c, a);
+}
+
 /* the filter kernel walks the chained table in both perf modes; "texture" = buffer-resource loads */
 template <bool REDUCE>
 hipError_t launchChained(const PFAC_context *c, const ScanArgs &a, bool tex)
@@ -1443,28 +1493,13 @@ hipError_t launchChained(const PFAC_context *c, const ScanArgs &a, bool tex)
         }
         stage = c->walker == PFACX_WALKER_STAGE || (veto == 0 && c->walker == PFACX_WALKER_AUTO && nearMisses);
     }
-#ifdef PFAC_QUICK      /* development builds (register / ISA inspection): the bench instances only */
-    if (REDUCE || !tex) return hipErrorNotSupported;
-    if (stage) return c->filter.hasShort ? launchFilter<true, true, false, true>(c, a) : launchFilter<true, false, false, true>(c, a);
-    if (veto == 2) return c->filter.hasShort ? launchFilter<true, true, false, false, 2>(c, a) : launchFilter<true, false, false, false, 2>(c, a);
-    if (veto) return c->filter.hasShort ? launchFilter<true, true, false, false, 1>(c, a) : launchFilter<true, false, false, false, 1>(c, a);
-    return c->filter.hasShort ? launchFilter<true, true, false, false>(c, a) : launchFilter<true, false, false, false>(c, a);
-#else
-    if (!REDUCE && veto == 2) {
-        if (tex) return c->filter.hasShort ? launchFilter<true, true, false, false, 2>(c, a) : launchFilter<true, false, false, false, 2>(c, a);
-        return c->filter.hasShort ? launchFilter<false, true, false, false, 2>(c, a) : launchFilter<false, false, false, false, 2>(c, a);
+    if constexpr (PFAC_QUICK && REDUCE) return hipErrorNotSupported;
+    else {
+        if (veto == 2) return launchInstance<false, false, 2>(c, a, tex);
+        if (veto) return launchInstance<false, false, 1>(c, a, tex);
+        if (stage) return launchInstance<false, true, 0>(c, a, tex);
+        return launchInstance<REDUCE, false, 0>(c, a, tex);
     }
-    if (!REDUCE && veto) {
-        if (tex) return c->filter.hasShort ? launchFilter<true, true, false, false, 1>(c, a) : launchFilter<true, false, false, false, 1>(c, a);
-        return c->filter.hasShort ? launchFilter<false, true, false, false, 1>(c, a) : launchFilter<false, false, false, false, 1>(c, a);
-    }
-    if (!REDUCE && stage) {
-        if (tex) return c->filter.hasShort ? launchFilter<true, true, false, true>(c, a) : launchFilter<true, false, false, true>(c, a);
-        return c->filter.hasShort ? launchFilter<false, true, false, true>(c, a) : launchFilter<false, false, false, true>(c, a);
-    }
-    if (tex) return c->filter.hasShort ? launchFilter<true, true, REDUCE, false>(c, a) : launchFilter<true, false, REDUCE, false>(c, a);
-    return c->filter.hasShort ? launchFilter<false, true, REDUCE, false>(c, a) : launchFilter<false, false, REDUCE, false>(c, a);
-#endif
 }
 
 } // namespace

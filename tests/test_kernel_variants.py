@@ -455,3 +455,88 @@ def test_veto_kernel_with_the_tail_table_in_device_memory_and_short_patterns(big
         assert_same(device_match(h, data, in_offset=5, out_offset=3), want, "veto kernel, short patterns / input +5 B, result +3 ints")
     finally:
         h.destroy()
+
+
+LDS_PER_CU, STAGE_BUFFER_BYTES = 160 * 1024, 163120 - 97 * 1024      # scan_filter.hip: the stage walker's pinned total less the bitmaps it is pinned with
+
+
+@pytest.fixture(scope="module")
+def last_region(workdir):
+    """Two sets of 3000 patterns, each without and with a one-byte and a two-byte pattern: `long` (12 .. 24 bytes: a tail table in LDS, behind
+    every other region of the block) and `brief` (4 .. 9 bytes: no pattern has the six bytes behind its stop node that a tail entry needs, so
+    no table, and the plain window walker).  The input is three 2 KiB chunks + 333 bytes of filler.  In the first and in the last 64 bytes of
+    every chunk lie a match and, three bytes behind it, a near miss that only its LAST byte gives away: the ladder lets it through to its stop
+    node and the tail table has to veto it.  One more pair ends with the input, and the short patterns are sprinkled over all of it.  The
+    reference is the CPU platform on the same bytes."""
+    rng = np.random.Generator(np.random.PCG64(811))
+    alpha = np.frombuffer(b"abcdefghijklmnopqrstuvwxyz", dtype=np.uint8)
+    n = 3 * 2048 + 333
+    out = {}
+    for name, lo, hi in (("long", 12, 24), ("brief", 4, 9)):
+        pats = set()
+        while len(pats) < 3000:
+            pats.add(alpha[rng.integers(0, alpha.size, int(rng.integers(lo, hi + 1)))].tobytes())
+        pats = sorted(pats)
+        known = set(pats)
+        data = (rng.integers(0, 6, n, dtype=np.uint8) + 48).astype(np.uint8)           # '0'..'5': matches nothing
+        data[rng.integers(0, n, 40)] = ord("Q")
+        for at in rng.integers(0, n - 2, 40):
+            data[at:at + 2] = (ord("Z"), ord("Z"))
+        planted = []
+        for k, at in enumerate([2048 * c + off for c in range(3) for off in (1, 2048 - 62)] + [None]):
+            p, q = pats[(37 * k) % len(pats)], pats[(53 * k + 11) % len(pats)]
+            miss = next(m for m in (q[:-1] + bytes([c]) for c in alpha) if m not in known)
+            if at is None:                                                              # the last pair: the match ends with the input
+                at = n - len(p) - 3 - len(miss)
+                p, miss = miss, p
+                planted.append(at + len(p) + 3)
+            else:
+                assert len(p) + 3 + len(miss) <= 62
+                planted.append(at)
+            data[at:at + len(p)] = np.frombuffer(p, dtype=np.uint8)
+            data[at + len(p) + 3:at + len(p) + 3 + len(miss)] = np.frombuffer(miss, dtype=np.uint8)
+        for short in (False, True):
+            pf = wl.write_pattern_file(os.path.join(workdir, f"last_region_{name}{int(short)}.pat"), pats + ([b"Q", b"ZZ"] if short else []))
+            ref = api.PFAC.createHostOnly()
+            try:
+                ref.setPlatform(api.PFAC_PLATFORM_CPU)
+                ref.readPatternFromFile(pf)
+                want = np.full(n, -7, dtype=np.int32)
+                ref.matchFromHost(data.ctypes.data, n, want.ctypes.data)
+            finally:
+                ref.destroy()
+            assert np.all(want[planted] > 0) and np.all(want >= 0) and (np.count_nonzero(want) >= len(planted) + 40) == short
+            out[name, short] = (pf, data, want)
+    return out
+
+
+@pytest.mark.parametrize("short", [False, True], ids=["no-short", "short"])
+@pytest.mark.parametrize("perf,tex,mode_name", MODES)
+def test_last_lds_region_of_every_filter_instance(last_region, perf, tex, mode_name, short):
+    """The filter kernel's LDS is described once for kernel and launcher (scan_filter.hip: FilterLds).  A total that came out one region short
+    would leave the region that lies last outside the allocation, where reads return zeros and matches go missing without an error.  So: the
+    instances with that region in use -- the stage walker with hot slots, VETO = 1 with its tail table -- and the plain window walker and the
+    compacted output, whose last regions are the dense and the pair staging, on an input with matches and near misses at both ends of every
+    chunk, against the CPU platform."""
+    for set_name, walker, veto in (("brief", api.PFACX_WALKER_WINDOW, 0), ("long", api.PFACX_WALKER_WINDOW, 1), ("long", api.PFACX_WALKER_STAGE, 0)):
+        pf, data, want = last_region[set_name, short]
+        what = f"last region/{mode_name}/{set_name}/walker {walker}/short {short}"
+        h = make_handle(pf, perf, tex, api.PFACX_KERNEL_FILTER | (walker << 8))
+        try:
+            info = h.info()
+            assert bool(info.filterHasShort) == short and (info.filterTailEntries > 0) == (set_name == "long") and info.filterTailGlobalEntries == 0, what
+            bitmaps = 32768 + ((1 << info.filterLog2BitsLadder) + (1 << info.filterLog2BitsFinal3)) // 8 + (8192 if short else 0)
+            assert (LDS_PER_CU - bitmaps - STAGE_BUFFER_BYTES) // 16 >= 1024 and info.chainSlots >= 2048, what      # room for hot slots, and slots to put there
+            assert_same(device_match(h, data), want, what)
+            st = h.scanStats()
+            assert st["walker"] == walker and st["veto"] == veto, (what, st)
+            if set_name == "long" and walker == api.PFACX_WALKER_WINDOW:
+                n = data.size                                                           # ... and the compacted output of the same handle
+                d_in = torch.from_numpy(data).to("cuda:0")
+                d_ids = torch.full((n,), -3, dtype=torch.int32, device="cuda:0")
+                d_pos = torch.full((n,), -3, dtype=torch.int32, device="cuda:0")
+                _, count = h.matchFromDeviceReduce(d_in.data_ptr(), n, d_ids.data_ptr(), d_pos.data_ptr())
+                nz = np.flatnonzero(want)
+                assert count == nz.size and np.array_equal(d_pos[:count].cpu().numpy(), nz) and np.array_equal(d_ids[:count].cpu().numpy(), want[nz]), what
+        finally:
+            h.destroy()

@@ -61,10 +61,10 @@ constexpr HostSlot kHostSeam = {12, 13};          /* a stream call: the pairs of
 constexpr HostSlot kHostFlows = {14, 15};         /* a flows call: its pairs (scan_flows.hip: pfac_flows_done stores both words) */
 constexpr HostSlot kHostLines = {16, 18};         /* a lines call: the lines, then the selected lines (scan_lines.hip, by pfac_block_scan) */
 constexpr HostSlot kHostGather = {20, 22};        /* a gather: the 64-bit size of its text (scan_lines.hip) */
-constexpr HostSlot kHostSpans = {24, 26};         /* a spans call: one 64-bit value, the spans | the covered bytes << 32 (scan_spans.hip: pfac_spans_finish) */
+constexpr HostSlot kHostSpans = {24, 26};         /* a spans call: one 64-bit value, the spans | the covered bytes << 32 (scan_spans.hip, by pfac_pairs_finish) */
 constexpr HostSlot kHostCount = {28, 30};         /* a count call: the 64-bit number of occurrences it added (scan_count.hip: pfac_count_store) */
 constexpr HostSlot kHostNonzero = {32, 36};       /* the non-zero counts: two 64-bit values, the distinct patterns, then the sum of the counts (scan_count.hip: pfac_count_finish) */
-constexpr HostSlot kHostDisjoint = {40, 42};      /* a disjoint call: one 64-bit value, the tokens | the covered bytes << 32 (scan_disjoint.hip: pfac_disjoint_finish) */
+constexpr HostSlot kHostDisjoint = {40, 42};      /* a disjoint call: one 64-bit value, the tokens | the covered bytes << 32 (scan_disjoint.hip, by pfac_pairs_finish) */
 constexpr HostSlot kHostReplace = {44, 46};       /* a replacement: the 64-bit sum of (replacement - match) lengths; the size of the text is the input's plus that (scan_disjoint.hip) */
 constexpr HostSlot kHostRules = {48, 50};         /* a rules call: the 64-bit length of its fired list (scan_rules.hip, by pfac_array_scan) */
 constexpr int kHostWords = 52;

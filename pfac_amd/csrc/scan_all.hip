@@ -109,13 +109,6 @@ __global__ __launch_bounds__(kAllBlock) void pfac_all_seg_first(const int *first
     }
 }
 
-/* grow-only scratch of the expansion: the block totals, then (batch form) the expanded offset of every longest pair */
-char *allScratch(PFAC_context *c, size_t bytes)
-{
-    if (c->scratch.all.count() < bytes && c->scratch.all.reserve(bytes + bytes / 2) != PFAC_STATUS_SUCCESS) return nullptr;
-    return c->scratch.all.get();
-}
-
 } // namespace
 
 extern "C" {
@@ -148,16 +141,14 @@ PFAC_status_t PFACX_allExpand(PFAC_handle_t handle, const int *d_pairIds, const 
     x.ids = d_ids;
     x.pos = d_pos;
     x.capacity = capacity;
-    size_t blocks = (count + kAllBlock - 1) / kAllBlock;
-    if (blocks > gridCap(c, 8)) blocks = gridCap(c, 8);
-    x.per = blocks ? ((count + blocks - 1) / blocks + kAllBlock - 1) / kAllBlock * kAllBlock : kAllBlock;
-    blocks = (count + x.per - 1) / x.per;
-    x.blocks = (unsigned int)blocks;
-    const size_t baseBytes = round256((blocks + 1) * sizeof(unsigned long long));
-    char *s = allScratch(c, baseBytes + (d_segFirst ? count * sizeof(unsigned long long) : 0));
-    if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
-    x.blockBase = reinterpret_cast<unsigned long long *>(s);
-    x.pairOffset = d_segFirst ? reinterpret_cast<unsigned long long *>(s + baseBytes) : nullptr;
+    x.blocks = offsetBlocks(c, count, kAllBlock, x.per);
+    const size_t blocks = x.blocks;
+    /* grow-only, half as much again where it grows: the block totals, then (batch form) the expanded offset of every longest pair */
+    const PFAC_status_t carved = carveScratch(c->scratch.all, [&](ScratchCarver &k) {
+        x.blockBase = k.take<unsigned long long>(blocks + 1);
+        x.pairOffset = d_segFirst ? k.take<unsigned long long>(count) : nullptr;
+    }, nullptr, true);
+    if (carved != PFAC_STATUS_SUCCESS) return carved;
     const HostHandoff list(c, pfac::kHostAll);
     if (blocks) hipLaunchKernelGGL(pfac_all_count, dim3((unsigned int)blocks), dim3(kAllBlock), 0, 0, x);
     hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, x.blockBase, (unsigned int)blocks, x.blockBase + blocks,

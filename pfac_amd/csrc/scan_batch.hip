@@ -210,9 +210,6 @@ BatchArgs batchArgs(const PFAC_context *c, const char *d_input, size_t size, con
     return b;
 }
 
-/* grow-only scratch of the compacted form: [0, 256) drop counter, then kept counts per block, then the compacted ids and positions */
-char *batchScratch(PFAC_context *c, size_t bytes) { return c->scratch.batch.reserve(bytes) == PFAC_STATUS_SUCCESS ? c->scratch.batch.get() : nullptr; }
-
 } // namespace
 
 extern "C" {
@@ -257,11 +254,16 @@ PFAC_status_t PFACX_batchReduceFixup(PFAC_handle_t handle, const char *d_input, 
     const unsigned int n = (unsigned int)*count;
     if (n > 0 && b.maxWalk > 0) {
         const size_t blocks = ((size_t)n + kBatchBlock - 1) / kBatchBlock;
-        const size_t head = 256, keptBytes = round256(blocks * sizeof(unsigned int));
-        char *s = batchScratch(c, head + keptBytes + 2 * (size_t)n * sizeof(int));
-        if (!s) return PFAC_STATUS_CUDA_ALLOC_FAILED;
-        unsigned int *drops = reinterpret_cast<unsigned int *>(s), *blockKept = reinterpret_cast<unsigned int *>(s + head);
-        int *idsOut = reinterpret_cast<int *>(s + head + keptBytes), *posOut = idsOut + n;
+        /* grow-only scratch of the compacted form: [0, 256) drop counter, then kept counts per block, then the compacted ids and positions */
+        unsigned int *drops = nullptr, *blockKept = nullptr;
+        int *idsOut = nullptr;
+        const PFAC_status_t carved = carveScratch(c->scratch.batch, [&](ScratchCarver &k) {
+            drops = k.take<unsigned int>(1);
+            blockKept = k.take<unsigned int>(blocks);
+            idsOut = k.take<int>(2 * (size_t)n);
+        });
+        if (carved != PFAC_STATUS_SUCCESS) return carved;
+        int *posOut = idsOut + n;
         if (hipMemsetAsync(drops, 0, sizeof(unsigned int), 0) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
         if (tex)
             hipLaunchKernelGGL(pfac_batch_pair_fixup<true>, dim3((unsigned int)blocks), dim3(kBatchBlock), 0, 0, b, a, d_ids, d_pos, n, blockKept, drops);

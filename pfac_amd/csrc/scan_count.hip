@@ -170,10 +170,7 @@ __global__ __launch_bounds__(kCountThreads) void pfac_count_store(StoreArgs a, u
             a.counts[id] = id != 0 ? a.hist[id] : 0u;
         }
     }
-    if (hostTotal != nullptr && a.total != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-        __hip_atomic_store(hostTotal, *a.total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __threadfence_system();
-    }
+    if (a.total != nullptr && blockIdx.x == 0 && threadIdx.x == 0) storeToHost(hostTotal, *a.total);
 }
 
 __global__ __launch_bounds__(kCountThreads) void pfac_count_chain(StoreArgs a)
@@ -244,19 +241,8 @@ __global__ __launch_bounds__(1024) void pfac_count_finish(NonzeroArgs a, unsigne
         const unsigned long long distinct = a.blockBase[a.blocks];
         a.value[0] = distinct;
         a.value[1] = sum;
-        if (hostValue != nullptr) {
-            __hip_atomic_store(hostValue, distinct, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(hostValue + 1, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __threadfence_system();
-        }
+        storeToHost(hostValue, distinct, sum);
     }
-}
-
-/* the grow-only scratch of the count calls */
-char *countScratch(PFAC_context *c, size_t bytes)
-{
-    if (c->scratch.count.count() < bytes && c->scratch.count.reserve(bytes) != PFAC_STATUS_SUCCESS) return nullptr;
-    return c->scratch.count.get();
 }
 
 } // namespace
@@ -275,14 +261,13 @@ PFAC_status_t PFACX_countPairs(PFAC_handle_t handle, char *d_scan, size_t size, 
     const bool accumulate = (flags & PFACX_COUNT_ACCUMULATE) != 0;
 
     HistArgs h{};
-    ScratchCarver k;
-    for (int pass = 0; pass < 2; pass++) {
+    size_t bytes = 0;
+    const PFAC_status_t carved = carveScratch(c->scratch.count, [&](ScratchCarver &k) {
         h.hist = k.take<unsigned int>((size_t)F + 1);
         h.total = k.take<unsigned long long>(1);
-        if (pass == 0) k = ScratchCarver{countScratch(c, k.bytes)};
-        if (k.base == nullptr) return PFAC_STATUS_CUDA_ALLOC_FAILED;
-    }
-    if (hipMemsetAsync(h.hist, 0, k.bytes, 0) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;        /* L and the total: in front of the scan */
+    }, &bytes);
+    if (carved != PFAC_STATUS_SUCCESS) return carved;
+    if (hipMemsetAsync(h.hist, 0, bytes, 0) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;        /* L and the total: in front of the scan */
 
     size_t count = numPairs;
     if (d_scan) {
@@ -343,15 +328,13 @@ PFAC_status_t PFACX_countNonzero(PFAC_handle_t handle, const unsigned long long 
     a.ids = d_ids;
     a.outCounts = d_outCounts;
     a.capacity = capacity;
-    ScratchCarver k;
-    for (int pass = 0; pass < 2; pass++) {
+    const PFAC_status_t carved = carveScratch(c->scratch.count, [&](ScratchCarver &k) {
         a.blockCount = k.take<unsigned int>(blocks);
         a.blockBase = k.take<unsigned int>(blocks + 1);
         a.blockSum = k.take<unsigned long long>(blocks);
         a.value = k.take<unsigned long long>(2);
-        if (pass == 0) k = ScratchCarver{countScratch(c, k.bytes)};
-        if (k.base == nullptr) return PFAC_STATUS_CUDA_ALLOC_FAILED;
-    }
+    });
+    if (carved != PFAC_STATUS_SUCCESS) return carved;
     const HostHandoff list(c, pfac::kHostNonzero);
     hipLaunchKernelGGL(pfac_count_flags, dim3(a.blocks), dim3(kNzBlock), 0, 0, a);
     blockScan<OpSum>({{a.blockCount}, {a.blockBase}}, a.blocks, nullptr, nullptr);

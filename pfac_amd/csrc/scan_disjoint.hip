@@ -19,7 +19,7 @@
  *   pfac_disjoint_stage       token k = (id, pos) into handle scratch -- not over the pair list: token k may land on a pair that another block has
  *                             not read yet (the two arrays of J are free by now and take the staged tokens)
  *   pfac_disjoint_emit        the tokens over the caller's arrays, the sum of their lengths
- *   pfac_disjoint_finish      both counts as one 64-bit value to mapped host memory, then pfac_host_done (scan_passes.h: HostHandoff)
+ *   pfac_pairs_finish         (scan_passes.h) both counts as one 64-bit value to mapped host memory, then pfac_host_done (scan_passes.h: HostHandoff)
  * No block waits on another, nothing walks the blocks one after another, and nothing relies on chains merging: ab / ba over abab... has two chains
  * that never meet, and only the one through pair 0 is ever marked.  Nothing here touches the input.
  * SCRATCH of a select call with P pairs, B = (P + 511) / 512 blocks: 2 x 4 P (J, then the staged tokens) + P (marks) + 4 B + 4 (B + 1) (tokens of
@@ -57,14 +57,9 @@ constexpr unsigned int kDisjointBlock = 512;                           /* pairs 
 constexpr unsigned int kDisjointRounds = 9;                            /* a chain inside a block has at most 2^9 pairs */
 static_assert((1u << kDisjointRounds) == kDisjointBlock, "the pointer jumping in LDS must cover a whole block");
 constexpr unsigned int kPassThreads = 256;
-constexpr unsigned int kReplaceTile = 4096;                            /* output bytes per tile of the replacement */
 constexpr unsigned int kReplaceStage = 1024;                           /* tokens a tile stages at a time */
 
-struct DisjointArgs {
-    const int *ids, *pos;               /* the scan's ordered pairs (the caller's arrays) */
-    unsigned int count, n;
-    const int *patternLen;              /* by id, numIds entries */
-    unsigned int numIds;
+struct DisjointArgs : PairArgs {       /* scan_passes.h: the scan's ordered pairs, pairOf */
     unsigned int blocks;
     unsigned int *jump[2];              /* [count] each: J and J'; behind pfac_disjoint_mark the staged ids and positions */
     unsigned char *mark;                /* [count] */
@@ -73,13 +68,6 @@ struct DisjointArgs {
     unsigned long long *value;          /* numTokens | coveredBytes << 32 */
     int *outIds, *outPos;
 };
-
-/* position and end of pair i, both inside [0, n] whatever the pair says */
-__device__ __forceinline__ void pairOf(const DisjointArgs &a, unsigned int i, unsigned int &p, unsigned int &e)
-{
-    const int id = a.ids[i];
-    clampSpan(a.pos[i], (unsigned int)id < a.numIds ? a.patternLen[id] : 0, a.n, p, e);
-}
 
 /* next(i) of the thread's pair i = blockIdx.x * kDisjointBlock + threadIdx.x (count for a thread without a pair), inside (i, count] whatever the pairs
  * say; sPos: the positions of the block's pairs (every thread of the block calls this; synchronised on return) */
@@ -202,17 +190,6 @@ __global__ __launch_bounds__(kPassThreads) void pfac_disjoint_emit(DisjointArgs 
     if (threadIdx.x == 0 && total != 0) atomicAdd(a.covered, total);
 }
 
-__global__ void pfac_disjoint_finish(DisjointArgs a, unsigned long long *hostValue)
-{
-    const unsigned int all = a.tokBase[a.blocks], tokens = all < a.count ? all : a.count;
-    const unsigned long long v = (unsigned long long)tokens | (unsigned long long)*a.covered << 32;
-    *a.value = v;
-    if (hostValue != nullptr) {
-        __hip_atomic_store(hostValue, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __threadfence_system();
-    }
-}
-
 /* ------------------------------------------------------------------ the replacement */
 
 struct ReplaceArgs {
@@ -255,41 +232,19 @@ __device__ __forceinline__ Token tokenOf(const ReplaceArgs &a, size_t k)
     return t;
 }
 
-__device__ __forceinline__ unsigned long long deltaOf(const ReplaceArgs &a, size_t k)
-{
-    const Token t = tokenOf(a, k);
-    return (unsigned long long)t.rlen - (unsigned long long)t.len;      /* modulo 2^64 */
-}
+/* what a token adds to the size of the text, modulo 2^64 */
+__device__ __forceinline__ unsigned long long deltaOf(const Token &t) { return (unsigned long long)t.rlen - (unsigned long long)t.len; }
 
 __global__ __launch_bounds__(kPassThreads) void pfac_replace_delta(ReplaceArgs a)
 {
-    __shared__ unsigned long long waveSum[kPassThreads / 64];
-    const size_t first = (size_t)blockIdx.x * a.per;
-    const size_t end = a.count - first < a.per ? a.count : first + a.per;
-    unsigned long long own = 0;
-    for (size_t k = first + threadIdx.x; k < end; k += kPassThreads) own += deltaOf(a, k);
-    unsigned long long total = 0;
-    (void)blockExclusive<kPassThreads>(own, waveSum, total);
-    if (threadIdx.x == 0) a.blockBase[blockIdx.x] = total;
+    offsetsBlockTotal<kPassThreads>(a.count, a.per, a.blockBase, [&](size_t k) { return deltaOf(tokenOf(a, k)); });
 }
 
 __global__ __launch_bounds__(kPassThreads) void pfac_replace_offsets(ReplaceArgs a)
 {
-    __shared__ unsigned long long waveSum[kPassThreads / 64];
-    const size_t first = (size_t)blockIdx.x * a.per;
-    const size_t end = a.count - first < a.per ? a.count : first + a.per;
-    unsigned long long base = a.blockBase[blockIdx.x];
-    for (size_t k0 = first; k0 < end; k0 += kPassThreads) {            /* the same trip count for every thread of the block */
-        const size_t k = k0 + threadIdx.x;
-        const bool has = k < end;
-        Token t{};
-        if (has) t = tokenOf(a, k);
-        const unsigned long long d = has ? (unsigned long long)t.rlen - (unsigned long long)t.len : 0ull;
-        unsigned long long stepTotal = 0;
-        const unsigned long long before = base + blockExclusive<kPassThreads>(d, waveSum, stepTotal);
-        base += stepTotal;
-        if (has) a.outStart[k] = (long long)((unsigned long long)t.s + before);
-    }
+    Token t{};                                                         /* the token of the trip: from its value to its store */
+    offsetsOfBlock<kPassThreads>(a.count, a.per, a.blockBase, [&](size_t k) { t = tokenOf(a, k); return deltaOf(t); },
+                                 [&](size_t k, unsigned long long before) { a.outStart[k] = (long long)((unsigned long long)t.s + before); });
 }
 
 /* Tiles are cut in v = o + misOut, the output offset counted from the aligned 16-byte block that holds out[0].  SLOT q >= 1 is token q - 1; slot 0
@@ -303,10 +258,9 @@ __global__ __launch_bounds__(kPassThreads) void pfac_replace_copy(ReplaceArgs a)
     const unsigned long long total = (unsigned long long)a.n + a.blockBase[a.blocks];       /* a bad list: anything */
     const unsigned long long limit = total < a.outCapacity ? total : a.outCapacity;
     const unsigned int t = threadIdx.x;
-    for (unsigned long long vLo = (unsigned long long)blockIdx.x * kReplaceTile; vLo < limit + a.misOut; vLo += (unsigned long long)gridDim.x * kReplaceTile) {
-        const unsigned long long oLo = vLo > a.misOut ? vLo - a.misOut : 0ull;
-        const unsigned long long oEnd = vLo + kReplaceTile - a.misOut;
-        const unsigned long long oHi = oEnd < limit ? oEnd : limit;
+    for (unsigned long long vLo = (unsigned long long)blockIdx.x * kOutTile; vLo < limit + a.misOut; vLo += (unsigned long long)gridDim.x * kOutTile) {
+        const TileFrame<unsigned long long> f = tileFrame(vLo, a.misOut, limit);
+        const unsigned long long oLo = f.oLo, oHi = f.oHi;
         if (t < 64u) {
             /* the first token that starts behind oLo -- the slot of the token in front of it owns oLo --, and the first that starts at or behind oHi */
             const unsigned int above = waveLowerBound(0u, a.count, [&](unsigned int k) { return a.outStart[k] > (long long)oLo; });
@@ -315,11 +269,9 @@ __global__ __launch_bounds__(kPassThreads) void pfac_replace_copy(ReplaceArgs a)
         }
         __syncthreads();
         const unsigned int qFirst = sFirst, qEnd = sEnd;
-        const unsigned long long v0 = vLo + (unsigned long long)t * 16;
-        const unsigned long long cLo = v0 > a.misOut ? v0 - a.misOut : 0ull;
-        const unsigned long long cHi = v0 + 16 > a.misOut ? (v0 + 16 - a.misOut < oHi ? v0 + 16 - a.misOut : oHi) : 0ull;
-        const bool active = cLo < cHi;
-        const unsigned int nb = active ? (unsigned int)(cHi - cLo) : 0u;
+        const unsigned long long cLo = f.cLo, cHi = f.cLo + f.nb;
+        const unsigned int nb = f.nb;
+        const bool active = nb != 0;
         uint32_t w[4] = {0, 0, 0, 0};                                  /* byte b of the thread's bytes: bits 8 (b & 3) of w[b >> 2] */
         for (unsigned int qBase = qFirst; qBase < qEnd; qBase += kReplaceStage) {
             const unsigned int cnt = qEnd - qBase < kReplaceStage ? qEnd - qBase : kReplaceStage;
@@ -386,15 +338,7 @@ __global__ __launch_bounds__(kPassThreads) void pfac_replace_copy(ReplaceArgs a)
                 }
             }
         }
-        if (active) {
-            if (nb == 16u && v0 >= a.misOut) {
-                __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4 *>(a.out + cLo));
-            } else {
-#pragma unroll
-                for (unsigned int b = 0; b < 16; b++)
-                    if (b < nb) a.out[cLo + b] = (unsigned char)(w[b >> 2] >> (8 * (b & 3)));
-            }
-        }
+        if (active) tileStore(a.out, f, u32x4{w[0], w[1], w[2], w[3]});
         __syncthreads();                                               /* sFirst and the stage are rewritten by the next tile */
     }
 }
@@ -411,40 +355,25 @@ PFAC_status_t PFACX_disjointSelect(PFAC_handle_t handle, char *d_scan, size_t si
         return PFAC_STATUS_INVALID_PARAMETER;
     PFAC_context *c = handle;
 
-    /* the compacted scan with its ordering launches: ids in d_ids, positions in d_pos, ascending */
-    size_t count = 0;
-    const PFAC_status_t st = compactedScan(handle, d_scan, size, hashed, d_ids, d_pos, true, &count);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    *h_numTokens = 0;
-    *h_coveredBytes = 0;
-    if (count == 0) return PFAC_STATUS_SUCCESS;
-
+    /* the ordered pairs, in the arrays that take the tokens */
     DisjointArgs a{};
-    a.ids = d_ids;
-    a.pos = d_pos;
-    a.count = (unsigned int)count;
-    a.n = (unsigned int)size;
-    a.patternLen = d_patternLen;
-    a.numIds = (unsigned int)(numIds < (size_t)0x7fffffff ? numIds : (size_t)0x7fffffff);
+    const PFAC_status_t st = pairsSelectHead(handle, d_scan, size, hashed, d_patternLen, numIds, d_ids, d_pos, h_numTokens, h_coveredBytes, a);
+    if (st != PFAC_STATUS_SUCCESS || a.count == 0) return st;
+    const size_t count = a.count;
     const size_t blocks = (count + kDisjointBlock - 1) / kDisjointBlock;
     a.blocks = (unsigned int)blocks;
-    ScratchCarver k;
-    for (int pass = 0; pass < 2; pass++) {
+    const PFAC_status_t carved = carveScratch(c->scratch.disjoint, [&](ScratchCarver &k) {
         a.jump[0] = k.take<unsigned int>(count);
         a.jump[1] = k.take<unsigned int>(count);
         a.mark = k.take<unsigned char>(count);
         a.tokCount = k.take<unsigned int>(blocks);
         a.tokBase = k.take<unsigned int>(blocks + 1);
         a.value = k.take<unsigned long long>(1, 8);            /* and, behind it, the word `covered` */
-        if (pass == 0) {
-            if (c->scratch.disjoint.count() < k.bytes && c->scratch.disjoint.reserve(k.bytes) != PFAC_STATUS_SUCCESS) return PFAC_STATUS_CUDA_ALLOC_FAILED;
-            k = ScratchCarver{c->scratch.disjoint.get()};
-        }
-    }
+    });
+    if (carved != PFAC_STATUS_SUCCESS) return carved;
     a.covered = reinterpret_cast<unsigned int *>(a.value + 1);
     a.outIds = d_ids;
     a.outPos = d_pos;
-    const HostHandoff counts(c, pfac::kHostDisjoint);
 
     hipLaunchKernelGGL(pfac_disjoint_exit, dim3(a.blocks), dim3(kDisjointBlock), 0, 0, a);
     unsigned int from = 0;
@@ -454,14 +383,7 @@ PFAC_status_t PFACX_disjointSelect(PFAC_handle_t handle, char *d_scan, size_t si
     blockScan<OpSum>({{a.tokCount}, {a.tokBase}}, a.blocks, nullptr, a.covered);
     hipLaunchKernelGGL(pfac_disjoint_stage, dim3(a.blocks), dim3(kDisjointBlock), 0, 0, a);
     hipLaunchKernelGGL(pfac_disjoint_emit, dim3(gridFor(c, count)), dim3(kPassThreads), 0, 0, a);
-    hipLaunchKernelGGL(pfac_disjoint_finish, dim3(1), dim3(1), 0, 0, a, reinterpret_cast<unsigned long long *>(counts.d_value));
-    unsigned long long v = 0;
-    if (!counts.finish(&v, a.value)) return PFAC_STATUS_INTERNAL_ERROR;
-    const size_t tokens = (size_t)(v & 0xFFFFFFFFull), covered = (size_t)(v >> 32);
-    if (tokens == 0 || tokens > count || covered < tokens || covered > size) return PFAC_STATUS_INTERNAL_ERROR;
-    *h_numTokens = tokens;
-    *h_coveredBytes = covered;
-    return PFAC_STATUS_SUCCESS;
+    return pairsSelectTail(c, pfac::kHostDisjoint, a.tokBase + a.blocks, count, size, a.value, h_numTokens, h_coveredBytes);
 }
 
 PFAC_status_t PFACX_replaceRun(PFAC_handle_t handle, const char *d_input, size_t size, const int *d_ids, const int *d_pos, size_t numTokens,
@@ -488,31 +410,23 @@ PFAC_status_t PFACX_replaceRun(PFAC_handle_t handle, const char *d_input, size_t
     a.out = reinterpret_cast<unsigned char *>(d_out);
     a.outCapacity = outCapacity;
     a.misOut = (unsigned int)(reinterpret_cast<uintptr_t>(d_out) & 15u);
-    size_t blocks = (numTokens + kPassThreads - 1) / kPassThreads;
-    if (blocks > gridCap(c, 8)) blocks = gridCap(c, 8);
-    a.per = ((numTokens + blocks - 1) / blocks + kPassThreads - 1) / kPassThreads * kPassThreads;
-    blocks = (numTokens + a.per - 1) / a.per;
-    a.blocks = (unsigned int)blocks;
-    ScratchCarver k;
-    for (int pass = 0; pass < 2; pass++) {
+    a.blocks = offsetBlocks(c, numTokens, kPassThreads, a.per);
+    const PFAC_status_t carved = carveScratch(c->scratch.disjoint, [&](ScratchCarver &k) {
         a.outStart = k.take<long long>(numTokens);
-        a.blockBase = k.take<unsigned long long>(blocks + 1);
-        if (pass == 0) {
-            if (c->scratch.disjoint.count() < k.bytes && c->scratch.disjoint.reserve(k.bytes) != PFAC_STATUS_SUCCESS) return PFAC_STATUS_CUDA_ALLOC_FAILED;
-            k = ScratchCarver{c->scratch.disjoint.get()};
-        }
-    }
+        a.blockBase = k.take<unsigned long long>((size_t)a.blocks + 1);
+    });
+    if (carved != PFAC_STATUS_SUCCESS) return carved;
     const HostHandoff text(c, pfac::kHostReplace);
     hipLaunchKernelGGL(pfac_replace_delta, dim3(a.blocks), dim3(kPassThreads), 0, 0, a);
     hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, a.blockBase, a.blocks, a.blockBase + a.blocks,
                        reinterpret_cast<unsigned long long *>(text.d_value));
     hipLaunchKernelGGL(pfac_replace_offsets, dim3(a.blocks), dim3(kPassThreads), 0, 0, a);
     if (outCapacity) {                                                 /* whatever the size of the text, a launch never needs more tiles than outCapacity has */
-        const unsigned long long tiles = ((unsigned long long)outCapacity + a.misOut + kReplaceTile - 1) / kReplaceTile, cap = gridCap(c, 8) * 4ull;
+        const unsigned long long tiles = ((unsigned long long)outCapacity + a.misOut + kOutTile - 1) / kOutTile, cap = gridCap(c, 8) * 4ull;
         hipLaunchKernelGGL(pfac_replace_copy, dim3((unsigned int)(tiles < cap ? tiles : cap)), dim3(kPassThreads), 0, 0, a);
     }
     unsigned long long sum = 0;
-    if (!text.finish(&sum, a.blockBase + blocks)) return PFAC_STATUS_INTERNAL_ERROR;
+    if (!text.finish(&sum, a.blockBase + a.blocks)) return PFAC_STATUS_INTERNAL_ERROR;
     const unsigned long long total = (unsigned long long)size + sum;
     *h_outBytes = (size_t)total;
     return total > outCapacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;

@@ -49,7 +49,6 @@ namespace {
 constexpr unsigned int kLinesThreads = 256;                /* four waves, a block of positions each */
 constexpr unsigned int kBlockShift = 11;                   /* 2048 positions per block ... */
 constexpr unsigned int kBlockWords = 64;                   /* ... = 64 bitmap words, one per lane */
-constexpr unsigned int kTile = 4096;                       /* output bytes per tile of the gather */
 
 struct LinesArgs {
     const unsigned char *in;            /* the caller's bytes */
@@ -195,51 +194,36 @@ __device__ __forceinline__ size_t lineOf(const GatherArgs &g, size_t i, size_t &
     return e - s;
 }
 
+/* line i in the text: its bytes and its newline */
+__device__ __forceinline__ unsigned long long textOf(const GatherArgs &g, size_t i)
+{
+    size_t s;
+    return lineOf(g, i, s) + 1;
+}
+
 __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_count(GatherArgs g)
 {
-    __shared__ unsigned long long waveSum[kLinesThreads / 64];
-    const size_t first = (size_t)blockIdx.x * g.per;
-    const size_t end = g.count - first < g.per ? g.count : first + g.per;
-    unsigned long long own = 0;
-    size_t s;
-    for (size_t i = first + threadIdx.x; i < end; i += kLinesThreads) own += lineOf(g, i, s) + 1;
-    unsigned long long total = 0;
-    (void)blockExclusive<kLinesThreads>(own, waveSum, total);
-    if (threadIdx.x == 0) g.blockBase[blockIdx.x] = total;
+    offsetsBlockTotal<kLinesThreads>(g.count, g.per, g.blockBase, [&](size_t i) { return textOf(g, i); });
 }
 
 __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_offsets(GatherArgs g)
 {
-    __shared__ unsigned long long waveSum[kLinesThreads / 64];
-    const size_t first = (size_t)blockIdx.x * g.per;
-    const size_t end = g.count - first < g.per ? g.count : first + g.per;
-    unsigned long long base = g.blockBase[blockIdx.x];
-    for (size_t i0 = first; i0 < end; i0 += kLinesThreads) {        /* the same trip count for every thread of the block */
-        const size_t i = i0 + threadIdx.x;
-        const bool has = i < end;
-        size_t s;
-        const unsigned long long c = has ? lineOf(g, i, s) + 1 : 0ull;
-        unsigned long long stepTotal = 0;
-        const unsigned long long o = base + blockExclusive<kLinesThreads>(c, waveSum, stepTotal);
-        base += stepTotal;
-        if (has) g.off[i] = o;
-    }
+    offsetsOfBlock<kLinesThreads>(g.count, g.per, g.blockBase, [&](size_t i) { return textOf(g, i); }, [&](size_t i, unsigned long long o) { g.off[i] = o; });
 }
 
-/* the text, a tile of kTile output bytes at a time.  Tiles are cut in v = o + misOut, the output offset counted from the aligned 16-byte block that
+/* the text, a tile of kOutTile output bytes at a time.  Tiles are cut in v = o + misOut, the output offset counted from the aligned 16-byte block that
  * holds out[0]: a thread's 16 bytes are one aligned store unless they hang over an end of the text */
 __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_copy(GatherArgs g)
 {
-    __shared__ unsigned int rel[kTile + 1];              /* offsets of the tile's lines behind its first, relative to the tile's first byte */
+    __shared__ unsigned int rel[kOutTile + 1];              /* offsets of the tile's lines behind its first, relative to the tile's first byte */
     __shared__ size_t sFirst;
     __shared__ unsigned int sCount;
     const unsigned long long total = g.blockBase[g.blocks];
     const unsigned long long limit = total < g.outCapacity ? total : g.outCapacity;
     const unsigned int t = threadIdx.x;
-    for (unsigned long long vLo = (unsigned long long)blockIdx.x * kTile; vLo < limit + g.misOut; vLo += (unsigned long long)gridDim.x * kTile) {
-        const unsigned long long oLo = vLo > g.misOut ? vLo - g.misOut : 0ull;
-        const unsigned long long oEnd = vLo + kTile - g.misOut;
-        const unsigned long long oHi = oEnd < limit ? oEnd : limit;
+    for (unsigned long long vLo = (unsigned long long)blockIdx.x * kOutTile; vLo < limit + g.misOut; vLo += (unsigned long long)gridDim.x * kOutTile) {
+        const TileFrame<unsigned long long> f = tileFrame(vLo, g.misOut, limit);
+        const unsigned long long oLo = f.oLo, oHi = f.oHi;
         if (t == 0) {
             /* the last line that starts at or in front of oLo (off[0] == 0), and the last that starts in front of oHi */
             size_t lo = 0, hi = g.count;
@@ -253,19 +237,16 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_copy(GatherAr
                 if (g.off[mid] < oHi) lo2 = mid; else hi2 = mid;
             }
             sFirst = lo;
-            const size_t c = lo2 - lo + 1;              /* offsets are strictly ascending: at most kTile lines start inside a tile */
-            sCount = c > kTile ? kTile : (unsigned int)c;
+            const size_t c = lo2 - lo + 1;              /* offsets are strictly ascending: at most kOutTile lines start inside a tile */
+            sCount = c > kOutTile ? kOutTile : (unsigned int)c;
         }
         __syncthreads();
         const size_t first = sFirst;
         const unsigned int cnt = sCount;
         for (unsigned int j = t; j < cnt; j += kLinesThreads) rel[j] = j == 0 ? 0u : (unsigned int)(g.off[first + j] - oLo);
         __syncthreads();
-        const unsigned long long v0 = vLo + (unsigned long long)t * 16;
-        const unsigned long long cLo = v0 > g.misOut ? v0 - g.misOut : 0ull;
-        unsigned long long cHi = v0 + 16 > g.misOut ? v0 + 16 - g.misOut : 0ull;
-        cHi = cHi < oHi ? cHi : oHi;
-        if (cLo < cHi) {
+        const unsigned long long cLo = f.cLo;
+        if (f.nb != 0) {
             const unsigned int r = (unsigned int)(cLo - oLo);
             unsigned int lo = 0, hi = cnt;
             while (hi - lo > 1) {
@@ -287,34 +268,18 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_gather_copy(GatherAr
                 }
                 return byte;
             };
-            if (cHi - cLo == 16 && v0 >= g.misOut) {
-                uint32_t x[4];
+            uint32_t x[4] = {0, 0, 0, 0};
 #pragma unroll
-                for (int d = 0; d < 4; d++) {
-                    uint32_t y = next();
-                    y |= next() << 8;
-                    y |= next() << 16;
-                    y |= next() << 24;
-                    x[d] = y;
-                }
-                *reinterpret_cast<pfacmod::u32x4 *>(g.out + cLo) = pfacmod::u32x4{x[0], x[1], x[2], x[3]};
-            } else {
-                for (unsigned long long o = cLo; o < cHi; o++) g.out[o] = (unsigned char)next();
-            }
+            for (unsigned int b = 0; b < 16; b++)
+                if (b < f.nb) x[b >> 2] |= next() << (8 * (b & 3));
+            tileStore(g.out, f, pfacmod::u32x4{x[0], x[1], x[2], x[3]});
         }
         __syncthreads();                                 /* rel is rewritten by the next tile */
     }
 }
 
-/* grow-only scratch of the lines calls (exactly what a call needs: a fixed function of its size) */
-char *linesScratch(PFAC_context *c, size_t bytes)
-{
-    if (c->scratch.lines.count() < bytes && c->scratch.lines.reserve(bytes) != PFAC_STATUS_SUCCESS) return nullptr;
-    return c->scratch.lines.get();
-}
-
-/* the arguments of the passes over the n bytes at `in`, their arrays carved from the handle's lines scratch: the newline pass's (select == false)
- * or those of a whole select call.  false: no memory */
+/* the arguments of the passes over the n bytes at `in`, their arrays carved from the handle's lines scratch (grow-only; exactly what a call needs:
+ * a fixed function of its size): the newline pass's (select == false) or those of a whole select call.  false: no memory */
 bool linesArgs(PFAC_context *c, const void *in, size_t n, bool select, LinesArgs &a)
 {
     a.in = static_cast<const unsigned char *>(in);
@@ -322,8 +287,7 @@ bool linesArgs(PFAC_context *c, const void *in, size_t n, bool select, LinesArgs
     a.mis = (unsigned int)(reinterpret_cast<uintptr_t>(in) & 15u);
     const size_t blocks = ((size_t)a.mis + n) / (size_t(1) << kBlockShift) + 1, words = blocks * kBlockWords;      /* positions q in [0, mis + n] */
     a.blocks = (unsigned int)blocks;
-    ScratchCarver k;
-    for (int pass = 0; pass < 2; pass++) {
+    return carveScratch(c->scratch.lines, [&](ScratchCarver &k) {
         a.nlBits = k.take<uint32_t>(words);
         a.hitBits = k.take<uint32_t>(words, 256);              /* and the word a funnel may read behind it */
         a.rank = k.take<uint16_t>(words);
@@ -337,10 +301,7 @@ bool linesArgs(PFAC_context *c, const void *in, size_t n, bool select, LinesArgs
         } else {
             a.lineCount = k.take<unsigned int>(blocks);
         }
-        if (pass == 0) k = ScratchCarver{linesScratch(c, k.bytes)};
-        if (k.base == nullptr) return false;
-    }
-    return true;
+    }) == PFAC_STATUS_SUCCESS;
 }
 
 /* the grid of the passes that take a block of positions per wave */
@@ -428,18 +389,12 @@ PFAC_status_t PFACX_linesGather(PFAC_handle_t handle, const char *d_input, size_
     g.out = reinterpret_cast<unsigned char *>(d_out);
     g.outCapacity = outCapacity;
     g.misOut = (unsigned int)(reinterpret_cast<uintptr_t>(d_out) & 15u);
-    size_t blocks = (numSelected + kLinesThreads - 1) / kLinesThreads;
-    if (blocks > gridCap(c, 8)) blocks = gridCap(c, 8);
-    g.per = ((numSelected + blocks - 1) / blocks + kLinesThreads - 1) / kLinesThreads * kLinesThreads;
-    blocks = (numSelected + g.per - 1) / g.per;
-    g.blocks = (unsigned int)blocks;
-    ScratchCarver k;
-    for (int pass = 0; pass < 2; pass++) {
-        g.blockBase = k.take<unsigned long long>(blocks + 1);
+    g.blocks = offsetBlocks(c, numSelected, kLinesThreads, g.per);
+    const PFAC_status_t carved = carveScratch(c->scratch.lines, [&](ScratchCarver &k) {
+        g.blockBase = k.take<unsigned long long>((size_t)g.blocks + 1);
         g.off = k.take<unsigned long long>(numSelected);
-        if (pass == 0) k = ScratchCarver{linesScratch(c, k.bytes)};
-        if (k.base == nullptr) return PFAC_STATUS_CUDA_ALLOC_FAILED;
-    }
+    });
+    if (carved != PFAC_STATUS_SUCCESS) return carved;
     const HostHandoff text(c, pfac::kHostGather);
     hipLaunchKernelGGL(pfac_lines_gather_count, dim3(g.blocks), dim3(kLinesThreads), 0, 0, g);
     hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, g.blockBase, g.blocks, g.blockBase + g.blocks,
@@ -449,11 +404,11 @@ PFAC_status_t PFACX_linesGather(PFAC_handle_t handle, const char *d_input, size_
     if (outCapacity) {
         const unsigned long long bound = (unsigned long long)numSelected * (size + 1);
         const unsigned long long most = (bound < outCapacity ? bound : (unsigned long long)outCapacity) + g.misOut;
-        const unsigned long long tiles = (most + kTile - 1) / kTile;
+        const unsigned long long tiles = (most + kOutTile - 1) / kOutTile;
         hipLaunchKernelGGL(pfac_lines_gather_copy, dim3((unsigned int)(tiles < gridCap(c, 8) * 4ull ? tiles : gridCap(c, 8) * 4ull)), dim3(kLinesThreads), 0, 0, g);
     }
     unsigned long long total = 0;
-    if (!text.finish(&total, g.blockBase + blocks)) return PFAC_STATUS_INTERNAL_ERROR;
+    if (!text.finish(&total, g.blockBase + g.blocks)) return PFAC_STATUS_INTERNAL_ERROR;
     *h_outBytes = (size_t)total;
     return total > outCapacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
 }

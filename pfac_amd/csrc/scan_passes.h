@@ -1,12 +1,15 @@
 /*
  * scan_passes.h -- what the passes around the scan share (scan_module.hip with scan_order.inc, scan_batch.hip, scan_all.hip, scan_fold.hip,
- * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip, scan_disjoint.hip; the product kernels' units do not include it): launch sizes, the layout of a
- * call's scratch, the compacted scan as a pass runs it, the hand-off of a call's result to the host through mapped memory, the device fold byte,
- * the clamp of a caller's (start, len), 16 bytes out of two aligned blocks (funnel, loadBytes16), wave and block prefixes under a sum or a maximum,
- * the 64-ary search of a wave (waveLowerBound), the two scan
- * kernels (pfac_array_scan: one block, in place; pfac_block_scan: a block per 8192 values that folds what lies in front of them), the seam of
- * a stream.  Like scan_common.h, everything is in an unnamed namespace: inline device code, each
- * unit its own copy.
+ * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip, scan_disjoint.hip, scan_rules.hip; the product kernels' units do
+ * not include it): launch sizes, the layout of a call's scratch and its carving out of a buffer of the handle (ScratchCarver, carveScratch), the
+ * compacted scan as a pass runs it, the hand-off of a call's result to the host through mapped memory (HostHandoff; storeToHost on the device),
+ * the device fold byte, the clamp of a caller's (start, len), 16 bytes out of two aligned blocks (funnel, loadBytes16), the frame of an output
+ * tile and its store tail (kOutTile, tileFrame, tileStore), wave and block prefixes
+ * under a sum or a maximum, the 64-ary search of a wave (waveLowerBound), the two scan kernels (pfac_array_scan: one block, in place;
+ * pfac_block_scan: a block per 8192 values that folds what lies in front of them), the two passes that give items of 64-bit values their offsets
+ * (offsetBlocks, offsetsBlockTotal, offsetsOfBlock), the pairs of an ordered scan with the head, the tail and the finish kernel of a select call
+ * over them (PairArgs, pairsSelectHead, pairsSelectTail, pfac_pairs_finish), the seam of a stream.  Like scan_common.h, everything is in an
+ * unnamed namespace: inline device code, each unit its own copy.
  */
 #ifndef PFAC_SCAN_PASSES_H_
 #define PFAC_SCAN_PASSES_H_
@@ -48,6 +51,25 @@ struct ScratchCarver {
         return at;
     }
 };
+
+/* A call's regions out of one of the handle's grow-only buffers: `layout` (it takes a ScratchCarver &) runs once without a base for the bytes and
+ * again over the buffer for the pointers; *bytes (where given) = what the regions take.  A buffer that has to grow loses its contents; halfMore:
+ * it is then reserved with half as much again as the call needs (the all-match expansion).  No memory: the status of the reserve, and no pointer
+ * is valid */
+template <class Layout>
+inline PFAC_status_t carveScratch(pfac::DeviceBuffer<char> &buffer, Layout layout, size_t *bytes = nullptr, bool halfMore = false)
+{
+    ScratchCarver k;
+    layout(k);
+    if (buffer.count() < k.bytes) {
+        const PFAC_status_t st = buffer.reserve(k.bytes + (halfMore ? k.bytes / 2 : 0));
+        if (st != PFAC_STATUS_SUCCESS) return st;
+    }
+    if (bytes != nullptr) *bytes = k.bytes;
+    k = ScratchCarver{buffer.get()};
+    layout(k);
+    return PFAC_STATUS_SUCCESS;
+}
 
 /* The compacted scan of d_scan[0, size) as a pass runs it: the (id, position) pairs into d_ids / d_pos (`size` entries each), in position order or
  * -- the four ordering launches not paid for -- in any; *count is inside [0, size].  The handle's own setting is put back */
@@ -133,6 +155,24 @@ struct HostHandoff {
     }
 };
 
+/* a kernel's side of it: v (and v1 in the word behind it) to the call's mapped host words, if the handle has them.  No sequence number: the
+ * call's done word is written by a later launch (scan_stream.hip and scan_flows.hip release theirs in the same kernel, and do not use this) */
+template <class T>
+__device__ __forceinline__ void storeToHost(T *host, T v)
+{
+    if (host == nullptr) return;
+    __hip_atomic_store(host, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __threadfence_system();
+}
+template <class T>
+__device__ __forceinline__ void storeToHost(T *host, T v, T v1)
+{
+    if (host == nullptr) return;
+    __hip_atomic_store(host, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(host + 1, v1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __threadfence_system();
+}
+
 /* ------------------------------------------------------------------ the fold of a byte */
 
 /* pfac::asciiFold on the device, for a caseless set (fold != 0) */
@@ -177,6 +217,50 @@ __device__ __forceinline__ u32x4 loadBytes16(const unsigned char *in, unsigned i
     for (int d = 0; d < 4; d++)
         w[d] = (uint32_t)in[o + 4 * d] | (uint32_t)in[o + 4 * d + 1] << 8 | (uint32_t)in[o + 4 * d + 2] << 16 | (uint32_t)in[o + 4 * d + 3] << 24;
     return u32x4{w[0], w[1], w[2], w[3]};
+}
+
+/* ------------------------------------------------------------------ output tiles (the gather, the redaction, the replacement) */
+
+/* An output of `limit` bytes is written a TILE of kOutTile bytes at a time by blocks of 256 threads, 16 bytes a thread.  Tiles are cut in
+ * v = o + misOut, the output offset counted from the aligned 16-byte block that holds out[0] (misOut = address of out & 15): a thread's 16 bytes
+ * are one aligned store unless they hang over an end of the output */
+constexpr unsigned int kOutTile = 4096;
+
+/* the tile that starts at vLo (a multiple of kOutTile) as output bytes [oLo, oHi), and this thread's bytes of it, [cLo, cLo + nb) (nb == 0: none;
+ * whole: all sixteen, aligned).  I: the width the caller counts output bytes in */
+template <class I>
+struct TileFrame {
+    I oLo, oHi, cLo;
+    unsigned int nb;
+    bool whole;
+};
+template <class I>
+__device__ __forceinline__ TileFrame<I> tileFrame(unsigned long long vLo, unsigned int misOut, I limit)
+{
+    TileFrame<I> f;
+    f.oLo = vLo > misOut ? (I)(vLo - misOut) : (I)0;
+    const unsigned long long oEnd = vLo + kOutTile - misOut;
+    f.oHi = oEnd < limit ? (I)oEnd : limit;
+    const unsigned long long v0 = vLo + (unsigned long long)threadIdx.x * 16;
+    f.cLo = v0 > misOut ? (I)(v0 - misOut) : (I)0;
+    const I cHi = v0 + 16 > misOut ? (v0 + 16 - misOut < f.oHi ? (I)(v0 + 16 - misOut) : f.oHi) : (I)0;
+    f.nb = f.cLo < cHi ? (unsigned int)(cHi - f.cLo) : 0u;
+    f.whole = f.nb == 16u && v0 >= misOut;
+    return f;
+}
+
+/* the thread's bytes out (byte b: bits 8 (b & 3) of word b >> 2 of x): one aligned 16-byte store, or bytes where the 16 hang over an end */
+template <class I>
+__device__ __forceinline__ void tileStore(unsigned char *out, const TileFrame<I> &f, u32x4 x)
+{
+    if (f.whole) {
+        __builtin_nontemporal_store(x, reinterpret_cast<u32x4 *>(out + f.cLo));
+    } else {
+        const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (unsigned int b = 0; b < 16; b++)
+            if (b < f.nb) out[f.cLo + b] = (unsigned char)(w[b >> 2] >> (8 * (b & 3)));
+    }
 }
 
 /* ------------------------------------------------------------------ wave and block prefixes */
@@ -294,10 +378,7 @@ __global__ __launch_bounds__(1024) void pfac_array_scan(T *v, unsigned int n, T 
     }
     if (threadIdx.x == 0) {
         if (total != nullptr) *total = carry;
-        if (hostTotal != nullptr) {
-            __hip_atomic_store(hostTotal, carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __threadfence_system();
-        }
+        storeToHost(hostTotal, carry);
     }
 }
 
@@ -370,10 +451,7 @@ __global__ __launch_bounds__(1024) void pfac_block_scan(ScanColumns s, unsigned 
         }
         if (c == 0 && blockIdx.x == gridDim.x - 1 && threadIdx.x == 1023) {       /* the last thread of the last block has seen everything */
             s.out[0][n] = run;
-            if (hostTotal != nullptr) {
-                __hip_atomic_store(hostTotal, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __threadfence_system();
-            }
+            storeToHost(hostTotal, run);
         }
     }
 }
@@ -383,6 +461,117 @@ template <class Op0, class Op1 = Op0, unsigned int COLS = 1>
 inline void blockScan(const ScanColumns &s, unsigned int n, unsigned int *hostTotal, unsigned int *zero)
 {
     hipLaunchKernelGGL((pfac_block_scan<Op0, Op1, COLS>), dim3((n + kScanBlock - 1) / kScanBlock), dim3(1024), 0, 0, s, n, hostTotal, zero);
+}
+
+/* ------------------------------------------------------------------ offsets of items with 64-bit values (the gather's lines, the replacement's tokens, the expansion's pairs) */
+
+/* the cut of `count` items for the two passes below: blocks of `threads` threads, eight per compute unit at most; per: the items of a block, a
+ * multiple of `threads` (no items: no blocks) */
+inline unsigned int offsetBlocks(const PFAC_context *c, size_t count, unsigned int threads, size_t &per)
+{
+    size_t blocks = (count + threads - 1) / threads;
+    if (blocks > gridCap(c, 8)) blocks = gridCap(c, 8);
+    per = blocks ? ((count + blocks - 1) / blocks + threads - 1) / threads * threads : threads;
+    return (unsigned int)((count + per - 1) / per);
+}
+
+/* the first pass, by a block of BLOCK threads: blockBase[blockIdx.x] = the sum of value(k) over the block's items */
+template <unsigned int BLOCK, class Value>
+__device__ __forceinline__ void offsetsBlockTotal(size_t count, size_t per, unsigned long long *blockBase, Value value)
+{
+    __shared__ unsigned long long waveSum[BLOCK / 64];
+    const size_t first = (size_t)blockIdx.x * per;
+    const size_t end = count - first < per ? count : first + per;
+    unsigned long long own = 0;
+    for (size_t k = first + threadIdx.x; k < end; k += BLOCK) own += value(k);
+    unsigned long long total = 0;
+    (void)blockExclusive<BLOCK>(own, waveSum, total);
+    if (threadIdx.x == 0) blockBase[blockIdx.x] = total;
+}
+
+/* the second, behind the scan of blockBase: store(k, the sum of the values in front of item k).  A thread calls store(k, ...) right behind its
+ * value(k): a value may leave what it loaded to its store */
+template <unsigned int BLOCK, class Value, class Store>
+__device__ __forceinline__ void offsetsOfBlock(size_t count, size_t per, const unsigned long long *blockBase, Value value, Store store)
+{
+    __shared__ unsigned long long waveSum[BLOCK / 64];
+    const size_t first = (size_t)blockIdx.x * per;
+    const size_t end = count - first < per ? count : first + per;
+    unsigned long long base = blockBase[blockIdx.x];
+    for (size_t k0 = first; k0 < end; k0 += BLOCK) {                   /* the same trip count for every thread of the block */
+        const size_t k = k0 + threadIdx.x;
+        const bool has = k < end;
+        const unsigned long long v = has ? value(k) : 0ull;
+        unsigned long long stepTotal = 0;
+        const unsigned long long before = base + blockExclusive<BLOCK>(v, waveSum, stepTotal);
+        base += stepTotal;
+        if (has) store(k, before);
+    }
+}
+
+/* ------------------------------------------------------------------ the pairs of an ordered scan (scan_spans.hip, scan_disjoint.hip) */
+
+/* what the arguments of both select calls start with */
+struct PairArgs {
+    const int *ids, *pos;               /* the scan's ordered pairs (the caller's arrays) */
+    unsigned int count, n;
+    const int *patternLen;              /* by id, numIds entries */
+    unsigned int numIds;
+};
+
+/* position and end of pair i, both inside [0, n] whatever the pair says */
+__device__ __forceinline__ void pairOf(const PairArgs &a, unsigned int i, unsigned int &p, unsigned int &e)
+{
+    const int id = a.ids[i];
+    clampSpan(a.pos[i], (unsigned int)id < a.numIds ? a.patternLen[id] : 0, a.n, p, e);
+}
+
+/* the last launch of a select call: min(*total, bound) | *covered << 32, both counts as one 64-bit value, to *value and to the host (a template
+ * like the scan kernels: only a unit that launches it has a copy) */
+template <class T>
+__global__ void pfac_pairs_finish(const T *total, T bound, const T *covered, unsigned long long *value, unsigned long long *hostValue)
+{
+    const T all = *total, kept = all < bound ? all : bound;
+    const unsigned long long v = (unsigned long long)kept | (unsigned long long)*covered << 32;
+    *value = v;
+    storeToHost(hostValue, v);
+}
+
+/* The head of a select call: the compacted scan WITH its ordering launches into the caller's arrays (ids in d_ids, positions in d_pos, ascending),
+ * both outputs zeroed, the common arguments filled in.  a.count == 0 behind a success: nothing found, the call is over */
+inline PFAC_status_t pairsSelectHead(PFAC_handle_t handle, char *d_scan, size_t size, int hashed, const int *d_patternLen, size_t numIds, int *d_ids,
+                                     int *d_pos, size_t *h_count, size_t *h_covered, PairArgs &a)
+{
+    size_t count = 0;
+    const PFAC_status_t st = compactedScan(handle, d_scan, size, hashed, d_ids, d_pos, true, &count);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    *h_count = 0;
+    *h_covered = 0;
+    a.ids = d_ids;
+    a.pos = d_pos;
+    a.count = (unsigned int)count;
+    a.n = (unsigned int)size;
+    a.patternLen = d_patternLen;
+    a.numIds = (unsigned int)(numIds < (size_t)0x7fffffff ? numIds : (size_t)0x7fffffff);
+    return PFAC_STATUS_SUCCESS;
+}
+
+/* The tail, behind the call's own launches: pfac_pairs_finish over *d_total and the word `covered` that lies behind *d_value, the hand-off through
+ * `slot`, and (count, covered) unpacked: 1 <= count <= bound (the entries the call had room for) and count <= covered <= size, or the call failed */
+template <class T>
+inline PFAC_status_t pairsSelectTail(PFAC_context *c, pfac::HostSlot slot, const T *d_total, size_t bound, size_t size, unsigned long long *d_value,
+                                     size_t *h_count, size_t *h_covered)
+{
+    const HostHandoff counts(c, slot);
+    hipLaunchKernelGGL(pfac_pairs_finish<T>, dim3(1), dim3(1), 0, 0, d_total, (T)bound, reinterpret_cast<const T *>(d_value + 1), d_value,
+                       reinterpret_cast<unsigned long long *>(counts.d_value));
+    unsigned long long v = 0;
+    if (!counts.finish(&v, d_value)) return PFAC_STATUS_INTERNAL_ERROR;
+    const size_t count = (size_t)(v & 0xFFFFFFFFull), covered = (size_t)(v >> 32);
+    if (count == 0 || count > bound || covered < count || covered > size) return PFAC_STATUS_INTERNAL_ERROR;
+    *h_count = count;
+    *h_covered = covered;
+    return PFAC_STATUS_SUCCESS;
 }
 
 /* ------------------------------------------------------------------ the seam of a stream (scan_stream.hip, scan_flows.hip) */

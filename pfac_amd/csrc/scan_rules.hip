@@ -193,13 +193,6 @@ __global__ __launch_bounds__(kRulesBlockPairs) void pfac_rules_pass(RulesArgs a)
     }
 }
 
-/* the grow-only scratch of the rules calls */
-char *rulesScratch(PFAC_context *c, size_t bytes)
-{
-    if (c->scratch.rules.count() < bytes && c->scratch.rules.reserve(bytes) != PFAC_STATUS_SUCCESS) return nullptr;
-    return c->scratch.rules.get();
-}
-
 } // namespace
 
 extern "C" {
@@ -226,12 +219,8 @@ PFAC_status_t PFACX_rulesRun(PFAC_handle_t handle, const PFACX_rulesRun_t *run, 
     a.firedSeg = run->d_firedSeg;
     a.firedRule = run->d_firedRule;
     a.capacity = run->capacity;
-    ScratchCarver k;
-    for (int pass = 0; pass < 2; pass++) {
-        a.segFirst = k.take<unsigned long long>(run->numSegments + 1);
-        if (pass == 0) k = ScratchCarver{rulesScratch(c, k.bytes)};
-        if (k.base == nullptr) return PFAC_STATUS_CUDA_ALLOC_FAILED;
-    }
+    const PFAC_status_t carved = carveScratch(c->scratch.rules, [&](ScratchCarver &k) { a.segFirst = k.take<unsigned long long>(run->numSegments + 1); });
+    if (carved != PFAC_STATUS_SUCCESS) return carved;
     const unsigned int grid = a.numSegments < gridCap(c, 4) ? a.numSegments : gridCap(c, 4);
     const HostHandoff list(c, pfac::kHostRules);
     hipLaunchKernelGGL(pfac_rules_pass<false>, dim3(grid), dim3(kRulesBlockPairs), 0, 0, a);

@@ -16,7 +16,7 @@
  *   pfac_spans_heads<1>       the same walk again: head k writes start_k and end_(k-1) = E_i into handle scratch -- not over the pair list: span k may
  *                             land on a pair that another block has not read yet
  *   pfac_spans_emit           (start, len) of the spans over the caller's arrays, the sum of the lengths
- *   pfac_spans_finish         both counts as one 64-bit value to mapped host memory, then pfac_host_done (scan_passes.h: HostHandoff)
+ *   pfac_pairs_finish         (scan_passes.h) both counts as one 64-bit value to mapped host memory, then pfac_host_done (scan_passes.h: HostHandoff)
  * Nothing here touches the input: the work is proportional to the pairs.
  * SCRATCH of a select call with P pairs, S = min(P, (size + 1) / 2) (no more spans fit the buffer), B = (P + 511) / 512 blocks:
  * 2 x 4 S (starts and ends) + 4 B + 4 (B + 1) + 4 B + 4 (B + 1) (largest end, heads, and their scans) + 256 bytes, each part rounded up to 256:
@@ -45,16 +45,11 @@ namespace {
 constexpr unsigned int kSpanThreads = 256;
 constexpr unsigned int kSpanPer = 2;                                   /* consecutive pairs per thread */
 constexpr unsigned int kSpanBlock = kSpanThreads * kSpanPer;           /* 512 pairs per block */
-constexpr unsigned int kTile = 4096;                                   /* output bytes per tile of the redaction */
 constexpr unsigned int kStage = 1024;                                  /* spans a tile stages at a time */
-constexpr unsigned int kStageTrips = 3;                                /* kStage * kStageTrips >= kTile / 2 + 1 */
-static_assert(kStage * kStageTrips >= kTile / 2 + 1, "a tile must be able to stage every span of an ascending disjoint list that meets it");
+constexpr unsigned int kStageTrips = 3;                                /* kStage * kStageTrips >= kOutTile / 2 + 1 */
+static_assert(kStage * kStageTrips >= kOutTile / 2 + 1, "a tile must be able to stage every span of an ascending disjoint list that meets it");
 
-struct SpanArgs {
-    const int *ids, *pos;               /* the scan's ordered pairs (the caller's arrays) */
-    unsigned int count, n;
-    const int *patternLen;              /* by id, numIds entries */
-    unsigned int numIds;
+struct SpanArgs : PairArgs {           /* scan_passes.h: the scan's ordered pairs, pairOf */
     unsigned int blocks;
     unsigned int bound;                 /* entries of outStart / outEnd */
     unsigned int *blockMax, *blockTop;  /* [blocks] largest end of the block; [blocks + 1] largest end in front of the block, [blocks] = of all */
@@ -64,13 +59,6 @@ struct SpanArgs {
     unsigned long long *value;          /* numSpans | coveredBytes << 32 */
     int *spanStart, *spanLen;
 };
-
-/* position and end of pair i, both inside [0, n] whatever the pair says */
-__device__ __forceinline__ void pairOf(const SpanArgs &a, unsigned int i, unsigned int &p, unsigned int &e)
-{
-    const int id = a.ids[i];
-    clampSpan(a.pos[i], (unsigned int)id < a.numIds ? a.patternLen[id] : 0, a.n, p, e);
-}
 
 __global__ __launch_bounds__(kSpanThreads) void pfac_spans_reduce(SpanArgs a)
 {
@@ -151,17 +139,6 @@ __global__ __launch_bounds__(kSpanThreads) void pfac_spans_emit(SpanArgs a)
     if (threadIdx.x == 0 && total != 0) atomicAdd(a.covered, total);
 }
 
-__global__ void pfac_spans_finish(SpanArgs a, unsigned long long *hostValue)
-{
-    const unsigned int all = a.headBase[a.blocks], spans = all < a.bound ? all : a.bound;
-    const unsigned long long v = (unsigned long long)spans | (unsigned long long)*a.covered << 32;
-    *a.value = v;
-    if (hostValue != nullptr) {
-        __hip_atomic_store(hostValue, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __threadfence_system();
-    }
-}
-
 /* ------------------------------------------------------------------ the redaction */
 
 struct RedactArgs {
@@ -191,9 +168,9 @@ __global__ __launch_bounds__(kSpanThreads) void pfac_spans_redact(RedactArgs a)
     __shared__ unsigned int sFirst, sCount;
     const unsigned int t = threadIdx.x;
     const size_t vEnd = (size_t)a.n + a.misOut;
-    for (size_t vLo = (size_t)blockIdx.x * kTile; vLo < vEnd; vLo += (size_t)gridDim.x * kTile) {
-        const unsigned int oLo = vLo > a.misOut ? (unsigned int)(vLo - a.misOut) : 0u;
-        const unsigned int oHi = vLo + kTile - a.misOut < a.n ? (unsigned int)(vLo + kTile - a.misOut) : a.n;
+    for (size_t vLo = (size_t)blockIdx.x * kOutTile; vLo < vEnd; vLo += (size_t)gridDim.x * kOutTile) {
+        const TileFrame<unsigned int> f = tileFrame(vLo, a.misOut, a.n);
+        const unsigned int oLo = f.oLo, oHi = f.oHi;
         if (t < 64u) {
             /* the first span that ends behind oLo, and the first behind it that starts at or behind oHi */
             const unsigned int first = waveLowerBound(0u, a.count, [&](unsigned int i) { unsigned int s, e; spanOf(a, i, s, e); return e > oLo; });
@@ -203,10 +180,8 @@ __global__ __launch_bounds__(kSpanThreads) void pfac_spans_redact(RedactArgs a)
         }
         __syncthreads();
         const unsigned int first = sFirst, total = sCount;
-        const size_t v0 = vLo + (size_t)t * 16;
-        const unsigned int cLo = v0 > a.misOut ? (unsigned int)(v0 - a.misOut) : 0u;
-        unsigned int cHi = v0 + 16 > a.misOut ? (unsigned int)(v0 + 16 - a.misOut < oHi ? v0 + 16 - a.misOut : oHi) : 0u;
-        const bool active = cLo < cHi;
+        const unsigned int cLo = f.cLo, cHi = f.cLo + f.nb;
+        const bool active = f.nb != 0;
         uint32_t mask = 0;                                        /* bit j: byte cLo + j is covered */
         for (unsigned int base = 0; base < total; base += kStage) {
             const unsigned int cnt = total - base < kStage ? total - base : kStage;
@@ -228,23 +203,24 @@ __global__ __launch_bounds__(kSpanThreads) void pfac_spans_redact(RedactArgs a)
                 }
             }
         }
-        if (active) {
-            if (cHi - cLo == 16u && v0 >= a.misOut) {
-                pfacmod::u32x4 *dst = reinterpret_cast<pfacmod::u32x4 *>(a.out + cLo);
-                const pfacmod::u32x4 fill = {a.fill4, a.fill4, a.fill4, a.fill4};
-                if (mask == 0xFFFFu) {
-                    __builtin_nontemporal_store(fill, dst);
-                } else if (!a.inPlace || mask != 0) {
-                    const pfacmod::u32x4 x = a.inPlace ? *dst : load16(a, cLo);
-                    const pfacmod::u32x4 m = {byteMask(mask & 15u), byteMask((mask >> 4) & 15u), byteMask((mask >> 8) & 15u), byteMask(mask >> 12)};
-                    __builtin_nontemporal_store((x & ~m) | (fill & m), dst);
+        if (active && (!a.inPlace || mask != 0)) {                /* in place, only threads that cover something write */
+            const pfacmod::u32x4 fill = {a.fill4, a.fill4, a.fill4, a.fill4};
+            pfacmod::u32x4 x = fill;
+            if (mask != 0xFFFFu) {                                /* the bytes as they are, blended with the fill */
+                pfacmod::u32x4 src;
+                if (f.whole) {
+                    src = a.inPlace ? *reinterpret_cast<const pfacmod::u32x4 *>(a.out + cLo) : load16(a, cLo);
+                } else {
+                    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+                    for (unsigned int b = 0; b < 16; b++)
+                        if (b < f.nb) w[b >> 2] |= (uint32_t)a.in[cLo + b] << (8 * (b & 3));
+                    src = pfacmod::u32x4{w[0], w[1], w[2], w[3]};
                 }
-            } else {
-                for (unsigned int o = cLo; o < cHi; o++) {
-                    if ((mask >> (o - cLo)) & 1u) a.out[o] = (unsigned char)a.fill4;
-                    else if (!a.inPlace) a.out[o] = a.in[o];
-                }
+                const pfacmod::u32x4 m = {byteMask(mask & 15u), byteMask((mask >> 4) & 15u), byteMask((mask >> 8) & 15u), byteMask(mask >> 12)};
+                x = (src & ~m) | (fill & m);
             }
+            tileStore(a.out, f, x);
         }
         __syncthreads();                                          /* sFirst and the stage are rewritten by the next tile */
     }
@@ -262,27 +238,16 @@ PFAC_status_t PFACX_spansSelect(PFAC_handle_t handle, char *d_scan, size_t size,
         return PFAC_STATUS_INVALID_PARAMETER;
     PFAC_context *c = handle;
 
-    /* the compacted scan with its ordering launches: ids in d_spanStart, positions in d_spanLen, ascending */
-    size_t count = 0;
-    const PFAC_status_t st = compactedScan(handle, d_scan, size, hashed, d_spanStart, d_spanLen, true, &count);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    *h_numSpans = 0;
-    *h_coveredBytes = 0;
-    if (count == 0) return PFAC_STATUS_SUCCESS;
-
+    /* the ordered pairs: ids in d_spanStart, positions in d_spanLen */
     SpanArgs a{};
-    a.ids = d_spanStart;
-    a.pos = d_spanLen;
-    a.count = (unsigned int)count;
-    a.n = (unsigned int)size;
-    a.patternLen = d_patternLen;
-    a.numIds = (unsigned int)(numIds < (size_t)0x7fffffff ? numIds : (size_t)0x7fffffff);
+    const PFAC_status_t st = pairsSelectHead(handle, d_scan, size, hashed, d_patternLen, numIds, d_spanStart, d_spanLen, h_numSpans, h_coveredBytes, a);
+    if (st != PFAC_STATUS_SUCCESS || a.count == 0) return st;
+    const size_t count = a.count;
     const size_t blocks = (count + kSpanBlock - 1) / kSpanBlock;
     const size_t bound = count < (size + 1) / 2 ? count : (size + 1) / 2;
     a.blocks = (unsigned int)blocks;
     a.bound = (unsigned int)bound;
-    ScratchCarver k;
-    for (int pass = 0; pass < 2; pass++) {
+    const PFAC_status_t carved = carveScratch(c->scratch.spans, [&](ScratchCarver &k) {
         a.outStart = k.take<unsigned int>(bound);
         a.outEnd = k.take<unsigned int>(bound);
         a.blockMax = k.take<unsigned int>(blocks);
@@ -290,15 +255,11 @@ PFAC_status_t PFACX_spansSelect(PFAC_handle_t handle, char *d_scan, size_t size,
         a.headCount = k.take<unsigned int>(blocks);
         a.headBase = k.take<unsigned int>(blocks + 1);
         a.value = k.take<unsigned long long>(1, 8);            /* and, behind it, the word `covered` */
-        if (pass == 0) {
-            if (c->scratch.spans.count() < k.bytes && c->scratch.spans.reserve(k.bytes) != PFAC_STATUS_SUCCESS) return PFAC_STATUS_CUDA_ALLOC_FAILED;
-            k = ScratchCarver{c->scratch.spans.get()};
-        }
-    }
+    });
+    if (carved != PFAC_STATUS_SUCCESS) return carved;
     a.covered = reinterpret_cast<unsigned int *>(a.value + 1);
     a.spanStart = d_spanStart;
     a.spanLen = d_spanLen;
-    const HostHandoff counts(c, pfac::kHostSpans);
 
     hipLaunchKernelGGL(pfac_spans_reduce, dim3(a.blocks), dim3(kSpanThreads), 0, 0, a);
     blockScan<OpMax>({{a.blockMax}, {a.blockTop}}, a.blocks, nullptr, a.covered);
@@ -306,14 +267,7 @@ PFAC_status_t PFACX_spansSelect(PFAC_handle_t handle, char *d_scan, size_t size,
     blockScan<OpSum>({{a.headCount}, {a.headBase}}, a.blocks, nullptr, nullptr);
     hipLaunchKernelGGL(pfac_spans_heads<1>, dim3(a.blocks), dim3(kSpanThreads), 0, 0, a);
     hipLaunchKernelGGL(pfac_spans_emit, dim3(gridFor(c, bound)), dim3(kSpanThreads), 0, 0, a);
-    hipLaunchKernelGGL(pfac_spans_finish, dim3(1), dim3(1), 0, 0, a, reinterpret_cast<unsigned long long *>(counts.d_value));
-    unsigned long long v = 0;
-    if (!counts.finish(&v, a.value)) return PFAC_STATUS_INTERNAL_ERROR;
-    const size_t spans = (size_t)(v & 0xFFFFFFFFull), covered = (size_t)(v >> 32);
-    if (spans == 0 || spans > bound || covered < spans || covered > size) return PFAC_STATUS_INTERNAL_ERROR;
-    *h_numSpans = spans;
-    *h_coveredBytes = covered;
-    return PFAC_STATUS_SUCCESS;
+    return pairsSelectTail(c, pfac::kHostSpans, a.headBase + a.blocks, bound, size, a.value, h_numSpans, h_coveredBytes);
 }
 
 PFAC_status_t PFACX_spansRedact(PFAC_handle_t handle, const char *d_input, size_t size, const int *d_spanStart, const int *d_spanLen, size_t numSpans,
@@ -334,7 +288,7 @@ PFAC_status_t PFACX_spansRedact(PFAC_handle_t handle, const char *d_input, size_
     a.misOut = (unsigned int)(reinterpret_cast<uintptr_t>(d_out) & 15u);
     a.inPlace = d_input == d_out ? 1u : 0u;
     if (a.inPlace && numSpans == 0) return PFAC_STATUS_SUCCESS;
-    const size_t tiles = (size + a.misOut + kTile - 1) / kTile, cap = (size_t)gridCap(c, 8) * 4;
+    const size_t tiles = (size + a.misOut + kOutTile - 1) / kOutTile, cap = (size_t)gridCap(c, 8) * 4;
     hipLaunchKernelGGL(pfac_spans_redact, dim3((unsigned int)(tiles < cap ? tiles : cap)), dim3(kSpanThreads), 0, 0, a);
     return hipGetLastError() == hipSuccess ? PFAC_STATUS_SUCCESS : PFAC_STATUS_INTERNAL_ERROR;
 }

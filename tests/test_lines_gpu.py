@@ -448,6 +448,41 @@ def test_gather_clamps_bad_line_arrays(workdir):
         h.destroy()
 
 
+def test_gather_every_misalignment_of_the_output_and_sizes_around_the_tile(workdir):
+    """every (address of d_out) & 15 against texts of 1 byte, around the 16 bytes of a thread and around the 4096 of a tile, outCapacity == the
+    text: the first and the last thread of a text store bytes, not 16 at once, and nothing lands in front of d_out or behind the text"""
+    front, tile = 64, 4096
+    rng = np.random.default_rng(20261018)
+    data = rng.integers(32, 127, size=2 * tile + 64, dtype=np.uint8)
+    d_in = torch.from_numpy(data.copy()).to("cuda:0")
+    h = gpu_handle(pattern_file(workdir, "gather-misaligned", ref.PATS))
+    try:
+        for total in (1, 15, 16, 17, tile - 1, tile, tile + 1, 2 * tile + 5):
+            # a few short lines (one of them empty) around one line sized to hit the total; a line of len bytes is len + 1 bytes of text
+            short = [(40, 3), (9, 0), (21, 7)][:max(0, min(3, (total - 1) // 8))]
+            used = sum(ln + 1 for _, ln in short)
+            lines = short[:1] + [(5, total - used - 1)] + short[1:]
+            start = np.array([s for s, _ in lines], dtype=np.int32)
+            length = np.array([ln for _, ln in lines], dtype=np.int32)
+            expect = ref.gather_py(data.tobytes(), start, length)
+            assert len(expect) == total
+            d_start, d_len = torch.from_numpy(start).to("cuda:0"), torch.from_numpy(length).to("cuda:0")
+            for off in range(16):
+                d_out = torch.full((front + off + total + GUARD,), 0xEE, dtype=torch.uint8, device="cuda:0")
+                assert d_out.data_ptr() % 16 == 0
+                st, got = h.gatherLinesFromDevice(d_in.data_ptr(), data.size, d_start.data_ptr(), d_len.data_ptr(), len(lines),
+                                                  d_out.data_ptr() + front + off, total, check=False)
+                torch.cuda.synchronize()
+                out = d_out.cpu().numpy()
+                what = f"{total} bytes at offset {off}"
+                assert (st, got) == (0, total), f"{what}: status {st}, {got} bytes"
+                assert np.all(out[:front + off] == 0xEE), f"{what}: wrote in front of d_out"
+                assert np.all(out[front + off + total:] == 0xEE), f"{what}: wrote behind the text"
+                assert out[front + off:front + off + total].tobytes() == expect, f"{what}: gathered text differs"
+    finally:
+        h.destroy()
+
+
 def test_example_program_equals_grep(workdir):
     subprocess.run(["make", "-C", os.path.join(ROOT, "examples"), "lines_example"], check=True, stdout=subprocess.PIPE)
     name, pats, data = ref.NOCASE_CASES[0]

@@ -11,6 +11,22 @@ TAIL_MUL, TAIL_MUL2 = 0x9E3779B1, 0x85EBCA77
 LADDER_LAST = 20                   # kLadderLast: the levels every kernel tests; a DEEP ladder (info.filterLadderLast = 60) goes on behind it
 
 
+def level1_model(h, data):
+    """Level 1 alone: the 3-gram test of every position of `data` (zeros behind its end), as a boolean array.  It is also the whole
+    early-out of pfac_scan_tiled (scan_tiled.hip: the word at (product >> 16) & mask3, the bits of the position's first and second
+    byte), whose survivor count per group picks the plain, crowded or dense listing: == prefilter_model(h, data, veto=False)[0]
+    (tests/test_tiled_edges_host.py holds the two together) without the ladder's work."""
+    info = h.info()
+    g3 = h.table(api.PFACX_TABLE_FILTER_GRAM3)
+    u = np.uint64
+    n = data.size
+    d = np.concatenate([data, np.zeros(4, dtype=np.uint8)]).astype(np.uint64)
+    x = d[:n] | (d[1:n + 1] << u(8)) | (d[2:n + 2] << u(16))
+    prod = (x * u(GRAM3_MUL)) & u(0xFFFFFFFF)
+    word = g3[((prod >> u(18)) & u((1 << (info.filterLog2Bits - 5)) - 1)).astype(np.int64)]
+    return (((word >> (x & u(31)).astype(np.uint32)) & (word >> ((x >> u(8)) & u(31)).astype(np.uint32))) & 1).astype(bool)
+
+
 def prefilter_model(h, data, veto=True):
     """(level-1 hits, ladder candidates, positions that are walked): boolean arrays over the positions of `data`.
     veto: as the VETO kernels do it -- the levels behind LADDER_LAST of a deep ladder are tested too and a stop is put to the tail

@@ -47,17 +47,51 @@ def make_handle(pattern_file, perf, tex, variant=api.PFACX_KERNEL_FILTER):
     return h
 
 
-def device_match(h, data, in_offset=0, out_offset=0):
-    """matchFromDevice with poisoned output; optional byte/int offsets to misalign the pointers."""
+def _device_input(data, in_offset, front, behind):
+    """the input in_offset bytes into a device buffer: `front` in every byte before it, `behind` (then zeros) in the 64 after it"""
     n = int(data.size)
-    d_in = torch.zeros(n + in_offset + 64, dtype=torch.uint8, device="cuda:0")
-    d_in[in_offset:in_offset + n] = torch.from_numpy(np.ascontiguousarray(data)).to("cuda:0")
+    host = np.zeros(n + in_offset + 64, dtype=np.uint8)
+    host[:in_offset] = front
+    host[in_offset:in_offset + n] = data
+    host[in_offset + n:in_offset + n + len(behind)] = np.frombuffer(behind, dtype=np.uint8)
+    return torch.from_numpy(host).to("cuda:0")
+
+
+def device_match(h, data, in_offset=0, out_offset=0, front=0, behind=b""):
+    """matchFromDevice with poisoned output; optional byte/int offsets to misalign the pointers.  front / behind: what lies around the
+    input in device memory (bytes that would complete a match if a kernel read them as input)."""
+    n = int(data.size)
+    d_in = _device_input(data, in_offset, front, behind)
     d_out = torch.full((n + out_offset + 64,), -5, dtype=torch.int32, device="cuda:0")
     h.matchFromDevice(d_in.data_ptr() + in_offset, n, d_out.data_ptr() + 4 * out_offset)
     torch.cuda.synchronize()
     out = d_out.cpu().numpy()
     assert np.all(out[:out_offset] == -5) and np.all(out[out_offset + n:] == -5), "wrote outside [0, n)"
     return out[out_offset:out_offset + n]
+
+
+def device_reduce(h, data, in_offset=0, front=0, behind=b""):
+    """matchFromDeviceReduce: (positions, ids) of the pairs.  Both arrays have room for a pair per position and 64 poisoned ints on
+    either side, which stay as they were."""
+    n = int(data.size)
+    d_in = _device_input(data, in_offset, front, behind)
+    d_ids = torch.full((n + 128,), -5, dtype=torch.int32, device="cuda:0")
+    d_pos = torch.full((n + 128,), -5, dtype=torch.int32, device="cuda:0")
+    _, count = h.matchFromDeviceReduce(d_in.data_ptr() + in_offset, n, d_ids.data_ptr() + 256, d_pos.data_ptr() + 256)
+    torch.cuda.synchronize()
+    ids, pos = d_ids.cpu().numpy(), d_pos.cpu().numpy()
+    assert 0 <= count <= n, count
+    for a in (ids, pos):
+        assert np.all(a[:64] == -5) and np.all(a[64 + n:] == -5), "wrote outside the n pairs of the caller's arrays"
+    return pos[64:64 + count], ids[64:64 + count]
+
+
+def assert_pairs(pairs, want, what):
+    """the pairs of a compacted-output call == the non-zero results of the full vector `want`, in position order"""
+    pos, ids = pairs
+    nz = np.flatnonzero(want)
+    if not (pos.size == nz.size and np.array_equal(pos, nz) and np.array_equal(ids, want[nz])):
+        raise AssertionError(f"{what}: {pos.size} pairs, want {nz.size}; first positions {pos[:4].tolist()} want {nz[:4].tolist()}")
 
 
 def assert_same(got, want, what):

@@ -25,6 +25,7 @@ from pfac_amd import api, sharding  # noqa: E402,F401
 from pfac_amd import workloads as wl  # noqa: E402,F401
 from tests.gpu_helpers import (MODES, STAGE, VARIANTS, WALKERS, assert_same, device_match, digest_record, digests, make_handle,  # noqa: E402,F401
                                o_prefix, oracle_match, perf_asserts, run_bench, timed_match)
+from tests.tiled_edges import fuzz_case  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -123,22 +124,8 @@ def test_fuzzed_pattern_sets_over_tiny_alphabets(workdir, seed):
     import os
     from oracle import binding as ob
     from pfac_amd import workloads as wl
-    rng = np.random.Generator(np.random.PCG64(900 + seed))
-    alphabet = [bytes([b]) for b in rng.choice([0x00, 0xFF, 0x41, 0x42, 0x7A, 0x20, 0x0D], size=int(rng.integers(2, 5)), replace=False)]
-    pats = set()
-    base = b"".join(alphabet[int(i)] for i in rng.integers(0, len(alphabet), 48))
-    for cut in rng.integers(1, 48, int(rng.integers(3, 14))):           # prefixes of one long string
-        pats.add(base[:int(cut)])
-    while len(pats) < int(rng.integers(8, 70)):
-        ln = int(rng.integers(1 if seed % 2 else 3, 41))
-        pats.add(b"".join(alphabet[int(i)] for i in rng.integers(0, len(alphabet), ln)))
-    pats = sorted(pats, key=lambda p: (rng.random(), p))               # file order = pattern IDs: shuffled
-    pf = wl.write_pattern_file(os.path.join(workdir, f"fuzz{seed}.pat"), pats)
-    n = int(rng.integers(40_000, 200_000))
-    idx = rng.integers(0, len(alphabet), n)
-    data = np.frombuffer(b"".join(alphabet), dtype=np.uint8)[idx].copy()
-    at = int(rng.integers(0, n - 100))
-    data[at:at + len(base)] = np.frombuffer(base, dtype=np.uint8)
+    pf, data = fuzz_case(workdir, seed)                                 # (tests/tiled_edges.py: test_tiled_edges_gpu.py runs it through the tiled kernel)
+    n = int(data.size)
     o = ob.Oracle(pf, hashed=False)
     want = o.match(data)
     o.close()

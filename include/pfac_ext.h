@@ -16,7 +16,9 @@
  * (PFACX_countFromDevice / ...FromHost, PFACX_countPairsFromDevice,
  * PFACX_countNonzeroFromDevice) and the disjoint leftmost-longest matches
  * with their replacement by a string per pattern (PFACX_matchDisjoint*,
- * PFACX_replaceFromDevice / ...FromHost).
+ * PFACX_replaceFromDevice / ...FromHost), rule sets (PFACX_rules*) and the
+ * occurrences bounded by bytes outside a class: whole words, lines and
+ * fields (PFACX_matchWords*, PFACX_wordsPairsFromDevice).
  */
 #ifndef PFAC_EXT_H_
 #define PFAC_EXT_H_
@@ -672,6 +674,60 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
 PFAC_status_t PFACX_rulesMatchFromHost  (PFACX_rules_t rules, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments,
                                          int *h_firedSeg, int *h_firedRule, size_t capacity, size_t *h_segFirst /* may be NULL */,
                                          size_t *h_numFired);
+
+/* Whole-word and delimiter-bounded matches: the occurrences whose neighbours in the input are not in a byte class -- `grep -w -F -f`, `grep -x`, "the
+ * field of a CSV record equals one of 100 000 keys", term frequencies that do not count `the` inside `other`.
+ *   A CLASS W is a set of byte values, given as 256 bits in `unsigned int cls[8]`: byte b is in W if bit b & 31 of cls[b >> 5] is set.  h_class == NULL:
+ *   the default class [0-9A-Za-z_].  The eight words are HOST memory in every call and are copied.
+ *   Let the input have n bytes.  An occurrence of pattern id at p, of length L = len(id), is BOUNDED if (p == 0 or in[p - 1] is not in W) and (p + L == n
+ *   or in[p + L] is not in W).  This is the test of grep -w; it does not ask whether the pattern's own edge bytes are in W (a pattern "-x-" is bounded
+ *   between two spaces, where a regular expression's \b would refuse it).
+ *   THE WORD LIST (flags 0): for every position p at which some pattern has a bounded occurrence, the pair (the LONGEST such pattern, p); positions
+ *   ascend.  The longest pattern at p may fail the test where a shorter one -- a proper prefix of it -- passes: `foo` and `foobar` over "foo bar" and
+ *   over "foobar".  The list is never longer than the list of PFAC_matchFromDeviceReduce, so it has at most `size` pairs.
+ *   ALL (PFACX_WORDS_ALL): every bounded occurrence; positions ascend, within one position the longest pattern comes first, as in PFACX_matchAll*.  This
+ *   list can be longer than the input: the patterns `a`, `a a`, `a a a`, `a a a a`, `a a a a a` over the 9 bytes "a a a a a" give 15 pairs.  So the
+ *   count is a size_t and truncation follows PFACX_matchAll* exactly: the first `capacity` pairs are written, nothing at or behind `capacity`,
+ *   *h_num_matched is the full count, and the call returns PFACX_STATUS_OUTPUT_TRUNCATED.
+ *   Duplicate lines report under the highest id, as everywhere.  A caseless handle (PFACX_READ_NOCASE) matches the folded set over the folded input;
+ *   THE CLASS IS TESTED ON THE CALLER'S ORIGINAL BYTES, which are never modified: a class with 'a' but without 'A' tells "a" from "A" around a match.
+ *   CONSEQUENCES: an empty class (all zero) bounds everything -- ALL is then exactly the list of PFACX_matchAll*, the word list exactly the list of
+ *   PFAC_matchFromDeviceReduce.  A full class leaves only occurrences with p == 0 and p + L == n.  The class "every byte but '\n'" is grep -x: the
+ *   occurrence is a whole line, with or without a last newline.  The class "every byte but ',' and '\n'" gives whole CSV fields.
+ *   PFACX_countPairsFromDevice(..., PFACX_COUNT_LONGEST) over the ids of the ALL list gives whole-word term frequencies.
+ * PFACX_matchWordsFromDevice / ...FromHost: capacity = entries of each array, >= size (smaller: PFAC_STATUS_INVALID_PARAMETER): as in PFACX_matchAll*
+ * the caller's arrays take the scan's unordered list before the result is written, so entries below `size` may be overwritten beyond the count.
+ * size >= 2^31, an unknown flag bit, or a null pointer other than h_class: PFAC_STATUS_INVALID_PARAMETER.  No pattern set:
+ * PFAC_STATUS_PATTERNS_NOT_READY.  size == 0: success, 0 pairs, nothing touched.  A device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.  All
+ * three calls are synchronous (the count comes to the host) and take the handle's lock.  The device form runs on whatever kernel variant, walker, perf
+ * mode and texture mode the handle selects.  The host form follows PFAC_setPlatform like PFACX_countFromHost: the CPU platforms, host-only handles
+ * included, use the CPU matcher and a host loop over temporaries of 8 bytes per input byte; the GPU platform uses the pipelined pairs path and the
+ * same loop.
+ * PFACX_wordsPairsFromDevice: the same lists from a LONGEST list the caller already has -- the pairs of PFAC_matchFromDeviceReduce, or of
+ * PFACX_matchBatchFromDeviceReduce, whose positions are relative to the buffer -- over the same d_input; it runs no second scan.  THE LIST MUST BE A
+ * LONGEST LIST, one pair per position, ascending (the all-match list would report every chain again from each of its members).  The pair arrays are
+ * DEVICE memory and the caller's contract, like the token arrays of PFACX_replaceFromDevice: an id outside [1, F] is ignored, a position outside
+ * [0, size) too, a chain member whose [pos, pos + len) does not lie inside [0, size] is not kept, and nothing outside the buffers is ever read or
+ * written.  `capacity` is free; with capacity == 0 the output arrays may be null: the count query.  Output arrays that overlap the input pair arrays:
+ * PFAC_STATUS_INVALID_PARAMETER; numPairs >= 2^31 too.  numPairs == 0: success, 0 pairs.
+ * OUT OF SCOPE: the pairs of streams and flow sets (negative positions, carried bytes that are no longer in the caller's buffer) and per-segment
+ * boundaries of a batch -- the byte in front of a segment's first byte is its neighbour like any other; a caller who wants segment ends to bound puts a
+ * byte outside W between the segments.
+ * MEMORY of the device forms: grow-only handle scratch, deviceScratchBytes of PFACX_getInfo, freed by PFACX_trim.  Both: 8 (B + 1) bytes rounded up to
+ * 256 with B = (P + 255) / 256 blocks for P longest pairs (never more than eight blocks per compute unit), and 4 (F + 1) bytes of pattern lengths
+ * (shared with the batch calls); a set in which one pattern is a prefix of another also 8 (F + 1) bytes of {prefix, chain length} table (shared with
+ * PFACX_matchAll* and PFACX_count*).  PFACX_matchWordsFromDevice: also the ordered pair list, exactly the pair scratch a PFACX_matchAll* call
+ * over the same input allocates (8 bytes per pair the scan's ordering has room for).
+ * COST: the compacted scan WITH its ordering launches, then two passes over the pairs that read at most 1 + chainLen input bytes per
+ * pair and a one-block scan between them: the extra over PFACX_matchAll* follows the pairs, not the bytes. */
+#define PFACX_WORDS_ALL 1u   /* every bounded occurrence instead of the longest one per position */
+PFAC_status_t PFACX_matchWordsFromDevice(PFAC_handle_t handle, char *d_input, size_t size, const unsigned int *h_class /* 8 words or NULL */,
+                                         unsigned int flags, int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_matchWordsFromHost  (PFAC_handle_t handle, char *h_input, size_t size, const unsigned int *h_class /* 8 words or NULL */,
+                                         unsigned int flags, int *h_ids, int *h_pos, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_wordsPairsFromDevice(PFAC_handle_t handle, const char *d_input, size_t size, const unsigned int *h_class /* 8 words or NULL */,
+                                         unsigned int flags, const int *d_pairIds, const int *d_pairPos, size_t numPairs,
+                                         int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched);
 
 #ifdef __cplusplus
 }

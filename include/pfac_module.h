@@ -212,6 +212,30 @@ typedef struct {
 } PFACX_rulesRun_t;
 PFAC_status_t PFACX_rulesRun(PFAC_handle_t handle, const PFACX_rulesRun_t *run, size_t *h_total);
 
+/* Whole-word and delimiter-bounded matches (no reference counterpart; include/pfac_ext.h: PFACX_matchWords* / PFACX_wordsPairsFromDevice), scan_words.hip.
+ * PFACX_wordsRun: the bounded occurrences of an ordered list of LONGEST pairs.  d_input[0, size), 0 < size < 2^31, are the CALLER's bytes (never the
+ * folded copy of a caseless set: the class is tested on them); d_pairIds / d_pairPos[0, count), count < 2^31: one pair per position, ascending -- the
+ * handle's pair scratch behind PFACX_allReduce, or a caller's list: an id outside [1, numIds] or a position outside [0, size) is a pair that gives
+ * nothing, a chain member that does not lie inside the input is not kept.  d_table: pfac::Int2 {prefixPattern, chainLen} by id, numIds + 1 entries, or
+ * null: every chain is the pair itself; d_patternLen: the pattern lengths by id, numIds + 1 entries.  cls: the class, bit b & 31 of cls[b >> 5] for
+ * byte b.  all == 0: per pair the longest bounded member of its chain; else every bounded member, longest first.  Output: (id, position) into d_ids /
+ * d_pos, nothing at or beyond `capacity` (0: both may be null, and nothing is written); *h_total = the full length of the list.  The output arrays must
+ * not overlap the pair arrays (the caller checks).  Synchronous. */
+typedef struct {
+    const char *d_input;
+    size_t size;
+    const int *d_pairIds, *d_pairPos;
+    size_t count;
+    const void *d_table;
+    const int *d_patternLen;
+    size_t numIds;
+    unsigned int cls[8];
+    unsigned int all;
+    int *d_ids, *d_pos;
+    size_t capacity;
+} PFACX_wordsRun_t;
+PFAC_status_t PFACX_wordsRun(PFAC_handle_t handle, const PFACX_wordsRun_t *run, size_t *h_total);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -225,7 +249,7 @@ PFAC_status_t PFACX_rulesRun(PFAC_handle_t handle, const PFACX_rulesRun_t *run, 
     X(spans_select_ptr, PFACX_spansSelect) X(spans_redact_ptr, PFACX_spansRedact) \
     X(count_pairs_ptr, PFACX_countPairs) X(count_nonzero_ptr, PFACX_countNonzero) \
     X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun) \
-    X(rules_run_ptr, PFACX_rulesRun)
+    X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

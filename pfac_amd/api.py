@@ -30,6 +30,8 @@ PFACX_READ_STRICT, PFACX_READ_STRIP_CR, PFACX_READ_NOCASE = 1, 2, 8
 PFACX_LINES_INVERT = 1                          # pfac_ext.h: PFACX_matchLines* select the lines that do NOT match
 PFACX_COUNT_LONGEST = 1                         # pfac_ext.h: PFACX_count* count one pattern per position, the longest
 PFACX_COUNT_ACCUMULATE = 2                      # ... add to counts[] instead of overwriting it
+PFACX_WORDS_ALL = 1                             # pfac_ext.h: PFACX_matchWords* report every bounded occurrence, not the longest per position
+PFACX_WORDS_BLOCK = 256                         # scan_words.hip: kWordsBlock, the pairs one block of the boundary passes takes (never more than eight blocks per CU)
 PFACX_DISJOINT_BLOCK = 512                      # scan_disjoint.hip: kDisjointBlock, the pairs one block of the selection takes
 PFACX_REPLACE_TILE = 4096                       # scan_disjoint.hip: kReplaceTile, the output bytes of one tile of the replacement
 PFACX_RULES_WINDOW = 8192                       # scan_rules.hip: kRulesWindow, the rules whose masks a block keeps in LDS at a time
@@ -120,6 +122,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_countFromDevice", "PFACX_countFromHost", "PFACX_countPairsFromDevice", "PFACX_countNonzeroFromDevice",
     "PFACX_matchDisjointFromDevice", "PFACX_matchDisjointFromHost", "PFACX_replaceFromDevice", "PFACX_replaceFromHost",
     "PFACX_rulesOpen", "PFACX_rulesClose", "PFACX_rulesMatchFromDevice", "PFACX_rulesMatchFromHost",
+    "PFACX_matchWordsFromDevice", "PFACX_matchWordsFromHost", "PFACX_wordsPairsFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -132,6 +135,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_countPairs", "PFACX_countNonzero",
     "PFACX_disjointSelect", "PFACX_replaceRun",
     "PFACX_rulesRun",
+    "PFACX_wordsRun",
 )
 
 
@@ -247,6 +251,14 @@ def load_library() -> C.CDLL:
         rules = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, SZ]
         lib.PFACX_rulesMatchFromDevice.argtypes = rules
         lib.PFACX_rulesMatchFromHost.argtypes = rules
+    if hasattr(lib, "PFACX_matchWordsFromDevice"):
+        SZ = C.POINTER(C.c_size_t)
+        CLS = C.POINTER(C.c_uint)
+        words = [H, C.c_void_p, C.c_size_t, CLS, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, SZ]
+        lib.PFACX_matchWordsFromDevice.argtypes = words
+        lib.PFACX_matchWordsFromHost.argtypes = words
+        lib.PFACX_wordsPairsFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, CLS, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                   C.c_size_t, SZ]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -255,6 +267,28 @@ def load_library() -> C.CDLL:
             fn.restype = C.c_int
     _lib = lib
     return lib
+
+
+def word_class(members=None):
+    """The eight words of a byte class for PFACX_matchWords*: byte b is in the class iff bit b & 31 of word b >> 5 is set.  `members`: bytes (or any
+    iterable of byte values); None: the default class [0-9A-Za-z_]."""
+    if members is None:
+        members = b"0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz_"
+    words = [0] * 8
+    for b in bytes(members):
+        words[b >> 5] |= 1 << (b & 31)
+    return (C.c_uint * 8)(*words)
+
+
+def word_class_except(excluded):
+    """... of every byte but `excluded`: word_class_except(b"\n") is grep -x, word_class_except(b",\n") whole CSV fields."""
+    return word_class(bytes(set(range(256)) - set(bytes(excluded))))
+
+
+def _class_arg(cls):
+    if cls is None or isinstance(cls, C.Array):
+        return cls
+    return word_class(cls)
 
 
 _libc = C.CDLL(None)
@@ -619,6 +653,44 @@ class PFAC:
         st = self._lib.PFACX_replaceFromHost(self._h, h_input, size, h_ids, h_pos, num_tokens, h_repl_off, num_off, h_repl_bytes, repl_bytes,
                                              h_out, out_capacity, C.byref(n))
         return self._ret(st, "PFACX_replaceFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    # -- whole-word and delimiter-bounded matches (include/pfac_ext.h: PFACX_matchWords*) ----------------
+    def matchWordsFromDevice(self, d_input: int, size: int, cls, flags: int, d_ids: int, d_pos: int, capacity: int, check: bool = True):
+        """``PFACX_matchWordsFromDevice`` -> (status, full length of the list); `cls`: word_class(...), bytes, or None for [0-9A-Za-z_].
+        OUTPUT_TRUNCATED is returned, not raised."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_matchWordsFromDevice(self._h, d_input, size, _class_arg(cls), flags, d_ids, d_pos, capacity, C.byref(n))
+        return self._ret(st, "PFACX_matchWordsFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def matchWordsFromHost(self, h_input: int, size: int, cls, flags: int, h_ids: int, h_pos: int, capacity: int, check: bool = True):
+        """``PFACX_matchWordsFromHost`` -> (status, full length of the list); follows PFAC_setPlatform.  OUTPUT_TRUNCATED is returned, not raised."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_matchWordsFromHost(self._h, h_input, size, _class_arg(cls), flags, h_ids, h_pos, capacity, C.byref(n))
+        return self._ret(st, "PFACX_matchWordsFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def wordsPairsFromDevice(self, d_input: int, size: int, cls, flags: int, d_pair_ids, d_pair_pos, num_pairs: int, d_ids, d_pos, capacity: int,
+                             check: bool = True):
+        """``PFACX_wordsPairsFromDevice`` -> (status, full length of the list): the bounded occurrences of a LONGEST pair list the caller
+        already has.  OUTPUT_TRUNCATED is returned, not raised."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_wordsPairsFromDevice(self._h, d_input, size, _class_arg(cls), flags, d_pair_ids, d_pair_pos, num_pairs, d_ids, d_pos,
+                                                  capacity, C.byref(n))
+        return self._ret(st, "PFACX_wordsPairsFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def match_words_host_array(self, data, cls=None, all_matches: bool = False, capacity=None):
+        """matchWordsFromHost over a numpy array -> (pos, ids), ascending position.  capacity=None: size * maxMatchesPerPosition (never
+        truncates); a smaller capacity that truncates raises PFACError."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if data.size == 0:
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+        cap = data.size * max(1, int(self.info().maxMatchesPerPosition)) if capacity is None else int(capacity)
+        ids = np.full(cap, -7, dtype=np.int32)
+        pos = np.full(cap, -7, dtype=np.int32)
+        st, n = self.matchWordsFromHost(data.ctypes.data, data.size, cls, PFACX_WORDS_ALL if all_matches else 0, ids.ctypes.data, pos.ctypes.data, cap,
+                                        check=False)
+        self._ret(st, "PFACX_matchWordsFromHost", True)
+        return pos[:n].copy(), ids[:n].copy()
 
     # -- input that arrives in pieces (include/pfac_ext.h: PFACX_stream*) ----------------
     def streamOpen(self, check: bool = True) -> "Stream":

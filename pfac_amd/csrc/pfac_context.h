@@ -67,7 +67,8 @@ constexpr HostSlot kHostNonzero = {32, 36};       /* the non-zero counts: two 64
 constexpr HostSlot kHostDisjoint = {40, 42};      /* a disjoint call: one 64-bit value, the tokens | the covered bytes << 32 (scan_disjoint.hip, by pfac_pairs_finish) */
 constexpr HostSlot kHostReplace = {44, 46};       /* a replacement: the 64-bit sum of (replacement - match) lengths; the size of the text is the input's plus that (scan_disjoint.hip) */
 constexpr HostSlot kHostRules = {48, 50};         /* a rules call: the 64-bit length of its fired list (scan_rules.hip, by pfac_array_scan) */
-constexpr int kHostWords = 52;
+constexpr HostSlot kHostWordList = {52, 54};      /* a words call: the 64-bit length of its list (scan_words.hip, by pfac_array_scan) */
+constexpr int kHostWords = 56;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -437,12 +438,16 @@ struct DeviceScratch {
      * 8 (numSegments + 1) bytes rounded up to 256; the pair list is allPairs, the first pair of each segment allSegFirst, the prefix table allTable:
      * shared with the all-match calls.  The tables of a rule set are state of that set, not scratch (rules_api.cpp) */
     DeviceBuffer<char> rules;
+    /* the words calls (PFACX_matchWords* / PFACX_wordsPairsFromDevice, scan_words.hip): the 64-bit list offsets of the blocks of its pair passes:
+     * 8 (blocks + 1) bytes rounded up to 256, a block per 256 pairs, eight per compute unit at most; the pair list of PFACX_matchWordsFromDevice is
+     * allPairs, the prefix table allTable, the pattern lengths patternLen: shared with the all-match and the batch calls */
+    DeviceBuffer<char> words;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines);
-        f(spans); f(count); f(disjoint); f(rules);
+        f(spans); f(count); f(disjoint); f(rules); f(words);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }

@@ -1,6 +1,6 @@
 /*
  * scan_passes.h -- what the passes around the scan share (scan_module.hip with scan_order.inc, scan_batch.hip, scan_all.hip, scan_fold.hip,
- * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip, scan_disjoint.hip, scan_rules.hip; the product kernels' units do
+ * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip, scan_disjoint.hip, scan_rules.hip, scan_words.hip; the product kernels' units do
  * not include it): launch sizes, the layout of a call's scratch and its carving out of a buffer of the handle (ScratchCarver, carveScratch), the
  * compacted scan as a pass runs it, the hand-off of a call's result to the host through mapped memory (HostHandoff; storeToHost on the device),
  * the device fold byte, the clamp of a caller's (start, len), 16 bytes out of two aligned blocks (funnel, loadBytes16), the frame of an output
@@ -463,7 +463,7 @@ inline void blockScan(const ScanColumns &s, unsigned int n, unsigned int *hostTo
     hipLaunchKernelGGL((pfac_block_scan<Op0, Op1, COLS>), dim3((n + kScanBlock - 1) / kScanBlock), dim3(1024), 0, 0, s, n, hostTotal, zero);
 }
 
-/* ------------------------------------------------------------------ offsets of items with 64-bit values (the gather's lines, the replacement's tokens, the expansion's pairs) */
+/* ------------------------------------------------------------------ offsets of items with 64-bit values (the gather's lines, the replacement's tokens, the expansion's pairs, the bounded members of a words call) */
 
 /* the cut of `count` items for the two passes below: blocks of `threads` threads, eight per compute unit at most; per: the items of a block, a
  * multiple of `threads` (no items: no blocks) */

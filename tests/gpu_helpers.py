@@ -1,5 +1,6 @@
 """Helpers shared by the GPU test files (tests/test_full_result.py, test_reduce.py, test_host_paths.py, test_hostile.py,
-test_kernel_variants.py, test_full_size_digests.py, test_multi_gpu.py): handles in every table mode and kernel variant, poisoned
+test_kernel_variants.py, test_full_size_digests.py, test_multi_gpu.py, test_tiled_edges_gpu.py, test_filter_edges_gpu.py with its fixtures
+tests/filter_edges.py, checked on the host by test_filter_edges_host.py): handles in every table mode and kernel variant, poisoned
 device buffers, the committed reference digests, event-timed launches.  Test infrastructure only."""
 import json
 import os

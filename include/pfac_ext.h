@@ -663,10 +663,40 @@ PFAC_status_t PFACX_replaceFromHost  (PFAC_handle_t handle, const char *h_input,
  * length} table (8 (F + 1) bytes), the pattern lengths (4 (F + 1) bytes) and the fix-up's scratch of PFACX_matchBatchFromDeviceReduce.  Nothing is
  * sized by segments x rules.
  * COST: the ordered compacted batch scan, then two passes over the pairs whose work follows the pairs times the memberships of the
- * patterns on their prefix chains. */
+ * patterns on their prefix chains.
+ *
+ * CONDITIONED RULE SETS (PFACX_rulesOpenEx): a rule's member is a pattern id with a polarity and a position window -- Snort's
+ * content:!"x", offset and depth; "starts with ERROR, contains payment, does not contain retry".  Rule r is the members h_members[h_ruleOff[r],
+ * h_ruleOff[r + 1]).  The result is an ordinary PFACX_rules_t: the match calls, PFACX_rulesClose, the fired list, segFirst, capacity, truncation, the
+ * count query, offsets, the generation check, PFAC_destroy, PFACX_trim, the lock and the caseless fold are exactly as above.
+ *   An OCCURRENCE is as above: pattern id at segment-relative start s, of length L, wholly inside a segment of n bytes; a proper prefix of the
+ *   longest pattern at a position counts.
+ *   The occurrence SATISFIES THE MEMBER'S WINDOW if, with a = s -- or a = n - s - L with PFACX_RULE_FROM_END --, a >= offset and (depth == 0 or
+ *   a + L <= offset + depth); evaluated without wrap-around (offset = depth = 0xFFFFFFFF satisfies nothing).  offset 0, depth L: startswith; the same
+ *   with PFACX_RULE_FROM_END: endswith; Snort's offset:o; depth:d maps directly; {id, 0, 0, 0} is every occurrence.
+ *   A positive member HOLDS if some occurrence of its pattern satisfies its window; a PFACX_RULE_NOT member holds if none does.  The rule FIRES on
+ *   a segment if every member holds.  The test is made for every pattern on a prefix chain by itself: over "GET /admin" the member {GET, depth 3}
+ *   holds although the longest pattern at 0, `GET /admin`, fails that window.
+ *   Ids are resolved as above (duplicate lines: the reported id); members equal in (resolved id, flags, offset, depth) count once; the same id with
+ *   another window or polarity is another member; a rule that contradicts itself never fires.
+ * PFAC_STATUS_INVALID_PARAMETER: everything PFACX_rulesOpen refuses (1 to 32 distinct MEMBERS after resolution), a flag bit other than the two
+ * below, a rule without a positive member (it would fire on segments in which nothing matches, which the pass never visits).
+ * A set whose members are all {id, 0, 0, 0} gives the list of PFACX_rulesOpen over the same ids on every input.
+ * Device offsets are clamped to [0, size] before they become a segment's bounds; a pair whose position relative to them is negative, or whose
+ * pattern ends behind them, satisfies nothing; no input byte is read for the test (wrong offsets: a wrong list, never an access outside the buffers).
+ * MEMORY: a conditioned set adds 8 bytes per member after resolution to its device tables: 4 (F + 2) + 4 I + 4 R + 8 I bytes, four allocations; a
+ * set opened by PFACX_rulesOpen allocates nothing new.  A device call of a conditioned set stages the pattern lengths (4 (F + 1) bytes of handle
+ * scratch) also when d_offsets is NULL.  The host form of a conditioned set keeps 8 bytes per input byte instead of 4.
+ * OUT OF SCOPE: distance / within (conditions between the positions of two members), rules of negated members only, minimum counts, more than 32
+ * members, rules over streams or flows. */
+#define PFACX_RULE_NOT      1u   /* the member holds if NO occurrence satisfies its window (content:!"...") */
+#define PFACX_RULE_FROM_END 2u   /* the window is measured from the segment's end instead of its start */
+typedef struct { int pattern; unsigned int flags, offset, depth; } PFACX_rule_member_t;   /* depth 0: no upper bound */
 typedef struct PFACX_rules_s *PFACX_rules_t;
 PFAC_status_t PFACX_rulesOpen (PFAC_handle_t handle, const int *h_ruleOff /* numRules + 1 */, const int *h_rulePatterns,
                                size_t numRules, PFACX_rules_t *rules);
+PFAC_status_t PFACX_rulesOpenEx(PFAC_handle_t handle, const int *h_ruleOff /* numRules + 1 */, const PFACX_rule_member_t *h_members,
+                                size_t numRules, PFACX_rules_t *rules);
 PFAC_status_t PFACX_rulesClose(PFACX_rules_t rules);
 PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
                                          int *d_firedSeg, int *d_firedRule, size_t capacity, size_t *d_segFirst /* numSegments + 1, may be NULL */,

@@ -195,7 +195,12 @@ PFAC_status_t PFACX_replaceRun(PFAC_handle_t handle, const char *d_input, size_t
  * d_table: pfac::Int2 {prefixPattern, chainLen} by id, numIds + 1 entries.  The rule set: d_memberOff[numIds + 2], the memberships of pattern id
  * at d_member[d_memberOff[id], d_memberOff[id + 1]) as rule << 5 | bit, ascending rule; d_need[numRules], the full mask of each rule; 0 < numRules <
  * 2^24.  Output: the pairs in ascending (segment, rule) order into d_firedSeg / d_firedRule, nothing at or beyond `capacity` (0: both may be null);
- * d_segFirst (numSegments + 1 size_t, or null) indexes the whole list; *h_total = its full length.  0 < numSegments < 2^31.  Synchronous. */
+ * d_segFirst (numSegments + 1 size_t, or null) indexes the whole list; *h_total = its full length.  0 < numSegments < 2^31.  Synchronous.
+ * A CONDITIONED set (PFACX_rulesOpenEx) gives d_memberCond, indexed like d_member: {lo, hi} per membership -- lo the window's offset, hi bits 0 .. 30
+ * its end offset + depth saturated to 2^31 - 1 (no upper bound: 2^31 - 1), bit 31 PFACX_RULE_FROM_END -- and with it d_pairPos[0, count), the pairs'
+ * positions in the buffer, d_patternLen (the pattern lengths by id, numIds + 1 entries), `size` and d_offsets (numSegments + 1 size_t, clamped to
+ * [0, size] where read; null: one segment [0, size)).  A membership's bit is set only by an occurrence that lies inside its segment and satisfies the
+ * window; d_need holds the positive bits only.  d_memberCond == null: a plain set, none of the five is read. */
 typedef struct {
     const int *d_pairIds;
     size_t count;
@@ -209,6 +214,11 @@ typedef struct {
     int *d_firedSeg, *d_firedRule;
     size_t capacity;
     size_t *d_segFirst;
+    const int *d_pairPos;
+    const size_t *d_offsets;
+    size_t size;
+    const int *d_patternLen;
+    const unsigned int *d_memberCond;
 } PFACX_rulesRun_t;
 PFAC_status_t PFACX_rulesRun(PFAC_handle_t handle, const PFACX_rulesRun_t *run, size_t *h_total);
 

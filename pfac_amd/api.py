@@ -36,6 +36,9 @@ PFACX_DISJOINT_BLOCK = 512                      # scan_disjoint.hip: kDisjointBl
 PFACX_REPLACE_TILE = 4096                       # scan_disjoint.hip: kReplaceTile, the output bytes of one tile of the replacement
 PFACX_RULES_WINDOW = 8192                       # scan_rules.hip: kRulesWindow, the rules whose masks a block keeps in LDS at a time
 PFACX_RULES_TOUCHED = 1024                      # scan_rules.hip: kRulesTouched, the touched-list length; a segment that touches more rules of a window sweeps the whole table
+PFACX_RULE_NOT = 1                              # PFACX_rule_member_t.flags: the member holds if NO occurrence satisfies its window
+PFACX_RULE_FROM_END = 2                         # the window is measured from the segment's end
+RULE_MEMBER_FIELDS = [("pattern", "<i4"), ("flags", "<u4"), ("offset", "<u4"), ("depth", "<u4")]     # PFACX_rule_member_t as a numpy structured dtype: rule_member_dtype()
 PFACX_RULES_BLOCK_PAIRS = 256                   # scan_rules.hip: kRulesBlockPairs, the pairs a block takes from a segment in one go
 PFACX_COUNT_LDS_DIRECT = 16384                  # scan_count.hip: kCountDirect -- sets with F + 1 <= this count into a counter per id in LDS, larger ones into a tagged cache
 (PFACX_TABLE_DENSE, PFACX_TABLE_HASH_ROWPTR, PFACX_TABLE_HASH_VALPTR, PFACX_TABLE_INITIAL_ROW,
@@ -121,7 +124,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_matchSpansFromDevice", "PFACX_matchSpansFromHost", "PFACX_redactSpansFromDevice",
     "PFACX_countFromDevice", "PFACX_countFromHost", "PFACX_countPairsFromDevice", "PFACX_countNonzeroFromDevice",
     "PFACX_matchDisjointFromDevice", "PFACX_matchDisjointFromHost", "PFACX_replaceFromDevice", "PFACX_replaceFromHost",
-    "PFACX_rulesOpen", "PFACX_rulesClose", "PFACX_rulesMatchFromDevice", "PFACX_rulesMatchFromHost",
+    "PFACX_rulesOpen", "PFACX_rulesOpenEx", "PFACX_rulesClose", "PFACX_rulesMatchFromDevice", "PFACX_rulesMatchFromHost",
     "PFACX_matchWordsFromDevice", "PFACX_matchWordsFromHost", "PFACX_wordsPairsFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
@@ -247,6 +250,8 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "PFACX_rulesOpen"):
         SZ = C.POINTER(C.c_size_t)
         lib.PFACX_rulesOpen.argtypes = [H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        if hasattr(lib, "PFACX_rulesOpenEx"):
+            lib.PFACX_rulesOpenEx.argtypes = [H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         lib.PFACX_rulesClose.argtypes = [C.c_void_p]
         rules = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, SZ]
         lib.PFACX_rulesMatchFromDevice.argtypes = rules
@@ -721,6 +726,21 @@ class PFAC:
         self._ret(st, "PFACX_rulesOpen", check)
         return Rules(self, s, max(0, off.size - 1), st)
 
+    def rulesOpenEx(self, rule_off, members, check: bool = True) -> "Rules":
+        """``PFACX_rulesOpenEx`` -> a :class:`Rules` set whose members carry a polarity and a position window: rule r is
+        ``members[rule_off[r]:rule_off[r + 1]]``, an array of :func:`rule_member_dtype` (or a sequence of ``(pattern, flags, offset, depth)``
+        tuples); the arrays are copied."""
+        import numpy as np
+        off = np.ascontiguousarray(rule_off, dtype=np.int32)
+        if not isinstance(members, np.ndarray):
+            members = [tuple(m) for m in members]
+        mem = np.ascontiguousarray(np.asarray(members, dtype=rule_member_dtype()))
+        buf = mem if mem.size else np.zeros(1, dtype=rule_member_dtype())
+        s = C.c_void_p()
+        st = self._lib.PFACX_rulesOpenEx(self._h, off.ctypes.data if off.size else None, buf.ctypes.data, max(0, off.size - 1), C.byref(s))
+        self._ret(st, "PFACX_rulesOpenEx", check)
+        return Rules(self, s, max(0, off.size - 1), st)
+
     # -- numpy conveniences over matchFromHost (still the C ABI underneath) ----------
     def match_host_array(self, data):
         import numpy as np
@@ -921,6 +941,12 @@ class Flows:
         flb = fl if fl.size else np.zeros(1, dtype=np.uint32)
         st, n = self.flush(flb.ctypes.data, fl.size, ids.ctypes.data, pos.ctypes.data, cap, first.ctypes.data, check=check)
         return st, ids[:n].copy(), pos[:n].copy(), first
+
+
+def rule_member_dtype():
+    """``PFACX_rule_member_t`` as a numpy structured dtype: pattern (int32), flags, offset, depth (uint32); 16 bytes, no padding."""
+    import numpy as np
+    return np.dtype(RULE_MEMBER_FIELDS)
 
 
 class Rules:

@@ -10,6 +10,12 @@
  * PFACX_matchBatchFromDeviceReduce behind it, and PFACX_rulesRun (scan_rules.hip) over the pairs.  The host form takes the longest pairs of every
  * segment -- the CPU platforms through hostLongestPairs, segment by segment; the GPU platform through the pipelined batch path -- and keeps one
  * mask per touched rule in a loop of its own.
+ *
+ * PFACX_rulesOpenEx is the same open over members {pattern, flags, offset, depth}: what is made distinct and numbered is the member,
+ * need[rule] keeps the bits of the positive members only (a bit a negated member sets makes mask != need), and memberCond[], indexed like member[],
+ * holds each membership's window.  PFACX_rulesOpen is its unconditioned case and leaves memberCond empty: a plain set, which runs what it always has.
+ * For a conditioned set both forms keep the pairs' positions and OR a membership's bit only where the pattern on the chain, by itself, lies inside
+ * the segment and satisfies the window (windowHolds here, pfac_rules_pass<EMIT, true> on the device); no input byte is read for it.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -32,13 +38,17 @@ struct PFACX_rules_s {
     size_t numIds = 0;                        /* F of the pattern set it was opened on */
     std::vector<int> memberOff;               /* [F + 2] */
     std::vector<unsigned int> member;         /* rule << 5 | bit, ascending rule within a pattern */
-    std::vector<unsigned int> need;           /* [numRules] */
+    std::vector<unsigned int> need;           /* [numRules]: the bits of the positive members */
+    /* a conditioned set (PFACX_rulesOpenEx): {lo, hi} per membership, indexed like member[] (2 j, 2 j + 1) -- lo the window's offset, hi its end
+     * offset + depth saturated to kNoEnd (no upper bound: kNoEnd), bit 31 PFACX_RULE_FROM_END.  Empty: a plain set, every occurrence sets its bit */
+    std::vector<unsigned int> memberCond;
     /* the same on the device, uploaded by the first device call: state of the set (deviceTableBytes), freed by PFACX_rulesClose */
     pfac::DeviceBuffer<int> d_memberOff;
-    pfac::DeviceBuffer<unsigned int> d_member, d_need;
+    pfac::DeviceBuffer<unsigned int> d_member, d_need, d_memberCond;
 
-    void releaseDevice() { d_memberOff.release(); d_member.release(); d_need.release(); }
-    size_t deviceBytes() const { return d_memberOff.bytes() + d_member.bytes() + d_need.bytes(); }
+    bool conditioned() const { return !memberCond.empty(); }
+    void releaseDevice() { d_memberOff.release(); d_member.release(); d_need.release(); d_memberCond.release(); }
+    size_t deviceBytes() const { return d_memberOff.bytes() + d_member.bytes() + d_need.bytes() + d_memberCond.bytes(); }
 };
 
 namespace pfac_internal {
@@ -66,8 +76,36 @@ namespace {
 
 constexpr size_t kMaxRules = size_t(1) << 24, kMaxRulePatterns = 32, kTwoGiB = size_t(1) << 31;
 
-/* The rules inverted into s (the caller holds c->lock; the arguments are checked for null).  false: a rule set the contract refuses */
-bool invertRules(const pfac::Automaton &fa, const int *ruleOff, const int *rulePatterns, size_t numRules, PFACX_rules_s *s)
+constexpr unsigned int kNoEnd = 0x7FFFFFFFu, kFromEnd = 0x80000000u;      /* memberCond's hi: no occurrence ends behind 2^31 - 1; the direction */
+
+/* a member as the tables keep it: ordered and compared by (resolved id, flags, offset, depth) */
+struct Member {
+    int id;
+    unsigned int flags, offset, depth;
+    bool operator<(const Member &o) const
+    {
+        if (id != o.id) return id < o.id;
+        if (flags != o.flags) return flags < o.flags;
+        return offset != o.offset ? offset < o.offset : depth < o.depth;
+    }
+    bool operator==(const Member &o) const { return id == o.id && flags == o.flags && offset == o.offset && depth == o.depth; }
+};
+
+/* Does the occurrence at segment-relative s, of length len, in a segment of n bytes satisfy the window {lo, hi} of memberCond?  The test of
+ * scan_rules.hip: an occurrence that does not lie inside the segment satisfies nothing, so a + len <= n < 2^31 and nothing wraps */
+inline bool windowHolds(long long s, long long len, long long n, unsigned int lo, unsigned int hi)
+{
+    const long long tail = n - s - len;
+    if (s < 0 || tail < 0) return false;
+    const long long a = (hi & kFromEnd) ? tail : s;
+    return a >= (long long)lo && a + len <= (long long)(hi & kNoEnd);
+}
+
+/* The rules inverted into s (the caller holds c->lock; the arguments are checked for null); memberAt(j): member j of the caller's array.
+ * conditioned: windows and polarity are kept (PFACX_rulesOpenEx); else every member is {id, 0, 0, 0} and the set is plain.  false: a rule set the
+ * contract refuses */
+template <typename MemberAt>
+bool invertRules(const pfac::Automaton &fa, const int *ruleOff, MemberAt memberAt, size_t numRules, bool conditioned, PFACX_rules_s *s)
 {
     const size_t F = (size_t)fa.numPatterns;
     if (ruleOff[0] != 0) return false;
@@ -77,12 +115,15 @@ bool invertRules(const pfac::Automaton &fa, const int *ruleOff, const int *ruleP
     auto bytesOf = [&](size_t id) {
         return std::string(reinterpret_cast<const char *>(fa.file.data()) + fa.patternOff[id], (size_t)fa.patternLen[id]);
     };
-    std::vector<std::vector<int>> rules(numRules);
+    std::vector<std::vector<Member>> rules(numRules);
     for (size_t r = 0; r < numRules; r++) {
-        std::vector<int> &ids = rules[r];
+        std::vector<Member> &ids = rules[r];
+        bool positive = false;
         for (int j = ruleOff[r]; j < ruleOff[r + 1]; j++) {
-            int id = rulePatterns[j];
-            if (id < 1 || (size_t)id > F) return false;
+            const PFACX_rule_member_t given = memberAt((size_t)j);
+            int id = given.pattern;
+            if (id < 1 || (size_t)id > F || (given.flags & ~(PFACX_RULE_NOT | PFACX_RULE_FROM_END))) return false;
+            positive = positive || !(given.flags & PFACX_RULE_NOT);
             if (fa.chainLen[(size_t)id] <= 0) {             /* not in the trie: the lower id of duplicate lines */
                 if (reported.empty())
                     for (size_t q = 1; q <= F; q++)
@@ -91,23 +132,35 @@ bool invertRules(const pfac::Automaton &fa, const int *ruleOff, const int *ruleP
                 if (it == reported.end()) return false;
                 id = it->second;
             }
-            ids.push_back(id);
+            ids.push_back(Member{id, given.flags, given.offset, given.depth});
         }
         std::sort(ids.begin(), ids.end());
         ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-        if (ids.empty() || ids.size() > kMaxRulePatterns) return false;
+        if (ids.empty() || ids.size() > kMaxRulePatterns || !positive) return false;
     }
     s->memberOff.assign(F + 2, 0);
-    for (const std::vector<int> &ids : rules)
-        for (int id : ids) s->memberOff[(size_t)id + 1]++;
+    for (const std::vector<Member> &ids : rules)
+        for (const Member &m : ids) s->memberOff[(size_t)m.id + 1]++;
     for (size_t id = 0; id <= F; id++) s->memberOff[id + 1] += s->memberOff[id];
     s->member.resize((size_t)s->memberOff[F + 1]);
+    s->memberCond.assign(conditioned ? 2 * s->member.size() : 0, 0u);
     s->need.resize(numRules);
     std::vector<int> at(s->memberOff.begin(), s->memberOff.end() - 1);
     for (size_t r = 0; r < numRules; r++) {                 /* ascending r: the memberships of a pattern ascend */
-        const std::vector<int> &ids = rules[r];
-        for (size_t b = 0; b < ids.size(); b++) s->member[(size_t)at[(size_t)ids[b]]++] = (unsigned int)(r << 5 | b);
-        s->need[r] = ids.size() == 32 ? 0xFFFFFFFFu : (1u << ids.size()) - 1u;
+        const std::vector<Member> &ids = rules[r];
+        unsigned int need = 0;
+        for (size_t b = 0; b < ids.size(); b++) {
+            const Member &m = ids[b];
+            const size_t j = (size_t)at[(size_t)m.id]++;
+            s->member[j] = (unsigned int)(r << 5 | b);
+            if (!(m.flags & PFACX_RULE_NOT)) need |= 1u << b;
+            if (conditioned) {
+                const unsigned long long end = m.depth ? (unsigned long long)m.offset + m.depth : kNoEnd;       /* 64-bit: offset + depth does not wrap */
+                s->memberCond[2 * j] = m.offset;
+                s->memberCond[2 * j + 1] = (unsigned int)std::min<unsigned long long>(end, kNoEnd) | ((m.flags & PFACX_RULE_FROM_END) ? kFromEnd : 0u);
+            }
+        }
+        s->need[r] = need;
     }
     s->numRules = numRules;
     s->numIds = F;
@@ -124,24 +177,30 @@ PFAC_status_t checkMatchArgs(PFACX_rules_t rules, const void *input, size_t size
     return PFAC_STATUS_SUCCESS;
 }
 
-/* The fired list of a batch whose longest pairs are known: the ids of segment k at ids[first[k], first[k] + numPairs[k]).  Returns the full length */
-size_t firedOnHost(const pfac::Automaton &fa, const PFACX_rules_s &s, const int *ids, const size_t *first, const int *numPairs, size_t numSegments,
-                   int *firedSeg, int *firedRule, size_t capacity, size_t *segFirst)
+/* The fired list of a batch whose longest pairs are known: the ids of segment k at ids[first[k], first[k] + numPairs[k]), their positions in the
+ * segment at pos[] likewise (read for a conditioned set only: may be null for a plain one); segment k has first[k + 1] - first[k] bytes.  Returns
+ * the full length */
+size_t firedOnHost(const pfac::Automaton &fa, const PFACX_rules_s &s, const int *ids, const int *pos, const size_t *first, const int *numPairs,
+                   size_t numSegments, int *firedSeg, int *firedRule, size_t capacity, size_t *segFirst)
 {
     std::vector<unsigned int> mask(s.numRules, 0u);
     std::vector<unsigned int> touched, fired;
+    const bool cond = s.conditioned();
     size_t total = 0;
     for (size_t k = 0; k < numSegments; k++) {
         if (segFirst) segFirst[k] = total;
         touched.clear();
         fired.clear();
+        const long long n = (long long)(first[k + 1] - first[k]);
         for (int i = 0; i < numPairs[k]; i++) {
             int q = ids[first[k] + (size_t)i];
             if (q < 1 || (size_t)q > s.numIds) continue;
+            const long long at = cond ? pos[first[k] + (size_t)i] : 0;
             const int steps = fa.chainLen[(size_t)q];
             for (int c = 0; c < (steps > 1 ? steps : 1) && q >= 1 && (size_t)q <= s.numIds; c++) {
                 for (int j = s.memberOff[(size_t)q]; j < s.memberOff[(size_t)q + 1]; j++) {
                     const unsigned int m = s.member[(size_t)j], r = m >> 5;
+                    if (cond && !windowHolds(at, fa.patternLen[(size_t)q], n, s.memberCond[2 * (size_t)j], s.memberCond[2 * (size_t)j + 1])) continue;
                     if (mask[r] == 0) touched.push_back(r);
                     mask[r] |= 1u << (m & 31u);
                 }
@@ -169,8 +228,28 @@ PFAC_status_t ensureDeviceTables(PFACX_rules_s *s)
     PFAC_status_t st = s->d_memberOff.upload(s->memberOff.data(), s->memberOff.size());
     if (st == PFAC_STATUS_SUCCESS) st = s->d_member.upload(s->member.data(), s->member.size());
     if (st == PFAC_STATUS_SUCCESS) st = s->d_need.upload(s->need.data(), s->need.size());
+    if (st == PFAC_STATUS_SUCCESS && s->conditioned()) st = s->d_memberCond.upload(s->memberCond.data(), s->memberCond.size());
     if (st != PFAC_STATUS_SUCCESS) s->releaseDevice();
     return st;
+}
+
+/* PFACX_rulesOpen (conditioned == false: memberAt gives {id, 0, 0, 0}) and PFACX_rulesOpenEx behind their null checks */
+template <typename MemberAt>
+PFAC_status_t openRules(PFAC_handle_t handle, const int *h_ruleOff, MemberAt memberAt, size_t numRules, bool conditioned, PFACX_rules_t *rules)
+{
+    if (numRules == 0 || numRules >= kMaxRules) return PFAC_STATUS_INVALID_PARAMETER;
+    PFACX_rules_s *s = new (std::nothrow) PFACX_rules_s();
+    if (!s) return PFAC_STATUS_ALLOC_FAILED;
+    std::lock_guard<std::mutex> guard(handle->lock);
+    if (!handle->isPatternsReady) { delete s; return PFAC_STATUS_PATTERNS_NOT_READY; }
+    try {
+        if (!invertRules(handle->fa, h_ruleOff, memberAt, numRules, conditioned, s)) { delete s; return PFAC_STATUS_INVALID_PARAMETER; }
+        handle->ruleSets.push_back(s);
+    } catch (const std::bad_alloc &) { delete s; return PFAC_STATUS_ALLOC_FAILED; }
+    s->handle = handle;
+    s->generation = handle->setGeneration;
+    *rules = s;
+    return PFAC_STATUS_SUCCESS;
 }
 
 } // namespace
@@ -182,19 +261,17 @@ PFAC_status_t PFACX_rulesOpen(PFAC_handle_t handle, const int *h_ruleOff, const 
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
     if (!rules) return PFAC_STATUS_INVALID_PARAMETER;
     *rules = nullptr;
-    if (!h_ruleOff || !h_rulePatterns || numRules == 0 || numRules >= kMaxRules) return PFAC_STATUS_INVALID_PARAMETER;
-    PFACX_rules_s *s = new (std::nothrow) PFACX_rules_s();
-    if (!s) return PFAC_STATUS_ALLOC_FAILED;
-    std::lock_guard<std::mutex> guard(handle->lock);
-    if (!handle->isPatternsReady) { delete s; return PFAC_STATUS_PATTERNS_NOT_READY; }
-    try {
-        if (!invertRules(handle->fa, h_ruleOff, h_rulePatterns, numRules, s)) { delete s; return PFAC_STATUS_INVALID_PARAMETER; }
-        handle->ruleSets.push_back(s);
-    } catch (const std::bad_alloc &) { delete s; return PFAC_STATUS_ALLOC_FAILED; }
-    s->handle = handle;
-    s->generation = handle->setGeneration;
-    *rules = s;
-    return PFAC_STATUS_SUCCESS;
+    if (!h_ruleOff || !h_rulePatterns) return PFAC_STATUS_INVALID_PARAMETER;
+    return openRules(handle, h_ruleOff, [=](size_t j) { return PFACX_rule_member_t{h_rulePatterns[j], 0u, 0u, 0u}; }, numRules, false, rules);
+}
+
+PFAC_status_t PFACX_rulesOpenEx(PFAC_handle_t handle, const int *h_ruleOff, const PFACX_rule_member_t *h_members, size_t numRules, PFACX_rules_t *rules)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!rules) return PFAC_STATUS_INVALID_PARAMETER;
+    *rules = nullptr;
+    if (!h_ruleOff || !h_members) return PFAC_STATUS_INVALID_PARAMETER;
+    return openRules(handle, h_ruleOff, [=](size_t j) { return h_members[j]; }, numRules, true, rules);
 }
 
 PFAC_status_t PFACX_rulesClose(PFACX_rules_t rules)
@@ -229,7 +306,8 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
     }
     st = ensureDeviceTables(rules);
     if (st == PFAC_STATUS_SUCCESS) st = ensureAllTable(c);
-    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = ensurePatternLen(c);
+    const bool cond = rules->conditioned();
+    if (st == PFAC_STATUS_SUCCESS && (d_offsets || cond)) st = ensurePatternLen(c);      /* the fix-up's, and the window test's */
     if (st == PFAC_STATUS_SUCCESS && d_offsets) st = c->scratch.allSegFirst.reserve(numSegments + 1);
     pfac::DeviceBuffer<int> &pairs = c->scratch.allPairs;
     if (st == PFAC_STATUS_SUCCESS) st = pairs.reserve(2 * size);
@@ -259,6 +337,13 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
     run.d_firedRule = d_firedRule;
     run.capacity = capacity;
     run.d_segFirst = d_segFirst;
+    if (cond) {                                                                 /* the window test: positions, bounds and lengths, no input byte */
+        run.d_pairPos = pos;
+        run.d_offsets = d_offsets;
+        run.size = size;
+        run.d_patternLen = c->scratch.patternLen.get();
+        run.d_memberCond = rules->d_memberCond.get();
+    }
     size_t total = 0;
     st = c->rules_run_ptr(c, &run, &total);
     if (st != PFAC_STATUS_SUCCESS) return st;
@@ -288,14 +373,16 @@ PFAC_status_t PFACX_rulesMatchFromHost(PFACX_rules_t rules, char *h_input, size_
     size_t longest = 0;
     for (size_t k = 0; k < numSegments; k++) longest = std::max(longest, offsets[k + 1] - offsets[k]);
     /* the longest ids of segment k from ids[offsets[k]] on; not initialised: a page nothing writes costs nothing */
-    std::unique_ptr<int[]> ids(new (std::nothrow) int[size]), pos(onGpu ? nullptr : new (std::nothrow) int[longest]);
+    const bool cond = rules->conditioned();                                     /* then every pair keeps its position in its segment, at the index of its id */
+    const size_t numPos = cond ? size : (onGpu ? 0 : longest);
+    std::unique_ptr<int[]> ids(new (std::nothrow) int[size]), pos(numPos ? new (std::nothrow) int[numPos] : nullptr);
     std::vector<int> numPairs;
     try {
         numPairs.assign(numSegments, 0);
     } catch (const std::bad_alloc &) {
         return PFAC_STATUS_ALLOC_FAILED;
     }
-    if (!ids || (!onGpu && !pos)) return PFAC_STATUS_ALLOC_FAILED;
+    if (!ids || (numPos && !pos)) return PFAC_STATUS_ALLOC_FAILED;
     if (onGpu) {
         /* the pipelined batch path: the full result of every segment, compacted in place (pair z of a segment comes from an entry at or behind z) */
         st = matchBatchHostOnGpu(c, h_input, size, offsets, numSegments, ids.get());
@@ -303,7 +390,10 @@ PFAC_status_t PFACX_rulesMatchFromHost(PFACX_rules_t rules, char *h_input, size_
         for (size_t k = 0; k < numSegments; k++) {
             int z = 0;
             for (size_t i = offsets[k]; i < offsets[k + 1]; i++)
-                if (ids[i] > 0) ids[offsets[k] + (size_t)z++] = ids[i];
+                if (ids[i] > 0) {
+                    if (cond) pos[offsets[k] + (size_t)z] = (int)(i - offsets[k]);      /* the pair's index in the full result is its position */
+                    ids[offsets[k] + (size_t)z++] = ids[i];
+                }
             numPairs[k] = z;
         }
     } else {
@@ -311,14 +401,14 @@ PFAC_status_t PFACX_rulesMatchFromHost(PFACX_rules_t rules, char *h_input, size_
         for (size_t k = 0; k < numSegments; k++) {
             const size_t n = offsets[k + 1] - offsets[k];
             if (n == 0) continue;
-            st = hostLongestPairs(c, h_input + offsets[k], n, ids.get() + offsets[k], pos.get(), &numPairs[k]);
+            st = hostLongestPairs(c, h_input + offsets[k], n, ids.get() + offsets[k], pos.get() + (cond ? offsets[k] : 0), &numPairs[k]);
             if (st != PFAC_STATUS_SUCCESS) return st;
         }
     }
     std::shared_lock<std::shared_mutex> tables(c->tablesInUse);
     if (!onGpu && (rules->generation != c->setGeneration || (size_t)c->fa.numPatterns != rules->numIds)) return PFAC_STATUS_INVALID_PARAMETER;   /* another thread has replaced the set meanwhile */
     try {
-        const size_t total = firedOnHost(c->fa, *rules, ids.get(), offsets, numPairs.data(), numSegments, h_firedSeg, h_firedRule, capacity, h_segFirst);
+        const size_t total = firedOnHost(c->fa, *rules, ids.get(), pos.get(), offsets, numPairs.data(), numSegments, h_firedSeg, h_firedRule, capacity, h_segFirst);
         *h_numFired = total;
         return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
     } catch (const std::bad_alloc &) {

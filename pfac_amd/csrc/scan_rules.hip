@@ -27,8 +27,16 @@
  * nextWindow are as the kernel's prologue left them when the segment ends.
  * SCRATCH: 8 (numSegments + 1) bytes rounded up to 256 (DeviceScratch::rules).  LDS of a block: 4 kRulesWindow + kRulesWindow / 8 + 2 kRulesTouched
  * + 48 bytes = 35.05 KiB: four blocks, sixteen waves, on a compute unit's 160 KiB.
- * Plain C++, vector stores and LDS atomics only; the caller's offsets are not read here (scan_batch.hip has clamped them into the first pairs, which
- * are clamped to the pair list again where they are read).
+ * Plain C++, vector stores and LDS atomics only; for a plain set the caller's offsets are not read here (scan_batch.hip has clamped them into the
+ * first pairs, which are clamped to the pair list again where they are read).
+ *
+ * CONDITIONED SETS (PFACX_rulesOpenEx): pfac_rules_pass<EMIT, COND>.  COND == false is the code above and what a plain set launches.
+ * With COND a membership has a window memberCond[j] = {offset, end | direction} and a polarity that lives in need[] alone (the positive bits: mask ==
+ * need says "every positive member, no negated one").  The walk loads the segment's bounds once per segment (the caller's offsets clamped to [0, size];
+ * none: 0 and size), the pair's position once per pair and patternLen[q] once per member of its chain, and ORs a membership's bit only if THAT member
+ * lies inside the segment and satisfies the window -- the longest pattern at a position can fail a window its proper prefix passes.  No input byte is
+ * read.  nextWindow is lowered in front of the test: a later window can hold a rule this pair completes or vetoes.  Windows, the touched list and its
+ * sweep, the bitmap, the emit, pass 2 and the clean state are the same code; a failed test touches nothing.
  */
 #if !defined(__gfx950__) && defined(__HIP_DEVICE_COMPILE__)
 #error "scan_rules.hip is written for gfx950 (CDNA4): wave64"
@@ -65,7 +73,15 @@ struct RulesArgs {
     unsigned long long *segFirst;       /* [numSegments + 1]: pass 1 writes the counts, the scan turns them into the first fired pair of each segment */
     int *firedSeg, *firedRule;
     unsigned long long capacity;
+    /* a conditioned set (COND) only; all null or 0 for a plain one */
+    const int *pairPos;                 /* the pairs' positions in the buffer */
+    const unsigned long long *offsets;  /* [numSegments + 1] bytes, clamped to [0, size] where read; null: one segment [0, size) */
+    unsigned int size;
+    const int *patternLen;              /* [numIds + 1] by id */
+    const uint2 *memberCond;            /* indexed like member: x the window's offset, y its end (bits 0 .. 30, saturated) and kCondFromEnd */
 };
+constexpr unsigned int kCondFromEnd = 0x80000000u, kCondEnd = 0x7FFFFFFFu;
+static_assert(sizeof(size_t) == sizeof(unsigned long long), "the caller's offsets are 64-bit");
 
 /* the first pair of segment k among the `count` pairs */
 __device__ __forceinline__ unsigned int firstPairOf(const RulesArgs &a, unsigned int k)
@@ -74,7 +90,14 @@ __device__ __forceinline__ unsigned int firstPairOf(const RulesArgs &a, unsigned
     return f < 0 ? 0u : ((unsigned int)f < a.count ? (unsigned int)f : a.count);
 }
 
-template <bool EMIT>
+/* segment bound k of a conditioned call: the caller's offset clamped to [0, size], as scan_batch.hip clamps it */
+__device__ __forceinline__ int boundOf(const RulesArgs &a, unsigned int k)
+{
+    const unsigned long long o = a.offsets[k];
+    return (int)(o < a.size ? (unsigned int)o : a.size);
+}
+
+template <bool EMIT, bool COND>
 __global__ __launch_bounds__(kRulesBlockPairs) void pfac_rules_pass(RulesArgs a)
 {
     __shared__ unsigned int mask[kRulesWindow];
@@ -104,6 +127,14 @@ __global__ __launch_bounds__(kRulesBlockPairs) void pfac_rules_pass(RulesArgs a)
             last = firstPairOf(a, k + 1);
             if (last < first) last = first;                                         /* hostile offsets: an empty segment */
         }
+        int segStart = 0, segEnd = 0;                                               /* COND: the segment's bytes [segStart, segEnd) of the buffer (size < 2^31) */
+        if constexpr (COND) {
+            segEnd = (int)a.size;
+            if (a.offsets != nullptr) {
+                segStart = boundOf(a, k);
+                segEnd = boundOf(a, k + 1);
+            }
+        }
         unsigned int fired = 0;                                                     /* of this segment so far: the same in every thread */
         unsigned int window = first < last ? 0u : kNoWindow;
         while (window != kNoWindow) {
@@ -112,7 +143,20 @@ __global__ __launch_bounds__(kRulesBlockPairs) void pfac_rules_pass(RulesArgs a)
                 int q = a.pairIds[i];
                 if (q < 1 || (unsigned int)q > a.numIds) continue;
                 const int steps = a.table[q].y;                                     /* the patterns on the chain, q included: the walk ends there whatever the table says */
+                int at = 0, room = 0;                                               /* COND: the pair's position in its segment, the bytes from there to the segment's end */
+                if constexpr (COND) {
+                    const int p = a.pairPos[i];
+                    at = p - segStart;                                              /* (both in [-2^31, 2^31): no wrap) */
+                    room = segEnd - p;
+                }
                 for (int s = 0; s < (steps > 1 ? steps : 1) && q >= 1 && (unsigned int)q <= a.numIds; s++) {
+                    /* COND: the member of the chain by itself -- the bytes behind it in the segment; negative (or at < 0): it does not lie inside,
+                     * and satisfies nothing.  Inside, at + len <= segEnd - segStart < 2^31: the sums below do not wrap */
+                    int len = 0, tail = -1;
+                    if constexpr (COND) {
+                        len = a.patternLen[q];
+                        tail = at < 0 || len < 0 || len > room ? -1 : room - len;
+                    }
                     unsigned int lo = (unsigned int)a.memberOff[q];
                     const unsigned int end = (unsigned int)a.memberOff[q + 1];
                     if (w0 != 0) {                                                  /* the first membership at or behind the window's first rule */
@@ -125,8 +169,13 @@ __global__ __launch_bounds__(kRulesBlockPairs) void pfac_rules_pass(RulesArgs a)
                     for (; lo < end; lo++) {
                         const unsigned int m = a.member[lo], r = (m >> 5) - w0;
                         if (r >= kRulesWindow) {
-                            atomicMin(&nextWindow, (m >> 5) >> kRulesWindowLog2);
+                            atomicMin(&nextWindow, (m >> 5) >> kRulesWindowLog2);  /* whatever the window test says: the next window is visited */
                             break;
+                        }
+                        if constexpr (COND) {
+                            const uint2 c = a.memberCond[lo];
+                            const unsigned int from = (c.y & kCondFromEnd) ? (unsigned int)tail : (unsigned int)at;
+                            if (tail < 0 || from < c.x || from + (unsigned int)len > (c.y & kCondEnd)) continue;
                         }
                         if (atomicOr(&mask[r], 1u << (m & 31u)) == 0u) {
                             const unsigned int slot = atomicAdd(&numTouched, 1u);
@@ -204,6 +253,8 @@ PFAC_status_t PFACX_rulesRun(PFAC_handle_t handle, const PFACX_rulesRun_t *run, 
         run->numRules == 0 || run->numRules >= (size_t(1) << 24) || run->numIds >= (size_t)0x7fffffff || (run->count && !run->d_pairIds) ||
         !run->d_table || !run->d_memberOff || !run->d_member || !run->d_need || (run->capacity && (!run->d_firedSeg || !run->d_firedRule)))
         return PFAC_STATUS_INVALID_PARAMETER;
+    const bool cond = run->d_memberCond != nullptr;
+    if (cond && ((run->count && !run->d_pairPos) || !run->d_patternLen || run->size >= (size_t)0x80000000u)) return PFAC_STATUS_INVALID_PARAMETER;
     PFAC_context *c = handle;
     RulesArgs a{};
     a.pairIds = run->d_pairIds;
@@ -219,14 +270,23 @@ PFAC_status_t PFACX_rulesRun(PFAC_handle_t handle, const PFACX_rulesRun_t *run, 
     a.firedSeg = run->d_firedSeg;
     a.firedRule = run->d_firedRule;
     a.capacity = run->capacity;
+    if (cond) {
+        a.pairPos = run->d_pairPos;
+        a.offsets = reinterpret_cast<const unsigned long long *>(run->d_offsets);
+        a.size = (unsigned int)run->size;
+        a.patternLen = run->d_patternLen;
+        a.memberCond = reinterpret_cast<const uint2 *>(run->d_memberCond);
+    }
     const PFAC_status_t carved = carveScratch(c->scratch.rules, [&](ScratchCarver &k) { a.segFirst = k.take<unsigned long long>(run->numSegments + 1); });
     if (carved != PFAC_STATUS_SUCCESS) return carved;
     const unsigned int grid = a.numSegments < gridCap(c, 4) ? a.numSegments : gridCap(c, 4);
     const HostHandoff list(c, pfac::kHostRules);
-    hipLaunchKernelGGL(pfac_rules_pass<false>, dim3(grid), dim3(kRulesBlockPairs), 0, 0, a);
+    const auto count = cond ? pfac_rules_pass<false, true> : pfac_rules_pass<false, false>;       /* a plain set launches what it always has */
+    const auto emit = cond ? pfac_rules_pass<true, true> : pfac_rules_pass<true, false>;
+    hipLaunchKernelGGL(count, dim3(grid), dim3(kRulesBlockPairs), 0, 0, a);
     hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, a.segFirst, a.numSegments, a.segFirst + a.numSegments,
                        reinterpret_cast<unsigned long long *>(list.d_value));
-    if (run->capacity) hipLaunchKernelGGL(pfac_rules_pass<true>, dim3(grid), dim3(kRulesBlockPairs), 0, 0, a);
+    if (run->capacity) hipLaunchKernelGGL(emit, dim3(grid), dim3(kRulesBlockPairs), 0, 0, a);
     if (run->d_segFirst != nullptr &&
         hipMemcpyAsync(run->d_segFirst, a.segFirst, (run->numSegments + 1) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, nullptr) != hipSuccess)
         return PFAC_STATUS_INTERNAL_ERROR;

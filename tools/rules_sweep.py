@@ -8,7 +8,12 @@ with the fastest and the slowest.  With --parent-lib DIR (libpfac.so and libpfac
 ends the sweep.  One JSON line per shape on stdout; with --out the lines go to that file (profiles/rules_sweep.txt).  `memberships` is the number
 of (pair on a prefix chain, rule that names its pattern) steps the pass takes per call: the design claim is that the extra over (a) follows it.
 
-    python tools/rules_sweep.py [--shapes 16777216:1536,...] [--steps 11] [--parent-lib DIR] [--out FILE]
+Conditioned sets (PFACX_rulesOpenEx), with --cond: the same rules opened three more ways -- `cond0`: every member {id, 0, 0, 0}, so
+the fired list is that of `rules` and the difference is what the window test costs (one position and one length load per chain member, 8 bytes per
+membership); `condw`: seeded windows, a fifth of the members negated; and, with --parent-lib, `rules` again in the parent commit's build, twice
+(`parent`, `parent2`): plain sets launch the instantiation they always have, so `rules` is expected inside the spread of those two rounds.
+
+    python tools/rules_sweep.py [--shapes 16777216:1536,...] [--steps 11] [--parent-lib DIR] [--cond] [--modes rules,cond0,...] [--out FILE]
 """
 import argparse
 import json
@@ -31,6 +36,25 @@ def make_rules(num_patterns):
     off = np.zeros(NUM_RULES + 1, dtype=np.int32)
     off[1:] = np.cumsum([len(r) for r in rules])
     return off, np.array([i for r in rules for i in r], dtype=np.int32)
+
+
+def make_members(rule_off, rule_pats, windows):
+    """the rules of make_rules as PFACX_rule_member_t; windows: a seeded window per member -- a quarter from the end, offset 0 .. 255, depth 0 for
+    half of them, else 64 .. 1023 -- and a fifth of the members negated (never a rule's first)"""
+    import numpy as np
+    from pfac_amd import api
+    members = np.zeros(rule_pats.size, dtype=api.rule_member_dtype())
+    members["pattern"] = rule_pats
+    if windows:
+        rng = np.random.Generator(np.random.PCG64(SEED + 1))
+        k = rule_pats.size
+        first = np.zeros(k, dtype=bool)
+        first[rule_off[:-1]] = True
+        members["flags"] = np.where((rng.integers(0, 5, size=k) == 0) & ~first, api.PFACX_RULE_NOT, 0) | \
+            np.where(rng.integers(0, 4, size=k) == 0, api.PFACX_RULE_FROM_END, 0)
+        members["offset"] = rng.integers(0, 256, size=k)
+        members["depth"] = np.where(rng.integers(0, 2, size=k) == 0, 0, rng.integers(64, 1024, size=k))
+    return members
 
 
 def one(mode, n, seg, steps):
@@ -56,7 +80,6 @@ def one(mode, n, seg, steps):
     result = {}
 
     # the inverted index, by the ids the library reports (duplicate lines: the highest id)
-    prefix = h.table(api.PFACX_TABLE_PREFIX_PATTERN).view(np.int32).reshape(-1, 2)
     by_bytes = {}
     for i, p in enumerate(cfg.patterns):
         by_bytes[bytes(p)] = i + 1
@@ -68,8 +91,8 @@ def one(mode, n, seg, steps):
     member_off = torch.from_numpy(np.concatenate([[0], np.cumsum(np.bincount(resolved, minlength=F + 1))]).astype(np.int64)).to("cuda:0")
     need = torch.from_numpy(((1 << np.diff(rule_off).astype(np.int64)) - 1)).to("cuda:0")
 
-    if mode == "rules":
-        r = h.rulesOpen(rule_off, rule_pats)
+    if mode in ("rules", "parent", "parent2", "cond0", "condw"):
+        r = h.rulesOpenEx(rule_off, make_members(rule_off, rule_pats, mode == "condw")) if mode.startswith("cond") else h.rulesOpen(rule_off, rule_pats)
         _, fired = r.match_device(d_in.data_ptr(), n, d_off.data_ptr(), segs, None, None, 0, None, check=False)
         d_seg = torch.empty(max(1, fired), dtype=torch.int32, device="cuda:0")
         d_rule = torch.empty(max(1, fired), dtype=torch.int32, device="cuda:0")
@@ -130,6 +153,8 @@ def main():
     ap.add_argument("--steps", type=int, default=11)
     ap.add_argument("--timeout", type=int, default=300, help="seconds per child")
     ap.add_argument("--parent-lib", default="", help="directory with the parent commit's libpfac.so and libpfac_gfx950.so")
+    ap.add_argument("--cond", action="store_true", help="also the conditioned sets (and, with --parent-lib, the plain call in the parent's build)")
+    ap.add_argument("--modes", default="", help="comma separated, instead of the default list")
     ap.add_argument("--out", default="")
     ap.add_argument("--one", default="", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -141,9 +166,12 @@ def main():
     rc = 0
     for shape in a.shapes.split(","):
         row = {"shape": shape}
-        for mode in ("rules", "allbatch", "diy"):
+        modes = ["rules", "allbatch", "diy"]
+        if a.cond:
+            modes = ["rules", "cond0", "condw"] + (["parent", "parent2"] if a.parent_lib else []) + modes[1:]
+        for mode in (a.modes.split(",") if a.modes else modes):
             env = dict(os.environ)
-            if a.parent_lib and mode != "rules":
+            if a.parent_lib and mode not in ("rules", "cond0", "condw"):
                 env["PFAC_HOST_LIB"] = os.path.join(os.path.abspath(a.parent_lib), "libpfac.so")
                 env["PFAC_AB_OLD_LIBS"] = "1"
             try:
@@ -171,6 +199,12 @@ def main():
             row["extra_us"] = round(row["rules_us"] - row["allbatch_us"], 2)
         if "rules_us" in row and "diy_us" in row:
             row["diy_over_rules"] = round(row["diy_us"] / row["rules_us"], 2)
+        for mode in ("cond0", "condw"):
+            if "rules_us" in row and mode + "_us" in row:
+                row[mode + "_over_rules"] = round(row[mode + "_us"] / row["rules_us"], 3)
+        if "rules_us" in row and "parent_us" in row and "parent2_us" in row:
+            row["rules_over_parent"] = round(row["rules_us"] / row["parent_us"], 3)
+            row["parent2_over_parent"] = round(row["parent2_us"] / row["parent_us"], 3)
         ln = json.dumps(row)
         lines.append(ln)
         print(ln, flush=True)
@@ -183,6 +217,9 @@ def main():
                     "# and stream, %d seeded rules of 1 - 4 patterns; microseconds, median of %d event-timed calls after 2 warm-ups, *_us_range = fastest and\n"
                     "# slowest of them, *_wall_us = the host's clock; allbatch and diy %s\n"
                     % (NUM_RULES, a.steps, "in the parent commit's build" if a.parent_lib else "in this build"))
+            if a.cond:
+                f.write("# cond0: the same rules through PFACX_rulesOpenEx, every member {id, 0, 0, 0} (the same fired list); condw: seeded windows, a fifth of the\n"
+                        "# members negated; parent, parent2: the plain call in the parent commit's build, two rounds\n")
             for ln in lines:
                 f.write(ln + "\n")
     return rc

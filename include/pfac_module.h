@@ -143,6 +143,15 @@ PFAC_status_t PFACX_linesGather(PFAC_handle_t handle, const char *d_input, size_
  * value on an error.  tools/lines_sweep.py reports it next to the fold kernel's rate. */
 double PFACX_linesBitmapProbe(PFAC_handle_t handle, const void *d_in, size_t n, int launches);
 
+/* Test only: the four ordering launches of a compacted-output call (scan_order.inc) alone, on a caller's pairs.  Orders (d_ids[k], d_pos[k]), k < count,
+ * in place by ascending position, with the bin layout and through the scratch of a call over an input of n bytes -- 0 < n < 2^31, count <= n -- on a
+ * handle of PFAC_create: the sequence of PFAC_reduce_kernel's second round (more pairs than the scratch held), which grows the handle's ordering
+ * scratch to `count` pairs where it holds fewer.  The arrays hold `count` entries and nothing beyond them is written.  The positions must be DISTINCT
+ * and below n: the kernels trust them as they trust the scan's, and a list that breaks this has them write outside the arrays.  Synchronous; the
+ * handle's next compacted-output call clears its counters itself.  count == 0 succeeds and launches nothing; PFAC_STATUS_INVALID_PARAMETER for n == 0,
+ * n >= 2^31, count > n, or a null array with count > 0.  tests/test_order_edges_gpu.py runs every bin width and bin edge through it. */
+PFAC_status_t PFACX_orderPairsProbe(PFAC_handle_t handle, int *d_ids, int *d_pos, size_t count, size_t n);
+
 /* Covered spans and redaction (no reference counterpart; include/pfac_ext.h: PFACX_matchSpans* / PFACX_redactSpansFromDevice), scan_spans.hip.
  * PFACX_spansSelect: the maximal runs of bytes of d_scan[0, size) -- 0 < size < 2^31; the caller's bytes, or their folded copy for a caseless set --
  * that belong to a match.  The scan (PFAC_reduce_kernel, hashed != 0: PFAC_reduce_inplace_kernel, WITH its ordering launches) uses d_spanStart /

@@ -133,7 +133,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_batchFixup", "PFACX_batchReduceFixup",
     "PFACX_allReduce", "PFACX_allExpand", "PFACX_foldInput",
     "PFACX_streamSeam", "PFACX_streamReduce", "PFACX_flowsRun",
-    "PFACX_linesSelect", "PFACX_linesGather", "PFACX_linesBitmapProbe",
+    "PFACX_linesSelect", "PFACX_linesGather", "PFACX_linesBitmapProbe", "PFACX_orderPairsProbe",
     "PFACX_spansSelect", "PFACX_spansRedact",
     "PFACX_countPairs", "PFACX_countNonzero",
     "PFACX_disjointSelect", "PFACX_replaceRun",
@@ -793,6 +793,21 @@ class PFAC:
             return np.zeros(0, dtype=dtype)
         buf = (C.c_char * nbytes.value).from_address(ptr.value)
         return np.frombuffer(buf, dtype=dtype).copy()
+
+
+_module: Optional[C.CDLL] = None
+
+
+def order_pairs_probe(handle: "PFAC", d_ids: int, d_pos: int, count: int, n: int, check: bool = True) -> int:
+    """``PFACX_orderPairsProbe`` (include/pfac_module.h, test only; bound from the kernel module as tools/lines_sweep.py binds its probe): the
+    ordering launches of a compacted-output call over `n` bytes alone, on the `count` (id, position) pairs at the device addresses d_ids / d_pos;
+    in place, by ascending position.  The positions must be distinct and below `n`."""
+    global _module
+    if _module is None:
+        _module = C.CDLL(library_paths()[1])
+        _module.PFACX_orderPairsProbe.restype = C.c_int
+        _module.PFACX_orderPairsProbe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+    return handle._ret(_module.PFACX_orderPairsProbe(handle._h, d_ids, d_pos, count, n), "PFACX_orderPairsProbe", check)
 
 
 class Stream:

@@ -335,6 +335,22 @@ PFAC_status_t orderIntoAllPairs(PFAC_context *mc, PairOrder &order)
     return st;
 }
 
+/* The ordering alone, over `count` pairs that lie in d_ids / d_pos and whose number the host knows: the scratch planned for them as for a call over
+ * n input bytes, the counters cleared, the count copied to the device counter, the four launches; synchronous.  reduceScan's second round (more pairs
+ * than the scratch held) and PFACX_orderPairsProbe.  It uses the counters of the handle's current parity and leaves parity and orderCleanBase as they
+ * are: the caller has set orderCleanBase to null, or sets it (the probe) -- nobody has checked that this round left its counters zero. */
+PFAC_status_t orderKnownPairs(PFAC_context *mc, size_t n, unsigned int count, int *d_ids, int *d_pos, bool intoAll)
+{
+    PairOrder order;
+    PFAC_status_t st = order.plan(mc, n, count, d_ids, d_pos, mc->orderParity);
+    if (st == PFAC_STATUS_SUCCESS && intoAll) st = orderIntoAllPairs(mc, order);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (order.clearCounters() != hipSuccess || hipMemcpyAsync(order.o.count, &count, sizeof(count), hipMemcpyHostToDevice, 0) != hipSuccess ||
+        order.order(mc) != hipSuccess || hipStreamSynchronize(0) != hipSuccess)      /* `count` is read by that copy */
+        return PFAC_STATUS_INTERNAL_ERROR;
+    return PFAC_STATUS_SUCCESS;
+}
+
 PFAC_status_t reduceScan(PFAC_handle_t handle, int *d_input_string, int input_size, int *d_match_result, int *d_pos,
                          int *h_num_matched, int *h_match_result, int *h_pos, bool hashed, bool intoAll = false, int ownedPositions = -1)
 {
@@ -426,12 +442,8 @@ PFAC_status_t reduceScan(PFAC_handle_t handle, int *d_input_string, int input_si
     }
     if (count > (unsigned int)input_size) return PFAC_STATUS_INTERNAL_ERROR;
     if (ordered && count > order.o.capacity) {             /* more pairs than the scratch held: the launches left at once */
-        st = order.plan(handle, n, count, d_match_result, d_pos, handle->orderParity);
-        if (st == PFAC_STATUS_SUCCESS && intoAll) st = orderIntoAllPairs(handle, order);
+        st = orderKnownPairs(handle, n, count, d_match_result, d_pos, intoAll);
         if (st != PFAC_STATUS_SUCCESS) return st;
-        if (order.clearCounters() != hipSuccess || hipMemcpyAsync(order.o.count, &count, sizeof(count), hipMemcpyHostToDevice, 0) != hipSuccess ||
-            order.order(c) != hipSuccess || hipStreamSynchronize(0) != hipSuccess)      /* `count` is read by that copy */
-            return PFAC_STATUS_INTERNAL_ERROR;
     } else if (tidy) {
         handle->orderParity ^= 1u;                         /* the counters this call has just left zero */
         handle->orderCleanBase = order.o.counts;
@@ -508,6 +520,17 @@ double PFACX_streamProbe(const void *d_in, void *d_out, size_t n, int launches)
     if (b) (void)hipEventDestroy(b);
     if (sink) (void)hipFree(sink);
     return ms;
+}
+
+/* pfac_module.h: the ordering launches alone on a caller's pairs (tests/test_order_edges_gpu.py) */
+PFAC_status_t PFACX_orderPairsProbe(PFAC_handle_t handle, int *d_ids, int *d_pos, size_t count, size_t n)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (n == 0 || n > (size_t)0x7fffffff || count > n || (count && (!d_ids || !d_pos))) return PFAC_STATUS_INVALID_PARAMETER;
+    if (count == 0) return PFAC_STATUS_SUCCESS;
+    std::lock_guard<std::mutex> guard(handle->lock);       /* the ordering scratch and its counters belong to the handle */
+    handle->orderCleanBase = nullptr;                      /* as in reduceScan's second round: the next call clears its counters itself */
+    return orderKnownPairs(handle, n, (unsigned int)count, d_ids, d_pos, false);
 }
 
 PFAC_status_t PFAC_kernel_timeDriven_warpper(PFAC_handle_t handle, char *d_input_string, size_t input_size,

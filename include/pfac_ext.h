@@ -320,7 +320,10 @@ PFAC_status_t PFACX_matchBatchFromDeviceReduce(PFAC_handle_t handle, char *d_inp
 PFAC_status_t PFACX_matchAllFromDevice(PFAC_handle_t handle, char *d_input, size_t size, int *d_ids, int *d_pos, size_t capacity,
                                        size_t *h_num_matched);
 /* over host buffers; follows PFAC_setPlatform: the CPU platforms (host-only handles included) match on the CPU, the GPU platform
- * runs the pipelined path of PFAC_matchFromHostReduce; either way the list is expanded in place on the host */
+ * runs the pipelined path of PFAC_matchFromHostReduce; either way the list is expanded in place on the host.  This and every other host form
+ * that scans and then works on the pairs (PFACX_count / matchLines / matchSpans / matchDisjoint / matchWords / rulesMatch ...FromHost) and
+ * PFACX_replaceFromHost: a call whose handle receives another pattern set from a second thread while it runs returns
+ * PFAC_STATUS_PATTERNS_NOT_READY (rule sets: PFAC_STATUS_INVALID_PARAMETER) and writes no result counts */
 PFAC_status_t PFACX_matchAllFromHost(PFAC_handle_t handle, char *h_input, size_t size, int *h_ids, int *h_pos, size_t capacity,
                                      size_t *h_num_matched);
 /* batch form (offsets as for PFACX_matchBatch*; device offsets are clamped, never checked): every segment its own all-match list,

@@ -12,7 +12,6 @@
 #include <hip/hip_runtime_api.h>
 
 #include <mutex>
-#include <shared_mutex>
 #include <vector>
 
 #include "pfac_host.h"
@@ -60,7 +59,7 @@ static PFAC_status_t matchAllDeviceLocked(PFAC_context *c, char *d_input, size_t
                                d_offsets ? c->scratch.allSegFirst.get() : nullptr, numSegments, d_segFirst, &total);
     if (st != PFAC_STATUS_SUCCESS) return st;
     *h_num_matched = total;
-    return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+    return truncatedIf(total, capacity);
 }
 
 /* The `count` ordered longest pairs in ids / pos (room for `capacity` >= count) become the all-match list, in place: walked from
@@ -68,20 +67,20 @@ static PFAC_status_t matchAllDeviceLocked(PFAC_context *c, char *d_input, size_t
  * length; slots >= capacity are not written. */
 static size_t expandOnHost(const pfac::Automaton &fa, int *ids, int *pos, size_t count, size_t capacity)
 {
-    auto chainOf = [&](int id) -> size_t { return id >= 1 && id <= fa.numPatterns && fa.chainLen[(size_t)id] > 0 ? (size_t)fa.chainLen[(size_t)id] : 1; };
+    /* the members forEachChainMember visits (the ids come from a scan of this set: all of them are in [1, numPatterns]) */
+    auto chainOf = [&](int id) -> size_t { return id < 1 || id > fa.numPatterns ? 0 : (fa.chainLen[(size_t)id] > 1 ? (size_t)fa.chainLen[(size_t)id] : 1); };
     size_t total = 0;
     for (size_t i = 0; i < count; i++) total += chainOf(ids[i]);
     if (fa.maxChain <= 1) return total;
     size_t o = total;
     for (size_t i = count; i-- > 0;) {
         const int id = ids[i], p = pos[i];
-        const size_t c = chainOf(id);
-        o -= c;
-        int q = id;
-        for (size_t k = 0; k < c; k++) {
-            if (o + k < capacity) { ids[o + k] = q; pos[o + k] = p; }
-            q = q >= 1 && q <= fa.numPatterns ? fa.prefixPattern[(size_t)q] : 0;
-        }
+        size_t k = o -= chainOf(id);
+        forEachChainMember(fa, id, [&](int q) {
+            if (k < capacity) { ids[k] = q; pos[k] = p; }
+            k++;
+            return true;
+        });
     }
     return total;
 }
@@ -94,13 +93,11 @@ extern "C" {
 PFAC_status_t PFACX_matchAllFromDevice(PFAC_handle_t handle, char *d_input, size_t size, int *d_ids, int *d_pos, size_t capacity,
                                        size_t *h_num_matched)
 {
-    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
-    if (!d_input || !d_ids || !d_pos || !h_num_matched) return PFAC_STATUS_INVALID_PARAMETER;
+    if (const PFAC_status_t st = checkSetAndPointers(handle, {d_input, d_ids, d_pos, h_num_matched})) return st;
     if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
     std::lock_guard<std::mutex> guard(handle->lock);
     return matchAllDeviceLocked(handle, d_input, size, nullptr, 0, d_ids, d_pos, capacity, nullptr, h_num_matched);
 }
@@ -108,32 +105,26 @@ PFAC_status_t PFACX_matchAllFromDevice(PFAC_handle_t handle, char *d_input, size
 PFAC_status_t PFACX_matchAllFromHost(PFAC_handle_t handle, char *h_input, size_t size, int *h_ids, int *h_pos, size_t capacity,
                                      size_t *h_num_matched)
 {
-    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
-    if (!h_input || !h_ids || !h_pos || !h_num_matched) return PFAC_STATUS_INVALID_PARAMETER;
+    if (const PFAC_status_t st = checkSetAndPointers(handle, {h_input, h_ids, h_pos, h_num_matched})) return st;
     if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
-    int count = 0;
-    const PFAC_status_t st = hostLongestPairs(handle, h_input, size, h_ids, h_pos, &count);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    std::shared_lock<std::shared_mutex> tables(handle->tablesInUse);
-    const size_t total = expandOnHost(handle->fa, h_ids, h_pos, (size_t)count, capacity);
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
+    const PinnedPairs scan(handle, h_input, size, h_ids, h_pos);
+    if (scan.status != PFAC_STATUS_SUCCESS) return scan.status;
+    const size_t total = expandOnHost(handle->fa, h_ids, h_pos, (size_t)scan.count, capacity);
     *h_num_matched = total;
-    return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+    return truncatedIf(total, capacity);
 }
 
 PFAC_status_t PFACX_matchAllBatchFromDevice(PFAC_handle_t handle, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
                                             int *d_ids, int *d_pos, size_t capacity, size_t *d_segFirst, size_t *h_num_matched)
 {
-    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
-    if (!d_input || !d_offsets || !d_ids || !d_pos || !d_segFirst || !h_num_matched) return PFAC_STATUS_INVALID_PARAMETER;
+    if (const PFAC_status_t st = checkSetAndPointers(handle, {d_input, d_offsets, d_ids, d_pos, d_segFirst, h_num_matched})) return st;
     if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
     if (numSegments == 0 || numSegments >= SIZE_MAX / sizeof(size_t)) return PFAC_STATUS_INVALID_PARAMETER;
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
     std::lock_guard<std::mutex> guard(handle->lock);
     return matchAllDeviceLocked(handle, d_input, size, d_offsets, numSegments, d_ids, d_pos, capacity, d_segFirst, h_num_matched);
 }

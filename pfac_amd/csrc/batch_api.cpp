@@ -39,7 +39,7 @@ PFAC_status_t ensurePatternLen(PFAC_context *c)
  * of the segment ends behind it on the default stream */
 PFAC_status_t matchBatchDeviceLocked(PFAC_context *c, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments, int *d_matched_result)
 {
-    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
     PFAC_status_t st = ensurePatternLen(c);
     if (st != PFAC_STATUS_SUCCESS) return st;
     st = matchDeviceLocked(c, d_input, size, d_matched_result);
@@ -116,8 +116,8 @@ PFAC_status_t PFACX_matchBatchFromDeviceReduce(PFAC_handle_t handle, char *d_inp
     if (!d_input || !d_offsets || !d_matched_result || !d_pos || !d_segFirst || !h_num_matched) return PFAC_STATUS_INVALID_PARAMETER;
     if (size == 0) return PFAC_STATUS_SUCCESS;
     if (numSegments == 0 || numSegments >= SIZE_MAX / sizeof(size_t)) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
     std::lock_guard<std::mutex> guard(handle->lock);
     PFAC_status_t st = ensurePatternLen(handle);
     if (st != PFAC_STATUS_SUCCESS) return st;

@@ -11,10 +11,7 @@
  */
 #include <hip/hip_runtime_api.h>
 
-#include <memory>
 #include <mutex>
-#include <new>
-#include <shared_mutex>
 #include <vector>
 
 #include "pfac_host.h"
@@ -23,13 +20,14 @@ namespace pfac_internal {
 
 constexpr unsigned int kCountFlags = PFACX_COUNT_LONGEST | PFACX_COUNT_ACCUMULATE;
 
+static bool countsFit(const pfac::Automaton &fa, size_t numCounts) { return fa.numPatterns >= 0 && numCounts >= (size_t)fa.numPatterns + 1; }   /* an entry for every id of the set, which the caller holds still */
 /* what the count calls that need a pattern set check first */
 static PFAC_status_t checkCountArgs(PFAC_handle_t handle, unsigned int flags, const unsigned long long *counts, size_t numCounts)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
-    if (!counts || (flags & ~kCountFlags)) return PFAC_STATUS_INVALID_PARAMETER;
-    if (handle->fa.numPatterns < 0 || numCounts < (size_t)handle->fa.numPatterns + 1) return PFAC_STATUS_INVALID_PARAMETER;
+    const SetPin pin(handle);
+    if (pin.status() != PFAC_STATUS_SUCCESS) return pin.status();
+    if (!counts || (flags & ~kCountFlags) || !countsFit(handle->fa, numCounts)) return PFAC_STATUS_INVALID_PARAMETER;
     return PFAC_STATUS_SUCCESS;
 }
 
@@ -50,14 +48,9 @@ static unsigned long long countsFromLongest(const pfac::Automaton &fa, std::vect
     unsigned long long total = 0;
     if (!(flags & PFACX_COUNT_LONGEST) && fa.maxChain > 1) {
         const std::vector<unsigned long long> longest(L);
-        for (size_t id = 1; id <= F; id++) {
-            if (longest[id] == 0) continue;
-            int q = fa.prefixPattern[id];
-            for (int k = 1; k < fa.chainLen[id] && q >= 1 && (size_t)q <= F; k++) {
-                L[(size_t)q] += longest[id];
-                q = fa.prefixPattern[(size_t)q];
-            }
-        }
+        for (size_t id = 1; id <= F; id++)
+            if (longest[id] != 0)
+                forEachChainMember(fa, (int)id, [&](int q) { if ((size_t)q != id) L[(size_t)q] += longest[id]; return true; });
     }
     for (size_t id = 1; id <= F; id++) total += L[id];
     if (flags & PFACX_COUNT_ACCUMULATE) {
@@ -80,8 +73,8 @@ PFAC_status_t PFACX_countFromDevice(PFAC_handle_t handle, char *d_input, size_t 
     PFAC_status_t st = checkCountArgs(handle, flags, d_counts, numCounts);
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (!d_input || !h_total) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     if (size == 0) {                                                       /* nothing matched: the counts zeroed, or left alone */
         st = handle->count_pairs_ptr(handle, nullptr, 0, 0, nullptr, 0, nullptr, flags, d_counts, nullptr);
@@ -104,28 +97,22 @@ PFAC_status_t PFACX_countFromHost(PFAC_handle_t handle, char *h_input, size_t si
     PFAC_status_t st = checkCountArgs(handle, flags, h_counts, numCounts);
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (!h_input || !h_total) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
-    if (handle->platform == PFAC_PLATFORM_GPU && (!handle->hasDevice || !handle->module)) return PFAC_STATUS_LIB_NOT_EXIST;
-    const size_t F = (size_t)handle->fa.numPatterns;
-    std::vector<unsigned long long> L;
-    std::unique_ptr<int[]> pairs(new (std::nothrow) int[2 * size + 1]);   /* the ids, then the positions; not initialised: a page nothing writes costs nothing */
-    try {
-        L.assign(F + 1, 0);
-    } catch (const std::bad_alloc &) {
-        return PFAC_STATUS_ALLOC_FAILED;
-    }
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
+    if (hostLacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
+    const HostPairs pairs(size, size);
     if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
-    if (size > 0) {
-        int n = 0;
-        const int *ids = pairs.get();
-        st = hostLongestPairs(handle, h_input, size, pairs.get(), pairs.get() + size, &n);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-        for (int i = 0; i < n; i++)
-            if (ids[i] > 0 && (size_t)ids[i] <= F) L[(size_t)ids[i]]++;
-    }
-    std::shared_lock<std::shared_mutex> tables(handle->tablesInUse);
-    if ((size_t)handle->fa.numPatterns != F) return PFAC_STATUS_PATTERNS_NOT_READY;          /* another thread has replaced the set meanwhile */
+    int n = 0;
+    unsigned long long generation = 0;
+    if (size > 0) st = hostLongestPairs(handle, h_input, size, pairs.ids, pairs.pos, &n, &generation);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    const SetPin pin = size > 0 ? SetPin(handle, generation) : SetPin(handle);   /* the set the pairs came from; nothing scanned: whichever is loaded */
+    if (pin.status() != PFAC_STATUS_SUCCESS) return pin.status();
+    if (!countsFit(handle->fa, numCounts)) return PFAC_STATUS_INVALID_PARAMETER;   /* ... which need not be the one checkCountArgs saw */
+    const size_t F = (size_t)handle->fa.numPatterns;
     try {
+        std::vector<unsigned long long> L(F + 1, 0);
+        for (int i = 0; i < n; i++)
+            if (pairs.ids[i] > 0 && (size_t)pairs.ids[i] <= F) L[(size_t)pairs.ids[i]]++;
         *h_total = (size_t)countsFromLongest(handle->fa, L, flags, h_counts);
     } catch (const std::bad_alloc &) {
         return PFAC_STATUS_ALLOC_FAILED;
@@ -138,8 +125,8 @@ PFAC_status_t PFACX_countPairsFromDevice(PFAC_handle_t handle, const int *d_ids,
 {
     PFAC_status_t st = checkCountArgs(handle, flags, d_counts, numCounts);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    if (numPairs > (size_t)0x7fffffff || (numPairs && !d_ids)) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (numPairs > kMaxInt || (numPairs && !d_ids)) return PFAC_STATUS_INVALID_PARAMETER;
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     const void *d_table = nullptr;
     st = chainTable(handle, flags, &d_table);
@@ -153,8 +140,8 @@ PFAC_status_t PFACX_countNonzeroFromDevice(PFAC_handle_t handle, const unsigned 
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
     if (!h_numDistinct || !h_total) return PFAC_STATUS_INVALID_PARAMETER;
     if (numCounts == 0) { *h_numDistinct = 0; *h_total = 0; return PFAC_STATUS_SUCCESS; }
-    if (!d_counts || (capacity && (!d_ids || !d_outCounts)) || numCounts > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (!d_counts || (capacity && (!d_ids || !d_outCounts)) || numCounts > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     return handle->count_nonzero_ptr(handle, d_counts, numCounts, d_ids, d_outCounts, capacity, h_numDistinct, h_total);
 }

@@ -16,14 +16,7 @@
 
 namespace pfac_internal {
 
-static PFAC_status_t checkDisjointArgs(PFAC_handle_t handle, const char *input, const int *ids, const int *pos, const size_t *h_numTokens,
-                                       const size_t *h_coveredBytes)
-{
-    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
-    if (!input || !ids || !pos || !h_numTokens || !h_coveredBytes) return PFAC_STATUS_INVALID_PARAMETER;
-    return PFAC_STATUS_SUCCESS;
-}
+static bool replOffFits(const pfac::Automaton &fa, size_t numOff) { return numOff >= (size_t)fa.numPatterns + 2; }   /* two offsets for every id of the set, which the caller holds still */
 
 /* what both forms of the replacement refuse; *done: the call has its answer (size == 0) */
 static PFAC_status_t checkReplaceArgs(PFAC_handle_t handle, const char *input, size_t size, const int *ids, const int *pos, size_t numTokens,
@@ -32,14 +25,15 @@ static PFAC_status_t checkReplaceArgs(PFAC_handle_t handle, const char *input, s
 {
     *done = false;
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
+    const SetPin pin(handle);
+    if (pin.status() != PFAC_STATUS_SUCCESS) return pin.status();
     if (!h_outBytes) return PFAC_STATUS_INVALID_PARAMETER;
     if (size == 0) { *h_outBytes = 0; *done = true; return PFAC_STATUS_SUCCESS; }
     if (!input || (!out && outCapacity)) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff || numTokens > (size_t)0x7fffffff || replBytes > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size > kMaxInt || numTokens > kMaxInt || replBytes > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
     if (numTokens) {
         if (!ids || !pos || !replOff || (!replBytesAt && replBytes)) return PFAC_STATUS_INVALID_PARAMETER;
-        if (numOff < (size_t)handle->fa.numPatterns + 2) return PFAC_STATUS_INVALID_PARAMETER;
+        if (!replOffFits(handle->fa, numOff)) return PFAC_STATUS_INVALID_PARAMETER;
     }
     const uintptr_t I = reinterpret_cast<uintptr_t>(input), O = reinterpret_cast<uintptr_t>(out);
     if (outCapacity && I < O + outCapacity && O < I + size) return PFAC_STATUS_INVALID_PARAMETER;      /* a text whose length changes has no in-place form */
@@ -54,12 +48,12 @@ extern "C" {
 PFAC_status_t PFACX_matchDisjointFromDevice(PFAC_handle_t handle, char *d_input, size_t size, int *d_ids, int *d_pos, size_t capacity,
                                             size_t *h_numTokens, size_t *h_coveredBytes)
 {
-    PFAC_status_t st = checkDisjointArgs(handle, d_input, d_ids, d_pos, h_numTokens, h_coveredBytes);
+    PFAC_status_t st = checkSetAndPointers(handle, {d_input, d_ids, d_pos, h_numTokens, h_coveredBytes});
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (size == 0) { *h_numTokens = 0; *h_coveredBytes = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     st = ensurePatternLen(handle);
     if (st != PFAC_STATUS_SUCCESS) return st;
@@ -73,21 +67,19 @@ PFAC_status_t PFACX_matchDisjointFromDevice(PFAC_handle_t handle, char *d_input,
 PFAC_status_t PFACX_matchDisjointFromHost(PFAC_handle_t handle, char *h_input, size_t size, int *h_ids, int *h_pos, size_t capacity,
                                           size_t *h_numTokens, size_t *h_coveredBytes)
 {
-    PFAC_status_t st = checkDisjointArgs(handle, h_input, h_ids, h_pos, h_numTokens, h_coveredBytes);
+    PFAC_status_t st = checkSetAndPointers(handle, {h_input, h_ids, h_pos, h_numTokens, h_coveredBytes});
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (size == 0) { *h_numTokens = 0; *h_coveredBytes = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
-    const std::vector<int> &patternLen = handle->fa.patternLen;
-    int count = 0;
-    st = hostLongestPairs(handle, h_input, size, h_ids, h_pos, &count);                /* in position order */
-    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
+    const PinnedPairs scan(handle, h_input, size, h_ids, h_pos);                       /* in position order */
+    if (scan.status != PFAC_STATUS_SUCCESS) return scan.status;
     size_t o = 0, covered = 0, end = 0;                                               /* end: where the last taken match ended */
-    for (size_t j = 0; j < (size_t)count; j++) {
+    for (size_t j = 0; j < (size_t)scan.count; j++) {
         const size_t p = (size_t)h_pos[j];
         if (p < end) continue;                                                         /* starts inside a taken match */
         const int id = h_ids[j];
-        const size_t len = id > 0 && (size_t)id < patternLen.size() ? (size_t)patternLen[id] : 0;
+        const size_t len = patternLenOf(handle->fa, id);
         h_ids[o] = id;
         h_pos[o] = (int)p;
         o++;
@@ -107,14 +99,14 @@ PFAC_status_t PFACX_replaceFromDevice(PFAC_handle_t handle, const char *d_input,
     PFAC_status_t st = checkReplaceArgs(handle, d_input, size, d_ids, d_pos, numTokens, d_replOff, numOff, d_replBytes, replBytes, d_out, outCapacity,
                                         h_outBytes, &done);
     if (st != PFAC_STATUS_SUCCESS || done) return st;
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     if (numTokens == 0) {                                                              /* a plain copy */
         const size_t bytes = size < outCapacity ? size : outCapacity;
         if (bytes && hipMemcpy(d_out, d_input, bytes, hipMemcpyDeviceToDevice) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
         if (hipStreamSynchronize(0) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
         *h_outBytes = size;
-        return size > outCapacity ? (PFAC_status_t)PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+        return truncatedIf(size, outCapacity);
     }
     st = ensurePatternLen(handle);
     if (st != PFAC_STATUS_SUCCESS) return st;
@@ -130,7 +122,9 @@ PFAC_status_t PFACX_replaceFromHost(PFAC_handle_t handle, const char *h_input, s
     const PFAC_status_t st = checkReplaceArgs(handle, h_input, size, h_ids, h_pos, numTokens, h_replOff, numOff, h_replBytes, replBytes, h_out,
                                               outCapacity, h_outBytes, &done);
     if (st != PFAC_STATUS_SUCCESS || done) return st;
-    std::lock_guard<std::mutex> guard(handle->lock);                                   /* the pattern lengths must not change under the loop */
+    const SetPin pin(handle);                                                          /* no scan: the lengths of whichever set is loaded, held still under the loop */
+    if (pin.status() != PFAC_STATUS_SUCCESS) return pin.status();
+    if (numTokens && !replOffFits(handle->fa, numOff)) return PFAC_STATUS_INVALID_PARAMETER;   /* ... which need not be the one checkReplaceArgs saw */
     const std::vector<int> &patternLen = handle->fa.patternLen;
     const size_t numIds = patternLen.size();                                           /* F + 1 <= numOff - 1: every id with a length has two offsets */
     unsigned long long w = 0;                                                          /* bytes of the text so far */
@@ -152,7 +146,7 @@ PFAC_status_t PFACX_replaceFromHost(PFAC_handle_t handle, const char *h_input, s
     }
     if (size > cur) put(h_input + cur, size - cur);
     *h_outBytes = (size_t)w;
-    return w > outCapacity ? (PFAC_status_t)PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+    return truncatedIf(w, outCapacity);
 }
 
 } /* extern "C" */

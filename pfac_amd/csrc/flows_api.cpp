@@ -274,7 +274,7 @@ PFAC_status_t PFACX_flowsMatchFromDevice(PFACX_flows_t flows, char *d_input, siz
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (numPieces == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
     if (size && flows->kind == 1) return PFAC_STATUS_INVALID_PARAMETER;          /* a host-fed set */
-    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
     correctTextureMode(c);                                                       /* (a call whose pieces have only seams resolves it too) */
     const size_t M = (size_t)c->fa.maxPatternLen;
     st = ensureCarries(flows, M);
@@ -344,7 +344,7 @@ PFAC_status_t PFACX_flowsMatchFromHost(PFACX_flows_t flows, char *h_input, size_
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (numPieces == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
     if (size && flows->kind == 2) return PFAC_STATUS_INVALID_PARAMETER;          /* a device-fed set */
-    if (c->platform == PFAC_PLATFORM_GPU && (!c->hasDevice || !c->module)) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
     int at = 0;
     try {
         std::vector<std::vector<unsigned char>> next(numPieces);                /* the flows change when the whole call has succeeded */
@@ -392,7 +392,7 @@ PFAC_status_t PFACX_flowsFlush(PFACX_flows_t flows, const unsigned int *h_flowId
     int total = 0;
     try {
         if (flows->kind == 2 && n) {
-            if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+            if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
             st = ensureCarries(flows, M);
             if (st != PFAC_STATUS_SUCCESS) return st;
             PFACX_flowPiece_t *pieces = nullptr;
@@ -413,7 +413,7 @@ PFAC_status_t PFACX_flowsFlush(PFACX_flows_t flows, const unsigned int *h_flowId
             if (st == PFAC_STATUS_SUCCESS) st = runOnDevice(flows, nullptr, n, sumFinal, 0, ids, pos, capacity, first, &total);
             if (st != PFAC_STATUS_SUCCESS) return st;
         } else if (flows->kind == 1) {
-            if (c->platform == PFAC_PLATFORM_GPU && (!c->hasDevice || !c->module)) return PFAC_STATUS_LIB_NOT_EXIST;
+            if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
             std::vector<unsigned char> none;
             for (size_t k = 0; k < n; k++) {
                 first[k] = total;

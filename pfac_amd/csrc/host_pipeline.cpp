@@ -27,7 +27,7 @@ namespace pfac_internal {
 /* PFAC_matchFromDevice behind the argument checks; the caller holds handle->lock */
 PFAC_status_t matchDeviceLocked(PFAC_context *c, char *d_inputString, size_t size, int *d_matched_result)
 {
-    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;      /* never a CPU fallback */
+    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;      /* never a CPU fallback */
     correctTextureMode(c);
     if (c->perfMode == PFAC_TIME_DRIVEN) return c->kernel_time_driven_ptr(c, d_inputString, size, d_matched_result);
     if (c->perfMode == PFAC_SPACE_DRIVEN) return c->kernel_space_driven_ptr(c, d_inputString, size, d_matched_result);
@@ -73,7 +73,7 @@ static PFAC_status_t ensureHostStage(PFAC_context *c, size_t need)
  * starts with), and the runtime's own staging of pageable host memory (one throwaway upload of a pageable piece).  The caller holds c->lock. */
 PFAC_status_t prepareHostPath(PFAC_context *c, size_t maxBytes)
 {
-    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
     const size_t n = PieceCut(maxBytes ? maxBytes : kHostPiece, ~size_t(0), kHostPiece, (size_t)c->fa.maxPatternLen).stageNeed();   /* the longest piece of such a call */
     PFAC_status_t st = ensureHostStage(c, n);
     if (st != PFAC_STATUS_SUCCESS) return st;
@@ -192,7 +192,7 @@ static PFAC_status_t stagedPairs(PFAC_context *c, char *h_inputString, const Pie
  */
 PFAC_status_t matchHostOnGpu(PFAC_context *c, char *h_inputString, size_t owned, size_t readable, int *h_matched_result)
 {
-    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
     const PieceCut cut(owned, readable, kHostPiece, (size_t)c->fa.maxPatternLen);
     unsigned helpers = 0;                                      /* of the zero fill: sized from the cores this thread may run on, up to 8 */
     if (owned >= (size_t(4) << 20)) {
@@ -251,7 +251,7 @@ PFAC_status_t matchHostOnGpu(PFAC_context *c, char *h_inputString, size_t owned,
 constexpr size_t kHostReducePiece = size_t(16) << 20;
 PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t size, size_t readable, size_t posBase, int *h_matched_result, int *h_pos, int *h_num_matched)
 {
-    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
     const PieceCut cut(size, readable, kHostReducePiece, (size_t)c->fa.maxPatternLen);
     size_t total = 0;
     const PFAC_status_t st = stagedPairs(c, h_inputString, cut, /* ordered */ true, [](Staged) {}, [&](const Piece &p, size_t count, const int *d_ids, const int *d_pos) {
@@ -280,7 +280,7 @@ PFAC_status_t matchHostReduceOnGpu(PFAC_context *c, char *h_inputString, size_t 
  */
 PFAC_status_t matchBatchHostOnGpu(PFAC_context *c, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments, int *h_matched_result)
 {
-    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
     const size_t overlap = (size_t)c->fa.maxPatternLen;
     const size_t piece = size < kHostPiece ? size : kHostPiece;
     PFAC_status_t st = ensureHostStage(c, piece + overlap);

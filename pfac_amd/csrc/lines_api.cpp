@@ -50,11 +50,8 @@ static void listLines(const char *in, size_t n, const std::vector<uint64_t> &hit
 static PFAC_status_t checkLinesArgs(PFAC_handle_t handle, const char *input, unsigned int flags, const int *lineStart, const int *lineLen,
                                     const size_t *h_numLines, const size_t *h_numSelected)
 {
-    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
-    if (!input || !lineStart || !lineLen || !h_numLines || !h_numSelected) return PFAC_STATUS_INVALID_PARAMETER;
-    if (flags & ~PFACX_LINES_INVERT) return PFAC_STATUS_INVALID_PARAMETER;
-    return PFAC_STATUS_SUCCESS;
+    const PFAC_status_t st = checkSetAndPointers(handle, {input, lineStart, lineLen, h_numLines, h_numSelected});
+    return st == PFAC_STATUS_SUCCESS && (flags & ~PFACX_LINES_INVERT) ? PFAC_STATUS_INVALID_PARAMETER : st;
 }
 
 } // namespace pfac_internal
@@ -69,8 +66,8 @@ PFAC_status_t PFACX_matchLinesFromDevice(PFAC_handle_t handle, char *d_input, si
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (size == 0) { *h_numLines = 0; *h_numSelected = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     DeviceScan scan;                                                       /* a caseless set: the scan reads the folded copy, the line ends are the caller's */
     st = beginDeviceScan(handle, d_input, size, &scan);
@@ -86,7 +83,7 @@ PFAC_status_t PFACX_matchLinesFromHost(PFAC_handle_t handle, char *h_input, size
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (size == 0) { *h_numLines = 0; *h_numSelected = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
     const bool invert = (flags & PFACX_LINES_INVERT) != 0;
     std::vector<uint64_t> hit;
     try {
@@ -95,7 +92,7 @@ PFAC_status_t PFACX_matchLinesFromHost(PFAC_handle_t handle, char *h_input, size
         return PFAC_STATUS_ALLOC_FAILED;
     }
     int count = 0;
-    st = hostLongestPairs(handle, h_input, size, h_lineStart, h_lineLen, &count);      /* ids, positions: in position order */
+    st = hostLongestPairs(handle, h_input, size, h_lineStart, h_lineLen, &count, nullptr);      /* ids, positions: in position order */
     if (st != PFAC_STATUS_SUCCESS) return st;
     size_t j = 0;                                                         /* one walk over lines and positions together */
     forEachLine(h_input, size, [&](size_t k, size_t, size_t e) {
@@ -113,8 +110,8 @@ PFAC_status_t PFACX_gatherLinesFromDevice(PFAC_handle_t handle, const char *d_in
     if (!h_outBytes) return PFAC_STATUS_INVALID_PARAMETER;
     if (numSelected == 0) { *h_outBytes = 0; return PFAC_STATUS_SUCCESS; }
     if (!d_lineStart || !d_lineLen || (!d_input && size) || (!d_out && outCapacity)) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff || numSelected > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > kMaxInt || numSelected > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     return handle->lines_gather_ptr(handle, d_input, size, d_lineStart, d_lineLen, numSelected, d_out, outCapacity, h_outBytes);
 }

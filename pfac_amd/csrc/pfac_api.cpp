@@ -85,7 +85,7 @@ PFAC_status_t foldDeviceInput(PFAC_context *c, char *d_in, size_t size, char **d
 {
     *d_use = d_in;
     if (!c->caseInsensitive || size == 0) return PFAC_STATUS_SUCCESS;
-    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
     PFAC_status_t st = c->scratch.fold.reserve(up256(size));
     if (st != PFAC_STATUS_SUCCESS) return st;
     st = c->fold_input_ptr(c, d_in, c->scratch.fold.get(), size);
@@ -301,12 +301,13 @@ PFAC_status_t loadModule(PFAC_context *c)
  * and drives several threads through one handle (multi_gpu.cpp: the workers of a CPU-platform handle): the tables first, once -- the dense
  * table is built on first use (ensureHostRefTable) --, then any number of threads may match side by side */
 PFAC_status_t prepareCpuPlatformLocked(PFAC_context *c) { return ensureHostRefTable(c); }
-PFAC_status_t matchHostOnCpuPlatformPrepared(PFAC_context *c, const char *in, size_t n, int *out)
+PFAC_status_t matchHostOnCpuPlatformPrepared(PFAC_context *c, const char *in, size_t n, int *out, unsigned long long *generation)
 {
     bool omp = false;
     if (c->platform == PFAC_PLATFORM_CPU_OMP) omp = (std::getenv("OMP_NUM_THREADS") != nullptr);
     std::shared_lock<std::shared_mutex> r(c->tablesInUse);             /* a setter on another thread waits until the match is through */
-    if (c->perfMode == PFAC_TIME_DRIVEN && c->h_dense.empty()) return PFAC_STATUS_PATTERNS_NOT_READY;   /* ... or has just replaced the set: its tables are built on the next call */
+    if (generation) *generation = c->setGeneration;
+    if (!c->isPatternsReady || (c->perfMode == PFAC_TIME_DRIVEN && c->h_dense.empty())) return PFAC_STATUS_PATTERNS_NOT_READY;   /* ... or has just dropped or replaced the set: its tables are built on the next call */
     return pfac::matchOnCpu(c, reinterpret_cast<const unsigned char *>(in), n, out, omp);
 }
 /* ... and the tables under c->lock, which a caller that does not hold it takes for that step alone */
@@ -318,9 +319,9 @@ static PFAC_status_t prepareCpuPlatform(PFAC_context *c)
 
 /* The longest pairs of a host buffer on whatever platform the handle is on (pfac_host.h): what every host form that works on pairs calls.  On a
  * CPU platform (ref PFAC.cpp:1036-1068) the full result vector goes into ids and is compacted in place */
-static PFAC_status_t cpuPairsPrepared(PFAC_context *c, const char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count)
+static PFAC_status_t cpuPairsPrepared(PFAC_context *c, const char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count, unsigned long long *generation = nullptr)
 {
-    const PFAC_status_t st = matchHostOnCpuPlatformPrepared(c, in, readable, ids);
+    const PFAC_status_t st = matchHostOnCpuPlatformPrepared(c, in, readable, ids, generation);
     if (st == PFAC_STATUS_SUCCESS) *count = compactPairs(ids, owned, posShift, ids, pos);
     return st;
 }
@@ -337,13 +338,14 @@ PFAC_status_t hostLongestPairsLocked(PFAC_context *c, char *in, size_t owned, si
     *count = n;
     return PFAC_STATUS_SUCCESS;
 }
-PFAC_status_t hostLongestPairs(PFAC_context *c, char *in, size_t size, int *ids, int *pos, int *count)
+PFAC_status_t hostLongestPairs(PFAC_context *c, char *in, size_t size, int *ids, int *pos, int *count, unsigned long long *generation)
 {
     if (c->platform != PFAC_PLATFORM_GPU) {
         const PFAC_status_t st = prepareCpuPlatform(c);
-        return st == PFAC_STATUS_SUCCESS ? cpuPairsPrepared(c, in, size, size, 0, ids, pos, count) : st;
+        return st == PFAC_STATUS_SUCCESS ? cpuPairsPrepared(c, in, size, size, 0, ids, pos, count, generation) : st;
     }
     std::lock_guard<std::mutex> guard(c->lock);          /* the staging buffers, the match counter and the sort scratch belong to the handle */
+    if (generation) *generation = c->setGeneration;      /* no set is replaced while the lock is held */
     return hostLongestPairsLocked(c, in, size, size, 0, ids, pos, count);
 }
 
@@ -580,8 +582,8 @@ PFAC_status_t PFAC_matchFromDeviceReduce(PFAC_handle_t handle, char *d_inputStri
     if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
     if (!d_inputString || !d_matched_result || !d_pos || !h_num_matched) return PFAC_STATUS_INVALID_PARAMETER;
     if (size == 0) return PFAC_STATUS_SUCCESS;
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
     std::lock_guard<std::mutex> guard(handle->lock);          /* the match counter and the sort scratch belong to the handle */
     DeviceScan scan;
     const PFAC_status_t st = beginDeviceScan(handle, d_inputString, size, &scan);
@@ -596,8 +598,8 @@ PFAC_status_t PFAC_matchFromHostReduce(PFAC_handle_t handle, char *h_inputString
     if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
     if (!h_inputString || !h_matched_result || !h_pos || !h_num_matched) return PFAC_STATUS_INVALID_PARAMETER;
     if (size == 0) return PFAC_STATUS_SUCCESS;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
-    return hostLongestPairs(handle, h_inputString, size, h_matched_result, h_pos, h_num_matched);
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
+    return hostLongestPairs(handle, h_inputString, size, h_matched_result, h_pos, h_num_matched, nullptr);
 }
 
 /* ------------------------------------------------------------- extensions */
@@ -735,9 +737,9 @@ PFAC_status_t PFACX_trim(PFAC_handle_t handle)
 PFAC_status_t PFACX_prepare(PFAC_handle_t handle, size_t maxBytes)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    std::lock_guard<std::mutex> guard(handle->lock);      /* first: setPlatform and the readers of a pattern set write what is checked here */
     if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
     if (handle->platform != PFAC_PLATFORM_GPU) return PFAC_STATUS_SUCCESS;       /* the CPU platforms keep nothing between calls */
-    std::lock_guard<std::mutex> guard(handle->lock);
     return prepareHostPath(handle, maxBytes);
 }
 

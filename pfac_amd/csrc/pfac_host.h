@@ -4,6 +4,10 @@
 #ifndef PFAC_HOST_H_
 #define PFAC_HOST_H_
 
+#include <memory>
+#include <new>
+#include <optional>
+
 #include "pfac_context.h"
 
 namespace pfac {
@@ -46,14 +50,70 @@ PFAC_status_t bindTable(PFAC_context *c);
 PFAC_status_t bindCompiledSet(PFAC_context *c);
 void correctTextureMode(PFAC_context *c);
 PFAC_status_t prepareCpuPlatformLocked(PFAC_context *c);                                        /* the caller holds c->lock */
-PFAC_status_t matchHostOnCpuPlatformPrepared(PFAC_context *c, const char *in, size_t n, int *out);   /* ... has called the above; any number of threads */
+/* ... has called the above; any number of threads.  *generation (may be null): c->setGeneration, read in the section that reads the tables */
+PFAC_status_t matchHostOnCpuPlatformPrepared(PFAC_context *c, const char *in, size_t n, int *out, unsigned long long *generation = nullptr);
 /* the longest match at positions [0, owned) of `readable` >= owned host bytes (the rest read-ahead only) as (id, position + posShift) pairs in position
  * order; ids/pos hold `readable` entries at least; any platform: the CPU matcher into ids, compacted in place, or the pipelined path of the GPU
  * platform (LIB_NOT_EXIST without a device or a module).  The caller holds c->lock */
 PFAC_status_t hostLongestPairsLocked(PFAC_context *c, char *in, size_t owned, size_t readable, int posShift, int *ids, int *pos, int *count);
 /* ... of a whole buffer, for a caller without the lock: held for the whole call on the GPU platform, on the CPU platforms only while the tables are
- * prepared -- several threads match there side by side */
-PFAC_status_t hostLongestPairs(PFAC_context *c, char *in, size_t size, int *ids, int *pos, int *count);
+ * prepared -- several threads match there side by side.  *generation (may be null): the setGeneration of the set that was scanned, read while the scan holds it still */
+PFAC_status_t hostLongestPairs(PFAC_context *c, char *in, size_t size, int *ids, int *pos, int *count, unsigned long long *generation);
+/* The compiled set (c->fa) held still for a scope: tablesInUse shared, which whoever replaces the set holds exclusively.  status(): SUCCESS iff a set
+ * is loaded and -- where a generation is given -- it is still the one with that number, else PATTERNS_NOT_READY.  Never held across a scan: the CPU
+ * platforms' first match takes tablesInUse exclusively (ensureHostRefTable) */
+class SetPin {
+public:
+    explicit SetPin(PFAC_context *c) : held_(c->tablesInUse), ok_(c->isPatternsReady) {}
+    SetPin(PFAC_context *c, unsigned long long generation) : held_(c->tablesInUse), ok_(c->isPatternsReady && c->setGeneration == generation) {}
+    PFAC_status_t status() const { return ok_ ? PFAC_STATUS_SUCCESS : PFAC_STATUS_PATTERNS_NOT_READY; }
+private:
+    std::shared_lock<std::shared_mutex> held_;
+    bool ok_;
+};
+/* the two steps of a host form whose post-pass reads c->fa: the longest pairs of the buffer, then the pin on the set they came from */
+struct PinnedPairs {
+    PinnedPairs(PFAC_context *c, char *in, size_t size, int *ids, int *pos) : status(hostLongestPairs(c, in, size, ids, pos, &count, &generation))
+    { if (status == PFAC_STATUS_SUCCESS) status = pin.emplace(c, generation).status(); }
+    int count = 0;
+    unsigned long long generation = 0;
+    PFAC_status_t status;                     /* (declared behind what its initialiser writes) */
+    std::optional<SetPin> pin;
+};
+/* what most calls that need a pattern set check first, before they hold a lock: the handle, a loaded set, no null among the pointers they require */
+inline PFAC_status_t checkSetAndPointers(PFAC_context *c, std::initializer_list<const void *> required)
+{
+    if (!c) return PFAC_STATUS_INVALID_HANDLE;
+    if (SetPin(c).status() != PFAC_STATUS_SUCCESS) return PFAC_STATUS_PATTERNS_NOT_READY;
+    for (const void *p : required)
+        if (!p) return PFAC_STATUS_INVALID_PARAMETER;
+    return PFAC_STATUS_SUCCESS;
+}
+/* positions, counts and lengths are ints on the device and in the callers' arrays */
+constexpr size_t kMaxInt = 0x7fffffff;
+/* nothing to launch with: LIB_NOT_EXIST of every device form, and of a host form on the GPU platform */
+inline bool lacksModule(const PFAC_context *c) { return !c->hasDevice || !c->module; }
+inline bool hostLacksModule(const PFAC_context *c) { return c->platform == PFAC_PLATFORM_GPU && lacksModule(c); }
+/* the status of a call whose full list has `total` entries */
+inline PFAC_status_t truncatedIf(unsigned long long total, size_t capacity) { return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS; }
+/* the pair temporaries of a host form in one allocation: numIds ids, then numPos positions; not initialised: a page nothing writes costs nothing */
+struct HostPairs {
+    HostPairs(size_t numIds, size_t numPos) : mem(new (std::nothrow) int[numIds + numPos + 1]), ids(mem.get()), pos(mem ? mem.get() + numIds : nullptr) {}
+    explicit operator bool() const { return mem != nullptr; }
+    std::unique_ptr<int[]> mem;
+    int *const ids, *const pos;
+};
+/* f(q) for the patterns that occur where pattern id is the longest -- id, then its chain of prefix patterns (Automaton::prefixPattern): at most
+ * chainLen[id] of them (one for an id that is not in the trie), none for an id outside [1, numPatterns]; ends at such an id, or where f returns false */
+template <class F>
+inline void forEachChainMember(const pfac::Automaton &fa, int id, F f)
+{
+    if (id < 1 || id > fa.numPatterns) return;
+    const int steps = fa.chainLen[(size_t)id] > 1 ? fa.chainLen[(size_t)id] : 1;
+    for (int k = 0, q = id; k < steps && q >= 1 && q <= fa.numPatterns && f(q); k++) q = fa.prefixPattern[(size_t)q];
+}
+/* the length of pattern id, 0 for an id the set does not have */
+inline size_t patternLenOf(const pfac::Automaton &fa, int id) { return id > 0 && (size_t)id < fa.patternLen.size() ? (size_t)fa.patternLen[(size_t)id] : 0; }
 /* what the stream and the flows calls check first (the caller holds c->lock: the set cannot change between this check and the end of the call) */
 inline PFAC_status_t checkSetGeneration(const PFAC_context *c, unsigned long long generation)
 {

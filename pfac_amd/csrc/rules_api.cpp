@@ -21,10 +21,7 @@
 
 #include <algorithm>
 #include <cstring>
-#include <memory>
 #include <mutex>
-#include <new>
-#include <shared_mutex>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -193,19 +190,16 @@ size_t firedOnHost(const pfac::Automaton &fa, const PFACX_rules_s &s, const int 
         fired.clear();
         const long long n = (long long)(first[k + 1] - first[k]);
         for (int i = 0; i < numPairs[k]; i++) {
-            int q = ids[first[k] + (size_t)i];
-            if (q < 1 || (size_t)q > s.numIds) continue;
             const long long at = cond ? pos[first[k] + (size_t)i] : 0;
-            const int steps = fa.chainLen[(size_t)q];
-            for (int c = 0; c < (steps > 1 ? steps : 1) && q >= 1 && (size_t)q <= s.numIds; c++) {
+            forEachChainMember(fa, ids[first[k] + (size_t)i], [&](int q) {        /* (the caller's pin: fa.numPatterns == s.numIds) */
                 for (int j = s.memberOff[(size_t)q]; j < s.memberOff[(size_t)q + 1]; j++) {
                     const unsigned int m = s.member[(size_t)j], r = m >> 5;
                     if (cond && !windowHolds(at, fa.patternLen[(size_t)q], n, s.memberCond[2 * (size_t)j], s.memberCond[2 * (size_t)j + 1])) continue;
                     if (mask[r] == 0) touched.push_back(r);
                     mask[r] |= 1u << (m & 31u);
                 }
-                q = fa.prefixPattern[(size_t)q];
-            }
+                return true;
+            });
         }
         for (unsigned int r : touched) {
             if (mask[r] == s.need[r]) fired.push_back(r);
@@ -295,7 +289,7 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
     PFAC_status_t st = checkMatchArgs(rules, d_input, size, d_offsets, numSegments, d_firedSeg, d_firedRule, capacity, h_numFired);
     if (st != PFAC_STATUS_SUCCESS) return st;
     PFAC_context *c = rules->handle;
-    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(c->lock);
     st = checkSetGeneration(c, rules->generation);
     if (st != PFAC_STATUS_SUCCESS) return st;
@@ -348,7 +342,7 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
     st = c->rules_run_ptr(c, &run, &total);
     if (st != PFAC_STATUS_SUCCESS) return st;
     *h_numFired = total;
-    return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+    return truncatedIf(total, capacity);
 }
 
 PFAC_status_t PFACX_rulesMatchFromHost(PFACX_rules_t rules, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments,
@@ -369,23 +363,22 @@ PFAC_status_t PFACX_rulesMatchFromHost(PFACX_rules_t rules, char *h_input, size_
         *h_numFired = 0;
         return PFAC_STATUS_SUCCESS;
     }
-    if (onGpu && (!c->hasDevice || !c->module)) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
     size_t longest = 0;
     for (size_t k = 0; k < numSegments; k++) longest = std::max(longest, offsets[k + 1] - offsets[k]);
-    /* the longest ids of segment k from ids[offsets[k]] on; not initialised: a page nothing writes costs nothing */
     const bool cond = rules->conditioned();                                     /* then every pair keeps its position in its segment, at the index of its id */
-    const size_t numPos = cond ? size : (onGpu ? 0 : longest);
-    std::unique_ptr<int[]> ids(new (std::nothrow) int[size]), pos(numPos ? new (std::nothrow) int[numPos] : nullptr);
+    const HostPairs pairs(size, cond ? size : (onGpu ? 0 : longest));           /* the longest ids of segment k from ids[offsets[k]] on */
+    int *const ids = pairs.ids, *const pos = pairs.pos;
     std::vector<int> numPairs;
     try {
         numPairs.assign(numSegments, 0);
     } catch (const std::bad_alloc &) {
         return PFAC_STATUS_ALLOC_FAILED;
     }
-    if (!ids || (numPos && !pos)) return PFAC_STATUS_ALLOC_FAILED;
+    if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
     if (onGpu) {
         /* the pipelined batch path: the full result of every segment, compacted in place (pair z of a segment comes from an entry at or behind z) */
-        st = matchBatchHostOnGpu(c, h_input, size, offsets, numSegments, ids.get());
+        st = matchBatchHostOnGpu(c, h_input, size, offsets, numSegments, ids);
         if (st != PFAC_STATUS_SUCCESS) return st;
         for (size_t k = 0; k < numSegments; k++) {
             int z = 0;
@@ -401,16 +394,17 @@ PFAC_status_t PFACX_rulesMatchFromHost(PFACX_rules_t rules, char *h_input, size_
         for (size_t k = 0; k < numSegments; k++) {
             const size_t n = offsets[k + 1] - offsets[k];
             if (n == 0) continue;
-            st = hostLongestPairs(c, h_input + offsets[k], n, ids.get() + offsets[k], pos.get() + (cond ? offsets[k] : 0), &numPairs[k]);
+            st = hostLongestPairs(c, h_input + offsets[k], n, ids + offsets[k], pos + (cond ? offsets[k] : 0), &numPairs[k], nullptr);
             if (st != PFAC_STATUS_SUCCESS) return st;
         }
     }
-    std::shared_lock<std::shared_mutex> tables(c->tablesInUse);
-    if (!onGpu && (rules->generation != c->setGeneration || (size_t)c->fa.numPatterns != rules->numIds)) return PFAC_STATUS_INVALID_PARAMETER;   /* another thread has replaced the set meanwhile */
+    /* generations only count up: the set is the one the rules were opened on now, so it was during every scan above (on the GPU platform the lock is still held) */
+    const SetPin pin(c, rules->generation);
+    if (pin.status() != PFAC_STATUS_SUCCESS) return PFAC_STATUS_INVALID_PARAMETER;      /* another thread has replaced the set meanwhile: the contract's answer for a rule set */
     try {
-        const size_t total = firedOnHost(c->fa, *rules, ids.get(), pos.get(), offsets, numPairs.data(), numSegments, h_firedSeg, h_firedRule, capacity, h_segFirst);
+        const size_t total = firedOnHost(c->fa, *rules, ids, pos, offsets, numPairs.data(), numSegments, h_firedSeg, h_firedRule, capacity, h_segFirst);
         *h_numFired = total;
-        return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+        return truncatedIf(total, capacity);
     } catch (const std::bad_alloc &) {
         return PFAC_STATUS_ALLOC_FAILED;
     }

@@ -37,15 +37,6 @@ static void mergeSpans(Next next, int *spanStart, int *spanLen, size_t *numSpans
     *coveredBytes = covered;
 }
 
-static PFAC_status_t checkSpansArgs(PFAC_handle_t handle, const char *input, const int *spanStart, const int *spanLen, const size_t *h_numSpans,
-                                    const size_t *h_coveredBytes)
-{
-    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
-    if (!input || !spanStart || !spanLen || !h_numSpans || !h_coveredBytes) return PFAC_STATUS_INVALID_PARAMETER;
-    return PFAC_STATUS_SUCCESS;
-}
-
 } // namespace pfac_internal
 using namespace pfac_internal;
 
@@ -54,12 +45,12 @@ extern "C" {
 PFAC_status_t PFACX_matchSpansFromDevice(PFAC_handle_t handle, char *d_input, size_t size, int *d_spanStart, int *d_spanLen, size_t capacity,
                                          size_t *h_numSpans, size_t *h_coveredBytes)
 {
-    PFAC_status_t st = checkSpansArgs(handle, d_input, d_spanStart, d_spanLen, h_numSpans, h_coveredBytes);
+    PFAC_status_t st = checkSetAndPointers(handle, {d_input, d_spanStart, d_spanLen, h_numSpans, h_coveredBytes});
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (size == 0) { *h_numSpans = 0; *h_coveredBytes = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     st = ensurePatternLen(handle);
     if (st != PFAC_STATUS_SUCCESS) return st;
@@ -73,21 +64,18 @@ PFAC_status_t PFACX_matchSpansFromDevice(PFAC_handle_t handle, char *d_input, si
 PFAC_status_t PFACX_matchSpansFromHost(PFAC_handle_t handle, char *h_input, size_t size, int *h_spanStart, int *h_spanLen, size_t capacity,
                                        size_t *h_numSpans, size_t *h_coveredBytes)
 {
-    PFAC_status_t st = checkSpansArgs(handle, h_input, h_spanStart, h_spanLen, h_numSpans, h_coveredBytes);
+    PFAC_status_t st = checkSetAndPointers(handle, {h_input, h_spanStart, h_spanLen, h_numSpans, h_coveredBytes});
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (size == 0) { *h_numSpans = 0; *h_coveredBytes = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
-    const std::vector<int> &patternLen = handle->fa.patternLen;
-    auto lenOf = [&](int id) -> size_t { return id > 0 && (size_t)id < patternLen.size() ? (size_t)patternLen[id] : 0; };
-    int count = 0;
-    st = hostLongestPairs(handle, h_input, size, h_spanStart, h_spanLen, &count);      /* ids, positions: in position order */
-    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
+    const PinnedPairs scan(handle, h_input, size, h_spanStart, h_spanLen);                          /* ids, positions: in position order */
+    if (scan.status != PFAC_STATUS_SUCCESS) return scan.status;
     size_t j = 0;
     mergeSpans([&](size_t &p, size_t &e) {
-        if (j >= (size_t)count) return false;
+        if (j >= (size_t)scan.count) return false;
         p = (size_t)h_spanLen[j];
-        e = p + lenOf(h_spanStart[j]);
+        e = p + patternLenOf(handle->fa, h_spanStart[j]);
         j++;
         return true;
     }, h_spanStart, h_spanLen, h_numSpans, h_coveredBytes);
@@ -100,10 +88,10 @@ PFAC_status_t PFACX_redactSpansFromDevice(PFAC_handle_t handle, const char *d_in
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
     if (size == 0) return PFAC_STATUS_SUCCESS;
     if (!d_input || !d_out || (numSpans && (!d_spanStart || !d_spanLen))) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff || numSpans > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size > kMaxInt || numSpans > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
     const uintptr_t I = reinterpret_cast<uintptr_t>(d_input), O = reinterpret_cast<uintptr_t>(d_out);
     if (I != O && I < O + size && O < I + size) return PFAC_STATUS_INVALID_PARAMETER;        /* in place, or apart */
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     return handle->spans_redact_ptr(handle, d_input, size, d_spanStart, d_spanLen, numSpans, fill, d_out);
 }

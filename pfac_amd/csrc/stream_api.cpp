@@ -194,8 +194,8 @@ PFAC_status_t PFACX_streamMatchFromDevice(PFACX_stream_t stream, char *d_piece, 
     const size_t M = (size_t)c->fa.maxPatternLen;
     if (capacity < size || capacity - size < M) return PFAC_STATUS_INVALID_PARAMETER;
     if (stream->kind == 1) return PFAC_STATUS_INVALID_PARAMETER;           /* a host-fed stream */
-    if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;   /* int positions */
+    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
     correctTextureMode(c);                                                 /* (a piece that has only a seam resolves it too) */
     const StreamSplit sp = streamSplitOf(stream->carried, size, M);
     int seamPairs = 0, piecePairs = 0;
@@ -241,10 +241,10 @@ PFAC_status_t PFACX_streamMatchFromHost(PFACX_stream_t stream, char *h_piece, si
     if (size == 0) { *h_num_matched = 0; *h_pieceOffset = stream->total; return PFAC_STATUS_SUCCESS; }
     const size_t M = (size_t)c->fa.maxPatternLen;
     if (capacity < size || capacity - size < M) return PFAC_STATUS_INVALID_PARAMETER;
-    if (size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
     if (stream->kind == 2) return PFAC_STATUS_INVALID_PARAMETER;           /* a device-fed stream */
     const bool gpu = c->platform == PFAC_PLATFORM_GPU;
-    if (gpu && (!c->hasDevice || !c->module)) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (gpu && lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
     int pairs = 0;
     try {
         std::vector<unsigned char> next;                       /* the stream changes when the whole call has succeeded */
@@ -274,12 +274,12 @@ PFAC_status_t PFACX_streamFlush(PFACX_stream_t stream, int *ids, int *pos, size_
     const size_t carried = stream->carried;
     int pairs = 0;
     if (carried && stream->kind == 2) {
-        if (!c->hasDevice || !c->module) return PFAC_STATUS_LIB_NOT_EXIST;
+        if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
         st = c->stream_seam_ptr(c, stream->d_carry[stream->cur], carried, nullptr, 0, carried, stream->d_carry[stream->cur ^ 1], stream->d_stage, ids, pos,
                                 &pairs);
         if (st != PFAC_STATUS_SUCCESS) return st;
     } else if (carried && stream->kind == 1) {
-        if (c->platform == PFAC_PLATFORM_GPU && (!c->hasDevice || !c->module)) return PFAC_STATUS_LIB_NOT_EXIST;
+        if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
         try {
             std::vector<unsigned char> none;
             st = hostPiece(c, stream->h_carry.data(), carried, nullptr, 0, true, ids, pos, none, &pairs);

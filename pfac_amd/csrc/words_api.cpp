@@ -11,10 +11,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
-#include <memory>
 #include <mutex>
-#include <new>
-#include <shared_mutex>
 
 #include "pfac_host.h"
 
@@ -28,10 +25,8 @@ static bool inClass(const unsigned int *cls, unsigned char b) { return (cls[b >>
 /* what all three calls check first */
 static PFAC_status_t checkWordsArgs(PFAC_handle_t handle, const void *input, size_t size, unsigned int flags, const size_t *h_num_matched)
 {
-    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
-    if (!input || !h_num_matched || (flags & ~PFACX_WORDS_ALL) || size > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;
-    return PFAC_STATUS_SUCCESS;
+    const PFAC_status_t st = checkSetAndPointers(handle, {input, h_num_matched});
+    return st == PFAC_STATUS_SUCCESS && ((flags & ~PFACX_WORDS_ALL) || size > kMaxInt) ? PFAC_STATUS_INVALID_PARAMETER : st;
 }
 
 /* do [a, a + na) and [b, b + nb) share a byte? */
@@ -67,7 +62,7 @@ static PFAC_status_t wordsRunLocked(PFAC_context *c, const char *d_input, size_t
     st = c->words_run_ptr(c, &run, &total);
     if (st != PFAC_STATUS_SUCCESS) return st;
     *h_num_matched = total;
-    return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+    return truncatedIf(total, capacity);
 }
 
 /* The host loop: the bounded members of the chains of `count` ordered longest pairs into ids / pos (slots >= capacity are not written); returns the
@@ -78,20 +73,15 @@ static size_t wordsOnHost(const pfac::Automaton &fa, const unsigned char *in, si
     size_t total = 0;
     for (size_t i = 0; i < count; i++) {
         const int id = pairIds[i], p = pairPos[i];
-        if (id < 1 || id > fa.numPatterns || p < 0 || (size_t)p >= n) continue;
-        if (p > 0 && inClass(cls, in[p - 1])) continue;
-        const int steps = fa.chainLen[(size_t)id] > 0 ? fa.chainLen[(size_t)id] : 1;
-        int q = id;
-        for (int s = 0; s < steps && q >= 1 && q <= fa.numPatterns; s++) {
+        if (p < 0 || (size_t)p >= n || (p > 0 && inClass(cls, in[p - 1]))) continue;
+        forEachChainMember(fa, id, [&](int q) {
             const int len = fa.patternLen[(size_t)q];
             const size_t e = (size_t)p + (size_t)(len > 0 ? len : 0);
-            if (len > 0 && e <= n && (e == n || !inClass(cls, in[e]))) {
-                if (total < capacity) { ids[total] = q; pos[total] = p; }
-                total++;
-                if (!all) break;
-            }
-            q = fa.prefixPattern[(size_t)q];
-        }
+            if (len <= 0 || e > n || (e < n && inClass(cls, in[e]))) return true;
+            if (total < capacity) { ids[total] = q; pos[total] = p; }
+            total++;
+            return all;                                                   /* list mode: the longest bounded member alone */
+        });
     }
     return total;
 }
@@ -109,7 +99,7 @@ PFAC_status_t PFACX_matchWordsFromDevice(PFAC_handle_t handle, char *d_input, si
     if (!d_ids || !d_pos) return PFAC_STATUS_INVALID_PARAMETER;
     if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
     DeviceScan scan;                                                       /* a caseless set: the scan reads the folded copy, the boundary passes the caller's bytes */
     st = beginDeviceScan(handle, d_input, size, &scan);
@@ -133,19 +123,15 @@ PFAC_status_t PFACX_matchWordsFromHost(PFAC_handle_t handle, char *h_input, size
     if (!h_ids || !h_pos) return PFAC_STATUS_INVALID_PARAMETER;
     if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (handle->platform == PFAC_PLATFORM_GPU && (!handle->hasDevice || !handle->module)) return PFAC_STATUS_LIB_NOT_EXIST;
-    const int F = handle->fa.numPatterns;
-    std::unique_ptr<int[]> pairs(new (std::nothrow) int[2 * size]);       /* the ids, then the positions; not initialised: a page nothing writes costs nothing */
+    if (hostLacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
+    const HostPairs pairs(size, size);
     if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
-    int count = 0;
-    st = hostLongestPairs(handle, h_input, size, pairs.get(), pairs.get() + size, &count);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    std::shared_lock<std::shared_mutex> tables(handle->tablesInUse);
-    if (!handle->isPatternsReady || handle->fa.numPatterns != F) return PFAC_STATUS_PATTERNS_NOT_READY;   /* another thread has replaced the set meanwhile */
+    const PinnedPairs scan(handle, h_input, size, pairs.ids, pairs.pos);
+    if (scan.status != PFAC_STATUS_SUCCESS) return scan.status;
     const size_t total = wordsOnHost(handle->fa, reinterpret_cast<const unsigned char *>(h_input), size, h_class ? h_class : kWordClass,
-                                     (flags & PFACX_WORDS_ALL) != 0, pairs.get(), pairs.get() + size, (size_t)(count > 0 ? count : 0), h_ids, h_pos, capacity);
+                                     (flags & PFACX_WORDS_ALL) != 0, pairs.ids, pairs.pos, (size_t)(scan.count > 0 ? scan.count : 0), h_ids, h_pos, capacity);
     *h_num_matched = total;
-    return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS;
+    return truncatedIf(total, capacity);
 }
 
 PFAC_status_t PFACX_wordsPairsFromDevice(PFAC_handle_t handle, const char *d_input, size_t size, const unsigned int *h_class, unsigned int flags,
@@ -154,7 +140,7 @@ PFAC_status_t PFACX_wordsPairsFromDevice(PFAC_handle_t handle, const char *d_inp
 {
     PFAC_status_t st = checkWordsArgs(handle, d_input, size, flags, h_num_matched);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    if (numPairs > (size_t)0x7fffffff || capacity > SIZE_MAX / sizeof(int) || (numPairs && (!d_pairIds || !d_pairPos)) || (capacity && (!d_ids || !d_pos)))
+    if (numPairs > kMaxInt || capacity > SIZE_MAX / sizeof(int) || (numPairs && (!d_pairIds || !d_pairPos)) || (capacity && (!d_ids || !d_pos)))
         return PFAC_STATUS_INVALID_PARAMETER;
     if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
     if (capacity && numPairs) {
@@ -162,7 +148,7 @@ PFAC_status_t PFACX_wordsPairsFromDevice(PFAC_handle_t handle, const char *d_inp
         if (overlap(d_ids, out, d_pairIds, in) || overlap(d_ids, out, d_pairPos, in) || overlap(d_pos, out, d_pairIds, in) || overlap(d_pos, out, d_pairPos, in))
             return PFAC_STATUS_INVALID_PARAMETER;
     }
-    if (!handle->hasDevice || !handle->module) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     if (numPairs == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
     std::lock_guard<std::mutex> guard(handle->lock);
     return wordsRunLocked(handle, d_input, size, h_class, flags, d_pairIds, d_pairPos, numPairs, d_ids, d_pos, capacity, h_num_matched);

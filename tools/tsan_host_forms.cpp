@@ -1,0 +1,171 @@
+/* tools/tsan_host_forms.cpp -- the host forms that scan and then read the compiled set (PFACX_matchAllFromHost, countFromHost, matchWordsFromHost in
+ * both modes, matchSpansFromHost, matchDisjointFromHost, matchLinesFromHost) and PFACX_replaceFromHost, under ThreadSanitizer (`make -C pfac_amd/csrc
+ * tsan`): four threads call them on one host-only handle while a fifth replaces its pattern set, cycling through three sets.  A and B have the same
+ * number of patterns -- A with chains of prefixes, B with none, and other lengths per id --, C has more.  Every call must end in the documented
+ * refusal or in success with the single-threaded answer of one of the sets, a mixture of two sets never; and every form must have given every
+ * set's answer at least once, so that a library that refuses everything does not pass.  CPU only.   tsan_host_forms [rounds] [pause in microseconds] */
+#include <atomic>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "PFAC.h"
+#include "pfac_ext.h"
+
+namespace {
+
+enum Form { kAll, kCount, kWordsList, kWordsAll, kSpans, kDisjoint, kLines, kReplace, kForms };
+const char *const kFormName[kForms] = {"matchAll", "count", "words", "words(all)", "spans", "disjoint", "lines", "replace"};
+
+const std::string kSets[3] = {
+    "a\nab\nabc\nabcd\nhe\nhers\n",                          /* A: chains a < ab < abc < abcd, he < hers */
+    "she\nhi\nbcda\nx\ndog\ncats\n",                         /* B: as many patterns, none a prefix of another, other lengths per id */
+    "abc\nab\nshe\nhe\nhers\ndog\ndo\ncat\nhis\n",           /* C: more patterns */
+};
+constexpr size_t kNumA = 6, kNumC = 9, kCanaries = 4;
+constexpr unsigned long long kCanary = 0xC0FFEE0DDF00Dull;
+
+struct Fixture {
+    PFAC_handle_t h = nullptr;
+    std::string input;
+    std::vector<int> tokIds, tokPos;                         /* the disjoint tokens of set A: what PFACX_replaceFromHost is given, whatever set is loaded */
+    std::vector<int> replOff;                                /* two offsets for every id of the largest set */
+    std::string replBytes;
+};
+
+struct Scratch {
+    std::vector<int> a, b, c;
+    std::vector<unsigned long long> counts;                  /* exactly kNumA + 1 entries, then the canaries */
+    std::string out;
+    explicit Scratch(size_t n) : a(4 * n), b(4 * n), c(n), counts(kNumA + 1 + kCanaries, kCanary), out(8 * n, '\0') {}
+};
+
+/* one call of form f: its status, and on success everything it wrote as one list of numbers.  false: a canary behind counts[] has changed */
+bool call(Form f, const Fixture &x, Scratch &w, PFAC_status_t *status, std::vector<long long> *result)
+{
+    char *in = const_cast<char *>(x.input.data());
+    const size_t n = x.input.size();
+    size_t u = 0, v = 0, listed = 0;
+    std::vector<long long> &r = *result;
+    r.clear();
+    PFAC_status_t st = PFAC_STATUS_INTERNAL_ERROR;
+    switch (f) {
+    case kAll: st = PFACX_matchAllFromHost(x.h, in, n, w.a.data(), w.b.data(), w.a.size(), &u); listed = u; break;
+    case kCount:
+        st = PFACX_countFromHost(x.h, in, n, 0, w.counts.data(), kNumA + 1, &u);
+        for (size_t k = 0; k < kCanaries; k++)
+            if (w.counts[kNumA + 1 + k] != kCanary) return false;
+        if (st == PFAC_STATUS_SUCCESS) r.assign(w.counts.begin(), w.counts.begin() + kNumA + 1);
+        break;
+    case kWordsList: st = PFACX_matchWordsFromHost(x.h, in, n, nullptr, 0, w.a.data(), w.b.data(), w.a.size(), &u); listed = u; break;
+    case kWordsAll: st = PFACX_matchWordsFromHost(x.h, in, n, nullptr, PFACX_WORDS_ALL, w.a.data(), w.b.data(), w.a.size(), &u); listed = u; break;
+    case kSpans: st = PFACX_matchSpansFromHost(x.h, in, n, w.a.data(), w.b.data(), w.a.size(), &u, &v); listed = u; break;
+    case kDisjoint: st = PFACX_matchDisjointFromHost(x.h, in, n, w.a.data(), w.b.data(), w.a.size(), &u, &v); listed = u; break;
+    case kLines:
+        st = PFACX_matchLinesFromHost(x.h, in, n, 0, w.a.data(), w.b.data(), w.c.data(), w.c.size(), &v, &u);
+        listed = u;
+        if (st == PFAC_STATUS_SUCCESS) r.assign(w.c.begin(), w.c.begin() + u);
+        break;
+    case kReplace:
+        st = PFACX_replaceFromHost(x.h, in, n, x.tokIds.data(), x.tokPos.data(), x.tokIds.size(), x.replOff.data(), x.replOff.size(), x.replBytes.data(),
+                                   x.replBytes.size(), &w.out[0], w.out.size(), &u);
+        if (st == PFAC_STATUS_SUCCESS) r.assign(w.out.begin(), w.out.begin() + u);
+        break;
+    default: break;
+    }
+    *status = st;
+    if (st != PFAC_STATUS_SUCCESS) { r.clear(); return true; }
+    r.push_back((long long)u);
+    r.push_back((long long)v);
+    r.insert(r.end(), w.a.begin(), w.a.begin() + listed);
+    r.insert(r.end(), w.b.begin(), w.b.begin() + listed);
+    return true;
+}
+
+bool load(PFAC_handle_t h, int set) { return PFACX_readPatternFromMemory(h, kSets[set].data(), kSets[set].size()) == PFAC_STATUS_SUCCESS; }
+
+} // namespace
+
+int main(int argc, char **argv)
+{
+    const int rounds = argc > 1 ? atoi(argv[1]) : 500, pauseUs = argc > 2 ? atoi(argv[2]) : 2000, threads = 4;
+    Fixture x;
+    if (PFACX_createHostOnly(&x.h) != PFAC_STATUS_SUCCESS || PFAC_setPlatform(x.h, PFAC_PLATFORM_CPU) != PFAC_STATUS_SUCCESS) return 2;
+    /* lines in which all three sets occur, and one line each that only A, only B, only C selects */
+    const char *const lines[] = {"abcd she sells hers, his dog and cats", "x marks hi; abc ab a_b (he) hers_", "one penny a piece", "do cat abcda bcda shells", "",
+                                 "x: 1 + 2 = 3", "the dogs do chase cats: abcdabcd he she his", "do it once more"};
+    for (size_t k = 0; x.input.size() < 4096; k++) {
+        x.input += lines[k % 8];
+        x.input += '\n';
+    }
+    for (size_t id = 0; id <= kNumC + 1; id++) {             /* the string of id: <id>; ids 0 and F + 1 have offsets and no string of their own */
+        x.replOff.push_back((int)x.replBytes.size());
+        if (id >= 1 && id <= kNumC) x.replBytes += "<" + std::to_string(id) + ">";
+    }
+    /* the single-threaded answers: want[form][set]; count on set C is the refusal of its numCounts check */
+    std::vector<long long> want[kForms][3];
+    PFAC_status_t wantStatus[kForms][3];
+    Scratch w0(x.input.size());
+    for (int set = 0; set < 3; set++) {
+        if (!load(x.h, set)) { fprintf(stderr, "set %d refused\n", set); return 2; }
+        for (int f = 0; f < kForms; f++) {
+            if (f == kReplace && set == 0) {                 /* its tokens: the disjoint list of A, recorded above as {count, covered, ids, positions} */
+                const std::vector<long long> &d = want[kDisjoint][0];
+                x.tokIds.assign(d.begin() + 2, d.begin() + 2 + d[0]);
+                x.tokPos.assign(d.begin() + 2 + d[0], d.end());
+            }
+            if (!call((Form)f, x, w0, &wantStatus[f][set], &want[f][set])) return 2;
+            const PFAC_status_t expected = f == kCount && set == 2 ? PFAC_STATUS_INVALID_PARAMETER : PFAC_STATUS_SUCCESS;
+            if (wantStatus[f][set] != expected || (expected == PFAC_STATUS_SUCCESS && want[f][set].size() <= 2)) {
+                fprintf(stderr, "%s on set %d alone: status %d, %zu numbers\n", kFormName[f], set, (int)wantStatus[f][set], want[f][set].size());
+                return 2;
+            }
+        }
+    }
+    for (int f = 0; f < kForms; f++)                         /* an answer that two sets share would hide a mixture */
+        if (want[f][0] == want[f][1] || want[f][0] == want[f][2] || want[f][1] == want[f][2]) { fprintf(stderr, "%s: two sets, one answer\n", kFormName[f]); return 2; }
+
+    std::atomic<bool> done{false};
+    std::atomic<long> seen[kForms][3], refused[kForms], wrong{0};
+    for (int f = 0; f < kForms; f++) {
+        refused[f] = 0;
+        for (int set = 0; set < 3; set++) seen[f][set] = 0;
+    }
+    std::vector<std::thread> pool;
+    for (int t = 0; t < threads; t++)
+        pool.emplace_back([&, t]() {
+            Scratch w(x.input.size());
+            std::vector<long long> got;
+            for (long i = t; !done.load(); i++) {
+                const Form f = (Form)(i % kForms);
+                PFAC_status_t st;
+                if (!call(f, x, w, &st, &got)) { wrong++; fprintf(stderr, "%s: canary overwritten\n", kFormName[f]); continue; }
+                if (st == PFAC_STATUS_PATTERNS_NOT_READY) { refused[f]++; continue; }
+                int set = -1;
+                if (st == PFAC_STATUS_INVALID_PARAMETER && f == kCount) set = 2;
+                for (int k = 0; k < 3 && st == PFAC_STATUS_SUCCESS; k++)
+                    if (wantStatus[f][k] == PFAC_STATUS_SUCCESS && got == want[f][k]) set = k;
+                if (set < 0) { wrong++; fprintf(stderr, "%s: status %d, an answer of no set (%zu numbers)\n", kFormName[f], (int)st, got.size()); }
+                else seen[f][set]++;
+            }
+        });
+    int failedLoads = 0;
+    for (int r = 0; r < rounds; r++) {
+        if (!load(x.h, (r + 1) % 3)) failedLoads++;
+        std::this_thread::sleep_for(std::chrono::microseconds(pauseUs));
+    }
+    done = true;
+    for (auto &th : pool) th.join();
+    (void)PFAC_destroy(x.h);
+    int unseen = 0;
+    for (int f = 0; f < kForms; f++) {
+        printf("%-11s A %6ld  B %6ld  C %6ld  refused %6ld\n", kFormName[f], seen[f][0].load(), seen[f][1].load(), seen[f][2].load(), refused[f].load());
+        for (int set = 0; set < 3; set++) unseen += seen[f][set] == 0 ? 1 : 0;
+    }
+    printf("tsan_host_forms: %d threads, %d swaps: %ld wrong outcomes, %d failed loads, %d (form, set) answers never seen\n", threads, rounds, wrong.load(),
+           failedLoads, unseen);
+    return wrong.load() || failedLoads || unseen ? 1 : 0;
+}

@@ -16,7 +16,8 @@
  * (PFACX_countFromDevice / ...FromHost, PFACX_countPairsFromDevice,
  * PFACX_countNonzeroFromDevice) and the disjoint leftmost-longest matches
  * with their replacement by a string per pattern (PFACX_matchDisjoint*,
- * PFACX_replaceFromDevice / ...FromHost), rule sets (PFACX_rules*) and the
+ * PFACX_replaceFromDevice / ...FromHost), rule sets (PFACX_rules*), the
+ * counts of every pattern in every segment (PFACX_countBatch*) and the
  * occurrences bounded by bytes outside a class: whole words, lines and
  * fields (PFACX_matchWords*, PFACX_wordsPairsFromDevice).
  */
@@ -707,6 +708,66 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
 PFAC_status_t PFACX_rulesMatchFromHost  (PFACX_rules_t rules, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments,
                                          int *h_firedSeg, int *h_firedRule, size_t capacity, size_t *h_segFirst /* may be NULL */,
                                          size_t *h_numFired);
+
+/* Per-segment counts: how often each pattern occurred in each segment of a batch -- the term-document matrix of a corpus, the keyword feature vector
+ * of each log line or packet, grep -c per keyword per file -- as a sparse matrix in CSR form.  It is the join of PFACX_count* (how often, over one
+ * buffer) and PFACX_rules* (in which segment), without the expanded all-match list and without a dense segments x F matrix.
+ *   Offsets follow the rules of PFACX_matchBatch*: numSegments + 1 entries, first 0, last `size`, never decreasing, empty segments allowed.
+ *   For segment k, A_k[id] is the number of pairs with that id in the all-match list of segment k alone (PFACX_matchAll* / PFACX_matchBatch*): a
+ *   proper prefix of the longest pattern at a position counts; a match that crosses a segment border does not.  With PFACX_COUNT_LONGEST the call
+ *   counts L_k[id], the number of positions of segment k whose longest pattern is id.  Duplicate pattern lines count under the reported (highest)
+ *   id.  A caseless handle (PFACX_READ_NOCASE) counts the folded set over the folded input; the caller's bytes are never modified.
+ *   THE COUNT LIST is the entries (id, count) with count != 0, in ascending segment order and ascending id within a segment.
+ * Output is CSR: ids[i] (int) and counts[i] (unsigned int; a count is at most size < 2^31); the entries of segment k are [segFirst[k],
+ * segFirst[k + 1]).  segFirst has numSegments + 1 size_t entries and is REQUIRED whenever numSegments > 0: it is the row pointer.  *h_numEntries is
+ * the full length of the list.  *h_total is the sum of all counts: *h_num_matched of PFACX_matchAllBatchFromDevice over the same batch, or the
+ * number of longest pairs under PFACX_COUNT_LONGEST.
+ * Capacity and truncation are those of the fired list of PFACX_rules*: `capacity` (entries of each array) is free and need not be >= size.  A list
+ * longer than capacity: exactly its first `capacity` entries are written and nothing behind them, segFirst, *h_numEntries and *h_total are complete,
+ * and the call returns PFACX_STATUS_OUTPUT_TRUNCATED; with capacity == 0 the two arrays may be null: the count query.  The scan's own pair list
+ * lives in the handle's pair scratch, never in the caller's arrays.
+ * The only flag is PFACX_COUNT_LONGEST; any other bit, PFACX_COUNT_ACCUMULATE included: PFAC_STATUS_INVALID_PARAMETER.  offsets == NULL with
+ * numSegments == 1: the whole buffer is one segment.  Host offsets are validated, device offsets are clamped and never checked (wrong offsets: a
+ * wrong list, never an access outside the buffers).  PFAC_STATUS_INVALID_PARAMETER: numSegments >= 2^31, size >= 2^31, a null pointer other than
+ * those named above, offsets == NULL with numSegments != 1, numSegments == 0 with size > 0.  No pattern set: PFAC_STATUS_PATTERNS_NOT_READY.  size ==
+ * 0: success, both values 0, segFirst all zero where numSegments > 0.  A device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.  All three
+ * calls are synchronous (the values come to the host) and take the handle's lock.
+ * The device form runs on whatever kernel variant, walker, perf mode and texture mode the handle selects.  The host form follows PFAC_setPlatform:
+ * the CPU platforms, host-only handles included, run on the CPU -- the longest pairs segment by segment, their prefix chains, one counter per touched
+ * pattern (temporaries: 4 bytes per input byte and per segment, 4 per pattern; a failed allocation: PFAC_STATUS_ALLOC_FAILED); the GPU platform runs
+ * the pipelined path of PFACX_matchBatchFromHost and the same loop on the host.  A pattern set that another thread replaces during a host call:
+ * PFAC_STATUS_PATTERNS_NOT_READY, no count written.
+ * PFACX_countBatchPairsFromDevice: the same list from a LONGEST pair list the caller already has -- d_matched_result and d_segFirst of
+ * PFACX_matchBatchFromDeviceReduce, or `ids` and `first` of a PFACX_flows* call (per-flow counts); it runs no scan.  The warning of
+ * PFACX_countPairsFromDevice applies: WITHOUT PFACX_COUNT_LONGEST EVERY PAIR ALSO COUNTS FOR EVERY PATTERN ON ITS PREFIX CHAIN, so an all-match
+ * list counts with PFACX_COUNT_LONGEST.  The arrays are DEVICE memory and the caller's contract: d_pairIds at any 4-byte alignment, an id outside
+ * [1, F] is ignored and never used as an index; d_segFirstPairs (numSegments + 1 ints; NULL with numSegments == 1: one segment of all pairs) is
+ * clamped to [0, numPairs] where it is read, a decreasing pair is an empty segment.  numPairs >= 2^31: PFAC_STATUS_INVALID_PARAMETER; numPairs ==
+ * 0 (d_pairIds may then be null): success, zeros, segFirst zeroed.
+ * A SEGMENT IS ONE BLOCK'S WORK on the device: 256 threads walk its pairs once for every window of 8192 pattern ids it has an id in.  Batches of
+ * packets, lines and documents are what the call is for; counts over one huge buffer are what PFACX_countFromDevice is for.
+ * MEMORY of the device forms: grow-only handle scratch, deviceScratchBytes of PFACX_getInfo, freed by PFACX_trim: 8 (numSegments + 1) + 8 bytes
+ * rounded up to 256 for the per-segment entry counts, their scan and the sum, and -- PFACX_countBatchFromDevice only -- what the scan behind it
+ * shares with other calls: the pair list (8 bytes per input byte, the pair scratch of PFACX_matchAll* / PFACX_countFromDevice / PFACX_rules*),
+ * 4 (numSegments + 1) bytes for the first pair of each segment, the pattern lengths (4 (F + 1) bytes) and the fix-up's scratch of
+ * PFACX_matchBatchFromDeviceReduce; both forms, for the all-occurrence counts of a set in which a pattern is a prefix of another, the {prefix, chain
+ * length} table (8 (F + 1) bytes).  Nothing is sized by segments x patterns.
+ * COST: the ordered compacted batch scan, then two passes over the pairs whose work follows the pairs times their chain lengths
+ * times the windows a segment touches -- the LDS atomics and, for the all-occurrence counts, the reads of the {prefix, chain length} table too: a
+ * pair's whole chain is read again in every window its segment touches, and an id of another window costs its table load for nothing -- and a
+ * one-block scan of the numSegments entry counts between the passes, which is what millions of segments pay for (5m has the figures).
+ * OUT OF SCOPE: a dense segments x F output, PFACX_COUNT_ACCUMULATE across calls, one long segment split over several blocks, counts over flows
+ * with carried state (the pairs form covers per-call flow output), minimum-count rule members. */
+PFAC_status_t PFACX_countBatchFromDevice(PFAC_handle_t handle, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                                         unsigned int flags, int *d_ids, unsigned int *d_counts, size_t capacity,
+                                         size_t *d_segFirst /* numSegments + 1 */, size_t *h_numEntries, unsigned long long *h_total);
+PFAC_status_t PFACX_countBatchFromHost  (PFAC_handle_t handle, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments,
+                                         unsigned int flags, int *h_ids, unsigned int *h_counts, size_t capacity,
+                                         size_t *h_segFirst /* numSegments + 1 */, size_t *h_numEntries, unsigned long long *h_total);
+PFAC_status_t PFACX_countBatchPairsFromDevice(PFAC_handle_t handle, const int *d_pairIds, size_t numPairs,
+                                              const int *d_segFirstPairs /* numSegments + 1 */, size_t numSegments, unsigned int flags,
+                                              int *d_ids, unsigned int *d_counts, size_t capacity, size_t *d_segFirst,
+                                              size_t *h_numEntries, unsigned long long *h_total);
 
 /* Whole-word and delimiter-bounded matches: the occurrences whose neighbours in the input are not in a byte class -- `grep -w -F -f`, `grep -x`, "the
  * field of a CSV record equals one of 100 000 keys", term frequencies that do not count `the` inside `other`.

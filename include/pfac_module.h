@@ -255,6 +255,29 @@ typedef struct {
 } PFACX_wordsRun_t;
 PFAC_status_t PFACX_wordsRun(PFAC_handle_t handle, const PFACX_wordsRun_t *run, size_t *h_total);
 
+/* Per-segment occurrence counts (no reference counterpart; include/pfac_ext.h: PFACX_countBatch*), scan_segcount.hip.
+ * PFACX_segCountRun: the (id, count) list of a batch in CSR form from its ordered LONGEST pairs.  d_pairIds[0, count), count < 2^31, any 4-byte
+ * alignment: the ids of the ordered compacted batch scan (in the handle's pair scratch) or a caller's list, an id outside [1, numIds] ignored;
+ * d_segFirstPairs (numSegments + 1 ints: the first pair of each segment, as PFACX_batchReduceFixup leaves them, clamped to [0, count] where read, a
+ * decreasing pair an empty segment), or null: one segment of all pairs.  d_table: pfac::Int2 {prefixPattern, chainLen} by id, numIds + 1 entries
+ * -- every pair also counts for the patterns on its prefix chain --, or null: one count per pair, the table is never read.  Output: the entries with
+ * a non-zero count in ascending (segment, id) order into d_ids / d_counts, nothing at or beyond `capacity` (0: both may be null); d_segFirst
+ * (numSegments + 1 size_t, required) indexes the whole list; *h_numEntries = its full length, *h_total = the sum of all counts.  0 < numSegments <
+ * 2^31.  A segment is one block's work.  Synchronous. */
+typedef struct {
+    const int *d_pairIds;
+    size_t count;
+    const int *d_segFirstPairs;
+    size_t numSegments;
+    const void *d_table;
+    size_t numIds;
+    int *d_ids;
+    unsigned int *d_counts;
+    size_t capacity;
+    size_t *d_segFirst;
+} PFACX_segCountRun_t;
+PFAC_status_t PFACX_segCountRun(PFAC_handle_t handle, const PFACX_segCountRun_t *run, size_t *h_numEntries, unsigned long long *h_total);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -268,7 +291,7 @@ PFAC_status_t PFACX_wordsRun(PFAC_handle_t handle, const PFACX_wordsRun_t *run, 
     X(spans_select_ptr, PFACX_spansSelect) X(spans_redact_ptr, PFACX_spansRedact) \
     X(count_pairs_ptr, PFACX_countPairs) X(count_nonzero_ptr, PFACX_countNonzero) \
     X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun) \
-    X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun)
+    X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun) X(segcount_run_ptr, PFACX_segCountRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

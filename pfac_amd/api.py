@@ -40,6 +40,9 @@ PFACX_RULE_NOT = 1                              # PFACX_rule_member_t.flags: the
 PFACX_RULE_FROM_END = 2                         # the window is measured from the segment's end
 RULE_MEMBER_FIELDS = [("pattern", "<i4"), ("flags", "<u4"), ("offset", "<u4"), ("depth", "<u4")]     # PFACX_rule_member_t as a numpy structured dtype: rule_member_dtype()
 PFACX_RULES_BLOCK_PAIRS = 256                   # scan_rules.hip: kRulesBlockPairs, the pairs a block takes from a segment in one go
+PFACX_SEGCOUNT_WINDOW = 8192                    # scan_segcount.hip: kSegWindow, the pattern ids whose counters a block keeps in LDS at a time
+PFACX_SEGCOUNT_TOUCHED = 1024                   # scan_segcount.hip: kSegTouched, the touched-list length; a segment that touches more ids of a window sweeps the whole window
+PFACX_SEGCOUNT_BLOCK_PAIRS = 256                # scan_segcount.hip: kSegBlockPairs, the pairs a block takes from a segment in one go
 PFACX_COUNT_LDS_DIRECT = 16384                  # scan_count.hip: kCountDirect -- sets with F + 1 <= this count into a counter per id in LDS, larger ones into a tagged cache
 (PFACX_TABLE_DENSE, PFACX_TABLE_HASH_ROWPTR, PFACX_TABLE_HASH_VALPTR, PFACX_TABLE_INITIAL_ROW,
  PFACX_TABLE_FILTER_GRAM3, PFACX_TABLE_FILTER_SHORT, PFACX_TABLE_FILTER_LADDER, PFACX_TABLE_FILTER_FINAL3,
@@ -126,6 +129,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_matchDisjointFromDevice", "PFACX_matchDisjointFromHost", "PFACX_replaceFromDevice", "PFACX_replaceFromHost",
     "PFACX_rulesOpen", "PFACX_rulesOpenEx", "PFACX_rulesClose", "PFACX_rulesMatchFromDevice", "PFACX_rulesMatchFromHost",
     "PFACX_matchWordsFromDevice", "PFACX_matchWordsFromHost", "PFACX_wordsPairsFromDevice",
+    "PFACX_countBatchFromDevice", "PFACX_countBatchFromHost", "PFACX_countBatchPairsFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -139,6 +143,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_disjointSelect", "PFACX_replaceRun",
     "PFACX_rulesRun",
     "PFACX_wordsRun",
+    "PFACX_segCountRun",
 )
 
 
@@ -264,6 +269,12 @@ def load_library() -> C.CDLL:
         lib.PFACX_matchWordsFromHost.argtypes = words
         lib.PFACX_wordsPairsFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, CLS, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                    C.c_size_t, SZ]
+    if hasattr(lib, "PFACX_countBatchFromDevice"):
+        SZ = C.POINTER(C.c_size_t)
+        batch = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, SZ, C.POINTER(C.c_ulonglong)]
+        lib.PFACX_countBatchFromDevice.argtypes = batch
+        lib.PFACX_countBatchFromHost.argtypes = batch
+        lib.PFACX_countBatchPairsFromDevice.argtypes = batch
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -629,6 +640,55 @@ class PFAC:
         buf = data if data.size else np.zeros(1, dtype=np.uint8)
         _, total = self.countFromHost(buf.ctypes.data, data.size, PFACX_COUNT_LONGEST if longest else 0, counts.ctypes.data, counts.size)
         return counts, total
+
+    # -- how often each pattern occurred in each segment, in CSR form (include/pfac_ext.h: PFACX_countBatch*) ------------
+    def _count_batch(self, name: str, items, num_items: int, offsets, num_segments: int, flags: int, ids, counts, capacity: int, seg_first,
+                     check: bool):
+        n, total = C.c_size_t(0), C.c_ulonglong(0)
+        st = getattr(self._lib, name)(self._h, items, num_items, offsets, num_segments, flags, ids, counts, capacity, seg_first, C.byref(n),
+                                      C.byref(total))
+        return self._ret(st, name, check and st != STATUS.OUTPUT_TRUNCATED), n.value, total.value
+
+    def countBatchFromDevice(self, d_input: int, size: int, d_offsets, num_segments: int, flags: int, d_ids, d_counts, capacity: int, d_seg_first,
+                             check: bool = True):
+        """``PFACX_countBatchFromDevice`` -> (status, full length of the count list, sum of all counts): `d_offsets` (num_segments + 1 ``size_t``,
+        device) may be None with one segment, `d_ids` (int) / `d_counts` (unsigned int) may be None with capacity 0, `d_seg_first`
+        (num_segments + 1 ``size_t``, device) is the row pointer.  OUTPUT_TRUNCATED is returned, not raised."""
+        return self._count_batch("PFACX_countBatchFromDevice", d_input, size, d_offsets, num_segments, flags, d_ids, d_counts, capacity, d_seg_first, check)
+
+    def countBatchFromHost(self, h_input: int, size: int, h_offsets, num_segments: int, flags: int, h_ids, h_counts, capacity: int, h_seg_first,
+                           check: bool = True):
+        """``PFACX_countBatchFromHost``: the same over host memory; follows PFAC_setPlatform."""
+        return self._count_batch("PFACX_countBatchFromHost", h_input, size, h_offsets, num_segments, flags, h_ids, h_counts, capacity, h_seg_first, check)
+
+    def countBatchPairsFromDevice(self, d_pair_ids, num_pairs: int, d_seg_first_pairs, num_segments: int, flags: int, d_ids, d_counts, capacity: int,
+                                  d_seg_first, check: bool = True):
+        """``PFACX_countBatchPairsFromDevice``: the same list from a LONGEST id list the caller already has and the first pair of each segment
+        (num_segments + 1 ``int``, device): the output of matchBatchFromDeviceReduce or of a flows call."""
+        return self._count_batch("PFACX_countBatchPairsFromDevice", d_pair_ids, num_pairs, d_seg_first_pairs, num_segments, flags, d_ids, d_counts,
+                                 capacity, d_seg_first, check)
+
+    def count_batch_host_array(self, data, offsets=None, longest: bool = False):
+        """countBatchFromHost over numpy arrays -> (segFirst, ids, counts, total) of the whole count list: the count query first, then arrays of
+        exactly that length; offsets=None: the buffer is one segment."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uintp)
+        segments = 1 if off is None else off.size - 1
+        first = np.full(segments + 1, 0xDEAD, dtype=np.uintp)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        optr = None if off is None else off.ctypes.data
+        flags = PFACX_COUNT_LONGEST if longest else 0
+        st, n, total = self.countBatchFromHost(buf.ctypes.data, data.size, optr, segments, flags, None, None, 0, first.ctypes.data)    # the count query
+        if st not in (0, STATUS.OUTPUT_TRUNCATED):                                 # (a list that does not fit capacity 0: what a query returns)
+            raise PFACError(st, "PFACX_countBatchFromHost", error_string(st))
+        ids = np.full(max(1, n), -7, dtype=np.int32)
+        counts = np.full(max(1, n), 0xDEAD, dtype=np.uint32)
+        st, n2, total2 = self.countBatchFromHost(buf.ctypes.data, data.size, optr, segments, flags, ids.ctypes.data, counts.ctypes.data, n,
+                                                 first.ctypes.data)
+        if st != 0 or n2 != n or total2 != total:                                  # (truncated now: the list grew between the two calls)
+            raise PFACError(st, "PFACX_countBatchFromHost", f"{n2} entries and a total of {total2} behind a count query that said {n} and {total}")
+        return first, ids[:n].copy(), counts[:n].copy(), total
 
     # -- disjoint leftmost-longest matches and their replacement (include/pfac_ext.h: PFACX_matchDisjoint* / PFACX_replace*) ----
     def matchDisjointFromDevice(self, d_input: int, size: int, d_ids: int, d_pos: int, capacity: int, check: bool = True):

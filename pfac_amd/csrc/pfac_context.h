@@ -68,7 +68,8 @@ constexpr HostSlot kHostDisjoint = {40, 42};      /* a disjoint call: one 64-bit
 constexpr HostSlot kHostReplace = {44, 46};       /* a replacement: the 64-bit sum of (replacement - match) lengths; the size of the text is the input's plus that (scan_disjoint.hip) */
 constexpr HostSlot kHostRules = {48, 50};         /* a rules call: the 64-bit length of its fired list (scan_rules.hip, by pfac_array_scan) */
 constexpr HostSlot kHostWordList = {52, 54};      /* a words call: the 64-bit length of its list (scan_words.hip, by pfac_array_scan) */
-constexpr int kHostWords = 56;
+constexpr HostSlot kHostSegCount = {56, 60};      /* a batch count call: two 64-bit values, the length of its count list (scan_segcount.hip, by pfac_array_scan), then the sum of the counts (pfac_segcount_finish) */
+constexpr int kHostWords = 64;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -442,12 +443,16 @@ struct DeviceScratch {
      * 8 (blocks + 1) bytes rounded up to 256, a block per 256 pairs, eight per compute unit at most; the pair list of PFACX_matchWordsFromDevice is
      * allPairs, the prefix table allTable, the pattern lengths patternLen: shared with the all-match and the batch calls */
     DeviceBuffer<char> words;
+    /* the batch count calls (PFACX_countBatch*, scan_segcount.hip): the 64-bit entry counts of the segments and, scanned in place, the first entry
+     * of each, then the 64-bit sum of all counts: 8 (numSegments + 1) + 8 bytes rounded up to 256; the pair list of PFACX_countBatchFromDevice is
+     * allPairs, the first pair of each segment allSegFirst, the prefix table allTable: shared with the all-match and the rules calls */
+    DeviceBuffer<char> segCount;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines);
-        f(spans); f(count); f(disjoint); f(rules); f(words);
+        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }

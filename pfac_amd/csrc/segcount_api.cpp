@@ -1,0 +1,227 @@
+/*
+ * segcount_api.cpp -- PFACX_countBatchFromDevice / ...FromHost / PFACX_countBatchPairsFromDevice (include/pfac_ext.h): how often each pattern
+ * occurred in each segment of a batch, as (id, count) entries in CSR form.
+ *
+ * Every pattern that occurs at a position is a prefix of the longest one there, so all three forms work on longest pairs.  The device form is
+ * PFACX_rulesMatchFromDevice up to its run call -- the ordered compacted scan into the handle's pair scratch (DeviceScratch::allPairs: the ids in its
+ * first half, the positions in its second, `size` entries each), the batch fix-up of PFACX_matchBatchFromDeviceReduce behind it -- and then
+ * PFACX_segCountRun (scan_segcount.hip) over the pairs; the pairs form is that run call alone over the caller's list.  The host form takes the longest
+ * pairs of every segment -- the CPU platforms through hostLongestPairs, segment by segment; the GPU platform through the pipelined batch path -- and
+ * keeps one counter per touched pattern in a loop of its own.
+ */
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "pfac_host.h"
+
+using namespace pfac_internal;
+
+namespace {
+
+constexpr size_t kTwoGiB = size_t(1) << 31;
+
+/* what the three calls check first, in the order of the contract (the pattern set: under the lock); items: the input, or the pair list */
+PFAC_status_t checkArgs(PFAC_handle_t handle, const void *items, size_t numItems, bool itemsRequired, const void *offsets, size_t numSegments,
+                        unsigned int flags, const int *ids, const unsigned int *counts, size_t capacity, const size_t *segFirst,
+                        const size_t *h_numEntries, const unsigned long long *h_total)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if ((itemsRequired && !items) || !h_numEntries || !h_total || (capacity && (!ids || !counts)) || (!offsets && numSegments != 1) ||
+        (numSegments && !segFirst) || (flags & ~PFACX_COUNT_LONGEST))
+        return PFAC_STATUS_INVALID_PARAMETER;
+    if (numItems >= kTwoGiB || numSegments >= kTwoGiB || (numSegments == 0 && numItems > 0)) return PFAC_STATUS_INVALID_PARAMETER;
+    return PFAC_STATUS_SUCCESS;
+}
+
+/* does the call follow the prefix chains?  Not for the longest counts, nor in a set in which no pattern is a prefix of another */
+bool followsChains(const pfac::Automaton &fa, unsigned int flags) { return !(flags & PFACX_COUNT_LONGEST) && fa.maxChain > 1; }
+
+/* the run call of both device forms behind their checks (the caller holds c->lock; numSegments > 0) */
+PFAC_status_t runOnDevice(PFAC_context *c, const int *d_pairIds, size_t count, const int *d_segFirstPairs, size_t numSegments, unsigned int flags,
+                          int *d_ids, unsigned int *d_counts, size_t capacity, size_t *d_segFirst, size_t *h_numEntries, unsigned long long *h_total)
+{
+    PFACX_segCountRun_t run{};
+    run.d_pairIds = d_pairIds;
+    run.count = count;
+    run.d_segFirstPairs = d_segFirstPairs;
+    run.numSegments = numSegments;
+    run.d_table = followsChains(c->fa, flags) ? c->scratch.allTable.get() : nullptr;
+    run.numIds = (size_t)c->fa.numPatterns;
+    run.d_ids = d_ids;
+    run.d_counts = d_counts;
+    run.capacity = capacity;
+    run.d_segFirst = d_segFirst;
+    size_t entries = 0;
+    unsigned long long total = 0;
+    const PFAC_status_t st = c->segcount_run_ptr(c, &run, &entries, &total);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    *h_numEntries = entries;
+    *h_total = total;
+    return truncatedIf(entries, capacity);
+}
+
+/* nothing to count on the device: zeros, segFirst zeroed */
+PFAC_status_t nothingOnDevice(size_t *d_segFirst, size_t numSegments, size_t *h_numEntries, unsigned long long *h_total)
+{
+    if (numSegments && hipMemset(d_segFirst, 0, (numSegments + 1) * sizeof(size_t)) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+    *h_numEntries = 0;
+    *h_total = 0;
+    return PFAC_STATUS_SUCCESS;
+}
+
+/* The count list of a batch whose longest pairs are known: the ids of segment k at ids[first[k], first[k] + numPairs[k]).  Returns the full length */
+size_t countsOnHost(const pfac::Automaton &fa, unsigned int flags, const int *ids, const size_t *first, const int *numPairs, size_t numSegments,
+                    int *outIds, unsigned int *outCounts, size_t capacity, size_t *segFirst, unsigned long long *sum)
+{
+    const bool chains = followsChains(fa, flags);
+    std::vector<unsigned int> counter((size_t)fa.numPatterns + 1, 0u);
+    std::vector<int> touched;
+    size_t total = 0;
+    unsigned long long all = 0;
+    for (size_t k = 0; k < numSegments; k++) {
+        segFirst[k] = total;
+        touched.clear();
+        auto add = [&](int q) {
+            if (counter[(size_t)q]++ == 0) touched.push_back(q);
+            return true;
+        };
+        for (int i = 0; i < numPairs[k]; i++) {
+            const int id = ids[first[k] + (size_t)i];
+            if (chains) forEachChainMember(fa, id, add);
+            else if (id >= 1 && id <= fa.numPatterns) add(id);
+        }
+        std::sort(touched.begin(), touched.end());
+        for (int q : touched) {
+            if (total < capacity) { outIds[total] = q; outCounts[total] = counter[(size_t)q]; }
+            all += counter[(size_t)q];
+            counter[(size_t)q] = 0;
+            total++;
+        }
+    }
+    segFirst[numSegments] = total;
+    *sum = all;
+    return total;
+}
+
+} // namespace
+
+extern "C" {
+
+PFAC_status_t PFACX_countBatchFromDevice(PFAC_handle_t handle, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                                         unsigned int flags, int *d_ids, unsigned int *d_counts, size_t capacity, size_t *d_segFirst,
+                                         size_t *h_numEntries, unsigned long long *h_total)
+{
+    PFAC_status_t st = checkArgs(handle, d_input, size, true, d_offsets, numSegments, flags, d_ids, d_counts, capacity, d_segFirst, h_numEntries, h_total);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    PFAC_context *c = handle;
+    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
+    std::lock_guard<std::mutex> guard(c->lock);
+    if (!c->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
+    if (size == 0) return nothingOnDevice(d_segFirst, numSegments, h_numEntries, h_total);
+    if (followsChains(c->fa, flags)) st = ensureAllTable(c);
+    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = ensurePatternLen(c);              /* the fix-up's */
+    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = c->scratch.allSegFirst.reserve(numSegments + 1);
+    pfac::DeviceBuffer<int> &pairs = c->scratch.allPairs;
+    if (st == PFAC_STATUS_SUCCESS) st = pairs.reserve(2 * size);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    int *ids = pairs.get(), *pos = ids + pairs.count() / 2;               /* one allocation: the ids, then as many positions */
+    DeviceScan scan;                                                      /* a caseless set: the scan and the fix-up read the folded bytes */
+    st = beginDeviceScan(c, d_input, size, &scan);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    int count = 0;
+    st = reduceOnDevice(c, scan.d_scan, size, ids, pos, true, &count);          /* ordered: the fix-up and the segments' first pairs search the positions */
+    if (st == PFAC_STATUS_SUCCESS && d_offsets)
+        st = c->batch_reduce_fixup_ptr(c, scan.d_scan, size, d_offsets, numSegments, ids, pos, &count, c->scratch.allSegFirst.get(), c->scratch.patternLen.get());
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (count < 0) return PFAC_STATUS_INTERNAL_ERROR;
+    return runOnDevice(c, ids, (size_t)count, d_offsets ? c->scratch.allSegFirst.get() : nullptr, numSegments, flags, d_ids, d_counts, capacity,
+                       d_segFirst, h_numEntries, h_total);
+}
+
+PFAC_status_t PFACX_countBatchPairsFromDevice(PFAC_handle_t handle, const int *d_pairIds, size_t numPairs, const int *d_segFirstPairs,
+                                              size_t numSegments, unsigned int flags, int *d_ids, unsigned int *d_counts, size_t capacity,
+                                              size_t *d_segFirst, size_t *h_numEntries, unsigned long long *h_total)
+{
+    PFAC_status_t st = checkArgs(handle, d_pairIds, numPairs, numPairs != 0, d_segFirstPairs, numSegments, flags, d_ids, d_counts, capacity, d_segFirst,
+                                 h_numEntries, h_total);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    PFAC_context *c = handle;
+    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
+    std::lock_guard<std::mutex> guard(c->lock);
+    if (!c->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
+    if (numPairs == 0) return nothingOnDevice(d_segFirst, numSegments, h_numEntries, h_total);
+    if (followsChains(c->fa, flags)) st = ensureAllTable(c);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    return runOnDevice(c, d_pairIds, numPairs, d_segFirstPairs, numSegments, flags, d_ids, d_counts, capacity, d_segFirst, h_numEntries, h_total);
+}
+
+PFAC_status_t PFACX_countBatchFromHost(PFAC_handle_t handle, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments,
+                                       unsigned int flags, int *h_ids, unsigned int *h_counts, size_t capacity, size_t *h_segFirst,
+                                       size_t *h_numEntries, unsigned long long *h_total)
+{
+    PFAC_status_t st = checkArgs(handle, h_input, size, true, h_offsets, numSegments, flags, h_ids, h_counts, capacity, h_segFirst, h_numEntries, h_total);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (h_offsets && numSegments && !batchOffsetsValid(h_offsets, numSegments, size)) return PFAC_STATUS_INVALID_PARAMETER;
+    PFAC_context *c = handle;
+    const size_t whole[2] = {0, size};
+    const size_t *offsets = h_offsets ? h_offsets : whole;
+    const bool onGpu = c->platform == PFAC_PLATFORM_GPU;
+    std::unique_lock<std::mutex> guard(c->lock);
+    if (!c->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
+    const unsigned long long generation = c->setGeneration;                    /* the set every scan below has to see */
+    if (size == 0) {
+        if (numSegments) std::memset(h_segFirst, 0, (numSegments + 1) * sizeof(size_t));
+        *h_numEntries = 0;
+        *h_total = 0;
+        return PFAC_STATUS_SUCCESS;
+    }
+    if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
+    size_t longest = 0;
+    for (size_t k = 0; k < numSegments; k++) longest = std::max(longest, offsets[k + 1] - offsets[k]);
+    const HostPairs pairs(size, onGpu ? 0 : longest);                           /* the longest ids of segment k from ids[offsets[k]] on; the positions are not kept */
+    int *const ids = pairs.ids, *const pos = pairs.pos;
+    std::vector<int> numPairs;
+    try {
+        numPairs.assign(numSegments, 0);
+    } catch (const std::bad_alloc &) {
+        return PFAC_STATUS_ALLOC_FAILED;
+    }
+    if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
+    if (onGpu) {
+        /* the pipelined batch path: the full result of every segment, compacted in place (pair z of a segment comes from an entry at or behind z) */
+        st = matchBatchHostOnGpu(c, h_input, size, offsets, numSegments, ids);
+        if (st != PFAC_STATUS_SUCCESS) return st;
+        for (size_t k = 0; k < numSegments; k++) {
+            int z = 0;
+            for (size_t i = offsets[k]; i < offsets[k + 1]; i++)
+                if (ids[i] > 0) ids[offsets[k] + (size_t)z++] = ids[i];
+            numPairs[k] = z;
+        }
+    } else {
+        guard.unlock();                                     /* the CPU platforms: the helper takes the lock while it prepares the tables, several threads match side by side */
+        for (size_t k = 0; k < numSegments; k++) {
+            const size_t n = offsets[k + 1] - offsets[k];
+            if (n == 0) continue;
+            st = hostLongestPairs(c, h_input + offsets[k], n, ids + offsets[k], pos, &numPairs[k], nullptr);
+            if (st != PFAC_STATUS_SUCCESS) return st;
+        }
+    }
+    /* generations only count up: the set is the one the call started on now, so it was during every scan above (on the GPU platform the lock is still held) */
+    const SetPin pin(c, generation);
+    if (pin.status() != PFAC_STATUS_SUCCESS) return pin.status();              /* another thread has replaced the set meanwhile: no count is written */
+    try {
+        unsigned long long sum = 0;
+        const size_t total = countsOnHost(c->fa, flags, ids, offsets, numPairs.data(), numSegments, h_ids, h_counts, capacity, h_segFirst, &sum);
+        *h_numEntries = total;
+        *h_total = sum;
+        return truncatedIf(total, capacity);
+    } catch (const std::bad_alloc &) {
+        return PFAC_STATUS_ALLOC_FAILED;
+    }
+}
+
+} /* extern "C" */

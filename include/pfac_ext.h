@@ -17,9 +17,10 @@
  * PFACX_countNonzeroFromDevice) and the disjoint leftmost-longest matches
  * with their replacement by a string per pattern (PFACX_matchDisjoint*,
  * PFACX_replaceFromDevice / ...FromHost), rule sets (PFACX_rules*), the
- * counts of every pattern in every segment (PFACX_countBatch*) and the
+ * counts of every pattern in every segment (PFACX_countBatch*), the
  * occurrences bounded by bytes outside a class: whole words, lines and
- * fields (PFACX_matchWords*, PFACX_wordsPairsFromDevice).
+ * fields (PFACX_matchWords*, PFACX_wordsPairsFromDevice) and pattern
+ * groups: each segment of a batch sees only its own patterns (PFACX_groups*).
  */
 #ifndef PFAC_EXT_H_
 #define PFAC_EXT_H_
@@ -822,6 +823,79 @@ PFAC_status_t PFACX_matchWordsFromHost  (PFAC_handle_t handle, char *h_input, si
 PFAC_status_t PFACX_wordsPairsFromDevice(PFAC_handle_t handle, const char *d_input, size_t size, const unsigned int *h_class /* 8 words or NULL */,
                                          unsigned int flags, const int *d_pairIds, const int *d_pairPos, size_t numPairs,
                                          int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched);
+
+/* Pattern groups: each segment of a batch sees only its own patterns -- the fast-pattern set of a packet's port groups in an IDS, a tenant's keyword
+ * list over that tenant's records, a per-language stop list per document -- with ONE compiled set and ONE scan over the whole batch.
+ *   There are 64 GROUPS.  Pattern id has the mask M[id] = h_patternMasks[id] (numMasks >= F + 1 entries, entry 0 ignored; fewer:
+ *   PFAC_STATUS_INVALID_PARAMETER); bit g set: the pattern is in group g.  PFACX_groupsOpen copies the table.  Duplicate pattern lines are one
+ *   pattern, reported under the highest of their ids as everywhere; the mask of the reported id is the OR of the masks of ALL ids that name that
+ *   pattern (the same string in two port groups, under two ids, belongs to both -- the resolution PFACX_rulesOpen does for ids), and the ids that
+ *   are never reported end with mask 0.  A pattern whose mask is 0 is never reported by these calls.
+ *   Segment k has the mask segMasks[k]; segMasks == NULL: every segment has all 64 bits set.  Pattern id is ENABLED in segment k if
+ *   M[id] & segMasks[k] is non-zero.
+ *   THE ALL-MATCH LIST of segment k is that of PFACX_matchAllBatchFromDevice: occurrences wholly inside the segment, positions relative to the
+ *   buffer and ascending, within one position the longest pattern first.
+ *   THE GROUP LIST, with PFACX_GROUPS_ALL: the all-match list of every segment without the pairs of patterns that are not enabled in that segment,
+ *   the segments concatenated.  With flags 0: the first pair of each position of that list -- THE LONGEST ENABLED PATTERN at each position that has
+ *   one.  That is not a filter over the longest pairs: where the longest pattern at a position belongs to another group, a proper prefix of it that
+ *   is enabled is reported (`foo` in group 0, `foobar` in group 1, "foobar" in a segment of group 0: `foo`).
+ *   CONSEQUENCES: all pattern masks and all segment masks ~0: ALL is exactly the list of PFACX_matchAllBatchFromDevice, flags 0 exactly the list of
+ *   PFACX_matchBatchFromDeviceReduce.  A segment mask of 0 gives an empty segment.  A caseless handle (PFACX_READ_NOCASE) folds as in every other
+ *   call.  No input byte is ever read by the pass behind the scan, and the caller's buffers are never modified.
+ * segFirst (numSegments + 1 size_t, optional): entries [segFirst[k], segFirst[k + 1]) of the list are segment k's pairs; complete also under truncation.
+ * segGroups (numSegments 64-bit words, optional): segGroups[k] = the OR of M[id] & segMasks[k] over ALL enabled occurrences of segment k, whatever
+ * the flags and the capacity: "which groups have a hit in this segment", the prefilter answer an IDS asks for; available with capacity == 0; a
+ * segment without a hit gets 0.
+ * `capacity` (entries of each pair array) is free, as for the fired list of PFACX_rules*: the scan's pair list lives in the handle's pair scratch,
+ * never in the caller's arrays.  A list longer than capacity: exactly its first `capacity` pairs are written and nothing at or behind `capacity`,
+ * *h_num_matched is the full length, segFirst and segGroups are complete, and the call returns PFACX_STATUS_OUTPUT_TRUNCATED; with capacity == 0
+ * the two pair arrays may be null: the count query.
+ * Offsets follow the rules of PFACX_matchBatch*: host offsets are validated; device offsets and device segment masks are the caller's contract,
+ * clamped and never checked (wrong offsets: a wrong list, never an access outside the buffers).  offsets == NULL with numSegments == 1: the whole
+ * buffer is one segment -- the plain "subset of the set" call.
+ * PFAC_STATUS_INVALID_PARAMETER: size >= 2^31, numSegments >= 2^31, an unknown flag bit, a required null pointer, offsets == NULL with numSegments
+ * != 1, numSegments == 0 with size > 0, numMasks < F + 1.  No pattern set at open: PFAC_STATUS_PATTERNS_NOT_READY.  size == 0: success, 0 pairs,
+ * segFirst and segGroups zeroed where given.  A device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST; opening on one works.  After the
+ * handle reads or loads another pattern set every match call returns PFAC_STATUS_INVALID_PARAMETER and only PFACX_groupsClose works.  PFAC_destroy
+ * closes the handle's group tables, as it closes rule sets.  All calls are synchronous and take the handle's lock.  The device forms run on
+ * whatever kernel variant, walker, perf mode and texture mode the handle selects; the host form follows PFAC_setPlatform like
+ * PFACX_countBatchFromHost: the CPU platforms, host-only handles included, run on the CPU -- the longest pairs segment by segment, then their
+ * prefix chains (temporaries: 8 bytes per input byte, 4 per segment) --, the GPU platform runs the pipelined path of PFACX_matchBatchFromHost and
+ * the same loop.  A pattern set that another thread replaces during a host call: PFAC_STATUS_INVALID_PARAMETER, as after the call.
+ * PFACX_groupsPairsFromDevice runs no scan: it takes a LONGEST list with the first pair of each segment -- d_matched_result, d_pos and d_segFirst of
+ * PFACX_matchBatchFromDeviceReduce, or ids, pos and pieceFirst of a PFACX_flows* call, which PFACX_wordsPairsFromDevice cannot take: this pass
+ * reads no input.  Positions are copied through as they are, negative ones included: that gives per-flow groups.  The arrays are DEVICE memory and
+ * the caller's contract: an id outside [1, F] is ignored and never used as an index; every entry of d_segFirstPairs (numSegments + 1 ints; NULL
+ * with numSegments == 1: one segment of all pairs) is clamped to [0, numPairs] and then raised to the largest entry in front of it, so a
+ * decreasing pair is an empty segment; pairs before the first or behind the last bound belong to no segment.  Output arrays that overlap the
+ * input pair arrays: PFAC_STATUS_INVALID_PARAMETER; numPairs >= 2^31 too.  numPairs == 0: success with zeros.
+ * MEMORY of the device forms.  The mask table, 8 (F + 1) bytes made by the first device call, is state like a rule set's tables: counted under
+ * deviceTableBytes, kept by PFACX_trim, freed by PFACX_groupsClose.  Grow-only handle scratch (deviceScratchBytes, freed by PFACX_trim): 8 (B + 1)
+ * bytes rounded up to 256, B = one block per 256 longest pairs, eight per compute unit at most, and with a segment array 4 (numSegments + 1) bytes
+ * rounded up to 256 for its bounds; PFACX_groupsMatchFromDevice also what the scan shares with PFACX_countBatchFromDevice (the pair list, the first
+ * pair of each segment, the pattern lengths, the fix-up's scratch); a set in which a pattern is a prefix of another the {prefix, chain length}
+ * table of PFACX_matchAll*.  Nothing is sized by segments x patterns.
+ * COST: the ordered compacted batch scan, then two passes over the pairs that walk each pair's chain through two 8-byte tables and
+ * a one-block scan between them: the extra over the scan follows the pairs and the segments, not the bytes.
+ * OUT OF SCOPE: more than 64 groups; changing masks without close and reopen; a per-pair output of the groups that hit (the caller has M[id] &
+ * segMasks[k]); groups inside PFACX_rules* or PFACX_countBatch* (feed their pairs forms); carried state across flows calls. */
+typedef struct PFACX_groups_s *PFACX_groups_t;
+#define PFACX_GROUPS_ALL 1u   /* every enabled occurrence instead of the longest enabled one per position */
+PFAC_status_t PFACX_groupsOpen (PFAC_handle_t handle, const unsigned long long *h_patternMasks, size_t numMasks /* >= F + 1 */, PFACX_groups_t *groups);
+PFAC_status_t PFACX_groupsClose(PFACX_groups_t groups);
+PFAC_status_t PFACX_groupsMatchFromDevice(PFACX_groups_t groups, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                                          const unsigned long long *d_segMasks /* numSegments, may be NULL */, unsigned int flags,
+                                          int *d_ids, int *d_pos, size_t capacity, size_t *d_segFirst /* numSegments + 1, may be NULL */,
+                                          unsigned long long *d_segGroups /* numSegments, may be NULL */, size_t *h_num_matched);
+PFAC_status_t PFACX_groupsMatchFromHost  (PFACX_groups_t groups, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments,
+                                          const unsigned long long *h_segMasks, unsigned int flags,
+                                          int *h_ids, int *h_pos, size_t capacity, size_t *h_segFirst, unsigned long long *h_segGroups,
+                                          size_t *h_num_matched);
+PFAC_status_t PFACX_groupsPairsFromDevice(PFACX_groups_t groups, const int *d_pairIds, const int *d_pairPos, size_t numPairs,
+                                          const int *d_segFirstPairs /* numSegments + 1; NULL with numSegments == 1 */, size_t numSegments,
+                                          const unsigned long long *d_segMasks, unsigned int flags,
+                                          int *d_ids, int *d_pos, size_t capacity, size_t *d_segFirst, unsigned long long *d_segGroups,
+                                          size_t *h_num_matched);
 
 #ifdef __cplusplus
 }

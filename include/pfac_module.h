@@ -278,6 +278,35 @@ typedef struct {
 } PFACX_segCountRun_t;
 PFAC_status_t PFACX_segCountRun(PFAC_handle_t handle, const PFACX_segCountRun_t *run, size_t *h_numEntries, unsigned long long *h_total);
 
+/* Pattern groups (no reference counterpart; include/pfac_ext.h: PFACX_groups*), scan_groups.hip.
+ * PFACX_groupsRun: the group list of a batch from its ordered LONGEST pairs.  d_pairIds / d_pairPos[0, count), count < 2^31: one pair per position,
+ * ordered by segment -- the handle's pair scratch behind the ordered compacted batch scan, or a caller's list: an id outside [1, numIds] is a pair
+ * that gives nothing, a position is copied through and never used as an index.  d_segFirstPairs (numSegments + 1 ints: the first pair of each
+ * segment, clamped to [0, count] and raised to the largest entry in front of it where it is read: a decreasing pair is an empty segment, pairs
+ * before the first or behind the last bound belong to no segment), or null with numSegments == 1: one segment of all pairs.  d_segMasks: numSegments
+ * 64-bit masks, or null: all bits set.  d_patternMasks: numIds + 1 64-bit masks by id.  d_table: pfac::Int2 {prefixPattern, chainLen} by id,
+ * numIds + 1 entries, or null: every chain is the pair itself.  all == 0: per pair the longest member of its chain whose mask meets the segment's;
+ * else every such member, longest first.  Output: (id, position) into d_ids / d_pos, nothing at or beyond `capacity` (0: both may be null);
+ * d_segFirst (numSegments + 1 size_t, or null) indexes the whole list; d_segGroups (numSegments 64-bit words, or null): the OR of mask & segment
+ * mask over every member of every chain of the segment, whatever `all` and `capacity`; *h_total = the full length of the list.  The output arrays
+ * must not overlap the pair arrays (the caller checks).  0 < numSegments < 2^31.  Synchronous. */
+typedef struct {
+    const int *d_pairIds, *d_pairPos;
+    size_t count;
+    const int *d_segFirstPairs;
+    size_t numSegments;
+    const unsigned long long *d_segMasks;
+    const unsigned long long *d_patternMasks;
+    const void *d_table;
+    size_t numIds;
+    unsigned int all;
+    int *d_ids, *d_pos;
+    size_t capacity;
+    size_t *d_segFirst;
+    unsigned long long *d_segGroups;
+} PFACX_groupsRun_t;
+PFAC_status_t PFACX_groupsRun(PFAC_handle_t handle, const PFACX_groupsRun_t *run, size_t *h_total);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -291,7 +320,8 @@ PFAC_status_t PFACX_segCountRun(PFAC_handle_t handle, const PFACX_segCountRun_t 
     X(spans_select_ptr, PFACX_spansSelect) X(spans_redact_ptr, PFACX_spansRedact) \
     X(count_pairs_ptr, PFACX_countPairs) X(count_nonzero_ptr, PFACX_countNonzero) \
     X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun) \
-    X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun) X(segcount_run_ptr, PFACX_segCountRun)
+    X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun) X(segcount_run_ptr, PFACX_segCountRun) \
+    X(groups_run_ptr, PFACX_groupsRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

@@ -14,7 +14,9 @@ importing :mod:`pfac_amd.api` fails loudly if the libraries are missing.
 """
 
 from .api import (  # noqa: F401
+    Groups,
     PFAC,
+    PFACX_GROUPS_ALL,
     PFACError,
     PFAC_AUTOMATIC,
     PFAC_PLATFORM_CPU,

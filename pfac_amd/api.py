@@ -31,6 +31,8 @@ PFACX_LINES_INVERT = 1                          # pfac_ext.h: PFACX_matchLines* 
 PFACX_COUNT_LONGEST = 1                         # pfac_ext.h: PFACX_count* count one pattern per position, the longest
 PFACX_COUNT_ACCUMULATE = 2                      # ... add to counts[] instead of overwriting it
 PFACX_WORDS_ALL = 1                             # pfac_ext.h: PFACX_matchWords* report every bounded occurrence, not the longest per position
+PFACX_GROUPS_ALL = 1                            # pfac_ext.h: PFACX_groups* report every enabled occurrence, not the longest enabled one per position
+PFACX_GROUPS_BLOCK = 256                        # scan_groups.hip: kGroupsBlock, the pairs one block of the group passes takes (never more than eight blocks per CU)
 PFACX_WORDS_BLOCK = 256                         # scan_words.hip: kWordsBlock, the pairs one block of the boundary passes takes (never more than eight blocks per CU)
 PFACX_DISJOINT_BLOCK = 512                      # scan_disjoint.hip: kDisjointBlock, the pairs one block of the selection takes
 PFACX_REPLACE_TILE = 4096                       # scan_disjoint.hip: kReplaceTile, the output bytes of one tile of the replacement
@@ -130,6 +132,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_rulesOpen", "PFACX_rulesOpenEx", "PFACX_rulesClose", "PFACX_rulesMatchFromDevice", "PFACX_rulesMatchFromHost",
     "PFACX_matchWordsFromDevice", "PFACX_matchWordsFromHost", "PFACX_wordsPairsFromDevice",
     "PFACX_countBatchFromDevice", "PFACX_countBatchFromHost", "PFACX_countBatchPairsFromDevice",
+    "PFACX_groupsOpen", "PFACX_groupsClose", "PFACX_groupsMatchFromDevice", "PFACX_groupsMatchFromHost", "PFACX_groupsPairsFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -144,6 +147,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_rulesRun",
     "PFACX_wordsRun",
     "PFACX_segCountRun",
+    "PFACX_groupsRun",
 )
 
 
@@ -275,6 +279,16 @@ def load_library() -> C.CDLL:
         lib.PFACX_countBatchFromDevice.argtypes = batch
         lib.PFACX_countBatchFromHost.argtypes = batch
         lib.PFACX_countBatchPairsFromDevice.argtypes = batch
+    if hasattr(lib, "PFACX_groupsOpen"):
+        SZ = C.POINTER(C.c_size_t)
+        lib.PFACX_groupsOpen.argtypes = [H, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        lib.PFACX_groupsClose.argtypes = [C.c_void_p]
+        groups = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                  C.c_void_p, SZ]
+        lib.PFACX_groupsMatchFromDevice.argtypes = groups
+        lib.PFACX_groupsMatchFromHost.argtypes = groups
+        lib.PFACX_groupsPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint,
+                                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, SZ]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -801,6 +815,27 @@ class PFAC:
         self._ret(st, "PFACX_rulesOpenEx", check)
         return Rules(self, s, max(0, off.size - 1), st)
 
+    # -- pattern groups: each segment sees only its own patterns (include/pfac_ext.h: PFACX_groups*) ----------------
+    def groupsOpen(self, pattern_masks, check: bool = True) -> "Groups":
+        """``PFACX_groupsOpen`` -> a :class:`Groups` table of this handle (``.status`` holds the call's status): ``pattern_masks[id]`` is the
+        64-bit group mask of pattern id (entry 0 ignored; at least F + 1 entries); the array is copied."""
+        import numpy as np
+        masks = np.ascontiguousarray(pattern_masks, dtype=np.uint64)
+        buf = masks if masks.size else np.zeros(1, dtype=np.uint64)
+        g = C.c_void_p()
+        st = self._lib.PFACX_groupsOpen(self._h, buf.ctypes.data, masks.size, C.byref(g))
+        self._ret(st, "PFACX_groupsOpen", check)
+        return Groups(self, g, st)
+
+    def match_groups_host_array(self, data, pattern_masks, offsets=None, seg_masks=None, all_matches: bool = False):
+        """groupsOpen, groupsMatchFromHost over numpy arrays and groupsClose -> (pos, ids, segFirst, segGroups) of the whole group list: the count
+        query first, then arrays of exactly that length; offsets=None: the buffer is one segment, seg_masks=None: every segment has all bits."""
+        g = self.groupsOpen(pattern_masks)
+        try:
+            return g.match_host_array(data, offsets, seg_masks, all_matches)
+        finally:
+            g.close(check=False)
+
     # -- numpy conveniences over matchFromHost (still the C ABI underneath) ----------
     def match_host_array(self, data):
         import numpy as np
@@ -1016,6 +1051,77 @@ class Flows:
         flb = fl if fl.size else np.zeros(1, dtype=np.uint32)
         st, n = self.flush(flb.ctypes.data, fl.size, ids.ctypes.data, pos.ctypes.data, cap, first.ctypes.data, check=check)
         return st, ids[:n].copy(), pos[:n].copy(), first
+
+
+class Groups:
+    """One group table (``PFACX_groups_t``) of a handle: a batch of segments and a 64-bit mask per segment in, the matches of the patterns
+    whose mask meets their segment's out.  Every match call returns ``(status, full length of the list)``; OUTPUT_TRUNCATED is returned, not
+    raised."""
+
+    def __init__(self, handle: "PFAC", groups: C.c_void_p, status: int = 0):
+        self._owner = handle
+        self._lib = handle._lib
+        self._g = groups
+        self.status = status
+
+    def _ret(self, st: int, where: str, check: bool) -> int:
+        if check and st != 0:
+            raise PFACError(st, where, error_string(st))
+        return st
+
+    def match_device(self, d_input: int, size: int, d_offsets, num_segments: int, d_seg_masks, flags: int, d_ids, d_pos, capacity: int,
+                     d_seg_first, d_seg_groups, check: bool = True):
+        """``PFACX_groupsMatchFromDevice``: `d_offsets` (num_segments + 1 ``size_t``, device) may be None with one segment, `d_seg_masks`
+        (num_segments ``uint64``), `d_seg_first` (num_segments + 1 ``size_t``) and `d_seg_groups` (num_segments ``uint64``) may be None, the two
+        pair arrays may be None with capacity 0."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_groupsMatchFromDevice(self._g, d_input, size, d_offsets, num_segments, d_seg_masks, flags, d_ids, d_pos, capacity,
+                                                   d_seg_first, d_seg_groups, C.byref(n))
+        return self._ret(st, "PFACX_groupsMatchFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def match_host(self, h_input: int, size: int, h_offsets, num_segments: int, h_seg_masks, flags: int, h_ids, h_pos, capacity: int, h_seg_first,
+                   h_seg_groups, check: bool = True):
+        """``PFACX_groupsMatchFromHost``: follows PFAC_setPlatform (the CPU platforms run on the CPU)."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_groupsMatchFromHost(self._g, h_input, size, h_offsets, num_segments, h_seg_masks, flags, h_ids, h_pos, capacity,
+                                                 h_seg_first, h_seg_groups, C.byref(n))
+        return self._ret(st, "PFACX_groupsMatchFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def pairs_device(self, d_pair_ids, d_pair_pos, num_pairs: int, d_seg_first_pairs, num_segments: int, d_seg_masks, flags: int, d_ids, d_pos,
+                     capacity: int, d_seg_first, d_seg_groups, check: bool = True):
+        """``PFACX_groupsPairsFromDevice``: the same list from a LONGEST pair list the caller already has and the first pair of each segment
+        (num_segments + 1 ``int``, device): the output of matchBatchFromDeviceReduce or of a flows call.  It runs no scan."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_groupsPairsFromDevice(self._g, d_pair_ids, d_pair_pos, num_pairs, d_seg_first_pairs, num_segments, d_seg_masks, flags,
+                                                   d_ids, d_pos, capacity, d_seg_first, d_seg_groups, C.byref(n))
+        return self._ret(st, "PFACX_groupsPairsFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def close(self, check: bool = True) -> int:
+        st = self._lib.PFACX_groupsClose(self._g)
+        self._g = C.c_void_p()
+        return self._ret(st, "PFACX_groupsClose", check)
+
+    def match_host_array(self, data, offsets=None, seg_masks=None, all_matches: bool = False):
+        """match_host over numpy arrays -> (pos, ids, segFirst, segGroups) of the whole group list; offsets=None: the buffer is one segment."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uintp)
+        segments = 1 if off is None else off.size - 1
+        sm = None if seg_masks is None else np.ascontiguousarray(seg_masks, dtype=np.uint64)
+        first = np.full(segments + 1, 0xDEAD, dtype=np.uintp)
+        hit = np.full(max(1, segments), 0xDEAD, dtype=np.uint64)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        optr = None if off is None else off.ctypes.data
+        mptr = None if sm is None or sm.size == 0 else sm.ctypes.data
+        flags = PFACX_GROUPS_ALL if all_matches else 0
+        _, n = self.match_host(buf.ctypes.data, data.size, optr, segments, mptr, flags, None, None, 0, first.ctypes.data, hit.ctypes.data)   # the count query
+        ids = np.full(max(1, n), -7, dtype=np.int32)
+        pos = np.full(max(1, n), -7, dtype=np.int32)
+        st, n2 = self.match_host(buf.ctypes.data, data.size, optr, segments, mptr, flags, ids.ctypes.data, pos.ctypes.data, n, first.ctypes.data,
+                                 hit.ctypes.data)
+        if st != 0 or n2 != n:
+            raise PFACError(st, "PFACX_groupsMatchFromHost", f"{n2} pairs behind a count query that said {n}")
+        return pos[:n].copy(), ids[:n].copy(), first, hit[:segments].copy()
 
 
 def rule_member_dtype():

@@ -404,6 +404,7 @@ PFAC_status_t PFAC_destroy(PFAC_handle_t handle)
     closeAllStreams(handle);
     closeAllFlowSets(handle);
     closeAllRuleSets(handle);
+    closeAllGroupTables(handle);
     freeResources(handle);
     /* drops this handle's reference; the module stays mapped while other handles hold theirs (dlopen refcounts) */
     if (handle->module) dlclose(handle->module);
@@ -652,7 +653,7 @@ PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info)
         /* what the pattern set holds on the device -- the chained tables, the initial row, the prefilter bitmaps, the launch counters, the
          * reference-layout table only while PFACX_KERNEL_REFTABLE has asked for it -- the carried bytes of device-fed streams and the tables of rule sets: state, not
          * scratch (PFACX_trim keeps them) */
-        v.deviceTableBytes = handle->tables.bytes() + streamDeviceBytes(handle) + flowsDeviceBytes(handle) + rulesDeviceBytes(handle);
+        v.deviceTableBytes = handle->tables.bytes() + streamDeviceBytes(handle) + flowsDeviceBytes(handle) + rulesDeviceBytes(handle) + groupsDeviceBytes(handle);
         /* ... and what its calls have left allocated (grow-only, PFACX_trim gives it back) */
         v.deviceScratchBytes = handle->scratch.bytes();
         if (handle->h_modeHint) {

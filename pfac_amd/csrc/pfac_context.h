@@ -69,6 +69,7 @@ constexpr HostSlot kHostReplace = {44, 46};       /* a replacement: the 64-bit s
 constexpr HostSlot kHostRules = {48, 50};         /* a rules call: the 64-bit length of its fired list (scan_rules.hip, by pfac_array_scan) */
 constexpr HostSlot kHostWordList = {52, 54};      /* a words call: the 64-bit length of its list (scan_words.hip, by pfac_array_scan) */
 constexpr HostSlot kHostSegCount = {56, 60};      /* a batch count call: two 64-bit values, the length of its count list (scan_segcount.hip, by pfac_array_scan), then the sum of the counts (pfac_segcount_finish) */
+constexpr HostSlot kHostGroups = {62, 61};        /* a groups call: the 64-bit length of its list (scan_groups.hip, by pfac_array_scan) */
 constexpr int kHostWords = 64;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
@@ -447,12 +448,17 @@ struct DeviceScratch {
      * of each, then the 64-bit sum of all counts: 8 (numSegments + 1) + 8 bytes rounded up to 256; the pair list of PFACX_countBatchFromDevice is
      * allPairs, the first pair of each segment allSegFirst, the prefix table allTable: shared with the all-match and the rules calls */
     DeviceBuffer<char> segCount;
+    /* the groups calls (PFACX_groups*, scan_groups.hip): the 64-bit list offsets of the blocks of its pair passes, 8 (blocks + 1) bytes rounded up
+     * to 256, a block per 256 pairs, eight per compute unit at most; then, with a segment array, the segments' bounds in the pair list, 4
+     * (numSegments + 1) bytes rounded up to 256; the pair list of PFACX_groupsMatchFromDevice is allPairs, the first pair of each segment
+     * allSegFirst, the prefix table allTable: shared.  The mask table of a group handle is state of that handle, not scratch (groups_api.cpp) */
+    DeviceBuffer<char> groups;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines);
-        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount);
+        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }
@@ -544,6 +550,8 @@ struct PFAC_context {
     std::vector<PFACX_flows_s *> flowSets;
     /* rule sets (PFACX_rules*, rules_api.cpp): the open sets of this handle (PFAC_destroy closes them); their device tables are state like the carries */
     std::vector<PFACX_rules_s *> ruleSets;
+    /* group tables (PFACX_groups*, groups_api.cpp): the open tables of this handle (PFAC_destroy closes them); their device copies are state likewise */
+    std::vector<PFACX_groups_s *> groupSets;
     void *h_flowPieces = nullptr;             /* pinned host memory a flows call builds its piece descriptors in (grow-only; freed with the scratch) */
     size_t h_flowPiecesBytes = 0;
 

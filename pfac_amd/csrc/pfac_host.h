@@ -183,6 +183,9 @@ size_t flowsDeviceBytes(const PFAC_context *c);
 /* rules_api.cpp: PFAC_destroy closes the handle's rule sets; the device bytes their tables hold (PFACX_getInfo: deviceTableBytes) */
 void closeAllRuleSets(PFAC_context *c);
 size_t rulesDeviceBytes(const PFAC_context *c);
+/* groups_api.cpp: PFAC_destroy closes the handle's group tables; the device bytes their mask tables hold (PFACX_getInfo: deviceTableBytes) */
+void closeAllGroupTables(PFAC_context *c);
+size_t groupsDeviceBytes(const PFAC_context *c);
 /* batch_api.cpp: offsets[0] == 0, offsets[n] == size, never decreasing */
 bool batchOffsetsValid(const size_t *offsets, size_t numSegments, size_t size);
 /* batch_api.cpp: the batch calls (PFACX_matchBatch*) behind their argument checks; the caller holds c->lock */

@@ -1,6 +1,6 @@
 /*
  * scan_passes.h -- what the passes around the scan share (scan_module.hip with scan_order.inc, scan_batch.hip, scan_all.hip, scan_fold.hip,
- * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip, scan_disjoint.hip, scan_rules.hip, scan_words.hip, scan_segcount.hip; the product kernels' units do
+ * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip, scan_disjoint.hip, scan_rules.hip, scan_words.hip, scan_segcount.hip, scan_groups.hip; the product kernels' units do
  * not include it): launch sizes, the layout of a call's scratch and its carving out of a buffer of the handle (ScratchCarver, carveScratch), the
  * compacted scan as a pass runs it, the hand-off of a call's result to the host through mapped memory (HostHandoff; storeToHost on the device),
  * the device fold byte, the clamp of a caller's (start, len), 16 bytes out of two aligned blocks (funnel, loadBytes16), the frame of an output

@@ -42,16 +42,15 @@ static PFAC_status_t matchAllDeviceLocked(PFAC_context *c, char *d_input, size_t
     if (st != PFAC_STATUS_SUCCESS) return st;
     int count = 0;
     int *ids = d_ids, *pos = d_pos;
-    if (expand) {
+    if (expand) {                                                   /* the pairs into handle scratch (PFACX_allReduce reserves it), the fix-up behind them */
         st = c->all_reduce_ptr(c, reinterpret_cast<int *>(d_input), (int)size, d_ids, d_pos, &count, scan.hashed);
         ids = c->scratch.allPairs.get();
         pos = ids + c->scratch.allPairs.count() / 2;              /* one allocation: the ids, then as many positions */
-    } else {
-        st = reduceOnDevice(c, d_input, size, d_ids, d_pos, true, &count);
+        if (st == PFAC_STATUS_SUCCESS && d_offsets)
+            st = c->batch_reduce_fixup_ptr(c, d_input, size, d_offsets, numSegments, ids, pos, &count, c->scratch.allSegFirst.get(), c->scratch.patternLen.get());
+    } else {                                                        /* ... straight into the caller's arrays */
+        st = batchReduceLocked(c, d_input, size, d_offsets, numSegments, d_ids, d_pos, d_offsets ? c->scratch.allSegFirst.get() : nullptr, &count);
     }
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (d_offsets)
-        st = c->batch_reduce_fixup_ptr(c, d_input, size, d_offsets, numSegments, ids, pos, &count, c->scratch.allSegFirst.get(), c->scratch.patternLen.get());
     if (st != PFAC_STATUS_SUCCESS) return st;
     size_t total = (size_t)count;
     if (expand || d_offsets)

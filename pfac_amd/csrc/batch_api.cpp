@@ -1,6 +1,7 @@
 /*
  * batch_api.cpp -- PFACX_matchBatchFromDevice / ...FromHost / ...FromDeviceReduce (include/pfac_ext.h): many independent segments
- * of one buffer in one call, no match running from one segment into the next.
+ * of one buffer in one call, no match running from one segment into the next; and what every later call over "the longest pairs of each
+ * segment" starts with (pfac_host.h: batchReduceLocked and scratchBatchPairs on the device, HostBatchPairs on the host).
  *
  * The GPU forms scan the whole concatenation with the unchanged match path (matchDeviceLocked / the compacted-output kernels:
  * whatever kernel variant, walker, perf mode and texture mode the handle selects) and then correct the few positions near a
@@ -9,6 +10,7 @@
  */
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -45,6 +47,95 @@ PFAC_status_t matchBatchDeviceLocked(PFAC_context *c, char *d_input, size_t size
     st = matchDeviceLocked(c, d_input, size, d_matched_result);
     if (st != PFAC_STATUS_SUCCESS) return st;
     return c->batch_fixup_ptr(c, d_input, size, d_offsets, numSegments, d_matched_result, c->scratch.patternLen.get());
+}
+
+PFAC_status_t batchReduceLocked(PFAC_context *c, char *d_scan, size_t size, const size_t *d_offsets, size_t numSegments, int *d_ids, int *d_pos,
+                                int *d_segFirstPairs, int *h_count)
+{
+    PFAC_status_t st = d_offsets ? ensurePatternLen(c) : PFAC_STATUS_SUCCESS;
+    int count = 0;
+    if (st == PFAC_STATUS_SUCCESS) st = reduceOnDevice(c, d_scan, size, d_ids, d_pos, true, &count);      /* ordered: the fix-up and the segments' first pairs search the positions */
+    if (st == PFAC_STATUS_SUCCESS && d_offsets)
+        st = c->batch_reduce_fixup_ptr(c, d_scan, size, d_offsets, numSegments, d_ids, d_pos, &count, d_segFirstPairs, c->scratch.patternLen.get());
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (count < 0) return PFAC_STATUS_INTERNAL_ERROR;
+    *h_count = count;
+    return PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t scratchBatchPairs(PFAC_context *c, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments, BatchPairs *out)
+{
+    PFAC_status_t st = d_offsets ? c->scratch.allSegFirst.reserve(numSegments + 1) : PFAC_STATUS_SUCCESS;
+    pfac::DeviceBuffer<int> &pairs = c->scratch.allPairs;
+    if (st == PFAC_STATUS_SUCCESS) st = pairs.reserve(2 * size);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    out->ids = pairs.get();
+    out->pos = out->ids + pairs.count() / 2;                               /* one allocation: the ids, then as many positions */
+    int *const segFirstPairs = d_offsets ? c->scratch.allSegFirst.get() : nullptr;
+    out->segFirstPairs = segFirstPairs;
+    DeviceScan scan;                                                     /* a caseless set: the scan and the fix-up read the folded bytes */
+    st = beginDeviceScan(c, d_input, size, &scan);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    out->d_scan = scan.d_scan;
+    int count = 0;
+    st = batchReduceLocked(c, scan.d_scan, size, d_offsets, numSegments, out->ids, out->pos, segFirstPairs, &count);
+    out->count = (size_t)count;
+    return st;
+}
+
+PFAC_status_t zeroSegmentArrays(size_t *d_segFirst, unsigned long long *d_segGroups, size_t numSegments)
+{
+    if (d_segFirst && numSegments && hipMemset(d_segFirst, 0, (numSegments + 1) * sizeof(size_t)) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+    if (d_segGroups && numSegments && hipMemset(d_segGroups, 0, numSegments * sizeof(unsigned long long)) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+    return PFAC_STATUS_SUCCESS;
+}
+
+HostBatchPairs::HostBatchPairs(PFAC_context *c, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments, bool keepPositions,
+                               std::unique_lock<std::mutex> &guard)
+    : offsets(h_offsets ? h_offsets : whole_), c_(c), whole_{0, size}
+{
+    status = scan(h_input, size, numSegments, keepPositions, guard);
+}
+
+PFAC_status_t HostBatchPairs::scan(char *h_input, size_t size, size_t numSegments, bool keepPositions, std::unique_lock<std::mutex> &guard)
+{
+    PFAC_context *c = c_;
+    if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
+    const bool onGpu = c->platform == PFAC_PLATFORM_GPU;
+    size_t longest = 0;
+    for (size_t k = 0; k < numSegments; k++) longest = std::max(longest, offsets[k + 1] - offsets[k]);
+    pairs_.emplace(size, keepPositions ? size : (onGpu ? 0 : longest));         /* positions not kept: the room one segment's scan needs on the CPU platforms */
+    try {
+        numPairs.assign(numSegments, 0);
+    } catch (const std::bad_alloc &) {
+        return PFAC_STATUS_ALLOC_FAILED;
+    }
+    if (!*pairs_) return PFAC_STATUS_ALLOC_FAILED;
+    ids = pairs_->ids;
+    pos = pairs_->pos;
+    if (onGpu) {
+        /* the pipelined batch path: the full result of every segment, compacted in place (pair z of a segment comes from an entry at or behind z) */
+        const PFAC_status_t st = matchBatchHostOnGpu(c, h_input, size, offsets, numSegments, ids);
+        if (st != PFAC_STATUS_SUCCESS) return st;
+        for (size_t k = 0; k < numSegments; k++) {
+            int z = 0;
+            for (size_t i = offsets[k]; i < offsets[k + 1]; i++)
+                if (ids[i] > 0) {
+                    if (keepPositions) pos[offsets[k] + (size_t)z] = (int)(i - offsets[k]);     /* the pair's index in the full result is its position */
+                    ids[offsets[k] + (size_t)z++] = ids[i];
+                }
+            numPairs[k] = z;
+        }
+        return PFAC_STATUS_SUCCESS;
+    }
+    guard.unlock();
+    for (size_t k = 0; k < numSegments; k++) {
+        const size_t n = offsets[k + 1] - offsets[k];
+        if (n == 0) continue;
+        const PFAC_status_t st = hostLongestPairs(c, h_input + offsets[k], n, ids + offsets[k], pos + (keepPositions ? offsets[k] : 0), &numPairs[k], nullptr);
+        if (st != PFAC_STATUS_SUCCESS) return st;
+    }
+    return PFAC_STATUS_SUCCESS;
 }
 
 /* the CPU platforms: one match per non-empty segment.  PFAC_PLATFORM_CPU_OMP (with OMP_NUM_THREADS set, as for PFAC_matchFromHost)
@@ -119,16 +210,11 @@ PFAC_status_t PFACX_matchBatchFromDeviceReduce(PFAC_handle_t handle, char *d_inp
     if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
     std::lock_guard<std::mutex> guard(handle->lock);
-    PFAC_status_t st = ensurePatternLen(handle);
-    if (st != PFAC_STATUS_SUCCESS) return st;
     DeviceScan scan;                                                    /* a caseless set: the scan and the fix-up read the folded bytes */
-    st = beginDeviceScan(handle, d_input, size, &scan);
+    PFAC_status_t st = beginDeviceScan(handle, d_input, size, &scan);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    d_input = scan.d_scan;
     int count = 0;
-    st = reduceOnDevice(handle, d_input, size, d_matched_result, d_pos, true, &count);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    st = handle->batch_reduce_fixup_ptr(handle, d_input, size, d_offsets, numSegments, d_matched_result, d_pos, &count, d_segFirst, handle->scratch.patternLen.get());
+    st = batchReduceLocked(handle, scan.d_scan, size, d_offsets, numSegments, d_matched_result, d_pos, d_segFirst, &count);
     if (st != PFAC_STATUS_SUCCESS) return st;
     *h_num_matched = count;
     return PFAC_STATUS_SUCCESS;

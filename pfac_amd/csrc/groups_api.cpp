@@ -5,11 +5,10 @@
  * The mask table is resolved once, at open: the mask of every id that names a pattern is ORed into the id that pattern is reported under
  * (duplicate lines), every other id ends with 0.  Every pattern that occurs at a position is a prefix of the longest one there, so all three forms
  * work on longest pairs and walk each pair's prefix chain (Automaton::prefixPattern) once; what decides a member is one 64-bit AND.  The device
- * form is PFACX_countBatchFromDevice up to its run call -- the ordered compacted scan into the handle's pair scratch (DeviceScratch::allPairs: the
- * ids in its first half, the positions in its second, `size` entries each), the batch fix-up of PFACX_matchBatchFromDeviceReduce behind it -- and
- * then PFACX_groupsRun (scan_groups.hip) over the pairs; the pairs form is that run call alone over the caller's list.  The host form takes the
- * longest pairs of every segment -- the CPU platforms through hostLongestPairs, segment by segment; the GPU platform through the pipelined batch
- * path -- and walks the chains in a loop of its own, under the pin of the set the pairs came from.
+ * form takes the ordered pairs of the batch in the handle's pair scratch from scratchBatchPairs (batch_api.cpp) and runs PFACX_groupsRun
+ * (scan_groups.hip) over them; the pairs form is that run call alone over the caller's list.  The host form takes the longest pairs of every
+ * segment, with their positions, from HostBatchPairs (batch_api.cpp), pins the set the table was opened on, and walks the chains in a loop of
+ * its own (groupsOnHost).
  */
 #include <hip/hip_runtime_api.h>
 
@@ -54,8 +53,6 @@ size_t groupsDeviceBytes(const PFAC_context *c)
 using namespace pfac_internal;
 
 namespace {
-
-constexpr size_t kTwoGiB = size_t(1) << 31;
 
 /* the caller's masks by id resolved into g->masks (the caller holds the handle's lock) */
 void resolveMasks(const pfac::Automaton &fa, const unsigned long long *given, PFACX_groups_s *g)
@@ -107,8 +104,8 @@ PFAC_status_t ensureDeviceMasks(PFACX_groups_s *g) { return g->d_masks ? PFAC_ST
 /* nothing to match on the device: 0 pairs, segFirst and segGroups zeroed where given */
 PFAC_status_t nothingOnDevice(size_t *d_segFirst, unsigned long long *d_segGroups, size_t numSegments, size_t *h_num_matched)
 {
-    if (d_segFirst && numSegments && hipMemset(d_segFirst, 0, (numSegments + 1) * sizeof(size_t)) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
-    if (d_segGroups && numSegments && hipMemset(d_segGroups, 0, numSegments * sizeof(unsigned long long)) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+    const PFAC_status_t st = zeroSegmentArrays(d_segFirst, d_segGroups, numSegments);
+    if (st != PFAC_STATUS_SUCCESS) return st;
     *h_num_matched = 0;
     return PFAC_STATUS_SUCCESS;
 }
@@ -228,23 +225,11 @@ PFAC_status_t PFACX_groupsMatchFromDevice(PFACX_groups_t groups, char *d_input, 
     if (size == 0) return nothingOnDevice(d_segFirst, d_segGroups, numSegments, h_num_matched);
     st = ensureDeviceMasks(groups);
     if (st == PFAC_STATUS_SUCCESS && c->fa.maxChain > 1) st = ensureAllTable(c);
-    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = ensurePatternLen(c);              /* the fix-up's */
-    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = c->scratch.allSegFirst.reserve(numSegments + 1);
-    pfac::DeviceBuffer<int> &pairs = c->scratch.allPairs;
-    if (st == PFAC_STATUS_SUCCESS) st = pairs.reserve(2 * size);
+    BatchPairs pairs{};
+    if (st == PFAC_STATUS_SUCCESS) st = scratchBatchPairs(c, d_input, size, d_offsets, numSegments, &pairs);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    int *ids = pairs.get(), *pos = ids + pairs.count() / 2;               /* one allocation: the ids, then as many positions */
-    DeviceScan scan;                                                      /* a caseless set: the scan and the fix-up read the folded bytes */
-    st = beginDeviceScan(c, d_input, size, &scan);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    int count = 0;
-    st = reduceOnDevice(c, scan.d_scan, size, ids, pos, true, &count);          /* ordered: the fix-up and the segments' first pairs search the positions */
-    if (st == PFAC_STATUS_SUCCESS && d_offsets)
-        st = c->batch_reduce_fixup_ptr(c, scan.d_scan, size, d_offsets, numSegments, ids, pos, &count, c->scratch.allSegFirst.get(), c->scratch.patternLen.get());
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0) return PFAC_STATUS_INTERNAL_ERROR;
-    return runOnDevice(groups, ids, pos, (size_t)count, d_offsets ? c->scratch.allSegFirst.get() : nullptr, numSegments, d_segMasks, flags, d_ids,
-                       d_pos, capacity, d_segFirst, d_segGroups, h_num_matched);
+    return runOnDevice(groups, pairs.ids, pairs.pos, pairs.count, pairs.segFirstPairs, numSegments, d_segMasks, flags, d_ids, d_pos, capacity, d_segFirst,
+                       d_segGroups, h_num_matched);
 }
 
 PFAC_status_t PFACX_groupsPairsFromDevice(PFACX_groups_t groups, const int *d_pairIds, const int *d_pairPos, size_t numPairs,
@@ -282,9 +267,6 @@ PFAC_status_t PFACX_groupsMatchFromHost(PFACX_groups_t groups, char *h_input, si
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (h_offsets && numSegments && !batchOffsetsValid(h_offsets, numSegments, size)) return PFAC_STATUS_INVALID_PARAMETER;
     PFAC_context *c = groups->handle;
-    const size_t whole[2] = {0, size};
-    const size_t *offsets = h_offsets ? h_offsets : whole;
-    const bool onGpu = c->platform == PFAC_PLATFORM_GPU;
     std::unique_lock<std::mutex> guard(c->lock);
     st = checkSetGeneration(c, groups->generation);
     if (st != PFAC_STATUS_SUCCESS) return st;
@@ -294,43 +276,11 @@ PFAC_status_t PFACX_groupsMatchFromHost(PFACX_groups_t groups, char *h_input, si
         *h_num_matched = 0;
         return PFAC_STATUS_SUCCESS;
     }
-    if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    const HostPairs pairs(size, size);                      /* the longest pairs of segment k from index offsets[k] on: ids, and positions in the segment */
-    int *const ids = pairs.ids, *const pos = pairs.pos;
-    std::vector<int> numPairs;
-    try {
-        numPairs.assign(numSegments, 0);
-    } catch (const std::bad_alloc &) {
-        return PFAC_STATUS_ALLOC_FAILED;
-    }
-    if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
-    if (onGpu) {
-        /* the pipelined batch path: the full result of every segment, compacted in place (pair z of a segment comes from an entry at or behind z) */
-        st = matchBatchHostOnGpu(c, h_input, size, offsets, numSegments, ids);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-        for (size_t k = 0; k < numSegments; k++) {
-            int z = 0;
-            for (size_t i = offsets[k]; i < offsets[k + 1]; i++)
-                if (ids[i] > 0) {
-                    pos[offsets[k] + (size_t)z] = (int)(i - offsets[k]);        /* the pair's index in the full result is its position */
-                    ids[offsets[k] + (size_t)z++] = ids[i];
-                }
-            numPairs[k] = z;
-        }
-    } else {
-        guard.unlock();                                     /* the CPU platforms: the helper takes the lock while it prepares the tables, several threads match side by side */
-        for (size_t k = 0; k < numSegments; k++) {
-            const size_t n = offsets[k + 1] - offsets[k];
-            if (n == 0) continue;
-            st = hostLongestPairs(c, h_input + offsets[k], n, ids + offsets[k], pos + offsets[k], &numPairs[k], nullptr);
-            if (st != PFAC_STATUS_SUCCESS) return st;
-        }
-    }
-    /* generations only count up: the set is the one the table was opened on now, so it was during every scan above (on the GPU platform the lock is still held) */
-    const SetPin pin(c, groups->generation);
-    if (pin.status() != PFAC_STATUS_SUCCESS) return PFAC_STATUS_INVALID_PARAMETER;      /* another thread has replaced the set meanwhile: the contract's answer for a group table */
-    const size_t total = groupsOnHost(c->fa, *groups, ids, pos, offsets, numPairs.data(), numSegments, h_segMasks, (flags & PFACX_GROUPS_ALL) != 0, h_ids,
-                                      h_pos, capacity, h_segFirst, h_segGroups);
+    HostBatchPairs pairs(c, h_input, size, h_offsets, numSegments, true, guard);
+    if (pairs.status != PFAC_STATUS_SUCCESS) return pairs.status;
+    if (pairs.pin(groups->generation) != PFAC_STATUS_SUCCESS) return PFAC_STATUS_INVALID_PARAMETER;      /* another thread has replaced the set meanwhile: the contract's answer for a group table */
+    const size_t total = groupsOnHost(c->fa, *groups, pairs.ids, pairs.pos, pairs.offsets, pairs.numPairs.data(), numSegments, h_segMasks,
+                                      (flags & PFACX_GROUPS_ALL) != 0, h_ids, h_pos, capacity, h_segFirst, h_segGroups);
     *h_num_matched = total;
     return truncatedIf(total, capacity);
 }

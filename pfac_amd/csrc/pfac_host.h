@@ -91,6 +91,8 @@ inline PFAC_status_t checkSetAndPointers(PFAC_context *c, std::initializer_list<
 }
 /* positions, counts and lengths are ints on the device and in the callers' arrays */
 constexpr size_t kMaxInt = 0x7fffffff;
+/* what the rules, count-batch and groups calls refuse: a size or a number of segments from here on */
+constexpr size_t kTwoGiB = size_t(1) << 31;
 /* nothing to launch with: LIB_NOT_EXIST of every device form, and of a host form on the GPU platform */
 inline bool lacksModule(const PFAC_context *c) { return !c->hasDevice || !c->module; }
 inline bool hostLacksModule(const PFAC_context *c) { return c->platform == PFAC_PLATFORM_GPU && lacksModule(c); }
@@ -191,6 +193,49 @@ bool batchOffsetsValid(const size_t *offsets, size_t numSegments, size_t size);
 /* batch_api.cpp: the batch calls (PFACX_matchBatch*) behind their argument checks; the caller holds c->lock */
 PFAC_status_t ensurePatternLen(PFAC_context *c);            /* the device copy of fa.patternLen the batch fix-ups read */
 PFAC_status_t matchBatchDeviceLocked(PFAC_context *c, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments, int *d_matched_result);
+/* batch_api.cpp: the ordered longest pairs of a batch on the device; the caller holds c->lock.
+ * batchReduceLocked: behind beginDeviceScan, over the bytes the scan reads.  The compacted scan WITH its ordering launches into d_ids / d_pos
+ * (`size` entries each) and, with offsets, the batch fix-up behind it (scan_batch.hip): no pair runs from one segment into the next, the first
+ * pair of each segment to d_segFirstPairs[numSegments + 1]; the fix-up's pattern lengths are uploaded here.  d_offsets null: one segment, no
+ * fix-up, nothing written to d_segFirstPairs.
+ * scratchBatchPairs: the same from the caller's input into the handle's pair scratch -- DeviceScratch::allPairs, one allocation of 2 size
+ * entries, the ids in its first half and the positions in its second; DeviceScratch::allSegFirst with offsets only -- behind beginDeviceScan:
+ * what every call that works on "the pairs of each segment" starts with */
+PFAC_status_t batchReduceLocked(PFAC_context *c, char *d_scan, size_t size, const size_t *d_offsets, size_t numSegments, int *d_ids, int *d_pos,
+                                int *d_segFirstPairs, int *h_count);
+struct BatchPairs {
+    int *ids, *pos;                           /* `count` pairs in position order */
+    size_t count;
+    const int *segFirstPairs;                 /* [numSegments + 1]; null without offsets */
+    char *d_scan;                             /* the bytes that were scanned: the input, or its fold for a caseless set */
+};
+PFAC_status_t scratchBatchPairs(PFAC_context *c, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments, BatchPairs *out);
+/* nothing to do on the device: d_segFirst[numSegments + 1] and d_segGroups[numSegments] zeroed, each where given */
+PFAC_status_t zeroSegmentArrays(size_t *d_segFirst, unsigned long long *d_segGroups, size_t numSegments);
+/* batch_api.cpp: the two steps of a batch host form whose post-pass reads c->fa -- PinnedPairs segment by segment.  The constructor takes the
+ * longest pairs of every segment of a validated batch (h_offsets null: one segment, the whole buffer): the ids of segment k at ids[offsets[k],
+ * offsets[k] + numPairs[k]).  keepPositions: pos[] holds each pair's position IN ITS SEGMENT at the index of its id; else pos is room the scan
+ * needs and holds nothing.  The caller holds c->lock through `guard`, size > 0: the GPU platform runs the pipelined batch path under it and
+ * leaves it held; the CPU platforms unlock it and match segment by segment (hostLongestPairs takes the lock while it prepares the tables:
+ * several threads match side by side).  Then pin(generation): the set held still for the post-pass, PATTERNS_NOT_READY if it is not that
+ * generation's any more -- generations only count up, so a set that is the caller's now was the caller's during every scan */
+class HostBatchPairs {
+public:
+    HostBatchPairs(PFAC_context *c, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments, bool keepPositions,
+                   std::unique_lock<std::mutex> &guard);
+    HostBatchPairs(const HostBatchPairs &) = delete;
+    PFAC_status_t pin(unsigned long long generation) { return pin_.emplace(c_, generation).status(); }
+    PFAC_status_t status = PFAC_STATUS_SUCCESS;
+    const size_t *offsets;                    /* h_offsets, or {0, size} */
+    int *ids = nullptr, *pos = nullptr;
+    std::vector<int> numPairs;
+private:
+    PFAC_status_t scan(char *h_input, size_t size, size_t numSegments, bool keepPositions, std::unique_lock<std::mutex> &guard);
+    PFAC_context *c_;
+    size_t whole_[2];
+    std::optional<HostPairs> pairs_;
+    std::optional<SetPin> pin_;
+};
 /* all_api.cpp: the device copy of {fa.prefixPattern, fa.chainLen} by id (scratch.allTable) that the all-match expansion and the count calls read;
  * the caller holds c->lock */
 PFAC_status_t ensureAllTable(PFAC_context *c);

@@ -5,11 +5,9 @@
  * A rule set is inverted once, at open: every named id resolved to the id that is reported (duplicate lines), the ids of a rule made distinct and
  * numbered 0 .. 31 in ascending order, then a CSR by pattern id -- memberOff[F + 2], member[] = rule << 5 | bit, ascending rule -- and need[rule],
  * the full mask.  Pattern id occurs in a segment iff it lies on the prefix chain (Automaton::prefixPattern) of one of the segment's longest pairs, so
- * both forms work on longest pairs.  The device form runs the ordered compacted scan into the handle's pair scratch (DeviceScratch::allPairs: the
- * ids in its first half, the positions in its second, `size` entries each, as PFACX_countFromDevice sizes it), the batch fix-up of
- * PFACX_matchBatchFromDeviceReduce behind it, and PFACX_rulesRun (scan_rules.hip) over the pairs.  The host form takes the longest pairs of every
- * segment -- the CPU platforms through hostLongestPairs, segment by segment; the GPU platform through the pipelined batch path -- and keeps one
- * mask per touched rule in a loop of its own.
+ * both forms work on longest pairs.  The device form takes the ordered pairs of the batch in the handle's pair scratch from scratchBatchPairs
+ * (batch_api.cpp) and runs PFACX_rulesRun (scan_rules.hip) over them.  The host form takes the longest pairs of every segment from HostBatchPairs
+ * (batch_api.cpp), pins the set the rules were opened on, and keeps one mask per touched rule in a loop of its own (firedOnHost).
  *
  * PFACX_rulesOpenEx is the same open over members {pattern, flags, offset, depth}: what is made distinct and numbered is the member,
  * need[rule] keeps the bits of the positive members only (a bit a negated member sets makes mask != need), and memberCond[], indexed like member[],
@@ -71,7 +69,7 @@ using namespace pfac_internal;
 
 namespace {
 
-constexpr size_t kMaxRules = size_t(1) << 24, kMaxRulePatterns = 32, kTwoGiB = size_t(1) << 31;
+constexpr size_t kMaxRules = size_t(1) << 24, kMaxRulePatterns = 32;
 
 constexpr unsigned int kNoEnd = 0x7FFFFFFFu, kFromEnd = 0x80000000u;      /* memberCond's hi: no occurrence ends behind 2^31 - 1; the direction */
 
@@ -294,32 +292,21 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
     st = checkSetGeneration(c, rules->generation);
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (size == 0) {
-        if (d_segFirst && numSegments && hipMemset(d_segFirst, 0, (numSegments + 1) * sizeof(size_t)) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
-        *h_numFired = 0;
-        return PFAC_STATUS_SUCCESS;
+        st = zeroSegmentArrays(d_segFirst, nullptr, numSegments);
+        if (st == PFAC_STATUS_SUCCESS) *h_numFired = 0;
+        return st;
     }
     st = ensureDeviceTables(rules);
     if (st == PFAC_STATUS_SUCCESS) st = ensureAllTable(c);
     const bool cond = rules->conditioned();
-    if (st == PFAC_STATUS_SUCCESS && (d_offsets || cond)) st = ensurePatternLen(c);      /* the fix-up's, and the window test's */
-    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = c->scratch.allSegFirst.reserve(numSegments + 1);
-    pfac::DeviceBuffer<int> &pairs = c->scratch.allPairs;
-    if (st == PFAC_STATUS_SUCCESS) st = pairs.reserve(2 * size);
+    if (st == PFAC_STATUS_SUCCESS && cond) st = ensurePatternLen(c);            /* the window test's, offsets or none */
+    BatchPairs pairs{};
+    if (st == PFAC_STATUS_SUCCESS) st = scratchBatchPairs(c, d_input, size, d_offsets, numSegments, &pairs);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    int *ids = pairs.get(), *pos = ids + pairs.count() / 2;               /* one allocation: the ids, then as many positions */
-    DeviceScan scan;                                                      /* a caseless set: the scan and the fix-up read the folded bytes */
-    st = beginDeviceScan(c, d_input, size, &scan);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    int count = 0;
-    st = reduceOnDevice(c, scan.d_scan, size, ids, pos, true, &count);          /* ordered: the fix-up and the segments' first pairs search the positions */
-    if (st == PFAC_STATUS_SUCCESS && d_offsets)
-        st = c->batch_reduce_fixup_ptr(c, scan.d_scan, size, d_offsets, numSegments, ids, pos, &count, c->scratch.allSegFirst.get(), c->scratch.patternLen.get());
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0) return PFAC_STATUS_INTERNAL_ERROR;
     PFACX_rulesRun_t run{};
-    run.d_pairIds = ids;
-    run.count = (size_t)count;
-    run.d_segFirstPairs = d_offsets ? c->scratch.allSegFirst.get() : nullptr;
+    run.d_pairIds = pairs.ids;
+    run.count = pairs.count;
+    run.d_segFirstPairs = pairs.segFirstPairs;
     run.numSegments = numSegments;
     run.d_table = c->scratch.allTable.get();
     run.numIds = rules->numIds;
@@ -332,7 +319,7 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
     run.capacity = capacity;
     run.d_segFirst = d_segFirst;
     if (cond) {                                                                 /* the window test: positions, bounds and lengths, no input byte */
-        run.d_pairPos = pos;
+        run.d_pairPos = pairs.pos;
         run.d_offsets = d_offsets;
         run.size = size;
         run.d_patternLen = c->scratch.patternLen.get();
@@ -352,9 +339,6 @@ PFAC_status_t PFACX_rulesMatchFromHost(PFACX_rules_t rules, char *h_input, size_
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (h_offsets && numSegments && !batchOffsetsValid(h_offsets, numSegments, size)) return PFAC_STATUS_INVALID_PARAMETER;
     PFAC_context *c = rules->handle;
-    const size_t whole[2] = {0, size};
-    const size_t *offsets = h_offsets ? h_offsets : whole;
-    const bool onGpu = c->platform == PFAC_PLATFORM_GPU;
     std::unique_lock<std::mutex> guard(c->lock);
     st = checkSetGeneration(c, rules->generation);
     if (st != PFAC_STATUS_SUCCESS) return st;
@@ -363,46 +347,12 @@ PFAC_status_t PFACX_rulesMatchFromHost(PFACX_rules_t rules, char *h_input, size_
         *h_numFired = 0;
         return PFAC_STATUS_SUCCESS;
     }
-    if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    size_t longest = 0;
-    for (size_t k = 0; k < numSegments; k++) longest = std::max(longest, offsets[k + 1] - offsets[k]);
-    const bool cond = rules->conditioned();                                     /* then every pair keeps its position in its segment, at the index of its id */
-    const HostPairs pairs(size, cond ? size : (onGpu ? 0 : longest));           /* the longest ids of segment k from ids[offsets[k]] on */
-    int *const ids = pairs.ids, *const pos = pairs.pos;
-    std::vector<int> numPairs;
+    HostBatchPairs pairs(c, h_input, size, h_offsets, numSegments, rules->conditioned(), guard);       /* a conditioned set reads the positions */
+    if (pairs.status != PFAC_STATUS_SUCCESS) return pairs.status;
+    if (pairs.pin(rules->generation) != PFAC_STATUS_SUCCESS) return PFAC_STATUS_INVALID_PARAMETER;      /* another thread has replaced the set meanwhile: the contract's answer for a rule set */
     try {
-        numPairs.assign(numSegments, 0);
-    } catch (const std::bad_alloc &) {
-        return PFAC_STATUS_ALLOC_FAILED;
-    }
-    if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
-    if (onGpu) {
-        /* the pipelined batch path: the full result of every segment, compacted in place (pair z of a segment comes from an entry at or behind z) */
-        st = matchBatchHostOnGpu(c, h_input, size, offsets, numSegments, ids);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-        for (size_t k = 0; k < numSegments; k++) {
-            int z = 0;
-            for (size_t i = offsets[k]; i < offsets[k + 1]; i++)
-                if (ids[i] > 0) {
-                    if (cond) pos[offsets[k] + (size_t)z] = (int)(i - offsets[k]);      /* the pair's index in the full result is its position */
-                    ids[offsets[k] + (size_t)z++] = ids[i];
-                }
-            numPairs[k] = z;
-        }
-    } else {
-        guard.unlock();                                     /* the CPU platforms: the helper takes the lock while it prepares the tables, several threads match side by side */
-        for (size_t k = 0; k < numSegments; k++) {
-            const size_t n = offsets[k + 1] - offsets[k];
-            if (n == 0) continue;
-            st = hostLongestPairs(c, h_input + offsets[k], n, ids + offsets[k], pos + (cond ? offsets[k] : 0), &numPairs[k], nullptr);
-            if (st != PFAC_STATUS_SUCCESS) return st;
-        }
-    }
-    /* generations only count up: the set is the one the rules were opened on now, so it was during every scan above (on the GPU platform the lock is still held) */
-    const SetPin pin(c, rules->generation);
-    if (pin.status() != PFAC_STATUS_SUCCESS) return PFAC_STATUS_INVALID_PARAMETER;      /* another thread has replaced the set meanwhile: the contract's answer for a rule set */
-    try {
-        const size_t total = firedOnHost(c->fa, *rules, ids, pos, offsets, numPairs.data(), numSegments, h_firedSeg, h_firedRule, capacity, h_segFirst);
+        const size_t total = firedOnHost(c->fa, *rules, pairs.ids, pairs.pos, pairs.offsets, pairs.numPairs.data(), numSegments, h_firedSeg, h_firedRule,
+                                         capacity, h_segFirst);
         *h_numFired = total;
         return truncatedIf(total, capacity);
     } catch (const std::bad_alloc &) {

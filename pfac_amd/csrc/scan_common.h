@@ -13,7 +13,8 @@
  *   scan_spans.hip    pfac_spans_*: the covered spans from the scan's ordered pairs (running maximum of the ends), the redaction (PFACX_matchSpans*)
  *   scan_count.hip    pfac_count_*: the histogram of the scan's pairs, the counts along the prefix chains, the non-zero counts (PFACX_count*)
  *   scan_disjoint.hip pfac_disjoint_* / pfac_replace_*: the disjoint leftmost-longest list from the scan's ordered pairs (pointer doubling), the replacement (PFACX_matchDisjoint* / PFACX_replace*)
- * scan_passes.h holds what the units around the product kernels share on top of this: the hand-off to the host, block prefix sums, the seam.
+ * scan_passes.h holds what the units around the product kernels share on top of this: the hand-off to the host, block prefix sums, the seam,
+ * the segment-window frame of scan_rules.hip and scan_segcount.hip.
  */
 #ifndef PFAC_SCAN_COMMON_H_
 #define PFAC_SCAN_COMMON_H_

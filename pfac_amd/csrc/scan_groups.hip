@@ -68,9 +68,6 @@ struct GroupsArgs {
     unsigned long long *segGroups;      /* [numSegments], or null (zeroed in front of the count pass) */
 };
 
-/* a caller's first pair inside [0, count] */
-__device__ __forceinline__ unsigned int clampFirst(int f, unsigned int count) { return f < 0 ? 0u : ((unsigned int)f < count ? (unsigned int)f : count); }
-
 /* bounds[k] = the largest of the clamped entries [0, k] of segFirstPairs, k < n = numSegments + 1 */
 __global__ __launch_bounds__(1024) void pfac_groups_bounds(const int *segFirstPairs, unsigned int n, unsigned int count, unsigned int *bounds)
 {
@@ -78,11 +75,11 @@ __global__ __launch_bounds__(1024) void pfac_groups_bounds(const int *segFirstPa
     const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const unsigned int base = blockIdx.x * kBoundsBlock, i0 = base + threadIdx.x * kBoundsPer;
     unsigned int front = 0;                                             /* what lies in front of the block's entries: coalesced, from L2 */
-    for (unsigned int q = threadIdx.x; q < base; q += 1024u) front = OpMax()(front, clampFirst(segFirstPairs[q], count));
+    for (unsigned int q = threadIdx.x; q < base; q += 1024u) front = OpMax()(front, clampFirstPair(segFirstPairs[q], count));
     unsigned int x[kBoundsPer], own = 0;
 #pragma unroll
     for (unsigned int k = 0; k < kBoundsPer; k++) {
-        x[k] = i0 + k < n ? clampFirst(segFirstPairs[i0 + k], count) : 0u;
+        x[k] = i0 + k < n ? clampFirstPair(segFirstPairs[i0 + k], count) : 0u;
         own = OpMax()(own, x[k]);
     }
     const unsigned int incl = waveInclusive(own, OpMax());

@@ -7,9 +7,11 @@
  * tile and its store tail (kOutTile, tileFrame, tileStore), wave and block prefixes
  * under a sum or a maximum, the 64-ary search of a wave (waveLowerBound), the two scan kernels (pfac_array_scan: one block, in place;
  * pfac_block_scan: a block per 8192 values that folds what lies in front of them), the two passes that give items of 64-bit values their offsets
- * (offsetBlocks, offsetsBlockTotal, offsetsOfBlock), the pairs of an ordered scan with the head, the tail and the finish kernel of a select call
- * over them (PairArgs, pairsSelectHead, pairsSelectTail, pfac_pairs_finish), the seam of a stream.  Like scan_common.h, everything is in an
- * unnamed namespace: inline device code, each unit its own copy.
+ * (offsetBlocks, offsetsBlockTotal, offsetsOfBlock), the frame and the launches of a pass that takes whole segments and works their pairs
+ * through windows of an LDS table (clampFirstPair, SegmentFrame, segmentWindows, carveSegFirst, segmentWindowPasses: the rules and the
+ * count-batch passes), the pairs of an ordered scan with the head, the tail and the finish kernel of a select call over them (PairArgs,
+ * pairsSelectHead, pairsSelectTail, pfac_pairs_finish), the seam of a stream.  Like scan_common.h, everything is in an unnamed namespace: inline
+ * device code, each unit its own copy.
  */
 #ifndef PFAC_SCAN_PASSES_H_
 #define PFAC_SCAN_PASSES_H_
@@ -507,6 +509,158 @@ __device__ __forceinline__ void offsetsOfBlock(size_t count, size_t per, const u
         base += stepTotal;
         if (has) store(k, before);
     }
+}
+
+/* ------------------------------------------------------------------ the segment-window frame (scan_rules.hip, scan_segcount.hip) */
+
+/* a caller's first pair inside [0, count] (scan_groups.hip too) */
+__device__ __forceinline__ unsigned int clampFirstPair(int f, unsigned int count) { return f < 0 ? 0u : ((unsigned int)f < count ? (unsigned int)f : count); }
+
+/* What the arguments of a segment-window pass start with.  A pass turns the ordered longest pairs of each segment into a list of entries per
+ * segment, ascending within the segment, in CSR form: the count pass (EMIT == false) writes each segment's number of entries to segFirst[k],
+ * pfac_array_scan turns them into first entries, the emit pass writes the entries below `capacity` */
+struct SegmentFrame {
+    unsigned int count;                 /* the pairs */
+    const int *segFirstPairs;           /* [numSegments + 1], clamped where read; null: one segment of all pairs */
+    unsigned int numSegments;
+    unsigned long long *segFirst;       /* [numSegments + 1] */
+    unsigned long long capacity;
+};
+constexpr unsigned int kNoWindow = 0xFFFFFFFFu;
+
+/* The frame of both passes, by a block of BLOCK threads that takes whole segments, k = blockIdx.x, + gridDim.x, ...  What an entry is keyed by
+ * (a rule, a pattern id) is cut into WINDOWS of 2^LOG2 keys; `table` is the unit's LDS table of one window, a word per SLOT, all zero between
+ * windows.  For a window the block walks the segment's pairs, one per thread and trip: pair(i, w0, touch, beyond) works pair i into the table of
+ * the window that starts at key w0, calls touch(r) where it saw slot r go from zero (the touched list: TOUCHED 16-bit slots; a list that overflows
+ * only counts on, and the sweep then covers the whole table) and beyond(w) for a key of a later window w (nextWindow, an LDS atomic minimum: the
+ * block goes on with the next window any pair of the segment has a key in, so a segment costs the windows it touches).  Then every touched slot
+ * with decide(value, key) sets its bit in a bitmap of the window; the bitmap's words are swept in order, one per thread -- popcounts under a block
+ * prefix give the number of entries and, with EMIT, the write position: emit(o, k, key, value) for the entries below capacity, ascending without
+ * a sort.  segment(k) runs once per segment, in front of its windows.
+ * RESET_IN_SWEEP says where a slot returns to zero.  false: where it is decided -- the sweep is then for the entries alone: skipped for a window
+ * in which nothing was decided for (anyMarked), ended at capacity, and emit's value is 0.  true: under its bit in the sweep, behind its emit --
+ * every touched window is swept to its end in both passes.
+ * Whatever path a segment takes -- touched list, overflow sweep, truncation, no pair at all -- the table, the bitmap, the touched count and
+ * nextWindow are as the prologue left them when the segment ends.  EMIT: a segment with no entry below capacity is left at once */
+template <bool EMIT, unsigned int LOG2, unsigned int TOUCHED, unsigned int BLOCK, bool RESET_IN_SWEEP, class Segment, class Pair, class Decide, class Emit>
+__device__ __forceinline__ void segmentWindows(const SegmentFrame &f, unsigned int *table, Segment segment, Pair pair, Decide decide, Emit emit)
+{
+    constexpr unsigned int WINDOW = 1u << LOG2;
+    static_assert(WINDOW / 32 == BLOCK, "the sweep gives every thread one word of the bitmap");
+    static_assert(WINDOW <= 65536, "the touched list holds 16-bit slots");
+    __shared__ unsigned int bits[WINDOW / 32];
+    __shared__ unsigned short touched[TOUCHED];
+    __shared__ unsigned int waveSum[BLOCK / 64];
+    __shared__ unsigned int words[RESET_IN_SWEEP ? 2 : 3];
+    unsigned int &numTouched = words[0], &nextWindow = words[1];
+    const unsigned int t = threadIdx.x;
+    const auto resetWords = [&]() {
+        numTouched = 0;
+        nextWindow = kNoWindow;
+        if constexpr (!RESET_IN_SWEEP) words[2] = 0;                                /* anyMarked */
+    };
+    for (unsigned int i = t; i < WINDOW; i += BLOCK) table[i] = 0;
+    bits[t] = 0;
+    if (t == 0) resetWords();
+    __syncthreads();
+
+    const auto touch = [&](unsigned int r) {
+        const unsigned int slot = atomicAdd(&numTouched, 1u);
+        if (slot < TOUCHED) touched[slot] = (unsigned short)r;
+    };
+    const auto beyond = [&](unsigned int w) { atomicMin(&nextWindow, w); };
+    for (unsigned int k = blockIdx.x; k < f.numSegments; k += gridDim.x) {          /* (numSegments < 2^31: k + gridDim.x does not wrap) */
+        unsigned long long base = 0;
+        if constexpr (EMIT) {
+            base = f.segFirst[k];
+            if (f.segFirst[k + 1] == base || base >= f.capacity) continue;          /* no entry here, or none of them fits: the whole block leaves */
+        }
+        unsigned int first = 0, last = f.count;
+        if (f.segFirstPairs != nullptr) {
+            first = clampFirstPair(f.segFirstPairs[k], f.count);
+            last = clampFirstPair(f.segFirstPairs[k + 1], f.count);
+            if (last < first) last = first;                                         /* hostile offsets: an empty segment */
+        }
+        segment(k);
+        unsigned int entries = 0;                                                   /* of this segment so far: the same in every thread */
+        unsigned int window = first < last ? 0u : kNoWindow;
+        while (window != kNoWindow) {
+            const unsigned int w0 = window << LOG2;
+            for (unsigned int i = first + t; i < last; i += BLOCK) pair(i, w0, touch, beyond);
+            __syncthreads();
+            const unsigned int n = numTouched, next = nextWindow;
+            if (n != 0) {                                                           /* the same in every thread */
+                const auto mark = [&](unsigned int r, unsigned int value) {         /* a slot that is not zero */
+                    if (decide(value, w0 + r)) {
+                        atomicOr(&bits[r >> 5], 1u << (r & 31u));
+                        if constexpr (!RESET_IN_SWEEP) words[2] = 1u;
+                    }
+                    if constexpr (!RESET_IN_SWEEP) table[r] = 0;
+                };
+                if (n <= TOUCHED) {
+                    for (unsigned int j = t; j < n; j += BLOCK) {
+                        const unsigned int r = touched[j];
+                        mark(r, table[r]);
+                    }
+                } else {                                                            /* more slots than the list holds: every slot of the table */
+                    for (unsigned int r = t; r < WINDOW; r += BLOCK) {
+                        const unsigned int value = table[r];
+                        if (value != 0) mark(r, value);
+                    }
+                }
+                __syncthreads();
+                bool sweep = true;
+                if constexpr (!RESET_IN_SWEEP) sweep = words[2] != 0;               /* the same in every thread: read behind the barrier, reset behind the next */
+                if (sweep) {
+                    unsigned int word = bits[t];
+                    bits[t] = 0;
+                    unsigned int total = 0;
+                    const unsigned int before = blockExclusive<BLOCK>((unsigned int)__popc(word), waveSum, total);
+                    unsigned long long o = base + entries + before;
+                    while (word != 0 && (RESET_IN_SWEEP || (EMIT && o < f.capacity))) {
+                        const unsigned int r = t * 32u + (unsigned int)__ffs((int)word) - 1u;
+                        word &= word - 1u;
+                        if constexpr (EMIT) {
+                            if (o < f.capacity) emit(o, k, w0 + r, RESET_IN_SWEEP ? table[r] : 0u);
+                            o++;
+                        }
+                        if constexpr (RESET_IN_SWEEP) table[r] = 0;
+                    }
+                    entries += total;
+                }
+            }
+            __syncthreads();                                                        /* everyone has read the words */
+            if (t == 0) resetWords();
+            __syncthreads();
+            window = next;
+        }
+        if constexpr (!EMIT) {
+            if (t == 0) f.segFirst[k] = entries;
+        }
+    }
+}
+
+/* The launches of such a call, behind its argument checks.  carveSegFirst: segFirst[numSegments + 1] and `extraBytes` behind it, one region of
+ * `scratch`.  segmentWindowPasses (a: the filled arguments, Args::f their SegmentFrame; list: the call's hand-off): the count pass, the scan of
+ * the counts -- the length of the list to segFirst[numSegments] and to the hand-off's first value --, the emit pass where the caller has room
+ * for an entry, segFirst to d_segFirst where given.  The caller ends the call: list.finish, behind what else it hands over.  false: a copy failed */
+inline PFAC_status_t carveSegFirst(pfac::DeviceBuffer<char> &scratch, SegmentFrame &f, size_t extraBytes)
+{
+    return carveScratch(scratch, [&](ScratchCarver &k) { f.segFirst = k.take<unsigned long long>((size_t)f.numSegments + 1, extraBytes); });
+}
+template <class Args>
+inline bool segmentWindowPasses(const PFAC_context *c, const Args &a, void (*count)(Args), void (*emit)(Args), unsigned int block, const HostHandoff &list,
+                                size_t *d_segFirst)
+{
+    static_assert(sizeof(size_t) == sizeof(unsigned long long), "the caller's segFirst is 64-bit");
+    const SegmentFrame &f = a.f;
+    const unsigned int grid = f.numSegments < gridCap(c, 4) ? f.numSegments : gridCap(c, 4);
+    hipLaunchKernelGGL(count, dim3(grid), dim3(block), 0, 0, a);
+    hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, f.segFirst, f.numSegments, f.segFirst + f.numSegments,
+                       reinterpret_cast<unsigned long long *>(list.d_value));
+    if (f.capacity) hipLaunchKernelGGL(emit, dim3(grid), dim3(block), 0, 0, a);
+    return d_segFirst == nullptr ||
+           hipMemcpyAsync(d_segFirst, f.segFirst, ((size_t)f.numSegments + 1) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, nullptr) == hipSuccess;
 }
 
 /* ------------------------------------------------------------------ the pairs of an ordered scan (scan_spans.hip, scan_disjoint.hip) */

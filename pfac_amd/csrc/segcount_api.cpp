@@ -2,12 +2,10 @@
  * segcount_api.cpp -- PFACX_countBatchFromDevice / ...FromHost / PFACX_countBatchPairsFromDevice (include/pfac_ext.h): how often each pattern
  * occurred in each segment of a batch, as (id, count) entries in CSR form.
  *
- * Every pattern that occurs at a position is a prefix of the longest one there, so all three forms work on longest pairs.  The device form is
- * PFACX_rulesMatchFromDevice up to its run call -- the ordered compacted scan into the handle's pair scratch (DeviceScratch::allPairs: the ids in its
- * first half, the positions in its second, `size` entries each), the batch fix-up of PFACX_matchBatchFromDeviceReduce behind it -- and then
- * PFACX_segCountRun (scan_segcount.hip) over the pairs; the pairs form is that run call alone over the caller's list.  The host form takes the longest
- * pairs of every segment -- the CPU platforms through hostLongestPairs, segment by segment; the GPU platform through the pipelined batch path -- and
- * keeps one counter per touched pattern in a loop of its own.
+ * Every pattern that occurs at a position is a prefix of the longest one there, so all three forms work on longest pairs.  The device form takes
+ * the ordered pairs of the batch in the handle's pair scratch from scratchBatchPairs (batch_api.cpp) and runs PFACX_segCountRun (scan_segcount.hip)
+ * over them; the pairs form is that run call alone over the caller's list.  The host form takes the longest pairs of every segment from
+ * HostBatchPairs (batch_api.cpp), pins the set the call started on, and keeps one counter per touched pattern in a loop of its own (countsOnHost).
  */
 #include <hip/hip_runtime_api.h>
 
@@ -21,8 +19,6 @@
 using namespace pfac_internal;
 
 namespace {
-
-constexpr size_t kTwoGiB = size_t(1) << 31;
 
 /* what the three calls check first, in the order of the contract (the pattern set: under the lock); items: the input, or the pair list */
 PFAC_status_t checkArgs(PFAC_handle_t handle, const void *items, size_t numItems, bool itemsRequired, const void *offsets, size_t numSegments,
@@ -67,7 +63,8 @@ PFAC_status_t runOnDevice(PFAC_context *c, const int *d_pairIds, size_t count, c
 /* nothing to count on the device: zeros, segFirst zeroed */
 PFAC_status_t nothingOnDevice(size_t *d_segFirst, size_t numSegments, size_t *h_numEntries, unsigned long long *h_total)
 {
-    if (numSegments && hipMemset(d_segFirst, 0, (numSegments + 1) * sizeof(size_t)) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+    const PFAC_status_t st = zeroSegmentArrays(d_segFirst, nullptr, numSegments);
+    if (st != PFAC_STATUS_SUCCESS) return st;
     *h_numEntries = 0;
     *h_total = 0;
     return PFAC_STATUS_SUCCESS;
@@ -123,23 +120,10 @@ PFAC_status_t PFACX_countBatchFromDevice(PFAC_handle_t handle, char *d_input, si
     if (!c->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
     if (size == 0) return nothingOnDevice(d_segFirst, numSegments, h_numEntries, h_total);
     if (followsChains(c->fa, flags)) st = ensureAllTable(c);
-    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = ensurePatternLen(c);              /* the fix-up's */
-    if (st == PFAC_STATUS_SUCCESS && d_offsets) st = c->scratch.allSegFirst.reserve(numSegments + 1);
-    pfac::DeviceBuffer<int> &pairs = c->scratch.allPairs;
-    if (st == PFAC_STATUS_SUCCESS) st = pairs.reserve(2 * size);
+    BatchPairs pairs{};
+    if (st == PFAC_STATUS_SUCCESS) st = scratchBatchPairs(c, d_input, size, d_offsets, numSegments, &pairs);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    int *ids = pairs.get(), *pos = ids + pairs.count() / 2;               /* one allocation: the ids, then as many positions */
-    DeviceScan scan;                                                      /* a caseless set: the scan and the fix-up read the folded bytes */
-    st = beginDeviceScan(c, d_input, size, &scan);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    int count = 0;
-    st = reduceOnDevice(c, scan.d_scan, size, ids, pos, true, &count);          /* ordered: the fix-up and the segments' first pairs search the positions */
-    if (st == PFAC_STATUS_SUCCESS && d_offsets)
-        st = c->batch_reduce_fixup_ptr(c, scan.d_scan, size, d_offsets, numSegments, ids, pos, &count, c->scratch.allSegFirst.get(), c->scratch.patternLen.get());
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0) return PFAC_STATUS_INTERNAL_ERROR;
-    return runOnDevice(c, ids, (size_t)count, d_offsets ? c->scratch.allSegFirst.get() : nullptr, numSegments, flags, d_ids, d_counts, capacity,
-                       d_segFirst, h_numEntries, h_total);
+    return runOnDevice(c, pairs.ids, pairs.count, pairs.segFirstPairs, numSegments, flags, d_ids, d_counts, capacity, d_segFirst, h_numEntries, h_total);
 }
 
 PFAC_status_t PFACX_countBatchPairsFromDevice(PFAC_handle_t handle, const int *d_pairIds, size_t numPairs, const int *d_segFirstPairs,
@@ -167,9 +151,6 @@ PFAC_status_t PFACX_countBatchFromHost(PFAC_handle_t handle, char *h_input, size
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (h_offsets && numSegments && !batchOffsetsValid(h_offsets, numSegments, size)) return PFAC_STATUS_INVALID_PARAMETER;
     PFAC_context *c = handle;
-    const size_t whole[2] = {0, size};
-    const size_t *offsets = h_offsets ? h_offsets : whole;
-    const bool onGpu = c->platform == PFAC_PLATFORM_GPU;
     std::unique_lock<std::mutex> guard(c->lock);
     if (!c->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
     const unsigned long long generation = c->setGeneration;                    /* the set every scan below has to see */
@@ -179,43 +160,13 @@ PFAC_status_t PFACX_countBatchFromHost(PFAC_handle_t handle, char *h_input, size
         *h_total = 0;
         return PFAC_STATUS_SUCCESS;
     }
-    if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    size_t longest = 0;
-    for (size_t k = 0; k < numSegments; k++) longest = std::max(longest, offsets[k + 1] - offsets[k]);
-    const HostPairs pairs(size, onGpu ? 0 : longest);                           /* the longest ids of segment k from ids[offsets[k]] on; the positions are not kept */
-    int *const ids = pairs.ids, *const pos = pairs.pos;
-    std::vector<int> numPairs;
-    try {
-        numPairs.assign(numSegments, 0);
-    } catch (const std::bad_alloc &) {
-        return PFAC_STATUS_ALLOC_FAILED;
-    }
-    if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
-    if (onGpu) {
-        /* the pipelined batch path: the full result of every segment, compacted in place (pair z of a segment comes from an entry at or behind z) */
-        st = matchBatchHostOnGpu(c, h_input, size, offsets, numSegments, ids);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-        for (size_t k = 0; k < numSegments; k++) {
-            int z = 0;
-            for (size_t i = offsets[k]; i < offsets[k + 1]; i++)
-                if (ids[i] > 0) ids[offsets[k] + (size_t)z++] = ids[i];
-            numPairs[k] = z;
-        }
-    } else {
-        guard.unlock();                                     /* the CPU platforms: the helper takes the lock while it prepares the tables, several threads match side by side */
-        for (size_t k = 0; k < numSegments; k++) {
-            const size_t n = offsets[k + 1] - offsets[k];
-            if (n == 0) continue;
-            st = hostLongestPairs(c, h_input + offsets[k], n, ids + offsets[k], pos, &numPairs[k], nullptr);
-            if (st != PFAC_STATUS_SUCCESS) return st;
-        }
-    }
-    /* generations only count up: the set is the one the call started on now, so it was during every scan above (on the GPU platform the lock is still held) */
-    const SetPin pin(c, generation);
-    if (pin.status() != PFAC_STATUS_SUCCESS) return pin.status();              /* another thread has replaced the set meanwhile: no count is written */
+    HostBatchPairs pairs(c, h_input, size, h_offsets, numSegments, false, guard);
+    if (pairs.status != PFAC_STATUS_SUCCESS) return pairs.status;
+    st = pairs.pin(generation);
+    if (st != PFAC_STATUS_SUCCESS) return st;                                  /* another thread has replaced the set meanwhile: PATTERNS_NOT_READY, no count is written */
     try {
         unsigned long long sum = 0;
-        const size_t total = countsOnHost(c->fa, flags, ids, offsets, numPairs.data(), numSegments, h_ids, h_counts, capacity, h_segFirst, &sum);
+        const size_t total = countsOnHost(c->fa, flags, pairs.ids, pairs.offsets, pairs.numPairs.data(), numSegments, h_ids, h_counts, capacity, h_segFirst, &sum);
         *h_numEntries = total;
         *h_total = sum;
         return truncatedIf(total, capacity);

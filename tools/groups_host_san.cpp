@@ -1,7 +1,8 @@
 /*
  * groups_host_san.cpp -- PFACX_groupsMatchFromHost on a host-only handle over the case table of tests/groups_ref.py, for the sanitizer build of the
  * host library (make -C pfac_amd/csrc san: build/groups_host_san links lib/san/libpfac.so; CPU only).  Every case runs in both modes, on both CPU
- * platforms, at a capacity that fits and at ones that truncate (0, 1, the length minus 1), into arrays allocated at exactly `capacity`, numSegments +
+ * platforms -- the longest pairs of every segment come from HostBatchPairs (batch_api.cpp), which the rules and the count-batch host forms share --,
+ * at a capacity that fits and at ones that truncate (0, 1, the length minus 1), into arrays allocated at exactly `capacity`, numSegments +
  * 1 and numSegments entries -- a write behind them is the sanitizer's to find -- and is compared with the definition, evaluated here position by
  * position.  Exit status 0: every list agreed.
  */

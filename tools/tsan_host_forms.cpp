@@ -1,9 +1,11 @@
 /* tools/tsan_host_forms.cpp -- the host forms that scan and then read the compiled set (PFACX_matchAllFromHost, countFromHost, matchWordsFromHost in
- * both modes, matchSpansFromHost, matchDisjointFromHost, matchLinesFromHost) and PFACX_replaceFromHost, under ThreadSanitizer (`make -C pfac_amd/csrc
- * tsan`): four threads call them on one host-only handle while a fifth replaces its pattern set, cycling through three sets.  A and B have the same
- * number of patterns -- A with chains of prefixes, B with none, and other lengths per id --, C has more.  Every call must end in the documented
- * refusal or in success with the single-threaded answer of one of the sets, a mixture of two sets never; and every form must have given every
- * set's answer at least once, so that a library that refuses everything does not pass.  CPU only.   tsan_host_forms [rounds] [pause in microseconds] */
+ * both modes, matchSpansFromHost, matchDisjointFromHost, matchLinesFromHost), PFACX_replaceFromHost and the batch host forms over the input cut at
+ * its newlines (PFACX_countBatchFromHost, rulesMatchFromHost, groupsMatchFromHost), under ThreadSanitizer (`make -C pfac_amd/csrc tsan`): four
+ * threads call them on one host-only handle while a fifth replaces its pattern set, cycling through three sets.  A and B have the same number of
+ * patterns -- A with chains of prefixes, B with none, and other lengths per id --, C has more.  Every call must end in the documented refusal
+ * (PATTERNS_NOT_READY; INVALID_PARAMETER for a rule set or a group table opened on a set that has been replaced: the thread opens a new one) or in
+ * success with the single-threaded answer of one of the sets, a mixture of two sets never; and every form must have given every set's answer at
+ * least once, so that a library that refuses everything does not pass.  CPU only.   tsan_host_forms [rounds] [pause in microseconds] */
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -17,15 +19,15 @@
 
 namespace {
 
-enum Form { kAll, kCount, kWordsList, kWordsAll, kSpans, kDisjoint, kLines, kReplace, kForms };
-const char *const kFormName[kForms] = {"matchAll", "count", "words", "words(all)", "spans", "disjoint", "lines", "replace"};
+enum Form { kAll, kCount, kWordsList, kWordsAll, kSpans, kDisjoint, kLines, kReplace, kCountBatch, kRules, kGroups, kForms };
+const char *const kFormName[kForms] = {"matchAll", "count", "words", "words(all)", "spans", "disjoint", "lines", "replace", "countBatch", "rules", "groups"};
 
 const std::string kSets[3] = {
     "a\nab\nabc\nabcd\nhe\nhers\n",                          /* A: chains a < ab < abc < abcd, he < hers */
     "she\nhi\nbcda\nx\ndog\ncats\n",                         /* B: as many patterns, none a prefix of another, other lengths per id */
     "abc\nab\nshe\nhe\nhers\ndog\ndo\ncat\nhis\n",           /* C: more patterns */
 };
-constexpr size_t kNumA = 6, kNumC = 9, kCanaries = 4;
+constexpr size_t kNumA = 6, kNumC = 9, kCanaries = 4, kBatchSegments = 16;
 constexpr unsigned long long kCanary = 0xC0FFEE0DDF00Dull;
 
 struct Fixture {
@@ -34,13 +36,32 @@ struct Fixture {
     std::vector<int> tokIds, tokPos;                         /* the disjoint tokens of set A: what PFACX_replaceFromHost is given, whatever set is loaded */
     std::vector<int> replOff;                                /* two offsets for every id of the largest set */
     std::string replBytes;
+    std::vector<size_t> offsets;                             /* the batch forms: the first kBatchSegments lines, a segment each (a call short enough to end between two swaps) */
+    std::vector<unsigned long long> segMasks;
 };
+
+/* the rule set and the group table of the batch forms; every id is one that all three sets have.  Rules: pattern 1; 2 and 5; 3 within the first 8
+ * bytes of the segment and no 6 */
+const int kRuleOff[4] = {0, 1, 3, 5};
+const PFACX_rule_member_t kRuleMembers[5] = {{1, 0u, 0u, 0u}, {2, 0u, 0u, 0u}, {5, 0u, 0u, 0u}, {3, 0u, 0u, 8u}, {6, PFACX_RULE_NOT, 0u, 0u}};
+const unsigned long long kPatternMasks[10] = {0, 1, 2, 4, 8, 16, 32, 1, 2, 4};
 
 struct Scratch {
     std::vector<int> a, b, c;
     std::vector<unsigned long long> counts;                  /* exactly kNumA + 1 entries, then the canaries */
     std::string out;
-    explicit Scratch(size_t n) : a(4 * n), b(4 * n), c(n), counts(kNumA + 1 + kCanaries, kCanary), out(8 * n, '\0') {}
+    std::vector<size_t> first;                               /* segFirst of the batch forms */
+    std::vector<unsigned long long> groups;                  /* segGroups */
+    PFACX_rules_t rules = nullptr;                           /* this thread's, opened on the set that was loaded then; null: none */
+    PFACX_groups_t table = nullptr;
+    Scratch(size_t n, size_t segments) : a(4 * n), b(4 * n), c(n), counts(kNumA + 1 + kCanaries, kCanary), out(8 * n, '\0'), first(segments + 1), groups(segments) {}
+    void closeTables()
+    {
+        if (rules) (void)PFACX_rulesClose(rules);
+        if (table) (void)PFACX_groupsClose(table);
+        rules = nullptr;
+        table = nullptr;
+    }
 };
 
 /* one call of form f: its status, and on success everything it wrote as one list of numbers.  false: a canary behind counts[] has changed */
@@ -74,9 +95,37 @@ bool call(Form f, const Fixture &x, Scratch &w, PFAC_status_t *status, std::vect
                                    x.replBytes.size(), &w.out[0], w.out.size(), &u);
         if (st == PFAC_STATUS_SUCCESS) r.assign(w.out.begin(), w.out.begin() + u);
         break;
+    case kCountBatch: {
+        unsigned long long total = 0;
+        st = PFACX_countBatchFromHost(x.h, in, x.offsets.back(), x.offsets.data(), x.offsets.size() - 1, 0, w.a.data(), reinterpret_cast<unsigned int *>(w.b.data()),
+                                      w.a.size(), w.first.data(), &u, &total);
+        v = (size_t)total;
+        listed = u;
+        if (st == PFAC_STATUS_SUCCESS) r.assign(w.first.begin(), w.first.end());
+        break;
+    }
+    case kRules:
+        st = w.rules ? PFAC_STATUS_SUCCESS : PFACX_rulesOpenEx(x.h, kRuleOff, kRuleMembers, 3, &w.rules);
+        if (st == PFAC_STATUS_SUCCESS)
+            st = PFACX_rulesMatchFromHost(w.rules, in, x.offsets.back(), x.offsets.data(), x.offsets.size() - 1, w.a.data(), w.b.data(), w.a.size(), w.first.data(), &u);
+        listed = u;
+        if (st == PFAC_STATUS_SUCCESS) r.assign(w.first.begin(), w.first.end());
+        break;
+    case kGroups:
+        st = w.table ? PFAC_STATUS_SUCCESS : PFACX_groupsOpen(x.h, kPatternMasks, kNumC + 1, &w.table);
+        if (st == PFAC_STATUS_SUCCESS)
+            st = PFACX_groupsMatchFromHost(w.table, in, x.offsets.back(), x.offsets.data(), x.offsets.size() - 1, x.segMasks.data(), PFACX_GROUPS_ALL, w.a.data(), w.b.data(),
+                                           w.a.size(), w.first.data(), w.groups.data(), &u);
+        listed = u;
+        if (st == PFAC_STATUS_SUCCESS) {
+            r.assign(w.first.begin(), w.first.end());
+            r.insert(r.end(), w.groups.begin(), w.groups.end());
+        }
+        break;
     default: break;
     }
     *status = st;
+    if (st == PFAC_STATUS_INVALID_PARAMETER && (f == kRules || f == kGroups)) w.closeTables();      /* opened on a set that is gone: a new one next time */
     if (st != PFAC_STATUS_SUCCESS) { r.clear(); return true; }
     r.push_back((long long)u);
     r.push_back((long long)v);
@@ -101,6 +150,10 @@ int main(int argc, char **argv)
         x.input += lines[k % 8];
         x.input += '\n';
     }
+    x.offsets.push_back(0);
+    for (size_t i = 0; i < x.input.size() && x.offsets.size() <= kBatchSegments; i++)
+        if (x.input[i] == '\n') x.offsets.push_back(i + 1);
+    for (size_t k = 0; k + 1 < x.offsets.size(); k++) x.segMasks.push_back((k * 11 + 1) & 63);
     for (size_t id = 0; id <= kNumC + 1; id++) {             /* the string of id: <id>; ids 0 and F + 1 have offsets and no string of their own */
         x.replOff.push_back((int)x.replBytes.size());
         if (id >= 1 && id <= kNumC) x.replBytes += "<" + std::to_string(id) + ">";
@@ -108,9 +161,10 @@ int main(int argc, char **argv)
     /* the single-threaded answers: want[form][set]; count on set C is the refusal of its numCounts check */
     std::vector<long long> want[kForms][3];
     PFAC_status_t wantStatus[kForms][3];
-    Scratch w0(x.input.size());
+    Scratch w0(x.input.size(), x.offsets.size() - 1);
     for (int set = 0; set < 3; set++) {
         if (!load(x.h, set)) { fprintf(stderr, "set %d refused\n", set); return 2; }
+        w0.closeTables();                                    /* a rule set and a group table of this set */
         for (int f = 0; f < kForms; f++) {
             if (f == kReplace && set == 0) {                 /* its tokens: the disjoint list of A, recorded above as {count, covered, ids, positions} */
                 const std::vector<long long> &d = want[kDisjoint][0];
@@ -125,6 +179,7 @@ int main(int argc, char **argv)
             }
         }
     }
+    w0.closeTables();
     for (int f = 0; f < kForms; f++)                         /* an answer that two sets share would hide a mixture */
         if (want[f][0] == want[f][1] || want[f][0] == want[f][2] || want[f][1] == want[f][2]) { fprintf(stderr, "%s: two sets, one answer\n", kFormName[f]); return 2; }
 
@@ -137,13 +192,14 @@ int main(int argc, char **argv)
     std::vector<std::thread> pool;
     for (int t = 0; t < threads; t++)
         pool.emplace_back([&, t]() {
-            Scratch w(x.input.size());
+            Scratch w(x.input.size(), x.offsets.size() - 1);
             std::vector<long long> got;
             for (long i = t; !done.load(); i++) {
                 const Form f = (Form)(i % kForms);
                 PFAC_status_t st;
                 if (!call(f, x, w, &st, &got)) { wrong++; fprintf(stderr, "%s: canary overwritten\n", kFormName[f]); continue; }
                 if (st == PFAC_STATUS_PATTERNS_NOT_READY) { refused[f]++; continue; }
+                if (st == PFAC_STATUS_INVALID_PARAMETER && (f == kRules || f == kGroups)) { refused[f]++; continue; }
                 int set = -1;
                 if (st == PFAC_STATUS_INVALID_PARAMETER && f == kCount) set = 2;
                 for (int k = 0; k < 3 && st == PFAC_STATUS_SUCCESS; k++)
@@ -151,6 +207,7 @@ int main(int argc, char **argv)
                 if (set < 0) { wrong++; fprintf(stderr, "%s: status %d, an answer of no set (%zu numbers)\n", kFormName[f], (int)st, got.size()); }
                 else seen[f][set]++;
             }
+            w.closeTables();
         });
     int failedLoads = 0;
     for (int r = 0; r < rounds; r++) {

@@ -10,7 +10,8 @@
  * does not have: batches of segments (PFACX_matchBatch*), every pattern at a
  * position (PFACX_matchAll*), caseless sets (PFACX_READ_NOCASE), streams
  * (PFACX_stream*), flow sets (PFACX_flows*), the lines that contain a
- * pattern (PFACX_matchLines*, PFACX_gatherLinesFromDevice), the bytes that
+ * pattern (PFACX_matchLines*, PFACX_gatherLinesFromDevice) and the lines
+ * around them (PFACX_matchLinesContext*), the bytes that
  * belong to a match, with their redaction (PFACX_matchSpans*,
  * PFACX_redactSpansFromDevice), the number of occurrences of every pattern
  * (PFACX_countFromDevice / ...FromHost, PFACX_countPairsFromDevice,
@@ -474,6 +475,44 @@ PFAC_status_t PFACX_matchLinesFromHost  (PFAC_handle_t handle, char *h_input, si
 PFAC_status_t PFACX_gatherLinesFromDevice(PFAC_handle_t handle, const char *d_input, size_t size,
                                           const int *d_lineStart, const int *d_lineLen, size_t numSelected,
                                           char *d_out, size_t outCapacity, size_t *h_outBytes);
+
+/* Lines with context: the lines around the lines PFACX_matchLines* select -- grep -A after -B before (-C n: both n).  Lines, line numbers, "a line
+ * matches", the caseless fold and PFACX_LINES_INVERT are exactly those of PFACX_matchLines*.
+ *   SELECTED.  Let H be the set of line numbers the plain call would select with the same flags: the matching lines, or under PFACX_LINES_INVERT
+ *   the lines that do not match.  With before and after -- any value -- the selected lines are { k in [0, numLines) : some h in H has
+ *   h - before <= k <= h + after }, evaluated without wrap-around: before = after = 0xFFFFFFFF selects every line as soon as H is not empty, and
+ *   nothing when it is.
+ *   GROUPS.  A group is a maximal run of consecutive selected line numbers; groups are numbered from 0 in ascending order.  Two windows that touch
+ *   or overlap are one group, as in grep, which prints "--" only where line numbers jump.
+ * The selected lines come in ascending order, each once; lineStart, lineLen and lineIndex (may be null) are as in PFACX_matchLines*.  lineTag[i]
+ * (unless the pointer is null) = group << 1 | m: m = 1 if line lineIndex[i] is in H -- the line grep prints with ':' --, m = 0 if it is context,
+ * which grep prints with '-'.  There are at most (numLines + 1) / 2 groups, so a tag is a non-negative int.  *h_numMatching = |H|, *h_numGroups =
+ * the number of groups, *h_numSelected = the length of the list; all four counts are written on every success.
+ * Consequences: with before = after = 0 the list is exactly that of PFACX_matchLines* with the same flags, every tag has m = 1 and the groups are
+ * the runs of adjacent matching lines; PFACX_gatherLinesFromDevice over (lineStart, lineLen) gives the text of grep -A / -B without its "--" lines;
+ * a caller who wants separators inserts one wherever lineTag[i] >> 1 changes.
+ * Everything else is PFACX_matchLines* word for word: capacity >= size entries of each array (smaller: PFAC_STATUS_INVALID_PARAMETER); lineStart /
+ * lineLen double as the scan's pair list, entries below `size` may be overwritten beyond the lines returned, nothing is written at or beyond
+ * capacity; numSelected <= numLines <= size, the list is never truncated.  size >= 2^31, an unknown flag bit, a null pointer other than lineIndex
+ * and lineTag: PFAC_STATUS_INVALID_PARAMETER; no pattern set: PFAC_STATUS_PATTERNS_NOT_READY; size == 0: success, all four counts 0, nothing
+ * touched; the device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.  Both calls are synchronous and take the handle's lock; the device
+ * form runs on whatever kernel variant, walker, perf mode and texture mode the handle selects; the host form follows PFAC_setPlatform as
+ * PFACX_matchLinesFromHost does (host-only handles included) and widens on the host; its temporaries are two bits per possible line
+ * (PFAC_STATUS_ALLOC_FAILED if they cannot be had).
+ * MEMORY of the device form: the scratch of PFACX_matchLinesFromDevice and, in a buffer of its own that a plain lines call never allocates, with
+ * B = (size + 15) / 2048 + 1: (256 B + 256) + 128 B + 4 B + 4 B + 4 (B + 1) + 4 B + 4 B + 4 (B + 1) + 4 bytes, each term rounded up to 256 --
+ * about 0.20 bytes per input byte, a function of the size alone: deviceScratchBytes of PFACX_getInfo, freed by PFACX_trim.
+ * COST: the plain call plus four launches over size / 8 bytes of bitmaps by line number; the same for every before and after.
+ * OUT OF SCOPE: "--" separators written by the gather; -m NUM; per-line match counts; context over streams or flows; context per segment of a
+ * batch. */
+PFAC_status_t PFACX_matchLinesContextFromDevice(PFAC_handle_t handle, char *d_input, size_t size, unsigned int flags,
+                                                unsigned int before, unsigned int after,
+                                                int *d_lineStart, int *d_lineLen, int *d_lineIndex /* may be NULL */, int *d_lineTag /* may be NULL */,
+                                                size_t capacity, size_t *h_numLines, size_t *h_numSelected, size_t *h_numMatching, size_t *h_numGroups);
+PFAC_status_t PFACX_matchLinesContextFromHost  (PFAC_handle_t handle, char *h_input, size_t size, unsigned int flags,
+                                                unsigned int before, unsigned int after,
+                                                int *h_lineStart, int *h_lineLen, int *h_lineIndex /* may be NULL */, int *h_lineTag /* may be NULL */,
+                                                size_t capacity, size_t *h_numLines, size_t *h_numSelected, size_t *h_numMatching, size_t *h_numGroups);
 
 /* Spans: the bytes of a buffer that belong to a match -- what grep --color highlights -- and the buffer with those bytes overwritten (redaction).
  *   COVERED.  Let r be the full result of PFAC_matchFromHost on a CPU platform over the whole buffer of n bytes and len(id) the length of pattern id.

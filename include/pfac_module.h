@@ -137,6 +137,14 @@ PFAC_status_t PFACX_linesSelect(PFAC_handle_t handle, const char *d_input, char 
                                 int *d_lineLen, int *d_lineIndex, size_t *h_numLines, size_t *h_numSelected);
 PFAC_status_t PFACX_linesGather(PFAC_handle_t handle, const char *d_input, size_t size, const int *d_lineStart, const int *d_lineLen,
                                 size_t numSelected, char *d_out, size_t outCapacity, size_t *h_outBytes);
+/* PFACX_linesSelectContext (include/pfac_ext.h: PFACX_matchLinesContext*): PFACX_linesSelect with the lines up to `before` in front of and `after`
+ * behind each line that call would select.  The same launches with the context stage between the marks and the select passes: the hit bitmap
+ * becomes that of the lines the plain call selects, is widened by line number, and the select passes run over the widened bitmap; d_lineTag (unless
+ * null) gets group << 1 | (the line is one the plain call selects).  *h_numMatching = the lines the plain call selects, *h_numGroups = the runs of
+ * consecutive selected lines.  Scratch of the stage: the handle's context scratch (scan_lines.hip has the formula).  Synchronous. */
+PFAC_status_t PFACX_linesSelectContext(PFAC_handle_t handle, const char *d_input, char *d_scan, size_t size, int invert, int hashed,
+                                       unsigned int before, unsigned int after, int *d_lineStart, int *d_lineLen, int *d_lineIndex, int *d_lineTag,
+                                       size_t *h_numLines, size_t *h_numSelected, size_t *h_numMatching, size_t *h_numGroups);
 
 /* Measurement only: the newline pass of PFACX_linesSelect alone (pfac_lines_bitmap: one read of the input, size / 8 + size / 8 + size / 16 bytes written
  * into the handle's lines scratch).  Returns the average milliseconds of `launches` launches over the first n < 2^31 bytes of d_in, or a negative
@@ -316,7 +324,7 @@ PFAC_status_t PFACX_groupsRun(PFAC_handle_t handle, const PFACX_groupsRun_t *run
     X(batch_fixup_ptr, PFACX_batchFixup) X(batch_reduce_fixup_ptr, PFACX_batchReduceFixup) \
     X(all_reduce_ptr, PFACX_allReduce) X(all_expand_ptr, PFACX_allExpand) X(fold_input_ptr, PFACX_foldInput) \
     X(stream_seam_ptr, PFACX_streamSeam) X(stream_reduce_ptr, PFACX_streamReduce) X(flows_run_ptr, PFACX_flowsRun) \
-    X(lines_select_ptr, PFACX_linesSelect) X(lines_gather_ptr, PFACX_linesGather) \
+    X(lines_select_ptr, PFACX_linesSelect) X(lines_select_context_ptr, PFACX_linesSelectContext) X(lines_gather_ptr, PFACX_linesGather) \
     X(spans_select_ptr, PFACX_spansSelect) X(spans_redact_ptr, PFACX_spansRedact) \
     X(count_pairs_ptr, PFACX_countPairs) X(count_nonzero_ptr, PFACX_countNonzero) \
     X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun) \

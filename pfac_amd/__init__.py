@@ -17,6 +17,7 @@ from .api import (  # noqa: F401
     Groups,
     PFAC,
     PFACX_GROUPS_ALL,
+    PFACX_LINES_INVERT,
     PFACError,
     PFAC_AUTOMATIC,
     PFAC_PLATFORM_CPU,

@@ -126,6 +126,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_streamOpen", "PFACX_streamReset", "PFACX_streamClose", "PFACX_streamMatchFromDevice", "PFACX_streamMatchFromHost", "PFACX_streamFlush",
     "PFACX_flowsOpen", "PFACX_flowsClose", "PFACX_flowsReset", "PFACX_flowsMatchFromDevice", "PFACX_flowsMatchFromHost", "PFACX_flowsFlush",
     "PFACX_matchLinesFromDevice", "PFACX_matchLinesFromHost", "PFACX_gatherLinesFromDevice",
+    "PFACX_matchLinesContextFromDevice", "PFACX_matchLinesContextFromHost",
     "PFACX_matchSpansFromDevice", "PFACX_matchSpansFromHost", "PFACX_redactSpansFromDevice",
     "PFACX_countFromDevice", "PFACX_countFromHost", "PFACX_countPairsFromDevice", "PFACX_countNonzeroFromDevice",
     "PFACX_matchDisjointFromDevice", "PFACX_matchDisjointFromHost", "PFACX_replaceFromDevice", "PFACX_replaceFromHost",
@@ -140,7 +141,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_batchFixup", "PFACX_batchReduceFixup",
     "PFACX_allReduce", "PFACX_allExpand", "PFACX_foldInput",
     "PFACX_streamSeam", "PFACX_streamReduce", "PFACX_flowsRun",
-    "PFACX_linesSelect", "PFACX_linesGather", "PFACX_linesBitmapProbe", "PFACX_orderPairsProbe",
+    "PFACX_linesSelect", "PFACX_linesSelectContext", "PFACX_linesGather", "PFACX_linesBitmapProbe", "PFACX_orderPairsProbe",
     "PFACX_spansSelect", "PFACX_spansRedact",
     "PFACX_countPairs", "PFACX_countNonzero",
     "PFACX_disjointSelect", "PFACX_replaceRun",
@@ -235,6 +236,11 @@ def load_library() -> C.CDLL:
         lib.PFACX_matchLinesFromDevice.argtypes = lines
         lib.PFACX_matchLinesFromHost.argtypes = lines
         lib.PFACX_gatherLinesFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, SZ]
+    if hasattr(lib, "PFACX_matchLinesContextFromDevice"):
+        SZ = C.POINTER(C.c_size_t)
+        context = [H, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, SZ, SZ, SZ, SZ]
+        lib.PFACX_matchLinesContextFromDevice.argtypes = context
+        lib.PFACX_matchLinesContextFromHost.argtypes = context
     if hasattr(lib, "PFACX_matchSpansFromDevice"):
         SZ = C.POINTER(C.c_size_t)
         spans = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, SZ, SZ]
@@ -591,6 +597,40 @@ class PFAC:
         _, nl, ns = self.matchLinesFromHost(data.ctypes.data if data.size else start.ctypes.data, data.size, PFACX_LINES_INVERT if invert else 0,
                                             start.ctypes.data, length.ctypes.data, index.ctypes.data, cap)
         return nl, start[:ns].copy(), length[:ns].copy(), index[:ns].copy()
+
+    # -- the lines around the selected lines (include/pfac_ext.h: PFACX_matchLinesContext*) ------------
+    def _lines_context(self, name, input_, size, flags, before, after, line_start, line_len, line_index, line_tag, capacity, check):
+        nl, ns, nm, ng = (C.c_size_t(0) for _ in range(4))
+        st = getattr(self._lib, name)(self._h, input_, size, flags, before, after, line_start, line_len, line_index, line_tag, capacity,
+                                      C.byref(nl), C.byref(ns), C.byref(nm), C.byref(ng))
+        return self._ret(st, name, check), nl.value, ns.value, nm.value, ng.value
+
+    def matchLinesContextFromDevice(self, d_input: int, size: int, flags: int, before: int, after: int, d_line_start: int, d_line_len: int,
+                                    d_line_index, d_line_tag, capacity: int, check: bool = True):
+        """``PFACX_matchLinesContextFromDevice`` -> (status, lines, selected lines, matching lines, groups); `d_line_index` and
+        `d_line_tag` may be None."""
+        return self._lines_context("PFACX_matchLinesContextFromDevice", d_input, size, flags, before, after, d_line_start, d_line_len,
+                                   d_line_index, d_line_tag, capacity, check)
+
+    def matchLinesContextFromHost(self, h_input: int, size: int, flags: int, before: int, after: int, h_line_start: int, h_line_len: int,
+                                  h_line_index, h_line_tag, capacity: int, check: bool = True):
+        """``PFACX_matchLinesContextFromHost`` -> (status, lines, selected lines, matching lines, groups); `h_line_index` and
+        `h_line_tag` may be None."""
+        return self._lines_context("PFACX_matchLinesContextFromHost", h_input, size, flags, before, after, h_line_start, h_line_len,
+                                   h_line_index, h_line_tag, capacity, check)
+
+    def match_lines_context_host_array(self, data, before: int = 0, after: int = 0, invert: bool = False):
+        """matchLinesContextFromHost over a numpy array -> (line_start, line_len, line_index, line_tag, (lines, selected, matching, groups)):
+        the lines within `before` in front of and `after` behind a line that contains a pattern (invert: that contains none), ascending;
+        line_tag = group << 1 | (1 for such a line itself, 0 for context)."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        cap = max(1, data.size)
+        start, length, index, tag = (np.full(cap, -7, dtype=np.int32) for _ in range(4))
+        _, nl, ns, nm, ng = self.matchLinesContextFromHost(data.ctypes.data if data.size else start.ctypes.data, data.size,
+                                                           PFACX_LINES_INVERT if invert else 0, before, after, start.ctypes.data,
+                                                           length.ctypes.data, index.ctypes.data, tag.ctypes.data, cap)
+        return start[:ns].copy(), length[:ns].copy(), index[:ns].copy(), tag[:ns].copy(), (nl, ns, nm, ng)
 
     # -- the bytes that belong to a match, and their redaction (include/pfac_ext.h: PFACX_matchSpans*) ------------
     def matchSpansFromDevice(self, d_input: int, size: int, d_span_start: int, d_span_len: int, capacity: int, check: bool = True):

@@ -70,7 +70,8 @@ constexpr HostSlot kHostRules = {48, 50};         /* a rules call: the 64-bit le
 constexpr HostSlot kHostWordList = {52, 54};      /* a words call: the 64-bit length of its list (scan_words.hip, by pfac_array_scan) */
 constexpr HostSlot kHostSegCount = {56, 60};      /* a batch count call: two 64-bit values, the length of its count list (scan_segcount.hip, by pfac_array_scan), then the sum of the counts (pfac_segcount_finish) */
 constexpr HostSlot kHostGroups = {62, 61};        /* a groups call: the 64-bit length of its list (scan_groups.hip, by pfac_array_scan) */
-constexpr int kHostWords = 64;
+constexpr HostSlot kHostLinesContext = {64, 68}; /* a lines call with context: the lines, the selected lines, the matching lines, the groups (scan_lines.hip, by pfac_block_scan and pfac_lines_widen) */
+constexpr int kHostWords = 72;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -423,6 +424,10 @@ struct DeviceScratch {
      * the per-word ranks and the per-block counts (a fixed function of the input size: scan_lines.hip has the formula), or into the offsets of a gather;
      * not allocated before the first lines call */
     DeviceBuffer<char> lines;
+    /* the context stage of PFACX_matchLinesContext* (scan_lines.hip has the formula): ONE allocation a call cuts into the widened bitmap by line
+     * number, the group ranks per word and, per 2048 lines, the nearest members, the group starts and their scans; a plain lines call allocates
+     * none of it */
+    DeviceBuffer<char> linesContext;
     /* the spans calls (PFACX_matchSpans*, scan_spans.hip): ONE allocation a call cuts into the starts and ends of the spans and the per-block values of
      * its pair-space passes -- 8.04 bytes per pair of the scan at most (scan_spans.hip has the formula); not allocated before the first spans call that
      * finds a pair */
@@ -457,7 +462,7 @@ struct DeviceScratch {
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
-        f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines);
+        f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines); f(linesContext);
         f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups);
     }
     void release() { forEach([](auto &b) { b.release(); }); }

@@ -32,6 +32,27 @@
  * first line by binary search in the offsets, stages the offsets of its lines (at most 4096) in LDS, and every thread assembles 16 output
  * bytes -- one 3 MiB line and a million 20-byte lines are the same work per byte.  Tiles are aligned on the output address, a tile stops at
  * outCapacity.  SCRATCH of a gather: 8 (numSelected + 1) bytes of offsets + 8 bytes per 256 .. 2048 lines of block sums.
+ *
+ * Context (PFACX_matchLinesContext*): the lines within `before` in front of and `after` behind a line of H, the lines the plain call
+ * selects.  It is a dilation of the line-hit bitmap in the LINE-INDEX domain -- bit k is line k; a LINE BLOCK is 2048 lines = 64 words = one wave
+ * -- between pfac_lines_mark and the select passes, entered from PFACX_linesSelectContext only:
+ *   pfac_lines_members     the hit bitmap becomes H's in place: hit ^ invert, the bits at and beyond the number of lines cleared (under INVERT
+ *                          they are all ones: they must be gone before anything is widened).  Per line block: H's last member + 1, the
+ *                          complement of its first (nearer = larger, so that the scan below is a maximum too; stored back to front), and
+ *                          H's popcount added to one word: the number of matching lines
+ *   pfac_block_scan<max, max>  in one launch the nearest member in front of each line block and -- the second column runs back to front --
+ *                          the nearest behind it
+ *   pfac_lines_widen       a word per lane: the nearest members in front of and behind the word by a wave prefix and a wave suffix maximum on
+ *                          top of the block's two values.  A member in front reaches the word's low bits, a member behind its high bits, the
+ *                          word's own members are smeared by min(after, 31) and min(before, 31) in five doubling shifts: the work is the same
+ *                          for every before and after.  Writes the widened bitmap, and the GROUP STARTS -- selected lines whose predecessor
+ *                          is not -- in front of each word of its line block (ushort) and per line block
+ *   pfac_block_scan<sum>   the group starts in front of each line block; the total is the number of groups
+ *   pfac_lines_select<0 / 1, ContextArgs>  the plain walk over the widened bitmap; the emit pass also writes the tag: the group from the group
+ *                          starts in front of the word's first line, counted on along its lines, and the member bit from H's bitmap
+ * SCRATCH of the stage, B as above (a buffer of its own: a plain call allocates none of it): 256 B + 256 once (widened bitmap) + 128 B (group
+ * ranks) + 4 B + 4 B + 4 (B + 1) + 4 B + 4 B + 4 (B + 1) + 4 bytes (per line block: the two nearest members and their scans, the group starts
+ * and their scan; the matching lines), each part rounded up to 256 bytes: 0.20 bytes per input byte.
  * Plain C++ and vector stores only.
  */
 #if !defined(__gfx950__) && defined(__HIP_DEVICE_COMPILE__)
@@ -63,6 +84,20 @@ struct LinesArgs {
     unsigned int *lastNl, *prevNl;      /* [blocks] q + 1 of the block's last newline (0: none; q itself may pass 2^31); of the last newline in front of the block */
     uint32_t invert;                    /* 0 or 0xFFFFFFFF */
     int *lineStart, *lineLen, *lineIndex;
+};
+
+/* the same with context: bitmaps and counts by LINE NUMBER, a line block = 2048 lines = 64 words.  hitBits holds H once pfac_lines_members has run */
+struct ContextArgs : LinesArgs {
+    uint32_t *selBits;                  /* [blocks * 64 + 64] bit k: line k is selected */
+    uint16_t *groupRank;                /* [blocks * 64] group starts of the line block in front of the word */
+    unsigned int *memberTop, *memberNext;   /* [blocks] k + 1 of the line block's last member of H (0: none); ~k of its first, block b at blocks - 1 - b */
+    unsigned int *prevMember, *nextMember;  /* [blocks + 1], [blocks] their running maxima: the nearest member in front of / behind the line block */
+    unsigned int *groupCount, *groupBase;   /* [blocks] group starts per line block; [blocks + 1] in front of it, [blocks] = the number of groups */
+    unsigned int *matching;             /* one word, zero when pfac_lines_members starts: |H| */
+    unsigned int *hostMatching;         /* the same in mapped host memory, or null */
+    uint32_t membersInvert;             /* 0 or 0xFFFFFFFF: H = hit ^ this (invert itself stays 0: the select passes read selBits as it is) */
+    unsigned int before, after;
+    int *lineTag;
 };
 
 /* bits 7, 15, 23, 31 of m -- one per byte -- as a nibble, byte 0 in bit 0: the four products land on bits 21..24 and nothing carries */
@@ -129,10 +164,17 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_mark(LinesArgs a, co
     }
 }
 
-/* WRITE == 0: the selected lines that end in each block, and the block's last newline; WRITE == 1: their (start, len, index) */
-template <int WRITE>
-__global__ __launch_bounds__(kLinesThreads) void pfac_lines_select(LinesArgs a)
+/* the bitmap by line number that the select passes read: the hits, or with context the widened bitmap (invert == 0 there) */
+__device__ __forceinline__ const uint32_t *selectBits(const LinesArgs &a) { return a.hitBits; }
+__device__ __forceinline__ const uint32_t *selectBits(const ContextArgs &a) { return a.selBits; }
+
+/* WRITE == 0: the selected lines that end in each block, and the block's last newline; WRITE == 1: their (start, len, index) -- and, with
+ * context (Args = ContextArgs), their tags */
+template <int WRITE, class Args = LinesArgs>
+__global__ __launch_bounds__(kLinesThreads) void pfac_lines_select(Args a)
 {
+    constexpr bool kContext = std::is_same<Args, ContextArgs>::value;
+    const uint32_t *const bits = selectBits(a);
     const unsigned int lane = threadIdx.x & 63u;
     const unsigned int waves = gridDim.x * (kLinesThreads / 64);
     for (unsigned int b = blockIdx.x * (kLinesThreads / 64) + (threadIdx.x >> 6); b < a.blocks; b += waves) {
@@ -140,7 +182,7 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_select(LinesArgs a)
         uint32_t word = a.nlBits[w];
         const uint32_t c = (uint32_t)__popc(word);
         const unsigned int first = a.lineBase[b] + a.rank[w];           /* the lines that end in this word: [first, first + c) */
-        const uint32_t h0 = a.hitBits[first >> 5], h1 = a.hitBits[(first >> 5) + 1];
+        const uint32_t h0 = bits[first >> 5], h1 = bits[(first >> 5) + 1];
         const uint32_t hits = (uint32_t)((((uint64_t)h1 << 32) | h0) >> (first & 31u));
         const uint32_t sel = (hits ^ a.invert) & (c >= 32u ? 0xFFFFFFFFu : (1u << c) - 1u);
         const uint32_t ns = (uint32_t)__popc(sel);
@@ -154,6 +196,20 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_select(LinesArgs a)
             /* q + 1 of the last newline in front of this word: where its first line starts */
             unsigned int prev = OpMax()(a.prevNl[b], waveExclusiveOf(waveInclusive(last, OpMax())));
             size_t o = (size_t)a.selBase[b] + (incl - ns);
+            /* with context: H's bits of these lines, the group starts up to the first of them, whether the line in front of it is selected */
+            uint32_t members = 0, behind = 0;
+            unsigned int groups = 0;
+            if constexpr (kContext) {
+                if (a.lineTag != nullptr && c != 0) {
+                    const unsigned int wi = first >> 5, r = first & 31u;
+                    const uint32_t m0 = a.hitBits[wi], m1 = a.hitBits[wi + 1];
+                    members = (uint32_t)((((uint64_t)m1 << 32) | m0) >> r);
+                    const uint32_t carry = wi ? bits[wi - 1] >> 31 : 0u;
+                    const uint32_t starts = h0 & ~((h0 << 1) | carry);
+                    groups = a.groupBase[wi >> 6] + a.groupRank[wi] + (unsigned int)__popc(starts & ((1u << r) - 1u));
+                    behind = r ? (h0 >> (r - 1u)) & 1u : carry;
+                }
+            }
             for (unsigned int j = 0; word; j++) {
                 const unsigned int q = qWord + (unsigned int)__ffs((int)word) - 1u;
                 word &= word - 1u;
@@ -162,11 +218,120 @@ __global__ __launch_bounds__(kLinesThreads) void pfac_lines_select(LinesArgs a)
                     a.lineStart[o] = (int)(startQ - a.mis);
                     a.lineLen[o] = (int)(q - startQ);
                     if (a.lineIndex != nullptr) a.lineIndex[o] = (int)(first + j);
+                    if constexpr (kContext) {
+                        if (a.lineTag != nullptr) {
+                            groups += behind ^ 1u;                         /* a selected line behind one that is not: the next group */
+                            a.lineTag[o] = (int)(((groups - 1u) << 1) | ((members >> j) & 1u));
+                        }
+                    }
                     o++;
                 }
+                if constexpr (kContext) behind = (sel >> j) & 1u;
                 prev = q + 1u;
             }
         }
+    }
+}
+
+/* ------------------------------------------------------------------ context: the dilation of H by line number */
+
+/* the bits of word w of a bitmap by line number that stand for lines: those below numLines */
+__device__ __forceinline__ uint32_t lineBitsOf(unsigned int numLines, unsigned int k0)
+{
+    return k0 >= numLines ? 0u : (numLines - k0 >= 32u ? 0xFFFFFFFFu : (1u << (numLines - k0)) - 1u);
+}
+
+/* x with every bit also set in the s <= 31 places above it (below it): shifts of 1, 2, 4, ... that add up to s reach every distance up to s */
+__device__ __forceinline__ uint32_t smearUp(uint32_t x, uint32_t s)
+{
+    for (uint32_t d = 1; s != 0; d <<= 1) {
+        const uint32_t t = d < s ? d : s;
+        x |= x << t;
+        s -= t;
+    }
+    return x;
+}
+__device__ __forceinline__ uint32_t smearDown(uint32_t x, uint32_t s)
+{
+    for (uint32_t d = 1; s != 0; d <<= 1) {
+        const uint32_t t = d < s ? d : s;
+        x |= x >> t;
+        s -= t;
+    }
+    return x;
+}
+
+/* a word h of H's bitmap whose first line is k0: k + 1 of its last member (0: none), and ~k of its first -- the nearer to k0, the larger; never 0
+ * for a member, k < 2^31 */
+__device__ __forceinline__ unsigned int lastMemberOf(uint32_t h, unsigned int k0) { return h ? k0 + 32u - (unsigned int)__clz((int)h) : 0u; }
+__device__ __forceinline__ unsigned int firstMemberOf(uint32_t h, unsigned int k0) { return h ? ~(k0 + (unsigned int)__ffs((int)h) - 1u) : 0u; }
+
+/* a wave per line block: the hit bitmap becomes H's, and what the line block hands to the two running maxima and to |H| */
+__global__ __launch_bounds__(kLinesThreads) void pfac_lines_members(ContextArgs a)
+{
+    const unsigned int lane = threadIdx.x & 63u;
+    const unsigned int waves = gridDim.x * (kLinesThreads / 64);
+    const unsigned int numLines = a.lineBase[a.blocks];
+    for (unsigned int b = blockIdx.x * (kLinesThreads / 64) + (threadIdx.x >> 6); b < a.blocks; b += waves) {
+        if ((b << kBlockShift) >= numLines) {                  /* no line here (most line blocks: a line has a byte or more): nothing reads these words */
+            if (lane == 63u) { a.memberTop[b] = 0; a.memberNext[a.blocks - 1u - b] = 0; }
+            continue;
+        }
+        const size_t w = (size_t)b * kBlockWords + lane;
+        const unsigned int k0 = (b << kBlockShift) + lane * 32u;
+        const uint32_t h = (a.hitBits[w] ^ a.membersInvert) & lineBitsOf(numLines, k0);
+        a.hitBits[w] = h;
+        const unsigned int top = waveReduce(lastMemberOf(h, k0), OpMax()), next = waveReduce(firstMemberOf(h, k0), OpMax());
+        const uint32_t members = waveInclusiveScan((uint32_t)__popc(h));
+        if (lane == 63u) {
+            a.memberTop[b] = top;
+            a.memberNext[a.blocks - 1u - b] = next;
+            if (members != 0) atomicAdd(a.matching, members);
+        }
+    }
+}
+
+/* a wave per line block, a word per lane: the widened bitmap and its group starts */
+__global__ __launch_bounds__(kLinesThreads) void pfac_lines_widen(ContextArgs a)
+{
+    const unsigned int lane = threadIdx.x & 63u;
+    const unsigned int waves = gridDim.x * (kLinesThreads / 64);
+    const unsigned int numLines = a.lineBase[a.blocks];
+    const uint32_t up = a.after < 31u ? a.after : 31u, down = a.before < 31u ? a.before : 31u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) storeToHost(a.hostMatching, *a.matching);
+    for (unsigned int b = blockIdx.x * (kLinesThreads / 64) + (threadIdx.x >> 6); b < a.blocks; b += waves) {
+        if ((b << kBlockShift) >= numLines) {
+            if (lane == 63u) a.groupCount[b] = 0;
+            continue;
+        }
+        const size_t w = (size_t)b * kBlockWords + lane;
+        const unsigned int k0 = (b << kBlockShift) + lane * 32u;
+        const uint32_t h = a.hitBits[w];
+        /* k + 1 of the nearest member in front of line k0; ~k of the nearest from line k0 + 32 on: the suffix is a prefix over the lanes back to front */
+        const unsigned int prev = OpMax()(a.prevMember[b], waveExclusiveOf(waveInclusive(lastMemberOf(h, k0), OpMax())));
+        const unsigned int back = (unsigned int)__shfl((int)firstMemberOf(h, k0), (int)(63u - lane));
+        const unsigned int suffix = (unsigned int)__shfl((int)waveExclusiveOf(waveInclusive(back, OpMax())), (int)(63u - lane));
+        const unsigned int next = OpMax()(a.nextMember[a.blocks - 1u - b], suffix);
+        uint32_t sel = smearUp(h, up) | smearDown(h, down);
+        uint32_t behind = 0;                                    /* line k0 - 1 is selected */
+        if (prev != 0) {
+            const unsigned long long reach = (unsigned long long)(prev - 1u) + a.after;        /* the last line that member selects */
+            if (reach >= k0) sel |= reach - k0 >= 31u ? 0xFFFFFFFFu : (2u << (unsigned int)(reach - k0)) - 1u;
+            behind = reach + 1u >= k0 ? 1u : 0u;
+        }
+        if (next != 0) {
+            const unsigned int m = ~next, from = m > a.before ? m - a.before : 0u;              /* the first line that member selects */
+            if (from <= k0 + 31u) sel |= from > k0 ? 0xFFFFFFFFu << (from - k0) : 0xFFFFFFFFu;
+        }
+        const unsigned int near = h ? ~firstMemberOf(h, k0) : ~next;                             /* the nearest member from line k0 on, if h | next */
+        if ((h | next) != 0 && (near > a.before ? near - a.before : 0u) < k0) behind = 1u;
+        sel &= lineBitsOf(numLines, k0);
+        const uint32_t starts = sel & ~((sel << 1) | behind);
+        const uint32_t c = (uint32_t)__popc(starts);
+        const uint32_t incl = waveInclusiveScan(c);
+        a.selBits[w] = sel;
+        a.groupRank[w] = (uint16_t)(incl - c);
+        if (lane == 63u) a.groupCount[b] = incl;
     }
 }
 
@@ -304,6 +469,23 @@ bool linesArgs(PFAC_context *c, const void *in, size_t n, bool select, LinesArgs
     }) == PFAC_STATUS_SUCCESS;
 }
 
+/* ... and what the context stage adds, from the handle's context scratch (a buffer of its own: a plain lines call allocates none of it) */
+bool contextArgs(PFAC_context *c, ContextArgs &a)
+{
+    const size_t blocks = a.blocks, words = blocks * kBlockWords;
+    return carveScratch(c->scratch.linesContext, [&](ScratchCarver &k) {
+        a.selBits = k.take<uint32_t>(words, 256);               /* and the word a funnel may read behind it */
+        a.groupRank = k.take<uint16_t>(words);
+        a.memberTop = k.take<unsigned int>(blocks);
+        a.memberNext = k.take<unsigned int>(blocks);
+        a.prevMember = k.take<unsigned int>(blocks + 1);
+        a.nextMember = k.take<unsigned int>(blocks);
+        a.groupCount = k.take<unsigned int>(blocks);
+        a.groupBase = k.take<unsigned int>(blocks + 1);
+        a.matching = k.take<unsigned int>(1);
+    }) == PFAC_STATUS_SUCCESS;
+}
+
 /* the grid of the passes that take a block of positions per wave */
 unsigned int waveGridFor(const PFAC_context *c, unsigned int blocks) { return (blocks + 3) / 4 < gridCap(c, 8) ? (blocks + 3) / 4 : gridCap(c, 8); }
 
@@ -346,6 +528,70 @@ PFAC_status_t PFACX_linesSelect(PFAC_handle_t handle, const char *d_input, char 
     if (lines[0] > size || lines[1] > lines[0]) return PFAC_STATUS_INTERNAL_ERROR;
     *h_numLines = lines[0];
     *h_numSelected = lines[1];
+    return PFAC_STATUS_SUCCESS;
+}
+
+PFAC_status_t PFACX_linesSelectContext(PFAC_handle_t handle, const char *d_input, char *d_scan, size_t size, int invert, int hashed,
+                                       unsigned int before, unsigned int after, int *d_lineStart, int *d_lineLen, int *d_lineIndex, int *d_lineTag,
+                                       size_t *h_numLines, size_t *h_numSelected, size_t *h_numMatching, size_t *h_numGroups)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!d_input || !d_scan || !d_lineStart || !d_lineLen || !h_numLines || !h_numSelected || !h_numMatching || !h_numGroups || size == 0 ||
+        size > (size_t)0x7fffffff)
+        return PFAC_STATUS_INVALID_PARAMETER;
+    PFAC_context *c = handle;
+    ContextArgs a{};
+    if (!linesArgs(c, d_input, size, true, a) || !contextArgs(c, a)) return PFAC_STATUS_CUDA_ALLOC_FAILED;
+    a.invert = 0;                                               /* the select passes read the widened bitmap as it is */
+    a.membersInvert = invert ? 0xFFFFFFFFu : 0u;
+    a.before = before;
+    a.after = after;
+    a.lineStart = d_lineStart;
+    a.lineLen = d_lineLen;
+    a.lineIndex = d_lineIndex;
+    a.lineTag = d_lineTag;
+    const HostHandoff counts(c, pfac::kHostLinesContext);      /* the lines, the selected lines, the matching lines, the groups */
+    a.hostMatching = counts.word(2);
+    const unsigned int waveGrid = waveGridFor(c, a.blocks);
+
+    /* the head of a plain call: the line index, the scan, the marks; the scan of the line counts also clears the word |H| is added up in */
+    hipLaunchKernelGGL(pfac_lines_bitmap, dim3(waveGrid), dim3(kLinesThreads), 0, 0, static_cast<const LinesArgs &>(a));
+    blockScan<OpSum>({{a.lineCount}, {a.lineBase}}, a.blocks, counts.word(0), a.matching);
+    if (hipGetLastError() != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+    size_t count = 0;
+    const PFAC_status_t st = compactedScan(handle, d_scan, size, hashed, d_lineStart, d_lineLen, false, &count);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    if (count > 0)
+        hipLaunchKernelGGL(pfac_lines_mark, dim3(gridFor(c, count)), dim3(kLinesThreads), 0, 0, static_cast<const LinesArgs &>(a), (const int *)d_lineLen,
+                           (unsigned int)count);
+
+    /* the context stage: H, the nearest members around each line block, the widened bitmap, the group starts in front of each line block */
+    hipLaunchKernelGGL(pfac_lines_members, dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
+    blockScan<OpMax, OpMax, 2>({{a.memberTop, a.memberNext}, {a.prevMember, a.nextMember}}, a.blocks, nullptr, nullptr);
+    hipLaunchKernelGGL(pfac_lines_widen, dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
+    blockScan<OpSum>({{a.groupCount}, {a.groupBase}}, a.blocks, counts.word(3), nullptr);
+
+    /* the tail of a plain call, over the widened bitmap */
+    hipLaunchKernelGGL((pfac_lines_select<0, ContextArgs>), dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
+    blockScan<OpSum, OpMax, 2>({{a.selCount, a.lastNl}, {a.selBase, a.prevNl}}, a.blocks, counts.word(1), nullptr);
+    hipLaunchKernelGGL((pfac_lines_select<1, ContextArgs>), dim3(waveGrid), dim3(kLinesThreads), 0, 0, a);
+
+    unsigned int v[4] = {0, 0, 0, 0};                           /* lines, selected, matching, groups */
+    if (counts.mapped()) {
+        counts.queueDone();
+        if (!counts.wait()) return PFAC_STATUS_INTERNAL_ERROR;
+        for (int k = 0; k < 4; k++) v[k] = __atomic_load_n(const_cast<const unsigned int *>(counts.h_value) + k, __ATOMIC_ACQUIRE);
+    } else {
+        const unsigned int *const from[4] = {a.lineBase + a.blocks, a.selBase + a.blocks, a.matching, a.groupBase + a.blocks};
+        if (hipGetLastError() != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+        for (int k = 0; k < 4; k++)
+            if (hipMemcpy(&v[k], from[k], sizeof(unsigned int), hipMemcpyDeviceToHost) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
+    }
+    if (v[0] > size || v[1] > v[0] || v[2] > v[1] || v[3] > v[2] || (v[1] != 0) != (v[2] != 0)) return PFAC_STATUS_INTERNAL_ERROR;
+    *h_numLines = v[0];
+    *h_numSelected = v[1];
+    *h_numMatching = v[2];
+    *h_numGroups = v[3];
     return PFAC_STATUS_SUCCESS;
 }
 

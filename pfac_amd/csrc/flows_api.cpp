@@ -38,10 +38,8 @@ struct Flow {
 };
 }
 
-struct PFACX_flows_s {
-    PFAC_context *handle = nullptr;
-    unsigned long long generation = 0;        /* PFAC_context::setGeneration when the set was opened or last reset as a whole */
-    int kind = 0;                             /* 0: not fed yet, 1: host calls, 2: device calls */
+struct PFACX_flows_s : pfac_internal::HandleObject {
+    int kind = 0;                            /* 0: not fed yet, 1: host calls, 2: device calls */
     std::vector<Flow> flows;
     std::vector<unsigned int> named;          /* per flow: the number of the last call that named it (a flow named twice) */
     unsigned int callNo = 0;
@@ -49,27 +47,16 @@ struct PFACX_flows_s {
     size_t carryStride = 0;
     int deviceM = 0;                          /* the maxPatternLen the carries were sized for */
     std::mutex lock;                          /* one call at a time per set */
+
+    void freeDevice()
+    {
+        d_carries.release();
+        deviceM = 0;
+    }
+    ~PFACX_flows_s() override { freeDevice(); }
+    size_t deviceBytes() const override { return d_carries.bytes(); }
 };
 
-namespace pfac_internal {
-
-void closeAllFlowSets(PFAC_context *c)
-{
-    for (PFACX_flows_s *s : c->flowSets) {
-        s->d_carries.release();
-        delete s;
-    }
-    c->flowSets.clear();
-}
-
-size_t flowsDeviceBytes(const PFAC_context *c)
-{
-    size_t bytes = 0;
-    for (const PFACX_flows_s *s : c->flowSets) bytes += s->d_carries.bytes();
-    return bytes;
-}
-
-} // namespace pfac_internal
 using namespace pfac_internal;
 
 namespace {
@@ -99,8 +86,7 @@ bool idsValid(PFACX_flows_s *s, const unsigned int *ids, size_t n)
 PFAC_status_t ensureCarries(PFACX_flows_s *s, size_t M)
 {
     if (M <= 1 || (s->d_carries && s->deviceM == (int)M)) return PFAC_STATUS_SUCCESS;
-    s->d_carries.release();
-    s->deviceM = 0;
+    s->freeDevice();
     const size_t stride = ((M - 1) + 15) & ~size_t(15);
     if (s->flows.size() > (SIZE_MAX - 256) / (2 * stride)) return PFAC_STATUS_ALLOC_FAILED;
     if (s->d_carries.reserve(2 * stride * s->flows.size() + 256) != PFAC_STATUS_SUCCESS) return PFAC_STATUS_ALLOC_FAILED;
@@ -215,35 +201,14 @@ PFAC_status_t PFACX_flowsOpen(PFAC_handle_t handle, size_t numFlows, PFACX_flows
     if (!flows) return PFAC_STATUS_INVALID_PARAMETER;
     *flows = nullptr;
     if (numFlows == 0 || numFlows >= (size_t)0x80000000u) return PFAC_STATUS_INVALID_PARAMETER;
-    PFACX_flows_s *s = new (std::nothrow) PFACX_flows_s();
-    if (!s) return PFAC_STATUS_ALLOC_FAILED;
-    std::lock_guard<std::mutex> guard(handle->lock);
-    if (!handle->isPatternsReady) { delete s; return PFAC_STATUS_PATTERNS_NOT_READY; }
-    try {
-        s->flows.resize(numFlows);
-        s->named.assign(numFlows, 0u);
-        handle->flowSets.push_back(s);
-    } catch (const std::bad_alloc &) { delete s; return PFAC_STATUS_ALLOC_FAILED; }
-    s->handle = handle;
-    s->generation = handle->setGeneration;
-    *flows = s;
-    return PFAC_STATUS_SUCCESS;
+    return adoptNew(handle, flows, [numFlows](PFACX_flows_s &s) {
+        s.flows.resize(numFlows);
+        s.named.assign(numFlows, 0u);
+        return PFAC_STATUS_SUCCESS;
+    });
 }
 
-PFAC_status_t PFACX_flowsClose(PFACX_flows_t flows)
-{
-    if (!flows || !flows->handle) return PFAC_STATUS_INVALID_HANDLE;
-    PFAC_context *c = flows->handle;
-    {
-        std::lock_guard<std::mutex> guard(c->lock);
-        auto it = std::find(c->flowSets.begin(), c->flowSets.end(), flows);
-        if (it == c->flowSets.end()) return PFAC_STATUS_INVALID_HANDLE;
-        c->flowSets.erase(it);
-        flows->d_carries.release();
-    }
-    delete flows;
-    return PFAC_STATUS_SUCCESS;
-}
+PFAC_status_t PFACX_flowsClose(PFACX_flows_t flows) { return closeObject(flows); }
 
 PFAC_status_t PFACX_flowsReset(PFACX_flows_t flows, const unsigned int *h_flowIds, size_t n)
 {

@@ -22,34 +22,16 @@
 
 #include "pfac_host.h"
 
-struct PFACX_groups_s {
-    PFAC_context *handle = nullptr;
-    unsigned long long generation = 0;        /* PFAC_context::setGeneration when the table was opened */
+struct PFACX_groups_s : pfac_internal::HandleObject {
     size_t numIds = 0;                        /* F of the pattern set it was opened on */
     std::vector<unsigned long long> masks;    /* [F + 1] by REPORTED id: the OR over the duplicate lines; 0 for entry 0 and for ids never reported */
     /* the same on the device, uploaded by the first device call: state of the table (deviceTableBytes), freed by PFACX_groupsClose */
     pfac::DeviceBuffer<unsigned long long> d_masks;
+
+    ~PFACX_groups_s() override { d_masks.release(); }
+    size_t deviceBytes() const override { return d_masks.bytes(); }
 };
 
-namespace pfac_internal {
-
-void closeAllGroupTables(PFAC_context *c)
-{
-    for (PFACX_groups_s *g : c->groupSets) {
-        g->d_masks.release();
-        delete g;
-    }
-    c->groupSets.clear();
-}
-
-size_t groupsDeviceBytes(const PFAC_context *c)
-{
-    size_t bytes = 0;
-    for (const PFACX_groups_s *g : c->groupSets) bytes += g->d_masks.bytes();
-    return bytes;
-}
-
-} // namespace pfac_internal
 using namespace pfac_internal;
 
 namespace {
@@ -89,13 +71,6 @@ PFAC_status_t checkMatchArgs(PFACX_groups_t groups, size_t numItems, bool itemsM
     if (itemsMissing || !h_num_matched || (capacity && (!ids || !pos)) || (!offsets && numSegments != 1) || (numSegments == 0 && numItems > 0))
         return PFAC_STATUS_INVALID_PARAMETER;
     return PFAC_STATUS_SUCCESS;
-}
-
-/* do [a, a + na) and [b, b + nb) share a byte? */
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return na != 0 && nb != 0 && x < y + nb && y < x + na;
 }
 
 /* the first device call of a group handle: its mask table (the caller holds the handle's lock) */
@@ -181,35 +156,14 @@ PFAC_status_t PFACX_groupsOpen(PFAC_handle_t handle, const unsigned long long *h
     if (!groups) return PFAC_STATUS_INVALID_PARAMETER;
     *groups = nullptr;
     if (!h_patternMasks) return PFAC_STATUS_INVALID_PARAMETER;
-    PFACX_groups_s *g = new (std::nothrow) PFACX_groups_s();
-    if (!g) return PFAC_STATUS_ALLOC_FAILED;
-    std::lock_guard<std::mutex> guard(handle->lock);
-    if (!handle->isPatternsReady) { delete g; return PFAC_STATUS_PATTERNS_NOT_READY; }
-    if (numMasks < (size_t)handle->fa.numPatterns + 1) { delete g; return PFAC_STATUS_INVALID_PARAMETER; }
-    try {
-        resolveMasks(handle->fa, h_patternMasks, g);
-        handle->groupSets.push_back(g);
-    } catch (const std::bad_alloc &) { delete g; return PFAC_STATUS_ALLOC_FAILED; }
-    g->handle = handle;
-    g->generation = handle->setGeneration;
-    *groups = g;
-    return PFAC_STATUS_SUCCESS;
+    return adoptNew(handle, groups, [=](PFACX_groups_s &g) -> PFAC_status_t {
+        if (numMasks < (size_t)handle->fa.numPatterns + 1) return PFAC_STATUS_INVALID_PARAMETER;
+        resolveMasks(handle->fa, h_patternMasks, &g);
+        return PFAC_STATUS_SUCCESS;
+    });
 }
 
-PFAC_status_t PFACX_groupsClose(PFACX_groups_t groups)
-{
-    if (!groups || !groups->handle) return PFAC_STATUS_INVALID_HANDLE;
-    PFAC_context *c = groups->handle;
-    {
-        std::lock_guard<std::mutex> guard(c->lock);
-        auto it = std::find(c->groupSets.begin(), c->groupSets.end(), groups);
-        if (it == c->groupSets.end()) return PFAC_STATUS_INVALID_HANDLE;
-        c->groupSets.erase(it);
-        groups->d_masks.release();
-    }
-    delete groups;
-    return PFAC_STATUS_SUCCESS;
-}
+PFAC_status_t PFACX_groupsClose(PFACX_groups_t groups) { return closeObject(groups); }
 
 PFAC_status_t PFACX_groupsMatchFromDevice(PFACX_groups_t groups, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
                                           const unsigned long long *d_segMasks, unsigned int flags, int *d_ids, int *d_pos, size_t capacity,

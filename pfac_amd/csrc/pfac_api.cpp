@@ -20,6 +20,7 @@
 #include <emmintrin.h>
 #endif
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -117,6 +118,33 @@ void freeResources(PFAC_context *c)
     c->filter = pfac::Filter();
     c->isPatternsReady = false;
     c->setGeneration++;                        /* the handle's streams belong to the set that has just gone (PFACX_streamReset) */
+}
+
+PFAC_status_t closeObject(HandleObject *obj)
+{
+    if (!obj || !obj->handle) return PFAC_STATUS_INVALID_HANDLE;
+    PFAC_context *c = obj->handle;
+    std::lock_guard<std::mutex> guard(c->lock);
+    const auto it = std::find(c->objects.begin(), c->objects.end(), obj);
+    if (it == c->objects.end()) return PFAC_STATUS_INVALID_HANDLE;
+    c->objects.erase(it);
+    delete obj;
+    return PFAC_STATUS_SUCCESS;
+}
+
+/* PFAC_destroy: whatever the caller has left open */
+static void closeAllObjects(PFAC_context *c)
+{
+    for (HandleObject *obj : c->objects) delete obj;
+    c->objects.clear();
+}
+
+/* PFACX_getInfo: what the open objects hold on the device (the caller holds c->lock) */
+static size_t objectsDeviceBytes(const PFAC_context *c)
+{
+    size_t bytes = 0;
+    for (const HandleObject *obj : c->objects) bytes += obj->deviceBytes();
+    return bytes;
 }
 
 
@@ -401,10 +429,7 @@ PFAC_status_t PFACX_createHostOnly(PFAC_handle_t *handle)
 PFAC_status_t PFAC_destroy(PFAC_handle_t handle)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    closeAllStreams(handle);
-    closeAllFlowSets(handle);
-    closeAllRuleSets(handle);
-    closeAllGroupTables(handle);
+    closeAllObjects(handle);
     freeResources(handle);
     /* drops this handle's reference; the module stays mapped while other handles hold theirs (dlopen refcounts) */
     if (handle->module) dlclose(handle->module);
@@ -651,9 +676,9 @@ PFAC_status_t PFACX_getInfo(PFAC_handle_t handle, PFACX_info_t *info)
         v.chainSlots = handle->h_chainSlots.size();
         v.multiProcessorCount = handle->multiProcessorCount;
         /* what the pattern set holds on the device -- the chained tables, the initial row, the prefilter bitmaps, the launch counters, the
-         * reference-layout table only while PFACX_KERNEL_REFTABLE has asked for it -- the carried bytes of device-fed streams and the tables of rule sets: state, not
-         * scratch (PFACX_trim keeps them) */
-        v.deviceTableBytes = handle->tables.bytes() + streamDeviceBytes(handle) + flowsDeviceBytes(handle) + rulesDeviceBytes(handle) + groupsDeviceBytes(handle);
+         * reference-layout table only while PFACX_KERNEL_REFTABLE has asked for it -- and what the open streams, flow sets, rule sets and group tables
+         * hold there: state, not scratch (PFACX_trim keeps them) */
+        v.deviceTableBytes = handle->tables.bytes() + objectsDeviceBytes(handle);
         /* ... and what its calls have left allocated (grow-only, PFACX_trim gives it back) */
         v.deviceScratchBytes = handle->scratch.bytes();
         if (handle->h_modeHint) {

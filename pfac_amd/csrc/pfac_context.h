@@ -471,6 +471,8 @@ struct DeviceScratch {
 
 } // namespace pfac
 
+namespace pfac_internal { struct HandleObject; }       /* pfac_host.h: the kernel module never looks inside one */
+
 struct PFAC_context {
     /* compiled pattern set */
     pfac::Automaton fa;
@@ -546,17 +548,12 @@ struct PFAC_context {
     /* per-device handles of PFACX_matchFromHostMultiGPU, created on first use: (device, handle) */
     std::vector<std::pair<int, PFAC_context *>> children;
 
-    /* streams (PFACX_stream*, stream_api.cpp): the open streams of this handle (PFAC_destroy closes them) and the number of the pattern set
-     * they were opened on: whatever replaces or drops the set (freeResources) counts it up, and a stream of an older set is refused until
-     * PFACX_streamReset.  The carried bytes of device-fed streams are state, not scratch: counted under deviceTableBytes, kept by PFACX_trim */
-    std::vector<PFACX_stream_s *> streams;
+    /* what the caller has opened on this handle and not closed yet -- streams, flow sets, rule sets, group tables (pfac_host.h: HandleObject;
+     * PFAC_destroy closes them) -- and the number of the pattern set: whatever replaces or drops the set (freeResources) counts it up, and an
+     * object opened on an older set is refused (a stream or a flow set: until its reset).  What these objects hold on the device is state, not
+     * scratch: counted under deviceTableBytes, kept by PFACX_trim */
+    std::vector<pfac_internal::HandleObject *> objects;
     unsigned long long setGeneration = 0;
-    /* flow sets (PFACX_flows*, flows_api.cpp): the open sets of this handle (PFAC_destroy closes them); their carries are state like the streams' */
-    std::vector<PFACX_flows_s *> flowSets;
-    /* rule sets (PFACX_rules*, rules_api.cpp): the open sets of this handle (PFAC_destroy closes them); their device tables are state like the carries */
-    std::vector<PFACX_rules_s *> ruleSets;
-    /* group tables (PFACX_groups*, groups_api.cpp): the open tables of this handle (PFAC_destroy closes them); their device copies are state likewise */
-    std::vector<PFACX_groups_s *> groupSets;
     void *h_flowPieces = nullptr;             /* pinned host memory a flows call builds its piece descriptors in (grow-only; freed with the scratch) */
     size_t h_flowPiecesBytes = 0;
 

@@ -116,14 +116,53 @@ inline void forEachChainMember(const pfac::Automaton &fa, int id, F f)
 }
 /* the length of pattern id, 0 for an id the set does not have */
 inline size_t patternLenOf(const pfac::Automaton &fa, int id) { return id > 0 && (size_t)id < fa.patternLen.size() ? (size_t)fa.patternLen[(size_t)id] : 0; }
-/* what the stream and the flows calls check first (the caller holds c->lock: the set cannot change between this check and the end of the call) */
+/* What a caller opens on a handle and closes again: the common head of PFACX_stream_s, PFACX_flows_s, PFACX_rules_s and PFACX_groups_s, and what
+ * PFAC_context::objects holds.  A kind's destructor is the one place that gives its device memory back, deviceBytes() what PFACX_getInfo counts
+ * of it (deviceTableBytes) */
+struct HandleObject {
+    PFAC_context *handle = nullptr;           /* the handle that holds it; null while it is being set up */
+    unsigned long long generation = 0;        /* PFAC_context::setGeneration when it was opened (a stream, a flow set: or last reset as a whole) */
+    virtual ~HandleObject() = default;
+    virtual size_t deviceBytes() const = 0;
+};
+/* What every PFACX_...Open ends with, behind its argument checks (*out is null): a new T that the handle holds, stamped with the set's generation.
+ * Under c->lock: PATTERNS_NOT_READY without a set, then setUp(T &) -- it may read c->fa, refuse with a status or throw bad_alloc.  Whatever
+ * fails, the object is gone and *out stays null */
+template <class T, class SetUp>
+PFAC_status_t adoptNew(PFAC_context *c, T **out, SetUp setUp)
+{
+    std::unique_ptr<T> obj(new (std::nothrow) T());
+    if (!obj) return PFAC_STATUS_ALLOC_FAILED;
+    std::lock_guard<std::mutex> guard(c->lock);
+    if (!c->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
+    try {
+        const PFAC_status_t st = setUp(*obj);
+        if (st != PFAC_STATUS_SUCCESS) return st;
+        c->objects.push_back(obj.get());
+    } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
+    obj->handle = c;
+    obj->generation = c->setGeneration;
+    *out = obj.release();
+    return PFAC_STATUS_SUCCESS;
+}
+/* pfac_api.cpp: every PFACX_...Close -- INVALID_HANDLE for null, for an object no handle holds, for one its handle does not hold (any more);
+ * the object is destroyed, its device memory with it, while the handle's lock is held */
+PFAC_status_t closeObject(HandleObject *obj);
+/* what the calls on such an object check first (the caller holds c->lock: the set cannot change between this check and the end of the call):
+ * the stream, flows, rules and groups calls alike */
 inline PFAC_status_t checkSetGeneration(const PFAC_context *c, unsigned long long generation)
 {
-    if (generation != c->setGeneration) return PFAC_STATUS_INVALID_PARAMETER;     /* another pattern set since: PFACX_streamReset / PFACX_flowsReset */
+    if (generation != c->setGeneration) return PFAC_STATUS_INVALID_PARAMETER;     /* another pattern set since: PFACX_streamReset / PFACX_flowsReset; a rule set or a group table is opened anew */
     if (!c->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
     return PFAC_STATUS_SUCCESS;
 }
 inline size_t up256(size_t n) { return (n + 255) & ~size_t(255); }
+/* do [a, a + na) and [b, b + nb) share a byte? */
+inline bool overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return na != 0 && nb != 0 && x < y + nb && y < x + na;
+}
 /* host_pipeline.cpp: the caller holds c->lock */
 PFAC_status_t prepareHostPath(PFAC_context *c, size_t maxBytes);
 PFAC_status_t matchDeviceLocked(PFAC_context *c, char *d_inputString, size_t size, int *d_matched_result);
@@ -166,10 +205,7 @@ inline int compactPairs(const int *results, size_t owned, int posShift, int *ids
     }
     return z;
 }
-/* stream_api.cpp: PFAC_destroy closes the handle's streams; the device bytes their carries hold (PFACX_getInfo: deviceTableBytes) */
-void closeAllStreams(PFAC_context *c);
-size_t streamDeviceBytes(const PFAC_context *c);
-/* ... and what the stream and the flows calls share (the caller holds c->lock).  streamSplitOf: how a piece of `size` bytes splits the work of a
+/* stream_api.cpp: what the stream and the flows calls share (the caller holds c->lock).  streamSplitOf: how a piece of `size` bytes splits the work of a
  * stream that carries `carried` bytes -- of the pending and the piece's positions the first seam + owned are final, `seam` of them carried.
  * hostPiece: one host-fed piece (or, size == 0 and flush: the stream's end) of a stream whose carry is carry[0, carried): the seam
  * [carry | head of the piece], in room of its own, and the piece's final positions through hostLongestPairsLocked; the pairs go to ids / pos
@@ -179,15 +215,6 @@ struct StreamSplit { size_t seam, owned; };
 StreamSplit streamSplitOf(size_t carried, size_t size, size_t M);
 PFAC_status_t hostPiece(PFAC_context *c, const unsigned char *carry, size_t carried, char *piece, size_t size, bool flush, int *ids, int *pos,
                         std::vector<unsigned char> &next, int *count);
-/* flows_api.cpp: PFAC_destroy closes the handle's flow sets; the device bytes their carries hold (PFACX_getInfo: deviceTableBytes) */
-void closeAllFlowSets(PFAC_context *c);
-size_t flowsDeviceBytes(const PFAC_context *c);
-/* rules_api.cpp: PFAC_destroy closes the handle's rule sets; the device bytes their tables hold (PFACX_getInfo: deviceTableBytes) */
-void closeAllRuleSets(PFAC_context *c);
-size_t rulesDeviceBytes(const PFAC_context *c);
-/* groups_api.cpp: PFAC_destroy closes the handle's group tables; the device bytes their mask tables hold (PFACX_getInfo: deviceTableBytes) */
-void closeAllGroupTables(PFAC_context *c);
-size_t groupsDeviceBytes(const PFAC_context *c);
 /* batch_api.cpp: offsets[0] == 0, offsets[n] == size, never decreasing */
 bool batchOffsetsValid(const size_t *offsets, size_t numSegments, size_t size);
 /* batch_api.cpp: the batch calls (PFACX_matchBatch*) behind their argument checks; the caller holds c->lock */

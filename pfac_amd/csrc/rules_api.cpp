@@ -26,9 +26,7 @@
 
 #include "pfac_host.h"
 
-struct PFACX_rules_s {
-    PFAC_context *handle = nullptr;
-    unsigned long long generation = 0;        /* PFAC_context::setGeneration when the set was opened */
+struct PFACX_rules_s : pfac_internal::HandleObject {
     size_t numRules = 0;
     size_t numIds = 0;                        /* F of the pattern set it was opened on */
     std::vector<int> memberOff;               /* [F + 2] */
@@ -43,28 +41,10 @@ struct PFACX_rules_s {
 
     bool conditioned() const { return !memberCond.empty(); }
     void releaseDevice() { d_memberOff.release(); d_member.release(); d_need.release(); d_memberCond.release(); }
-    size_t deviceBytes() const { return d_memberOff.bytes() + d_member.bytes() + d_need.bytes() + d_memberCond.bytes(); }
+    ~PFACX_rules_s() override { releaseDevice(); }
+    size_t deviceBytes() const override { return d_memberOff.bytes() + d_member.bytes() + d_need.bytes() + d_memberCond.bytes(); }
 };
 
-namespace pfac_internal {
-
-void closeAllRuleSets(PFAC_context *c)
-{
-    for (PFACX_rules_s *s : c->ruleSets) {
-        s->releaseDevice();
-        delete s;
-    }
-    c->ruleSets.clear();
-}
-
-size_t rulesDeviceBytes(const PFAC_context *c)
-{
-    size_t bytes = 0;
-    for (const PFACX_rules_s *s : c->ruleSets) bytes += s->deviceBytes();
-    return bytes;
-}
-
-} // namespace pfac_internal
 using namespace pfac_internal;
 
 namespace {
@@ -230,18 +210,9 @@ template <typename MemberAt>
 PFAC_status_t openRules(PFAC_handle_t handle, const int *h_ruleOff, MemberAt memberAt, size_t numRules, bool conditioned, PFACX_rules_t *rules)
 {
     if (numRules == 0 || numRules >= kMaxRules) return PFAC_STATUS_INVALID_PARAMETER;
-    PFACX_rules_s *s = new (std::nothrow) PFACX_rules_s();
-    if (!s) return PFAC_STATUS_ALLOC_FAILED;
-    std::lock_guard<std::mutex> guard(handle->lock);
-    if (!handle->isPatternsReady) { delete s; return PFAC_STATUS_PATTERNS_NOT_READY; }
-    try {
-        if (!invertRules(handle->fa, h_ruleOff, memberAt, numRules, conditioned, s)) { delete s; return PFAC_STATUS_INVALID_PARAMETER; }
-        handle->ruleSets.push_back(s);
-    } catch (const std::bad_alloc &) { delete s; return PFAC_STATUS_ALLOC_FAILED; }
-    s->handle = handle;
-    s->generation = handle->setGeneration;
-    *rules = s;
-    return PFAC_STATUS_SUCCESS;
+    return adoptNew(handle, rules, [&](PFACX_rules_s &s) {
+        return invertRules(handle->fa, h_ruleOff, memberAt, numRules, conditioned, &s) ? PFAC_STATUS_SUCCESS : PFAC_STATUS_INVALID_PARAMETER;
+    });
 }
 
 } // namespace
@@ -266,20 +237,7 @@ PFAC_status_t PFACX_rulesOpenEx(PFAC_handle_t handle, const int *h_ruleOff, cons
     return openRules(handle, h_ruleOff, [=](size_t j) { return h_members[j]; }, numRules, true, rules);
 }
 
-PFAC_status_t PFACX_rulesClose(PFACX_rules_t rules)
-{
-    if (!rules || !rules->handle) return PFAC_STATUS_INVALID_HANDLE;
-    PFAC_context *c = rules->handle;
-    {
-        std::lock_guard<std::mutex> guard(c->lock);
-        auto it = std::find(c->ruleSets.begin(), c->ruleSets.end(), rules);
-        if (it == c->ruleSets.end()) return PFAC_STATUS_INVALID_HANDLE;
-        c->ruleSets.erase(it);
-        rules->releaseDevice();
-    }
-    delete rules;
-    return PFAC_STATUS_SUCCESS;
-}
+PFAC_status_t PFACX_rulesClose(PFACX_rules_t rules) { return closeObject(rules); }
 
 PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
                                          int *d_firedSeg, int *d_firedRule, size_t capacity, size_t *d_segFirst, size_t *h_numFired)

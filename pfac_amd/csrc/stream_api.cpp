@@ -24,10 +24,8 @@
 
 #include "pfac_host.h"
 
-struct PFACX_stream_s {
-    PFAC_context *handle = nullptr;
-    unsigned long long generation = 0;        /* PFAC_context::setGeneration when the stream was opened or last reset */
-    int kind = 0;                             /* 0: not fed yet, 1: host calls, 2: device calls */
+struct PFACX_stream_s : pfac_internal::HandleObject {
+    int kind = 0;                            /* 0: not fed yet, 1: host calls, 2: device calls */
     unsigned long long total = 0;             /* T: bytes seen */
     size_t carried = 0;                       /* min(M - 1, T): the pending positions are the carried ones */
     std::vector<unsigned char> h_carry;       /* host-fed */
@@ -37,32 +35,18 @@ struct PFACX_stream_s {
     int deviceM = 0;                          /* the maxPatternLen the block was sized for */
     int cur = 0;
     std::mutex lock;                          /* one call at a time per stream */
+
+    void freeDevice()
+    {
+        d_block.release();
+        d_carry[0] = d_carry[1] = d_stage = nullptr;
+        deviceM = 0;
+    }
+    ~PFACX_stream_s() override { freeDevice(); }
+    size_t deviceBytes() const override { return d_block.bytes(); }
 };
 
 namespace pfac_internal {
-
-static void freeStreamDevice(PFACX_stream_s *s)
-{
-    s->d_block.release();
-    s->d_carry[0] = s->d_carry[1] = s->d_stage = nullptr;
-    s->deviceM = 0;
-}
-
-void closeAllStreams(PFAC_context *c)
-{
-    for (PFACX_stream_s *s : c->streams) {
-        freeStreamDevice(s);
-        delete s;
-    }
-    c->streams.clear();
-}
-
-size_t streamDeviceBytes(const PFAC_context *c)
-{
-    size_t bytes = 0;
-    for (const PFACX_stream_s *s : c->streams) bytes += s->d_block.bytes();
-    return bytes;
-}
 
 static void forget(PFACX_stream_s *s)
 {
@@ -77,7 +61,7 @@ static void forget(PFACX_stream_s *s)
 static PFAC_status_t ensureStreamDevice(PFACX_stream_s *s, int M)
 {
     if (s->d_block && s->deviceM == M) return PFAC_STATUS_SUCCESS;
-    freeStreamDevice(s);
+    s->freeDevice();
     const size_t one = up256((size_t)M - 1);
     const size_t seam = 2 * ((size_t)M - 1);
     const size_t stage = seam > pfac::kStreamSeamLdsBytes ? up256(seam) : 0;
@@ -144,15 +128,7 @@ PFAC_status_t PFACX_streamOpen(PFAC_handle_t handle, PFACX_stream_t *stream)
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
     if (!stream) return PFAC_STATUS_INVALID_PARAMETER;
     *stream = nullptr;
-    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
-    PFACX_stream_s *s = new (std::nothrow) PFACX_stream_s();
-    if (!s) return PFAC_STATUS_ALLOC_FAILED;
-    std::lock_guard<std::mutex> guard(handle->lock);
-    s->handle = handle;
-    s->generation = handle->setGeneration;
-    try { handle->streams.push_back(s); } catch (const std::bad_alloc &) { delete s; return PFAC_STATUS_ALLOC_FAILED; }
-    *stream = s;
-    return PFAC_STATUS_SUCCESS;
+    return adoptNew(handle, stream, [](PFACX_stream_s &) { return PFAC_STATUS_SUCCESS; });
 }
 
 PFAC_status_t PFACX_streamReset(PFACX_stream_t stream)
@@ -165,20 +141,7 @@ PFAC_status_t PFACX_streamReset(PFACX_stream_t stream)
     return PFAC_STATUS_SUCCESS;
 }
 
-PFAC_status_t PFACX_streamClose(PFACX_stream_t stream)
-{
-    if (!stream || !stream->handle) return PFAC_STATUS_INVALID_HANDLE;
-    PFAC_context *c = stream->handle;
-    {
-        std::lock_guard<std::mutex> guard(c->lock);
-        auto it = std::find(c->streams.begin(), c->streams.end(), stream);
-        if (it == c->streams.end()) return PFAC_STATUS_INVALID_HANDLE;
-        c->streams.erase(it);
-        freeStreamDevice(stream);
-    }
-    delete stream;
-    return PFAC_STATUS_SUCCESS;
-}
+PFAC_status_t PFACX_streamClose(PFACX_stream_t stream) { return closeObject(stream); }
 
 PFAC_status_t PFACX_streamMatchFromDevice(PFACX_stream_t stream, char *d_piece, size_t size, int *d_ids, int *d_pos, size_t capacity,
                                           int *h_num_matched, unsigned long long *h_pieceOffset)

@@ -29,13 +29,6 @@ static PFAC_status_t checkWordsArgs(PFAC_handle_t handle, const void *input, siz
     return st == PFAC_STATUS_SUCCESS && ((flags & ~PFACX_WORDS_ALL) || size > kMaxInt) ? PFAC_STATUS_INVALID_PARAMETER : st;
 }
 
-/* do [a, a + na) and [b, b + nb) share a byte? */
-static bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return na != 0 && nb != 0 && x < y + nb && y < x + na;
-}
-
 /* the boundary passes over `count` ordered longest pairs, behind the argument checks; the caller holds c->lock */
 static PFAC_status_t wordsRunLocked(PFAC_context *c, const char *d_input, size_t size, const unsigned int *h_class, unsigned int flags,
                                     const int *d_pairIds, const int *d_pairPos, size_t count, int *d_ids, int *d_pos, size_t capacity,

@@ -2,7 +2,9 @@
 
 PFACX_matchAllFromHost, countFromHost, matchWordsFromHost (both modes), matchSpansFromHost, matchDisjointFromHost and matchLinesFromHost take their
 longest pairs from hostLongestPairs and then read handle->fa; PFACX_replaceFromHost reads the pattern lengths.  Between the scan and that post-pass
-nothing but the set's generation ties the pairs to the set: the post-pass holds a SetPin (pfac_amd/csrc/pfac_host.h).  tools/tsan_host_forms.cpp is
+nothing but the set's generation ties the pairs to the set: the post-pass holds a SetPin (pfac_amd/csrc/pfac_host.h).  A stream and a flow set are
+opened, fed from the host in two pieces, flushed and closed inside one form each, so that every PFACX_...Open and ...Close (adoptNew and closeObject
+of pfac_host.h) races with the thread that replaces the set too.  tools/tsan_host_forms.cpp is
 a stand-alone program built with -fsanitize=thread against pfac_amd/lib/tsan/libpfac.so: four threads call every form on one host-only handle
 while a fifth cycles PFACX_readPatternFromMemory through three sets -- two with the same number of patterns and other chains and lengths, one with
 more.  It exits non-zero on a sanitizer report, on a call that ends in anything but the documented refusal or the single-threaded answer of ONE of

@@ -1,9 +1,10 @@
 /* tools/tsan_host_forms.cpp -- the host forms that scan and then read the compiled set (PFACX_matchAllFromHost, countFromHost, matchWordsFromHost in
  * both modes, matchSpansFromHost, matchDisjointFromHost, matchLinesFromHost), PFACX_replaceFromHost and the batch host forms over the input cut at
- * its newlines (PFACX_countBatchFromHost, rulesMatchFromHost, groupsMatchFromHost), under ThreadSanitizer (`make -C pfac_amd/csrc tsan`): four
+ * its newlines (PFACX_countBatchFromHost, rulesMatchFromHost, groupsMatchFromHost), and a stream and a flow set opened, fed from the host in two
+ * pieces, flushed and closed within one call, under ThreadSanitizer (`make -C pfac_amd/csrc tsan`): four
  * threads call them on one host-only handle while a fifth replaces its pattern set, cycling through three sets.  A and B have the same number of
  * patterns -- A with chains of prefixes, B with none, and other lengths per id --, C has more.  Every call must end in the documented refusal
- * (PATTERNS_NOT_READY; INVALID_PARAMETER for a rule set or a group table opened on a set that has been replaced: the thread opens a new one) or in
+ * (PATTERNS_NOT_READY; INVALID_PARAMETER for a rule set, a group table, a stream or a flow set opened on a set that has been replaced: the thread opens a new one) or in
  * success with the single-threaded answer of one of the sets, a mixture of two sets never; and every form must have given every set's answer at
  * least once, so that a library that refuses everything does not pass.  CPU only.   tsan_host_forms [rounds] [pause in microseconds] */
 #include <atomic>
@@ -19,8 +20,8 @@
 
 namespace {
 
-enum Form { kAll, kCount, kWordsList, kWordsAll, kSpans, kDisjoint, kLines, kReplace, kCountBatch, kRules, kGroups, kForms };
-const char *const kFormName[kForms] = {"matchAll", "count", "words", "words(all)", "spans", "disjoint", "lines", "replace", "countBatch", "rules", "groups"};
+enum Form { kAll, kCount, kWordsList, kWordsAll, kSpans, kDisjoint, kLines, kReplace, kCountBatch, kRules, kGroups, kStream, kFlows, kForms };
+const char *const kFormName[kForms] = {"matchAll", "count", "words", "words(all)", "spans", "disjoint", "lines", "replace", "countBatch", "rules", "groups", "stream", "flows"};
 
 const std::string kSets[3] = {
     "a\nab\nabc\nabcd\nhe\nhers\n",                          /* A: chains a < ab < abc < abcd, he < hers */
@@ -38,6 +39,7 @@ struct Fixture {
     std::string replBytes;
     std::vector<size_t> offsets;                             /* the batch forms: the first kBatchSegments lines, a segment each (a call short enough to end between two swaps) */
     std::vector<unsigned long long> segMasks;
+    size_t pieces[3] = {0, 0, 0};                            /* the stream and the flows forms: the same lines in two pieces, cut inside an occurrence */
 };
 
 /* the rule set and the group table of the batch forms; every id is one that all three sets have.  Rules: pattern 1; 2 and 5; 3 within the first 8
@@ -63,6 +65,49 @@ struct Scratch {
         table = nullptr;
     }
 };
+
+/* The stream and the flows form open their object, feed x.pieces from the host, flush and close, all inside the one call: the open and the close
+ * race with the thread that replaces the set as well.  The pairs of every step go to w.a / w.b one behind the other, *listed = their number; a close
+ * that does not succeed is no documented outcome.  The stream: two piece calls and the flush, positions made relative to the stream's start */
+PFAC_status_t streamForm(const Fixture &x, Scratch &w, size_t *listed)
+{
+    PFACX_stream_t s = nullptr;
+    PFAC_status_t st = PFACX_streamOpen(x.h, &s);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    size_t at = 0;
+    for (int k = 0; k < 3 && st == PFAC_STATUS_SUCCESS; k++) {
+        int n = 0;
+        unsigned long long base = x.pieces[2];               /* the flush: relative to the stream's end */
+        if (k < 2)
+            st = PFACX_streamMatchFromHost(s, const_cast<char *>(x.input.data()) + x.pieces[k], x.pieces[k + 1] - x.pieces[k], w.a.data() + at, w.b.data() + at,
+                                           w.a.size() - at, &n, &base);
+        else
+            st = PFACX_streamFlush(s, w.a.data() + at, w.b.data() + at, w.a.size() - at, &n);
+        if (st != PFAC_STATUS_SUCCESS) break;
+        for (int i = 0; i < n; i++) w.b[at + (size_t)i] += (int)base;
+        at += (size_t)n;
+    }
+    if (PFACX_streamClose(s) != PFAC_STATUS_SUCCESS) return PFAC_STATUS_INTERNAL_ERROR;
+    *listed = at;
+    return st;
+}
+
+/* ... a set of two flows: one call with a piece for each, then the flush of both; *r = pieceFirst of the call, then `first` of the flush */
+PFAC_status_t flowsForm(const Fixture &x, Scratch &w, size_t *listed, std::vector<long long> *r)
+{
+    PFACX_flows_t fl = nullptr;
+    PFAC_status_t st = PFACX_flowsOpen(x.h, 2, &fl);
+    if (st != PFAC_STATUS_SUCCESS) return st;
+    const unsigned int flowIds[2] = {0, 1};
+    int first[6] = {0, 0, 0, 0, 0, 0}, n = 0, m = 0;
+    unsigned long long pieceOffsets[2] = {0, 0};
+    st = PFACX_flowsMatchFromHost(fl, const_cast<char *>(x.input.data()), x.pieces[2], x.pieces, flowIds, 2, w.a.data(), w.b.data(), w.a.size(), first, pieceOffsets, &n);
+    if (st == PFAC_STATUS_SUCCESS) st = PFACX_flowsFlush(fl, flowIds, 2, w.a.data() + n, w.b.data() + n, w.a.size() - (size_t)n, first + 3, &m);
+    if (PFACX_flowsClose(fl) != PFAC_STATUS_SUCCESS) return PFAC_STATUS_INTERNAL_ERROR;
+    if (st == PFAC_STATUS_SUCCESS) r->assign(first, first + 6);
+    *listed = (size_t)n + (size_t)m;
+    return st;
+}
 
 /* one call of form f: its status, and on success everything it wrote as one list of numbers.  false: a canary behind counts[] has changed */
 bool call(Form f, const Fixture &x, Scratch &w, PFAC_status_t *status, std::vector<long long> *result)
@@ -122,6 +167,8 @@ bool call(Form f, const Fixture &x, Scratch &w, PFAC_status_t *status, std::vect
             r.insert(r.end(), w.groups.begin(), w.groups.end());
         }
         break;
+    case kStream: st = streamForm(x, w, &listed); u = listed; break;
+    case kFlows: st = flowsForm(x, w, &listed, &r); u = listed; break;
     default: break;
     }
     *status = st;
@@ -154,6 +201,8 @@ int main(int argc, char **argv)
     for (size_t i = 0; i < x.input.size() && x.offsets.size() <= kBatchSegments; i++)
         if (x.input[i] == '\n') x.offsets.push_back(i + 1);
     for (size_t k = 0; k + 1 < x.offsets.size(); k++) x.segMasks.push_back((k * 11 + 1) & 63);
+    x.pieces[1] = x.offsets[8] + 2;                          /* inside the abcd that line 8 begins with: ab | cd */
+    x.pieces[2] = x.offsets.back();
     for (size_t id = 0; id <= kNumC + 1; id++) {             /* the string of id: <id>; ids 0 and F + 1 have offsets and no string of their own */
         x.replOff.push_back((int)x.replBytes.size());
         if (id >= 1 && id <= kNumC) x.replBytes += "<" + std::to_string(id) + ">";
@@ -199,7 +248,7 @@ int main(int argc, char **argv)
                 PFAC_status_t st;
                 if (!call(f, x, w, &st, &got)) { wrong++; fprintf(stderr, "%s: canary overwritten\n", kFormName[f]); continue; }
                 if (st == PFAC_STATUS_PATTERNS_NOT_READY) { refused[f]++; continue; }
-                if (st == PFAC_STATUS_INVALID_PARAMETER && (f == kRules || f == kGroups)) { refused[f]++; continue; }
+                if (st == PFAC_STATUS_INVALID_PARAMETER && (f == kRules || f == kGroups || f == kStream || f == kFlows)) { refused[f]++; continue; }
                 int set = -1;
                 if (st == PFAC_STATUS_INVALID_PARAMETER && f == kCount) set = 2;
                 for (int k = 0; k < 3 && st == PFAC_STATUS_SUCCESS; k++)

@@ -731,16 +731,53 @@ PFAC_status_t PFACX_replaceFromHost  (PFAC_handle_t handle, const char *h_input,
  * MEMORY: a conditioned set adds 8 bytes per member after resolution to its device tables: 4 (F + 2) + 4 I + 4 R + 8 I bytes, four allocations; a
  * set opened by PFACX_rulesOpen allocates nothing new.  A device call of a conditioned set stages the pattern lengths (4 (F + 1) bytes of handle
  * scratch) also when d_offsets is NULL.  The host form of a conditioned set keeps 8 bytes per input byte instead of 4.
- * OUT OF SCOPE: distance / within (conditions between the positions of two members), rules of negated members only, minimum counts, more than 32
- * members, rules over streams or flows. */
+ * OUT OF SCOPE: rules of negated members only, minimum counts, more than 32 members, rules over streams or flows (distance / within: below).
+ *
+ * ORDERED RULE MEMBERS (PFACX_rulesOpenSeq): members that also carry Snort's relative modifiers -- "B starts at least `distance` bytes
+ * behind the end of A and ends within `within` bytes of it": `timeout` within 40 bytes after `payment-service`; `User-Agent:` and then `sqlmap`.
+ * Rule r is the members h_members[h_ruleOff[r], h_ruleOff[r + 1]) of type PFACX_rule_seq_member_t; PFACX_rule_member_t is unchanged.  The result is
+ * an ordinary PFACX_rules_t: the match calls, PFACX_rulesClose, the fired list, segFirst, capacity, truncation, the count query, offsets (host
+ * offsets validated, device offsets clamped), the generation check, PFAC_destroy, PFACX_trim, the lock and the caseless fold are exactly as above.
+ *   An occurrence and a member's own window {flags & PFACX_RULE_FROM_END, offset, depth} are exactly those of PFACX_rulesOpenEx: a proper prefix of
+ *   the longest pattern at a position counts, the occurrence lies wholly inside the segment.
+ *   A member with PFACX_RULE_RELATIVE is tied to the member immediately in front of it in the rule, its predecessor.  A maximal run "member without
+ *   PFACX_RULE_RELATIVE, then PFACX_RULE_RELATIVE members" is a CHAIN m_0 .. m_c.  The chain HOLDS if there are occurrences o_0 .. o_c such that o_j
+ *   is an occurrence of m_j's pattern that satisfies m_j's own window and, for every j >= 1, with e = start(o_j-1) + len(o_j-1): start(o_j) >= e +
+ *   distance_j and (within_j == 0 or start(o_j) + len(o_j) <= e + within_j) -- evaluated without wrap-around (distance = 0xFFFFFFFF satisfies
+ *   nothing).  Any such assignment will do: existence, what Snort's backtracking search decides; never a greedy first or last occurrence.  distance
+ *   is unsigned, so two neighbouring members of a chain never share a byte.  {PFACX_RULE_RELATIVE, distance 0, within 0}: somewhere behind its
+ *   predecessor, not overlapping it; within == len(B) with distance 0: adjacent; within < len(B): never.
+ *   The rule FIRES on a segment if every chain holds and every member outside a chain -- positive or PFACX_RULE_NOT, without PFACX_RULE_RELATIVE --
+ *   holds as under PFACX_rulesOpenEx.  Chains are independent of each other: two chains may use the same occurrence.
+ *   A rule that contains a PFACX_RULE_RELATIVE member keeps its members in the order given and nothing is merged (ids are resolved to the reported
+ *   id, as everywhere); 32 members at most.  A rule without one is treated exactly as PFACX_rulesOpenEx treats it, merging of equal members included.
+ * PFAC_STATUS_INVALID_PARAMETER: everything PFACX_rulesOpenEx refuses, a flag bit other than the three below, PFACX_RULE_RELATIVE on the first member
+ * of a rule, together with PFACX_RULE_NOT, or behind a PFACX_RULE_NOT member, distance or within non-zero on a member without PFACX_RULE_RELATIVE.
+ * A set without any PFACX_RULE_RELATIVE member gives the list of PFACX_rulesOpenEx over the same members on every input, from the same kernels.
+ * The device form verifies a rule whose members all passed their own tests (a CANDIDATE) in the block that owns the segment, from the pairs'
+ * positions and the pattern lengths: no input byte is read, device offsets are clamped exactly as for a conditioned set.  The host form verifies
+ * it by a loop over the segment's occurrences.  Both are exact.
+ * MEMORY: a set with a chain adds, with K links (the members of all chains), 4 (R + 1) + 20 K bytes in two allocations to its device tables (state:
+ * deviceTableBytes, kept by PFACX_trim, freed by PFACX_rulesClose); a device call of such a set adds 8 bytes per pair of the scan -- two arrays of 4
+ * bytes per pair, each rounded up to 256 -- to the handle's grow-only rules scratch (deviceScratchBytes, freed by PFACX_trim).  A set without a
+ * chain adds neither.
+ * COST: the conditioned passes, plus, in both passes, for every candidate with chains one walk over the pairs of its segment per link:
+ * candidates x links x pairs of the segment.  A rule whose first member is common and whose segments are huge (one segment of many MiB) is what this
+ * is not for: give such a rule a rare member outside the chain, or cut the input into records.
+ * OUT OF SCOPE: negative distance, negated relative members, relative to a member other than the one in front, isdataat and byte tests, minimum
+ * counts, rules over streams or flows, a report of where the chain matched. */
 #define PFACX_RULE_NOT      1u   /* the member holds if NO occurrence satisfies its window (content:!"...") */
 #define PFACX_RULE_FROM_END 2u   /* the window is measured from the segment's end instead of its start */
+#define PFACX_RULE_RELATIVE 4u   /* PFACX_rulesOpenSeq: distance / within tie the member to the one in front of it */
 typedef struct { int pattern; unsigned int flags, offset, depth; } PFACX_rule_member_t;   /* depth 0: no upper bound */
+typedef struct { int pattern; unsigned int flags, offset, depth, distance, within; } PFACX_rule_seq_member_t;  /* within 0: no upper bound */
 typedef struct PFACX_rules_s *PFACX_rules_t;
 PFAC_status_t PFACX_rulesOpen (PFAC_handle_t handle, const int *h_ruleOff /* numRules + 1 */, const int *h_rulePatterns,
                                size_t numRules, PFACX_rules_t *rules);
 PFAC_status_t PFACX_rulesOpenEx(PFAC_handle_t handle, const int *h_ruleOff /* numRules + 1 */, const PFACX_rule_member_t *h_members,
                                 size_t numRules, PFACX_rules_t *rules);
+PFAC_status_t PFACX_rulesOpenSeq(PFAC_handle_t handle, const int *h_ruleOff /* numRules + 1 */, const PFACX_rule_seq_member_t *h_members,
+                                 size_t numRules, PFACX_rules_t *rules);
 PFAC_status_t PFACX_rulesClose(PFACX_rules_t rules);
 PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
                                          int *d_firedSeg, int *d_firedRule, size_t capacity, size_t *d_segFirst /* numSegments + 1, may be NULL */,

@@ -217,7 +217,12 @@ PFAC_status_t PFACX_replaceRun(PFAC_handle_t handle, const char *d_input, size_t
  * its end offset + depth saturated to 2^31 - 1 (no upper bound: 2^31 - 1), bit 31 PFACX_RULE_FROM_END -- and with it d_pairPos[0, count), the pairs'
  * positions in the buffer, d_patternLen (the pattern lengths by id, numIds + 1 entries), `size` and d_offsets (numSegments + 1 size_t, clamped to
  * [0, size] where read; null: one segment [0, size)).  A membership's bit is set only by an occurrence that lies inside its segment and satisfies the
- * window; d_need holds the positive bits only.  d_memberCond == null: a plain set, none of the five is read. */
+ * window; d_need holds the positive bits only.  d_memberCond == null: a plain set, none of the five is read.
+ * A set WITH CHAINS (PFACX_rulesOpenSeq with a PFACX_RULE_RELATIVE member; conditioned as well) gives d_seqOff[numRules + 1] and d_seqLink, five
+ * words per link: the links of rule r at d_seqLink[5 d_seqOff[r], 5 d_seqOff[r + 1]), chain by chain in rule order, as {pattern id | bit 31 on the
+ * first link of a chain, lo, hi as in d_memberCond, distance, within (0: no upper bound)}.  A rule with mask == need and links fires only if every
+ * chain holds; the call then takes 2 x round256(4 count) bytes more of the handle's rules scratch for its two frontier arrays.  Both null: no rule
+ * has a chain, and the launches are those of a conditioned set. */
 typedef struct {
     const int *d_pairIds;
     size_t count;
@@ -236,6 +241,8 @@ typedef struct {
     size_t size;
     const int *d_patternLen;
     const unsigned int *d_memberCond;
+    const int *d_seqOff;
+    const unsigned int *d_seqLink;
 } PFACX_rulesRun_t;
 PFAC_status_t PFACX_rulesRun(PFAC_handle_t handle, const PFACX_rulesRun_t *run, size_t *h_total);
 

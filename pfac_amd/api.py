@@ -41,6 +41,8 @@ PFACX_RULES_TOUCHED = 1024                      # scan_rules.hip: kRulesTouched,
 PFACX_RULE_NOT = 1                              # PFACX_rule_member_t.flags: the member holds if NO occurrence satisfies its window
 PFACX_RULE_FROM_END = 2                         # the window is measured from the segment's end
 RULE_MEMBER_FIELDS = [("pattern", "<i4"), ("flags", "<u4"), ("offset", "<u4"), ("depth", "<u4")]     # PFACX_rule_member_t as a numpy structured dtype: rule_member_dtype()
+PFACX_RULE_RELATIVE = 4                         # PFACX_rule_seq_member_t.flags: distance / within tie the member to the one in front of it (PFACX_rulesOpenSeq)
+RULE_SEQ_MEMBER_FIELDS = RULE_MEMBER_FIELDS + [("distance", "<u4"), ("within", "<u4")]                # PFACX_rule_seq_member_t: rule_seq_member_dtype()
 PFACX_RULES_BLOCK_PAIRS = 256                   # scan_rules.hip: kRulesBlockPairs, the pairs a block takes from a segment in one go
 PFACX_SEGCOUNT_WINDOW = 8192                    # scan_segcount.hip: kSegWindow, the pattern ids whose counters a block keeps in LDS at a time
 PFACX_SEGCOUNT_TOUCHED = 1024                   # scan_segcount.hip: kSegTouched, the touched-list length; a segment that touches more ids of a window sweeps the whole window
@@ -130,7 +132,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_matchSpansFromDevice", "PFACX_matchSpansFromHost", "PFACX_redactSpansFromDevice",
     "PFACX_countFromDevice", "PFACX_countFromHost", "PFACX_countPairsFromDevice", "PFACX_countNonzeroFromDevice",
     "PFACX_matchDisjointFromDevice", "PFACX_matchDisjointFromHost", "PFACX_replaceFromDevice", "PFACX_replaceFromHost",
-    "PFACX_rulesOpen", "PFACX_rulesOpenEx", "PFACX_rulesClose", "PFACX_rulesMatchFromDevice", "PFACX_rulesMatchFromHost",
+    "PFACX_rulesOpen", "PFACX_rulesOpenEx", "PFACX_rulesOpenSeq", "PFACX_rulesClose", "PFACX_rulesMatchFromDevice", "PFACX_rulesMatchFromHost",
     "PFACX_matchWordsFromDevice", "PFACX_matchWordsFromHost", "PFACX_wordsPairsFromDevice",
     "PFACX_countBatchFromDevice", "PFACX_countBatchFromHost", "PFACX_countBatchPairsFromDevice",
     "PFACX_groupsOpen", "PFACX_groupsClose", "PFACX_groupsMatchFromDevice", "PFACX_groupsMatchFromHost", "PFACX_groupsPairsFromDevice",
@@ -267,6 +269,8 @@ def load_library() -> C.CDLL:
         lib.PFACX_rulesOpen.argtypes = [H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         if hasattr(lib, "PFACX_rulesOpenEx"):
             lib.PFACX_rulesOpenEx.argtypes = [H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        if hasattr(lib, "PFACX_rulesOpenSeq"):
+            lib.PFACX_rulesOpenSeq.argtypes = [H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         lib.PFACX_rulesClose.argtypes = [C.c_void_p]
         rules = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, SZ]
         lib.PFACX_rulesMatchFromDevice.argtypes = rules
@@ -855,6 +859,23 @@ class PFAC:
         self._ret(st, "PFACX_rulesOpenEx", check)
         return Rules(self, s, max(0, off.size - 1), st)
 
+    def rulesOpenSeq(self, rule_off, members, check: bool = True) -> "Rules":
+        """``PFACX_rulesOpenSeq`` -> a :class:`Rules` set whose members also carry ``distance`` / ``within`` relative to the member in front
+        (``PFACX_RULE_RELATIVE``): rule r is ``members[rule_off[r]:rule_off[r + 1]]``, an array of :func:`rule_seq_member_dtype` (or a sequence
+        of ``(pattern, flags, offset, depth, distance, within)`` tuples); the arrays are copied."""
+        import numpy as np
+        off = np.ascontiguousarray(rule_off, dtype=np.int32)
+        if not isinstance(members, np.ndarray):
+            members = [tuple(m) for m in members]
+        mem = np.ascontiguousarray(np.asarray(members, dtype=rule_seq_member_dtype()))
+        buf = mem if mem.size else np.zeros(1, dtype=rule_seq_member_dtype())
+        s = C.c_void_p()
+        st = self._lib.PFACX_rulesOpenSeq(self._h, off.ctypes.data if off.size else None, buf.ctypes.data, max(0, off.size - 1), C.byref(s))
+        self._ret(st, "PFACX_rulesOpenSeq", check)
+        return Rules(self, s, max(0, off.size - 1), st)
+
+    rules_open_seq = rulesOpenSeq
+
     # -- pattern groups: each segment sees only its own patterns (include/pfac_ext.h: PFACX_groups*) ----------------
     def groupsOpen(self, pattern_masks, check: bool = True) -> "Groups":
         """``PFACX_groupsOpen`` -> a :class:`Groups` table of this handle (``.status`` holds the call's status): ``pattern_masks[id]`` is the
@@ -1168,6 +1189,13 @@ def rule_member_dtype():
     """``PFACX_rule_member_t`` as a numpy structured dtype: pattern (int32), flags, offset, depth (uint32); 16 bytes, no padding."""
     import numpy as np
     return np.dtype(RULE_MEMBER_FIELDS)
+
+
+def rule_seq_member_dtype():
+    """``PFACX_rule_seq_member_t`` as a numpy structured dtype: pattern (int32), flags, offset, depth, distance, within (uint32); 24 bytes, no
+    padding."""
+    import numpy as np
+    return np.dtype(RULE_SEQ_MEMBER_FIELDS)
 
 
 class Rules:

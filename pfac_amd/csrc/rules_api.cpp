@@ -14,6 +14,13 @@
  * holds each membership's window.  PFACX_rulesOpen is its unconditioned case and leaves memberCond empty: a plain set, which runs what it always has.
  * For a conditioned set both forms keep the pairs' positions and OR a membership's bit only where the pattern on the chain, by itself, lies inside
  * the segment and satisfies the window (windowHolds here, pfac_rules_pass<EMIT, true> on the device); no input byte is read for it.
+ *
+ * PFACX_rulesOpenSeq is the same open over members that also carry {distance, within}.  A rule with a PFACX_RULE_RELATIVE member keeps
+ * its members in the order given, nothing merged: bit b is member b, a relative member sets its bit like any conditioned one, so mask == need[rule] is
+ * necessary and makes the rule a CANDIDATE.  What decides it is the rule's CHAINS -- seqOff[numRules + 1] and seqLink[], kSeqLinkWords words per link
+ * in rule order: {resolved id | kSeqFirst on a chain's first link, lo, hi as in memberCond, distance, within} -- which chainsHoldOnHost verifies
+ * link by link over the segment's occurrences, and pfac_rules_seq_pass on the device.  A set without a relative member has no seqOff and is the
+ * conditioned set PFACX_rulesOpenEx makes of the same members.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -35,14 +42,23 @@ struct PFACX_rules_s : pfac_internal::HandleObject {
     /* a conditioned set (PFACX_rulesOpenEx): {lo, hi} per membership, indexed like member[] (2 j, 2 j + 1) -- lo the window's offset, hi its end
      * offset + depth saturated to kNoEnd (no upper bound: kNoEnd), bit 31 PFACX_RULE_FROM_END.  Empty: a plain set, every occurrence sets its bit */
     std::vector<unsigned int> memberCond;
+    /* a set with chains (PFACX_rulesOpenSeq with a PFACX_RULE_RELATIVE member): the links of rule r at seqLink[kSeqLinkWords seqOff[r], kSeqLinkWords
+     * seqOff[r + 1]), chain by chain in rule order; a rule without a chain has none.  Empty: no rule has a chain */
+    std::vector<int> seqOff;
+    std::vector<unsigned int> seqLink;
     /* the same on the device, uploaded by the first device call: state of the set (deviceTableBytes), freed by PFACX_rulesClose */
     pfac::DeviceBuffer<int> d_memberOff;
-    pfac::DeviceBuffer<unsigned int> d_member, d_need, d_memberCond;
+    pfac::DeviceBuffer<unsigned int> d_member, d_need, d_memberCond, d_seqLink;
+    pfac::DeviceBuffer<int> d_seqOff;
 
     bool conditioned() const { return !memberCond.empty(); }
-    void releaseDevice() { d_memberOff.release(); d_member.release(); d_need.release(); d_memberCond.release(); }
+    bool sequenced() const { return !seqOff.empty(); }
+    void releaseDevice() { d_memberOff.release(); d_member.release(); d_need.release(); d_memberCond.release(); d_seqOff.release(); d_seqLink.release(); }
     ~PFACX_rules_s() override { releaseDevice(); }
-    size_t deviceBytes() const override { return d_memberOff.bytes() + d_member.bytes() + d_need.bytes() + d_memberCond.bytes(); }
+    size_t deviceBytes() const override
+    {
+        return d_memberOff.bytes() + d_member.bytes() + d_need.bytes() + d_memberCond.bytes() + d_seqOff.bytes() + d_seqLink.bytes();
+    }
 };
 
 using namespace pfac_internal;
@@ -53,10 +69,14 @@ constexpr size_t kMaxRules = size_t(1) << 24, kMaxRulePatterns = 32;
 
 constexpr unsigned int kNoEnd = 0x7FFFFFFFu, kFromEnd = 0x80000000u;      /* memberCond's hi: no occurrence ends behind 2^31 - 1; the direction */
 
-/* a member as the tables keep it: ordered and compared by (resolved id, flags, offset, depth) */
+constexpr size_t kSeqLinkWords = 5;                                      /* seqLink: id | kSeqFirst, lo, hi, distance, within (scan_rules.hip: kSeqLinkWords) */
+constexpr unsigned int kSeqFirst = 0x80000000u;                           /* the link opens a chain: it has no predecessor */
+
+/* a member as the tables keep it: ordered and compared by (resolved id, flags, offset, depth); distance and within are not 0 on a relative member
+ * alone, and a rule that has one is neither ordered nor compared */
 struct Member {
     int id;
-    unsigned int flags, offset, depth;
+    unsigned int flags, offset, depth, distance = 0, within = 0;
     bool operator<(const Member &o) const
     {
         if (id != o.id) return id < o.id;
@@ -76,11 +96,21 @@ inline bool windowHolds(long long s, long long len, long long n, unsigned int lo
     return a >= (long long)lo && a + len <= (long long)(hi & kNoEnd);
 }
 
-/* The rules inverted into s (the caller holds c->lock; the arguments are checked for null); memberAt(j): member j of the caller's array.
- * conditioned: windows and polarity are kept (PFACX_rulesOpenEx); else every member is {id, 0, 0, 0} and the set is plain.  false: a rule set the
- * contract refuses */
+/* {lo, hi} of memberCond for a member's own window */
+inline void condOf(const Member &m, unsigned int &lo, unsigned int &hi)
+{
+    const unsigned long long end = m.depth ? (unsigned long long)m.offset + m.depth : kNoEnd;       /* 64-bit: offset + depth does not wrap */
+    lo = m.offset;
+    hi = (unsigned int)std::min<unsigned long long>(end, kNoEnd) | ((m.flags & PFACX_RULE_FROM_END) ? kFromEnd : 0u);
+}
+
+/* The rules inverted into s (the caller holds c->lock; the arguments are checked for null); memberAt(j): member j of the caller's array as a
+ * PFACX_rule_seq_member_t.  conditioned: windows and polarity are kept (PFACX_rulesOpenEx); else every member is {id, 0, 0, 0} and the set is plain.
+ * flagBits: the flags the call knows -- with PFACX_RULE_RELATIVE among them (PFACX_rulesOpenSeq) a rule that has such a member keeps its order and
+ * gets its chains.  false: a rule set the contract refuses */
 template <typename MemberAt>
-bool invertRules(const pfac::Automaton &fa, const int *ruleOff, MemberAt memberAt, size_t numRules, bool conditioned, PFACX_rules_s *s)
+bool invertRules(const pfac::Automaton &fa, const int *ruleOff, MemberAt memberAt, size_t numRules, bool conditioned, unsigned int flagBits,
+                 PFACX_rules_s *s)
 {
     const size_t F = (size_t)fa.numPatterns;
     if (ruleOff[0] != 0) return false;
@@ -93,11 +123,17 @@ bool invertRules(const pfac::Automaton &fa, const int *ruleOff, MemberAt memberA
     std::vector<std::vector<Member>> rules(numRules);
     for (size_t r = 0; r < numRules; r++) {
         std::vector<Member> &ids = rules[r];
-        bool positive = false;
+        bool positive = false, relative = false;
         for (int j = ruleOff[r]; j < ruleOff[r + 1]; j++) {
-            const PFACX_rule_member_t given = memberAt((size_t)j);
+            const PFACX_rule_seq_member_t given = memberAt((size_t)j);
             int id = given.pattern;
-            if (id < 1 || (size_t)id > F || (given.flags & ~(PFACX_RULE_NOT | PFACX_RULE_FROM_END))) return false;
+            if (id < 1 || (size_t)id > F || (given.flags & ~flagBits)) return false;
+            if (given.flags & PFACX_RULE_RELATIVE) {        /* tied to the member in front: there is one, and both are positive */
+                if (j == ruleOff[r] || (given.flags & PFACX_RULE_NOT) || (ids.back().flags & PFACX_RULE_NOT)) return false;
+                relative = true;
+            } else if (given.distance != 0 || given.within != 0) {
+                return false;
+            }
             positive = positive || !(given.flags & PFACX_RULE_NOT);
             if (fa.chainLen[(size_t)id] <= 0) {             /* not in the trie: the lower id of duplicate lines */
                 if (reported.empty())
@@ -107,10 +143,14 @@ bool invertRules(const pfac::Automaton &fa, const int *ruleOff, MemberAt memberA
                 if (it == reported.end()) return false;
                 id = it->second;
             }
-            ids.push_back(Member{id, given.flags, given.offset, given.depth});
+            ids.push_back(Member{id, given.flags, given.offset, given.depth, given.distance, given.within});
         }
-        std::sort(ids.begin(), ids.end());
-        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        if (!relative) {                                    /* (a rule with a chain: the order given, nothing merged) */
+            std::sort(ids.begin(), ids.end());
+            ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        } else if (s->seqOff.empty()) {
+            s->seqOff.assign(numRules + 1, 0);
+        }
         if (ids.empty() || ids.size() > kMaxRulePatterns || !positive) return false;
     }
     s->memberOff.assign(F + 2, 0);
@@ -129,13 +169,20 @@ bool invertRules(const pfac::Automaton &fa, const int *ruleOff, MemberAt memberA
             const size_t j = (size_t)at[(size_t)m.id]++;
             s->member[j] = (unsigned int)(r << 5 | b);
             if (!(m.flags & PFACX_RULE_NOT)) need |= 1u << b;
-            if (conditioned) {
-                const unsigned long long end = m.depth ? (unsigned long long)m.offset + m.depth : kNoEnd;       /* 64-bit: offset + depth does not wrap */
-                s->memberCond[2 * j] = m.offset;
-                s->memberCond[2 * j + 1] = (unsigned int)std::min<unsigned long long>(end, kNoEnd) | ((m.flags & PFACX_RULE_FROM_END) ? kFromEnd : 0u);
-            }
+            if (conditioned) condOf(m, s->memberCond[2 * j], s->memberCond[2 * j + 1]);
         }
         s->need[r] = need;
+        if (s->sequenced()) {                               /* the chains: every maximal run "member, then relative members" of two members or more */
+            for (size_t b = 0; b < ids.size(); b++) {
+                const bool rel = (ids[b].flags & PFACX_RULE_RELATIVE) != 0;
+                if (!rel && !(b + 1 < ids.size() && (ids[b + 1].flags & PFACX_RULE_RELATIVE))) continue;
+                unsigned int lo, hi;
+                condOf(ids[b], lo, hi);
+                const unsigned int link[kSeqLinkWords] = {(unsigned int)ids[b].id | (rel ? 0u : kSeqFirst), lo, hi, ids[b].distance, ids[b].within};
+                s->seqLink.insert(s->seqLink.end(), link, link + kSeqLinkWords);
+            }
+            s->seqOff[r + 1] = (int)(s->seqLink.size() / kSeqLinkWords);
+        }
     }
     s->numRules = numRules;
     s->numIds = F;
@@ -152,6 +199,41 @@ PFAC_status_t checkMatchArgs(PFACX_rules_t rules, const void *input, size_t size
     return PFAC_STATUS_SUCCESS;
 }
 
+/* Do all chains of rule r hold in a segment of n bytes whose numPairs longest pairs are (ids[i], pos[i]), pos relative to the segment and ascending?
+ * Link by link: `reach` is the ascending starts of the occurrences of the link in front that satisfy their own window and, behind a chain's first
+ * link, have a reachable predecessor.  An occurrence at s of the next link is reachable iff some start p of reach has p + lenPrev + distance <= s
+ * and (within == 0 or s + len <= p + lenPrev + within): p in [low, high], which the LARGEST p <= high decides -- exact, whatever the assignment a
+ * search would have tried first.  64-bit throughout: distance = 0xFFFFFFFF makes high negative */
+bool chainsHoldOnHost(const pfac::Automaton &fa, const PFACX_rules_s &s, unsigned int r, const int *ids, const int *pos, int numPairs, long long n,
+                      std::vector<long long> &reach, std::vector<long long> &next)
+{
+    long long lenPrev = 0;
+    for (int l = s.seqOff[r]; l < s.seqOff[r + 1]; l++) {
+        const unsigned int *link = &s.seqLink[kSeqLinkWords * (size_t)l];
+        const int id = (int)(link[0] & ~kSeqFirst);
+        const bool first = (link[0] & kSeqFirst) != 0;
+        const long long len = fa.patternLen[(size_t)id], distance = link[3], within = link[4];
+        next.clear();
+        for (int i = 0; i < numPairs; i++) {
+            bool occurs = false;
+            forEachChainMember(fa, ids[i], [&](int q) { occurs = q == id; return !occurs; });
+            const long long at = pos[i];
+            if (!occurs || !windowHolds(at, len, n, link[1], link[2])) continue;
+            if (!first) {
+                const long long high = at - distance - lenPrev, low = within ? at + len - within - lenPrev : 0;
+                const auto behind = std::upper_bound(reach.begin(), reach.end(), high);
+                if (behind == reach.begin() || *(behind - 1) < low) continue;
+            }
+            next.push_back(at);
+        }
+        if (next.empty()) return false;                     /* whichever link it is: its chain does not hold */
+        if (!std::is_sorted(next.begin(), next.end())) std::sort(next.begin(), next.end());         /* (pairs that came in another order) */
+        reach.swap(next);
+        lenPrev = len;
+    }
+    return true;
+}
+
 /* The fired list of a batch whose longest pairs are known: the ids of segment k at ids[first[k], first[k] + numPairs[k]), their positions in the
  * segment at pos[] likewise (read for a conditioned set only: may be null for a plain one); segment k has first[k + 1] - first[k] bytes.  Returns
  * the full length */
@@ -160,6 +242,7 @@ size_t firedOnHost(const pfac::Automaton &fa, const PFACX_rules_s &s, const int 
 {
     std::vector<unsigned int> mask(s.numRules, 0u);
     std::vector<unsigned int> touched, fired;
+    std::vector<long long> reach, next;                     /* chainsHoldOnHost's */
     const bool cond = s.conditioned();
     size_t total = 0;
     for (size_t k = 0; k < numSegments; k++) {
@@ -180,7 +263,10 @@ size_t firedOnHost(const pfac::Automaton &fa, const PFACX_rules_s &s, const int 
             });
         }
         for (unsigned int r : touched) {
-            if (mask[r] == s.need[r]) fired.push_back(r);
+            /* (a candidate with chains: verified over the segment's pairs) */
+            if (mask[r] == s.need[r] && (!s.sequenced() || s.seqOff[r] == s.seqOff[r + 1] ||
+                                         chainsHoldOnHost(fa, s, r, ids + first[k], pos + first[k], numPairs[k], n, reach, next)))
+                fired.push_back(r);
             mask[r] = 0;
         }
         std::sort(fired.begin(), fired.end());
@@ -201,19 +287,23 @@ PFAC_status_t ensureDeviceTables(PFACX_rules_s *s)
     if (st == PFAC_STATUS_SUCCESS) st = s->d_member.upload(s->member.data(), s->member.size());
     if (st == PFAC_STATUS_SUCCESS) st = s->d_need.upload(s->need.data(), s->need.size());
     if (st == PFAC_STATUS_SUCCESS && s->conditioned()) st = s->d_memberCond.upload(s->memberCond.data(), s->memberCond.size());
+    if (st == PFAC_STATUS_SUCCESS && s->sequenced()) st = s->d_seqOff.upload(s->seqOff.data(), s->seqOff.size());
+    if (st == PFAC_STATUS_SUCCESS && s->sequenced()) st = s->d_seqLink.upload(s->seqLink.data(), s->seqLink.size());
     if (st != PFAC_STATUS_SUCCESS) s->releaseDevice();
     return st;
 }
 
-/* PFACX_rulesOpen (conditioned == false: memberAt gives {id, 0, 0, 0}) and PFACX_rulesOpenEx behind their null checks */
+/* PFACX_rulesOpen (conditioned == false: memberAt gives {id, 0, 0, 0, 0, 0}), PFACX_rulesOpenEx and PFACX_rulesOpenSeq behind their null checks */
 template <typename MemberAt>
-PFAC_status_t openRules(PFAC_handle_t handle, const int *h_ruleOff, MemberAt memberAt, size_t numRules, bool conditioned, PFACX_rules_t *rules)
+PFAC_status_t openRules(PFAC_handle_t handle, const int *h_ruleOff, MemberAt memberAt, size_t numRules, bool conditioned, unsigned int flagBits,
+                        PFACX_rules_t *rules)
 {
     if (numRules == 0 || numRules >= kMaxRules) return PFAC_STATUS_INVALID_PARAMETER;
     return adoptNew(handle, rules, [&](PFACX_rules_s &s) {
-        return invertRules(handle->fa, h_ruleOff, memberAt, numRules, conditioned, &s) ? PFAC_STATUS_SUCCESS : PFAC_STATUS_INVALID_PARAMETER;
+        return invertRules(handle->fa, h_ruleOff, memberAt, numRules, conditioned, flagBits, &s) ? PFAC_STATUS_SUCCESS : PFAC_STATUS_INVALID_PARAMETER;
     });
 }
+constexpr unsigned int kCondFlags = PFACX_RULE_NOT | PFACX_RULE_FROM_END;
 
 } // namespace
 
@@ -225,7 +315,8 @@ PFAC_status_t PFACX_rulesOpen(PFAC_handle_t handle, const int *h_ruleOff, const 
     if (!rules) return PFAC_STATUS_INVALID_PARAMETER;
     *rules = nullptr;
     if (!h_ruleOff || !h_rulePatterns) return PFAC_STATUS_INVALID_PARAMETER;
-    return openRules(handle, h_ruleOff, [=](size_t j) { return PFACX_rule_member_t{h_rulePatterns[j], 0u, 0u, 0u}; }, numRules, false, rules);
+    return openRules(handle, h_ruleOff, [=](size_t j) { return PFACX_rule_seq_member_t{h_rulePatterns[j], 0u, 0u, 0u, 0u, 0u}; }, numRules, false, 0u,
+                     rules);
 }
 
 PFAC_status_t PFACX_rulesOpenEx(PFAC_handle_t handle, const int *h_ruleOff, const PFACX_rule_member_t *h_members, size_t numRules, PFACX_rules_t *rules)
@@ -234,7 +325,22 @@ PFAC_status_t PFACX_rulesOpenEx(PFAC_handle_t handle, const int *h_ruleOff, cons
     if (!rules) return PFAC_STATUS_INVALID_PARAMETER;
     *rules = nullptr;
     if (!h_ruleOff || !h_members) return PFAC_STATUS_INVALID_PARAMETER;
-    return openRules(handle, h_ruleOff, [=](size_t j) { return h_members[j]; }, numRules, true, rules);
+    return openRules(handle, h_ruleOff,
+                     [=](size_t j) {
+                         const PFACX_rule_member_t &m = h_members[j];
+                         return PFACX_rule_seq_member_t{m.pattern, m.flags, m.offset, m.depth, 0u, 0u};
+                     },
+                     numRules, true, kCondFlags, rules);
+}
+
+PFAC_status_t PFACX_rulesOpenSeq(PFAC_handle_t handle, const int *h_ruleOff, const PFACX_rule_seq_member_t *h_members, size_t numRules,
+                                 PFACX_rules_t *rules)
+{
+    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
+    if (!rules) return PFAC_STATUS_INVALID_PARAMETER;
+    *rules = nullptr;
+    if (!h_ruleOff || !h_members) return PFAC_STATUS_INVALID_PARAMETER;
+    return openRules(handle, h_ruleOff, [=](size_t j) { return h_members[j]; }, numRules, true, kCondFlags | PFACX_RULE_RELATIVE, rules);
 }
 
 PFAC_status_t PFACX_rulesClose(PFACX_rules_t rules) { return closeObject(rules); }
@@ -282,6 +388,8 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
         run.size = size;
         run.d_patternLen = c->scratch.patternLen.get();
         run.d_memberCond = rules->d_memberCond.get();
+        run.d_seqOff = rules->d_seqOff.get();                                   /* (both null for a set without chains) */
+        run.d_seqLink = rules->d_seqLink.get();
     }
     size_t total = 0;
     st = c->rules_run_ptr(c, &run, &total);

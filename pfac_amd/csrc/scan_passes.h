@@ -541,9 +541,15 @@ constexpr unsigned int kNoWindow = 0xFFFFFFFFu;
  * in which nothing was decided for (anyMarked), ended at capacity, and emit's value is 0.  true: under its bit in the sweep, behind its emit --
  * every touched window is swept to its end in both passes.
  * Whatever path a segment takes -- touched list, overflow sweep, truncation, no pair at all -- the table, the bitmap, the touched count and
- * nextWindow are as the prologue left them when the segment ends.  EMIT: a segment with no entry below capacity is left at once */
-template <bool EMIT, unsigned int LOG2, unsigned int TOUCHED, unsigned int BLOCK, bool RESET_IN_SWEEP, class Segment, class Pair, class Decide, class Emit>
-__device__ __forceinline__ void segmentWindows(const SegmentFrame &f, unsigned int *table, Segment segment, Pair pair, Decide decide, Emit emit)
+ * nextWindow are as the prologue left them when the segment ends.  EMIT: a segment with no entry below capacity is left at once.
+ * verify (NoVerify: none, and nothing of it is compiled) is a hook between the decisions and the sweep: verify(bits, w0, first, last) is called by
+ * the whole block, behind a barrier, for a window whose bitmap `bits` is complete -- bit r: key w0 + r was decided for -- over the segment's pairs
+ * [first, last); it may clear bits, in both passes alike, and returns behind a barrier of its own.  A cleared bit is an entry that never was */
+struct NoVerify {};
+template <bool EMIT, unsigned int LOG2, unsigned int TOUCHED, unsigned int BLOCK, bool RESET_IN_SWEEP, class Segment, class Pair, class Decide, class Emit,
+          class Verify = NoVerify>
+__device__ __forceinline__ void segmentWindows(const SegmentFrame &f, unsigned int *table, Segment segment, Pair pair, Decide decide, Emit emit,
+                                               Verify verify = Verify())
 {
     constexpr unsigned int WINDOW = 1u << LOG2;
     static_assert(WINDOW / 32 == BLOCK, "the sweep gives every thread one word of the bitmap");
@@ -612,6 +618,7 @@ __device__ __forceinline__ void segmentWindows(const SegmentFrame &f, unsigned i
                 bool sweep = true;
                 if constexpr (!RESET_IN_SWEEP) sweep = words[2] != 0;               /* the same in every thread: read behind the barrier, reset behind the next */
                 if (sweep) {
+                    if constexpr (!std::is_same<Verify, NoVerify>::value) verify(bits, w0, first, last);
                     unsigned int word = bits[t];
                     bits[t] = 0;
                     unsigned int total = 0;

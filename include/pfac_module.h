@@ -63,7 +63,7 @@ PFAC_status_t PFACX_batchReduceFixup(PFAC_handle_t handle, const char *d_input, 
  * writes the ordered (id, position) pairs into the handle's all-match scratch -- one buffer, pfac::DeviceScratch::allPairs: the ids in its first
  * half, the positions in its second -- instead of into d_match_result / d_pos, which hold `input_size` entries and take only the
  * scan's unordered list; synchronous, *h_num_matched = the number of pairs.
- * PFACX_allExpand, scan_all.hip: expands `count` ordered longest pairs through d_table (pfac::Int2 {prefixPattern, chainLen} by
+ * PFACX_allExpand, scan_all.hip (its passes and launches are the expansion frame of scan_passes.h): expands `count` ordered longest pairs through d_table (pfac::Int2 {prefixPattern, chainLen} by
  * id) into d_ids / d_pos, every pattern at a position, longest first; slots >= capacity are not written; *h_total = the length
  * of the whole list.  d_segFirst (or null): numSegments + 1 size_t, entry k = d_segFirstPairs[k] (the first longest pair of
  * segment k) through the expansion.  d_table may be null when count == 0 or every chain has length 1 (then only d_segFirst is

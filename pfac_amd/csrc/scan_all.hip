@@ -8,12 +8,16 @@
  * ... -- longest first.  The longest-match scan is the unchanged compacted-output path (scan_module.hip: PFACX_allReduce, whose
  * ordering writes the ordered pairs into the handle's scratch); behind it, on the default stream:
  *   pfac_all_count       blocks own consecutive ranges of the longest pairs; each lane reads chainLen[id] (a table of 8 bytes
- *                        per id: L2 resident for any real set), the block's total goes to blockBase[block]
+ *                        per id: L2 resident for any real set), the block's total goes to blockBase[block] (scan_passes.h: expandCount)
  *   pfac_array_scan      exclusive scan of the block totals (one block; 64-bit; scan_passes.h), the grand total to mapped host memory
- *   pfac_all_scatter     the block's range again: lane prefix of the chain lengths, then each lane writes its pair and follows
- *                        prefixPattern into consecutive slots; slots >= capacity are skipped (the caller learns the full count)
+ *   pfac_all_scatter     the block's range again (expandWrite): lane prefix of the chain lengths, then each lane hands its pair and what
+ *                        follows along prefixPattern to the frame, which writes consecutive slots; slots >= capacity are skipped (the
+ *                        caller learns the full count); the batch form's pairOffset is the hook of the write pass
  *   pfac_all_seg_first   batch form: one lane per segment boundary, the expanded offset of the first longest pair of the segment
  *   pfac_host_done       writes the call's sequence number to mapped host memory (the host polls it instead of a stream sync; scan_passes.h: HostHandoff)
+ * Both passes, the capacity-checked store and the launches (expandPasses) are the expansion frame of scan_passes.h, shared with scan_words.hip
+ * and scan_groups.hip; the walk of a chain under a test of its members is forEachChainMember there (this unit keeps every member and writes a
+ * fixed number of slots per pair: pfac_all_scatter says why).
  * Writes are plain vector stores; no kernel of the other units is touched.
  */
 #if !defined(__gfx950__) && defined(__HIP_DEVICE_COMPILE__)
@@ -31,66 +35,47 @@ namespace {
 constexpr int kAllBlock = 256;
 
 struct ExpandArgs {
-    const int *pairIds;                 /* the ordered longest pairs */
-    const int *pairPos;
-    size_t count;
-    const pfac::Int2 *table;            /* [numIds + 1] {prefixPattern, chainLen} by id */
-    int numIds;
-    size_t per;                         /* longest pairs per block: a multiple of kAllBlock */
-    unsigned long long *blockBase;      /* [blocks + 1]: block totals -> their exclusive prefix; [blocks] = the grand total */
-    unsigned int blocks;
-    int *ids;                           /* the caller's arrays: capacity entries each */
-    int *pos;
-    size_t capacity;
+    ExpandFrame f;                      /* the pairs, the chain table, the block cut, the caller's arrays (scan_passes.h); `all` is not read */
     unsigned long long *pairOffset;     /* batch form: the expanded offset of every longest pair (else null) */
 };
 
 /* an id the scan cannot report (outside [1, numIds]) stands for itself alone */
-__device__ __forceinline__ unsigned int chainOf(const ExpandArgs &x, int id)
+__device__ __forceinline__ unsigned int chainOf(const ExpandFrame &f, int id)
 {
-    if (id < 1 || id > x.numIds) return 1u;
-    const int c = x.table[id].y;
+    if ((unsigned int)id - 1u >= f.numIds) return 1u;
+    const int c = f.table[id].y;
     return c > 0 ? (unsigned int)c : 1u;
 }
 
 __global__ __launch_bounds__(kAllBlock) void pfac_all_count(ExpandArgs x)
 {
-    __shared__ unsigned long long waveSum[kAllBlock / 64];
-    const size_t first = (size_t)blockIdx.x * x.per;
-    const size_t end = x.count - first < x.per ? x.count : first + x.per;
-    unsigned long long own = 0;
-    for (size_t i = first + threadIdx.x; i < end; i += kAllBlock) own += chainOf(x, x.pairIds[i]);
-    unsigned long long total = 0;
-    (void)blockExclusive<kAllBlock>(own, waveSum, total);
-    if (threadIdx.x == 0) x.blockBase[blockIdx.x] = total;
+    expandCount<kAllBlock>(x.f, [&](size_t k) -> unsigned long long { return chainOf(x.f, x.f.pairIds[k]); });
 }
 
+/* Every pair fills exactly the chainOf(id) slots that the count pass -- a lookup, not a walk -- gave it, an id outside the set its one: a
+ * fixed-count loop, not forEachChainMember, which visits nothing for such an id and may end in front of chainLen */
 __global__ __launch_bounds__(kAllBlock) void pfac_all_scatter(ExpandArgs x)
 {
-    __shared__ unsigned long long waveSum[kAllBlock / 64];
-    const size_t first = (size_t)blockIdx.x * x.per;
-    const size_t end = x.count - first < x.per ? x.count : first + x.per;
-    unsigned long long base = x.blockBase[blockIdx.x];
-    for (size_t i0 = first; i0 < end; i0 += kAllBlock) {        /* the same trip count for every thread of the block */
-        const size_t i = i0 + threadIdx.x;
-        const bool has = i < end;
-        const int id = has ? x.pairIds[i] : 0;
-        const int p = has ? x.pairPos[i] : 0;
-        const unsigned int c = has ? chainOf(x, id) : 0u;
-        unsigned long long stepTotal = 0;
-        const unsigned long long o = base + blockExclusive<kAllBlock>((unsigned long long)c, waveSum, stepTotal);
-        base += stepTotal;
-        if (!has) continue;
-        if (x.pairOffset != nullptr) x.pairOffset[i] = o;
-        int q = id;
-        for (unsigned int k = 0; k < c; k++) {
-            if (o + k < x.capacity) {
-                x.ids[o + k] = q;
-                x.pos[o + k] = p;
+    const ExpandFrame &f = x.f;
+    int id = 0;                                                 /* of the pair a thread has just valued: left to its store */
+    unsigned int c = 0;
+    expandWrite<kAllBlock>(
+        f,
+        [&](size_t k) -> unsigned long long {
+            id = f.pairIds[k];
+            c = chainOf(f, id);
+            return c;
+        },
+        [&](size_t, auto emit) {
+            int q = id;
+            for (unsigned int j = 0; j < c; j++) {
+                emit(q);
+                q = (unsigned int)q - 1u < f.numIds ? f.table[q].x : 0;
             }
-            q = q >= 1 && q <= x.numIds ? x.table[q].x : 0;
-        }
-    }
+        },
+        [&](size_t k, unsigned long long before) {
+            if (x.pairOffset != nullptr) x.pairOffset[k] = before;
+        });
 }
 
 /* segFirst[k] for k in [0, numSegments]: first[k] (the first longest pair of segment k; clamped to count) through the expansion:
@@ -109,6 +94,14 @@ __global__ __launch_bounds__(kAllBlock) void pfac_all_seg_first(const int *first
     }
 }
 
+inline void launchSegFirst(const PFAC_context *c, const int *first, size_t numSegments, size_t count, const unsigned long long *pairOffset,
+                           const unsigned long long *total, size_t *segFirst)
+{
+    const size_t lanes = numSegments + 1, b = (lanes + kAllBlock - 1) / kAllBlock;
+    const unsigned int grid = b < gridCap(c, 8) ? (unsigned int)b : gridCap(c, 8);
+    hipLaunchKernelGGL(pfac_all_seg_first, dim3(grid), dim3(kAllBlock), 0, 0, first, numSegments, count, pairOffset, total, segFirst);
+}
+
 } // namespace
 
 extern "C" {
@@ -123,47 +116,22 @@ PFAC_status_t PFACX_allExpand(PFAC_handle_t handle, const int *d_pairIds, const 
     PFAC_context *c = handle;
     if (!d_table) {                                    /* chains of length 1: the list is the longest list, only segFirst changes type */
         if (d_segFirst) {
-            const size_t lanes = numSegments + 1, b = (lanes + kAllBlock - 1) / kAllBlock;
-            const unsigned int grid = b < gridCap(c, 8) ? (unsigned int)b : gridCap(c, 8);
-            hipLaunchKernelGGL(pfac_all_seg_first, dim3(grid), dim3(kAllBlock), 0, 0, d_segFirstPairs, numSegments, count,
-                               (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, d_segFirst);
+            launchSegFirst(c, d_segFirstPairs, numSegments, count, nullptr, nullptr, d_segFirst);
             if (hipGetLastError() != hipSuccess || hipStreamSynchronize(0) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
         }
         *h_total = count;
         return PFAC_STATUS_SUCCESS;
     }
     ExpandArgs x{};
-    x.pairIds = d_pairIds;
-    x.pairPos = d_pairPos;
-    x.count = count;
-    x.table = static_cast<const pfac::Int2 *>(d_table);
-    x.numIds = c->fa.numPatterns;
-    x.ids = d_ids;
-    x.pos = d_pos;
-    x.capacity = capacity;
-    x.blocks = offsetBlocks(c, count, kAllBlock, x.per);
-    const size_t blocks = x.blocks;
+    x.f = ExpandFrame{d_pairIds, d_pairPos, count, static_cast<const pfac::Int2 *>(d_table), (unsigned int)c->fa.numPatterns, 1u, 0, nullptr,
+                      d_ids, d_pos, capacity};
     /* grow-only, half as much again where it grows: the block totals, then (batch form) the expanded offset of every longest pair */
-    const PFAC_status_t carved = carveScratch(c->scratch.all, [&](ScratchCarver &k) {
-        x.blockBase = k.take<unsigned long long>(blocks + 1);
-        x.pairOffset = d_segFirst ? k.take<unsigned long long>(count) : nullptr;
-    }, nullptr, true);
-    if (carved != PFAC_STATUS_SUCCESS) return carved;
-    const HostHandoff list(c, pfac::kHostAll);
-    if (blocks) hipLaunchKernelGGL(pfac_all_count, dim3((unsigned int)blocks), dim3(kAllBlock), 0, 0, x);
-    hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, x.blockBase, (unsigned int)blocks, x.blockBase + blocks,
-                       reinterpret_cast<unsigned long long *>(list.d_value));
-    if (blocks) hipLaunchKernelGGL(pfac_all_scatter, dim3((unsigned int)blocks), dim3(kAllBlock), 0, 0, x);
-    if (d_segFirst) {
-        const size_t lanes = numSegments + 1, b = (lanes + kAllBlock - 1) / kAllBlock;
-        const unsigned int grid = b < gridCap(c, 8) ? (unsigned int)b : gridCap(c, 8);
-        hipLaunchKernelGGL(pfac_all_seg_first, dim3(grid), dim3(kAllBlock), 0, 0, d_segFirstPairs, numSegments, count, x.pairOffset,
-                           x.blockBase + blocks, d_segFirst);
-    }
-    unsigned long long total = 0;
-    if (!list.finish(&total, x.blockBase + blocks)) return PFAC_STATUS_INTERNAL_ERROR;
-    *h_total = (size_t)total;
-    return PFAC_STATUS_SUCCESS;
+    return expandPasses(
+        c, c->scratch.all, pfac::kHostAll, x, pfac_all_count, pfac_all_scatter, kAllBlock, true, h_total,
+        [&](ScratchCarver &k) { x.pairOffset = d_segFirst ? k.take<unsigned long long>(count) : nullptr; }, true, ExpandNothing(),
+        [&](const unsigned long long *d_total) {                /* behind the passes: the segments' first entries */
+            if (d_segFirst) launchSegFirst(c, d_segFirstPairs, numSegments, count, x.pairOffset, d_total, d_segFirst);
+        });
 }
 
 } /* extern "C" */

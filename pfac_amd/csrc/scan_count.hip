@@ -179,12 +179,12 @@ __global__ __launch_bounds__(kCountThreads) void pfac_count_chain(StoreArgs a)
     for (unsigned int id = blockIdx.x * kCountThreads + threadIdx.x + 1u; id <= a.numIds; id += stride) {
         const unsigned long long own = a.hist[id];
         if (own == 0) continue;
-        const int steps = a.table[id].y;                            /* the patterns on the chain, id included: the walk ends there whatever the table says */
-        int q = a.table[id].x;
-        for (int k = 1; k < steps && q >= 1 && (unsigned int)q <= a.numIds; k++) {
-            atomicAdd(&a.counts[q], own);
-            q = a.table[q].x;
-        }
+        bool head = true;                                           /* id itself has its count from pfac_count_store: the members behind it */
+        forEachChainMember(a.table, a.numIds, (int)id, [&](int q) {
+            if (!head) atomicAdd(&a.counts[q], own);
+            head = false;
+            return true;
+        });
     }
 }
 

@@ -12,10 +12,10 @@
  *   pfac_groups_count    a thread per pair, blocks of kGroupsBlock, cut by offsetBlocks.  The pair's segment, its mask once, then the chain from the
  *                        longest pattern down through {prefix, chain length}, patMasks[q] ANDed with the mask.  The value of a pair is 0 / 1 (the
  *                        first enabled member) or 0 .. chainLen (ALL); the hit bits are ORed over the WHOLE chain in both modes.  Block totals
- *                        through offsetsBlockTotal; the lanes of a wave that share a segment combine their hit bits by shuffles (both halves of
+ *                        through expandCount (scan_passes.h); the lanes of a wave that share a segment combine their hit bits by shuffles (both halves of
  *                        the 64 bits), the last lane of each run adds them to segGroups[segment] with one 64-bit atomicOr
  *   pfac_array_scan      exclusive scan of the block totals (one block; 64-bit), the length of the list to mapped host memory
- *   pfac_groups_write    only with capacity > 0 or segFirst given: offsetsOfBlock, the chain again, (id, pos) into the slots below `capacity`, and
+ *   pfac_groups_write    only with capacity > 0 or segFirst given: expandWrite, the chain again, (id, pos) into the slots below `capacity` by the frame, and
  *                        segFirst (see below)
  *   pfac_host_done       the call's sequence number to mapped host memory (scan_passes.h: HostHandoff)
  * THE PAIR'S SEGMENT.  Pairs are ordered by segment: pair i lies in segment u(i) - 1, u(i) = the number of bounds <= i (0: in front of the first
@@ -26,8 +26,11 @@
  * writes the list offset in front of its pair to every such k, from u(i) - 1 downwards -- one entry where the segment in front of it has pairs, a
  * run of them behind empty segments.  The entries with bounds[k] == count -- the segments behind the last pair, and entry numSegments -- get the
  * length of the list from a grid-stride loop of the same launch.  Every entry has exactly one writer.
+ * THE FRAME.  The walk along the chain (forEachChainMember), both passes, the capacity-checked store and the launches (expandPasses) are the expansion
+ * frame of scan_passes.h, shared with scan_all.hip and scan_words.hip; this unit's own are the pair's segment, the test of a member (walkChain),
+ * the hit bits and segFirst (the hook of the write pass).
  * BOUNDS: an id is checked against [1, numIds] before it indexes anything; a walk ends after chainLen steps and at an id outside [1, numIds]
- * whatever the table says; a segment index is below numSegments where it indexes segMasks or segGroups; positions are copied, never used.
+ * whatever the table says (both in forEachChainMember); a segment index is below numSegments where it indexes segMasks or segGroups; positions are copied, never used.
  * SCRATCH: 8 (blocks + 1) bytes rounded up to 256, then 4 (numSegments + 1) bytes rounded up to 256 with a segment array (DeviceScratch::groups).
  * Plain C++, vector stores and 64-bit vector atomics only.
  */
@@ -49,21 +52,11 @@ constexpr unsigned int kBoundsBlock = 1024 * kBoundsPer;
 constexpr unsigned int kNoSegment = 0xFFFFFFFFu;
 
 struct GroupsArgs {
-    const int *pairIds;                 /* the ordered longest pairs */
-    const int *pairPos;
-    size_t count;
+    ExpandFrame f;                      /* the pairs, the chain table, PFACX_GROUPS_ALL, the block cut, the caller's arrays (scan_passes.h) */
     const unsigned int *bounds;         /* [numSegments + 1] ascending, inside [0, count] (pfac_groups_bounds); null: one segment of all pairs */
     unsigned int numSegments;
     const unsigned long long *segMasks; /* [numSegments], or null: all bits */
     const unsigned long long *patMasks; /* [numIds + 1] by id */
-    const pfac::Int2 *table;            /* [numIds + 1] {prefixPattern, chainLen} by id, or null: every chain is the pair itself */
-    unsigned int numIds;
-    unsigned int all;                   /* PFACX_GROUPS_ALL: every enabled member, else the longest one */
-    size_t per;                         /* pairs per block: a multiple of kGroupsBlock */
-    unsigned long long *blockBase;      /* [blocks + 1]: block totals -> their exclusive prefix; [blocks] = the length of the list */
-    int *ids;                           /* the caller's arrays: capacity entries each */
-    int *pos;
-    size_t capacity;
     unsigned long long *segFirst;       /* [numSegments + 1], or null */
     unsigned long long *segGroups;      /* [numSegments], or null (zeroed in front of the count pass) */
 };
@@ -107,8 +100,8 @@ __device__ __forceinline__ BlockSegs blockSegs(const GroupsArgs &a)
 {
     BlockSegs b{1u, 1u};                                                /* no segment array: u(i) = 1, segment 0 */
     if (a.bounds == nullptr) return b;
-    const size_t first = (size_t)blockIdx.x * a.per;
-    const size_t end = a.count - first < a.per ? a.count : first + a.per;
+    const size_t first = (size_t)blockIdx.x * a.f.per;
+    const size_t end = a.f.count - first < a.f.per ? a.f.count : first + a.f.per;
     const unsigned int iLo = (unsigned int)first, iHi = (unsigned int)(end - 1);
     b.lo = waveLowerBound(0u, a.numSegments + 1u, [&](unsigned int k) { return a.bounds[k] > iLo; });
     b.hi = waveLowerBound(b.lo, a.numSegments + 1u, [&](unsigned int k) { return a.bounds[k] > iHi; });
@@ -130,28 +123,24 @@ __device__ __forceinline__ unsigned int boundsUpTo(const GroupsArgs &a, const Bl
 /* the segment of a pair with u bounds at or in front of it */
 __device__ __forceinline__ unsigned int segmentOf(const GroupsArgs &a, unsigned int u) { return u >= 1u && u <= a.numSegments ? u - 1u : kNoSegment; }
 
-/* The enabled members of the chain of pattern id under the segment mask, longest first: emit(q, j) for the j-th that is reported (list mode: the
- * first alone); returns their number.  HITS: the whole chain is walked and `hits` takes mask & segment mask of every member, reported or not */
+/* The enabled members of the chain of pattern id under the segment mask, longest first (scan_passes.h: forEachChainMember): emit(q) for each that
+ * is reported (list mode: the first alone); returns their number.  HITS: the whole chain is walked and `hits` takes mask & segment mask of every
+ * member, reported or not */
 template <bool HITS, class Emit>
 __device__ __forceinline__ unsigned int walkChain(const GroupsArgs &a, int id, unsigned long long segMask, unsigned long long &hits, Emit emit)
 {
-    if ((unsigned int)id - 1u >= a.numIds || segMask == 0ull) return 0u;
-    int steps = a.table != nullptr ? a.table[id].y : 1;
-    if (steps < 1) steps = 1;                                   /* an id the trie does not hold stands for itself alone */
+    if (segMask == 0ull) return 0u;
     unsigned int found = 0;
-    int q = id;
-    for (int s = 0; s < steps && (unsigned int)q - 1u < a.numIds; s++) {
+    forEachChainMember(a.f.table, a.f.numIds, id, [&](int q) {
         const unsigned long long m = a.patMasks[q] & segMask;
-        if (m != 0ull) {
-            if (HITS) hits |= m;
-            if (a.all || found == 0u) {
-                emit(q, found);
-                found++;
-            }
-            if (!HITS && !a.all) break;
+        if (m == 0ull) return true;
+        if (HITS) hits |= m;
+        if (a.f.all || found == 0u) {
+            emit(q);
+            found++;
         }
-        q = a.table != nullptr ? a.table[q].x : 0;
-    }
+        return HITS || a.f.all != 0u;
+    });
     return found;
 }
 
@@ -177,12 +166,12 @@ __device__ __forceinline__ void addSegmentHits(unsigned long long *segGroups, un
 __global__ __launch_bounds__(kGroupsBlock) void pfac_groups_count(GroupsArgs a)
 {
     const BlockSegs b = blockSegs(a);
-    offsetsBlockTotal<kGroupsBlock>(a.count, a.per, a.blockBase, [&](size_t k) -> unsigned long long {
+    expandCount<kGroupsBlock>(a.f, [&](size_t k) -> unsigned long long {
         const unsigned int seg = segmentOf(a, a.bounds != nullptr ? boundsUpTo(a, b, (unsigned int)k) : 1u);
         unsigned long long hits = 0;
         unsigned int found = 0;
         if (seg != kNoSegment)
-            found = walkChain<true>(a, a.pairIds[k], a.segMasks != nullptr ? a.segMasks[seg] : ~0ull, hits, [](int, unsigned int) {});
+            found = walkChain<true>(a, a.f.pairIds[k], a.segMasks != nullptr ? a.segMasks[seg] : ~0ull, hits, [](int) {});
         if (a.segGroups != nullptr) addSegmentHits(a.segGroups, seg, hits);
         return found;
     });
@@ -191,42 +180,33 @@ __global__ __launch_bounds__(kGroupsBlock) void pfac_groups_count(GroupsArgs a)
 __global__ __launch_bounds__(kGroupsBlock) void pfac_groups_write(GroupsArgs a)
 {
     const BlockSegs b = blockSegs(a);
-    const unsigned int count = (unsigned int)a.count;
+    const unsigned int count = (unsigned int)a.f.count;
     /* the entries of segFirst that no pair owns: bounds[k] == count */
     if (a.segFirst != nullptr) {
         const unsigned int tail = a.bounds != nullptr ? waveLowerBound(0u, a.numSegments + 1u, [&](unsigned int k) { return a.bounds[k] >= count; }) : 1u;
-        const unsigned long long total = a.blockBase[gridDim.x];
+        const unsigned long long total = a.f.blockBase[gridDim.x];
         for (size_t k = (size_t)tail + (size_t)blockIdx.x * kGroupsBlock + threadIdx.x; k <= a.numSegments; k += (size_t)gridDim.x * kGroupsBlock)
             a.segFirst[k] = total;
     }
     unsigned int u = 1u;                                        /* of the pair a thread has just valued: left to its store */
     unsigned long long segMask = 0;
-    offsetsOfBlock<kGroupsBlock>(
-        a.count, a.per, a.blockBase,
+    unsigned long long unused = 0;
+    expandWrite<kGroupsBlock>(
+        a.f,
         [&](size_t k) -> unsigned long long {
             u = a.bounds != nullptr ? boundsUpTo(a, b, (unsigned int)k) : 1u;
             const unsigned int seg = segmentOf(a, u);
             segMask = seg == kNoSegment ? 0ull : (a.segMasks != nullptr ? a.segMasks[seg] : ~0ull);
-            unsigned long long unused = 0;
-            return walkChain<false>(a, a.pairIds[k], segMask, unused, [](int, unsigned int) {});
+            return walkChain<false>(a, a.f.pairIds[k], segMask, unused, [](int) {});
         },
+        [&](size_t k, auto emit) { (void)walkChain<false>(a, a.f.pairIds[k], segMask, unused, emit); },
         [&](size_t k, unsigned long long before) {
-            if (a.segFirst != nullptr) {                        /* every segment that starts at this pair */
-                if (a.bounds == nullptr) {
-                    if (k == 0) a.segFirst[0] = before;
-                } else {
-                    for (unsigned int j = u; j > 0u && a.bounds[j - 1u] == (unsigned int)k; j--) a.segFirst[j - 1u] = before;
-                }
+            if (a.segFirst == nullptr) return;                  /* every segment that starts at this pair */
+            if (a.bounds == nullptr) {
+                if (k == 0) a.segFirst[0] = before;
+            } else {
+                for (unsigned int j = u; j > 0u && a.bounds[j - 1u] == (unsigned int)k; j--) a.segFirst[j - 1u] = before;
             }
-            if (before >= a.capacity) return;
-            const int p = a.pairPos[k];
-            unsigned long long unused = 0;
-            (void)walkChain<false>(a, a.pairIds[k], segMask, unused, [&](int q, unsigned int j) {
-                if (before + j < a.capacity) {
-                    a.ids[before + j] = q;
-                    a.pos[before + j] = p;
-                }
-            });
         });
 }
 
@@ -249,42 +229,28 @@ PFAC_status_t PFACX_groupsRun(PFAC_handle_t handle, const PFACX_groupsRun_t *run
     }
     PFAC_context *c = handle;
     GroupsArgs a{};
-    a.pairIds = run->d_pairIds;
-    a.pairPos = run->d_pairPos;
-    a.count = run->count;
+    a.f = ExpandFrame{run->d_pairIds, run->d_pairPos, run->count, static_cast<const pfac::Int2 *>(run->d_table), (unsigned int)run->numIds,
+                      run->all ? 1u : 0u, 0, nullptr, run->d_ids, run->d_pos, run->capacity};
     a.numSegments = (unsigned int)run->numSegments;
     a.segMasks = run->d_segMasks;
     a.patMasks = run->d_patternMasks;
-    a.table = static_cast<const pfac::Int2 *>(run->d_table);
-    a.numIds = (unsigned int)run->numIds;
-    a.all = run->all ? 1u : 0u;
-    a.ids = run->d_ids;
-    a.pos = run->d_pos;
-    a.capacity = run->capacity;
     static_assert(sizeof(size_t) == sizeof(unsigned long long), "segFirst is written as 64-bit words");
     a.segFirst = reinterpret_cast<unsigned long long *>(run->d_segFirst);
     a.segGroups = run->d_segGroups;
-    const unsigned int blocks = offsetBlocks(c, a.count, kGroupsBlock, a.per);
     unsigned int *bounds = nullptr;
-    const PFAC_status_t carved = carveScratch(c->scratch.groups, [&](ScratchCarver &k) {
-        a.blockBase = k.take<unsigned long long>((size_t)blocks + 1);
-        if (run->d_segFirstPairs) bounds = k.take<unsigned int>(run->numSegments + 1);
-    });
-    if (carved != PFAC_STATUS_SUCCESS) return carved;
-    a.bounds = bounds;
-    if (a.segGroups && hipMemsetAsync(a.segGroups, 0, run->numSegments * sizeof(unsigned long long), nullptr) != hipSuccess) return PFAC_STATUS_INTERNAL_ERROR;
-    if (bounds)
-        hipLaunchKernelGGL(pfac_groups_bounds, dim3((a.numSegments + 1u + kBoundsBlock - 1u) / kBoundsBlock), dim3(1024), 0, 0, run->d_segFirstPairs,
-                           a.numSegments + 1u, (unsigned int)a.count, bounds);
-    const HostHandoff list(c, pfac::kHostGroups);
-    hipLaunchKernelGGL(pfac_groups_count, dim3(blocks), dim3(kGroupsBlock), 0, 0, a);
-    hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, a.blockBase, blocks, a.blockBase + blocks,
-                       reinterpret_cast<unsigned long long *>(list.d_value));
-    if (a.capacity || a.segFirst) hipLaunchKernelGGL(pfac_groups_write, dim3(blocks), dim3(kGroupsBlock), 0, 0, a);
-    unsigned long long total = 0;
-    if (!list.finish(&total, a.blockBase + blocks)) return PFAC_STATUS_INTERNAL_ERROR;
-    *h_total = (size_t)total;
-    return PFAC_STATUS_SUCCESS;
+    return expandPasses(
+        c, c->scratch.groups, pfac::kHostGroups, a, pfac_groups_count, pfac_groups_write, kGroupsBlock, a.f.capacity || a.segFirst, h_total,
+        [&](ScratchCarver &k) {
+            if (run->d_segFirstPairs) a.bounds = bounds = k.take<unsigned int>(run->numSegments + 1);
+        },
+        false,
+        [&]() {                                                 /* in front of the passes: segGroups zeroed, the bounds */
+            if (a.segGroups && hipMemsetAsync(a.segGroups, 0, run->numSegments * sizeof(unsigned long long), nullptr) != hipSuccess) return false;
+            if (bounds)
+                hipLaunchKernelGGL(pfac_groups_bounds, dim3((a.numSegments + 1u + kBoundsBlock - 1u) / kBoundsBlock), dim3(1024), 0, 0,
+                                   run->d_segFirstPairs, a.numSegments + 1u, (unsigned int)a.f.count, bounds);
+            return true;
+        });
 }
 
 } /* extern "C" */

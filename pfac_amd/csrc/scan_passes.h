@@ -9,7 +9,9 @@
  * pfac_block_scan: a block per 8192 values that folds what lies in front of them), the two passes that give items of 64-bit values their offsets
  * (offsetBlocks, offsetsBlockTotal, offsetsOfBlock), the frame and the launches of a pass that takes whole segments and works their pairs
  * through windows of an LDS table (clampFirstPair, SegmentFrame, segmentWindows, carveSegFirst, segmentWindowPasses: the rules and the
- * count-batch passes), the pairs of an ordered scan with the head, the tail and the finish kernel of a select call over them (PairArgs,
+ * count-batch passes), the walk along a pattern's prefix chain (forEachChainMember: the one such loop on the device) with the frame and the
+ * launches of a pass that expands longest pairs into the members of their chains (ExpandFrame, expandCount, expandWrite, expandPasses: the
+ * all-match, the words and the groups passes), the pairs of an ordered scan with the head, the tail and the finish kernel of a select call over them (PairArgs,
  * pairsSelectHead, pairsSelectTail, pfac_pairs_finish), the seam of a stream.  Like scan_common.h, everything is in an unnamed namespace: inline
  * device code, each unit its own copy.
  */
@@ -668,6 +670,106 @@ inline bool segmentWindowPasses(const PFAC_context *c, const Args &a, void (*cou
     if (f.capacity) hipLaunchKernelGGL(emit, dim3(grid), dim3(block), 0, 0, a);
     return d_segFirst == nullptr ||
            hipMemcpyAsync(d_segFirst, f.segFirst, ((size_t)f.numSegments + 1) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, nullptr) == hipSuccess;
+}
+
+/* ------------------------------------------------------------------ the prefix chain of a pattern; the expansion frame (scan_all.hip, scan_words.hip, scan_groups.hip) */
+
+/* pfac_host.h's forEachChainMember on the device: visit(q) for the patterns that occur where pattern id is the longest -- id, then along
+ * prefixPattern through `table` ([numIds + 1] {prefixPattern, chainLen} by id; null: every chain is the pair itself): at most
+ * max(1, chainLen[id]) of them, none for an id outside [1, numIds]; ends at such an id, or where visit returns false.  The one place where an id
+ * is checked before it indexes the table and where a walk is bounded whatever the table says: the chain walks of scan_words.hip, scan_groups.hip,
+ * scan_count.hip and scan_segcount.hip are calls of this (scan_rules.hip keeps its two loops, profiles/expand_refactor_resources.txt says why;
+ * scan_all.hip writes a fixed number of slots per pair) */
+template <class Visit>
+__device__ __forceinline__ void forEachChainMember(const pfac::Int2 *table, unsigned int numIds, int id, Visit visit)
+{
+    if ((unsigned int)id - 1u >= numIds) return;
+    int steps = table != nullptr ? table[id].y : 1;
+    if (steps < 1) steps = 1;                                   /* an id the trie does not hold stands for itself alone */
+    int q = id;
+    for (int s = 0; s < steps && (unsigned int)q - 1u < numIds; s++) {
+        if (!visit(q)) return;
+        q = table != nullptr ? table[q].x : 0;
+    }
+}
+
+/* What the arguments of an expansion start with.  An expansion turns an ordered list of longest pairs into the list of the members of their
+ * prefix chains that a unit keeps, pair by pair, each chain longest first: the count pass leaves every block's number of entries in blockBase,
+ * pfac_array_scan turns them into first entries, the write pass stores (id, position) into the slots below `capacity` */
+struct ExpandFrame {
+    const int *pairIds;                 /* the ordered longest pairs */
+    const int *pairPos;
+    size_t count;
+    const pfac::Int2 *table;            /* [numIds + 1] {prefixPattern, chainLen} by id, or null: every chain is the pair itself */
+    unsigned int numIds;
+    unsigned int all;                   /* every member that is kept, else the longest one */
+    size_t per;                         /* pairs per block: a multiple of the block size (offsetBlocks) */
+    unsigned long long *blockBase;      /* [blocks + 1]: block totals -> their exclusive prefix; [blocks] = the length of the list */
+    int *ids;                           /* the caller's arrays: capacity entries each */
+    int *pos;
+    size_t capacity;
+};
+
+/* Both passes, by blocks of BLOCK threads, a thread per pair and trip.  value(k): the number of entries of pair k.  members(k, emit): the same
+ * entries again, emit(q) for each in order; the frame gives them the slots behind the entries in front of pair k, checks every slot against the
+ * capacity and stores (q, the pair's position) -- the one pair store of an expansion.  hook(k, before), where given, runs for every pair in front
+ * of its store, whatever the capacity.  A thread runs hook and members right behind its value(k), which may leave them what it loaded */
+struct NoExpandHook { __device__ __forceinline__ void operator()(size_t, unsigned long long) const {} };
+template <unsigned int BLOCK, class Value>
+__device__ __forceinline__ void expandCount(const ExpandFrame &f, Value value) { offsetsBlockTotal<BLOCK>(f.count, f.per, f.blockBase, value); }
+template <unsigned int BLOCK, class Value, class Members, class Hook = NoExpandHook>
+__device__ __forceinline__ void expandWrite(const ExpandFrame &f, Value value, Members members, Hook hook = Hook())
+{
+    /* the pair's position: loaded with its value, in front of the block prefix, whatever the capacity (a unit's argument checks refuse pairs without positions) */
+    int p = 0;
+    const auto valued = [&](size_t k) -> unsigned long long { p = f.pairPos[k]; return value(k); };
+    offsetsOfBlock<BLOCK>(f.count, f.per, f.blockBase, valued, [&](size_t k, unsigned long long before) {
+        hook(k, before);
+        if (before >= f.capacity) return;
+        unsigned long long o = before;
+        members(k, [&](int q) {
+            if (o < f.capacity) {
+                f.ids[o] = q;
+                f.pos[o] = p;
+            }
+            o++;
+        });
+    });
+}
+
+/* The launches of an expansion, behind the unit's argument checks (a: the filled arguments, Args::f their ExpandFrame): the cut of the pairs
+ * into blocks of `block` threads, blockBase[blocks + 1] and what carve(ScratchCarver &) takes behind it out of `scratch` (halfMore: carveScratch),
+ * front() -- the unit's own launches in front of the passes; false: one failed --, the hand-off through `slot`, the count pass, the scan of the
+ * block totals, the write pass where wantWrite, behind(the device address of the total) -- the unit's own launches behind them --, the end of the
+ * call; *h_total = the length of the whole list.  A list of no pairs has no blocks: only the scan runs, over nothing */
+struct ExpandNothing {
+    void operator()(ScratchCarver &) const {}
+    bool operator()() const { return true; }
+    void operator()(const unsigned long long *) const {}
+};
+template <class Args, class Carve = ExpandNothing, class Front = ExpandNothing, class Behind = ExpandNothing>
+inline PFAC_status_t expandPasses(PFAC_context *c, pfac::DeviceBuffer<char> &scratch, pfac::HostSlot slot, Args &a, void (*count)(Args), void (*write)(Args),
+                                  unsigned int block, bool wantWrite, size_t *h_total, Carve carve = Carve(), bool halfMore = false, Front front = Front(),
+                                  Behind behind = Behind())
+{
+    ExpandFrame &f = a.f;
+    const unsigned int blocks = offsetBlocks(c, f.count, block, f.per);
+    const PFAC_status_t carved = carveScratch(scratch, [&](ScratchCarver &k) {
+        f.blockBase = k.take<unsigned long long>((size_t)blocks + 1);
+        carve(k);
+    }, nullptr, halfMore);
+    if (carved != PFAC_STATUS_SUCCESS) return carved;
+    if (!front()) return PFAC_STATUS_INTERNAL_ERROR;
+    const HostHandoff list(c, slot);
+    if (blocks) hipLaunchKernelGGL(count, dim3(blocks), dim3(block), 0, 0, a);
+    hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, f.blockBase, blocks, f.blockBase + blocks,
+                       reinterpret_cast<unsigned long long *>(list.d_value));
+    if (blocks && wantWrite) hipLaunchKernelGGL(write, dim3(blocks), dim3(block), 0, 0, a);
+    behind(f.blockBase + blocks);
+    unsigned long long total = 0;
+    if (!list.finish(&total, f.blockBase + blocks)) return PFAC_STATUS_INTERNAL_ERROR;
+    *h_total = (size_t)total;
+    return PFAC_STATUS_SUCCESS;
 }
 
 /* ------------------------------------------------------------------ the pairs of an ordered scan (scan_spans.hip, scan_disjoint.hip) */

@@ -74,14 +74,11 @@ __global__ __launch_bounds__(kSegBlockPairs) void pfac_segcount_pass(SegCountArg
     segmentWindows<EMIT, kSegWindowLog2, kSegTouched, kSegBlockPairs, true>(
         a.f, counter, [](unsigned int) {},
         [&](unsigned int i, unsigned int w0, auto touch, auto beyond) {
-            int q = a.pairIds[i];
-            if (q < 1 || (unsigned int)q > a.numIds) return;                        /* ignored, never used as an index */
-            int steps = 1;                                                          /* the patterns on the chain, q included: the walk ends there whatever the table says */
-            if constexpr (ALL) {
-                const int len = a.table[q].y;
-                steps = len > 1 ? len : 1;
-            }
-            for (int s = 0; s < steps && q >= 1 && (unsigned int)q <= a.numIds; s++) {
+            /* the patterns on the pair's chain, without ALL -- no table: it is not read -- the pair alone; an id outside [1, numIds] is ignored,
+             * never used as an index (scan_passes.h: forEachChainMember) */
+            const pfac::Int2 *table = nullptr;
+            if constexpr (ALL) table = a.table;
+            forEachChainMember(table, a.numIds, a.pairIds[i], [&](int q) {
                 const unsigned int r = (unsigned int)q - w0;                        /* (wraps for an id in front of the window: counted there) */
                 if ((unsigned int)q >= w0) {
                     if (r >= kSegWindow) {
@@ -91,8 +88,8 @@ __global__ __launch_bounds__(kSegBlockPairs) void pfac_segcount_pass(SegCountArg
                         added++;
                     }
                 }
-                if constexpr (ALL) q = a.table[q].x;
-            }
+                return true;
+            });
         },
         [](unsigned int, unsigned int) { return true; },
         [&](unsigned long long o, unsigned int, unsigned int id, unsigned int count) {

@@ -7,11 +7,13 @@
  * handle's pair scratch behind PFACX_allReduce, or a list of the caller's -- and look at the input again, at most 1 + chainLen bytes per pair:
  *   pfac_words_count     a thread per pair: in[p - 1] once, then the chain from the longest pattern down, in[p + len(q)] for each member q.  The value
  *                        of a pair is 0 / 1 in list mode (the walk stops at the first bounded member) and 0 .. chainLen in ALL mode; the block's total
- *                        goes to blockBase[block] (scan_passes.h: offsetsBlockTotal)
+ *                        goes to blockBase[block] (scan_passes.h: expandCount)
  *   pfac_array_scan      exclusive scan of the block totals (one block; 64-bit), the length of the list to mapped host memory
- *   pfac_words_write     the block's pairs again (offsetsOfBlock): each thread walks its chain once more and writes (id, p) for every bounded member into
- *                        consecutive slots; slots >= capacity are skipped (the caller learns the full length)
+ *   pfac_words_write     the block's pairs again (expandWrite): each thread walks its chain once more and hands every bounded member to the frame, which
+ *                        writes (id, p) into consecutive slots; slots >= capacity are skipped (the caller learns the full length)
  *   pfac_host_done       the call's sequence number to mapped host memory (scan_passes.h: HostHandoff)
+ * The walk along the chain (forEachChainMember), both passes, the capacity-checked store and the launches (expandPasses) are the expansion frame of
+ * scan_passes.h, shared with scan_all.hip and scan_groups.hip; this unit's own is the test of a member (walkPair).
  * The class is 256 bits; a block keeps its eight words in LDS (a kernel-argument array indexed by a lane's byte would go to scratch).  Every index
  * into the input is checked against [0, n) before the load; an id outside [1, F] is a pair that counts nothing, a chain member that does not lie
  * inside the input is not kept, and a walk ends after chainLen steps whatever the table says: a caller's list cannot make a pass read or write outside
@@ -33,21 +35,11 @@ namespace {
 constexpr unsigned int kWordsBlock = 256;
 
 struct WordsArgs {
+    ExpandFrame f;                      /* the pairs, the chain table, PFACX_WORDS_ALL, the block cut, the caller's arrays (scan_passes.h) */
     const unsigned char *in;            /* the caller's bytes: never the folded copy */
     unsigned int n;
-    const int *pairIds;                 /* the ordered longest pairs */
-    const int *pairPos;
-    size_t count;
-    const pfac::Int2 *table;            /* [numIds + 1] {prefixPattern, chainLen} by id, or null: every chain is the pair itself */
     const int *patternLen;              /* [numIds + 1] by id */
-    unsigned int numIds;
-    unsigned int all;                   /* PFACX_WORDS_ALL: every bounded member, else the longest one */
     unsigned int cls[8];                /* W: byte b is in it iff bit b & 31 of cls[b >> 5] is set */
-    size_t per;                         /* pairs per block: a multiple of kWordsBlock */
-    unsigned long long *blockBase;      /* [blocks + 1]: block totals -> their exclusive prefix; [blocks] = the length of the list */
-    int *ids;                           /* the caller's arrays: capacity entries each */
-    int *pos;
-    size_t capacity;
 };
 
 /* W into the block's LDS: constant indices into the argument, one thread */
@@ -68,27 +60,23 @@ __device__ __forceinline__ bool inClassAt(const WordsArgs &a, const unsigned int
     return (cls[b >> 5] >> (b & 31u)) & 1u;
 }
 
-/* The bounded members of pair k's chain, longest first: emit(q, j) for the j-th of them; returns their number (list mode: 0 or 1) */
+/* The bounded members of pair k's chain, longest first (scan_passes.h: forEachChainMember): emit(q) for each of them; returns their number
+ * (list mode: 0 or 1) */
 template <class Emit>
 __device__ __forceinline__ unsigned int walkPair(const WordsArgs &a, const unsigned int *cls, size_t k, Emit emit)
 {
-    const int id = a.pairIds[k], p = a.pairPos[k];
-    if ((unsigned int)id - 1u >= a.numIds || p < 0 || (unsigned int)p >= a.n) return 0u;
+    const int id = a.f.pairIds[k], p = a.f.pairPos[k];
+    if (p < 0 || (unsigned int)p >= a.n) return 0u;
     if (p > 0 && inClassAt(a, cls, (unsigned int)p - 1u)) return 0u;
-    int steps = a.table != nullptr ? a.table[id].y : 1;
-    if (steps < 1) steps = 1;                                   /* an id the trie does not hold stands for itself alone */
     const unsigned int room = a.n - (unsigned int)p;
     unsigned int found = 0;
-    int q = id;
-    for (int s = 0; s < steps && (unsigned int)q - 1u < a.numIds; s++) {
+    forEachChainMember(a.f.table, a.f.numIds, id, [&](int q) {
         const int len = a.patternLen[q];
-        if (len > 0 && (unsigned int)len <= room && !inClassAt(a, cls, (unsigned int)p + (unsigned int)len)) {
-            emit(q, found);
-            found++;
-            if (!a.all) break;
-        }
-        q = a.table != nullptr ? a.table[q].x : 0;
-    }
+        if (len <= 0 || (unsigned int)len > room || inClassAt(a, cls, (unsigned int)p + (unsigned int)len)) return true;
+        emit(q);
+        found++;
+        return a.f.all != 0u;
+    });
     return found;
 }
 
@@ -96,25 +84,16 @@ __global__ __launch_bounds__(kWordsBlock) void pfac_words_count(WordsArgs a)
 {
     __shared__ unsigned int cls[8];
     stageClass(a, cls);
-    offsetsBlockTotal<kWordsBlock>(a.count, a.per, a.blockBase, [&](size_t k) -> unsigned long long { return walkPair(a, cls, k, [](int, unsigned int) {}); });
+    expandCount<kWordsBlock>(a.f, [&](size_t k) -> unsigned long long { return walkPair(a, cls, k, [](int) {}); });
 }
 
 __global__ __launch_bounds__(kWordsBlock) void pfac_words_write(WordsArgs a)
 {
     __shared__ unsigned int cls[8];
     stageClass(a, cls);
-    offsetsOfBlock<kWordsBlock>(
-        a.count, a.per, a.blockBase, [&](size_t k) -> unsigned long long { return walkPair(a, cls, k, [](int, unsigned int) {}); },
-        [&](size_t k, unsigned long long before) {
-            if (before >= a.capacity) return;
-            const int p = a.pairPos[k];
-            (void)walkPair(a, cls, k, [&](int q, unsigned int j) {
-                if (before + j < a.capacity) {
-                    a.ids[before + j] = q;
-                    a.pos[before + j] = p;
-                }
-            });
-        });
+    expandWrite<kWordsBlock>(
+        a.f, [&](size_t k) -> unsigned long long { return walkPair(a, cls, k, [](int) {}); },
+        [&](size_t k, auto emit) { (void)walkPair(a, cls, k, emit); });
 }
 
 } // namespace
@@ -133,29 +112,11 @@ PFAC_status_t PFACX_wordsRun(PFAC_handle_t handle, const PFACX_wordsRun_t *run, 
     WordsArgs a{};
     a.in = reinterpret_cast<const unsigned char *>(run->d_input);
     a.n = (unsigned int)run->size;
-    a.pairIds = run->d_pairIds;
-    a.pairPos = run->d_pairPos;
-    a.count = run->count;
-    a.table = static_cast<const pfac::Int2 *>(run->d_table);
     a.patternLen = run->d_patternLen;
-    a.numIds = (unsigned int)run->numIds;
-    a.all = run->all ? 1u : 0u;
     for (int k = 0; k < 8; k++) a.cls[k] = run->cls[k];
-    a.ids = run->d_ids;
-    a.pos = run->d_pos;
-    a.capacity = run->capacity;
-    const unsigned int blocks = offsetBlocks(c, a.count, kWordsBlock, a.per);
-    const PFAC_status_t carved = carveScratch(c->scratch.words, [&](ScratchCarver &k) { a.blockBase = k.take<unsigned long long>((size_t)blocks + 1); });
-    if (carved != PFAC_STATUS_SUCCESS) return carved;
-    const HostHandoff list(c, pfac::kHostWordList);
-    hipLaunchKernelGGL(pfac_words_count, dim3(blocks), dim3(kWordsBlock), 0, 0, a);
-    hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, a.blockBase, blocks, a.blockBase + blocks,
-                       reinterpret_cast<unsigned long long *>(list.d_value));
-    if (a.capacity) hipLaunchKernelGGL(pfac_words_write, dim3(blocks), dim3(kWordsBlock), 0, 0, a);
-    unsigned long long total = 0;
-    if (!list.finish(&total, a.blockBase + blocks)) return PFAC_STATUS_INTERNAL_ERROR;
-    *h_total = (size_t)total;
-    return PFAC_STATUS_SUCCESS;
+    a.f = ExpandFrame{run->d_pairIds, run->d_pairPos, run->count, static_cast<const pfac::Int2 *>(run->d_table), (unsigned int)run->numIds,
+                      run->all ? 1u : 0u, 0, nullptr, run->d_ids, run->d_pos, run->capacity};
+    return expandPasses(c, c->scratch.words, pfac::kHostWordList, a, pfac_words_count, pfac_words_write, kWordsBlock, a.f.capacity != 0, h_total);
 }
 
 } /* extern "C" */

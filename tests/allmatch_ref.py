@@ -52,6 +52,27 @@ def brute_all(pats, data):
     return np.array(pos, dtype=np.int32), np.array(ids, dtype=np.int32)
 
 
+NESTED_TOKEN_PATTERNS = [b"a", b"ab", b"abc"]       # ids 1, 2, 3: the chain of "abc" is 3, 2, 1
+
+
+def nested_tokens(count):
+    """`count` tokens "abc", "ab", "a", cycling in this order, each followed by the filler byte "x": one longest pair per token (no other
+    byte starts a pattern), chains of 3, 2 and 1 alternating.  -> (data, pos, ids, start, pair_first): the input, the all-match list of
+    NESTED_TOKEN_PATTERNS over it by construction, the byte each token starts at, and the list offset of each longest pair's first
+    entry (count + 1 entries, the last one the length of the list)."""
+    k = np.arange(count, dtype=np.int64)
+    kind = k % 3
+    toklen, chain = 4 - kind, 3 - kind
+    ends = np.cumsum(toklen)
+    start = ends - toklen
+    pair_first = np.concatenate([[0], np.cumsum(chain)]).astype(np.int64)
+    data = np.frombuffer(b"abcxabxax" * (count // 3 + 1), dtype=np.uint8)[:int(ends[-1]) if count else 0].copy()
+    within = np.arange(pair_first[-1], dtype=np.int64) - np.repeat(pair_first[:-1], chain)
+    pos = np.repeat(start, chain).astype(np.int32)
+    ids = (np.repeat(chain, chain) - within).astype(np.int32)
+    return data, pos, ids, start, pair_first
+
+
 def expand_longest(pats, longest):
     """(pos, ids) of the all-match list from the longest-match result vector (oracle): at a position whose longest pattern is L,
     every shorter pattern that is a prefix of L's bytes also occurs there."""

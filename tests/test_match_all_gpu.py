@@ -1,8 +1,9 @@
 """PFACX_matchAllFromDevice / PFACX_matchAllBatchFromDevice / PFACX_matchAllFromHost (GPU platform) against all-match lists
 computed without the library's trie (tests/allmatch_ref.py): every kernel variant, walker, perf and texture mode; sizes on both sides
 of the small-call switch; guard words behind capacity; truncation; the fast path of sets without nested prefixes; batches; scratch
-reuse; the example program."""
+reuse; pair counts around the wave and the block, a capacity inside a chain, more pairs than one grid pass takes; the example program."""
 
+import hashlib
 import os
 import subprocess
 
@@ -256,6 +257,95 @@ def test_batch_equals_brute_force_per_segment(small_sets, name):
                 assert np.array_equal(seg, want_first), f"{name}/{mode_name}/{shape}: segFirst"
         finally:
             h.destroy()
+
+
+@pytest.fixture(scope="module")
+def token_handle(workdir):
+    """a, ab, abc: the input of tests/allmatch_ref.py: nested_tokens gives a known number of longest pairs with chains of 3, 2 and 1"""
+    pf = write_patterns(os.path.join(workdir, "allgpu_tokens.pat"), ref.NESTED_TOKEN_PATTERNS)
+    h = make_handle(pf, api.PFAC_TIME_DRIVEN, api.PFAC_TEXTURE_OFF, api.PFACX_KERNEL_AUTO)
+    yield h
+    h.destroy()
+
+
+def device_all_poisoned(h, data, capacity, room):
+    """matchAllFromDevice into poisoned arrays of `room` entries, of which the call may write `capacity` -> (status, count, pos, ids), whole arrays"""
+    d_in = torch.from_numpy(np.ascontiguousarray(data)).to("cuda:0")
+    d_ids = torch.full((room,), -5, dtype=torch.int32, device="cuda:0")
+    d_pos = torch.full((room,), -5, dtype=torch.int32, device="cuda:0")
+    st, cnt = h.matchAllFromDevice(d_in.data_ptr(), int(data.size), d_ids.data_ptr(), d_pos.data_ptr(), int(capacity), check=False)
+    torch.cuda.synchronize()
+    return st, cnt, d_pos.cpu().numpy(), d_ids.cpu().numpy()
+
+
+@pytest.mark.parametrize("pairs", [63, 64, 65, 255, 256, 257])
+def test_pair_counts_around_the_wave_and_the_block(token_handle, pairs):
+    """the expansion's block of 256 pairs, its waves of 64, and a capacity that cuts inside a chain"""
+    data, want_pos, want_ids, _, pair_first = ref.nested_tokens(pairs)
+    total = int(pair_first[-1])
+    st, cnt, pos, ids = device_all(token_handle, data)
+    assert st == api.STATUS.SUCCESS and cnt == total
+    check_list(pos, ids, want_pos, want_ids, f"{pairs} pairs")
+
+
+@pytest.mark.parametrize("pairs,cut_pair", [(63, None), (64, None), (65, None), (255, None), (256, None), (257, None), (258, 256), (384, 256)])
+def test_capacity_cuts_inside_a_chain(workdir, pairs, cut_pair):
+    """The call takes no capacity below the input's size, and a, ab, abc never list more entries than the input has bytes.  a, aa, aaa over
+    "aaax" tokens (and a last "a" or "aa": exactly `pairs` longest pairs) have the same chains of 3, 2, 1 and list 6 entries per 4 bytes.
+    The capacity is one entry into the chain of cut_pair -- pair 256: the first chain of the expansion's second block -- or, without one, the
+    smallest capacity >= size that is not the first entry of a pair.  The slots below it are exact, the rest stay poison, the full length
+    is returned"""
+    pats = [b"a", b"aa", b"aaa"]
+    data = np.frombuffer(b"aaax" * (pairs // 3) + b"aa"[:pairs % 3], dtype=np.uint8).copy()
+    want_pos, want_ids = ref.brute_all(pats, data)
+    total = want_pos.size
+    first_of_pair = np.concatenate([[True], want_pos[1:] != want_pos[:-1]])
+    assert int(first_of_pair.sum()) == pairs
+    if cut_pair is None:
+        cap = int(data.size)
+        while first_of_pair[cap]:
+            cap += 1
+    else:
+        cap = int(np.nonzero(first_of_pair)[0][cut_pair]) + 1
+        assert not first_of_pair[cap]
+    assert data.size <= cap < total
+    h = make_handle(write_patterns(os.path.join(workdir, "allgpu_arun3.pat"), pats), api.PFAC_TIME_DRIVEN, api.PFAC_TEXTURE_OFF, api.PFACX_KERNEL_AUTO)
+    try:
+        st, cnt, pos, ids = device_all_poisoned(h, data, cap, total + GUARD)
+    finally:
+        h.destroy()
+    assert st == api.STATUS.OUTPUT_TRUNCATED and cnt == total
+    check_list(pos[:cap], ids[:cap], want_pos[:cap], want_ids[:cap], f"{pairs} pairs, capacity {cap}")
+    assert np.all(pos[cap:] == -5) and np.all(ids[cap:] == -5), "wrote at or behind capacity"
+
+
+def test_batch_cut_at_the_block_edge_with_empty_segments(token_handle):
+    """257 pairs; segments that start at pairs 0, 255 (three times: two empty segments), 256 and end at 257: segFirst against the
+    offsets of the constructed list"""
+    data, want_pos, want_ids, start, pair_first = ref.nested_tokens(257)
+    first_pairs = [0, 255, 255, 255, 256]
+    offs = np.array([int(start[k]) for k in first_pairs] + [data.size], dtype=np.uint64)
+    st, cnt, pos, ids, seg = device_all_batch(token_handle, data, offs)
+    assert st == api.STATUS.SUCCESS and cnt == want_pos.size
+    check_list(pos, ids, want_pos, want_ids, "batch of 257 pairs")
+    assert np.array_equal(seg, pair_first[first_pairs + [257]]), f"segFirst {seg}"
+
+
+def test_more_pairs_than_one_grid_pass(token_handle):
+    """600 000 longest pairs: more than eight blocks per compute unit of 256 take a pair each (524 288 on 256 compute units), so a block's
+    range is 512 pairs and it makes two trips"""
+    pairs = 600000
+    data, want_pos, want_ids, _, pair_first = ref.nested_tokens(pairs)
+    total = int(pair_first[-1])
+    assert total == 1200000 and data.size == 1800000
+    st, cnt, pos, ids = device_all_poisoned(token_handle, data, data.size, data.size + GUARD)       # (the call takes no capacity below the size)
+    assert st == api.STATUS.SUCCESS and cnt == total
+    assert np.all(pos[total:] == -5) and np.all(ids[total:] == -5), "wrote behind the list"
+    pos, ids = pos[:total], ids[:total]
+    check_list(pos[:1000], ids[:1000], want_pos[:1000], want_ids[:1000], "first 1000")
+    check_list(pos[-1000:], ids[-1000:], want_pos[-1000:], want_ids[-1000:], "last 1000")
+    digest = lambda a: hashlib.sha256(np.ascontiguousarray(a, dtype=np.int32).tobytes()).hexdigest()     # noqa: E731
+    assert digest(pos) == digest(want_pos) and digest(ids) == digest(want_ids)
 
 
 def test_scratch_reuse_and_trim(nested_sets, small_sets):

@@ -17,7 +17,8 @@
  * (PFACX_countFromDevice / ...FromHost, PFACX_countPairsFromDevice,
  * PFACX_countNonzeroFromDevice) and the disjoint leftmost-longest matches
  * with their replacement by a string per pattern (PFACX_matchDisjoint*,
- * PFACX_replaceFromDevice / ...FromHost), rule sets (PFACX_rules*), the
+ * PFACX_replaceFromDevice / ...FromHost), rule sets (PFACX_rules*) and rule
+ * sets over the pieces of a flow (PFACX_flowRules*), the
  * counts of every pattern in every segment (PFACX_countBatch*), the
  * occurrences bounded by bytes outside a class: whole words, lines and
  * fields (PFACX_matchWords*, PFACX_wordsPairsFromDevice) and pattern
@@ -731,7 +732,7 @@ PFAC_status_t PFACX_replaceFromHost  (PFAC_handle_t handle, const char *h_input,
  * MEMORY: a conditioned set adds 8 bytes per member after resolution to its device tables: 4 (F + 2) + 4 I + 4 R + 8 I bytes, four allocations; a
  * set opened by PFACX_rulesOpen allocates nothing new.  A device call of a conditioned set stages the pattern lengths (4 (F + 1) bytes of handle
  * scratch) also when d_offsets is NULL.  The host form of a conditioned set keeps 8 bytes per input byte instead of 4.
- * OUT OF SCOPE: rules of negated members only, minimum counts, more than 32 members, rules over streams or flows (distance / within: below).
+ * OUT OF SCOPE: rules of negated members only, minimum counts, more than 32 members, conditioned members over streams or flows (plain rule sets over flows: PFACX_flowRules*; distance / within: below).
  *
  * ORDERED RULE MEMBERS (PFACX_rulesOpenSeq): members that also carry Snort's relative modifiers -- "B starts at least `distance` bytes
  * behind the end of A and ends within `within` bytes of it": `timeout` within 40 bytes after `payment-service`; `User-Agent:` and then `sqlmap`.
@@ -765,7 +766,7 @@ PFAC_status_t PFACX_replaceFromHost  (PFAC_handle_t handle, const char *h_input,
  * candidates x links x pairs of the segment.  A rule whose first member is common and whose segments are huge (one segment of many MiB) is what this
  * is not for: give such a rule a rare member outside the chain, or cut the input into records.
  * OUT OF SCOPE: negative distance, negated relative members, relative to a member other than the one in front, isdataat and byte tests, minimum
- * counts, rules over streams or flows, a report of where the chain matched. */
+ * counts, ordered members over streams or flows (plain rule sets over flows: PFACX_flowRules*), a report of where the chain matched. */
 #define PFACX_RULE_NOT      1u   /* the member holds if NO occurrence satisfies its window (content:!"...") */
 #define PFACX_RULE_FROM_END 2u   /* the window is measured from the segment's end instead of its start */
 #define PFACX_RULE_RELATIVE 4u   /* PFACX_rulesOpenSeq: distance / within tie the member to the one in front of it */
@@ -785,6 +786,66 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
 PFAC_status_t PFACX_rulesMatchFromHost  (PFACX_rules_t rules, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments,
                                          int *h_firedSeg, int *h_firedRule, size_t capacity, size_t *h_segFirst /* may be NULL */,
                                          size_t *h_numFired);
+
+/* Flow-rule sets: rules whose patterns arrive in different pieces of a flow -- `User-Agent:` in one packet, `sqlmap` three batches later.  PFACX_flows*
+ * reports every occurrence of every flow exactly once however the flow was cut; PFACX_rules* says which segments of ONE buffer hold every pattern of
+ * a rule.  This is what joins them: per-flow state that outlives a call, and the decision "complete now, not before", on the device behind the
+ * flows call, without a copy of the pairs to the host.
+ *   A FLOW-RULE SET is R plain rules over the handle's current pattern set -- h_ruleOff / h_rulePatterns exactly as PFACX_rulesOpen takes, validates
+ *   and resolves them (1 to 32 distinct patterns a rule after resolution of duplicate lines, 0 < numRules < 2^24) -- plus the state of numFlows
+ *   flows, 0 < numFlows < 2^31, all empty at open.
+ *   THE CALLS TAKE PAIRS, NOT BYTES: what PFACX_flowsMatchFromDevice / ...FromHost just returned -- `ids`, `pieceFirst`, the call's h_flowIds and
+ *   *h_num_matched as numPairs -- or what PFACX_flowsFlush returned: `ids`, `first` and the flows named.  No position is read.  The set is
+ *   independent of the PFACX_flows_t: the caller uses the same flow indices and mirrors a flow's flush or reset with PFACX_flowRulesReset.  A single
+ *   stream is a flow set of one flow.
+ *   Pattern id HAS OCCURRED in flow f if some pair fed for f since its last reset carries that id on its prefix chain (PFACX_TABLE_PREFIX_PATTERN;
+ *   the pair's own id included): a proper prefix of the longest pattern at a position counts.
+ *   Rule r FIRES on piece k (flow f = h_flowIds[k]) in the call after whose pairs every pattern of r has occurred in f for the first time.  Each
+ *   (flow, rule) fires once until the flow is reset; two members that arrive in the same call fire the rule once; pairs that only repeat what was
+ *   seen fire nothing.  Over one stream fed completely, flush included, the rules fired over all calls are exactly the fired list of
+ *   PFACX_rulesMatchFromHost over the stream as one segment.
+ * THE FIRED LIST: the pairs (piece, rule) = (firedPiece[i], firedRule[i]) in ascending piece order, ascending rule order within a piece.
+ * pieceFiredFirst (numPieces + 1 size_t, may be NULL): the rules fired on piece k are entries [pieceFiredFirst[k], pieceFiredFirst[k + 1]).
+ * `capacity` (entries of each array) is free; with capacity == 0 the two arrays may be null: the count query.
+ * STATE CHANGES ONLY ON SUCCESS.  A list longer than capacity: exactly its first `capacity` pairs are written and nothing behind them, *h_numFired is
+ * the full count, pieceFiredFirst is complete, the call returns PFACX_STATUS_OUTPUT_TRUNCATED -- and NO FLOW'S STATE CHANGES: repeat the call with
+ * larger arrays and get the whole list.  Any status but PFAC_STATUS_SUCCESS leaves every flow unchanged.  Feeding the same pairs twice is harmless:
+ * the second list is empty.
+ * Host arrays are validated completely: every h_flowIds[k] < numFlows, no flow twice in one call, and for the host form pieceFirst[0] == 0,
+ * pieceFirst[numPieces] == numPairs, never decreasing.  Device arrays are the caller's contract: a pieceFirst entry is clamped to [0, numPairs], a
+ * decreasing pair is an empty piece, an id outside [1, F] is skipped (in both forms) -- wrong device arrays give a wrong list, never an access outside
+ * the buffers.  The pair arrays are never written.  PFAC_STATUS_INVALID_PARAMETER: a null pointer other than those named above (d_pairIds may be
+ * null with numPairs == 0), numPairs or numPieces >= 2^31, numFlows == 0 or >= 2^31, numPieces == 0 with numPairs > 0.  numPieces == 0 with
+ * numPairs == 0: success, nothing fired, nothing written.  The device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.  Without a pattern
+ * set: PFAC_STATUS_PATTERNS_NOT_READY.
+ * PFACX_flowRulesReset empties the n named flows (ids below numFlows), or, with (NULL, 0), all flows.  A set is fed by one kind of call, host or
+ * device, until a reset of all flows (the other kind: PFAC_STATUS_INVALID_PARAMETER), as flow sets are.  After the handle reads or loads another
+ * pattern set the ids mean something else: every call returns PFAC_STATUS_INVALID_PARAMETER and only PFACX_flowRulesClose works, as for rule sets.
+ * Calls take the handle's lock and the set's own and are synchronous.  Any number of sets per handle; PFAC_destroy closes them.  A caseless handle
+ * needs nothing special: the ids are those of the folded set.  The host form is a loop over the host arrays on every platform.
+ * MEMORY, with F patterns, I ids in all rules after resolution, and D distinct ids among them: a flow holds a bitmap of D bits, ceil(D / 32) 32-bit
+ * words.  A device-fed set makes, on its first device call, ONE allocation of numFlows x 4 x ceil(D / 32) bytes for the bitmaps and five for its
+ * tables -- 4 (F + 2) + 4 I bytes for the rule set inverted by pattern, 4 (R + 1) for the first member of each rule (its full mask follows from
+ * their number), 4 I for the forward list rule -> bits and 4 (F + 1) for the table pattern -> bit: 4 (F + 2) + 8 I + 4 (R + 1) + 4 (F + 1) bytes.  All
+ * of it is state: counted under deviceTableBytes of PFACX_getInfo, kept by PFACX_trim, freed by PFACX_flowRulesClose.  What a device call stages is
+ * grow-only handle scratch, deviceScratchBytes, given back by PFACX_trim: 4 numPieces bytes for the flow ids and 8 (numPieces + 1) for the fired
+ * counts and their scan, each rounded up to 256, and the {prefix, chain length} table (8 (F + 1) bytes) it shares with other calls.  A host-fed set
+ * keeps the same bitmaps in host memory.  Nothing is sized by flows x rules or pieces x rules.
+ * COST: two passes over the pairs whose work follows the pairs times the memberships of the patterns on their prefix chains, at most
+ * 32 bit tests per rule a piece touches, and one pass that sets bits.
+ * OUT OF SCOPE: conditioned and ordered members over flows (PFACX_rulesOpenEx / PFACX_rulesOpenSeq members), a report of which call supplied which
+ * member, device-resident flow ids, changing rules without reopening. */
+typedef struct PFACX_flowRules_s *PFACX_flowRules_t;
+PFAC_status_t PFACX_flowRulesOpen(PFAC_handle_t handle, const int *h_ruleOff /* numRules + 1 */, const int *h_rulePatterns, size_t numRules,
+                                  size_t numFlows, PFACX_flowRules_t *fr);
+PFAC_status_t PFACX_flowRulesClose(PFACX_flowRules_t fr);
+PFAC_status_t PFACX_flowRulesReset(PFACX_flowRules_t fr, const unsigned int *h_flowIds, size_t n);   /* NULL, 0: all flows */
+PFAC_status_t PFACX_flowRulesPairsFromDevice(PFACX_flowRules_t fr, const int *d_pairIds, size_t numPairs, const int *d_pieceFirst /* numPieces + 1 */,
+                                             const unsigned int *h_flowIds, size_t numPieces, int *d_firedPiece, int *d_firedRule, size_t capacity,
+                                             size_t *d_pieceFiredFirst /* numPieces + 1, may be NULL */, size_t *h_numFired);
+PFAC_status_t PFACX_flowRulesPairsFromHost  (PFACX_flowRules_t fr, const int *h_pairIds, size_t numPairs, const int *h_pieceFirst /* numPieces + 1 */,
+                                             const unsigned int *h_flowIds, size_t numPieces, int *h_firedPiece, int *h_firedRule, size_t capacity,
+                                             size_t *h_pieceFiredFirst /* may be NULL */, size_t *h_numFired);
 
 /* Per-segment counts: how often each pattern occurred in each segment of a batch -- the term-document matrix of a corpus, the keyword feature vector
  * of each log line or packet, grep -c per keyword per file -- as a sparse matrix in CSR form.  It is the join of PFACX_count* (how often, over one

@@ -322,6 +322,44 @@ typedef struct {
 } PFACX_groupsRun_t;
 PFAC_status_t PFACX_groupsRun(PFAC_handle_t handle, const PFACX_groupsRun_t *run, size_t *h_total);
 
+/* Flow-rule sets (no reference counterpart; include/pfac_ext.h: PFACX_flowRules*), scan_flowrules.hip.
+ * PFACX_flowRulesRun: the fired (piece, rule) list of one flows call from its LONGEST pairs, against the patterns each flow has seen so far.
+ * d_pairIds[0, count), count < 2^31: the ids of a flows call or flush (the caller's array, never written; an id outside [1, numIds] ignored);
+ * d_pieceFirst (numPieces + 1 ints: the first pair of each piece, clamped to [0, count] where read, a decreasing pair an empty piece);
+ * h_flowIds[numPieces], HOST memory: the flow of each piece, every one below numFlows and no two equal (the caller has validated them; the call
+ * uploads them into its scratch).
+ * d_table: pfac::Int2 {prefixPattern, chainLen} by id, numIds + 1 entries.  The set: d_memberOff[numIds + 2] and d_member (rule << 5 | bit,
+ * ascending rule) as PFACX_rulesRun takes them; d_ruleFirst[numRules + 1]: rule r has d_ruleFirst[r + 1] - d_ruleFirst[r] members, 1 to 32, its
+ * full mask that many low bits, and member b of it is bit d_ruleBits[d_ruleFirst[r] + b] of a flow's bitmap; d_bitOf[numIds + 1]: the bit of
+ * pattern id in a flow's bitmap, -1 for a pattern no rule names; d_flowBits: numFlows x wordsPerFlow words, flow f at d_flowBits + f *
+ * wordsPerFlow, bit set: the pattern has occurred in the flow.  0 < numRules < 2^24.
+ * Rule r fires on piece k iff the piece's pairs complete it: (old | new) == full mask and old != full mask, old from the flow's bitmap.  Output:
+ * the pairs in ascending (piece, rule) order into d_firedPiece / d_firedRule, nothing at or beyond `capacity` (0: both may be null);
+ * d_pieceFiredFirst (numPieces + 1 size_t, or null) indexes the whole list; *h_total = its full length.  Only where *h_total <= capacity does
+ * the call then OR the bits of the pieces' pairs into their flows' bitmaps (pfac_flowrules_commit): a longer list leaves d_flowBits as it was.
+ * 0 < numPieces < 2^31.  Synchronous. */
+typedef struct {
+    const int *d_pairIds;
+    size_t count;
+    const int *d_pieceFirst;
+    const unsigned int *h_flowIds;
+    size_t numPieces;
+    const void *d_table;
+    size_t numIds;
+    const int *d_memberOff;
+    const unsigned int *d_member;
+    const int *d_ruleFirst;
+    const unsigned int *d_ruleBits;
+    const int *d_bitOf;
+    size_t numRules;
+    unsigned int *d_flowBits;
+    size_t numFlows, wordsPerFlow;
+    int *d_firedPiece, *d_firedRule;
+    size_t capacity;
+    size_t *d_pieceFiredFirst;
+} PFACX_flowRulesRun_t;
+PFAC_status_t PFACX_flowRulesRun(PFAC_handle_t handle, const PFACX_flowRulesRun_t *run, size_t *h_total);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -336,7 +374,7 @@ PFAC_status_t PFACX_groupsRun(PFAC_handle_t handle, const PFACX_groupsRun_t *run
     X(count_pairs_ptr, PFACX_countPairs) X(count_nonzero_ptr, PFACX_countNonzero) \
     X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun) \
     X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun) X(segcount_run_ptr, PFACX_segCountRun) \
-    X(groups_run_ptr, PFACX_groupsRun)
+    X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

@@ -44,6 +44,9 @@ RULE_MEMBER_FIELDS = [("pattern", "<i4"), ("flags", "<u4"), ("offset", "<u4"), (
 PFACX_RULE_RELATIVE = 4                         # PFACX_rule_seq_member_t.flags: distance / within tie the member to the one in front of it (PFACX_rulesOpenSeq)
 RULE_SEQ_MEMBER_FIELDS = RULE_MEMBER_FIELDS + [("distance", "<u4"), ("within", "<u4")]                # PFACX_rule_seq_member_t: rule_seq_member_dtype()
 PFACX_RULES_BLOCK_PAIRS = 256                   # scan_rules.hip: kRulesBlockPairs, the pairs a block takes from a segment in one go
+PFACX_FLOWRULES_WINDOW = 8192                   # scan_flowrules.hip: kFlowRulesWindow, the rules whose masks a block keeps in LDS at a time
+PFACX_FLOWRULES_TOUCHED = 1024                  # scan_flowrules.hip: kFlowRulesTouched, the touched-list length; a piece that touches more rules of a window sweeps the whole table
+PFACX_FLOWRULES_BLOCK_PAIRS = 256               # scan_flowrules.hip: kFlowRulesBlockPairs, the pairs a block takes from a piece in one go
 PFACX_SEGCOUNT_WINDOW = 8192                    # scan_segcount.hip: kSegWindow, the pattern ids whose counters a block keeps in LDS at a time
 PFACX_SEGCOUNT_TOUCHED = 1024                   # scan_segcount.hip: kSegTouched, the touched-list length; a segment that touches more ids of a window sweeps the whole window
 PFACX_SEGCOUNT_BLOCK_PAIRS = 256                # scan_segcount.hip: kSegBlockPairs, the pairs a block takes from a segment in one go
@@ -133,6 +136,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_countFromDevice", "PFACX_countFromHost", "PFACX_countPairsFromDevice", "PFACX_countNonzeroFromDevice",
     "PFACX_matchDisjointFromDevice", "PFACX_matchDisjointFromHost", "PFACX_replaceFromDevice", "PFACX_replaceFromHost",
     "PFACX_rulesOpen", "PFACX_rulesOpenEx", "PFACX_rulesOpenSeq", "PFACX_rulesClose", "PFACX_rulesMatchFromDevice", "PFACX_rulesMatchFromHost",
+    "PFACX_flowRulesOpen", "PFACX_flowRulesClose", "PFACX_flowRulesReset", "PFACX_flowRulesPairsFromDevice", "PFACX_flowRulesPairsFromHost",
     "PFACX_matchWordsFromDevice", "PFACX_matchWordsFromHost", "PFACX_wordsPairsFromDevice",
     "PFACX_countBatchFromDevice", "PFACX_countBatchFromHost", "PFACX_countBatchPairsFromDevice",
     "PFACX_groupsOpen", "PFACX_groupsClose", "PFACX_groupsMatchFromDevice", "PFACX_groupsMatchFromHost", "PFACX_groupsPairsFromDevice",
@@ -151,6 +155,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_wordsRun",
     "PFACX_segCountRun",
     "PFACX_groupsRun",
+    "PFACX_flowRulesRun",
 )
 
 
@@ -275,6 +280,14 @@ def load_library() -> C.CDLL:
         rules = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, SZ]
         lib.PFACX_rulesMatchFromDevice.argtypes = rules
         lib.PFACX_rulesMatchFromHost.argtypes = rules
+    if hasattr(lib, "PFACX_flowRulesOpen"):
+        SZ = C.POINTER(C.c_size_t)
+        lib.PFACX_flowRulesOpen.argtypes = [H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]
+        lib.PFACX_flowRulesClose.argtypes = [C.c_void_p]
+        lib.PFACX_flowRulesReset.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        pairs = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, SZ]
+        lib.PFACX_flowRulesPairsFromDevice.argtypes = pairs
+        lib.PFACX_flowRulesPairsFromHost.argtypes = pairs
     if hasattr(lib, "PFACX_matchWordsFromDevice"):
         SZ = C.POINTER(C.c_size_t)
         CLS = C.POINTER(C.c_uint)
@@ -876,6 +889,19 @@ class PFAC:
 
     rules_open_seq = rulesOpenSeq
 
+    # -- rules whose patterns arrive in different pieces of a flow (include/pfac_ext.h: PFACX_flowRules*) ----------------
+    def flowRulesOpen(self, rule_off, rule_patterns, num_flows: int, check: bool = True) -> "FlowRules":
+        """``PFACX_flowRulesOpen`` -> a :class:`FlowRules` set of ``num_flows`` flows of this handle (``.status`` holds the call's status): rule r
+        is the pattern ids ``rule_patterns[rule_off[r]:rule_off[r + 1]]``, as ``rulesOpen`` takes them; the arrays are copied."""
+        import numpy as np
+        off = np.ascontiguousarray(rule_off, dtype=np.int32)
+        pats = np.ascontiguousarray(rule_patterns, dtype=np.int32)
+        buf = pats if pats.size else np.zeros(1, dtype=np.int32)
+        s = C.c_void_p()
+        st = self._lib.PFACX_flowRulesOpen(self._h, off.ctypes.data if off.size else None, buf.ctypes.data, max(0, off.size - 1), num_flows, C.byref(s))
+        self._ret(st, "PFACX_flowRulesOpen", check)
+        return FlowRules(self, s, max(0, off.size - 1), num_flows, st)
+
     # -- pattern groups: each segment sees only its own patterns (include/pfac_ext.h: PFACX_groups*) ----------------
     def groupsOpen(self, pattern_masks, check: bool = True) -> "Groups":
         """``PFACX_groupsOpen`` -> a :class:`Groups` table of this handle (``.status`` holds the call's status): ``pattern_masks[id]`` is the
@@ -1251,3 +1277,75 @@ class Rules:
         st, n2 = self.match_host(buf.ctypes.data, data.size, optr, segments, seg.ctypes.data, rule.ctypes.data, n, first.ctypes.data)
         assert st == 0 and n2 == n
         return seg[:n].copy(), rule[:n].copy(), first
+
+
+class FlowRules:
+    """One flow-rule set (``PFACX_flowRules_t``) of a handle: the pairs of a flows call in (``ids``, ``pieceFirst``, the call's flow ids and its
+    number of pairs -- or ``ids``, ``first`` and the flows of a flush), the (piece, rule) pairs the call completes out.  Every pairs call returns
+    ``(status, full length of the list)``; OUTPUT_TRUNCATED is returned, not raised, and leaves every flow as it was."""
+
+    def __init__(self, handle: PFAC, fr: C.c_void_p, num_rules: int, num_flows: int, status: int = 0):
+        self._owner = handle
+        self._lib = handle._lib
+        self._f = fr
+        self.num_rules = num_rules
+        self.num_flows = num_flows
+        self.status = status
+
+    def _ret(self, st: int, where: str, check: bool) -> int:
+        if check and st not in (0, STATUS.OUTPUT_TRUNCATED):
+            raise PFACError(st, where, error_string(st))
+        return st
+
+    def pairs_device(self, d_pair_ids, num_pairs: int, d_piece_first, h_flow_ids, num_pieces: int, d_fired_piece, d_fired_rule, capacity: int,
+                     d_piece_fired_first, check: bool = True):
+        """``PFACX_flowRulesPairsFromDevice``: device arrays but for ``h_flow_ids``; ``d_piece_fired_first`` (numPieces + 1 ``size_t``) may be None,
+        and so may the two fired arrays with capacity 0."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_flowRulesPairsFromDevice(self._f, d_pair_ids, num_pairs, d_piece_first, h_flow_ids, num_pieces, d_fired_piece,
+                                                      d_fired_rule, capacity, d_piece_fired_first, C.byref(n))
+        return self._ret(st, "PFACX_flowRulesPairsFromDevice", check), n.value
+
+    def pairs_host(self, h_pair_ids, num_pairs: int, h_piece_first, h_flow_ids, num_pieces: int, h_fired_piece, h_fired_rule, capacity: int,
+                   h_piece_fired_first, check: bool = True):
+        """``PFACX_flowRulesPairsFromHost``: the same over host arrays, a loop on the host on every platform."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_flowRulesPairsFromHost(self._f, h_pair_ids, num_pairs, h_piece_first, h_flow_ids, num_pieces, h_fired_piece,
+                                                    h_fired_rule, capacity, h_piece_fired_first, C.byref(n))
+        return self._ret(st, "PFACX_flowRulesPairsFromHost", check), n.value
+
+    def reset(self, flow_ids=None, check: bool = True) -> int:
+        """``PFACX_flowRulesReset``: the named flows, or (None) all flows."""
+        import numpy as np
+        if flow_ids is None:
+            return self._ret(self._lib.PFACX_flowRulesReset(self._f, None, 0), "PFACX_flowRulesReset", check)
+        f = np.ascontiguousarray(flow_ids, dtype=np.uint32)
+        buf = f if f.size else np.zeros(1, dtype=np.uint32)
+        return self._ret(self._lib.PFACX_flowRulesReset(self._f, buf.ctypes.data, f.size), "PFACX_flowRulesReset", check)
+
+    def close(self, check: bool = True) -> int:
+        st = self._lib.PFACX_flowRulesClose(self._f)
+        self._f = C.c_void_p()
+        return self._ret(st, "PFACX_flowRulesClose", check)
+
+    def pairs_host_array(self, ids, piece_first, flow_ids, capacity=None, check: bool = True):
+        """pairs_host over numpy arrays -> (status, piece[], rule[], pieceFiredFirst[numPieces + 1], full length).  capacity None: the count query
+        first, then arrays of exactly that length; a number: arrays of exactly that many entries (status may be OUTPUT_TRUNCATED)."""
+        import numpy as np
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        first = np.ascontiguousarray(piece_first, dtype=np.int32)
+        fl = np.ascontiguousarray(flow_ids, dtype=np.uint32)
+        pieces = fl.size
+        idb = ids if ids.size else np.zeros(1, dtype=np.int32)
+        flb = fl if fl.size else np.zeros(1, dtype=np.uint32)
+        fired_first = np.zeros(pieces + 1, dtype=np.uintp)
+        if capacity is None:
+            st, capacity = self.pairs_host(idb.ctypes.data, ids.size, first.ctypes.data, flb.ctypes.data, pieces, None, None, 0, None, check=check)
+            if st not in (0, STATUS.OUTPUT_TRUNCATED):
+                return st, np.zeros(0, np.int32), np.zeros(0, np.int32), fired_first, 0
+        piece = np.full(max(1, capacity), -7, dtype=np.int32)
+        rule = np.full(max(1, capacity), -7, dtype=np.int32)
+        st, n = self.pairs_host(idb.ctypes.data, ids.size, first.ctypes.data, flb.ctypes.data, pieces, piece.ctypes.data, rule.ctypes.data, capacity,
+                                fired_first.ctypes.data, check=check)
+        k = min(n, capacity)
+        return st, piece[:k].copy(), rule[:k].copy(), fired_first, n

@@ -71,7 +71,8 @@ constexpr HostSlot kHostWordList = {52, 54};      /* a words call: the 64-bit le
 constexpr HostSlot kHostSegCount = {56, 60};      /* a batch count call: two 64-bit values, the length of its count list (scan_segcount.hip, by pfac_array_scan), then the sum of the counts (pfac_segcount_finish) */
 constexpr HostSlot kHostGroups = {62, 61};        /* a groups call: the 64-bit length of its list (scan_groups.hip, by pfac_array_scan) */
 constexpr HostSlot kHostLinesContext = {64, 68}; /* a lines call with context: the lines, the selected lines, the matching lines, the groups (scan_lines.hip, by pfac_block_scan and pfac_lines_widen) */
-constexpr int kHostWords = 72;
+constexpr HostSlot kHostFlowRules = {72, 74};    /* a flow-rules call: the 64-bit length of its fired list (scan_flowrules.hip, by pfac_array_scan) */
+constexpr int kHostWords = 76;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -458,12 +459,17 @@ struct DeviceScratch {
      * (numSegments + 1) bytes rounded up to 256; the pair list of PFACX_groupsMatchFromDevice is allPairs, the first pair of each segment
      * allSegFirst, the prefix table allTable: shared.  The mask table of a group handle is state of that handle, not scratch (groups_api.cpp) */
     DeviceBuffer<char> groups;
+    /* the flow-rules calls (PFACX_flowRules*, scan_flowrules.hip): the flow of each piece, 4 numPieces bytes rounded up to 256, then the 64-bit
+     * fired counts of the pieces and, scanned in place, the first fired pair of each: 8 (numPieces + 1) bytes rounded up to 256.  The pairs are the
+     * caller's; the prefix table is allTable: shared.  The tables and the bitmaps of a flow-rule set are state of that set, not scratch
+     * (flowrules_api.cpp) */
+    DeviceBuffer<char> flowRules;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines); f(linesContext);
-        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups);
+        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }

@@ -263,6 +263,16 @@ private:
     std::optional<HostPairs> pairs_;
     std::optional<SetPin> pin_;
 };
+/* rules_api.cpp: the plain rules of PFACX_rulesOpen, validated and inverted exactly as that call does it (the caller holds c->lock, fa is the
+ * handle's set, the pointers are not null) -- what a flow-rule set (flowrules_api.cpp) is opened over.  memberOff[F + 2], member[] = rule << 5 |
+ * bit, ascending rule within a pattern, bit b of a rule its b-th resolved id in ascending order; need[rule] the full mask.  INVALID_PARAMETER:
+ * whatever PFACX_rulesOpen refuses, the limits on numRules included */
+struct PlainRuleTables {
+    size_t numRules = 0, numIds = 0;
+    std::vector<int> memberOff;
+    std::vector<unsigned int> member, need;
+};
+PFAC_status_t invertPlainRules(const pfac::Automaton &fa, const int *h_ruleOff, const int *h_rulePatterns, size_t numRules, PlainRuleTables *out);
 /* all_api.cpp: the device copy of {fa.prefixPattern, fa.chainLen} by id (scratch.allTable) that the all-match expansion and the count calls read;
  * the caller holds c->lock */
 PFAC_status_t ensureAllTable(PFAC_context *c);

@@ -307,6 +307,22 @@ constexpr unsigned int kCondFlags = PFACX_RULE_NOT | PFACX_RULE_FROM_END;
 
 } // namespace
 
+/* pfac_host.h: what PFACX_rulesOpen makes of its arrays, for the flow-rule sets */
+PFAC_status_t pfac_internal::invertPlainRules(const pfac::Automaton &fa, const int *h_ruleOff, const int *h_rulePatterns, size_t numRules,
+                                              PlainRuleTables *out)
+{
+    if (numRules == 0 || numRules >= kMaxRules) return PFAC_STATUS_INVALID_PARAMETER;
+    PFACX_rules_s s;
+    if (!invertRules(fa, h_ruleOff, [=](size_t j) { return PFACX_rule_seq_member_t{h_rulePatterns[j], 0u, 0u, 0u, 0u, 0u}; }, numRules, false, 0u, &s))
+        return PFAC_STATUS_INVALID_PARAMETER;
+    out->numRules = s.numRules;
+    out->numIds = s.numIds;
+    out->memberOff.swap(s.memberOff);
+    out->member.swap(s.member);
+    out->need.swap(s.need);
+    return PFAC_STATUS_SUCCESS;
+}
+
 extern "C" {
 
 PFAC_status_t PFACX_rulesOpen(PFAC_handle_t handle, const int *h_ruleOff, const int *h_rulePatterns, size_t numRules, PFACX_rules_t *rules)

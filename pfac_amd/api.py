@@ -43,6 +43,9 @@ PFACX_RULE_FROM_END = 2                         # the window is measured from th
 RULE_MEMBER_FIELDS = [("pattern", "<i4"), ("flags", "<u4"), ("offset", "<u4"), ("depth", "<u4")]     # PFACX_rule_member_t as a numpy structured dtype: rule_member_dtype()
 PFACX_RULE_RELATIVE = 4                         # PFACX_rule_seq_member_t.flags: distance / within tie the member to the one in front of it (PFACX_rulesOpenSeq)
 RULE_SEQ_MEMBER_FIELDS = RULE_MEMBER_FIELDS + [("distance", "<u4"), ("within", "<u4")]                # PFACX_rule_seq_member_t: rule_seq_member_dtype()
+PFACX_BATCH_BLOCK = 256                         # scan_batch.hip: kBatchBlock, the lanes of a block of every batch fix-up kernel (a block of pairs of the compacted form)
+PFACX_BATCH_SEGS_PER_TRIP = 8                   # scan_batch.hip: kSegsPerTrip, the consecutive segments a group of pfac_batch_fixup takes per trip
+PFACX_BATCH_MAX_GROUP_LOG2 = 6                  # scan_batch.hip: the `groupLog2 < 6` loop of PFACX_batchFixup, at most 64 lanes per segment
 PFACX_RULES_BLOCK_PAIRS = 256                   # scan_rules.hip: kRulesBlockPairs, the pairs a block takes from a segment in one go
 PFACX_FLOWRULES_WINDOW = 8192                   # scan_flowrules.hip: kFlowRulesWindow, the rules whose masks a block keeps in LDS at a time
 PFACX_FLOWRULES_TOUCHED = 1024                  # scan_flowrules.hip: kFlowRulesTouched, the touched-list length; a piece that touches more rules of a window sweeps the whole table

@@ -34,7 +34,7 @@
 
 namespace {
 
-constexpr int kBatchBlock = 256;
+constexpr int kBatchBlock = 256;                       /* pfac_amd/api.py: PFACX_BATCH_BLOCK (tests/batch_edges.py builds its cases on it) */
 
 struct BatchArgs {
     const unsigned char *in;
@@ -63,7 +63,7 @@ __device__ __forceinline__ bool crossesEnd(const BatchArgs &b, int id, size_t p,
 /* A group takes kSegsPerTrip consecutive segments per trip: their offsets, then the first zone position of each, are loaded as
  * independent loads -- one memory round trip per kSegsPerTrip segments instead of two per segment (a batch of 64-byte segments is
  * millions of them; DESIGN.md "batch" has what that bought: less than hoped) */
-constexpr int kSegsPerTrip = 8;
+constexpr int kSegsPerTrip = 8;                        /* pfac_amd/api.py: PFACX_BATCH_SEGS_PER_TRIP */
 
 template <bool TEX>
 __global__ __launch_bounds__(kBatchBlock) void pfac_batch_fixup(BatchArgs b, ScanArgs a, int *out, uint32_t groupLog2)
@@ -227,7 +227,7 @@ PFAC_status_t PFACX_batchFixup(PFAC_handle_t handle, const char *d_input, size_t
     if (size == 0 || b.maxWalk == 0) return PFAC_STATUS_SUCCESS;      /* patterns of one byte never cross an end */
     /* lanes per segment: the zone, or the mean segment if that is shorter, rounded up to a power of two */
     const size_t mean = size / numSegments, want = mean < b.maxWalk ? (mean ? mean : 1) : b.maxWalk;
-    uint32_t groupLog2 = 0;
+    uint32_t groupLog2 = 0;                            /* (the 6: pfac_amd/api.py: PFACX_BATCH_MAX_GROUP_LOG2; tests/batch_edges.py: group_log2 repeats this choice) */
     while (groupLog2 < 6 && (size_t(1) << groupLog2) < want) groupLog2++;
     const size_t perBlock = ((size_t)kBatchBlock >> groupLog2) * kSegsPerTrip;      /* segments a block takes per trip */
     const size_t blocks = numSegments / perBlock + 1;

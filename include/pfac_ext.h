@@ -21,8 +21,10 @@
  * sets over the pieces of a flow (PFACX_flowRules*), the
  * counts of every pattern in every segment (PFACX_countBatch*), the
  * occurrences bounded by bytes outside a class: whole words, lines and
- * fields (PFACX_matchWords*, PFACX_wordsPairsFromDevice) and pattern
- * groups: each segment of a batch sees only its own patterns (PFACX_groups*).
+ * fields (PFACX_matchWords*, PFACX_wordsPairsFromDevice), pattern
+ * groups: each segment of a batch sees only its own patterns (PFACX_groups*)
+ * and the offsets that cut a buffer into the segments of a batch at the bytes
+ * of a delimiter class (PFACX_splitFromDevice / ...FromHost).
  */
 #ifndef PFAC_EXT_H_
 #define PFAC_EXT_H_
@@ -1033,6 +1035,51 @@ PFAC_status_t PFACX_groupsPairsFromDevice(PFACX_groups_t groups, const int *d_pa
                                           const unsigned long long *d_segMasks, unsigned int flags,
                                           int *d_ids, int *d_pos, size_t capacity, size_t *d_segFirst, unsigned long long *d_segGroups,
                                           size_t *h_num_matched);
+
+/* Split: the offsets that cut a buffer into records at the bytes of a delimiter class -- the `d_offsets` that PFACX_matchBatch*,
+ * PFACX_matchAllBatchFromDevice, PFACX_rules*, PFACX_countBatch* and PFACX_groups* take, made where the text lies: the lines of a log, the records
+ * of a CRLF protocol, the fields of a line.
+ *   THE CLASS D is a set of byte values, 256 bits in `unsigned int cls[8]` exactly as the class of PFACX_matchWords*: byte b is in D if bit b & 31 of
+ *   cls[b >> 5] is set.  The eight words are HOST memory in both calls and are copied.  h_class == NULL: the class {'\n'}.  The class is tested on the
+ *   caller's bytes: a caseless handle (PFACX_READ_NOCASE) changes nothing -- 'A' in the class does not cut at 'a' --, and the input is never written.
+ *   CUTS.  Let the input have n bytes; a position p with in[p] in D is a DELIMITER.
+ *     flags 0:            every delimiter p with p + 1 < n gives the cut p + 1: a delimiter closes the segment in front of it.
+ *     PFACX_SPLIT_BEFORE: every delimiter p with p > 0 gives the cut p: a delimiter opens the segment behind it.
+ *     PFACX_SPLIT_RUNS:   only one delimiter of each maximal run of delimiters cuts -- without BEFORE the last one (in[p + 1] is not in D), with
+ *                         BEFORE the first one (in[p - 1] is not in D).
+ *   Cuts are distinct and lie strictly inside (0, n).  THE OFFSETS are 0, then the cuts ascending, then n; numSegments = the number of cuts + 1;
+ *   segment k is in[offsets[k], offsets[k + 1]).  No segment is ever empty.
+ *   CONSEQUENCES: with flags 0 and the default class, segment k is line k of the PFACX_matchLines* definition together with its '\n' (an unterminated
+ *   last line is a segment like every other), and numSegments == numLines of those calls.  An empty class gives one segment, [0, n).  A full class
+ *   gives n segments of one byte, under PFACX_SPLIT_RUNS one.
+ *   SEGMENT ENDS.  Delimiters are never dropped: a segment includes its closing delimiter or, with PFACX_SPLIT_BEFORE, its opening one.  For the
+ *   windows of PFACX_rulesOpenEx the delimiter counts as a byte of the segment: a PFACX_RULE_FROM_END window over lines cut with flags 0 measures
+ *   from behind the '\n' -- "in the last 16 bytes of the line" needs offset 1 --, while PFACX_SPLIT_BEFORE puts the delimiter at the segment's front,
+ *   where FROM_END windows never see it (windows from the start then count it as byte 0).  This is why BEFORE exists.
+ * OUTPUT.  *h_numSegments is always the full count; *h_longest (may be NULL) is the longest segment in bytes -- the capacity a per-segment buffer
+ * needs --, the full value also when the list is truncated.  `capacity` is the number of entries of the offsets array: numSegments + 1 are needed,
+ * size + 1 always suffices.  A smaller capacity: exactly the first `capacity` entries are written -- 0 and the first capacity - 1 cuts --, nothing
+ * at or behind them, and the call returns PFACX_STATUS_OUTPUT_TRUNCATED.  capacity == 0 is the count query: the array may be null.
+ * LIMITS.  There is no 2^31 limit: positions are computed in 64 bits throughout (of the batch calls the full-result form has no limit either; the
+ * others refuse sizes from 2^31 on).  size == 0: success, 0 segments, *h_longest = 0, nothing written.  PFAC_STATUS_INVALID_PARAMETER: an unknown
+ * flag bit; a null handle, input or h_numSegments; a null array with capacity > 0; an offsets pointer that is not 8-byte aligned.  The call needs no
+ * pattern set: on a handle without one it succeeds.  The device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.  Both forms take the handle's
+ * lock and are synchronous (the counts come to the host).  The host form is a host loop on every platform, as PFACX_flowRulesPairsFromHost is; a
+ * class of one byte runs at the speed of memchr.
+ * MEMORY of the device form: grow-only handle scratch sized by the number of tiles alone -- with T = ceil(size / 16384): 8 (T + 1) + 16 T + 4 T +
+ * 4 T + 4 T + 8 bytes, each term rounded up to 256: 0.0022 bytes per input byte, whatever the data.  Counted under deviceScratchBytes of
+ * PFACX_getInfo, freed by PFACX_trim, not allocated before the first split call.
+ * COST: two streaming reads of the input -- one counts the cuts per tile, one writes them -- and 8 bytes written per segment; between
+ * them two one-block launches over the per-tile values.
+ * OUT OF SCOPE: multi-byte delimiters ("\r\n" as ONE delimiter: the class {'\r', '\n'} with PFACX_SPLIT_RUNS cuts once per "\r\n", and once per
+ * blank-line run); dropping the delimiters from the segments -- the batch calls take contiguous segments; quoting rules for CSV; device-resident
+ * classes; splitting the pieces of a stream or flow. */
+#define PFACX_SPLIT_BEFORE 1u   /* a delimiter opens the segment behind it instead of closing the one in front */
+#define PFACX_SPLIT_RUNS   2u   /* a maximal run of delimiters cuts once */
+PFAC_status_t PFACX_splitFromDevice(PFAC_handle_t handle, const char *d_input, size_t size, const unsigned int *h_class /* 8 words or NULL */,
+                                    unsigned int flags, size_t *d_offsets, size_t capacity, size_t *h_numSegments, size_t *h_longest /* may be NULL */);
+PFAC_status_t PFACX_splitFromHost  (PFAC_handle_t handle, const char *h_input, size_t size, const unsigned int *h_class /* 8 words or NULL */,
+                                    unsigned int flags, size_t *h_offsets, size_t capacity, size_t *h_numSegments, size_t *h_longest /* may be NULL */);
 
 #ifdef __cplusplus
 }

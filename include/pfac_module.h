@@ -360,6 +360,23 @@ typedef struct {
 } PFACX_flowRulesRun_t;
 PFAC_status_t PFACX_flowRulesRun(PFAC_handle_t handle, const PFACX_flowRulesRun_t *run, size_t *h_total);
 
+/* Split (no reference counterpart; include/pfac_ext.h: PFACX_split*), scan_split.hip.
+ * PFACX_splitRun: the offsets that cut d_input[0, size), size > 0 and any size that has fewer than 2^31 tiles of 16 KiB, at the bytes of the class
+ * cls (bit b & 31 of cls[b >> 5] for byte b; the caller's bytes are tested as they are and never written): 0, the cuts of pfac_ext.h's definition
+ * under `flags` (PFACX_SPLIT_BEFORE, PFACX_SPLIT_RUNS) ascending, `size`, as 64-bit values into d_offsets -- entries [0, capacity) of them, nothing at
+ * or beyond `capacity` (0: the array may be null, nothing is written).  *h_numSegments = the cuts + 1 and *h_longest (or null) = the longest segment
+ * in bytes are the full values whatever the capacity.  Two reads of the input; scratch: the handle's split scratch, sized by the tiles alone
+ * (scan_split.hip has the formula).  Synchronous. */
+typedef struct {
+    const char *d_input;
+    size_t size;
+    unsigned int cls[8];
+    unsigned int flags;
+    size_t *d_offsets;
+    size_t capacity;
+} PFACX_splitRun_t;
+PFAC_status_t PFACX_splitRun(PFAC_handle_t handle, const PFACX_splitRun_t *run, size_t *h_numSegments, size_t *h_longest);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -374,7 +391,7 @@ PFAC_status_t PFACX_flowRulesRun(PFAC_handle_t handle, const PFACX_flowRulesRun_
     X(count_pairs_ptr, PFACX_countPairs) X(count_nonzero_ptr, PFACX_countNonzero) \
     X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun) \
     X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun) X(segcount_run_ptr, PFACX_segCountRun) \
-    X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun)
+    X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun) X(split_run_ptr, PFACX_splitRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

@@ -34,6 +34,11 @@ PFACX_WORDS_ALL = 1                             # pfac_ext.h: PFACX_matchWords* 
 PFACX_GROUPS_ALL = 1                            # pfac_ext.h: PFACX_groups* report every enabled occurrence, not the longest enabled one per position
 PFACX_GROUPS_BLOCK = 256                        # scan_groups.hip: kGroupsBlock, the pairs one block of the group passes takes (never more than eight blocks per CU)
 PFACX_WORDS_BLOCK = 256                         # scan_words.hip: kWordsBlock, the pairs one block of the boundary passes takes (never more than eight blocks per CU)
+PFACX_SPLIT_BEFORE = 1                          # pfac_ext.h: PFACX_split* a delimiter opens the segment behind it instead of closing the one in front
+PFACX_SPLIT_RUNS = 2                            # ... a maximal run of delimiters cuts once
+PFACX_SPLIT_TILE = 16384                        # scan_split.hip: kSplitTile, the input bytes one block of the split passes takes at a time (never more than eight blocks per CU a pass)
+PFACX_SPLIT_SCAN_STEP = 1024                    # scan_passes.h: pfac_array_scan, the per-tile counts its one block takes per step
+PFACX_SPLIT_LONGEST_STEP = 4096                 # scan_split.hip: pfac_split_longest, the tiles its one block takes per step (kSplitPerThread a thread)
 PFACX_DISJOINT_BLOCK = 512                      # scan_disjoint.hip: kDisjointBlock, the pairs one block of the selection takes
 PFACX_REPLACE_TILE = 4096                       # scan_disjoint.hip: kReplaceTile, the output bytes of one tile of the replacement
 PFACX_RULES_WINDOW = 8192                       # scan_rules.hip: kRulesWindow, the rules whose masks a block keeps in LDS at a time
@@ -143,6 +148,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_matchWordsFromDevice", "PFACX_matchWordsFromHost", "PFACX_wordsPairsFromDevice",
     "PFACX_countBatchFromDevice", "PFACX_countBatchFromHost", "PFACX_countBatchPairsFromDevice",
     "PFACX_groupsOpen", "PFACX_groupsClose", "PFACX_groupsMatchFromDevice", "PFACX_groupsMatchFromHost", "PFACX_groupsPairsFromDevice",
+    "PFACX_splitFromDevice", "PFACX_splitFromHost",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -159,6 +165,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_segCountRun",
     "PFACX_groupsRun",
     "PFACX_flowRulesRun",
+    "PFACX_splitRun",
 )
 
 
@@ -315,6 +322,11 @@ def load_library() -> C.CDLL:
         lib.PFACX_groupsMatchFromHost.argtypes = groups
         lib.PFACX_groupsPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint,
                                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, SZ]
+    if hasattr(lib, "PFACX_splitFromDevice"):
+        SZ = C.POINTER(C.c_size_t)
+        split = [H, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint), C.c_uint, C.c_void_p, C.c_size_t, SZ, SZ]
+        lib.PFACX_splitFromDevice.argtypes = split
+        lib.PFACX_splitFromHost.argtypes = split
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -830,6 +842,38 @@ class PFAC:
                                         check=False)
         self._ret(st, "PFACX_matchWordsFromHost", True)
         return pos[:n].copy(), ids[:n].copy()
+
+    # -- the offsets that cut a buffer into segments at a delimiter class (include/pfac_ext.h: PFACX_split*) ----------------
+    def _split(self, name: str, input_, size: int, cls, flags: int, offsets, capacity: int, want_longest: bool, check: bool):
+        n, longest = C.c_size_t(0), C.c_size_t(0)
+        st = getattr(self._lib, name)(self._h, input_, size, _class_arg(cls), flags, offsets, capacity, C.byref(n),
+                                      C.byref(longest) if want_longest else None)
+        return self._ret(st, name, check and st != STATUS.OUTPUT_TRUNCATED), n.value, longest.value
+
+    def splitFromDevice(self, d_input: int, size: int, cls, flags: int, d_offsets, capacity: int, want_longest: bool = True, check: bool = True):
+        """``PFACX_splitFromDevice`` -> (status, number of segments, longest segment); `cls`: word_class(...), bytes, or None for {'\n'};
+        `d_offsets` (``size_t``, device) may be None with capacity 0: the count query.  OUTPUT_TRUNCATED is returned, not raised."""
+        return self._split("PFACX_splitFromDevice", d_input, size, cls, flags, d_offsets, capacity, want_longest, check)
+
+    def splitFromHost(self, h_input: int, size: int, cls, flags: int, h_offsets, capacity: int, want_longest: bool = True, check: bool = True):
+        """``PFACX_splitFromHost``: the same over host memory, a host loop on every platform."""
+        return self._split("PFACX_splitFromHost", h_input, size, cls, flags, h_offsets, capacity, want_longest, check)
+
+    def split_host_array(self, data, cls=None, before: bool = False, runs: bool = False):
+        """splitFromHost over a numpy array -> (offsets as a numpy ``uint64`` array of numSegments + 1 entries -- empty for empty data --, the longest
+        segment): the count query first, then an array of exactly that length."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        flags = (PFACX_SPLIT_BEFORE if before else 0) | (PFACX_SPLIT_RUNS if runs else 0)
+        st, n, longest = self.splitFromHost(buf.ctypes.data, data.size, cls, flags, None, 0)                   # the count query
+        if data.size == 0:
+            return np.zeros(0, dtype=np.uint64), longest
+        offsets = np.full(n + 1, 0xDEAD, dtype=np.uint64)
+        st, n2, longest2 = self.splitFromHost(buf.ctypes.data, data.size, cls, flags, offsets.ctypes.data, offsets.size)
+        if st != 0 or n2 != n or longest2 != longest:
+            raise PFACError(st, "PFACX_splitFromHost", f"{n2} segments, the longest {longest2}, behind a count query that said {n} and {longest}")
+        return offsets, longest
 
     # -- input that arrives in pieces (include/pfac_ext.h: PFACX_stream*) ----------------
     def streamOpen(self, check: bool = True) -> "Stream":

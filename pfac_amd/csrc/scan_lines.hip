@@ -100,15 +100,8 @@ struct ContextArgs : LinesArgs {
     int *lineTag;
 };
 
-/* bits 7, 15, 23, 31 of m -- one per byte -- as a nibble, byte 0 in bit 0: the four products land on bits 21..24 and nothing carries */
-__device__ __forceinline__ uint32_t nibbleOf(uint32_t m) { return (((m >> 7) * 0x00204081u) >> 21) & 0xFu; }
-
-/* bit i: byte i of x is '\n' (exact: the carry of a byte's low seven bits never leaves it) */
-__device__ __forceinline__ uint32_t newlines4(uint32_t x)
-{
-    const uint32_t t = x ^ 0x0A0A0A0Au;
-    return nibbleOf(~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u);
-}
+/* bit i: byte i of x is '\n' (scan_passes.h: bytesEqual4) */
+__device__ __forceinline__ uint32_t newlines4(uint32_t x) { return bytesEqual4(x, 0x0A0A0A0Au); }
 
 /* the 16 bits of granule g (positions q in [16 g, 16 g + 16)) */
 __device__ __forceinline__ uint32_t granuleBits(const LinesArgs &a, size_t g)

@@ -22,9 +22,11 @@
  * counts of every pattern in every segment (PFACX_countBatch*), the
  * occurrences bounded by bytes outside a class: whole words, lines and
  * fields (PFACX_matchWords*, PFACX_wordsPairsFromDevice), pattern
- * groups: each segment of a batch sees only its own patterns (PFACX_groups*)
- * and the offsets that cut a buffer into the segments of a batch at the bytes
- * of a delimiter class (PFACX_splitFromDevice / ...FromHost).
+ * groups: each segment of a batch sees only its own patterns (PFACX_groups*),
+ * the offsets that cut a buffer into the segments of a batch at the bytes
+ * of a delimiter class (PFACX_splitFromDevice / ...FromHost) and the record
+ * and column of every match by the same cuts (PFACX_locatePairs*,
+ * PFACX_matchLocated*).
  */
 #ifndef PFAC_EXT_H_
 #define PFAC_EXT_H_
@@ -1080,6 +1082,52 @@ PFAC_status_t PFACX_splitFromDevice(PFAC_handle_t handle, const char *d_input, s
                                     unsigned int flags, size_t *d_offsets, size_t capacity, size_t *h_numSegments, size_t *h_longest /* may be NULL */);
 PFAC_status_t PFACX_splitFromHost  (PFAC_handle_t handle, const char *h_input, size_t size, const unsigned int *h_class /* 8 words or NULL */,
                                     unsigned int flags, size_t *h_offsets, size_t capacity, size_t *h_numSegments, size_t *h_longest /* may be NULL */);
+
+/* Locate: the record and the column of every match -- what `grep -n -b -o` prints: the line of a log and the byte in it, the record of a CRLF protocol
+ * and the offset inside it.  Every compacted call hands back positions as byte offsets into the buffer; these calls turn them into (record, column)
+ * where the text lies, without the offsets array of PFACX_split*.
+ *   RECORDS.  The class D (`unsigned int cls[8]`, HOST memory, copied; NULL: {'\n'}) and the flags (PFACX_SPLIT_BEFORE, PFACX_SPLIT_RUNS, the same
+ *   values; any other bit: PFAC_STATUS_INVALID_PARAMETER) are those of PFACX_split*, word for word.  The class is tested on the caller's bytes: a
+ *   caseless handle changes nothing.  Let C be the cuts PFACX_split* defines for (input, D, flags).  For a position p of [0, size):
+ *     record(p) = the number of cuts c <= p;   start(p) = the largest cut <= p, 0 if there is none;   column(p) = p - start(p).
+ *   Equivalently, with `offsets` the array PFACX_split* returns: record = (the number of offsets <= p) - 1, column = p - offsets[record].
+ *   CONSEQUENCES: with the default class and flags 0, record is the 0-based line number (lineIndex of PFACX_matchLines*) and column the 0-based byte
+ *   offset in the line; with flags 0 the '\n' byte itself belongs to the line it ends.  Both values are int: size >= 2^31 is
+ *   PFAC_STATUS_INVALID_PARAMETER, as for every pairs call.  A position outside [0, size) -- the negative positions of streams and flows -- gets
+ *   record = column = -1.
+ * THE PAIRS FORMS take a position list that any call of the library left behind (reduce, matchAll, words, disjoint, groups).  The list must be
+ * non-decreasing; equal neighbours are allowed, as PFACX_matchAll* produces them; every list the library returns is.  The arrays are the caller's
+ * contract (device memory in the device form): a list that is not non-decreasing gives unspecified record and column values, but never an access
+ * outside input[0, size), pos[0, numPairs) or the outputs' numPairs entries.  d_column may be NULL.  *h_numRecords (may be NULL) is the segment
+ * count PFACX_split* would report.  numPairs == 0 or size == 0: success, no array is touched; *h_numRecords is still written (0 for size == 0).
+ * The calls need no pattern set, are synchronous and take the handle's lock.  PFAC_STATUS_INVALID_PARAMETER: an unknown flag bit; a null handle or
+ * input; a null list or record array with numPairs > 0; size or numPairs >= 2^31.  The device form on a host-only handle:
+ * PFAC_STATUS_LIB_NOT_EXIST.  The host form is a host loop on every platform: one forward walk over input and positions together, no offsets array.
+ * THE SCAN FORMS scan, then locate: ids and pos (`size` entries each) are exactly what PFAC_matchFromDeviceReduce / PFAC_matchFromHostReduce return,
+ * record and column (may be NULL) belong to those pairs.  More pairs than locCapacity: exactly the first locCapacity record and column entries are
+ * written, *h_num_matched is the full count and the call returns PFACX_STATUS_OUTPUT_TRUNCATED (locCapacity == 0: both arrays may be null).  A
+ * caseless handle folds for the match and never for the class.  Error cases are those of PFAC_matchFromDeviceReduce, plus the flag check and a null
+ * record array with locCapacity > 0.  The host form follows PFAC_setPlatform as PFACX_matchAllFromHost does: on the GPU platform the staged-piece
+ * path of the other host forms, then the host loop.
+ * MEMORY of the device forms: grow-only handle scratch sized by the number of tiles alone -- with T = ceil(size / 16384): 8 (T + 1) + 4 T + 4 T
+ * bytes, each term rounded up to 256: 0.001 bytes per input byte, whatever the data and however many pairs.  Counted under deviceScratchBytes of
+ * PFACX_getInfo, freed by PFACX_trim, not allocated before the first locate call.
+ * COST: one streaming read of the input that counts the cuts per tile, two one-block launches over the per-tile values, a launch over
+ * the list, and a second read of only the tiles that hold a pair; 4 bytes read and 8 written per pair.
+ * OUT OF SCOPE: stream and flow pairs (positions that count from a piece's first byte); per-segment records of a batch; columns in characters (UTF-8)
+ * or with tab expansion; 1-based numbering; unsorted position lists; device-resident classes. */
+PFAC_status_t PFACX_locatePairsFromDevice(PFAC_handle_t handle, const char *d_input, size_t size, const unsigned int *h_class /* 8 words or NULL */,
+                                          unsigned int flags, const int *d_pos, size_t numPairs, int *d_record, int *d_column /* may be NULL */,
+                                          size_t *h_numRecords /* may be NULL */);
+PFAC_status_t PFACX_locatePairsFromHost  (PFAC_handle_t handle, const char *h_input, size_t size, const unsigned int *h_class /* 8 words or NULL */,
+                                          unsigned int flags, const int *h_pos, size_t numPairs, int *h_record, int *h_column /* may be NULL */,
+                                          size_t *h_numRecords /* may be NULL */);
+PFAC_status_t PFACX_matchLocatedFromDevice(PFAC_handle_t handle, char *d_input, size_t size, const unsigned int *h_class /* 8 words or NULL */,
+                                           unsigned int flags, int *d_ids, int *d_pos /* size entries each */, int *d_record,
+                                           int *d_column /* may be NULL */, size_t locCapacity, int *h_num_matched);
+PFAC_status_t PFACX_matchLocatedFromHost  (PFAC_handle_t handle, char *h_input, size_t size, const unsigned int *h_class /* 8 words or NULL */,
+                                           unsigned int flags, int *h_ids, int *h_pos /* size entries each */, int *h_record,
+                                           int *h_column /* may be NULL */, size_t locCapacity, int *h_num_matched);
 
 #ifdef __cplusplus
 }

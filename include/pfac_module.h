@@ -377,6 +377,25 @@ typedef struct {
 } PFACX_splitRun_t;
 PFAC_status_t PFACX_splitRun(PFAC_handle_t handle, const PFACX_splitRun_t *run, size_t *h_numSegments, size_t *h_longest);
 
+/* Locate (no reference counterpart; include/pfac_ext.h: PFACX_locate*), scan_locate.hip.
+ * PFACX_locateRun: for the positions d_pos[0, numPairs) (non-decreasing; 0 <= numPairs < 2^31) in d_input[0, size), 0 < size < 2^31, the record
+ * and the column by the cuts that PFACX_splitRun makes of the same class and flags: d_record[i] = the number of cuts <= d_pos[i], d_column[i]
+ * (the array may be null) = d_pos[i] - the largest such cut (0: none); both -1 for a position outside [0, size).  *h_numRecords = the cuts + 1.
+ * numPairs == 0: only the count, no array is touched.  The list is never trusted: a list that is not non-decreasing gets unspecified values and
+ * no access outside the input, the list and the outputs' numPairs entries.  One read of the input and a second of the tiles of 16 KiB that hold
+ * a position; scratch: the handle's locate scratch, sized by the tiles alone (scan_locate.hip has the formula).  Synchronous. */
+typedef struct {
+    const char *d_input;
+    size_t size;
+    unsigned int cls[8];
+    unsigned int flags;
+    const int *d_pos;
+    size_t numPairs;
+    int *d_record;
+    int *d_column;
+} PFACX_locateRun_t;
+PFAC_status_t PFACX_locateRun(PFAC_handle_t handle, const PFACX_locateRun_t *run, size_t *h_numRecords);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -391,7 +410,8 @@ PFAC_status_t PFACX_splitRun(PFAC_handle_t handle, const PFACX_splitRun_t *run, 
     X(count_pairs_ptr, PFACX_countPairs) X(count_nonzero_ptr, PFACX_countNonzero) \
     X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun) \
     X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun) X(segcount_run_ptr, PFACX_segCountRun) \
-    X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun) X(split_run_ptr, PFACX_splitRun)
+    X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun) X(split_run_ptr, PFACX_splitRun) \
+    X(locate_run_ptr, PFACX_locateRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

@@ -38,6 +38,7 @@ PFACX_SPLIT_BEFORE = 1                          # pfac_ext.h: PFACX_split* a del
 PFACX_SPLIT_RUNS = 2                            # ... a maximal run of delimiters cuts once
 PFACX_SPLIT_TILE = 16384                        # scan_split.hip: kSplitTile, the input bytes one block of the split passes takes at a time (never more than eight blocks per CU a pass)
 PFACX_SPLIT_SCAN_STEP = 1024                    # scan_passes.h: pfac_array_scan, the per-tile counts its one block takes per step
+PFACX_LOCATE_CARRY_STEP = 1024                  # scan_locate.hip: pfac_locate_carry, the tiles its one block takes per step (the step of pfac_array_scan)
 PFACX_SPLIT_LONGEST_STEP = 4096                 # scan_split.hip: pfac_split_longest, the tiles its one block takes per step (kSplitPerThread a thread)
 PFACX_DISJOINT_BLOCK = 512                      # scan_disjoint.hip: kDisjointBlock, the pairs one block of the selection takes
 PFACX_REPLACE_TILE = 4096                       # scan_disjoint.hip: kReplaceTile, the output bytes of one tile of the replacement
@@ -149,6 +150,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_countBatchFromDevice", "PFACX_countBatchFromHost", "PFACX_countBatchPairsFromDevice",
     "PFACX_groupsOpen", "PFACX_groupsClose", "PFACX_groupsMatchFromDevice", "PFACX_groupsMatchFromHost", "PFACX_groupsPairsFromDevice",
     "PFACX_splitFromDevice", "PFACX_splitFromHost",
+    "PFACX_locatePairsFromDevice", "PFACX_locatePairsFromHost", "PFACX_matchLocatedFromDevice", "PFACX_matchLocatedFromHost",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -166,6 +168,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_groupsRun",
     "PFACX_flowRulesRun",
     "PFACX_splitRun",
+    "PFACX_locateRun",
 )
 
 
@@ -327,6 +330,15 @@ def load_library() -> C.CDLL:
         split = [H, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint), C.c_uint, C.c_void_p, C.c_size_t, SZ, SZ]
         lib.PFACX_splitFromDevice.argtypes = split
         lib.PFACX_splitFromHost.argtypes = split
+    if hasattr(lib, "PFACX_locatePairsFromDevice"):
+        SZ = C.POINTER(C.c_size_t)
+        pairs = [H, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint), C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, SZ]
+        lib.PFACX_locatePairsFromDevice.argtypes = pairs
+        lib.PFACX_locatePairsFromHost.argtypes = pairs
+        located = [H, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint), C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                   C.POINTER(C.c_int)]
+        lib.PFACX_matchLocatedFromDevice.argtypes = located
+        lib.PFACX_matchLocatedFromHost.argtypes = located
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -874,6 +886,53 @@ class PFAC:
         if st != 0 or n2 != n or longest2 != longest:
             raise PFACError(st, "PFACX_splitFromHost", f"{n2} segments, the longest {longest2}, behind a count query that said {n} and {longest}")
         return offsets, longest
+
+    # -- the record and the column of every match (include/pfac_ext.h: PFACX_locatePairs*, PFACX_matchLocated*) ----------------
+    def _locate_pairs(self, name: str, input_, size: int, cls, flags: int, pos, num_pairs: int, record, column, want_records: bool, check: bool):
+        n = C.c_size_t(0)
+        st = getattr(self._lib, name)(self._h, input_, size, _class_arg(cls), flags, pos, num_pairs, record, column,
+                                      C.byref(n) if want_records else None)
+        return self._ret(st, name, check), n.value
+
+    def locatePairsFromDevice(self, d_input: int, size: int, cls, flags: int, d_pos, num_pairs: int, d_record, d_column,
+                              want_records: bool = True, check: bool = True):
+        """``PFACX_locatePairsFromDevice`` -> (status, number of records); `cls`: word_class(...), bytes, or None for {'\n'}; `d_pos`,
+        `d_record`, `d_column` (``int``, device; `d_column` may be None): num_pairs entries each."""
+        return self._locate_pairs("PFACX_locatePairsFromDevice", d_input, size, cls, flags, d_pos, num_pairs, d_record, d_column, want_records, check)
+
+    def locatePairsFromHost(self, h_input: int, size: int, cls, flags: int, h_pos, num_pairs: int, h_record, h_column,
+                            want_records: bool = True, check: bool = True):
+        """``PFACX_locatePairsFromHost``: the same over host memory, a host loop on every platform."""
+        return self._locate_pairs("PFACX_locatePairsFromHost", h_input, size, cls, flags, h_pos, num_pairs, h_record, h_column, want_records, check)
+
+    def _match_located(self, name: str, input_, size: int, cls, flags: int, ids, pos, record, column, loc_capacity: int, check: bool):
+        n = C.c_int(0)
+        st = getattr(self._lib, name)(self._h, input_, size, _class_arg(cls), flags, ids, pos, record, column, loc_capacity, C.byref(n))
+        return self._ret(st, name, check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def matchLocatedFromDevice(self, d_input: int, size: int, cls, flags: int, d_ids, d_pos, d_record, d_column, loc_capacity: int,
+                               check: bool = True):
+        """``PFACX_matchLocatedFromDevice`` -> (status, number of pairs): `d_ids`, `d_pos` size entries each as for matchFromDeviceReduce,
+        `d_record`, `d_column` (may be None) loc_capacity entries each.  OUTPUT_TRUNCATED is returned, not raised."""
+        return self._match_located("PFACX_matchLocatedFromDevice", d_input, size, cls, flags, d_ids, d_pos, d_record, d_column, loc_capacity, check)
+
+    def matchLocatedFromHost(self, h_input: int, size: int, cls, flags: int, h_ids, h_pos, h_record, h_column, loc_capacity: int,
+                             check: bool = True):
+        """``PFACX_matchLocatedFromHost``: the same over host memory; follows PFAC_setPlatform."""
+        return self._match_located("PFACX_matchLocatedFromHost", h_input, size, cls, flags, h_ids, h_pos, h_record, h_column, loc_capacity, check)
+
+    def locate_host_array(self, data, positions, cls=None, before: bool = False, runs: bool = False):
+        """locatePairsFromHost over numpy arrays -> (records, columns, number of records): `positions` non-decreasing ``int32``."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        pos = np.ascontiguousarray(positions, dtype=np.int32)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        flags = (PFACX_SPLIT_BEFORE if before else 0) | (PFACX_SPLIT_RUNS if runs else 0)
+        record = np.full(max(pos.size, 1), -7, dtype=np.int32)
+        column = np.full(max(pos.size, 1), -7, dtype=np.int32)
+        st, n = self.locatePairsFromHost(buf.ctypes.data, data.size, cls, flags, pos.ctypes.data if pos.size else None, pos.size,
+                                         record.ctypes.data, column.ctypes.data)
+        return record[:pos.size], column[:pos.size], n
 
     # -- input that arrives in pieces (include/pfac_ext.h: PFACX_stream*) ----------------
     def streamOpen(self, check: bool = True) -> "Stream":

@@ -73,7 +73,8 @@ constexpr HostSlot kHostGroups = {62, 61};        /* a groups call: the 64-bit l
 constexpr HostSlot kHostLinesContext = {64, 68}; /* a lines call with context: the lines, the selected lines, the matching lines, the groups (scan_lines.hip, by pfac_block_scan and pfac_lines_widen) */
 constexpr HostSlot kHostFlowRules = {72, 74};    /* a flow-rules call: the 64-bit length of its fired list (scan_flowrules.hip, by pfac_array_scan) */
 constexpr HostSlot kHostSplit = {76, 80};        /* a split call: two 64-bit values, the cuts (scan_split.hip, by pfac_array_scan), then the longest segment (pfac_split_longest) */
-constexpr int kHostWords = 82;
+constexpr HostSlot kHostLocate = {82, 84};       /* a locate call: the 64-bit number of cuts (scan_locate.hip, by pfac_array_scan) */
+constexpr int kHostWords = 86;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -469,12 +470,16 @@ struct DeviceScratch {
      * regions, its first and last cut and its longest inner distance, then the 64-bit longest segment: 8 (T + 1) + 16 T + 4 T + 4 T + 4 T + 8 bytes,
      * each part rounded up to 256; not allocated before the first split call */
     DeviceBuffer<char> split;
+    /* the locate calls (PFACX_locatePairsFromDevice, PFACX_matchLocatedFromDevice, scan_locate.hip): per tile of 16 KiB the cuts (64-bit, scanned in
+     * place, + 1 entry), the last cut of -- then in front of -- the tile and the first pair that lies in it: 8 (T + 1) + 4 T + 4 T bytes, each part
+     * rounded up to 256; not allocated before the first locate call */
+    DeviceBuffer<char> locate;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines); f(linesContext);
-        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split);
+        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }

@@ -98,6 +98,15 @@ inline bool lacksModule(const PFAC_context *c) { return !c->hasDevice || !c->mod
 inline bool hostLacksModule(const PFAC_context *c) { return c->platform == PFAC_PLATFORM_GPU && lacksModule(c); }
 /* the status of a call whose full list has `total` entries */
 inline PFAC_status_t truncatedIf(unsigned long long total, size_t capacity) { return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS; }
+/* The cuts of PFACX_split* on the host (split_api.cpp, locate_api.cpp).  kNewlineClass: {'\n'}, the class of a null h_class; inClass: byte b is in
+ * the class; isCut: position c of [1, n - 1] is a cut, given a = (in[c - 1] is in the class) and b = (in[c] is) -- the four flag combinations of
+ * the header in one place */
+constexpr unsigned int kNewlineClass[8] = {1u << '\n', 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+inline bool inClass(const unsigned int *cls, unsigned char b) { return (cls[b >> 5] >> (b & 31u)) & 1u; }
+inline bool isCut(unsigned int flags, bool a, bool b)
+{
+    return (flags & PFACX_SPLIT_RUNS) ? ((flags & PFACX_SPLIT_BEFORE) ? b && !a : a && !b) : ((flags & PFACX_SPLIT_BEFORE) ? b : a);
+}
 /* the pair temporaries of a host form in one allocation: numIds ids, then numPos positions; not initialised: a page nothing writes costs nothing */
 struct HostPairs {
     HostPairs(size_t numIds, size_t numPos) : mem(new (std::nothrow) int[numIds + numPos + 1]), ids(mem.get()), pos(mem ? mem.get() + numIds : nullptr) {}

@@ -1,6 +1,6 @@
 /*
  * scan_passes.h -- what the passes around the scan share (scan_module.hip with scan_order.inc, scan_batch.hip, scan_all.hip, scan_fold.hip,
- * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip, scan_disjoint.hip, scan_rules.hip, scan_words.hip, scan_segcount.hip, scan_groups.hip, scan_split.hip; the product kernels' units do
+ * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip, scan_disjoint.hip, scan_rules.hip, scan_words.hip, scan_segcount.hip, scan_groups.hip and, through scan_cuts.h, scan_split.hip and scan_locate.hip; the product kernels' units do
  * not include it): launch sizes, the layout of a call's scratch and its carving out of a buffer of the handle (ScratchCarver, carveScratch), the
  * compacted scan as a pass runs it, the hand-off of a call's result to the host through mapped memory (HostHandoff; storeToHost on the device),
  * the device fold byte, the exact SWAR test of four bytes against one (bytesEqual4), the clamp of a caller's (start, len), 16 bytes out of two aligned blocks (funnel, loadBytes16), the frame of an output
@@ -182,7 +182,7 @@ __device__ __forceinline__ void storeToHost(T *host, T v, T v1)
 /* pfac::asciiFold on the device, for a caseless set (fold != 0) */
 __device__ __forceinline__ unsigned char foldByte(unsigned char b, uint32_t fold) { return (unsigned char)(b + ((fold != 0 && (unsigned)(b - 'A') < 26u) ? 32 : 0)); }
 
-/* ------------------------------------------------------------------ four bytes against one (scan_lines.hip, scan_split.hip) */
+/* ------------------------------------------------------------------ four bytes against one (scan_lines.hip, scan_cuts.h) */
 
 /* bits 7, 15, 23, 31 of m -- one per byte -- as a nibble, byte 0 in bit 0: the four products land on bits 21..24 and nothing carries */
 __device__ __forceinline__ uint32_t nibbleOf(uint32_t m) { return (((m >> 7) * 0x00204081u) >> 21) & 0xFu; }

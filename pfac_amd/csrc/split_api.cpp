@@ -2,7 +2,7 @@
  * split_api.cpp -- PFACX_splitFromDevice / ...FromHost (include/pfac_ext.h): the offsets that cut a buffer into records at the bytes of a class --
  * what the batch, rules, count-batch and groups calls take as d_offsets, made where the text lies.
  *
- * Position c of [1, n - 1] is a cut by its own byte and the byte in front of it (the four flag combinations: cutAt below).  The device form is the
+ * Position c of [1, n - 1] is a cut by its own byte and the byte in front of it (the four flag combinations: pfac_host.h isCut).  The device form is the
  * passes of scan_split.hip (PFACX_splitRun) over the handle's split scratch (pfac::DeviceScratch::split: counted by PFACX_getInfo, freed by
  * PFACX_trim with every other scratch buffer).  The host form is the loop below on every platform; a class of one byte finds its delimiters with
  * memchr.  Neither needs a pattern set, neither folds: the class is tested on the caller's bytes.
@@ -16,11 +16,6 @@
 #include "pfac_host.h"
 
 namespace pfac_internal {
-
-/* {'\n'}: the class of a null h_class */
-static const unsigned int kNewlineClass[8] = {1u << '\n', 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-
-static bool inClass(const unsigned int *cls, unsigned char b) { return (cls[b >> 5] >> (b & 31u)) & 1u; }
 
 /* what both calls check first */
 static PFAC_status_t checkSplitArgs(PFAC_handle_t handle, const void *input, unsigned int flags, const size_t *offsets, size_t capacity,
@@ -67,7 +62,7 @@ static size_t splitOnHost(const unsigned char *in, size_t n, const unsigned int 
         bool a = inClass(cls, in[0]);                                      /* the byte in front of c is a delimiter */
         for (size_t c = 1; c < n; c++) {
             const bool b = inClass(cls, in[c]);
-            if (runs ? (before ? b && !a : a && !b) : (before ? b : a)) cut(c);
+            if (isCut(flags, a, b)) cut(c);
             a = b;
         }
     }

@@ -20,8 +20,6 @@ namespace pfac_internal {
 /* [0-9A-Za-z_]: the class of a null h_class */
 static const unsigned int kWordClass[8] = {0u, 0x03FF0000u, 0x87FFFFFEu, 0x07FFFFFEu, 0u, 0u, 0u, 0u};
 
-static bool inClass(const unsigned int *cls, unsigned char b) { return (cls[b >> 5] >> (b & 31u)) & 1u; }
-
 /* what all three calls check first */
 static PFAC_status_t checkWordsArgs(PFAC_handle_t handle, const void *input, size_t size, unsigned int flags, const size_t *h_num_matched)
 {

@@ -26,7 +26,8 @@
  * the offsets that cut a buffer into the segments of a batch at the bytes
  * of a delimiter class (PFACX_splitFromDevice / ...FromHost) and the record
  * and column of every match by the same cuts (PFACX_locatePairs*,
- * PFACX_matchLocated*).
+ * PFACX_matchLocated*) and the value behind every match
+ * (PFACX_capturePairs*, PFACX_matchCaptured*).
  */
 #ifndef PFAC_EXT_H_
 #define PFAC_EXT_H_
@@ -1128,6 +1129,71 @@ PFAC_status_t PFACX_matchLocatedFromDevice(PFAC_handle_t handle, char *d_input, 
 PFAC_status_t PFACX_matchLocatedFromHost  (PFAC_handle_t handle, char *h_input, size_t size, const unsigned int *h_class /* 8 words or NULL */,
                                            unsigned int flags, int *h_ids, int *h_pos /* size entries each */, int *h_record,
                                            int *h_column /* may be NULL */, size_t locCapacity, int *h_num_matched);
+
+/* Capture: the value behind every match -- what a log or protocol user wants from a key like `Host: `, `user=`, `"session_id":"` or
+ * `Content-Length:`: the bytes from the end of the match up to the next delimiter, with any blanks in front of the value skipped.  The patterns are
+ * the keys, these calls give the (start, length) of the values on the device, and PFACX_gatherLinesFromDevice writes them as text: two calls, no
+ * host round trip.
+ *   INPUTS.  input[0, n), 0 < n < 2^31.  A pair list (id_k, pos_k), k < numPairs < 2^31: positions non-decreasing, equal neighbours allowed; every
+ *   list the library returns is accepted (reduce, matchAll, words, disjoint, groups).  A skip class S: `h_skip`, 8 words of HOST memory, copied;
+ *   NULL: the empty class.  A stop class D: `h_stop`, 8 words of HOST memory, copied; NULL: {'\n'}.  Bits are laid out exactly as for PFACX_split*.
+ *   `window`, a size_t; 0: unbounded.  `flags`.  Both classes are tested on the caller's bytes: a caseless handle folds nothing here.  A byte that is
+ *   in both classes counts as a stop byte only: the library uses S \ D, computed once on the host.
+ *   FOR PAIR k:
+ *     1. If pos_k is outside [0, n), then valStart[k] = -1 and valLen[k] = 0.  The same holds without PFACX_CAPTURE_AT_POS when id_k is outside
+ *        [1, F] (F: the number of patterns).  The negative positions of streams and flows, and a caller's bad list, therefore give nothing.
+ *     2. b = pos_k + len(id_k), where len(id_k) is the length of pattern id_k.  With PFACX_CAPTURE_AT_POS, b = pos_k.  Then b = min(b, n).
+ *     3. w = n if window == 0, else min(n, b + window).  The pair never looks at a byte at or beyond w.
+ *     4. s is the smallest position in [b, w) whose byte is not in S \ D.  If there is none, s = w.
+ *     5. e is the smallest position in [s, w) whose byte is in D.  If there is none, e = w.
+ *     6. valStart[k] = s and valLen[k] = e - s.  Zero is a legal length: an empty value, or a window spent on blanks.
+ *   PFACX_CAPTURE_AT_POS uses the position as it is: ids may be NULL, the call needs no pattern set, and pos_k == n is then still outside [0, n) and
+ *   falls under rule 1.  Any other flag bit: PFAC_STATUS_INVALID_PARAMETER.
+ *   CONSEQUENCES: the stop byte is never part of the value.  With S empty, window == 0 and the default D, valStart + valLen is the position of the
+ *   '\n' that ends the line of b; if the line has none, it is n.  D = {'\r', '\n'} handles CRLF.
+ *   PFACX_gatherLinesFromDevice(d_input, size, d_valStart, d_valLen, numPairs, ...) writes the values as text, one per line; entries with
+ *   valStart == -1 come out as empty lines (that call clamps: -1 becomes offset 0, and the length is 0).
+ * THE PAIRS FORMS.  numPairs == 0 or size == 0: success, no array is touched.  PFAC_STATUS_INVALID_PARAMETER: a null handle or input; a null pos,
+ * valStart or valLen with numPairs > 0; null ids without PFACX_CAPTURE_AT_POS; size or numPairs >= 2^31; an unknown flag.  Without
+ * PFACX_CAPTURE_AT_POS a handle with no pattern set: PFAC_STATUS_PATTERNS_NOT_READY.  The device form on a host-only handle:
+ * PFAC_STATUS_LIB_NOT_EXIST.  The arrays are the caller's contract (device memory in the device form): a list that is not non-decreasing gets
+ * unspecified values, but never an access outside input[0, size), the list, or the outputs' numPairs entries.  The output arrays must not overlap the
+ * list.  The calls are synchronous and take the handle's lock.  The host form is a host loop on every platform.
+ * THE SCAN FORMS are PFAC_matchFromDeviceReduce (on the host: the same longest pairs) followed by the capture of the first min(count, capCapacity)
+ * pairs: ids and pos (`size` entries each) are exactly what that call returns, valStart and valLen belong to those pairs.  More pairs than
+ * capCapacity: exactly the first capCapacity entries are written, *h_num_matched is the full count and the call returns
+ * PFACX_STATUS_OUTPUT_TRUNCATED (capCapacity == 0: both arrays may be null).  PFACX_CAPTURE_AT_POS is accepted.  A caseless handle folds for the match
+ * and never for the classes.  Error cases are those of PFAC_matchFromDeviceReduce, plus the flag check and a null valStart or valLen with
+ * capCapacity > 0.  The host form follows PFAC_setPlatform as PFACX_matchLocatedFromHost does.
+ * MEMORY of the device forms: grow-only handle scratch sized by the number of tiles alone -- with T = ceil(size / 16384): 4 T + 8 bytes, each term
+ * rounded up to 256, whatever the data and however many pairs; without PFACX_CAPTURE_AT_POS also the device copy of the pattern lengths that the
+ * batch and spans calls share (4 bytes per pattern).  Counted under deviceScratchBytes of PFACX_getInfo, freed by PFACX_trim, not allocated before
+ * the first capture call.
+ * COST: no pass over the whole input.  A launch over the tiles' first-pair words, a launch over the list, and one read of only the
+ * tiles of 16 KiB that hold a pair, each with the 1 KiB behind it; 8 bytes read (4 with PFACX_CAPTURE_AT_POS) plus one gathered length and 8 written
+ * per pair.  A value that starts or ends more than 1 KiB behind its pair's tile is finished on the input itself, a pair alone: an unbounded window on
+ * hostile input (no stop byte, or nothing but skip bytes) costs up to the rest of the buffer per pair.  Callers with untrusted input set a window.
+ * OUT OF SCOPE: values in front of a match; quoted values and escapes; trimming trailing blanks; multi-byte stops; converting a value to a number;
+ * per-segment bounds of a batch (a stop class that contains the record delimiter gives the same effect); the pairs of streams and flows;
+ * device-resident classes; unsorted lists; a flag telling "ended at the window" from "ended at a stop byte" (the caller tests
+ * input[valStart + valLen]). */
+#define PFACX_CAPTURE_AT_POS 1u
+PFAC_status_t PFACX_capturePairsFromDevice(PFAC_handle_t handle, const char *d_input, size_t size, const unsigned int *h_skip /* 8 words or NULL */,
+                                           const unsigned int *h_stop /* 8 words or NULL */, size_t window, unsigned int flags,
+                                           const int *d_ids /* NULL with PFACX_CAPTURE_AT_POS */, const int *d_pos, size_t numPairs, int *d_valStart,
+                                           int *d_valLen);
+PFAC_status_t PFACX_capturePairsFromHost  (PFAC_handle_t handle, const char *h_input, size_t size, const unsigned int *h_skip /* 8 words or NULL */,
+                                           const unsigned int *h_stop /* 8 words or NULL */, size_t window, unsigned int flags,
+                                           const int *h_ids /* NULL with PFACX_CAPTURE_AT_POS */, const int *h_pos, size_t numPairs, int *h_valStart,
+                                           int *h_valLen);
+PFAC_status_t PFACX_matchCapturedFromDevice(PFAC_handle_t handle, char *d_input, size_t size, const unsigned int *h_skip /* 8 words or NULL */,
+                                            const unsigned int *h_stop /* 8 words or NULL */, size_t window, unsigned int flags, int *d_ids,
+                                            int *d_pos /* size entries each */, int *d_valStart, int *d_valLen, size_t capCapacity,
+                                            int *h_num_matched);
+PFAC_status_t PFACX_matchCapturedFromHost  (PFAC_handle_t handle, char *h_input, size_t size, const unsigned int *h_skip /* 8 words or NULL */,
+                                            const unsigned int *h_stop /* 8 words or NULL */, size_t window, unsigned int flags, int *h_ids,
+                                            int *h_pos /* size entries each */, int *h_valStart, int *h_valLen, size_t capCapacity,
+                                            int *h_num_matched);
 
 #ifdef __cplusplus
 }

@@ -396,6 +396,35 @@ typedef struct {
 } PFACX_locateRun_t;
 PFAC_status_t PFACX_locateRun(PFAC_handle_t handle, const PFACX_locateRun_t *run, size_t *h_numRecords);
 
+/* Capture (no reference counterpart; include/pfac_ext.h: PFACX_capture*), scan_capture.hip.
+ * PFACX_captureRun: for the pairs (d_ids[i], d_pos[i]), i < numPairs (positions non-decreasing; 0 < numPairs < 2^31) in d_input[0, size),
+ * 0 < size < 2^31, the value behind the match by the six rules of the header: b = the position + d_patternLen[id] (PFACX_CAPTURE_AT_POS: the
+ * position itself; d_ids and d_patternLen may then be null), never beyond size; w = size, or min(size, b + window) for window != 0; d_valStart[i]
+ * = the first position of [b, w) whose byte is not in `skip`, d_valStart[i] + d_valLen[i] = the first position from there on whose byte is in
+ * `stop`; w where there is none.  (-1, 0) for a position outside [0, size) and, without the flag, for an id outside [1, numLens - 1].  `skip` is
+ * S \ D already: the caller takes the stop bytes out of it.  d_patternLen: numLens = F + 1 lengths by id (the handle's device copy).
+ * *h_slowPairs = the pairs that left the bitmap of their tile and finished on the input itself.  The list is never trusted: a list that is not
+ * non-decreasing gets unspecified values and no access outside the input, the list, the lengths and the outputs' numPairs entries.  Only tiles of
+ * 16 KiB that hold a position are read; scratch: the handle's capture scratch, sized by the tiles alone (scan_capture.hip has the formula).
+ * Synchronous. */
+#define PFACX_CAPTURE_REACH 1024u      /* bytes behind a tile that its bitmap covers (scan_capture.hip: kCaptureReach; pfac_amd/api.py) */
+typedef struct {
+    const char *d_input;
+    size_t size;
+    unsigned int skip[8];
+    unsigned int stop[8];
+    size_t window;
+    unsigned int flags;
+    const int *d_ids;
+    const int *d_pos;
+    size_t numPairs;
+    const int *d_patternLen;
+    size_t numLens;
+    int *d_valStart;
+    int *d_valLen;
+} PFACX_captureRun_t;
+PFAC_status_t PFACX_captureRun(PFAC_handle_t handle, const PFACX_captureRun_t *run, size_t *h_slowPairs);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -411,7 +440,7 @@ PFAC_status_t PFACX_locateRun(PFAC_handle_t handle, const PFACX_locateRun_t *run
     X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun) \
     X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun) X(segcount_run_ptr, PFACX_segCountRun) \
     X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun) X(split_run_ptr, PFACX_splitRun) \
-    X(locate_run_ptr, PFACX_locateRun)
+    X(locate_run_ptr, PFACX_locateRun) X(capture_run_ptr, PFACX_captureRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

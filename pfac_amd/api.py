@@ -39,6 +39,8 @@ PFACX_SPLIT_RUNS = 2                            # ... a maximal run of delimiter
 PFACX_SPLIT_TILE = 16384                        # scan_split.hip: kSplitTile, the input bytes one block of the split passes takes at a time (never more than eight blocks per CU a pass)
 PFACX_SPLIT_SCAN_STEP = 1024                    # scan_passes.h: pfac_array_scan, the per-tile counts its one block takes per step
 PFACX_LOCATE_CARRY_STEP = 1024                  # scan_locate.hip: pfac_locate_carry, the tiles its one block takes per step (the step of pfac_array_scan)
+PFACX_CAPTURE_AT_POS = 1                        # pfac_ext.h: PFACX_capture* the value starts at the position itself: no ids, no pattern set
+PFACX_CAPTURE_REACH = 1024                      # scan_capture.hip: kCaptureReach, the bytes behind a tile of PFACX_SPLIT_TILE bytes that the tile's bitmaps cover; behind them the slow path
 PFACX_SPLIT_LONGEST_STEP = 4096                 # scan_split.hip: pfac_split_longest, the tiles its one block takes per step (kSplitPerThread a thread)
 PFACX_DISJOINT_BLOCK = 512                      # scan_disjoint.hip: kDisjointBlock, the pairs one block of the selection takes
 PFACX_REPLACE_TILE = 4096                       # scan_disjoint.hip: kReplaceTile, the output bytes of one tile of the replacement
@@ -151,6 +153,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_groupsOpen", "PFACX_groupsClose", "PFACX_groupsMatchFromDevice", "PFACX_groupsMatchFromHost", "PFACX_groupsPairsFromDevice",
     "PFACX_splitFromDevice", "PFACX_splitFromHost",
     "PFACX_locatePairsFromDevice", "PFACX_locatePairsFromHost", "PFACX_matchLocatedFromDevice", "PFACX_matchLocatedFromHost",
+    "PFACX_capturePairsFromDevice", "PFACX_capturePairsFromHost", "PFACX_matchCapturedFromDevice", "PFACX_matchCapturedFromHost",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -169,6 +172,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_flowRulesRun",
     "PFACX_splitRun",
     "PFACX_locateRun",
+    "PFACX_captureRun",
 )
 
 
@@ -339,6 +343,15 @@ def load_library() -> C.CDLL:
                    C.POINTER(C.c_int)]
         lib.PFACX_matchLocatedFromDevice.argtypes = located
         lib.PFACX_matchLocatedFromHost.argtypes = located
+    if hasattr(lib, "PFACX_capturePairsFromDevice"):
+        CLS = C.POINTER(C.c_uint)
+        pairs = [H, C.c_void_p, C.c_size_t, CLS, CLS, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.PFACX_capturePairsFromDevice.argtypes = pairs
+        lib.PFACX_capturePairsFromHost.argtypes = pairs
+        captured = [H, C.c_void_p, C.c_size_t, CLS, CLS, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                    C.POINTER(C.c_int)]
+        lib.PFACX_matchCapturedFromDevice.argtypes = captured
+        lib.PFACX_matchCapturedFromHost.argtypes = captured
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -933,6 +946,44 @@ class PFAC:
         st, n = self.locatePairsFromHost(buf.ctypes.data, data.size, cls, flags, pos.ctypes.data if pos.size else None, pos.size,
                                          record.ctypes.data, column.ctypes.data)
         return record[:pos.size], column[:pos.size], n
+
+    # -- the value behind every match (include/pfac_ext.h: PFACX_capturePairs*, PFACX_matchCaptured*) ----------------
+    def _capture_pairs(self, name: str, input_, size: int, skip, stop, window: int, flags: int, ids, pos, num_pairs: int, val_start, val_len, check: bool):
+        st = getattr(self._lib, name)(self._h, input_, size, _class_arg(skip), _class_arg(stop), window, flags, ids, pos, num_pairs, val_start, val_len)
+        return self._ret(st, name, check)
+
+    def capturePairsFromDevice(self, d_input: int, size: int, skip, stop, window: int, flags: int, d_ids, d_pos, num_pairs: int, d_val_start,
+                               d_val_len, check: bool = True) -> int:
+        """``PFACX_capturePairsFromDevice`` -> status; `skip`, `stop`: word_class(...), bytes, or None (the empty class; {'\n'}); `window` 0:
+        unbounded; `d_ids` (may be None with PFACX_CAPTURE_AT_POS), `d_pos`, `d_val_start`, `d_val_len` (``int``, device): num_pairs entries each."""
+        return self._capture_pairs("PFACX_capturePairsFromDevice", d_input, size, skip, stop, window, flags, d_ids, d_pos, num_pairs, d_val_start,
+                                   d_val_len, check)
+
+    def capturePairsFromHost(self, h_input: int, size: int, skip, stop, window: int, flags: int, h_ids, h_pos, num_pairs: int, h_val_start,
+                             h_val_len, check: bool = True) -> int:
+        """``PFACX_capturePairsFromHost``: the same over host memory, a host loop on every platform."""
+        return self._capture_pairs("PFACX_capturePairsFromHost", h_input, size, skip, stop, window, flags, h_ids, h_pos, num_pairs, h_val_start,
+                                   h_val_len, check)
+
+    def _match_captured(self, name: str, input_, size: int, skip, stop, window: int, flags: int, ids, pos, val_start, val_len, cap_capacity: int,
+                        check: bool):
+        n = C.c_int(0)
+        st = getattr(self._lib, name)(self._h, input_, size, _class_arg(skip), _class_arg(stop), window, flags, ids, pos, val_start, val_len,
+                                      cap_capacity, C.byref(n))
+        return self._ret(st, name, check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def matchCapturedFromDevice(self, d_input: int, size: int, skip, stop, window: int, flags: int, d_ids, d_pos, d_val_start, d_val_len,
+                                cap_capacity: int, check: bool = True):
+        """``PFACX_matchCapturedFromDevice`` -> (status, number of pairs): `d_ids`, `d_pos` size entries each as for matchFromDeviceReduce,
+        `d_val_start`, `d_val_len` cap_capacity entries each.  OUTPUT_TRUNCATED is returned, not raised."""
+        return self._match_captured("PFACX_matchCapturedFromDevice", d_input, size, skip, stop, window, flags, d_ids, d_pos, d_val_start, d_val_len,
+                                    cap_capacity, check)
+
+    def matchCapturedFromHost(self, h_input: int, size: int, skip, stop, window: int, flags: int, h_ids, h_pos, h_val_start, h_val_len,
+                              cap_capacity: int, check: bool = True):
+        """``PFACX_matchCapturedFromHost``: the same over host memory; follows PFAC_setPlatform."""
+        return self._match_captured("PFACX_matchCapturedFromHost", h_input, size, skip, stop, window, flags, h_ids, h_pos, h_val_start, h_val_len,
+                                    cap_capacity, check)
 
     # -- input that arrives in pieces (include/pfac_ext.h: PFACX_stream*) ----------------
     def streamOpen(self, check: bool = True) -> "Stream":

@@ -54,6 +54,11 @@ RULE_SEQ_MEMBER_FIELDS = RULE_MEMBER_FIELDS + [("distance", "<u4"), ("within", "
 PFACX_BATCH_BLOCK = 256                         # scan_batch.hip: kBatchBlock, the lanes of a block of every batch fix-up kernel (a block of pairs of the compacted form)
 PFACX_BATCH_SEGS_PER_TRIP = 8                   # scan_batch.hip: kSegsPerTrip, the consecutive segments a group of pfac_batch_fixup takes per trip
 PFACX_BATCH_MAX_GROUP_LOG2 = 6                  # scan_batch.hip: the `groupLog2 < 6` loop of PFACX_batchFixup, at most 64 lanes per segment
+PFACX_FLOWS_PIECE_BLOCK = 256                   # scan_flows.hip: kPieceBlock, the pieces one block of pfac_flows_count / pfac_flows_first takes (and the block sums pfac_flows_sums takes per trip)
+PFACX_FLOWS_WAVE_SEAM_MAX = 64                  # scan_flows.hip: kWaveSeamMax, M - 1 up to here takes the wave-per-piece seam, above it the block-per-piece seam
+PFACX_FLOWS_WAVE_SEAM_PIECES = 4                # scan_flows.hip: kWaveSeamWaves, the pieces (waves) of one block of pfac_flows_seam_wave
+PFACX_STREAM_SEAM_BLOCK = 1024                  # scan_flows.hip, scan_stream.hip: kSeamBlock, the most threads of a seam block: the carried positions seamBlock takes per trip
+PFACX_STREAM_SEAM_LDS = 49152                   # pfac_context.h: pfac::kStreamSeamLdsBytes, a seam of more than this many bytes (2 (M - 1)) is staged in device scratch
 PFACX_RULES_BLOCK_PAIRS = 256                   # scan_rules.hip: kRulesBlockPairs, the pairs a block takes from a segment in one go
 PFACX_FLOWRULES_WINDOW = 8192                   # scan_flowrules.hip: kFlowRulesWindow, the rules whose masks a block keeps in LDS at a time
 PFACX_FLOWRULES_TOUCHED = 1024                  # scan_flowrules.hip: kFlowRulesTouched, the touched-list length; a piece that touches more rules of a window sweeps the whole table

@@ -19,20 +19,13 @@
 
 namespace pfac_internal {
 
-/* the classes of a call as both forms use them: skip = S \ D (null S: empty), stop = D (null: {'\n'}); stopByte: the one member of D, -1: not one */
+/* the classes of a call as both forms use them: stop = D (null: {'\n'}), skip = S \ D (null S: empty) */
 struct CaptureClasses {
-    unsigned int skip[8], stop[8];
-    int stopByte;
-    CaptureClasses(const unsigned int *h_skip, const unsigned int *h_stop)
+    const ByteClass stop;
+    unsigned int skip[8];
+    CaptureClasses(const unsigned int *h_skip, const unsigned int *h_stop) : stop(h_stop)
     {
-        int members = 0, only = -1;
-        for (int k = 0; k < 8; k++) {
-            stop[k] = (h_stop ? h_stop : kNewlineClass)[k];
-            skip[k] = h_skip ? h_skip[k] & ~stop[k] : 0u;
-            members += __builtin_popcount(stop[k]);
-            if (stop[k]) only = k * 32 + __builtin_ctz(stop[k]);
-        }
-        stopByte = members == 1 ? only : -1;
+        for (int k = 0; k < 8; k++) skip[k] = h_skip ? h_skip[k] & ~stop.words[k] : 0u;
     }
 };
 
@@ -71,11 +64,11 @@ static void captureOnHost(const unsigned char *in, size_t n, const CaptureClasse
         size_t s = b;
         while (s < w && inClass(cls.skip, in[s])) s++;
         size_t e = s;
-        if (cls.stopByte >= 0) {
-            const void *hit = s < w ? std::memchr(in + s, cls.stopByte, w - s) : nullptr;
+        if (cls.stop.members == 1) {
+            const void *hit = s < w ? std::memchr(in + s, (int)cls.stop.only, w - s) : nullptr;
             e = hit ? (size_t)(static_cast<const unsigned char *>(hit) - in) : w;
         } else {
-            while (e < w && !inClass(cls.stop, in[e])) e++;
+            while (e < w && !inClass(cls.stop.words, in[e])) e++;
         }
         valStart[k] = (int)s;
         valLen[k] = (int)(e - s);
@@ -89,10 +82,8 @@ static PFAC_status_t captureOnDevice(PFAC_context *c, const char *d_input, size_
     PFACX_captureRun_t run{};
     run.d_input = d_input;
     run.size = size;
-    for (int k = 0; k < 8; k++) {
-        run.skip[k] = cls.skip[k];
-        run.stop[k] = cls.stop[k];
-    }
+    for (int k = 0; k < 8; k++) run.skip[k] = cls.skip[k];
+    cls.stop.copyTo(run.stop);
     run.window = window;
     run.flags = flags;
     run.d_pos = d_pos;
@@ -111,15 +102,10 @@ static PFAC_status_t captureOnDevice(PFAC_context *c, const char *d_input, size_
     return c->capture_run_ptr(c, &run, &slowPairs);
 }
 
-/* what both scan forms check first: the checks of PFAC_matchFromDeviceReduce in its order, and the flags */
-static PFAC_status_t checkMatchCapturedArgs(PFAC_handle_t handle, const void *input, const int *ids, const int *pos, const int *valStart, const int *valLen,
-                                            size_t capCapacity, unsigned int flags, const int *h_num_matched)
+/* what both scan forms check of their own arguments (pfac_host.h: scanForm) */
+static bool matchCapturedArgsOk(const int *valStart, const int *valLen, size_t capCapacity, unsigned int flags)
 {
-    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
-    if (!input || !ids || !pos || !h_num_matched || (capCapacity && (!valStart || !valLen)) || (flags & ~PFACX_CAPTURE_AT_POS))
-        return PFAC_STATUS_INVALID_PARAMETER;
-    return PFAC_STATUS_SUCCESS;
+    return !(capCapacity && (!valStart || !valLen)) && !(flags & ~PFACX_CAPTURE_AT_POS);
 }
 
 } // namespace pfac_internal
@@ -162,48 +148,25 @@ PFAC_status_t PFACX_matchCapturedFromDevice(PFAC_handle_t handle, char *d_input,
                                             size_t window, unsigned int flags, int *d_ids, int *d_pos, int *d_valStart, int *d_valLen, size_t capCapacity,
                                             int *h_num_matched)
 {
-    PFAC_status_t st = checkMatchCapturedArgs(handle, d_input, d_ids, d_pos, d_valStart, d_valLen, capCapacity, flags, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
-    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
-    const CaptureClasses cls(h_skip, h_stop);
-    std::lock_guard<std::mutex> guard(handle->lock);
-    DeviceScan scan;                                                       /* a caseless set: the scan reads the folded copy, the capture passes the caller's bytes */
-    st = beginDeviceScan(handle, d_input, size, &scan);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    int count = 0;
-    st = reduceOnDevice(handle, scan.d_scan, size, d_ids, d_pos, true, &count);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
-    *h_num_matched = count;
-    const size_t captured = (size_t)count < capCapacity ? (size_t)count : capCapacity;
-    if (captured) {
-        st = captureOnDevice(handle, d_input, size, cls, window, flags, d_ids, d_pos, captured, d_valStart, d_valLen);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-    }
-    return truncatedIf((unsigned long long)count, capCapacity);
+    return scanForm<DevicePairs>(handle, d_input, size, d_ids, d_pos, matchCapturedArgsOk(d_valStart, d_valLen, capCapacity, flags), capCapacity, h_num_matched,
+                          [&](size_t captured) {
+                              return captureOnDevice(handle, d_input, size, CaptureClasses(h_skip, h_stop), window, flags, d_ids, d_pos, captured,
+                                                     d_valStart, d_valLen);
+                          });
 }
 
 PFAC_status_t PFACX_matchCapturedFromHost(PFAC_handle_t handle, char *h_input, size_t size, const unsigned int *h_skip, const unsigned int *h_stop,
                                           size_t window, unsigned int flags, int *h_ids, int *h_pos, int *h_valStart, int *h_valLen, size_t capCapacity,
                                           int *h_num_matched)
 {
-    const PFAC_status_t st = checkMatchCapturedArgs(handle, h_input, h_ids, h_pos, h_valStart, h_valLen, capCapacity, flags, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
-    const CaptureClasses cls(h_skip, h_stop);
-    const PinnedPairs pairs(handle, h_input, size, h_ids, h_pos);          /* the lengths are read from the set the pairs came from */
-    if (pairs.status != PFAC_STATUS_SUCCESS) return pairs.status;
-    if (pairs.count < 0 || (size_t)pairs.count > size) return PFAC_STATUS_INTERNAL_ERROR;
-    *h_num_matched = pairs.count;
-    const size_t captured = (size_t)pairs.count < capCapacity ? (size_t)pairs.count : capCapacity;
-    const pfac::Automaton &fa = handle->fa;
-    if (captured)
-        captureOnHost(reinterpret_cast<const unsigned char *>(h_input), size, cls, window, flags, fa.patternLen.data(),
-                      fa.patternLen.empty() ? 0 : fa.patternLen.size() - 1, h_ids, h_pos, captured, h_valStart, h_valLen);
-    return truncatedIf((unsigned long long)pairs.count, capCapacity);
+    return scanForm<PinnedPairs>(handle, h_input, size, h_ids, h_pos, matchCapturedArgsOk(h_valStart, h_valLen, capCapacity, flags), capCapacity, h_num_matched,
+                        [&](size_t captured) {                             /* under the pin: the lengths are read from the set the pairs came from */
+                            const pfac::Automaton &fa = handle->fa;
+                            captureOnHost(reinterpret_cast<const unsigned char *>(h_input), size, CaptureClasses(h_skip, h_stop), window, flags,
+                                          fa.patternLen.data(), fa.patternLen.empty() ? 0 : fa.patternLen.size() - 1, h_ids, h_pos, captured,
+                                          h_valStart, h_valLen);
+                            return PFAC_STATUS_SUCCESS;
+                        });
 }
 
 } /* extern "C" */

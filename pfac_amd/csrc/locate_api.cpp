@@ -57,15 +57,19 @@ static size_t locateOnHost(const unsigned char *in, size_t n, const unsigned int
     return cuts + 1;
 }
 
-/* what both scan forms check first: the checks of PFAC_matchFromDeviceReduce in its order, and the flags */
-static PFAC_status_t checkMatchLocatedArgs(PFAC_handle_t handle, const void *input, const int *ids, const int *pos, const int *record, size_t locCapacity,
-                                           unsigned int flags, const int *h_num_matched)
+/* what both scan forms check of their own arguments (pfac_host.h: scanForm) */
+static bool matchLocatedArgsOk(const int *record, size_t locCapacity, unsigned int flags)
 {
-    if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!handle->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
-    if (!input || !ids || !pos || !h_num_matched || (locCapacity && !record) || (flags & ~(PFACX_SPLIT_BEFORE | PFACX_SPLIT_RUNS)))
-        return PFAC_STATUS_INVALID_PARAMETER;
-    return PFAC_STATUS_SUCCESS;
+    return !(locCapacity && !record) && !(flags & ~(PFACX_SPLIT_BEFORE | PFACX_SPLIT_RUNS));
+}
+
+/* the device passes over a list (the caller holds the lock and has checked the module) */
+static PFAC_status_t locateOnDevice(PFAC_context *c, const char *d_input, size_t size, const unsigned int *h_class, unsigned int flags, const int *d_pos,
+                                    size_t numPairs, int *d_record, int *d_column, size_t *records)
+{
+    PFACX_locateRun_t run{d_input, size, {}, flags, d_pos, numPairs, d_record, d_column};
+    ByteClass(h_class).copyTo(run.cls);
+    return c->locate_run_ptr(c, &run, records);
 }
 
 } // namespace pfac_internal
@@ -85,17 +89,8 @@ PFAC_status_t PFACX_locatePairsFromDevice(PFAC_handle_t handle, const char *d_in
     if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     if (numPairs == 0 && !h_numRecords) return PFAC_STATUS_SUCCESS;
     std::lock_guard<std::mutex> guard(handle->lock);
-    PFACX_locateRun_t run{};
-    run.d_input = d_input;
-    run.size = size;
-    for (int k = 0; k < 8; k++) run.cls[k] = (h_class ? h_class : kNewlineClass)[k];
-    run.flags = flags;
-    run.d_pos = d_pos;
-    run.numPairs = numPairs;
-    run.d_record = d_record;
-    run.d_column = d_column;
     size_t records = 0;
-    const PFAC_status_t ran = handle->locate_run_ptr(handle, &run, &records);
+    const PFAC_status_t ran = locateOnDevice(handle, d_input, size, h_class, flags, d_pos, numPairs, d_record, d_column, &records);
     if (ran == PFAC_STATUS_SUCCESS && h_numRecords) *h_numRecords = records;
     return ran;
 }
@@ -110,10 +105,9 @@ PFAC_status_t PFACX_locatePairsFromHost(PFAC_handle_t handle, const char *h_inpu
         return PFAC_STATUS_SUCCESS;
     }
     if (numPairs == 0 && !h_numRecords) return PFAC_STATUS_SUCCESS;
-    unsigned int cls[8];
-    for (int k = 0; k < 8; k++) cls[k] = (h_class ? h_class : kNewlineClass)[k];
+    const ByteClass cls(h_class);
     std::lock_guard<std::mutex> guard(handle->lock);
-    const size_t records = locateOnHost(reinterpret_cast<const unsigned char *>(h_input), size, cls, flags, h_pos, numPairs, h_record, h_column,
+    const size_t records = locateOnHost(reinterpret_cast<const unsigned char *>(h_input), size, cls.words, flags, h_pos, numPairs, h_record, h_column,
                                         h_numRecords != nullptr);
     if (h_numRecords) *h_numRecords = records;
     return PFAC_STATUS_SUCCESS;
@@ -122,55 +116,22 @@ PFAC_status_t PFACX_locatePairsFromHost(PFAC_handle_t handle, const char *h_inpu
 PFAC_status_t PFACX_matchLocatedFromDevice(PFAC_handle_t handle, char *d_input, size_t size, const unsigned int *h_class, unsigned int flags, int *d_ids,
                                            int *d_pos, int *d_record, int *d_column, size_t locCapacity, int *h_num_matched)
 {
-    PFAC_status_t st = checkMatchLocatedArgs(handle, d_input, d_ids, d_pos, d_record, locCapacity, flags, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
-    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
-    std::lock_guard<std::mutex> guard(handle->lock);
-    DeviceScan scan;                                                       /* a caseless set: the scan reads the folded copy, the locate passes the caller's bytes */
-    st = beginDeviceScan(handle, d_input, size, &scan);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    int count = 0;
-    st = reduceOnDevice(handle, scan.d_scan, size, d_ids, d_pos, true, &count);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
-    *h_num_matched = count;
-    const size_t located = (size_t)count < locCapacity ? (size_t)count : locCapacity;
-    if (located) {
-        PFACX_locateRun_t run{};
-        run.d_input = d_input;
-        run.size = size;
-        for (int k = 0; k < 8; k++) run.cls[k] = (h_class ? h_class : kNewlineClass)[k];
-        run.flags = flags;
-        run.d_pos = d_pos;
-        run.numPairs = located;
-        run.d_record = d_record;
-        run.d_column = d_column;
-        size_t records = 0;
-        st = handle->locate_run_ptr(handle, &run, &records);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-    }
-    return truncatedIf((unsigned long long)count, locCapacity);
+    return scanForm<DevicePairs>(handle, d_input, size, d_ids, d_pos, matchLocatedArgsOk(d_record, locCapacity, flags), locCapacity, h_num_matched,
+                          [&](size_t located) {
+                              size_t records = 0;
+                              return locateOnDevice(handle, d_input, size, h_class, flags, d_pos, located, d_record, d_column, &records);
+                          });
 }
 
 PFAC_status_t PFACX_matchLocatedFromHost(PFAC_handle_t handle, char *h_input, size_t size, const unsigned int *h_class, unsigned int flags, int *h_ids,
                                          int *h_pos, int *h_record, int *h_column, size_t locCapacity, int *h_num_matched)
 {
-    PFAC_status_t st = checkMatchLocatedArgs(handle, h_input, h_ids, h_pos, h_record, locCapacity, flags, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
-    int count = 0;
-    st = hostLongestPairs(handle, h_input, size, h_ids, h_pos, &count, nullptr);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
-    *h_num_matched = count;
-    const size_t located = (size_t)count < locCapacity ? (size_t)count : locCapacity;
-    if (located)
-        (void)locateOnHost(reinterpret_cast<const unsigned char *>(h_input), size, h_class ? h_class : kNewlineClass, flags, h_pos, located, h_record,
-                           h_column, false);
-    return truncatedIf((unsigned long long)count, locCapacity);
+    return scanForm<PinnedPairs>(handle, h_input, size, h_ids, h_pos, matchLocatedArgsOk(h_record, locCapacity, flags), locCapacity, h_num_matched,
+                        [&](size_t located) {
+                            (void)locateOnHost(reinterpret_cast<const unsigned char *>(h_input), size, ByteClass(h_class).words, flags, h_pos, located,
+                                               h_record, h_column, false);
+                            return PFAC_STATUS_SUCCESS;
+                        });
 }
 
 } /* extern "C" */

@@ -490,6 +490,24 @@ struct DeviceScratch {
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }
 };
 
+/* A class of bytes as the split, locate and capture calls take one (include/pfac_ext.h: bit b & 31 of word b >> 5: byte b is a member), for the host
+ * and the kernel module: the eight words -- `whenNull`'s for a null pointer; kNewlineClass: {'\n'} --, the number of members and, for a class of one,
+ * that member (`only`; of no meaning else): such a class every pass tests by a compare (memchr on the host, SINGLE on the device) */
+constexpr unsigned int kNewlineClass[8] = {1u << '\n', 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+struct ByteClass {
+    unsigned int words[8];
+    unsigned int members = 0, only = 0;
+    explicit ByteClass(const unsigned int *cls, const unsigned int *whenNull = kNewlineClass)
+    {
+        for (unsigned int k = 0; k < 8; k++) {
+            words[k] = (cls ? cls : whenNull)[k];
+            members += (unsigned int)__builtin_popcount(words[k]);
+            if (words[k]) only = k * 32u + (unsigned int)__builtin_ctz(words[k]);
+        }
+    }
+    void copyTo(unsigned int *out) const { for (unsigned int k = 0; k < 8; k++) out[k] = words[k]; }
+};
+
 } // namespace pfac
 
 namespace pfac_internal { struct HandleObject; }       /* pfac_host.h: the kernel module never looks inside one */

@@ -75,6 +75,7 @@ private:
 struct PinnedPairs {
     PinnedPairs(PFAC_context *c, char *in, size_t size, int *ids, int *pos) : status(hostLongestPairs(c, in, size, ids, pos, &count, &generation))
     { if (status == PFAC_STATUS_SUCCESS) status = pin.emplace(c, generation).status(); }
+    static constexpr bool needsModule = false;        /* scanForm: the GPU platform answers LIB_NOT_EXIST from inside the scan */
     int count = 0;
     unsigned long long generation = 0;
     PFAC_status_t status;                     /* (declared behind what its initialiser writes) */
@@ -98,10 +99,10 @@ inline bool lacksModule(const PFAC_context *c) { return !c->hasDevice || !c->mod
 inline bool hostLacksModule(const PFAC_context *c) { return c->platform == PFAC_PLATFORM_GPU && lacksModule(c); }
 /* the status of a call whose full list has `total` entries */
 inline PFAC_status_t truncatedIf(unsigned long long total, size_t capacity) { return total > capacity ? PFACX_STATUS_OUTPUT_TRUNCATED : PFAC_STATUS_SUCCESS; }
-/* The cuts of PFACX_split* on the host (split_api.cpp, locate_api.cpp).  kNewlineClass: {'\n'}, the class of a null h_class; inClass: byte b is in
- * the class; isCut: position c of [1, n - 1] is a cut, given a = (in[c - 1] is in the class) and b = (in[c] is) -- the four flag combinations of
- * the header in one place */
-constexpr unsigned int kNewlineClass[8] = {1u << '\n', 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+/* The cuts of PFACX_split* on the host (split_api.cpp, locate_api.cpp).  ByteClass (pfac_context.h): a caller's class, {'\n'} for a null h_class;
+ * inClass: byte b is in the class; isCut: position c of [1, n - 1] is a cut, given a = (in[c - 1] is in the class) and b = (in[c] is) -- the four
+ * flag combinations of the header in one place */
+using pfac::ByteClass;
 inline bool inClass(const unsigned int *cls, unsigned char b) { return (cls[b >> 5] >> (b & 31u)) & 1u; }
 inline bool isCut(unsigned int flags, bool a, bool b)
 {
@@ -202,6 +203,42 @@ inline PFAC_status_t reduceOnDevice(PFAC_context *c, char *d_in, size_t n, int *
     const PFAC_status_t st = fn(c, reinterpret_cast<int *>(d_in), (int)n, d_ids, d_pos, h_count, nullptr, nullptr);
     c->reduceUnordered = wasUnordered;
     return st;
+}
+/* the ordered longest pairs of a device buffer with c->lock held, as PinnedPairs has those of a host buffer with the set pinned */
+struct DevicePairs {
+    DevicePairs(PFAC_context *c, char *d_input, size_t size, int *d_ids, int *d_pos) : guard(c->lock)
+    {
+        DeviceScan scan;                                                   /* a caseless set: the scan reads the folded copy, a post-pass the caller's bytes */
+        status = beginDeviceScan(c, d_input, size, &scan);
+        if (status == PFAC_STATUS_SUCCESS) status = reduceOnDevice(c, scan.d_scan, size, d_ids, d_pos, true, &count);
+    }
+    static constexpr bool needsModule = true;
+    std::lock_guard<std::mutex> guard;
+    int count = 0;
+    PFAC_status_t status = PFAC_STATUS_SUCCESS;
+};
+/* The frame of a scan form with a post-pass over its pairs (PFACX_matchLocated*, PFACX_matchCaptured*), Pairs = DevicePairs: the device form, or
+ * PinnedPairs: the host form.  The checks of PFAC_matchFromDeviceReduce in its order -- the handle, a loaded set, the pointers and `restOk` (what
+ * the call checks of its own outputs and flags), size == 0, for the device form the module, size > kMaxInt --, then the pairs into ids / pos and
+ * their number to *h_num_matched; post(kept) over the first kept = min(count, capacity) > 0 of them while Pairs holds the lock or the pin, its
+ * status returned where it fails; OUTPUT_TRUNCATED where count > capacity */
+template <class Pairs, class Post>
+inline PFAC_status_t scanForm(PFAC_context *c, char *input, size_t size, int *ids, int *pos, bool restOk, size_t capacity, int *h_num_matched,
+                              Post post)
+{
+    if (!c) return PFAC_STATUS_INVALID_HANDLE;
+    if (!c->isPatternsReady) return PFAC_STATUS_PATTERNS_NOT_READY;
+    if (!input || !ids || !pos || !h_num_matched || !restOk) return PFAC_STATUS_INVALID_PARAMETER;
+    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
+    if (Pairs::needsModule && lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
+    if (size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
+    const Pairs pairs(c, input, size, ids, pos);
+    if (pairs.status != PFAC_STATUS_SUCCESS) return pairs.status;
+    if (pairs.count < 0 || (size_t)pairs.count > size) return PFAC_STATUS_INTERNAL_ERROR;
+    *h_num_matched = pairs.count;
+    const size_t kept = (size_t)pairs.count < capacity ? (size_t)pairs.count : capacity;
+    const PFAC_status_t st = kept ? post(kept) : PFAC_STATUS_SUCCESS;
+    return st != PFAC_STATUS_SUCCESS ? st : truncatedIf((unsigned long long)pairs.count, capacity);
 }
 /* the non-zero results of the first `owned` entries of a full result vector as (id, position + posShift) pairs; ids may be the vector
  * itself (pair z comes from an entry at or behind z).  Returns the number of pairs */

@@ -11,8 +11,8 @@
  * kSplitTile) that hold a pair are read.
  *
  *   pfac_capture_clear     every tile's first pair to "none", the slow-path count to 0
- *   pfac_capture_mark      a thread per pair: a position outside [0, n) gets (-1, 0); a pair whose neighbour in front is outside, or in another
- *                          tile, is its tile's FIRST PAIR (the pass of scan_locate.hip with the answers of this call)
+ *   pfac_capture_mark      a thread per pair (the pass of scan_locate.hip with the answers of this call): a position outside [0, n) gets (-1, 0);
+ *                          the first pair of every tile is marked (scan_cuts.h: firstPairOfItsTile)
  *   pfac_capture_pairs     grid-stride over the tiles.  A tile without a first pair costs that one word.  Else the block reads the tile and the
  *                          kCaptureReach bytes behind it once, 16 bytes a thread and step (loadBytes16: any alignment; what hangs over the input's
  *                          end byte by byte), and leaves two bitmaps in LDS, "byte in D" and "byte in GO", 2 x (16 Ki + reach) bits; bits at and
@@ -25,9 +25,9 @@
  *   pfac_capture_finish    the count to mapped host memory
  *   pfac_host_done         the call's sequence number behind it (scan_passes.h: HostHandoff)
  * The class walk is not splitRegion: that hands out the CUT bits of one class under the split's flags (never a bit for position 0, the byte in
- * front carried from lane to lane), this call wants the plain class bits of two classes out of one load and no neighbour.  It shares the tile
- * constants, the class test (delimiterBits: the exact SWAR compare for a D of one byte, the 256-bit table in LDS else; GO always through its table),
- * stageClass, fillCutClass and loadBytes16.
+ * front carried from lane to lane), this call wants the plain class bits of two classes out of one load and no neighbour.  From scan_cuts.h: the tile
+ * constants, fillCutArgs, tileGrid, dispatchSingle, the class test (delimiterBits: the exact SWAR compare for a D of one byte, the 256-bit table in
+ * LDS else; GO always through its table) and, of the tiles of a pair list, kNoPair and the first-pair rule (firstPairOfItsTile).
  * The list is the caller's and is never trusted: an index into it is below numPairs wherever it comes from, a position indexes a tile only when it
  * lies inside [0, n), an id indexes the lengths only when it lies inside [1, numLens), and the walk over a tile's pairs ends at the first that lies
  * outside the tile.  A list that is not non-decreasing gets unspecified values, nothing else.
@@ -50,7 +50,6 @@ constexpr unsigned int kCaptureReach = PFACX_CAPTURE_REACH;            /* the by
 constexpr unsigned int kCaptureBits = kSplitTile + kCaptureReach;       /* the bits of a bitmap */
 constexpr unsigned int kCaptureWords = kCaptureBits / 64;               /* ... its 64-bit words */
 constexpr unsigned int kCaptureChunks = kCaptureBits / 16;              /* ... the 16 bytes of a thread and step */
-constexpr uint32_t kNoPair = 0xFFFFFFFFu;
 static_assert(kCaptureReach % 64 == 0 && kCaptureReach >= 64, "whole words of the bitmap");
 
 struct CaptureArgs : CutArgs {          /* in, n < 2^31, tiles; cls and rep: the stop class D */
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(256) void pfac_capture_mark(CaptureArgs a)
             continue;
         }
         const uint32_t front = i ? (uint32_t)a.pos[i - 1] : kNoPair;
-        if (front >= a.n || front / kSplitTile != p / kSplitTile) a.tileFirstPair[p / kSplitTile] = (uint32_t)i;
+        if (firstPairOfItsTile(front, p, a.n)) a.tileFirstPair[p / kSplitTile] = (uint32_t)i;
     }
 }
 
@@ -141,8 +140,7 @@ __global__ __launch_bounds__(kSplitThreads) void pfac_capture_pairs(CaptureArgs 
         const uint32_t first = a.tileFirstPair[tile];
         if (first >= a.numPairs) continue;                              /* no pair here: the whole block goes on */
         const uint32_t lo = (uint32_t)(tile * kSplitTile);              /* < n */
-        /* loadBytes16 counts in 32 bits and reads aligned blocks around what it is asked for: it gets the tile and its reach as a buffer of its own
-         * that starts up to 16 bytes in front of lo and ends up to 16 bytes behind the reach, all of it inside the input */
+        /* the window of splitRegion (scan_cuts.h has the reason) around the tile and its reach, in 32 bits */
         const uint32_t back = lo < 16u ? lo : 16u;
         const unsigned char *const base = a.in + (lo - back);
         const uint32_t left = n - lo;
@@ -226,8 +224,7 @@ __global__ void pfac_capture_finish(const unsigned long long *slowPairs, unsigne
 template <bool SINGLE>
 void captureLaunches(const PFAC_context *c, const CaptureArgs &a, const HostHandoff &count)
 {
-    const size_t cap = gridCap(c, 8);
-    const unsigned int grid = (unsigned int)(a.tiles < cap ? a.tiles : cap);
+    const unsigned int grid = tileGrid(c, a.tiles);
     hipLaunchKernelGGL(pfac_capture_clear, dim3(gridFor(c, a.tiles)), dim3(256), 0, 0, a);
     hipLaunchKernelGGL(pfac_capture_mark, dim3(gridFor(c, a.numPairs)), dim3(256), 0, 0, a);
     hipLaunchKernelGGL(pfac_capture_pairs<SINGLE>, dim3(grid), dim3(kSplitThreads), 0, 0, a);
@@ -246,12 +243,10 @@ PFAC_status_t PFACX_captureRun(PFAC_handle_t handle, const PFACX_captureRun_t *r
         return PFAC_STATUS_INVALID_PARAMETER;
     const bool atPos = (run->flags & PFACX_CAPTURE_AT_POS) != 0;
     if (!atPos && (!run->d_ids || !run->d_patternLen || run->numLens > (size_t)0x7fffffff)) return PFAC_STATUS_INVALID_PARAMETER;
-    const size_t tiles = (run->size - 1) / kSplitTile + 1;
     PFAC_context *c = handle;
     CaptureArgs a{};
-    a.in = reinterpret_cast<const unsigned char *>(run->d_input);
-    a.n = run->size;
-    a.tiles = tiles;
+    const unsigned int members = fillCutArgs(a, run->d_input, run->size, 0, run->stop);
+    const size_t tiles = a.tiles;
     a.window = run->window;
     a.atPos = atPos ? 1u : 0u;
     a.ids = atPos ? nullptr : run->d_ids;
@@ -261,7 +256,6 @@ PFAC_status_t PFACX_captureRun(PFAC_handle_t handle, const PFACX_captureRun_t *r
     a.numLens = atPos ? 0u : (uint32_t)run->numLens;
     a.valStart = run->d_valStart;
     a.valLen = run->d_valLen;
-    const unsigned int members = fillCutClass(a, run->stop);
     for (unsigned int k = 0; k < 8; k++) a.go[k] = ~run->skip[k];
     const PFAC_status_t carved = carveScratch(c->scratch.capture, [&](ScratchCarver &k) {
         a.tileFirstPair = k.take<uint32_t>(tiles);
@@ -269,8 +263,7 @@ PFAC_status_t PFACX_captureRun(PFAC_handle_t handle, const PFACX_captureRun_t *r
     });
     if (carved != PFAC_STATUS_SUCCESS) return carved;
     const HostHandoff count(c, pfac::kHostCapture);                     /* the slow pairs */
-    if (members == 1) captureLaunches<true>(c, a, count);
-    else captureLaunches<false>(c, a, count);
+    dispatchSingle(members, [&](auto single) { captureLaunches<decltype(single)::value>(c, a, count); });
     unsigned long long slow = 0;
     if (!count.finish(&slow, a.slowPairs)) return PFAC_STATUS_INTERNAL_ERROR;
     if (slow > run->numPairs) return PFAC_STATUS_INTERNAL_ERROR;

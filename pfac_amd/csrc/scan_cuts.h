@@ -1,6 +1,7 @@
 /*
  * scan_cuts.h -- the cuts of a buffer at the bytes of a class D, as scan_split.hip (PFACX_split*) and scan_locate.hip (PFACX_locate*) both need
- * them: the one statement of the cut rule on the device.
+ * them: the one statement of the cut rule on the device; and the tiles of a pair list, as scan_locate.hip and scan_capture.hip (PFACX_capture*)
+ * both walk them.
  *
  * Let the input have n bytes, a = (in[c - 1] is in D), b = (in[c] is in D).  Position c of [1, n - 1] is a CUT if
  *   flags 0: a        PFACX_SPLIT_BEFORE: b        PFACX_SPLIT_RUNS: a and not b        both: b and not a
@@ -13,16 +14,23 @@
  * lane in front (a shuffle; lane 0: the top bit of the trip in front, carried in a register; trip 0: one byte read in front of the region, which
  * is how a run crosses a region's or a tile's edge), 16 cut bits.  Nothing passes from wave to wave but sums.
  *
- * Here: the tile constants, the arguments every pass over the cuts starts with (CutArgs, fillCutClass), the class test (isDelimiter,
- * delimiterBits, stageClass), the walk of a region (splitRegion) and the count pass (pfac_split_count).  Like scan_passes.h, everything is in an
- * unnamed namespace: each unit its own copy.
+ * Here, for all three units: the tile constants, the arguments every pass starts with and their fill (CutArgs, tilesOf, fillCutArgs), the grid of a
+ * block-per-tile launch (tileGrid), the choice of the SINGLE form (dispatchSingle), the class test (isDelimiter, delimiterBits, stageClass).  THE
+ * CUTS, split and locate: the walk of a region (splitRegion) and the count pass (pfac_split_count).  THE TILES OF A PAIR LIST, locate and capture:
+ * kNoPair and the first-pair rule (firstPairOfItsTile); the mark and the pairs kernels themselves stay in the two units.  Like scan_passes.h,
+ * everything is in an unnamed namespace: each unit its own copy.
  */
 #ifndef PFAC_SCAN_CUTS_H_
 #define PFAC_SCAN_CUTS_H_
 
+#include <algorithm>
+#include <type_traits>
+
 #include "scan_passes.h"
 
 namespace {
+
+/* ------------------------------------------------------------------ the tiles and the class */
 
 constexpr unsigned int kSplitThreads = 256;                              /* four waves, a region each */
 constexpr unsigned int kSplitWaves = kSplitThreads / 64;
@@ -46,18 +54,27 @@ struct CutArgs {
     uint32_t *tileGap;                  /* [tiles] the longest distance between two neighbouring cuts of the tile */
 };
 
-/* the class of a call into a.cls and a.rep; returns the number of its members (1: the SINGLE form of every pass) */
-inline unsigned int fillCutClass(CutArgs &a, const unsigned int *cls)
+inline size_t tilesOf(size_t size) { return (size - 1) / kSplitTile + 1; }                /* size > 0 */
+
+/* what every ...Run entry fills first: the input, its tiles, the flags, the class into a.cls and a.rep; returns the number of the class's members */
+inline unsigned int fillCutArgs(CutArgs &a, const char *d_input, size_t size, unsigned int flags, const unsigned int *cls)
 {
-    unsigned int members = 0, only = 0;
-    for (unsigned int k = 0; k < 8; k++) {
-        a.cls[k] = cls[k];
-        members += (unsigned int)__builtin_popcount(cls[k]);
-        if (cls[k]) only = k * 32u + (unsigned int)__builtin_ctz(cls[k]);
-    }
-    a.rep = only * 0x01010101u;
-    return members;
+    a.in = reinterpret_cast<const unsigned char *>(d_input);
+    a.n = size;
+    a.tiles = tilesOf(size);
+    a.flags = flags;
+    const pfac::ByteClass d(cls);
+    d.copyTo(a.cls);
+    a.rep = d.only * 0x01010101u;
+    return d.members;
 }
+
+/* the blocks of a launch that takes a block per tile, grid-stride: eight per compute unit at most */
+inline unsigned int tileGrid(const PFAC_context *c, size_t tiles) { return (unsigned int)std::min<size_t>(tiles, gridCap(c, 8)); }
+
+/* f(std::true_type) for a class of one member -- the SINGLE form of every pass --, f(std::false_type) for any other */
+template <class F>
+inline void dispatchSingle(unsigned int members, F f) { members == 1 ? f(std::true_type()) : f(std::false_type()); }
 
 /* is byte b a delimiter */
 template <bool SINGLE>
@@ -82,6 +99,18 @@ __device__ __forceinline__ uint32_t delimiterBits(const CutArgs &a, const uint32
     }
 }
 
+/* the class table in LDS (a class of one byte never reads it) */
+template <bool SINGLE>
+__device__ __forceinline__ void stageClass(const CutArgs &a, uint32_t *cls)
+{
+    if constexpr (!SINGLE) {
+        if (threadIdx.x < 8) cls[threadIdx.x] = a.cls[threadIdx.x];
+        __syncthreads();
+    }
+}
+
+/* ------------------------------------------------------------------ the cuts */
+
 /* The region that starts at input byte r0 < n, by one wave: visit(o, cut) once per trip in every lane -- o: the lane's first byte, counted from r0;
  * bit k of cut: r0 + o + k is a cut.  Bits are set for positions of [1, n - 1] only */
 template <bool SINGLE, class Visit>
@@ -89,7 +118,7 @@ __device__ __forceinline__ void splitRegion(const CutArgs &a, const uint32_t *cl
 {
     const unsigned int lane = threadIdx.x & 63u;
     /* loadBytes16 counts in 32 bits and reads aligned blocks around what it is asked for: it gets the region as a buffer of its own that starts up
-     * to 16 bytes in front of r0 and ends up to 16 bytes behind the region, all of it inside the input */
+     * to 16 bytes in front of r0 and ends up to 16 bytes behind the region, all of it inside the input (scan_capture.hip: the same for a tile) */
     const unsigned int back = r0 < 16 ? (unsigned int)r0 : 16u;
     const unsigned char *const base = a.in + (r0 - back);
     const size_t left = a.n - r0;
@@ -115,16 +144,6 @@ __device__ __forceinline__ void splitRegion(const CutArgs &a, const uint32_t *cl
         cut &= valid;
         if (r0 == 0 && o == 0) cut &= ~1u;                                                 /* position 0 is no cut */
         visit(o, cut);
-    }
-}
-
-/* the class table in LDS (a class of one byte never reads it) */
-template <bool SINGLE>
-__device__ __forceinline__ void stageClass(const CutArgs &a, uint32_t *cls)
-{
-    if constexpr (!SINGLE) {
-        if (threadIdx.x < 8) cls[threadIdx.x] = a.cls[threadIdx.x];
-        __syncthreads();
     }
 }
 
@@ -201,6 +220,21 @@ __global__ __launch_bounds__(kSplitThreads) void pfac_split_count(CutArgs a)
         __syncthreads();                                                /* region is rewritten by the next tile */
     }
 }
+
+/* ------------------------------------------------------------------ the tiles of a pair list */
+
+/* A non-decreasing list of positions, tiled by position, as scan_locate.hip and scan_capture.hip walk one: a mark pass, a thread per pair, answers
+ * the positions outside [0, n) and writes every tile's FIRST PAIR into a word per tile (kNoPair: none); a pairs kernel, a block per tile, reads the
+ * word, goes on -- the whole block, in front of the tile's first barrier -- if it is >= numPairs, and strides over the list from there until a
+ * position leaves the tile.  The list is the caller's and is never trusted: an index into it is below numPairs wherever it comes from, and a
+ * position names a tile only inside [0, n).  Shared here are the constant and the rule; the loops stay in the kernels of both units, whose
+ * generated code -- pfac_capture_pairs sits at the scalar-register limit -- is then the same as without this header
+ * (profiles/pair_tiles_refactor_resources.txt) */
+constexpr uint32_t kNoPair = 0xFFFFFFFFu;
+
+/* is the pair at position p < n, whose neighbour in front in the list is at `front` (kNoPair: it has none; a negative position is a large one),
+ * its tile's first pair: the neighbour lies outside the input, or in another tile */
+__device__ __forceinline__ bool firstPairOfItsTile(uint32_t front, uint32_t p, size_t n) { return front >= n || front / kSplitTile != p / kSplitTile; }
 
 } // namespace
 

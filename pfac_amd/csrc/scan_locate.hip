@@ -1,6 +1,7 @@
 /*
  * scan_locate.hip -- locate (include/pfac_ext.h: PFACX_locate*, PFACX_matchLocated*): the record and the column of every position of
- * a non-decreasing list, by the cuts of a class D as PFACX_split* defines them (scan_cuts.h: the rule, the tiles, the walk of a region).
+ * a non-decreasing list, by the cuts of a class D as PFACX_split* defines them (scan_cuts.h: the rule, the tiles, the walk of a region, the count
+ * pass; and what this unit shares with scan_capture.hip: kNoPair, firstPairOfItsTile).
  *
  * record(p) = the number of cuts c <= p, column(p) = p - the largest such cut (0: none).  The offsets array of the split is never made: a position
  * needs the cuts in front of its tile (a sum), the last cut in front of its tile (a maximum), and the cuts of its own tile, which only the tiles
@@ -12,7 +13,7 @@
  *                          prefix under the maximum, blockExclusive, carried from step to step; a position in the input, 0: none -- a cut is never
  *                          0, and 0 is where a record without a cut in front starts); every tile's first pair is set to "none"
  *   pfac_locate_mark       a thread per pair: a position outside [0, n) gets record = column = -1; a pair whose neighbour in front is outside, or
- *                          in another tile, is its tile's FIRST PAIR
+ *                          in another tile, is its tile's FIRST PAIR (scan_cuts.h: firstPairOfItsTile, shared with scan_capture.hip)
  *   pfac_locate_pairs      grid-stride over the tiles.  A tile without a first pair costs that one word.  Else the block walks the tile once
  *                          (splitRegion) and leaves its cuts as a bitmap in LDS, 16 Ki bits = 256 words of 64; a thread per word gives the
  *                          words their exclusive popcount and the last cut in front of them (two block prefixes); then the threads stride over
@@ -40,7 +41,6 @@
 namespace {
 
 constexpr unsigned int kLocateWords = kSplitTile / 64;                   /* the 64-bit words of a tile's bitmap: one per thread */
-constexpr uint32_t kNoPair = 0xFFFFFFFFu;
 static_assert(kLocateWords == kSplitThreads, "a thread per word of the bitmap");
 
 struct LocateArgs : CutArgs {           /* n < 2^31: positions, cuts and pair indices fit 32 bits; tileLast: see pfac_locate_carry */
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void pfac_locate_mark(LocateArgs a)
             continue;
         }
         const uint32_t front = i ? (uint32_t)a.pos[i - 1] : kNoPair;
-        if (front >= a.n || front / kSplitTile != p / kSplitTile) a.tileFirstPair[p / kSplitTile] = (uint32_t)i;
+        if (firstPairOfItsTile(front, p, a.n)) a.tileFirstPair[p / kSplitTile] = (uint32_t)i;
     }
 }
 
@@ -132,8 +132,7 @@ __global__ __launch_bounds__(kSplitThreads) void pfac_locate_pairs(LocateArgs a)
 template <bool SINGLE>
 void locateLaunches(const PFAC_context *c, const LocateArgs &a, const HostHandoff &count)
 {
-    const size_t cap = gridCap(c, 8);
-    const unsigned int grid = (unsigned int)(a.tiles < cap ? a.tiles : cap);
+    const unsigned int grid = tileGrid(c, a.tiles);
     hipLaunchKernelGGL((pfac_split_count<SINGLE, false>), dim3(grid), dim3(kSplitThreads), 0, 0, static_cast<const CutArgs &>(a));
     hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, a.tileBase, (unsigned int)a.tiles, a.tileBase + a.tiles,
                        reinterpret_cast<unsigned long long *>(count.d_value));
@@ -153,18 +152,14 @@ PFAC_status_t PFACX_locateRun(PFAC_handle_t handle, const PFACX_locateRun_t *run
     if (!run || !h_numRecords || !run->d_input || run->size == 0 || run->size > (size_t)0x7fffffff || run->numPairs > (size_t)0x7fffffff ||
         (run->numPairs && (!run->d_pos || !run->d_record)) || (run->flags & ~(PFACX_SPLIT_BEFORE | PFACX_SPLIT_RUNS)))
         return PFAC_STATUS_INVALID_PARAMETER;
-    const size_t tiles = (run->size - 1) / kSplitTile + 1;
     PFAC_context *c = handle;
     LocateArgs a{};
-    a.in = reinterpret_cast<const unsigned char *>(run->d_input);
-    a.n = run->size;
-    a.tiles = tiles;
-    a.flags = run->flags;
+    const unsigned int members = fillCutArgs(a, run->d_input, run->size, run->flags, run->cls);
+    const size_t tiles = a.tiles;
     a.pos = run->d_pos;
     a.numPairs = (uint32_t)run->numPairs;
     a.record = run->d_record;
     a.column = run->d_column;
-    const unsigned int members = fillCutClass(a, run->cls);
     const PFAC_status_t carved = carveScratch(c->scratch.locate, [&](ScratchCarver &k) {
         a.tileBase = k.take<unsigned long long>(tiles + 1);
         a.tileLast = k.take<uint32_t>(tiles);
@@ -172,8 +167,7 @@ PFAC_status_t PFACX_locateRun(PFAC_handle_t handle, const PFACX_locateRun_t *run
     });
     if (carved != PFAC_STATUS_SUCCESS) return carved;
     const HostHandoff count(c, pfac::kHostLocate);                      /* the cuts */
-    if (members == 1) locateLaunches<true>(c, a, count);
-    else locateLaunches<false>(c, a, count);
+    dispatchSingle(members, [&](auto single) { locateLaunches<decltype(single)::value>(c, a, count); });
     unsigned long long cuts = 0;
     if (!count.finish(&cuts, a.tileBase + tiles)) return PFAC_STATUS_INTERNAL_ERROR;
     if (cuts >= run->size) return PFAC_STATUS_INTERNAL_ERROR;

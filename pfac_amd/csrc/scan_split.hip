@@ -1,7 +1,8 @@
 /*
  * scan_split.hip -- split (include/pfac_ext.h: PFACX_split*): the offsets that cut a buffer into records at the bytes of a class D.
  *
- * The cut rule, the tiles of 16 KiB with their four regions, the class test and the walk of a region are scan_cuts.h, shared with scan_locate.hip.
+ * The cut rule, the tiles of 16 KiB with their four regions, the class test, the walk of a region, the count pass and the start of a ...Run entry
+ * (fillCutArgs, tileGrid, dispatchSingle) are scan_cuts.h, shared with scan_locate.hip and scan_capture.hip.
  * The offsets are 0, the cuts ascending, n.
  *
  *   pfac_split_count       (scan_cuts.h, with PARTS) grid-stride over the tiles: the tile's cuts (64-bit), the cuts of each region, the tile's
@@ -100,8 +101,7 @@ __global__ __launch_bounds__(kSplitThreads) void pfac_split_write(SplitArgs a)
 template <bool SINGLE>
 void splitLaunches(const PFAC_context *c, const SplitArgs &a, const HostHandoff &counts)
 {
-    const size_t cap = gridCap(c, 8);
-    const unsigned int grid = (unsigned int)(a.tiles < cap ? a.tiles : cap);
+    const unsigned int grid = tileGrid(c, a.tiles);
     unsigned long long *const hostValue = reinterpret_cast<unsigned long long *>(counts.d_value);
     hipLaunchKernelGGL((pfac_split_count<SINGLE, true>), dim3(grid), dim3(kSplitThreads), 0, 0, static_cast<const CutArgs &>(a));
     hipLaunchKernelGGL(pfac_array_scan<unsigned long long>, dim3(1), dim3(1024), 0, 0, a.tileBase, (unsigned int)a.tiles, a.tileBase + a.tiles, hostValue);
@@ -119,17 +119,13 @@ PFAC_status_t PFACX_splitRun(PFAC_handle_t handle, const PFACX_splitRun_t *run, 
     if (!run || !h_numSegments || !run->d_input || run->size == 0 || (run->capacity && !run->d_offsets) ||
         (run->flags & ~(PFACX_SPLIT_BEFORE | PFACX_SPLIT_RUNS)))
         return PFAC_STATUS_INVALID_PARAMETER;
-    const size_t tiles = (run->size - 1) / kSplitTile + 1;
+    const size_t tiles = tilesOf(run->size);
     if (tiles > (size_t)0x7fffffff) return PFAC_STATUS_INVALID_PARAMETER;              /* 2^45 bytes: the scan counts its values in 32 bits */
     PFAC_context *c = handle;
     SplitArgs a{};
-    a.in = reinterpret_cast<const unsigned char *>(run->d_input);
-    a.n = run->size;
-    a.tiles = tiles;
-    a.flags = run->flags;
+    const unsigned int members = fillCutArgs(a, run->d_input, run->size, run->flags, run->cls);
     a.offsets = run->d_offsets;
     a.capacity = run->capacity;
-    const unsigned int members = fillCutClass(a, run->cls);
     const PFAC_status_t carved = carveScratch(c->scratch.split, [&](ScratchCarver &k) {
         a.tileBase = k.take<unsigned long long>(tiles + 1);
         a.regionCount = k.take<uint32_t>(tiles * kSplitWaves);
@@ -140,8 +136,7 @@ PFAC_status_t PFACX_splitRun(PFAC_handle_t handle, const PFACX_splitRun_t *run, 
     });
     if (carved != PFAC_STATUS_SUCCESS) return carved;
     const HostHandoff counts(c, pfac::kHostSplit);                      /* the cuts, then the longest segment */
-    if (members == 1) splitLaunches<true>(c, a, counts);
-    else splitLaunches<false>(c, a, counts);
+    dispatchSingle(members, [&](auto single) { splitLaunches<decltype(single)::value>(c, a, counts); });
     unsigned long long v[2] = {0, 0};
     if (!counts.finish(v, a.tileBase + tiles, a.longest)) return PFAC_STATUS_INTERNAL_ERROR;
     if (v[0] >= run->size || v[1] == 0 || v[1] > run->size) return PFAC_STATUS_INTERNAL_ERROR;

@@ -29,7 +29,7 @@ static PFAC_status_t checkSplitArgs(PFAC_handle_t handle, const void *input, uns
 
 /* The offsets of in[0, n), n > 0, into offsets[0, capacity): 0, the cuts, n -- nothing at or behind capacity; returns the number of segments,
  * *longest = the longest of them */
-static size_t splitOnHost(const unsigned char *in, size_t n, const unsigned int *cls, unsigned int flags, size_t *offsets, size_t capacity,
+static size_t splitOnHost(const unsigned char *in, size_t n, const ByteClass &d, unsigned int flags, size_t *offsets, size_t capacity,
                           size_t *longest)
 {
     const bool before = (flags & PFACX_SPLIT_BEFORE) != 0, runs = (flags & PFACX_SPLIT_RUNS) != 0;
@@ -40,12 +40,8 @@ static size_t splitOnHost(const unsigned char *in, size_t n, const unsigned int 
         last = c;
         cuts++;
     };
-    unsigned int members = 0, only = 0;
-    for (unsigned int k = 0; k < 8; k++) {
-        members += (unsigned int)__builtin_popcount(cls[k]);
-        if (cls[k]) only = k * 32u + (unsigned int)__builtin_ctz(cls[k]);
-    }
-    if (members == 1) {
+    const unsigned int *const cls = d.words, only = d.only;
+    if (d.members == 1) {
         /* the delimiters by memchr; a run [p, e) of them cuts once under RUNS: in front of it, or behind it */
         for (size_t p = 0; p < n;) {
             const void *hit = std::memchr(in + p, (int)only, n - p);
@@ -58,7 +54,7 @@ static size_t splitOnHost(const unsigned char *in, size_t n, const unsigned int 
             if (c > 0 && c < n) cut(c);
             p = e;
         }
-    } else if (members != 0) {
+    } else if (d.members != 0) {
         bool a = inClass(cls, in[0]);                                      /* the byte in front of c is a delimiter */
         for (size_t c = 1; c < n; c++) {
             const bool b = inClass(cls, in[c]);
@@ -90,13 +86,8 @@ PFAC_status_t PFACX_splitFromDevice(PFAC_handle_t handle, const char *d_input, s
     }
     if (lacksModule(handle)) return PFAC_STATUS_LIB_NOT_EXIST;
     std::lock_guard<std::mutex> guard(handle->lock);
-    PFACX_splitRun_t run{};
-    run.d_input = d_input;
-    run.size = size;
-    for (int k = 0; k < 8; k++) run.cls[k] = (h_class ? h_class : kNewlineClass)[k];
-    run.flags = flags;
-    run.d_offsets = d_offsets;
-    run.capacity = capacity;
+    PFACX_splitRun_t run{d_input, size, {}, flags, d_offsets, capacity};
+    ByteClass(h_class).copyTo(run.cls);
     size_t segments = 0, longest = 0;
     const PFAC_status_t ran = handle->split_run_ptr(handle, &run, &segments, &longest);
     if (ran != PFAC_STATUS_SUCCESS) return ran;
@@ -115,8 +106,7 @@ PFAC_status_t PFACX_splitFromHost(PFAC_handle_t handle, const char *h_input, siz
         if (h_longest) *h_longest = 0;
         return PFAC_STATUS_SUCCESS;
     }
-    unsigned int cls[8];
-    for (int k = 0; k < 8; k++) cls[k] = (h_class ? h_class : kNewlineClass)[k];
+    const ByteClass cls(h_class);
     std::lock_guard<std::mutex> guard(handle->lock);
     size_t longest = 0;
     const size_t segments = splitOnHost(reinterpret_cast<const unsigned char *>(h_input), size, cls, flags, h_offsets, capacity, &longest);

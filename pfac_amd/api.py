@@ -39,6 +39,8 @@ PFACX_SPLIT_RUNS = 2                            # ... a maximal run of delimiter
 PFACX_SPLIT_TILE = 16384                        # scan_split.hip: kSplitTile, the input bytes one block of the split passes takes at a time (never more than eight blocks per CU a pass)
 PFACX_SPLIT_SCAN_STEP = 1024                    # scan_passes.h: pfac_array_scan, the per-tile counts its one block takes per step
 PFACX_LOCATE_CARRY_STEP = 1024                  # scan_locate.hip: pfac_locate_carry, the tiles its one block takes per step (the step of pfac_array_scan)
+PFACX_PAIRS_MARK_BLOCK = 256                    # scan_locate.hip, scan_capture.hip: pfac_locate_mark, pfac_capture_mark, the pairs one block of a mark pass takes (scan_passes.h: gridFor)
+PFACX_GRID_BLOCKS_PER_CU = 8                    # scan_passes.h: gridCap(c, 8) in gridFor and scan_cuts.h: tileGrid, the most blocks per compute unit of a mark pass and of a block-per-tile pass
 PFACX_CAPTURE_AT_POS = 1                        # pfac_ext.h: PFACX_capture* the value starts at the position itself: no ids, no pattern set
 PFACX_CAPTURE_REACH = 1024                      # scan_capture.hip: kCaptureReach, the bytes behind a tile of PFACX_SPLIT_TILE bytes that the tile's bitmaps cover; behind them the slow path
 PFACX_SPLIT_LONGEST_STEP = 4096                 # scan_split.hip: pfac_split_longest, the tiles its one block takes per step (kSplitPerThread a thread)

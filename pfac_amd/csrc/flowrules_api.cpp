@@ -2,15 +2,17 @@
  * flowrules_api.cpp -- PFACX_flowRulesOpen / Close / Reset / PairsFromDevice / PairsFromHost (include/pfac_ext.h): which rules a
  * flows call completes on each of its pieces, members that arrived in earlier calls included.
  *
- * A flow-rule set is the plain rule set of PFACX_rulesOpen -- validated and inverted by the same code (invertPlainRules, rules_api.cpp) -- plus
+ * A flow-rule set is the plain rule set of PFACX_rulesOpen -- validated and inverted by the same code (invertPlainRules, rules_api.cpp) into the
+ * same RuleTables (pfac_host.h) -- plus
  * the state of numFlows flows.  The D distinct resolved ids the rules name are numbered in ascending order (bitOf[id], -1 for every other
  * pattern), and a flow's state is one bitmap of D bits: the patterns that have occurred in it since its last reset.  Rule r's forward list --
  * ruleBits[ruleFirst[r] + b]: the bit of its b-th member -- turns the bitmap into the mask the rule had BEFORE a call; the inverted tables give
  * the bits the call's pairs add; the rule fires iff the two together are the full mask and the old one alone was not.
  * The calls take pairs, not bytes: ids and pieceFirst of a flows call (or flush), with that call's flow ids.  The device form runs
  * PFACX_flowRulesRun (scan_flowrules.hip) over the caller's device arrays; its bitmaps are ONE device allocation, made with the tables by the
- * first device call.  The host form is a plain loop over host arrays, the same on every platform, with the bitmaps in a host vector.  Both leave
- * every flow as it was unless the whole list fitted the caller's arrays.
+ * first device call.  The host form works on host arrays, the same on every platform, with the bitmaps in a host vector: the shared walk and
+ * list frame of pfac_host.h (touchedRuleMasks, sortedSegmentLists) around its own decision (firedOnHost).  Both leave every flow as it was unless
+ * the whole list fitted the caller's arrays.
  * Every call holds the set's own lock and the handle's lock from the check of the pattern set to its end.
  */
 #include <hip/hip_runtime_api.h>
@@ -27,7 +29,7 @@ struct PFACX_flowRules_s : pfac_internal::HandleObject {
     size_t numFlows = 0;
     size_t numBits = 0;                       /* D: the distinct resolved ids the rules name */
     size_t words = 0;                         /* ceil(D / 32): the words of a flow's bitmap */
-    pfac_internal::PlainRuleTables t;         /* memberOff[F + 2], member[] = rule << 5 | bit, need[rule] */
+    pfac_internal::RuleTables t;              /* memberOff[F + 2], member[] = rule << 5 | bit, need[rule]: a plain set */
     std::vector<int> ruleFirst;               /* [numRules + 1]: rule r has ruleFirst[r + 1] - ruleFirst[r] members */
     std::vector<unsigned int> ruleBits;       /* the forward list: the bit of member b of rule r at ruleFirst[r] + b */
     std::vector<int> bitOf;                   /* [F + 1] by id: its bit in a flow's bitmap, -1: no rule names it */
@@ -39,12 +41,10 @@ struct PFACX_flowRules_s : pfac_internal::HandleObject {
     pfac::DeviceBuffer<unsigned int> d_member, d_ruleBits, d_flowBits;
     std::mutex lock;                          /* one call at a time per set */
 
-    void releaseDevice() { d_memberOff.release(); d_ruleFirst.release(); d_bitOf.release(); d_member.release(); d_ruleBits.release(); d_flowBits.release(); }
+    template <class Self, class F> static void forEachDeviceBuffer(Self &s, F f) { f(s.d_memberOff); f(s.d_ruleFirst); f(s.d_bitOf); f(s.d_member); f(s.d_ruleBits); f(s.d_flowBits); }
+    void releaseDevice() { forEachDeviceBuffer(*this, [](auto &b) { b.release(); }); }
     ~PFACX_flowRules_s() override { releaseDevice(); }
-    size_t deviceBytes() const override
-    {
-        return d_memberOff.bytes() + d_ruleFirst.bytes() + d_bitOf.bytes() + d_member.bytes() + d_ruleBits.bytes() + d_flowBits.bytes();
-    }
+    size_t deviceBytes() const override { size_t n = 0; forEachDeviceBuffer(*this, [&n](const auto &b) { n += b.bytes(); }); return n; }
 };
 
 using namespace pfac_internal;
@@ -98,11 +98,8 @@ PFAC_status_t checkPairsArgs(PFACX_flowRules_t fr, const int *ids, size_t numPai
 PFAC_status_t ensureDeviceState(PFACX_flowRules_s *s)
 {
     if (s->d_flowBits) return PFAC_STATUS_SUCCESS;
-    PFAC_status_t st = s->d_memberOff.upload(s->t.memberOff.data(), s->t.memberOff.size());
-    if (st == PFAC_STATUS_SUCCESS) st = s->d_member.upload(s->t.member.data(), s->t.member.size());
-    if (st == PFAC_STATUS_SUCCESS) st = s->d_ruleFirst.upload(s->ruleFirst.data(), s->ruleFirst.size());
-    if (st == PFAC_STATUS_SUCCESS) st = s->d_ruleBits.upload(s->ruleBits.data(), s->ruleBits.size());
-    if (st == PFAC_STATUS_SUCCESS) st = s->d_bitOf.upload(s->bitOf.data(), s->bitOf.size());
+    PFAC_status_t st = uploadAll(s->d_memberOff, s->t.memberOff, s->d_member, s->t.member, s->d_ruleFirst, s->ruleFirst, s->d_ruleBits, s->ruleBits,
+                                 s->d_bitOf, s->bitOf);
     if (st == PFAC_STATUS_SUCCESS) st = s->d_flowBits.reserve(s->numFlows * s->words);
     if (st == PFAC_STATUS_SUCCESS && hipMemset(s->d_flowBits.get(), 0, s->d_flowBits.bytes()) != hipSuccess) st = PFAC_STATUS_INTERNAL_ERROR;
     if (st != PFAC_STATUS_SUCCESS) s->releaseDevice();
@@ -114,23 +111,10 @@ PFAC_status_t ensureDeviceState(PFACX_flowRules_s *s)
 size_t firedOnHost(const pfac::Automaton &fa, const PFACX_flowRules_s &s, const int *ids, const int *first, const unsigned int *flowIds,
                    size_t numPieces, int *firedPiece, int *firedRule, size_t capacity, size_t *pieceFiredFirst)
 {
-    std::vector<unsigned int> mask(s.t.numRules, 0u);
-    std::vector<unsigned int> touched, fired;
-    size_t total = 0;
-    for (size_t k = 0; k < numPieces; k++) {
-        if (pieceFiredFirst) pieceFiredFirst[k] = total;
+    std::vector<unsigned int> mask(s.t.numRules, 0u), touched;
+    auto fill = [&](size_t k, std::vector<unsigned int> &fired) {
         const unsigned int *seen = s.h_bits.data() + (size_t)flowIds[k] * s.words;
-        touched.clear();
-        fired.clear();
-        for (int i = first[k]; i < first[k + 1]; i++)
-            forEachChainMember(fa, ids[i], [&](int q) {
-                for (int j = s.t.memberOff[(size_t)q]; j < s.t.memberOff[(size_t)q + 1]; j++) {
-                    const unsigned int m = s.t.member[(size_t)j], r = m >> 5;
-                    if (mask[r] == 0) touched.push_back(r);
-                    mask[r] |= 1u << (m & 31u);
-                }
-                return true;
-            });
+        touchedRuleMasks(fa, s.t, ids + first[k], (size_t)(first[k + 1] - first[k]), mask, touched, [](size_t, size_t, int) { return true; });
         for (unsigned int r : touched) {
             unsigned int old = 0;
             for (int b = 0; b < s.ruleFirst[r + 1] - s.ruleFirst[r]; b++) {
@@ -140,14 +124,8 @@ size_t firedOnHost(const pfac::Automaton &fa, const PFACX_flowRules_s &s, const 
             if ((old | mask[r]) == s.t.need[r] && old != s.t.need[r]) fired.push_back(r);       /* complete now, not before */
             mask[r] = 0;
         }
-        std::sort(fired.begin(), fired.end());
-        for (unsigned int r : fired) {
-            if (total < capacity) { firedPiece[total] = (int)k; firedRule[total] = (int)r; }
-            total++;
-        }
-    }
-    if (pieceFiredFirst) pieceFiredFirst[numPieces] = total;
-    return total;
+    };
+    return sortedSegmentLists<unsigned int>(numPieces, capacity, pieceFiredFirst, fill, storeSegmentAndRule(firedPiece, firedRule));
 }
 
 /* ... and, the list having fitted, the pairs into their flows' bitmaps */

@@ -3,7 +3,7 @@
  * (include/pfac_ext.h): each segment of a batch sees only the patterns whose 64-bit group mask meets the segment's.
  *
  * The mask table is resolved once, at open: the mask of every id that names a pattern is ORed into the id that pattern is reported under
- * (duplicate lines), every other id ends with 0.  Every pattern that occurs at a position is a prefix of the longest one there, so all three forms
+ * (duplicate lines: ReportedIds, pfac_host.h), every other id ends with 0.  Every pattern that occurs at a position is a prefix of the longest one there, so all three forms
  * work on longest pairs and walk each pair's prefix chain (Automaton::prefixPattern) once; what decides a member is one 64-bit AND.  The device
  * form takes the ordered pairs of the batch in the handle's pair scratch from scratchBatchPairs (batch_api.cpp) and runs PFACX_groupsRun
  * (scan_groups.hip) over them; the pairs form is that run call alone over the caller's list.  The host form takes the longest pairs of every
@@ -16,8 +16,6 @@
 #include <cstdint>
 #include <cstring>
 #include <mutex>
-#include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "pfac_host.h"
@@ -41,22 +39,11 @@ void resolveMasks(const pfac::Automaton &fa, const unsigned long long *given, PF
 {
     const size_t F = (size_t)fa.numPatterns;
     g->masks.assign(F + 1, 0ull);
-    std::unordered_map<std::string, int> reported;          /* the bytes of a pattern -> the id it is reported under; built when a lower id of duplicate lines has a mask */
-    auto bytesOf = [&](size_t id) {
-        return std::string(reinterpret_cast<const char *>(fa.file.data()) + fa.patternOff[id], (size_t)fa.patternLen[id]);
-    };
+    ReportedIds reported(fa);                               /* (a lower id of duplicate lines may have a mask) */
     for (size_t id = 1; id <= F; id++) {
         if (given[id] == 0ull) continue;
-        size_t to = id;
-        if (fa.chainLen[id] <= 0) {                         /* not in the trie: the lower id of duplicate lines */
-            if (reported.empty())
-                for (size_t q = 1; q <= F; q++)
-                    if (fa.chainLen[q] > 0) reported.emplace(bytesOf(q), (int)q);
-            const auto it = reported.find(bytesOf(id));
-            if (it == reported.end()) continue;             /* a pattern the set does not report at all */
-            to = (size_t)it->second;
-        }
-        g->masks[to] |= given[id];
+        const int to = reported.of((int)id);
+        if (to) g->masks[(size_t)to] |= given[id];          /* (0: a pattern the set does not report at all) */
     }
     g->numIds = F;
 }

@@ -311,6 +311,12 @@ constexpr size_t kStreamSeamLdsBytes = 48 * 1024;
 /* the ASCII fold of PFACX_READ_NOCASE: 'A'-'Z' -> 'a'-'z', every other byte unchanged (scan_fold.hip folds dwords the same way) */
 inline unsigned char asciiFold(unsigned char b) { return (unsigned char)((unsigned)(b - 'A') < 26u ? b + 32 : b); }
 
+/* rule sets (PFACX_rules*): the layout rules_api.cpp builds and scan_rules.hip reads.  A window {lo, hi} of memberCond: lo its offset, hi its end
+ * saturated to kCondEnd (no occurrence ends behind 2^31 - 1; no upper bound: kCondEnd) with kCondFromEnd for PFACX_RULE_FROM_END.  A link of seqLink:
+ * kSeqLinkWords words {id | kSeqFirst where it opens a chain (no predecessor), lo, hi, distance, within} */
+constexpr unsigned int kCondFromEnd = 0x80000000u, kCondEnd = 0x7FFFFFFFu;
+constexpr unsigned int kSeqLinkWords = 5, kSeqFirst = 0x80000000u;
+
 /* One device allocation of the handle: the pointer and the number of T it was allocated for.  Plain data without a destructor --
  * libpfac.so and the kernel module share PFAC_context, built by two compilers -- so whoever owns one releases it (DeviceTables /
  * DeviceScratch below enumerate the handle's).  The size a buffer grows to is the caller's business: reserve() allocates exactly

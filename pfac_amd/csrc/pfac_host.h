@@ -4,9 +4,12 @@
 #ifndef PFAC_HOST_H_
 #define PFAC_HOST_H_
 
+#include <algorithm>
 #include <memory>
 #include <new>
 #include <optional>
+#include <string>
+#include <unordered_map>
 
 #include "pfac_context.h"
 
@@ -126,15 +129,24 @@ inline void forEachChainMember(const pfac::Automaton &fa, int id, F f)
 }
 /* the length of pattern id, 0 for an id the set does not have */
 inline size_t patternLenOf(const pfac::Automaton &fa, int id) { return id > 0 && (size_t)id < fa.patternLen.size() ? (size_t)fa.patternLen[(size_t)id] : 0; }
-/* What a caller opens on a handle and closes again: the common head of PFACX_stream_s, PFACX_flows_s, PFACX_rules_s and PFACX_groups_s, and what
- * PFAC_context::objects holds.  A kind's destructor is the one place that gives its device memory back, deviceBytes() what PFACX_getInfo counts
- * of it (deviceTableBytes) */
+/* What a caller opens on a handle and closes again: the common head of PFACX_stream_s, PFACX_flows_s, PFACX_rules_s, PFACX_groups_s and
+ * PFACX_flowRules_s, and what PFAC_context::objects holds.  A kind's destructor is the one place that gives its device memory back, deviceBytes()
+ * what PFACX_getInfo counts of it (deviceTableBytes); a kind with several device buffers (a rule set, a flow-rule set) lists them ONCE, in a
+ * forEachDeviceBuffer(self, f) of its own from which both follow, as DeviceTables::forEach does.  One is only ever built by adoptNew */
 struct HandleObject {
     PFAC_context *handle = nullptr;           /* the handle that holds it; null while it is being set up */
     unsigned long long generation = 0;        /* PFAC_context::setGeneration when it was opened (a stream, a flow set: or last reset as a whole) */
     virtual ~HandleObject() = default;
     virtual size_t deviceBytes() const = 0;
 };
+/* host vectors into their device buffers, (buffer, vector) pair by pair, up to the first that fails: the caller releases what went up */
+inline PFAC_status_t uploadAll() { return PFAC_STATUS_SUCCESS; }
+template <class T, class... Rest>
+inline PFAC_status_t uploadAll(pfac::DeviceBuffer<T> &to, const std::vector<T> &from, Rest &...rest)
+{
+    const PFAC_status_t st = to.upload(from.data(), from.size());
+    return st != PFAC_STATUS_SUCCESS ? st : uploadAll(rest...);
+}
 /* What every PFACX_...Open ends with, behind its argument checks (*out is null): a new T that the handle holds, stamped with the set's generation.
  * Under c->lock: PATTERNS_NOT_READY without a set, then setUp(T &) -- it may read c->fa, refuse with a status or throw bad_alloc.  Whatever
  * fails, the object is gone and *out stays null */
@@ -309,16 +321,85 @@ private:
     std::optional<HostPairs> pairs_;
     std::optional<SetPin> pin_;
 };
-/* rules_api.cpp: the plain rules of PFACX_rulesOpen, validated and inverted exactly as that call does it (the caller holds c->lock, fa is the
- * handle's set, the pointers are not null) -- what a flow-rule set (flowrules_api.cpp) is opened over.  memberOff[F + 2], member[] = rule << 5 |
- * bit, ascending rule within a pattern, bit b of a rule its b-th resolved id in ascending order; need[rule] the full mask.  INVALID_PARAMETER:
- * whatever PFACX_rulesOpen refuses, the limits on numRules included */
-struct PlainRuleTables {
-    size_t numRules = 0, numIds = 0;
-    std::vector<int> memberOff;
-    std::vector<unsigned int> member, need;
+/* The id a pattern line is reported under (rule sets, group tables): the id itself where it is in the trie; for the lower id of duplicate lines
+ * the id that has its bytes; 0 for a pattern the set does not report at all.  The map from bytes to id is built by the first id that is not in
+ * the trie */
+class ReportedIds {
+public:
+    explicit ReportedIds(const pfac::Automaton &fa) : fa_(fa) {}
+    int of(int id)                            /* id of [1, fa.numPatterns] */
+    {
+        if (fa_.chainLen[(size_t)id] > 0) return id;
+        if (map_.empty())
+            for (int q = 1; q <= fa_.numPatterns; q++)
+                if (fa_.chainLen[(size_t)q] > 0) map_.emplace(bytesOf(q), q);
+        const auto it = map_.find(bytesOf(id));
+        return it == map_.end() ? 0 : it->second;
+    }
+private:
+    std::string bytesOf(int id) const { return std::string(reinterpret_cast<const char *>(fa_.file.data()) + fa_.patternOff[(size_t)id], (size_t)fa_.patternLen[(size_t)id]); }
+    const pfac::Automaton &fa_;
+    std::unordered_map<std::string, int> map_;
 };
-PFAC_status_t invertPlainRules(const pfac::Automaton &fa, const int *h_ruleOff, const int *h_rulePatterns, size_t numRules, PlainRuleTables *out);
+/* A rule set inverted by pattern (rules_api.cpp: invertRules), what a PFACX_rules_s and a PFACX_flowRules_s each hold one of: memberOff[F + 2],
+ * member[] = rule << 5 | bit, ascending rule within a pattern; need[rule], the bits of the positive members.  A conditioned set (PFACX_rulesOpenEx)
+ * has memberCond, a window {lo, hi} per membership indexed like member[] (2 j, 2 j + 1; pfac_context.h: kCondEnd); empty: a plain set, every
+ * occurrence sets its bit.  A set with chains (PFACX_rulesOpenSeq with a PFACX_RULE_RELATIVE member) has the links of rule r at seqLink[kSeqLinkWords
+ * seqOff[r], kSeqLinkWords seqOff[r + 1]), chain by chain in rule order; empty: no rule has a chain */
+struct RuleTables {
+    size_t numRules = 0, numIds = 0;          /* numIds: F of the pattern set it was opened on */
+    std::vector<int> memberOff, seqOff;
+    std::vector<unsigned int> member, need, memberCond, seqLink;
+    bool conditioned() const { return !memberCond.empty(); }
+    bool sequenced() const { return !seqOff.empty(); }
+};
+/* rules_api.cpp: the plain rules of PFACX_rulesOpen, validated and inverted exactly as that call does it (the caller holds c->lock, fa is the
+ * handle's set, the pointers are not null) -- what a flow-rule set (flowrules_api.cpp) is opened over: bit b of a rule is its b-th resolved id in
+ * ascending order.  INVALID_PARAMETER: whatever PFACX_rulesOpen refuses, the limits on numRules included */
+PFAC_status_t invertPlainRules(const pfac::Automaton &fa, const int *h_ruleOff, const int *h_rulePatterns, size_t numRules, RuleTables *out);
+/* The rule masks the pairs ids[0, numPairs) of one segment (or piece) set: every membership j of every pattern q on pair i's prefix chain that
+ * accept(i, j, q) lets through ORs its bit into mask[rule]; `touched` returns as the rules whose mask left 0, in the order they were met.  mask[]
+ * is all 0 on entry, and whoever decides the touched rules clears what was set */
+template <class Accept>
+inline void touchedRuleMasks(const pfac::Automaton &fa, const RuleTables &t, const int *ids, size_t numPairs, std::vector<unsigned int> &mask,
+                             std::vector<unsigned int> &touched, Accept accept)
+{
+    touched.clear();
+    for (size_t i = 0; i < numPairs; i++)
+        forEachChainMember(fa, ids[i], [&](int q) {           /* (the caller's pin: fa.numPatterns == t.numIds) */
+            for (int j = t.memberOff[(size_t)q]; j < t.memberOff[(size_t)q + 1]; j++) {
+                if (!accept(i, (size_t)j, q)) continue;
+                const unsigned int m = t.member[(size_t)j], r = m >> 5;
+                if (mask[r] == 0) touched.push_back(r);
+                mask[r] |= 1u << (m & 31u);
+            }
+            return true;
+        });
+}
+/* The host frame of "a sorted list of entries per segment, in CSR form" (the rules, flow-rules and count-batch host forms; segmentWindowPasses
+ * of scan_passes.h on the device).  Segment by segment: segFirst[k] (where given) is the running total, fill(k, keys) puts the segment's keys
+ * into the cleared `keys`, they are sorted ascending, then store(k, key, at, fits) for every key -- `at` its place in the whole list, fits == at <
+ * capacity: only then may the entry be written, else it is only counted.  segFirst[numSegments] closes the list.  Returns the full length */
+template <class Key, class Fill, class Store>
+inline size_t sortedSegmentLists(size_t numSegments, size_t capacity, size_t *segFirst, Fill fill, Store store)
+{
+    std::vector<Key> keys;
+    size_t total = 0;
+    for (size_t k = 0; k < numSegments; k++) {
+        if (segFirst) segFirst[k] = total;
+        keys.clear();
+        fill(k, keys);
+        std::sort(keys.begin(), keys.end());
+        for (const Key key : keys) {
+            store(k, key, total, total < capacity);
+            total++;
+        }
+    }
+    if (segFirst) segFirst[numSegments] = total;
+    return total;
+}
+/* ... the store of the forms whose entry is (segment or piece, rule) */
+inline auto storeSegmentAndRule(int *seg, int *rule) { return [=](size_t k, unsigned int r, size_t at, bool fits) { if (fits) { seg[at] = (int)k; rule[at] = (int)r; } }; }
 /* all_api.cpp: the device copy of {fa.prefixPattern, fa.chainLen} by id (scratch.allTable) that the all-match expansion and the count calls read;
  * the caller holds c->lock */
 PFAC_status_t ensureAllTable(PFAC_context *c);

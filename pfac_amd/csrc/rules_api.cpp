@@ -7,7 +7,9 @@
  * the full mask.  Pattern id occurs in a segment iff it lies on the prefix chain (Automaton::prefixPattern) of one of the segment's longest pairs, so
  * both forms work on longest pairs.  The device form takes the ordered pairs of the batch in the handle's pair scratch from scratchBatchPairs
  * (batch_api.cpp) and runs PFACX_rulesRun (scan_rules.hip) over them.  The host form takes the longest pairs of every segment from HostBatchPairs
- * (batch_api.cpp), pins the set the rules were opened on, and keeps one mask per touched rule in a loop of its own (firedOnHost).
+ * (batch_api.cpp), pins the set the rules were opened on, and decides the touched rules of every segment (firedOnHost) inside the shared host pieces
+ * of pfac_host.h: touchedRuleMasks, the walk that sets one mask per touched rule, and sortedSegmentLists, the frame of the fired list.  RuleTables
+ * (pfac_host.h) is what the open inverts into; the layout of its windows and links is declared in pfac_context.h for both libraries.
  *
  * PFACX_rulesOpenEx is the same open over members {pattern, flags, offset, depth}: what is made distinct and numbered is the member,
  * need[rule] keeps the bits of the positive members only (a bit a negated member sets makes mask != need), and memberCond[], indexed like member[],
@@ -18,47 +20,29 @@
  * PFACX_rulesOpenSeq is the same open over members that also carry {distance, within}.  A rule with a PFACX_RULE_RELATIVE member keeps
  * its members in the order given, nothing merged: bit b is member b, a relative member sets its bit like any conditioned one, so mask == need[rule] is
  * necessary and makes the rule a CANDIDATE.  What decides it is the rule's CHAINS -- seqOff[numRules + 1] and seqLink[], kSeqLinkWords words per link
- * in rule order: {resolved id | kSeqFirst on a chain's first link, lo, hi as in memberCond, distance, within} -- which chainsHoldOnHost verifies
- * link by link over the segment's occurrences, and pfac_rules_seq_pass on the device.  A set without a relative member has no seqOff and is the
- * conditioned set PFACX_rulesOpenEx makes of the same members.
+ * in rule order (pfac_context.h): {resolved id | kSeqFirst on a chain's first link, lo, hi as in memberCond, distance, within} -- which
+ * chainsHoldOnHost verifies link by link over the segment's occurrences, and pfac_rules_seq_pass on the device.  A set without a relative member
+ * has no seqOff and is the conditioned set PFACX_rulesOpenEx makes of the same members.
  */
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cstring>
 #include <mutex>
-#include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "pfac_host.h"
 
 struct PFACX_rules_s : pfac_internal::HandleObject {
-    size_t numRules = 0;
-    size_t numIds = 0;                        /* F of the pattern set it was opened on */
-    std::vector<int> memberOff;               /* [F + 2] */
-    std::vector<unsigned int> member;         /* rule << 5 | bit, ascending rule within a pattern */
-    std::vector<unsigned int> need;           /* [numRules]: the bits of the positive members */
-    /* a conditioned set (PFACX_rulesOpenEx): {lo, hi} per membership, indexed like member[] (2 j, 2 j + 1) -- lo the window's offset, hi its end
-     * offset + depth saturated to kNoEnd (no upper bound: kNoEnd), bit 31 PFACX_RULE_FROM_END.  Empty: a plain set, every occurrence sets its bit */
-    std::vector<unsigned int> memberCond;
-    /* a set with chains (PFACX_rulesOpenSeq with a PFACX_RULE_RELATIVE member): the links of rule r at seqLink[kSeqLinkWords seqOff[r], kSeqLinkWords
-     * seqOff[r + 1]), chain by chain in rule order; a rule without a chain has none.  Empty: no rule has a chain */
-    std::vector<int> seqOff;
-    std::vector<unsigned int> seqLink;
+    pfac_internal::RuleTables t;
     /* the same on the device, uploaded by the first device call: state of the set (deviceTableBytes), freed by PFACX_rulesClose */
-    pfac::DeviceBuffer<int> d_memberOff;
+    pfac::DeviceBuffer<int> d_memberOff, d_seqOff;
     pfac::DeviceBuffer<unsigned int> d_member, d_need, d_memberCond, d_seqLink;
-    pfac::DeviceBuffer<int> d_seqOff;
 
-    bool conditioned() const { return !memberCond.empty(); }
-    bool sequenced() const { return !seqOff.empty(); }
-    void releaseDevice() { d_memberOff.release(); d_member.release(); d_need.release(); d_memberCond.release(); d_seqOff.release(); d_seqLink.release(); }
+    template <class Self, class F> static void forEachDeviceBuffer(Self &s, F f) { f(s.d_memberOff); f(s.d_member); f(s.d_need); f(s.d_memberCond); f(s.d_seqOff); f(s.d_seqLink); }
+    void releaseDevice() { forEachDeviceBuffer(*this, [](auto &b) { b.release(); }); }
     ~PFACX_rules_s() override { releaseDevice(); }
-    size_t deviceBytes() const override
-    {
-        return d_memberOff.bytes() + d_member.bytes() + d_need.bytes() + d_memberCond.bytes() + d_seqOff.bytes() + d_seqLink.bytes();
-    }
+    size_t deviceBytes() const override { size_t n = 0; forEachDeviceBuffer(*this, [&n](const auto &b) { n += b.bytes(); }); return n; }
 };
 
 using namespace pfac_internal;
@@ -67,10 +51,7 @@ namespace {
 
 constexpr size_t kMaxRules = size_t(1) << 24, kMaxRulePatterns = 32;
 
-constexpr unsigned int kNoEnd = 0x7FFFFFFFu, kFromEnd = 0x80000000u;      /* memberCond's hi: no occurrence ends behind 2^31 - 1; the direction */
-
-constexpr size_t kSeqLinkWords = 5;                                      /* seqLink: id | kSeqFirst, lo, hi, distance, within (scan_rules.hip: kSeqLinkWords) */
-constexpr unsigned int kSeqFirst = 0x80000000u;                           /* the link opens a chain: it has no predecessor */
+using pfac::kCondFromEnd, pfac::kCondEnd, pfac::kSeqLinkWords, pfac::kSeqFirst;      /* pfac_context.h: memberCond's hi, a link of seqLink */
 
 /* a member as the tables keep it: ordered and compared by (resolved id, flags, offset, depth); distance and within are not 0 on a relative member
  * alone, and a rule that has one is neither ordered nor compared */
@@ -92,41 +73,38 @@ inline bool windowHolds(long long s, long long len, long long n, unsigned int lo
 {
     const long long tail = n - s - len;
     if (s < 0 || tail < 0) return false;
-    const long long a = (hi & kFromEnd) ? tail : s;
-    return a >= (long long)lo && a + len <= (long long)(hi & kNoEnd);
+    const long long a = (hi & kCondFromEnd) ? tail : s;
+    return a >= (long long)lo && a + len <= (long long)(hi & kCondEnd);
 }
 
 /* {lo, hi} of memberCond for a member's own window */
 inline void condOf(const Member &m, unsigned int &lo, unsigned int &hi)
 {
-    const unsigned long long end = m.depth ? (unsigned long long)m.offset + m.depth : kNoEnd;       /* 64-bit: offset + depth does not wrap */
+    const unsigned long long end = m.depth ? (unsigned long long)m.offset + m.depth : kCondEnd;       /* 64-bit: offset + depth does not wrap */
     lo = m.offset;
-    hi = (unsigned int)std::min<unsigned long long>(end, kNoEnd) | ((m.flags & PFACX_RULE_FROM_END) ? kFromEnd : 0u);
+    hi = (unsigned int)std::min<unsigned long long>(end, kCondEnd) | ((m.flags & PFACX_RULE_FROM_END) ? kCondFromEnd : 0u);
 }
 
-/* The rules inverted into s (the caller holds c->lock; the arguments are checked for null); memberAt(j): member j of the caller's array as a
+/* The rules inverted into *s (the caller holds c->lock; the arguments are checked for null); memberAt(j): member j of the caller's array as a
  * PFACX_rule_seq_member_t.  conditioned: windows and polarity are kept (PFACX_rulesOpenEx); else every member is {id, 0, 0, 0} and the set is plain.
  * flagBits: the flags the call knows -- with PFACX_RULE_RELATIVE among them (PFACX_rulesOpenSeq) a rule that has such a member keeps its order and
  * gets its chains.  false: a rule set the contract refuses */
 template <typename MemberAt>
 bool invertRules(const pfac::Automaton &fa, const int *ruleOff, MemberAt memberAt, size_t numRules, bool conditioned, unsigned int flagBits,
-                 PFACX_rules_s *s)
+                 RuleTables *s)
 {
     const size_t F = (size_t)fa.numPatterns;
     if (ruleOff[0] != 0) return false;
     for (size_t r = 0; r < numRules; r++)
         if (ruleOff[r + 1] < ruleOff[r]) return false;
-    std::unordered_map<std::string, int> reported;          /* the bytes of a pattern -> the id it is reported under; built when a lower id of duplicate lines is named */
-    auto bytesOf = [&](size_t id) {
-        return std::string(reinterpret_cast<const char *>(fa.file.data()) + fa.patternOff[id], (size_t)fa.patternLen[id]);
-    };
+    ReportedIds reported(fa);                               /* (a lower id of duplicate lines may be named) */
     std::vector<std::vector<Member>> rules(numRules);
     for (size_t r = 0; r < numRules; r++) {
         std::vector<Member> &ids = rules[r];
         bool positive = false, relative = false;
         for (int j = ruleOff[r]; j < ruleOff[r + 1]; j++) {
             const PFACX_rule_seq_member_t given = memberAt((size_t)j);
-            int id = given.pattern;
+            const int id = given.pattern;
             if (id < 1 || (size_t)id > F || (given.flags & ~flagBits)) return false;
             if (given.flags & PFACX_RULE_RELATIVE) {        /* tied to the member in front: there is one, and both are positive */
                 if (j == ruleOff[r] || (given.flags & PFACX_RULE_NOT) || (ids.back().flags & PFACX_RULE_NOT)) return false;
@@ -135,15 +113,9 @@ bool invertRules(const pfac::Automaton &fa, const int *ruleOff, MemberAt memberA
                 return false;
             }
             positive = positive || !(given.flags & PFACX_RULE_NOT);
-            if (fa.chainLen[(size_t)id] <= 0) {             /* not in the trie: the lower id of duplicate lines */
-                if (reported.empty())
-                    for (size_t q = 1; q <= F; q++)
-                        if (fa.chainLen[q] > 0) reported.emplace(bytesOf(q), (int)q);
-                const auto it = reported.find(bytesOf((size_t)id));
-                if (it == reported.end()) return false;
-                id = it->second;
-            }
-            ids.push_back(Member{id, given.flags, given.offset, given.depth, given.distance, given.within});
+            const int as = reported.of(id);
+            if (as == 0) return false;
+            ids.push_back(Member{as, given.flags, given.offset, given.depth, given.distance, given.within});
         }
         if (!relative) {                                    /* (a rule with a chain: the order given, nothing merged) */
             std::sort(ids.begin(), ids.end());
@@ -204,7 +176,7 @@ PFAC_status_t checkMatchArgs(PFACX_rules_t rules, const void *input, size_t size
  * link, have a reachable predecessor.  An occurrence at s of the next link is reachable iff some start p of reach has p + lenPrev + distance <= s
  * and (within == 0 or s + len <= p + lenPrev + within): p in [low, high], which the LARGEST p <= high decides -- exact, whatever the assignment a
  * search would have tried first.  64-bit throughout: distance = 0xFFFFFFFF makes high negative */
-bool chainsHoldOnHost(const pfac::Automaton &fa, const PFACX_rules_s &s, unsigned int r, const int *ids, const int *pos, int numPairs, long long n,
+bool chainsHoldOnHost(const pfac::Automaton &fa, const RuleTables &s, unsigned int r, const int *ids, const int *pos, int numPairs, long long n,
                       std::vector<long long> &reach, std::vector<long long> &next)
 {
     long long lenPrev = 0;
@@ -237,58 +209,37 @@ bool chainsHoldOnHost(const pfac::Automaton &fa, const PFACX_rules_s &s, unsigne
 /* The fired list of a batch whose longest pairs are known: the ids of segment k at ids[first[k], first[k] + numPairs[k]), their positions in the
  * segment at pos[] likewise (read for a conditioned set only: may be null for a plain one); segment k has first[k + 1] - first[k] bytes.  Returns
  * the full length */
-size_t firedOnHost(const pfac::Automaton &fa, const PFACX_rules_s &s, const int *ids, const int *pos, const size_t *first, const int *numPairs,
+size_t firedOnHost(const pfac::Automaton &fa, const RuleTables &t, const int *ids, const int *pos, const size_t *first, const int *numPairs,
                    size_t numSegments, int *firedSeg, int *firedRule, size_t capacity, size_t *segFirst)
 {
-    std::vector<unsigned int> mask(s.numRules, 0u);
-    std::vector<unsigned int> touched, fired;
+    std::vector<unsigned int> mask(t.numRules, 0u), touched;
     std::vector<long long> reach, next;                     /* chainsHoldOnHost's */
-    const bool cond = s.conditioned();
-    size_t total = 0;
-    for (size_t k = 0; k < numSegments; k++) {
-        if (segFirst) segFirst[k] = total;
-        touched.clear();
-        fired.clear();
+    const bool cond = t.conditioned();
+    auto fill = [&](size_t k, std::vector<unsigned int> &fired) {
+        const int *segIds = ids + first[k], *segPos = cond ? pos + first[k] : nullptr;
         const long long n = (long long)(first[k + 1] - first[k]);
-        for (int i = 0; i < numPairs[k]; i++) {
-            const long long at = cond ? pos[first[k] + (size_t)i] : 0;
-            forEachChainMember(fa, ids[first[k] + (size_t)i], [&](int q) {        /* (the caller's pin: fa.numPatterns == s.numIds) */
-                for (int j = s.memberOff[(size_t)q]; j < s.memberOff[(size_t)q + 1]; j++) {
-                    const unsigned int m = s.member[(size_t)j], r = m >> 5;
-                    if (cond && !windowHolds(at, fa.patternLen[(size_t)q], n, s.memberCond[2 * (size_t)j], s.memberCond[2 * (size_t)j + 1])) continue;
-                    if (mask[r] == 0) touched.push_back(r);
-                    mask[r] |= 1u << (m & 31u);
-                }
-                return true;
-            });
-        }
+        touchedRuleMasks(fa, t, segIds, (size_t)numPairs[k], mask, touched, [&](size_t i, size_t j, int q) {      /* a plain set: every occurrence */
+            return !cond || windowHolds(segPos[i], fa.patternLen[(size_t)q], n, t.memberCond[2 * j], t.memberCond[2 * j + 1]);
+        });
         for (unsigned int r : touched) {
             /* (a candidate with chains: verified over the segment's pairs) */
-            if (mask[r] == s.need[r] && (!s.sequenced() || s.seqOff[r] == s.seqOff[r + 1] ||
-                                         chainsHoldOnHost(fa, s, r, ids + first[k], pos + first[k], numPairs[k], n, reach, next)))
+            if (mask[r] == t.need[r] &&
+                (!t.sequenced() || t.seqOff[r] == t.seqOff[r + 1] || chainsHoldOnHost(fa, t, r, segIds, segPos, numPairs[k], n, reach, next)))
                 fired.push_back(r);
             mask[r] = 0;
         }
-        std::sort(fired.begin(), fired.end());
-        for (unsigned int r : fired) {
-            if (total < capacity) { firedSeg[total] = (int)k; firedRule[total] = (int)r; }
-            total++;
-        }
-    }
-    if (segFirst) segFirst[numSegments] = total;
-    return total;
+    };
+    return sortedSegmentLists<unsigned int>(numSegments, capacity, segFirst, fill, storeSegmentAndRule(firedSeg, firedRule));
 }
 
 /* the first device call of a rule set: its tables (the caller holds the handle's lock) */
 PFAC_status_t ensureDeviceTables(PFACX_rules_s *s)
 {
     if (s->d_need) return PFAC_STATUS_SUCCESS;
-    PFAC_status_t st = s->d_memberOff.upload(s->memberOff.data(), s->memberOff.size());
-    if (st == PFAC_STATUS_SUCCESS) st = s->d_member.upload(s->member.data(), s->member.size());
-    if (st == PFAC_STATUS_SUCCESS) st = s->d_need.upload(s->need.data(), s->need.size());
-    if (st == PFAC_STATUS_SUCCESS && s->conditioned()) st = s->d_memberCond.upload(s->memberCond.data(), s->memberCond.size());
-    if (st == PFAC_STATUS_SUCCESS && s->sequenced()) st = s->d_seqOff.upload(s->seqOff.data(), s->seqOff.size());
-    if (st == PFAC_STATUS_SUCCESS && s->sequenced()) st = s->d_seqLink.upload(s->seqLink.data(), s->seqLink.size());
+    const RuleTables &t = s->t;
+    PFAC_status_t st = uploadAll(s->d_memberOff, t.memberOff, s->d_member, t.member, s->d_need, t.need);
+    if (st == PFAC_STATUS_SUCCESS && t.conditioned()) st = uploadAll(s->d_memberCond, t.memberCond);
+    if (st == PFAC_STATUS_SUCCESS && t.sequenced()) st = uploadAll(s->d_seqOff, t.seqOff, s->d_seqLink, t.seqLink);
     if (st != PFAC_STATUS_SUCCESS) s->releaseDevice();
     return st;
 }
@@ -300,7 +251,7 @@ PFAC_status_t openRules(PFAC_handle_t handle, const int *h_ruleOff, MemberAt mem
 {
     if (numRules == 0 || numRules >= kMaxRules) return PFAC_STATUS_INVALID_PARAMETER;
     return adoptNew(handle, rules, [&](PFACX_rules_s &s) {
-        return invertRules(handle->fa, h_ruleOff, memberAt, numRules, conditioned, flagBits, &s) ? PFAC_STATUS_SUCCESS : PFAC_STATUS_INVALID_PARAMETER;
+        return invertRules(handle->fa, h_ruleOff, memberAt, numRules, conditioned, flagBits, &s.t) ? PFAC_STATUS_SUCCESS : PFAC_STATUS_INVALID_PARAMETER;
     });
 }
 constexpr unsigned int kCondFlags = PFACX_RULE_NOT | PFACX_RULE_FROM_END;
@@ -308,19 +259,11 @@ constexpr unsigned int kCondFlags = PFACX_RULE_NOT | PFACX_RULE_FROM_END;
 } // namespace
 
 /* pfac_host.h: what PFACX_rulesOpen makes of its arrays, for the flow-rule sets */
-PFAC_status_t pfac_internal::invertPlainRules(const pfac::Automaton &fa, const int *h_ruleOff, const int *h_rulePatterns, size_t numRules,
-                                              PlainRuleTables *out)
+PFAC_status_t pfac_internal::invertPlainRules(const pfac::Automaton &fa, const int *h_ruleOff, const int *h_rulePatterns, size_t numRules, RuleTables *out)
 {
     if (numRules == 0 || numRules >= kMaxRules) return PFAC_STATUS_INVALID_PARAMETER;
-    PFACX_rules_s s;
-    if (!invertRules(fa, h_ruleOff, [=](size_t j) { return PFACX_rule_seq_member_t{h_rulePatterns[j], 0u, 0u, 0u, 0u, 0u}; }, numRules, false, 0u, &s))
-        return PFAC_STATUS_INVALID_PARAMETER;
-    out->numRules = s.numRules;
-    out->numIds = s.numIds;
-    out->memberOff.swap(s.memberOff);
-    out->member.swap(s.member);
-    out->need.swap(s.need);
-    return PFAC_STATUS_SUCCESS;
+    const auto memberAt = [=](size_t j) { return PFACX_rule_seq_member_t{h_rulePatterns[j], 0u, 0u, 0u, 0u, 0u}; };
+    return invertRules(fa, h_ruleOff, memberAt, numRules, false, 0u, out) ? PFAC_STATUS_SUCCESS : PFAC_STATUS_INVALID_PARAMETER;
 }
 
 extern "C" {
@@ -378,7 +321,7 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
     }
     st = ensureDeviceTables(rules);
     if (st == PFAC_STATUS_SUCCESS) st = ensureAllTable(c);
-    const bool cond = rules->conditioned();
+    const bool cond = rules->t.conditioned();
     if (st == PFAC_STATUS_SUCCESS && cond) st = ensurePatternLen(c);            /* the window test's, offsets or none */
     BatchPairs pairs{};
     if (st == PFAC_STATUS_SUCCESS) st = scratchBatchPairs(c, d_input, size, d_offsets, numSegments, &pairs);
@@ -389,11 +332,11 @@ PFAC_status_t PFACX_rulesMatchFromDevice(PFACX_rules_t rules, char *d_input, siz
     run.d_segFirstPairs = pairs.segFirstPairs;
     run.numSegments = numSegments;
     run.d_table = c->scratch.allTable.get();
-    run.numIds = rules->numIds;
+    run.numIds = rules->t.numIds;
     run.d_memberOff = rules->d_memberOff.get();
     run.d_member = rules->d_member.get();
     run.d_need = rules->d_need.get();
-    run.numRules = rules->numRules;
+    run.numRules = rules->t.numRules;
     run.d_firedSeg = d_firedSeg;
     run.d_firedRule = d_firedRule;
     run.capacity = capacity;
@@ -429,11 +372,11 @@ PFAC_status_t PFACX_rulesMatchFromHost(PFACX_rules_t rules, char *h_input, size_
         *h_numFired = 0;
         return PFAC_STATUS_SUCCESS;
     }
-    HostBatchPairs pairs(c, h_input, size, h_offsets, numSegments, rules->conditioned(), guard);       /* a conditioned set reads the positions */
+    HostBatchPairs pairs(c, h_input, size, h_offsets, numSegments, rules->t.conditioned(), guard);       /* a conditioned set reads the positions */
     if (pairs.status != PFAC_STATUS_SUCCESS) return pairs.status;
     if (pairs.pin(rules->generation) != PFAC_STATUS_SUCCESS) return PFAC_STATUS_INVALID_PARAMETER;      /* another thread has replaced the set meanwhile: the contract's answer for a rule set */
     try {
-        const size_t total = firedOnHost(c->fa, *rules, pairs.ids, pairs.pos, pairs.offsets, pairs.numPairs.data(), numSegments, h_firedSeg, h_firedRule,
+        const size_t total = firedOnHost(c->fa, rules->t, pairs.ids, pairs.pos, pairs.offsets, pairs.numPairs.data(), numSegments, h_firedSeg, h_firedRule,
                                          capacity, h_segFirst);
         *h_numFired = total;
         return truncatedIf(total, capacity);

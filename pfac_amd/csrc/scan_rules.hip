@@ -36,7 +36,7 @@
  *
  * SETS WITH CHAINS (PFACX_rulesOpenSeq with a PFACX_RULE_RELATIVE member): pfac_rules_seq_pass<EMIT>, the conditioned pass plus a
  * verification between the decisions and the sweep (the frame's verify hook).  A relative member sets its bit like any conditioned one, so a rule with
- * mask == need is a CANDIDATE; one that has links (seqOff / seqLink, built by rules_api.cpp) is verified by the whole block over the segment's pairs,
+ * mask == need is a CANDIDATE; one that has links (seqOff / seqLink, built by rules_api.cpp in the layout of pfac_context.h) is verified by the whole block over the segment's pairs,
  * link by link (chainsHold has the method and why it is exact), and its bit is cleared from the window's bitmap if a chain fails -- in both passes
  * alike, in front of the popcounts, so a failed candidate is an entry that never was and pass 2 writes where pass 1 counted.  Nothing is staged per
  * candidate or per fired entry.  The slots, the touched list and the bitmap return to their clean state on the frame's own paths; verification keeps
@@ -84,8 +84,7 @@ struct RulesArgs {
     const unsigned int *seqLink;        /* a link: id | kSeqFirst, the window as memberCond has it, distance, within */
     unsigned int *front[2];             /* [count] each: the frontier of the link in front and of the link at hand (chainsHold) */
 };
-constexpr unsigned int kCondFromEnd = 0x80000000u, kCondEnd = 0x7FFFFFFFu;
-constexpr unsigned int kSeqLinkWords = 5, kSeqFirst = 0x80000000u;      /* rules_api.cpp builds the links */
+using pfac::kCondFromEnd, pfac::kCondEnd, pfac::kSeqLinkWords, pfac::kSeqFirst;      /* pfac_context.h: the layout rules_api.cpp builds */
 static_assert(sizeof(size_t) == sizeof(unsigned long long), "the caller's offsets are 64-bit");
 
 /* segment bound k of a conditioned call: the caller's offset clamped to [0, size], as scan_batch.hip clamps it */

@@ -5,7 +5,8 @@
  * Every pattern that occurs at a position is a prefix of the longest one there, so all three forms work on longest pairs.  The device form takes
  * the ordered pairs of the batch in the handle's pair scratch from scratchBatchPairs (batch_api.cpp) and runs PFACX_segCountRun (scan_segcount.hip)
  * over them; the pairs form is that run call alone over the caller's list.  The host form takes the longest pairs of every segment from
- * HostBatchPairs (batch_api.cpp), pins the set the call started on, and keeps one counter per touched pattern in a loop of its own (countsOnHost).
+ * HostBatchPairs (batch_api.cpp), pins the set the call started on, and keeps one counter per touched pattern (countsOnHost) inside
+ * sortedSegmentLists, the host frame of such lists in pfac_host.h.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -76,12 +77,8 @@ size_t countsOnHost(const pfac::Automaton &fa, unsigned int flags, const int *id
 {
     const bool chains = followsChains(fa, flags);
     std::vector<unsigned int> counter((size_t)fa.numPatterns + 1, 0u);
-    std::vector<int> touched;
-    size_t total = 0;
     unsigned long long all = 0;
-    for (size_t k = 0; k < numSegments; k++) {
-        segFirst[k] = total;
-        touched.clear();
+    auto fill = [&](size_t k, std::vector<int> &touched) {
         auto add = [&](int q) {
             if (counter[(size_t)q]++ == 0) touched.push_back(q);
             return true;
@@ -91,15 +88,12 @@ size_t countsOnHost(const pfac::Automaton &fa, unsigned int flags, const int *id
             if (chains) forEachChainMember(fa, id, add);
             else if (id >= 1 && id <= fa.numPatterns) add(id);
         }
-        std::sort(touched.begin(), touched.end());
-        for (int q : touched) {
-            if (total < capacity) { outIds[total] = q; outCounts[total] = counter[(size_t)q]; }
-            all += counter[(size_t)q];
-            counter[(size_t)q] = 0;
-            total++;
-        }
-    }
-    segFirst[numSegments] = total;
+    };
+    const size_t total = sortedSegmentLists<int>(numSegments, capacity, segFirst, fill, [&](size_t, int q, size_t at, bool fits) {
+        if (fits) { outIds[at] = q; outCounts[at] = counter[(size_t)q]; }
+        all += counter[(size_t)q];
+        counter[(size_t)q] = 0;
+    });
     *sum = all;
     return total;
 }

@@ -167,6 +167,30 @@ def test_truncation_changes_no_flow():
         h.destroy()
 
 
+def test_every_capacity_with_empty_pieces_and_without_piece_fired_first():
+    """the list frame at its edges: an empty first, middle and last piece; every capacity below the length of the list -- inside a piece, exactly at a
+    piece's border (pieceFiredFirst = 0, 0, 4, 4, 5, 5), the length - 1 -- truncates and commits nothing, with pieceFiredFirst and with a null one;
+    the length itself and the length + 1 return the whole list"""
+    ids, first, flows = [1, 2, 4, 5, 3, 5], [0, 0, 4, 4, 6, 6], [4, 1, 3, 0, 2]
+    want = fx.Sets(PATS, RULES, 5).call(ids, first, flows)
+    assert want[2].tolist() == [0, 0, 4, 4, 5, 5]
+    total = int(want[0].size)
+    for room in (total, total + 1):
+        h, fl, _ = small(PATS, RULES, 5)
+        try:
+            for capacity in range(total):
+                for want_first in (True, False):
+                    st, piece, rule, fired_first, n = host_call(fl, ids, first, flows, capacity=capacity, want_first=want_first)
+                    assert (st, n) == (TRUNCATED, total), f"capacity {capacity}"
+                    assert np.array_equal(piece, want[0][:capacity]) and np.array_equal(rule, want[1][:capacity]), f"capacity {capacity}"
+                    assert np.array_equal(fired_first.astype(np.uint64), want[2]) if want_first else (fired_first == 0xABCD).all(), f"capacity {capacity}"
+            same(host_call(fl, ids, first, flows, capacity=room), want, f"capacity {room}: every truncated call left the flows as they were")
+            assert host_call(fl, ids, first, flows, capacity=0)[4] == 0                  # ... and now they have moved on
+        finally:
+            fl.close()
+            h.destroy()
+
+
 @pytest.mark.parametrize("D", [31, 32, 33])
 def test_bitmap_word_edges(D):
     """D distinct rule patterns: the last bit of a word, a full word, the first bit of the next"""

@@ -116,6 +116,27 @@ def test_random_cases(workdir, seed, platform):
         h.destroy()
 
 
+def test_every_capacity_of_a_conditioned_list(workdir):
+    """the list frame at its edges for a conditioned set: an empty first, middle and last segment and every capacity from 0 to the length of the
+    list + 1 -- inside a segment, exactly at a segment's border (segFirst = 0, 0, 2, 2, 4, 4), the length - 1, the length itself"""
+    pats = [b"a", b"aa", b"aaa", b"b", b"ab"]
+    rules = [[M(1, 0, 0, 1)], [M(4, FROM_END, 0, 1), M(3, NOT)], [M(2, 0, 1), M(5, NOT | FROM_END, 1)]]
+    data, offsets = ref.cut(b"", b"aaab", b"", b"baab", b"")
+    want = rc.fired_py(pats, rules, data, offsets)
+    assert rc.pairs(want) == [(1, 0), (1, 2), (3, 1), (3, 2)] and want[2].tolist() == [0, 0, 2, 2, 4, 4]
+    total = int(want[0].size)
+    h = host_handle(pattern_file(workdir, "rulecond_caps", pats))
+    try:
+        r = h.rulesOpenEx(*rc.csr(rules))
+        for capacity in range(total + 2):
+            st, got, n = rc.host_fired(r, data, offsets, capacity)
+            assert (st, n) == (api.STATUS.OUTPUT_TRUNCATED if capacity < total else 0, total), f"capacity {capacity}"
+            ref.same(got, (want[0][:capacity], want[1][:capacity], want[2]), f"capacity {capacity}")
+        r.close()
+    finally:
+        h.destroy()
+
+
 def test_the_random_seeds_fire_and_exercise_both_polarities_and_both_directions():
     """on the reference alone: three quarters of the seeds fire something; among the fired rules some have a negated member and some a window from
     the end; some rule is kept from firing by its negated members alone, some by its windows alone"""

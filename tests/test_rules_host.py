@@ -138,6 +138,32 @@ def test_random_cases(workdir, seed, platform):
         h.destroy()
 
 
+@pytest.mark.parametrize("platform", PLATFORMS, ids=[p[1] for p in PLATFORMS])
+def test_every_capacity_with_and_without_seg_first(workdir, platform):
+    """the list frame at its edges: an empty first, middle and last segment; every capacity from 0 to the length of the list + 1 -- inside a segment,
+    exactly at a segment's border (segFirst = 0, 0, 4, 4, 7, 7), the length - 1, the length itself --, each with segFirst and with a null one"""
+    pats, rules = [b"a", b"aa", b"aaa", b"b", b"ab"], [[1, 4], [3], [5, 2], [1]]
+    data, offsets = ref.cut(b"", b"aaab", b"", b"baab", b"")
+    want = ref.fired_py(pats, rules, data, offsets)
+    assert want[2].tolist() == [0, 0, 4, 4, 7, 7]
+    total = int(want[0].size)
+    h = host_handle(pattern_file(workdir, "rules_caps", pats), platform[0])
+    try:
+        r = h.rulesOpen(*ref.csr(rules))
+        for capacity in range(total + 2):
+            for seg_first in (True, False):
+                st, got, n = host_fired(r, data, offsets, capacity=capacity, seg_first=seg_first)
+                assert (st, n) == (TRUNCATED if capacity < total else 0, total), f"capacity {capacity}"
+                ref.same(got[:2], (want[0][:capacity], want[1][:capacity]), f"capacity {capacity}")
+                if seg_first:
+                    assert got[2].tolist() == want[2].tolist(), f"capacity {capacity}: segFirst is complete"
+                else:
+                    assert np.all(got[2] == 0xDEAD), "a null segFirst and something was written"
+        r.close()
+    finally:
+        h.destroy()
+
+
 def test_numpy_reference_agrees_with_the_plain_one():
     for seed in ref.RANDOM_SEEDS[:12]:
         pats, rules, data, offsets = ref.random_case(seed)

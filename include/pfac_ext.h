@@ -1039,6 +1039,59 @@ PFAC_status_t PFACX_groupsPairsFromDevice(PFACX_groups_t groups, const int *d_pa
                                           int *d_ids, int *d_pos, size_t capacity, size_t *d_segFirst, unsigned long long *d_segGroups,
                                           size_t *h_num_matched);
 
+/* Per-pattern case sensitivity over a caseless set: `nocase` as a property of each pattern, as in a Snort rule's `content:` -- `password` in any
+ * case next to `AKIA` and `-----BEGIN` exact, `host: ` in any case next to `GET ` exact -- with ONE caseless handle and ONE scan.
+ *   The pattern text has lines 1 .. F, ids as the reader assigns them.  Line i has the flag s_i = h_sensitive[i] != 0 (1: case-sensitive, 0: caseless;
+ *   entry 0 ignored).  fold is the ASCII fold of PFACX_READ_NOCASE: 'A'-'Z' -> 'a'-'z', every other byte unchanged.
+ *   OCCURRENCE: line i occurs at p iff p + len_i <= n and, s_i = 1: in[p, p + len_i) equals the line byte for byte; s_i = 0: the folded input bytes
+ *   equal the folded line.
+ *   SAME PATTERN: two lines whose flags are equal and whose bytes (s = 1) or folded bytes (s = 0) are equal.  They are reported once, under the
+ *   highest of their ids: the duplicate rule of every reader.  A sensitive `GET`, a sensitive `get` and a caseless `Get` are three patterns.
+ *   THE LIST (flags 0): one pair per position that has an occurrence, the longest occurring pattern, on equal length the highest id; positions
+ *   ascend.  That is not a filter over the caseless longest pairs: where the longest candidate fails its exact compare, a proper prefix may pass.
+ *   ALL (PFACX_CASE_ALL): every distinct occurring pattern, by position, then length descending, then id descending.
+ *   Reported ids are line numbers: the handle's id space; they differ from the handle's only where the caseless handle collapsed several lines.
+ * PFACX_caseOpen: the handle must hold a set read with PFACX_READ_NOCASE (else PFAC_STATUS_INVALID_PARAMETER).  `patterns` is the same text,
+ * unfolded, readFlags the PFACX_READ_STRICT / PFACX_READ_STRIP_CR bits of that read (any other bit, PFACX_READ_NOCASE included: ignored).  The
+ * text goes through the reader's own line splitter; a text whose folded lines are not the handle's set -- another F, or a folded line that differs
+ * from the handle's pattern of that id -- and numFlags < F + 1 are PFAC_STATUS_INVALID_PARAMETER.  The text and the flags are copied.
+ * *maxMatchesPerPosition (may be NULL): the largest number of ALL pairs one position can have.  The object belongs to the handle like a group
+ * table: PFAC_destroy closes it, and after the handle reads or loads another set every match call returns PFAC_STATUS_INVALID_PARAMETER and only
+ * PFACX_caseClose works.  Opening on a host-only handle works.
+ * PFACX_caseMatchFromDevice: capacity = entries of each array, >= size (smaller: PFAC_STATUS_INVALID_PARAMETER): as in PFACX_matchWordsFromDevice
+ * the caller's arrays take the scan's unordered list before the result is written.  PFACX_caseMatchFromHost and PFACX_casePairsFromDevice:
+ * `capacity` is free, with capacity == 0 the output arrays may be null: the count query.  A list longer than capacity: its first `capacity` pairs
+ * are written, nothing at or behind `capacity`, *h_num_matched is the full length, and the call returns PFACX_STATUS_OUTPUT_TRUNCATED.
+ * size >= 2^31, an unknown flag bit, a required null pointer: PFAC_STATUS_INVALID_PARAMETER.  size == 0: success, 0 pairs, nothing touched.  A
+ * device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.  All calls are synchronous and take the handle's lock.  The input is never
+ * modified.  The host form follows PFAC_setPlatform like PFACX_matchWordsFromHost (temporaries: 8 bytes per input byte).
+ * PFACX_casePairsFromDevice: the same lists from an ordered LONGEST list of the caseless handle over the same d_input (the pairs of
+ * PFAC_matchFromDeviceReduce); it runs no scan and reads the caller's unfolded bytes.  The pair arrays are the caller's contract: an id outside
+ * [1, F] or a position outside [0, size) is a pair that gives nothing, a member that does not fit the input is not kept, an unsorted list gets
+ * unspecified values, and nothing outside the buffers is ever read or written.  Output arrays that overlap the pair arrays, numPairs >= 2^31:
+ * PFAC_STATUS_INVALID_PARAMETER.  numPairs == 0: success, 0 pairs.
+ * MEMORY.  The tables, made by the first device call, are state of the object (deviceTableBytes, kept by PFACX_trim, freed by PFACX_caseClose):
+ * 8 bytes per distinct pattern, 4 (F + 2) bytes, and the bytes of the sensitive patterns, each padded to a multiple of 4.  Grow-only handle
+ * scratch: 8 (B + 1) bytes rounded up to 256, B = one block per 256 longest pairs, eight per compute unit at most; the pattern lengths and the
+ * {prefix, chain length} table shared with PFACX_matchWords*; PFACX_caseMatchFromDevice also the pair scratch of PFACX_matchAll*.
+ * COST: the caseless compacted scan with its ordering launches, then two passes over the pairs that compare the bytes of the
+ * sensitive candidates, four at a time; a thread per pair, so long sensitive patterns make lanes uneven.
+ * OUT OF SCOPE: the pairs of streams and flow sets; a full-result-vector form; segment bounds of a batch; non-ASCII folds; a read flag or a
+ * compiled-file form of the flags. */
+typedef struct PFACX_case_s *PFACX_case_t;
+#define PFACX_CASE_ALL 1u   /* every distinct occurring pattern instead of the longest one per position */
+PFAC_status_t PFACX_caseOpen (PFAC_handle_t handle, const char *patterns, size_t size, unsigned int readFlags,
+                              const unsigned char *h_sensitive, size_t numFlags /* >= F + 1, indexed by ID */,
+                              PFACX_case_t *cs, int *maxMatchesPerPosition /* may be NULL */);
+PFAC_status_t PFACX_caseClose(PFACX_case_t cs);
+PFAC_status_t PFACX_caseMatchFromDevice(PFACX_case_t cs, char *d_input, size_t size, unsigned int flags,
+                                        int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_caseMatchFromHost  (PFACX_case_t cs, char *h_input, size_t size, unsigned int flags,
+                                        int *h_ids, int *h_pos, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_casePairsFromDevice(PFACX_case_t cs, const char *d_input, size_t size, unsigned int flags,
+                                        const int *d_pairIds, const int *d_pairPos, size_t numPairs,
+                                        int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched);
+
 /* Split: the offsets that cut a buffer into records at the bytes of a delimiter class -- the `d_offsets` that PFACX_matchBatch*,
  * PFACX_matchAllBatchFromDevice, PFACX_rules*, PFACX_countBatch* and PFACX_groups* take, made where the text lies: the lines of a log, the records
  * of a CRLF protocol, the fields of a line.

@@ -425,6 +425,37 @@ typedef struct {
 } PFACX_captureRun_t;
 PFAC_status_t PFACX_captureRun(PFAC_handle_t handle, const PFACX_captureRun_t *run, size_t *h_slowPairs);
 
+/* Per-pattern case sensitivity over a caseless set (no reference counterpart; include/pfac_ext.h: PFACX_case*), scan_case.hip.
+ * PFACX_caseRun: the cased occurrences of an ordered list of LONGEST pairs of a caseless set.  d_input[0, size), 0 < size < 2^31, are the CALLER's
+ * bytes at any alignment (never the folded copy: the sensitive patterns are compared with them, and no load leaves [0, size)); d_pairIds /
+ * d_pairPos[0, count), count < 2^31: one pair per position, ascending -- the handle's pair scratch behind PFACX_allReduce, or a caller's list: an
+ * id outside [1, numIds] or a position outside [0, size) is a pair that gives nothing, a chain member that does not lie inside the input is not
+ * kept.  d_table: pfac::Int2 {prefixPattern, chainLen} by id, numIds + 1 entries, or null: every chain is the pair itself; d_patternLen: the
+ * pattern lengths by id, numIds + 1 entries.  The variants of automaton id q are d_vars[d_varOff[q] & 0x7FFFFFFF, d_varOff[q + 1] & 0x7FFFFFFF)
+ * (d_varOff: numIds + 2 entries), pfac::Int2 {line id, dword index of the pattern's original bytes in d_blob; -1: a caseless variant}, by line id
+ * descending; bit 31 of d_varOff[q]: the class is one caseless variant, reported as q without a look at the tables or the input.  d_blob: blobWords
+ * dwords, every pattern padded to a multiple of 4 bytes.  all == 0: per pair the first variant that holds, longest member first; else every
+ * variant that holds.  Output: (line id, position) into d_ids / d_pos, nothing at or beyond `capacity` (0: both may be null); *h_total = the full
+ * length of the list.  The output arrays must not overlap the pair arrays (the caller checks).  Synchronous. */
+typedef struct {
+    const char *d_input;
+    size_t size;
+    const int *d_pairIds, *d_pairPos;
+    size_t count;
+    const void *d_table;
+    const int *d_patternLen;
+    size_t numIds;
+    const unsigned int *d_varOff;
+    const void *d_vars;
+    size_t numVars;
+    const unsigned int *d_blob;
+    size_t blobWords;
+    unsigned int all;
+    int *d_ids, *d_pos;
+    size_t capacity;
+} PFACX_caseRun_t;
+PFAC_status_t PFACX_caseRun(PFAC_handle_t handle, const PFACX_caseRun_t *run, size_t *h_total);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -440,7 +471,7 @@ PFAC_status_t PFACX_captureRun(PFAC_handle_t handle, const PFACX_captureRun_t *r
     X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun) \
     X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun) X(segcount_run_ptr, PFACX_segCountRun) \
     X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun) X(split_run_ptr, PFACX_splitRun) \
-    X(locate_run_ptr, PFACX_locateRun) X(capture_run_ptr, PFACX_captureRun)
+    X(locate_run_ptr, PFACX_locateRun) X(capture_run_ptr, PFACX_captureRun) X(case_run_ptr, PFACX_caseRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

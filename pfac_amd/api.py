@@ -32,6 +32,9 @@ PFACX_COUNT_LONGEST = 1                         # pfac_ext.h: PFACX_count* count
 PFACX_COUNT_ACCUMULATE = 2                      # ... add to counts[] instead of overwriting it
 PFACX_WORDS_ALL = 1                             # pfac_ext.h: PFACX_matchWords* report every bounded occurrence, not the longest per position
 PFACX_GROUPS_ALL = 1                            # pfac_ext.h: PFACX_groups* report every enabled occurrence, not the longest enabled one per position
+PFACX_CASE_ALL = 1                              # pfac_ext.h: PFACX_case* report every distinct occurring pattern, not the longest one per position
+PFACX_CASE_BLOCK = 256                          # scan_case.hip: kCaseBlock, the pairs one block of the case passes takes (never more than eight blocks per CU)
+PFACX_CASE_BLOCKS_PER_CU = 8                    # scan_passes.h: offsetBlocks, the most blocks per compute unit a pass of the expansion frame launches
 PFACX_GROUPS_BLOCK = 256                        # scan_groups.hip: kGroupsBlock, the pairs one block of the group passes takes (never more than eight blocks per CU)
 PFACX_WORDS_BLOCK = 256                         # scan_words.hip: kWordsBlock, the pairs one block of the boundary passes takes (never more than eight blocks per CU)
 PFACX_SPLIT_BEFORE = 1                          # pfac_ext.h: PFACX_split* a delimiter opens the segment behind it instead of closing the one in front
@@ -161,6 +164,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_splitFromDevice", "PFACX_splitFromHost",
     "PFACX_locatePairsFromDevice", "PFACX_locatePairsFromHost", "PFACX_matchLocatedFromDevice", "PFACX_matchLocatedFromHost",
     "PFACX_capturePairsFromDevice", "PFACX_capturePairsFromHost", "PFACX_matchCapturedFromDevice", "PFACX_matchCapturedFromHost",
+    "PFACX_caseOpen", "PFACX_caseClose", "PFACX_caseMatchFromDevice", "PFACX_caseMatchFromHost", "PFACX_casePairsFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -180,6 +184,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_splitRun",
     "PFACX_locateRun",
     "PFACX_captureRun",
+    "PFACX_caseRun",
 )
 
 
@@ -359,6 +364,15 @@ def load_library() -> C.CDLL:
                     C.POINTER(C.c_int)]
         lib.PFACX_matchCapturedFromDevice.argtypes = captured
         lib.PFACX_matchCapturedFromHost.argtypes = captured
+    if hasattr(lib, "PFACX_caseOpen"):
+        SZ = C.POINTER(C.c_size_t)
+        lib.PFACX_caseOpen.argtypes = [H, C.c_char_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+        lib.PFACX_caseClose.argtypes = [C.c_void_p]
+        cased = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, SZ]
+        lib.PFACX_caseMatchFromDevice.argtypes = cased
+        lib.PFACX_caseMatchFromHost.argtypes = cased
+        lib.PFACX_casePairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                  C.c_size_t, SZ]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -1087,6 +1101,20 @@ class PFAC:
         finally:
             g.close(check=False)
 
+    # -- per-pattern case sensitivity over a caseless set (include/pfac_ext.h: PFACX_case*) ----------------
+    def caseOpen(self, patterns: bytes, sensitive, read_flags: int = 0, check: bool = True) -> "CaseSet":
+        """``PFACX_caseOpen`` -> a :class:`CaseSet` of this handle (``.status`` holds the call's status, ``.max_matches_per_position`` the
+        longest ALL list of one position): `patterns` is the unfolded text of the set the handle read with PFACX_READ_NOCASE, `read_flags` the
+        STRICT / STRIP_CR bits of that read, ``sensitive[id]`` non-zero for a case-sensitive line (entry 0 ignored; at least F + 1 entries);
+        both are copied."""
+        import numpy as np
+        flags = np.ascontiguousarray(sensitive, dtype=np.uint8)
+        buf = flags if flags.size else np.zeros(1, dtype=np.uint8)
+        s, most = C.c_void_p(), C.c_int(0)
+        st = self._lib.PFACX_caseOpen(self._h, bytes(patterns), len(patterns), read_flags, buf.ctypes.data, flags.size, C.byref(s), C.byref(most))
+        self._ret(st, "PFACX_caseOpen", check)
+        return CaseSet(self, s, most.value, st)
+
     # -- numpy conveniences over matchFromHost (still the C ABI underneath) ----------
     def match_host_array(self, data):
         import numpy as np
@@ -1373,6 +1401,69 @@ class Groups:
         if st != 0 or n2 != n:
             raise PFACError(st, "PFACX_groupsMatchFromHost", f"{n2} pairs behind a count query that said {n}")
         return pos[:n].copy(), ids[:n].copy(), first, hit[:segments].copy()
+
+
+class CaseSet:
+    """One case object (``PFACX_case_t``) of a caseless handle: per-pattern case sensitivity.  Every match call returns ``(status, full length of
+    the list)``; OUTPUT_TRUNCATED is returned, not raised.  A context manager: it closes itself."""
+
+    def __init__(self, handle: "PFAC", cs: C.c_void_p, max_matches_per_position: int = 0, status: int = 0):
+        self._owner = handle
+        self._lib = handle._lib
+        self._c = cs
+        self.max_matches_per_position = max_matches_per_position
+        self.status = status
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self._c:
+            self.close(check=False)
+
+    def _ret(self, st: int, where: str, check: bool) -> int:
+        if check and st != 0:
+            raise PFACError(st, where, error_string(st))
+        return st
+
+    def match_device(self, d_input: int, size: int, flags: int, d_ids, d_pos, capacity: int, check: bool = True):
+        """``PFACX_caseMatchFromDevice``: capacity >= size entries in each device array."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_caseMatchFromDevice(self._c, d_input, size, flags, d_ids, d_pos, capacity, C.byref(n))
+        return self._ret(st, "PFACX_caseMatchFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def match_host(self, h_input: int, size: int, flags: int, h_ids, h_pos, capacity: int, check: bool = True):
+        """``PFACX_caseMatchFromHost``: follows PFAC_setPlatform (the CPU platforms run on the CPU); any capacity, 0 with null arrays: the count."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_caseMatchFromHost(self._c, h_input, size, flags, h_ids, h_pos, capacity, C.byref(n))
+        return self._ret(st, "PFACX_caseMatchFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def pairs_device(self, d_input: int, size: int, flags: int, d_pair_ids, d_pair_pos, num_pairs: int, d_ids, d_pos, capacity: int,
+                     check: bool = True):
+        """``PFACX_casePairsFromDevice``: the same lists from an ordered LONGEST pair list of the caseless handle over the same input (the output
+        of matchFromDeviceReduce).  It runs no scan."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_casePairsFromDevice(self._c, d_input, size, flags, d_pair_ids, d_pair_pos, num_pairs, d_ids, d_pos, capacity, C.byref(n))
+        return self._ret(st, "PFACX_casePairsFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def close(self, check: bool = True) -> int:
+        st = self._lib.PFACX_caseClose(self._c)
+        self._c = C.c_void_p()
+        return self._ret(st, "PFACX_caseClose", check)
+
+    def match_host_array(self, data, all_matches: bool = False):
+        """match_host over a numpy array -> (pos, ids) of the whole list: the count query first, then arrays of exactly that length."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        flags = PFACX_CASE_ALL if all_matches else 0
+        _, n = self.match_host(buf.ctypes.data, data.size, flags, None, None, 0)
+        ids = np.full(max(1, n), -7, dtype=np.int32)
+        pos = np.full(max(1, n), -7, dtype=np.int32)
+        st, n2 = self.match_host(buf.ctypes.data, data.size, flags, ids.ctypes.data, pos.ctypes.data, n)
+        if st != 0 or n2 != n:
+            raise PFACError(st, "PFACX_caseMatchFromHost", f"{n2} pairs behind a count query that said {n}")
+        return pos[:n].copy(), ids[:n].copy()
 
 
 def rule_member_dtype():

@@ -75,7 +75,8 @@ constexpr HostSlot kHostFlowRules = {72, 74};    /* a flow-rules call: the 64-bi
 constexpr HostSlot kHostSplit = {76, 80};        /* a split call: two 64-bit values, the cuts (scan_split.hip, by pfac_array_scan), then the longest segment (pfac_split_longest) */
 constexpr HostSlot kHostLocate = {82, 84};       /* a locate call: the 64-bit number of cuts (scan_locate.hip, by pfac_array_scan) */
 constexpr HostSlot kHostCapture = {86, 88};      /* a capture call: the 64-bit number of pairs that took the slow path (scan_capture.hip: pfac_capture_finish) */
-constexpr int kHostWords = 90;
+constexpr HostSlot kHostCase = {90, 92};         /* a case call: the 64-bit length of its list (scan_case.hip, by pfac_array_scan) */
+constexpr int kHostWords = 94;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -485,12 +486,16 @@ struct DeviceScratch {
      * in it, then the 64-bit count of the pairs that took the slow path: 4 T + 8 bytes, each part rounded up to 256; not allocated before the first
      * capture call */
     DeviceBuffer<char> capture;
+    /* the case calls (PFACX_case*, scan_case.hip): the 64-bit list offsets of the blocks of its pair passes: 8 (blocks + 1) bytes rounded up to 256,
+     * a block per 256 pairs, eight per compute unit at most; the pair list of PFACX_caseMatchFromDevice is allPairs, the prefix table allTable, the
+     * pattern lengths patternLen: shared.  The variant tables of a case object are state of that object, not scratch (case_api.cpp) */
+    DeviceBuffer<char> caseSet;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines); f(linesContext);
-        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture);
+        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }

@@ -49,6 +49,8 @@ PFACX_CAPTURE_REACH = 1024                      # scan_capture.hip: kCaptureReac
 PFACX_SPLIT_LONGEST_STEP = 4096                 # scan_split.hip: pfac_split_longest, the tiles its one block takes per step (kSplitPerThread a thread)
 PFACX_DISJOINT_BLOCK = 512                      # scan_disjoint.hip: kDisjointBlock, the pairs one block of the selection takes
 PFACX_REPLACE_TILE = 4096                       # scan_disjoint.hip: kReplaceTile, the output bytes of one tile of the replacement
+PFACX_GATHER_TILE = 4096                        # scan_passes.h: kOutTile, the output bytes of one tile of pfac_lines_gather_copy (the tile of the redaction and the replacement)
+PFACX_GATHER_THREADS = 256                      # scan_lines.hip: kLinesThreads, the threads of a block of the gather's passes: 16 output bytes a thread of a tile, a line a thread of the offsets
 PFACX_RULES_WINDOW = 8192                       # scan_rules.hip: kRulesWindow, the rules whose masks a block keeps in LDS at a time
 PFACX_RULES_TOUCHED = 1024                      # scan_rules.hip: kRulesTouched, the touched-list length; a segment that touches more rules of a window sweeps the whole table
 PFACX_RULE_NOT = 1                              # PFACX_rule_member_t.flags: the member holds if NO occurrence satisfies its window

@@ -1092,6 +1092,67 @@ PFAC_status_t PFACX_casePairsFromDevice(PFACX_case_t cs, const char *d_input, si
                                         const int *d_pairIds, const int *d_pairPos, size_t numPairs,
                                         int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched);
 
+/* Masked byte signatures with wildcards: binary signatures of the ClamAV kind -- `4D 5A ?? ?? 50 45 00 00`, `E8 ?? ?? ?? ?? 5? C3` -- and text
+ * rules such as `id=`, any 4 bytes, `;`.  The library picks one fully specified run of each signature as its ANCHOR, loads the distinct anchors as
+ * the handle's pattern set, scans for them with the product kernels and verifies every signature of every anchor occurrence against the input.
+ *   SIGNATURES.  S signatures, ids 1 .. S in the order given.  Signature i has len_i >= 1 byte pairs (v, m); the library canonicalises v &= m.
+ *   OCCURRENCE: signature i occurs at start s iff 0 <= s, s + len_i <= n and (in[s + k] ^ v_k) & m_k == 0 for every k.  Every signature is its
+ *   own entry: two identical signatures are both reported.
+ *   ANCHOR.  A candidate is a run of bytes with mask 0xFF and a value other than 0x0A (the pattern reader splits lines at 0x0A, so that byte is
+ *   never part of an anchor: it is verified like a wildcard byte).  The anchor is the longest such run, the leftmost of equal ones, cut to its first
+ *   maxAnchorLen bytes; maxAnchorLen == 0 stands for 32.  A signature without such a byte is refused.  The rule is documented, but
+ *   callers rely on PFACX_sigGetAnchors.
+ *   THE LIST: every occurrence as (id, start), ordered by ANCHOR POSITION start + anchorOff[id] ascending; at one anchor position the longer
+ *   anchor first; within one anchor ids descend -- pair order, chain order, id order: the project's convention.  It is NOT sorted by start.
+ * PFACX_sigOpen: the signatures in CSR form in host memory -- h_values / h_masks[h_sigOff[i - 1], h_sigOff[i]) are signature i, h_sigOff has
+ * numSigs + 1 entries --, copied.  It loads the distinct anchors into the handle exactly as PFACX_readPatternFromMemory would: the handle's set is
+ * REPLACED (objects opened on the earlier set go stale as after any read), the handle becomes case-sensitive, and handle id q is the q-th distinct
+ * anchor in order of first appearance.  PFAC_STATUS_INVALID_PARAMETER, with the handle's set untouched: a required null pointer, numSigs == 0 or
+ * >= 2^31 - 1, and -- with the signature's id in *badSig (may be NULL; else 0) -- an h_sigOff that does not ascend (an empty signature), a
+ * signature longer than 65 535 bytes, a signature without a fully specified byte other than 0x0A; also signatures of more than 2^32 bytes in all.
+ * PFACX_sigOpenText: a parser in front of PFACX_sigOpen and nothing else.  One signature per '\n'-terminated line: hex digit pairs in either
+ * letter case, a byte may be `??`, `x?` or `?x`; blanks and tabs between pairs are ignored, and so is a '\r' in front of the '\n'.  Refused with
+ * PFAC_STATUS_INVALID_PARAMETER and the 1-based line in *badLine (may be NULL): an empty line, a digit without its partner, any other character,
+ * bytes behind the last '\n' (as under PFACX_READ_STRICT), and a line the binary form refuses.  A text without any line: *badLine = 0.
+ * PFACX_sigGetAnchors: by signature id (n >= S + 1 entries each, entry 0 is 0; smaller: PFAC_STATUS_INVALID_PARAMETER; an array may be NULL) the
+ * handle's pattern id of the anchor, the anchor's offset inside the signature and its length.
+ * The object belongs to the handle like a case object: PFAC_destroy closes it, and after the handle reads or loads another set every call on it
+ * returns PFAC_STATUS_INVALID_PARAMETER and only PFACX_sigClose works.  Opening on a host-only handle works.
+ * PFACX_sigMatchFromDevice: capacity = entries of each array, >= size (smaller: PFAC_STATUS_INVALID_PARAMETER): as in PFACX_caseMatchFromDevice
+ * the caller's arrays take the scan's unordered list before the result is written.  PFACX_sigMatchFromHost and PFACX_sigPairsFromDevice:
+ * `capacity` is free, with capacity == 0 the output arrays may be null: the count query.  A list longer than capacity: its first `capacity`
+ * entries are written, nothing at or behind `capacity`, *h_num_matched is the full length, and the call returns PFACX_STATUS_OUTPUT_TRUNCATED.
+ * size >= 2^31, a required null pointer: PFAC_STATUS_INVALID_PARAMETER.  size == 0: success, 0 entries, nothing touched.  A device form on a
+ * host-only handle: PFAC_STATUS_LIB_NOT_EXIST.  All calls are synchronous and take the handle's lock.  The input is never modified.  The host
+ * form follows PFAC_setPlatform like PFACX_caseMatchFromHost (temporaries: 8 bytes per input byte).
+ * PFACX_sigPairsFromDevice: the same list from an ordered LONGEST list of the handle over the same d_input (the pairs PFAC_matchFromDeviceReduce
+ * leaves); it runs no scan.  The pair arrays are the caller's contract: an id outside [1, F] or a position outside [0, size) is a pair that
+ * gives nothing, an unsorted list gets unspecified values, and nothing outside the buffers is ever read or written.  Output arrays that overlap
+ * the pair arrays, numPairs >= 2^31: PFAC_STATUS_INVALID_PARAMETER.  numPairs == 0: success, 0 entries.
+ * MEMORY.  The tables, made by the first device call, are state of the object (deviceTableBytes, kept by PFACX_trim, freed by PFACX_sigClose):
+ * 16 bytes per signature, 4 (F + 2) bytes, and twice the bytes of each signature padded to a multiple of 4.  Grow-only handle scratch: 8 (B + 1)
+ * bytes rounded up to 256, B = one block per 256 longest pairs, eight per compute unit at most; the {prefix, chain length} table shared with
+ * PFACX_matchWords*; PFACX_sigMatchFromDevice also the pair scratch of PFACX_matchAll*.
+ * COST: the compacted scan over the anchors with its ordering launches, then two passes over the pairs that compare the masked
+ * bytes of the candidates, four at a time; a thread per pair, so long signatures and large classes make lanes uneven.
+ * OUT OF SCOPE: variable gaps (`*`, `{n-m}`), alternatives and negated bytes; caseless signatures; segment bounds of a batch; the pairs of
+ * streams and flow sets; a full-result-vector form; a list sorted by start; a compiled-file form. */
+typedef struct PFACX_sig_s *PFACX_sig_t;
+PFAC_status_t PFACX_sigOpen    (PFAC_handle_t handle, const unsigned char *h_values, const unsigned char *h_masks,
+                                const size_t *h_sigOff /* numSigs + 1 */, size_t numSigs, size_t maxAnchorLen /* 0: 32 */,
+                                PFACX_sig_t *sig, int *badSig /* may be NULL */);
+PFAC_status_t PFACX_sigOpenText(PFAC_handle_t handle, const char *text, size_t size, size_t maxAnchorLen /* 0: 32 */,
+                                PFACX_sig_t *sig, int *badLine /* may be NULL */);
+PFAC_status_t PFACX_sigGetAnchors(PFACX_sig_t sig, int *h_anchorId, int *h_anchorOff, int *h_anchorLen, size_t n /* >= S + 1, indexed by ID */);
+PFAC_status_t PFACX_sigClose(PFACX_sig_t sig);
+PFAC_status_t PFACX_sigMatchFromDevice(PFACX_sig_t sig, char *d_input, size_t size,
+                                       int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_sigMatchFromHost  (PFACX_sig_t sig, char *h_input, size_t size,
+                                       int *h_ids, int *h_pos, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_sigPairsFromDevice(PFACX_sig_t sig, const char *d_input, size_t size,
+                                       const int *d_pairIds, const int *d_pairPos, size_t numPairs,
+                                       int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched);
+
 /* Split: the offsets that cut a buffer into records at the bytes of a delimiter class -- the `d_offsets` that PFACX_matchBatch*,
  * PFACX_matchAllBatchFromDevice, PFACX_rules*, PFACX_countBatch* and PFACX_groups* take, made where the text lies: the lines of a log, the records
  * of a CRLF protocol, the fields of a line.

@@ -456,6 +456,35 @@ typedef struct {
 } PFACX_caseRun_t;
 PFAC_status_t PFACX_caseRun(PFAC_handle_t handle, const PFACX_caseRun_t *run, size_t *h_total);
 
+/* Masked byte signatures (no reference counterpart; include/pfac_ext.h: PFACX_sig*), scan_sig.hip.
+ * PFACX_sigRun: the signatures that occur around an ordered list of LONGEST pairs of the anchor set.  d_input[0, size), 0 < size < 2^31, are the
+ * caller's bytes at any alignment (no load leaves [0, size)); d_pairIds / d_pairPos[0, count), count < 2^31: one pair per position, ascending --
+ * the handle's pair scratch behind PFACX_allReduce, or a caller's list: an id outside [1, numIds] or a position outside [0, size) is a pair that
+ * gives nothing.  d_table: pfac::Int2 {prefixPattern, chainLen} by id, numIds + 1 entries, or null: every chain is the pair itself.  The
+ * signatures anchored by pattern q are d_sigs[d_sigOff[q], d_sigOff[q + 1]) (d_sigOff: numIds + 2 entries; the range is clamped to numSigs), four
+ * ints each: {signature id, offset of the anchor in the signature, length of the signature, dword index of its bytes in d_blob}, by signature id
+ * descending.  d_blob, blobWords dwords: per signature (len + 3) / 4 value dwords, then as many mask dwords, values already ANDed with their
+ * masks, the bytes behind len with mask 0; an entry whose dwords do not lie inside the blob is skipped.  A signature of a chain member at pair
+ * position p starts at s = p - offset; it is kept iff 0 <= s, s + len <= size and (in[s + k] ^ value[k]) & mask[k] == 0 for every k.
+ * Output: (signature id, s) into d_ids / d_pos in pair order, chain order, table order; nothing at or beyond `capacity` (0: both may be null);
+ * *h_total = the full length of the list.  The output arrays must not overlap the pair arrays (the caller checks).  Synchronous. */
+typedef struct {
+    const char *d_input;
+    size_t size;
+    const int *d_pairIds, *d_pairPos;
+    size_t count;
+    const void *d_table;
+    size_t numIds;
+    const unsigned int *d_sigOff;
+    const void *d_sigs;
+    size_t numSigs;
+    const unsigned int *d_blob;
+    size_t blobWords;
+    int *d_ids, *d_pos;
+    size_t capacity;
+} PFACX_sigRun_t;
+PFAC_status_t PFACX_sigRun(PFAC_handle_t handle, const PFACX_sigRun_t *run, size_t *h_total);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -471,7 +500,8 @@ PFAC_status_t PFACX_caseRun(PFAC_handle_t handle, const PFACX_caseRun_t *run, si
     X(disjoint_select_ptr, PFACX_disjointSelect) X(replace_run_ptr, PFACX_replaceRun) \
     X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun) X(segcount_run_ptr, PFACX_segCountRun) \
     X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun) X(split_run_ptr, PFACX_splitRun) \
-    X(locate_run_ptr, PFACX_locateRun) X(capture_run_ptr, PFACX_captureRun) X(case_run_ptr, PFACX_caseRun)
+    X(locate_run_ptr, PFACX_locateRun) X(capture_run_ptr, PFACX_captureRun) X(case_run_ptr, PFACX_caseRun) \
+    X(sig_run_ptr, PFACX_sigRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

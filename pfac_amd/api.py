@@ -34,6 +34,9 @@ PFACX_WORDS_ALL = 1                             # pfac_ext.h: PFACX_matchWords* 
 PFACX_GROUPS_ALL = 1                            # pfac_ext.h: PFACX_groups* report every enabled occurrence, not the longest enabled one per position
 PFACX_CASE_ALL = 1                              # pfac_ext.h: PFACX_case* report every distinct occurring pattern, not the longest one per position
 PFACX_CASE_BLOCK = 256                          # scan_case.hip: kCaseBlock, the pairs one block of the case passes takes (never more than eight blocks per CU)
+PFACX_SIG_BLOCK = 256                           # scan_sig.hip: kSigBlock, the pairs one block of the signature passes takes (never more than eight blocks per CU)
+PFACX_SIG_BLOCKS_PER_CU = 8                     # scan_passes.h: offsetBlocks, as for the case passes
+PFACX_SIG_DEFAULT_ANCHOR = 32                   # pfac_ext.h: PFACX_sigOpen cuts an anchor to this many bytes where maxAnchorLen is 0
 PFACX_CASE_BLOCKS_PER_CU = 8                    # scan_passes.h: offsetBlocks, the most blocks per compute unit a pass of the expansion frame launches
 PFACX_GROUPS_BLOCK = 256                        # scan_groups.hip: kGroupsBlock, the pairs one block of the group passes takes (never more than eight blocks per CU)
 PFACX_WORDS_BLOCK = 256                         # scan_words.hip: kWordsBlock, the pairs one block of the boundary passes takes (never more than eight blocks per CU)
@@ -167,6 +170,8 @@ EXPORTED_SYMBOLS = (
     "PFACX_locatePairsFromDevice", "PFACX_locatePairsFromHost", "PFACX_matchLocatedFromDevice", "PFACX_matchLocatedFromHost",
     "PFACX_capturePairsFromDevice", "PFACX_capturePairsFromHost", "PFACX_matchCapturedFromDevice", "PFACX_matchCapturedFromHost",
     "PFACX_caseOpen", "PFACX_caseClose", "PFACX_caseMatchFromDevice", "PFACX_caseMatchFromHost", "PFACX_casePairsFromDevice",
+    "PFACX_sigOpen", "PFACX_sigOpenText", "PFACX_sigGetAnchors", "PFACX_sigClose", "PFACX_sigMatchFromDevice", "PFACX_sigMatchFromHost",
+    "PFACX_sigPairsFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -187,6 +192,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_locateRun",
     "PFACX_captureRun",
     "PFACX_caseRun",
+    "PFACX_sigRun",
 )
 
 
@@ -375,6 +381,16 @@ def load_library() -> C.CDLL:
         lib.PFACX_caseMatchFromHost.argtypes = cased
         lib.PFACX_casePairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                   C.c_size_t, SZ]
+    if hasattr(lib, "PFACX_sigOpen"):
+        SZ = C.POINTER(C.c_size_t)
+        lib.PFACX_sigOpen.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+        lib.PFACX_sigOpenText.argtypes = [H, C.c_char_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+        lib.PFACX_sigGetAnchors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.PFACX_sigClose.argtypes = [C.c_void_p]
+        masked = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, SZ]
+        lib.PFACX_sigMatchFromDevice.argtypes = masked
+        lib.PFACX_sigMatchFromHost.argtypes = masked
+        lib.PFACX_sigPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, SZ]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -1117,6 +1133,31 @@ class PFAC:
         self._ret(st, "PFACX_caseOpen", check)
         return CaseSet(self, s, most.value, st)
 
+    # -- masked byte signatures with wildcards (include/pfac_ext.h: PFACX_sig*) ----------------
+    def sigOpen(self, values, masks, sig_off, max_anchor_len: int = 0, check: bool = True) -> "SigSet":
+        """``PFACX_sigOpen`` -> a :class:`SigSet` of this handle (``.status`` holds the call's status, ``.bad`` the id of a refused signature):
+        the signatures in CSR form, `values` / `masks` uint8, `sig_off` numSigs + 1 offsets; all are copied.  The handle's pattern set is
+        REPLACED by the distinct anchors."""
+        import numpy as np
+        values = np.ascontiguousarray(values, dtype=np.uint8)
+        masks = np.ascontiguousarray(masks, dtype=np.uint8)
+        off = np.ascontiguousarray(sig_off, dtype=np.uint64)
+        pad = np.zeros(1, dtype=np.uint8)
+        s, bad = C.c_void_p(), C.c_int(0)
+        st = self._lib.PFACX_sigOpen(self._h, (values if values.size else pad).ctypes.data, (masks if masks.size else pad).ctypes.data,
+                                     off.ctypes.data if off.size else None, max(0, int(off.size) - 1), max_anchor_len, C.byref(s), C.byref(bad))
+        self._ret(st, "PFACX_sigOpen", check)
+        return SigSet(self, s, max(0, int(off.size) - 1) if st == 0 else 0, bad.value, st)
+
+    def sigOpenText(self, text: bytes, max_anchor_len: int = 0, check: bool = True) -> "SigSet":
+        """``PFACX_sigOpenText`` -> a :class:`SigSet` (``.bad``: the 1-based line that was refused): one signature per line of hex digit pairs,
+        a byte may be ``??``, ``x?`` or ``?x``."""
+        text = bytes(text)
+        s, bad = C.c_void_p(), C.c_int(0)
+        st = self._lib.PFACX_sigOpenText(self._h, text, len(text), max_anchor_len, C.byref(s), C.byref(bad))
+        self._ret(st, "PFACX_sigOpenText", check)
+        return SigSet(self, s, text.count(b"\n") if st == 0 else 0, bad.value, st)
+
     # -- numpy conveniences over matchFromHost (still the C ABI underneath) ----------
     def match_host_array(self, data):
         import numpy as np
@@ -1465,6 +1506,78 @@ class CaseSet:
         st, n2 = self.match_host(buf.ctypes.data, data.size, flags, ids.ctypes.data, pos.ctypes.data, n)
         if st != 0 or n2 != n:
             raise PFACError(st, "PFACX_caseMatchFromHost", f"{n2} pairs behind a count query that said {n}")
+        return pos[:n].copy(), ids[:n].copy()
+
+
+class SigSet:
+    """One signature object (``PFACX_sig_t``): masked byte signatures over the anchors it loaded into its handle.  Every match call returns
+    ``(status, full length of the list)``; OUTPUT_TRUNCATED is returned, not raised.  The list holds (signature id, start), ordered by anchor
+    position, not by start.  A context manager: it closes itself."""
+
+    def __init__(self, handle: "PFAC", sig: C.c_void_p, num_sigs: int = 0, bad: int = 0, status: int = 0):
+        self._owner = handle
+        self._lib = handle._lib
+        self._c = sig
+        self.num_sigs = num_sigs
+        self.bad = bad
+        self.status = status
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self._c:
+            self.close(check=False)
+
+    def _ret(self, st: int, where: str, check: bool) -> int:
+        if check and st != 0:
+            raise PFACError(st, where, error_string(st))
+        return st
+
+    def anchors(self, check: bool = True):
+        """``PFACX_sigGetAnchors`` -> (anchor_id, anchor_off, anchor_len), int32 arrays of num_sigs + 1 entries indexed by signature id."""
+        import numpy as np
+        n = self.num_sigs + 1
+        out = tuple(np.full(n, -7, dtype=np.int32) for _ in range(3))
+        st = self._lib.PFACX_sigGetAnchors(self._c, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, n)
+        self._ret(st, "PFACX_sigGetAnchors", check)
+        return out
+
+    def match_device(self, d_input: int, size: int, d_ids, d_pos, capacity: int, check: bool = True):
+        """``PFACX_sigMatchFromDevice``: capacity >= size entries in each device array."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_sigMatchFromDevice(self._c, d_input, size, d_ids, d_pos, capacity, C.byref(n))
+        return self._ret(st, "PFACX_sigMatchFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def match_host(self, h_input: int, size: int, h_ids, h_pos, capacity: int, check: bool = True):
+        """``PFACX_sigMatchFromHost``: follows PFAC_setPlatform (the CPU platforms run on the CPU); any capacity, 0 with null arrays: the count."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_sigMatchFromHost(self._c, h_input, size, h_ids, h_pos, capacity, C.byref(n))
+        return self._ret(st, "PFACX_sigMatchFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def pairs_device(self, d_input: int, size: int, d_pair_ids, d_pair_pos, num_pairs: int, d_ids, d_pos, capacity: int, check: bool = True):
+        """``PFACX_sigPairsFromDevice``: the same list from an ordered LONGEST pair list of the handle over the same input (the output of
+        matchFromDeviceReduce).  It runs no scan."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_sigPairsFromDevice(self._c, d_input, size, d_pair_ids, d_pair_pos, num_pairs, d_ids, d_pos, capacity, C.byref(n))
+        return self._ret(st, "PFACX_sigPairsFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def close(self, check: bool = True) -> int:
+        st = self._lib.PFACX_sigClose(self._c)
+        self._c = C.c_void_p()
+        return self._ret(st, "PFACX_sigClose", check)
+
+    def match_host_array(self, data):
+        """match_host over a numpy array -> (pos, ids) of the whole list: the count query first, then arrays of exactly that length."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        _, n = self.match_host(buf.ctypes.data, data.size, None, None, 0)
+        ids = np.full(max(1, n), -7, dtype=np.int32)
+        pos = np.full(max(1, n), -7, dtype=np.int32)
+        st, n2 = self.match_host(buf.ctypes.data, data.size, ids.ctypes.data, pos.ctypes.data, n)
+        if st != 0 or n2 != n:
+            raise PFACError(st, "PFACX_sigMatchFromHost", f"{n2} entries behind a count query that said {n}")
         return pos[:n].copy(), ids[:n].copy()
 
 

@@ -1153,6 +1153,78 @@ PFAC_status_t PFACX_sigPairsFromDevice(PFACX_sig_t sig, const char *d_input, siz
                                        const int *d_pairIds, const int *d_pairPos, size_t numPairs,
                                        int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched);
 
+/* Patterns matched within k mismatches: DNA reads against a panel of probes or primers, keyword lists over OCR output or typed text, known byte
+ * sequences that have been patched in a few places.  The library cuts each pattern into k + 1 disjoint parts -- at any occurrence within k
+ * substitutions at least one part is exact: the pigeonhole cut --, loads the distinct PIECES (the heads of the parts) as the handle's pattern set,
+ * scans for them with the product kernels and counts the differing bytes of every pattern of every piece occurrence against the input.
+ *   PATTERNS.  S patterns, ids 1 .. S in the order given, byte strings of L_i >= 1 bytes; h_budget[i - 1] = k_i, the number of bytes of pattern i
+ *   that may differ, 0 .. PFACX_APPROX_MAX_MISMATCHES.  Every pattern is its own entry: two identical patterns are both reported.
+ *   OCCURRENCE: pattern i occurs at start s with distance d iff 0 <= s, s + L_i <= n, d = #{t : in[s + t] != pat_i[t]} and d <= k_i.
+ *   Substitutions only: no insertions, no deletions.
+ *   PIECES.  Part j (j = 0 .. k) of a pattern of L bytes is [j L / (k + 1), (j + 1) L / (k + 1)), rounded down; its piece is the first
+ *   min(part length, maxPieceLen) bytes of the part.  maxPieceLen == 0 stands for 32 and minPieceLen == 0 for 4: both defaults are suppositions
+ *   carried over from the anchor default of PFACX_sigOpen, not measured.  A pattern shorter than (k + 1) minPieceLen is refused: its pieces would
+ *   be candidates too often.  The pattern reader splits lines at 0x0A, so a piece that holds that byte is refused; a 0x0A outside every piece is
+ *   compared like any other byte.  The rule is documented, but callers rely on PFACX_approxGetPieces.
+ *   EACH OCCURRENCE ONCE.  An occurrence is found once per exact piece; it is reported by its LOWEST EXACT PIECE j*, the smallest j whose piece
+ *   bytes equal in[s + partStart_j ...].
+ *   THE LIST: every occurrence as (id, start) with its distance in a third array, ordered by CANDIDATE POSITION start + partStart_{j*} ascending;
+ *   at one candidate position the longer piece first; within one piece string by pattern id descending, then by piece index descending -- pair
+ *   order, chain order, table order: the project's convention.  It is NOT sorted by start.  It may be longer than size: several patterns can
+ *   start at one position.
+ * PFACX_approxOpen: the patterns in CSR form in host memory -- h_bytes[h_patOff[i - 1], h_patOff[i]) is pattern i, h_patOff has numPatterns + 1
+ * entries, h_budget numPatterns --, copied.  It loads the distinct pieces into the handle exactly as PFACX_readPatternFromMemory would: the
+ * handle's set is REPLACED (objects opened on the earlier set go stale as after any read), the handle becomes case-sensitive, and handle id q is
+ * the q-th distinct piece in order of first appearance (pattern by pattern, piece by piece).  It checks under the handle's lock that the set it
+ * adopts is the one it loaded.  PFAC_STATUS_INVALID_PARAMETER, with the handle's set untouched: a required null pointer, numPatterns == 0 or
+ * >= 2^31 - 1, and -- with the pattern's id in *badPattern (may be NULL; else 0) -- an h_patOff that does not ascend (an empty pattern), a
+ * pattern longer than 65 535 bytes, a budget outside [0, 7], L < (k + 1) minPieceLen, a piece that holds 0x0A (the first of these by pattern id);
+ * also patterns of more than 2^32 bytes in all.
+ * PFACX_approxGetPieces: h_pieceOff, numPatterns + 2 entries in CSR form BY ID (h_pieceOff[0] = h_pieceOff[1] = 0; the pieces of pattern i are
+ * h_pieceOff[i] .. h_pieceOff[i + 1], piece j of it at h_pieceOff[i] + j; h_pieceOff[numPatterns + 1] = the number of pieces, the sum of
+ * k_i + 1), and per piece the handle's pattern id of its string, its start inside the pattern and its length, n entries each.  Any array may be
+ * NULL; n smaller than the number of pieces with one of the three per-piece arrays given: PFAC_STATUS_INVALID_PARAMETER, nothing written; with
+ * all three NULL n is not looked at (h_pieceOff alone says how many there are).
+ * The object belongs to the handle like a signature object: PFAC_destroy closes it, and after the handle reads or loads another set every call
+ * on it returns PFAC_STATUS_INVALID_PARAMETER and only PFACX_approxClose works.  Opening on a host-only handle works.
+ * PFACX_approxMatchFromDevice: capacity = entries of each array, >= size (smaller: PFAC_STATUS_INVALID_PARAMETER): as in
+ * PFACX_sigMatchFromDevice d_ids and d_pos take the scan's unordered list before the result is written.  d_mis (may be NULL in every form) is
+ * only ever written below min(the list, capacity).  PFACX_approxMatchFromHost and PFACX_approxPairsFromDevice: `capacity` is free, with
+ * capacity == 0 the output arrays may be null: the count query.  A list longer than capacity: its first `capacity` entries are written, nothing
+ * at or behind `capacity`, *h_num_matched is the full length, and the call returns PFACX_STATUS_OUTPUT_TRUNCATED.  size >= 2^31, a required null
+ * pointer: PFAC_STATUS_INVALID_PARAMETER.  size == 0: success, 0 entries, nothing touched.  A device form on a host-only handle:
+ * PFAC_STATUS_LIB_NOT_EXIST.  All calls are synchronous and take the handle's lock.  The input is never modified.  The host form follows
+ * PFAC_setPlatform like PFACX_sigMatchFromHost (temporaries: 8 bytes per input byte).
+ * PFACX_approxPairsFromDevice: the same list from an ordered LONGEST list of the handle over the same d_input (the pairs
+ * PFAC_matchFromDeviceReduce leaves); it runs no scan.  The pair arrays are the caller's contract: an id outside [1, F] or a position outside
+ * [0, size) is a pair that gives nothing, an unsorted list gets unspecified values, and nothing outside the buffers is ever read or written.
+ * Output arrays (d_mis included) that overlap the pair arrays, numPairs >= 2^31: PFAC_STATUS_INVALID_PARAMETER.  numPairs == 0: success, 0 entries.
+ * MEMORY.  The tables, made by the first device call, are state of the object (deviceTableBytes, kept by PFACX_trim, freed by
+ * PFACX_approxClose): 16 bytes per piece, 4 (F + 2) bytes, and the bytes of each pattern padded to a multiple of 4.  Grow-only handle scratch:
+ * 8 (B + 1) bytes rounded up to 256, B = one block per 256 longest pairs, eight per compute unit at most; the {prefix, chain length} table shared
+ * with PFACX_matchWords*; PFACX_approxMatchFromDevice also the pair scratch of PFACX_matchAll*.
+ * COST: the compacted scan over the pieces with its ordering launches, then two passes over the pairs that count the differing
+ * bytes of the candidates, four at a time, and give up every 16 bytes where the budget is spent; a thread per pair, so long patterns and large
+ * classes make lanes uneven, and short pieces over a small alphabet (4-byte pieces over ACGT: a false candidate per piece at 1 position in 256)
+ * make candidates frequent: this costs more than signatures do.
+ * OUT OF SCOPE: insertions and deletions; caseless or masked approximate patterns; pieces chosen by rarity; segment bounds of a batch; the pairs
+ * of streams and flow sets; a list sorted by start; a full-result-vector form; a compiled-file form; a wave per long pattern. */
+#define PFACX_APPROX_MAX_MISMATCHES 7
+typedef struct PFACX_approx_s *PFACX_approx_t;
+PFAC_status_t PFACX_approxOpen(PFAC_handle_t handle, const unsigned char *h_bytes, const size_t *h_patOff /* numPatterns + 1 */,
+                               const int *h_budget /* numPatterns */, size_t numPatterns, size_t minPieceLen /* 0: 4 */,
+                               size_t maxPieceLen /* 0: 32 */, PFACX_approx_t *approx, int *badPattern /* may be NULL */);
+PFAC_status_t PFACX_approxGetPieces(PFACX_approx_t approx, size_t *h_pieceOff /* numPatterns + 2, CSR by ID */, int *h_pieceId, int *h_pieceStart,
+                                    int *h_pieceLen, size_t n /* >= the number of pieces */);
+PFAC_status_t PFACX_approxClose(PFACX_approx_t approx);
+PFAC_status_t PFACX_approxMatchFromDevice(PFACX_approx_t approx, char *d_input, size_t size,
+                                          int *d_ids, int *d_pos, int *d_mis /* may be NULL */, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_approxMatchFromHost  (PFACX_approx_t approx, char *h_input, size_t size,
+                                          int *h_ids, int *h_pos, int *h_mis /* may be NULL */, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_approxPairsFromDevice(PFACX_approx_t approx, const char *d_input, size_t size,
+                                          const int *d_pairIds, const int *d_pairPos, size_t numPairs,
+                                          int *d_ids, int *d_pos, int *d_mis /* may be NULL */, size_t capacity, size_t *h_num_matched);
+
 /* Split: the offsets that cut a buffer into records at the bytes of a delimiter class -- the `d_offsets` that PFACX_matchBatch*,
  * PFACX_matchAllBatchFromDevice, PFACX_rules*, PFACX_countBatch* and PFACX_groups* take, made where the text lies: the lines of a log, the records
  * of a CRLF protocol, the fields of a line.

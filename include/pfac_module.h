@@ -485,6 +485,37 @@ typedef struct {
 } PFACX_sigRun_t;
 PFAC_status_t PFACX_sigRun(PFAC_handle_t handle, const PFACX_sigRun_t *run, size_t *h_total);
 
+/* Patterns matched within k mismatches (no reference counterpart; include/pfac_ext.h: PFACX_approx*), scan_approx.hip.
+ * PFACX_approxRun: the patterns that occur within their budgets around an ordered list of LONGEST pairs of the piece set.  d_input, size, the pair
+ * arrays, count, d_table and numIds are those of PFACX_sigRun.  The (pattern, piece) entries of piece string q are d_entries[d_entryOff[q],
+ * d_entryOff[q + 1]) (d_entryOff: numIds + 2 entries; the range is clamped to numEntries), 16 bytes each (pfac_context.h: ApproxEntry): {pattern
+ * id, dword index of the pattern's bytes in d_blob, start of the piece in the pattern | length L of the pattern << 16, budget k | piece index j
+ * << 8}, by pattern id descending, then piece index descending.  d_blob, blobWords dwords: per pattern (L + 3) / 4 dwords of its bytes; an entry
+ * whose dwords do not lie inside the blob, or with k > 7, j > k or L < k + 1, is skipped; the start is j L / (k + 1).  maxPieceLen >= 1: the
+ * piece of part j' of a pattern is the first min(part length, maxPieceLen) bytes at j' L / (k + 1).  An entry of a chain member at pair position p
+ * starts at s = p - start; it is kept iff 0 <= s, s + L <= size, d = #{t : in[s + t] != pattern[t]} <= k and no piece j' < j of the pattern equals
+ * the input at s + j' L / (k + 1): every occurrence once, by its lowest exact piece.
+ * Output: (pattern id, s) into d_ids / d_pos and d into d_mis (may be null) in pair order, chain order, table order; nothing at or beyond
+ * `capacity` (0: all three may be null); *h_total = the full length of the list.  The output arrays must not overlap the pair arrays (the caller
+ * checks).  Synchronous. */
+typedef struct {
+    const char *d_input;
+    size_t size;
+    const int *d_pairIds, *d_pairPos;
+    size_t count;
+    const void *d_table;
+    size_t numIds;
+    const unsigned int *d_entryOff;
+    const void *d_entries;
+    size_t numEntries;
+    const unsigned int *d_blob;
+    size_t blobWords;
+    size_t maxPieceLen;
+    int *d_ids, *d_pos, *d_mis;
+    size_t capacity;
+} PFACX_approxRun_t;
+PFAC_status_t PFACX_approxRun(PFAC_handle_t handle, const PFACX_approxRun_t *run, size_t *h_total);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -501,7 +532,7 @@ PFAC_status_t PFACX_sigRun(PFAC_handle_t handle, const PFACX_sigRun_t *run, size
     X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun) X(segcount_run_ptr, PFACX_segCountRun) \
     X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun) X(split_run_ptr, PFACX_splitRun) \
     X(locate_run_ptr, PFACX_locateRun) X(capture_run_ptr, PFACX_captureRun) X(case_run_ptr, PFACX_caseRun) \
-    X(sig_run_ptr, PFACX_sigRun)
+    X(sig_run_ptr, PFACX_sigRun) X(approx_run_ptr, PFACX_approxRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

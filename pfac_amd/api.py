@@ -38,6 +38,9 @@ PFACX_SIG_BLOCK = 256                           # scan_sig.hip: kSigBlock, the p
 PFACX_SIG_BLOCKS_PER_CU = 8                     # scan_passes.h: offsetBlocks, as for the case passes
 PFACX_SIG_DEFAULT_ANCHOR = 32                   # pfac_ext.h: PFACX_sigOpen cuts an anchor to this many bytes where maxAnchorLen is 0
 PFACX_CASE_BLOCKS_PER_CU = 8                    # scan_passes.h: offsetBlocks, the most blocks per compute unit a pass of the expansion frame launches
+PFACX_APPROX_BLOCK = 256                        # scan_approx.hip: kApproxBlock, the pairs one block of the approximate passes takes (never more than eight blocks per CU)
+PFACX_APPROX_BLOCKS_PER_CU = 8                  # scan_passes.h: offsetBlocks, as for the case passes
+PFACX_APPROX_MAX_MISMATCHES = 7                 # pfac_ext.h: the largest budget of a pattern of PFACX_approxOpen
 PFACX_GROUPS_BLOCK = 256                        # scan_groups.hip: kGroupsBlock, the pairs one block of the group passes takes (never more than eight blocks per CU)
 PFACX_WORDS_BLOCK = 256                         # scan_words.hip: kWordsBlock, the pairs one block of the boundary passes takes (never more than eight blocks per CU)
 PFACX_SPLIT_BEFORE = 1                          # pfac_ext.h: PFACX_split* a delimiter opens the segment behind it instead of closing the one in front
@@ -172,6 +175,8 @@ EXPORTED_SYMBOLS = (
     "PFACX_caseOpen", "PFACX_caseClose", "PFACX_caseMatchFromDevice", "PFACX_caseMatchFromHost", "PFACX_casePairsFromDevice",
     "PFACX_sigOpen", "PFACX_sigOpenText", "PFACX_sigGetAnchors", "PFACX_sigClose", "PFACX_sigMatchFromDevice", "PFACX_sigMatchFromHost",
     "PFACX_sigPairsFromDevice",
+    "PFACX_approxOpen", "PFACX_approxGetPieces", "PFACX_approxClose", "PFACX_approxMatchFromDevice", "PFACX_approxMatchFromHost",
+    "PFACX_approxPairsFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -193,6 +198,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_captureRun",
     "PFACX_caseRun",
     "PFACX_sigRun",
+    "PFACX_approxRun",
 )
 
 
@@ -391,6 +397,17 @@ def load_library() -> C.CDLL:
         lib.PFACX_sigMatchFromDevice.argtypes = masked
         lib.PFACX_sigMatchFromHost.argtypes = masked
         lib.PFACX_sigPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, SZ]
+    if hasattr(lib, "PFACX_approxOpen"):
+        SZ = C.POINTER(C.c_size_t)
+        lib.PFACX_approxOpen.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_int)]
+        lib.PFACX_approxGetPieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.PFACX_approxClose.argtypes = [C.c_void_p]
+        within = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, SZ]
+        lib.PFACX_approxMatchFromDevice.argtypes = within
+        lib.PFACX_approxMatchFromHost.argtypes = within
+        lib.PFACX_approxPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_size_t, SZ]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -1158,6 +1175,31 @@ class PFAC:
         self._ret(st, "PFACX_sigOpenText", check)
         return SigSet(self, s, text.count(b"\n") if st == 0 else 0, bad.value, st)
 
+    # -- patterns matched within k mismatches (include/pfac_ext.h: PFACX_approx*) ----------------
+    def approxOpen(self, patterns, budgets, min_piece_len: int = 0, max_piece_len: int = 0, check: bool = True) -> "ApproxSet":
+        """``PFACX_approxOpen`` -> an :class:`ApproxSet` of this handle (``.status`` holds the call's status, ``.bad`` the id of a refused
+        pattern): `patterns` is a list of bytes-likes, or the CSR pair ``(bytes uint8, offsets)``; `budgets` one k per pattern; all are copied.
+        The handle's pattern set is REPLACED by the distinct pieces."""
+        import numpy as np
+        if isinstance(patterns, tuple):
+            blob = np.ascontiguousarray(patterns[0], dtype=np.uint8)
+            off = np.ascontiguousarray(patterns[1], dtype=np.uint64)
+        else:
+            patterns = [bytes(p) for p in patterns]
+            blob = np.frombuffer(b"".join(patterns), dtype=np.uint8)
+            off = np.zeros(len(patterns) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(p) for p in patterns])
+        budgets = np.ascontiguousarray(budgets, dtype=np.int32)
+        count = max(0, int(off.size) - 1)
+        if budgets.size != count:
+            raise ValueError(f"{budgets.size} budgets for {count} patterns")
+        pad = np.zeros(1, dtype=np.uint8)
+        a, bad = C.c_void_p(), C.c_int(0)
+        st = self._lib.PFACX_approxOpen(self._h, (blob if blob.size else pad).ctypes.data, off.ctypes.data if off.size else None,
+                                        budgets.ctypes.data if budgets.size else None, count, min_piece_len, max_piece_len, C.byref(a), C.byref(bad))
+        self._ret(st, "PFACX_approxOpen", check)
+        return ApproxSet(self, a, count if st == 0 else 0, int(budgets.sum()) + count if st == 0 else 0, bad.value, st)
+
     # -- numpy conveniences over matchFromHost (still the C ABI underneath) ----------
     def match_host_array(self, data):
         import numpy as np
@@ -1579,6 +1621,79 @@ class SigSet:
         if st != 0 or n2 != n:
             raise PFACError(st, "PFACX_sigMatchFromHost", f"{n2} entries behind a count query that said {n}")
         return pos[:n].copy(), ids[:n].copy()
+
+
+class ApproxSet:
+    """One approximate object (``PFACX_approx_t``): patterns matched within k mismatches over the pieces it loaded into its handle.  Every match
+    call returns ``(status, full length of the list)``; OUTPUT_TRUNCATED is returned, not raised.  The list holds (pattern id, start) and the
+    distance in a third array, ordered by candidate position, not by start.  A context manager: it closes itself."""
+
+    def __init__(self, handle: "PFAC", approx: C.c_void_p, num_patterns: int = 0, num_pieces: int = 0, bad: int = 0, status: int = 0):
+        self._owner = handle
+        self._lib = handle._lib
+        self._c = approx
+        self.num_patterns = num_patterns
+        self.num_pieces = num_pieces                             # the sum of k + 1
+        self.bad = bad
+        self.status = status
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self._c:
+            self.close(check=False)
+
+    def _ret(self, st: int, where: str, check: bool) -> int:
+        if check and st != 0:
+            raise PFACError(st, where, error_string(st))
+        return st
+
+    def pieces(self, check: bool = True):
+        """``PFACX_approxGetPieces`` -> (piece_off, piece_id, piece_start, piece_len): piece_off uint64 with num_patterns + 2 entries in CSR form by
+        pattern id, the others int32 with one entry per piece."""
+        import numpy as np
+        off = np.full(self.num_patterns + 2, 7, dtype=np.uint64)
+        out = tuple(np.full(max(1, self.num_pieces), -7, dtype=np.int32) for _ in range(3))
+        st = self._lib.PFACX_approxGetPieces(self._c, off.ctypes.data, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, self.num_pieces)
+        self._ret(st, "PFACX_approxGetPieces", check)
+        return (off,) + tuple(a[:self.num_pieces] for a in out)
+
+    def match_device(self, d_input: int, size: int, d_ids, d_pos, d_mis, capacity: int, check: bool = True):
+        """``PFACX_approxMatchFromDevice``: capacity >= size entries in each device array; d_mis may be None."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_approxMatchFromDevice(self._c, d_input, size, d_ids, d_pos, d_mis, capacity, C.byref(n))
+        return self._ret(st, "PFACX_approxMatchFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def match_host(self, h_input: int, size: int, h_ids, h_pos, h_mis, capacity: int, check: bool = True):
+        """``PFACX_approxMatchFromHost``: follows PFAC_setPlatform (the CPU platforms run on the CPU); any capacity, 0 with null arrays: the count."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_approxMatchFromHost(self._c, h_input, size, h_ids, h_pos, h_mis, capacity, C.byref(n))
+        return self._ret(st, "PFACX_approxMatchFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def pairs_device(self, d_input: int, size: int, d_pair_ids, d_pair_pos, num_pairs: int, d_ids, d_pos, d_mis, capacity: int, check: bool = True):
+        """``PFACX_approxPairsFromDevice``: the same list from an ordered LONGEST pair list of the handle over the same input (the output of
+        matchFromDeviceReduce).  It runs no scan."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_approxPairsFromDevice(self._c, d_input, size, d_pair_ids, d_pair_pos, num_pairs, d_ids, d_pos, d_mis, capacity, C.byref(n))
+        return self._ret(st, "PFACX_approxPairsFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def close(self, check: bool = True) -> int:
+        st = self._lib.PFACX_approxClose(self._c)
+        self._c = C.c_void_p()
+        return self._ret(st, "PFACX_approxClose", check)
+
+    def match_host_array(self, data):
+        """match_host over a numpy array -> (pos, ids, mis) of the whole list: the count query first, then arrays of exactly that length."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        _, n = self.match_host(buf.ctypes.data, data.size, None, None, None, 0)
+        ids, pos, mis = (np.full(max(1, n), -7, dtype=np.int32) for _ in range(3))
+        st, n2 = self.match_host(buf.ctypes.data, data.size, ids.ctypes.data, pos.ctypes.data, mis.ctypes.data, n)
+        if st != 0 or n2 != n:
+            raise PFACError(st, "PFACX_approxMatchFromHost", f"{n2} entries behind a count query that said {n}")
+        return pos[:n].copy(), ids[:n].copy(), mis[:n].copy()
 
 
 def rule_member_dtype():

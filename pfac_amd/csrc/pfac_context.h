@@ -36,6 +36,9 @@ constexpr int kFileNameLen = 256;             /* ref FILENAME_LEN, PFAC_P.h:34 *
 
 struct Int2 { int x, y; };                    /* device layout of the hashed tables (CUDA int2) */
 struct alignas(16) SigEntry { int id, anchorOff, len, blobOff; };   /* one signature of an anchor's class (sig_api.cpp, scan_sig.hip): one 16-byte load */
+/* one (pattern, piece) of a piece's class (approx_api.cpp, scan_approx.hip), one 16-byte load: the pattern's id, the dword index of its bytes in the
+ * blob, the piece's start in the pattern | the pattern's length << 16 (both <= 65 535), the pattern's budget k | the piece's index j << 8 (j <= k <= 7) */
+struct alignas(16) ApproxEntry { int id, blobOff; unsigned int startLen, budgetPiece; };
 #ifndef PFAC_WORK_PARTS
 #define PFAC_WORK_PARTS 2
 #endif
@@ -78,7 +81,8 @@ constexpr HostSlot kHostLocate = {82, 84};       /* a locate call: the 64-bit nu
 constexpr HostSlot kHostCapture = {86, 88};      /* a capture call: the 64-bit number of pairs that took the slow path (scan_capture.hip: pfac_capture_finish) */
 constexpr HostSlot kHostCase = {90, 92};         /* a case call: the 64-bit length of its list (scan_case.hip, by pfac_array_scan) */
 constexpr HostSlot kHostSig = {94, 96};          /* a signature call: the 64-bit length of its list (scan_sig.hip, by pfac_array_scan) */
-constexpr int kHostWords = 98;
+constexpr HostSlot kHostApprox = {98, 100};      /* an approximate call: the 64-bit length of its list (scan_approx.hip, by pfac_array_scan) */
+constexpr int kHostWords = 102;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -496,12 +500,16 @@ struct DeviceScratch {
      * PFACX_sigMatchFromDevice is allPairs, the prefix table allTable: shared.  The signature tables of a signature object are state of that
      * object, not scratch (sig_api.cpp) */
     DeviceBuffer<char> sigSet;
+    /* the approximate calls (PFACX_approx*, scan_approx.hip): the 64-bit list offsets of the blocks of its pair passes, sized like caseSet; the pair
+     * list of PFACX_approxMatchFromDevice is allPairs, the prefix table allTable: shared.  The piece tables of an approximate object are state of
+     * that object, not scratch (approx_api.cpp) */
+    DeviceBuffer<char> approxSet;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines); f(linesContext);
-        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet); f(sigSet);
+        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet); f(sigSet); f(approxSet);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }

@@ -1,6 +1,6 @@
 /*
  * scan_passes.h -- what the passes around the scan share (scan_module.hip with scan_order.inc, scan_batch.hip, scan_all.hip, scan_fold.hip,
- * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip, scan_disjoint.hip, scan_rules.hip, scan_words.hip, scan_segcount.hip, scan_groups.hip, scan_case.hip, scan_sig.hip and, through scan_cuts.h, scan_split.hip and scan_locate.hip; the product kernels' units do
+ * scan_stream.hip, scan_flows.hip, scan_lines.hip, scan_spans.hip, scan_count.hip, scan_disjoint.hip, scan_rules.hip, scan_words.hip, scan_segcount.hip, scan_groups.hip, scan_case.hip, scan_sig.hip, scan_approx.hip and, through scan_cuts.h, scan_split.hip and scan_locate.hip; the product kernels' units do
  * not include it): launch sizes, the layout of a call's scratch and its carving out of a buffer of the handle (ScratchCarver, carveScratch), the
  * compacted scan as a pass runs it, the hand-off of a call's result to the host through mapped memory (HostHandoff; storeToHost on the device),
  * the device fold byte, the exact SWAR test of four bytes against one (bytesEqual4), the clamp of a caller's (start, len), 16 bytes out of two aligned blocks (funnel, loadBytes16), the frame of an output
@@ -11,7 +11,7 @@
  * through windows of an LDS table (clampFirstPair, SegmentFrame, segmentWindows, carveSegFirst, segmentWindowPasses: the rules and the
  * count-batch passes), the walk along a pattern's prefix chain (forEachChainMember: the one such loop on the device) with the frame and the
  * launches of a pass that expands longest pairs into the members of their chains (ExpandFrame, expandCount, expandWrite, expandPasses: the
- * all-match, the words, the groups, the case and the signature passes), the pairs of an ordered scan with the head, the tail and the finish kernel of a select call over them (PairArgs,
+ * all-match, the words, the groups, the case, the signature and the approximate passes), the pairs of an ordered scan with the head, the tail and the finish kernel of a select call over them (PairArgs,
  * pairsSelectHead, pairsSelectTail, pfac_pairs_finish), the seam of a stream.  Like scan_common.h, everything is in an unnamed namespace: inline
  * device code, each unit its own copy.
  */
@@ -684,12 +684,12 @@ inline bool segmentWindowPasses(const PFAC_context *c, const Args &a, void (*cou
            hipMemcpyAsync(d_segFirst, f.segFirst, ((size_t)f.numSegments + 1) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, nullptr) == hipSuccess;
 }
 
-/* ------------------------------------------------------------------ the prefix chain of a pattern; the expansion frame (scan_all.hip, scan_words.hip, scan_groups.hip, scan_case.hip, scan_sig.hip) */
+/* ------------------------------------------------------------------ the prefix chain of a pattern; the expansion frame (scan_all.hip, scan_words.hip, scan_groups.hip, scan_case.hip, scan_sig.hip, scan_approx.hip) */
 
 /* pfac_host.h's forEachChainMember on the device: visit(q) for the patterns that occur where pattern id is the longest -- id, then along
  * prefixPattern through `table` ([numIds + 1] {prefixPattern, chainLen} by id; null: every chain is the pair itself): at most
  * max(1, chainLen[id]) of them, none for an id outside [1, numIds]; ends at such an id, or where visit returns false.  The one place where an id
- * is checked before it indexes the table and where a walk is bounded whatever the table says: the chain walks of scan_words.hip, scan_groups.hip, scan_case.hip, scan_sig.hip,
+ * is checked before it indexes the table and where a walk is bounded whatever the table says: the chain walks of scan_words.hip, scan_groups.hip, scan_case.hip, scan_sig.hip, scan_approx.hip,
  * scan_count.hip and scan_segcount.hip are calls of this (scan_rules.hip keeps its two loops, profiles/expand_refactor_resources.txt says why;
  * scan_all.hip writes a fixed number of slots per pair) */
 template <class Visit>
@@ -725,7 +725,8 @@ struct ExpandFrame {
 /* Both passes, by blocks of BLOCK threads, a thread per pair and trip.  value(k): the number of entries of pair k.  members(k, emit): the same
  * entries again, emit(q) for each in order; the frame gives them the slots behind the entries in front of pair k, checks every slot against the
  * capacity and stores (q, the pair's position) -- the one pair store of an expansion; emit(q, at) stores (q, at) instead: a unit whose entries
- * lie elsewhere than their pair (scan_sig.hip: the start of a signature in front of its anchor).  hook(k, before), where given, runs for every
+ * lie elsewhere than their pair (scan_sig.hip: the start of a signature in front of its anchor; scan_approx.hip also reads emit.o and emit.f.capacity
+ * to put a third value into the same slot).  hook(k, before), where given, runs for every
  * pair in front of its store, whatever the capacity.  A thread runs hook and members right behind its value(k), which may leave them what it loaded */
 struct NoExpandHook { __device__ __forceinline__ void operator()(size_t, unsigned long long) const {} };
 struct ExpandEmit {

@@ -1135,7 +1135,7 @@ PFAC_status_t PFACX_casePairsFromDevice(PFACX_case_t cs, const char *d_input, si
  * PFACX_matchWords*; PFACX_sigMatchFromDevice also the pair scratch of PFACX_matchAll*.
  * COST: the compacted scan over the anchors with its ordering launches, then two passes over the pairs that compare the masked
  * bytes of the candidates, four at a time; a thread per pair, so long signatures and large classes make lanes uneven.
- * OUT OF SCOPE: variable gaps (`*`, `{n-m}`), alternatives and negated bytes; caseless signatures; segment bounds of a batch; the pairs of
+ * OUT OF SCOPE (bounded gaps between parts: PFACX_gapsig* below): alternatives and negated bytes; caseless signatures; segment bounds of a batch; the pairs of
  * streams and flow sets; a full-result-vector form; a list sorted by start; a compiled-file form. */
 typedef struct PFACX_sig_s *PFACX_sig_t;
 PFAC_status_t PFACX_sigOpen    (PFAC_handle_t handle, const unsigned char *h_values, const unsigned char *h_masks,
@@ -1224,6 +1224,76 @@ PFAC_status_t PFACX_approxMatchFromHost  (PFACX_approx_t approx, char *h_input, 
 PFAC_status_t PFACX_approxPairsFromDevice(PFACX_approx_t approx, const char *d_input, size_t size,
                                           const int *d_pairIds, const int *d_pairPos, size_t numPairs,
                                           int *d_ids, int *d_pos, int *d_mis /* may be NULL */, size_t capacity, size_t *h_num_matched);
+
+/* Signatures with bounded gaps between parts: the variable-length signatures of the ClamAV / YARA kind -- `4D 5A {2-6} 50 45 00 00`,
+ * `E8 ?? ?? ?? ?? [0-8] 5? C3`.  As for PFACX_sig* the library picks one fully specified run of each signature as its ANCHOR, loads the distinct
+ * anchors as the handle's pattern set, scans for them with the product kernels and verifies every signature of every anchor occurrence against
+ * the input; here the verification searches over the gap widths.
+ *   SIGNATURES.  S signatures, ids 1 .. S in the order given.  Signature i is a sequence of m_i parts, 1 <= m_i <= 64; a part is a string of 1 ..
+ *   65 535 byte pairs (v, m) as in PFACX_sig*, canonicalised v &= m; between part j and part j + 1 stands a gap [lo_j, hi_j], 0 <= lo_j <= hi_j
+ *   <= 65 535.  The SLACK, the sum of hi_j - lo_j, is at most PFACX_GAPSIG_MAX_SLACK = 63: where a part can lie relative to any other then fits
+ *   one 64-bit mask.  The span, the sum of the lengths and of the hi_j, stays below 2^31 - 1 (the other limits keep it below 2^23).
+ *   EMBEDDING of signature i at start s in n bytes: offsets o_0 = s, o_{j+1} = o_j + len_j + g_j with lo_j <= g_j <= hi_j, 0 <= s,
+ *   o_{m-1} + len_{m-1} <= n, and (in[o_j + k] ^ v_{j,k}) & m_{j,k} == 0 for every part j and byte k.  OCCURRENCE: signature i occurs at s iff an
+ *   embedding at s exists.  THE LIST holds one entry (id, start, end) per (id, start) that occurs; end is the SMALLEST o_{m-1} + len_{m-1} over
+ *   all embeddings at s -- a minimum over all gap choices, not what a lazy left-to-right choice finds.  Every signature is its own entry: two
+ *   identical signatures are both reported.  A signature of one part gives the entries PFACX_sig* gives for it, with end = start + len.
+ *   ANCHOR.  The rule of PFACX_sigOpen over all parts: a candidate is a run of bytes with mask 0xFF and a value other than 0x0A inside ONE part (a
+ *   run never crosses a part boundary, not even over a gap {0}); the anchor is the longest run, of equal ones the one in the lowest part, then
+ *   the leftmost, cut to its first maxAnchorLen bytes; 0 stands for 32 (the unmeasured supposition of PFACX_sigOpen).  A signature without such
+ *   a byte is refused.  Callers rely on PFACX_gapsigGetAnchors.
+ *   EACH OCCURRENCE ONCE.  The anchor part a may lie at several offsets for one start.  (id, s) is listed by the occurrence of part a at the
+ *   SMALLEST offset x that lies on some embedding at s -- not the smallest x that the parts in front of a reach: an x whose tail cannot be
+ *   completed owns nothing.
+ *   ORDER: by the owning anchor occurrence, x + anchorOff ascending; at one position the longer anchor first; within one anchor ids descend;
+ *   within one (anchor occurrence, signature) starts ascend.  It is NOT sorted by start.
+ * PFACX_gapsigOpen: CSR form in host memory, copied -- h_values / h_masks[h_partOff[j], h_partOff[j + 1]) are part j, the parts of signature i are
+ * h_sigPart[i - 1] .. h_sigPart[i] - 1, h_gapLo[j] / h_gapHi[j] the gap BEHIND part j (the entry of a signature's last part is not read).  It
+ * loads the distinct anchors exactly as PFACX_sigOpen does: the handle's set is REPLACED, the handle becomes case-sensitive, handle id q is the
+ * q-th distinct anchor in order of first appearance, and it checks under the handle's lock that the set it adopts is the one it loaded.
+ * PFAC_STATUS_INVALID_PARAMETER, with the handle's set untouched: a required null pointer (all six arrays), numSigs == 0 or >= 2^31 - 1, and --
+ * with the id of the FIRST such signature in *badSig (may be NULL; else 0) -- no part or more than 64, an empty part or one longer than 65 535
+ * bytes, lo > hi or hi > 65 535, a slack above 63, a span of 2^31 - 1 or more; behind those, by id, a signature without a fully specified
+ * byte other than 0x0A.
+ * PFACX_gapsigOpenText: a parser in front of it and nothing else: the grammar of PFACX_sigOpenText plus gap tokens between byte pairs: `{n}`,
+ * `{n-m}`, `{-m}` (0 .. m), and the same in brackets, `[n]`, `[n-m]`, `[-m]`; decimal, no blanks inside.  `??` bytes stay inside their part.
+ * Refused with the 1-based line in *badLine: all PFACX_sigOpenText refuses, a gap at the start or the end of a line, two gaps in a row, n > m, an
+ * unbounded gap (`*`, `{n-}`), an empty or unclosed token, a number above 65 535, and a line the binary form refuses.
+ * PFACX_gapsigGetAnchors: by signature id (n >= S + 1 entries each, entry 0 is 0; an array may be NULL) the handle's pattern id of the anchor,
+ * the part that holds it, its offset inside that part and its length.
+ * The object belongs to the handle like a signature object (PFAC_destroy closes it; stale after another read; host-only handles can open).
+ * The three match calls are those of PFACX_approx* word for word, with d_end (may be NULL in every form; only ever written below min(the list,
+ * capacity)) in the place of d_mis: the device form needs capacity >= size and its arrays take the scan's unordered list first; the host and
+ * pairs forms take any capacity, 0 with null arrays is the count query; a longer list: the first `capacity` entries, the full length, and
+ * PFACX_STATUS_OUTPUT_TRUNCATED; size >= 2^31 or a required null pointer: PFAC_STATUS_INVALID_PARAMETER; size == 0: success, nothing touched;
+ * a device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST; the pairs form ignores ids outside [1, F] and positions outside [0, size),
+ * refuses output arrays (d_end included) that overlap the pair arrays and numPairs >= 2^31, and owns an occurrence only through pairs of its
+ * list.  All calls are synchronous and take the handle's lock.  The input is never modified, and nothing outside it is read.
+ * MEMORY.  The tables, made by the first device call, are state of the object (deviceTableBytes, kept by PFACX_trim, freed by
+ * PFACX_gapsigClose): 16 bytes per signature, 16 per part, 4 (F + 2) bytes, and twice the bytes of each part padded to a multiple of 4.
+ * Grow-only handle scratch as for PFACX_sig*.
+ * COST: the compacted scan over the anchors with its ordering launches, then two passes over the pairs; a thread per pair runs the
+ * whole search of a candidate -- up to 64 starts, each up to parts x 64 masked compares, most of which end in their first dword.
+ * OUT OF SCOPE: unbounded gaps and slack above 63; alternatives and negated bytes; caseless parts; anchors chosen by rarity; a wave per long
+ * search; segment bounds, stream and flow pairs; a full-result-vector form; a list sorted by start. */
+#define PFACX_GAPSIG_MAX_SLACK 63
+typedef struct PFACX_gapsig_s *PFACX_gapsig_t;
+PFAC_status_t PFACX_gapsigOpen(PFAC_handle_t handle, const unsigned char *h_values, const unsigned char *h_masks,
+                               const size_t *h_partOff /* numParts + 1: bytes */, const size_t *h_sigPart /* numSigs + 1: parts */,
+                               const unsigned int *h_gapLo, const unsigned int *h_gapHi /* numParts each; entry of a signature's last part ignored */,
+                               size_t numSigs, size_t maxAnchorLen /* 0: 32 */, PFACX_gapsig_t *sig, int *badSig /* may be NULL */);
+PFAC_status_t PFACX_gapsigOpenText(PFAC_handle_t handle, const char *text, size_t size, size_t maxAnchorLen /* 0: 32 */,
+                                   PFACX_gapsig_t *sig, int *badLine /* may be NULL */);
+PFAC_status_t PFACX_gapsigGetAnchors(PFACX_gapsig_t sig, int *h_anchorId, int *h_anchorPart, int *h_anchorOff /* inside that part */,
+                                     int *h_anchorLen, size_t n /* >= S + 1, indexed by ID */);
+PFAC_status_t PFACX_gapsigClose(PFACX_gapsig_t sig);
+PFAC_status_t PFACX_gapsigMatchFromDevice(PFACX_gapsig_t sig, char *d_input, size_t size,
+                                          int *d_ids, int *d_pos, int *d_end /* may be NULL */, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_gapsigMatchFromHost  (PFACX_gapsig_t sig, char *h_input, size_t size,
+                                          int *h_ids, int *h_pos, int *h_end /* may be NULL */, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_gapsigPairsFromDevice(PFACX_gapsig_t sig, const char *d_input, size_t size,
+                                          const int *d_pairIds, const int *d_pairPos, size_t numPairs,
+                                          int *d_ids, int *d_pos, int *d_end /* may be NULL */, size_t capacity, size_t *h_num_matched);
 
 /* Split: the offsets that cut a buffer into records at the bytes of a delimiter class -- the `d_offsets` that PFACX_matchBatch*,
  * PFACX_matchAllBatchFromDevice, PFACX_rules*, PFACX_countBatch* and PFACX_groups* take, made where the text lies: the lines of a log, the records

@@ -516,6 +516,40 @@ typedef struct {
 } PFACX_approxRun_t;
 PFAC_status_t PFACX_approxRun(PFAC_handle_t handle, const PFACX_approxRun_t *run, size_t *h_total);
 
+/* Signatures with bounded gaps between parts (no reference counterpart; include/pfac_ext.h: PFACX_gapsig*), scan_gapsig.hip.
+ * PFACX_gapsigRun: the gapped signatures that occur around an ordered list of LONGEST pairs of the anchor set.  d_input, size, the pair arrays,
+ * count, d_table and numIds are those of PFACX_sigRun.  The signatures anchored by pattern q are d_sigs[d_sigOff[q], d_sigOff[q + 1]) (d_sigOff:
+ * numIds + 2 entries; the range is clamped to numSigs), 16 bytes each (pfac_context.h: GapSigEntry): {signature id, first part, number of parts |
+ * anchor part << 16, offset of the anchor inside that part}, by signature id descending.  d_parts, numParts entries of 16 bytes (GapSigPart):
+ * {len, dword index of its bytes in d_blob, lo, hi}, the gap behind the part.  d_blob, blobWords dwords: per part (len + 3) / 4 value dwords, then
+ * as many mask dwords, values already ANDed with their masks, the bytes behind len with mask 0.  An entry with no part or more than 64, parts
+ * outside the table or an anchor part outside the entry is skipped; so is, wherever it is met, a part that is empty, has hi < lo or hi - lo > 63,
+ * or whose dwords do not lie inside the blob: nothing lies there.  Only each gap is tested, not the sum over a signature: where a table's slack
+ * exceeds 63 the distances past bit 63 are dropped without a word -- fewer entries, nothing out of bounds; the library's own tables never do.  Part a of a chain member at pair position p lies at x = p - offset; (id, s,
+ * end) is kept iff an embedding of the signature at s has part a at x, no embedding at s has it at a smaller offset (every occurrence once, by
+ * the smallest offset of its anchor part), and end is the smallest end over all embeddings at s (include/pfac_ext.h says what an embedding is).
+ * Output: (signature id, s) into d_ids / d_pos and end into d_end (may be null) in pair order, chain order, table order, s ascending; nothing at
+ * or beyond `capacity` (0: all three may be null); *h_total = the full length of the list.  The output arrays must not overlap the pair arrays
+ * (the caller checks).  Synchronous. */
+typedef struct {
+    const char *d_input;
+    size_t size;
+    const int *d_pairIds, *d_pairPos;
+    size_t count;
+    const void *d_table;
+    size_t numIds;
+    const unsigned int *d_sigOff;
+    const void *d_sigs;
+    size_t numSigs;
+    const void *d_parts;
+    size_t numParts;
+    const unsigned int *d_blob;
+    size_t blobWords;
+    int *d_ids, *d_pos, *d_end;
+    size_t capacity;
+} PFACX_gapsigRun_t;
+PFAC_status_t PFACX_gapsigRun(PFAC_handle_t handle, const PFACX_gapsigRun_t *run, size_t *h_total);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -532,7 +566,7 @@ PFAC_status_t PFACX_approxRun(PFAC_handle_t handle, const PFACX_approxRun_t *run
     X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun) X(segcount_run_ptr, PFACX_segCountRun) \
     X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun) X(split_run_ptr, PFACX_splitRun) \
     X(locate_run_ptr, PFACX_locateRun) X(capture_run_ptr, PFACX_captureRun) X(case_run_ptr, PFACX_caseRun) \
-    X(sig_run_ptr, PFACX_sigRun) X(approx_run_ptr, PFACX_approxRun)
+    X(sig_run_ptr, PFACX_sigRun) X(approx_run_ptr, PFACX_approxRun) X(gapsig_run_ptr, PFACX_gapsigRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

@@ -41,6 +41,9 @@ PFACX_CASE_BLOCKS_PER_CU = 8                    # scan_passes.h: offsetBlocks, t
 PFACX_APPROX_BLOCK = 256                        # scan_approx.hip: kApproxBlock, the pairs one block of the approximate passes takes (never more than eight blocks per CU)
 PFACX_APPROX_BLOCKS_PER_CU = 8                  # scan_passes.h: offsetBlocks, as for the case passes
 PFACX_APPROX_MAX_MISMATCHES = 7                 # pfac_ext.h: the largest budget of a pattern of PFACX_approxOpen
+PFACX_GAPSIG_BLOCK = 256                        # scan_gapsig.hip: kGapSigBlock, the pairs one block of the gapped-signature passes takes (never more than eight blocks per CU)
+PFACX_GAPSIG_BLOCKS_PER_CU = 8                  # scan_passes.h: offsetBlocks, as for the case passes
+PFACX_GAPSIG_MAX_SLACK = 63                     # pfac_ext.h: the largest sum of hi - lo over the gaps of one signature of PFACX_gapsigOpen
 PFACX_GROUPS_BLOCK = 256                        # scan_groups.hip: kGroupsBlock, the pairs one block of the group passes takes (never more than eight blocks per CU)
 PFACX_WORDS_BLOCK = 256                         # scan_words.hip: kWordsBlock, the pairs one block of the boundary passes takes (never more than eight blocks per CU)
 PFACX_SPLIT_BEFORE = 1                          # pfac_ext.h: PFACX_split* a delimiter opens the segment behind it instead of closing the one in front
@@ -177,6 +180,8 @@ EXPORTED_SYMBOLS = (
     "PFACX_sigPairsFromDevice",
     "PFACX_approxOpen", "PFACX_approxGetPieces", "PFACX_approxClose", "PFACX_approxMatchFromDevice", "PFACX_approxMatchFromHost",
     "PFACX_approxPairsFromDevice",
+    "PFACX_gapsigOpen", "PFACX_gapsigOpenText", "PFACX_gapsigGetAnchors", "PFACX_gapsigClose", "PFACX_gapsigMatchFromDevice",
+    "PFACX_gapsigMatchFromHost", "PFACX_gapsigPairsFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -199,6 +204,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_caseRun",
     "PFACX_sigRun",
     "PFACX_approxRun",
+    "PFACX_gapsigRun",
 )
 
 
@@ -407,6 +413,18 @@ def load_library() -> C.CDLL:
         lib.PFACX_approxMatchFromDevice.argtypes = within
         lib.PFACX_approxMatchFromHost.argtypes = within
         lib.PFACX_approxPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_size_t, SZ]
+    if hasattr(lib, "PFACX_gapsigOpen"):
+        SZ = C.POINTER(C.c_size_t)
+        lib.PFACX_gapsigOpen.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                         C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+        lib.PFACX_gapsigOpenText.argtypes = [H, C.c_char_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+        lib.PFACX_gapsigGetAnchors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.PFACX_gapsigClose.argtypes = [C.c_void_p]
+        gapped = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, SZ]
+        lib.PFACX_gapsigMatchFromDevice.argtypes = gapped
+        lib.PFACX_gapsigMatchFromHost.argtypes = gapped
+        lib.PFACX_gapsigPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_size_t, SZ]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
@@ -1200,6 +1218,43 @@ class PFAC:
         self._ret(st, "PFACX_approxOpen", check)
         return ApproxSet(self, a, count if st == 0 else 0, int(budgets.sum()) + count if st == 0 else 0, bad.value, st)
 
+    # -- signatures with bounded gaps between parts (include/pfac_ext.h: PFACX_gapsig*) ----------------
+    def gapsigOpen(self, values, masks, part_off, sig_part, gap_lo, gap_hi, max_anchor_len: int = 0, check: bool = True) -> "GapSigSet":
+        """``PFACX_gapsigOpen`` -> a :class:`GapSigSet` of this handle (``.status`` holds the call's status, ``.bad`` the id of a refused
+        signature): the parts in CSR form, `values` / `masks` uint8, `part_off` numParts + 1 byte offsets, `sig_part` numSigs + 1 part indices,
+        `gap_lo` / `gap_hi` one entry per part (the gap behind it; a signature's last is ignored); all are copied.  The handle's pattern set
+        is REPLACED by the distinct anchors."""
+        import numpy as np
+        values = np.ascontiguousarray(values, dtype=np.uint8)
+        masks = np.ascontiguousarray(masks, dtype=np.uint8)
+        part_off = np.ascontiguousarray(part_off, dtype=np.uint64)
+        sig_part = np.ascontiguousarray(sig_part, dtype=np.uint64)
+        gap_lo = np.ascontiguousarray(gap_lo, dtype=np.uint32)
+        gap_hi = np.ascontiguousarray(gap_hi, dtype=np.uint32)
+        parts = max(0, int(part_off.size) - 1)
+        if gap_lo.size != parts or gap_hi.size != parts:
+            raise ValueError(f"{gap_lo.size} / {gap_hi.size} gaps for {parts} parts")
+        if sig_part.size and int(sig_part.max()) > parts:
+            raise ValueError(f"sig_part reaches part {int(sig_part.max())} of {parts}")
+        pad, pad32 = np.zeros(1, dtype=np.uint8), np.zeros(1, dtype=np.uint32)
+        s, bad = C.c_void_p(), C.c_int(0)
+        count = max(0, int(sig_part.size) - 1)
+        st = self._lib.PFACX_gapsigOpen(self._h, (values if values.size else pad).ctypes.data, (masks if masks.size else pad).ctypes.data,
+                                        part_off.ctypes.data if part_off.size else None, sig_part.ctypes.data if sig_part.size else None,
+                                        (gap_lo if parts else pad32).ctypes.data, (gap_hi if parts else pad32).ctypes.data, count, max_anchor_len,
+                                        C.byref(s), C.byref(bad))
+        self._ret(st, "PFACX_gapsigOpen", check)
+        return GapSigSet(self, s, count if st == 0 else 0, bad.value, st)
+
+    def gapsigOpenText(self, text: bytes, max_anchor_len: int = 0, check: bool = True) -> "GapSigSet":
+        """``PFACX_gapsigOpenText`` -> a :class:`GapSigSet` (``.bad``: the 1-based line that was refused): one signature per line of hex digit
+        pairs (``??``, ``x?``, ``?x``) with gap tokens ``{n}``, ``{n-m}``, ``{-m}``, ``[n]``, ``[n-m]``, ``[-m]`` between them."""
+        text = bytes(text)
+        s, bad = C.c_void_p(), C.c_int(0)
+        st = self._lib.PFACX_gapsigOpenText(self._h, text, len(text), max_anchor_len, C.byref(s), C.byref(bad))
+        self._ret(st, "PFACX_gapsigOpenText", check)
+        return GapSigSet(self, s, text.count(b"\n") if st == 0 else 0, bad.value, st)
+
     # -- numpy conveniences over matchFromHost (still the C ABI underneath) ----------
     def match_host_array(self, data):
         import numpy as np
@@ -1694,6 +1749,77 @@ class ApproxSet:
         if st != 0 or n2 != n:
             raise PFACError(st, "PFACX_approxMatchFromHost", f"{n2} entries behind a count query that said {n}")
         return pos[:n].copy(), ids[:n].copy(), mis[:n].copy()
+
+
+class GapSigSet:
+    """One gapped-signature object (``PFACX_gapsig_t``): signatures with bounded gaps between parts over the anchors it loaded into its handle.
+    Every match call returns ``(status, full length of the list)``; OUTPUT_TRUNCATED is returned, not raised.  The list holds (signature id,
+    start) and the smallest end in a third array, ordered by the owning anchor occurrence, not by start.  A context manager: it closes itself."""
+
+    def __init__(self, handle: "PFAC", sig: C.c_void_p, num_sigs: int = 0, bad: int = 0, status: int = 0):
+        self._owner = handle
+        self._lib = handle._lib
+        self._c = sig
+        self.num_sigs = num_sigs
+        self.bad = bad
+        self.status = status
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self._c:
+            self.close(check=False)
+
+    def _ret(self, st: int, where: str, check: bool) -> int:
+        if check and st != 0:
+            raise PFACError(st, where, error_string(st))
+        return st
+
+    def anchors(self, check: bool = True):
+        """``PFACX_gapsigGetAnchors`` -> (anchor_id, anchor_part, anchor_off, anchor_len), int32 arrays of num_sigs + 1 entries by signature id."""
+        import numpy as np
+        n = self.num_sigs + 1
+        out = tuple(np.full(n, -7, dtype=np.int32) for _ in range(4))
+        st = self._lib.PFACX_gapsigGetAnchors(self._c, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, out[3].ctypes.data, n)
+        self._ret(st, "PFACX_gapsigGetAnchors", check)
+        return out
+
+    def match_device(self, d_input: int, size: int, d_ids, d_pos, d_end, capacity: int, check: bool = True):
+        """``PFACX_gapsigMatchFromDevice``: capacity >= size entries in each device array; d_end may be None."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_gapsigMatchFromDevice(self._c, d_input, size, d_ids, d_pos, d_end, capacity, C.byref(n))
+        return self._ret(st, "PFACX_gapsigMatchFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def match_host(self, h_input: int, size: int, h_ids, h_pos, h_end, capacity: int, check: bool = True):
+        """``PFACX_gapsigMatchFromHost``: follows PFAC_setPlatform (the CPU platforms run on the CPU); any capacity, 0 with null arrays: the count."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_gapsigMatchFromHost(self._c, h_input, size, h_ids, h_pos, h_end, capacity, C.byref(n))
+        return self._ret(st, "PFACX_gapsigMatchFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def pairs_device(self, d_input: int, size: int, d_pair_ids, d_pair_pos, num_pairs: int, d_ids, d_pos, d_end, capacity: int, check: bool = True):
+        """``PFACX_gapsigPairsFromDevice``: the same list from an ordered LONGEST pair list of the handle over the same input (the output of
+        matchFromDeviceReduce).  It runs no scan."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_gapsigPairsFromDevice(self._c, d_input, size, d_pair_ids, d_pair_pos, num_pairs, d_ids, d_pos, d_end, capacity, C.byref(n))
+        return self._ret(st, "PFACX_gapsigPairsFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def close(self, check: bool = True) -> int:
+        st = self._lib.PFACX_gapsigClose(self._c)
+        self._c = C.c_void_p()
+        return self._ret(st, "PFACX_gapsigClose", check)
+
+    def match_host_array(self, data):
+        """match_host over a numpy array -> (pos, ids, end) of the whole list: the count query first, then arrays of exactly that length."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        _, n = self.match_host(buf.ctypes.data, data.size, None, None, None, 0)
+        ids, pos, end = (np.full(max(1, n), -7, dtype=np.int32) for _ in range(3))
+        st, n2 = self.match_host(buf.ctypes.data, data.size, ids.ctypes.data, pos.ctypes.data, end.ctypes.data, n)
+        if st != 0 or n2 != n:
+            raise PFACError(st, "PFACX_gapsigMatchFromHost", f"{n2} entries behind a count query that said {n}")
+        return pos[:n].copy(), ids[:n].copy(), end[:n].copy()
 
 
 def rule_member_dtype():

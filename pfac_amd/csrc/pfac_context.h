@@ -39,6 +39,12 @@ struct alignas(16) SigEntry { int id, anchorOff, len, blobOff; };   /* one signa
 /* one (pattern, piece) of a piece's class (approx_api.cpp, scan_approx.hip), one 16-byte load: the pattern's id, the dword index of its bytes in the
  * blob, the piece's start in the pattern | the pattern's length << 16 (both <= 65 535), the pattern's budget k | the piece's index j << 8 (j <= k <= 7) */
 struct alignas(16) ApproxEntry { int id, blobOff; unsigned int startLen, budgetPiece; };
+/* one gapped signature of an anchor's class (gapsig_api.cpp, scan_gapsig.hip), one 16-byte load: the signature's id, the index of its first part in
+ * the part table, its number of parts (1 .. 64) | the index of its anchor part << 16, the anchor's offset inside that part */
+struct alignas(16) GapSigEntry { int id; unsigned int firstPart, partsAnchor, anchorOff; };
+/* one part of a gapped signature, one 16-byte load: its length (1 .. 65 535), the dword index of its value dwords in the blob (the mask dwords lie
+ * behind them, as for SigEntry), the gap [lo, hi] between it and the next part (both 0 behind a signature's last part) */
+struct alignas(16) GapSigPart { unsigned int len, blobOff, lo, hi; };
 #ifndef PFAC_WORK_PARTS
 #define PFAC_WORK_PARTS 2
 #endif
@@ -82,7 +88,8 @@ constexpr HostSlot kHostCapture = {86, 88};      /* a capture call: the 64-bit n
 constexpr HostSlot kHostCase = {90, 92};         /* a case call: the 64-bit length of its list (scan_case.hip, by pfac_array_scan) */
 constexpr HostSlot kHostSig = {94, 96};          /* a signature call: the 64-bit length of its list (scan_sig.hip, by pfac_array_scan) */
 constexpr HostSlot kHostApprox = {98, 100};      /* an approximate call: the 64-bit length of its list (scan_approx.hip, by pfac_array_scan) */
-constexpr int kHostWords = 102;
+constexpr HostSlot kHostGapSig = {102, 104};     /* a gapped-signature call: the 64-bit length of its list (scan_gapsig.hip, by pfac_array_scan) */
+constexpr int kHostWords = 106;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -504,12 +511,16 @@ struct DeviceScratch {
      * list of PFACX_approxMatchFromDevice is allPairs, the prefix table allTable: shared.  The piece tables of an approximate object are state of
      * that object, not scratch (approx_api.cpp) */
     DeviceBuffer<char> approxSet;
+    /* the gapped-signature calls (PFACX_gapsig*, scan_gapsig.hip): the 64-bit list offsets of the blocks of its pair passes, sized like caseSet; the
+     * pair list of PFACX_gapsigMatchFromDevice is allPairs, the prefix table allTable: shared.  The signature and part tables of a gapped-signature
+     * object are state of that object, not scratch (gapsig_api.cpp) */
+    DeviceBuffer<char> gapsigSet;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines); f(linesContext);
-        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet); f(sigSet); f(approxSet);
+        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet); f(sigSet); f(approxSet); f(gapsigSet);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }

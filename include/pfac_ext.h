@@ -1295,6 +1295,62 @@ PFAC_status_t PFACX_gapsigPairsFromDevice(PFACX_gapsig_t sig, const char *d_inpu
                                           const int *d_pairIds, const int *d_pairPos, size_t numPairs,
                                           int *d_ids, int *d_pos, int *d_end /* may be NULL */, size_t capacity, size_t *h_num_matched);
 
+/* Patterns matched within k EDITS, insertions and deletions included: a typed keyword (`pasword`, `passsword`), OCR output that drops or doubles
+ * a letter, a DNA read with an indel, a byte sequence with an instruction inserted -- what PFACX_approx* leaves out of scope.  The pigeonhole cut
+ * carries over: an alignment with at most k edits over k + 1 disjoint parts leaves one part untouched, so its piece is exact somewhere in the
+ * input.  The exact piece fixes only a diagonal, not a start, so every candidate is verified by a banded dynamic program.
+ *   PATTERNS.  S byte strings, ids 1 .. S in the order given, L_i bytes; h_budget[i - 1] = k_i, the number of edits, 0 .. PFACX_EDIT_MAX_EDITS.
+ *   An edit is a substituted, an inserted or a deleted byte, each at cost 1 (Levenshtein).  Identical patterns are both reported.
+ *   DISTANCE AT AN END.  For an end e, 0 <= e <= n ("the match ends in front of in[e]"), D_i(e) = min over 0 <= s <= e of ed(pat_i, in[s, e)):
+ *   Sellers' recurrence C[0][c] = 0, C[r][0] = r, C[r][c] = min(C[r-1][c-1] + (pat[r-1] != in[c-1]), C[r-1][c] + 1, C[r][c-1] + 1),
+ *   D(e) = C[L][e].  Nothing outside [0, n) exists: a start in front of 0 or an end behind n is no occurrence.
+ *   OCCURRENCE AND ENTRY.  Pattern i occurs at end e iff D_i(e) <= k_i.  The entry is (id, start, end, distance): distance = D_i(e), start = the
+ *   LARGEST s with ed(pat_i, in[s, e)) = D_i(e), the shortest best match.  L > k is enforced, so start < end always.
+ *   WHICH ENDS.  flags 0: every end that occurs, the textbook output -- an exact copy with k = 2 gives five entries.  PFACX_EDIT_BEST_ENDS (a
+ *   flag of the open call): only the ends with all three of D(e) <= k, D(e - 1) > D(e), and e == n or D(e + 1) >= D(e).  This is a three-point
+ *   rule on D and nothing else; it is not a plateau analysis.
+ *   PIECES.  The cut is that of PFACX_approxOpen, word for word: part j is [j L / (k + 1), (j + 1) L / (k + 1)), its piece the first
+ *   min(part length, maxPieceLen) bytes of the part; the defaults are 4 and 32.  Refused with the id in *badPattern and the handle's set
+ *   untouched: L < (k + 1) minPieceLen, a piece that holds 0x0A, L > 65 535, k > 7, an empty pattern.  The distinct pieces are loaded as the
+ *   handle's set, which is REPLACED; the handle becomes case-sensitive, and handle id q is the q-th distinct piece.  PFACX_editGetPieces has the
+ *   signature and the meaning of PFACX_approxGetPieces.
+ *   CANDIDATES AND OWNERSHIP.  A candidate is (piece j of pattern i exact at input position p).  With o the start of the piece in the pattern
+ *   it has the diagonal d0 = p - o and COVERS the ends e with |e - L - d0| <= k, clipped to [0, n].  Every occurrence (i, e) is covered by at
+ *   least one candidate: the untouched part of a best alignment.  EACH OCCURRENCE ONCE: (i, e) is listed by the covering candidate with the
+ *   smallest j, and of those the smallest p.  The test reads the input, not the pair list: (i, e) is dropped on behalf of (j, p) where some
+ *   piece j' < j of the pattern is exact at a p' in [e - L + o_j' - k, e - L + o_j' + k] with the piece inside [0, n), or piece j itself at a
+ *   p' in [e - L + o_j - k, p - 1].  The pairs form therefore owns an occurrence only through pairs of its list.
+ *   THE LIST: by owning candidate position p ascending; at one position the longer piece first; within one piece string pattern ids
+ *   descending, then piece indices descending; within one (candidate, entry) ends ascending -- pair order, chain order, table order.  It is
+ *   NOT sorted by start or end, and it may be longer than size.
+ * PFACX_editOpen: the arguments of PFACX_approxOpen and `flags`: 0 or PFACX_EDIT_BEST_ENDS; any other bit: PFAC_STATUS_INVALID_PARAMETER.
+ * PFACX_editMatchFromDevice / FromHost / PFACX_editPairsFromDevice: d_pos takes the start; d_end and d_dist each stand where d_mis stands in
+ * PFACX_approx*: each may be NULL in every form, and each is only ever written below min(the list, capacity).  Everything else is that of
+ * PFACX_approx*, word for word: capacity and truncation (PFACX_STATUS_OUTPUT_TRUNCATED, the full length in *h_num_matched), the device form's
+ * capacity >= size, the 2^31 limits, size == 0, host-only handles, locking, staleness after another read, the refusal of output arrays (all
+ * four) that overlap the pair arrays, pairs with ids or positions that give nothing, deviceTableBytes / PFACX_trim / close.
+ * MEMORY: as PFACX_approx* (16 bytes per piece, 4 (F + 2) bytes, the patterns' bytes padded to dwords; scratch 8 (B + 1) bytes rounded to 256).
+ * COST: a thread per pair runs L x (4 k + 3) dependent cell updates for a candidate that holds, in both passes; a candidate that
+ * is far off ends at the first test of the early exit (every 4 rows).  This is far more than the compare of PFACX_approx*.
+ * OUT OF SCOPE: weighted edits and transpositions; caseless or masked patterns; pieces chosen by rarity; segment bounds, stream and flow pairs;
+ * a full-result-vector form; a list sorted by end; a compiled-file form; budgets above 7. */
+#define PFACX_EDIT_MAX_EDITS 7
+#define PFACX_EDIT_BEST_ENDS 1u
+typedef struct PFACX_edit_s *PFACX_edit_t;
+PFAC_status_t PFACX_editOpen(PFAC_handle_t handle, const unsigned char *h_bytes, const size_t *h_patOff /* numPatterns + 1 */,
+                             const int *h_budget /* numPatterns */, size_t numPatterns, size_t minPieceLen /* 0: 4 */,
+                             size_t maxPieceLen /* 0: 32 */, unsigned int flags, PFACX_edit_t *edit, int *badPattern /* may be NULL */);
+PFAC_status_t PFACX_editGetPieces(PFACX_edit_t edit, size_t *h_pieceOff /* numPatterns + 2, CSR by ID */, int *h_pieceId, int *h_pieceStart,
+                                  int *h_pieceLen, size_t n /* >= the number of pieces */);
+PFAC_status_t PFACX_editClose(PFACX_edit_t edit);
+PFAC_status_t PFACX_editMatchFromDevice(PFACX_edit_t edit, char *d_input, size_t size, int *d_ids, int *d_pos /* start */,
+                                        int *d_end /* may be NULL */, int *d_dist /* may be NULL */, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_editMatchFromHost  (PFACX_edit_t edit, char *h_input, size_t size, int *h_ids, int *h_pos /* start */,
+                                        int *h_end /* may be NULL */, int *h_dist /* may be NULL */, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_editPairsFromDevice(PFACX_edit_t edit, const char *d_input, size_t size,
+                                        const int *d_pairIds, const int *d_pairPos, size_t numPairs, int *d_ids, int *d_pos /* start */,
+                                        int *d_end /* may be NULL */, int *d_dist /* may be NULL */, size_t capacity, size_t *h_num_matched);
+
 /* Split: the offsets that cut a buffer into records at the bytes of a delimiter class -- the `d_offsets` that PFACX_matchBatch*,
  * PFACX_matchAllBatchFromDevice, PFACX_rules*, PFACX_countBatch* and PFACX_groups* take, made where the text lies: the lines of a log, the records
  * of a CRLF protocol, the fields of a line.

@@ -550,6 +550,38 @@ typedef struct {
 } PFACX_gapsigRun_t;
 PFAC_status_t PFACX_gapsigRun(PFAC_handle_t handle, const PFACX_gapsigRun_t *run, size_t *h_total);
 
+/* Patterns matched within k edits (no reference counterpart; include/pfac_ext.h: PFACX_edit*), scan_edit.hip.
+ * PFACX_editRun: the ends at which the patterns occur within their budgets around an ordered list of LONGEST pairs of the piece set.  d_input,
+ * size, the pair arrays, count, d_table and numIds are those of PFACX_sigRun; d_entryOff, d_entries (pfac_context.h: EditEntry), numEntries,
+ * d_blob, blobWords and maxPieceLen those of PFACX_approxRun.  maxBudget, 0 .. 7, is the largest k of the table: it selects the instantiation of
+ * the passes (k <= 1, k <= 3, k <= 7), and an entry with k > maxBudget, j > k or L <= k, or whose dwords leave the blob, is skipped.  bestEnds:
+ * the three-point rule of PFACX_EDIT_BEST_ENDS.  An entry of a chain member at pair position p is the candidate with the diagonal d0 = p - start;
+ * it is verified by the banded dynamic program of DESIGN.md 5y and lists the ends e with |e - L - d0| <= k, 0 <= e <= size, at which the pattern
+ * occurs (and which pass the three-point rule where bestEnds) and which no candidate with a smaller piece index, or the same piece at a smaller
+ * position, covers: every occurrence once.
+ * Output: (pattern id, start) into d_ids / d_pos, the end into d_end and the distance into d_dist (each may be null) in pair order, chain order,
+ * table order, ends ascending; nothing at or beyond `capacity` (0: all four may be null); *h_total = the full length of the list.  The output
+ * arrays must not overlap the pair arrays (the caller checks).  Synchronous. */
+typedef struct {
+    const char *d_input;
+    size_t size;
+    const int *d_pairIds, *d_pairPos;
+    size_t count;
+    const void *d_table;
+    size_t numIds;
+    const unsigned int *d_entryOff;
+    const void *d_entries;
+    size_t numEntries;
+    const unsigned int *d_blob;
+    size_t blobWords;
+    size_t maxPieceLen;
+    unsigned int maxBudget;
+    int bestEnds;
+    int *d_ids, *d_pos, *d_end, *d_dist;
+    size_t capacity;
+} PFACX_editRun_t;
+PFAC_status_t PFACX_editRun(PFAC_handle_t handle, const PFACX_editRun_t *run, size_t *h_total);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -566,7 +598,8 @@ PFAC_status_t PFACX_gapsigRun(PFAC_handle_t handle, const PFACX_gapsigRun_t *run
     X(rules_run_ptr, PFACX_rulesRun) X(words_run_ptr, PFACX_wordsRun) X(segcount_run_ptr, PFACX_segCountRun) \
     X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun) X(split_run_ptr, PFACX_splitRun) \
     X(locate_run_ptr, PFACX_locateRun) X(capture_run_ptr, PFACX_captureRun) X(case_run_ptr, PFACX_caseRun) \
-    X(sig_run_ptr, PFACX_sigRun) X(approx_run_ptr, PFACX_approxRun) X(gapsig_run_ptr, PFACX_gapsigRun)
+    X(sig_run_ptr, PFACX_sigRun) X(approx_run_ptr, PFACX_approxRun) X(gapsig_run_ptr, PFACX_gapsigRun) \
+    X(edit_run_ptr, PFACX_editRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

@@ -43,6 +43,10 @@ PFACX_APPROX_BLOCKS_PER_CU = 8                  # scan_passes.h: offsetBlocks, a
 PFACX_APPROX_MAX_MISMATCHES = 7                 # pfac_ext.h: the largest budget of a pattern of PFACX_approxOpen
 PFACX_GAPSIG_BLOCK = 256                        # scan_gapsig.hip: kGapSigBlock, the pairs one block of the gapped-signature passes takes (never more than eight blocks per CU)
 PFACX_GAPSIG_BLOCKS_PER_CU = 8                  # scan_passes.h: offsetBlocks, as for the case passes
+PFACX_EDIT_BLOCK = 256                          # scan_edit.hip: kEditBlock, the pairs one block of the edit-distance passes takes (never more than eight blocks per CU)
+PFACX_EDIT_BLOCKS_PER_CU = 8                    # scan_passes.h: offsetBlocks, as for the case passes
+PFACX_EDIT_MAX_EDITS = 7                        # pfac_ext.h: the largest budget of a pattern of PFACX_editOpen
+PFACX_EDIT_BEST_ENDS = 1                        # pfac_ext.h: the open-time flag that keeps only the ends the three-point rule on D passes
 PFACX_GAPSIG_MAX_SLACK = 63                     # pfac_ext.h: the largest sum of hi - lo over the gaps of one signature of PFACX_gapsigOpen
 PFACX_GROUPS_BLOCK = 256                        # scan_groups.hip: kGroupsBlock, the pairs one block of the group passes takes (never more than eight blocks per CU)
 PFACX_WORDS_BLOCK = 256                         # scan_words.hip: kWordsBlock, the pairs one block of the boundary passes takes (never more than eight blocks per CU)
@@ -182,6 +186,8 @@ EXPORTED_SYMBOLS = (
     "PFACX_approxPairsFromDevice",
     "PFACX_gapsigOpen", "PFACX_gapsigOpenText", "PFACX_gapsigGetAnchors", "PFACX_gapsigClose", "PFACX_gapsigMatchFromDevice",
     "PFACX_gapsigMatchFromHost", "PFACX_gapsigPairsFromDevice",
+    "PFACX_editOpen", "PFACX_editGetPieces", "PFACX_editClose", "PFACX_editMatchFromDevice", "PFACX_editMatchFromHost",
+    "PFACX_editPairsFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -205,6 +211,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_sigRun",
     "PFACX_approxRun",
     "PFACX_gapsigRun",
+    "PFACX_editRun",
 )
 
 
@@ -426,6 +433,17 @@ def load_library() -> C.CDLL:
         lib.PFACX_gapsigMatchFromHost.argtypes = gapped
         lib.PFACX_gapsigPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_size_t, SZ]
+    if hasattr(lib, "PFACX_editOpen"):
+        SZ = C.POINTER(C.c_size_t)
+        lib.PFACX_editOpen.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_int)]
+        lib.PFACX_editGetPieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.PFACX_editClose.argtypes = [C.c_void_p]
+        edits = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, SZ]
+        lib.PFACX_editMatchFromDevice.argtypes = edits
+        lib.PFACX_editMatchFromHost.argtypes = edits
+        lib.PFACX_editPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_size_t, SZ]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -1218,6 +1236,32 @@ class PFAC:
         self._ret(st, "PFACX_approxOpen", check)
         return ApproxSet(self, a, count if st == 0 else 0, int(budgets.sum()) + count if st == 0 else 0, bad.value, st)
 
+    # -- patterns matched within k edits, indels included (include/pfac_ext.h: PFACX_edit*) ----------------
+    def editOpen(self, patterns, budgets, min_piece_len: int = 0, max_piece_len: int = 0, flags: int = 0, check: bool = True) -> "EditSet":
+        """``PFACX_editOpen`` -> an :class:`EditSet` of this handle (``.status`` holds the call's status, ``.bad`` the id of a refused pattern):
+        `patterns` is a list of bytes-likes, or the CSR pair ``(bytes uint8, offsets)``; `budgets` one k per pattern; `flags` 0 or
+        ``PFACX_EDIT_BEST_ENDS``; all are copied.  The handle's pattern set is REPLACED by the distinct pieces."""
+        import numpy as np
+        if isinstance(patterns, tuple):
+            blob = np.ascontiguousarray(patterns[0], dtype=np.uint8)
+            off = np.ascontiguousarray(patterns[1], dtype=np.uint64)
+        else:
+            patterns = [bytes(p) for p in patterns]
+            blob = np.frombuffer(b"".join(patterns), dtype=np.uint8)
+            off = np.zeros(len(patterns) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(p) for p in patterns])
+        budgets = np.ascontiguousarray(budgets, dtype=np.int32)
+        count = max(0, int(off.size) - 1)
+        if budgets.size != count:
+            raise ValueError(f"{budgets.size} budgets for {count} patterns")
+        pad = np.zeros(1, dtype=np.uint8)
+        e, bad = C.c_void_p(), C.c_int(0)
+        st = self._lib.PFACX_editOpen(self._h, (blob if blob.size else pad).ctypes.data, off.ctypes.data if off.size else None,
+                                      budgets.ctypes.data if budgets.size else None, count, min_piece_len, max_piece_len, flags, C.byref(e),
+                                      C.byref(bad))
+        self._ret(st, "PFACX_editOpen", check)
+        return EditSet(self, e, count if st == 0 else 0, int(budgets.sum()) + count if st == 0 else 0, bad.value, st)
+
     # -- signatures with bounded gaps between parts (include/pfac_ext.h: PFACX_gapsig*) ----------------
     def gapsigOpen(self, values, masks, part_off, sig_part, gap_lo, gap_hi, max_anchor_len: int = 0, check: bool = True) -> "GapSigSet":
         """``PFACX_gapsigOpen`` -> a :class:`GapSigSet` of this handle (``.status`` holds the call's status, ``.bad`` the id of a refused
@@ -1749,6 +1793,82 @@ class ApproxSet:
         if st != 0 or n2 != n:
             raise PFACError(st, "PFACX_approxMatchFromHost", f"{n2} entries behind a count query that said {n}")
         return pos[:n].copy(), ids[:n].copy(), mis[:n].copy()
+
+
+class EditSet:
+    """One edit-distance object (``PFACX_edit_t``): patterns matched within k edits (substitutions, insertions, deletions) over the pieces it
+    loaded into its handle.  Every match call returns ``(status, full length of the list)``; OUTPUT_TRUNCATED is returned, not raised.  The
+    list holds (pattern id, start) with the end and the distance in a third and a fourth array, ordered by the owning candidate's position,
+    not by start or end.  A context manager: it closes itself."""
+
+    def __init__(self, handle: "PFAC", edit: C.c_void_p, num_patterns: int = 0, num_pieces: int = 0, bad: int = 0, status: int = 0):
+        self._owner = handle
+        self._lib = handle._lib
+        self._c = edit
+        self.num_patterns = num_patterns
+        self.num_pieces = num_pieces                             # the sum of k + 1
+        self.bad = bad
+        self.status = status
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self._c:
+            self.close(check=False)
+
+    def _ret(self, st: int, where: str, check: bool) -> int:
+        if check and st != 0:
+            raise PFACError(st, where, error_string(st))
+        return st
+
+    def pieces(self, check: bool = True):
+        """``PFACX_editGetPieces`` -> (piece_off, piece_id, piece_start, piece_len): piece_off uint64 with num_patterns + 2 entries in CSR form by
+        pattern id, the others int32 with one entry per piece."""
+        import numpy as np
+        off = np.full(self.num_patterns + 2, 7, dtype=np.uint64)
+        out = tuple(np.full(max(1, self.num_pieces), -7, dtype=np.int32) for _ in range(3))
+        st = self._lib.PFACX_editGetPieces(self._c, off.ctypes.data, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, self.num_pieces)
+        self._ret(st, "PFACX_editGetPieces", check)
+        return (off,) + tuple(a[:self.num_pieces] for a in out)
+
+    def match_device(self, d_input: int, size: int, d_ids, d_pos, d_end, d_dist, capacity: int, check: bool = True):
+        """``PFACX_editMatchFromDevice``: capacity >= size entries in each device array; d_end and d_dist may be None."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_editMatchFromDevice(self._c, d_input, size, d_ids, d_pos, d_end, d_dist, capacity, C.byref(n))
+        return self._ret(st, "PFACX_editMatchFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def match_host(self, h_input: int, size: int, h_ids, h_pos, h_end, h_dist, capacity: int, check: bool = True):
+        """``PFACX_editMatchFromHost``: follows PFAC_setPlatform (the CPU platforms run on the CPU); any capacity, 0 with null arrays: the count."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_editMatchFromHost(self._c, h_input, size, h_ids, h_pos, h_end, h_dist, capacity, C.byref(n))
+        return self._ret(st, "PFACX_editMatchFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def pairs_device(self, d_input: int, size: int, d_pair_ids, d_pair_pos, num_pairs: int, d_ids, d_pos, d_end, d_dist, capacity: int,
+                     check: bool = True):
+        """``PFACX_editPairsFromDevice``: the same list from an ordered LONGEST pair list of the handle over the same input (the output of
+        matchFromDeviceReduce).  It runs no scan."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_editPairsFromDevice(self._c, d_input, size, d_pair_ids, d_pair_pos, num_pairs, d_ids, d_pos, d_end, d_dist, capacity,
+                                                 C.byref(n))
+        return self._ret(st, "PFACX_editPairsFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def close(self, check: bool = True) -> int:
+        st = self._lib.PFACX_editClose(self._c)
+        self._c = C.c_void_p()
+        return self._ret(st, "PFACX_editClose", check)
+
+    def match_host_array(self, data):
+        """match_host over a numpy array -> (ids, start, end, dist) of the whole list: the count query first, then arrays of exactly that length."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        _, n = self.match_host(buf.ctypes.data, data.size, None, None, None, None, 0)
+        ids, pos, end, dist = (np.full(max(1, n), -7, dtype=np.int32) for _ in range(4))
+        st, n2 = self.match_host(buf.ctypes.data, data.size, ids.ctypes.data, pos.ctypes.data, end.ctypes.data, dist.ctypes.data, n)
+        if st != 0 or n2 != n:
+            raise PFACError(st, "PFACX_editMatchFromHost", f"{n2} entries behind a count query that said {n}")
+        return ids[:n].copy(), pos[:n].copy(), end[:n].copy(), dist[:n].copy()
 
 
 class GapSigSet:

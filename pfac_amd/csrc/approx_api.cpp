@@ -3,10 +3,10 @@
  * PFACX_approxPairsFromDevice (include/pfac_ext.h): patterns matched within k mismatches.
  *
  * A pattern of L bytes with budget k occurs at s where at most k bytes of in[s, s + L) differ from its own.  PFACX_approxOpen checks the caller's
- * CSR arrays and copies them, cuts pattern i into k_i + 1 disjoint parts (planPatterns: part j is [j L / (k + 1), (j + 1) L / (k + 1)), its PIECE
+ * CSR arrays and copies them, cuts pattern i into k_i + 1 disjoint parts (piece_cut.h, shared with edit_api.cpp: planPatterns: part j is [j L / (k + 1), (j + 1) L / (k + 1)), its PIECE
  * the first min(part length, maxPieceLen) bytes) -- at any occurrence at least one part, and so its piece, is exact --, loads the distinct pieces
  * into the handle through the reader every pattern set goes through -- one line per piece, in order of first appearance, so handle id q is the q-th
- * distinct piece -- and builds per handle id q the entries of its class (buildTables): {pattern id, blobOff, start | L << 16, k | j << 8} by
+ * distinct piece -- and builds per handle id q the entries of its class (buildPieceTables): {pattern id, blobOff, start | L << 16, k | j << 8} by
  * pattern id descending, then piece index descending, in CSR form by q, with a dword-aligned blob of each pattern's bytes.  Every piece that
  * occurs at p is a prefix of the longest one there, so all three match forms work on the LONGEST pairs of the piece set and walk each pair's
  * prefix chain (Automaton::prefixPattern), member by member through its class: a pattern starts at p - start, must lie inside the input, holds
@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "pfac_host.h"
+#include "piece_cut.h"
 
 struct PFACX_approx_s : pfac_internal::HandleObject {
     size_t numIds = 0;                        /* F of the piece set it loaded */
@@ -52,110 +53,6 @@ struct PFACX_approx_s : pfac_internal::HandleObject {
 using namespace pfac_internal;
 
 namespace {
-
-constexpr size_t kMaxPatternLen = 65535, kDefaultMaxPiece = 32, kDefaultMinPiece = 4;
-constexpr size_t kMaxPatternBytes = (size_t)1 << 32;
-
-/* the caller's patterns, copied, with the pieces of each and the piece set as the reader's text */
-struct ApproxPlan {
-    std::vector<unsigned char> bytes;                 /* all patterns back to back */
-    std::vector<size_t> off;                          /* [S + 1] into bytes */
-    std::vector<int> budget;                          /* by pattern id */
-    size_t maxPiece = 0;
-    std::vector<unsigned int> pieceOff;               /* [S + 2] by pattern id */
-    std::vector<int> pieceId, pieceStart, pieceLen;   /* per piece */
-    std::vector<std::string> pieces;                  /* by handle id - 1: the distinct pieces in order of first appearance */
-    std::string text;                                 /* one line per distinct piece */
-};
-
-/* part j of a pattern of len bytes with budget k starts here; part k ends at len */
-inline size_t partStart(size_t j, size_t len, size_t k) { return j * len / (k + 1); }
-
-/* The plan of S patterns in CSR form.  INVALID_PARAMETER with *badPattern = the id of the pattern: an offset that does not ascend (an empty
- * pattern), a pattern longer than 65 535 bytes, a budget outside [0, 7], a pattern shorter than (k + 1) minPieceLen, a piece that holds '\n' */
-PFAC_status_t planPatterns(const unsigned char *h_bytes, const size_t *h_patOff, const int *h_budget, size_t numPatterns, size_t minPieceLen,
-                           size_t maxPieceLen, ApproxPlan *plan, int *badPattern)
-{
-    const size_t S = numPatterns, cut = maxPieceLen ? maxPieceLen : kDefaultMaxPiece, least = minPieceLen ? minPieceLen : kDefaultMinPiece;
-    size_t blobWords = 0, numPieces = 0;
-    for (size_t i = 1; i <= S; i++) {                                       /* nothing is allocated before every pattern has passed */
-        *badPattern = (int)i;
-        if (h_patOff[i] <= h_patOff[i - 1] || h_patOff[i] - h_patOff[i - 1] > kMaxPatternLen) return PFAC_STATUS_INVALID_PARAMETER;
-        const size_t len = h_patOff[i] - h_patOff[i - 1];
-        if (h_budget[i - 1] < 0 || h_budget[i - 1] > PFACX_APPROX_MAX_MISMATCHES) return PFAC_STATUS_INVALID_PARAMETER;
-        const size_t k = (size_t)h_budget[i - 1];
-        if (least > kMaxPatternLen || len < (k + 1) * least) return PFAC_STATUS_INVALID_PARAMETER;
-        const unsigned char *pat = h_bytes + h_patOff[i - 1];
-        for (size_t j = 0; j <= k; j++) {
-            const size_t from = partStart(j, len, k), plen = std::min(partStart(j + 1, len, k) - from, cut);
-            if (std::memchr(pat + from, '\n', plen) != nullptr) return PFAC_STATUS_INVALID_PARAMETER;   /* the pattern reader splits lines there */
-        }
-        blobWords += (len + 3) / 4;
-        numPieces += k + 1;
-    }
-    *badPattern = 0;
-    if (h_patOff[S] - h_patOff[0] > kMaxPatternBytes || blobWords > kMaxInt || numPieces > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
-    plan->maxPiece = cut;
-    plan->off.assign(S + 1, 0);
-    plan->budget.assign(S + 1, 0);
-    plan->pieceOff.assign(S + 2, 0u);
-    plan->bytes.assign(h_bytes + h_patOff[0], h_bytes + h_patOff[S]);
-    plan->pieceId.reserve(numPieces);
-    plan->pieceStart.reserve(numPieces);
-    plan->pieceLen.reserve(numPieces);
-    std::map<std::string, int> seen;
-    for (size_t i = 1; i <= S; i++) {
-        const size_t len = h_patOff[i] - h_patOff[i - 1], k = (size_t)h_budget[i - 1];
-        plan->off[i] = plan->off[i - 1] + len;
-        plan->budget[i] = (int)k;
-        const unsigned char *pat = plan->bytes.data() + plan->off[i - 1];
-        for (size_t j = 0; j <= k; j++) {
-            const size_t from = partStart(j, len, k), plen = std::min(partStart(j + 1, len, k) - from, cut);
-            const std::string piece(reinterpret_cast<const char *>(pat) + from, plen);
-            const auto placed = seen.emplace(piece, (int)plan->pieces.size() + 1);
-            if (placed.second) {
-                plan->pieces.push_back(piece);
-                plan->text += piece;
-                plan->text += '\n';
-            }
-            plan->pieceId.push_back(placed.first->second);
-            plan->pieceStart.push_back((int)from);
-            plan->pieceLen.push_back((int)plen);
-        }
-        plan->pieceOff[i + 1] = (unsigned int)plan->pieceId.size();
-    }
-    return PFAC_STATUS_SUCCESS;
-}
-
-/* the tables of `ap` from the plan: the classes by handle id, each by pattern id descending, then piece index descending, and the blob */
-void buildTables(ApproxPlan &plan, PFACX_approx_s *ap)
-{
-    const size_t S = plan.off.size() - 1, F = plan.pieces.size(), E = plan.pieceId.size();
-    ap->numIds = F;
-    ap->numPatterns = S;
-    ap->maxPiece = plan.maxPiece;
-    ap->entryOff.assign(F + 2, 0u);
-    for (size_t e = 0; e < E; e++) ap->entryOff[(size_t)plan.pieceId[e] + 1]++;
-    for (size_t q = 1; q <= F + 1; q++) ap->entryOff[q] += ap->entryOff[q - 1];  /* entryOff[q + 1] = the end of class q; entryOff[q]: its start */
-    /* (entryOff[0] = entryOff[1] = 0: class 0 is empty) */
-    std::vector<unsigned int> next(ap->entryOff.begin(), ap->entryOff.end());
-    ap->entries.assign(E, pfac::ApproxEntry{0, 0, 0u, 0u});
-    ap->blob.clear();
-    for (size_t i = S; i >= 1; i--) {                                              /* pattern id descending within every class */
-        const size_t at = plan.off[i - 1], len = plan.off[i] - at, blobAt = ap->blob.size(), k = (size_t)plan.budget[i];
-        ap->blob.resize(blobAt + (len + 3) / 4, 0u);
-        std::memcpy(ap->blob.data() + blobAt, plan.bytes.data() + at, len);
-        for (size_t j = k + 1; j-- > 0;) {                                         /* ... then piece index descending */
-            const size_t e = plan.pieceOff[i] + j;
-            ap->entries[next[(size_t)plan.pieceId[e]]++] =
-                pfac::ApproxEntry{(int)i, (int)blobAt, (unsigned int)plan.pieceStart[e] | (unsigned int)len << 16, (unsigned int)k | (unsigned int)j << 8};
-        }
-    }
-    ap->pieceOff = std::move(plan.pieceOff);
-    ap->pieceId = std::move(plan.pieceId);
-    ap->pieceStart = std::move(plan.pieceStart);
-    ap->pieceLen = std::move(plan.pieceLen);
-}
 
 /* what the three match calls check first (the generation and the pattern set: under the lock) */
 PFAC_status_t checkApproxArgs(PFACX_approx_t ap, const void *input, size_t size, const size_t *h_num_matched)
@@ -260,7 +157,7 @@ PFAC_status_t PFACX_approxOpen(PFAC_handle_t handle, const unsigned char *h_byte
     int bad = 0;
     if (badPattern) *badPattern = 0;
     if (!h_bytes || !h_patOff || !h_budget || numPatterns == 0 || numPatterns >= kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
-    ApproxPlan plan;
+    PiecePlan plan;   /* piece_cut.h: the cut PFACX_editOpen shares */
     try {
         const PFAC_status_t st = planPatterns(h_bytes, h_patOff, h_budget, numPatterns, minPieceLen, maxPieceLen, &plan, &bad);
         if (badPattern) *badPattern = bad;
@@ -271,15 +168,8 @@ PFAC_status_t PFACX_approxOpen(PFAC_handle_t handle, const unsigned char *h_byte
     if (st != PFAC_STATUS_SUCCESS) return st;
     return adoptNew(handle, approx, [&](PFACX_approx_s &obj) -> PFAC_status_t {
         /* another thread may have replaced the set since: the tables hold only over the pieces, id by id */
-        const pfac::Automaton &fa = handle->fa;
-        if (handle->caseInsensitive || (size_t)fa.numPatterns != plan.pieces.size()) return PFAC_STATUS_INVALID_PARAMETER;
-        for (size_t q = 1; q <= plan.pieces.size(); q++) {
-            const std::string &piece = plan.pieces[q - 1];
-            if ((size_t)fa.patternLen[q] != piece.size() || fa.chainLen[q] < 1 ||
-                std::memcmp(fa.file.data() + fa.patternOff[q], piece.data(), piece.size()) != 0)
-                return PFAC_STATUS_INVALID_PARAMETER;
-        }
-        buildTables(plan, &obj);
+        if (!holdsPieces(handle, plan)) return PFAC_STATUS_INVALID_PARAMETER;
+        buildPieceTables<pfac::ApproxEntry>(plan, &obj);
         return PFAC_STATUS_SUCCESS;
     });
 }
@@ -293,15 +183,7 @@ PFAC_status_t PFACX_approxGetPieces(PFACX_approx_t approx, size_t *h_pieceOff, i
     std::lock_guard<std::mutex> guard(c->lock);
     const PFAC_status_t st = checkSetGeneration(c, approx->generation);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    const size_t pieces = approx->pieceId.size();
-    if ((h_pieceId || h_pieceStart || h_pieceLen) && n < pieces) return PFAC_STATUS_INVALID_PARAMETER;
-    if (h_pieceOff)
-        for (size_t i = 0; i < approx->pieceOff.size(); i++) h_pieceOff[i] = approx->pieceOff[i];
-    const size_t bytes = pieces * sizeof(int);
-    if (h_pieceId) std::memcpy(h_pieceId, approx->pieceId.data(), bytes);
-    if (h_pieceStart) std::memcpy(h_pieceStart, approx->pieceStart.data(), bytes);
-    if (h_pieceLen) std::memcpy(h_pieceLen, approx->pieceLen.data(), bytes);
-    return PFAC_STATUS_SUCCESS;
+    return getPieces(*approx, h_pieceOff, h_pieceId, h_pieceStart, h_pieceLen, n);
 }
 
 PFAC_status_t PFACX_approxMatchFromDevice(PFACX_approx_t approx, char *d_input, size_t size, int *d_ids, int *d_pos, int *d_mis, size_t capacity,

@@ -45,6 +45,9 @@ struct alignas(16) GapSigEntry { int id; unsigned int firstPart, partsAnchor, an
 /* one part of a gapped signature, one 16-byte load: its length (1 .. 65 535), the dword index of its value dwords in the blob (the mask dwords lie
  * behind them, as for SigEntry), the gap [lo, hi] between it and the next part (both 0 behind a signature's last part) */
 struct alignas(16) GapSigPart { unsigned int len, blobOff, lo, hi; };
+/* one (pattern, piece) of a piece's class (edit_api.cpp, scan_edit.hip), one 16-byte load, the fields of ApproxEntry: the pattern's id, the dword
+ * index of its bytes in the blob, the piece's start o in the pattern | the pattern's length L << 16, the pattern's budget k | the piece's index j << 8 */
+struct alignas(16) EditEntry { int id, blobOff; unsigned int startLen, budgetPiece; };
 #ifndef PFAC_WORK_PARTS
 #define PFAC_WORK_PARTS 2
 #endif
@@ -89,7 +92,8 @@ constexpr HostSlot kHostCase = {90, 92};         /* a case call: the 64-bit leng
 constexpr HostSlot kHostSig = {94, 96};          /* a signature call: the 64-bit length of its list (scan_sig.hip, by pfac_array_scan) */
 constexpr HostSlot kHostApprox = {98, 100};      /* an approximate call: the 64-bit length of its list (scan_approx.hip, by pfac_array_scan) */
 constexpr HostSlot kHostGapSig = {102, 104};     /* a gapped-signature call: the 64-bit length of its list (scan_gapsig.hip, by pfac_array_scan) */
-constexpr int kHostWords = 106;
+constexpr HostSlot kHostEdit = {106, 108};       /* an edit-distance call: the 64-bit length of its list (scan_edit.hip, by pfac_array_scan) */
+constexpr int kHostWords = 110;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -515,12 +519,16 @@ struct DeviceScratch {
      * pair list of PFACX_gapsigMatchFromDevice is allPairs, the prefix table allTable: shared.  The signature and part tables of a gapped-signature
      * object are state of that object, not scratch (gapsig_api.cpp) */
     DeviceBuffer<char> gapsigSet;
+    /* the edit-distance calls (PFACX_edit*, scan_edit.hip): the 64-bit list offsets of the blocks of its pair passes, sized like caseSet; the pair
+     * list of PFACX_editMatchFromDevice is allPairs, the prefix table allTable: shared.  The piece tables of an edit object are state of that
+     * object, not scratch (edit_api.cpp) */
+    DeviceBuffer<char> editSet;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines); f(linesContext);
-        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet); f(sigSet); f(approxSet); f(gapsigSet);
+        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet); f(sigSet); f(approxSet); f(gapsigSet); f(editSet);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }

@@ -1351,6 +1351,95 @@ PFAC_status_t PFACX_editPairsFromDevice(PFACX_edit_t edit, const char *d_input, 
                                         const int *d_pairIds, const int *d_pairPos, size_t numPairs, int *d_ids, int *d_pos /* start */,
                                         int *d_end /* may be NULL */, int *d_dist /* may be NULL */, size_t capacity, size_t *h_num_matched);
 
+/* Signatures of byte classes with bounded repeats: the token rules of a secret / PII / DLP scanner -- `AKIA[0-9A-Z]{16}`, `ghp_[A-Za-z0-9]{36}`,
+ * `xox[baprs]-[0-9A-Za-z-]{10,48}`, `[0-9]{3}-[0-9]{2}-[0-9]{4}`, `sess=[0-9a-f]{32};` --, what PFACX_sig* and PFACX_gapsig* leave out of scope as
+ * "alternatives and negated bytes".  Both are special cases: `??` is the full class {1}, `5?` a class of 16 bytes {1}, a gap `{2-6}` the full
+ * class {2,6}.  As for PFACX_gapsig* the library picks one run of literal bytes of each signature as its ANCHOR, loads the distinct anchors as the
+ * handle's pattern set, scans for them with the product kernels and verifies every signature of every anchor occurrence against the input.
+ *   CLASSES.  A table of numClasses byte classes, 1 .. 65 535 of them, each 256 bits in `unsigned int[8]` exactly as the class of
+ *   PFACX_matchWords* / PFACX_split*: byte b is in the class iff bit b & 31 of word b >> 5 is set.  An empty class is refused.
+ *   SIGNATURES.  S signatures, ids 1 .. S in the order given.  A signature is a sequence of ELEMENTS (class c, lo, hi): lo .. hi bytes, each in
+ *   class c; 0 <= lo <= hi <= 65 535 and hi >= 1.  A literal byte is a class of one value with {1,1}.  The SLACK, the sum of hi - lo, is at most
+ *   PFACX_CLSIG_MAX_SLACK = 63, the limit of PFACX_gapsig* for the same reason: where an element can lie relative to any other is one 64-bit mask.
+ *   At open the library FUSES every maximal run of neighbouring elements that have a one-byte class and lo == hi into one LITERAL PART, whose bytes
+ *   are the elements' bytes repeated lo times each; every other element is one CLASS PART.  After fusion a signature has 1 .. 64 parts, a literal
+ *   part at most 65 535 bytes, and its span, the sum of all hi, stays below 2^23.
+ *   EMBEDDING of a signature of m elements at start s in n bytes: run lengths r_j in [lo_j, hi_j], o_0 = s, o_{j+1} = o_j + r_j, every byte of
+ *   in[o_j, o_j + r_j) in C_j, s >= 0 and end = o_m <= n.  Nothing outside [0, n) exists.
+ *   BOUNDARIES, per signature, optional: a class index notBefore and a class index notAfter, -1 for none.  A start is VALID iff s == 0 or in[s - 1]
+ *   is not in notBefore; an end e is valid iff e == n or in[e] is not in notAfter; an embedding counts only if its start and its end are valid.
+ *   This is `(?<![..])` and `(?![..])`: without it a 16-letter token rule fires inside every longer base64 run.
+ *   OCCURRENCE AND ENTRY.  Signature i occurs at s iff a valid embedding at s exists.  THE LIST holds one entry (id, start, end) per (id, start)
+ *   that occurs; end is the LARGEST valid end over all embeddings at s -- the leftmost-longest end a token extractor wants --, with the open flag
+ *   PFACX_CLSIG_SHORTEST_END the smallest, which is the meaning of PFACX_gapsig*.  Both are a maximum / minimum over all run-length choices, not
+ *   what a greedy or lazy left-to-right choice finds.  Identical signatures are both reported.  The anchor has at least one byte, so start < end.
+ *   ANCHOR.  The rule of PFACX_gapsigOpen over the literal parts: a candidate is a run of bytes other than 0x0A inside ONE literal part; the anchor
+ *   is the longest run, of equal ones the one in the lowest part, then the leftmost, cut to its first maxAnchorLen bytes; 0 stands for 32 (the
+ *   unmeasured supposition of PFACX_sigOpen -- still a supposition).  A signature without such a byte (`[0-9]{3}[a-f]{2}`) is refused.  Callers
+ *   rely on PFACX_clsigGetAnchors.
+ *   EACH OCCURRENCE ONCE.  The owner rule of PFACX_gapsig*: the anchor part a may lie at several offsets for one start.  (id, s) is listed by
+ *   the occurrence of part a at the SMALLEST offset x that lies on some VALID embedding at s: an x whose tail cannot be completed, or completes
+ *   only to ends that are not valid, owns nothing.
+ *   ORDER: by the owning anchor occurrence, x + anchorOff ascending; at one position the longer anchor first; within one anchor ids descend;
+ *   within one (anchor occurrence, signature) starts ascend.  It is NOT sorted by start.
+ * PFACX_clsigOpen: host memory, copied -- h_classes holds 8 * numClasses words; element k is (h_elemClass[k], h_elemLo[k], h_elemHi[k]); the
+ * elements of signature i are h_sigElem[i - 1] .. h_sigElem[i] - 1; h_notBefore / h_notAfter hold numSigs class indices each (-1: none; either
+ * array may be NULL: none for any signature).  flags: 0 or PFACX_CLSIG_SHORTEST_END; any other bit: PFAC_STATUS_INVALID_PARAMETER.  It loads the
+ * distinct anchors exactly as PFACX_gapsigOpen does: the handle's set is REPLACED, the handle becomes case-sensitive, handle id q is the q-th
+ * distinct anchor in order of first appearance, and it checks under the handle's lock that the set it adopts is the one it loaded.
+ * PFAC_STATUS_INVALID_PARAMETER, with the handle's set untouched: a required null pointer (h_classes, the three element arrays, h_sigElem, sig),
+ * numSigs == 0 or >= 2^31 - 1, numClasses == 0 or > 65 535, an empty class, and -- with the id of the FIRST such signature in *badSig (may be
+ * NULL; else 0) -- a signature without elements, a class index outside the table (in notBefore / notAfter too, other than -1), lo > hi,
+ * hi == 0, hi > 65 535, a slack above 63, more than 64 parts after fusion, a literal part longer than 65 535 bytes, a span of 2^23 or more;
+ * behind those, by id, a signature without a literal byte other than 0x0A.
+ * PFACX_clsigOpenText: a parser in front of it and nothing else; one signature per '\n'-terminated line (a '\r' in front of the '\n' is
+ * ignored), in a subset of regular-expression syntax chosen so that every accepted line means the same to Python's `re` on bytes with re.DOTALL.
+ * A UNIT is a literal byte (any byte but `\ . [ ] ( ) { } ? * + | ^ $`; bytes >= 0x80 are literals), an escape (`\xHH`, `\n \r \t \f \v \0`, `\`
+ * plus one of the metacharacters), a class escape (`\d \D \w \W \s \S`, ASCII; \s = blank \t \n \r \f \v), `.` (any byte), or a bracket set
+ * `[...]` / `[^...]` of literals, escapes, class escapes and ranges `a-z`; inside a set `]` and `\` are always escaped, `-` is literal at the
+ * first or last place or escaped, `^` is literal unless first.  A QUANTIFIER may follow a unit: `{n}`, `{n,m}`, or `?` = {0,1}; decimal, no
+ * blanks.  At the very start of a line, optionally `(?<![set])`; at the very end, optionally `(?![set])`, each with a bracket set's body.
+ * Refused with the 1-based line in *badLine: `* + | ( ) ^ $` elsewhere, `{n,}`, `{,m}`, n > m, a quantifier without a unit or two in a row, an
+ * unclosed set, an empty set, a range that descends, an unknown escape, a number above 65 535, an empty line, bytes behind the last '\n', and a
+ * line the binary form refuses.  A text without a line: *badLine = 0.  Identical classes are stored once.
+ * PFACX_clsigGetAnchors: by signature id (n >= S + 1 entries each, entry 0 is 0; an array may be NULL) the handle's pattern id of the anchor,
+ * the part AFTER FUSION that holds it, its offset inside that part and its length.
+ * The object belongs to the handle like a gapped-signature object (PFAC_destroy closes it; stale after another read; host-only handles can
+ * open).  The three match calls are those of PFACX_gapsig* word for word: the device form needs capacity >= size and its arrays take the scan's
+ * unordered list first; the host and pairs forms take any capacity, 0 with null arrays is the count query; a longer list: the first `capacity`
+ * entries, the full length, and PFACX_STATUS_OUTPUT_TRUNCATED; d_end may be NULL in every form and is only ever written below min(the list,
+ * capacity); size >= 2^31 or a required null pointer: PFAC_STATUS_INVALID_PARAMETER; size == 0: success, nothing touched; a device form on a
+ * host-only handle: PFAC_STATUS_LIB_NOT_EXIST; the pairs form ignores ids outside [1, F] and positions outside [0, size), refuses output arrays
+ * (d_end included) that overlap the pair arrays and numPairs >= 2^31, and owns an occurrence only through pairs of its list.  The host form
+ * follows PFAC_setPlatform.  All calls are synchronous and take the handle's lock.  The input is never modified, and nothing outside it is read.
+ * MEMORY.  The tables, made by the first device call, are state of the object (deviceTableBytes, kept by PFACX_trim, freed by PFACX_clsigClose):
+ * 32 bytes per signature, 16 per part, 4 (F + 2) bytes, the literal parts' bytes padded to a multiple of 4 each, 32 bytes per class.
+ * Grow-only handle scratch as for PFACX_gapsig*.
+ * COST: the compacted scan over the anchors with its ordering launches, then two passes over the pairs; a thread per pair runs the
+ * whole search of a candidate -- up to 64 starts, each a walk of at most hi + 64 bytes per class part and a compare per set bit per literal part.
+ * OUT OF SCOPE: unbounded repeats and slack above 63; alternation and groups; caseless literals (write `[Aa]`); `\b`; anchors chosen by rarity;
+ * a wave per long search; segment bounds of a batch, stream and flow pairs; a full-result-vector form; a list sorted by start; a compiled-file
+ * form. */
+#define PFACX_CLSIG_MAX_SLACK    63
+#define PFACX_CLSIG_SHORTEST_END 1u
+typedef struct PFACX_clsig_s *PFACX_clsig_t;
+PFAC_status_t PFACX_clsigOpen(PFAC_handle_t handle, const unsigned int *h_classes /* 8 * numClasses */, size_t numClasses,
+                              const unsigned int *h_elemClass, const unsigned int *h_elemLo, const unsigned int *h_elemHi /* numElems each */,
+                              const size_t *h_sigElem /* numSigs + 1 */, const int *h_notBefore, const int *h_notAfter /* numSigs each; may be NULL */,
+                              size_t numSigs, size_t maxAnchorLen /* 0: 32 */, unsigned int flags, PFACX_clsig_t *sig, int *badSig /* may be NULL */);
+PFAC_status_t PFACX_clsigOpenText(PFAC_handle_t handle, const char *text, size_t size, size_t maxAnchorLen /* 0: 32 */, unsigned int flags,
+                                  PFACX_clsig_t *sig, int *badLine /* may be NULL */);
+PFAC_status_t PFACX_clsigGetAnchors(PFACX_clsig_t sig, int *h_anchorId, int *h_anchorPart /* after fusion */, int *h_anchorOff /* inside that part */,
+                                    int *h_anchorLen, size_t n /* >= S + 1, indexed by ID */);
+PFAC_status_t PFACX_clsigClose(PFACX_clsig_t sig);
+PFAC_status_t PFACX_clsigMatchFromDevice(PFACX_clsig_t sig, char *d_input, size_t size,
+                                         int *d_ids, int *d_pos, int *d_end /* may be NULL */, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_clsigMatchFromHost  (PFACX_clsig_t sig, char *h_input, size_t size,
+                                         int *h_ids, int *h_pos, int *h_end /* may be NULL */, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_clsigPairsFromDevice(PFACX_clsig_t sig, const char *d_input, size_t size,
+                                         const int *d_pairIds, const int *d_pairPos, size_t numPairs,
+                                         int *d_ids, int *d_pos, int *d_end /* may be NULL */, size_t capacity, size_t *h_num_matched);
+
 /* Split: the offsets that cut a buffer into records at the bytes of a delimiter class -- the `d_offsets` that PFACX_matchBatch*,
  * PFACX_matchAllBatchFromDevice, PFACX_rules*, PFACX_countBatch* and PFACX_groups* take, made where the text lies: the lines of a log, the records
  * of a CRLF protocol, the fields of a line.

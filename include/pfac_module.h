@@ -582,6 +582,43 @@ typedef struct {
 } PFACX_editRun_t;
 PFAC_status_t PFACX_editRun(PFAC_handle_t handle, const PFACX_editRun_t *run, size_t *h_total);
 
+/* Signatures of byte classes with bounded repeats (no reference counterpart; include/pfac_ext.h: PFACX_clsig*), scan_clsig.hip.
+ * PFACX_clsigRun: the class signatures that occur around an ordered list of LONGEST pairs of the anchor set.  d_input, size, the pair arrays,
+ * count, d_table and numIds are those of PFACX_gapsigRun.  The signatures anchored by pattern q are d_sigs[d_sigOff[q], d_sigOff[q + 1]) (d_sigOff:
+ * numIds + 2 entries; the range is clamped to numSigs), 32 bytes each (pfac_context.h: ClSigEntry): {signature id, first part, number of parts |
+ * anchor part << 16, offset of the anchor inside that part}, then {notBefore, notAfter, 0, 0}, by signature id descending.  d_parts, numParts
+ * entries of 16 bytes (ClSigPart): {0, len, dword index of its bytes in d_blob, 0} for a literal part, {1, class, lo, hi} for a class part.
+ * d_blob, blobWords dwords: per literal part (len + 3) / 4 value dwords.  d_classes: numClasses classes of eight dwords, byte b a member iff bit
+ * b & 31 of dword b >> 5 is set.  An entry with no part or more than 64, parts outside the table, an anchor part outside the entry or one that is
+ * no literal part is skipped; so is, wherever it is met, a literal part that is empty or whose dwords do not lie inside the blob, and a class part
+ * with a class outside the table, hi < lo, hi > 65 535 or hi - lo > 63: nothing lies there.  A boundary class outside the table (other than -1)
+ * forbids nothing.  Only each part is tested, not the sum over a signature: where a table's slack exceeds 63 the distances past bit 63 are dropped
+ * -- fewer entries, nothing out of bounds; the library's own tables never do.  Part a of a chain member at pair position p lies at x = p -
+ * offset; (id, s, end) is kept iff a valid embedding of the signature at s has part a at x, no valid embedding at s has it at a smaller offset,
+ * and end is the largest -- with PFACX_CLSIG_SHORTEST_END in `flags` the smallest -- valid end over all embeddings at s (include/pfac_ext.h says
+ * what a valid embedding is).  Output as for PFACX_gapsigRun.  Synchronous. */
+typedef struct {
+    const char *d_input;
+    size_t size;
+    const int *d_pairIds, *d_pairPos;
+    size_t count;
+    const void *d_table;
+    size_t numIds;
+    const unsigned int *d_sigOff;
+    const void *d_sigs;
+    size_t numSigs;
+    const void *d_parts;
+    size_t numParts;
+    const unsigned int *d_blob;
+    size_t blobWords;
+    const unsigned int *d_classes;
+    size_t numClasses;
+    unsigned int flags;
+    int *d_ids, *d_pos, *d_end;
+    size_t capacity;
+} PFACX_clsigRun_t;
+PFAC_status_t PFACX_clsigRun(PFAC_handle_t handle, const PFACX_clsigRun_t *run, size_t *h_total);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -599,7 +636,7 @@ PFAC_status_t PFACX_editRun(PFAC_handle_t handle, const PFACX_editRun_t *run, si
     X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun) X(split_run_ptr, PFACX_splitRun) \
     X(locate_run_ptr, PFACX_locateRun) X(capture_run_ptr, PFACX_captureRun) X(case_run_ptr, PFACX_caseRun) \
     X(sig_run_ptr, PFACX_sigRun) X(approx_run_ptr, PFACX_approxRun) X(gapsig_run_ptr, PFACX_gapsigRun) \
-    X(edit_run_ptr, PFACX_editRun)
+    X(edit_run_ptr, PFACX_editRun) X(clsig_run_ptr, PFACX_clsigRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

@@ -48,6 +48,11 @@ PFACX_EDIT_BLOCKS_PER_CU = 8                    # scan_passes.h: offsetBlocks, a
 PFACX_EDIT_MAX_EDITS = 7                        # pfac_ext.h: the largest budget of a pattern of PFACX_editOpen
 PFACX_EDIT_BEST_ENDS = 1                        # pfac_ext.h: the open-time flag that keeps only the ends the three-point rule on D passes
 PFACX_GAPSIG_MAX_SLACK = 63                     # pfac_ext.h: the largest sum of hi - lo over the gaps of one signature of PFACX_gapsigOpen
+PFACX_CLSIG_BLOCK = 256                         # scan_clsig.hip: kClSigBlock, the pairs one block of the class-signature passes takes (never more than eight blocks per CU)
+PFACX_CLSIG_BLOCKS_PER_CU = 8                   # scan_passes.h: offsetBlocks, as for the case passes
+PFACX_CLSIG_MAX_SLACK = 63                      # pfac_ext.h: the largest sum of hi - lo over the elements of one signature of PFACX_clsigOpen
+PFACX_CLSIG_SHORTEST_END = 1                    # pfac_ext.h: the open-time flag that lists the smallest end instead of the largest
+PFACX_CLSIG_STAGED_CLASSES = 64                 # scan_clsig.hip: kClSigStaged, the classes every block stages in LDS; the others are read from device memory
 PFACX_GROUPS_BLOCK = 256                        # scan_groups.hip: kGroupsBlock, the pairs one block of the group passes takes (never more than eight blocks per CU)
 PFACX_WORDS_BLOCK = 256                         # scan_words.hip: kWordsBlock, the pairs one block of the boundary passes takes (never more than eight blocks per CU)
 PFACX_SPLIT_BEFORE = 1                          # pfac_ext.h: PFACX_split* a delimiter opens the segment behind it instead of closing the one in front
@@ -188,6 +193,8 @@ EXPORTED_SYMBOLS = (
     "PFACX_gapsigMatchFromHost", "PFACX_gapsigPairsFromDevice",
     "PFACX_editOpen", "PFACX_editGetPieces", "PFACX_editClose", "PFACX_editMatchFromDevice", "PFACX_editMatchFromHost",
     "PFACX_editPairsFromDevice",
+    "PFACX_clsigOpen", "PFACX_clsigOpenText", "PFACX_clsigGetAnchors", "PFACX_clsigClose", "PFACX_clsigMatchFromDevice",
+    "PFACX_clsigMatchFromHost", "PFACX_clsigPairsFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -212,6 +219,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_approxRun",
     "PFACX_gapsigRun",
     "PFACX_editRun",
+    "PFACX_clsigRun",
 )
 
 
@@ -444,6 +452,18 @@ def load_library() -> C.CDLL:
         lib.PFACX_editMatchFromHost.argtypes = edits
         lib.PFACX_editPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_size_t, SZ]
+    if hasattr(lib, "PFACX_clsigOpen"):
+        SZ = C.POINTER(C.c_size_t)
+        lib.PFACX_clsigOpen.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_size_t, C.c_uint, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+        lib.PFACX_clsigOpenText.argtypes = [H, C.c_char_p, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+        lib.PFACX_clsigGetAnchors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.PFACX_clsigClose.argtypes = [C.c_void_p]
+        classed = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, SZ]
+        lib.PFACX_clsigMatchFromDevice.argtypes = classed
+        lib.PFACX_clsigMatchFromHost.argtypes = classed
+        lib.PFACX_clsigPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_size_t, SZ]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -1299,6 +1319,52 @@ class PFAC:
         self._ret(st, "PFACX_gapsigOpenText", check)
         return GapSigSet(self, s, text.count(b"\n") if st == 0 else 0, bad.value, st)
 
+    # -- signatures of byte classes with bounded repeats (include/pfac_ext.h: PFACX_clsig*) ----------------
+    def clsigOpen(self, classes, elem_class, elem_lo, elem_hi, sig_elem, not_before=None, not_after=None, max_anchor_len: int = 0,
+                  flags: int = 0, check: bool = True) -> "ClSigSet":
+        """``PFACX_clsigOpen`` -> a :class:`ClSigSet` of this handle (``.status`` holds the call's status, ``.bad`` the id of a refused
+        signature): `classes` uint32 of shape (numClasses, 8) as :func:`word_class` makes them, the elements (class, lo, hi) in three uint32
+        arrays, `sig_elem` numSigs + 1 element indices, `not_before` / `not_after` numSigs class indices each (-1: none) or None; all are copied.
+        The handle's pattern set is REPLACED by the distinct anchors."""
+        import numpy as np
+        classes = np.ascontiguousarray(classes, dtype=np.uint32).reshape(-1)
+        elem_class = np.ascontiguousarray(elem_class, dtype=np.uint32)
+        elem_lo = np.ascontiguousarray(elem_lo, dtype=np.uint32)
+        elem_hi = np.ascontiguousarray(elem_hi, dtype=np.uint32)
+        sig_elem = np.ascontiguousarray(sig_elem, dtype=np.uint64)
+        if classes.size % 8:
+            raise ValueError(f"{classes.size} class words: not a multiple of 8")
+        if elem_lo.size != elem_class.size or elem_hi.size != elem_class.size:
+            raise ValueError(f"{elem_class.size} / {elem_lo.size} / {elem_hi.size} entries of the element arrays")
+        if sig_elem.size and int(sig_elem.max()) > elem_class.size:
+            raise ValueError(f"sig_elem reaches element {int(sig_elem.max())} of {elem_class.size}")
+        count = max(0, int(sig_elem.size) - 1)
+        bounds = []
+        for b in (not_before, not_after):
+            b = None if b is None else np.ascontiguousarray(b, dtype=np.int32)
+            if b is not None and b.size != count:
+                raise ValueError(f"{b.size} boundary classes for {count} signatures")
+            bounds.append(b)
+        pad32 = np.zeros(8, dtype=np.uint32)
+        s, bad = C.c_void_p(), C.c_int(0)
+        st = self._lib.PFACX_clsigOpen(self._h, (classes if classes.size else pad32).ctypes.data, classes.size // 8,
+                                       (elem_class if elem_class.size else pad32).ctypes.data, (elem_lo if elem_lo.size else pad32).ctypes.data,
+                                       (elem_hi if elem_hi.size else pad32).ctypes.data, sig_elem.ctypes.data if sig_elem.size else None,
+                                       bounds[0].ctypes.data if bounds[0] is not None and count else None,
+                                       bounds[1].ctypes.data if bounds[1] is not None and count else None, count, max_anchor_len, flags,
+                                       C.byref(s), C.byref(bad))
+        self._ret(st, "PFACX_clsigOpen", check)
+        return ClSigSet(self, s, count if st == 0 else 0, bad.value, st)
+
+    def clsigOpenText(self, text: bytes, max_anchor_len: int = 0, flags: int = 0, check: bool = True) -> "ClSigSet":
+        """``PFACX_clsigOpenText`` -> a :class:`ClSigSet` (``.bad``: the 1-based line that was refused): one signature per line in the subset
+        of regular-expression syntax that include/pfac_ext.h lists, such as ``AKIA[0-9A-Z]{16}(?![0-9A-Z])``."""
+        text = bytes(text)
+        s, bad = C.c_void_p(), C.c_int(0)
+        st = self._lib.PFACX_clsigOpenText(self._h, text, len(text), max_anchor_len, flags, C.byref(s), C.byref(bad))
+        self._ret(st, "PFACX_clsigOpenText", check)
+        return ClSigSet(self, s, text.count(b"\n") if st == 0 else 0, bad.value, st)
+
     # -- numpy conveniences over matchFromHost (still the C ABI underneath) ----------
     def match_host_array(self, data):
         import numpy as np
@@ -1939,6 +2005,77 @@ class GapSigSet:
         st, n2 = self.match_host(buf.ctypes.data, data.size, ids.ctypes.data, pos.ctypes.data, end.ctypes.data, n)
         if st != 0 or n2 != n:
             raise PFACError(st, "PFACX_gapsigMatchFromHost", f"{n2} entries behind a count query that said {n}")
+        return pos[:n].copy(), ids[:n].copy(), end[:n].copy()
+
+
+class ClSigSet:
+    """One class-signature object (``PFACX_clsig_t``): signatures of byte classes with bounded repeats over the anchors it loaded into its handle.
+    Every match call returns ``(status, full length of the list)``; OUTPUT_TRUNCATED is returned, not raised.  The list holds (signature id,
+    start) and the largest end (PFACX_CLSIG_SHORTEST_END: the smallest) in a third array, ordered by the owning anchor occurrence, not by start.  A context manager: it closes itself."""
+
+    def __init__(self, handle: "PFAC", sig: C.c_void_p, num_sigs: int = 0, bad: int = 0, status: int = 0):
+        self._owner = handle
+        self._lib = handle._lib
+        self._c = sig
+        self.num_sigs = num_sigs
+        self.bad = bad
+        self.status = status
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self._c:
+            self.close(check=False)
+
+    def _ret(self, st: int, where: str, check: bool) -> int:
+        if check and st != 0:
+            raise PFACError(st, where, error_string(st))
+        return st
+
+    def anchors(self, check: bool = True):
+        """``PFACX_clsigGetAnchors`` -> (anchor_id, anchor_part after fusion, anchor_off, anchor_len), int32 arrays of num_sigs + 1 entries by signature id."""
+        import numpy as np
+        n = self.num_sigs + 1
+        out = tuple(np.full(n, -7, dtype=np.int32) for _ in range(4))
+        st = self._lib.PFACX_clsigGetAnchors(self._c, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, out[3].ctypes.data, n)
+        self._ret(st, "PFACX_clsigGetAnchors", check)
+        return out
+
+    def match_device(self, d_input: int, size: int, d_ids, d_pos, d_end, capacity: int, check: bool = True):
+        """``PFACX_clsigMatchFromDevice``: capacity >= size entries in each device array; d_end may be None."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_clsigMatchFromDevice(self._c, d_input, size, d_ids, d_pos, d_end, capacity, C.byref(n))
+        return self._ret(st, "PFACX_clsigMatchFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def match_host(self, h_input: int, size: int, h_ids, h_pos, h_end, capacity: int, check: bool = True):
+        """``PFACX_clsigMatchFromHost``: follows PFAC_setPlatform (the CPU platforms run on the CPU); any capacity, 0 with null arrays: the count."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_clsigMatchFromHost(self._c, h_input, size, h_ids, h_pos, h_end, capacity, C.byref(n))
+        return self._ret(st, "PFACX_clsigMatchFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def pairs_device(self, d_input: int, size: int, d_pair_ids, d_pair_pos, num_pairs: int, d_ids, d_pos, d_end, capacity: int, check: bool = True):
+        """``PFACX_clsigPairsFromDevice``: the same list from an ordered LONGEST pair list of the handle over the same input (the output of
+        matchFromDeviceReduce).  It runs no scan."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_clsigPairsFromDevice(self._c, d_input, size, d_pair_ids, d_pair_pos, num_pairs, d_ids, d_pos, d_end, capacity, C.byref(n))
+        return self._ret(st, "PFACX_clsigPairsFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def close(self, check: bool = True) -> int:
+        st = self._lib.PFACX_clsigClose(self._c)
+        self._c = C.c_void_p()
+        return self._ret(st, "PFACX_clsigClose", check)
+
+    def match_host_array(self, data):
+        """match_host over a numpy array -> (pos, ids, end) of the whole list: the count query first, then arrays of exactly that length."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        _, n = self.match_host(buf.ctypes.data, data.size, None, None, None, 0)
+        ids, pos, end = (np.full(max(1, n), -7, dtype=np.int32) for _ in range(3))
+        st, n2 = self.match_host(buf.ctypes.data, data.size, ids.ctypes.data, pos.ctypes.data, end.ctypes.data, n)
+        if st != 0 or n2 != n:
+            raise PFACError(st, "PFACX_clsigMatchFromHost", f"{n2} entries behind a count query that said {n}")
         return pos[:n].copy(), ids[:n].copy(), end[:n].copy()
 
 

@@ -48,6 +48,13 @@ struct alignas(16) GapSigPart { unsigned int len, blobOff, lo, hi; };
 /* one (pattern, piece) of a piece's class (edit_api.cpp, scan_edit.hip), one 16-byte load, the fields of ApproxEntry: the pattern's id, the dword
  * index of its bytes in the blob, the piece's start o in the pattern | the pattern's length L << 16, the pattern's budget k | the piece's index j << 8 */
 struct alignas(16) EditEntry { int id, blobOff; unsigned int startLen, budgetPiece; };
+/* one class signature of an anchor's class (clsig_api.cpp, scan_clsig.hip), two 16-byte loads: the header of GapSigEntry -- the signature's id, the
+ * index of its first part in the part table, its number of parts after fusion (1 .. 64) | the index of its anchor part << 16, the anchor's offset
+ * inside that part --, then the byte classes that must not stand in front of a start and behind an end (-1: none) */
+struct alignas(16) ClSigEntry { int id; unsigned int firstPart, partsAnchor, anchorOff; int notBefore, notAfter; unsigned int reserved[2]; };
+/* one part of a class signature after fusion, one 16-byte load.  kind 0, a LITERAL part: a = its length (1 .. 65 535), b = the dword index of its
+ * bytes in the blob (values only).  kind 1, a CLASS part: a = the class, b = lo, c = hi: lo .. hi bytes of that class */
+struct alignas(16) ClSigPart { unsigned int kind, a, b, c; };
 #ifndef PFAC_WORK_PARTS
 #define PFAC_WORK_PARTS 2
 #endif
@@ -93,7 +100,8 @@ constexpr HostSlot kHostSig = {94, 96};          /* a signature call: the 64-bit
 constexpr HostSlot kHostApprox = {98, 100};      /* an approximate call: the 64-bit length of its list (scan_approx.hip, by pfac_array_scan) */
 constexpr HostSlot kHostGapSig = {102, 104};     /* a gapped-signature call: the 64-bit length of its list (scan_gapsig.hip, by pfac_array_scan) */
 constexpr HostSlot kHostEdit = {106, 108};       /* an edit-distance call: the 64-bit length of its list (scan_edit.hip, by pfac_array_scan) */
-constexpr int kHostWords = 110;
+constexpr HostSlot kHostClSig = {110, 112};      /* a class-signature call: the 64-bit length of its list (scan_clsig.hip, by pfac_array_scan) */
+constexpr int kHostWords = 114;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -523,12 +531,16 @@ struct DeviceScratch {
      * list of PFACX_editMatchFromDevice is allPairs, the prefix table allTable: shared.  The piece tables of an edit object are state of that
      * object, not scratch (edit_api.cpp) */
     DeviceBuffer<char> editSet;
+    /* the class-signature calls (PFACX_clsig*, scan_clsig.hip): the 64-bit list offsets of the blocks of its pair passes, sized like caseSet; the
+     * pair list of PFACX_clsigMatchFromDevice is allPairs, the prefix table allTable: shared.  The signature, part and class tables of a
+     * class-signature object are state of that object, not scratch (clsig_api.cpp) */
+    DeviceBuffer<char> clsigSet;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines); f(linesContext);
-        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet); f(sigSet); f(approxSet); f(gapsigSet); f(editSet);
+        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet); f(sigSet); f(approxSet); f(gapsigSet); f(editSet); f(clsigSet);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }

@@ -1418,8 +1418,32 @@ PFAC_status_t PFACX_editPairsFromDevice(PFACX_edit_t edit, const char *d_input, 
  * COST: the compacted scan over the anchors with its ordering launches, then two passes over the pairs; a thread per pair runs the
  * whole search of a candidate -- up to 64 starts, each a walk of at most hi + 64 bytes per class part and a compare per set bit per literal part.
  * OUT OF SCOPE: unbounded repeats and slack above 63; alternation and groups; caseless literals (write `[Aa]`); `\b`; anchors chosen by rarity;
- * a wave per long search; segment bounds of a batch, stream and flow pairs; a full-result-vector form; a list sorted by start; a compiled-file
- * form. */
+ * a wave per long search; stream and flow pairs; a full-result-vector form; a list sorted by start; a compiled-file form.
+ *
+ * THE BATCH FORMS (PFACX_clsigBatch*): one buffer that holds many packets, log lines or small files, cut by numSegments + 1 offsets of size_t
+ * under the rules of PFACX_matchBatch* -- host offsets are validated (offsets[0] == 0, offsets[numSegments] == size, never decreasing; else
+ * PFAC_STATUS_INVALID_PARAMETER), device offsets are never checked: each is clamped to [0, size] and raised to the largest entry in front of it,
+ * so bad device offsets give the answer for the clamped offsets and never an access outside the buffers.  PFACX_split* makes such offsets on the
+ * device.  Segment k is [o_k, o_{k+1}) of the clamped offsets, and every definition above holds with [o_k, o_{k+1}) in place of [0, n): an
+ * embedding lies inside ONE segment; a start is valid iff s == o_k or in[s - 1] is not in notBefore; an end is valid iff e == o_{k+1} or in[e]
+ * is not in notAfter; the owner rule and the largest / smallest end range over the embeddings inside the segment only.  THE LIST is exactly the
+ * concatenation, in segment order, of what PFACX_clsigMatchFromDevice returns for each segment alone, o_k added to every start and end, each
+ * segment's entries in that call's order; a batch of one segment is the plain call.  No filter over the plain call's list gives this: a crossing
+ * embedding may hide a shorter one that stays inside (the reported end is a maximum or minimum), and an entry that a neighbour's byte forbids is
+ * not in the plain list at all.
+ *   A FULL notBefore CLASS therefore means "at the start of the segment" and a full notAfter class "ends with the segment": the text form writes
+ *   them `(?<![\x00-\xff])` and `(?![\x00-\xff])`.
+ *   d_segFirst / h_segFirst (may be NULL): numSegments + 1 entries of size_t; entry k is the list index of segment k's first entry, entry
+ *   numSegments the full length; indices past `capacity` name entries that were not written, as in PFACX_matchAllBatchFromDevice.  Written
+ *   whatever the capacity (the count query fills it).
+ *   numSegments: at least 1 for size > 0, below 2^31 - 1; a NULL offsets array: PFAC_STATUS_INVALID_PARAMETER.
+ *   The pairs form finds each pair's segment from its POSITION, so the pairs of a plain, a batch or an all-match scan of the handle over the same
+ *   input all work; a pair whose position lies in no segment (in front of o_0, at or behind the last offset) owns nothing.  For a pair list that
+ *   does not ascend by position the entries are still right pair by pair, and d_segFirst is unspecified.
+ * Everything else is the plain calls' word for word: capacity (the device form: capacity >= size), truncation, the count query, size >= 2^31,
+ * size == 0 (success, nothing touched, d_segFirst neither), host-only handles, the handle's lock, the overlap refusals of the pairs form,
+ * PFACX_CLSIG_SHORTEST_END from the open call.  Scratch: 4 (numSegments + 1) bytes more.  The device form scans the whole buffer once, as the
+ * plain call does, and searches each candidate inside its segment (DESIGN.md 5za says why that is enough, and what the call costs). */
 #define PFACX_CLSIG_MAX_SLACK    63
 #define PFACX_CLSIG_SHORTEST_END 1u
 typedef struct PFACX_clsig_s *PFACX_clsig_t;
@@ -1439,6 +1463,16 @@ PFAC_status_t PFACX_clsigMatchFromHost  (PFACX_clsig_t sig, char *h_input, size_
 PFAC_status_t PFACX_clsigPairsFromDevice(PFACX_clsig_t sig, const char *d_input, size_t size,
                                          const int *d_pairIds, const int *d_pairPos, size_t numPairs,
                                          int *d_ids, int *d_pos, int *d_end /* may be NULL */, size_t capacity, size_t *h_num_matched);
+PFAC_status_t PFACX_clsigBatchMatchFromDevice(PFACX_clsig_t sig, char *d_input, size_t size, const size_t *d_offsets /* numSegments + 1 */,
+                                              size_t numSegments, int *d_ids, int *d_pos, int *d_end /* may be NULL */, size_t capacity,
+                                              size_t *d_segFirst /* numSegments + 1; may be NULL */, size_t *h_num_matched);
+PFAC_status_t PFACX_clsigBatchMatchFromHost  (PFACX_clsig_t sig, char *h_input, size_t size, const size_t *h_offsets /* numSegments + 1 */,
+                                              size_t numSegments, int *h_ids, int *h_pos, int *h_end /* may be NULL */, size_t capacity,
+                                              size_t *h_segFirst /* numSegments + 1; may be NULL */, size_t *h_num_matched);
+PFAC_status_t PFACX_clsigBatchPairsFromDevice(PFACX_clsig_t sig, const char *d_input, size_t size, const size_t *d_offsets /* numSegments + 1 */,
+                                              size_t numSegments, const int *d_pairIds, const int *d_pairPos, size_t numPairs,
+                                              int *d_ids, int *d_pos, int *d_end /* may be NULL */, size_t capacity,
+                                              size_t *d_segFirst /* numSegments + 1; may be NULL */, size_t *h_num_matched);
 
 /* Split: the offsets that cut a buffer into records at the bytes of a delimiter class -- the `d_offsets` that PFACX_matchBatch*,
  * PFACX_matchAllBatchFromDevice, PFACX_rules*, PFACX_countBatch* and PFACX_groups* take, made where the text lies: the lines of a log, the records

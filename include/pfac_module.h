@@ -596,7 +596,13 @@ PFAC_status_t PFACX_editRun(PFAC_handle_t handle, const PFACX_editRun_t *run, si
  * -- fewer entries, nothing out of bounds; the library's own tables never do.  Part a of a chain member at pair position p lies at x = p -
  * offset; (id, s, end) is kept iff a valid embedding of the signature at s has part a at x, no valid embedding at s has it at a smaller offset,
  * and end is the largest -- with PFACX_CLSIG_SHORTEST_END in `flags` the smallest -- valid end over all embeddings at s (include/pfac_ext.h says
- * what a valid embedding is).  Output as for PFACX_gapsigRun.  Synchronous. */
+ * what a valid embedding is).  Output as for PFACX_gapsigRun.  Synchronous.
+ * A BATCH (PFACX_clsigBatch*): d_offsets, numSegments + 1 values of the caller's in device memory, 1 <= numSegments < 2^31 - 1; null: the plain
+ * call, and d_segFirst must be null too.  A launch in front of the passes makes a 32-bit copy of them, each clamped to [0, size] and raised to the
+ * largest entry in front of it, in the call's scratch; the passes read only that copy.  A pair belongs to the segment that holds its POSITION (one
+ * that lies in none owns nothing), and "the input" of every sentence above is that segment's bytes: starts and ends count from d_input all the
+ * same.  d_segFirst (may be null): numSegments + 1 entries, the list index of each segment's first entry and the length of the list, written
+ * whatever the capacity; right for a list that ascends by position, unspecified (but inside the array) for any other; all zero for no pairs. */
 typedef struct {
     const char *d_input;
     size_t size;
@@ -616,6 +622,9 @@ typedef struct {
     unsigned int flags;
     int *d_ids, *d_pos, *d_end;
     size_t capacity;
+    const size_t *d_offsets;
+    size_t numSegments;
+    size_t *d_segFirst;
 } PFACX_clsigRun_t;
 PFAC_status_t PFACX_clsigRun(PFAC_handle_t handle, const PFACX_clsigRun_t *run, size_t *h_total);
 

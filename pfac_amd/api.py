@@ -52,6 +52,7 @@ PFACX_CLSIG_BLOCK = 256                         # scan_clsig.hip: kClSigBlock, t
 PFACX_CLSIG_BLOCKS_PER_CU = 8                   # scan_passes.h: offsetBlocks, as for the case passes
 PFACX_CLSIG_MAX_SLACK = 63                      # pfac_ext.h: the largest sum of hi - lo over the elements of one signature of PFACX_clsigOpen
 PFACX_CLSIG_SHORTEST_END = 1                    # pfac_ext.h: the open-time flag that lists the smallest end instead of the largest
+PFACX_CLSIG_BOUNDS_BLOCK = 8192                 # scan_clsig.hip: kBoundsBlock, the offsets one block of the batch forms' bounds launch takes
 PFACX_CLSIG_STAGED_CLASSES = 64                 # scan_clsig.hip: kClSigStaged, the classes every block stages in LDS; the others are read from device memory
 PFACX_GROUPS_BLOCK = 256                        # scan_groups.hip: kGroupsBlock, the pairs one block of the group passes takes (never more than eight blocks per CU)
 PFACX_WORDS_BLOCK = 256                         # scan_words.hip: kWordsBlock, the pairs one block of the boundary passes takes (never more than eight blocks per CU)
@@ -194,7 +195,8 @@ EXPORTED_SYMBOLS = (
     "PFACX_editOpen", "PFACX_editGetPieces", "PFACX_editClose", "PFACX_editMatchFromDevice", "PFACX_editMatchFromHost",
     "PFACX_editPairsFromDevice",
     "PFACX_clsigOpen", "PFACX_clsigOpenText", "PFACX_clsigGetAnchors", "PFACX_clsigClose", "PFACX_clsigMatchFromDevice",
-    "PFACX_clsigMatchFromHost", "PFACX_clsigPairsFromDevice",
+    "PFACX_clsigMatchFromHost", "PFACX_clsigPairsFromDevice", "PFACX_clsigBatchMatchFromDevice", "PFACX_clsigBatchMatchFromHost",
+    "PFACX_clsigBatchPairsFromDevice",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -464,6 +466,13 @@ def load_library() -> C.CDLL:
         lib.PFACX_clsigMatchFromHost.argtypes = classed
         lib.PFACX_clsigPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_size_t, SZ]
+    if hasattr(lib, "PFACX_clsigBatchMatchFromDevice"):
+        SZ = C.POINTER(C.c_size_t)
+        batched = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, SZ]
+        lib.PFACX_clsigBatchMatchFromDevice.argtypes = batched
+        lib.PFACX_clsigBatchMatchFromHost.argtypes = batched
+        lib.PFACX_clsigBatchPairsFromDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, SZ]
     for name in EXPORTED_SYMBOLS:
         if os.environ.get("PFAC_AB_OLD_LIBS") and not hasattr(lib, name):     # tools/ab.py: the library of an earlier revision
             continue
@@ -2061,6 +2070,32 @@ class ClSigSet:
         st = self._lib.PFACX_clsigPairsFromDevice(self._c, d_input, size, d_pair_ids, d_pair_pos, num_pairs, d_ids, d_pos, d_end, capacity, C.byref(n))
         return self._ret(st, "PFACX_clsigPairsFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
 
+    def match_batch_device(self, d_input: int, size: int, d_offsets, num_segments: int, d_ids, d_pos, d_end, capacity: int, d_seg_first=None,
+                           check: bool = True):
+        """``PFACX_clsigBatchMatchFromDevice``: match_device with every embedding, boundary test and owner inside one segment of the
+        num_segments + 1 device offsets (size_t; clamped and raised, never trusted); d_seg_first: num_segments + 1 entries of size_t or None."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_clsigBatchMatchFromDevice(self._c, d_input, size, d_offsets, num_segments, d_ids, d_pos, d_end, capacity, d_seg_first,
+                                                       C.byref(n))
+        return self._ret(st, "PFACX_clsigBatchMatchFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def match_batch_host(self, h_input: int, size: int, h_offsets, num_segments: int, h_ids, h_pos, h_end, capacity: int, h_seg_first=None,
+                         check: bool = True):
+        """``PFACX_clsigBatchMatchFromHost``: the host form over validated host offsets; follows PFAC_setPlatform."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_clsigBatchMatchFromHost(self._c, h_input, size, h_offsets, num_segments, h_ids, h_pos, h_end, capacity, h_seg_first,
+                                                     C.byref(n))
+        return self._ret(st, "PFACX_clsigBatchMatchFromHost", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
+    def batch_pairs_device(self, d_input: int, size: int, d_offsets, num_segments: int, d_pair_ids, d_pair_pos, num_pairs: int, d_ids, d_pos, d_end,
+                           capacity: int, d_seg_first=None, check: bool = True):
+        """``PFACX_clsigBatchPairsFromDevice``: the batch list from a longest pair list of the handle over the same input; a pair's segment comes
+        from its position.  It runs no scan."""
+        n = C.c_size_t(0)
+        st = self._lib.PFACX_clsigBatchPairsFromDevice(self._c, d_input, size, d_offsets, num_segments, d_pair_ids, d_pair_pos, num_pairs, d_ids,
+                                                       d_pos, d_end, capacity, d_seg_first, C.byref(n))
+        return self._ret(st, "PFACX_clsigBatchPairsFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), n.value
+
     def close(self, check: bool = True) -> int:
         st = self._lib.PFACX_clsigClose(self._c)
         self._c = C.c_void_p()
@@ -2077,6 +2112,23 @@ class ClSigSet:
         if st != 0 or n2 != n:
             raise PFACError(st, "PFACX_clsigMatchFromHost", f"{n2} entries behind a count query that said {n}")
         return pos[:n].copy(), ids[:n].copy(), end[:n].copy()
+
+    def match_batch_host_array(self, data, offsets):
+        """match_batch_host over numpy arrays -> (pos, ids, end, seg_first) of the whole list: the count query first, then arrays of exactly
+        that length."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        buf = data if data.size else np.zeros(1, dtype=np.uint8)
+        segs = offsets.size - 1
+        _, n = self.match_batch_host(buf.ctypes.data, data.size, offsets.ctypes.data, segs, None, None, None, 0)
+        ids, pos, end = (np.full(max(1, n), -7, dtype=np.int32) for _ in range(3))
+        first = np.full(segs + 1, 2 ** 64 - 7, dtype=np.uint64)
+        st, n2 = self.match_batch_host(buf.ctypes.data, data.size, offsets.ctypes.data, segs, ids.ctypes.data, pos.ctypes.data, end.ctypes.data, n,
+                                       first.ctypes.data)
+        if st != 0 or n2 != n:
+            raise PFACError(st, "PFACX_clsigBatchMatchFromHost", f"{n2} entries behind a count query that said {n}")
+        return pos[:n].copy(), ids[:n].copy(), end[:n].copy(), first
 
 
 def rule_member_dtype():

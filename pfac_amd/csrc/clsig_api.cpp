@@ -15,6 +15,9 @@
  * with a run counted from each, not the kernel's one walk over the window.  The device form runs the unchanged compacted-output path with its
  * ordered pairs in handle scratch (PFACX_allReduce) and the passes of scan_clsig.hip (PFACX_clsigRun) behind it; the pairs form runs those
  * passes over a list of the caller's.  The host form takes the longest pairs from hostLongestPairs into a temporary of its own (clsigOnHost).
+ * The three batch forms (PFACX_clsigBatch*) are the same three functions with offsets: the scan stays the plain one over the whole buffer, the
+ * device passes get the offsets and clamp them (scan_clsig.hip), the host loop finds each pair's segment in the validated offsets and searches
+ * that segment's bytes as if they were the whole input.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -448,9 +451,11 @@ PFAC_status_t ensureDeviceTables(PFACX_clsig_s *sg)
     return st;
 }
 
-/* the passes over `count` ordered longest pairs, behind the argument checks; the caller holds c->lock */
+/* the passes over `count` ordered longest pairs, behind the argument checks; the caller holds c->lock.  d_offsets: a batch of numSegments
+ * segments (include/pfac_module.h), d_segFirst where the caller wants it; null: the plain call */
 PFAC_status_t clsigRunLocked(PFACX_clsig_s *sg, const char *d_input, size_t size, const int *d_pairIds, const int *d_pairPos, size_t count,
-                             int *d_ids, int *d_pos, int *d_end, size_t capacity, size_t *h_num_matched)
+                             int *d_ids, int *d_pos, int *d_end, size_t capacity, size_t *h_num_matched, const size_t *d_offsets = nullptr,
+                             size_t numSegments = 0, size_t *d_segFirst = nullptr)
 {
     PFAC_context *c = sg->handle;
     PFAC_status_t st = c->fa.maxChain > 1 ? ensureAllTable(c) : PFAC_STATUS_SUCCESS;
@@ -478,6 +483,9 @@ PFAC_status_t clsigRunLocked(PFACX_clsig_s *sg, const char *d_input, size_t size
     run.d_pos = d_pos;
     run.d_end = d_end;
     run.capacity = capacity;
+    run.d_offsets = d_offsets;
+    run.numSegments = numSegments;
+    run.d_segFirst = d_segFirst;
     size_t total = 0;
     st = c->clsig_run_ptr(c, &run, &total);
     if (st != PFAC_STATUS_SUCCESS) return st;
@@ -593,22 +601,32 @@ void searchOnHost(const PFACX_clsig_s &sg, const unsigned char *in, size_t n, co
 }
 
 /* The host loop: what the chains of `count` ordered longest pairs own into ids / pos / end (slots >= capacity are not written; end may be
- * null); returns the full length of the list */
+ * null); returns the full length of the list.  offsets (validated: 0 ... n, never decreasing; null: one segment, the buffer): a pair is searched
+ * inside the WINDOW [offsets[k], offsets[k + 1]) that holds its position -- the search sees the window's bytes as its whole input, and what it
+ * finds is shifted back --, and segFirst[k] (numSegments + 1 entries; may be null) = the length of the list in front of segment k */
 size_t clsigOnHost(const pfac::Automaton &fa, const PFACX_clsig_s &sg, const unsigned char *in, size_t n, const int *pairIds, const int *pairPos,
-                   size_t count, int *ids, int *pos, int *end, size_t capacity)
+                   size_t count, int *ids, int *pos, int *end, size_t capacity, const size_t *offsets = nullptr, size_t numSegments = 1,
+                   size_t *segFirst = nullptr)
 {
-    size_t total = 0;
+    const size_t whole[2] = {0, n};
+    if (!offsets) { offsets = whole; numSegments = 1; }
+    size_t total = 0, k = 0;                                                  /* k: the segments whose segFirst is written */
     for (size_t i = 0; i < count; i++) {
         const int p = pairPos[i];
         if (p < 0 || (size_t)p >= n) continue;
+        /* the last segment that starts at or in front of p: behind the empty ones that start there too */
+        const size_t seg = (size_t)(std::upper_bound(offsets, offsets + numSegments + 1, (size_t)p) - offsets) - 1;   /* offsets[0] == 0 <= p < n == offsets[numSegments] */
+        if (segFirst)
+            for (; k <= seg; k++) segFirst[k] = total;
+        const size_t lo = offsets[seg], hi = offsets[seg + 1];
         forEachChainMember(fa, pairIds[i], [&](int q) {                       /* (the caller's pin: fa.numPatterns == sg.numIds) */
             for (size_t v = sg.sigOff[(size_t)q]; v < sg.sigOff[(size_t)q + 1]; v++) {
                 const pfac::ClSigEntry &e = sg.sigs[v];
-                searchOnHost(sg, in, n, e, p, [&](int s, int behind) {
+                searchOnHost(sg, in + lo, hi - lo, e, p - (int)lo, [&](int s, int behind) {
                     if (total < capacity) {
                         ids[total] = e.id;
-                        pos[total] = s;
-                        if (end) end[total] = behind;
+                        pos[total] = s + (int)lo;
+                        if (end) end[total] = behind + (int)lo;
                     }
                     total++;
                 });
@@ -616,6 +634,8 @@ size_t clsigOnHost(const pfac::Automaton &fa, const PFACX_clsig_s &sg, const uns
             return true;
         });
     }
+    if (segFirst)
+        for (; k <= numSegments; k++) segFirst[k] = total;
     return total;
 }
 
@@ -711,12 +731,23 @@ PFAC_status_t PFACX_clsigGetAnchors(PFACX_clsig_t sig, int *h_anchorId, int *h_a
     return PFAC_STATUS_SUCCESS;
 }
 
-PFAC_status_t PFACX_clsigMatchFromDevice(PFACX_clsig_t sig, char *d_input, size_t size, int *d_ids, int *d_pos, int *d_end, size_t capacity,
-                                         size_t *h_num_matched)
+/* what the three batch forms check of their segments, behind checkClSigArgs: the offsets, their number (0 only with size == 0) */
+static PFAC_status_t checkBatchArgs(const size_t *offsets, size_t size, size_t numSegments)
+{
+    if (!offsets || numSegments >= kMaxInt || (size && numSegments == 0)) return PFAC_STATUS_INVALID_PARAMETER;
+    return PFAC_STATUS_SUCCESS;
+}
+
+/* The three forms, plain (batch == false: no offsets, no segFirst) and batch.  The device form scans the WHOLE buffer for the anchors, plain and
+ * ordered, also for a batch: every anchor that fits a segment at p is a prefix of the longest one at p, and the search rejects per signature what
+ * leaves the segment */
+static PFAC_status_t matchFromDevice(PFACX_clsig_t sig, char *d_input, size_t size, bool batch, const size_t *d_offsets, size_t numSegments, int *d_ids,
+                                     int *d_pos, int *d_end, size_t capacity, size_t *d_segFirst, size_t *h_num_matched)
 {
     PFAC_status_t st = checkClSigArgs(sig, d_input, size, h_num_matched);
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (!d_ids || !d_pos) return PFAC_STATUS_INVALID_PARAMETER;
+    if (batch && (st = checkBatchArgs(d_offsets, size, numSegments)) != PFAC_STATUS_SUCCESS) return st;
     PFAC_context *c = sig->handle;
     if (size && capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
     if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
@@ -734,16 +765,22 @@ PFAC_status_t PFACX_clsigMatchFromDevice(PFACX_clsig_t sig, char *d_input, size_
     if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
     const int *pairIds = c->scratch.allPairs.get();
     const int *pairPos = pairIds + c->scratch.allPairs.count() / 2;        /* one allocation: the ids, then as many positions */
-    if (count == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    return clsigRunLocked(sig, d_input, size, pairIds, pairPos, (size_t)count, d_ids, d_pos, d_end, capacity, h_num_matched);
+    if (count == 0) {
+        *h_num_matched = 0;
+        return d_segFirst ? zeroSegmentArrays(d_segFirst, nullptr, numSegments) : PFAC_STATUS_SUCCESS;
+    }
+    return clsigRunLocked(sig, d_input, size, pairIds, pairPos, (size_t)count, d_ids, d_pos, d_end, capacity, h_num_matched, d_offsets, numSegments,
+                          d_segFirst);
 }
 
-PFAC_status_t PFACX_clsigMatchFromHost(PFACX_clsig_t sig, char *h_input, size_t size, int *h_ids, int *h_pos, int *h_end, size_t capacity,
-                                       size_t *h_num_matched)
+static PFAC_status_t matchFromHost(PFACX_clsig_t sig, char *h_input, size_t size, bool batch, const size_t *h_offsets, size_t numSegments, int *h_ids,
+                                   int *h_pos, int *h_end, size_t capacity, size_t *h_segFirst, size_t *h_num_matched)
 {
     PFAC_status_t st = checkClSigArgs(sig, h_input, size, h_num_matched);
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (capacity && (!h_ids || !h_pos)) return PFAC_STATUS_INVALID_PARAMETER;
+    if (batch && (st = checkBatchArgs(h_offsets, size, numSegments)) != PFAC_STATUS_SUCCESS) return st;
+    if (batch && size && !batchOffsetsValid(h_offsets, numSegments, size)) return PFAC_STATUS_INVALID_PARAMETER;
     PFAC_context *c = sig->handle;
     {
         std::lock_guard<std::mutex> guard(c->lock);
@@ -752,24 +789,28 @@ PFAC_status_t PFACX_clsigMatchFromHost(PFACX_clsig_t sig, char *h_input, size_t 
     }
     if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
     if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
+    /* the longest pairs of the whole buffer on every platform (the GPU platform: the staged host path), the segments in the search alone */
     const HostPairs pairs(size, size);
     if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
     const PinnedPairs scan(c, h_input, size, pairs.ids, pairs.pos);
     if (scan.status != PFAC_STATUS_SUCCESS) return scan.status;
     if (scan.generation != sig->generation) return PFAC_STATUS_INVALID_PARAMETER;    /* another thread has replaced the set meanwhile: as after the call */
     const size_t total = clsigOnHost(c->fa, *sig, reinterpret_cast<const unsigned char *>(h_input), size, pairs.ids, pairs.pos,
-                                     (size_t)(scan.count > 0 ? scan.count : 0), h_ids, h_pos, h_end, capacity);
+                                     (size_t)(scan.count > 0 ? scan.count : 0), h_ids, h_pos, h_end, capacity, batch ? h_offsets : nullptr, numSegments,
+                                     h_segFirst);
     *h_num_matched = total;
     return truncatedIf(total, capacity);
 }
 
-PFAC_status_t PFACX_clsigPairsFromDevice(PFACX_clsig_t sig, const char *d_input, size_t size, const int *d_pairIds, const int *d_pairPos,
-                                         size_t numPairs, int *d_ids, int *d_pos, int *d_end, size_t capacity, size_t *h_num_matched)
+static PFAC_status_t pairsFromDevice(PFACX_clsig_t sig, const char *d_input, size_t size, bool batch, const size_t *d_offsets, size_t numSegments,
+                                     const int *d_pairIds, const int *d_pairPos, size_t numPairs, int *d_ids, int *d_pos, int *d_end, size_t capacity,
+                                     size_t *d_segFirst, size_t *h_num_matched)
 {
     PFAC_status_t st = checkClSigArgs(sig, d_input, size, h_num_matched);
     if (st != PFAC_STATUS_SUCCESS) return st;
     if (numPairs > kMaxInt || capacity > SIZE_MAX / sizeof(int) || (numPairs && (!d_pairIds || !d_pairPos)) || (capacity && (!d_ids || !d_pos)))
         return PFAC_STATUS_INVALID_PARAMETER;
+    if (batch && (st = checkBatchArgs(d_offsets, size, numSegments)) != PFAC_STATUS_SUCCESS) return st;
     if (capacity && numPairs) {
         const size_t in = numPairs * sizeof(int), out = capacity * sizeof(int);
         for (const int *array : {d_ids, d_pos, d_end})
@@ -780,8 +821,51 @@ PFAC_status_t PFACX_clsigPairsFromDevice(PFACX_clsig_t sig, const char *d_input,
     std::lock_guard<std::mutex> guard(c->lock);
     st = checkSetGeneration(c, sig->generation);
     if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0 || numPairs == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    return clsigRunLocked(sig, d_input, size, d_pairIds, d_pairPos, numPairs, d_ids, d_pos, d_end, capacity, h_num_matched);
+    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
+    if (numPairs == 0) {
+        *h_num_matched = 0;
+        return d_segFirst ? zeroSegmentArrays(d_segFirst, nullptr, numSegments) : PFAC_STATUS_SUCCESS;
+    }
+    return clsigRunLocked(sig, d_input, size, d_pairIds, d_pairPos, numPairs, d_ids, d_pos, d_end, capacity, h_num_matched, d_offsets, numSegments,
+                          d_segFirst);
+}
+
+PFAC_status_t PFACX_clsigMatchFromDevice(PFACX_clsig_t sig, char *d_input, size_t size, int *d_ids, int *d_pos, int *d_end, size_t capacity,
+                                         size_t *h_num_matched)
+{
+    return matchFromDevice(sig, d_input, size, false, nullptr, 0, d_ids, d_pos, d_end, capacity, nullptr, h_num_matched);
+}
+
+PFAC_status_t PFACX_clsigMatchFromHost(PFACX_clsig_t sig, char *h_input, size_t size, int *h_ids, int *h_pos, int *h_end, size_t capacity,
+                                       size_t *h_num_matched)
+{
+    return matchFromHost(sig, h_input, size, false, nullptr, 0, h_ids, h_pos, h_end, capacity, nullptr, h_num_matched);
+}
+
+PFAC_status_t PFACX_clsigPairsFromDevice(PFACX_clsig_t sig, const char *d_input, size_t size, const int *d_pairIds, const int *d_pairPos,
+                                         size_t numPairs, int *d_ids, int *d_pos, int *d_end, size_t capacity, size_t *h_num_matched)
+{
+    return pairsFromDevice(sig, d_input, size, false, nullptr, 0, d_pairIds, d_pairPos, numPairs, d_ids, d_pos, d_end, capacity, nullptr, h_num_matched);
+}
+
+PFAC_status_t PFACX_clsigBatchMatchFromDevice(PFACX_clsig_t sig, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments, int *d_ids,
+                                              int *d_pos, int *d_end, size_t capacity, size_t *d_segFirst, size_t *h_num_matched)
+{
+    return matchFromDevice(sig, d_input, size, true, d_offsets, numSegments, d_ids, d_pos, d_end, capacity, d_segFirst, h_num_matched);
+}
+
+PFAC_status_t PFACX_clsigBatchMatchFromHost(PFACX_clsig_t sig, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments, int *h_ids,
+                                            int *h_pos, int *h_end, size_t capacity, size_t *h_segFirst, size_t *h_num_matched)
+{
+    return matchFromHost(sig, h_input, size, true, h_offsets, numSegments, h_ids, h_pos, h_end, capacity, h_segFirst, h_num_matched);
+}
+
+PFAC_status_t PFACX_clsigBatchPairsFromDevice(PFACX_clsig_t sig, const char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
+                                              const int *d_pairIds, const int *d_pairPos, size_t numPairs, int *d_ids, int *d_pos, int *d_end,
+                                              size_t capacity, size_t *d_segFirst, size_t *h_num_matched)
+{
+    return pairsFromDevice(sig, d_input, size, true, d_offsets, numSegments, d_pairIds, d_pairPos, numPairs, d_ids, d_pos, d_end, capacity, d_segFirst,
+                           h_num_matched);
 }
 
 } /* extern "C" */

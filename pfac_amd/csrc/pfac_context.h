@@ -531,7 +531,8 @@ struct DeviceScratch {
      * list of PFACX_editMatchFromDevice is allPairs, the prefix table allTable: shared.  The piece tables of an edit object are state of that
      * object, not scratch (edit_api.cpp) */
     DeviceBuffer<char> editSet;
-    /* the class-signature calls (PFACX_clsig*, scan_clsig.hip): the 64-bit list offsets of the blocks of its pair passes, sized like caseSet; the
+    /* the class-signature calls (PFACX_clsig*, scan_clsig.hip): the 64-bit list offsets of the blocks of its pair passes, sized like caseSet, and
+     * behind them the 32-bit clamped offsets of a batch call; the
      * pair list of PFACX_clsigMatchFromDevice is allPairs, the prefix table allTable: shared.  The signature, part and class tables of a
      * class-signature object are state of that object, not scratch (clsig_api.cpp) */
     DeviceBuffer<char> clsigSet;

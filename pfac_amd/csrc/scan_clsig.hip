@@ -48,7 +48,11 @@
  * chainLen steps whatever the table says, signature and part ranges and class indices are clamped to their tables, a part whose dwords do not lie
  * inside the blob holds nowhere: a caller's list cannot make a pass read or write outside the buffers.  A thread per pair: DESIGN.md 5z says what
  * that costs.
- * SCRATCH: 8 (blocks + 1) bytes rounded up to 256 (DeviceScratch::clsigSet), blocks = one per 256 pairs, eight per compute unit at most.
+ * A BATCH (PFACX_clsigBatch*): the same search inside a WINDOW [lo, hi), the segment that holds the pair's position, wherever the
+ * text above says 0 and n (alignedDword alone keeps testing against the buffer: a dword that straddles a segment edge is loaded, and only bytes of
+ * [s, s + len) enter a compare); pfac_clsig_bounds, pfac_clsig_batch_count and pfac_clsig_batch_write stand further down with their own text.
+ * SCRATCH: 8 (blocks + 1) bytes rounded up to 256 (DeviceScratch::clsigSet), blocks = one per 256 pairs, eight per compute unit at most; a batch
+ * takes 4 (numSegments + 1) bytes rounded up to 256 behind them.
  * Plain C++ and vector stores only.
  */
 #if !defined(__gfx950__) && defined(__HIP_DEVICE_COMPILE__)
@@ -84,6 +88,23 @@ struct ClSigArgs {
     unsigned int numClasses;
     unsigned int shortest;              /* PFACX_CLSIG_SHORTEST_END */
     int *end;                           /* the ends, capacity entries, or null */
+};
+
+/* The bounds passes: the plain arguments and the segments of a batch */
+struct ClSigBatchArgs : ClSigArgs {
+    const unsigned int *bounds;         /* [numSegments + 1] ascending, inside [0, n] (pfac_clsig_bounds) */
+    unsigned int numSegments;
+    unsigned long long *segFirst;       /* [numSegments + 1], or null */
+};
+
+/* THE WINDOW [lo, hi) of a search: the bytes that exist for it.  The plain passes search the whole buffer -- lo a constant, hi the n of the
+ * arguments, so they compile to what they were --, the batch passes the segment that holds the pair's position */
+struct WholeBuffer {
+    static constexpr unsigned int lo = 0u;
+    unsigned int hi;
+};
+struct Segment {
+    unsigned int lo, hi;
 };
 
 /* where a boundary can lie: every offset, those of embeddings with the anchor part below x, those with it at x (lt and eq: subsets of all) */
@@ -146,9 +167,10 @@ __device__ __forceinline__ bool literalEqual(const ClSigArgs &a, unsigned int s,
     return true;
 }
 
-/* the bits t of m at which literal part q holds at offset base + dir * t: inside [0, n) -- tested before any load -- and every byte equal.  A
+/* the bits t of m at which literal part q holds at offset base + dir * t: inside the window -- tested before any load -- and every byte equal.  A
  * part that is empty or whose dwords do not lie inside the blob holds nowhere */
-__device__ __forceinline__ uint64_t literalWhere(const ClSigArgs &a, const pfac::ClSigPart &q, long long base, int dir, uint64_t m)
+template <class W>
+__device__ __forceinline__ uint64_t literalWhere(const ClSigArgs &a, const W &w, const pfac::ClSigPart &q, long long base, int dir, uint64_t m)
 {
     const unsigned int len = q.a, need = (len + 3u) >> 2;
     if (len == 0u || len > kClSigMaxRepeat || q.b >= a.blobWords || a.blobWords - q.b < need) return 0ull;
@@ -157,7 +179,7 @@ __device__ __forceinline__ uint64_t literalWhere(const ClSigArgs &a, const pfac:
         const int t = __builtin_ctzll(m);
         m &= m - 1ull;
         const long long o = base + (long long)dir * t;
-        if (o < 0 || o + (long long)len > (long long)a.n) continue;
+        if (o < (long long)w.lo || o + (long long)len > (long long)w.hi) continue;
         if (literalEqual(a, (unsigned int)o, len, q.b)) held |= 1ull << t;
     }
     return held;
@@ -174,14 +196,15 @@ __device__ __forceinline__ bool classUsable(const ClSigArgs &a, const pfac::ClSi
 
 /* class part q = (C, lo, hi) FORWARDS: bit t of r = the part starts at base + t; behind it bit t' = the next part starts at base + lo + t'.  One
  * walk from the far end of the window to its near end, `run` the length of the run of bytes of C that starts at o, counted inside the window */
-__device__ __forceinline__ Reach classForward(const ClSigArgs &a, const uint32_t *staged, const pfac::ClSigPart &q, long long base, const Reach &r)
+template <class W>
+__device__ __forceinline__ Reach classForward(const ClSigArgs &a, const W &w, const uint32_t *staged, const pfac::ClSigPart &q, long long base, const Reach &r)
 {
     Reach out{0ull, 0ull, 0ull};
     if (r.all == 0ull || !classUsable(a, q)) return out;
     const unsigned int lo = q.b, hi = q.c;
     long long far = base + (63 - __builtin_clzll(r.all)) + (long long)hi, near = base + __builtin_ctzll(r.all);
-    if (far > (long long)a.n) far = (long long)a.n;       /* nothing behind n exists: a run ends there */
-    if (near < 0) near = 0;
+    if (far > (long long)w.hi) far = (long long)w.hi;     /* nothing behind the window exists: a run ends there */
+    if (near < (long long)w.lo) near = (long long)w.lo;
     unsigned int run = 0;
     for (long long o = far; o >= near; o--) {             /* at most hi + 64 rounds */
         if (o < far) run = inClass(a, staged, q.a, a.in[o]) ? run + 1u : 0u;
@@ -199,13 +222,14 @@ __device__ __forceinline__ Reach classForward(const ClSigArgs &a, const uint32_t
 
 /* the same BACKWARDS: bit t of m = the part ends in front of base - t; bit t' of the result = it starts at base - lo - t'.  One walk upwards,
  * `run` the length of the run of bytes of C that ends in front of o, counted inside the window */
-__device__ __forceinline__ uint64_t classBackward(const ClSigArgs &a, const uint32_t *staged, const pfac::ClSigPart &q, long long base, uint64_t m)
+template <class W>
+__device__ __forceinline__ uint64_t classBackward(const ClSigArgs &a, const W &w, const uint32_t *staged, const pfac::ClSigPart &q, long long base, uint64_t m)
 {
     if (m == 0ull || !classUsable(a, q)) return 0ull;
     const unsigned int lo = q.b, hi = q.c;
     long long low = base - (63 - __builtin_clzll(m)) - (long long)hi, high = base - __builtin_ctzll(m);
-    if (low < 0) low = 0;                                 /* nothing in front of 0 exists: a run starts there */
-    if (high > (long long)a.n) high = (long long)a.n;
+    if (low < (long long)w.lo) low = (long long)w.lo;     /* nothing in front of the window exists: a run starts there */
+    if (high > (long long)w.hi) high = (long long)w.hi;
     uint64_t out = 0ull;
     unsigned int run = 0;
     for (long long o = low; o <= high; o++) {             /* at most hi + 64 rounds */
@@ -218,28 +242,28 @@ __device__ __forceinline__ uint64_t classBackward(const ClSigArgs &a, const uint
     return out;
 }
 
-/* The (start, end) that the pair at p owns of signature e (the header says how): emit(e.id, start, end) for each, starts ascending; returns
- * their number */
-template <class Emit>
-__device__ __forceinline__ unsigned int searchSignature(const ClSigArgs &a, const uint32_t *staged, const pfac::ClSigEntry &e, int p, Emit emit)
+/* The (start, end) that the pair at p, a position inside the window w, owns of signature e (the header says how): emit(e.id, start, end) for
+ * each, starts ascending; returns their number */
+template <class W, class Emit>
+__device__ __forceinline__ unsigned int searchSignature(const ClSigArgs &a, const W &w, const uint32_t *staged, const pfac::ClSigEntry &e, int p, Emit emit)
 {
     const unsigned int count = e.partsAnchor & 0xFFFFu, anchor = e.partsAnchor >> 16;
     if (count < 1u || count > kClSigMaxParts || anchor >= count || e.firstPart >= a.numParts || a.numParts - e.firstPart < count) return 0u;
-    if (e.anchorOff > (unsigned int)p) return 0u;                                                    /* x < 0: before any load */
+    if (e.anchorOff > (unsigned int)p - w.lo) return 0u;                                             /* x in front of the window: before any load */
     const pfac::ClSigPart *parts = a.parts + e.firstPart;
     const pfac::ClSigPart pa = parts[anchor];
     if (pa.kind != 0u) return 0u;
     const long long x = (long long)p - (long long)e.anchorOff;
     /* 1. backwards: bit t of `back` = the boundary lies t bytes in front of `tight`, its offset with every run up to part a at lo */
-    uint64_t back = literalWhere(a, pa, x, 1, 1ull);
+    uint64_t back = literalWhere(a, w, pa, x, 1, 1ull);
     long long tight = x;
     for (unsigned int j = anchor; j > 0u && back != 0ull; j--) {
         const pfac::ClSigPart q = parts[j - 1u];
         if (q.kind == 0u) {
             tight -= (long long)q.a;
-            back = literalWhere(a, q, tight, -1, back);
+            back = literalWhere(a, w, q, tight, -1, back);
         } else {
-            back = classBackward(a, staged, q, tight, back);
+            back = classBackward(a, w, staged, q, tight, back);
             tight -= (long long)q.b;
         }
     }
@@ -249,7 +273,7 @@ __device__ __forceinline__ unsigned int searchSignature(const ClSigArgs &a, cons
             const int t = __builtin_ctzll(m);
             m &= m - 1ull;
             const long long s = tight - t;
-            if (s > 0 && s <= (long long)a.n && inClass(a, staged, (unsigned int)e.notBefore, a.in[s - 1])) back &= ~(1ull << t);
+            if (s > (long long)w.lo && s <= (long long)w.hi && inClass(a, staged, (unsigned int)e.notBefore, a.in[s - 1])) back &= ~(1ull << t);
         }
     }
     unsigned int found = 0;
@@ -257,17 +281,17 @@ __device__ __forceinline__ unsigned int searchSignature(const ClSigArgs &a, cons
         const int tb = 63 - __builtin_clzll(back);
         back &= ~(1ull << tb);
         const long long s = tight - tb;
-        if (s < 0) continue;                                                                         /* (the steps drop them: never) */
+        if (s < (long long)w.lo) continue;                                                           /* (the steps drop them: never) */
         /* 2. forwards to boundary a: bit t = it lies t bytes behind `at`, its offset with every run from part 0 at lo */
         Reach r{1ull, 0ull, 0ull};
         long long at = s;
         for (unsigned int j = 0; j < anchor && r.all != 0ull; j++) {
             const pfac::ClSigPart q = parts[j];
             if (q.kind == 0u) {
-                r.all = literalWhere(a, q, at, 1, r.all);
+                r.all = literalWhere(a, w, q, at, 1, r.all);
                 at += (long long)q.a;
             } else {
-                r = classForward(a, staged, q, at, r);
+                r = classForward(a, w, staged, q, at, r);
                 at += (long long)q.b;
             }
         }
@@ -279,12 +303,12 @@ __device__ __forceinline__ unsigned int searchSignature(const ClSigArgs &a, cons
         for (unsigned int j = anchor; j < count && r.eq != 0ull; j++) {
             const pfac::ClSigPart q = parts[j];
             if (q.kind == 0u) {
-                r.all = literalWhere(a, q, at, 1, r.all);
+                r.all = literalWhere(a, w, q, at, 1, r.all);
                 r.lt &= r.all;
                 r.eq &= r.all;
                 at += (long long)q.a;
             } else {
-                r = classForward(a, staged, q, at, r);
+                r = classForward(a, w, staged, q, at, r);
                 at += (long long)q.b;
             }
         }
@@ -295,7 +319,7 @@ __device__ __forceinline__ unsigned int searchSignature(const ClSigArgs &a, cons
                 const int t = __builtin_ctzll(m);
                 m &= m - 1ull;
                 const long long end = at + t;
-                if (end >= (long long)a.n || !inClass(a, staged, (unsigned int)e.notAfter, a.in[end])) valid |= 1ull << t;
+                if (end >= (long long)w.hi || !inClass(a, staged, (unsigned int)e.notAfter, a.in[end])) valid |= 1ull << t;
             }
             r.all &= valid;
             r.lt &= valid;
@@ -310,20 +334,121 @@ __device__ __forceinline__ unsigned int searchSignature(const ClSigArgs &a, cons
 
 /* What pair k owns along its chain, longest anchor first, table order (signature id descending) within an anchor (scan_passes.h:
  * forEachChainMember), starts ascending within a signature: emit(signature id, start, end) for each; returns their number */
-template <class Emit>
-__device__ __forceinline__ unsigned int walkPair(const ClSigArgs &a, const uint32_t *staged, size_t k, Emit emit)
+template <class W, class Emit>
+__device__ __forceinline__ unsigned int walkChainAt(const ClSigArgs &a, const W &w, const uint32_t *staged, int id, int p, Emit emit)
 {
-    const int id = a.f.pairIds[k], p = a.f.pairPos[k];
-    if (p < 0 || (unsigned int)p >= a.n) return 0u;
     unsigned int found = 0;
     forEachChainMember(a.f.table, a.f.numIds, id, [&](int q) {
         const unsigned int first = a.sigOff[q];
         unsigned int end = a.sigOff[q + 1];
         if (end > a.numSigs) end = a.numSigs;
-        for (unsigned int v = first; v < end; v++) found += searchSignature(a, staged, a.sigs[v], p, emit);
+        for (unsigned int v = first; v < end; v++) found += searchSignature(a, w, staged, a.sigs[v], p, emit);
         return true;
     });
     return found;
+}
+
+/* ... of the plain passes: the window is the buffer */
+template <class Emit>
+__device__ __forceinline__ unsigned int walkPair(const ClSigArgs &a, const uint32_t *staged, size_t k, Emit emit)
+{
+    const int id = a.f.pairIds[k], p = a.f.pairPos[k];
+    if (p < 0 || (unsigned int)p >= a.n) return 0u;
+    return walkChainAt(a, WholeBuffer{a.n}, staged, id, p, emit);
+}
+
+/* ------------------------------------------------------------------ the batch passes (PFACX_clsigBatch*)
+ * THE PAIR'S SEGMENT comes from its POSITION p: u(p) = the number of bounds <= p; u in [1, numSegments]: segment u - 1 = [bounds[u - 1], bounds[u]),
+ * which holds p; else (p in front of the first bound, at or behind the last, negative): no segment, the pair owns nothing.  An ordered list has
+ * its u ascending, so a block searches the bounds ONCE for its first and its last pair, the whole wave at a time (waveLowerBound), and a lane then
+ * searches only between the two (scan_groups.hip does the same over pair indices).  What a lane finds there is CHECKED against the two bounds
+ * around it and, where it fails -- a caller's list that does not ascend --, searched for again over all bounds: the entries of a pair are right
+ * whatever the order of the list.
+ * WHO WRITES segFirst[k]: the thread of the first pair i with u(p_i) > k writes the list offset in front of its pair -- the entries k in
+ * [u(p_(i-1)), u(p_i)), found by walking down from u(p_i) while the bound lies behind the position of the pair in front (pair 0: all of them);
+ * the entries k >= u(the last pair's position) get the length of the list from a grid-stride loop of the same launch.  Over an ascending list
+ * every entry has exactly one writer; over any other the stores stay inside segFirst and their values are unspecified. */
+
+/* bounds[k] = the largest of the entries [0, k] of the caller's offsets, each clamped to [0, limit]; k < n = numSegments + 1 (a block of 1024
+ * threads per 8192 entries that folds what lies in front of them itself: pfac_groups_bounds of scan_groups.hip over 64-bit offsets) */
+constexpr unsigned int kBoundsPer = 8;
+constexpr unsigned int kBoundsBlock = 1024 * kBoundsPer;          /* pfac_amd/api.py: PFACX_CLSIG_BOUNDS_BLOCK */
+
+__device__ __forceinline__ unsigned int clampOffset(size_t o, unsigned int limit) { return o > (size_t)limit ? limit : (unsigned int)o; }
+
+__global__ __launch_bounds__(1024) void pfac_clsig_bounds(const size_t *offsets, unsigned int n, unsigned int limit, unsigned int *bounds)
+{
+    __shared__ unsigned int waveOwn[16], waveFront[16];
+    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned int base = blockIdx.x * kBoundsBlock, i0 = base + threadIdx.x * kBoundsPer;
+    unsigned int front = 0;                                             /* what lies in front of the block's entries: coalesced, from L2 */
+    for (unsigned int q = threadIdx.x; q < base; q += 1024u) front = OpMax()(front, clampOffset(offsets[q], limit));
+    unsigned int x[kBoundsPer], own = 0;
+#pragma unroll
+    for (unsigned int k = 0; k < kBoundsPer; k++) {
+        x[k] = i0 + k < n ? clampOffset(offsets[i0 + k], limit) : 0u;   /* (i0 + k < 2^31 + 8192: no wrap) */
+        own = OpMax()(own, x[k]);
+    }
+    const unsigned int incl = waveInclusive(own, OpMax());
+    const unsigned int frontAll = waveReduce(front, OpMax());
+    const unsigned int excl = waveExclusiveOf(incl);
+    if (lane == 63) { waveOwn[wave] = incl; waveFront[wave] = frontAll; }
+    __syncthreads();
+    unsigned int run = excl;
+    for (unsigned int w = 0; w < 16; w++) {
+        run = OpMax()(run, waveFront[w]);
+        if (w < wave) run = OpMax()(run, waveOwn[w]);
+    }
+#pragma unroll
+    for (unsigned int k = 0; k < kBoundsPer; k++) {
+        run = OpMax()(run, x[k]);
+        if (i0 + k < n) bounds[i0 + k] = run;
+    }
+}
+
+/* the first k of [lo, hi) with bounds[k] > p, else hi; a lane by itself (bounds[k] <= n < 2^31: the compare is signed) */
+__device__ __forceinline__ unsigned int boundsBehind(const ClSigBatchArgs &a, unsigned int lo, unsigned int hi, int p)
+{
+    while (lo < hi) {                                       /* at most 32 rounds */
+        const unsigned int mid = lo + ((hi - lo) >> 1);
+        if ((int)a.bounds[mid] > p) hi = mid;
+        else lo = mid + 1u;
+    }
+    return lo;
+}
+
+/* where u of a block's pairs lies if its list ascends: inside [lo, hi]; found once per block, by every wave alike (all 64 lanes call it) */
+struct BlockSegs { unsigned int lo, hi; };
+__device__ __forceinline__ BlockSegs blockSegs(const ClSigBatchArgs &a)
+{
+    const size_t first = (size_t)blockIdx.x * a.f.per;
+    const size_t end = a.f.count - first < a.f.per ? a.f.count : first + a.f.per;
+    const int pLo = a.f.pairPos[first], pHi = a.f.pairPos[end - 1];
+    BlockSegs b;
+    b.lo = waveLowerBound(0u, a.numSegments + 1u, [&](unsigned int k) { return (int)a.bounds[k] > pLo; });
+    b.hi = waveLowerBound(b.lo, a.numSegments + 1u, [&](unsigned int k) { return (int)a.bounds[k] > pHi; });
+    return b;
+}
+
+/* u(p) of a pair of the block, and its segment's window (false: it lies in no segment) */
+__device__ __forceinline__ bool segmentOfPair(const ClSigBatchArgs &a, const BlockSegs &b, int p, unsigned int &u, Segment &w)
+{
+    const unsigned int all = a.numSegments + 1u;
+    u = boundsBehind(a, b.lo, b.hi, p);
+    if ((u > 0u && (int)a.bounds[u - 1u] > p) || (u < all && (int)a.bounds[u] <= p)) u = boundsBehind(a, 0u, all, p);   /* the list does not ascend */
+    if (u < 1u || u > a.numSegments) return false;
+    w = Segment{a.bounds[u - 1u], a.bounds[u]};
+    return true;
+}
+
+/* what pair k owns inside its segment */
+template <class Emit>
+__device__ __forceinline__ unsigned int walkBatchPair(const ClSigBatchArgs &a, const BlockSegs &b, const uint32_t *staged, size_t k, unsigned int &u, Emit emit)
+{
+    const int id = a.f.pairIds[k], p = a.f.pairPos[k];
+    Segment w;
+    if (!segmentOfPair(a, b, p, u, w)) return 0u;           /* (inside a segment: 0 <= p < n) */
+    return walkChainAt(a, w, staged, id, p, emit);
 }
 
 /* the first kClSigStaged classes of the table into the block's LDS, by all of its threads; the block waits for them */
@@ -355,6 +480,47 @@ __global__ __launch_bounds__(kClSigBlock) void pfac_clsig_write(ClSigArgs a)
         });
 }
 
+__global__ __launch_bounds__(kClSigBlock) void pfac_clsig_batch_count(ClSigBatchArgs a)
+{
+    __shared__ uint32_t staged[8u * kClSigStaged];
+    stageClasses(a, staged);
+    const BlockSegs b = blockSegs(a);
+    expandCount<kClSigBlock>(a.f, [&](size_t k) -> unsigned long long {
+        unsigned int u;
+        return walkBatchPair(a, b, staged, k, u, [](int, int, int) {});
+    });
+}
+
+__global__ __launch_bounds__(kClSigBlock) void pfac_clsig_batch_write(ClSigBatchArgs a)
+{
+    __shared__ uint32_t staged[8u * kClSigStaged];
+    stageClasses(a, staged);
+    const BlockSegs b = blockSegs(a);
+    /* the entries of segFirst that no pair owns: the bounds behind the last pair's position */
+    if (a.segFirst != nullptr) {
+        const int pLast = a.f.pairPos[a.f.count - 1];
+        const unsigned int tail = waveLowerBound(0u, a.numSegments + 1u, [&](unsigned int k) { return (int)a.bounds[k] > pLast; });
+        const unsigned long long total = a.f.blockBase[gridDim.x];
+        for (size_t k = (size_t)tail + (size_t)blockIdx.x * kClSigBlock + threadIdx.x; k <= a.numSegments; k += (size_t)gridDim.x * kClSigBlock)
+            a.segFirst[k] = total;
+    }
+    unsigned int u = 0u;                                        /* of the pair a thread has just valued: left to its hook */
+    expandWrite<kClSigBlock>(
+        a.f, [&](size_t k) -> unsigned long long { return walkBatchPair(a, b, staged, k, u, [](int, int, int) {}); },
+        [&](size_t k, auto emit) {
+            unsigned int again;
+            (void)walkBatchPair(a, b, staged, k, again, [&](int id, int s, int end) {
+                if (a.end != nullptr && emit.o < emit.f.capacity) a.end[emit.o] = end;                /* the slot the frame's store takes next */
+                emit(id, s);
+            });
+        },
+        [&](size_t k, unsigned long long before) {
+            if (a.segFirst == nullptr) return;                  /* every segment that starts behind the pair in front and at or in front of this one */
+            const int prev = k > 0 ? a.f.pairPos[k - 1] : -1;
+            for (unsigned int j = u; j > 0u && (int)a.bounds[j - 1u] > prev; j--) a.segFirst[j - 1u] = before;   /* (u <= numSegments + 1) */
+        });
+}
+
 } // namespace
 
 extern "C" {
@@ -366,10 +532,16 @@ PFAC_status_t PFACX_clsigRun(PFAC_handle_t handle, const PFACX_clsigRun_t *run, 
         !run->d_sigs || run->numSigs > (size_t)0x7fffffff || !run->d_parts || run->numParts > (size_t)0x7fffffff ||
         run->blobWords > (size_t)0x7fffffff || !run->d_blob || !run->d_classes || run->numClasses == 0 || run->numClasses > (size_t)0xFFFF ||
         (run->flags & ~PFACX_CLSIG_SHORTEST_END) != 0u || run->count > (size_t)0x7fffffff || (run->count && (!run->d_pairIds || !run->d_pairPos)) ||
-        (run->capacity && (!run->d_ids || !run->d_pos)))
+        (run->capacity && (!run->d_ids || !run->d_pos)) ||
+        (run->d_offsets ? run->numSegments == 0 || run->numSegments >= (size_t)0x7fffffff : run->d_segFirst != nullptr))
         return PFAC_STATUS_INVALID_PARAMETER;
     *h_total = 0;
-    if (run->count == 0) return PFAC_STATUS_SUCCESS;
+    if (run->count == 0) {                                      /* no pair: nothing to launch */
+        if (!run->d_segFirst) return PFAC_STATUS_SUCCESS;
+        return hipMemsetAsync(run->d_segFirst, 0, (run->numSegments + 1) * sizeof(size_t), nullptr) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess
+                   ? PFAC_STATUS_SUCCESS
+                   : PFAC_STATUS_INTERNAL_ERROR;
+    }
     PFAC_context *c = handle;
     ClSigArgs a{};
     a.in = reinterpret_cast<const unsigned char *>(run->d_input);
@@ -387,6 +559,22 @@ PFAC_status_t PFACX_clsigRun(PFAC_handle_t handle, const PFACX_clsigRun_t *run, 
     a.end = run->capacity ? run->d_end : nullptr;
     a.f = ExpandFrame{run->d_pairIds, run->d_pairPos, run->count, static_cast<const pfac::Int2 *>(run->d_table), (unsigned int)run->numIds,
                       1u, 0, nullptr, run->d_ids, run->d_pos, run->capacity};
+    if (run->d_offsets) {                                       /* a batch: the bounds in front of the passes, behind the block totals in the same scratch */
+        ClSigBatchArgs b{};
+        static_cast<ClSigArgs &>(b) = a;
+        b.numSegments = (unsigned int)run->numSegments;
+        static_assert(sizeof(size_t) == sizeof(unsigned long long), "segFirst is written as 64-bit words");
+        b.segFirst = reinterpret_cast<unsigned long long *>(run->d_segFirst);
+        unsigned int *bounds = nullptr;
+        return expandPasses(
+            c, c->scratch.clsigSet, pfac::kHostClSig, b, pfac_clsig_batch_count, pfac_clsig_batch_write, kClSigBlock, b.f.capacity != 0 || b.segFirst != nullptr,
+            h_total, [&](ScratchCarver &k) { b.bounds = bounds = k.take<unsigned int>(run->numSegments + 1); }, false,
+            [&]() {
+                hipLaunchKernelGGL(pfac_clsig_bounds, dim3((b.numSegments + 1u + kBoundsBlock - 1u) / kBoundsBlock), dim3(1024), 0, 0, run->d_offsets,
+                                   b.numSegments + 1u, b.n, bounds);
+                return true;
+            });
+    }
     return expandPasses(c, c->scratch.clsigSet, pfac::kHostClSig, a, pfac_clsig_count, pfac_clsig_write, kClSigBlock, a.f.capacity != 0, h_total);
 }
 

@@ -1474,6 +1474,40 @@ PFAC_status_t PFACX_clsigBatchPairsFromDevice(PFACX_clsig_t sig, const char *d_i
                                               int *d_ids, int *d_pos, int *d_end /* may be NULL */, size_t capacity,
                                               size_t *d_segFirst /* numSegments + 1; may be NULL */, size_t *h_num_matched);
 
+/* Cover: an UNSORTED list of intervals as the maximal runs of the bytes they cover -- the step between a list of (id, start, end) hits
+ * (PFACX_gapsig*, PFACX_edit*, PFACX_clsig* and PFACX_clsigBatch*, whose lists are ordered by the owning anchor, not by start, and hold duplicate
+ * starts, nested and overlapping intervals) and PFACX_redactSpansFromDevice, which takes an ascending disjoint list.  Any caller-made list works
+ * as well; no matcher runs, and no pattern set is needed.
+ *   COVERED.  Interval i is [s_i, e_i) with s_i = start[i] and e_i = end[i] -- with PFACX_COVER_LENGTHS in `flags` the second array holds lengths
+ *   and e_i = start[i] + end[i] in 64-bit arithmetic.  Every interval is clamped to [0, size] where it is read; one that is empty after the clamp
+ *   (e <= s, s >= size, e <= 0, a negative length) covers nothing.  Byte b of [0, size) is covered iff some clamped interval holds it.  No order
+ *   is assumed: duplicates, nesting and overlap are all legal.  No input buffer is taken and none is read: `size` only bounds the positions.
+ *   The SPANS are exactly those of PFACX_matchSpans*: the maximal runs of covered bytes, ascending, disjoint and never adjacent -- intervals that
+ *   touch ([a, b) and [b, c)) form one span.  spanLen[i] >= 1; *h_coveredBytes = the sum of the lengths; numSpans <= (size + 1) / 2.  The result
+ *   is a legal argument of PFACX_redactSpansFromDevice as it stands.
+ *   Spans know NO SEGMENTS: over the list of a batch call (PFACX_clsigBatch*, whose entries are offsets into the whole buffer) a span that ends
+ *   with one segment and one that starts the next touch and come out as one.
+ * capacity: entries of each span array, ANY value -- the arrays are not a scan's scratch here.  More spans than `capacity`: exactly the first
+ * `capacity` spans are written and nothing behind them, both counts are still the full ones, and the call returns PFACX_STATUS_OUTPUT_TRUNCATED.
+ * capacity == 0 with null span arrays is the count query.
+ * PFAC_STATUS_INVALID_PARAMETER: a null count pointer, null interval arrays with numIntervals > 0, null span arrays with capacity > 0, size >=
+ * 2^31, numIntervals >= 2^31, a flag bit other than PFACX_COVER_LENGTHS and, in the device form, a span array that overlaps an interval array (the
+ * rule of the pairs forms).  size == 0: success, both counts 0, nothing touched.  numIntervals == 0: success, both counts 0, no span written.
+ * The device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.  The host form runs on the CPU on every platform, host-only handles included:
+ * the clamped intervals sorted by start and one sweep, memory proportional to numIntervals, never to `size`.  Both forms are synchronous and take
+ * the handle's lock.  The interval arrays are never modified.
+ * MEMORY of the device form: grow-only handle scratch sized by `size` alone -- a hierarchy of bitmaps with fan-out 32, a bit per byte at the
+ * bottom: about size / 8 x 32 / 31 bytes, plus 8 bytes per 32 KiB of positions -- zeroed by one memset per call: deviceScratchBytes of
+ * PFACX_getInfo, freed by PFACX_trim.
+ * COST: the memset, at most 14 atomic ORs per interval however long it is, two passes over the bitmap; not measured yet. */
+#define PFACX_COVER_LENGTHS 1u   /* the second array holds lengths, not ends */
+PFAC_status_t PFACX_coverSpansFromDevice(PFAC_handle_t handle, const int *d_start, const int *d_end, size_t numIntervals, size_t size,
+                                         unsigned int flags, int *d_spanStart, int *d_spanLen, size_t capacity,
+                                         size_t *h_numSpans, size_t *h_coveredBytes);
+PFAC_status_t PFACX_coverSpansFromHost  (PFAC_handle_t handle, const int *h_start, const int *h_end, size_t numIntervals, size_t size,
+                                         unsigned int flags, int *h_spanStart, int *h_spanLen, size_t capacity,
+                                         size_t *h_numSpans, size_t *h_coveredBytes);
+
 /* Split: the offsets that cut a buffer into records at the bytes of a delimiter class -- the `d_offsets` that PFACX_matchBatch*,
  * PFACX_matchAllBatchFromDevice, PFACX_rules*, PFACX_countBatch* and PFACX_groups* take, made where the text lies: the lines of a log, the records
  * of a CRLF protocol, the fields of a line.

@@ -628,6 +628,25 @@ typedef struct {
 } PFACX_clsigRun_t;
 PFAC_status_t PFACX_clsigRun(PFAC_handle_t handle, const PFACX_clsigRun_t *run, size_t *h_total);
 
+/* Covered spans of an unsorted interval list (no reference counterpart; include/pfac_ext.h: PFACX_coverSpans*), scan_cover.hip.
+ * PFACX_coverRun: the maximal runs of the bytes of [0, size), 0 < size < 2^31, that one of the intervals [d_start[i], e_i), i < numIntervals,
+ * 0 < numIntervals < 2^31, holds -- e_i = d_end[i], or d_start[i] + d_end[i] in 64-bit arithmetic with PFACX_COVER_LENGTHS in `flags` --, each
+ * clamped to [0, size] where it is read, an interval that is then empty ignored; any order, duplicates, nesting, overlap.  The interval arrays are
+ * only read.  Output: (start, length) of the spans, ascending, into d_spanStart / d_spanLen, nothing at or beyond `capacity` (0: both may be
+ * null); *h_numSpans and *h_coveredBytes are the full values whatever the capacity.  The span arrays must not overlap the interval arrays (the
+ * caller checks).  No input buffer: `size` only bounds the positions.  Scratch: the handle's cover scratch, sized by `size` alone (scan_cover.hip
+ * has the formula).  Synchronous. */
+#define PFACX_COVER_BLOCK_BYTES 32768u   /* positions one block of the extract passes covers (scan_cover.hip: kCoverBlockBits; pfac_amd/api.py) */
+typedef struct {
+    const int *d_start, *d_end;
+    size_t numIntervals;
+    size_t size;
+    unsigned int flags;
+    int *d_spanStart, *d_spanLen;
+    size_t capacity;
+} PFACX_coverRun_t;
+PFAC_status_t PFACX_coverRun(PFAC_handle_t handle, const PFACX_coverRun_t *run, size_t *h_numSpans, size_t *h_coveredBytes);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -645,7 +664,7 @@ PFAC_status_t PFACX_clsigRun(PFAC_handle_t handle, const PFACX_clsigRun_t *run, 
     X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun) X(split_run_ptr, PFACX_splitRun) \
     X(locate_run_ptr, PFACX_locateRun) X(capture_run_ptr, PFACX_captureRun) X(case_run_ptr, PFACX_caseRun) \
     X(sig_run_ptr, PFACX_sigRun) X(approx_run_ptr, PFACX_approxRun) X(gapsig_run_ptr, PFACX_gapsigRun) \
-    X(edit_run_ptr, PFACX_editRun) X(clsig_run_ptr, PFACX_clsigRun)
+    X(edit_run_ptr, PFACX_editRun) X(clsig_run_ptr, PFACX_clsigRun) X(cover_run_ptr, PFACX_coverRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

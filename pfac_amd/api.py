@@ -92,6 +92,9 @@ PFACX_FLOWRULES_BLOCK_PAIRS = 256               # scan_flowrules.hip: kFlowRules
 PFACX_SEGCOUNT_WINDOW = 8192                    # scan_segcount.hip: kSegWindow, the pattern ids whose counters a block keeps in LDS at a time
 PFACX_SEGCOUNT_TOUCHED = 1024                   # scan_segcount.hip: kSegTouched, the touched-list length; a segment that touches more ids of a window sweeps the whole window
 PFACX_SEGCOUNT_BLOCK_PAIRS = 256                # scan_segcount.hip: kSegBlockPairs, the pairs a block takes from a segment in one go
+PFACX_COVER_LENGTHS = 1                         # pfac_ext.h: PFACX_coverSpans* the second interval array holds lengths, not ends
+PFACX_COVER_BLOCK_BYTES = 32768                 # pfac_module.h: PFACX_COVER_BLOCK_BYTES = scan_cover.hip: kCoverBlockBits, the positions one block of the extract passes covers
+PFACX_COVER_MARK_BLOCK = 256                    # scan_cover.hip: kCoverThreads, the intervals one block of pfac_cover_mark takes per trip (scan_passes.h: gridFor, PFACX_GRID_BLOCKS_PER_CU)
 PFACX_COUNT_LDS_DIRECT = 16384                  # scan_count.hip: kCountDirect -- sets with F + 1 <= this count into a counter per id in LDS, larger ones into a tagged cache
 (PFACX_TABLE_DENSE, PFACX_TABLE_HASH_ROWPTR, PFACX_TABLE_HASH_VALPTR, PFACX_TABLE_INITIAL_ROW,
  PFACX_TABLE_FILTER_GRAM3, PFACX_TABLE_FILTER_SHORT, PFACX_TABLE_FILTER_LADDER, PFACX_TABLE_FILTER_FINAL3,
@@ -197,6 +200,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_clsigOpen", "PFACX_clsigOpenText", "PFACX_clsigGetAnchors", "PFACX_clsigClose", "PFACX_clsigMatchFromDevice",
     "PFACX_clsigMatchFromHost", "PFACX_clsigPairsFromDevice", "PFACX_clsigBatchMatchFromDevice", "PFACX_clsigBatchMatchFromHost",
     "PFACX_clsigBatchPairsFromDevice",
+    "PFACX_coverSpansFromDevice", "PFACX_coverSpansFromHost",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -222,6 +226,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_gapsigRun",
     "PFACX_editRun",
     "PFACX_clsigRun",
+    "PFACX_coverRun",
 )
 
 
@@ -320,6 +325,11 @@ def load_library() -> C.CDLL:
         lib.PFACX_matchSpansFromDevice.argtypes = spans
         lib.PFACX_matchSpansFromHost.argtypes = spans
         lib.PFACX_redactSpansFromDevice.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_ubyte, C.c_void_p]
+    if hasattr(lib, "PFACX_coverSpansFromDevice"):
+        SZ = C.POINTER(C.c_size_t)
+        cover = [H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, SZ, SZ]
+        lib.PFACX_coverSpansFromDevice.argtypes = cover
+        lib.PFACX_coverSpansFromHost.argtypes = cover
     if hasattr(lib, "PFACX_countFromDevice"):
         SZ = C.POINTER(C.c_size_t)
         count = [H, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t, SZ]
@@ -837,6 +847,40 @@ class PFAC:
         start = np.full(cap, -7, dtype=np.int32)
         length = np.full(cap, -7, dtype=np.int32)
         _, ns, cb = self.matchSpansFromHost(data.ctypes.data if data.size else start.ctypes.data, data.size, start.ctypes.data, length.ctypes.data, cap)
+        return start[:ns].copy(), length[:ns].copy(), cb
+
+    # -- an unsorted interval list as covered spans (include/pfac_ext.h: PFACX_coverSpans*) ------------
+    def coverSpansFromDevice(self, d_start, d_end, num_intervals: int, size: int, flags: int, d_span_start, d_span_len, capacity: int,
+                             check: bool = True):
+        """``PFACX_coverSpansFromDevice`` -> (status, number of spans, covered bytes); the interval arrays may be None with no interval, the
+        span arrays with capacity 0 (the count query).  ``PFACX_STATUS_OUTPUT_TRUNCATED`` is returned, not raised: both counts are complete."""
+        ns, cb = C.c_size_t(0), C.c_size_t(0)
+        st = self._lib.PFACX_coverSpansFromDevice(self._h, d_start, d_end, num_intervals, size, flags, d_span_start, d_span_len, capacity,
+                                                  C.byref(ns), C.byref(cb))
+        return self._ret(st, "PFACX_coverSpansFromDevice", check and st != STATUS.OUTPUT_TRUNCATED), ns.value, cb.value
+
+    def coverSpansFromHost(self, h_start, h_end, num_intervals: int, size: int, flags: int, h_span_start, h_span_len, capacity: int,
+                           check: bool = True):
+        """``PFACX_coverSpansFromHost`` -> (status, number of spans, covered bytes); runs on the CPU on every platform."""
+        ns, cb = C.c_size_t(0), C.c_size_t(0)
+        st = self._lib.PFACX_coverSpansFromHost(self._h, h_start, h_end, num_intervals, size, flags, h_span_start, h_span_len, capacity,
+                                                C.byref(ns), C.byref(cb))
+        return self._ret(st, "PFACX_coverSpansFromHost", check and st != STATUS.OUTPUT_TRUNCATED), ns.value, cb.value
+
+    def cover_spans_host_array(self, starts, ends, size: int, lengths: bool = False):
+        """coverSpansFromHost over two numpy arrays -> (span_start, span_len, covered bytes), ascending; `lengths`: `ends` holds lengths."""
+        import numpy as np
+        starts = np.ascontiguousarray(starts, dtype=np.int32)
+        ends = np.ascontiguousarray(ends, dtype=np.int32)
+        if starts.shape != ends.shape or starts.ndim != 1:
+            raise ValueError("cover_spans_host_array: starts and ends must be one-dimensional and of one length")
+        flags = PFACX_COVER_LENGTHS if lengths else 0
+        n = int(starts.size)
+        _, ns, _ = self.coverSpansFromHost(starts.ctypes.data if n else None, ends.ctypes.data if n else None, n, size, flags, None, None, 0)
+        start = np.full(max(1, ns), -7, dtype=np.int32)
+        length = np.full(max(1, ns), -7, dtype=np.int32)
+        _, ns, cb = self.coverSpansFromHost(starts.ctypes.data if n else None, ends.ctypes.data if n else None, n, size, flags,
+                                            start.ctypes.data, length.ctypes.data, ns)
         return start[:ns].copy(), length[:ns].copy(), cb
 
     # -- which patterns occurred, and how often (include/pfac_ext.h: PFACX_count*) ------------

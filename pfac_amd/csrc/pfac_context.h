@@ -101,7 +101,8 @@ constexpr HostSlot kHostApprox = {98, 100};      /* an approximate call: the 64-
 constexpr HostSlot kHostGapSig = {102, 104};     /* a gapped-signature call: the 64-bit length of its list (scan_gapsig.hip, by pfac_array_scan) */
 constexpr HostSlot kHostEdit = {106, 108};       /* an edit-distance call: the 64-bit length of its list (scan_edit.hip, by pfac_array_scan) */
 constexpr HostSlot kHostClSig = {110, 112};      /* a class-signature call: the 64-bit length of its list (scan_clsig.hip, by pfac_array_scan) */
-constexpr int kHostWords = 114;
+constexpr HostSlot kHostCover = {114, 116};      /* a cover call: one 64-bit value, the spans | the covered bytes << 32 (scan_cover.hip, by pfac_pairs_finish) */
+constexpr int kHostWords = 118;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -536,12 +537,17 @@ struct DeviceScratch {
      * pair list of PFACX_clsigMatchFromDevice is allPairs, the prefix table allTable: shared.  The signature, part and class tables of a
      * class-signature object are state of that object, not scratch (clsig_api.cpp) */
     DeviceBuffer<char> clsigSet;
+    /* the cover calls (PFACX_coverSpansFromDevice, scan_cover.hip): ONE allocation a call cuts into the bitmap hierarchy over [0, size) -- a bit per
+     * byte, then a bit per word of the level below, up to one word: about size / 8 x 32 / 31 bytes --, the per-block values of its extract passes
+     * and the words of its counts (scan_cover.hip has the formula); sized by `size` alone, not by the intervals; not allocated before the first
+     * cover call with an interval */
+    DeviceBuffer<char> cover;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines); f(linesContext);
-        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet); f(sigSet); f(approxSet); f(gapsigSet); f(editSet); f(clsigSet);
+        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet); f(sigSet); f(approxSet); f(gapsigSet); f(editSet); f(clsigSet); f(cover);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }

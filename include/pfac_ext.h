@@ -1508,6 +1508,44 @@ PFAC_status_t PFACX_coverSpansFromHost  (PFAC_handle_t handle, const int *h_star
                                          unsigned int flags, int *h_spanStart, int *h_spanLen, size_t capacity,
                                          size_t *h_numSpans, size_t *h_coveredBytes);
 
+/* Order: a hit list put in START ORDER on the device -- the step between the lists of PFACX_sig* (id, start), PFACX_approx* (id, start, distance),
+ * PFACX_gapsig* / PFACX_clsig* / PFACX_clsigBatch* (id, start, end) and PFACX_edit* (id, start, end, distance), which are in pair order, chain order,
+ * id / table order -- the order of the owning anchor, not of the start --, and every call that takes positions non-decreasing.  Any caller-made list
+ * works as well; no matcher runs, and no pattern set is needed.
+ *   ORDER.  Entry k is the tuple of the given columns at index k; the call permutes the entries in place.  `start` ends up non-decreasing as SIGNED
+ *   ints.  No range is assumed: negative starts (streams, flows) and values >= the size of any buffer are legal keys, which is why the call takes no
+ *   `size`.  Among equal starts the incoming order is kept: the sort is stable.  With PFACX_ORDER_TIES_BY_ID in `flags`, entries with equal starts
+ *   are put in ascending id order first (signed); entries equal in both start and id keep their incoming order.
+ *   COLUMNS.  d_ids, d_end and d_aux are optional; each one that is given is permuted with `start`.  A bare position list is legal.
+ *   PERMUTATION.  d_perm (numHits ints), where given, receives the incoming index of the entry now at k: callers with more columns gather them
+ *   themselves.  Without d_perm the permutation is never materialised for the caller.
+ *   ALREADY ORDERED.  *h_wasOrdered (where given) is 1 iff the list was already in the requested order; then no column is written and d_perm is the
+ *   identity.  Every list that the library's reduce, all, words, disjoint and groups calls return takes this exit.
+ *   The result is a legal argument of PFACX_locatePairsFromDevice, of PFACX_capturePairsFromDevice (with PFACX_CAPTURE_AT_POS) and of
+ *   PFACX_coverSpansFromDevice.  Over a PFACX_clsigBatch* list, segFirst stays valid as it is: segments are ascending disjoint ranges and every
+ *   start lies inside its segment, so ordering the whole list orders each segment's slice and moves no entry across a slice.
+ * PFAC_STATUS_INVALID_PARAMETER: a null handle, a null d_start with numHits > 0, numHits >= 2^31, a flag bit other than PFACX_ORDER_TIES_BY_ID, that
+ * flag without d_ids, any two of the given arrays overlapping, d_perm included (the rule of the pairs forms).  numHits == 0: success, nothing
+ * touched, *h_wasOrdered = 1.  The device form on a host-only handle: PFAC_STATUS_LIB_NOT_EXIST.  Both forms are synchronous, take the handle's lock
+ * and need no pattern set.  Scratch that cannot be allocated: PFAC_STATUS_ALLOC_FAILED, the caller's arrays untouched -- nothing of the caller's is
+ * written before the last sorting pass has finished.  The host form is a stable sort of an index array with the same comparator, on the CPU on
+ * every platform, host-only handles included, memory proportional to numHits.
+ * MEMORY of the device form: grow-only handle scratch (deviceScratchBytes of PFACX_getInfo, freed by PFACX_trim), not allocated before the first
+ * call: 40 bytes of probe words for a list that is found ordered; for one that needs a pass, with B = min((numHits + 2047) / 2048, 8 x compute
+ * units) blocks, 40 + 16 numHits (two buffers of (key, index) pairs) + 4 numHits (one column temp) + 1024 B + 1024 B + 4 (the digit counts of the
+ * blocks and their prefix) bytes, each of the six parts rounded up to 256.
+ * COST: one probe launch; then three launches per 8-bit digit in which two keys differ (starts below 2^24 and ids below 2^16: three
+ * digits, five with the ties flag), one gather and one copy per column.
+ * OUT OF SCOPE: ordering by end or by id alone, dropping duplicates, 64-bit positions, merging two ordered lists, and exploiting the bounded
+ * displacement of the library's own lists (an entry lies at most a pattern length from its place; open). */
+#define PFACX_ORDER_TIES_BY_ID 1u   /* among equal starts: ascending id, then incoming order */
+PFAC_status_t PFACX_orderHitsFromDevice(PFAC_handle_t handle, int *d_start, int *d_ids /* may be NULL */, int *d_end /* may be NULL */,
+                                        int *d_aux /* may be NULL */, size_t numHits, unsigned int flags, int *d_perm /* may be NULL */,
+                                        int *h_wasOrdered /* may be NULL */);
+PFAC_status_t PFACX_orderHitsFromHost  (PFAC_handle_t handle, int *h_start, int *h_ids /* may be NULL */, int *h_end /* may be NULL */,
+                                        int *h_aux /* may be NULL */, size_t numHits, unsigned int flags, int *h_perm /* may be NULL */,
+                                        int *h_wasOrdered /* may be NULL */);
+
 /* Split: the offsets that cut a buffer into records at the bytes of a delimiter class -- the `d_offsets` that PFACX_matchBatch*,
  * PFACX_matchAllBatchFromDevice, PFACX_rules*, PFACX_countBatch* and PFACX_groups* take, made where the text lies: the lines of a log, the records
  * of a CRLF protocol, the fields of a line.

@@ -647,6 +647,24 @@ typedef struct {
 } PFACX_coverRun_t;
 PFAC_status_t PFACX_coverRun(PFAC_handle_t handle, const PFACX_coverRun_t *run, size_t *h_numSpans, size_t *h_coveredBytes);
 
+/* Hit lists in start order (no reference counterpart; include/pfac_ext.h: PFACX_orderHits*), scan_order_hits.hip.
+ * PFACX_orderRun: the entries (d_start[k], d_ids[k], d_end[k], d_aux[k]), k < numHits, 0 < numHits < 2^31, of the columns that are given, permuted
+ * in place so that d_start is non-decreasing as signed ints, stably -- with PFACX_ORDER_TIES_BY_ID (d_ids given) entries of one start ascending by
+ * signed id first.  d_perm (null: none) receives the incoming index of the entry now at k.  *h_wasOrdered = 1: the list was in that order already,
+ * no column was written and d_perm is the identity.  No two of the arrays overlap (the caller checks).  Column values are keys and nothing else;
+ * no index that reaches a store comes from the caller.  Scratch: the handle's order scratch (scan_order_hits.hip has the formula), not allocated
+ * by a call that finds the list ordered.  No memory: the allocation status, no array written.  Synchronous. */
+#define PFACX_ORDER_TILE 2048u      /* entries of one tile of the count and scatter launches (scan_order_hits.hip: kOrderTile; pfac_amd/api.py) */
+#define PFACX_ORDER_THREADS 256u    /* threads of a block of those launches: four waves, each with a contiguous quarter of the tile in rounds of 64 */
+typedef struct {
+    int *d_start;
+    int *d_ids, *d_end, *d_aux;     /* each may be null */
+    size_t numHits;
+    unsigned int flags;
+    int *d_perm;                    /* may be null */
+} PFACX_orderRun_t;
+PFAC_status_t PFACX_orderRun(PFAC_handle_t handle, const PFACX_orderRun_t *run, int *h_wasOrdered);
+
 /* Every entry point libpfac.so binds out of the module, as X(member of PFAC_context, exported symbol): the one list behind the pointer
  * members (pfac_context.h: each has the type of its prototype above) and behind loadModule (pfac_api.cpp), which binds all of them or
  * none.  The first four keep the reference's member names and typedefs (PFAC_P.h:136-146). */
@@ -664,7 +682,8 @@ PFAC_status_t PFACX_coverRun(PFAC_handle_t handle, const PFACX_coverRun_t *run, 
     X(groups_run_ptr, PFACX_groupsRun) X(flowrules_run_ptr, PFACX_flowRulesRun) X(split_run_ptr, PFACX_splitRun) \
     X(locate_run_ptr, PFACX_locateRun) X(capture_run_ptr, PFACX_captureRun) X(case_run_ptr, PFACX_caseRun) \
     X(sig_run_ptr, PFACX_sigRun) X(approx_run_ptr, PFACX_approxRun) X(gapsig_run_ptr, PFACX_gapsigRun) \
-    X(edit_run_ptr, PFACX_editRun) X(clsig_run_ptr, PFACX_clsigRun) X(cover_run_ptr, PFACX_coverRun)
+    X(edit_run_ptr, PFACX_editRun) X(clsig_run_ptr, PFACX_clsigRun) X(cover_run_ptr, PFACX_coverRun) \
+    X(order_run_ptr, PFACX_orderRun)
 
 /* Measurement only (no reference counterpart): the traffic shape of the match path with nothing else in it -- every
  * wave reads 1 KiB of d_in and writes 4 KiB of zeros to d_out, non-temporal.  Returns the average milliseconds of

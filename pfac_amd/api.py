@@ -95,6 +95,9 @@ PFACX_SEGCOUNT_BLOCK_PAIRS = 256                # scan_segcount.hip: kSegBlockPa
 PFACX_COVER_LENGTHS = 1                         # pfac_ext.h: PFACX_coverSpans* the second interval array holds lengths, not ends
 PFACX_COVER_BLOCK_BYTES = 32768                 # pfac_module.h: PFACX_COVER_BLOCK_BYTES = scan_cover.hip: kCoverBlockBits, the positions one block of the extract passes covers
 PFACX_COVER_MARK_BLOCK = 256                    # scan_cover.hip: kCoverThreads, the intervals one block of pfac_cover_mark takes per trip (scan_passes.h: gridFor, PFACX_GRID_BLOCKS_PER_CU)
+PFACX_ORDER_TIES_BY_ID = 1                      # pfac_ext.h: PFACX_orderHits* among equal starts ascending id, then incoming order
+PFACX_ORDER_TILE = 2048                         # pfac_module.h: PFACX_ORDER_TILE = scan_order_hits.hip: kOrderTile, the entries of one tile of the count and scatter launches (a block owns contiguous tiles; PFACX_GRID_BLOCKS_PER_CU blocks per compute unit at most)
+PFACX_ORDER_THREADS = 256                       # pfac_module.h: PFACX_ORDER_THREADS = scan_order_hits.hip: kOrderThreads: four waves, each with a contiguous quarter of the tile in rounds of 64
 PFACX_COUNT_LDS_DIRECT = 16384                  # scan_count.hip: kCountDirect -- sets with F + 1 <= this count into a counter per id in LDS, larger ones into a tagged cache
 (PFACX_TABLE_DENSE, PFACX_TABLE_HASH_ROWPTR, PFACX_TABLE_HASH_VALPTR, PFACX_TABLE_INITIAL_ROW,
  PFACX_TABLE_FILTER_GRAM3, PFACX_TABLE_FILTER_SHORT, PFACX_TABLE_FILTER_LADDER, PFACX_TABLE_FILTER_FINAL3,
@@ -201,6 +204,7 @@ EXPORTED_SYMBOLS = (
     "PFACX_clsigMatchFromHost", "PFACX_clsigPairsFromDevice", "PFACX_clsigBatchMatchFromDevice", "PFACX_clsigBatchMatchFromHost",
     "PFACX_clsigBatchPairsFromDevice",
     "PFACX_coverSpansFromDevice", "PFACX_coverSpansFromHost",
+    "PFACX_orderHitsFromDevice", "PFACX_orderHitsFromHost",
 )
 MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFAC_kernel_timeDriven_warpper", "PFAC_kernel_spaceDriven_warpper",
@@ -227,6 +231,7 @@ MODULE_SYMBOLS = (  # include/pfac_module.h, exported by libpfac_gfx950.so
     "PFACX_editRun",
     "PFACX_clsigRun",
     "PFACX_coverRun",
+    "PFACX_orderRun",
 )
 
 
@@ -330,6 +335,10 @@ def load_library() -> C.CDLL:
         cover = [H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, SZ, SZ]
         lib.PFACX_coverSpansFromDevice.argtypes = cover
         lib.PFACX_coverSpansFromHost.argtypes = cover
+    if hasattr(lib, "PFACX_orderHitsFromDevice"):
+        order = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.POINTER(C.c_int)]
+        lib.PFACX_orderHitsFromDevice.argtypes = order
+        lib.PFACX_orderHitsFromHost.argtypes = order
     if hasattr(lib, "PFACX_countFromDevice"):
         SZ = C.POINTER(C.c_size_t)
         count = [H, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t, SZ]
@@ -882,6 +891,35 @@ class PFAC:
         _, ns, cb = self.coverSpansFromHost(starts.ctypes.data if n else None, ends.ctypes.data if n else None, n, size, flags,
                                             start.ctypes.data, length.ctypes.data, ns)
         return start[:ns].copy(), length[:ns].copy(), cb
+
+    # -- a hit list in start order (include/pfac_ext.h: PFACX_orderHits*) ------------
+    def orderHitsFromDevice(self, d_start, d_ids, d_end, d_aux, num_hits: int, flags: int, d_perm=None, check: bool = True):
+        """``PFACX_orderHitsFromDevice`` -> (status, was_ordered); every array but `d_start` may be None, `d_start` too with no hit.  The given
+        columns are permuted in place; `d_perm` receives the incoming index of the entry now at k."""
+        was = C.c_int(-1)
+        st = self._lib.PFACX_orderHitsFromDevice(self._h, d_start, d_ids, d_end, d_aux, num_hits, flags, d_perm, C.byref(was))
+        return self._ret(st, "PFACX_orderHitsFromDevice", check), was.value
+
+    def orderHitsFromHost(self, h_start, h_ids, h_end, h_aux, num_hits: int, flags: int, h_perm=None, check: bool = True):
+        """``PFACX_orderHitsFromHost`` -> (status, was_ordered); runs on the CPU on every platform."""
+        was = C.c_int(-1)
+        st = self._lib.PFACX_orderHitsFromHost(self._h, h_start, h_ids, h_end, h_aux, num_hits, flags, h_perm, C.byref(was))
+        return self._ret(st, "PFACX_orderHitsFromHost", check), was.value
+
+    def order_hits_host_array(self, starts, ids=None, ends=None, aux=None, ties_by_id: bool = False):
+        """orderHitsFromHost over copies of numpy arrays -> (the given columns in start order ..., perm, was_ordered): `starts` first, then
+        whichever of `ids`, `ends`, `aux` is given, in that order."""
+        import numpy as np
+        cols = [np.array(c, dtype=np.int32, ndmin=1, copy=True) for c in (starts, ids, ends, aux) if c is not None]
+        if starts is None or any(c.ndim != 1 or c.shape != cols[0].shape for c in cols):
+            raise ValueError("order_hits_host_array: starts is required, and every column must be one-dimensional and of one length")
+        n = int(cols[0].size)
+        perm = np.full(n, -7, dtype=np.int32)
+        ptrs = iter([c.ctypes.data if n else None for c in cols])
+        args = [next(ptrs) if c is not None else None for c in (starts, ids, ends, aux)]
+        _, was = self.orderHitsFromHost(args[0], args[1], args[2], args[3], n, PFACX_ORDER_TIES_BY_ID if ties_by_id else 0,
+                                        perm.ctypes.data if n else None)
+        return (*cols, perm, was)
 
     # -- which patterns occurred, and how often (include/pfac_ext.h: PFACX_count*) ------------
     def countFromDevice(self, d_input: int, size: int, flags: int, d_counts: int, num_counts: int, check: bool = True):

@@ -102,7 +102,8 @@ constexpr HostSlot kHostGapSig = {102, 104};     /* a gapped-signature call: the
 constexpr HostSlot kHostEdit = {106, 108};       /* an edit-distance call: the 64-bit length of its list (scan_edit.hip, by pfac_array_scan) */
 constexpr HostSlot kHostClSig = {110, 112};      /* a class-signature call: the 64-bit length of its list (scan_clsig.hip, by pfac_array_scan) */
 constexpr HostSlot kHostCover = {114, 116};      /* a cover call: one 64-bit value, the spans | the covered bytes << 32 (scan_cover.hip, by pfac_pairs_finish) */
-constexpr int kHostWords = 118;
+constexpr HostSlot kHostOrder = {118, 122};      /* an order call: two 64-bit values, the key bits in which two entries differ, then the descents (scan_order_hits.hip: pfac_order_finish) */
+constexpr int kHostWords = 124;
 constexpr int kStatsPublishedWord = 48 * 32;     /* 64-bit: the kStatsCount statistics of the last finished filter launch, then its dense chunks */
 constexpr int kStatsWord = 64 * 32;              /* 64-bit launch statistics of the scan kernel live here, behind the part counters (PFACX_getScanStats) */
 constexpr int kStatsCount = 6;                  /* walker rounds, lane steps, walks started, level-1 hits, positions scanned, ladder candidates */
@@ -542,12 +543,16 @@ struct DeviceScratch {
      * and the words of its counts (scan_cover.hip has the formula); sized by `size` alone, not by the intervals; not allocated before the first
      * cover call with an interval */
     DeviceBuffer<char> cover;
+    /* the order calls (PFACX_orderHitsFromDevice, scan_order_hits.hip): ONE allocation a call cuts into the probe words, two buffers of (key, index)
+     * pairs (16 bytes per hit), one column temp (4 bytes per hit) and the digit-major count table with its scan (2 x 4 x 256 x blocks bytes, blocks
+     * <= eight per compute unit: scan_order_hits.hip has the formula); a call that finds its list ordered takes the probe words alone */
+    DeviceBuffer<char> order;
 
     template <class F> void forEach(F f)
     {
         for (int b = 0; b < 2; b++) { f(stageIn[b]); f(stageOut[b]); f(stagePos[b]); }
         f(reduce); f(denseList); f(patternLen); f(batchOffsets); f(batch); f(allTable); f(allPairs); f(allSegFirst); f(all); f(flows); f(flowPieces); f(fold); f(lines); f(linesContext);
-        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet); f(sigSet); f(approxSet); f(gapsigSet); f(editSet); f(clsigSet); f(cover);
+        f(spans); f(count); f(disjoint); f(rules); f(words); f(segCount); f(groups); f(flowRules); f(split); f(locate); f(capture); f(caseSet); f(sigSet); f(approxSet); f(gapsigSet); f(editSet); f(clsigSet); f(cover); f(order);
     }
     void release() { forEach([](auto &b) { b.release(); }); }
     size_t bytes() { size_t n = 0; forEach([&n](auto &b) { n += b.bytes(); }); return n; }

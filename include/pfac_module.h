@@ -425,6 +425,22 @@ typedef struct {
 } PFACX_captureRun_t;
 PFAC_status_t PFACX_captureRun(PFAC_handle_t handle, const PFACX_captureRun_t *run, size_t *h_slowPairs);
 
+/* The six verify runs below (PFACX_caseRun ... PFACX_clsigRun) start with the same fields: the first member of each run struct, filled by one host
+ * function (pfac_amd/csrc/verify_calls.h: fillRunFrame) and checked and turned into the expansion frame by one function of the module
+ * (pfac_amd/csrc/scan_verify.h: verifyRunOk, verifyFrame).  The text of each run says what they mean there. */
+typedef struct {
+    const char *d_input;
+    size_t size;
+    const int *d_pairIds, *d_pairPos;
+    size_t count;
+    const void *d_table;
+    size_t numIds;
+    const unsigned int *d_blob;
+    size_t blobWords;
+    int *d_ids, *d_pos;
+    size_t capacity;
+} PFACX_verifyRun_t;
+
 /* Per-pattern case sensitivity over a caseless set (no reference counterpart; include/pfac_ext.h: PFACX_case*), scan_case.hip.
  * PFACX_caseRun: the cased occurrences of an ordered list of LONGEST pairs of a caseless set.  d_input[0, size), 0 < size < 2^31, are the CALLER's
  * bytes at any alignment (never the folded copy: the sensitive patterns are compared with them, and no load leaves [0, size)); d_pairIds /
@@ -438,21 +454,12 @@ PFAC_status_t PFACX_captureRun(PFAC_handle_t handle, const PFACX_captureRun_t *r
  * variant that holds.  Output: (line id, position) into d_ids / d_pos, nothing at or beyond `capacity` (0: both may be null); *h_total = the full
  * length of the list.  The output arrays must not overlap the pair arrays (the caller checks).  Synchronous. */
 typedef struct {
-    const char *d_input;
-    size_t size;
-    const int *d_pairIds, *d_pairPos;
-    size_t count;
-    const void *d_table;
+    PFACX_verifyRun_t v;            /* the input, the pairs, the chain table, the blob, the caller's arrays */
     const int *d_patternLen;
-    size_t numIds;
     const unsigned int *d_varOff;
     const void *d_vars;
     size_t numVars;
-    const unsigned int *d_blob;
-    size_t blobWords;
     unsigned int all;
-    int *d_ids, *d_pos;
-    size_t capacity;
 } PFACX_caseRun_t;
 PFAC_status_t PFACX_caseRun(PFAC_handle_t handle, const PFACX_caseRun_t *run, size_t *h_total);
 
@@ -469,19 +476,10 @@ PFAC_status_t PFACX_caseRun(PFAC_handle_t handle, const PFACX_caseRun_t *run, si
  * Output: (signature id, s) into d_ids / d_pos in pair order, chain order, table order; nothing at or beyond `capacity` (0: both may be null);
  * *h_total = the full length of the list.  The output arrays must not overlap the pair arrays (the caller checks).  Synchronous. */
 typedef struct {
-    const char *d_input;
-    size_t size;
-    const int *d_pairIds, *d_pairPos;
-    size_t count;
-    const void *d_table;
-    size_t numIds;
+    PFACX_verifyRun_t v;            /* the input, the pairs, the chain table, the blob, the caller's arrays */
     const unsigned int *d_sigOff;
     const void *d_sigs;
     size_t numSigs;
-    const unsigned int *d_blob;
-    size_t blobWords;
-    int *d_ids, *d_pos;
-    size_t capacity;
 } PFACX_sigRun_t;
 PFAC_status_t PFACX_sigRun(PFAC_handle_t handle, const PFACX_sigRun_t *run, size_t *h_total);
 
@@ -499,20 +497,12 @@ PFAC_status_t PFACX_sigRun(PFAC_handle_t handle, const PFACX_sigRun_t *run, size
  * `capacity` (0: all three may be null); *h_total = the full length of the list.  The output arrays must not overlap the pair arrays (the caller
  * checks).  Synchronous. */
 typedef struct {
-    const char *d_input;
-    size_t size;
-    const int *d_pairIds, *d_pairPos;
-    size_t count;
-    const void *d_table;
-    size_t numIds;
+    PFACX_verifyRun_t v;            /* the input, the pairs, the chain table, the blob, the caller's arrays */
     const unsigned int *d_entryOff;
     const void *d_entries;
     size_t numEntries;
-    const unsigned int *d_blob;
-    size_t blobWords;
     size_t maxPieceLen;
-    int *d_ids, *d_pos, *d_mis;
-    size_t capacity;
+    int *d_mis;
 } PFACX_approxRun_t;
 PFAC_status_t PFACX_approxRun(PFAC_handle_t handle, const PFACX_approxRun_t *run, size_t *h_total);
 
@@ -532,21 +522,13 @@ PFAC_status_t PFACX_approxRun(PFAC_handle_t handle, const PFACX_approxRun_t *run
  * or beyond `capacity` (0: all three may be null); *h_total = the full length of the list.  The output arrays must not overlap the pair arrays
  * (the caller checks).  Synchronous. */
 typedef struct {
-    const char *d_input;
-    size_t size;
-    const int *d_pairIds, *d_pairPos;
-    size_t count;
-    const void *d_table;
-    size_t numIds;
+    PFACX_verifyRun_t v;            /* the input, the pairs, the chain table, the blob, the caller's arrays */
     const unsigned int *d_sigOff;
     const void *d_sigs;
     size_t numSigs;
     const void *d_parts;
     size_t numParts;
-    const unsigned int *d_blob;
-    size_t blobWords;
-    int *d_ids, *d_pos, *d_end;
-    size_t capacity;
+    int *d_end;
 } PFACX_gapsigRun_t;
 PFAC_status_t PFACX_gapsigRun(PFAC_handle_t handle, const PFACX_gapsigRun_t *run, size_t *h_total);
 
@@ -563,22 +545,14 @@ PFAC_status_t PFACX_gapsigRun(PFAC_handle_t handle, const PFACX_gapsigRun_t *run
  * table order, ends ascending; nothing at or beyond `capacity` (0: all four may be null); *h_total = the full length of the list.  The output
  * arrays must not overlap the pair arrays (the caller checks).  Synchronous. */
 typedef struct {
-    const char *d_input;
-    size_t size;
-    const int *d_pairIds, *d_pairPos;
-    size_t count;
-    const void *d_table;
-    size_t numIds;
+    PFACX_verifyRun_t v;            /* the input, the pairs, the chain table, the blob, the caller's arrays */
     const unsigned int *d_entryOff;
     const void *d_entries;
     size_t numEntries;
-    const unsigned int *d_blob;
-    size_t blobWords;
     size_t maxPieceLen;
     unsigned int maxBudget;
     int bestEnds;
-    int *d_ids, *d_pos, *d_end, *d_dist;
-    size_t capacity;
+    int *d_end, *d_dist;
 } PFACX_editRun_t;
 PFAC_status_t PFACX_editRun(PFAC_handle_t handle, const PFACX_editRun_t *run, size_t *h_total);
 
@@ -604,24 +578,16 @@ PFAC_status_t PFACX_editRun(PFAC_handle_t handle, const PFACX_editRun_t *run, si
  * same.  d_segFirst (may be null): numSegments + 1 entries, the list index of each segment's first entry and the length of the list, written
  * whatever the capacity; right for a list that ascends by position, unspecified (but inside the array) for any other; all zero for no pairs. */
 typedef struct {
-    const char *d_input;
-    size_t size;
-    const int *d_pairIds, *d_pairPos;
-    size_t count;
-    const void *d_table;
-    size_t numIds;
+    PFACX_verifyRun_t v;            /* the input, the pairs, the chain table, the blob, the caller's arrays */
     const unsigned int *d_sigOff;
     const void *d_sigs;
     size_t numSigs;
     const void *d_parts;
     size_t numParts;
-    const unsigned int *d_blob;
-    size_t blobWords;
     const unsigned int *d_classes;
     size_t numClasses;
     unsigned int flags;
-    int *d_ids, *d_pos, *d_end;
-    size_t capacity;
+    int *d_end;
     const size_t *d_offsets;
     size_t numSegments;
     size_t *d_segFirst;

@@ -15,19 +15,21 @@
  * compacted-output path with its ordered pairs in handle scratch (PFACX_allReduce) and the passes of scan_approx.hip (PFACX_approxRun) behind
  * it; the pairs form runs those passes over a list of the caller's.  The host form takes the longest pairs from hostLongestPairs into a
  * temporary of its own and walks the chains here (approxOnHost).
+ * The open tail (the pieces loaded and the handle checked to hold them), the order of the checks, the scan, the pair temporaries and the
+ * generation re-check of the three forms are the frame of verify_calls.h; this file's own is the run's arguments (approxRunLocked) and the host loop.
  */
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "pfac_host.h"
 #include "piece_cut.h"
+#include "verify_calls.h"
 
 struct PFACX_approx_s : pfac_internal::HandleObject {
     size_t numIds = 0;                        /* F of the piece set it loaded */
@@ -46,6 +48,7 @@ struct PFACX_approx_s : pfac_internal::HandleObject {
     pfac::DeviceBuffer<pfac::ApproxEntry> d_entries;
 
     template <class Self, class F> static void forEachDeviceBuffer(Self &self, F f) { f(self.d_entryOff); f(self.d_entries); f(self.d_blob); }
+    PFAC_status_t uploadTables() { return pfac_internal::uploadAll(d_entryOff, entryOff, d_entries, entries, d_blob, blob); }
     ~PFACX_approx_s() override { forEachDeviceBuffer(*this, [](auto &b) { b.release(); }); }
     size_t deviceBytes() const override { size_t n = 0; forEachDeviceBuffer(*this, [&n](const auto &b) { n += b.bytes(); }); return n; }
 };
@@ -54,54 +57,18 @@ using namespace pfac_internal;
 
 namespace {
 
-/* what the three match calls check first (the generation and the pattern set: under the lock) */
-PFAC_status_t checkApproxArgs(PFACX_approx_t ap, const void *input, size_t size, const size_t *h_num_matched)
-{
-    if (!ap || !ap->handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!input || !h_num_matched || size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
-    return PFAC_STATUS_SUCCESS;
-}
-
-/* the first device call of an approximate object: its tables (the caller holds the handle's lock) */
-PFAC_status_t ensureDeviceTables(PFACX_approx_s *ap)
-{
-    if (ap->d_entryOff) return PFAC_STATUS_SUCCESS;
-    const PFAC_status_t st = uploadAll(ap->d_entryOff, ap->entryOff, ap->d_entries, ap->entries, ap->d_blob, ap->blob);
-    if (st != PFAC_STATUS_SUCCESS) PFACX_approx_s::forEachDeviceBuffer(*ap, [](auto &b) { b.release(); });
-    return st;
-}
-
 /* the passes over `count` ordered longest pairs, behind the argument checks; the caller holds c->lock */
-PFAC_status_t approxRunLocked(PFACX_approx_s *ap, const char *d_input, size_t size, const int *d_pairIds, const int *d_pairPos, size_t count,
-                              int *d_ids, int *d_pos, int *d_mis, size_t capacity, size_t *h_num_matched)
+PFAC_status_t approxRunLocked(PFACX_approx_s *ap, const VerifyCall &call, int *d_mis, const int *d_pairIds, const int *d_pairPos, size_t count)
 {
-    PFAC_context *c = ap->handle;
-    PFAC_status_t st = c->fa.maxChain > 1 ? ensureAllTable(c) : PFAC_STATUS_SUCCESS;
-    if (st == PFAC_STATUS_SUCCESS) st = ensureDeviceTables(ap);
-    if (st != PFAC_STATUS_SUCCESS) return st;
     PFACX_approxRun_t run{};
-    run.d_input = d_input;
-    run.size = size;
-    run.d_pairIds = d_pairIds;
-    run.d_pairPos = d_pairPos;
-    run.count = count;
-    run.d_table = c->fa.maxChain > 1 ? c->scratch.allTable.get() : nullptr;
-    run.numIds = ap->numIds;
+    const PFAC_status_t st = fillRunFrame(ap, call, d_pairIds, d_pairPos, count, &run.v);
+    if (st != PFAC_STATUS_SUCCESS) return st;
     run.d_entryOff = ap->d_entryOff.get();
     run.d_entries = ap->d_entries.get();
     run.numEntries = ap->entries.size();
-    run.d_blob = ap->d_blob.get();
-    run.blobWords = ap->blob.size();
     run.maxPieceLen = ap->maxPiece;
-    run.d_ids = d_ids;
-    run.d_pos = d_pos;
     run.d_mis = d_mis;
-    run.capacity = capacity;
-    size_t total = 0;
-    st = c->approx_run_ptr(c, &run, &total);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    *h_num_matched = total;
-    return truncatedIf(total, capacity);
+    return finishRun(ap->handle, ap->handle->approx_run_ptr, run, call);
 }
 
 /* The host loop: the entries that hold along the chains of `count` ordered longest pairs into ids / pos / mis (slots >= capacity are not
@@ -163,12 +130,7 @@ PFAC_status_t PFACX_approxOpen(PFAC_handle_t handle, const unsigned char *h_byte
         if (badPattern) *badPattern = bad;
         if (st != PFAC_STATUS_SUCCESS) return st;                             /* nothing of the handle has changed */
     } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
-    /* the pieces through the reader of every pattern set: the set is replaced, the handle case-sensitive */
-    PFAC_status_t st = PFACX_readPatternFromMemory(handle, plan.text.data(), plan.text.size());
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    return adoptNew(handle, approx, [&](PFACX_approx_s &obj) -> PFAC_status_t {
-        /* another thread may have replaced the set since: the tables hold only over the pieces, id by id */
-        if (!holdsPieces(handle, plan)) return PFAC_STATUS_INVALID_PARAMETER;
+    return adoptOverStrings(handle, plan.pieces, approx, [&](PFACX_approx_s &obj) -> PFAC_status_t {   /* (verify_calls.h: the tables hold only over the pieces) */
         buildPieceTables<pfac::ApproxEntry>(plan, &obj);
         return PFAC_STATUS_SUCCESS;
     });
@@ -189,74 +151,27 @@ PFAC_status_t PFACX_approxGetPieces(PFACX_approx_t approx, size_t *h_pieceOff, i
 PFAC_status_t PFACX_approxMatchFromDevice(PFACX_approx_t approx, char *d_input, size_t size, int *d_ids, int *d_pos, int *d_mis, size_t capacity,
                                           size_t *h_num_matched)
 {
-    PFAC_status_t st = checkApproxArgs(approx, d_input, size, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (!d_ids || !d_pos) return PFAC_STATUS_INVALID_PARAMETER;
-    PFAC_context *c = approx->handle;
-    if (size && capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    std::lock_guard<std::mutex> guard(c->lock);
-    st = checkSetGeneration(c, approx->generation);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    DeviceScan scan;
-    st = beginDeviceScan(c, d_input, size, &scan);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    /* the caller's arrays take the scan's unordered list, the ordered pairs go to the handle's pair scratch: the passes never filter in place */
-    int count = 0;
-    st = c->all_reduce_ptr(c, reinterpret_cast<int *>(scan.d_scan), (int)size, d_ids, d_pos, &count, scan.hashed);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
-    const int *pairIds = c->scratch.allPairs.get();
-    const int *pairPos = pairIds + c->scratch.allPairs.count() / 2;        /* one allocation: the ids, then as many positions */
-    if (count == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    return approxRunLocked(approx, d_input, size, pairIds, pairPos, (size_t)count, d_ids, d_pos, d_mis, capacity, h_num_matched);
+    const VerifyCall call{d_input, size, d_ids, d_pos, capacity, h_num_matched};
+    return verifyFromDevice(approx, call, [&](const int *ids, const int *pos, size_t count) { return approxRunLocked(approx, call, d_mis, ids, pos, count); });
 }
 
 PFAC_status_t PFACX_approxMatchFromHost(PFACX_approx_t approx, char *h_input, size_t size, int *h_ids, int *h_pos, int *h_mis, size_t capacity,
                                         size_t *h_num_matched)
 {
-    PFAC_status_t st = checkApproxArgs(approx, h_input, size, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (capacity && (!h_ids || !h_pos)) return PFAC_STATUS_INVALID_PARAMETER;
-    PFAC_context *c = approx->handle;
-    {
-        std::lock_guard<std::mutex> guard(c->lock);
-        st = checkSetGeneration(c, approx->generation);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-    }
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    const HostPairs pairs(size, size);
-    if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
-    const PinnedPairs scan(c, h_input, size, pairs.ids, pairs.pos);
-    if (scan.status != PFAC_STATUS_SUCCESS) return scan.status;
-    if (scan.generation != approx->generation) return PFAC_STATUS_INVALID_PARAMETER;    /* another thread has replaced the set meanwhile: as after the call */
-    const size_t total = approxOnHost(c->fa, *approx, reinterpret_cast<const unsigned char *>(h_input), size, pairs.ids, pairs.pos,
-                                      (size_t)(scan.count > 0 ? scan.count : 0), h_ids, h_pos, h_mis, capacity);
-    *h_num_matched = total;
-    return truncatedIf(total, capacity);
+    const VerifyCall call{h_input, size, h_ids, h_pos, capacity, h_num_matched};
+    return verifyFromHost(approx, call, [&](const int *ids, const int *pos, size_t count) {
+        return approxOnHost(approx->handle->fa, *approx, reinterpret_cast<const unsigned char *>(h_input), size, ids, pos, count, h_ids, h_pos, h_mis,
+                            capacity);
+    });
 }
 
 PFAC_status_t PFACX_approxPairsFromDevice(PFACX_approx_t approx, const char *d_input, size_t size, const int *d_pairIds, const int *d_pairPos,
                                           size_t numPairs, int *d_ids, int *d_pos, int *d_mis, size_t capacity, size_t *h_num_matched)
 {
-    PFAC_status_t st = checkApproxArgs(approx, d_input, size, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (numPairs > kMaxInt || capacity > SIZE_MAX / sizeof(int) || (numPairs && (!d_pairIds || !d_pairPos)) || (capacity && (!d_ids || !d_pos)))
-        return PFAC_STATUS_INVALID_PARAMETER;
-    if (capacity && numPairs) {
-        const size_t in = numPairs * sizeof(int), out = capacity * sizeof(int);
-        for (const int *array : {d_ids, d_pos, d_mis})
-            if (array && (overlap(array, out, d_pairIds, in) || overlap(array, out, d_pairPos, in))) return PFAC_STATUS_INVALID_PARAMETER;
-    }
-    PFAC_context *c = approx->handle;
-    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    std::lock_guard<std::mutex> guard(c->lock);
-    st = checkSetGeneration(c, approx->generation);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0 || numPairs == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    return approxRunLocked(approx, d_input, size, d_pairIds, d_pairPos, numPairs, d_ids, d_pos, d_mis, capacity, h_num_matched);
+    const VerifyCall call{d_input, size, d_ids, d_pos, capacity, h_num_matched};
+    return verifyPairsFromDevice(approx, call, d_pairIds, d_pairPos, numPairs, {d_ids, d_pos, d_mis}, [&](const int *ids, const int *pos, size_t count) {
+        return approxRunLocked(approx, call, d_mis, ids, pos, count);
+    });
 }
 
 } /* extern "C" */

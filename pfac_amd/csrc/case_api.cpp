@@ -12,6 +12,8 @@
  * handle scratch (PFACX_allReduce) and the passes of scan_case.hip (PFACX_caseRun) behind it, which read the CALLER's bytes; the pairs form runs
  * those passes over a list of the caller's.  The host form takes the longest pairs from hostLongestPairs into a temporary of its own and walks
  * the chains here (caseOnHost).
+ * The order of the checks, the scan, the pair temporaries and the generation re-check of the three forms are the frame of verify_calls.h; this
+ * file's own is the variant tables, the check of the folded lines in PFACX_caseOpen, the run's arguments (caseRunLocked) and the host loop.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -24,6 +26,7 @@
 #include <vector>
 
 #include "pfac_host.h"
+#include "verify_calls.h"
 
 struct PFACX_case_s : pfac_internal::HandleObject {
     size_t numIds = 0;                        /* F of the pattern set it was opened on */
@@ -38,6 +41,7 @@ struct PFACX_case_s : pfac_internal::HandleObject {
     pfac::DeviceBuffer<pfac::Int2> d_vars;
 
     template <class Self, class F> static void forEachDeviceBuffer(Self &self, F f) { f(self.d_varOff); f(self.d_vars); f(self.d_blob); }
+    PFAC_status_t uploadTables() { return pfac_internal::uploadAll(d_varOff, varOff, d_vars, vars, d_blob, blob); }
     ~PFACX_case_s() override { forEachDeviceBuffer(*this, [](auto &b) { b.release(); }); }
     size_t deviceBytes() const override { size_t n = 0; forEachDeviceBuffer(*this, [&n](const auto &b) { n += b.bytes(); }); return n; }
 };
@@ -104,55 +108,26 @@ void buildVariants(const pfac::Automaton &fa, const pfac::Automaton &lines, cons
     cs->maxPerPosition = (int)std::min<long long>(most, 0x7fffffff);
 }
 
-/* what the three match calls check first (the generation and the pattern set: under the lock) */
-PFAC_status_t checkCaseArgs(PFACX_case_t cs, const void *input, size_t size, unsigned int flags, const size_t *h_num_matched)
+/* the arguments of one call: the flags are this family's own test */
+VerifyCall caseCall(const char *input, size_t size, unsigned int flags, int *ids, int *pos, size_t capacity, size_t *h_num_matched)
 {
-    if (!cs || !cs->handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!input || !h_num_matched || (flags & ~PFACX_CASE_ALL) || size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
-    return PFAC_STATUS_SUCCESS;
-}
-
-/* the first device call of a case object: its tables (the caller holds the handle's lock) */
-PFAC_status_t ensureDeviceTables(PFACX_case_s *cs)
-{
-    if (cs->d_varOff) return PFAC_STATUS_SUCCESS;
-    const PFAC_status_t st = uploadAll(cs->d_varOff, cs->varOff, cs->d_vars, cs->vars, cs->d_blob, cs->blob);
-    if (st != PFAC_STATUS_SUCCESS) PFACX_case_s::forEachDeviceBuffer(*cs, [](auto &b) { b.release(); });
-    return st;
+    return VerifyCall{input, size, ids, pos, capacity, h_num_matched, (flags & ~PFACX_CASE_ALL) == 0u};
 }
 
 /* the passes over `count` ordered longest pairs, behind the argument checks; the caller holds c->lock */
-PFAC_status_t caseRunLocked(PFACX_case_s *cs, const char *d_input, size_t size, unsigned int flags, const int *d_pairIds, const int *d_pairPos,
-                            size_t count, int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched)
+PFAC_status_t caseRunLocked(PFACX_case_s *cs, const VerifyCall &call, unsigned int flags, const int *d_pairIds, const int *d_pairPos, size_t count)
 {
     PFAC_context *c = cs->handle;
-    PFAC_status_t st = ensurePatternLen(c);
-    if (st == PFAC_STATUS_SUCCESS && c->fa.maxChain > 1) st = ensureAllTable(c);
-    if (st == PFAC_STATUS_SUCCESS) st = ensureDeviceTables(cs);
-    if (st != PFAC_STATUS_SUCCESS) return st;
     PFACX_caseRun_t run{};
-    run.d_input = d_input;
-    run.size = size;
-    run.d_pairIds = d_pairIds;
-    run.d_pairPos = d_pairPos;
-    run.count = count;
-    run.d_table = c->fa.maxChain > 1 ? c->scratch.allTable.get() : nullptr;
+    PFAC_status_t st = ensurePatternLen(c);
+    if (st == PFAC_STATUS_SUCCESS) st = fillRunFrame(cs, call, d_pairIds, d_pairPos, count, &run.v);
+    if (st != PFAC_STATUS_SUCCESS) return st;
     run.d_patternLen = c->scratch.patternLen.get();
-    run.numIds = cs->numIds;
     run.d_varOff = cs->d_varOff.get();
     run.d_vars = cs->d_vars.get();
     run.numVars = cs->vars.size();
-    run.d_blob = cs->d_blob.get();
-    run.blobWords = cs->blob.size();
     run.all = (flags & PFACX_CASE_ALL) ? 1u : 0u;
-    run.d_ids = d_ids;
-    run.d_pos = d_pos;
-    run.capacity = capacity;
-    size_t total = 0;
-    st = c->case_run_ptr(c, &run, &total);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    *h_num_matched = total;
-    return truncatedIf(total, capacity);
+    return finishRun(c, c->case_run_ptr, run, call);
 }
 
 /* The host loop: the variants that hold along the chains of `count` ordered longest pairs into ids / pos (slots >= capacity are not written);
@@ -223,74 +198,26 @@ PFAC_status_t PFACX_caseClose(PFACX_case_t cs) { return closeObject(cs); }
 PFAC_status_t PFACX_caseMatchFromDevice(PFACX_case_t cs, char *d_input, size_t size, unsigned int flags, int *d_ids, int *d_pos, size_t capacity,
                                         size_t *h_num_matched)
 {
-    PFAC_status_t st = checkCaseArgs(cs, d_input, size, flags, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (!d_ids || !d_pos) return PFAC_STATUS_INVALID_PARAMETER;
-    PFAC_context *c = cs->handle;
-    if (size && capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    std::lock_guard<std::mutex> guard(c->lock);
-    st = checkSetGeneration(c, cs->generation);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    DeviceScan scan;                                                       /* the scan reads the folded copy, the passes behind it the caller's bytes */
-    st = beginDeviceScan(c, d_input, size, &scan);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    /* the caller's arrays take the scan's unordered list, the ordered pairs go to the handle's pair scratch: the passes never filter in place */
-    int count = 0;
-    st = c->all_reduce_ptr(c, reinterpret_cast<int *>(scan.d_scan), (int)size, d_ids, d_pos, &count, scan.hashed);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
-    const int *pairIds = c->scratch.allPairs.get();
-    const int *pairPos = pairIds + c->scratch.allPairs.count() / 2;        /* one allocation: the ids, then as many positions */
-    if (count == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    return caseRunLocked(cs, d_input, size, flags, pairIds, pairPos, (size_t)count, d_ids, d_pos, capacity, h_num_matched);
+    const VerifyCall call = caseCall(d_input, size, flags, d_ids, d_pos, capacity, h_num_matched);
+    return verifyFromDevice(cs, call, [&](const int *ids, const int *pos, size_t count) { return caseRunLocked(cs, call, flags, ids, pos, count); });
 }
 
 PFAC_status_t PFACX_caseMatchFromHost(PFACX_case_t cs, char *h_input, size_t size, unsigned int flags, int *h_ids, int *h_pos, size_t capacity,
                                       size_t *h_num_matched)
 {
-    PFAC_status_t st = checkCaseArgs(cs, h_input, size, flags, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (capacity && (!h_ids || !h_pos)) return PFAC_STATUS_INVALID_PARAMETER;
-    PFAC_context *c = cs->handle;
-    {
-        std::lock_guard<std::mutex> guard(c->lock);
-        st = checkSetGeneration(c, cs->generation);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-    }
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    const HostPairs pairs(size, size);
-    if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
-    const PinnedPairs scan(c, h_input, size, pairs.ids, pairs.pos);
-    if (scan.status != PFAC_STATUS_SUCCESS) return scan.status;
-    if (scan.generation != cs->generation) return PFAC_STATUS_INVALID_PARAMETER;     /* another thread has replaced the set meanwhile: as after the call */
-    const size_t total = caseOnHost(c->fa, *cs, reinterpret_cast<const unsigned char *>(h_input), size, (flags & PFACX_CASE_ALL) != 0, pairs.ids,
-                                    pairs.pos, (size_t)(scan.count > 0 ? scan.count : 0), h_ids, h_pos, capacity);
-    *h_num_matched = total;
-    return truncatedIf(total, capacity);
+    const VerifyCall call = caseCall(h_input, size, flags, h_ids, h_pos, capacity, h_num_matched);
+    return verifyFromHost(cs, call, [&](const int *ids, const int *pos, size_t count) {
+        return caseOnHost(cs->handle->fa, *cs, reinterpret_cast<const unsigned char *>(h_input), size, (flags & PFACX_CASE_ALL) != 0, ids, pos, count,
+                          h_ids, h_pos, capacity);
+    });
 }
 
 PFAC_status_t PFACX_casePairsFromDevice(PFACX_case_t cs, const char *d_input, size_t size, unsigned int flags, const int *d_pairIds,
                                         const int *d_pairPos, size_t numPairs, int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched)
 {
-    PFAC_status_t st = checkCaseArgs(cs, d_input, size, flags, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (numPairs > kMaxInt || capacity > SIZE_MAX / sizeof(int) || (numPairs && (!d_pairIds || !d_pairPos)) || (capacity && (!d_ids || !d_pos)))
-        return PFAC_STATUS_INVALID_PARAMETER;
-    if (capacity && numPairs) {
-        const size_t in = numPairs * sizeof(int), out = capacity * sizeof(int);
-        if (overlap(d_ids, out, d_pairIds, in) || overlap(d_ids, out, d_pairPos, in) || overlap(d_pos, out, d_pairIds, in) || overlap(d_pos, out, d_pairPos, in))
-            return PFAC_STATUS_INVALID_PARAMETER;
-    }
-    PFAC_context *c = cs->handle;
-    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    std::lock_guard<std::mutex> guard(c->lock);
-    st = checkSetGeneration(c, cs->generation);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0 || numPairs == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    return caseRunLocked(cs, d_input, size, flags, d_pairIds, d_pairPos, numPairs, d_ids, d_pos, capacity, h_num_matched);
+    const VerifyCall call = caseCall(d_input, size, flags, d_ids, d_pos, capacity, h_num_matched);
+    return verifyPairsFromDevice(cs, call, d_pairIds, d_pairPos, numPairs, {d_ids, d_pos},
+                                 [&](const int *ids, const int *pos, size_t count) { return caseRunLocked(cs, call, flags, ids, pos, count); });
 }
 
 } /* extern "C" */

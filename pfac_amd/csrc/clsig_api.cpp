@@ -18,6 +18,9 @@
  * The three batch forms (PFACX_clsigBatch*) are the same three functions with offsets: the scan stays the plain one over the whole buffer, the
  * device passes get the offsets and clamp them (scan_clsig.hip), the host loop finds each pair's segment in the validated offsets and searches
  * that segment's bytes as if they were the whole input.
+ * The open tail (the anchors loaded and the handle checked to hold them), the order of the checks, the scan, the pair temporaries and the
+ * generation re-check of the three forms, plain and batch, are the frame of verify_calls.h (ClSigForms hands it the segments' check and the
+ * all-zero segFirst of an empty list); this file's own is the plan, the parser, the tables, the run's arguments (clsigRunLocked) and the host search.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -31,6 +34,7 @@
 #include <vector>
 
 #include "pfac_host.h"
+#include "verify_calls.h"
 
 struct PFACX_clsig_s : pfac_internal::HandleObject {
     size_t numIds = 0;                        /* F of the anchor set it loaded */
@@ -52,6 +56,10 @@ struct PFACX_clsig_s : pfac_internal::HandleObject {
     template <class Self, class F> static void forEachDeviceBuffer(Self &self, F f)
     {
         f(self.d_sigOff); f(self.d_sigs); f(self.d_parts); f(self.d_blob); f(self.d_classes);
+    }
+    PFAC_status_t uploadTables()
+    {
+        return pfac_internal::uploadAll(d_sigOff, sigOff, d_sigs, sigs, d_parts, parts, d_blob, blob, d_classes, classes);
     }
     ~PFACX_clsig_s() override { forEachDeviceBuffer(*this, [](auto &b) { b.release(); }); }
     size_t deviceBytes() const override { size_t n = 0; forEachDeviceBuffer(*this, [&n](const auto &b) { n += b.bytes(); }); return n; }
@@ -81,8 +89,7 @@ struct ClSigPlan {
     std::vector<size_t> sigPart;                      /* [S + 1] into parts */
     std::vector<int> notBefore, notAfter;             /* by signature id - 1 */
     std::vector<int> anchorId, anchorPart, anchorOff, anchorLen;  /* by signature id */
-    std::vector<std::string> anchors;                 /* by handle id - 1: the distinct anchors in order of first appearance */
-    std::string text;                                 /* one line per distinct anchor */
+    StringSet anchors;                                /* by handle id - 1: the distinct anchors, and the anchor set as the reader's text */
 };
 
 /* The anchor of one signature over its `count` parts: the longest run of bytes other than '\n' (the pattern reader splits lines there) inside ONE
@@ -159,7 +166,6 @@ PFAC_status_t planSignatures(const std::vector<int> &single, const unsigned int 
     }
     *badSig = 0;
     if (plan->parts.size() > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;                            /* the tables index the parts with ints */
-    std::map<std::string, int> seen;
     for (size_t i = 1; i <= S; i++) {
         const size_t first = plan->sigPart[i - 1], count = plan->sigPart[i] - first;
         size_t apart = 0, aoff = 0, alen = 0;
@@ -167,14 +173,7 @@ PFAC_status_t planSignatures(const std::vector<int> &single, const unsigned int 
             *badSig = (int)i;
             return PFAC_STATUS_INVALID_PARAMETER;
         }
-        const std::string anchor = plan->parts[first + apart].bytes.substr(aoff, alen);
-        const auto placed = seen.emplace(anchor, (int)plan->anchors.size() + 1);
-        if (placed.second) {
-            plan->anchors.push_back(anchor);
-            plan->text += anchor;
-            plan->text += '\n';
-        }
-        plan->anchorId[i] = placed.first->second;
+        plan->anchorId[i] = plan->anchors.idOf(plan->parts[first + apart].bytes.substr(aoff, alen));
         plan->anchorPart[i] = (int)apart;
         plan->anchorOff[i] = (int)aoff;
         plan->anchorLen[i] = (int)alen;
@@ -433,64 +432,33 @@ bool parseText(const char *text, size_t size, ParsedText &out, int *badLine)
 
 /* ------------------------------------------------------------------ the calls */
 
-/* what the three match calls check first (the generation and the pattern set: under the lock) */
-PFAC_status_t checkClSigArgs(PFACX_clsig_t sg, const void *input, size_t size, const size_t *h_num_matched)
-{
-    if (!sg || !sg->handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!input || !h_num_matched || size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
-    return PFAC_STATUS_SUCCESS;
-}
+/* the segments of a batch call (a plain call: all null); the device forms hand them to the passes, the host form to its loop */
+struct Segments {
+    const size_t *offsets = nullptr;
+    size_t count = 0;
+    size_t *segFirst = nullptr;
+};
 
-/* the first device call of a class-signature object: its tables (the caller holds the handle's lock) */
-PFAC_status_t ensureDeviceTables(PFACX_clsig_s *sg)
+/* the passes over `count` ordered longest pairs, behind the argument checks; the caller holds c->lock.  seg: a batch (include/pfac_module.h) */
+PFAC_status_t clsigRunLocked(PFACX_clsig_s *sg, const VerifyCall &call, int *d_end, const Segments &seg, const int *d_pairIds, const int *d_pairPos,
+                             size_t count)
 {
-    if (sg->d_sigOff) return PFAC_STATUS_SUCCESS;
-    const PFAC_status_t st =
-        uploadAll(sg->d_sigOff, sg->sigOff, sg->d_sigs, sg->sigs, sg->d_parts, sg->parts, sg->d_blob, sg->blob, sg->d_classes, sg->classes);
-    if (st != PFAC_STATUS_SUCCESS) PFACX_clsig_s::forEachDeviceBuffer(*sg, [](auto &b) { b.release(); });
-    return st;
-}
-
-/* the passes over `count` ordered longest pairs, behind the argument checks; the caller holds c->lock.  d_offsets: a batch of numSegments
- * segments (include/pfac_module.h), d_segFirst where the caller wants it; null: the plain call */
-PFAC_status_t clsigRunLocked(PFACX_clsig_s *sg, const char *d_input, size_t size, const int *d_pairIds, const int *d_pairPos, size_t count,
-                             int *d_ids, int *d_pos, int *d_end, size_t capacity, size_t *h_num_matched, const size_t *d_offsets = nullptr,
-                             size_t numSegments = 0, size_t *d_segFirst = nullptr)
-{
-    PFAC_context *c = sg->handle;
-    PFAC_status_t st = c->fa.maxChain > 1 ? ensureAllTable(c) : PFAC_STATUS_SUCCESS;
-    if (st == PFAC_STATUS_SUCCESS) st = ensureDeviceTables(sg);
-    if (st != PFAC_STATUS_SUCCESS) return st;
     PFACX_clsigRun_t run{};
-    run.d_input = d_input;
-    run.size = size;
-    run.d_pairIds = d_pairIds;
-    run.d_pairPos = d_pairPos;
-    run.count = count;
-    run.d_table = c->fa.maxChain > 1 ? c->scratch.allTable.get() : nullptr;
-    run.numIds = sg->numIds;
+    const PFAC_status_t st = fillRunFrame(sg, call, d_pairIds, d_pairPos, count, &run.v);
+    if (st != PFAC_STATUS_SUCCESS) return st;
     run.d_sigOff = sg->d_sigOff.get();
     run.d_sigs = sg->d_sigs.get();
     run.numSigs = sg->sigs.size();
     run.d_parts = sg->d_parts.get();
     run.numParts = sg->parts.size();
-    run.d_blob = sg->d_blob.get();
-    run.blobWords = sg->blob.size();
     run.d_classes = sg->d_classes.get();
     run.numClasses = sg->classes.size() / 8;
     run.flags = sg->flags;
-    run.d_ids = d_ids;
-    run.d_pos = d_pos;
     run.d_end = d_end;
-    run.capacity = capacity;
-    run.d_offsets = d_offsets;
-    run.numSegments = numSegments;
-    run.d_segFirst = d_segFirst;
-    size_t total = 0;
-    st = c->clsig_run_ptr(c, &run, &total);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    *h_num_matched = total;
-    return truncatedIf(total, capacity);
+    run.d_offsets = seg.offsets;
+    run.numSegments = seg.count;
+    run.d_segFirst = seg.segFirst;
+    return finishRun(sg->handle, sg->handle->clsig_run_ptr, run, call);
 }
 
 /* The host form's own search.  A mask holds where a BOUNDARY between two parts can lie: bit t = t bytes behind (forwards) or in front of
@@ -672,19 +640,7 @@ PFAC_status_t PFACX_clsigOpen(PFAC_handle_t handle, const unsigned int *h_classe
         if (badSig) *badSig = bad;
         if (st != PFAC_STATUS_SUCCESS) return st;                             /* nothing of the handle has changed */
     } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
-    /* the anchors through the reader of every pattern set: the set is replaced, the handle case-sensitive */
-    PFAC_status_t st = PFACX_readPatternFromMemory(handle, plan.text.data(), plan.text.size());
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    return adoptNew(handle, sig, [&](PFACX_clsig_s &obj) -> PFAC_status_t {
-        /* another thread may have replaced the set since: the tables hold only over the anchors, id by id */
-        const pfac::Automaton &fa = handle->fa;
-        if (handle->caseInsensitive || (size_t)fa.numPatterns != plan.anchors.size()) return PFAC_STATUS_INVALID_PARAMETER;
-        for (size_t q = 1; q <= plan.anchors.size(); q++) {
-            const std::string &anchor = plan.anchors[q - 1];
-            if ((size_t)fa.patternLen[q] != anchor.size() || fa.chainLen[q] < 1 ||
-                std::memcmp(fa.file.data() + fa.patternOff[q], anchor.data(), anchor.size()) != 0)
-                return PFAC_STATUS_INVALID_PARAMETER;
-        }
+    return adoptOverStrings(handle, plan.anchors, sig, [&](PFACX_clsig_s &obj) -> PFAC_status_t {     /* (verify_calls.h: the tables hold only over the anchors) */
         if (!buildTables(plan, &obj)) return PFAC_STATUS_INVALID_PARAMETER;
         obj.classes = std::move(classes);
         obj.flags = flags;
@@ -731,141 +687,92 @@ PFAC_status_t PFACX_clsigGetAnchors(PFACX_clsig_t sig, int *h_anchorId, int *h_a
     return PFAC_STATUS_SUCCESS;
 }
 
-/* what the three batch forms check of their segments, behind checkClSigArgs: the offsets, their number (0 only with size == 0) */
-static PFAC_status_t checkBatchArgs(const size_t *offsets, size_t size, size_t numSegments)
-{
-    if (!offsets || numSegments >= kMaxInt || (size && numSegments == 0)) return PFAC_STATUS_INVALID_PARAMETER;
-    return PFAC_STATUS_SUCCESS;
-}
+/* The three forms, plain (batch == false: no offsets, no segFirst) and batch, over the frame of verify_calls.h.  The device form scans the WHOLE
+ * buffer for the anchors, plain and ordered, also for a batch: every anchor that fits a segment at p is a prefix of the longest one at p, and the
+ * search rejects per signature what leaves the segment.  What a batch adds: the check of its segments in front of the lock (the
+ * offsets, their number -- 0 only with size == 0 --, and on the host their values), and segFirst all zero where there is no pair */
+namespace {
 
-/* The three forms, plain (batch == false: no offsets, no segFirst) and batch.  The device form scans the WHOLE buffer for the anchors, plain and
- * ordered, also for a batch: every anchor that fits a segment at p is a prefix of the longest one at p, and the search rejects per signature what
- * leaves the segment */
-static PFAC_status_t matchFromDevice(PFACX_clsig_t sig, char *d_input, size_t size, bool batch, const size_t *d_offsets, size_t numSegments, int *d_ids,
-                                     int *d_pos, int *d_end, size_t capacity, size_t *d_segFirst, size_t *h_num_matched)
-{
-    PFAC_status_t st = checkClSigArgs(sig, d_input, size, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (!d_ids || !d_pos) return PFAC_STATUS_INVALID_PARAMETER;
-    if (batch && (st = checkBatchArgs(d_offsets, size, numSegments)) != PFAC_STATUS_SUCCESS) return st;
-    PFAC_context *c = sig->handle;
-    if (size && capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    std::lock_guard<std::mutex> guard(c->lock);
-    st = checkSetGeneration(c, sig->generation);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    DeviceScan scan;
-    st = beginDeviceScan(c, d_input, size, &scan);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    /* the caller's arrays take the scan's unordered list, the ordered pairs go to the handle's pair scratch: the passes never filter in place */
-    int count = 0;
-    st = c->all_reduce_ptr(c, reinterpret_cast<int *>(scan.d_scan), (int)size, d_ids, d_pos, &count, scan.hashed);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
-    const int *pairIds = c->scratch.allPairs.get();
-    const int *pairPos = pairIds + c->scratch.allPairs.count() / 2;        /* one allocation: the ids, then as many positions */
-    if (count == 0) {
-        *h_num_matched = 0;
-        return d_segFirst ? zeroSegmentArrays(d_segFirst, nullptr, numSegments) : PFAC_STATUS_SUCCESS;
-    }
-    return clsigRunLocked(sig, d_input, size, pairIds, pairPos, (size_t)count, d_ids, d_pos, d_end, capacity, h_num_matched, d_offsets, numSegments,
-                          d_segFirst);
-}
+struct ClSigForms {
+    PFACX_clsig_t sig;
+    VerifyCall call;
+    int *end;
+    bool batch;
+    Segments seg;
 
-static PFAC_status_t matchFromHost(PFACX_clsig_t sig, char *h_input, size_t size, bool batch, const size_t *h_offsets, size_t numSegments, int *h_ids,
-                                   int *h_pos, int *h_end, size_t capacity, size_t *h_segFirst, size_t *h_num_matched)
-{
-    PFAC_status_t st = checkClSigArgs(sig, h_input, size, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (capacity && (!h_ids || !h_pos)) return PFAC_STATUS_INVALID_PARAMETER;
-    if (batch && (st = checkBatchArgs(h_offsets, size, numSegments)) != PFAC_STATUS_SUCCESS) return st;
-    if (batch && size && !batchOffsetsValid(h_offsets, numSegments, size)) return PFAC_STATUS_INVALID_PARAMETER;
-    PFAC_context *c = sig->handle;
+    PFAC_status_t checkSegments(bool onHost) const
     {
-        std::lock_guard<std::mutex> guard(c->lock);
-        st = checkSetGeneration(c, sig->generation);
-        if (st != PFAC_STATUS_SUCCESS) return st;
+        if (!batch) return PFAC_STATUS_SUCCESS;
+        if (!seg.offsets || seg.count >= kMaxInt || (call.size && seg.count == 0)) return PFAC_STATUS_INVALID_PARAMETER;
+        if (onHost && call.size && !batchOffsetsValid(seg.offsets, seg.count, call.size)) return PFAC_STATUS_INVALID_PARAMETER;
+        return PFAC_STATUS_SUCCESS;
     }
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    /* the longest pairs of the whole buffer on every platform (the GPU platform: the staged host path), the segments in the search alone */
-    const HostPairs pairs(size, size);
-    if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
-    const PinnedPairs scan(c, h_input, size, pairs.ids, pairs.pos);
-    if (scan.status != PFAC_STATUS_SUCCESS) return scan.status;
-    if (scan.generation != sig->generation) return PFAC_STATUS_INVALID_PARAMETER;    /* another thread has replaced the set meanwhile: as after the call */
-    const size_t total = clsigOnHost(c->fa, *sig, reinterpret_cast<const unsigned char *>(h_input), size, pairs.ids, pairs.pos,
-                                     (size_t)(scan.count > 0 ? scan.count : 0), h_ids, h_pos, h_end, capacity, batch ? h_offsets : nullptr, numSegments,
-                                     h_segFirst);
-    *h_num_matched = total;
-    return truncatedIf(total, capacity);
-}
+    auto run() const
+    {
+        return [this](const int *ids, const int *pos, size_t count) { return clsigRunLocked(sig, call, end, seg, ids, pos, count); };
+    }
+    auto noPairs() const
+    {
+        return [this]() { return seg.segFirst ? zeroSegmentArrays(seg.segFirst, nullptr, seg.count) : PFAC_STATUS_SUCCESS; };
+    }
 
-static PFAC_status_t pairsFromDevice(PFACX_clsig_t sig, const char *d_input, size_t size, bool batch, const size_t *d_offsets, size_t numSegments,
-                                     const int *d_pairIds, const int *d_pairPos, size_t numPairs, int *d_ids, int *d_pos, int *d_end, size_t capacity,
-                                     size_t *d_segFirst, size_t *h_num_matched)
-{
-    PFAC_status_t st = checkClSigArgs(sig, d_input, size, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (numPairs > kMaxInt || capacity > SIZE_MAX / sizeof(int) || (numPairs && (!d_pairIds || !d_pairPos)) || (capacity && (!d_ids || !d_pos)))
-        return PFAC_STATUS_INVALID_PARAMETER;
-    if (batch && (st = checkBatchArgs(d_offsets, size, numSegments)) != PFAC_STATUS_SUCCESS) return st;
-    if (capacity && numPairs) {
-        const size_t in = numPairs * sizeof(int), out = capacity * sizeof(int);
-        for (const int *array : {d_ids, d_pos, d_end})
-            if (array && (overlap(array, out, d_pairIds, in) || overlap(array, out, d_pairPos, in))) return PFAC_STATUS_INVALID_PARAMETER;
+    PFAC_status_t fromDevice() const { return verifyFromDevice(sig, call, run(), [this]() { return checkSegments(false); }, noPairs()); }
+    PFAC_status_t fromHost() const
+    {
+        /* the longest pairs of the whole buffer on every platform (the GPU platform: the staged host path), the segments in the search alone */
+        return verifyFromHost(
+            sig, call,
+            [this](const int *ids, const int *pos, size_t count) {
+                return clsigOnHost(sig->handle->fa, *sig, reinterpret_cast<const unsigned char *>(call.input), call.size, ids, pos, count, call.ids, call.pos,
+                                   end, call.capacity, batch ? seg.offsets : nullptr, seg.count, seg.segFirst);
+            },
+            [this]() { return checkSegments(true); });
     }
-    PFAC_context *c = sig->handle;
-    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    std::lock_guard<std::mutex> guard(c->lock);
-    st = checkSetGeneration(c, sig->generation);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    if (numPairs == 0) {
-        *h_num_matched = 0;
-        return d_segFirst ? zeroSegmentArrays(d_segFirst, nullptr, numSegments) : PFAC_STATUS_SUCCESS;
+    PFAC_status_t pairsFromDevice(const int *d_pairIds, const int *d_pairPos, size_t numPairs) const
+    {
+        return verifyPairsFromDevice(sig, call, d_pairIds, d_pairPos, numPairs, {call.ids, call.pos, end}, run(), [this]() { return checkSegments(false); },
+                                     noPairs());
     }
-    return clsigRunLocked(sig, d_input, size, d_pairIds, d_pairPos, numPairs, d_ids, d_pos, d_end, capacity, h_num_matched, d_offsets, numSegments,
-                          d_segFirst);
-}
+};
+
+} // namespace
 
 PFAC_status_t PFACX_clsigMatchFromDevice(PFACX_clsig_t sig, char *d_input, size_t size, int *d_ids, int *d_pos, int *d_end, size_t capacity,
                                          size_t *h_num_matched)
 {
-    return matchFromDevice(sig, d_input, size, false, nullptr, 0, d_ids, d_pos, d_end, capacity, nullptr, h_num_matched);
+    return ClSigForms{sig, {d_input, size, d_ids, d_pos, capacity, h_num_matched}, d_end, false, {}}.fromDevice();
 }
 
 PFAC_status_t PFACX_clsigMatchFromHost(PFACX_clsig_t sig, char *h_input, size_t size, int *h_ids, int *h_pos, int *h_end, size_t capacity,
                                        size_t *h_num_matched)
 {
-    return matchFromHost(sig, h_input, size, false, nullptr, 0, h_ids, h_pos, h_end, capacity, nullptr, h_num_matched);
+    return ClSigForms{sig, {h_input, size, h_ids, h_pos, capacity, h_num_matched}, h_end, false, {}}.fromHost();
 }
 
 PFAC_status_t PFACX_clsigPairsFromDevice(PFACX_clsig_t sig, const char *d_input, size_t size, const int *d_pairIds, const int *d_pairPos,
                                          size_t numPairs, int *d_ids, int *d_pos, int *d_end, size_t capacity, size_t *h_num_matched)
 {
-    return pairsFromDevice(sig, d_input, size, false, nullptr, 0, d_pairIds, d_pairPos, numPairs, d_ids, d_pos, d_end, capacity, nullptr, h_num_matched);
+    return ClSigForms{sig, {d_input, size, d_ids, d_pos, capacity, h_num_matched}, d_end, false, {}}.pairsFromDevice(d_pairIds, d_pairPos, numPairs);
 }
 
 PFAC_status_t PFACX_clsigBatchMatchFromDevice(PFACX_clsig_t sig, char *d_input, size_t size, const size_t *d_offsets, size_t numSegments, int *d_ids,
                                               int *d_pos, int *d_end, size_t capacity, size_t *d_segFirst, size_t *h_num_matched)
 {
-    return matchFromDevice(sig, d_input, size, true, d_offsets, numSegments, d_ids, d_pos, d_end, capacity, d_segFirst, h_num_matched);
+    return ClSigForms{sig, {d_input, size, d_ids, d_pos, capacity, h_num_matched}, d_end, true, {d_offsets, numSegments, d_segFirst}}.fromDevice();
 }
 
 PFAC_status_t PFACX_clsigBatchMatchFromHost(PFACX_clsig_t sig, char *h_input, size_t size, const size_t *h_offsets, size_t numSegments, int *h_ids,
                                             int *h_pos, int *h_end, size_t capacity, size_t *h_segFirst, size_t *h_num_matched)
 {
-    return matchFromHost(sig, h_input, size, true, h_offsets, numSegments, h_ids, h_pos, h_end, capacity, h_segFirst, h_num_matched);
+    return ClSigForms{sig, {h_input, size, h_ids, h_pos, capacity, h_num_matched}, h_end, true, {h_offsets, numSegments, h_segFirst}}.fromHost();
 }
 
 PFAC_status_t PFACX_clsigBatchPairsFromDevice(PFACX_clsig_t sig, const char *d_input, size_t size, const size_t *d_offsets, size_t numSegments,
                                               const int *d_pairIds, const int *d_pairPos, size_t numPairs, int *d_ids, int *d_pos, int *d_end,
                                               size_t capacity, size_t *d_segFirst, size_t *h_num_matched)
 {
-    return pairsFromDevice(sig, d_input, size, true, d_offsets, numSegments, d_pairIds, d_pairPos, numPairs, d_ids, d_pos, d_end, capacity, d_segFirst,
-                           h_num_matched);
+    return ClSigForms{sig, {d_input, size, d_ids, d_pos, capacity, h_num_matched}, d_end, true, {d_offsets, numSegments, d_segFirst}}.pairsFromDevice(
+        d_pairIds, d_pairPos, numPairs);
 }
 
 } /* extern "C" */

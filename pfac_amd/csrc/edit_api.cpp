@@ -13,6 +13,8 @@
  * compacted-output path with its ordered pairs in handle scratch (PFACX_allReduce) and the passes of scan_edit.hip (PFACX_editRun) behind it;
  * the pairs form runs those passes over a list of the caller's.  The host form takes the longest pairs from hostLongestPairs into a temporary
  * of its own and verifies with byte loops here (editOnHost): the same band, the same ownership rule, no code shared with the kernel.
+ * The open tail (the pieces loaded and the handle checked to hold them), the order of the checks, the scan, the pair temporaries and the
+ * generation re-check of the three forms are the frame of verify_calls.h; this file's own is the run's arguments (editRunLocked) and the host loop.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -24,6 +26,7 @@
 
 #include "pfac_host.h"
 #include "piece_cut.h"
+#include "verify_calls.h"
 
 struct PFACX_edit_s : pfac_internal::HandleObject {
     size_t numIds = 0;                        /* F of the piece set it loaded */
@@ -42,6 +45,7 @@ struct PFACX_edit_s : pfac_internal::HandleObject {
     pfac::DeviceBuffer<pfac::EditEntry> d_entries;
 
     template <class Self, class F> static void forEachDeviceBuffer(Self &self, F f) { f(self.d_entryOff); f(self.d_entries); f(self.d_blob); }
+    PFAC_status_t uploadTables() { return pfac_internal::uploadAll(d_entryOff, entryOff, d_entries, entries, d_blob, blob); }
     ~PFACX_edit_s() override { forEachDeviceBuffer(*this, [](auto &b) { b.release(); }); }
     size_t deviceBytes() const override { size_t n = 0; forEachDeviceBuffer(*this, [&n](const auto &b) { n += b.bytes(); }); return n; }
 };
@@ -50,57 +54,21 @@ using namespace pfac_internal;
 
 namespace {
 
-/* what the three match calls check first (the generation and the pattern set: under the lock) */
-PFAC_status_t checkEditArgs(PFACX_edit_t ed, const void *input, size_t size, const size_t *h_num_matched)
-{
-    if (!ed || !ed->handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!input || !h_num_matched || size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
-    return PFAC_STATUS_SUCCESS;
-}
-
-/* the first device call of an edit object: its tables (the caller holds the handle's lock) */
-PFAC_status_t ensureDeviceTables(PFACX_edit_s *ed)
-{
-    if (ed->d_entryOff) return PFAC_STATUS_SUCCESS;
-    const PFAC_status_t st = uploadAll(ed->d_entryOff, ed->entryOff, ed->d_entries, ed->entries, ed->d_blob, ed->blob);
-    if (st != PFAC_STATUS_SUCCESS) PFACX_edit_s::forEachDeviceBuffer(*ed, [](auto &b) { b.release(); });
-    return st;
-}
-
 /* the passes over `count` ordered longest pairs, behind the argument checks; the caller holds c->lock */
-PFAC_status_t editRunLocked(PFACX_edit_s *ed, const char *d_input, size_t size, const int *d_pairIds, const int *d_pairPos, size_t count, int *d_ids,
-                            int *d_pos, int *d_end, int *d_dist, size_t capacity, size_t *h_num_matched)
+PFAC_status_t editRunLocked(PFACX_edit_s *ed, const VerifyCall &call, int *d_end, int *d_dist, const int *d_pairIds, const int *d_pairPos, size_t count)
 {
-    PFAC_context *c = ed->handle;
-    PFAC_status_t st = c->fa.maxChain > 1 ? ensureAllTable(c) : PFAC_STATUS_SUCCESS;
-    if (st == PFAC_STATUS_SUCCESS) st = ensureDeviceTables(ed);
-    if (st != PFAC_STATUS_SUCCESS) return st;
     PFACX_editRun_t run{};
-    run.d_input = d_input;
-    run.size = size;
-    run.d_pairIds = d_pairIds;
-    run.d_pairPos = d_pairPos;
-    run.count = count;
-    run.d_table = c->fa.maxChain > 1 ? c->scratch.allTable.get() : nullptr;
-    run.numIds = ed->numIds;
+    const PFAC_status_t st = fillRunFrame(ed, call, d_pairIds, d_pairPos, count, &run.v);
+    if (st != PFAC_STATUS_SUCCESS) return st;
     run.d_entryOff = ed->d_entryOff.get();
     run.d_entries = ed->d_entries.get();
     run.numEntries = ed->entries.size();
-    run.d_blob = ed->d_blob.get();
-    run.blobWords = ed->blob.size();
     run.maxPieceLen = ed->maxPiece;
     run.maxBudget = ed->maxBudget;
     run.bestEnds = ed->bestEnds ? 1 : 0;
-    run.d_ids = d_ids;
-    run.d_pos = d_pos;
     run.d_end = d_end;
     run.d_dist = d_dist;
-    run.capacity = capacity;
-    size_t total = 0;
-    st = c->edit_run_ptr(c, &run, &total);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    *h_num_matched = total;
-    return truncatedIf(total, capacity);
+    return finishRun(ed->handle, ed->handle->edit_run_ptr, run, call);
 }
 
 /* one cell of the band on the host: the cost, saturated at k + 1, and the start of the shortest best match */
@@ -211,11 +179,7 @@ PFAC_status_t PFACX_editOpen(PFAC_handle_t handle, const unsigned char *h_bytes,
         if (badPattern) *badPattern = bad;
         if (st != PFAC_STATUS_SUCCESS) return st;                             /* nothing of the handle has changed */
     } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
-    /* the pieces through the reader of every pattern set: the set is replaced, the handle case-sensitive */
-    PFAC_status_t st = PFACX_readPatternFromMemory(handle, plan.text.data(), plan.text.size());
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    return adoptNew(handle, edit, [&](PFACX_edit_s &obj) -> PFAC_status_t {
-        if (!holdsPieces(handle, plan)) return PFAC_STATUS_INVALID_PARAMETER;   /* another thread has replaced the set since */
+    return adoptOverStrings(handle, plan.pieces, edit, [&](PFACX_edit_s &obj) -> PFAC_status_t {       /* (verify_calls.h: the tables hold only over the pieces) */
         obj.maxBudget = (unsigned int)*std::max_element(plan.budget.begin(), plan.budget.end());
         obj.bestEnds = (flags & PFACX_EDIT_BEST_ENDS) != 0u;
         buildPieceTables<pfac::EditEntry>(plan, &obj);
@@ -238,74 +202,27 @@ PFAC_status_t PFACX_editGetPieces(PFACX_edit_t edit, size_t *h_pieceOff, int *h_
 PFAC_status_t PFACX_editMatchFromDevice(PFACX_edit_t edit, char *d_input, size_t size, int *d_ids, int *d_pos, int *d_end, int *d_dist, size_t capacity,
                                         size_t *h_num_matched)
 {
-    PFAC_status_t st = checkEditArgs(edit, d_input, size, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (!d_ids || !d_pos) return PFAC_STATUS_INVALID_PARAMETER;
-    PFAC_context *c = edit->handle;
-    if (size && capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    std::lock_guard<std::mutex> guard(c->lock);
-    st = checkSetGeneration(c, edit->generation);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    DeviceScan scan;
-    st = beginDeviceScan(c, d_input, size, &scan);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    /* the caller's arrays take the scan's unordered list, the ordered pairs go to the handle's pair scratch: the passes never filter in place */
-    int count = 0;
-    st = c->all_reduce_ptr(c, reinterpret_cast<int *>(scan.d_scan), (int)size, d_ids, d_pos, &count, scan.hashed);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
-    const int *pairIds = c->scratch.allPairs.get();
-    const int *pairPos = pairIds + c->scratch.allPairs.count() / 2;        /* one allocation: the ids, then as many positions */
-    if (count == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    return editRunLocked(edit, d_input, size, pairIds, pairPos, (size_t)count, d_ids, d_pos, d_end, d_dist, capacity, h_num_matched);
+    const VerifyCall call{d_input, size, d_ids, d_pos, capacity, h_num_matched};
+    return verifyFromDevice(edit, call, [&](const int *ids, const int *pos, size_t count) { return editRunLocked(edit, call, d_end, d_dist, ids, pos, count); });
 }
 
 PFAC_status_t PFACX_editMatchFromHost(PFACX_edit_t edit, char *h_input, size_t size, int *h_ids, int *h_pos, int *h_end, int *h_dist, size_t capacity,
                                       size_t *h_num_matched)
 {
-    PFAC_status_t st = checkEditArgs(edit, h_input, size, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (capacity && (!h_ids || !h_pos)) return PFAC_STATUS_INVALID_PARAMETER;
-    PFAC_context *c = edit->handle;
-    {
-        std::lock_guard<std::mutex> guard(c->lock);
-        st = checkSetGeneration(c, edit->generation);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-    }
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    const HostPairs pairs(size, size);
-    if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
-    const PinnedPairs scan(c, h_input, size, pairs.ids, pairs.pos);
-    if (scan.status != PFAC_STATUS_SUCCESS) return scan.status;
-    if (scan.generation != edit->generation) return PFAC_STATUS_INVALID_PARAMETER;      /* another thread has replaced the set meanwhile: as after the call */
-    const size_t total = editOnHost(c->fa, *edit, reinterpret_cast<const unsigned char *>(h_input), size, pairs.ids, pairs.pos,
-                                    (size_t)(scan.count > 0 ? scan.count : 0), h_ids, h_pos, h_end, h_dist, capacity);
-    *h_num_matched = total;
-    return truncatedIf(total, capacity);
+    const VerifyCall call{h_input, size, h_ids, h_pos, capacity, h_num_matched};
+    return verifyFromHost(edit, call, [&](const int *ids, const int *pos, size_t count) {
+        return editOnHost(edit->handle->fa, *edit, reinterpret_cast<const unsigned char *>(h_input), size, ids, pos, count, h_ids, h_pos, h_end, h_dist,
+                          capacity);
+    });
 }
 
 PFAC_status_t PFACX_editPairsFromDevice(PFACX_edit_t edit, const char *d_input, size_t size, const int *d_pairIds, const int *d_pairPos,
                                         size_t numPairs, int *d_ids, int *d_pos, int *d_end, int *d_dist, size_t capacity, size_t *h_num_matched)
 {
-    PFAC_status_t st = checkEditArgs(edit, d_input, size, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (numPairs > kMaxInt || capacity > SIZE_MAX / sizeof(int) || (numPairs && (!d_pairIds || !d_pairPos)) || (capacity && (!d_ids || !d_pos)))
-        return PFAC_STATUS_INVALID_PARAMETER;
-    if (capacity && numPairs) {
-        const size_t in = numPairs * sizeof(int), out = capacity * sizeof(int);
-        for (const int *array : {d_ids, d_pos, d_end, d_dist})
-            if (array && (overlap(array, out, d_pairIds, in) || overlap(array, out, d_pairPos, in))) return PFAC_STATUS_INVALID_PARAMETER;
-    }
-    PFAC_context *c = edit->handle;
-    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    std::lock_guard<std::mutex> guard(c->lock);
-    st = checkSetGeneration(c, edit->generation);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0 || numPairs == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    return editRunLocked(edit, d_input, size, d_pairIds, d_pairPos, numPairs, d_ids, d_pos, d_end, d_dist, capacity, h_num_matched);
+    const VerifyCall call{d_input, size, d_ids, d_pos, capacity, h_num_matched};
+    return verifyPairsFromDevice(edit, call, d_pairIds, d_pairPos, numPairs, {d_ids, d_pos, d_end, d_dist}, [&](const int *ids, const int *pos, size_t count) {
+        return editRunLocked(edit, call, d_end, d_dist, ids, pos, count);
+    });
 }
 
 } /* extern "C" */

@@ -2,7 +2,8 @@
  * piece_cut.h -- the pigeonhole cut that PFACX_approxOpen and PFACX_editOpen share (approx_api.cpp, edit_api.cpp): a pattern with budget k is cut
  * into k + 1 disjoint parts, of which any occurrence within k mismatches -- or k edits -- leaves one untouched; the PIECE of a part is its head.
  * planPatterns checks the caller's CSR arrays, copies them and lays out the pieces and the piece set as the reader's text; buildPieceTables makes
- * the per-class entry tables and the blob of an object from the plan; getPieces is the getter of both families.
+ * the per-class entry tables and the blob of an object from the plan; getPieces is the getter of both families.  Loading the piece set and
+ * checking that the handle holds it is verify_calls.h's adoptOverStrings.
  */
 #ifndef PFAC_PIECE_CUT_H
 #define PFAC_PIECE_CUT_H
@@ -10,11 +11,11 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "pfac_host.h"
+#include "verify_calls.h"
 
 namespace pfac_internal {
 
@@ -29,8 +30,7 @@ struct PiecePlan {
     size_t maxPiece = 0;
     std::vector<unsigned int> pieceOff;               /* [S + 2] by pattern id */
     std::vector<int> pieceId, pieceStart, pieceLen;   /* per piece */
-    std::vector<std::string> pieces;                  /* by handle id - 1: the distinct pieces in order of first appearance */
-    std::string text;                                 /* one line per distinct piece */
+    StringSet pieces;                                 /* by handle id - 1: the distinct pieces, and the piece set as the reader's text (verify_calls.h) */
 };
 
 /* part j of a pattern of len bytes with budget k starts here; part k ends at len */
@@ -68,7 +68,6 @@ inline PFAC_status_t planPatterns(const unsigned char *h_bytes, const size_t *h_
     plan->pieceId.reserve(numPieces);
     plan->pieceStart.reserve(numPieces);
     plan->pieceLen.reserve(numPieces);
-    std::map<std::string, int> seen;
     for (size_t i = 1; i <= S; i++) {
         const size_t len = h_patOff[i] - h_patOff[i - 1], k = (size_t)h_budget[i - 1];
         plan->off[i] = plan->off[i - 1] + len;
@@ -76,14 +75,7 @@ inline PFAC_status_t planPatterns(const unsigned char *h_bytes, const size_t *h_
         const unsigned char *pat = plan->bytes.data() + plan->off[i - 1];
         for (size_t j = 0; j <= k; j++) {
             const size_t from = partStart(j, len, k), plen = std::min(partStart(j + 1, len, k) - from, cut);
-            const std::string piece(reinterpret_cast<const char *>(pat) + from, plen);
-            const auto placed = seen.emplace(piece, (int)plan->pieces.size() + 1);
-            if (placed.second) {
-                plan->pieces.push_back(piece);
-                plan->text += piece;
-                plan->text += '\n';
-            }
-            plan->pieceId.push_back(placed.first->second);
+            plan->pieceId.push_back(plan->pieces.idOf(std::string(reinterpret_cast<const char *>(pat) + from, plen)));
             plan->pieceStart.push_back((int)from);
             plan->pieceLen.push_back((int)plen);
         }
@@ -122,20 +114,6 @@ inline void buildPieceTables(PiecePlan &plan, Obj *obj)
     obj->pieceId = std::move(plan.pieceId);
     obj->pieceStart = std::move(plan.pieceStart);
     obj->pieceLen = std::move(plan.pieceLen);
-}
-
-/* is the set the handle holds now the plan's pieces, id by id?  (another thread may have replaced it since the plan was loaded) */
-inline bool holdsPieces(const PFAC_context *handle, const PiecePlan &plan)
-{
-    const pfac::Automaton &fa = handle->fa;
-    if (handle->caseInsensitive || (size_t)fa.numPatterns != plan.pieces.size()) return false;
-    for (size_t q = 1; q <= plan.pieces.size(); q++) {
-        const std::string &piece = plan.pieces[q - 1];
-        if ((size_t)fa.patternLen[q] != piece.size() || fa.chainLen[q] < 1 ||
-            std::memcmp(fa.file.data() + fa.patternOff[q], piece.data(), piece.size()) != 0)
-            return false;
-    }
-    return true;
 }
 
 /* the getter of both families, behind the caller's handle and generation checks */

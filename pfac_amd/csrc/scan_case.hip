@@ -16,11 +16,11 @@
  *                        holds to the frame, which writes (id, p) into consecutive slots; slots >= capacity are skipped
  *   pfac_host_done       the call's sequence number to mapped host memory (scan_passes.h: HostHandoff)
  * The walk along the chain (forEachChainMember), both passes, the capacity-checked store and the launches (expandPasses) are the expansion frame of
- * scan_passes.h, shared with scan_all.hip, scan_words.hip and scan_groups.hip; this unit's own is the test of a member (walkPair) and the compare.
- * THE COMPARE works on dwords: the blob is dword-aligned, the input side of dword k is composed from the two aligned dwords around in[p + 4 k] with
- * v_alignbyte, the way pfac_fold<Q> composes a misaligned source; the differences are ORed up and tested every 16 bytes.  An aligned dword that
- * would reach outside [0, n) -- in front of in[0] where the caller's pointer is misaligned and p < 3, behind in[n - 1] at the end -- is put
- * together from its bytes inside the buffer (three at most), and so are the len & 3 bytes behind the pattern's last whole dword.
+ * scan_passes.h, shared with scan_all.hip, scan_words.hip, scan_groups.hip and the other verify units; the compare and the head of PFACX_caseRun
+ * are scan_verify.h's; this unit's own is the test of a member (walkPair) with its class loop, which ends the whole walk in list mode.
+ * THE COMPARE (scan_verify.h: bytesEqual) works on dwords: the blob is dword-aligned, the input side of dword k is composed from the two aligned
+ * dwords around in[p + 4 k] with v_alignbyte, the way pfac_fold<Q> composes a misaligned source; the differences are ORed up and tested every 16
+ * bytes.
  * Every index into the input is checked against [0, n) before the load; an id outside [1, F] is a pair that counts nothing, a member that does not
  * lie inside the input is not kept, a walk ends after chainLen steps whatever the table says, and a class's variant range is clamped to the table:
  * a caller's list cannot make a pass read or write outside the buffers.  A thread per pair: a long sensitive pattern keeps its lane busy while
@@ -37,6 +37,7 @@
 
 #include "pfac_context.h"
 #include "scan_passes.h"
+#include "scan_verify.h"
 
 namespace {
 
@@ -45,8 +46,7 @@ constexpr unsigned int kCaseTrivial = 0x80000000u;      /* bit 31 of varOff[q]: 
 
 struct CaseArgs {
     ExpandFrame f;                      /* the pairs, the chain table, PFACX_CASE_ALL, the block cut, the caller's arrays (scan_passes.h) */
-    const unsigned char *in;            /* the caller's bytes: never the folded copy */
-    unsigned int n;
+    InputView v;                        /* the caller's bytes (scan_verify.h) */
     const int *patternLen;              /* [numIds + 1] by id */
     const unsigned int *varOff;         /* [numIds + 2] by id: first variant | kCaseTrivial */
     const pfac::Int2 *vars;             /* {line id, dword index into blob or -1} */
@@ -55,60 +55,14 @@ struct CaseArgs {
     unsigned int blobWords;
 };
 
-/* the aligned dword of the input whose first byte is in[o] (o: any sign; in + o is dword-aligned): one load where it lies inside [0, n), else its
- * bytes inside the buffer, zero for the others */
-__device__ __forceinline__ uint32_t alignedDword(const CaseArgs &a, long long o)
-{
-    if (o >= 0 && o + 4 <= (long long)a.n) return *reinterpret_cast<const uint32_t *>(a.in + o);
-    uint32_t w = 0;
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-        const long long i = o + b;
-        if (i >= 0 && i < (long long)a.n) w |= (uint32_t)a.in[i] << (8 * b);
-    }
-    return w;
-}
-
-/* in[p, p + len) == the len bytes at blob[off ...]?  p + len <= n and the pattern's dwords lie inside the blob (the caller has checked both) */
-__device__ __forceinline__ bool bytesEqual(const CaseArgs &a, unsigned int p, unsigned int len, unsigned int off)
-{
-    const unsigned int words = len >> 2, r = (unsigned int)(reinterpret_cast<uintptr_t>(a.in + p) & 3u);
-    const uint32_t *pat = a.blob + off;
-    uint32_t diff = 0;
-    if (r == 0) {
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.in + p);       /* whole dwords inside [p, p + len) */
-        for (unsigned int k = 0; k < words; k++) {
-            diff |= src[k] ^ pat[k];
-            if ((k & 3u) == 3u && diff != 0) return false;
-        }
-    } else {
-        const long long base = (long long)p - (long long)r;                     /* the aligned dword that holds in[p] */
-        uint32_t lo = words ? alignedDword(a, base) : 0u;
-        for (unsigned int k = 0; k < words; k++) {
-            const uint32_t hi = alignedDword(a, base + 4ll * (k + 1u));
-            diff |= __builtin_amdgcn_alignbyte(hi, lo, r) ^ pat[k];
-            if ((k & 3u) == 3u && diff != 0) return false;
-            lo = hi;
-        }
-    }
-    if (diff != 0) return false;
-    const unsigned int tail = len & 3u;
-    if (tail) {
-        const uint32_t last = pat[words];
-        for (unsigned int b = 0; b < tail; b++)
-            if (a.in[p + 4u * words + b] != (unsigned char)(last >> (8u * b))) return false;
-    }
-    return true;
-}
-
 /* The variants that hold along pair k's chain, longest member first, highest line id first within a member (scan_passes.h: forEachChainMember):
  * emit(line id) for each of them; returns their number (list mode: 0 or 1) */
 template <class Emit>
 __device__ __forceinline__ unsigned int walkPair(const CaseArgs &a, size_t k, Emit emit)
 {
     const int id = a.f.pairIds[k], p = a.f.pairPos[k];
-    if (p < 0 || (unsigned int)p >= a.n) return 0u;
-    const unsigned int room = a.n - (unsigned int)p;
+    if (p < 0 || (unsigned int)p >= a.v.n) return 0u;
+    const unsigned int room = a.v.n - (unsigned int)p;
     unsigned int found = 0;
     forEachChainMember(a.f.table, a.f.numIds, id, [&](int q) {
         const int len = a.patternLen[q];
@@ -125,8 +79,8 @@ __device__ __forceinline__ unsigned int walkPair(const CaseArgs &a, size_t k, Em
             const pfac::Int2 var = a.vars[v];
             if (var.y >= 0) {
                 const unsigned int off = (unsigned int)var.y;
-                if (off >= a.blobWords || a.blobWords - off < ((unsigned int)len + 3u) / 4u) continue;     /* (a table of the library's own: never) */
-                if (!bytesEqual(a, (unsigned int)p, (unsigned int)len, off)) continue;
+                if (!inBlob(a.blobWords, off, ((unsigned int)len + 3u) / 4u)) continue;                    /* (a table of the library's own: never) */
+                if (!bytesEqual(a.v, a.blob + off, (unsigned int)p, (unsigned int)len)) continue;
             }
             emit(var.x);
             found++;
@@ -156,24 +110,20 @@ extern "C" {
 PFAC_status_t PFACX_caseRun(PFAC_handle_t handle, const PFACX_caseRun_t *run, size_t *h_total)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!run || !h_total || !run->d_input || run->size == 0 || run->size > (size_t)0x7fffffff || !run->d_patternLen || run->numIds > (size_t)0x7ffffffe ||
-        !run->d_varOff || !run->d_vars || run->numVars > (size_t)0x7fffffff || run->blobWords > (size_t)0x7fffffff || (run->blobWords && !run->d_blob) ||
-        run->count > (size_t)0x7fffffff || (run->count && (!run->d_pairIds || !run->d_pairPos)) || (run->capacity && (!run->d_ids || !run->d_pos)))
+    if (!run || !verifyRunOk(run->v, h_total) || !run->d_patternLen || !run->d_varOff || !run->d_vars || run->numVars > (size_t)0x7fffffff)
         return PFAC_STATUS_INVALID_PARAMETER;
     *h_total = 0;
-    if (run->count == 0) return PFAC_STATUS_SUCCESS;
+    if (run->v.count == 0) return PFAC_STATUS_SUCCESS;
     PFAC_context *c = handle;
     CaseArgs a{};
-    a.in = reinterpret_cast<const unsigned char *>(run->d_input);
-    a.n = (unsigned int)run->size;
+    a.v = verifyInput(run->v);
     a.patternLen = run->d_patternLen;
     a.varOff = run->d_varOff;
     a.vars = static_cast<const pfac::Int2 *>(run->d_vars);
     a.numVars = (unsigned int)run->numVars;
-    a.blob = run->d_blob;
-    a.blobWords = (unsigned int)run->blobWords;
-    a.f = ExpandFrame{run->d_pairIds, run->d_pairPos, run->count, static_cast<const pfac::Int2 *>(run->d_table), (unsigned int)run->numIds,
-                      run->all ? 1u : 0u, 0, nullptr, run->d_ids, run->d_pos, run->capacity};
+    a.blob = run->v.d_blob;
+    a.blobWords = (unsigned int)run->v.blobWords;
+    a.f = verifyFrame(run->v, run->all ? 1u : 0u);
     return expandPasses(c, c->scratch.caseSet, pfac::kHostCase, a, pfac_case_count, pfac_case_write, kCaseBlock, a.f.capacity != 0, h_total);
 }
 

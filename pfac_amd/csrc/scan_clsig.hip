@@ -5,7 +5,7 @@
  * anchor a scan found, the (signature, start) for which a choice of run lengths exists under which every part holds in the caller's input and the
  * bytes around it pass the signature's boundary classes, each listed once, with the largest (or, by a flag, the smallest) end over all such choices.
  *
- * The frame is that of scan_gapsig.hip: every anchor that starts at p is a prefix of the longest one that starts there, so the candidates at p are
+ * The frame is scan_verify.h's, as in scan_gapsig.hip: every anchor that starts at p is a prefix of the longest one that starts there, so the candidates at p are
  * the longest one's prefix chain (scan_all.hip), and behind a member q stands its CLASS OF SIGNATURES: those that chose q as their anchor, highest
  * signature id first, each {id, first part, number of parts | anchor part << 16, offset of the anchor inside that part} {notBefore, notAfter};
  * a part is {0, len, blobOff} or {1, class, lo, hi} (clsig_api.cpp builds the tables).  The passes work on an ordered list of LONGEST pairs -- the
@@ -16,7 +16,7 @@
  *   pfac_array_scan      exclusive scan of the block totals (one block; 64-bit), the length of the list to mapped host memory
  *   pfac_clsig_write     the block's pairs again (expandWrite): each thread runs the same search once more -- one function, so both passes
  *                        decide alike -- and hands (signature id, start) to the frame (ExpandEmit with a position); the end goes to end[slot]
- *                        in front of the frame's store, as in scan_gapsig.hip
+ *                        in front of the frame's store (scan_verify.h: emitWithAux)
  *   pfac_host_done       the call's sequence number to mapped host memory (scan_passes.h: HostHandoff)
  * The walk along the chain, both passes, the capacity-checked store and the launches are the expansion frame of scan_passes.h, unchanged; this
  * unit's own is the search (searchSignature) and its part steps.
@@ -43,7 +43,7 @@
  * CLASS LOOKUPS.  A class is 256 bits in eight dwords; membership of byte b is bit b & 31 of dword b >> 5, read from memory by its index, never
  * out of eight registers.  The first kClSigStaged classes of the table are staged in LDS by every block (2 KiB; a supposition, not measured), the
  * others are read from device memory.
- * THE COMPARE of a literal part is the bounds-safe dword compare of scan_gapsig.hip without the mask (a copy: that unit stays as it is).
+ * THE COMPARE of a literal part is the bounds-safe dword compare without a mask (scan_verify.h: bytesEqual, which scan_case.hip uses too).
  * Every index into the input is checked against [0, n) before the load; an id outside [1, F] is a pair that counts nothing, a walk ends after
  * chainLen steps whatever the table says, signature and part ranges and class indices are clamped to their tables, a part whose dwords do not lie
  * inside the blob holds nowhere: a caller's list cannot make a pass read or write outside the buffers.  A thread per pair: DESIGN.md 5z says what
@@ -64,6 +64,7 @@
 
 #include "pfac_context.h"
 #include "scan_passes.h"
+#include "scan_verify.h"
 
 namespace {
 
@@ -75,8 +76,7 @@ constexpr unsigned int kClSigStaged = 64;         /* the classes every block sta
 
 struct ClSigArgs {
     ExpandFrame f;                      /* the pairs, the chain table, the block cut, the caller's arrays (scan_passes.h); f.all is not read */
-    const unsigned char *in;            /* the caller's bytes */
-    unsigned int n;
+    InputView v;                        /* the caller's bytes (scan_verify.h) */
     const unsigned int *sigOff;         /* [numIds + 2] by anchor id: the first signature of its class */
     const pfac::ClSigEntry *sigs;
     unsigned int numSigs;
@@ -120,67 +120,20 @@ __device__ __forceinline__ bool inClass(const ClSigArgs &a, const uint32_t *stag
     return (word >> (b & 31u) & 1u) != 0u;
 }
 
-/* the aligned dword of the input whose first byte is in[o] (o: any sign; in + o is dword-aligned): one load where it lies inside [0, n), else its
- * bytes inside the buffer, zero for the others */
-__device__ __forceinline__ uint32_t alignedDword(const ClSigArgs &a, long long o)
-{
-    if (o >= 0 && o + 4 <= (long long)a.n) return *reinterpret_cast<const uint32_t *>(a.in + o);
-    uint32_t w = 0;
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-        const long long i = o + b;
-        if (i >= 0 && i < (long long)a.n) w |= (uint32_t)a.in[i] << (8 * b);
-    }
-    return w;
-}
-
-/* in[s + k] == value[k] for every k < len?  s + len <= n and the part's (len + 3) / 4 dwords at blob[off ...] lie inside the blob (the caller has
- * checked both) */
-__device__ __forceinline__ bool literalEqual(const ClSigArgs &a, unsigned int s, unsigned int len, unsigned int off)
-{
-    const unsigned int words = len >> 2, r = (unsigned int)(reinterpret_cast<uintptr_t>(a.in + s) & 3u);
-    const uint32_t *val = a.blob + off;
-    uint32_t diff = 0;
-    if (r == 0) {
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.in + s);       /* whole dwords inside [s, s + len) */
-        for (unsigned int k = 0; k < words; k++) {
-            diff |= src[k] ^ val[k];
-            if ((k & 3u) == 3u && diff != 0) return false;
-        }
-    } else {
-        const long long base = (long long)s - (long long)r;                     /* the aligned dword that holds in[s] */
-        uint32_t lo = words ? alignedDword(a, base) : 0u;
-        for (unsigned int k = 0; k < words; k++) {
-            const uint32_t hi = alignedDword(a, base + 4ll * (k + 1u));
-            diff |= __builtin_amdgcn_alignbyte(hi, lo, r) ^ val[k];
-            if ((k & 3u) == 3u && diff != 0) return false;
-            lo = hi;
-        }
-    }
-    if (diff != 0) return false;
-    const unsigned int tail = len & 3u;
-    if (tail) {
-        const uint32_t v = val[words];
-        for (unsigned int b = 0; b < tail; b++)
-            if ((((uint32_t)a.in[s + 4u * words + b] ^ (v >> (8u * b))) & 0xFFu) != 0u) return false;
-    }
-    return true;
-}
-
 /* the bits t of m at which literal part q holds at offset base + dir * t: inside the window -- tested before any load -- and every byte equal.  A
  * part that is empty or whose dwords do not lie inside the blob holds nowhere */
 template <class W>
 __device__ __forceinline__ uint64_t literalWhere(const ClSigArgs &a, const W &w, const pfac::ClSigPart &q, long long base, int dir, uint64_t m)
 {
     const unsigned int len = q.a, need = (len + 3u) >> 2;
-    if (len == 0u || len > kClSigMaxRepeat || q.b >= a.blobWords || a.blobWords - q.b < need) return 0ull;
+    if (len == 0u || len > kClSigMaxRepeat || !inBlob(a.blobWords, q.b, need)) return 0ull;
     uint64_t held = 0;
     while (m != 0ull) {                                   /* at most 64 rounds */
         const int t = __builtin_ctzll(m);
         m &= m - 1ull;
         const long long o = base + (long long)dir * t;
         if (o < (long long)w.lo || o + (long long)len > (long long)w.hi) continue;
-        if (literalEqual(a, (unsigned int)o, len, q.b)) held |= 1ull << t;
+        if (bytesEqual(a.v, a.blob + q.b, (unsigned int)o, len)) held |= 1ull << t;
     }
     return held;
 }
@@ -207,7 +160,7 @@ __device__ __forceinline__ Reach classForward(const ClSigArgs &a, const W &w, co
     if (near < (long long)w.lo) near = (long long)w.lo;
     unsigned int run = 0;
     for (long long o = far; o >= near; o--) {             /* at most hi + 64 rounds */
-        if (o < far) run = inClass(a, staged, q.a, a.in[o]) ? run + 1u : 0u;
+        if (o < far) run = inClass(a, staged, q.a, a.v.in[o]) ? run + 1u : 0u;
         const long long t = o - base;
         if (t > 63 || !(r.all >> t & 1ull)) continue;
         const unsigned int len = run < hi ? run : hi;
@@ -233,7 +186,7 @@ __device__ __forceinline__ uint64_t classBackward(const ClSigArgs &a, const W &w
     uint64_t out = 0ull;
     unsigned int run = 0;
     for (long long o = low; o <= high; o++) {             /* at most hi + 64 rounds */
-        if (o > low) run = inClass(a, staged, q.a, a.in[o - 1]) ? run + 1u : 0u;
+        if (o > low) run = inClass(a, staged, q.a, a.v.in[o - 1]) ? run + 1u : 0u;
         const long long t = base - o;
         if (t > 63 || !(m >> t & 1ull)) continue;
         const unsigned int len = run < hi ? run : hi;
@@ -273,7 +226,7 @@ __device__ __forceinline__ unsigned int searchSignature(const ClSigArgs &a, cons
             const int t = __builtin_ctzll(m);
             m &= m - 1ull;
             const long long s = tight - t;
-            if (s > (long long)w.lo && s <= (long long)w.hi && inClass(a, staged, (unsigned int)e.notBefore, a.in[s - 1])) back &= ~(1ull << t);
+            if (s > (long long)w.lo && s <= (long long)w.hi && inClass(a, staged, (unsigned int)e.notBefore, a.v.in[s - 1])) back &= ~(1ull << t);
         }
     }
     unsigned int found = 0;
@@ -319,7 +272,7 @@ __device__ __forceinline__ unsigned int searchSignature(const ClSigArgs &a, cons
                 const int t = __builtin_ctzll(m);
                 m &= m - 1ull;
                 const long long end = at + t;
-                if (end >= (long long)w.hi || !inClass(a, staged, (unsigned int)e.notAfter, a.in[end])) valid |= 1ull << t;
+                if (end >= (long long)w.hi || !inClass(a, staged, (unsigned int)e.notAfter, a.v.in[end])) valid |= 1ull << t;
             }
             r.all &= valid;
             r.lt &= valid;
@@ -339,10 +292,7 @@ __device__ __forceinline__ unsigned int walkChainAt(const ClSigArgs &a, const W 
 {
     unsigned int found = 0;
     forEachChainMember(a.f.table, a.f.numIds, id, [&](int q) {
-        const unsigned int first = a.sigOff[q];
-        unsigned int end = a.sigOff[q + 1];
-        if (end > a.numSigs) end = a.numSigs;
-        for (unsigned int v = first; v < end; v++) found += searchSignature(a, w, staged, a.sigs[v], p, emit);
+        forEachClassEntry(a.sigOff, a.numSigs, q, [&](unsigned int v) { found += searchSignature(a, w, staged, a.sigs[v], p, emit); });
         return true;
     });
     return found;
@@ -353,8 +303,8 @@ template <class Emit>
 __device__ __forceinline__ unsigned int walkPair(const ClSigArgs &a, const uint32_t *staged, size_t k, Emit emit)
 {
     const int id = a.f.pairIds[k], p = a.f.pairPos[k];
-    if (p < 0 || (unsigned int)p >= a.n) return 0u;
-    return walkChainAt(a, WholeBuffer{a.n}, staged, id, p, emit);
+    if (p < 0 || (unsigned int)p >= a.v.n) return 0u;
+    return walkChainAt(a, WholeBuffer{a.v.n}, staged, id, p, emit);
 }
 
 /* ------------------------------------------------------------------ the batch passes (PFACX_clsigBatch*)
@@ -473,10 +423,7 @@ __global__ __launch_bounds__(kClSigBlock) void pfac_clsig_write(ClSigArgs a)
     expandWrite<kClSigBlock>(
         a.f, [&](size_t k) -> unsigned long long { return walkPair(a, staged, k, [](int, int, int) {}); },
         [&](size_t k, auto emit) {
-            (void)walkPair(a, staged, k, [&](int id, int s, int end) {
-                if (a.end != nullptr && emit.o < emit.f.capacity) a.end[emit.o] = end;                /* the slot the frame's store takes next */
-                emit(id, s);
-            });
+            (void)walkPair(a, staged, k, [&](int id, int s, int end) { emitWithAux(emit, id, s, a.end, end); });
         });
 }
 
@@ -509,10 +456,7 @@ __global__ __launch_bounds__(kClSigBlock) void pfac_clsig_batch_write(ClSigBatch
         a.f, [&](size_t k) -> unsigned long long { return walkBatchPair(a, b, staged, k, u, [](int, int, int) {}); },
         [&](size_t k, auto emit) {
             unsigned int again;
-            (void)walkBatchPair(a, b, staged, k, again, [&](int id, int s, int end) {
-                if (a.end != nullptr && emit.o < emit.f.capacity) a.end[emit.o] = end;                /* the slot the frame's store takes next */
-                emit(id, s);
-            });
+            (void)walkBatchPair(a, b, staged, k, again, [&](int id, int s, int end) { emitWithAux(emit, id, s, a.end, end); });
         },
         [&](size_t k, unsigned long long before) {
             if (a.segFirst == nullptr) return;                  /* every segment that starts behind the pair in front and at or in front of this one */
@@ -528,15 +472,13 @@ extern "C" {
 PFAC_status_t PFACX_clsigRun(PFAC_handle_t handle, const PFACX_clsigRun_t *run, size_t *h_total)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!run || !h_total || !run->d_input || run->size == 0 || run->size > (size_t)0x7fffffff || run->numIds > (size_t)0x7ffffffe || !run->d_sigOff ||
-        !run->d_sigs || run->numSigs > (size_t)0x7fffffff || !run->d_parts || run->numParts > (size_t)0x7fffffff ||
-        run->blobWords > (size_t)0x7fffffff || !run->d_blob || !run->d_classes || run->numClasses == 0 || run->numClasses > (size_t)0xFFFF ||
-        (run->flags & ~PFACX_CLSIG_SHORTEST_END) != 0u || run->count > (size_t)0x7fffffff || (run->count && (!run->d_pairIds || !run->d_pairPos)) ||
-        (run->capacity && (!run->d_ids || !run->d_pos)) ||
+    if (!run || !verifyRunOk(run->v, h_total) || !run->v.d_blob || !run->d_sigOff || !run->d_sigs || run->numSigs > (size_t)0x7fffffff || !run->d_parts ||
+        run->numParts > (size_t)0x7fffffff || !run->d_classes || run->numClasses == 0 || run->numClasses > (size_t)0xFFFF ||
+        (run->flags & ~PFACX_CLSIG_SHORTEST_END) != 0u ||
         (run->d_offsets ? run->numSegments == 0 || run->numSegments >= (size_t)0x7fffffff : run->d_segFirst != nullptr))
         return PFAC_STATUS_INVALID_PARAMETER;
     *h_total = 0;
-    if (run->count == 0) {                                      /* no pair: nothing to launch */
+    if (run->v.count == 0) {                                      /* no pair: nothing to launch */
         if (!run->d_segFirst) return PFAC_STATUS_SUCCESS;
         return hipMemsetAsync(run->d_segFirst, 0, (run->numSegments + 1) * sizeof(size_t), nullptr) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess
                    ? PFAC_STATUS_SUCCESS
@@ -544,21 +486,19 @@ PFAC_status_t PFACX_clsigRun(PFAC_handle_t handle, const PFACX_clsigRun_t *run, 
     }
     PFAC_context *c = handle;
     ClSigArgs a{};
-    a.in = reinterpret_cast<const unsigned char *>(run->d_input);
-    a.n = (unsigned int)run->size;
+    a.v = verifyInput(run->v);
     a.sigOff = run->d_sigOff;
     a.sigs = static_cast<const pfac::ClSigEntry *>(run->d_sigs);
     a.numSigs = (unsigned int)run->numSigs;
     a.parts = static_cast<const pfac::ClSigPart *>(run->d_parts);
     a.numParts = (unsigned int)run->numParts;
-    a.blob = run->d_blob;
-    a.blobWords = (unsigned int)run->blobWords;
+    a.blob = run->v.d_blob;
+    a.blobWords = (unsigned int)run->v.blobWords;
     a.classes = run->d_classes;
     a.numClasses = (unsigned int)run->numClasses;
     a.shortest = run->flags & PFACX_CLSIG_SHORTEST_END;
-    a.end = run->capacity ? run->d_end : nullptr;
-    a.f = ExpandFrame{run->d_pairIds, run->d_pairPos, run->count, static_cast<const pfac::Int2 *>(run->d_table), (unsigned int)run->numIds,
-                      1u, 0, nullptr, run->d_ids, run->d_pos, run->capacity};
+    a.end = run->v.capacity ? run->d_end : nullptr;
+    a.f = verifyFrame(run->v);
     if (run->d_offsets) {                                       /* a batch: the bounds in front of the passes, behind the block totals in the same scratch */
         ClSigBatchArgs b{};
         static_cast<ClSigArgs &>(b) = a;
@@ -571,7 +511,7 @@ PFAC_status_t PFACX_clsigRun(PFAC_handle_t handle, const PFACX_clsigRun_t *run, 
             h_total, [&](ScratchCarver &k) { b.bounds = bounds = k.take<unsigned int>(run->numSegments + 1); }, false,
             [&]() {
                 hipLaunchKernelGGL(pfac_clsig_bounds, dim3((b.numSegments + 1u + kBoundsBlock - 1u) / kBoundsBlock), dim3(1024), 0, 0, run->d_offsets,
-                                   b.numSegments + 1u, b.n, bounds);
+                                   b.numSegments + 1u, b.v.n, bounds);
                 return true;
             });
     }

@@ -14,7 +14,9 @@
  *   scan_count.hip    pfac_count_*: the histogram of the scan's pairs, the counts along the prefix chains, the non-zero counts (PFACX_count*)
  *   scan_disjoint.hip pfac_disjoint_* / pfac_replace_*: the disjoint leftmost-longest list from the scan's ordered pairs (pointer doubling), the replacement (PFACX_matchDisjoint* / PFACX_replace*)
  * scan_passes.h holds what the units around the product kernels share on top of this: the hand-off to the host, block prefix sums, the seam,
- * the segment-window frame of scan_rules.hip and scan_segcount.hip.
+ * the segment-window frame of scan_rules.hip and scan_segcount.hip.  scan_verify.h holds what scan_case.hip, scan_sig.hip, scan_approx.hip,
+ * scan_gapsig.hip, scan_edit.hip and scan_clsig.hip share on top of that: the bounds-safe dword walk over the caller's bytes with its three
+ * compares, the clamped class loop, the store with further arrays, the head of their PFACX_*Run.
  */
 #ifndef PFAC_SCAN_COMMON_H_
 #define PFAC_SCAN_COMMON_H_

@@ -28,7 +28,7 @@
  *   e - L + o_j' + k] with the piece inside [0, n), or piece j itself at a p' in [e - L + o_j - k, p - 1]: every occurrence once, by the
  *   covering candidate with the smallest j and of those the smallest p.  It reads the input, not the pair list.
  * The write pass hands (pattern id, start) to the frame's emit and stores end and distance itself in front of it, under the emit's own slot and
- * capacity, as scan_approx.hip does for its third array.
+ * capacity (scan_verify.h: emitWithAux, which also holds the class loop and the head of PFACX_editRun).
  * Table defence as in the siblings: an id outside [1, F] is a pair that counts nothing, a position outside [0, n) too, a class's range is
  * clamped to the table, an entry whose dwords leave the blob, or with k > K, j > k or L <= k, is skipped.
  * A thread per pair: a candidate that holds costs L x (4 K + 3) dependent cell updates in one lane, in the count pass and twice in the write
@@ -45,6 +45,7 @@
 
 #include "pfac_context.h"
 #include "scan_passes.h"
+#include "scan_verify.h"
 
 namespace {
 
@@ -54,8 +55,7 @@ constexpr unsigned int kExitEvery = 4;                    /* rows between two te
 
 struct EditArgs {
     ExpandFrame f;                      /* the pairs, the chain table, the block cut, the caller's arrays (scan_passes.h); f.all is not read */
-    const unsigned char *in;            /* the caller's bytes */
-    unsigned int n;
+    InputView v;                        /* the caller's bytes (scan_verify.h) */
     const unsigned int *entryOff;       /* [numIds + 2] by piece id: the first entry of its class */
     const pfac::EditEntry *entries;     /* {pattern id, blobOff, o | L << 16, k | j << 8} */
     unsigned int numEntries;
@@ -82,10 +82,10 @@ __device__ __forceinline__ bool coveredEarlier(const EditArgs &a, unsigned int e
         long long lo = (long long)e - (long long)len + (long long)from - (long long)k;
         long long hi = jj < j ? lo + 2ll * (long long)k : (long long)p - 1ll;
         if (lo < 0) lo = 0;
-        if (hi > (long long)a.n - (long long)plen) hi = (long long)a.n - (long long)plen;
+        if (hi > (long long)a.v.n - (long long)plen) hi = (long long)a.v.n - (long long)plen;
         for (long long q = lo; q <= hi; q++) {
             unsigned int t = 0;
-            while (t < plen && a.in[q + t] == pat[from + t]) t++;
+            while (t < plen && a.v.in[q + t] == pat[from + t]) t++;
             if (t == plen) return true;
         }
         from = to;
@@ -101,7 +101,7 @@ __device__ __forceinline__ unsigned int verify(const EditArgs &a, int id, unsign
 {
     constexpr int W = 2 * K + 1, NB = 4 * K + 3, ND = K + 1;
     if ((long long)p - (long long)o < -(long long)k) return 0u;                                   /* every start lies in front of the input */
-    if ((long long)len + (long long)p - (long long)o - (long long)k > (long long)a.n) return 0u;    /* every covered end behind it */
+    if ((long long)len + (long long)p - (long long)o - (long long)k > (long long)a.v.n) return 0u;    /* every covered end behind it */
     /* ub = d0 + W >= 0: column c of cell t in row r is ub + r + t - 2 W, the window's byte t of row r is in[ub + r + t - 2 W - 1] */
     const unsigned int ub = p + (unsigned int)W - o;
     const uint32_t inf = ((k + 1u) << 5) | kStartMask;
@@ -111,10 +111,10 @@ __device__ __forceinline__ unsigned int verify(const EditArgs &a, int id, unsign
 #pragma unroll
     for (int t = 0; t < NB; t++) {
         const unsigned int x = ub + (unsigned int)t;                                             /* c + 2 W */
-        const bool inside = x >= 2u * W && x - 2u * W <= a.n;
+        const bool inside = x >= 2u * W && x - 2u * W <= a.v.n;
         cell[t] = inside ? kStartMask - (uint32_t)t : inf;
         uint32_t b = 0u;                                                                         /* the window of row 0: in[c - 1] */
-        if (x >= 2u * W + 1u && x - (2u * W + 1u) < a.n) b = a.in[x - (2u * W + 1u)];
+        if (x >= 2u * W + 1u && x - (2u * W + 1u) < a.v.n) b = a.v.in[x - (2u * W + 1u)];
         win[t >> 2] |= b << (8 * (t & 3));
     }
     uint32_t pw = 0u;
@@ -122,7 +122,7 @@ __device__ __forceinline__ unsigned int verify(const EditArgs &a, int id, unsign
         pw = ((r - 1u) & 3u) == 0u ? a.blob[off + ((r - 1u) >> 2)] : pw >> 8;
         const uint32_t pb = (pw & 0xFFu) * 0x01010101u;
         const unsigned int at = ub + r - 1u;                                                     /* the one new byte: in[r + d0 + W - 1] */
-        const uint32_t nb = at < a.n ? (uint32_t)a.in[at] : 0u;
+        const uint32_t nb = at < a.v.n ? (uint32_t)a.v.in[at] : 0u;
         uint32_t x[ND];
 #pragma unroll
         for (int i = 0; i + 1 < ND; i++) win[i] = __builtin_amdgcn_alignbyte(win[i + 1], win[i], 1u);
@@ -151,9 +151,9 @@ __device__ __forceinline__ unsigned int verify(const EditArgs &a, int id, unsign
         const unsigned int away = (unsigned int)(t < W ? W - t : t - W);
         const uint32_t v = cell[t], d = v >> 5;
         const unsigned int x = ub + len + (unsigned int)t;                                       /* e + 2 W */
-        if (away > k || d > k || x - 2u * W > a.n) continue;                                     /* (d <= k: the cell's column is >= 0) */
+        if (away > k || d > k || x - 2u * W > a.v.n) continue;                                     /* (d <= k: the cell's column is >= 0) */
         const unsigned int e = x - 2u * W;
-        if (a.bestEnds && ((cell[t - 1] >> 5) <= d || (e != a.n && (cell[t + 1] >> 5) < d))) continue;
+        if (a.bestEnds && ((cell[t - 1] >> 5) <= d || (e != a.v.n && (cell[t + 1] >> 5) < d))) continue;
         if (coveredEarlier(a, e, len, k, j, p, off)) continue;
         emit(id, (int)(ub + (kStartMask - (v & kStartMask)) - 2u * W), (int)e, (int)d);
         found++;
@@ -167,20 +167,17 @@ template <int K, class Emit>
 __device__ __forceinline__ unsigned int walkPair(const EditArgs &a, size_t i, Emit emit)
 {
     const int id = a.f.pairIds[i], p = a.f.pairPos[i];
-    if (p < 0 || (unsigned int)p >= a.n) return 0u;
+    if (p < 0 || (unsigned int)p >= a.v.n) return 0u;
     unsigned int found = 0;
     forEachChainMember(a.f.table, a.f.numIds, id, [&](int q) {
-        const unsigned int first = a.entryOff[q];
-        unsigned int end = a.entryOff[q + 1];
-        if (end > a.numEntries) end = a.numEntries;
-        for (unsigned int v = first; v < end; v++) {
+        forEachClassEntry(a.entryOff, a.numEntries, q, [&](unsigned int v) {
             const pfac::EditEntry e = a.entries[v];
             const unsigned int o = e.startLen & 0xFFFFu, len = e.startLen >> 16, k = e.budgetPiece & 0xFFu, j = (e.budgetPiece >> 8) & 0xFFu;
-            if (k > (unsigned int)K || j > k || len <= k || o >= len) continue;
-            const unsigned int off = (unsigned int)e.blobOff, need = (len + 3u) >> 2;
-            if (e.blobOff < 0 || off >= a.blobWords || a.blobWords - off < need) continue;           /* (a table of the library's own: never) */
+            if (k > (unsigned int)K || j > k || len <= k || o >= len) return;
+            const unsigned int off = (unsigned int)e.blobOff;
+            if (e.blobOff < 0 || !inBlob(a.blobWords, off, (len + 3u) >> 2)) return;                 /* (a table of the library's own: never) */
             found += verify<K>(a, e.id, o, len, k, j, off, (unsigned int)p, emit);
-        }
+        });
         return true;
     });
     return found;
@@ -198,13 +195,7 @@ __global__ __launch_bounds__(kEditBlock) void pfac_edit_write(EditArgs a)
     expandWrite<kEditBlock>(
         a.f, [&](size_t i) -> unsigned long long { return walkPair<K>(a, i, [](int, int, int, int) {}); },
         [&](size_t i, auto emit) {
-            (void)walkPair<K>(a, i, [&](int id, int s, int e, int d) {
-                if (emit.o < emit.f.capacity) {                                                      /* the slot the frame's store takes next */
-                    if (a.end != nullptr) a.end[emit.o] = e;
-                    if (a.dist != nullptr) a.dist[emit.o] = d;
-                }
-                emit(id, s);
-            });
+            (void)walkPair<K>(a, i, [&](int id, int s, int e, int d) { emitWithAux(emit, id, s, a.end, e, a.dist, d); });
         });
 }
 
@@ -215,28 +206,24 @@ extern "C" {
 PFAC_status_t PFACX_editRun(PFAC_handle_t handle, const PFACX_editRun_t *run, size_t *h_total)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!run || !h_total || !run->d_input || run->size == 0 || run->size > (size_t)0x7fffffff || run->numIds > (size_t)0x7ffffffe || !run->d_entryOff ||
-        !run->d_entries || run->numEntries > (size_t)0x7fffffff || run->blobWords > (size_t)0x7fffffff || !run->d_blob || run->maxPieceLen == 0 ||
-        run->maxBudget > 7u || run->count > (size_t)0x7fffffff || (run->count && (!run->d_pairIds || !run->d_pairPos)) ||
-        (run->capacity && (!run->d_ids || !run->d_pos)))
+    if (!run || !verifyRunOk(run->v, h_total) || !run->v.d_blob || !run->d_entryOff || !run->d_entries || run->numEntries > (size_t)0x7fffffff ||
+        run->maxPieceLen == 0 || run->maxBudget > 7u)
         return PFAC_STATUS_INVALID_PARAMETER;
     *h_total = 0;
-    if (run->count == 0) return PFAC_STATUS_SUCCESS;
+    if (run->v.count == 0) return PFAC_STATUS_SUCCESS;
     PFAC_context *c = handle;
     EditArgs a{};
-    a.in = reinterpret_cast<const unsigned char *>(run->d_input);
-    a.n = (unsigned int)run->size;
+    a.v = verifyInput(run->v);
     a.entryOff = run->d_entryOff;
     a.entries = static_cast<const pfac::EditEntry *>(run->d_entries);
     a.numEntries = (unsigned int)run->numEntries;
-    a.blob = run->d_blob;
-    a.blobWords = (unsigned int)run->blobWords;
+    a.blob = run->v.d_blob;
+    a.blobWords = (unsigned int)run->v.blobWords;
     a.maxPiece = (unsigned int)(run->maxPieceLen < (size_t)0xFFFF ? run->maxPieceLen : (size_t)0xFFFF);    /* no part is longer than a pattern */
     a.bestEnds = run->bestEnds ? 1u : 0u;
-    a.end = run->capacity ? run->d_end : nullptr;
-    a.dist = run->capacity ? run->d_dist : nullptr;
-    a.f = ExpandFrame{run->d_pairIds, run->d_pairPos, run->count, static_cast<const pfac::Int2 *>(run->d_table), (unsigned int)run->numIds,
-                      1u, 0, nullptr, run->d_ids, run->d_pos, run->capacity};
+    a.end = run->v.capacity ? run->d_end : nullptr;
+    a.dist = run->v.capacity ? run->d_dist : nullptr;
+    a.f = verifyFrame(run->v);
     const bool wantWrite = a.f.capacity != 0;
     /* the budget class of the launch: the band of the largest budget of the table */
     if (run->maxBudget <= 1u)

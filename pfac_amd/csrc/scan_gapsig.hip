@@ -1,6 +1,6 @@
 /*
  * scan_gapsig.hip -- signatures with bounded gaps between parts (include/pfac_ext.h: PFACX_gapsig*): a signature is a sequence of
- * PARTS, each a fixed-length string of (value, mask) bytes as in scan_sig.hip, with a gap of lo .. hi arbitrary bytes between part j and part
+ * PARTS, each a fixed-length string of (value, mask) bytes as a signature of scan_sig.hip is, with a gap of lo .. hi arbitrary bytes between part j and part
  * j + 1; the handle's patterns are the ANCHORS -- one fully specified run inside one part of each signature --, and of the signatures whose anchor
  * a scan found, the (signature, start) for which a choice of gap widths exists under which every part holds in the caller's input, each listed
  * once, with the smallest end over all such choices.
@@ -16,10 +16,11 @@
  *   pfac_array_scan      exclusive scan of the block totals (one block; 64-bit), the length of the list to mapped host memory
  *   pfac_gapsig_write    the block's pairs again (expandWrite): each thread runs the same search once more -- one function, so both passes
  *                        decide alike -- and hands (signature id, start) to the frame (ExpandEmit with a position); the end goes to end[slot]
- *                        in front of the frame's store, as the distance does in scan_approx.hip
+ *                        in front of the frame's store (scan_verify.h: emitWithAux)
  *   pfac_host_done       the call's sequence number to mapped host memory (scan_passes.h: HostHandoff)
  * The walk along the chain, both passes, the capacity-checked store and the launches are the expansion frame of scan_passes.h, shared with
- * scan_all.hip, scan_words.hip, scan_groups.hip, scan_case.hip, scan_sig.hip and scan_approx.hip; this unit's own is the search (searchSignature).
+ * scan_all.hip, scan_words.hip, scan_groups.hip and the other verify units; the class loop, the compare and the head of PFACX_gapsigRun are
+ * scan_verify.h's; this unit's own is the search (searchSignature).
  * THE SEARCH.  The slack of a signature, the sum of hi - lo over its gaps, is at most 63, so where a part can lie relative to its TIGHTEST offset
  * (every gap in between at lo) is a set of at most 64 distances: one 64-bit mask.  A step from a part to its neighbour smears the mask by the
  * gap's hi - lo (shift-and-OR doubling: smear) and keeps the bits at which the neighbour holds (holdsWhere: a compare per set bit; a bit whose
@@ -32,8 +33,8 @@
  *      the pair there owns (id, s) --: nothing.  Else (id, s) is this pair's, and its end is the lowest bit of `all`: every embedding at s has part
  *      a at an offset of A, none below x completes, so `all` holds every end there is
  * Every loop is bounded by the tables' own limits: at most 64 parts, at most 64 bits, at most 64 starts.
- * THE COMPARE of a part is the bounds-safe masked dword compare of scan_sig.hip (a copy: that unit stays as it is): the input side composed with
- * v_alignbyte, edge dwords assembled from the bytes inside the buffer, the len & 3 bytes behind the last whole dword byte by byte.
+ * THE COMPARE of a part is the bounds-safe masked dword compare that scan_sig.hip uses (scan_verify.h: maskedEqual): the input side composed
+ * with v_alignbyte, edge dwords assembled from the bytes inside the buffer, the len & 3 bytes behind the last whole dword byte by byte.
  * Every index into the input is checked against [0, n) before the load; an id outside [1, F] is a pair that counts nothing, a walk ends after
  * chainLen steps whatever the table says, class and part ranges are clamped to their tables, a part whose dwords do not lie inside the blob
  * holds nowhere: a caller's list cannot make a pass read or write outside the buffers.  A thread per pair: DESIGN.md 5x says what that costs.
@@ -49,6 +50,7 @@
 
 #include "pfac_context.h"
 #include "scan_passes.h"
+#include "scan_verify.h"
 
 namespace {
 
@@ -58,8 +60,7 @@ constexpr unsigned int kGapSigMaxSlack = 63;      /* pfac_ext.h: PFACX_GAPSIG_MA
 
 struct GapSigArgs {
     ExpandFrame f;                      /* the pairs, the chain table, the block cut, the caller's arrays (scan_passes.h); f.all is not read */
-    const unsigned char *in;            /* the caller's bytes */
-    unsigned int n;
+    InputView v;                        /* the caller's bytes (scan_verify.h) */
     const unsigned int *sigOff;         /* [numIds + 2] by anchor id: the first signature of its class */
     const pfac::GapSigEntry *sigs;      /* {signature id, first part, parts | anchor part << 16, anchorOff} */
     unsigned int numSigs;
@@ -69,53 +70,6 @@ struct GapSigArgs {
     unsigned int blobWords;
     int *end;                           /* the ends, capacity entries, or null */
 };
-
-/* the aligned dword of the input whose first byte is in[o] (o: any sign; in + o is dword-aligned): one load where it lies inside [0, n), else its
- * bytes inside the buffer, zero for the others */
-__device__ __forceinline__ uint32_t alignedDword(const GapSigArgs &a, long long o)
-{
-    if (o >= 0 && o + 4 <= (long long)a.n) return *reinterpret_cast<const uint32_t *>(a.in + o);
-    uint32_t w = 0;
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-        const long long i = o + b;
-        if (i >= 0 && i < (long long)a.n) w |= (uint32_t)a.in[i] << (8 * b);
-    }
-    return w;
-}
-
-/* ((in[s + k] ^ value[k]) & mask[k]) == 0 for every k < len?  s + len <= n and the part's 2 ((len + 3) / 4) dwords at blob[off ...] lie inside
- * the blob (the caller has checked both) */
-__device__ __forceinline__ bool maskedEqual(const GapSigArgs &a, unsigned int s, unsigned int len, unsigned int off)
-{
-    const unsigned int words = len >> 2, r = (unsigned int)(reinterpret_cast<uintptr_t>(a.in + s) & 3u);
-    const uint32_t *val = a.blob + off, *mask = val + ((len + 3u) >> 2);
-    uint32_t diff = 0;
-    if (r == 0) {
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.in + s);       /* whole dwords inside [s, s + len) */
-        for (unsigned int k = 0; k < words; k++) {
-            diff |= (src[k] ^ val[k]) & mask[k];
-            if ((k & 3u) == 3u && diff != 0) return false;
-        }
-    } else {
-        const long long base = (long long)s - (long long)r;                     /* the aligned dword that holds in[s] */
-        uint32_t lo = words ? alignedDword(a, base) : 0u;
-        for (unsigned int k = 0; k < words; k++) {
-            const uint32_t hi = alignedDword(a, base + 4ll * (k + 1u));
-            diff |= (__builtin_amdgcn_alignbyte(hi, lo, r) ^ val[k]) & mask[k];
-            if ((k & 3u) == 3u && diff != 0) return false;
-            lo = hi;
-        }
-    }
-    if (diff != 0) return false;
-    const unsigned int tail = len & 3u;
-    if (tail) {
-        const uint32_t v = val[words], m = mask[words];
-        for (unsigned int b = 0; b < tail; b++)
-            if ((((uint32_t)a.in[s + 4u * words + b] ^ (v >> (8u * b))) & (m >> (8u * b)) & 0xFFu) != 0u) return false;
-    }
-    return true;
-}
 
 /* the OR of m << k for k = 0 .. w (w <= 63; bits pushed past bit 63 are gone): what a gap of width lo .. lo + w does to the distances of a part */
 __device__ __forceinline__ uint64_t smear(uint64_t m, unsigned int w)
@@ -136,14 +90,14 @@ __device__ __forceinline__ bool gapUsable(const pfac::GapSigPart &q) { return q.
 __device__ __forceinline__ uint64_t holdsWhere(const GapSigArgs &a, const pfac::GapSigPart &q, long long base, int dir, uint64_t m)
 {
     const unsigned int len = q.len, need = 2u * ((len + 3u) >> 2);
-    if (len == 0u || len > 0xFFFFu || q.blobOff >= a.blobWords || a.blobWords - q.blobOff < need) return 0ull;
+    if (len == 0u || len > 0xFFFFu || !inBlob(a.blobWords, q.blobOff, need)) return 0ull;
     uint64_t held = 0;
     while (m != 0ull) {                                   /* at most 64 rounds */
         const int t = __builtin_ctzll(m);
         m &= m - 1ull;
         const long long o = base + (long long)dir * t;
-        if (o < 0 || o + (long long)len > (long long)a.n) continue;
-        if (maskedEqual(a, (unsigned int)o, len, q.blobOff)) held |= 1ull << t;
+        if (o < 0 || o + (long long)len > (long long)a.v.n) continue;
+        if (maskedEqual(a.v, a.blob + q.blobOff, (unsigned int)o, len)) held |= 1ull << t;
     }
     return held;
 }
@@ -206,13 +160,10 @@ template <class Emit>
 __device__ __forceinline__ unsigned int walkPair(const GapSigArgs &a, size_t k, Emit emit)
 {
     const int id = a.f.pairIds[k], p = a.f.pairPos[k];
-    if (p < 0 || (unsigned int)p >= a.n) return 0u;
+    if (p < 0 || (unsigned int)p >= a.v.n) return 0u;
     unsigned int found = 0;
     forEachChainMember(a.f.table, a.f.numIds, id, [&](int q) {
-        const unsigned int first = a.sigOff[q];
-        unsigned int end = a.sigOff[q + 1];
-        if (end > a.numSigs) end = a.numSigs;
-        for (unsigned int v = first; v < end; v++) found += searchSignature(a, a.sigs[v], p, emit);
+        forEachClassEntry(a.sigOff, a.numSigs, q, [&](unsigned int v) { found += searchSignature(a, a.sigs[v], p, emit); });
         return true;
     });
     return found;
@@ -228,10 +179,7 @@ __global__ __launch_bounds__(kGapSigBlock) void pfac_gapsig_write(GapSigArgs a)
     expandWrite<kGapSigBlock>(
         a.f, [&](size_t k) -> unsigned long long { return walkPair(a, k, [](int, int, int) {}); },
         [&](size_t k, auto emit) {
-            (void)walkPair(a, k, [&](int id, int s, int end) {
-                if (a.end != nullptr && emit.o < emit.f.capacity) a.end[emit.o] = end;                /* the slot the frame's store takes next */
-                emit(id, s);
-            });
+            (void)walkPair(a, k, [&](int id, int s, int end) { emitWithAux(emit, id, s, a.end, end); });
         });
 }
 
@@ -242,27 +190,23 @@ extern "C" {
 PFAC_status_t PFACX_gapsigRun(PFAC_handle_t handle, const PFACX_gapsigRun_t *run, size_t *h_total)
 {
     if (!handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!run || !h_total || !run->d_input || run->size == 0 || run->size > (size_t)0x7fffffff || run->numIds > (size_t)0x7ffffffe || !run->d_sigOff ||
-        !run->d_sigs || run->numSigs > (size_t)0x7fffffff || !run->d_parts || run->numParts > (size_t)0x7fffffff ||
-        run->blobWords > (size_t)0x7fffffff || !run->d_blob || run->count > (size_t)0x7fffffff || (run->count && (!run->d_pairIds || !run->d_pairPos)) ||
-        (run->capacity && (!run->d_ids || !run->d_pos)))
+    if (!run || !verifyRunOk(run->v, h_total) || !run->v.d_blob || !run->d_sigOff || !run->d_sigs || run->numSigs > (size_t)0x7fffffff || !run->d_parts ||
+        run->numParts > (size_t)0x7fffffff)
         return PFAC_STATUS_INVALID_PARAMETER;
     *h_total = 0;
-    if (run->count == 0) return PFAC_STATUS_SUCCESS;
+    if (run->v.count == 0) return PFAC_STATUS_SUCCESS;
     PFAC_context *c = handle;
     GapSigArgs a{};
-    a.in = reinterpret_cast<const unsigned char *>(run->d_input);
-    a.n = (unsigned int)run->size;
+    a.v = verifyInput(run->v);
     a.sigOff = run->d_sigOff;
     a.sigs = static_cast<const pfac::GapSigEntry *>(run->d_sigs);
     a.numSigs = (unsigned int)run->numSigs;
     a.parts = static_cast<const pfac::GapSigPart *>(run->d_parts);
     a.numParts = (unsigned int)run->numParts;
-    a.blob = run->d_blob;
-    a.blobWords = (unsigned int)run->blobWords;
-    a.end = run->capacity ? run->d_end : nullptr;
-    a.f = ExpandFrame{run->d_pairIds, run->d_pairPos, run->count, static_cast<const pfac::Int2 *>(run->d_table), (unsigned int)run->numIds,
-                      1u, 0, nullptr, run->d_ids, run->d_pos, run->capacity};
+    a.blob = run->v.d_blob;
+    a.blobWords = (unsigned int)run->v.blobWords;
+    a.end = run->v.capacity ? run->d_end : nullptr;
+    a.f = verifyFrame(run->v);
     return expandPasses(c, c->scratch.gapsigSet, pfac::kHostGapSig, a, pfac_gapsig_count, pfac_gapsig_write, kGapSigBlock, a.f.capacity != 0, h_total);
 }
 

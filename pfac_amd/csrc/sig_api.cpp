@@ -13,18 +13,21 @@
  * where every masked byte does.  The device form runs the unchanged compacted-output path with its ordered pairs in handle scratch
  * (PFACX_allReduce) and the passes of scan_sig.hip (PFACX_sigRun) behind it; the pairs form runs those passes over a list of the caller's.  The
  * host form takes the longest pairs from hostLongestPairs into a temporary of its own and walks the chains here (sigOnHost).
+ * The open tail (the anchors loaded and the handle checked to hold them), the order of the checks, the scan, the pair temporaries and the
+ * generation re-check of the three forms are the frame of verify_calls.h; this file's own is the plan, the tables, the run's arguments
+ * (sigRunLocked) and the host loop.
  */
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "pfac_host.h"
+#include "verify_calls.h"
 
 struct PFACX_sig_s : pfac_internal::HandleObject {
     size_t numIds = 0;                        /* F of the anchor set it loaded */
@@ -40,6 +43,7 @@ struct PFACX_sig_s : pfac_internal::HandleObject {
     pfac::DeviceBuffer<pfac::SigEntry> d_sigs;
 
     template <class Self, class F> static void forEachDeviceBuffer(Self &self, F f) { f(self.d_sigOff); f(self.d_sigs); f(self.d_blob); }
+    PFAC_status_t uploadTables() { return pfac_internal::uploadAll(d_sigOff, sigOff, d_sigs, sigs, d_blob, blob); }
     ~PFACX_sig_s() override { forEachDeviceBuffer(*this, [](auto &b) { b.release(); }); }
     size_t deviceBytes() const override { size_t n = 0; forEachDeviceBuffer(*this, [&n](const auto &b) { n += b.bytes(); }); return n; }
 };
@@ -55,8 +59,7 @@ struct SigPlan {
     std::vector<unsigned char> values, masks;         /* all signatures back to back */
     std::vector<size_t> off;                          /* [S + 1] into both */
     std::vector<int> anchorId, anchorOff, anchorLen;  /* by signature id */
-    std::vector<std::string> anchors;                 /* by handle id - 1: the distinct anchors in order of first appearance */
-    std::string text;                                 /* one line per distinct anchor */
+    StringSet anchors;                                /* by handle id - 1: the distinct anchors, and the anchor set as the reader's text */
 };
 
 /* The anchor of one signature: the longest run of bytes with mask 0xFF and a value other than '\n' (the pattern reader splits lines there), the
@@ -98,7 +101,6 @@ PFAC_status_t planSignatures(const unsigned char *h_values, const unsigned char 
     if (blobWords > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;          /* the tables index the blob with ints */
     plan->values.resize(plan->off[S]);
     plan->masks.resize(plan->off[S]);
-    std::map<std::string, int> seen;
     for (size_t i = 1; i <= S; i++) {
         const size_t from = h_sigOff[i - 1], at = plan->off[i - 1], len = plan->off[i] - at;
         unsigned char *v = plan->values.data() + at, *m = plan->masks.data() + at;
@@ -108,14 +110,7 @@ PFAC_status_t planSignatures(const unsigned char *h_values, const unsigned char 
         }
         size_t aoff = 0, alen = 0;
         if (!chooseAnchor(v, m, len, cut, &aoff, &alen)) { *badSig = (int)i; return PFAC_STATUS_INVALID_PARAMETER; }
-        const std::string anchor(reinterpret_cast<const char *>(v) + aoff, alen);
-        const auto placed = seen.emplace(anchor, (int)plan->anchors.size() + 1);
-        if (placed.second) {
-            plan->anchors.push_back(anchor);
-            plan->text += anchor;
-            plan->text += '\n';
-        }
-        plan->anchorId[i] = placed.first->second;
+        plan->anchorId[i] = plan->anchors.idOf(std::string(reinterpret_cast<const char *>(v) + aoff, alen));
         plan->anchorOff[i] = (int)aoff;
         plan->anchorLen[i] = (int)alen;
     }
@@ -183,52 +178,16 @@ bool parseText(const char *text, size_t size, std::vector<unsigned char> &values
     return true;
 }
 
-/* what the three match calls check first (the generation and the pattern set: under the lock) */
-PFAC_status_t checkSigArgs(PFACX_sig_t sg, const void *input, size_t size, const size_t *h_num_matched)
-{
-    if (!sg || !sg->handle) return PFAC_STATUS_INVALID_HANDLE;
-    if (!input || !h_num_matched || size > kMaxInt) return PFAC_STATUS_INVALID_PARAMETER;
-    return PFAC_STATUS_SUCCESS;
-}
-
-/* the first device call of a signature object: its tables (the caller holds the handle's lock) */
-PFAC_status_t ensureDeviceTables(PFACX_sig_s *sg)
-{
-    if (sg->d_sigOff) return PFAC_STATUS_SUCCESS;
-    const PFAC_status_t st = uploadAll(sg->d_sigOff, sg->sigOff, sg->d_sigs, sg->sigs, sg->d_blob, sg->blob);
-    if (st != PFAC_STATUS_SUCCESS) PFACX_sig_s::forEachDeviceBuffer(*sg, [](auto &b) { b.release(); });
-    return st;
-}
-
 /* the passes over `count` ordered longest pairs, behind the argument checks; the caller holds c->lock */
-PFAC_status_t sigRunLocked(PFACX_sig_s *sg, const char *d_input, size_t size, const int *d_pairIds, const int *d_pairPos, size_t count, int *d_ids,
-                           int *d_pos, size_t capacity, size_t *h_num_matched)
+PFAC_status_t sigRunLocked(PFACX_sig_s *sg, const VerifyCall &call, const int *d_pairIds, const int *d_pairPos, size_t count)
 {
-    PFAC_context *c = sg->handle;
-    PFAC_status_t st = c->fa.maxChain > 1 ? ensureAllTable(c) : PFAC_STATUS_SUCCESS;
-    if (st == PFAC_STATUS_SUCCESS) st = ensureDeviceTables(sg);
-    if (st != PFAC_STATUS_SUCCESS) return st;
     PFACX_sigRun_t run{};
-    run.d_input = d_input;
-    run.size = size;
-    run.d_pairIds = d_pairIds;
-    run.d_pairPos = d_pairPos;
-    run.count = count;
-    run.d_table = c->fa.maxChain > 1 ? c->scratch.allTable.get() : nullptr;
-    run.numIds = sg->numIds;
+    const PFAC_status_t st = fillRunFrame(sg, call, d_pairIds, d_pairPos, count, &run.v);
+    if (st != PFAC_STATUS_SUCCESS) return st;
     run.d_sigOff = sg->d_sigOff.get();
     run.d_sigs = sg->d_sigs.get();
     run.numSigs = sg->sigs.size();
-    run.d_blob = sg->d_blob.get();
-    run.blobWords = sg->blob.size();
-    run.d_ids = d_ids;
-    run.d_pos = d_pos;
-    run.capacity = capacity;
-    size_t total = 0;
-    st = c->sig_run_ptr(c, &run, &total);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    *h_num_matched = total;
-    return truncatedIf(total, capacity);
+    return finishRun(sg->handle, sg->handle->sig_run_ptr, run, call);
 }
 
 /* The host loop: the signatures that hold along the chains of `count` ordered longest pairs into ids / pos (slots >= capacity are not written);
@@ -279,19 +238,7 @@ PFAC_status_t PFACX_sigOpen(PFAC_handle_t handle, const unsigned char *h_values,
         if (badSig) *badSig = bad;
         if (st != PFAC_STATUS_SUCCESS) return st;                             /* nothing of the handle has changed */
     } catch (const std::bad_alloc &) { return PFAC_STATUS_ALLOC_FAILED; }
-    /* the anchors through the reader of every pattern set: the set is replaced, the handle case-sensitive */
-    PFAC_status_t st = PFACX_readPatternFromMemory(handle, plan.text.data(), plan.text.size());
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    return adoptNew(handle, sig, [&](PFACX_sig_s &obj) -> PFAC_status_t {
-        /* another thread may have replaced the set since: the tables hold only over the anchors, id by id */
-        const pfac::Automaton &fa = handle->fa;
-        if (handle->caseInsensitive || (size_t)fa.numPatterns != plan.anchors.size()) return PFAC_STATUS_INVALID_PARAMETER;
-        for (size_t q = 1; q <= plan.anchors.size(); q++) {
-            const std::string &anchor = plan.anchors[q - 1];
-            if ((size_t)fa.patternLen[q] != anchor.size() || fa.chainLen[q] < 1 ||
-                std::memcmp(fa.file.data() + fa.patternOff[q], anchor.data(), anchor.size()) != 0)
-                return PFAC_STATUS_INVALID_PARAMETER;
-        }
+    return adoptOverStrings(handle, plan.anchors, sig, [&](PFACX_sig_s &obj) -> PFAC_status_t {       /* (verify_calls.h: the tables hold only over the anchors) */
         buildTables(plan, &obj);
         return PFAC_STATUS_SUCCESS;
     });
@@ -335,73 +282,24 @@ PFAC_status_t PFACX_sigGetAnchors(PFACX_sig_t sig, int *h_anchorId, int *h_ancho
 
 PFAC_status_t PFACX_sigMatchFromDevice(PFACX_sig_t sig, char *d_input, size_t size, int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched)
 {
-    PFAC_status_t st = checkSigArgs(sig, d_input, size, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (!d_ids || !d_pos) return PFAC_STATUS_INVALID_PARAMETER;
-    PFAC_context *c = sig->handle;
-    if (size && capacity < size) return PFAC_STATUS_INVALID_PARAMETER;
-    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    std::lock_guard<std::mutex> guard(c->lock);
-    st = checkSetGeneration(c, sig->generation);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    DeviceScan scan;
-    st = beginDeviceScan(c, d_input, size, &scan);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    /* the caller's arrays take the scan's unordered list, the ordered pairs go to the handle's pair scratch: the passes never filter in place */
-    int count = 0;
-    st = c->all_reduce_ptr(c, reinterpret_cast<int *>(scan.d_scan), (int)size, d_ids, d_pos, &count, scan.hashed);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (count < 0 || (size_t)count > size) return PFAC_STATUS_INTERNAL_ERROR;
-    const int *pairIds = c->scratch.allPairs.get();
-    const int *pairPos = pairIds + c->scratch.allPairs.count() / 2;        /* one allocation: the ids, then as many positions */
-    if (count == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    return sigRunLocked(sig, d_input, size, pairIds, pairPos, (size_t)count, d_ids, d_pos, capacity, h_num_matched);
+    const VerifyCall call{d_input, size, d_ids, d_pos, capacity, h_num_matched};
+    return verifyFromDevice(sig, call, [&](const int *ids, const int *pos, size_t count) { return sigRunLocked(sig, call, ids, pos, count); });
 }
 
 PFAC_status_t PFACX_sigMatchFromHost(PFACX_sig_t sig, char *h_input, size_t size, int *h_ids, int *h_pos, size_t capacity, size_t *h_num_matched)
 {
-    PFAC_status_t st = checkSigArgs(sig, h_input, size, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (capacity && (!h_ids || !h_pos)) return PFAC_STATUS_INVALID_PARAMETER;
-    PFAC_context *c = sig->handle;
-    {
-        std::lock_guard<std::mutex> guard(c->lock);
-        st = checkSetGeneration(c, sig->generation);
-        if (st != PFAC_STATUS_SUCCESS) return st;
-    }
-    if (size == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    if (hostLacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    const HostPairs pairs(size, size);
-    if (!pairs) return PFAC_STATUS_ALLOC_FAILED;
-    const PinnedPairs scan(c, h_input, size, pairs.ids, pairs.pos);
-    if (scan.status != PFAC_STATUS_SUCCESS) return scan.status;
-    if (scan.generation != sig->generation) return PFAC_STATUS_INVALID_PARAMETER;    /* another thread has replaced the set meanwhile: as after the call */
-    const size_t total = sigOnHost(c->fa, *sig, reinterpret_cast<const unsigned char *>(h_input), size, pairs.ids, pairs.pos,
-                                   (size_t)(scan.count > 0 ? scan.count : 0), h_ids, h_pos, capacity);
-    *h_num_matched = total;
-    return truncatedIf(total, capacity);
+    const VerifyCall call{h_input, size, h_ids, h_pos, capacity, h_num_matched};
+    return verifyFromHost(sig, call, [&](const int *ids, const int *pos, size_t count) {
+        return sigOnHost(sig->handle->fa, *sig, reinterpret_cast<const unsigned char *>(h_input), size, ids, pos, count, h_ids, h_pos, capacity);
+    });
 }
 
 PFAC_status_t PFACX_sigPairsFromDevice(PFACX_sig_t sig, const char *d_input, size_t size, const int *d_pairIds, const int *d_pairPos, size_t numPairs,
                                        int *d_ids, int *d_pos, size_t capacity, size_t *h_num_matched)
 {
-    PFAC_status_t st = checkSigArgs(sig, d_input, size, h_num_matched);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (numPairs > kMaxInt || capacity > SIZE_MAX / sizeof(int) || (numPairs && (!d_pairIds || !d_pairPos)) || (capacity && (!d_ids || !d_pos)))
-        return PFAC_STATUS_INVALID_PARAMETER;
-    if (capacity && numPairs) {
-        const size_t in = numPairs * sizeof(int), out = capacity * sizeof(int);
-        if (overlap(d_ids, out, d_pairIds, in) || overlap(d_ids, out, d_pairPos, in) || overlap(d_pos, out, d_pairIds, in) || overlap(d_pos, out, d_pairPos, in))
-            return PFAC_STATUS_INVALID_PARAMETER;
-    }
-    PFAC_context *c = sig->handle;
-    if (lacksModule(c)) return PFAC_STATUS_LIB_NOT_EXIST;
-    std::lock_guard<std::mutex> guard(c->lock);
-    st = checkSetGeneration(c, sig->generation);
-    if (st != PFAC_STATUS_SUCCESS) return st;
-    if (size == 0 || numPairs == 0) { *h_num_matched = 0; return PFAC_STATUS_SUCCESS; }
-    return sigRunLocked(sig, d_input, size, d_pairIds, d_pairPos, numPairs, d_ids, d_pos, capacity, h_num_matched);
+    const VerifyCall call{d_input, size, d_ids, d_pos, capacity, h_num_matched};
+    return verifyPairsFromDevice(sig, call, d_pairIds, d_pairPos, numPairs, {d_ids, d_pos},
+                                 [&](const int *ids, const int *pos, size_t count) { return sigRunLocked(sig, call, ids, pos, count); });
 }
 
 } /* extern "C" */
